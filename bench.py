@@ -5,6 +5,11 @@ One "step" = one full Diffusion.denoise_guided call (T=255 reverse steps, 125 of
 B=1024 synthetic trajectories per GPU + the end-of-sampling best-trajectory selection (and, for N>1, the RCCL gather).
 value = trajectories x denoise-steps / second over all ranks.  Inputs (weights, scene tables, the (T+1,B,7,50) f64
 noise stream) are resident in HBM before the timed region.  Prints ONE JSON line on rank 0.
+
+A plain run sets up, warms up, times --steps calls and prints the line (headline keys + what the timed call returned).
+--full adds the informative measurements: the all-fp32-MFMA A/B leg, success-kernel cost, end-to-end scene times, two
+scenes in flight, the problem set, the roofline passes and the CPU baseline.  --dump-outputs DIR writes what the last
+timed call returned (rank 0) as .npy files, for output-for-output comparison of two builds on the same seeded inputs.
 """
 from __future__ import annotations
 
@@ -84,7 +89,14 @@ def main():
     ap.add_argument("--no-two-scenes", action="store_true", help="skip the informative two-scenes-in-flight measurement")
     ap.add_argument("--no-native-leg", action="store_true", help="skip the A/B leg with every conv on the fp32-MFMA kernels (value_native_f32)")
     ap.add_argument("--no-problem-set", action="store_true", help="skip the informative problem-set measurement (16 distinct scenes through infer_serial.run)")
+    ap.add_argument("--full", action="store_true",
+                    help="also run the informative measurements after the timed steps (native-fp32 leg, success-kernel cost, end-to-end scene times, two scenes in "
+                         "flight, problem set, roofline, CPU baseline); the --no-* switches above select among them")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="write what the last timed call returned on rank 0 (trajectories, swept volumes, per-row success flags, best row) to DIR/<name>.npy")
     args = ap.parse_args()
+    if args.steps < 1 or args.warmup < 0:
+        raise SystemExit(f"--steps {args.steps} --warmup {args.warmup}: need steps >= 1 and warmup >= 0")
 
     backend = os.environ.get("EDMP_DIST_BACKEND", "nccl")  # "gloo" lets N ranks share one GPU (single-GPU test boxes)
     ngpu = torch.cuda.device_count()
@@ -95,16 +107,27 @@ def main():
         raise SystemExit(f"--gpus {args.gpus} but only {ngpu} GPU(s) visible (EDMP_DIST_BACKEND=gloo lets ranks share a GPU: test boxes only)")
     if args.gpus > 1 and "WORLD_SIZE" not in os.environ:
         # started as plain `python bench.py --gpus N` (the reference's launch model is one process per device,
-        # benchmark/cfgs/cfg2.yaml:2,14): re-exec under the launcher the contract names instead of falling through to one rank
+        # benchmark/cfgs/cfg2.yaml:2,14): run under the launcher the contract names instead of falling through to one rank.
+        # A child process, not exec: this process has already initialised the GPU runtime (device_count above).
+        import signal
         import socket
+        import subprocess
 
         with socket.socket() as sk:
             sk.bind(("127.0.0.1", 0))
             port = sk.getsockname()[1]
         cmd = [sys.executable, "-m", "torch.distributed.run", "--nnodes=1", f"--nproc-per-node={args.gpus}", "--master-addr", "127.0.0.1", "--master-port", str(port),
                os.path.abspath(__file__), *sys.argv[1:]]
-        print(f"[bench] --gpus {args.gpus} without a launcher: re-exec as {' '.join(cmd[1:9])} ...", file=sys.stderr, flush=True)
-        os.execv(sys.executable, cmd)
+        print(f"[bench] --gpus {args.gpus} without a launcher: running {' '.join(cmd[1:9])} ...", file=sys.stderr, flush=True)
+        proc = subprocess.Popen(cmd)
+        # a caller that signals only this process still stops the launcher (which stops its ranks)
+        for s in (signal.SIGTERM, signal.SIGINT, signal.SIGHUP):
+            signal.signal(s, lambda signum, _frame: proc.send_signal(signum))
+        rc = proc.wait()
+        if rc < 0:  # the launcher died of a signal: die of the same one, so the caller sees 128 + N as if it had run in this process
+            signal.signal(-rc, signal.SIG_DFL)
+            os.kill(os.getpid(), -rc)
+        raise SystemExit(rc)
     world = int(os.environ.get("WORLD_SIZE", "1"))
     rank = int(os.environ.get("RANK", "0"))
     local_rank = int(os.environ.get("LOCAL_RANK", "0"))
@@ -170,11 +193,11 @@ def main():
         vols, idx = guide.row_swept_volumes(start, goal, X)  # synchronises (argmin comes back to the host)
         # plan success of EVERY row (exact link-box vs obstacle check, csrc/success.hip): the second half of the metric
         sr = guide.success_rows(X)
-        last["X"] = X
         traj = X[idx].cpu().numpy()
         res = ED.gather_best(float(vols[idx]), idx, traj, bool(sr["ok"][idx]), device=dev, rows_ok=sr["rows_ok"], rows=sr["rows"],
                              collision_free=bool(sr["collision_free"][idx]), rows_collision_free=sr["rows_collision_free"])
         res["aabb_volume_zero"] = ED.geometric_success(float(vols[idx]), traj)  # the guide's own (conservative) criterion, rank-local
+        last.update(X=X, vols=vols, sr=sr, res=res)
         return res
 
     def barrier():
@@ -204,12 +227,31 @@ def main():
             raise SystemExit(f"--gpus {args.gpus} but the process group summed {n_ranks_seen} ranks")
     value = world * B * T * args.steps / dt
 
+    if args.dump_outputs and rank == 0:
+        # the last timed call's results as a caller receives them; with --gpus > 1 the per-row arrays are rank 0's rows
+        os.makedirs(args.dump_outputs, exist_ok=True)
+        sr, res = last["sr"], last["res"]
+        # at most 64 MB in all: above that, a fixed seeded sample of rows (listed in sample_rows.npy) stands for the batch
+        row_bytes = C * N * 8 + 4 + 4 * 8
+        rows = np.arange(B)
+        if B * row_bytes > 64_000_000 - 65_536:
+            rows = np.sort(np.random.RandomState(0).choice(B, (64_000_000 - 65_536) // (row_bytes + 8), replace=False))
+        dumps = {"trajectories": last["X"][torch.as_tensor(rows, device=last["X"].device)].cpu().numpy().astype(np.float64),  # (rows, 7, 50)
+                 "swept_volumes": np.asarray(last["vols"], dtype=np.float32)[rows],  # (rows,)
+                 "row_flags": np.stack([sr["ok"], sr["collision_free"], sr["within"], sr["first"]], axis=1).astype(np.float64)[rows],  # (rows, 4): ok, collision-free, within limits, first colliding configuration
+                 "best_trajectory": np.asarray(res["traj"], dtype=np.float64),  # (7, 50)
+                 "best": np.array([res["rank"], res["index"], res["volume"], res["success"], res["collision_free"]], dtype=np.float64)}
+        if rows.size < B:
+            dumps["sample_rows"] = rows.astype(np.float64)
+        for name, arr in dumps.items():
+            np.save(os.path.join(args.dump_outputs, name + ".npy"), arr)
+
     # ---- A/B leg (round 6): the same workload with EVERY conv on the fp32-MFMA kernels (EDMP_BF16X3=0 at model-build time) --------
     # `value` is the default product path: 26 of the 40 conv launches of a reverse step form each fp32 product as six exact bf16
     # partial products on the bf16 matrix pipe, fp32 accumulation (csrc/bf3.hip) - measured at HALF the fp32-MFMA kernels' error
     # against float64 (profiles/r06_bf16x3.md, tests: test_bf16x3_split_layers_are_at_least_as_accurate_as_the_fp32_mfma_layers).  The native leg keeps the two numbers side by side.
     native = None
-    if not args.no_native_leg:
+    if args.full and not args.no_native_leg:
         env_prev = os.environ.get("EDMP_BF16X3")
         os.environ["EDMP_BF16X3"] = "0"
         try:
@@ -294,7 +336,7 @@ def main():
     # ---- cost of the success kernel: on the batch just produced (random-init rows collide early and leave the obstacle loop at the
     # first hit: the EASY case) and on a collision-free in-limit batch against the scene moved 10 m away (every configuration x link
     # box x obstacle tested: the WORST case, what trained weights should produce) ------------------------------------------------
-    if world == 1 and rank == 0:
+    if args.full and world == 1 and rank == 0:
         from edmp_amd import franka
 
         def timed_check(g_, X_):
@@ -329,7 +371,7 @@ def main():
         del gfar, Xfree
 
     # ---- informative: whole-scene wall time when the noise is NOT pre-resident (never `value`) -------------------------
-    if world == 1 and rank == 0 and not logical:
+    if args.full and world == 1 and rank == 0 and not logical:
         def scene_time(**kw):
             t1 = time.perf_counter()
             X = dif.denoise_guided(net, guide, N, C, cfgs["guidance_schedule"], batch_size=B, start=start, goal=goal, return_device=True, **kw)
@@ -358,7 +400,7 @@ def main():
     # Every launch of the loop is one wave of 256 workgroups, so one chain leaves the chip idle in each dispatch gap and
     # under-filled in each kernel tail; a second, independent scene on its own context / stream / host thread fills the holes.
     # Throughput mode for a driver that has many scenes to plan (the reference's scene loop, infer_serial.py:95-170, is serial).
-    if world == 1 and rank == 0 and not logical and not args.no_two_scenes:
+    if args.full and world == 1 and rank == 0 and not logical and not args.no_two_scenes:
         import threading
 
         from edmp_amd.runtime import lane_context
@@ -403,7 +445,7 @@ def main():
     # The reference's per-scene clock (infer_serial.py:108-157) covers guide construction + IK-goal filter + sampling + best pick;
     # the timed loop above builds the guide once.  infer_serial.run over 16 distinct synthetic scenes of this workload's size
     # (true cylinders included, noise drawn per scene from NumPy's global RandomState), serial and with two scenes in flight.
-    if world == 1 and rank == 0 and not logical and not args.no_problem_set:
+    if args.full and world == 1 and rank == 0 and not logical and not args.no_problem_set:
         sys.path.insert(0, os.path.join(ROOT, "scripts"))
         import problem_set_bench
 
@@ -422,7 +464,7 @@ def main():
     #          per-launch overhead (sum of pass B - pass A, divided by the launches) is subtracted from every bracket.
     # FLOPs are the EXECUTED ones (taps that fall into the zero padding are never issued); the nominal SURVEY 8(d)
     # figure is reported next to it.
-    if world == 1 and rank == 0 and not args.no_roofline:
+    if args.full and world == 1 and rank == 0 and not args.no_roofline:
         ctx.prof(2)
         ctx.prof_read(reset=True)
         torch.cuda.synchronize()
@@ -510,7 +552,7 @@ def main():
         }
 
     # ---- CPU baseline: the oracle (port of the reference) on this box's host cores, bounded sample -----------------
-    if world == 1 and rank == 0 and not args.no_cpu_baseline:
+    if args.full and world == 1 and rank == 0 and not args.no_cpu_baseline:
         from edmp_amd import weights as W
         from oracle import edmp_oracle as O
 

@@ -12,6 +12,7 @@ Fixtures are data only (arrays, a torch state-dict file); no reference source te
 """
 from __future__ import annotations
 
+import copy
 import os
 import shutil
 import sys
@@ -98,11 +99,12 @@ def main():
     net.train(False)
     with torch.no_grad():
         y = net(x, t).numpy()
+        y64 = copy.deepcopy(net).double()(x.double(), t.double()).numpy()  # float32 sums depend on the host's order; float64 ones do not
     dst = os.path.join(OUT, "g14_ref_checkpoint")
     shutil.rmtree(dst, ignore_errors=True)
     os.makedirs(dst)
     shutil.copy(os.path.join(name, "weights_latest.pt"), os.path.join(dst, "weights_latest.pt"))
-    np.savez_compressed(os.path.join(dst, "forward.npz"), x=x.numpy(), t=t.numpy(), y=y, dims=np.array(TINY_DIMS))
+    np.savez_compressed(os.path.join(dst, "forward.npz"), x=x.numpy(), t=t.numpy(), y=y, dims=np.array(TINY_DIMS), y64=y64)
     print(f"  wrote g14_ref_checkpoint/ ({os.path.getsize(os.path.join(dst, 'weights_latest.pt')) / 1024:.0f} KiB state dict written by the reference)")
     shutil.rmtree(tmp, ignore_errors=True)
 
