@@ -49,7 +49,7 @@ SIGNATURES = {
     "edmp_unet_param_count": (C.c_int64, [C.POINTER(UNetDesc)]),
     "edmp_unet_load": (_i, [_vp, C.POINTER(UNetDesc), _pf, C.c_int64, _i]),
     "edmp_unet_forward_dev": (_i, [_vp, _vp, _i, _i, _vp]),
-    "edmp_unet_read_activation_dev": (_i, [_vp, _i, _i, _vp, C.POINTER(_i), C.POINTER(_i)]),
+    "edmp_unet_read_activation_dev": (_i, [_vp, _i, _i, _vp, C.c_int64, C.POINTER(_i), C.POINTER(_i)]),
     "edmp_unet_flops": (_i, [_vp, _pd, _pd]),
     "edmp_scene_set": (_i, [_vp, _pd, _i, _pd, _pd, _i, _i, _pf, _pf, _pf]),
     "edmp_rows_set": (_i, [_vp, _pi32, _pf, _pd, _pd, _i, _i]),

@@ -1382,6 +1382,10 @@ struct LayerPlan {
         o_tw = pk.vec(tw_all.data(), (int)tw_all.size()), o_tb = pk.vec(tb_all.data(), (int)tb_all.size());
         head_buf = x.buf;
         for (auto& o : pops) EDMP_REQUIRE(!((o.kind == OP_GN || o.kind == OP_RCB) && o.res == -2), "identity residual over a channel concat is not supported");
+        // the generic GroupNorm keeps a group in registers (gn_mish_kernel, at most 8 x 64 elements): refuse the architecture
+        // here, at load, rather than in the middle of its first forward (launch_gn keeps the same check)
+        for (auto& o : pops)
+            EDMP_REQUIRE(!(o.kind == OP_GN && (o.C / 8) * o.L > 512), "GroupNorm group of %d elements exceeds the register-resident limit (512)", (o.C / 8) * o.L);
         return EDMP_OK;
     }
 };
@@ -1794,15 +1798,20 @@ extern "C" int edmp_unet_forward_dev(edmp_ctx* ctx, const float* x_dev, int B, i
     return unet_forward_impl(ctx, x_dev, B, t, eps_dev);
 }
 
-extern "C" int edmp_unet_read_activation_dev(edmp_ctx* ctx, int which, int B, float* out_dev, int* C_out, int* L_out) {
-    EDMP_REQUIRE(ctx && ctx->unet && out_dev, "edmp_unet_read_activation_dev: null argument / no model");
+extern "C" int edmp_unet_read_activation_dev(edmp_ctx* ctx, int which, int B, float* out_dev, int64_t capacity, int* C_out, int* L_out) {
+    EDMP_REQUIRE(ctx && ctx->unet, "edmp_unet_read_activation_dev: no model");
     for (auto& t : ctx->unet->taps)
         if (t.which == which) {
-            int total = B * t.C * t.L;
-            hipLaunchKernelGGL(unpack_kernel, dim3((total + 255) / 256), dim3(256), 0, ctx->stream, t.p, out_dev, B, t.L, t.C);
-            EDMP_HIP_CHECK(hipGetLastError());
             if (C_out) *C_out = t.C;
             if (L_out) *L_out = t.L;
+            if (!out_dev && capacity == 0) return EDMP_OK;  // shape query
+            EDMP_REQUIRE(out_dev, "edmp_unet_read_activation_dev: null output");
+            EDMP_REQUIRE(B >= 1 && B <= ctx->unet->max_batch, "batch %d outside 1..max_batch=%d", B, ctx->unet->max_batch);
+            const int64_t total = (int64_t)B * t.C * t.L;
+            EDMP_REQUIRE(capacity >= total, "buffer of %lld floats, activation tap %d holds %lld (B=%d, C=%d, L=%d)", (long long)capacity, which,
+                         (long long)total, B, t.C, t.L);
+            hipLaunchKernelGGL(unpack_kernel, dim3((unsigned)((total + 255) / 256)), dim3(256), 0, ctx->stream, t.p, out_dev, B, t.L, t.C);
+            EDMP_HIP_CHECK(hipGetLastError());
             return EDMP_OK;
         }
     set_error("no activation tap %d", which);

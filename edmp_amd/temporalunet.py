@@ -148,11 +148,12 @@ class TemporalUNet:
         """(B, C, L) f32 copy of an internal activation of THIS model's last forward (parity/debug)."""
         ctx = self.ctx
         self._bind()  # (every resident model keeps its own activation buffers)
-        buf = ctx.empty((B * 4096,), torch.float32)
         c, l = C.c_int(), C.c_int()
-        _capi.check(ctx.lib.edmp_unet_read_activation_dev(ctx.h, which, B, ptr(buf), C.byref(c), C.byref(l)))
+        _capi.check(ctx.lib.edmp_unet_read_activation_dev(ctx.h, which, B, None, 0, C.byref(c), C.byref(l)), "edmp_unet_read_activation_dev")
+        buf = ctx.empty((max(int(B), 1), c.value, l.value), torch.float32)  # (the library refuses a B outside 1..max_batch)
+        _capi.check(ctx.lib.edmp_unet_read_activation_dev(ctx.h, which, B, ptr(buf), buf.numel(), C.byref(c), C.byref(l)), "edmp_unet_read_activation_dev")
         ctx.sync()
-        return buf[: B * c.value * l.value].reshape(B, c.value, l.value)
+        return buf
 
     def flops_per_trajectory(self):
         self._bind()

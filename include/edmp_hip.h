@@ -73,9 +73,11 @@ int edmp_unet_load_packed(edmp_ctx* ctx, const edmp_unet_desc* desc, const float
                           int max_batch);
 /* replaces TemporalUNet.forward (temporalunet.py:47-76): x (B,C,N) f32, integer t in [1,T] -> eps (B,C,N) f32 */
 int edmp_unet_forward_dev(edmp_ctx* ctx, const float* x_dev, int B, int t, float* eps_dev);
-/* debug/parity: copy an internal activation, converted to the reference layout (B, C, L) f32.
- * which: 0..n_levels-1 = output of down level i, 100 = middle block, 200+i = output of up level i */
-int edmp_unet_read_activation_dev(edmp_ctx* ctx, int which, int B, float* out_dev, int* C_out, int* L_out);
+/* debug/parity: copy an internal activation of the last forward, converted to the reference layout (B, C, L) f32, into
+ * out_dev (room for `capacity` floats).  which: 0..n_levels-1 = output of down level i, 100 = middle block, 200+i = output
+ * of up level i.  B must lie in 1..max_batch and B*C*L must fit, else nothing is launched.  out_dev == NULL with
+ * capacity == 0 only reports the tap's C and L (size the buffer first) */
+int edmp_unet_read_activation_dev(edmp_ctx* ctx, int which, int B, float* out_dev, int64_t capacity, int* C_out, int* L_out);
 /* algorithmic FLOPs of one forward per trajectory: (a) nominal = every conv tap counted, the reference's own
  * arithmetic (SURVEY.md §8d, 187 339 904 for the full net); (b) executed = taps that fall in the zero padding are
  * skipped by the kernels */
