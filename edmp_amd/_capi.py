@@ -94,6 +94,8 @@ SIGNATURES = {
     "edmp_prof_enable": (_i, [_vp, _i]),
     "edmp_prof_read": (_i, [_vp, _pd, C.POINTER(C.c_int64), _i]),
     "edmp_prof_ops": (_i, [_vp, _i, C.POINTER(C.c_int), _pd, C.POINTER(C.c_int64), _pd, C.c_char_p]),
+    "edmp_unet_op_attrs": (_i, [_vp, _i, C.POINTER(C.c_int), C.c_char_p, _pi32, _pi32, _pi32, _pi32]),
+    "edmp_cu_claim": (_i, [_i, _i, _i, _i]),
 }
 
 _lib = None

@@ -34,6 +34,10 @@
 
 namespace edmp {
 
+// Threads per workgroup: eight waves, two per SIMD.  The kernel's __launch_bounds__, its launch (launch_bf3_t) and its tiling
+// (Bf3Cfg::NTH) all take it from here; the CU claim below (bf3_conv_kernel) depends on it: 2 waves x 256 VGPRs = a SIMD's file.
+constexpr int kBf3Threads = 512;
+
 typedef __attribute__((ext_vector_type(8))) __bf16 bf16x8_t;
 typedef __attribute__((ext_vector_type(2))) __bf16 bf16x2_t;
 typedef __attribute__((ext_vector_type(4))) float f32x4_t;
@@ -57,7 +61,7 @@ inline void split3_bf16_rne(float x, unsigned short (&c)[3]) {
 
 template <int KIND, int MS, int CG, int GS, int LIN, bool RES>
 struct Bf3Cfg {
-    static constexpr int NTH = 512, NMW = 4;  // threads; MFMA waves (waves 4..7 stage)
+    static constexpr int NTH = kBf3Threads, NMW = 4;  // threads; MFMA waves (waves 4..7 stage)
     static constexpr int LOUT = (KIND == WK_K5) ? LIN : (KIND == WK_DOWN) ? (LIN - 1) / 2 + 1 : ((2 * LIN == 8 || 2 * LIN == 14 || 2 * LIN == 26) ? 2 * LIN - 1 : 2 * LIN);
     static constexpr bool GN = (KIND == WK_K5);
     static constexpr int SW = 16, S = CG / SW, PARTS = NMW / S;  // CG = 32: two slabs x two parts; CG = 64: four slabs, one wave each
@@ -165,7 +169,7 @@ __device__ long long g_bf3_stamps[8][8];
 #endif
 
 template <int KIND, int MS, int CG, int GS, int LIN, bool RES>
-__global__ __launch_bounds__(512) void bf3_conv_kernel(const float* a_src1, const float* a_src2, const void* a_W, int a_C1, int a_C2, int a_Cout, int a_B,
+__global__ __launch_bounds__(kBf3Threads) void bf3_conv_kernel(const float* a_src1, const float* a_src2, const void* a_W, int a_C1, int a_C2, int a_Cout, int a_B,
                                                        int a_gx_shift, int a_ng_shift, RcbP p) {
     using Cf = Bf3Cfg<KIND, MS, CG, GS, LIN, RES>;
     constexpr int LOUT = Cf::LOUT, KC = Cf::KC, RS = Cf::RS, PLANE = Cf::PLANE, STAGE = Cf::STAGE, NSLOT = Cf::NSLOT, NTILE = Cf::NTILE, MAXT = Cf::MAXT;
@@ -528,15 +532,29 @@ inline void pack_fragments_bf3(const float* w_tco_ci, int cout, int cin, int nta
             }
 }
 
+// q != nullptr: launch nothing; fill q with what the runtime reports for this instance at its launch configuration (the CU-claim
+// check when a layer program is built, unet.hip: check_bf3_cu_claim)
 template <int KIND, int MS, int CG, int GS, int LIN, bool RES>
-int launch_bf3_t(const RcbP& p, hipStream_t s) {
+int launch_bf3_t(const RcbP& p, hipStream_t s, KernelAttrs* q) {
     using Cf = Bf3Cfg<KIND, MS, CG, GS, LIN, RES>;
     static std::atomic<int> attr_set{0};
     constexpr size_t bytes = Cf::lds_bytes();
     static_assert(bytes <= 160 * 1024, "bf16x3 position-tile kernel exceeds the 160 KiB LDS of a CU");
+    const void* fn = reinterpret_cast<const void*>(&bf3_conv_kernel<KIND, MS, CG, GS, LIN, RES>);
     if (!attr_set.load(std::memory_order_acquire)) {
-        EDMP_HIP_CHECK(hipFuncSetAttribute(reinterpret_cast<const void*>(&bf3_conv_kernel<KIND, MS, CG, GS, LIN, RES>), hipFuncAttributeMaxDynamicSharedMemorySize, (int)bytes));
+        EDMP_HIP_CHECK(hipFuncSetAttribute(fn, hipFuncAttributeMaxDynamicSharedMemorySize, (int)bytes));
         attr_set.store(1, std::memory_order_release);
+    }
+    if (q) {
+        hipFuncAttributes fa{};
+        EDMP_HIP_CHECK(hipFuncGetAttributes(&fa, fn));
+        int wg = 0;
+        EDMP_HIP_CHECK(hipOccupancyMaxActiveBlocksPerMultiprocessor(&wg, fn, kBf3Threads, bytes));
+        q->regs = fa.numRegs;
+        q->block = kBf3Threads;
+        q->lds = (int)bytes;
+        q->wg_per_cu = wg;
+        return EDMP_OK;
     }
     EDMP_REQUIRE(p.C1 % Cf::KC == 0 && p.C2 % Cf::KC == 0 && p.Cout % CG == 0, "bf3_conv_kernel: channels must be multiples of 32 (C1=%d, C2=%d, Cout=%d)", p.C1, p.C2, p.Cout);
     EDMP_REQUIRE(p.C2 == 0 || p.C2 == p.C1, "bf3_conv_kernel: the two halves of a concatenated input must have the same width (C1=%d, C2=%d)", p.C1, p.C2);
@@ -547,7 +565,7 @@ int launch_bf3_t(const RcbP& p, hipStream_t s) {
         gxs = __builtin_ctz(gx);
         ngs = __builtin_ctz(ng);
     }
-    hipLaunchKernelGGL((bf3_conv_kernel<KIND, MS, CG, GS, LIN, RES>), dim3(ng * nt), dim3(512), bytes, s, p.src1, p.src2, reinterpret_cast<const void*>(p.W), p.C1, p.C2, p.Cout, p.B, gxs, ngs, p);
+    hipLaunchKernelGGL((bf3_conv_kernel<KIND, MS, CG, GS, LIN, RES>), dim3(ng * nt), dim3(kBf3Threads), bytes, s, p.src1, p.src2, reinterpret_cast<const void*>(p.W), p.C1, p.C2, p.Cout, p.B, gxs, ngs, p);
     return EDMP_OK;
 }
 

@@ -48,6 +48,14 @@ struct RcbP {
     int gx_shift = -1, ng_shift = -1;  // wide_conv_kernel: log2 of the XCDs across the channel groups (wide.hip: xcd_split) and of the group count, set by the launcher; -1 = plain mapping
 };
 
+// what the runtime reports for a kernel instance at its launch configuration (bf3.hip: launch_bf3_t's query mode)
+struct KernelAttrs {
+    int regs = 0;       // VGPRs per lane, arch + acc (hipFuncAttributes::numRegs)
+    int block = 0;      // threads per workgroup
+    int lds = 0;        // dynamic LDS bytes per workgroup
+    int wg_per_cu = 0;  // hipOccupancyMaxActiveBlocksPerMultiprocessor at (block, lds)
+};
+
 // whole-level kernel (level.hip)
 enum LevelMode { LV_DOWN = 0, LV_UP = 1, LV_UP_FINAL = 2 };
 

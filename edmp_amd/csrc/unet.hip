@@ -140,6 +140,7 @@ struct Op {
     double flops_direct;               // per trajectory: the direct form with padding taps skipped (round-1 'executed' accounting)
     double flops_bf16;                 // per trajectory: MFMA work issued on the bf16 pipe (bf3.hip ops: 6 partial products x the direct form; else 0)
     char name[64];                     // kernel instance as rocprofv3 prints it (without the edmp:: prefix)
+    KernelAttrs attrs;                 // bf16x3 ops: what the runtime reports for the instance (check_bf3_cu_claim); else zeros
 };
 
 struct UNet {
@@ -393,7 +394,7 @@ namespace edmp {
 #define EDMP_X(sh, K, MS, CG, GS, L, R) extern template int launch_wide_t<K, MS, CG, GS, L, R>(const RcbP&, hipStream_t);
 EDMP_WIDE_INSTANCES(EDMP_X)
 #undef EDMP_X
-#define EDMP_X(sh, K, MS, CG, GS, L, R) extern template int launch_bf3_t<K, MS, CG, GS, L, R>(const RcbP&, hipStream_t);
+#define EDMP_X(sh, K, MS, CG, GS, L, R) extern template int launch_bf3_t<K, MS, CG, GS, L, R>(const RcbP&, hipStream_t, KernelAttrs*);
 EDMP_BF3_INSTANCES(EDMP_X)
 #undef EDMP_X
 #define EDMP_X(sh, M, C, L, SB, CIN) extern template int launch_level_t<M, C, L, SB, CIN>(const LevelP&, hipStream_t);
@@ -639,18 +640,19 @@ static int wide_ms(int cout, int L, int kind) {
     if (kind == WK_UP && cg == 64 && L == 2) return (m & 16) ? 16 : 32;
     return 32;
 }
-static int launch_rcb(const RcbP& p, int L, int form, int ms, int bf3, hipStream_t s) {
+// q: see launch_bf3_t (bf16x3 ops only)
+static int launch_rcb(const RcbP& p, int L, int form, int ms, int bf3, hipStream_t s, KernelAttrs* q = nullptr) {
     const int cg = p.Cout / 8;
     const bool res = p.res_out != nullptr;
     if (bf3) {
 #define EDMP_B3(MS, GS, LL) \
-    return res ? launch_bf3_t<WK_K5, MS, 32, GS, LL, true>(p, s) : launch_bf3_t<WK_K5, MS, 32, GS, LL, false>(p, s);
+    return res ? launch_bf3_t<WK_K5, MS, 32, GS, LL, true>(p, s, q) : launch_bf3_t<WK_K5, MS, 32, GS, LL, false>(p, s, q);
         if (cg == 32 && L == 7) { EDMP_B3(32, 32, 7) }
         if (cg == 16 && L == 7) { EDMP_B3(16, 16, 7) }
         if (cg == 16 && L == 13) { EDMP_B3(16, 16, 13) }
         if (cg == 32 && L == 4) { EDMP_B3(32, 32, 4) }
 #undef EDMP_B3
-        if (cg == 64 && L == 4) return res ? launch_bf3_t<WK_K5, 32, 64, 64, 4, true>(p, s) : launch_bf3_t<WK_K5, 32, 64, 64, 4, false>(p, s);
+        if (cg == 64 && L == 4) return res ? launch_bf3_t<WK_K5, 32, 64, 64, 4, true>(p, s, q) : launch_bf3_t<WK_K5, 32, 64, 64, 4, false>(p, s, q);
         set_error("no bf16x3 conv+GroupNorm kernel for Cout=%d L=%d", p.Cout, L);
         return EDMP_ERR_STATE;
     }
@@ -732,15 +734,15 @@ static bool wrs_supported(int cout, int cin, int Lin, bool transposed) {
     if (transposed) return (cg == 64 && Lin == 2) || (cg == 32 && Lin == 4) || (cg == 16 && Lin == 7);
     return (cg == 64 && Lin == 4) || (cg == 32 && Lin == 7) || (cg == 16 && Lin == 13);
 }
-static int launch_wrs(const RcbP& p, int kind, int Lin, int ms, int bf3, hipStream_t s) {
+static int launch_wrs(const RcbP& p, int kind, int Lin, int ms, int bf3, hipStream_t s, KernelAttrs* q = nullptr) {
     const int cg = p.Cout / 8;
     if (bf3) {  // bf3.hip: no GroupNorm behind a resampler, so 32-channel workgroups at every width
-        if (kind == WK_DOWN && cg == 32 && Lin == 7) return launch_bf3_t<WK_DOWN, 32, 32, 32, 7, false>(p, s);
-        if (kind == WK_UP && cg == 32 && Lin == 4) return launch_bf3_t<WK_UP, 32, 32, 32, 4, false>(p, s);
-        if (kind == WK_DOWN && cg == 64 && Lin == 4) return launch_bf3_t<WK_DOWN, 32, 32, 32, 4, false>(p, s);
-        if (kind == WK_UP && cg == 64 && Lin == 2) return launch_bf3_t<WK_UP, 32, 32, 32, 2, false>(p, s);
-        if (kind == WK_DOWN && cg == 16 && Lin == 13) return launch_bf3_t<WK_DOWN, 16, 32, 16, 13, false>(p, s);
-        if (kind == WK_UP && cg == 16 && Lin == 7) return launch_bf3_t<WK_UP, 16, 32, 16, 7, false>(p, s);
+        if (kind == WK_DOWN && cg == 32 && Lin == 7) return launch_bf3_t<WK_DOWN, 32, 32, 32, 7, false>(p, s, q);
+        if (kind == WK_UP && cg == 32 && Lin == 4) return launch_bf3_t<WK_UP, 32, 32, 32, 4, false>(p, s, q);
+        if (kind == WK_DOWN && cg == 64 && Lin == 4) return launch_bf3_t<WK_DOWN, 32, 32, 32, 4, false>(p, s, q);
+        if (kind == WK_UP && cg == 64 && Lin == 2) return launch_bf3_t<WK_UP, 32, 32, 32, 2, false>(p, s, q);
+        if (kind == WK_DOWN && cg == 16 && Lin == 13) return launch_bf3_t<WK_DOWN, 16, 32, 16, 13, false>(p, s, q);
+        if (kind == WK_UP && cg == 16 && Lin == 7) return launch_bf3_t<WK_UP, 16, 32, 16, 7, false>(p, s, q);
         set_error("no bf16x3 resampling kernel for kind=%d Cout=%d Lin=%d", kind, p.Cout, Lin);
         return EDMP_ERR_STATE;
     }
@@ -789,6 +791,33 @@ static void op_kernel_name(const Op& op, char* out) {
     }
 }
 
+
+// ---- the bf16x3 kernels' CU claim (bf3.hip: bf3_conv_kernel; profiles/r06_coresidency_fault.md) ------------------------------------
+// A bf16x3 workgroup must own its CU: one workgroup per CU, and its waves' registers fill the 512-entry file of every SIMD
+// (allocated in granules of 8 per lane), so that no wave of another kernel fits beside it.  Host-only: a function of what the
+// runtime reports, unit-tested on the CPU through edmp_cu_claim.
+static bool owns_cu(int regs, int block, int lds, int wg_per_cu) {
+    if (regs <= 0 || block <= 0 || lds < 0) return false;
+    const int alloc = (regs + 7) / 8 * 8, waves_per_simd = ((block + 63) / 64 + 3) / 4;
+    const int free_regs = 512 - alloc * waves_per_simd;  // per lane, on a SIMD that holds this workgroup's waves
+    const int wg_by_regs = (512 / alloc) / waves_per_simd, wg_by_lds = lds > 0 ? 160 * 1024 / lds : wg_by_regs;
+    return free_regs < 8 && std::min(wg_by_regs, wg_by_lds) == 1 && wg_per_cu == 1;
+}
+
+static int check_bf3_cu_claim(UNet* u) {
+    for (Op& op : u->prog) {
+        if (!((op.kind == OP_RCB || op.kind == OP_WRS) && op.rc_bf3)) continue;
+        int rc = op.kind == OP_RCB ? launch_rcb(op.rc, op.rc_L, op.rc_form, op.rc_ms, 1, nullptr, &op.attrs)
+                                   : launch_wrs(op.rc, op.wrs_kind, op.rc_L, op.rc_ms, 1, nullptr, &op.attrs);
+        if (rc) return rc;
+        const KernelAttrs& a = op.attrs;
+        EDMP_REQUIRE(owns_cu(a.regs, a.block, a.lds, a.wg_per_cu),
+                     "%s does not own its CU (%d VGPRs x %d threads, %d B of LDS, %d workgroups per CU): the bf16x3 containment of "
+                     "profiles/r06_coresidency_fault.md is lost; build the model with EDMP_BF16X3=0",
+                     op.name, a.regs, a.block, a.lds, a.wg_per_cu);
+    }
+    return EDMP_OK;
+}
 
 bool unet_complete(const UNet* u) { return u && u->wpack && u->tbias && !u->prog.empty(); }
 
@@ -1595,6 +1624,7 @@ static int unet_build(edmp_ctx* ctx, const edmp_unet_desc* desc, const float* pa
         EDMP_HIP_CHECK(hipStreamSynchronize(ctx->stream));
     }
     resolve_program(u, pl);
+    if (int rc = check_bf3_cu_claim(u)) return rc;
     u->flops_nominal += pl.head_flops;
     u->flops_exec += pl.head_flops;
     u->flops_direct += pl.head_flops;
@@ -1863,6 +1893,26 @@ extern "C" int edmp_prof_ops(edmp_ctx* ctx, int cap, int* n_ops, double* ms, int
             strncpy(names + (size_t)i * 64, op.name, 63);
             names[(size_t)i * 64 + 63] = 0;
         }
+    }
+    return EDMP_OK;
+}
+
+extern "C" int edmp_cu_claim(int regs, int block, int lds_bytes, int wg_per_cu) { return owns_cu(regs, block, lds_bytes, wg_per_cu) ? 1 : 0; }
+
+extern "C" int edmp_unet_op_attrs(edmp_ctx* ctx, int cap, int* n_ops, char* names, int* regs, int* block, int* lds_bytes, int* wg_per_cu) {
+    EDMP_REQUIRE(ctx && ctx->unet && n_ops, "edmp_unet_op_attrs: null argument / no model");
+    const int n = (int)ctx->unet->prog.size();
+    *n_ops = n;
+    for (int i = 0; i < n && i < cap; ++i) {
+        const Op& op = ctx->unet->prog[i];
+        if (names) {
+            strncpy(names + (size_t)i * 64, op.name, 63);
+            names[(size_t)i * 64 + 63] = 0;
+        }
+        if (regs) regs[i] = op.attrs.regs;
+        if (block) block[i] = op.attrs.block;
+        if (lds_bytes) lds_bytes[i] = op.attrs.lds;
+        if (wg_per_cu) wg_per_cu[i] = op.attrs.wg_per_cu;
     }
     return EDMP_OK;
 }

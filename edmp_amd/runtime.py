@@ -198,6 +198,18 @@ class Context:
         _capi.check(self.lib.edmp_prof_ops_bf16(self.h, cap, C.byref(n), fl))
         return [float(fl[i]) for i in range(min(n.value, cap))]
 
+    def op_attrs(self):
+        """per program op of the loaded UNet, as the HIP runtime reported it when the model was built: dicts of kernel instance
+        name, VGPRs per lane, threads per workgroup, dynamic LDS bytes and workgroups per CU (bf16x3 ops; zeros for the others)."""
+        cap = 256
+        n = C.c_int()
+        names = C.create_string_buffer(cap * 64)
+        cols = [(C.c_int32 * cap)() for _ in range(4)]
+        _capi.check(self.lib.edmp_unet_op_attrs(self.h, cap, C.byref(n), names, *cols))
+        keys = ("regs", "block", "lds", "wg_per_cu")
+        return [dict(name=names.raw[i * 64:(i + 1) * 64].split(b"\0", 1)[0].decode(), **{k: int(c[i]) for k, c in zip(keys, cols)})
+                for i in range(min(n.value, cap))]
+
 
 _slot_counter = [0]
 

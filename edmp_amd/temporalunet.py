@@ -168,6 +168,11 @@ class TemporalUNet:
         _capi.check(self.ctx.lib.edmp_unet_flops_pipes(self.ctx.h, C.byref(a), C.byref(b)))
         return a.value, b.value
 
+    def op_attrs(self):
+        """per op of this model's layer program: kernel name and the runtime's VGPRs / block / LDS / workgroups per CU (see edmp_unet_op_attrs)."""
+        self._bind()
+        return self.ctx.op_attrs()
+
     def pack(self, path=None):
         """Write the device weight image next to the checkpoint (<model_name>/weights_packed.edmp, or ``path``): later
         constructions of this architecture load it with one mmap + one copy.  No reference counterpart."""

@@ -266,6 +266,14 @@ int edmp_prof_read(edmp_ctx* ctx, double* conv_ms, int64_t* conv_launches, int r
 int edmp_prof_ops(edmp_ctx* ctx, int cap, int* n_ops, double* ms, int64_t* calls, double* flops_exec, char* names);
 /* per op of the same program: FLOPs per trajectory per launch issued on the bf16 matrix pipe (0 for an fp32-MFMA op) */
 int edmp_prof_ops_bf16(edmp_ctx* ctx, int cap, int* n_ops, double* flops_bf16);
+/* per op of the same program, as the HIP runtime reports them when the model is built (no reference counterpart): kernel instance
+ * name (64 bytes each), VGPRs per lane (arch + acc), threads per workgroup, dynamic LDS bytes and workgroups per CU at that size.
+ * Filled for the bf16x3 ops, whose CU claim the build checks (profiles/r06_coresidency_fault.md); 0 for every other op. */
+int edmp_unet_op_attrs(edmp_ctx* ctx, int cap, int* n_ops, char* names, int* regs, int* block, int* lds_bytes, int* wg_per_cu);
+/* host-only: 1 if a workgroup with these runtime attributes owns its CU (one workgroup per CU, and its waves' VGPRs, allocated in
+ * granules of 8, fill the 512-entry file of every SIMD it runs on, so that no wave of another kernel fits beside it); else 0.
+ * The decision edmp_unet_load applies to every bf16x3 op, refusing the model (EDMP_BF16X3=0 builds it without them). */
+int edmp_cu_claim(int regs, int block, int lds_bytes, int wg_per_cu);
 
 #ifdef __cplusplus
 }
