@@ -9,6 +9,8 @@ _HERE = os.path.dirname(os.path.abspath(__file__))
 LIB_PATH = os.path.join(_HERE, "libedmp_hip.so")
 
 MAX_LEVELS = 8
+MAX_SCENES = 16  # EDMP_MAX_SCENES
+MAX_OBSTACLES = 64  # EDMP_MAX_OBSTACLES
 
 
 class UNetDesc(C.Structure):
@@ -72,6 +74,9 @@ SIGNATURES = {
     "edmp_denoise_guided_rng_dev": (_i, [_vp, C.c_uint64, _i, _pd, _pd, _i, _i, _i, _vp]),
     "edmp_rng_normal_dev": (_i, [_vp, C.c_uint64, _i, _i, _i, _i, _vp]),
     "edmp_sampler_set_graph": (_i, [_vp, _i]),
+    "edmp_scene_batch_set": (_i, [_vp, _i, _pi32, _pd, _pi32, _pd, _pd, _i, _pf, _pf, _pf]),
+    "edmp_denoise_scenes_dev": (_i, [_vp, _vp, _i, _i, _pd, _pd, _i, _i, _i, _vp]),
+    "edmp_denoise_scenes_segment_dev": (_i, [_vp, _vp, _i, _i, _pd, _pd, _i, _i, _i, _i, _i, _vp]),
     "edmp_q_sample_dev": (_i, [_vp, _vp, _vp, _pi32, _i, _i, _i, _i, _i, _vp, _vp]),
     "edmp_unet_packed_size": (C.c_int64, [_vp, C.POINTER(C.c_int)]),
     "edmp_unet_read_packed": (_i, [_vp, _pf, C.c_int64]),

@@ -15,6 +15,14 @@ struct RobotConst {
 struct Guide {
     int no = 0, G = 0, T = 0;
     float* aabb = nullptr;  // [G][T+1][no][6]
+    // scene batch (edmp_scene_batch_set): S scenes share this object; class c holds cls_no[c] obstacles in its own [T+1][cls_no][6] block
+    // at float offset cls_off[c] of aabb (no = the largest count).  S = 1 / cls_no = nullptr: one scene, the table above
+    int S = 1;
+    int32_t* cls_no = nullptr;    // [2][G] device: counts, then float offsets
+    std::vector<int> cls_off_h;   // [G] host copy of the offsets (S > 1)
+    std::vector<int> cls_no_h;    // [G] host copy (S > 1)
+    std::vector<int> cls_scene_h; // [G] scene of each class (S > 1)
+    int rps = 0;                  // rows per scene, set by edmp_rows_set (= B for one scene)
     RobotConst rc{};
     // the obstacles as the simulator of the reference spawns them (lib/environment.py:230-268): oriented boxes / cylinders,
     // f64 [no][16] = world rotation (row-major 3x3, columns = axes), centre, half extents, pad; kind 0 cuboid / 1 cylinder
@@ -30,12 +38,23 @@ struct Guide {
     // scratch
     float* graw = nullptr;    // [B][7][L] raw f32 gradient
     double* rowsq = nullptr;  // [B]
-    double* sumsq = nullptr;  // [1]
-    float* startgoal = nullptr;  // [14] f32
+    double* sumsq = nullptr;  // [EDMP_MAX_SCENES]: one sum(g^2) per scene (index 0 = the whole batch of one scene)
+    float* startgoal = nullptr;  // [EDMP_MAX_SCENES][14] f32: start (7) | goal (7) per scene
     int scratch_B = 0, scratch_L = 0;
     float* vol_rows = nullptr;  // [B] for best trajectory
     int32_t* flags = nullptr;   // [3][flags_B] success check: ok, first colliding waypoint, within limits; + [4] counts
     int flags_B = 0;
 };
+
+// the per-scene entry points (cost, gradient, best trajectory, success, shapes) on a bound scene batch: refused, never answered
+// with scene 0's data
+#define EDMP_REFUSE_SCENE_BATCH(g, what)                                                                                          \
+    do {                                                                                                                          \
+        if ((g) && (g)->S > 1) {                                                                                                  \
+            edmp::set_error("%s: the bound guide is a scene batch of %d scenes (edmp_scene_batch_set); use one guide per scene", \
+                            what, (g)->S);                                                                                        \
+            return EDMP_ERR_STATE;                                                                                                \
+        }                                                                                                                         \
+    } while (0)
 
 }  // namespace edmp

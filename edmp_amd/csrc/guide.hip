@@ -64,7 +64,8 @@ void ctx_pool_destroy(edmp_ctx* ctx) {
 void guide_destroy(edmp_ctx* ctx, Guide* g) {
     if (!g) return;
     for (void* p : {(void*)g->aabb, (void*)g->row_class, (void*)g->method, (void*)g->grad_norm, (void*)g->sched, (void*)g->graw,
-                    (void*)g->rowsq, (void*)g->sumsq, (void*)g->startgoal, (void*)g->vol_rows, (void*)g->obb, (void*)g->kind, (void*)g->flags})
+                    (void*)g->rowsq, (void*)g->sumsq, (void*)g->startgoal, (void*)g->vol_rows, (void*)g->obb, (void*)g->kind, (void*)g->flags,
+                    (void*)g->cls_no})
         ctx_release(ctx, p);
     delete g;
 }
@@ -139,7 +140,10 @@ struct GuideArgs {
     const float* method;  // GM_GRAD: 0 iv / 1 sv per row
     const float* aabb;    // [G][T+1][no][6]
     int T, no;
-    const float* startgoal;  // [14] f32
+    const int32_t* cls_no;   // scene batch: obstacles of each class, else nullptr
+    const int32_t* cls_off;  // scene batch: float offset of each class's [T+1][cls_no][6] block in aabb
+    int rps;                 // scene batch: rows per scene (row r uses start/goal of scene r / rps), else 0
+    const float* startgoal;  // [14] f32 (scene batch: [S][14])
     float* out;              // volumes / raw gradient / row sums
     double* rowsq;           // GM_GRAD: per-row sum g^2
 };
@@ -191,11 +195,13 @@ __global__ __launch_bounds__(256, (SPLIT == 4 ? 4 : 1)) void guide_kernel(GuideA
     const bool row_ok = r < a.n;
     const int rr = row_ok ? r : 0;
     const int L = a.L;
-    const int no = a.no;
+    const int cls = a.use_row_class ? a.row_class[rr] : 0;
+    // the row's own obstacle count (a scene batch: its scene's, from a table without padding - the arithmetic is the serial run's)
+    const int no_cls = a.cls_no ? a.cls_no[cls] : a.no;
+    const int no = no_cls;
     // obstacle AABBs of this row's class at step t -> LDS slice of this wave (SPLIT = 4: one table for the row's four waves)
     {
-        const int cls = a.use_row_class ? a.row_class[rr] : 0;
-        const float* src = a.aabb + ((size_t)cls * (a.T + 1) + a.t) * no * 6;
+        const float* src = a.cls_no ? a.aabb + a.cls_off[cls] + (size_t)a.t * no_cls * 6 : a.aabb + ((size_t)cls * (a.T + 1) + a.t) * no_cls * 6;
         if (SPLIT == 4) {
             for (int i = threadIdx.x; i < no * 6; i += 256) s_obs[0][i] = src[i];
         } else {
@@ -216,6 +222,7 @@ __global__ __launch_bounds__(256, (SPLIT == 4 ? 4 : 1)) void guide_kernel(GuideA
 
     // this lane's joint vector: padded waypoint w = lane (0 start, 1..L interior, >= L+1 goal)
     const int w = lane;
+    const float* sgp = a.startgoal + (a.rps ? (rr / a.rps) * 14 : 0);  // this row's scene's start | goal
     float q[7];
     {
         // all seven joint values are requested before any of them is looked at (per-joint branches would serialise seven
@@ -236,7 +243,7 @@ __global__ __launch_bounds__(256, (SPLIT == 4 ? 4 : 1)) void guide_kernel(GuideA
             } else {
                 v = (float)xr[j];
             }
-            const float vs = a.startgoal[j], vg = a.startgoal[7 + j];
+            const float vs = sgp[j], vg = sgp[7 + j];
             q[j] = (w == 0) ? vs : ((w > L) ? vg : v);
         }
     }
@@ -458,10 +465,12 @@ __device__ __forceinline__ double block_sum_rowsq(const double* __restrict__ row
     }
     return sm[0];
 }
+// block s sums rows [s*B, (s+1)*B): one block = the whole batch; a scene batch launches one block per scene (B = rows per scene), so
+// each scene's sum is formed exactly as a B-row run of that scene forms it
 __global__ void reduce_rowsq_kernel(const double* __restrict__ rowsq, int B, double* __restrict__ out) {
     __shared__ double sm[256];
-    const double tot = block_sum_rowsq(rowsq, B, sm);
-    if (threadIdx.x == 0) out[0] = tot;
+    const double tot = block_sum_rowsq(rowsq + (size_t)blockIdx.x * B, B, sm);
+    if (threadIdx.x == 0) out[blockIdx.x] = tot;
 }
 
 // gradient1 = (1 - gn) * g + gn * (g / ||g||)   (lib/guide.py:627-629): f32 division, f64 mix; written as f64
@@ -561,6 +570,9 @@ static int launch_guide(edmp_ctx* ctx, const TIn* joints, int ldw, int off, int 
     a.aabb = g->aabb;
     a.T = g->T;
     a.no = g->no;
+    a.cls_no = (g->S > 1) ? g->cls_no : nullptr;
+    a.cls_off = (g->S > 1) ? g->cls_no + g->G : nullptr;
+    a.rps = (g->S > 1) ? g->rps : 0;
     a.startgoal = g->startgoal;
     a.out = out;
     a.rowsq = rowsq;
@@ -594,7 +606,9 @@ int guide_raw_gradient_from_X(edmp_ctx* ctx, const double* X_dev, int B, int N, 
     if (rc) return rc;
     rc = launch_guide<GM_GRAD, double>(ctx, X_dev, N, 1, B, N - 2, t, 1, 1, g->graw, g->rowsq);
     if (rc) return rc;
-    if (reduce) hipLaunchKernelGGL(reduce_rowsq_kernel, dim3(1), dim3(256), 0, ctx->stream, g->rowsq, B, g->sumsq);
+    // a scene batch always reduces here: one sum per scene, each over its own rows (the update kernel's in-block re-sum is one sum)
+    if (g->S > 1) hipLaunchKernelGGL(reduce_rowsq_kernel, dim3(g->S), dim3(256), 0, ctx->stream, g->rowsq, g->rps, g->sumsq);
+    else if (reduce) hipLaunchKernelGGL(reduce_rowsq_kernel, dim3(1), dim3(256), 0, ctx->stream, g->rowsq, B, g->sumsq);
     EDMP_HIP_CHECK(hipGetLastError());
     return EDMP_OK;
 }
@@ -606,6 +620,18 @@ int guide_set_startgoal(edmp_ctx* ctx, const double* start, const double* goal) 
         gl[i] = (float)goal[i];
     }
     return upload_startgoal(ctx, s, gl);
+}
+// scene batch: S rows of (start 7 | goal 7) f64 -> the guide's f32 [S][14]
+int guide_set_startgoal_scenes(edmp_ctx* ctx, int S, const double* starts, const double* goals) {
+    float sg[EDMP_MAX_SCENES * 14];
+    for (int s = 0; s < S; ++s)
+        for (int i = 0; i < 7; ++i) {
+            sg[s * 14 + i] = (float)starts[s * 7 + i];
+            sg[s * 14 + 7 + i] = (float)goals[s * 7 + i];
+        }
+    EDMP_HIP_CHECK(hipMemcpyAsync(ctx->guide->startgoal, sg, (size_t)S * 14 * sizeof(float), hipMemcpyHostToDevice, ctx->stream));
+    EDMP_HIP_CHECK(hipStreamSynchronize(ctx->stream));  // the host array lives on this frame
+    return EDMP_OK;
 }
 const float* guide_graw(edmp_ctx* ctx) { return ctx->guide->graw; }
 const double* guide_grad_norm(edmp_ctx* ctx) { return ctx->guide->grad_norm; }
@@ -634,31 +660,52 @@ static void quat_to_matrix(const double* q, double m[3][3]) {
     m[2][2] = -x2 - y2 + z2 + w2;
 }
 
-extern "C" int edmp_scene_set(edmp_ctx* ctx, const double* obstacle_config, int no, const double* clearance, const double* expansion, int G,
-                              int T, const float* link_half_extents, const float* dh, const float* static_frames) {
-    EDMP_REQUIRE(ctx && obstacle_config && clearance && expansion && link_half_extents && dh && static_frames, "edmp_scene_set: null argument");
-    EDMP_REQUIRE(no >= 1 && no <= EDMP_MAX_OBSTACLES, "n_obstacles %d outside 1..%d", no, EDMP_MAX_OBSTACLES);
-    ctx->epoch++;
-    EDMP_REQUIRE(G >= 1 && T >= 1, "need at least one guide class and one step");
+// the scene tables of S scenes (S = 1: edmp_scene_set) in the CURRENT guide object: obstacles of scene s are rows
+// [sum_{s'<s} nos[s'], ...) of obstacle_config, its classes rows [sum_{s'<s} ncls[s'], ...) of clearance / expansion.  The table is scene
+// after scene, each scene's block the [G_s][T+1][no_s][6] table a one-scene guide of that scene holds (no padding: a zero-size padded
+// obstacle would be arithmetically neutral, so a row looping over another scene's count would go unnoticed); cls_no = [G] counts then
+// [G] float offsets.  A one-scene table is exactly the table edmp_scene_set always built.
+static int scene_tables_set(edmp_ctx* ctx, int S, const int32_t* nos, const double* obstacle_config, const int32_t* ncls, const double* clearance,
+                            const double* expansion, int T, const float* link_half_extents, const float* dh, const float* static_frames) {
+    int no_tot = 0, no_max = 0, G = 0;
+    for (int s = 0; s < S; ++s) {
+        no_tot += nos[s];
+        no_max = std::max(no_max, (int)nos[s]);
+        G += ncls[s];
+    }
     EDMP_HIP_CHECK(hipSetDevice(ctx->device));
     // (device blocks come from / go back to the context's pool and every copy is enqueued on the context's stream: no hipFree, no
     // null-stream copy - a scene change on one context must not wait for another context's queued loop, see common.h)
     if (!ctx->guide) {
         ctx->guide = new Guide();
-        if (int rc = ctx_alloc(ctx, (void**)&ctx->guide->sumsq, sizeof(double))) return rc;
-        if (int rc = ctx_alloc(ctx, (void**)&ctx->guide->startgoal, 14 * sizeof(float))) return rc;
-        EDMP_HIP_CHECK(hipMemsetAsync(ctx->guide->startgoal, 0, 14 * sizeof(float), ctx->stream));
+        if (int rc = ctx_alloc(ctx, (void**)&ctx->guide->sumsq, EDMP_MAX_SCENES * sizeof(double))) return rc;
+        if (int rc = ctx_alloc(ctx, (void**)&ctx->guide->startgoal, EDMP_MAX_SCENES * 14 * sizeof(float))) return rc;
+        EDMP_HIP_CHECK(hipMemsetAsync(ctx->guide->startgoal, 0, EDMP_MAX_SCENES * 14 * sizeof(float), ctx->stream));
     }
     Guide* g = ctx->guide;
     // nothing enqueued may still read the tables that go back to the pool (as edmp_rows_set; hipFree used to wait for every stream)
     EDMP_HIP_CHECK(hipStreamSynchronize(ctx->stream));
-    for (void** p : {(void**)&g->aabb, (void**)&g->obb, (void**)&g->kind}) {
+    for (void** p : {(void**)&g->aabb, (void**)&g->obb, (void**)&g->kind, (void**)&g->cls_no}) {
         ctx_release(ctx, *p);
         *p = nullptr;
     }
-    g->no = no;
+    g->no = no_max;
     g->G = G;
     g->T = T;
+    g->S = S;
+    g->rps = 0;
+    g->cls_no_h.clear();
+    g->cls_scene_h.clear();
+    g->cls_off_h.clear();
+    size_t table_floats = 0;
+    for (int s = 0; s < S; ++s)
+        for (int c = 0; c < ncls[s]; ++c) {
+            g->cls_no_h.push_back(nos[s]);
+            g->cls_scene_h.push_back(s);
+            g->cls_off_h.push_back((int)table_floats);
+            table_floats += (size_t)(T + 1) * nos[s] * 6;
+        }
+    EDMP_REQUIRE(table_floats < (size_t)1 << 31, "scene batch: obstacle table of %zu floats is too large", table_floats);
     memcpy(g->rc.dh, dh, sizeof(g->rc.dh));
     memcpy(g->rc.sf, static_frames, sizeof(g->rc.sf));
     memcpy(g->rc.he, link_half_extents, sizeof(g->rc.he));
@@ -669,9 +716,9 @@ extern "C" int edmp_scene_set(edmp_ctx* ctx, const double* obstacle_config, int 
         g->rc.qlo[i] = lo_deg[i] * (pi / 180);  // diffusion.py:282-296 evaluates deg*(np.pi/180)
         g->rc.qhi[i] = hi_deg[i] * (pi / 180);
     }
-    std::vector<double> sizes(no * 3), obb((size_t)no * 16, 0.0);
-    std::vector<float> tf(no * 12);
-    for (int o = 0; o < no; ++o) {
+    std::vector<double> sizes(no_tot * 3), obb((size_t)no_tot * 16, 0.0);
+    std::vector<float> tf(no_tot * 12);
+    for (int o = 0; o < no_tot; ++o) {
         const double* c = obstacle_config + o * 10;
         double m[3][3];
         quat_to_matrix(c + 3, m);
@@ -692,22 +739,29 @@ extern "C" int edmp_scene_set(edmp_ctx* ctx, const double* obstacle_config, int 
     const size_t n_sz = sizes.size(), n_gt = (size_t)G * T;
     double* d_in = nullptr;  // one staging block for the table kernel's inputs: sizes | clearance | expansion (f64), then the transforms (f32)
     int rc = ctx_alloc(ctx, (void**)&g->obb, obb.size() * sizeof(double));
-    if (!rc) rc = ctx_alloc(ctx, (void**)&g->kind, no * sizeof(int32_t));
+    if (!rc) rc = ctx_alloc(ctx, (void**)&g->kind, no_tot * sizeof(int32_t));
     if (!rc) rc = ctx_alloc(ctx, (void**)&d_in, (n_sz + 2 * n_gt) * sizeof(double) + tf.size() * sizeof(float));
-    if (!rc) rc = ctx_alloc(ctx, (void**)&g->aabb, (size_t)G * (T + 1) * no * 6 * sizeof(float));
+    // (+ one zeroed slice of the largest count behind the last class: a scene batch's kernels never read it)
+    if (!rc) rc = ctx_alloc(ctx, (void**)&g->aabb, (table_floats + (S > 1 ? (size_t)no_max * 6 : 0)) * sizeof(float));
+    if (!rc && S > 1) rc = ctx_alloc(ctx, (void**)&g->cls_no, 2 * G * sizeof(int32_t));
     hipError_t e = hipSuccess;
     if (!rc) {
         double *d_sizes = d_in, *d_clr = d_in + n_sz, *d_exp = d_clr + n_gt;
         float* d_tf = reinterpret_cast<float*>(d_exp + n_gt);
         e = hipMemcpyAsync(g->obb, obb.data(), obb.size() * sizeof(double), hipMemcpyHostToDevice, st);
-        if (e == hipSuccess) e = hipMemsetAsync(g->kind, 0, no * sizeof(int32_t), st);  // every obstacle a cuboid until edmp_scene_set_shapes says otherwise
+        if (e == hipSuccess) e = hipMemsetAsync(g->kind, 0, no_tot * sizeof(int32_t), st);  // every obstacle a cuboid until edmp_scene_set_shapes says otherwise
         if (e == hipSuccess) e = hipMemcpyAsync(d_sizes, sizes.data(), n_sz * sizeof(double), hipMemcpyHostToDevice, st);
         if (e == hipSuccess) e = hipMemcpyAsync(d_tf, tf.data(), tf.size() * sizeof(float), hipMemcpyHostToDevice, st);
         if (e == hipSuccess) e = hipMemcpyAsync(d_clr, clearance, n_gt * sizeof(double), hipMemcpyHostToDevice, st);
         if (e == hipSuccess) e = hipMemcpyAsync(d_exp, expansion, n_gt * sizeof(double), hipMemcpyHostToDevice, st);
-        if (e == hipSuccess) {
-            int total = G * (T + 1) * no;
-            hipLaunchKernelGGL(obstacle_table_kernel, dim3((total + 255) / 256), dim3(256), 0, st, d_sizes, d_tf, d_clr, d_exp, g->aabb, G, T, no);
+        if (e == hipSuccess && S > 1) e = hipMemcpyAsync(g->cls_no, g->cls_no_h.data(), G * sizeof(int32_t), hipMemcpyHostToDevice, st);
+        if (e == hipSuccess && S > 1) e = hipMemcpyAsync(g->cls_no + G, g->cls_off_h.data(), G * sizeof(int32_t), hipMemcpyHostToDevice, st);
+        if (e == hipSuccess && S > 1) e = hipMemsetAsync(g->aabb + table_floats, 0, (size_t)no_max * 6 * sizeof(float), st);
+        // one table launch per scene: its obstacles and classes into its block
+        for (int sc = 0, o0 = 0, c0 = 0; sc < S && e == hipSuccess; o0 += nos[sc], c0 += ncls[sc], ++sc) {
+            const int total = ncls[sc] * (T + 1) * nos[sc];
+            hipLaunchKernelGGL(obstacle_table_kernel, dim3((total + 255) / 256), dim3(256), 0, st, d_sizes + (size_t)o0 * 3, d_tf + (size_t)o0 * 12,
+                               d_clr + (size_t)c0 * T, d_exp + (size_t)c0 * T, g->aabb + g->cls_off_h[c0], (int)ncls[sc], T, (int)nos[sc]);
             e = hipGetLastError();
         }
         const hipError_t e2 = hipStreamSynchronize(st);
@@ -719,6 +773,32 @@ extern "C" int edmp_scene_set(edmp_ctx* ctx, const double* obstacle_config, int 
     return EDMP_OK;
 }
 
+extern "C" int edmp_scene_set(edmp_ctx* ctx, const double* obstacle_config, int no, const double* clearance, const double* expansion, int G,
+                              int T, const float* link_half_extents, const float* dh, const float* static_frames) {
+    EDMP_REQUIRE(ctx && obstacle_config && clearance && expansion && link_half_extents && dh && static_frames, "edmp_scene_set: null argument");
+    EDMP_REQUIRE(no >= 1 && no <= EDMP_MAX_OBSTACLES, "n_obstacles %d outside 1..%d", no, EDMP_MAX_OBSTACLES);
+    ctx->epoch++;
+    EDMP_REQUIRE(G >= 1 && T >= 1, "need at least one guide class and one step");
+    const int32_t nos[1] = {no}, ncls[1] = {G};
+    return scene_tables_set(ctx, 1, nos, obstacle_config, ncls, clearance, expansion, T, link_half_extents, dh, static_frames);
+}
+
+extern "C" int edmp_scene_batch_set(edmp_ctx* ctx, int S, const int32_t* n_obstacles, const double* obstacle_config, const int32_t* n_classes,
+                                    const double* clearance, const double* expansion, int T, const float* link_half_extents, const float* dh,
+                                    const float* static_frames) {
+    EDMP_REQUIRE(ctx && n_obstacles && obstacle_config && n_classes && clearance && expansion && link_half_extents && dh && static_frames,
+                 "edmp_scene_batch_set: null argument");
+    EDMP_REQUIRE(S >= 1 && S <= EDMP_MAX_SCENES, "edmp_scene_batch_set: %d scenes outside 1..%d", S, EDMP_MAX_SCENES);
+    EDMP_REQUIRE(T >= 1, "edmp_scene_batch_set: need at least one step");
+    for (int s = 0; s < S; ++s) {
+        EDMP_REQUIRE(n_obstacles[s] >= 1 && n_obstacles[s] <= EDMP_MAX_OBSTACLES, "edmp_scene_batch_set: scene %d has %d obstacles, outside 1..%d", s,
+                     n_obstacles[s], EDMP_MAX_OBSTACLES);
+        EDMP_REQUIRE(n_classes[s] >= 1, "edmp_scene_batch_set: scene %d has %d guide classes (need >= 1)", s, n_classes[s]);
+    }
+    ctx->epoch++;
+    return scene_tables_set(ctx, S, n_obstacles, obstacle_config, n_classes, clearance, expansion, T, link_half_extents, dh, static_frames);
+}
+
 extern "C" int edmp_rows_set(edmp_ctx* ctx, const int32_t* row_class, const float* method, const double* grad_norm, const double* sched, int B,
                              int T) {
     EDMP_REQUIRE(ctx && ctx->guide && ctx->guide->aabb, "edmp_rows_set: call edmp_scene_set first");
@@ -726,9 +806,14 @@ extern "C" int edmp_rows_set(edmp_ctx* ctx, const int32_t* row_class, const floa
     EDMP_REQUIRE(T == ctx->guide->T, "edmp_rows_set: guidance_schedule has %d steps, the scene tables %d (the reference indexes both with t-1)", T, ctx->guide->T);
     ctx->epoch++;
     Guide* g = ctx->guide;
+    // a scene batch: the rows split evenly over the scenes, and every row of scene s uses one of scene s's classes
+    EDMP_REQUIRE(B % g->S == 0, "edmp_rows_set: %d rows do not split evenly over the %d scenes of the batch", B, g->S);
+    const int rps = B / g->S;
     for (int i = 0; i < B; ++i) {
         EDMP_REQUIRE(row_class[i] >= 0 && row_class[i] < g->G, "row %d: class %d outside 0..%d", i, row_class[i], g->G - 1);
         EDMP_REQUIRE(method[i] == 0.0f || method[i] == 1.0f, "row %d: guidance_method must be 0 (iv) or 1 (sv)", i);
+        EDMP_REQUIRE(g->S == 1 || g->cls_scene_h[row_class[i]] == i / rps, "row %d (scene %d): class %d belongs to scene %d", i, i / rps, row_class[i],
+                     g->cls_scene_h[row_class[i]]);
     }
     EDMP_HIP_CHECK(hipSetDevice(ctx->device));
     EDMP_HIP_CHECK(hipStreamSynchronize(ctx->stream));  // nothing enqueued still reads the arrays that are replaced
@@ -749,6 +834,7 @@ extern "C" int edmp_rows_set(edmp_ctx* ctx, const int32_t* row_class, const floa
     EDMP_HIP_CHECK(e);
     EDMP_HIP_CHECK(e2);
     g->B = B;
+    g->rps = rps;
     g->rows_T = T;
     return EDMP_OK;
 }
@@ -769,7 +855,9 @@ extern "C" int edmp_scene_read_aabbs(edmp_ctx* ctx, int cls, int t, float* out_h
     EDMP_REQUIRE(ctx && ctx->guide && ctx->guide->aabb && out_host, "edmp_scene_read_aabbs: scene not set");
     Guide* g = ctx->guide;
     EDMP_REQUIRE(cls >= 0 && cls < g->G && t >= 0 && t <= g->T, "class/t out of range");
-    EDMP_HIP_CHECK(hipMemcpyAsync(out_host, g->aabb + ((size_t)cls * (g->T + 1) + t) * g->no * 6, (size_t)g->no * 6 * sizeof(float), hipMemcpyDeviceToHost, ctx->stream));
+    const int no = g->S > 1 ? g->cls_no_h[cls] : g->no;  // a scene batch: the class's own scene's obstacles
+    const float* src = g->S > 1 ? g->aabb + g->cls_off_h[cls] + (size_t)t * no * 6 : g->aabb + ((size_t)cls * (g->T + 1) + t) * g->no * 6;
+    EDMP_HIP_CHECK(hipMemcpyAsync(out_host, src, (size_t)no * 6 * sizeof(float), hipMemcpyDeviceToHost, ctx->stream));
     EDMP_HIP_CHECK(hipStreamSynchronize(ctx->stream));
     return EDMP_OK;
 }
@@ -777,6 +865,7 @@ extern "C" int edmp_scene_read_aabbs(edmp_ctx* ctx, int cls, int t, float* out_h
 static int check_cost_args(edmp_ctx* ctx, int n, int L, int t, int use_row_class) {
     EDMP_REQUIRE(ctx && ctx->guide && ctx->guide->aabb, "scene not set");
     Guide* g = ctx->guide;
+    EDMP_REFUSE_SCENE_BATCH(g, "cost / gradient / best-trajectory entry point");
     EDMP_REQUIRE(n >= 1 && L >= 1 && L + 2 <= 64, "need 1 <= L <= 62 waypoints per row (got %d)", L);
     EDMP_REQUIRE(t >= 0 && t <= g->T, "t=%d outside 0..%d", t, g->T);
     EDMP_REQUIRE(!use_row_class || (g->row_class && n <= g->B), "use_row_class needs edmp_rows_set with >= n rows");

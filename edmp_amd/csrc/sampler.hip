@@ -31,14 +31,16 @@ const double* guide_grad_norm(edmp_ctx* ctx);
 const double* guide_sched(edmp_ctx* ctx);
 double* guide_sumsq(edmp_ctx* ctx);
 int guide_rows_T(edmp_ctx* ctx);
+int guide_set_startgoal_scenes(edmp_ctx* ctx, int S, const double* starts, const double* goals);
 
 struct Sampler {
     int T = 0;
     std::vector<double> beta, alpha, alpha_bar, c1, sqrt_alpha;  // host tables (f64)
     // scratch for the loop
     double* X = nullptr;    // (B,C,N) f64 loop state
-    double* sg = nullptr;   // [14] start|goal f64
+    double* sg = nullptr;   // [EDMP_MAX_SCENES][14] start|goal f64 (one pair per scene of a scene batch)
     int run_B = 0;          // batch of the run whose state sits in X (segmented runs)
+    int run_rps = 0;        // its rows per scene (0 = one scene)
     int condition = 1;      // pin X[:, :, 0] / X[:, :, -1] to start / goal (diffusion.py:305-307, 347-349)
     int cap = 0;            // elements
     // whole-run hipGraph (edmp_sampler_set_graph): the enqueue of one denoise_loop call captured once and replayed while the
@@ -47,11 +49,11 @@ struct Sampler {
         const void* noise = nullptr;
         const void* hook = nullptr;  // the (native) all-reduce hook's communicator record the capture contains, or null
         uint64_t seed = 0;
-        int use_rng = 0, B = 0, guided = 0, t_hi = 0, t_lo = 0, init = 0, zero_row0 = 0, condition = 0;
+        int use_rng = 0, B = 0, guided = 0, t_hi = 0, t_lo = 0, init = 0, zero_row0 = 0, condition = 0, rps = 0;
         uint64_t epoch = 0;  // bumped by anything that invalidates captured pointers/arguments (scene, rows, weights)
         bool operator==(const GraphKey& o) const {
             return noise == o.noise && hook == o.hook && seed == o.seed && use_rng == o.use_rng && B == o.B && guided == o.guided && t_hi == o.t_hi &&
-                   t_lo == o.t_lo && init == o.init && zero_row0 == o.zero_row0 && condition == o.condition && epoch == o.epoch;
+                   t_lo == o.t_lo && init == o.init && zero_row0 == o.zero_row0 && condition == o.condition && rps == o.rps && epoch == o.epoch;
         }
     } gkey;
     hipGraphExec_t gexec = nullptr;
@@ -91,13 +93,15 @@ __global__ void psample_kernel(double* __restrict__ X, const float* __restrict__
 
 // X[:, :, 1:-1] -= sched[:, t-1] * ((1-gn) g + gn g/||g||);  then X[:, :, 0] = start, X[:, :, -1] = goal
 // rowsq != nullptr: the whole-batch sum(g^2) is formed here from the per-row partials, by every block in the summation order
-// of reduce_rowsq_kernel (bit-identical) - one launch less per guided step of the device-resident loop
+// of reduce_rowsq_kernel (bit-identical) - one launch less per guided step of the device-resident loop.
+// rps != 0 (a scene batch, rowsq == nullptr): row b belongs to scene b / rps and mixes with that scene's sum sumsq[b / rps] and
+// conditions on that scene's start / goal (an update block can straddle two scenes, so the in-block re-sum is not used there)
 __global__ __launch_bounds__(256) void update_kernel(double* __restrict__ X, const float* __restrict__ graw, const double* __restrict__ sumsq,
                               const double* __restrict__ rowsq, const double* __restrict__ grad_norm, const double* __restrict__ sched, int sched_T, int t, int B, int C, int N,
-                              const double* __restrict__ sg, int guided, double* __restrict__ grad_out, float* __restrict__ xin, int cond, int n) {
+                              const double* __restrict__ sg, int guided, double* __restrict__ grad_out, float* __restrict__ xin, int cond, int n, int rps) {
     __shared__ double sm[256];
     double total = 0.0;
-    if (guided) total = rowsq ? block_sum_rowsq(rowsq, B, sm) : sumsq[0];
+    if (guided && rowsq) total = block_sum_rowsq(rowsq, B, sm);
     // (one element per thread: a grid-stride variant with 256 blocks - the redundant reduction paid 256 instead of 1344 times - was
     // measured SLOWER, 11.6 vs 7.9 us: five dependent f64 round trips per thread at one wave per SIMD; round 5)
     const int i = blockIdx.x * blockDim.x + threadIdx.x;
@@ -105,6 +109,9 @@ __global__ __launch_bounds__(256) void update_kernel(double* __restrict__ X, con
     const int l = i % N;
     const int c = (i / N) % C;
     const int b = i / (N * C);
+    const int sc = rps ? b / rps : 0;
+    if (guided && !rowsq) total = sumsq[sc];
+    sg += 14 * sc;
     double xnew = X[i];
     if (l == 0) {
         if (cond) {
@@ -134,10 +141,11 @@ __global__ __launch_bounds__(256) void update_kernel(double* __restrict__ X, con
     }
 }
 
-__global__ void condition_kernel(double* __restrict__ X, int B, int C, int N, const double* __restrict__ sg) {
+__global__ void condition_kernel(double* __restrict__ X, int B, int C, int N, const double* __restrict__ sg, int rps) {
     int i = blockIdx.x * blockDim.x + threadIdx.x;  // over B*C
     if (i >= B * C) return;
     int c = i % C;
+    if (rps) sg += 14 * ((i / C) / rps);  // a scene batch: the row's scene's start / goal
     X[(size_t)i * N] = sg[c];
     X[(size_t)i * N + N - 1] = sg[7 + c];
 }
@@ -195,7 +203,7 @@ template <bool FINISH, bool RNG, int CIN>
 __global__ __launch_bounds__(256) void head_psample_kernel(const float* __restrict__ h, const float* __restrict__ w, const float* __restrict__ bias,
                                                            double* __restrict__ X, const double* __restrict__ z, float* __restrict__ eps_out,
                                                            float* __restrict__ xin, const double* __restrict__ sg, int B, int N, int Cin, int C,
-                                                           double c1, double sqrt_alpha, double beta, int zero_row0, uint64_t seed, int rng_step, int cond) {
+                                                           double c1, double sqrt_alpha, double beta, int zero_row0, int rps, uint64_t seed, int rng_step, int cond) {
     int i = blockIdx.x * blockDim.x + threadIdx.x;
     if constexpr (CIN > 0) {  // compile-time width: all input loads are issued back to back; the shared tail does the rest
         // the head's weights through LDS (224 wave-uniform scalar loads in a row serialise on the scalar cache)
@@ -213,7 +221,7 @@ __global__ __launch_bounds__(256) void head_psample_kernel(const float* __restri
         tail_fetch(X, z, RNG, b, l, N, C, xv, zv);
         __syncthreads();
         if (mine)
-            head_psample_item<FINISH, RNG, (CIN > 0 ? CIN : 4)>(hv, xv, zv, i, b, l, sw, sw + 8 * CIN, X, eps_out, xin, sg, N, C, c1, sqrt_alpha, beta, zero_row0, seed, rng_step, cond);
+            head_psample_item<FINISH, RNG, (CIN > 0 ? CIN : 4)>(hv, xv, zv, i, b, l, sw, sw + 8 * CIN, X, eps_out, xin, sg, N, C, c1, sqrt_alpha, beta, zero_row0, rps, seed, rng_step, cond);
         return;
     }
     if (i >= B * N) return;
@@ -222,6 +230,7 @@ __global__ __launch_bounds__(256) void head_psample_kernel(const float* __restri
     float xo[8] = {0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f};
     float zr[8] = {0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f};
     if (RNG) rng_normal8(seed, (uint32_t)rng_step, (uint32_t)i, zr);
+    if (FINISH && rps) sg += 14 * (b / rps);
     // each thread's Cin inputs are read ONCE (float4) and reused by all C outputs; weights are wave-uniform (scalar loads)
     float acc[8];
 #pragma unroll
@@ -248,7 +257,7 @@ __global__ __launch_bounds__(256) void head_psample_kernel(const float* __restri
         const size_t idx = ((size_t)b * C + co) * N + l;
         if (eps_out) eps_out[idx] = a;
         double zz = RNG ? (double)zr[co] : z[idx];
-        if (zero_row0 && b == 0) zz = 0.0;
+        if (zero_row0 && (rps ? b % rps : b) == 0) zz = 0.0;
         double x = (X[idx] - c1 * (double)a) / sqrt_alpha + beta * zz;
         if (FINISH) {
             if (cond && l == 0) x = sg[co];
@@ -306,12 +315,28 @@ static int set_startgoal(edmp_ctx* ctx, const double* start, const double* goal,
     return EDMP_OK;
 }
 
+// a scene batch: S pairs of start / goal (S,7) f64 -> sg [S][14] (and the guide's f32 copy)
+static int set_startgoal_scenes(edmp_ctx* ctx, int S, const double* starts, const double* goals, bool need_guide) {
+    Sampler* s = ctx->sampler;
+    double sg[EDMP_MAX_SCENES * 14];
+    for (int k = 0; k < S; ++k)
+        for (int i = 0; i < 7; ++i) {
+            sg[k * 14 + i] = starts[k * 7 + i];
+            sg[k * 14 + 7 + i] = goals[k * 7 + i];
+        }
+    EDMP_HIP_CHECK(hipMemcpyAsync(s->sg, sg, (size_t)S * 14 * sizeof(double), hipMemcpyHostToDevice, ctx->stream));
+    EDMP_HIP_CHECK(hipStreamSynchronize(ctx->stream));
+    if (need_guide) return guide_set_startgoal_scenes(ctx, S, starts, goals);
+    return EDMP_OK;
+}
+
 // One reverse step, first half.  `fused` (the device-resident loop): the UNet input of this step already sits in
 // unet->x_in (written by the previous step's tail kernel) and, on steps without guidance, the tail kernel also applies
 // the start/goal conditioning and writes the next input.  Otherwise (teacher-forced API): X comes from the caller, is
 // packed here, and conditioning is left to step_b so that the un-conditioned posterior can be returned.
+// rps: rows per scene of a scene batch (0 = one scene)
 static int step_a(edmp_ctx* ctx, double* X, const double* z, int B, int t, int zero_row0, int guided, float* eps_out, double* xpost_out,
-                  bool fused, bool use_rng = false, uint64_t seed = 0) {
+                  bool fused, bool use_rng = false, uint64_t seed = 0, int rps = 0) {
     Sampler* s = ctx->sampler;
     UNet* u = ctx->unet;
     const int C = u->desc.input_dim, N = u->desc.horizon;
@@ -340,6 +365,7 @@ static int step_a(edmp_ctx* ctx, double* X, const double* z, int B, int t, int z
         tail.sqrt_alpha = s->sqrt_alpha[t - 1];
         tail.beta = s->beta[t - 1];
         tail.zero_row0 = zr;
+        tail.rps = rps;
         tail.seed = seed;
         tail.rng_step = rstep;
         tail.cond = s->condition;
@@ -348,7 +374,7 @@ static int step_a(edmp_ctx* ctx, double* X, const double* z, int B, int t, int z
     }
     int rc = unet_run_program(ctx, B, t, want_tail ? &tail : nullptr, &tail_done);
     if (rc) return rc;
-#define EDMP_HP_ARGS(xin_ptr) hlast, u->head_w, u->head_b, X, z, eps_out, (xin_ptr), s->sg, B, N, u->head_cin, C, s->c1[t - 1], s->sqrt_alpha[t - 1], s->beta[t - 1], zr, seed, rstep, s->condition
+#define EDMP_HP_ARGS(xin_ptr) hlast, u->head_w, u->head_b, X, z, eps_out, (xin_ptr), s->sg, B, N, u->head_cin, C, s->c1[t - 1], s->sqrt_alpha[t - 1], s->beta[t - 1], zr, rps, seed, rstep, s->condition
 #define EDMP_HP_LAUNCH(FIN, RN, xin_ptr)                                                                                              \
     {                                                                                                                                  \
         if (u->head_cin == 32) hipLaunchKernelGGL((head_psample_kernel<FIN, RN, 32>), grid_bn, dim3(256), 0, st, EDMP_HP_ARGS(xin_ptr));      \
@@ -375,17 +401,19 @@ static int step_a(edmp_ctx* ctx, double* X, const double* z, int B, int t, int z
     return EDMP_OK;
 }
 
-static int step_b(edmp_ctx* ctx, double* X, int B, int t, int guided, double* grad_out, bool fused) {
+static int step_b(edmp_ctx* ctx, double* X, int B, int t, int guided, double* grad_out, bool fused, int rps = 0) {
     Sampler* s = ctx->sampler;
     UNet* u = ctx->unet;
     const int C = u->desc.input_dim, N = u->desc.horizon;
     hipStream_t st = ctx->stream;
     if (guided && guided_step(t)) {
         const int n = B * C * N;
-        hipLaunchKernelGGL(update_kernel, dim3((n + 255) / 256), dim3(256), 0, st, X, guide_graw(ctx), guide_sumsq(ctx), (fused && !s->ar_fn) ? guide_rowsq(ctx) : nullptr, guide_grad_norm(ctx),
-                           guide_sched(ctx), guide_rows_T(ctx), t, B, C, N, s->sg, 1, grad_out, fused ? u->x_in : nullptr, s->condition, n);
+        // (a scene batch has its per-scene sums from guide_raw_gradient_from_X: no in-block re-sum)
+        const double* rowsq = (fused && !s->ar_fn && !rps) ? guide_rowsq(ctx) : nullptr;
+        hipLaunchKernelGGL(update_kernel, dim3((n + 255) / 256), dim3(256), 0, st, X, guide_graw(ctx), guide_sumsq(ctx), rowsq, guide_grad_norm(ctx),
+                           guide_sched(ctx), guide_rows_T(ctx), t, B, C, N, s->sg, 1, grad_out, fused ? u->x_in : nullptr, s->condition, n, rps);
     } else if (!fused && s->condition) {
-        hipLaunchKernelGGL(condition_kernel, dim3((B * C + 255) / 256), dim3(256), 0, st, X, B, C, N, s->sg);
+        hipLaunchKernelGGL(condition_kernel, dim3((B * C + 255) / 256), dim3(256), 0, st, X, B, C, N, s->sg, rps);
     }  // fused + unguided: head_psample_kernel<true> already conditioned X and wrote the next input
     EDMP_HIP_CHECK(hipGetLastError());
     return EDMP_OK;
@@ -506,7 +534,7 @@ extern "C" int edmp_sampler_init(edmp_ctx* ctx, int T, double variance_thresh) {
     EDMP_HIP_CHECK(hipSetDevice(ctx->device));
     if (!ctx->sampler) {
         ctx->sampler = new Sampler();
-        EDMP_HIP_CHECK(hipMalloc((void**)&ctx->sampler->sg, 14 * sizeof(double)));
+        EDMP_HIP_CHECK(hipMalloc((void**)&ctx->sampler->sg, EDMP_MAX_SCENES * 14 * sizeof(double)));
     }
     Sampler* s = ctx->sampler;
     s->T = T;
@@ -558,8 +586,14 @@ extern "C" int edmp_psample_dev(edmp_ctx* ctx, double* X_dev, const float* eps_d
     return EDMP_OK;
 }
 
-static int check_loop_state(edmp_ctx* ctx, int B, bool guided) {
+// S: scenes of the run (1 = a single-scene entry point).  A guided run uses the bound guide's rows, so its scene count must match.
+static int check_loop_state(edmp_ctx* ctx, int B, bool guided, int S = 1) {
     EDMP_REQUIRE(ctx && ctx->sampler && ctx->unet, "sampler / model not initialised");
+    if (guided && ctx->guide && ctx->guide->S != S) {
+        if (S == 1) set_error("the bound guide is a scene batch of %d scenes (edmp_scene_batch_set): use edmp_denoise_scenes_dev, or one guide per scene", ctx->guide->S);
+        else set_error("the bound guide holds %d scene(s), the run %d scenes: bind the scene batch built for them (edmp_scene_batch_set)", ctx->guide->S, S);
+        return EDMP_ERR_STATE;
+    }
     EDMP_REQUIRE(ctx->unet->desc.input_dim == 7 || !guided, "the guide needs 7 joint channels");
     EDMP_REQUIRE(ctx->sampler->T <= ctx->unet->desc.T, "sampler T exceeds the model's time-bias table");
     EDMP_REQUIRE(B >= 1 && B <= ctx->unet->max_batch, "batch %d outside 1..%d", B, ctx->unet->max_batch);
@@ -608,7 +642,7 @@ extern "C" double* edmp_sumsq_ptr_dev(edmp_ctx* ctx) { return ctx ? guide_sumsq(
 // upload the next chunk of the NumPy noise stream while this one computes.
 // the stream work of one denoise_loop call: no host synchronisation, no allocation (capturable into a hipGraph)
 static int enqueue_loop(edmp_ctx* ctx, const double* noise_dev, bool use_rng, uint64_t seed, int B, int guided, int t_hi, int t_lo, bool init,
-                        int zero_row0, double* X_out_dev) {
+                        int zero_row0, double* X_out_dev, int rps) {
     Sampler* s = ctx->sampler;
     const int C = ctx->unet->desc.input_dim, N = ctx->unet->desc.horizon;
     const size_t n = (size_t)B * C * N;
@@ -621,14 +655,14 @@ static int enqueue_loop(edmp_ctx* ctx, const double* noise_dev, bool use_rng, ui
                                s->condition);
         } else {
             EDMP_HIP_CHECK(hipMemcpyAsync(s->X, noise_dev, n * sizeof(double), hipMemcpyDeviceToDevice, st));
-            if (s->condition) hipLaunchKernelGGL(condition_kernel, dim3((B * C + 255) / 256), dim3(256), 0, st, s->X, B, C, N, s->sg);
+            if (s->condition) hipLaunchKernelGGL(condition_kernel, dim3((B * C + 255) / 256), dim3(256), 0, st, s->X, B, C, N, s->sg, rps);
             hipLaunchKernelGGL(pack_state_kernel, dim3((B * N + 255) / 256), dim3(256), 0, st, s->X, ctx->unet->x_in, B, C, N);
             noise_dev += n;
         }
     }
     for (int t = t_hi; t > t_lo; --t) {
         const double* z = use_rng ? nullptr : noise_dev + (size_t)(t_hi - t) * n;
-        rc = step_a(ctx, s->X, z, B, t, zero_row0, guided, nullptr, nullptr, true, use_rng, seed);
+        rc = step_a(ctx, s->X, z, B, t, zero_row0, guided, nullptr, nullptr, true, use_rng, seed, rps);
         if (rc) return rc;
         if (s->ar_fn && guided && guided_step(t)) {
             // sharded logical batch: this rank's sum(g^2) -> the whole batch's, enqueued by the caller's collective on
@@ -644,17 +678,27 @@ static int enqueue_loop(edmp_ctx* ctx, const double* noise_dev, bool use_rng, ui
                 return EDMP_ERR_STATE;
             }
         }
-        rc = step_b(ctx, s->X, B, t, guided, nullptr, true);
+        rc = step_b(ctx, s->X, B, t, guided, nullptr, true, rps);
         if (rc) return rc;
     }
     if (X_out_dev) EDMP_HIP_CHECK(hipMemcpyAsync(X_out_dev, s->X, n * sizeof(double), hipMemcpyDeviceToDevice, st));
     return EDMP_OK;
 }
 
+// S > 1: a scene batch of S scenes x B / S rows; start / goal then hold S rows of 7 each
 static int denoise_loop(edmp_ctx* ctx, const double* noise_dev, bool use_rng, uint64_t seed, int B, const double* start, const double* goal,
-                        int guided, int t_hi, int t_lo, bool init, int zero_row0, double* X_out_dev, bool allow_graph = true) {
-    int rc = check_loop_state(ctx, B, guided != 0);
+                        int guided, int t_hi, int t_lo, bool init, int zero_row0, double* X_out_dev, bool allow_graph = true, int S = 1) {
+    int rc = check_loop_state(ctx, B, guided != 0, S);
     if (rc) return rc;
+    const int rps = S > 1 ? B / S : 0;
+    if (S > 1) {
+        if (guided) EDMP_REQUIRE(ctx->guide->B == B, "the scene batch's rows are set for %d rows, the run has %d", ctx->guide->B, B);
+        if (ctx->sampler->ar_fn) {
+            set_error("a scene batch cannot run with an all-reduce hook installed (the hook sums ONE sum(g^2), a scene batch has one per scene)");
+            return EDMP_ERR_STATE;
+        }
+        EDMP_REQUIRE(!use_rng, "the device noise mode has no scene batch");
+    }
     EDMP_REQUIRE(noise_dev || use_rng, "null noise pointer");
     Sampler* s = ctx->sampler;
     const int T = s->T;
@@ -668,11 +712,12 @@ static int denoise_loop(edmp_ctx* ctx, const double* noise_dev, bool use_rng, ui
         EDMP_REQUIRE(start && goal, "null start/goal");
         rc = ensure_sampler_scratch(ctx, (int)n);
         if (rc) return rc;
-        rc = set_startgoal(ctx, start, goal, guided != 0);
+        rc = S > 1 ? set_startgoal_scenes(ctx, S, start, goal, guided != 0) : set_startgoal(ctx, start, goal, guided != 0);
         if (rc) return rc;
         s->run_B = B;
+        s->run_rps = rps;
     } else {
-        EDMP_REQUIRE(s->X && s->run_B == B, "no run in progress for batch %d (call with init first)", B);
+        EDMP_REQUIRE(s->X && s->run_B == B && s->run_rps == rps, "no run in progress for batch %d / %d scene(s) (call with init first)", B, S);
     }
     // a caller-supplied collective is not capturable; segments of a chunked run carry a fresh noise pointer each, so a
     // captured graph would never be replayed (capture + instantiate + destroy per chunk): they are enqueued directly
@@ -684,7 +729,7 @@ static int denoise_loop(edmp_ctx* ctx, const double* noise_dev, bool use_rng, ui
             if (rc) return rc;
         }
         key.noise = noise_dev, key.hook = s->ar_fn ? s->ar_user : nullptr, key.seed = seed, key.use_rng = use_rng, key.B = B, key.guided = guided, key.t_hi = t_hi, key.t_lo = t_lo;
-        key.init = init, key.zero_row0 = zero_row0, key.condition = s->condition, key.epoch = ctx->epoch;
+        key.init = init, key.zero_row0 = zero_row0, key.condition = s->condition, key.rps = rps, key.epoch = ctx->epoch;
         if (s->gexec && key == s->gkey) {
             s->graph_replays++;
             EDMP_HIP_CHECK(hipGraphLaunch(s->gexec, st));
@@ -698,7 +743,7 @@ static int denoise_loop(edmp_ctx* ctx, const double* noise_dev, bool use_rng, ui
         EDMP_HIP_CHECK(hipStreamBeginCapture(st, hipStreamCaptureModeThreadLocal));
     }
     // the copy-out stays outside the graph: callers hand a fresh output buffer to every call
-    rc = enqueue_loop(ctx, noise_dev, use_rng, seed, B, guided, t_hi, t_lo, init, zero_row0, graph ? nullptr : X_out_dev);
+    rc = enqueue_loop(ctx, noise_dev, use_rng, seed, B, guided, t_hi, t_lo, init, zero_row0, graph ? nullptr : X_out_dev, rps);
     if (graph) {
         hipGraph_t g = nullptr;
         hipError_t e = hipStreamEndCapture(st, &g);
@@ -735,6 +780,36 @@ extern "C" int edmp_denoise_guided_segment_dev(edmp_ctx* ctx, const double* nois
                                                int t_hi, int t_lo, int init, int zero_row0, double* X_out_dev) {
     EDMP_REQUIRE(ctx && ctx->sampler && noise_dev, "edmp_denoise_guided_segment_dev: bad arguments");
     return denoise_loop(ctx, noise_dev, false, 0, B, start, goal, guided, t_hi, t_lo, init != 0, zero_row0, X_out_dev, false);
+}
+
+// a scene batch: S scenes x B rows as one (S*B, C, N) run; starts / goals may be NULL only when neither conditioning nor guided
+static int scenes_args(edmp_ctx* ctx, int S, int B, const double*& starts, const double*& goals, int guided, const double* zeros) {
+    EDMP_REQUIRE(ctx && ctx->sampler, "sampler not initialised");
+    EDMP_REQUIRE(S >= 1 && S <= EDMP_MAX_SCENES, "scene batch: %d scenes outside 1..%d", S, EDMP_MAX_SCENES);
+    EDMP_REQUIRE(B >= 1 && (!ctx->unet || (int64_t)S * B <= ctx->unet->max_batch), "scene batch: %d scenes x %d rows outside 1..%d rows (the model's max_batch)", S, B,
+                 ctx->unet ? ctx->unet->max_batch : 0);
+    if (!starts || !goals) {
+        EDMP_REQUIRE(!ctx->sampler->condition && !guided, "scene batch: starts and goals are required when conditioning or guiding");
+        starts = zeros;
+        goals = zeros;
+    }
+    return EDMP_OK;
+}
+
+extern "C" int edmp_denoise_scenes_dev(edmp_ctx* ctx, const double* noise_dev, int S, int B, const double* starts, const double* goals, int guided,
+                                       int t_stop, int zero_row0, double* X_out_dev) {
+    EDMP_REQUIRE(noise_dev && X_out_dev, "edmp_denoise_scenes_dev: null pointer");
+    static const double zeros[EDMP_MAX_SCENES * 7] = {};
+    if (int rc = scenes_args(ctx, S, B, starts, goals, guided, zeros)) return rc;
+    return denoise_loop(ctx, noise_dev, false, 0, S * B, starts, goals, guided, ctx->sampler->T, t_stop, true, zero_row0, X_out_dev, true, S);
+}
+
+extern "C" int edmp_denoise_scenes_segment_dev(edmp_ctx* ctx, const double* noise_dev, int S, int B, const double* starts, const double* goals, int guided,
+                                               int t_hi, int t_lo, int init, int zero_row0, double* X_out_dev) {
+    EDMP_REQUIRE(noise_dev, "edmp_denoise_scenes_segment_dev: null noise pointer");
+    static const double zeros[EDMP_MAX_SCENES * 7] = {};
+    if (int rc = scenes_args(ctx, S, B, starts, goals, guided, zeros)) return rc;
+    return denoise_loop(ctx, noise_dev, false, 0, S * B, starts, goals, guided, t_hi, t_lo, init != 0, zero_row0, X_out_dev, false, S);
 }
 
 extern "C" int edmp_sampler_set_allreduce(edmp_ctx* ctx, edmp_allreduce_fn fn, void* user) {

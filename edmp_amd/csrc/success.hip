@@ -292,6 +292,7 @@ using namespace edmp;
 
 extern "C" int edmp_scene_set_shapes(edmp_ctx* ctx, const int32_t* kind, int n_obstacles) {
     EDMP_REQUIRE(ctx && ctx->guide && ctx->guide->obb && ctx->guide->kind, "edmp_scene_set_shapes: call edmp_scene_set first");
+    EDMP_REFUSE_SCENE_BATCH(ctx->guide, "edmp_scene_set_shapes");
     Guide* g = ctx->guide;
     EDMP_REQUIRE(kind && n_obstacles == g->no, "edmp_scene_set_shapes: need %d kinds (one per obstacle of the scene)", g->no);
     for (int i = 0; i < n_obstacles; ++i) EDMP_REQUIRE(kind[i] == 0 || kind[i] == 1, "obstacle %d: kind must be 0 (cuboid) or 1 (cylinder)", i);
@@ -304,6 +305,7 @@ extern "C" int edmp_scene_set_shapes(edmp_ctx* ctx, const int32_t* kind, int n_o
 extern "C" int edmp_success_rows_dev(edmp_ctx* ctx, const double* X_dev, int B, int N, int substeps, const double* dh_f64, int32_t* ok_dev,
                                      int32_t* first_dev, int32_t* within_dev, int32_t* counts_host) {
     EDMP_REQUIRE(ctx && ctx->guide && ctx->guide->obb, "edmp_success_rows_dev: scene not set");
+    EDMP_REFUSE_SCENE_BATCH(ctx->guide, "edmp_success_rows_dev");
     Guide* g = ctx->guide;
     EDMP_REQUIRE(X_dev && B >= 1 && N >= 2 && substeps >= 1 && substeps <= 64, "edmp_success_rows_dev: need B >= 1, N >= 2, 1 <= substeps <= 64");
     EDMP_HIP_CHECK(hipSetDevice(ctx->device));

@@ -61,10 +61,11 @@ struct TailP {
     double* X = nullptr;          // state (B, C, N) f64
     const double* z = nullptr;    // noise of this step (B, C, N) f64 (rng == 0)
     float* xin = nullptr;         // next UNet input [B][N][8] f32 (finish)
-    const double* sg = nullptr;   // start (7) | goal (7)
+    const double* sg = nullptr;   // start (7) | goal (7) (scene batch: one pair per scene)
     int C = 0, N = 0;
     double c1 = 0.0, sqrt_alpha = 1.0, beta = 0.0;
     int zero_row0 = 0;
+    int rps = 0;           // scene batch: rows per scene (row b is row b % rps of scene b / rps); 0 = one scene
     unsigned long long seed = 0;
     int rng_step = 0;
     int cond = 0;
@@ -75,6 +76,7 @@ struct TailP {
 // eps[c] = final 1x1 conv of the UNet (final_conv.1, temporalunet.py:36) on the CIN activations hv of (sample b, waypoint l);
 // X <- (X - c1 eps)/sqrt(alpha) + beta z (diffusion.py:116-135); FINISH: X[:, :, 0] = start, X[:, :, -1] = goal
 // (diffusion.py:347-349) and the next UNet input.  i = b * N + l.  One code path for both callers: bit-identical results.
+// rps != 0 (a scene batch): row b conditions on its scene's start / goal (sg + 14 * (b / rps)) and Q3 zeroes the first row of every scene.
 // The state and noise values of the item are fetched by the caller (tail_fetch) - ahead of the work whose result hv is, so
 // that their memory latency is off the tail's critical path.
 __device__ __forceinline__ void tail_fetch(const double* __restrict__ X, const double* __restrict__ z, bool rng, int b, int l, int N, int C, double (&xv)[8],
@@ -95,10 +97,11 @@ template <bool FINISH, bool RNG, int CIN>
 __device__ __forceinline__ void head_psample_item(const float4 (&hv)[CIN / 4], const double (&xv)[8], const double (&zv)[8], int i, int b, int l,
                                                   const float* __restrict__ w, const float* __restrict__ bias, double* __restrict__ X,
                                                   float* __restrict__ eps_out, float* __restrict__ xin, const double* __restrict__ sg, int N, int C, double c1,
-                                                  double sqrt_alpha, double beta, int zero_row0, uint64_t seed, int rng_step, int cond) {
+                                                  double sqrt_alpha, double beta, int zero_row0, int rps, uint64_t seed, int rng_step, int cond) {
     float xo[8] = {0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f};
     float zr[8] = {0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f};
     if (RNG) rng_normal8(seed, (uint32_t)rng_step, (uint32_t)i, zr);
+    if (FINISH && rps) sg += 14 * (b / rps);
     float acc[8];
 #pragma unroll
     for (int co = 0; co < 8; ++co) acc[co] = (co < C) ? bias[co] : 0.0f;
@@ -122,7 +125,7 @@ __device__ __forceinline__ void head_psample_item(const float4 (&hv)[CIN / 4], c
         const size_t idx = ((size_t)b * C + co) * N + l;
         if (eps_out) eps_out[idx] = a;
         double zz = RNG ? (double)zr[co] : zv[co];
-        if (zero_row0 && b == 0) zz = 0.0;
+        if (zero_row0 && (rps ? b % rps : b) == 0) zz = 0.0;
         double x = (xv[co] - c1 * (double)a) / sqrt_alpha + beta * zz;
         if (FINISH) {
             if (cond && l == 0) x = sg[co];

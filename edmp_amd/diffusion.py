@@ -37,6 +37,21 @@ def _startgoal(start, goal, needed: bool):
     return out
 
 
+def place_scene_rows(dst: torch.Tensor, pieces) -> torch.Tensor:
+    """A scene batch's noise layout: ``pieces`` = S tensors (steps, B, C, N), scene s's draws; ``dst`` (steps, S*B, C, N) receives
+    piece s at rows [s*B, (s+1)*B) of every draw, by one strided copy per scene (on the current stream)."""
+    S = len(pieces)
+    steps, SB = dst.shape[0], dst.shape[1]
+    if S < 1 or SB % S:
+        raise ValueError(f"{SB} rows do not split over {S} scenes")
+    B = SB // S
+    for s, p in enumerate(pieces):
+        if tuple(p.shape) != (steps, B) + tuple(dst.shape[2:]):
+            raise ValueError(f"scene {s}: piece {tuple(p.shape)} does not fit ({steps}, {B}) + {tuple(dst.shape[2:])}")
+        dst[:, s * B:(s + 1) * B].copy_(p)
+    return dst
+
+
 class PinnedNoiseStream:
     """A (T+1, B, C, N) f64 noise stream in page-locked host memory that is still BEING DRAWN: the producer (infer_serial's feeder
     thread) fills it front to back and publishes how far it got; `Diffusion.denoise_guided(noise=stream)` uploads chunk after chunk as
@@ -366,6 +381,130 @@ class Diffusion:
         if return_device:
             return ctx.hand_over(out)
         return ctx.to_host(out)
+
+    def denoise_guided_scenes(self, model, batch, traj_len, num_channels, starts, goals, *, noise=None, t_stop=0, zero_row0=True, condition=True,
+                              chunk_steps=16, return_device=False, guided=True):
+        """S scenes of B rows each planned in ONE device-resident loop (edmp_denoise_scenes_dev): what S calls of denoise_guided, one per
+        scene of ``batch`` (a guide.SceneBatch), return - bit for bit - as an (S, B, C, N) f64 array.  ``starts`` / ``goals`` (S, 7).
+        ``noise``: None = the S streams from the global NumPy RandomState in scene order (the state ends where S denoise_guided calls leave
+        it); a list of S (T+1, B, C, N) arrays / device tensors; or a list of S pinned tensors / PinnedNoiseStreams, uploaded in chunks
+        beside the loop.  ``zero_row0``: quirk Q3 on row 0 of every scene.  ``guided=False``: the unguided loop, per-scene conditioning."""
+        from .guide import SceneBatch
+
+        ctx = self.ctx
+        if not isinstance(batch, SceneBatch):
+            raise ValueError("batch must be a guide.SceneBatch")
+        S, B = batch.n_scenes, batch.batch_size
+        if model.ctx is not ctx or batch.ctx is not ctx:
+            raise _capi.EdmpError("model, scene batch and diffuser must live on the same GPU")
+        if int(traj_len) != model.horizon or int(num_channels) != model.input_dim:
+            raise ValueError(f"traj_len/num_channels ({traj_len}, {num_channels}) do not match the model's ({model.horizon}, {model.input_dim})")
+        if S * B > model.max_batch:
+            raise ValueError(f"{S} scenes x {B} rows exceed the model's max_batch ({model.max_batch})")
+        if not 0 <= int(t_stop) < self.T:
+            raise ValueError(f"t_stop must lie in [0, {self.T}), got {t_stop}")
+        needed = bool(condition) or bool(guided)
+        if starts is None or goals is None:
+            if needed:
+                raise ValueError("starts and goals are required when conditioning or guiding")
+            starts = goals = np.zeros((S, 7))
+        sg = []
+        for name, v in (("starts", starts), ("goals", goals)):
+            a = np.ascontiguousarray(np.asarray(v, dtype=np.float64))
+            if a.shape != (S, 7):
+                raise ValueError(f"{name} must be ({S}, 7), got {a.shape}")
+            sg.append(a)
+        s_arr, g_arr = sg
+        if isinstance(noise, str):
+            raise _capi.EdmpError("the device noise mode (noise='device') has no scene batch: pass NumPy-stream noise")
+        if noise is not None and (not isinstance(noise, (list, tuple)) or len(noise) != S):
+            raise ValueError(f"noise must be None or a list of {S} per-scene streams")
+        Cc, N, T = int(num_channels), int(traj_len), self.T
+        per = (T + 1, B, Cc, N)
+        if noise is None:
+            # every scene's stream in scene order, as S serial calls draw them (each draws X_T and the steps down to t_stop + 1)
+            noise = [nprng.standard_normal((T + 1 - int(t_stop), B, Cc, N)) for _ in range(S)]
+            per = (T + 1 - int(t_stop), B, Cc, N)
+        streams = [x if isinstance(x, PinnedNoiseStream) else None for x in noise]
+        tens = [x.tensor if isinstance(x, PinnedNoiseStream) else x for x in noise]
+        pinned = [isinstance(x, torch.Tensor) and not x.is_cuda and x.is_pinned() and x.dtype == torch.float64 and x.is_contiguous() for x in tens]
+        if any(pinned) and not all(pinned):
+            raise ValueError("noise: either every scene's stream is pinned host memory or none is")
+        for k, x in enumerate(tens):
+            if tuple(x.shape) not in (per, (T + 1, B, Cc, N)):
+                raise ValueError(f"noise[{k}] must be f64 {(T + 1, B, Cc, N)}, got {tuple(x.shape)}")
+        ctx.ensure_sampler(self.T, self.variance_thresh)
+        model._bind()
+        if guided:
+            batch._bind()
+        _capi.check(ctx.lib.edmp_sampler_set_condition(ctx.h, 1 if condition else 0))
+        out = ctx.empty((S * B, Cc, N), torch.float64)
+        gflag, zr = 1 if guided else 0, 1 if zero_row0 else 0
+        if all(pinned):
+            # chunks of the S pinned streams (the single-scene plan: 1, 2, 4, ... chunk_steps steps, X_T with the first), each scene's
+            # piece uploaded by DMA and placed at rows [s*B, (s+1)*B) of the chunk by a strided device copy
+            per_step, keep = B * Cc * N, []
+            flats = [x.view(-1) for x in tens]
+            t_hi, off, k, first = T, 0, 1, True
+            try:
+                while t_hi > int(t_stop):
+                    kk = min(k, int(chunk_steps), t_hi - int(t_stop))
+                    steps = kk + (1 if first else 0)
+                    n = steps * per_step
+                    chunk = ctx.empty((steps, S * B, Cc, N), torch.float64)
+                    pieces = []
+                    for sc in range(S):
+                        if streams[sc] is not None:
+                            streams[sc].wait_until(off + n)
+                        pieces.append(ctx.upload_pinned({"t": flats[sc][off:off + n]}, n).view(steps, B, Cc, N))
+                    with torch.cuda.stream(ctx.stream):
+                        place_scene_rows(chunk, pieces)
+                    keep.append(chunk)
+                    last = t_hi - kk == int(t_stop)
+                    _capi.check(
+                        ctx.lib.edmp_denoise_scenes_segment_dev(ctx.h, ptr(chunk), S, B, _capi.as_pd(s_arr), _capi.as_pd(g_arr), gflag, t_hi, t_hi - kk,
+                                                                1 if first else 0, zr, ptr(out) if last else None),
+                        "edmp_denoise_scenes_segment_dev",
+                    )
+                    t_hi, off, k, first = t_hi - kk, off + n, k * 2, False
+            except BaseException:
+                try:  # nothing in flight may still read the chunks or the pinned streams when the error propagates
+                    ctx.sync()
+                except Exception:
+                    pass
+                raise
+            if return_device:
+                ctx.sync()
+                return out.view(S, B, Cc, N)
+            res = ctx.to_host(out)
+            del keep
+            return res.reshape(S, B, Cc, N)
+        steps = tens[0].shape[0]
+        if any(tuple(x.shape)[0] != steps for x in tens):
+            raise ValueError("noise: every scene's stream must have the same number of draws")
+        if any(isinstance(x, torch.Tensor) and x.dtype != torch.float64 for x in tens):
+            raise ValueError("noise: every scene's stream must be f64")
+        nd = ctx.empty((steps, S * B, Cc, N), torch.float64)
+        try:
+            pieces = [ctx.adopt(x) if (isinstance(x, torch.Tensor) and x.is_cuda) else ctx.to_dev(np.asarray(x, dtype=np.float64), torch.float64) for x in tens]
+            with torch.cuda.stream(ctx.stream):
+                place_scene_rows(nd, pieces)
+            if steps == T + 1:
+                _capi.check(ctx.lib.edmp_denoise_scenes_dev(ctx.h, ptr(nd), S, B, _capi.as_pd(s_arr), _capi.as_pd(g_arr), gflag, int(t_stop), zr, ptr(out)),
+                            "edmp_denoise_scenes_dev")
+            else:  # the NumPy stream of a run that stops at t_stop: X_T and T - t_stop steps
+                _capi.check(ctx.lib.edmp_denoise_scenes_segment_dev(ctx.h, ptr(nd), S, B, _capi.as_pd(s_arr), _capi.as_pd(g_arr), gflag, T, int(t_stop), 1, zr,
+                                                                    ptr(out)), "edmp_denoise_scenes_segment_dev")
+        except BaseException:
+            try:
+                ctx.sync()
+            except Exception:
+                pass
+            raise
+        if return_device:
+            ctx.sync()
+            return ctx.hand_over(out).view(S, B, Cc, N)
+        return ctx.to_host(out).reshape(S, B, Cc, N)
 
     def denoise(self, model, traj_len, num_channels, start=None, goal=None, condition=True, *, batch_size=1, noise=None):
         """diffusion.py:253-278 (unguided), batched; returns X[0] like the reference when batch_size == 1."""

@@ -243,3 +243,96 @@ class IntersectionVolumeGuide:
     def choose_best_trajectory(self, start, goal, trajectories):
         _, idx = self.row_swept_volumes(start, goal, trajectories)
         return trajectories[idx]
+
+
+def scene_batch_tables(scenes):
+    """Host side of a scene batch (edmp_scene_batch_set + ONE edmp_rows_set): ``scenes`` is a list of S dicts with one scene's
+    obstacle_config (no, 10), row_class (B,) int32, class clearance / expansion (G, T), method (B,), grad_norm (B,) and
+    guidance_schedule (B, T).  Returns the concatenation the C ABI takes: n_obstacles (S,) int32, obstacle_config (sum no, 10),
+    n_classes (S,) int32, clearance / expansion (sum G, T), and the S*B row arrays with row_class renumbered across the scenes
+    (scene s's classes follow scene s-1's), so that every row of scene s indexes one of scene s's own class schedules."""
+    if not 1 <= len(scenes) <= _capi.MAX_SCENES:
+        raise ValueError(f"a scene batch holds 1..{_capi.MAX_SCENES} scenes, got {len(scenes)}")
+    B = int(np.asarray(scenes[0]["row_class"]).shape[0])
+    T = int(np.asarray(scenes[0]["clearance"]).shape[1])
+    cls_off, row_class, n_obs, n_cls = 0, [], [], []
+    for s, sc in enumerate(scenes):
+        rc = np.asarray(sc["row_class"], dtype=np.int32).reshape(-1)
+        G = int(np.asarray(sc["clearance"]).shape[0])
+        no = int(np.asarray(sc["obstacle_config"]).shape[0])
+        if rc.shape[0] != B:
+            raise ValueError(f"scene {s} has {rc.shape[0]} rows, scene 0 has {B}: every scene of a batch has the same rows")
+        if np.asarray(sc["clearance"]).shape != (G, T) or np.asarray(sc["expansion"]).shape != (G, T):
+            raise ValueError(f"scene {s}: class schedules must be ({G}, {T})")
+        if not 1 <= no <= _capi.MAX_OBSTACLES:
+            raise ValueError(f"scene {s} has {no} obstacles, outside 1..{_capi.MAX_OBSTACLES}")
+        if rc.size and (rc.min() < 0 or rc.max() >= G):
+            raise ValueError(f"scene {s}: row classes outside 0..{G - 1}")
+        row_class.append(rc + cls_off)
+        n_obs.append(no)
+        n_cls.append(G)
+        cls_off += G
+
+    def cat(key, dtype, shape_tail=()):
+        return np.ascontiguousarray(np.concatenate([np.asarray(sc[key], dtype=dtype).reshape((-1,) + shape_tail) for sc in scenes]))
+
+    return dict(n_obstacles=np.asarray(n_obs, dtype=np.int32), obstacle_config=cat("obstacle_config", np.float64, (10,)),
+                n_classes=np.asarray(n_cls, dtype=np.int32), clearance=cat("clearance", np.float64, (T,)), expansion=cat("expansion", np.float64, (T,)),
+                row_class=np.ascontiguousarray(np.concatenate(row_class).astype(np.int32)), method=cat("method", np.float32),
+                grad_norm=cat("grad_norm", np.float64), guidance_schedule=cat("guidance_schedule", np.float64, (T,)))
+
+
+class SceneBatch:
+    """S per-scene guides (IntersectionVolumeGuide, one context, equal batch_size and T, one robot) as ONE guide object of the
+    library: scene s owns rows [s*B, (s+1)*B) of a (S*B, 7, N) run (Diffusion.denoise_guided_scenes).  The per-scene guides stay
+    what they were - the IK filter, row_swept_volumes, choose_best_trajectory and success_rows go through them; the batch lives in
+    its own resident slot, so switching between it and its scenes re-uploads nothing while both stay resident."""
+
+    def __init__(self, guides):
+        guides = list(guides)
+        if not 1 <= len(guides) <= _capi.MAX_SCENES:
+            raise ValueError(f"a scene batch holds 1..{_capi.MAX_SCENES} scenes, got {len(guides)}")
+        g0 = guides[0]
+        for k, g in enumerate(guides):
+            if not isinstance(g, IntersectionVolumeGuide):
+                raise ValueError(f"scene {k} is not an IntersectionVolumeGuide")
+            if g.ctx is not g0.ctx:
+                raise ValueError(f"scene {k} lives on another context than scene 0")
+            if g.batch_size != g0.batch_size or g.T != g0.T:
+                raise ValueError(f"scene {k}: batch_size / T ({g.batch_size}, {g.T}) differ from scene 0's ({g0.batch_size}, {g0.T})")
+            for name in ("_half", "_dh", "_sf"):
+                if not np.array_equal(getattr(g, name), getattr(g0, name)):
+                    raise ValueError(f"scene {k}: link / DH / static-frame tables differ from scene 0's (one robot per batch)")
+        self.guides, self.ctx, self.device = guides, g0.ctx, g0.device
+        self.n_scenes, self.batch_size, self.T = len(guides), g0.batch_size, g0.T
+        self.tables = scene_batch_tables([
+            dict(obstacle_config=g.obstacle_config, row_class=g.row_class, clearance=g._cls_clr, expansion=g._cls_exp,
+                 method=np.asarray(g.guide_cfgs["guidance_method"], dtype=np.float32).reshape(-1),
+                 grad_norm=np.asarray(g.guide_cfgs["grad_norm"], dtype=np.float64).reshape(-1), guidance_schedule=g._sched) for g in guides])
+        self._slot = new_slot_key()
+        self._bind()
+
+    def _bind(self):
+        ctx = self.ctx
+        if ctx.bound_guide is self:
+            return
+        have = ctx.lib.edmp_guide_slot(ctx.h, self._slot)
+        if have < 0:
+            _capi.check(have, "edmp_guide_slot")
+        if have == 1:
+            ctx.bound_guide = self
+            return
+        ctx.bound_guide = None
+        tb, g0 = self.tables, self.guides[0]
+        _capi.check(
+            ctx.lib.edmp_scene_batch_set(ctx.h, self.n_scenes, _capi.as_pi32(tb["n_obstacles"]), _capi.as_pd(tb["obstacle_config"]),
+                                         _capi.as_pi32(tb["n_classes"]), _capi.as_pd(tb["clearance"]), _capi.as_pd(tb["expansion"]), self.T,
+                                         _capi.as_pf(g0._half), _capi.as_pf(g0._dh), _capi.as_pf(g0._sf)),
+            "edmp_scene_batch_set",
+        )
+        _capi.check(
+            ctx.lib.edmp_rows_set(ctx.h, _capi.as_pi32(tb["row_class"]), _capi.as_pf(tb["method"]), _capi.as_pd(tb["grad_norm"]),
+                                  _capi.as_pd(tb["guidance_schedule"]), self.n_scenes * self.batch_size, self.T),
+            "edmp_rows_set",
+        )
+        ctx.bound_guide = self

@@ -32,6 +32,7 @@ extern "C" {
 #define EDMP_N_JOINTS 7
 #define EDMP_N_LINKS 9
 #define EDMP_MAX_OBSTACLES 64
+#define EDMP_MAX_SCENES 16
 
 typedef struct edmp_ctx edmp_ctx;
 
@@ -179,6 +180,33 @@ int edmp_denoise_guided_dev(edmp_ctx* ctx, const double* noise_dev, int B, const
  * X_out_dev may be NULL except for the last segment.  Used by Diffusion.denoise_guided to overlap NumPy's RandomState
  * (the reference's noise contract, ~0.85 s per 1024-row scene on the host) with the denoising itself. */
 int edmp_denoise_guided_segment_dev(edmp_ctx* ctx, const double* noise_dev, int B, const double* start, const double* goal,
+                                    int guided, int t_hi, int t_lo, int init, int zero_row0, double* X_out_dev);
+
+/* ---- scene batch: several scenes in one launch chain ------------------------------------------------------ */
+/* S scenes of B rows each run as ONE (S*B, C, N) state through the device-resident loop; scene s owns rows [s*B, (s+1)*B).  The
+ * reference plans one scene per Diffusion.denoise_guided call (infer_serial.py:108-157); its only coupling between rows is the
+ * whole-batch norm of lib/guide.py:629, which a scene batch forms PER SCENE, so every scene's rows equal its own serial run bit for bit.
+ *
+ * edmp_scene_batch_set replaces S calls of edmp_scene_set (lib/guide.py:13-43, 118-158) with ONE guide object in the current guide
+ * slot: n_obstacles (S,) int32 with 1..EDMP_MAX_OBSTACLES each; obstacle_config (sum n_obstacles, 10) f64, scene after scene;
+ * n_classes (S,) int32; clearance / expansion (sum n_classes, T) f64, scene after scene.  Classes are numbered across the scenes
+ * (scene s's follow scene s-1's) and each keeps its own scene's obstacle count.  link_half_extents, dh, static_frames as
+ * edmp_scene_set (one robot).  edmp_rows_set is then called ONCE for all S*B rows with row_class in that numbering; rows / S is the
+ * rows per scene (rows that do not split evenly over S are refused).  On a bound scene batch the single-scene loop (guided), the
+ * teacher-forced steps, the cost / gradient / best-trajectory / success entry points and edmp_scene_set_shapes are refused
+ * (EDMP_ERR_STATE): use one guide per scene for those. */
+int edmp_scene_batch_set(edmp_ctx* ctx, int S, const int32_t* n_obstacles, const double* obstacle_config, const int32_t* n_classes,
+                         const double* clearance, const double* expansion, int T, const float* link_half_extents, const float* dh,
+                         const float* static_frames);
+/* replaces S calls of Diffusion.denoise_guided (diffusion.py:300-356), one per scene, with one loop: noise (T+1, S*B, C, N) f64 on the
+ * device, noise[k] rows [s*B, (s+1)*B) = scene s's own draw k.  starts / goals (S,7) f64 host (may be NULL only when neither
+ * conditioning nor guided).  X_out (S*B, C, N) f64.  zero_row0 applies quirk Q3 to row 0 of EVERY scene.  guided = 0: the unguided
+ * loop with per-scene conditioning (no guide needed).  Guided needs a bound scene batch of S scenes and S*B rows.  The device noise
+ * mode and the all-reduce hook are refused (the hook sums ONE scalar). */
+int edmp_denoise_scenes_dev(edmp_ctx* ctx, const double* noise_dev, int S, int B, const double* starts, const double* goals, int guided,
+                            int t_stop, int zero_row0, double* X_out_dev);
+/* the same loop in segments, with the t_hi / t_lo / init contract of edmp_denoise_guided_segment_dev */
+int edmp_denoise_scenes_segment_dev(edmp_ctx* ctx, const double* noise_dev, int S, int B, const double* starts, const double* goals,
                                     int guided, int t_hi, int t_lo, int init, int zero_row0, double* X_out_dev);
 
 /* Device noise source — explicitly NOT the reference's NumPy RandomState stream (that contract is served by

@@ -20,7 +20,7 @@ from edmp_amd import dist as ED
 from edmp_amd import evaluation as EV
 from edmp_amd import guide_cfg as GC
 from edmp_amd.diffusion import Diffusion
-from edmp_amd.guide import IntersectionVolumeGuide
+from edmp_amd.guide import IntersectionVolumeGuide, SceneBatch
 from edmp_amd.scenes import SyntheticDataset
 from edmp_amd.temporalunet import TemporalUNet
 
@@ -131,7 +131,7 @@ def job_summary(results, world=1):
     return out
 
 
-def run(cfg_path, dataset=None, max_scenes=None, verbose=True, scenes_in_flight=1, shard_scenes=True):
+def run(cfg_path, dataset=None, max_scenes=None, verbose=True, scenes_in_flight=1, shard_scenes=True, scenes_per_launch=1):
     """The reference's scene loop (infer_serial.py:95-170).  Under ``torch.distributed.run`` (one process per GPU, extension: the
     reference is one process) the scenes are dealt round-robin to the ranks - scene i of the cfg's order goes to rank i mod world -
     and nothing is exchanged until `job_summary` adds the tallies up: scenes are independent problems, this is the problem set's natural
@@ -142,12 +142,24 @@ def run(cfg_path, dataset=None, max_scenes=None, verbose=True, scenes_in_flight=
     bench.py: two_scenes_in_flight).  Per-scene results are identical to the serial loop's: scenes are prepared in order on the
     calling thread and each scene's noise is drawn - by ONE background feeder thread, a whole scene ahead, serial loop included - from the
     global NumPy RandomState in scene order.  While a run is in progress nothing else may draw from (or seed) the global RandomState: the
-    feeder reads and advances it from its own thread (np.random.get_state / set_state are not atomic)."""
+    feeder reads and advances it from its own thread (np.random.get_state / set_state are not atomic).
+
+    ``scenes_per_launch`` = k > 1 (an extension) plans k consecutive scenes of this rank in ONE device-resident loop
+    (Diffusion.denoise_guided_scenes over a guide.SceneBatch): each scene is prepared in order (guide, IK filter), the group is planned
+    in one call, then every scene's best row and success are picked from its own rows.  Per-scene results equal the serial loop's bit
+    for bit; the last group may be smaller.  The model is built for k * rows, and the feeder keeps 2k whole-scene pinned buffers
+    (k = 2 at 1024 rows: 4 x 734 MB page-locked).  Each result carries `scenes_in_launch`; its `denoise_s` is the GROUP's time.
+    Not combined with scenes_in_flight > 1."""
     from concurrent.futures import ThreadPoolExecutor
 
     from edmp_amd.runtime import get_context, lane_context
 
     t_enter = time.time()
+    kl = int(scenes_per_launch)
+    if kl < 1:
+        raise ValueError(f"scenes_per_launch must be >= 1, got {scenes_per_launch}")
+    if kl > 1 and int(scenes_in_flight) > 1:
+        raise ValueError("scenes_per_launch > 1 and scenes_in_flight > 1 do not combine: choose one")
     benchmark_cfg = GC.load_yaml(cfg_path)
     rank, world, device = _ranks(benchmark_cfg["model"]["device"]) if shard_scenes else (0, 1, benchmark_cfg["model"]["device"])
     traj_len = benchmark_cfg["model"]["traj_len"]
@@ -182,7 +194,7 @@ def run(cfg_path, dataset=None, max_scenes=None, verbose=True, scenes_in_flight=
     for j in range(k):
         ctx = lane_context(base, j)  # lane 0 = the device's context; further lanes are cached per (device, lane), not re-created per call
         lanes.append((Diffusion(T=T, device=ctx), TemporalUNet(model_name=model_name, input_dim=num_channels, time_dim=32, dims=(32, 64, 128, 256, 512, 512),
-                                                                device=ctx, max_batch=total_batch_size)))
+                                                                device=ctx, max_batch=total_batch_size * kl)))
 
     def plan(lane, guide, start_joints, goal_joints, noise, meta, t0):
         diffuser, denoiser = lanes[lane]
@@ -242,9 +254,65 @@ def run(cfg_path, dataset=None, max_scenes=None, verbose=True, scenes_in_flight=
             i += 1
     # the noise of EVERY scene comes from the feeder thread, one whole scene ahead (round 6: the serial loop too - drawing chunk by chunk
     # beside the GPU had no margin left once a reverse step took 0.92 ms: a slower host capped the scene loop, BENCH_r05 0.947 x value)
-    feeder = _NoiseFeeder(base, len(mine), (T + 1, total_batch_size, num_channels, traj_len), k + 1) if mine else None
+    feeder = _NoiseFeeder(base, len(mine), (T + 1, total_batch_size, num_channels, traj_len), 2 * kl if kl > 1 else k + 1) if mine else None
     run.last_setup_s = time.time() - t_enter  # config, dataset, model load / upload: per run, not per scene
+    def prepare(lane, scene_type, scene_num):
+        """guide + IK filter of one scene (infer_serial.py:108-129): (guide, start, goal, meta, t0)"""
+        obstacle_config, _, _, num_cuboids, num_cylinders, start_joints, all_ik_goals = dataset.fetch_data(scene_num=scene_num, scene_type=scene_type)
+        t0 = time.time()
+        kinds = np.concatenate([np.zeros(int(num_cuboids), dtype=np.int32), np.ones(int(num_cylinders), dtype=np.int32)])
+        guide = IntersectionVolumeGuide(obstacle_config=obstacle_config, device=lanes[lane][0].ctx, guide_cfgs=guide_cfgs, batch_size=total_batch_size,
+                                        obstacle_kinds=kinds, mesh_dir=benchmark_cfg["model"].get("mesh_dir"))
+        t1 = time.time()
+        volumes = guide.cost(torch.tensor(all_ik_goals.reshape((-1, 7, 1))), 0, batch_size=all_ik_goals.shape[0]).sum(axis=(1, 2)).cpu().numpy()
+        indices = np.argsort(volumes)
+        goal_joints = all_ik_goals[indices][volumes[indices] < np.min(volumes) + 0.0008]
+        goal_joints = goal_joints[np.argmin(np.linalg.norm(start_joints - goal_joints, axis=1))]
+        meta = dict(scene_type=scene_type, scene_num=scene_num, timings=dict(guide_ctor_s=t1 - t0, ik_filter_s=time.time() - t1))
+        return guide, start_joints, goal_joints, meta, t0
+
+    def plan_group(group):
+        """k prepared scenes in one launch chain; per scene: best row, success, the serial loop's result keys"""
+        diffuser, denoiser = lanes[0]
+        t_w = time.time()
+        streams = [feeder.next() for _ in group]
+        noise_wait = time.time() - t_w
+        batch = SceneBatch([g[0] for g in group])
+        ta = time.time()
+        X = diffuser.denoise_guided_scenes(denoiser, batch, traj_len, num_channels, np.stack([g[1] for g in group]), np.stack([g[2] for g in group]),
+                                           noise=streams, condition=True)
+        tb = time.time()
+        for st in streams:
+            feeder.recycle(st)  # (the call returned host trajectories: every upload out of the buffers is done)
+        out = []
+        for s, (guide, start_joints, goal_joints, meta, t0) in enumerate(group):
+            tm = dict(meta.pop("timings"))
+            tm["noise_wait_s"] = noise_wait
+            tc = time.time()
+            trajectories = X[s]
+            vols, idx = guide.row_swept_volumes(start_joints, goal_joints, trajectories)
+            trajectory = trajectories[idx]
+            tm["denoise_s"] = tb - ta  # the whole group's loop
+            tm["denoise_s_is"] = f"group of {len(group)} scenes"
+            tm["best_trajectory_s"] = time.time() - tc
+            td = time.time()
+            chk = guide.success_rows(trajectories)
+            tm["success_check_s"] = time.time() - td
+            t_plan = time.time() - t0
+            out.append(dict(**meta, timings=tm, scenes_in_launch=len(group), best_row=int(idx), swept_volume=float(vols[idx]),
+                            success_proxy=int(chk["collision_free"][idx]), success_strict=int(chk["ok"][idx]), rows_collision_free=chk["rows_collision_free"],
+                            rows_ok=chk["rows_ok"], rows=chk["rows"], aabb_volume_zero=bool(ED.geometric_success(float(vols[idx]), trajectory)),
+                            first_collision_waypoint=int(chk["first"][idx]), path_length=EV.path_lengths(trajectory), sparc=EV.smoothness(trajectory),
+                            planning_time_s=t_plan, scene_wall_s=time.time() - t0, trajectory=trajectory))
+        return out
+
     try:
+        if kl > 1:
+            for g0 in range(0, len(mine), kl):
+                group = [prepare(0, scene_type, scene_num) for _, scene_type, scene_num in mine[g0:g0 + kl]]
+                for r in plan_group(group):
+                    collect(r)
+            mine = []  # (planned above)
         with ThreadPoolExecutor(max_workers=k) as pool:
             for i, scene_type, scene_num in mine:
                 lane = (i // world) % k
@@ -291,6 +359,8 @@ def main(argv=None):
     parser = argparse.ArgumentParser(prog="Benchmarking Diffusion", description="Benchmarking with IK on Test sets")
     parser.add_argument("-c", "--cfg_path", type=str, default="./configs/cfg_c1_plumbing.yaml")
     parser.add_argument("--scenes-in-flight", type=int, default=1, help="plan this many scenes concurrently on the GPU (extension; the reference is serial)")
+    parser.add_argument("--scenes-per-launch", type=int, default=1, help="plan this many consecutive scenes in one device-resident loop (extension; "
+                                                                             "the model is built for that many times the rows)")
     parser.add_argument("--max-scenes", type=int, default=None, help="stop after this many scenes of the cfg's order (all ranks together)")
     parser.add_argument("--seed", type=int, default=None, help="np.random.seed(seed + rank) before the loop (the reference never seeds; for repeatable runs)")
     parser.add_argument("--results-json", type=str, default=None, help="write this rank's per-scene results (without the trajectories) and the job summary "
@@ -299,7 +369,7 @@ def main(argv=None):
     rank = int(os.environ.get("RANK", "0"))
     if args.seed is not None:
         np.random.seed(args.seed + rank)
-    results = run(args.cfg_path, scenes_in_flight=args.scenes_in_flight, max_scenes=args.max_scenes)
+    results = run(args.cfg_path, scenes_in_flight=args.scenes_in_flight, max_scenes=args.max_scenes, scenes_per_launch=args.scenes_per_launch)
     if args.results_json:
         import json
 
