@@ -1,4 +1,4 @@
-"""Result evaluation: plan success over the whole batch (on the GPU) and trajectory metrics (host, like the reference's).
+"""Result evaluation: plan success over the whole batch (on the GPU) and trajectory metrics (host like the reference's, and whole batches on the GPU).
 
 Success.  The reference scores a plan by executing it in pybullet (`RobotEnvironment.benchmark_trajectory`,
 lib/environment.py:632-680: position control through the waypoints, contact query `check_collisions` :591-608 against
@@ -9,7 +9,9 @@ guide's conservative world-AABB overlap — and evaluated for every row of the b
 reported as such.  There is no host fallback: the checker of the kernel lives in oracle/success_oracle.py (tests only).
 
 Metrics.  lib/metrics.py:11-125 (`MetricsCalculator`, host NumPy / torch-CPU in the reference too, never called by its
-driver): path length and SPARC smoothness, pinned to the reference by tests/golden/g13_metrics.npz.
+driver): path length and SPARC smoothness, pinned to the reference by tests/golden/g13_metrics.npz.  `path_lengths`, `sparc`,
+`smoothness_metric` score ONE trajectory on the host; `batch_metrics` scores every row of a batch on the GPU (edmp_metrics_rows_dev,
+csrc/metrics.hip) and is checked against them; `ensemble_report` turns volumes, success flags and metrics into the per-guide table.
 """
 from __future__ import annotations
 
@@ -113,3 +115,86 @@ def smoothness_metric(trajectory, dt: float = 0.1) -> tuple:
 def smoothness(trajectory, dt: float = 0.1) -> float:
     """joint-space SPARC of a (7, N) trajectory (first component of smoothness_metric)."""
     return smoothness_metric(trajectory, dt)[0]
+
+
+METRIC_KEYS = ("joint_path_length", "ee_path_length", "joint_sparc", "ee_sparc")  # row order of edmp_metrics_rows_dev's (4, B) output
+
+
+def metrics_rows_on(ctx, trajectories, dt: float = 0.1, return_device: bool = False) -> dict:
+    """edmp_metrics_rows_dev on the context `ctx` (runtime.Context): see batch_metrics."""
+    import ctypes as C
+
+    import torch
+
+    from . import _capi
+    from .runtime import ptr
+
+    if isinstance(trajectories, torch.Tensor) and trajectories.is_cuda:
+        X = ctx.adopt(trajectories.to(torch.float64).contiguous())
+    else:
+        X = ctx.to_dev(np.asarray(trajectories, dtype=np.float64), torch.float64)
+    if X.dim() != 3 or X.shape[1] != 7:
+        raise ValueError(f"trajectories must be (B, 7, N), got {tuple(X.shape)}")
+    B, N = X.shape[0], X.shape[2]
+    out = ctx.empty((4, B), torch.float64)
+    dh = np.ascontiguousarray(franka.dh_table_f64())
+    _capi.check(ctx.lib.edmp_metrics_rows_dev(ctx.h, ptr(X), B, N, C.c_double(float(dt)), _capi.as_pd(dh), ptr(out)), "edmp_metrics_rows_dev")
+    if return_device:
+        X.record_stream(ctx.stream)  # (the kernel may still be reading it when the caller drops the tensor)
+        ctx.hand_over(out)
+        return {k: out[i] for i, k in enumerate(METRIC_KEYS)}
+    h = ctx.to_host(out)
+    return {k: h[i].copy() for i, k in enumerate(METRIC_KEYS)}
+
+
+def batch_metrics(trajectories, device="cuda:0", dt: float = 0.1, return_device: bool = False) -> dict:
+    """The reference's result metrics (lib/metrics.py:11-125, MetricsCalculator) for EVERY row of a batch in one kernel
+    (edmp_metrics_rows_dev, csrc/metrics.hip): trajectories (B, 7, N) ndarray or device tensor, 3 <= N <= 129 -> dict of four (B,)
+    float64 arrays joint_path_length, ee_path_length, joint_sparc, ee_sparc (device tensors with return_device).  Row b equals
+    path_lengths(trajectories[b]) and smoothness_metric(trajectories[b], dt) - the single-trajectory host functions above, which stay
+    the yardstick - to 1e-9; a row whose speed profile is not finite gets SPARC = NaN where the host functions raise.  Needs no scene
+    and no guide.  Runs on the GPU only: there is no host fallback."""
+    from .runtime import get_context
+
+    return metrics_rows_on(get_context(device), trajectories, dt, return_device)
+
+
+def ensemble_report(guides, batch_size_per_guide, volumes, success, metrics) -> list:
+    """Which guide of the ensemble produced collision-free, short, smooth plans: one entry per guide slice of the batch.  Guide i of
+    `guides` (the run cfg's guide numbers) owns rows [i * bpg, (i + 1) * bpg) (infer_serial.py:70-91); `batch_size_per_guide` may also
+    be a sequence of per-guide row counts (the `total_rows` extension deals uneven blocks).  volumes (B,) = row_swept_volumes' output,
+    success = success_rows' dict (collision_free, ok), metrics = batch_metrics' dict; host arrays.  Entry: guide, first_row, rows,
+    rows_collision_free, rows_ok, best_row (batch index of the slice's first minimum swept volume), min_swept_volume, and mean / median
+    (dicts over the four metrics) of the slice's collision-free rows, None when it has none."""
+    guides = [int(g) for g in guides]
+    counts = [int(batch_size_per_guide)] * len(guides) if np.ndim(batch_size_per_guide) == 0 else [int(c) for c in batch_size_per_guide]
+    vol = np.asarray(volumes)
+    free, ok = np.asarray(success["collision_free"], dtype=bool), np.asarray(success["ok"], dtype=bool)
+    met = {k: np.asarray(metrics[k], dtype=np.float64) for k in METRIC_KEYS}
+    if len(counts) != len(guides) or sum(counts) != vol.shape[0] or any(a.shape != vol.shape for a in (free, ok, *met.values())):
+        raise ValueError(f"ensemble_report: {len(guides)} guides with rows {counts} do not tile (B,) = {vol.shape} arrays")
+    out, r0 = [], 0
+    for g, cnt in zip(guides, counts):
+        sl = slice(r0, r0 + cnt)
+        keep = free[sl]
+        some = bool(keep.any())
+        out.append(dict(guide=g, first_row=r0, rows=cnt, rows_collision_free=int(keep.sum()), rows_ok=int(ok[sl].sum()),
+                        best_row=(r0 + int(np.argmin(vol[sl]))) if cnt else None, min_swept_volume=float(np.min(vol[sl])) if cnt else None,
+                        mean={k: float(np.mean(met[k][sl][keep])) for k in METRIC_KEYS} if some else None,
+                        median={k: float(np.median(met[k][sl][keep])) for k in METRIC_KEYS} if some else None))
+        r0 += cnt
+    return out
+
+
+def format_ensemble_report(report) -> list:
+    """one printable line per entry of ensemble_report"""
+    lines = []
+    for e in report:
+        line = (f"  guide {e['guide']:>3}: rows {e['first_row']}..{e['first_row'] + e['rows'] - 1}, collision-free {e['rows_collision_free']}/{e['rows']}, "
+                f"ok {e['rows_ok']}/{e['rows']}, best row {e['best_row']} (swept volume {e['min_swept_volume']:.4g})")
+        if e["mean"] is not None:
+            m, d = e["mean"], e["median"]
+            line += (f"; collision-free rows: joint path {m['joint_path_length']:.3f} (median {d['joint_path_length']:.3f}), ee path {m['ee_path_length']:.3f} "
+                     f"({d['ee_path_length']:.3f}), joint SPARC {m['joint_sparc']:.3f} ({d['joint_sparc']:.3f}), ee SPARC {m['ee_sparc']:.3f} ({d['ee_sparc']:.3f})")
+        lines.append(line)
+    return lines

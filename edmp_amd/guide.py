@@ -240,8 +240,49 @@ class IntersectionVolumeGuide:
             out.update(ok=f[0].astype(bool), first=f[1].copy(), within=f[2].astype(bool), collision_free=f[1] < 0)
         return out
 
-    def choose_best_trajectory(self, start, goal, trajectories):
-        _, idx = self.row_swept_volumes(start, goal, trajectories)
+    def metrics_rows(self, trajectories, dt: float = 0.1, return_device: bool = False):
+        """evaluation.batch_metrics on this guide's context: path lengths and SPARC of EVERY row (edmp_metrics_rows_dev; stands for
+        lib/metrics.py:11-125) -> dict of four (B,) f64 arrays joint_path_length, ee_path_length, joint_sparc, ee_sparc."""
+        from .evaluation import metrics_rows_on
+
+        return metrics_rows_on(self.ctx, trajectories, dt, return_device)
+
+    def select_row(self, start, goal, trajectories, prefer=None, volume_trust_region: float = 0.0008):
+        """The row choose_best_trajectory returns, as (index, volumes (B,) f32, metrics dict or None).  prefer=None: the reference's
+        rule, the first arg-min of the t = 0 swept volume (lib/guide.py:637-653) - row_swept_volumes' index, nothing else is launched.
+        prefer="shortest" / "smoothest": the rule of the reference's IK-goal filter (infer_serial.py:119-129) applied to the plans -
+        among the rows whose volume lies within `volume_trust_region` of the minimum, the one with the smallest joint path length /
+        the joint SPARC closest to 0 (edmp_select_row_dev on edmp_metrics_rows_dev's output; volumes, metrics and the pick stay on the
+        device, one index comes back)."""
+        if prefer is None:
+            vols, idx = self.row_swept_volumes(start, goal, trajectories)
+            return idx, vols, None
+        if prefer not in ("shortest", "smoothest"):
+            raise ValueError(f"prefer must be None, 'shortest' or 'smoothest', got {prefer!r}")
+        self._bind()
+        ctx = self.ctx
+        if isinstance(trajectories, torch.Tensor) and trajectories.is_cuda:
+            X = ctx.adopt(trajectories.to(torch.float64).contiguous())
+        else:
+            X = ctx.to_dev(np.asarray(trajectories, dtype=np.float64), torch.float64)
+        B, N = X.shape[0], X.shape[2]
+        s = np.ascontiguousarray(np.asarray(start, dtype=np.float64).reshape(7))
+        g = np.ascontiguousarray(np.asarray(goal, dtype=np.float64).reshape(7))
+        vols = ctx.empty((B,), torch.float32)
+        _capi.check(ctx.lib.edmp_row_swept_volumes_dev(ctx.h, ptr(X), B, N, _capi.as_pd(s), _capi.as_pd(g), ptr(vols), None), "edmp_row_swept_volumes_dev")
+        met = self.metrics_rows(X, return_device=True)
+        with torch.cuda.stream(ctx.stream):
+            key = met["joint_path_length"] if prefer == "shortest" else torch.neg(met["joint_sparc"])  # SPARC <= 0: closest to 0 = largest
+        idx = C.c_int()
+        _capi.check(ctx.lib.edmp_select_row_dev(ctx.h, ptr(vols), ptr(key), B, C.c_double(float(volume_trust_region)), C.byref(idx)), "edmp_select_row_dev")
+        with torch.cuda.stream(ctx.stream):
+            m = torch.stack([met[k] for k in met])
+        mh = ctx.to_host(m)
+        return idx.value, ctx.to_host(vols), {k: mh[i].copy() for i, k in enumerate(met)}
+
+    def choose_best_trajectory(self, start, goal, trajectories, *, prefer=None, volume_trust_region: float = 0.0008):
+        """lib/guide.py:637-653; the keyword `prefer` (an extension, see select_row) breaks the tie among near-minimal rows."""
+        idx, _, _ = self.select_row(start, goal, trajectories, prefer=prefer, volume_trust_region=volume_trust_region)
         return trajectories[idx]
 
 

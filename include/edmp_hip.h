@@ -145,6 +145,24 @@ int edmp_scene_set_shapes(edmp_ctx* ctx, const int32_t* kind, int n_obstacles);
 int edmp_success_rows_dev(edmp_ctx* ctx, const double* X_dev, int B, int N, int substeps, const double* dh_f64, int32_t* ok_dev,
                           int32_t* first_dev, int32_t* within_dev, int32_t* counts_host);
 
+/* ---- result metrics of a whole batch (csrc/metrics.hip) ----------------------------------------------------------- */
+/* stands for MetricsCalculator.path_length_metric and .smoothness_metric / .sparc (lib/metrics.py:32-45, 11-30, 47-125; end effector
+ * through get_end_effector_transform, lib/guide.py:100-116: the seven joint rows and the three fixed rows of the modified-DH table),
+ * for EVERY row of a batch instead of one trajectory on the host: X (B,7,N) f64 on the device, 3 <= N <= 129, sample time dt > 0
+ * (SPARC at fs = 1 / dt with the reference's defaults padlevel 4, fc 10, amp_th 0.05).  out (4,B) f64 on the device: joint path length,
+ * end-effector path length, joint SPARC, end-effector SPARC.  A row whose speed profile holds a NaN or an infinity gets SPARC = NaN
+ * (the reference raises there); its path lengths follow IEEE.  All f64, every sum in one fixed order: bit-identical between runs and
+ * independent of B and of the row's position.  Needs a context only - no scene, no guide - so it also serves the S*B rows of a scene
+ * batch in one call.  dh_f64 (host, optional): (7,4) f64 rows [a, d, cos(alpha), sin(alpha)]; NULL = the Franka table of lib/guide.py:29-35.
+ * Does not synchronise. */
+int edmp_metrics_rows_dev(edmp_ctx* ctx, const double* X_dev, int B, int N, double dt, const double* dh_f64, double* out_dev);
+/* choose_best_trajectory's arg-min (lib/guide.py:637-653) widened by the rule of the reference's IK-goal filter (infer_serial.py:119-129:
+ * keep everything within volume_trust_region of the minimum, then take the nearest): volumes (B,) f32 and key (B,) f64 on the device.
+ * m = edmp_argmin_dev's index (first minimum, NaN is the smallest).  If volumes[m] is NaN the answer is m.  Otherwise the candidates are
+ * the rows with (double)v_b < (double)v_m + trust_region and the answer is the candidate with the smallest FINITE key, first index on
+ * ties; m if no candidate has a finite key.  *index_host is written on the host (synchronises). */
+int edmp_select_row_dev(edmp_ctx* ctx, const float* volumes_dev, const double* key_dev, int B, double trust_region, int* index_host);
+
 /* ---- sampler: Diffusion ------------------------------------------------------------------------------ */
 /* replaces Diffusion.__init__/schedule_variance (diffusion/diffusion.py:10-20, 37-49) */
 int edmp_sampler_init(edmp_ctx* ctx, int T, double variance_thresh);

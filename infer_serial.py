@@ -131,7 +131,7 @@ def job_summary(results, world=1):
     return out
 
 
-def run(cfg_path, dataset=None, max_scenes=None, verbose=True, scenes_in_flight=1, shard_scenes=True, scenes_per_launch=1):
+def run(cfg_path, dataset=None, max_scenes=None, verbose=True, scenes_in_flight=1, shard_scenes=True, scenes_per_launch=1, ensemble_report=False, prefer=None):
     """The reference's scene loop (infer_serial.py:95-170).  Under ``torch.distributed.run`` (one process per GPU, extension: the
     reference is one process) the scenes are dealt round-robin to the ranks - scene i of the cfg's order goes to rank i mod world -
     and nothing is exchanged until `job_summary` adds the tallies up: scenes are independent problems, this is the problem set's natural
@@ -149,7 +149,14 @@ def run(cfg_path, dataset=None, max_scenes=None, verbose=True, scenes_in_flight=
     in one call, then every scene's best row and success are picked from its own rows.  Per-scene results equal the serial loop's bit
     for bit; the last group may be smaller.  The model is built for k * rows, and the feeder keeps 2k whole-scene pinned buffers
     (k = 2 at 1024 rows: 4 x 734 MB page-locked).  Each result carries `scenes_in_launch`; its `denoise_s` is the GROUP's time.
-    Not combined with scenes_in_flight > 1."""
+    Not combined with scenes_in_flight > 1.
+
+    ``ensemble_report`` (an extension) scores EVERY row of each scene's batch on the GPU (evaluation.batch_metrics: the path lengths and
+    SPARC of lib/metrics.py, which the reference's driver never calls) and adds `ensemble` to the scene's result: one entry per guide of
+    the cfg with its rows' collision-free / ok counts, best row, minimum swept volume and the mean / median metrics of its collision-free
+    rows (evaluation.ensemble_report).  ``prefer`` = "shortest" | "smoothest" (an extension) picks the plan with
+    IntersectionVolumeGuide.select_row - among the rows within the trust region of the minimum swept volume, the shortest joint path /
+    the smoothest - instead of the first arg-min, and records `prefer` in the result.  Without either the results are the reference-shaped ones."""
     from concurrent.futures import ThreadPoolExecutor
 
     from edmp_amd.runtime import get_context, lane_context
@@ -183,6 +190,20 @@ def run(cfg_path, dataset=None, max_scenes=None, verbose=True, scenes_in_flight=
                                    num_scenes_per_type=benchmark_cfg["dataset"].get("num_scenes_per_type", 1))
     guide_cfgs = GC.guide_cfgs_from_run_cfg(benchmark_cfg, base_dir=os.path.dirname(os.path.abspath(cfg_path)) + "/..")
     total_batch_size = guide_cfgs["total_batch_size"]
+    if prefer not in (None, "shortest", "smoothest"):
+        raise ValueError(f"prefer must be None, 'shortest' or 'smoothest', got {prefer!r}")
+    guide_numbers = [int(n) for n in benchmark_cfg["guide"]["guides"]]
+    guide_rows = GC.split_rows(int(benchmark_cfg["guide"]["total_rows"]), len(guide_numbers)) if benchmark_cfg["guide"].get("total_rows") else guide_cfgs["batch_size_per_guide"]
+
+    def extras(vols, chk, met):
+        """the keys the two extensions add to a scene's result (none without them)"""
+        out = {}
+        if prefer is not None:
+            out["prefer"] = prefer
+        if ensemble_report:
+            out["ensemble"] = EV.ensemble_report(guide_numbers, guide_rows, vols, chk, met)
+        return out
+
     model_name = benchmark_cfg["model"]["model_dir"] + "TemporalUNetModel" + str(T) + "_N" + str(traj_len)
     if not os.path.exists(model_name):
         if verbose and rank == 0:
@@ -212,10 +233,14 @@ def run(cfg_path, dataset=None, max_scenes=None, verbose=True, scenes_in_flight=
         tb = time.time()
         if pinned is not None:
             feeder.recycle(pinned)  # (denoise_guided returned host trajectories: the upload out of the buffer is long done)
-        vols, idx = guide.row_swept_volumes(start_joints, goal_joints, trajectories)
+        idx, vols, met = guide.select_row(start_joints, goal_joints, trajectories, prefer=prefer)
         trajectory = trajectories[idx]
         t_plan = time.time() - t0
         tm["denoise_s"], tm["best_trajectory_s"] = tb - ta, time.time() - tb
+        if ensemble_report and met is None:
+            te = time.time()
+            met = guide.metrics_rows(trajectories)
+            tm["batch_metrics_s"] = time.time() - te
         # success: pybullet execution (lib/environment.py:632-680) is unavailable -> exact link-box vs cuboid / cylinder
         # check along the interpolated trajectory, for EVERY row of the batch in one kernel (csrc/success.hip); the
         # scene's success is the chosen row's flag (infer_serial.py:165-168) under the reference's rule - no contact;
@@ -227,7 +252,8 @@ def run(cfg_path, dataset=None, max_scenes=None, verbose=True, scenes_in_flight=
         return dict(**meta, timings=tm, best_row=int(idx), swept_volume=float(vols[idx]), success_proxy=int(chk["collision_free"][idx]), success_strict=int(chk["ok"][idx]),
                     rows_collision_free=chk["rows_collision_free"], rows_ok=chk["rows_ok"], rows=chk["rows"],
                     aabb_volume_zero=bool(ED.geometric_success(float(vols[idx]), trajectory)), first_collision_waypoint=int(chk["first"][idx]),
-                    path_length=EV.path_lengths(trajectory), sparc=EV.smoothness(trajectory), planning_time_s=t_plan, scene_wall_s=time.time() - t0, trajectory=trajectory)
+                    path_length=EV.path_lengths(trajectory), sparc=EV.smoothness(trajectory), planning_time_s=t_plan, scene_wall_s=time.time() - t0, trajectory=trajectory,
+                    **extras(vols, chk, met))
 
     t_success, t_strict, i, results, pending = 0, 0, 0, [], []
 
@@ -242,6 +268,8 @@ def run(cfg_path, dataset=None, max_scenes=None, verbose=True, scenes_in_flight=
             print(("" if world == 1 else f"[rank {rank}] ") + f"Scene {len(results)} ({r['scene_type']}/{r['scene_num']}): planning {r['planning_time_s']:.2f} s, best row {r['best_row']}, swept volume "
                   f"{r['swept_volume']:.4g}, geometric success (proxy, collision-free) {r['success_proxy']} ({r['rows_collision_free']}/{r['rows']} rows of the batch); "
                   f"also within the joint limits {r['success_strict']} ({r['rows_ok']}/{r['rows']})   running {t_success}/{len(results)} (strict {t_strict}/{len(results)})")
+            for line in EV.format_ensemble_report(r.get("ensemble", ())):
+                print(line)
 
     # this rank's scenes, in the cfg's order (scene i of that order belongs to rank i mod world)
     mine = []
@@ -284,13 +312,21 @@ def run(cfg_path, dataset=None, max_scenes=None, verbose=True, scenes_in_flight=
         tb = time.time()
         for st in streams:
             feeder.recycle(st)  # (the call returned host trajectories: every upload out of the buffers is done)
+        all_met = None
+        if ensemble_report:  # ONE kernel over the S * B rows of the group (the metrics need no scene); per-scene slices below
+            te = time.time()
+            all_met = EV.batch_metrics(np.asarray(X).reshape((-1,) + tuple(np.shape(X)[-2:])), device=diffuser.ctx)
+            t_met = time.time() - te
         out = []
         for s, (guide, start_joints, goal_joints, meta, t0) in enumerate(group):
             tm = dict(meta.pop("timings"))
             tm["noise_wait_s"] = noise_wait
             tc = time.time()
             trajectories = X[s]
-            vols, idx = guide.row_swept_volumes(start_joints, goal_joints, trajectories)
+            idx, vols, met = guide.select_row(start_joints, goal_joints, trajectories, prefer=prefer)
+            if all_met is not None:
+                met = {k: v[s * total_batch_size:(s + 1) * total_batch_size] for k, v in all_met.items()}
+                tm["batch_metrics_s"] = t_met  # the whole group's call
             trajectory = trajectories[idx]
             tm["denoise_s"] = tb - ta  # the whole group's loop
             tm["denoise_s_is"] = f"group of {len(group)} scenes"
@@ -303,7 +339,7 @@ def run(cfg_path, dataset=None, max_scenes=None, verbose=True, scenes_in_flight=
                             success_proxy=int(chk["collision_free"][idx]), success_strict=int(chk["ok"][idx]), rows_collision_free=chk["rows_collision_free"],
                             rows_ok=chk["rows_ok"], rows=chk["rows"], aabb_volume_zero=bool(ED.geometric_success(float(vols[idx]), trajectory)),
                             first_collision_waypoint=int(chk["first"][idx]), path_length=EV.path_lengths(trajectory), sparc=EV.smoothness(trajectory),
-                            planning_time_s=t_plan, scene_wall_s=time.time() - t0, trajectory=trajectory))
+                            planning_time_s=t_plan, scene_wall_s=time.time() - t0, trajectory=trajectory, **extras(vols, chk, met)))
         return out
 
     try:
@@ -365,11 +401,16 @@ def main(argv=None):
     parser.add_argument("--seed", type=int, default=None, help="np.random.seed(seed + rank) before the loop (the reference never seeds; for repeatable runs)")
     parser.add_argument("--results-json", type=str, default=None, help="write this rank's per-scene results (without the trajectories) and the job summary "
                                                                        "to PATH (rank 0) / PATH.rank<r> (other ranks)")
+    parser.add_argument("--ensemble-report", action="store_true", help="score every row of each batch on the GPU (path lengths, SPARC) and report, per guide of the "
+                                                                       "ensemble, its collision-free rows and their metrics (extension; adds `ensemble` to the results)")
+    parser.add_argument("--prefer", choices=("shortest", "smoothest"), default=None, help="among the rows within the trust region of the minimum swept volume pick the "
+                                                                                             "shortest joint path / the smoothest plan instead of the first arg-min (extension)")
     args = parser.parse_args(argv)
     rank = int(os.environ.get("RANK", "0"))
     if args.seed is not None:
         np.random.seed(args.seed + rank)
-    results = run(args.cfg_path, scenes_in_flight=args.scenes_in_flight, max_scenes=args.max_scenes, scenes_per_launch=args.scenes_per_launch)
+    results = run(args.cfg_path, scenes_in_flight=args.scenes_in_flight, max_scenes=args.max_scenes, scenes_per_launch=args.scenes_per_launch,
+                  ensemble_report=args.ensemble_report, prefer=args.prefer)
     if args.results_json:
         import json
 
