@@ -107,6 +107,10 @@ int ctx_alloc(edmp_ctx* ctx, void** p, size_t bytes);  // guide.hip: from the co
 void ctx_release(edmp_ctx* ctx, void* p);               // back into the pool (hipFree only beyond the pool's byte cap)
 void ctx_pool_destroy(edmp_ctx* ctx);
 void sampler_destroy(Sampler*);
+// sampler.hip: a segmented run in progress is over.  Called by every entry point outside the loop that replaces something the next
+// segment would read: the bound model's input buffer (edmp_unet_forward_dev), the guide's start / goal pair (gradient, swept cost,
+// row volumes)
+void sampler_end_run(edmp_ctx* ctx);
 
 // RAII-less helper: device allocation tracked by the owner
 template <class T>

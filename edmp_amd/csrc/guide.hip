@@ -886,6 +886,7 @@ extern "C" int edmp_guide_swept_cost_dev(edmp_ctx* ctx, const float* joints_dev,
     if (rc) return rc;
     EDMP_REQUIRE(joints_dev && volumes_dev && start && goal, "null pointer");
     EDMP_HIP_CHECK(hipSetDevice(ctx->device));
+    sampler_end_run(ctx);  // (the guide's start / goal pair is replaced)
     rc = upload_startgoal(ctx, start, goal);
     if (rc) return rc;
     return launch_guide<GM_SV_VOL, float>(ctx, joints_dev, L, 0, n, L, t, use_row_class, 0, volumes_dev, nullptr);
@@ -899,6 +900,7 @@ extern "C" int edmp_guide_gradient_dev(edmp_ctx* ctx, const double* joints_dev, 
     EDMP_REQUIRE(joints_dev && grad_dev && start && goal, "null pointer");
     EDMP_REQUIRE(B == g->B, "batch %d != rows set (%d)", B, g->B);
     EDMP_HIP_CHECK(hipSetDevice(ctx->device));
+    sampler_end_run(ctx);  // (the guide's start / goal pair and the step scratch are replaced)
     rc = ensure_scratch(ctx, g, B, L);
     if (rc) return rc;
     rc = guide_set_startgoal(ctx, start, goal);
@@ -920,6 +922,7 @@ extern "C" int edmp_row_swept_volumes_dev(edmp_ctx* ctx, const double* X_dev, in
     Guide* g = ctx->guide;
     EDMP_REQUIRE(X_dev && start && goal, "null pointer");
     EDMP_HIP_CHECK(hipSetDevice(ctx->device));
+    sampler_end_run(ctx);
     rc = ensure_scratch(ctx, g, B, N - 2);
     if (rc) return rc;
     rc = guide_set_startgoal(ctx, start, goal);

@@ -41,6 +41,9 @@ struct Sampler {
     double* sg = nullptr;   // [EDMP_MAX_SCENES][14] start|goal f64 (one pair per scene of a scene batch)
     int run_B = 0;          // batch of the run whose state sits in X (segmented runs)
     int run_rps = 0;        // its rows per scene (0 = one scene)
+    int run_next = 0;       // the step the kept state stands at = the t_hi the next segment must bring (0 = no run in progress)
+    uint64_t run_epoch = 0;  // ctx->epoch when the last segment returned: model, scene, rows and schedule tables of the run
+    int run_guided = 0;     // the init segment was guided: only then does the guide hold the run's start / goal pair
     int condition = 1;      // pin X[:, :, 0] / X[:, :, -1] to start / goal (diffusion.py:305-307, 347-349)
     int cap = 0;            // elements
     // whole-run hipGraph (edmp_sampler_set_graph): the enqueue of one denoise_loop call captured once and replayed while the
@@ -71,6 +74,10 @@ struct Sampler {
 
 void sampler_rccl_destroy(Sampler* s);            // rccl_hook.hip
 bool sampler_hook_is_native(const Sampler* s);    // rccl_hook.hip: the installed hook is the stream-capturable ncclAllReduce one
+
+void sampler_end_run(edmp_ctx* ctx) {
+    if (ctx && ctx->sampler) ctx->sampler->run_next = 0;
+}
 
 void sampler_destroy(Sampler* s) {
     if (!s) return;
@@ -309,6 +316,7 @@ static int set_startgoal(edmp_ctx* ctx, const double* start, const double* goal,
         sg[i] = start[i];
         sg[7 + i] = goal[i];
     }
+    s->run_next = 0;  // the pairs a segmented run conditions on are replaced: that run is over
     EDMP_HIP_CHECK(hipMemcpyAsync(s->sg, sg, sizeof(sg), hipMemcpyHostToDevice, ctx->stream));
     EDMP_HIP_CHECK(hipStreamSynchronize(ctx->stream));
     if (need_guide) return guide_set_startgoal(ctx, start, goal);
@@ -324,6 +332,7 @@ static int set_startgoal_scenes(edmp_ctx* ctx, int S, const double* starts, cons
             sg[k * 14 + i] = starts[k * 7 + i];
             sg[k * 14 + 7 + i] = goals[k * 7 + i];
         }
+    s->run_next = 0;
     EDMP_HIP_CHECK(hipMemcpyAsync(s->sg, sg, (size_t)S * 14 * sizeof(double), hipMemcpyHostToDevice, ctx->stream));
     EDMP_HIP_CHECK(hipStreamSynchronize(ctx->stream));
     if (need_guide) return guide_set_startgoal_scenes(ctx, S, starts, goals);
@@ -537,6 +546,7 @@ extern "C" int edmp_sampler_init(edmp_ctx* ctx, int T, double variance_thresh) {
         EDMP_HIP_CHECK(hipMalloc((void**)&ctx->sampler->sg, EDMP_MAX_SCENES * 14 * sizeof(double)));
     }
     Sampler* s = ctx->sampler;
+    s->run_next = 0;  // new schedule tables: a segmented run in progress cannot be continued
     s->T = T;
     s->beta.resize(T);
     s->alpha.resize(T);
@@ -560,6 +570,7 @@ extern "C" int edmp_sampler_init(edmp_ctx* ctx, int T, double variance_thresh) {
 
 extern "C" int edmp_sampler_set_condition(edmp_ctx* ctx, int on) {
     EDMP_REQUIRE(ctx && ctx->sampler, "sampler not initialised");
+    if (ctx->sampler->condition != (on ? 1 : 0)) ctx->sampler->run_next = 0;  // (a run is conditioned, or not, from X_T to the end)
     ctx->sampler->condition = on ? 1 : 0;
     return EDMP_OK;
 }
@@ -686,8 +697,12 @@ static int enqueue_loop(edmp_ctx* ctx, const double* noise_dev, bool use_rng, ui
 }
 
 // S > 1: a scene batch of S scenes x B / S rows; start / goal then hold S rows of 7 each
+// segment: one of the *_segment_dev entry points.  Only they leave a run in progress (Sampler::run_next): a segment that returns with
+// t_lo > 0 records the step the kept state stands at and the context's epoch, and a continuing segment (init == 0) must bring
+// exactly that t_hi under that epoch.  Every other loop call, a run that reached t_lo == 0, new start / goal pairs, a changed
+// conditioning switch and edmp_sampler_init end the run.  start / goal of a continuing segment are not read.
 static int denoise_loop(edmp_ctx* ctx, const double* noise_dev, bool use_rng, uint64_t seed, int B, const double* start, const double* goal,
-                        int guided, int t_hi, int t_lo, bool init, int zero_row0, double* X_out_dev, bool allow_graph = true, int S = 1) {
+                        int guided, int t_hi, int t_lo, bool init, int zero_row0, double* X_out_dev, bool segment = false, int S = 1) {
     int rc = check_loop_state(ctx, B, guided != 0, S);
     if (rc) return rc;
     const int rps = S > 1 ? B / S : 0;
@@ -710,18 +725,39 @@ static int denoise_loop(edmp_ctx* ctx, const double* noise_dev, bool use_rng, ui
     hipStream_t st = ctx->stream;
     if (init) {
         EDMP_REQUIRE(start && goal, "null start/goal");
+        s->run_next = 0;
         rc = ensure_sampler_scratch(ctx, (int)n);
         if (rc) return rc;
         rc = S > 1 ? set_startgoal_scenes(ctx, S, start, goal, guided != 0) : set_startgoal(ctx, start, goal, guided != 0);
         if (rc) return rc;
         s->run_B = B;
         s->run_rps = rps;
+        s->run_guided = guided != 0;
     } else {
-        EDMP_REQUIRE(s->X && s->run_B == B && s->run_rps == rps, "no run in progress for batch %d / %d scene(s) (call with init first)", B, S);
+        if (!(s->X && s->run_next > 0 && s->run_B == B && s->run_rps == rps)) {
+            set_error("no run in progress for batch %d / %d scene(s): call with init first (a complete run, a run that reached step 0, new start / goal "
+                      "pairs and edmp_sampler_init end a segmented run)", B, S);
+            return EDMP_ERR_STATE;
+        }
+        if (t_hi != s->run_next) {
+            set_error("the run in progress stands at step %d: a continuing segment starts there, t_hi = %d was given", s->run_next, t_hi);
+            return EDMP_ERR_STATE;
+        }
+        if (guided && !s->run_guided) {
+            set_error("the run in progress (step %d) was started unguided: the guide holds no start / goal pair of it, a guided segment cannot continue it",
+                      s->run_next);
+            return EDMP_ERR_STATE;
+        }
+        if (ctx->epoch != s->run_epoch) {
+            set_error("the model, the scene, the rows or the sampler's tables changed since the previous segment (step %d): start the run again with init",
+                      s->run_next);
+            return EDMP_ERR_STATE;
+        }
+        s->run_next = 0;  // (set again below when this segment has been enqueued completely)
     }
     // a caller-supplied collective is not capturable; segments of a chunked run carry a fresh noise pointer each, so a
     // captured graph would never be replayed (capture + instantiate + destroy per chunk): they are enqueued directly
-    const bool graph = allow_graph && s->graph_on == 1 && !ctx->prof.on && (!s->ar_fn || sampler_hook_is_native(s));
+    const bool graph = !segment && s->graph_on == 1 && !ctx->prof.on && (!s->ar_fn || sampler_hook_is_native(s));
     Sampler::GraphKey key;
     if (graph) {
         if (guided) {
@@ -760,6 +796,11 @@ static int denoise_loop(edmp_ctx* ctx, const double* noise_dev, bool use_rng, ui
         EDMP_HIP_CHECK(hipGraphLaunch(s->gexec, st));
         if (X_out_dev) EDMP_HIP_CHECK(hipMemcpyAsync(X_out_dev, s->X, n * sizeof(double), hipMemcpyDeviceToDevice, st));
     }
+    if (!rc && segment) {
+        // the epoch as it stands NOW: the run itself moves it (ensure_sampler_scratch when X grows, guide_prepare when the scratch moves)
+        s->run_next = t_lo;
+        s->run_epoch = ctx->epoch;
+    }
     return rc;
 }
 
@@ -779,7 +820,7 @@ extern "C" int edmp_denoise_guided_rng_dev(edmp_ctx* ctx, uint64_t seed, int B, 
 extern "C" int edmp_denoise_guided_segment_dev(edmp_ctx* ctx, const double* noise_dev, int B, const double* start, const double* goal, int guided,
                                                int t_hi, int t_lo, int init, int zero_row0, double* X_out_dev) {
     EDMP_REQUIRE(ctx && ctx->sampler && noise_dev, "edmp_denoise_guided_segment_dev: bad arguments");
-    return denoise_loop(ctx, noise_dev, false, 0, B, start, goal, guided, t_hi, t_lo, init != 0, zero_row0, X_out_dev, false);
+    return denoise_loop(ctx, noise_dev, false, 0, B, start, goal, guided, t_hi, t_lo, init != 0, zero_row0, X_out_dev, true);
 }
 
 // a scene batch: S scenes x B rows as one (S*B, C, N) run; starts / goals may be NULL only when neither conditioning nor guided
@@ -801,7 +842,7 @@ extern "C" int edmp_denoise_scenes_dev(edmp_ctx* ctx, const double* noise_dev, i
     EDMP_REQUIRE(noise_dev && X_out_dev, "edmp_denoise_scenes_dev: null pointer");
     static const double zeros[EDMP_MAX_SCENES * 7] = {};
     if (int rc = scenes_args(ctx, S, B, starts, goals, guided, zeros)) return rc;
-    return denoise_loop(ctx, noise_dev, false, 0, S * B, starts, goals, guided, ctx->sampler->T, t_stop, true, zero_row0, X_out_dev, true, S);
+    return denoise_loop(ctx, noise_dev, false, 0, S * B, starts, goals, guided, ctx->sampler->T, t_stop, true, zero_row0, X_out_dev, false, S);
 }
 
 extern "C" int edmp_denoise_scenes_segment_dev(edmp_ctx* ctx, const double* noise_dev, int S, int B, const double* starts, const double* goals, int guided,
@@ -809,7 +850,7 @@ extern "C" int edmp_denoise_scenes_segment_dev(edmp_ctx* ctx, const double* nois
     EDMP_REQUIRE(noise_dev, "edmp_denoise_scenes_segment_dev: null noise pointer");
     static const double zeros[EDMP_MAX_SCENES * 7] = {};
     if (int rc = scenes_args(ctx, S, B, starts, goals, guided, zeros)) return rc;
-    return denoise_loop(ctx, noise_dev, false, 0, S * B, starts, goals, guided, t_hi, t_lo, init != 0, zero_row0, X_out_dev, false, S);
+    return denoise_loop(ctx, noise_dev, false, 0, S * B, starts, goals, guided, t_hi, t_lo, init != 0, zero_row0, X_out_dev, true, S);
 }
 
 extern "C" int edmp_sampler_set_allreduce(edmp_ctx* ctx, edmp_allreduce_fn fn, void* user) {

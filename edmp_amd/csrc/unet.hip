@@ -1825,6 +1825,7 @@ int unet_forward_impl(edmp_ctx* ctx, const float* x_dev, int B, int t, float* ep
 extern "C" int edmp_unet_forward_dev(edmp_ctx* ctx, const float* x_dev, int B, int t, float* eps_dev) {
     EDMP_REQUIRE(ctx && x_dev && eps_dev, "edmp_unet_forward_dev: null argument");
     EDMP_HIP_CHECK(hipSetDevice(ctx->device));
+    sampler_end_run(ctx);  // the input buffer carries the next segment's UNet input
     return unet_forward_impl(ctx, x_dev, B, t, eps_dev);
 }
 

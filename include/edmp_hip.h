@@ -196,7 +196,18 @@ int edmp_denoise_guided_dev(edmp_ctx* ctx, const double* noise_dev, int B, const
  * init != 0 starts a run at t_hi = T (noise_dev[0] is the X_T draw, then one (B,C,N) draw per step); init == 0 continues
  * from the state kept in the context (noise_dev[0] is the draw of step t_hi) and performs no host synchronisation.
  * X_out_dev may be NULL except for the last segment.  Used by Diffusion.denoise_guided to overlap NumPy's RandomState
- * (the reference's noise contract, ~0.85 s per 1024-row scene on the host) with the denoising itself. */
+ * (the reference's noise contract, ~0.85 s per 1024-row scene on the host) with the denoising itself.
+ * The context remembers where the run stands: a segment that returns with t_lo > 0 leaves a run in progress at step t_lo, and
+ * a continuing segment must bring t_hi == that step, the same B, and a context whose model, scene, rows and sampler tables are
+ * those of the previous segment; anything else is refused with EDMP_ERR_STATE (the message names the expected and the given
+ * step) and launches nothing.  A run ends when a segment reaches t_lo == 0, and is ended by every other loop entry point
+ * (edmp_denoise_guided_dev / _rng_dev / edmp_denoise_scenes_dev), by the teacher-forced steps, edmp_guide_gradient_dev,
+ * edmp_guide_swept_cost_dev and edmp_row_swept_volumes_dev (they replace a start / goal pair), by edmp_unet_forward_dev (the
+ * model's input buffer carries the next segment's input), by a changed edmp_sampler_set_condition and by edmp_sampler_init: a
+ * continuing segment after any of them is refused.  A run started with guided = 0 cannot be continued with guided = 1 (the guide
+ * never received its pair).
+ * start / goal are read by the init segment only (uploaded once, kept on the device); a continuing segment IGNORES its start /
+ * goal arguments and goes on with the init segment's pair. */
 int edmp_denoise_guided_segment_dev(edmp_ctx* ctx, const double* noise_dev, int B, const double* start, const double* goal,
                                     int guided, int t_hi, int t_lo, int init, int zero_row0, double* X_out_dev);
 
@@ -223,7 +234,8 @@ int edmp_scene_batch_set(edmp_ctx* ctx, int S, const int32_t* n_obstacles, const
  * mode and the all-reduce hook are refused (the hook sums ONE scalar). */
 int edmp_denoise_scenes_dev(edmp_ctx* ctx, const double* noise_dev, int S, int B, const double* starts, const double* goals, int guided,
                             int t_stop, int zero_row0, double* X_out_dev);
-/* the same loop in segments, with the t_hi / t_lo / init contract of edmp_denoise_guided_segment_dev */
+/* the same loop in segments, with the t_hi / t_lo / init contract of edmp_denoise_guided_segment_dev (run bookkeeping included:
+ * the continuing segment's S, B and t_hi must be the run's; its starts / goals are ignored) */
 int edmp_denoise_scenes_segment_dev(edmp_ctx* ctx, const double* noise_dev, int S, int B, const double* starts, const double* goals,
                                     int guided, int t_hi, int t_lo, int init, int zero_row0, double* X_out_dev);
 

@@ -15,6 +15,7 @@ import pytest
 import torch
 
 from tests.util import T, cfgs_for, maxabs, rmse
+from tests.util import f64_error_ratio as _ratio
 
 pytestmark = pytest.mark.gpu
 
@@ -112,12 +113,6 @@ def _missing_tap_explained(which, n_levels, names):
     if which == 200 + n_levels - 2:
         return any(s.startswith("level_kernel<2") or s.startswith("level2_kernel<1") for s in names)
     return False
-
-
-def _ratio(hip, ref32, ref64):
-    """HIP's rmse against float64 over torch-float32's (floor: 1e-7 x rms)"""
-    floor = 1e-7 * float(np.sqrt(np.mean(ref64 ** 2)))
-    return rmse(hip, ref64) / max(rmse(ref32, ref64), floor, 1e-30)
 
 
 def _sweep(aid, net, tag):
