@@ -2,8 +2,12 @@
 (`denoise_guided`) runs device-resident in libedmp_hip.so (edmp_amd/csrc/sampler.hip): one host call per scene."""
 from __future__ import annotations
 
+import contextlib
 import ctypes as C
 import os
+import threading
+import time
+from typing import NamedTuple
 
 import numpy as np
 import torch
@@ -37,6 +41,49 @@ def _startgoal(start, goal, needed: bool):
     return out
 
 
+DEFAULT_CHUNK_STEPS = 16
+
+
+class Segment(NamedTuple):
+    """one piece of a run whose noise arrives in chunks: reverse steps t_hi .. t_lo + 1, under `draws` draws of (B, C, N) that begin
+    `offset` draws into the run's stream; `init`: the first piece, whose chunk begins with X_T"""
+
+    t_hi: int
+    t_lo: int
+    init: bool
+    draws: int
+    offset: int
+
+
+def chunk_plan(T, t_stop=0, chunk_steps=DEFAULT_CHUNK_STEPS):
+    """The segments of a run from T down to t_stop.  The first chunks are short and double (1, 2, 4, ... steps, capped at
+    `chunk_steps`) so that the GPU starts after ONE step's worth of draws and the host gets ahead of it geometrically; X_T rides
+    with the first chunk.  Every producer and consumer of chunked noise (the draw thread, the pinned uploads, infer_serial's feeder
+    and its watermarks) works in units of this plan."""
+    plan, t_hi, k, offset = [], int(T), 1, 0
+    while t_hi > int(t_stop):
+        steps = min(k, int(chunk_steps), t_hi - int(t_stop))
+        seg = Segment(t_hi, t_hi - steps, not plan, steps + (0 if plan else 1), offset)
+        plan.append(seg)
+        t_hi, k, offset = seg.t_lo, 2 * k, offset + seg.draws
+    return plan
+
+
+def guided_step(t) -> bool:
+    """the reverse steps that add the guide's gradient: every second one, down to t = 5 (diffusion.py:311, 326-327; the device loop's
+    own copy of the rule is guided_step in csrc/sampler.hip)"""
+    return (t % 2) < 1 and t >= 5
+
+
+def _is_pinned_f64(x) -> bool:
+    """a contiguous f64 tensor in page-locked host memory: what the copy stream can upload by DMA, slice by slice"""
+    return isinstance(x, torch.Tensor) and not x.is_cuda and x.is_pinned() and x.dtype == torch.float64 and x.is_contiguous()
+
+
+def _noise_error(name, want, x):
+    return ValueError(f"{name} must be f64 {tuple(want)}, got {tuple(x.shape)} {x.dtype}")
+
+
 def place_scene_rows(dst: torch.Tensor, pieces) -> torch.Tensor:
     """A scene batch's noise layout: ``pieces`` = S tensors (steps, B, C, N), scene s's draws; ``dst`` (steps, S*B, C, N) receives
     piece s at rows [s*B, (s+1)*B) of every draw, by one strided copy per scene (on the current stream)."""
@@ -58,8 +105,6 @@ class PinnedNoiseStream:
     soon as each is complete - the first scene of a run starts after one step's worth of draws, later scenes find their stream ready."""
 
     def __init__(self, tensor):
-        import threading
-
         self.tensor, self.drawn, self.error = tensor, 0, None
         self._cv = threading.Condition()
 
@@ -171,52 +216,40 @@ class Diffusion:
                 raise ValueError(f"guide was built for batch {guide.batch_size}, denoise_guided called with {batch_size}")
             guide._set_rows(guidance_schedule if guidance_schedule is not None else guide._sched)
 
-    def denoise_guided(self, model, guide, traj_len, num_channels, guidance_schedule, batch_size=1, start=None, goal=None,
-                       condition=True, benchmarking=False, *, noise=None, seed=0, t_stop=0, zero_row0=True, return_device=False, chunk_steps=16, allreduce=None):
-        """diffusion.py:300-356.  ``noise``: optional pre-drawn (T+1,B,C,N) f64 ndarray / device tensor (default:
-        drawn from the global NumPy RNG in the reference's order); ``noise="device"`` draws z on the GPU (Philox,
-        ``seed``) — a non-parity mode without the host draw / upload.  ``allreduce``: this call is one row shard
-        of a batch spread over several GPUs; an ``edmp_amd.dist.RcclAllReduce`` (native ncclAllReduce inside the device loop) or a
-        callable that sums the f64 device scalar over ranks in place (edmp_amd.dist.allreduce_sum_; a Python callback per guided step).
-        Returns (B,C,N) f64 ndarray (a fresh copy)."""
-        ctx = self.ctx
-        self._prepare(model, guide, batch_size, guidance_schedule)
-        _capi.check(ctx.lib.edmp_sampler_set_condition(ctx.h, 1 if condition else 0))
-        s, g = _startgoal(start, goal, needed=bool(condition) or guide is not None)
+    def _check_run(self, model, traj_len, num_channels, t_stop):
         if int(traj_len) != model.horizon or int(num_channels) != model.input_dim:
             raise ValueError(f"traj_len/num_channels ({traj_len}, {num_channels}) do not match the model's ({model.horizon}, {model.input_dim})")
         if not 0 <= int(t_stop) < self.T:
             raise ValueError(f"t_stop must lie in [0, {self.T}), got {t_stop}")
-        out = ctx.empty((batch_size, num_channels, traj_len), torch.float64)
-        if allreduce is not None:
-            # "one logical batch across GPUs": this rank holds a row shard of a larger reference batch; the only cross-row
-            # coupling, the whole-batch sum(g^2) (lib/guide.py:629), is summed over ranks between the two halves of every
-            # guided step - INSIDE the device-resident loop: the library calls the hook once per guided step with the
-            # context's stream and the device scalar, the collective is ordered by the stream (no host round trip)
-            if noise is None or isinstance(noise, str):
-                raise ValueError("sharded runs take an explicit noise array (this rank's rows of the global stream)")
-            from .dist import RcclAllReduce
 
-            def _read_stats():
-                raw = (C.c_uint64 * 3)()
-                _capi.check(ctx.lib.edmp_sampler_allreduce_stats(ctx.h, raw, 1))
-                # host time inside the hook, measured by the library around each call (any hook): GIL + collective enqueue
-                self.hook_stats = dict(calls=int(raw[0]), total_s=1e-9 * int(raw[1]), max_s=1e-9 * int(raw[2]),
-                                       kind="native ncclAllReduce (csrc/rccl_hook.hip)" if native else "python callback (ctypes -> torch.distributed)")
+    def _finish(self, out, return_device, *, sync=False, hand_over=True):
+        """the result as the caller asked for it: a fresh host copy, or the device tensor itself - after a host synchronisation (`sync`)
+        and / or with torch's current stream ordered after the context's (`hand_over`)"""
+        if not return_device:
+            return self.ctx.to_host(out)
+        if sync:
+            self.ctx.sync()
+        return self.ctx.hand_over(out) if hand_over else out
 
-            native = isinstance(allreduce, RcclAllReduce)
-            if native:
-                # the hook is native code installed once on this context (csrc/rccl_hook.hip): nothing to install per call
-                if allreduce.ctx is not ctx or not allreduce.attached():
-                    raise ValueError("this RcclAllReduce is not attached to the diffuser's context (or was closed)")
-                _capi.check(ctx.lib.edmp_rccl_enable(ctx.h, 1), "edmp_rccl_enable")
-                _read_stats()
-                try:
-                    return self.denoise_guided(model, guide, traj_len, num_channels, guidance_schedule, batch_size, start, goal, condition, benchmarking,
-                                               noise=noise, seed=seed, t_stop=t_stop, zero_row0=zero_row0, return_device=return_device)
-                finally:
-                    _capi.check(ctx.lib.edmp_rccl_enable(ctx.h, 0), "edmp_rccl_enable")  # other runs of this context are not shards
-                    _read_stats()
+    @contextlib.contextmanager
+    def _sharded(self, allreduce):
+        """One logical batch across GPUs: this rank holds a row shard of a larger reference batch; the only cross-row coupling, the
+        whole-batch sum(g^2) (lib/guide.py:629), is summed over ranks between the two halves of every guided step - INSIDE the
+        device-resident loop: the library calls the hook once per guided step with the context's stream and the device scalar, the
+        collective is ordered by the stream (no host round trip).  The hook is in place for the body and `hook_stats` is read after it."""
+        from .dist import RcclAllReduce
+
+        ctx = self.ctx
+        if isinstance(allreduce, RcclAllReduce):
+            # the hook is native code installed once on this context (csrc/rccl_hook.hip): nothing to install per call
+            if allreduce.ctx is not ctx or not allreduce.attached():
+                raise ValueError("this RcclAllReduce is not attached to the diffuser's context (or was closed)")
+            kind = "native ncclAllReduce (csrc/rccl_hook.hip)"
+
+            def install(on):  # (off again after the body: other runs of this context are not shards)
+                _capi.check(ctx.lib.edmp_rccl_enable(ctx.h, 1 if on else 0), "edmp_rccl_enable")
+        else:
+            kind = "python callback (ctypes -> torch.distributed)"
             sumsq = self.sumsq_tensor()
 
             def _hook(_user, _stream, _ptr):
@@ -229,161 +262,173 @@ class Diffusion:
                     return 1
 
             cb = _capi.ALLREDUCE_FN(_hook)
-            self._hook_error = None
-            _capi.check(ctx.lib.edmp_sampler_set_allreduce(ctx.h, C.cast(cb, C.c_void_p), None))
-            _read_stats()
-            try:
-                res = self.denoise_guided(model, guide, traj_len, num_channels, guidance_schedule, batch_size, start, goal, condition, benchmarking,
-                                          noise=noise, seed=seed, t_stop=t_stop, zero_row0=zero_row0, return_device=return_device)
-            except _capi.EdmpError:
-                if self._hook_error is not None:
-                    raise self._hook_error
-                raise
-            finally:
-                _capi.check(ctx.lib.edmp_sampler_set_allreduce(ctx.h, None, None))
-                _read_stats()
-            return res
-        if isinstance(noise, str):
-            if noise != "device":
-                raise ValueError("noise must be an array, a device tensor, None (NumPy stream) or 'device'")
-            _capi.check(
-                ctx.lib.edmp_denoise_guided_rng_dev(ctx.h, int(seed) & 0xFFFFFFFFFFFFFFFF, batch_size, _capi.as_pd(s), _capi.as_pd(g),
-                                                    1 if guide is not None else 0, int(t_stop), 1 if zero_row0 else 0, ptr(out)),
-                "edmp_denoise_guided_rng_dev",
-            )
-            return ctx.hand_over(out) if return_device else ctx.to_host(out)
-        if noise is None:
-            # Reference contract: z comes from the GLOBAL NumPy RandomState, X_T first, then one draw per step
-            # (diffusion.py:303, 126).  The stream is drawn in chunks of `chunk_steps` steps and each chunk is uploaded and
-            # enqueued at once, so the host RNG (edmp_amd.nprng: ~0.9 ms per step for 1024 rows on 16 cores; NumPy itself needs 3.3-4 ms) runs while the GPU
-            # denoises the previous chunk.  The numbers and their order are those of one big standard_normal call.
-            guided = 1 if guide is not None else 0
-            # chunk plan: (steps, carries X_T).  The first chunks are short and double (1, 2, 4, ... steps) so that the GPU
-            # starts after ONE step's worth of draws and the host gets ahead of it geometrically.
-            plan, t_left, first, k = [], self.T - int(t_stop), True, 1
-            while t_left > 0:
-                kk = min(k, int(chunk_steps), t_left)
-                plan.append((kk, first))
-                t_left -= kk
-                first = False
-                k *= 2
-            per_step = batch_size * num_channels * traj_len
-            # The draws go straight into PINNED host memory (a ring of staging buffers owned by the context), so the upload is
-            # one asynchronous DMA on the copy stream - no pageable-memory staging copy on a host core, which the draw threads
-            # need.  A staging buffer is reused only after the copy out of it has completed (event).  The draws run in ONE
-            # background thread (the C helper releases the GIL), strictly in order, with two threads fewer than the CPU quota
-            # (nprng.draw_threads): chunk i+1 is drawn while this thread uploads chunk i and enqueues its kernel launches.
-            ring = ctx.pinned_ring(3, (int(chunk_steps) + 1) * per_step)
-            nthr = nprng.draw_threads()
 
-            import os as _os
-            import time as _time
+            def install(on):
+                _capi.check(ctx.lib.edmp_sampler_set_allreduce(ctx.h, C.cast(cb, C.c_void_p) if on else None, None))
 
-            trace = self.noise_trace = [] if _os.environ.get("EDMP_NOISE_TRACE") else None  # per chunk: host timestamps (debug)
-            t_call = _time.perf_counter()
+        def read_stats():
+            raw = (C.c_uint64 * 3)()
+            _capi.check(ctx.lib.edmp_sampler_allreduce_stats(ctx.h, raw, 1))
+            # host time inside the hook, measured by the library around each call (any hook): GIL + collective enqueue
+            self.hook_stats = dict(calls=int(raw[0]), total_s=1e-9 * int(raw[1]), max_s=1e-9 * int(raw[2]), kind=kind)
 
-            def draw(i):
-                kk, f = plan[i]
-                slot = ring[i % len(ring)]
-                t0 = _time.perf_counter()
-                if slot["event"] is not None:
-                    slot["event"].synchronize()  # the previous upload out of this buffer is done
-                t1 = _time.perf_counter()
-                n = (kk + (1 if f else 0)) * per_step
-                nprng.standard_normal((n,), nthreads=nthr, out=slot["np"][:n])
-                if trace is not None:
-                    trace.append(("draw", i, kk, t0 - t_call, t1 - t_call, _time.perf_counter() - t_call))
-                return slot, n
+        self._hook_error = None
+        install(True)
+        read_stats()
+        try:
+            yield
+        except _capi.EdmpError:
+            if self._hook_error is not None:
+                raise self._hook_error
+            raise
+        finally:
+            install(False)
+            read_stats()
 
-            t_hi, keep = self.T, []
-            pool = ctx.draw_pool()  # ONE long-lived draw thread per context: its OpenMP team stays alive (and warm) between scenes
-            pending = pool.submit(draw, 0) if plan else None
-            try:
-                for i, (kk, f) in enumerate(plan):
-                    ta = _time.perf_counter()
-                    slot, n = pending.result()
-                    tb = _time.perf_counter()
-                    pending = pool.submit(draw, i + 1) if i + 1 < len(plan) else None
-                    zd = ctx.upload_pinned(slot, n)  # copy stream; this context's stream waits for it
-                    keep.append(zd)  # stays allocated until the stream has consumed it
-                    last = i + 1 == len(plan)
-                    tc = _time.perf_counter()
-                    _capi.check(
-                        ctx.lib.edmp_denoise_guided_segment_dev(ctx.h, ptr(zd), batch_size, _capi.as_pd(s), _capi.as_pd(g), guided, t_hi, t_hi - kk,
-                                                                1 if f else 0, 1 if zero_row0 else 0, ptr(out) if last else None),
-                        "edmp_denoise_guided_segment_dev",
-                    )
-                    if trace is not None:
-                        ev = torch.cuda.Event(enable_timing=True)
-                        ev.record(ctx.stream)
-                        trace.append(("main", i, kk, ta - t_call, tb - t_call, tc - t_call, _time.perf_counter() - t_call, ev))
-                    t_hi -= kk
-            except BaseException:
-                # leave nothing in flight that still reads the staging ring or the chunk tensors: the draw thread finishes its
-                # current chunk, the stream drains, then the error propagates
-                if pending is not None:
-                    try:
-                        pending.result()
-                    except Exception:
-                        pass
+    def _run_segments(self, plan, source, segment, out, return_device, drain=lambda: None):
+        """The segmented loop.  For every segment of `plan` (chunk_plan), `source(seg)` gives its noise chunk as a device tensor and
+        `segment(chunk, seg, X_out)` enqueues its steps; X_out is `out` for the last segment and None before.  `drain()` waits for what
+        the source still has in flight on the host."""
+        keep = []  # every chunk stays allocated until the stream has consumed it
+        try:
+            for seg in plan:
+                keep.append(source(seg))
+                segment(keep[-1], seg, out if seg is plan[-1] else None)
+        except BaseException:
+            # leave nothing in flight that still reads the staging ring, a pinned stream or the chunk tensors: the draw thread finishes
+            # its current chunk, the stream drains, then the error propagates
+            for wait in (drain, self.ctx.sync):
                 try:
-                    ctx.sync()
+                    wait()
                 except Exception:
                     pass
-                raise
-            if return_device:
-                ctx.sync()
-                return out
-            res = ctx.to_host(out)
-            del keep
-            return res
+            raise
+        return self._finish(out, return_device, sync=True, hand_over=False)  # (a device result: the chunks die with this frame, after the sync)
+
+    def _pinned_chunks(self, tensor, stream, per_step):
+        """source of a plan's chunks out of one scene's stream in PAGE-LOCKED host memory, pre-drawn or (`stream`, a PinnedNoiseStream
+        over `tensor`) still being drawn by infer_serial's scene-ahead feeder: every copy is queued at once on the copy stream and each
+        segment of the loop is ordered after its chunk - the GPU starts after 5.7 MB instead of after the whole 734 MB, and no host core
+        draws or copies anything while the loop runs."""
+        flat = tensor.view(-1)
+
+        def source(seg):
+            lo, hi = seg.offset * per_step, (seg.offset + seg.draws) * per_step
+            if stream is not None:
+                stream.wait_until(hi)  # (only the first scene of a run ever waits here: the feeder works a whole scene ahead)
+            return self.ctx.upload_pinned({"t": flat[lo:hi]}, hi - lo)
+
+        return source
+
+    def _run_numpy_stream(self, plan, per_step, chunk_steps, segment, out, return_device):
+        """Reference contract: z comes from the GLOBAL NumPy RandomState, X_T first, then one draw per step (diffusion.py:303, 126).
+        The stream is drawn chunk by chunk and each chunk is uploaded and enqueued at once, so the host RNG (edmp_amd.nprng: ~0.9 ms
+        per step for 1024 rows on 16 cores; NumPy itself needs 3.3-4 ms) runs while the GPU denoises the previous chunk.  The numbers
+        and their order are those of one big standard_normal call."""
+        ctx = self.ctx
+        # The draws go straight into PINNED host memory (a ring of staging buffers owned by the context), so the upload is
+        # one asynchronous DMA on the copy stream - no pageable-memory staging copy on a host core, which the draw threads
+        # need.  A staging buffer is reused only after the copy out of it has completed (event).  The draws run in ONE
+        # background thread (the C helper releases the GIL), strictly in order, with two threads fewer than the CPU quota
+        # (nprng.draw_threads): chunk i+1 is drawn while this thread uploads chunk i and enqueues its kernel launches.
+        ring = ctx.pinned_ring(3, (int(chunk_steps) + 1) * per_step)
+        nthr = nprng.draw_threads()
+        trace = self.noise_trace = [] if os.environ.get("EDMP_NOISE_TRACE") else None  # per chunk: host timestamps (debug)
+        t_call = time.perf_counter()
+
+        def since():
+            return time.perf_counter() - t_call
+
+        def draw(i):
+            slot = ring[i % len(ring)]
+            t0 = since()
+            if slot["event"] is not None:
+                slot["event"].synchronize()  # the previous upload out of this buffer is done
+            t1 = since()
+            n = plan[i].draws * per_step
+            nprng.standard_normal((n,), nthreads=nthr, out=slot["np"][:n])
+            if trace is not None:
+                trace.append(("draw", i, plan[i].t_hi - plan[i].t_lo, t0, t1, since()))
+            return slot, n
+
+        pool = ctx.draw_pool()  # ONE long-lived draw thread per context: its OpenMP team stays alive (and warm) between scenes
+        i, pending, stamps = 0, pool.submit(draw, 0), ()
+
+        def source(seg):
+            nonlocal i, pending, stamps
+            ta = since()
+            slot, n = pending.result()
+            tb = since()
+            i += 1
+            pending = pool.submit(draw, i) if i < len(plan) else None
+            zd = ctx.upload_pinned(slot, n)  # copy stream; this context's stream waits for it
+            stamps = (ta, tb, since())
+            return zd
+
+        def drain():
+            if pending is not None:
+                pending.result()
+
+        def traced(zd, seg, X_out):
+            segment(zd, seg, X_out)
+            ev = torch.cuda.Event(enable_timing=True)
+            ev.record(ctx.stream)
+            trace.append(("main", i - 1, seg.t_hi - seg.t_lo, *stamps, since(), ev))
+
+        return self._run_segments(plan, source, segment if trace is None else traced, out, return_device, drain)
+
+    def denoise_guided(self, model, guide, traj_len, num_channels, guidance_schedule, batch_size=1, start=None, goal=None,
+                       condition=True, benchmarking=False, *, noise=None, seed=0, t_stop=0, zero_row0=True, return_device=False,
+                       chunk_steps=DEFAULT_CHUNK_STEPS, allreduce=None):
+        """diffusion.py:300-356.  ``noise``: optional pre-drawn (T+1,B,C,N) f64 ndarray / device tensor (default:
+        drawn from the global NumPy RNG in the reference's order); ``noise="device"`` draws z on the GPU (Philox,
+        ``seed``) — a non-parity mode without the host draw / upload.  ``allreduce``: this call is one row shard
+        of a batch spread over several GPUs; an ``edmp_amd.dist.RcclAllReduce`` (native ncclAllReduce inside the device loop) or a
+        callable that sums the f64 device scalar over ranks in place (edmp_amd.dist.allreduce_sum_; a Python callback per guided step).
+        Returns (B,C,N) f64 ndarray (a fresh copy)."""
+        ctx = self.ctx
+        self._prepare(model, guide, batch_size, guidance_schedule)
+        _capi.check(ctx.lib.edmp_sampler_set_condition(ctx.h, 1 if condition else 0))
+        s, g = _startgoal(start, goal, needed=bool(condition) or guide is not None)
+        self._check_run(model, traj_len, num_channels, t_stop)
+        out = ctx.empty((batch_size, num_channels, traj_len), torch.float64)
+        if allreduce is not None and (noise is None or isinstance(noise, str)):
+            raise ValueError("sharded runs take an explicit noise array (this rank's rows of the global stream)")
+        shape = (self.T + 1, batch_size, num_channels, traj_len)
+        per_step = batch_size * num_channels * traj_len
+        sp, gp, guided, zr = _capi.as_pd(s), _capi.as_pd(g), 1 if guide is not None else 0, 1 if zero_row0 else 0
+
+        def segment(zd, seg, X_out):
+            _capi.check(
+                ctx.lib.edmp_denoise_guided_segment_dev(ctx.h, ptr(zd), batch_size, sp, gp, guided, seg.t_hi, seg.t_lo, 1 if seg.init else 0, zr,
+                                                        ptr(X_out) if X_out is not None else None),
+                "edmp_denoise_guided_segment_dev",
+            )
+
         stream = noise if isinstance(noise, PinnedNoiseStream) else None
         if stream is not None:
             noise = stream.tensor
-        if isinstance(noise, torch.Tensor) and not noise.is_cuda and noise.is_pinned() and noise.dtype == torch.float64 and noise.is_contiguous():
-            # A pre-drawn (or, PinnedNoiseStream, still being drawn) stream in PAGE-LOCKED host memory (infer_serial's scene-ahead feeder): uploaded in the same doubling chunks as the
-            # on-the-fly path (1, 2, 4, ... chunk_steps steps; X_T rides with the first), every copy queued at once on the copy stream and each
-            # segment of the loop ordered after its chunk - the GPU starts after 5.7 MB instead of after the whole 734 MB, and no host core
-            # draws or copies anything while the loop runs.
-            if tuple(noise.shape) != (self.T + 1, batch_size, num_channels, traj_len):
-                raise ValueError(f"noise must be f64 {(self.T + 1, batch_size, num_channels, traj_len)}, got {tuple(noise.shape)}")
-            guided = 1 if guide is not None else 0
-            flat, per_step = noise.view(-1), batch_size * num_channels * traj_len
-            t_hi, off, k, first, keep = self.T, 0, 1, True, []
-            while t_hi > int(t_stop):
-                kk = min(k, int(chunk_steps), t_hi - int(t_stop))
-                n = (kk + (1 if first else 0)) * per_step
-                if stream is not None:
-                    stream.wait_until(off + n)  # (only the first scene of a run ever waits here: the feeder works a whole scene ahead)
-                zd = ctx.upload_pinned({"t": flat[off:off + n]}, n)
-                keep.append(zd)
-                last = t_hi - kk == int(t_stop)
-                _capi.check(
-                    ctx.lib.edmp_denoise_guided_segment_dev(ctx.h, ptr(zd), batch_size, _capi.as_pd(s), _capi.as_pd(g), guided, t_hi, t_hi - kk,
-                                                            1 if first else 0, 1 if zero_row0 else 0, ptr(out) if last else None),
-                    "edmp_denoise_guided_segment_dev",
-                )
-                t_hi, off, k, first = t_hi - kk, off + n, k * 2, False
-            if return_device:
-                ctx.sync()  # (the chunk tensors die with this frame)
-                return out
-            res = ctx.to_host(out)
-            del keep
-            return res
-        nd = ctx.adopt(noise) if (isinstance(noise, torch.Tensor) and noise.is_cuda) else ctx.to_dev(noise, torch.float64)
-        if tuple(nd.shape) != (self.T + 1, batch_size, num_channels, traj_len) or nd.dtype != torch.float64:
-            raise ValueError(f"noise must be f64 {(self.T + 1, batch_size, num_channels, traj_len)}, got {tuple(nd.shape)} {nd.dtype}")
-        _capi.check(
-            ctx.lib.edmp_denoise_guided_dev(ctx.h, ptr(nd), batch_size, _capi.as_pd(s), _capi.as_pd(g), 1 if guide is not None else 0, int(t_stop),
-                                            1 if zero_row0 else 0, ptr(out)),
-            "edmp_denoise_guided_dev",
-        )
-        if return_device:
-            return ctx.hand_over(out)
-        return ctx.to_host(out)
+        with self._sharded(allreduce) if allreduce is not None else contextlib.nullcontext():
+            if isinstance(noise, str):
+                if noise != "device":
+                    raise ValueError("noise must be an array, a device tensor, None (NumPy stream) or 'device'")
+                _capi.check(ctx.lib.edmp_denoise_guided_rng_dev(ctx.h, int(seed) & 0xFFFFFFFFFFFFFFFF, batch_size, sp, gp, guided, int(t_stop), zr, ptr(out)),
+                            "edmp_denoise_guided_rng_dev")
+                return self._finish(out, return_device)
+            if noise is None:
+                return self._run_numpy_stream(chunk_plan(self.T, t_stop, chunk_steps), per_step, chunk_steps, segment, out, return_device)
+            if _is_pinned_f64(noise):  # uploaded in the same chunks as the on-the-fly stream
+                if tuple(noise.shape) != shape:
+                    raise _noise_error("noise", shape, noise)
+                return self._run_segments(chunk_plan(self.T, t_stop, chunk_steps), self._pinned_chunks(noise, stream, per_step), segment, out, return_device)
+            nd = ctx.adopt(noise) if (isinstance(noise, torch.Tensor) and noise.is_cuda) else ctx.to_dev(noise, torch.float64)
+            if tuple(nd.shape) != shape or nd.dtype != torch.float64:
+                raise _noise_error("noise", shape, nd)
+            _capi.check(ctx.lib.edmp_denoise_guided_dev(ctx.h, ptr(nd), batch_size, sp, gp, guided, int(t_stop), zr, ptr(out)), "edmp_denoise_guided_dev")
+            return self._finish(out, return_device)
 
     def denoise_guided_scenes(self, model, batch, traj_len, num_channels, starts, goals, *, noise=None, t_stop=0, zero_row0=True, condition=True,
-                              chunk_steps=16, return_device=False, guided=True):
+                              chunk_steps=DEFAULT_CHUNK_STEPS, return_device=False, guided=True):
         """S scenes of B rows each planned in ONE device-resident loop (edmp_denoise_scenes_dev): what S calls of denoise_guided, one per
         scene of ``batch`` (a guide.SceneBatch), return - bit for bit - as an (S, B, C, N) f64 array.  ``starts`` / ``goals`` (S, 7).
         ``noise``: None = the S streams from the global NumPy RandomState in scene order (the state ends where S denoise_guided calls leave
@@ -397,12 +442,9 @@ class Diffusion:
         S, B = batch.n_scenes, batch.batch_size
         if model.ctx is not ctx or batch.ctx is not ctx:
             raise _capi.EdmpError("model, scene batch and diffuser must live on the same GPU")
-        if int(traj_len) != model.horizon or int(num_channels) != model.input_dim:
-            raise ValueError(f"traj_len/num_channels ({traj_len}, {num_channels}) do not match the model's ({model.horizon}, {model.input_dim})")
+        self._check_run(model, traj_len, num_channels, t_stop)
         if S * B > model.max_batch:
             raise ValueError(f"{S} scenes x {B} rows exceed the model's max_batch ({model.max_batch})")
-        if not 0 <= int(t_stop) < self.T:
-            raise ValueError(f"t_stop must lie in [0, {self.T}), got {t_stop}")
         needed = bool(condition) or bool(guided)
         if starts is None or goals is None:
             if needed:
@@ -427,58 +469,39 @@ class Diffusion:
             per = (T + 1 - int(t_stop), B, Cc, N)
         streams = [x if isinstance(x, PinnedNoiseStream) else None for x in noise]
         tens = [x.tensor if isinstance(x, PinnedNoiseStream) else x for x in noise]
-        pinned = [isinstance(x, torch.Tensor) and not x.is_cuda and x.is_pinned() and x.dtype == torch.float64 and x.is_contiguous() for x in tens]
+        pinned = [_is_pinned_f64(x) for x in tens]
         if any(pinned) and not all(pinned):
             raise ValueError("noise: either every scene's stream is pinned host memory or none is")
         for k, x in enumerate(tens):
             if tuple(x.shape) not in (per, (T + 1, B, Cc, N)):
-                raise ValueError(f"noise[{k}] must be f64 {(T + 1, B, Cc, N)}, got {tuple(x.shape)}")
+                raise _noise_error(f"noise[{k}]", (T + 1, B, Cc, N), x)
         ctx.ensure_sampler(self.T, self.variance_thresh)
         model._bind()
         if guided:
             batch._bind()
         _capi.check(ctx.lib.edmp_sampler_set_condition(ctx.h, 1 if condition else 0))
         out = ctx.empty((S * B, Cc, N), torch.float64)
-        gflag, zr = 1 if guided else 0, 1 if zero_row0 else 0
+        sp, gp, gflag, zr = _capi.as_pd(s_arr), _capi.as_pd(g_arr), 1 if guided else 0, 1 if zero_row0 else 0
+
+        def segment(zd, seg, X_out):
+            _capi.check(
+                ctx.lib.edmp_denoise_scenes_segment_dev(ctx.h, ptr(zd), S, B, sp, gp, gflag, seg.t_hi, seg.t_lo, 1 if seg.init else 0, zr,
+                                                        ptr(X_out) if X_out is not None else None),
+                "edmp_denoise_scenes_segment_dev",
+            )
+
         if all(pinned):
-            # chunks of the S pinned streams (the single-scene plan: 1, 2, 4, ... chunk_steps steps, X_T with the first), each scene's
-            # piece uploaded by DMA and placed at rows [s*B, (s+1)*B) of the chunk by a strided device copy
-            per_step, keep = B * Cc * N, []
-            flats = [x.view(-1) for x in tens]
-            t_hi, off, k, first = T, 0, 1, True
-            try:
-                while t_hi > int(t_stop):
-                    kk = min(k, int(chunk_steps), t_hi - int(t_stop))
-                    steps = kk + (1 if first else 0)
-                    n = steps * per_step
-                    chunk = ctx.empty((steps, S * B, Cc, N), torch.float64)
-                    pieces = []
-                    for sc in range(S):
-                        if streams[sc] is not None:
-                            streams[sc].wait_until(off + n)
-                        pieces.append(ctx.upload_pinned({"t": flats[sc][off:off + n]}, n).view(steps, B, Cc, N))
-                    with torch.cuda.stream(ctx.stream):
-                        place_scene_rows(chunk, pieces)
-                    keep.append(chunk)
-                    last = t_hi - kk == int(t_stop)
-                    _capi.check(
-                        ctx.lib.edmp_denoise_scenes_segment_dev(ctx.h, ptr(chunk), S, B, _capi.as_pd(s_arr), _capi.as_pd(g_arr), gflag, t_hi, t_hi - kk,
-                                                                1 if first else 0, zr, ptr(out) if last else None),
-                        "edmp_denoise_scenes_segment_dev",
-                    )
-                    t_hi, off, k, first = t_hi - kk, off + n, k * 2, False
-            except BaseException:
-                try:  # nothing in flight may still read the chunks or the pinned streams when the error propagates
-                    ctx.sync()
-                except Exception:
-                    pass
-                raise
-            if return_device:
-                ctx.sync()
-                return out.view(S, B, Cc, N)
-            res = ctx.to_host(out)
-            del keep
-            return res.reshape(S, B, Cc, N)
+            # chunks of the S pinned streams (the single-scene plan), each scene's piece uploaded by DMA and placed at rows
+            # [s*B, (s+1)*B) of the chunk by a strided device copy
+            parts = [self._pinned_chunks(x, st, B * Cc * N) for x, st in zip(tens, streams)]
+
+            def source(seg):
+                chunk = ctx.empty((seg.draws, S * B, Cc, N), torch.float64)
+                pieces = [part(seg).view(seg.draws, B, Cc, N) for part in parts]
+                with torch.cuda.stream(ctx.stream):
+                    return place_scene_rows(chunk, pieces)
+
+            return self._run_segments(chunk_plan(T, t_stop, chunk_steps), source, segment, out, return_device).reshape(S, B, Cc, N)
         steps = tens[0].shape[0]
         if any(tuple(x.shape)[0] != steps for x in tens):
             raise ValueError("noise: every scene's stream must have the same number of draws")
@@ -490,21 +513,16 @@ class Diffusion:
             with torch.cuda.stream(ctx.stream):
                 place_scene_rows(nd, pieces)
             if steps == T + 1:
-                _capi.check(ctx.lib.edmp_denoise_scenes_dev(ctx.h, ptr(nd), S, B, _capi.as_pd(s_arr), _capi.as_pd(g_arr), gflag, int(t_stop), zr, ptr(out)),
-                            "edmp_denoise_scenes_dev")
-            else:  # the NumPy stream of a run that stops at t_stop: X_T and T - t_stop steps
-                _capi.check(ctx.lib.edmp_denoise_scenes_segment_dev(ctx.h, ptr(nd), S, B, _capi.as_pd(s_arr), _capi.as_pd(g_arr), gflag, T, int(t_stop), 1, zr,
-                                                                    ptr(out)), "edmp_denoise_scenes_segment_dev")
+                _capi.check(ctx.lib.edmp_denoise_scenes_dev(ctx.h, ptr(nd), S, B, sp, gp, gflag, int(t_stop), zr, ptr(out)), "edmp_denoise_scenes_dev")
+            else:  # the NumPy stream of a run that stops at t_stop, X_T and T - t_stop steps: the whole run as one segment
+                segment(nd, Segment(T, int(t_stop), True, steps, 0), out)
         except BaseException:
             try:
                 ctx.sync()
             except Exception:
                 pass
             raise
-        if return_device:
-            ctx.sync()
-            return ctx.hand_over(out).view(S, B, Cc, N)
-        return ctx.to_host(out).reshape(S, B, Cc, N)
+        return self._finish(out, return_device, sync=True).reshape(S, B, Cc, N)
 
     def denoise(self, model, traj_len, num_channels, start=None, goal=None, condition=True, *, batch_size=1, noise=None):
         """diffusion.py:253-278 (unguided), batched; returns X[0] like the reference when batch_size == 1."""
@@ -525,7 +543,7 @@ class Diffusion:
         xpost = ctx.empty((B, Cc, N), torch.float64)
         grad = ctx.empty((B, Cc, N - 2), torch.float64)
         _capi.check(ctx.lib.edmp_step_a_dev(ctx.h, ptr(Xd), ptr(zd), B, int(t), _capi.as_pd(s), _capi.as_pd(g), 1 if zero_row0 else 0, ptr(eps), ptr(xpost)), "edmp_step_a_dev")
-        guided = (t % 2) < 1 and t >= 5
+        guided = guided_step(t)
         if guided and allreduce is not None:
             with torch.cuda.stream(ctx.stream):
                 allreduce(self.sumsq_tensor())

@@ -19,7 +19,7 @@ import torch
 from edmp_amd import dist as ED
 from edmp_amd import evaluation as EV
 from edmp_amd import guide_cfg as GC
-from edmp_amd.diffusion import Diffusion
+from edmp_amd.diffusion import DEFAULT_CHUNK_STEPS, Diffusion, PinnedNoiseStream, chunk_plan
 from edmp_amd.guide import IntersectionVolumeGuide, SceneBatch
 from edmp_amd.scenes import SyntheticDataset
 from edmp_amd.temporalunet import TemporalUNet
@@ -66,15 +66,7 @@ class _NoiseFeeder:
         for b in cache[:n_buffers]:
             self.free.put(b)
         nthr = nprng.draw_threads()
-
-        from edmp_amd.diffusion import PinnedNoiseStream
-
-        per_step = int(np.prod(shape[1:]))
-        pieces, left, kk, first = [], int(shape[0]) - 1, 1, True  # (X_T + 1 step), 2, 4, 8, 16, 16, ... steps: the sampler's own chunk plan
-        while left > 0:
-            st = min(kk, 16, left)
-            pieces.append((st + (1 if first else 0)) * per_step)
-            left, kk, first = left - st, kk * 2, False
+        pieces = self.pieces(shape)
 
         def work():
             stream = None
@@ -97,6 +89,13 @@ class _NoiseFeeder:
 
         self.thread = threading.Thread(target=work, name="edmp-scene-noise", daemon=True)
         self.thread.start()
+
+    @staticmethod
+    def pieces(shape):
+        """doubles per published piece of one (T+1, B, C, N) stream: the chunks of the sampler's own plan, so that every watermark a consumer
+        waits for is the end of a piece"""
+        per_step = int(np.prod(shape[1:]))
+        return [seg.draws * per_step for seg in chunk_plan(int(shape[0]) - 1, 0, DEFAULT_CHUNK_STEPS)]
 
     def next(self):
         """the next scene's stream (scene order): a PinnedNoiseStream over a pinned (T+1, B, C, N) f64 tensor, possibly still being drawn"""

@@ -606,6 +606,31 @@ def test_chunked_numpy_stream_equals_resident_stream(golden, tiny_net):
     np.random.seed(31)
     np.random.standard_normal((T + 1, B, 7, 50))
     assert np.array_equal(after, np.random.standard_normal(3))
+    # a run that stops early draws X_T and the 21 steps it takes, nothing more: 22 * B * 7 * 50 normals
+    kw = dict(batch_size=B, start=g["start"], goal=g["goal"])
+    stream = noise_for(31, B)
+    Xs = {0: Xr, T - 21: dif.denoise_guided(net, guide, 50, 7, cfgs["guidance_schedule"], noise=stream, t_stop=T - 21, **kw)}
+    assert not np.array_equal(Xs[0], Xs[T - 21])
+    np.random.seed(31)
+    Xc = dif.denoise_guided(net, guide, 50, 7, cfgs["guidance_schedule"], chunk_steps=7, t_stop=T - 21, **kw)
+    after = np.random.standard_normal(3)
+    assert np.array_equal(Xc, Xs[T - 21])
+    np.random.seed(31)
+    np.random.standard_normal((22, B, 7, 50))
+    assert np.array_equal(after, np.random.standard_normal(3))
+    # the same stream in page-locked host memory, whole or handed over as a (fully published) stream that is being drawn
+    from edmp_amd.diffusion import PinnedNoiseStream
+
+    pinned = torch.from_numpy(stream).pin_memory()
+    for chunk in (16, 7):
+        for t_stop in (0, T - 21):
+            for as_stream in (False, True):
+                z = pinned
+                if as_stream:
+                    z = PinnedNoiseStream(pinned)
+                    z.publish(pinned.numel())
+                Xp = dif.denoise_guided(net, guide, 50, 7, cfgs["guidance_schedule"], noise=z, chunk_steps=chunk, t_stop=t_stop, **kw)
+                assert np.array_equal(Xp, Xs[t_stop]), (chunk, t_stop, as_stream)
 
 
 def test_condition_false(oracle, tiny_net):

@@ -418,3 +418,78 @@ def test_pinned_noise_stream_watermark():
     bad.publish(1, error=RuntimeError("draw failed"))
     with pytest.raises(RuntimeError, match="draw failed"):
         bad.wait_until(3)
+
+
+def test_chunk_plan_literals_and_invariants():
+    """edmp_amd.diffusion.chunk_plan, the one statement of how a run's noise is cut into chunks: 1, 2, 4, ... steps capped at chunk_steps,
+    X_T with the first chunk; the segments tile [t_stop, T] and their draws tile the stream."""
+    from edmp_amd.diffusion import DEFAULT_CHUNK_STEPS, chunk_plan
+
+    assert DEFAULT_CHUNK_STEPS == 16
+    plan = chunk_plan(255, 0, 16)
+    assert [s.t_hi - s.t_lo for s in plan] == [1, 2, 4, 8] + [16] * 15 and len(plan) == 19
+    assert plan == chunk_plan(255) and [tuple(s) for s in plan[:3]] == [(255, 254, True, 2, 0), (254, 252, False, 2, 2), (252, 248, False, 4, 4)]
+    assert [s.t_hi - s.t_lo for s in chunk_plan(255, 234, 7)] == [1, 2, 4, 7, 7]
+    assert [s.t_hi - s.t_lo for s in chunk_plan(16, 0, 1000)] == [1, 2, 4, 8, 1]
+    for T in (1, 2, 16, 255):
+        for t_stop in range(T):
+            for chunk in (1, 7, 8, 16, 255, 1000):
+                plan = chunk_plan(T, t_stop, chunk)
+                steps = [s.t_hi - s.t_lo for s in plan]
+                assert sum(steps) == T - t_stop and all(1 <= k <= chunk for k in steps), (T, t_stop, chunk)
+                assert plan[0].t_hi == T and plan[-1].t_lo == t_stop
+                assert all(a.t_lo == b.t_hi for a, b in zip(plan, plan[1:]))
+                assert [s.init for s in plan] == [True] + [False] * (len(plan) - 1)
+                assert [s.draws for s in plan] == [steps[0] + 1] + steps[1:]
+                assert [s.offset for s in plan] == [sum(s.draws for s in plan[:i]) for i in range(len(plan))]
+
+
+def test_feeder_publishes_in_units_of_the_chunk_plan():
+    """infer_serial's feeder publishes its watermarks where the sampler's chunks end: a consumer waits for exactly one piece per segment"""
+    import infer_serial
+    from edmp_amd.diffusion import chunk_plan
+
+    shape = (256, 12, 7, 50)
+    pieces = infer_serial._NoiseFeeder.pieces(shape)
+    assert pieces == [s.draws * 12 * 7 * 50 for s in chunk_plan(255, 0, 16)] and sum(pieces) == int(np.prod(shape))
+    assert infer_serial._NoiseFeeder.pieces((4, 2, 7, 50)) == [2 * 700, 2 * 700]
+
+
+def test_segment_driver_drains_before_an_error_propagates():
+    """Diffusion._run_segments, the one loop behind every chunked noise path: segments in plan order, the output only with the last; when
+    a source fails, what it has in flight is awaited and the context synchronised (once each) before the original exception propagates"""
+    from edmp_amd.diffusion import Diffusion, chunk_plan
+
+    log = []
+
+    class Ctx:
+        def sync(self):
+            log.append("sync")
+
+        def to_host(self, t):
+            log.append("to_host")
+            return t
+
+    dif = object.__new__(Diffusion)
+    dif.ctx = Ctx()
+    plan = chunk_plan(16, 9, 4)  # 1, 2, 4 steps
+    calls = []
+    res = dif._run_segments(plan, lambda seg: ("chunk", seg.offset), lambda zd, seg, out: calls.append((zd, seg.t_hi, seg.t_lo, seg.init, out)), "X", False,
+                            lambda: log.append("drain"))
+    assert res == "X" and log == ["to_host"]
+    assert calls == [(("chunk", 0), 16, 15, True, None), (("chunk", 2), 15, 13, False, None), (("chunk", 4), 13, 9, False, "X")]
+    assert dif._run_segments(plan, lambda seg: 0, lambda *a: None, "X", True) == "X" and log == ["to_host", "sync"]
+
+    def failing(seg):
+        if seg is plan[2]:
+            raise KeyError("third chunk")
+        return seg.offset
+
+    def bad_drain():
+        log.append("drain")
+        raise RuntimeError("the draw failed too")  # best effort: must not mask the first error
+
+    del log[:], calls[:]
+    with pytest.raises(KeyError, match="third chunk"):
+        dif._run_segments(plan, failing, lambda zd, seg, out: calls.append(seg.t_hi), "X", False, bad_drain)
+    assert calls == [16, 15] and log == ["drain", "sync"]
