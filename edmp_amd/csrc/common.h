@@ -93,7 +93,7 @@ struct edmp_ctx {
     std::multimap<size_t, void*> pool_free;
     std::unordered_map<void*, size_t> pool_cap;
     size_t pool_bytes = 0;
-    int* d_int = nullptr;  // one device int for small read-backs (edmp_argmin_dev)
+    int* d_int = nullptr;  // EDMP_MAX_SCENES device ints for small read-backs (edmp_argmin_dev, one picked row per scene)
 };
 
 namespace edmp {

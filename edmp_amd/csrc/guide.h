@@ -18,6 +18,9 @@ struct Guide {
     // scene batch (edmp_scene_batch_set): S scenes share this object; class c holds cls_no[c] obstacles in its own [T+1][cls_no][6] block
     // at float offset cls_off[c] of aabb (no = the largest count).  S = 1 / cls_no = nullptr: one scene, the table above
     int S = 1;
+    bool is_batch = false;         // built by edmp_scene_batch_set (a batch of ONE scene included): the edmp_scenes_* scoring calls need it
+    std::vector<int> scene_no_h;   // [S] obstacles of each scene
+    std::vector<int> scene_off_h;  // [S] first obstacle row of each scene in obb / kind
     int32_t* cls_no = nullptr;    // [2][G] device: counts, then float offsets
     std::vector<int> cls_off_h;   // [G] host copy of the offsets (S > 1)
     std::vector<int> cls_no_h;    // [G] host copy (S > 1)
@@ -42,8 +45,8 @@ struct Guide {
     float* startgoal = nullptr;  // [EDMP_MAX_SCENES][14] f32: start (7) | goal (7) per scene
     int scratch_B = 0, scratch_L = 0;
     float* vol_rows = nullptr;  // [B] for best trajectory
-    int32_t* flags = nullptr;   // [3][flags_B] success check: ok, first colliding waypoint, within limits; + [4] counts
-    int flags_B = 0;
+    int32_t* flags = nullptr;   // [3][flags_B] success check: ok, first colliding waypoint, within limits; + [flags_Q][4] counts
+    int flags_B = 0, flags_Q = 1;  // (one count quadruple per scene: a scene batch asks for S of them)
 };
 
 // the per-scene entry points (cost, gradient, best trajectory, success, shapes) on a bound scene batch: refused, never answered
@@ -55,6 +58,24 @@ struct Guide {
                             what, (g)->S);                                                                                        \
             return EDMP_ERR_STATE;                                                                                                \
         }                                                                                                                         \
+    } while (0)
+
+// the edmp_scenes_* scoring calls: the bound guide is a scene batch of exactly S scenes x B rows
+#define EDMP_REQUIRE_SCENE_BATCH(ctx, S_, B_, what)                                                                                       \
+    do {                                                                                                                                  \
+        if (!(ctx) || !(ctx)->guide || !(ctx)->guide->aabb || !(ctx)->guide->obb || !(ctx)->guide->row_class) {                         \
+            edmp::set_error("%s: no scene batch bound (edmp_scene_batch_set + edmp_rows_set first)", what);                             \
+            return (ctx) ? EDMP_ERR_STATE : EDMP_ERR_ARG;                                                                               \
+        }                                                                                                                                 \
+        if (!(ctx)->guide->is_batch) {                                                                                                    \
+            edmp::set_error("%s: the bound guide is a single-scene guide (edmp_scene_set); it has its own per-scene entry point", what); \
+            return EDMP_ERR_STATE;                                                                                                        \
+        }                                                                                                                                 \
+        if ((S_) != (ctx)->guide->S || (B_) < 1 || (int64_t)(S_) * (B_) != (ctx)->guide->B) {                                          \
+            edmp::set_error("%s: %d scenes x %d rows given, the bound scene batch holds %d scenes x %d rows", what, (int)(S_), (int)(B_), \
+                            (ctx)->guide->S, (ctx)->guide->rps);                                                                         \
+            return EDMP_ERR_ARG;                                                                                                          \
+        }                                                                                                                                 \
     } while (0)
 
 }  // namespace edmp

@@ -485,10 +485,13 @@ __global__ void mix_gradient_kernel(const float* __restrict__ graw, const double
     out[i] = (1.0 - gn) * (double)gv + gn * (double)(gv / nrm);
 }
 
+// wave s (= block s) takes the n values [s*n, (s+1)*n) and writes the index inside its own segment to out[s]: grid 1 is the arg-min of one
+// batch, grid S the per-scene arg-min of a scene batch (n = rows per scene) - ONE statement of the comparison for both
 __global__ void argmin_kernel(const float* __restrict__ v, int n, int* __restrict__ out) {
-    // single wave; torch.argmin semantics (lib/guide.py:650): first index on ties, and NaN compares as the smallest
+    // single wave per segment; torch.argmin semantics (lib/guide.py:650): first index on ties, and NaN compares as the smallest
     // value, so the first NaN row wins if there is one
     int lane = threadIdx.x;
+    v += (size_t)blockIdx.x * n;
     float best = INFINITY;
     int bi = 0x7fffffff;
     bool bnan = false;
@@ -516,7 +519,7 @@ __global__ void argmin_kernel(const float* __restrict__ v, int n, int* __restric
             bnan = on;
         }
     }
-    if (lane == 0) out[0] = (bi == 0x7fffffff) ? 0 : bi;
+    if (lane == 0) out[blockIdx.x] = (bi == 0x7fffffff) ? 0 : bi;
 }
 
 // *realloc (optional) is set when the blocks were replaced: captured graphs baked the old pointers in (the pool can hand
@@ -697,6 +700,12 @@ static int scene_tables_set(edmp_ctx* ctx, int S, const int32_t* nos, const doub
     g->cls_no_h.clear();
     g->cls_scene_h.clear();
     g->cls_off_h.clear();
+    g->scene_no_h.clear();
+    g->scene_off_h.clear();
+    for (int s = 0, o0 = 0; s < S; o0 += nos[s], ++s) {
+        g->scene_no_h.push_back(nos[s]);
+        g->scene_off_h.push_back(o0);
+    }
     size_t table_floats = 0;
     for (int s = 0; s < S; ++s)
         for (int c = 0; c < ncls[s]; ++c) {
@@ -780,7 +789,9 @@ extern "C" int edmp_scene_set(edmp_ctx* ctx, const double* obstacle_config, int 
     ctx->epoch++;
     EDMP_REQUIRE(G >= 1 && T >= 1, "need at least one guide class and one step");
     const int32_t nos[1] = {no}, ncls[1] = {G};
-    return scene_tables_set(ctx, 1, nos, obstacle_config, ncls, clearance, expansion, T, link_half_extents, dh, static_frames);
+    int rc = scene_tables_set(ctx, 1, nos, obstacle_config, ncls, clearance, expansion, T, link_half_extents, dh, static_frames);
+    if (ctx->guide) ctx->guide->is_batch = false;
+    return rc;
 }
 
 extern "C" int edmp_scene_batch_set(edmp_ctx* ctx, int S, const int32_t* n_obstacles, const double* obstacle_config, const int32_t* n_classes,
@@ -796,7 +807,9 @@ extern "C" int edmp_scene_batch_set(edmp_ctx* ctx, int S, const int32_t* n_obsta
         EDMP_REQUIRE(n_classes[s] >= 1, "edmp_scene_batch_set: scene %d has %d guide classes (need >= 1)", s, n_classes[s]);
     }
     ctx->epoch++;
-    return scene_tables_set(ctx, S, n_obstacles, obstacle_config, n_classes, clearance, expansion, T, link_half_extents, dh, static_frames);
+    int rc = scene_tables_set(ctx, S, n_obstacles, obstacle_config, n_classes, clearance, expansion, T, link_half_extents, dh, static_frames);
+    if (ctx->guide) ctx->guide->is_batch = true;
+    return rc;
 }
 
 extern "C" int edmp_rows_set(edmp_ctx* ctx, const int32_t* row_class, const float* method, const double* grad_norm, const double* sched, int B,
@@ -842,7 +855,7 @@ extern "C" int edmp_rows_set(edmp_ctx* ctx, const int32_t* row_class, const floa
 extern "C" int edmp_argmin_dev(edmp_ctx* ctx, const float* v_dev, int n, int* index_host) {
     EDMP_REQUIRE(ctx && v_dev && index_host && n >= 1, "edmp_argmin_dev: bad arguments");
     EDMP_HIP_CHECK(hipSetDevice(ctx->device));
-    if (!ctx->d_int) EDMP_HIP_CHECK(hipMalloc((void**)&ctx->d_int, sizeof(int)));  // kept for the life of the context
+    if (!ctx->d_int) EDMP_HIP_CHECK(hipMalloc((void**)&ctx->d_int, EDMP_MAX_SCENES * sizeof(int)));  // kept for the life of the context
     int* d_idx = ctx->d_int;
     hipLaunchKernelGGL(argmin_kernel, dim3(1), dim3(64), 0, ctx->stream, v_dev, n, d_idx);
     hipError_t e = hipMemcpyAsync(index_host, d_idx, sizeof(int), hipMemcpyDeviceToHost, ctx->stream);
@@ -940,3 +953,36 @@ extern "C" int edmp_row_swept_volumes_dev(edmp_ctx* ctx, const double* X_dev, in
     return EDMP_OK;
 }
 
+
+// the best-trajectory volumes of a whole scene batch: every row against its own scene's obstacles and start / goal pair, then one
+// arg-min wave per scene
+extern "C" int edmp_scenes_swept_volumes_dev(edmp_ctx* ctx, const double* X_dev, int S, int B, int N, const double* starts, const double* goals,
+                                             float* volumes_dev, int* best_index_host) {
+    EDMP_REQUIRE_SCENE_BATCH(ctx, S, B, "edmp_scenes_swept_volumes_dev");
+    Guide* g = ctx->guide;
+    EDMP_REQUIRE(N >= 3 && N <= 64, "edmp_scenes_swept_volumes_dev: need 3 <= N <= 64 waypoints per row (got %d)", N);
+    EDMP_REQUIRE(X_dev, "edmp_scenes_swept_volumes_dev: X_dev is NULL");
+    EDMP_REQUIRE(starts && goals, "edmp_scenes_swept_volumes_dev: starts and goals (S,7) are required (got %s NULL)",
+                 !starts && !goals ? "both" : (!starts ? "starts" : "goals"));
+    EDMP_HIP_CHECK(hipSetDevice(ctx->device));
+    sampler_end_run(ctx);  // (the guide's start / goal pairs are replaced)
+    const int n = S * B;
+    bool moved = false;
+    int rc = ensure_scratch(ctx, g, n, N - 2, &moved);
+    if (moved) ctx->epoch++;
+    if (rc) return rc;
+    rc = guide_set_startgoal_scenes(ctx, S, starts, goals);
+    if (rc) return rc;
+    float* dst = volumes_dev ? volumes_dev : g->vol_rows;
+    // t = 0: a class block is uninflated there, so ANY class of the row's scene serves - the row's own (class 0 would be scene 0's table)
+    rc = launch_guide<GM_SV_ROWSUM, double>(ctx, X_dev, N, 1, n, N - 2, 0, 1, 0, dst, nullptr);
+    if (rc) return rc;
+    int* d_idx = reinterpret_cast<int*>(g->rowsq);  // scratch reuse (S*B doubles hold S ints)
+    hipLaunchKernelGGL(argmin_kernel, dim3(S), dim3(64), 0, ctx->stream, dst, B, d_idx);
+    EDMP_HIP_CHECK(hipGetLastError());
+    if (best_index_host) {
+        EDMP_HIP_CHECK(hipMemcpyAsync(best_index_host, d_idx, S * sizeof(int), hipMemcpyDeviceToHost, ctx->stream));
+        EDMP_HIP_CHECK(hipStreamSynchronize(ctx->stream));
+    }
+    return EDMP_OK;
+}

@@ -20,6 +20,7 @@
 // Every sum runs in one fixed order that depends on the row's own data only: results are bit-identical between runs, for any B and
 // any position of the row in the batch.  No floating-point atomics.
 #include "common.h"
+#include "guide.h"
 
 #include <cmath>
 
@@ -258,10 +259,15 @@ __device__ __forceinline__ Pick block_pick(Pick mine, Pick* s_pick) {
 // volumes (B,) f32, key (B,) f64 -> out[0]: m = first minimum of the volumes with NaN as the smallest value (argmin_kernel's rule,
 // lib/guide.py:650); a NaN minimum keeps m; else among the rows with (double)v_b < (double)v_m + trust the one with the smallest
 // finite key, first index on ties (infer_serial.py:119-129); m when no such row has a finite key.
+// Block s applies the rule to the rows [s*B, (s+1)*B) - candidates, minimum and pick all inside them - and writes the index inside that
+// segment to out[s]: grid 1 is one batch, grid S a scene batch with B rows per scene.
 __global__ __launch_bounds__(kMetricsThreads) void select_row_kernel(const float* __restrict__ vol, const double* __restrict__ key, int B, double trust,
                                                                      int* __restrict__ out) {
     __shared__ Pick s_pick[kMetricsThreads / kWave];
     const int tid = threadIdx.x;
+    vol += (size_t)blockIdx.x * B;
+    key += (size_t)blockIdx.x * B;
+    out += blockIdx.x;
     const Pick none = {3, 0.0, 0x7fffffff};
     Pick mine = none;
     for (int b = tid; b < B; b += kMetricsThreads) {
@@ -332,10 +338,24 @@ extern "C" int edmp_select_row_dev(edmp_ctx* ctx, const float* volumes_dev, cons
     EDMP_REQUIRE(ctx && volumes_dev && key_dev && index_host && B >= 1, "edmp_select_row_dev: need a context, volumes, key, index and B >= 1");
     EDMP_REQUIRE(!std::isnan(trust_region) && trust_region >= 0.0, "edmp_select_row_dev: trust_region must be >= 0 (got %g)", trust_region);
     EDMP_HIP_CHECK(hipSetDevice(ctx->device));
-    if (!ctx->d_int) EDMP_HIP_CHECK(hipMalloc((void**)&ctx->d_int, sizeof(int)));  // kept for the life of the context
+    if (!ctx->d_int) EDMP_HIP_CHECK(hipMalloc((void**)&ctx->d_int, EDMP_MAX_SCENES * sizeof(int)));  // kept for the life of the context
     hipLaunchKernelGGL(select_row_kernel, dim3(1), dim3(kMetricsThreads), 0, ctx->stream, volumes_dev, key_dev, B, trust_region, ctx->d_int);
     EDMP_HIP_CHECK(hipGetLastError());
     EDMP_HIP_CHECK(hipMemcpyAsync(index_host, ctx->d_int, sizeof(int), hipMemcpyDeviceToHost, ctx->stream));
+    EDMP_HIP_CHECK(hipStreamSynchronize(ctx->stream));
+    return EDMP_OK;
+}
+
+extern "C" int edmp_scenes_select_rows_dev(edmp_ctx* ctx, const float* volumes_dev, const double* key_dev, int S, int B, double trust_region,
+                                           int* index_host) {
+    EDMP_REQUIRE_SCENE_BATCH(ctx, S, B, "edmp_scenes_select_rows_dev");
+    EDMP_REQUIRE(volumes_dev && key_dev && index_host, "edmp_scenes_select_rows_dev: need volumes, key and index");
+    EDMP_REQUIRE(!std::isnan(trust_region) && trust_region >= 0.0, "edmp_scenes_select_rows_dev: trust_region must be >= 0 (got %g)", trust_region);
+    EDMP_HIP_CHECK(hipSetDevice(ctx->device));
+    if (!ctx->d_int) EDMP_HIP_CHECK(hipMalloc((void**)&ctx->d_int, EDMP_MAX_SCENES * sizeof(int)));  // kept for the life of the context
+    hipLaunchKernelGGL(select_row_kernel, dim3(S), dim3(kMetricsThreads), 0, ctx->stream, volumes_dev, key_dev, B, trust_region, ctx->d_int);
+    EDMP_HIP_CHECK(hipGetLastError());
+    EDMP_HIP_CHECK(hipMemcpyAsync(index_host, ctx->d_int, S * sizeof(int), hipMemcpyDeviceToHost, ctx->stream));
     EDMP_HIP_CHECK(hipStreamSynchronize(ctx->stream));
     return EDMP_OK;
 }

@@ -172,15 +172,27 @@ __device__ __noinline__ bool obb_cylinder_overlap(const double Rb[3][3], const d
     return hit;
 }
 
-// X (B, 7, N) f64.  flags: ok[B], first[B] (first colliding waypoint, -1 none), within[B] (all waypoints inside the limits)
-__global__ __launch_bounds__(256) void success_rows_kernel(const double* __restrict__ X, int B, int N, int S, const double* __restrict__ obb,
-                                                           const int32_t* __restrict__ kind, int no, Robot64 rc, int32_t* __restrict__ ok,
+// the obstacle rows of every scene of the guide object inside obb / kind: scene s owns rows [off[s], off[s] + cnt[s]); row r of the
+// state belongs to scene r / rps.  One scene: rps = B, off[0] = 0, cnt[0] = no.
+struct SceneSlices {
+    int rps;
+    int off[EDMP_MAX_SCENES], cnt[EDMP_MAX_SCENES];
+};
+
+// X (B, 7, N) f64.  flags: ok[B], first[B] (first colliding waypoint, -1 none), within[B] (all waypoints inside the limits).
+// Workgroup r stages the boxes and kinds of ITS scene only; everything after the staging is the row's own arithmetic.
+__global__ __launch_bounds__(256) void success_rows_kernel(const double* __restrict__ X, int B, int N, int substeps, const double* __restrict__ obb,
+                                                           const int32_t* __restrict__ kind, SceneSlices sl, Robot64 rc, int32_t* __restrict__ ok,
                                                            int32_t* __restrict__ first, int32_t* __restrict__ within) {
     __shared__ double s_ob[EDMP_MAX_OBSTACLES * 16];
     __shared__ int s_kind[EDMP_MAX_OBSTACLES];
     __shared__ int s_first, s_out;
     const int r = blockIdx.x;
     const int tid = threadIdx.x;
+    const int scene = r / sl.rps;
+    const int no = min(sl.cnt[scene], EDMP_MAX_OBSTACLES);
+    obb += (size_t)sl.off[scene] * 16;
+    kind += sl.off[scene];
     for (int i = tid; i < no * 16; i += 256) s_ob[i] = obb[i];
     for (int i = tid; i < no; i += 256) s_kind[i] = kind[i];
     if (tid == 0) {
@@ -199,15 +211,15 @@ __global__ __launch_bounds__(256) void success_rows_kernel(const double* __restr
         }
         if (bad) atomicOr(&s_out, 1);
     }
-    const int nc = (N - 1) * S + 1;
+    const int nc = (N - 1) * substeps + 1;
     for (int c = tid; c < nc; c += 256) {
-        const int i = c / S, s = c - i * S;
+        const int i = c / substeps, s = c - i * substeps;
         double q[7];
         if (s == 0) {
 #pragma unroll
             for (int j = 0; j < 7; ++j) q[j] = xr[j * N + i];
         } else {
-            const double f = (double)s / (double)S;
+            const double f = (double)s / (double)substeps;
 #pragma unroll
             for (int j = 0; j < 7; ++j) q[j] = (1.0 - f) * xr[j * N + i] + f * xr[j * N + i + 1];
         }
@@ -256,16 +268,21 @@ __global__ __launch_bounds__(256) void success_rows_kernel(const double* __restr
     if (tid == 0) {
         const int fc = s_first;
         const int w = s_out ? 0 : 1;
-        first[r] = (fc == 0x7fffffff) ? -1 : fc / S;
+        first[r] = (fc == 0x7fffffff) ? -1 : fc / substeps;
         within[r] = w;
         ok[r] = (w && fc == 0x7fffffff) ? 1 : 0;
     }
 }
 
-// counts[0] = rows ok, [1] = rows within the limits, [2] = rows without a collision, [3] = B
+// counts[0] = rows ok, [1] = rows within the limits, [2] = rows without a collision, [3] = B; block s counts the rows [s*B, (s+1)*B) into
+// quadruple s (grid 1: the whole batch; a scene batch: one block per scene, B = rows per scene)
 __global__ void count_flags_kernel(const int32_t* __restrict__ ok, const int32_t* __restrict__ first, const int32_t* __restrict__ within, int B,
                                    int32_t* __restrict__ counts) {
     __shared__ int s[3];
+    ok += (size_t)blockIdx.x * B;
+    first += (size_t)blockIdx.x * B;
+    within += (size_t)blockIdx.x * B;
+    counts += 4 * blockIdx.x;
     if (threadIdx.x < 3) s[threadIdx.x] = 0;
     __syncthreads();
     int a = 0, w = 0, f = 0;
@@ -290,6 +307,35 @@ __global__ void count_flags_kernel(const int32_t* __restrict__ ok, const int32_t
 
 using namespace edmp;
 
+// flags: room for `rows` rows and `quads` count quadruples; grow-only, from the context's pool
+static int ensure_flags(edmp_ctx* ctx, Guide* g, int rows, int quads) {
+    if (g->flags && g->flags_B >= rows && g->flags_Q >= quads) return EDMP_OK;
+    const int nb = std::max(rows, g->flags_B), nq = std::max(quads, g->flags_Q);
+    ctx_release(ctx, g->flags);
+    g->flags = nullptr;
+    g->flags_B = 0;
+    g->flags_Q = 1;
+    if (int rc = ctx_alloc(ctx, (void**)&g->flags, ((size_t)3 * nb + 4 * (size_t)nq) * sizeof(int32_t))) return rc;
+    g->flags_B = nb;
+    g->flags_Q = nq;
+    return EDMP_OK;
+}
+
+static Robot64 robot64_of(const Guide* g, const double* dh_f64) {
+    Robot64 rc;
+    for (int j = 0; j < 7; ++j)
+        for (int k = 0; k < 4; ++k) rc.dh[j][k] = dh_f64 ? dh_f64[j * 4 + k] : (double)g->rc.dh[j][k];
+    for (int l = 0; l < 9; ++l) {
+        for (int k = 0; k < 12; ++k) rc.sf[l][k] = (double)g->rc.sf[l][k];
+        for (int k = 0; k < 3; ++k) rc.he[l][k] = (double)g->rc.he[l][k];
+    }
+    for (int j = 0; j < 7; ++j) {
+        rc.qlo[j] = g->rc.qlo[j];
+        rc.qhi[j] = g->rc.qhi[j];
+    }
+    return rc;
+}
+
 extern "C" int edmp_scene_set_shapes(edmp_ctx* ctx, const int32_t* kind, int n_obstacles) {
     EDMP_REQUIRE(ctx && ctx->guide && ctx->guide->obb && ctx->guide->kind, "edmp_scene_set_shapes: call edmp_scene_set first");
     EDMP_REFUSE_SCENE_BATCH(ctx->guide, "edmp_scene_set_shapes");
@@ -309,34 +355,75 @@ extern "C" int edmp_success_rows_dev(edmp_ctx* ctx, const double* X_dev, int B, 
     Guide* g = ctx->guide;
     EDMP_REQUIRE(X_dev && B >= 1 && N >= 2 && substeps >= 1 && substeps <= 64, "edmp_success_rows_dev: need B >= 1, N >= 2, 1 <= substeps <= 64");
     EDMP_HIP_CHECK(hipSetDevice(ctx->device));
-    if (g->flags_B < B) {
-        ctx_release(ctx, g->flags);
-        g->flags = nullptr;
-        g->flags_B = 0;
-        if (int rc = ctx_alloc(ctx, (void**)&g->flags, ((size_t)3 * B + 4) * sizeof(int32_t))) return rc;
-        g->flags_B = B;
-    }
+    if (int rc = ensure_flags(ctx, g, B, 1)) return rc;
     int32_t* ok = ok_dev ? ok_dev : g->flags;
     int32_t* first = first_dev ? first_dev : g->flags + g->flags_B;
     int32_t* within = within_dev ? within_dev : g->flags + 2 * (size_t)g->flags_B;
     int32_t* counts = g->flags + 3 * (size_t)g->flags_B;
-    Robot64 rc;
-    for (int j = 0; j < 7; ++j)
-        for (int k = 0; k < 4; ++k) rc.dh[j][k] = dh_f64 ? dh_f64[j * 4 + k] : (double)g->rc.dh[j][k];
-    for (int l = 0; l < 9; ++l) {
-        for (int k = 0; k < 12; ++k) rc.sf[l][k] = (double)g->rc.sf[l][k];
-        for (int k = 0; k < 3; ++k) rc.he[l][k] = (double)g->rc.he[l][k];
-    }
-    for (int j = 0; j < 7; ++j) {
-        rc.qlo[j] = g->rc.qlo[j];
-        rc.qhi[j] = g->rc.qhi[j];
-    }
-    hipLaunchKernelGGL(success_rows_kernel, dim3(B), dim3(256), 0, ctx->stream, X_dev, B, N, substeps, g->obb, g->kind, g->no, rc, ok, first, within);
+    const Robot64 rc = robot64_of(g, dh_f64);
+    SceneSlices sl = {};
+    sl.rps = B;
+    sl.cnt[0] = g->no;
+    hipLaunchKernelGGL(success_rows_kernel, dim3(B), dim3(256), 0, ctx->stream, X_dev, B, N, substeps, g->obb, g->kind, sl, rc, ok, first, within);
     EDMP_HIP_CHECK(hipGetLastError());
     if (counts_host) {
         hipLaunchKernelGGL(count_flags_kernel, dim3(1), dim3(256), 0, ctx->stream, ok, first, within, B, counts);
         EDMP_HIP_CHECK(hipGetLastError());
         EDMP_HIP_CHECK(hipMemcpyAsync(counts_host, counts, 4 * sizeof(int32_t), hipMemcpyDeviceToHost, ctx->stream));
+        EDMP_HIP_CHECK(hipStreamSynchronize(ctx->stream));
+    }
+    return EDMP_OK;
+}
+
+extern "C" int edmp_scene_batch_set_shapes(edmp_ctx* ctx, const int32_t* kind, int n_total) {
+    EDMP_REQUIRE(ctx, "edmp_scene_batch_set_shapes: null context");
+    Guide* g = ctx->guide;
+    if (!g || !g->obb || !g->kind) {
+        set_error("edmp_scene_batch_set_shapes: call edmp_scene_batch_set first");
+        return EDMP_ERR_STATE;
+    }
+    if (!g->is_batch) {
+        set_error("edmp_scene_batch_set_shapes: the bound guide is a single-scene guide (edmp_scene_set); use edmp_scene_set_shapes");
+        return EDMP_ERR_STATE;
+    }
+    const int total = g->scene_off_h.back() + g->scene_no_h.back();
+    EDMP_REQUIRE(kind && n_total == total, "edmp_scene_batch_set_shapes: need %d kinds (one per obstacle of the batch's %d scenes, scene after scene), got %d",
+                 total, g->S, n_total);
+    for (int i = 0; i < n_total; ++i) EDMP_REQUIRE(kind[i] == 0 || kind[i] == 1, "obstacle %d: kind must be 0 (cuboid) or 1 (cylinder)", i);
+    EDMP_HIP_CHECK(hipSetDevice(ctx->device));
+    EDMP_HIP_CHECK(hipMemcpyAsync(g->kind, kind, n_total * sizeof(int32_t), hipMemcpyHostToDevice, ctx->stream));
+    EDMP_HIP_CHECK(hipStreamSynchronize(ctx->stream));
+    return EDMP_OK;
+}
+
+extern "C" int edmp_scenes_success_rows_dev(edmp_ctx* ctx, const double* X_dev, int S, int B, int N, int substeps, const double* dh_f64, int32_t* ok_dev,
+                                            int32_t* first_dev, int32_t* within_dev, int32_t* counts_host) {
+    EDMP_REQUIRE_SCENE_BATCH(ctx, S, B, "edmp_scenes_success_rows_dev");
+    Guide* g = ctx->guide;
+    EDMP_REQUIRE(X_dev && N >= 2 && substeps >= 1 && substeps <= 64, "edmp_scenes_success_rows_dev: need X, N >= 2 (got %d), 1 <= substeps <= 64 (got %d)", N,
+                 substeps);
+    EDMP_HIP_CHECK(hipSetDevice(ctx->device));
+    const int n = S * B;
+    const int32_t* had = g->flags;
+    if (int rc = ensure_flags(ctx, g, n, S)) return rc;
+    if (g->flags != had) ctx->epoch++;
+    int32_t* ok = ok_dev ? ok_dev : g->flags;
+    int32_t* first = first_dev ? first_dev : g->flags + g->flags_B;
+    int32_t* within = within_dev ? within_dev : g->flags + 2 * (size_t)g->flags_B;
+    int32_t* counts = g->flags + 3 * (size_t)g->flags_B;
+    const Robot64 rc = robot64_of(g, dh_f64);
+    SceneSlices sl = {};
+    sl.rps = B;
+    for (int s = 0; s < S; ++s) {
+        sl.off[s] = g->scene_off_h[s];
+        sl.cnt[s] = g->scene_no_h[s];
+    }
+    hipLaunchKernelGGL(success_rows_kernel, dim3(n), dim3(256), 0, ctx->stream, X_dev, n, N, substeps, g->obb, g->kind, sl, rc, ok, first, within);
+    EDMP_HIP_CHECK(hipGetLastError());
+    if (counts_host) {
+        hipLaunchKernelGGL(count_flags_kernel, dim3(S), dim3(256), 0, ctx->stream, ok, first, within, B, counts);
+        EDMP_HIP_CHECK(hipGetLastError());
+        EDMP_HIP_CHECK(hipMemcpyAsync(counts_host, counts, (size_t)S * 4 * sizeof(int32_t), hipMemcpyDeviceToHost, ctx->stream));
         EDMP_HIP_CHECK(hipStreamSynchronize(ctx->stream));
     }
     return EDMP_OK;

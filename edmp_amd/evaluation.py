@@ -5,7 +5,8 @@ lib/environment.py:632-680: position control through the waypoints, contact quer
 spawned cuboids AND true cylinders :230-268) and tallies `t_success` (infer_serial.py:94-99,165-168).  pybullet is not
 available offline, so the criterion is restated geometrically — EXACT oriented-box / finite-cylinder tests instead of the
 guide's conservative world-AABB overlap — and evaluated for every row of the batch by `edmp_success_rows_dev`
-(csrc/success.hip) through `IntersectionVolumeGuide.success_rows`.  It is a stand-in (no dynamics, box-shaped links),
+(csrc/success.hip) through `IntersectionVolumeGuide.success_rows`, and for the S * B rows of a scene batch, each against its own scene, by
+`edmp_scenes_success_rows_dev` through `SceneBatch.success_rows`.  It is a stand-in (no dynamics, box-shaped links),
 reported as such.  There is no host fallback: the checker of the kernel lives in oracle/success_oracle.py (tests only).
 
 Metrics.  lib/metrics.py:11-125 (`MetricsCalculator`, host NumPy / torch-CPU in the reference too, never called by its
@@ -39,10 +40,12 @@ def geometric_success(trajectory, guide, substeps: int = 4) -> dict:
 
 def success_rate(trajectories, guide, substeps: int = 4) -> dict:
     """every row of a batch (B, 7, N): dict(rows_ok, rows, rate, ok (B,), first (B,), within (B,)) - the batch form of the
-    reference's running tally `t_success / i` (infer_serial.py:99)."""
+    reference's running tally `t_success / i` (infer_serial.py:99).  `guide` may be a guide.SceneBatch with trajectories (S, B, 7, N) or
+    (S*B, 7, N): the per-row arrays are then (S, B) and the counts and rates (S,), one entry per scene (one launch for all scenes)."""
     r = guide.success_rows(trajectories, substeps=substeps)
-    r["rate"] = r["rows_ok"] / max(r["rows"], 1)
-    r["collision_free_rate"] = r["rows_collision_free"] / max(r["rows"], 1)  # the reference's criterion (lib/environment.py:672)
+    rows = np.maximum(r["rows"], 1) if np.ndim(r["rows"]) else max(r["rows"], 1)
+    r["rate"] = r["rows_ok"] / rows
+    r["collision_free_rate"] = r["rows_collision_free"] / rows  # the reference's criterion (lib/environment.py:672)
     return r
 
 

@@ -326,8 +326,14 @@ def scene_batch_tables(scenes):
 class SceneBatch:
     """S per-scene guides (IntersectionVolumeGuide, one context, equal batch_size and T, one robot) as ONE guide object of the
     library: scene s owns rows [s*B, (s+1)*B) of a (S*B, 7, N) run (Diffusion.denoise_guided_scenes).  The per-scene guides stay
-    what they were - the IK filter, row_swept_volumes, choose_best_trajectory and success_rows go through them; the batch lives in
-    its own resident slot, so switching between it and its scenes re-uploads nothing while both stay resident."""
+    what they were (the IK filter goes through them); the batch lives in its own resident slot, so switching between it and its
+    scenes re-uploads nothing while both stay resident.
+
+    The finished state is scored on the batch itself, one launch per step for all S scenes: row_swept_volumes, select_rows,
+    choose_best_trajectories and success_rows take X as (S, B, 7, N) or (S*B, 7, N), ndarray or device tensor (the tensor of
+    denoise_guided_scenes(..., return_device=True) is adopted, not copied) and give, scene by scene, exactly what the scene's own
+    guide gives for X[s].  The obstacle kinds of the success check are the guides' own at construction (a guide without kinds counts
+    as all cuboids); set_obstacle_kinds replaces them."""
 
     def __init__(self, guides):
         guides = list(guides)
@@ -351,6 +357,10 @@ class SceneBatch:
                  method=np.asarray(g.guide_cfgs["guidance_method"], dtype=np.float32).reshape(-1),
                  grad_norm=np.asarray(g.guide_cfgs["grad_norm"], dtype=np.float64).reshape(-1), guidance_schedule=g._sched) for g in guides])
         self._slot = new_slot_key()
+        self._kinds = None
+        if any(g._kinds is not None for g in guides):
+            self._kinds = np.ascontiguousarray(np.concatenate(
+                [g._kinds if g._kinds is not None else np.zeros(g.obstacle_config.shape[0], dtype=np.int32) for g in guides]).astype(np.int32))
         self._bind()
 
     def _bind(self):
@@ -376,4 +386,117 @@ class SceneBatch:
                                   _capi.as_pd(tb["guidance_schedule"]), self.n_scenes * self.batch_size, self.T),
             "edmp_rows_set",
         )
+        if self._kinds is not None:
+            _capi.check(ctx.lib.edmp_scene_batch_set_shapes(ctx.h, _capi.as_pi32(self._kinds), int(self._kinds.shape[0])), "edmp_scene_batch_set_shapes")
         ctx.bound_guide = self
+
+    # ---- scoring the finished state of the batch ------------------------------------------------------------------------
+    def _check_kinds(self, kinds):
+        if isinstance(kinds, (list, tuple)) and len(kinds) and np.ndim(kinds[0]) == 1:
+            kinds = np.concatenate([np.asarray(k).reshape(-1) for k in kinds])  # one array per scene
+        k = np.ascontiguousarray(np.asarray(kinds, dtype=np.int32).reshape(-1))
+        total = int(np.sum(self.tables["n_obstacles"]))
+        if k.shape[0] != total or not np.all((k == 0) | (k == 1)):
+            raise ValueError(f"obstacle_kinds: one entry per obstacle of the batch ({total}, scene after scene; got {k.shape[0]}), 0 = cuboid, 1 = cylinder")
+        return k
+
+    def set_obstacle_kinds(self, kinds):
+        """IntersectionVolumeGuide.set_obstacle_kinds for the batch: the kinds of all obstacles, scene after scene (one flat array or
+        one array per scene).  Only success_rows reads them; the per-scene guides keep their own."""
+        self._kinds = self._check_kinds(kinds)
+        self._bind()
+        _capi.check(self.ctx.lib.edmp_scene_batch_set_shapes(self.ctx.h, _capi.as_pi32(self._kinds), int(self._kinds.shape[0])), "edmp_scene_batch_set_shapes")
+
+    def _state(self, X):
+        """X as (S, B, 7, N) or (S*B, 7, N), ndarray or device tensor -> the contiguous (S*B, 7, N) f64 device tensor (shape checked first)"""
+        S, B = self.n_scenes, self.batch_size
+        shape = tuple(X.shape) if isinstance(X, torch.Tensor) else np.shape(X)
+        if not ((len(shape) == 4 and shape[:3] == (S, B, 7)) or (len(shape) == 3 and shape[:2] == (S * B, 7))):
+            raise ValueError(f"trajectories must be ({S}, {B}, 7, N) or ({S * B}, 7, N), got {tuple(shape)}")
+        N = int(shape[-1])
+        if isinstance(X, torch.Tensor) and X.is_cuda:
+            Xd = self.ctx.adopt(X.to(torch.float64).contiguous())
+        else:
+            Xd = self.ctx.to_dev(X if isinstance(X, torch.Tensor) else np.asarray(X, dtype=np.float64), torch.float64)
+        return Xd.reshape(S * B, 7, N), N
+
+    def _pairs(self, starts, goals):
+        out = []
+        for name, v in (("starts", starts), ("goals", goals)):
+            if v is None:
+                raise ValueError(f"{name} is required: ({self.n_scenes}, 7)")
+            a = np.ascontiguousarray(np.asarray(v, dtype=np.float64))
+            if a.shape != (self.n_scenes, 7):
+                raise ValueError(f"{name} must be ({self.n_scenes}, 7), got {a.shape}")
+            out.append(a)
+        return out
+
+    def _volumes(self, starts, goals, X, want_index):
+        s, g = self._pairs(starts, goals)
+        Xd, N = self._state(X)
+        self._bind()
+        ctx, S, B = self.ctx, self.n_scenes, self.batch_size
+        vols = ctx.empty((S * B,), torch.float32)
+        idx = (C.c_int * S)() if want_index else None
+        _capi.check(ctx.lib.edmp_scenes_swept_volumes_dev(ctx.h, ptr(Xd), S, B, N, _capi.as_pd(s), _capi.as_pd(g), ptr(vols), idx), "edmp_scenes_swept_volumes_dev")
+        Xd.record_stream(ctx.stream)
+        return Xd, vols, (np.array(idx[:], dtype=np.int64) if want_index else None)
+
+    def row_swept_volumes(self, starts, goals, trajectories):
+        """per scene what IntersectionVolumeGuide.row_swept_volumes gives: ((S, B) f32 t = 0 swept volumes, (S,) arg-min inside the scene)"""
+        _, vols, idx = self._volumes(starts, goals, trajectories, True)
+        return self.ctx.to_host(vols).reshape(self.n_scenes, self.batch_size), idx
+
+    def select_rows(self, starts, goals, trajectories, prefer=None, volume_trust_region: float = 0.0008):
+        """IntersectionVolumeGuide.select_row for every scene of the batch: (indices (S,) inside the scene, volumes (S, B) f32, metrics
+        dict of (S, B) f64 arrays or None).  prefer=None: the first arg-min per scene; "shortest" / "smoothest": the trust-region pick
+        (edmp_scenes_select_rows_dev on ONE edmp_metrics_rows_dev call over the S*B rows)."""
+        if prefer not in (None, "shortest", "smoothest"):
+            raise ValueError(f"prefer must be None, 'shortest' or 'smoothest', got {prefer!r}")
+        ctx, S, B = self.ctx, self.n_scenes, self.batch_size
+        Xd, vols, idx = self._volumes(starts, goals, trajectories, prefer is None)
+        if prefer is None:
+            return idx, ctx.to_host(vols).reshape(S, B), None
+        from .evaluation import metrics_rows_on
+
+        met = metrics_rows_on(ctx, Xd, return_device=True)
+        with torch.cuda.stream(ctx.stream):
+            key = met["joint_path_length"] if prefer == "shortest" else torch.neg(met["joint_sparc"])  # SPARC <= 0: closest to 0 = largest
+        pick = (C.c_int * S)()
+        _capi.check(ctx.lib.edmp_scenes_select_rows_dev(ctx.h, ptr(vols), ptr(key), S, B, C.c_double(float(volume_trust_region)), pick), "edmp_scenes_select_rows_dev")
+        with torch.cuda.stream(ctx.stream):
+            m = torch.stack([met[k] for k in met])
+        mh = ctx.to_host(m)
+        return np.array(pick[:], dtype=np.int64), ctx.to_host(vols).reshape(S, B), {k: mh[i].reshape(S, B).copy() for i, k in enumerate(met)}
+
+    def choose_best_trajectories(self, starts, goals, trajectories, *, prefer=None, volume_trust_region: float = 0.0008):
+        """choose_best_trajectory (lib/guide.py:637-653) for every scene: (S, 7, N), in the kind of array `trajectories` is"""
+        idx, _, _ = self.select_rows(starts, goals, trajectories, prefer=prefer, volume_trust_region=volume_trust_region)
+        S, B = self.n_scenes, self.batch_size
+        rows = np.arange(S) * B + idx
+        flat = trajectories.reshape(S * B, 7, -1)
+        return flat[torch.as_tensor(rows, device=flat.device)] if isinstance(flat, torch.Tensor) else np.asarray(flat)[rows]
+
+    def success_rows(self, trajectories, substeps: int = 4, return_device: bool = False):
+        """IntersectionVolumeGuide.success_rows for every scene (edmp_scenes_success_rows_dev): the same dict, the per-row arrays ok,
+        first, within, collision_free shaped (S, B) - each row checked against its own scene's obstacles and kinds - and the counts
+        rows_ok, rows_within, rows_collision_free, rows as (S,) int arrays, one entry per scene."""
+        Xd, N = self._state(trajectories)
+        self._bind()
+        ctx, S, B = self.ctx, self.n_scenes, self.batch_size
+        flags = ctx.empty((3, S * B), torch.int32)
+        counts = (C.c_int32 * (4 * S))()
+        dh = np.ascontiguousarray(franka.dh_table_f64())
+        _capi.check(ctx.lib.edmp_scenes_success_rows_dev(ctx.h, ptr(Xd), S, B, N, int(substeps), _capi.as_pd(dh), C.c_void_p(flags[0].data_ptr()),
+                                                         C.c_void_p(flags[1].data_ptr()), C.c_void_p(flags[2].data_ptr()), counts), "edmp_scenes_success_rows_dev")
+        cn = np.array(counts[:], dtype=np.int64).reshape(S, 4)
+        out = dict(rows_ok=cn[:, 0].copy(), rows_within=cn[:, 1].copy(), rows_collision_free=cn[:, 2].copy(), rows=cn[:, 3].copy())
+        if return_device:
+            f = flags.view(3, S, B)
+            with torch.cuda.stream(ctx.stream):
+                cf = f[1] < 0
+            out.update(ok=f[0], first=f[1], within=f[2], collision_free=cf)
+        else:
+            f = ctx.to_host(flags).reshape(3, S, B)
+            out.update(ok=f[0].astype(bool), first=f[1].copy(), within=f[2].astype(bool), collision_free=f[1] < 0)
+        return out

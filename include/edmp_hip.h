@@ -202,7 +202,7 @@ int edmp_denoise_guided_dev(edmp_ctx* ctx, const double* noise_dev, int B, const
  * those of the previous segment; anything else is refused with EDMP_ERR_STATE (the message names the expected and the given
  * step) and launches nothing.  A run ends when a segment reaches t_lo == 0, and is ended by every other loop entry point
  * (edmp_denoise_guided_dev / _rng_dev / edmp_denoise_scenes_dev), by the teacher-forced steps, edmp_guide_gradient_dev,
- * edmp_guide_swept_cost_dev and edmp_row_swept_volumes_dev (they replace a start / goal pair), by edmp_unet_forward_dev (the
+ * edmp_guide_swept_cost_dev, edmp_row_swept_volumes_dev and edmp_scenes_swept_volumes_dev (they replace a start / goal pair), by edmp_unet_forward_dev (the
  * model's input buffer carries the next segment's input), by a changed edmp_sampler_set_condition and by edmp_sampler_init: a
  * continuing segment after any of them is refused.  A run started with guided = 0 cannot be continued with guided = 1 (the guide
  * never received its pair).
@@ -223,7 +223,7 @@ int edmp_denoise_guided_segment_dev(edmp_ctx* ctx, const double* noise_dev, int 
  * edmp_scene_set (one robot).  edmp_rows_set is then called ONCE for all S*B rows with row_class in that numbering; rows / S is the
  * rows per scene (rows that do not split evenly over S are refused).  On a bound scene batch the single-scene loop (guided), the
  * teacher-forced steps, the cost / gradient / best-trajectory / success entry points and edmp_scene_set_shapes are refused
- * (EDMP_ERR_STATE): use one guide per scene for those. */
+ * (EDMP_ERR_STATE): use one guide per scene for those, or - for the scoring of the finished state - the edmp_scenes_* calls below. */
 int edmp_scene_batch_set(edmp_ctx* ctx, int S, const int32_t* n_obstacles, const double* obstacle_config, const int32_t* n_classes,
                          const double* clearance, const double* expansion, int T, const float* link_half_extents, const float* dh,
                          const float* static_frames);
@@ -238,6 +238,37 @@ int edmp_denoise_scenes_dev(edmp_ctx* ctx, const double* noise_dev, int S, int B
  * the continuing segment's S, B and t_hi must be the run's; its starts / goals are ignored) */
 int edmp_denoise_scenes_segment_dev(edmp_ctx* ctx, const double* noise_dev, int S, int B, const double* starts, const double* goals,
                                     int guided, int t_hi, int t_lo, int init, int zero_row0, double* X_out_dev);
+
+/* ---- scoring a bound scene batch: best row and success per scene ------------------------------------------------ */
+/* What the reference does once per scene after its loop - choose_best_trajectory (lib/guide.py:637-653) and the success tally
+ * (infer_serial.py:94-99, 165-168 on lib/environment.py:632-680) - for the finished (S*B, 7, N) state of a scene batch, in one launch
+ * per step instead of one guide per scene.  Every call needs the bound guide to be a scene batch (edmp_scene_batch_set, a batch of ONE
+ * scene included, + edmp_rows_set) and S, B to be that batch's scenes and rows per scene: on a single-scene guide they are refused with
+ * EDMP_ERR_STATE, with another S or B with EDMP_ERR_ARG, and nothing is launched.  Scene s's results equal, bit for bit, what the
+ * per-scene entry point returns for rows [s*B, (s+1)*B) on scene s's own guide.
+ *
+ * edmp_scene_batch_set_shapes: edmp_scene_set_shapes (lib/environment.py:249-268) for the batch: kind (n_total,) int32, 0 cuboid / 1
+ * cylinder, for all sum n_obstacles obstacles, scene after scene (all cuboids after edmp_scene_batch_set).  n_total must be the batch's
+ * total (EDMP_ERR_ARG otherwise); refused on a single-scene guide (EDMP_ERR_STATE), which has edmp_scene_set_shapes. */
+int edmp_scene_batch_set_shapes(edmp_ctx* ctx, const int32_t* kind, int n_total);
+/* edmp_row_swept_volumes_dev (the volume part of choose_best_trajectory, lib/guide.py:637-653) per scene: X (S*B,7,N) f64 on the device,
+ * 3 <= N <= 64; starts / goals (S,7) f64 host (required); volumes (S*B,) f32 on the device (NULL: kept in the guide's scratch): every row's
+ * t = 0 swept volume against its OWN scene's obstacles and start / goal pair.  best_index_host (S,) int or NULL: the arg-min of each
+ * scene's B volumes as edmp_argmin_dev defines it (first index on ties, the first NaN wins), relative to the scene; synchronises only
+ * when given.  Replaces the guide's start / goal pairs, so it ends a segmented run like its single-scene sibling. */
+int edmp_scenes_swept_volumes_dev(edmp_ctx* ctx, const double* X_dev, int S, int B, int N, const double* starts, const double* goals,
+                                  float* volumes_dev, int* best_index_host);
+/* edmp_select_row_dev's rule (lib/guide.py:637-653 widened by infer_serial.py:119-129) per scene: volumes (S*B,) f32 and key (S*B,) f64 on
+ * the device; minimum, candidates and pick all lie inside the scene's own B rows.  index_host (S,) int, relative to the scene
+ * (synchronises).  One launch for the whole batch. */
+int edmp_scenes_select_rows_dev(edmp_ctx* ctx, const float* volumes_dev, const double* key_dev, int S, int B, double trust_region,
+                                int* index_host);
+/* edmp_success_rows_dev (RobotEnvironment.benchmark_trajectory + check_collisions, lib/environment.py:632-680, 591-608; tally of
+ * infer_serial.py:94-99, 165-168) per scene: X (S*B,7,N) f64 on the device, N >= 2, 1 <= substeps <= 64; a row is checked against the
+ * obstacles and kinds of its own scene only.  ok / first / within (S*B,) int32 on the device, each optional.  counts_host (S,4) int32 or
+ * NULL (synchronises when given): per scene [rows ok, rows within limits, rows collision-free, B]. */
+int edmp_scenes_success_rows_dev(edmp_ctx* ctx, const double* X_dev, int S, int B, int N, int substeps, const double* dh_f64,
+                                 int32_t* ok_dev, int32_t* first_dev, int32_t* within_dev, int32_t* counts_host);
 
 /* Device noise source — explicitly NOT the reference's NumPy RandomState stream (that contract is served by
  * edmp_denoise_guided_dev): Philox4x32-10 counter RNG + Box-Muller inside the sampler kernels, no noise tensor, no

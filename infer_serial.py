@@ -145,7 +145,8 @@ def run(cfg_path, dataset=None, max_scenes=None, verbose=True, scenes_in_flight=
 
     ``scenes_per_launch`` = k > 1 (an extension) plans k consecutive scenes of this rank in ONE device-resident loop
     (Diffusion.denoise_guided_scenes over a guide.SceneBatch): each scene is prepared in order (guide, IK filter), the group is planned
-    in one call, then every scene's best row and success are picked from its own rows.  Per-scene results equal the serial loop's bit
+    in one call, then the finished state stays on the device and every scene's best row and success are picked from its own rows by the
+    batch's own scoring calls (SceneBatch.select_rows / success_rows: one launch per step for the group).  Per-scene results equal the serial loop's bit
     for bit; the last group may be smaller.  The model is built for k * rows, and the feeder keeps 2k whole-scene pinned buffers
     (k = 2 at 1024 rows: 4 x 734 MB page-locked).  Each result carries `scenes_in_launch`; its `denoise_s` is the GROUP's time.
     Not combined with scenes_in_flight > 1.
@@ -305,34 +306,37 @@ def run(cfg_path, dataset=None, max_scenes=None, verbose=True, scenes_in_flight=
         streams = [feeder.next() for _ in group]
         noise_wait = time.time() - t_w
         batch = SceneBatch([g[0] for g in group])
+        starts, goals = np.stack([g[1] for g in group]), np.stack([g[2] for g in group])
         ta = time.time()
-        X = diffuser.denoise_guided_scenes(denoiser, batch, traj_len, num_channels, np.stack([g[1] for g in group]), np.stack([g[2] for g in group]),
-                                           noise=streams, condition=True)
+        Xd = diffuser.denoise_guided_scenes(denoiser, batch, traj_len, num_channels, starts, goals, noise=streams, condition=True, return_device=True)
         tb = time.time()
         for st in streams:
-            feeder.recycle(st)  # (the call returned host trajectories: every upload out of the buffers is done)
-        all_met = None
-        if ensemble_report:  # ONE kernel over the S * B rows of the group (the metrics need no scene); per-scene slices below
-            te = time.time()
-            all_met = EV.batch_metrics(np.asarray(X).reshape((-1,) + tuple(np.shape(X)[-2:])), device=diffuser.ctx)
-            t_met = time.time() - te
+            feeder.recycle(st)  # (the call synchronised before it returned the device state: every upload out of the buffers is done)
+        # the finished (S, B, C, N) state stays on the device and is scored as ONE batch: per-scene volumes + pick, per-scene success
+        # flags + counts, and the metrics of all S * B rows (they need no scene) - three calls for the group, not four per scene
+        idxs, all_vols, all_met = batch.select_rows(starts, goals, Xd, prefer=prefer)
+        tc = time.time()
+        t_met = None
+        if ensemble_report and all_met is None:
+            all_met = {k: v.reshape(len(group), total_batch_size) for k, v in EV.batch_metrics(Xd.reshape((-1,) + tuple(Xd.shape[-2:])), device=diffuser.ctx).items()}
+            t_met = time.time() - tc
+        td = time.time()
+        all_chk = batch.success_rows(Xd)
+        te = time.time()
+        X = diffuser.ctx.to_host(Xd)  # once, for the result dicts
         out = []
         for s, (guide, start_joints, goal_joints, meta, t0) in enumerate(group):
             tm = dict(meta.pop("timings"))
             tm["noise_wait_s"] = noise_wait
-            tc = time.time()
-            trajectories = X[s]
-            idx, vols, met = guide.select_row(start_joints, goal_joints, trajectories, prefer=prefer)
-            if all_met is not None:
-                met = {k: v[s * total_batch_size:(s + 1) * total_batch_size] for k, v in all_met.items()}
+            trajectories, idx, vols = X[s], int(idxs[s]), all_vols[s]
+            met = None if all_met is None else {k: v[s] for k, v in all_met.items()}
+            chk = {k: (v[s] if k in ("ok", "first", "within", "collision_free") else int(v[s])) for k, v in all_chk.items()}
+            if t_met is not None:
                 tm["batch_metrics_s"] = t_met  # the whole group's call
             trajectory = trajectories[idx]
             tm["denoise_s"] = tb - ta  # the whole group's loop
             tm["denoise_s_is"] = f"group of {len(group)} scenes"
-            tm["best_trajectory_s"] = time.time() - tc
-            td = time.time()
-            chk = guide.success_rows(trajectories)
-            tm["success_check_s"] = time.time() - td
+            tm["best_trajectory_s"], tm["success_check_s"] = tc - tb, te - td  # the whole group's calls
             t_plan = time.time() - t0
             out.append(dict(**meta, timings=tm, scenes_in_launch=len(group), best_row=int(idx), swept_volume=float(vols[idx]),
                             success_proxy=int(chk["collision_free"][idx]), success_strict=int(chk["ok"][idx]), rows_collision_free=chk["rows_collision_free"],
