@@ -79,6 +79,8 @@ SIGNATURES = {
     "edmp_scene_batch_set": (_i, [_vp, _i, _pi32, _pd, _pi32, _pd, _pd, _i, _pf, _pf, _pf]),
     "edmp_denoise_scenes_dev": (_i, [_vp, _vp, _i, _i, _pd, _pd, _i, _i, _i, _vp]),
     "edmp_denoise_scenes_segment_dev": (_i, [_vp, _vp, _i, _i, _pd, _pd, _i, _i, _i, _i, _i, _vp]),
+    "edmp_sampler_seed_dev": (_i, [_vp, _vp, _i, _vp, _i, _pd, _pd, _i, _i, _vp]),
+    "edmp_sampler_seed_scenes_dev": (_i, [_vp, _vp, _i, _vp, _i, _i, _pd, _pd, _i, _i, _vp]),
     "edmp_scene_batch_set_shapes": (_i, [_vp, _pi32, _i]),
     "edmp_scenes_swept_volumes_dev": (_i, [_vp, _vp, _i, _i, _i, _pd, _pd, _vp, C.POINTER(_i)]),
     "edmp_scenes_select_rows_dev": (_i, [_vp, _vp, _vp, _i, _i, _d, C.POINTER(_i)]),

@@ -280,20 +280,58 @@ __global__ __launch_bounds__(256) void head_psample_kernel(const float* __restri
     }
 }
 
+// sa * x + sb * eps as NumPy evaluates the expression: two products and one sum, each rounded on its own (*mean = sa * x).  The one
+// place the forward process is written down: q_sample_kernel and seed_state_kernel both call it.
+__device__ __forceinline__ double q_noised(double sa, double x, double sb, double eps, double* mean) {
+#pragma clang fp contract(off)  // hipcc fuses a*b + c into an FMA by default (and __dmul_rn / __dadd_rn are plain * and +)
+    const double m = sa * x;
+    const double e = sb * eps;
+    *mean = m;
+    return m + e;
+}
+
 // forward process: xt = sa*x + sb*eps per row (coef = [B][2]); products and sum rounded separately (NumPy's evaluation)
 __global__ void q_sample_kernel(const double* __restrict__ x, const double* __restrict__ eps, const double* __restrict__ coef,
                                 double* __restrict__ xt, double* __restrict__ mean, int n, int per_row, int N, int condition) {
-#pragma clang fp contract(off)  // hipcc fuses a*b + c into an FMA by default (and __dmul_rn / __dadd_rn are plain * and +)
     int i = blockIdx.x * blockDim.x + threadIdx.x;
     if (i >= n) return;
     const int b = i / per_row, w = i % N;
     const double xv = x[i];
-    const double m = coef[2 * b] * xv;
-    const double e = coef[2 * b + 1] * eps[i];
-    double v = m + e;
+    double m;
+    double v = q_noised(coef[2 * b], xv, coef[2 * b + 1], eps[i], &m);
     if (condition && (w == 0 || w == N - 1)) v = xv;
     xt[i] = v;
     if (mean) mean[i] = m;
+}
+
+// The state of a run that begins below T (edmp_sampler_seed_dev), thread per (row, waypoint) like init_state_rng_kernel:
+//   X = sa * x0 + sb * eps (eps == nullptr: X = x0, a saved state), columns 0 / N-1 pinned to the run's start / goal pair when
+//   conditioning is on, and the first step's UNet input [B][N][8] f32 (channels >= C zero) as pack_state_kernel writes it.
+// x0 holds one plan per row (per_row) or one plan per group of rows: the whole batch (rps == 0), or the row's scene b / rps.
+__global__ void seed_state_kernel(const double* __restrict__ x0, int per_row, const double* __restrict__ eps, double sa, double sb,
+                                  double* __restrict__ X, float* __restrict__ xin, const double* __restrict__ sg, int B, int C, int N, int cond, int rps) {
+    int i = blockIdx.x * blockDim.x + threadIdx.x;
+    if (i >= B * N) return;
+    const int b = i / N, l = i - b * N;
+    const int sc = rps ? b / rps : 0;
+    const int src = per_row ? b : sc;
+    sg += 14 * sc;
+    float xo[8] = {0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f};
+    for (int c = 0; c < C && c < 8; ++c) {
+        const size_t idx = ((size_t)b * C + c) * N + l;
+        double x = x0[((size_t)src * C + c) * N + l];
+        if (eps) {
+            double m;
+            x = q_noised(sa, x, sb, eps[idx], &m);
+        }
+        if (cond && l == 0) x = sg[c];
+        if (cond && l == N - 1) x = sg[7 + c];
+        X[idx] = x;
+        xo[c] = (float)x;
+    }
+    float4* o = reinterpret_cast<float4*>(xin + (size_t)i * 8);
+    o[0] = make_float4(xo[0], xo[1], xo[2], xo[3]);
+    o[1] = make_float4(xo[4], xo[5], xo[6], xo[7]);
 }
 
 static int ensure_sampler_scratch(edmp_ctx* ctx, int n) {
@@ -696,29 +734,36 @@ static int enqueue_loop(edmp_ctx* ctx, const double* noise_dev, bool use_rng, ui
     return EDMP_OK;
 }
 
-// S > 1: a scene batch of S scenes x B / S rows; start / goal then hold S rows of 7 each
-// segment: one of the *_segment_dev entry points.  Only they leave a run in progress (Sampler::run_next): a segment that returns with
-// t_lo > 0 records the step the kept state stands at and the context's epoch, and a continuing segment (init == 0) must bring
-// exactly that t_hi under that epoch.  Every other loop call, a run that reached t_lo == 0, new start / goal pairs, a changed
-// conditioning switch and edmp_sampler_init end the run.  start / goal of a continuing segment are not read.
-static int denoise_loop(edmp_ctx* ctx, const double* noise_dev, bool use_rng, uint64_t seed, int B, const double* start, const double* goal,
-                        int guided, int t_hi, int t_lo, bool init, int zero_row0, double* X_out_dev, bool segment = false, int S = 1) {
-    int rc = check_loop_state(ctx, B, guided != 0, S);
+// what a run of B rows over S scenes needs of the context, whether it starts at T (denoise_loop) or below (sampler_seed)
+static int check_run_state(edmp_ctx* ctx, int B, bool guided, int S) {
+    int rc = check_loop_state(ctx, B, guided, S);
     if (rc) return rc;
-    const int rps = S > 1 ? B / S : 0;
     if (S > 1) {
         if (guided) EDMP_REQUIRE(ctx->guide->B == B, "the scene batch's rows are set for %d rows, the run has %d", ctx->guide->B, B);
         if (ctx->sampler->ar_fn) {
             set_error("a scene batch cannot run with an all-reduce hook installed (the hook sums ONE sum(g^2), a scene batch has one per scene)");
             return EDMP_ERR_STATE;
         }
-        EDMP_REQUIRE(!use_rng, "the device noise mode has no scene batch");
     }
+    return EDMP_OK;
+}
+
+// S > 1: a scene batch of S scenes x B / S rows; start / goal then hold S rows of 7 each
+// segment: one of the *_segment_dev entry points.  Only they leave a run in progress (Sampler::run_next): a segment that returns with
+// t_lo > 0 records the step the kept state stands at and the context's epoch, and a continuing segment (init == 0) must bring
+// exactly that t_hi under that epoch.  sampler_seed leaves the same record for a run that begins below T.  Every other loop call, a run that reached t_lo == 0, new start / goal pairs, a changed
+// conditioning switch and edmp_sampler_init end the run.  start / goal of a continuing segment are not read.
+static int denoise_loop(edmp_ctx* ctx, const double* noise_dev, bool use_rng, uint64_t seed, int B, const double* start, const double* goal,
+                        int guided, int t_hi, int t_lo, bool init, int zero_row0, double* X_out_dev, bool segment = false, int S = 1) {
+    int rc = check_run_state(ctx, B, guided != 0, S);
+    if (rc) return rc;
+    const int rps = S > 1 ? B / S : 0;
+    EDMP_REQUIRE(S == 1 || !use_rng, "the device noise mode has no scene batch");
     EDMP_REQUIRE(noise_dev || use_rng, "null noise pointer");
     Sampler* s = ctx->sampler;
     const int T = s->T;
     EDMP_REQUIRE(t_hi >= 1 && t_hi <= T && t_lo >= 0 && t_lo < t_hi, "step range %d..%d outside 1..%d", t_hi, t_lo + 1, T);
-    EDMP_REQUIRE(!init || t_hi == T, "a run starts at t = T");
+    EDMP_REQUIRE(!init || t_hi == T, "an init segment starts at t = T (edmp_sampler_seed_dev starts a run below T)");
     EDMP_HIP_CHECK(hipSetDevice(ctx->device));
     const int C = ctx->unet->desc.input_dim, N = ctx->unet->desc.horizon;
     const size_t n = (size_t)B * C * N;
@@ -851,6 +896,52 @@ extern "C" int edmp_denoise_scenes_segment_dev(edmp_ctx* ctx, const double* nois
     static const double zeros[EDMP_MAX_SCENES * 7] = {};
     if (int rc = scenes_args(ctx, S, B, starts, goals, guided, zeros)) return rc;
     return denoise_loop(ctx, noise_dev, false, 0, S * B, starts, goals, guided, t_hi, t_lo, init != 0, zero_row0, X_out_dev, true, S);
+}
+
+// The init of a segmented run that begins at t_start <= T from the caller's plan: the checks, the start / goal upload and the run
+// record of an init segment, with seed_state_kernel in the place of the X_T copy.  B = all rows (S * rows per scene).
+static int sampler_seed(edmp_ctx* ctx, const double* x0_dev, int x0_rows, const double* eps_dev, int B, const double* start, const double* goal,
+                        int guided, int t_start, double* X_out_dev, int S) {
+    int rc = check_run_state(ctx, B, guided != 0, S);
+    if (rc) return rc;
+    Sampler* s = ctx->sampler;
+    EDMP_REQUIRE(x0_dev && start && goal, "seed: null x0 / start / goal");
+    EDMP_REQUIRE(t_start >= 1 && t_start <= s->T, "seed: t_start = %d outside 1..%d", t_start, s->T);
+    EDMP_REQUIRE(x0_rows == S || x0_rows == B, "seed: x0 holds %d plans, the run takes %d (one per %s) or %d (one per row)", x0_rows, S,
+                 S > 1 ? "scene" : "batch", B);
+    EDMP_HIP_CHECK(hipSetDevice(ctx->device));
+    const int C = ctx->unet->desc.input_dim, N = ctx->unet->desc.horizon;
+    const size_t n = (size_t)B * C * N;
+    const int rps = S > 1 ? B / S : 0;
+    s->run_next = 0;
+    rc = ensure_sampler_scratch(ctx, (int)n);
+    if (rc) return rc;
+    rc = S > 1 ? set_startgoal_scenes(ctx, S, start, goal, guided != 0) : set_startgoal(ctx, start, goal, guided != 0);
+    if (rc) return rc;
+    const double ab = s->alpha_bar[t_start - 1];
+    hipLaunchKernelGGL(seed_state_kernel, dim3((B * N + 255) / 256), dim3(256), 0, ctx->stream, x0_dev, x0_rows == B ? 1 : 0, eps_dev, sqrt(ab), sqrt(1.0 - ab),
+                       s->X, ctx->unet->x_in, s->sg, B, C, N, s->condition, rps);
+    EDMP_HIP_CHECK(hipGetLastError());
+    if (X_out_dev) EDMP_HIP_CHECK(hipMemcpyAsync(X_out_dev, s->X, n * sizeof(double), hipMemcpyDeviceToDevice, ctx->stream));
+    s->run_B = B;
+    s->run_rps = rps;
+    s->run_guided = guided != 0;
+    s->run_next = t_start;
+    s->run_epoch = ctx->epoch;
+    return EDMP_OK;
+}
+
+extern "C" int edmp_sampler_seed_dev(edmp_ctx* ctx, const double* x0_dev, int x0_rows, const double* eps_dev, int B, const double* start,
+                                     const double* goal, int guided, int t_start, double* X_out_dev) {
+    EDMP_REQUIRE(ctx && ctx->sampler, "edmp_sampler_seed_dev: sampler not initialised");
+    return sampler_seed(ctx, x0_dev, x0_rows, eps_dev, B, start, goal, guided, t_start, X_out_dev, 1);
+}
+
+extern "C" int edmp_sampler_seed_scenes_dev(edmp_ctx* ctx, const double* x0_dev, int x0_rows, const double* eps_dev, int S, int B, const double* starts,
+                                            const double* goals, int guided, int t_start, double* X_out_dev) {
+    static const double zeros[EDMP_MAX_SCENES * 7] = {};
+    if (int rc = scenes_args(ctx, S, B, starts, goals, guided, zeros)) return rc;
+    return sampler_seed(ctx, x0_dev, x0_rows, eps_dev, S * B, starts, goals, guided, t_start, X_out_dev, S);
 }
 
 extern "C" int edmp_sampler_set_allreduce(edmp_ctx* ctx, edmp_allreduce_fn fn, void* user) {

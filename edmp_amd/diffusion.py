@@ -4,6 +4,7 @@ from __future__ import annotations
 
 import contextlib
 import ctypes as C
+import operator
 import os
 import threading
 import time
@@ -67,6 +68,51 @@ def chunk_plan(T, t_stop=0, chunk_steps=DEFAULT_CHUNK_STEPS):
         plan.append(seg)
         t_hi, k, offset = seg.t_lo, 2 * k, offset + seg.draws
     return plan
+
+
+def warm_plan(t_start, t_stop=0, lead=1, chunk_steps=DEFAULT_CHUNK_STEPS):
+    """The segments of a warm-started run from t_start down to t_stop: chunk_plan's, whose first segment (`init`: the seed call comes
+    first) carries `lead` extra draws in front of its steps' - 1 = the eps draw of the re-noising, which rides where X_T's draw rides in
+    a full run; 0 = a resume, whose stream holds the steps' draws only."""
+    if lead not in (0, 1):
+        raise ValueError(f"lead must be 0 or 1, got {lead}")
+    plan = chunk_plan(t_start, t_stop, chunk_steps)
+    if lead:
+        return plan
+    return [Segment(s.t_hi, s.t_lo, s.init, s.draws - (1 if s.init else 0), s.offset - (0 if s.init else 1)) for s in plan]
+
+
+class WarmStart:
+    """A prior plan to start the reverse loop from at step `t_start` instead of from pure noise at T (`warm_start=` of
+    Diffusion.denoise_guided / denoise_guided_scenes).  `x0`: host array or tensor, or device tensor, of real numbers: (C, N) - one plan
+    for every row - or (B, C, N); for a scene batch (S, C, N) - one plan per scene - or (S, B, C, N).  `renoise`: forward-noise x0 to
+    t_start with the first draw of the call's noise stream (q(x_t | x_0)); False takes x0 as the state at t_start itself, e.g. what a
+    call with t_stop = t_start returned.  Whether the shape fits the run and t_start lies in 1..T is checked by the call that uses it."""
+
+    def __init__(self, x0, t_start, renoise=True):
+        if isinstance(t_start, bool):
+            raise TypeError("t_start must be an integer, got a bool")
+        try:
+            self.t_start = operator.index(t_start)
+        except TypeError:
+            raise TypeError(f"t_start must be an integer, got {type(t_start).__name__}") from None
+        if isinstance(x0, torch.Tensor):
+            if x0.dtype == torch.bool or x0.is_complex():
+                raise TypeError(f"x0 must hold real numbers, got {x0.dtype}")
+        else:
+            x0 = np.asarray(x0)
+            if x0.dtype.kind not in "fiu":
+                raise TypeError(f"x0 must hold real numbers, got dtype {x0.dtype}")
+            x0 = np.ascontiguousarray(x0, dtype=np.float64)
+        if x0.ndim not in (2, 3, 4) or 0 in tuple(x0.shape):
+            raise ValueError(f"x0 must be (C, N) or (B, C, N) - scene batch: (S, C, N) or (S, B, C, N) -, got shape {tuple(x0.shape)}")
+        self.x0 = x0
+        self.renoise = bool(renoise)
+
+    @property
+    def lead(self) -> int:
+        """draws in front of the steps' in the run's noise stream: the eps draw when re-noising"""
+        return 1 if self.renoise else 0
 
 
 def guided_step(t) -> bool:
@@ -221,6 +267,30 @@ class Diffusion:
             raise ValueError(f"traj_len/num_channels ({traj_len}, {num_channels}) do not match the model's ({model.horizon}, {model.input_dim})")
         if not 0 <= int(t_stop) < self.T:
             raise ValueError(f"t_stop must lie in [0, {self.T}), got {t_stop}")
+
+    def _check_warm(self, ws, t_stop, noise, allreduce, shapes):
+        """a warm start against the run it is given to, before anything is bound or enqueued.  `shapes`: {accepted x0 shape: x0_rows of
+        the seed call}.  Returns x0_rows."""
+        if not isinstance(ws, WarmStart):
+            raise ValueError("warm_start must be a diffusion.WarmStart")
+        if isinstance(noise, str):
+            raise ValueError("a warm start takes NumPy-stream noise: the device noise mode (noise='device') has no segment form")
+        if allreduce is not None:
+            raise ValueError("a warm start of a sharded run (allreduce=...) is not supported")
+        if not 1 <= ws.t_start <= self.T:
+            raise ValueError(f"warm start: t_start must lie in 1..{self.T}, got {ws.t_start}")
+        if not 0 <= int(t_stop) < ws.t_start:
+            raise ValueError(f"warm start: t_stop must lie in [0, t_start = {ws.t_start}), got {t_stop}")
+        if tuple(ws.x0.shape) not in shapes:
+            raise ValueError(f"warm start: x0 must have one of the shapes {sorted(shapes, key=len)}, got {tuple(ws.x0.shape)}")
+        return shapes[tuple(ws.x0.shape)]
+
+    @staticmethod
+    def _after_lead(zd, seg, ws, per_step):
+        """(eps pointer or None, pointer to the first step's draw) inside a warm run's chunk `zd`"""
+        if seg.init and ws.renoise:
+            return ptr(zd), C.c_void_p(zd.data_ptr() + per_step * 8)
+        return None, ptr(zd)
 
     def _finish(self, out, return_device, *, sync=False, hand_over=True):
         """the result as the caller asked for it: a fresh host copy, or the device tensor itself - after a host synchronisation (`sync`)
@@ -379,14 +449,24 @@ class Diffusion:
 
     def denoise_guided(self, model, guide, traj_len, num_channels, guidance_schedule, batch_size=1, start=None, goal=None,
                        condition=True, benchmarking=False, *, noise=None, seed=0, t_stop=0, zero_row0=True, return_device=False,
-                       chunk_steps=DEFAULT_CHUNK_STEPS, allreduce=None):
+                       chunk_steps=DEFAULT_CHUNK_STEPS, allreduce=None, warm_start=None):
         """diffusion.py:300-356.  ``noise``: optional pre-drawn (T+1,B,C,N) f64 ndarray / device tensor (default:
         drawn from the global NumPy RNG in the reference's order); ``noise="device"`` draws z on the GPU (Philox,
         ``seed``) — a non-parity mode without the host draw / upload.  ``allreduce``: this call is one row shard
         of a batch spread over several GPUs; an ``edmp_amd.dist.RcclAllReduce`` (native ncclAllReduce inside the device loop) or a
         callable that sums the f64 device scalar over ranks in place (edmp_amd.dist.allreduce_sum_; a Python callback per guided step).
+        ``warm_start``: a WarmStart(x0, t_start, renoise) - the run covers steps t_start .. t_stop + 1 only, from x0 forward-noised to
+        t_start (or from x0 itself); ``noise`` is then (lead + t_start - t_stop, B, C, N), the eps draw first when re-noising (lead = 1),
+        from the same sources.
         Returns (B,C,N) f64 ndarray (a fresh copy)."""
         ctx = self.ctx
+        ws = warm_start
+        if ws is not None:
+            cn = (int(num_channels), int(traj_len))
+            x0_rows = self._check_warm(ws, t_stop, noise, allreduce, {cn: 1, (int(batch_size),) + cn: int(batch_size)})
+            want = (ws.lead + ws.t_start - int(t_stop), int(batch_size)) + cn
+            if hasattr(noise, "shape") and tuple(noise.shape) != want:
+                raise _noise_error("noise", want, noise)
         self._prepare(model, guide, batch_size, guidance_schedule)
         _capi.check(ctx.lib.edmp_sampler_set_condition(ctx.h, 1 if condition else 0))
         s, g = _startgoal(start, goal, needed=bool(condition) or guide is not None)
@@ -397,13 +477,26 @@ class Diffusion:
         shape = (self.T + 1, batch_size, num_channels, traj_len)
         per_step = batch_size * num_channels * traj_len
         sp, gp, guided, zr = _capi.as_pd(s), _capi.as_pd(g), 1 if guide is not None else 0, 1 if zero_row0 else 0
+        if ws is not None:
+            shape = (ws.lead + ws.t_start - int(t_stop),) + shape[1:]
+            x0d = ctx.to_dev(ws.x0, torch.float64)
 
         def segment(zd, seg, X_out):
+            init, z = 1 if seg.init else 0, ptr(zd)
+            if ws is not None:  # the seed call is the run's init; every segment continues it
+                eps, z = self._after_lead(zd, seg, ws, per_step)
+                if init:
+                    _capi.check(ctx.lib.edmp_sampler_seed_dev(ctx.h, ptr(x0d), x0_rows, eps, batch_size, sp, gp, guided, ws.t_start, None), "edmp_sampler_seed_dev")
+                init = 0
             _capi.check(
-                ctx.lib.edmp_denoise_guided_segment_dev(ctx.h, ptr(zd), batch_size, sp, gp, guided, seg.t_hi, seg.t_lo, 1 if seg.init else 0, zr,
+                ctx.lib.edmp_denoise_guided_segment_dev(ctx.h, z, batch_size, sp, gp, guided, seg.t_hi, seg.t_lo, init, zr,
                                                         ptr(X_out) if X_out is not None else None),
                 "edmp_denoise_guided_segment_dev",
             )
+
+        t_top, plan_of = self.T, chunk_plan
+        if ws is not None:
+            t_top, plan_of = ws.t_start, lambda t_hi, t_lo, steps: warm_plan(t_hi, t_lo, ws.lead, steps)
 
         stream = noise if isinstance(noise, PinnedNoiseStream) else None
         if stream is not None:
@@ -416,30 +509,39 @@ class Diffusion:
                             "edmp_denoise_guided_rng_dev")
                 return self._finish(out, return_device)
             if noise is None:
-                return self._run_numpy_stream(chunk_plan(self.T, t_stop, chunk_steps), per_step, chunk_steps, segment, out, return_device)
+                return self._run_numpy_stream(plan_of(t_top, t_stop, chunk_steps), per_step, chunk_steps, segment, out, return_device)
             if _is_pinned_f64(noise):  # uploaded in the same chunks as the on-the-fly stream
                 if tuple(noise.shape) != shape:
                     raise _noise_error("noise", shape, noise)
-                return self._run_segments(chunk_plan(self.T, t_stop, chunk_steps), self._pinned_chunks(noise, stream, per_step), segment, out, return_device)
+                return self._run_segments(plan_of(t_top, t_stop, chunk_steps), self._pinned_chunks(noise, stream, per_step), segment, out, return_device)
             nd = ctx.adopt(noise) if (isinstance(noise, torch.Tensor) and noise.is_cuda) else ctx.to_dev(noise, torch.float64)
             if tuple(nd.shape) != shape or nd.dtype != torch.float64:
                 raise _noise_error("noise", shape, nd)
+            if ws is not None:  # the resident stream of a warm run: seed + one segment
+                segment(nd, Segment(ws.t_start, int(t_stop), True, shape[0], 0), out)
+                return self._finish(out, return_device, sync=True)
             _capi.check(ctx.lib.edmp_denoise_guided_dev(ctx.h, ptr(nd), batch_size, sp, gp, guided, int(t_stop), zr, ptr(out)), "edmp_denoise_guided_dev")
             return self._finish(out, return_device)
 
     def denoise_guided_scenes(self, model, batch, traj_len, num_channels, starts, goals, *, noise=None, t_stop=0, zero_row0=True, condition=True,
-                              chunk_steps=DEFAULT_CHUNK_STEPS, return_device=False, guided=True):
+                              chunk_steps=DEFAULT_CHUNK_STEPS, return_device=False, guided=True, warm_start=None):
         """S scenes of B rows each planned in ONE device-resident loop (edmp_denoise_scenes_dev): what S calls of denoise_guided, one per
         scene of ``batch`` (a guide.SceneBatch), return - bit for bit - as an (S, B, C, N) f64 array.  ``starts`` / ``goals`` (S, 7).
         ``noise``: None = the S streams from the global NumPy RandomState in scene order (the state ends where S denoise_guided calls leave
         it); a list of S (T+1, B, C, N) arrays / device tensors; or a list of S pinned tensors / PinnedNoiseStreams, uploaded in chunks
-        beside the loop.  ``zero_row0``: quirk Q3 on row 0 of every scene.  ``guided=False``: the unguided loop, per-scene conditioning."""
+        beside the loop.  ``zero_row0``: quirk Q3 on row 0 of every scene.  ``guided=False``: the unguided loop, per-scene conditioning.
+        ``warm_start``: as in denoise_guided, x0 (S, C, N) - scene s's plan for all its rows - or (S, B, C, N); every scene's stream is then
+        (lead + t_start - t_stop, B, C, N)."""
         from .guide import SceneBatch
 
         ctx = self.ctx
         if not isinstance(batch, SceneBatch):
             raise ValueError("batch must be a guide.SceneBatch")
         S, B = batch.n_scenes, batch.batch_size
+        ws = warm_start
+        if ws is not None:
+            cn = (int(num_channels), int(traj_len))
+            x0_rows = self._check_warm(ws, t_stop, noise, None, {(S,) + cn: S, (S, B) + cn: S * B})
         if model.ctx is not ctx or batch.ctx is not ctx:
             raise _capi.EdmpError("model, scene batch and diffuser must live on the same GPU")
         self._check_run(model, traj_len, num_channels, t_stop)
@@ -463,18 +565,21 @@ class Diffusion:
             raise ValueError(f"noise must be None or a list of {S} per-scene streams")
         Cc, N, T = int(num_channels), int(traj_len), self.T
         per = (T + 1, B, Cc, N)
+        if ws is not None:  # a warm run's streams hold exactly its draws, from every source
+            per = (ws.lead + ws.t_start - int(t_stop), B, Cc, N)
         if noise is None:
             # every scene's stream in scene order, as S serial calls draw them (each draws X_T and the steps down to t_stop + 1)
-            noise = [nprng.standard_normal((T + 1 - int(t_stop), B, Cc, N)) for _ in range(S)]
-            per = (T + 1 - int(t_stop), B, Cc, N)
+            if ws is None:
+                per = (T + 1 - int(t_stop), B, Cc, N)
+            noise = [nprng.standard_normal(per) for _ in range(S)]
         streams = [x if isinstance(x, PinnedNoiseStream) else None for x in noise]
         tens = [x.tensor if isinstance(x, PinnedNoiseStream) else x for x in noise]
         pinned = [_is_pinned_f64(x) for x in tens]
         if any(pinned) and not all(pinned):
             raise ValueError("noise: either every scene's stream is pinned host memory or none is")
         for k, x in enumerate(tens):
-            if tuple(x.shape) not in (per, (T + 1, B, Cc, N)):
-                raise _noise_error(f"noise[{k}]", (T + 1, B, Cc, N), x)
+            if tuple(x.shape) not in ((per,) if ws is not None else (per, (T + 1, B, Cc, N))):
+                raise _noise_error(f"noise[{k}]", per if ws is not None else (T + 1, B, Cc, N), x)
         ctx.ensure_sampler(self.T, self.variance_thresh)
         model._bind()
         if guided:
@@ -483,12 +588,24 @@ class Diffusion:
         out = ctx.empty((S * B, Cc, N), torch.float64)
         sp, gp, gflag, zr = _capi.as_pd(s_arr), _capi.as_pd(g_arr), 1 if guided else 0, 1 if zero_row0 else 0
 
+        if ws is not None:
+            x0d = ctx.to_dev(ws.x0, torch.float64)
+
         def segment(zd, seg, X_out):
+            init, z = 1 if seg.init else 0, ptr(zd)
+            if ws is not None:  # the seed call is the run's init; every segment continues it
+                eps, z = self._after_lead(zd, seg, ws, S * B * Cc * N)
+                if init:
+                    _capi.check(ctx.lib.edmp_sampler_seed_scenes_dev(ctx.h, ptr(x0d), x0_rows, eps, S, B, sp, gp, gflag, ws.t_start, None),
+                                "edmp_sampler_seed_scenes_dev")
+                init = 0
             _capi.check(
-                ctx.lib.edmp_denoise_scenes_segment_dev(ctx.h, ptr(zd), S, B, sp, gp, gflag, seg.t_hi, seg.t_lo, 1 if seg.init else 0, zr,
+                ctx.lib.edmp_denoise_scenes_segment_dev(ctx.h, z, S, B, sp, gp, gflag, seg.t_hi, seg.t_lo, init, zr,
                                                         ptr(X_out) if X_out is not None else None),
                 "edmp_denoise_scenes_segment_dev",
             )
+
+        plan = chunk_plan(T, t_stop, chunk_steps) if ws is None else warm_plan(ws.t_start, t_stop, ws.lead, chunk_steps)
 
         if all(pinned):
             # chunks of the S pinned streams (the single-scene plan), each scene's piece uploaded by DMA and placed at rows
@@ -501,7 +618,7 @@ class Diffusion:
                 with torch.cuda.stream(ctx.stream):
                     return place_scene_rows(chunk, pieces)
 
-            return self._run_segments(chunk_plan(T, t_stop, chunk_steps), source, segment, out, return_device).reshape(S, B, Cc, N)
+            return self._run_segments(plan, source, segment, out, return_device).reshape(S, B, Cc, N)
         steps = tens[0].shape[0]
         if any(tuple(x.shape)[0] != steps for x in tens):
             raise ValueError("noise: every scene's stream must have the same number of draws")
@@ -512,7 +629,9 @@ class Diffusion:
             pieces = [ctx.adopt(x) if (isinstance(x, torch.Tensor) and x.is_cuda) else ctx.to_dev(np.asarray(x, dtype=np.float64), torch.float64) for x in tens]
             with torch.cuda.stream(ctx.stream):
                 place_scene_rows(nd, pieces)
-            if steps == T + 1:
+            if ws is not None:  # the resident streams of a warm run: seed + one segment
+                segment(nd, Segment(ws.t_start, int(t_stop), True, steps, 0), out)
+            elif steps == T + 1:
                 _capi.check(ctx.lib.edmp_denoise_scenes_dev(ctx.h, ptr(nd), S, B, sp, gp, gflag, int(t_stop), zr, ptr(out)), "edmp_denoise_scenes_dev")
             else:  # the NumPy stream of a run that stops at t_stop, X_T and T - t_stop steps: the whole run as one segment
                 segment(nd, Segment(T, int(t_stop), True, steps, 0), out)
@@ -524,9 +643,10 @@ class Diffusion:
             raise
         return self._finish(out, return_device, sync=True).reshape(S, B, Cc, N)
 
-    def denoise(self, model, traj_len, num_channels, start=None, goal=None, condition=True, *, batch_size=1, noise=None):
+    def denoise(self, model, traj_len, num_channels, start=None, goal=None, condition=True, *, batch_size=1, noise=None, warm_start=None):
         """diffusion.py:253-278 (unguided), batched; returns X[0] like the reference when batch_size == 1."""
-        X = self.denoise_guided(model, None, traj_len, num_channels, None, batch_size=batch_size, start=start, goal=goal, condition=condition, noise=noise)
+        X = self.denoise_guided(model, None, traj_len, num_channels, None, batch_size=batch_size, start=start, goal=goal, condition=condition, noise=noise,
+                                warm_start=warm_start)
         return X[0] if batch_size == 1 else X
 
     def denoise_step(self, model, guide, X, z, t, start, goal, guidance_schedule=None, zero_row0=True, allreduce=None):

@@ -193,7 +193,8 @@ int edmp_denoise_guided_dev(edmp_ctx* ctx, const double* noise_dev, int B, const
                             int guided, int t_stop, int zero_row0, double* X_out_dev);
 
 /* The same loop in segments (steps t_hi .. t_lo+1), for callers that produce the noise stream while the GPU works:
- * init != 0 starts a run at t_hi = T (noise_dev[0] is the X_T draw, then one (B,C,N) draw per step); init == 0 continues
+ * init != 0 starts a run at t_hi = T (noise_dev[0] is the X_T draw, then one (B,C,N) draw per step; a run that begins below T is
+ * started by edmp_sampler_seed_dev instead, see below); init == 0 continues
  * from the state kept in the context (noise_dev[0] is the draw of step t_hi) and performs no host synchronisation.
  * X_out_dev may be NULL except for the last segment.  Used by Diffusion.denoise_guided to overlap NumPy's RandomState
  * (the reference's noise contract, ~0.85 s per 1024-row scene on the host) with the denoising itself.
@@ -210,6 +211,22 @@ int edmp_denoise_guided_dev(edmp_ctx* ctx, const double* noise_dev, int B, const
  * goal arguments and goes on with the init segment's pair. */
 int edmp_denoise_guided_segment_dev(edmp_ctx* ctx, const double* noise_dev, int B, const double* start, const double* goal,
                                     int guided, int t_hi, int t_lo, int init, int zero_row0, double* X_out_dev);
+
+/* Warm start: the init of a segmented run that begins at step t_start <= T from a prior plan instead of at T from pure noise (no
+ * reference counterpart; the forward process is Diffusion.q_sample_from_x0's, diffusion.py:79-105).  One kernel builds the run's state
+ *   X = sqrt(alpha_bar[t_start - 1]) * x0 + sqrt(1 - alpha_bar[t_start - 1]) * eps      (rounded as edmp_q_sample_dev, cumulative = 1)
+ * or X = x0 when eps_dev is NULL (a resume from a saved state), pins X[:, :, 0] / X[:, :, -1] to start / goal - the run's pair, not x0's
+ * own end columns - when conditioning is on, and writes the first step's UNet input.  x0 (x0_rows, C, N) f64 on the device: x0_rows = B
+ * is one plan per row, x0_rows = 1 one plan for the whole batch; eps (B, C, N) f64 on the device.  1 <= t_start <= T and x0_rows in
+ * {1, B}, else EDMP_ERR_ARG.  X_out_dev (B, C, N) f64 or NULL receives the seeded state.
+ * The call is an init segment in every other respect: the same checks (model and sampler present, B <= max_batch, a bound single-scene
+ * guide with B rows when guided), the same upload of start / goal (to the guide too when guided; that upload is the call's only host
+ * synchronisation, X_out_dev or not), and it leaves a run in progress at step t_start.  edmp_denoise_guided_segment_dev continues it with
+ * init = 0 and t_hi = t_start (noise_dev[0] = the draw of step t_start); everything said above about what ends or invalidates a run
+ * holds unchanged, the guided = 0 rule included.  A refused call launches nothing.  Segments are never replayed from a hipGraph
+ * (edmp_sampler_set_graph), so a warm-started run is always enqueued eagerly. */
+int edmp_sampler_seed_dev(edmp_ctx* ctx, const double* x0_dev, int x0_rows, const double* eps_dev, int B, const double* start,
+                          const double* goal, int guided, int t_start, double* X_out_dev);
 
 /* ---- scene batch: several scenes in one launch chain ------------------------------------------------------ */
 /* S scenes of B rows each run as ONE (S*B, C, N) state through the device-resident loop; scene s owns rows [s*B, (s+1)*B).  The
@@ -238,6 +255,13 @@ int edmp_denoise_scenes_dev(edmp_ctx* ctx, const double* noise_dev, int S, int B
  * the continuing segment's S, B and t_hi must be the run's; its starts / goals are ignored) */
 int edmp_denoise_scenes_segment_dev(edmp_ctx* ctx, const double* noise_dev, int S, int B, const double* starts, const double* goals,
                                     int guided, int t_hi, int t_lo, int init, int zero_row0, double* X_out_dev);
+
+/* edmp_sampler_seed_dev for a scene batch: x0 (x0_rows, C, N) with x0_rows = S*B (one plan per row) or S (scene s's plan for all its B
+ * rows), eps (S*B, C, N), starts / goals (S,7) as edmp_denoise_scenes_dev; every row is pinned to its own scene's pair.  Guided needs the
+ * bound scene batch of S scenes and S*B rows; on a single-scene guide it is refused with EDMP_ERR_STATE, as edmp_sampler_seed_dev is on a
+ * bound scene batch.  edmp_denoise_scenes_segment_dev continues the run with init = 0 and t_hi = t_start. */
+int edmp_sampler_seed_scenes_dev(edmp_ctx* ctx, const double* x0_dev, int x0_rows, const double* eps_dev, int S, int B, const double* starts,
+                                 const double* goals, int guided, int t_start, double* X_out_dev);
 
 /* ---- scoring a bound scene batch: best row and success per scene ------------------------------------------------ */
 /* What the reference does once per scene after its loop - choose_best_trajectory (lib/guide.py:637-653) and the success tally
