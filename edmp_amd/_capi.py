@@ -85,6 +85,7 @@ SIGNATURES = {
     "edmp_scenes_swept_volumes_dev": (_i, [_vp, _vp, _i, _i, _i, _pd, _pd, _vp, C.POINTER(_i)]),
     "edmp_scenes_select_rows_dev": (_i, [_vp, _vp, _vp, _i, _i, _d, C.POINTER(_i)]),
     "edmp_scenes_success_rows_dev": (_i, [_vp, _vp, _i, _i, _i, _i, _pd, _vp, _vp, _vp, _pi32]),
+    "edmp_scenes_goal_filter_dev": (_i, [_vp, _vp, _i, _pi32, _pd, _d, _vp, _vp, C.POINTER(_i)]),
     "edmp_q_sample_dev": (_i, [_vp, _vp, _vp, _pi32, _i, _i, _i, _i, _i, _vp, _vp]),
     "edmp_unet_packed_size": (C.c_int64, [_vp, C.POINTER(C.c_int)]),
     "edmp_unet_read_packed": (_i, [_vp, _pf, C.c_int64]),

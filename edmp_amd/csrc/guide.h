@@ -47,6 +47,10 @@ struct Guide {
     float* vol_rows = nullptr;  // [B] for best trajectory
     int32_t* flags = nullptr;   // [3][flags_B] success check: ok, first colliding waypoint, within limits; + [flags_Q][4] counts
     int flags_B = 0, flags_Q = 1;  // (one count quadruple per scene: a scene batch asks for S of them)
+    // IK-goal filter of a scene batch (edmp_scenes_goal_filter_dev): one volume and one key per candidate, grow-only
+    float* cand_vol = nullptr;   // [cand_cap]
+    double* cand_key = nullptr;  // [cand_cap]
+    int cand_cap = 0;
 };
 
 // the per-scene entry points (cost, gradient, best trajectory, success, shapes) on a bound scene batch: refused, never answered

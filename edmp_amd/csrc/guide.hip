@@ -3,7 +3,8 @@
 //
 // Replaces (reference lib/guide.py): define_obstacles :118-158, get_tf_mat :45-72, forward_kinematics :74-98,
 // get_link_transform :344-352, cost :354-395, swept_volume_cost :473-537, get_gradient :597-635 (autograd there),
-// choose_best_trajectory :637-653.  Design:
+// choose_best_trajectory :637-653; and the driver's IK-goal filter built on cost (infer_serial.py:117-129) for a whole scene group
+// (GM_CAND_VOL, goal_pick_kernel, edmp_scenes_goal_filter_dev).  Design:
 //   * one 64-lane wave per trajectory row, lane w = padded waypoint w (0 = start, 1..L interior, L+1 = goal);
 //     the swept-volume coupling between consecutive waypoints is two wave shuffles per link (neighbour AABB down,
 //     routed face coefficients back up) — no LDS, no global round trip.
@@ -14,6 +15,10 @@
 //     (torch.min/max(dim)), half/half on elementwise min/max ties, clamp(min=0) passes gradient at len >= 0.
 #include "common.h"
 #include "guide.h"
+#include "pick.h"
+
+#include <cmath>
+#include <type_traits>
 
 namespace edmp {
 
@@ -65,7 +70,7 @@ void guide_destroy(edmp_ctx* ctx, Guide* g) {
     if (!g) return;
     for (void* p : {(void*)g->aabb, (void*)g->row_class, (void*)g->method, (void*)g->grad_norm, (void*)g->sched, (void*)g->graw,
                     (void*)g->rowsq, (void*)g->sumsq, (void*)g->startgoal, (void*)g->vol_rows, (void*)g->obb, (void*)g->kind, (void*)g->flags,
-                    (void*)g->cls_no})
+                    (void*)g->cls_no, (void*)g->cand_vol, (void*)g->cand_key})
         ctx_release(ctx, p);
     delete g;
 }
@@ -126,7 +131,11 @@ __global__ void obstacle_table_kernel(const double* __restrict__ sizes, const fl
 // ---------------------------------------------------------------------------------------------------------------
 // the guide kernel
 // ---------------------------------------------------------------------------------------------------------------
-enum GuideMode { GM_IV_VOL = 0, GM_SV_VOL = 1, GM_GRAD = 2, GM_SV_ROWSUM = 3 };
+// GM_CAND_VOL: the IK-goal candidates of a scene group (infer_serial.py:117-118 for every scene at once).  A candidate is ONE
+// configuration (L = 1), so the lane is the candidate, not the waypoint: a workgroup takes up to 256 candidates of one scene, stages that
+// scene's t = 0 obstacle table once, and every lane walks the 9 links x no obstacles of its own candidate.  Only the lane -> (row,
+// waypoint) map, the staging and the output differ from GM_IV_VOL; the element arithmetic is the one statement below.
+enum GuideMode { GM_IV_VOL = 0, GM_SV_VOL = 1, GM_GRAD = 2, GM_SV_ROWSUM = 3, GM_CAND_VOL = 4 };
 
 template <class TIn>
 struct GuideArgs {
@@ -146,6 +155,19 @@ struct GuideArgs {
     const float* startgoal;  // [14] f32 (scene batch: [S][14])
     float* out;              // volumes / raw gradient / row sums
     double* rowsq;           // GM_GRAD: per-row sum g^2
+};
+
+// GM_CAND_VOL: the ragged row -> scene map, by value (as SceneSlices in success.hip).  Scene s owns the candidates [off[s], off[s+1]) and
+// the workgroups [blk[s], blk[s+1]) of the grid, blk[s+1] - blk[s] = ceil(M_s / 256); cls[s] is the scene's first guide class (t = 0: a
+// class block is uninflated there, any class of the scene serves).
+struct CandSlices {
+    int S;
+    int off[EDMP_MAX_SCENES + 1];
+    int blk[EDMP_MAX_SCENES + 1];
+    int cls[EDMP_MAX_SCENES];
+};
+struct CandArgs : GuideArgs<double> {
+    CandSlices sl;
 };
 
 struct Vec3 {
@@ -184,25 +206,40 @@ __device__ __forceinline__ Vec3 corner_pos(const float R[3][3], const float o[3]
 // the fixed order ((w0 + w1) + w2) + w3.  One wave per row is a latency-bound layout (1024 rows = one wave per SIMD, ~15 k dependent
 // VALU instructions each: 44.5 us per launch); with four waves per SIMD the same work is throughput-bound.  The link sum is
 // regrouped, so results differ from SPLIT = 1 by f32 rounding (same gates).
-template <int MODE, class TIn, int SPLIT = 1>
-__global__ __launch_bounds__(256, (SPLIT == 4 ? 4 : 1)) void guide_kernel(GuideArgs<TIn> a, RobotConst rc) {
+template <int MODE, class TIn, int SPLIT = 1, class Args = GuideArgs<TIn>>
+__global__ __launch_bounds__(256, (SPLIT == 4 ? 4 : 1)) void guide_kernel(Args a, RobotConst rc) {
     static_assert(SPLIT == 1 || (SPLIT == 4 && MODE == GM_GRAD), "the link-split layout exists for the gradient only");
-    __shared__ float s_obs[SPLIT == 4 ? 1 : 4][EDMP_MAX_OBSTACLES * 6];
+    constexpr bool CAND = (MODE == GM_CAND_VOL);  // lane = candidate of one scene (see GuideMode)
+    static_assert(CAND == std::is_same<Args, CandArgs>::value, "the candidate mode, and it alone, brings the ragged scene map");
+    __shared__ float s_obs[(SPLIT == 4 || CAND) ? 1 : 4][EDMP_MAX_OBSTACLES * 6];
     __shared__ float s_g[SPLIT == 4 ? 3 : 1][SPLIT == 4 ? 7 : 1][64];  // partial gradients of waves 1..3
     const int lane = threadIdx.x & 63;
     const int wv = __builtin_amdgcn_readfirstlane(threadIdx.x >> 6);
-    const int r = (SPLIT == 4) ? blockIdx.x : blockIdx.x * 4 + wv;
-    const bool row_ok = r < a.n;
-    const int rr = row_ok ? r : 0;
+    int r, cls;
+    bool row_ok;
+    int rr;
+    if constexpr (CAND) {
+        // block -> (scene, chunk of 256 candidates) from the by-value offsets (block-uniform)
+        int sc = 0;
+        while (sc + 1 < a.sl.S && (int)blockIdx.x >= a.sl.blk[sc + 1]) ++sc;
+        r = a.sl.off[sc] + ((int)blockIdx.x - a.sl.blk[sc]) * 256 + (int)threadIdx.x;
+        row_ok = r < a.sl.off[sc + 1];
+        rr = row_ok ? r : a.sl.off[sc];  // (M_s >= 1: a candidate of this scene)
+        cls = a.sl.cls[sc];
+    } else {
+        r = (SPLIT == 4) ? blockIdx.x : blockIdx.x * 4 + wv;
+        row_ok = r < a.n;
+        rr = row_ok ? r : 0;
+        cls = a.use_row_class ? a.row_class[rr] : 0;
+    }
     const int L = a.L;
-    const int cls = a.use_row_class ? a.row_class[rr] : 0;
     // the row's own obstacle count (a scene batch: its scene's, from a table without padding - the arithmetic is the serial run's)
     const int no_cls = a.cls_no ? a.cls_no[cls] : a.no;
     const int no = no_cls;
     // obstacle AABBs of this row's class at step t -> LDS slice of this wave (SPLIT = 4: one table for the row's four waves)
     {
         const float* src = a.cls_no ? a.aabb + a.cls_off[cls] + (size_t)a.t * no_cls * 6 : a.aabb + ((size_t)cls * (a.T + 1) + a.t) * no_cls * 6;
-        if (SPLIT == 4) {
+        if (SPLIT == 4 || CAND) {
             for (int i = threadIdx.x; i < no * 6; i += 256) s_obs[0][i] = src[i];
         } else {
             for (int i = lane; i < no * 6; i += 64) s_obs[wv][i] = src[i];
@@ -211,18 +248,19 @@ __global__ __launch_bounds__(256, (SPLIT == 4 ? 4 : 1)) void guide_kernel(GuideA
     __syncthreads();
     // (scalar loads of the wave-uniform obstacle values straight from the table instead of LDS reads were tried in round 5: as many VALU
     // instructions - an SGPR operand per instruction, the rest moved into VGPRs - and the loads' latency in the loop: not kept)
-    const float* obs = s_obs[SPLIT == 4 ? 0 : wv];
+    const float* obs = s_obs[(SPLIT == 4 || CAND) ? 0 : wv];
     // SPLIT = 4: this wave's links and the last joint frame it needs
     const int my_jmax = (SPLIT == 4) ? (wv == 0 ? 2 : wv == 1 ? 4 : 6) : 6;
 
     bool sv;
-    if (MODE == GM_IV_VOL) sv = false;
+    if (MODE == GM_IV_VOL || CAND) sv = false;
     else if (MODE == GM_SV_VOL || MODE == GM_SV_ROWSUM) sv = true;
     else sv = a.method[rr] != 0.0f;
 
     // this lane's joint vector: padded waypoint w = lane (0 start, 1..L interior, >= L+1 goal)
-    const int w = lane;
-    const float* sgp = a.startgoal + (a.rps ? (rr / a.rps) * 14 : 0);  // this row's scene's start | goal
+    // (GM_CAND_VOL: every lane holds the one interior waypoint of its own candidate; no start / goal pair takes part)
+    const int w = CAND ? 1 : lane;
+    const float* sgp = a.startgoal + ((!CAND && a.rps) ? (rr / a.rps) * 14 : 0);  // this row's scene's start | goal
     float q[7];
     {
         // all seven joint values are requested before any of them is looked at (per-joint branches would serialise seven
@@ -256,6 +294,7 @@ __global__ __launch_bounds__(256, (SPLIT == 4 ? 4 : 1)) void guide_kernel(GuideA
     float zax[7][3], org[7][3];
     float g[7] = {0, 0, 0, 0, 0, 0, 0};
     float rowacc = 0.f;  // GM_SV_ROWSUM
+    double candacc = 0.0;  // GM_CAND_VOL: sum over the links, in link order, of the per-link sums
 
 #pragma unroll
     for (int j = 0; j < 7; ++j) {
@@ -348,6 +387,7 @@ __global__ __launch_bounds__(256, (SPLIT == 4 ? 4 : 1)) void guide_kernel(GuideA
             }
             // obstacle loop: volumes and d(volume)/d(face) coefficients                      lib/guide.py:387-392
             float cmin[3] = {0, 0, 0}, cmax[3] = {0, 0, 0};
+            double linkacc = 0.0;  // GM_CAND_VOL: this link's volumes in obstacle order, f64
             for (int ob = 0; ob < no; ++ob) {
                 const float* ab = obs + ob * 6;
                 float len[3], cl[3], wlo[3], whi[3];
@@ -370,6 +410,8 @@ __global__ __launch_bounds__(256, (SPLIT == 4 ? 4 : 1)) void guide_kernel(GuideA
                     if (row_ok && seg_ok) a.out[((size_t)r * (L + 1) + w) * (9 * no) + l * no + ob] = vol;
                 } else if (MODE == GM_SV_ROWSUM) {
                     if (seg_ok) rowacc += vol;
+                } else if (CAND) {
+                    linkacc += (double)vol;
                 } else {
                     const float p0 = cl[1] * cl[2], p1 = cl[0] * cl[2], p2 = cl[0] * cl[1];
                     const float pk[3] = {p0, p1, p2};
@@ -381,6 +423,7 @@ __global__ __launch_bounds__(256, (SPLIT == 4 ? 4 : 1)) void guide_kernel(GuideA
                     }
                 }
             }
+            if (CAND) candacc += linkacc;
             if (MODE == GM_GRAD) {
                 // route the segment-face coefficients to the waypoint that owns the face
                 float tmin[3], tmax[3];
@@ -449,7 +492,43 @@ __global__ __launch_bounds__(256, (SPLIT == 4 ? 4 : 1)) void guide_kernel(GuideA
     } else if (MODE == GM_SV_ROWSUM) {
         float tot = wave_sum(rowacc);
         if (row_ok && lane == 0) a.out[r] = tot;
+    } else if (CAND) {
+        // (float) sum_l ( sum_ob (double) v[l][ob] ): both sums sequential in f64 in index order, rounded to f32 once
+        if (row_ok) a.out[r] = (float)candacc;
     }
+}
+
+// one workgroup per scene of a candidate batch: key_r = ||start_s - goal_r|| for the scene's own rows (f64, squares added in joint
+// order without contraction, then one correctly rounded square root: np.linalg.norm(start - goals, axis=1) bit for bit), then the
+// trust-region pick among them (pick.h; equal keys: the smaller volume, then the first index).  out[s] = index inside the scene.
+// ||start - goal|| as NumPy evaluates np.linalg.norm(start - goals, axis=1): seven differences, seven squares, the squares added in
+// joint order, each operation rounded on its own, one correctly rounded root
+__device__ __forceinline__ double goal_key(const double* start, const double* __restrict__ goal) {
+#pragma clang fp contract(off)  // hipcc fuses a*b + c into an FMA by default (__dmul_rn / __dadd_rn are plain * and + compiled outside this pragma: no help)
+    double acc = 0.0;
+#pragma unroll
+    for (int j = 0; j < 7; ++j) {
+        const double d = start[j] - goal[j];
+        const double sq = d * d;
+        acc = acc + sq;
+    }
+    return __dsqrt_rn(acc);
+}
+struct GoalPickArgs {
+    int off[EDMP_MAX_SCENES + 1];
+    double start[EDMP_MAX_SCENES][7];
+};
+__global__ __launch_bounds__(kPickThreads) void goal_pick_kernel(const double* __restrict__ goals, const float* __restrict__ vol, double* key,
+                                                                 GoalPickArgs p, double trust, int* __restrict__ out) {
+    __shared__ Pick s_pick[kPickThreads / kWave];
+    const int s = blockIdx.x;
+    const int r0 = p.off[s], n = p.off[s + 1] - r0;
+    for (int b = threadIdx.x; b < n; b += kPickThreads) {
+        key[r0 + b] = goal_key(p.start[s], goals + (size_t)(r0 + b) * 7);
+    }
+    __syncthreads();  // the scene's keys are written by this workgroup and read by it alone
+    const int idx = segment_select<true>(vol + r0, key + r0, n, trust, s_pick);
+    if (threadIdx.x == 0) out[s] = idx;
 }
 
 // deterministic sum of the per-row partials -> one f64 (the whole-batch ||g||^2, lib/guide.py:629)
@@ -984,5 +1063,87 @@ extern "C" int edmp_scenes_swept_volumes_dev(edmp_ctx* ctx, const double* X_dev,
         EDMP_HIP_CHECK(hipMemcpyAsync(best_index_host, d_idx, S * sizeof(int), hipMemcpyDeviceToHost, ctx->stream));
         EDMP_HIP_CHECK(hipStreamSynchronize(ctx->stream));
     }
+    return EDMP_OK;
+}
+
+// the candidate scratch of the guide object: grow-only pool blocks; *moved when a block was replaced
+static int ensure_cand_scratch(edmp_ctx* ctx, Guide* g, int total, bool* moved) {
+    *moved = false;
+    if (g->cand_cap >= total) return EDMP_OK;
+    *moved = true;
+    EDMP_HIP_CHECK(hipStreamSynchronize(ctx->stream));  // nothing enqueued still reads the blocks that go back to the pool
+    for (void* p : {(void*)g->cand_vol, (void*)g->cand_key}) ctx_release(ctx, p);
+    g->cand_vol = nullptr;
+    g->cand_key = nullptr;
+    g->cand_cap = 0;
+    if (int rc = ctx_alloc(ctx, (void**)&g->cand_vol, (size_t)total * sizeof(float))) return rc;
+    if (int rc = ctx_alloc(ctx, (void**)&g->cand_key, (size_t)total * sizeof(double))) return rc;
+    g->cand_cap = total;
+    return EDMP_OK;
+}
+
+// the IK-goal filter of a whole scene group (infer_serial.py:117-129, once per scene there): one launch for every candidate's t = 0
+// volume against its own scene's obstacles, one launch for the per-scene pick
+extern "C" int edmp_scenes_goal_filter_dev(edmp_ctx* ctx, const double* goals_dev, int S, const int32_t* n_goals, const double* starts,
+                                           double trust_region, float* volumes_dev, double* key_dev, int* index_host) {
+    EDMP_REQUIRE_SCENE_BATCH(ctx, S, ctx->guide->rps, "edmp_scenes_goal_filter_dev");
+    Guide* g = ctx->guide;
+    EDMP_REQUIRE(goals_dev && n_goals && starts && index_host, "edmp_scenes_goal_filter_dev: goals, n_goals, starts and index_host are required (got%s%s%s%s NULL)",
+                 goals_dev ? "" : " goals", n_goals ? "" : " n_goals", starts ? "" : " starts", index_host ? "" : " index_host");
+    EDMP_REQUIRE(!std::isnan(trust_region) && trust_region >= 0.0, "edmp_scenes_goal_filter_dev: trust_region must be >= 0 (got %g)", trust_region);
+    static_assert(kPickThreads == 256, "a workgroup of the candidate kernel and of the pick hold the same 256 threads");
+    CandArgs a = {};
+    GoalPickArgs pk = {};
+    int64_t total = 0;
+    int blocks = 0;
+    for (int s = 0; s < S; ++s) {
+        EDMP_REQUIRE(n_goals[s] >= 1, "edmp_scenes_goal_filter_dev: scene %d brings %d candidates (need >= 1)", s, n_goals[s]);
+        a.sl.off[s] = pk.off[s] = (int)total;
+        a.sl.blk[s] = blocks;
+        total += n_goals[s];
+        EDMP_REQUIRE(total <= (int64_t)1 << 24, "edmp_scenes_goal_filter_dev: more than %d candidates in one call", 1 << 24);
+        blocks += (n_goals[s] + 255) / 256;
+        for (int j = 0; j < 7; ++j) pk.start[s][j] = starts[s * 7 + j];
+    }
+    a.sl.S = S;
+    a.sl.off[S] = pk.off[S] = (int)total;
+    a.sl.blk[S] = blocks;
+    // the first class of every scene (one scene: class 0 of the plain table)
+    for (int s = 0; s < S; ++s) a.sl.cls[s] = 0;
+    if (g->S > 1)
+        for (int c = g->G - 1; c >= 0; --c) a.sl.cls[g->cls_scene_h[c]] = c;
+    EDMP_HIP_CHECK(hipSetDevice(ctx->device));
+    if (!ctx->d_int) EDMP_HIP_CHECK(hipMalloc((void**)&ctx->d_int, EDMP_MAX_SCENES * sizeof(int)));  // kept for the life of the context
+    bool moved = false;
+    int rc = ensure_cand_scratch(ctx, g, (int)total, &moved);
+    if (moved) ctx->epoch++;
+    if (rc) return rc;
+    float* vol = volumes_dev ? volumes_dev : g->cand_vol;
+    double* key = key_dev ? key_dev : g->cand_key;
+    a.joints = goals_dev;  // candidate r, joint j at goals[r * 7 + j]: one waypoint per row
+    a.ldw = 1;
+    a.off = 0;
+    a.n = (int)total;
+    a.L = 1;
+    a.t = 0;
+    a.use_row_class = 0;
+    a.do_clip = 0;  // (cost clips nothing)
+    a.row_class = g->row_class;
+    a.method = g->method;
+    a.aabb = g->aabb;
+    a.T = g->T;
+    a.no = g->no;
+    a.cls_no = (g->S > 1) ? g->cls_no : nullptr;
+    a.cls_off = (g->S > 1) ? g->cls_no + g->G : nullptr;
+    a.rps = 0;
+    a.startgoal = g->startgoal;  // (not read: no start / goal column in a candidate)
+    a.out = vol;
+    a.rowsq = nullptr;
+    hipLaunchKernelGGL((guide_kernel<GM_CAND_VOL, double, 1, CandArgs>), dim3(blocks), dim3(256), 0, ctx->stream, a, g->rc);
+    EDMP_HIP_CHECK(hipGetLastError());
+    hipLaunchKernelGGL(goal_pick_kernel, dim3(S), dim3(kPickThreads), 0, ctx->stream, goals_dev, (const float*)vol, key, pk, trust_region, ctx->d_int);
+    EDMP_HIP_CHECK(hipGetLastError());
+    EDMP_HIP_CHECK(hipMemcpyAsync(index_host, ctx->d_int, S * sizeof(int), hipMemcpyDeviceToHost, ctx->stream));
+    EDMP_HIP_CHECK(hipStreamSynchronize(ctx->stream));
     return EDMP_OK;
 }

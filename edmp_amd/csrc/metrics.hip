@@ -21,6 +21,7 @@
 // any position of the row in the batch.  No floating-point atomics.
 #include "common.h"
 #include "guide.h"
+#include "pick.h"
 
 #include <cmath>
 
@@ -33,7 +34,7 @@ constexpr double kSparcZeroTol = 1e-8;  // np.allclose(profile, 0): every |v_i| 
 constexpr int kMetricsMinN = 3, kMetricsMaxN = 129;
 constexpr int kMetricsMaxM = kMetricsMaxN - 1;  // samples of a speed profile
 constexpr int kMetricsMaxNfft = 2048;           // 2^(ceil(log2 128) + 4)
-constexpr int kMetricsThreads = 256;
+constexpr int kMetricsThreads = kPickThreads;  // (block_pick reduces over a workgroup of this size)
 constexpr int kDftBins = 4;  // bins a thread accumulates side by side (1024 bins at N = 50: one pass)
 
 // rows 8-10 of the reference's modified-DH table [a, d, alpha, theta] (lib/guide.py:36-38) = evaluation.EE_STATIC_DH
@@ -230,32 +231,6 @@ __global__ __launch_bounds__(kMetricsThreads) void metrics_rows_kernel(const dou
     }
 }
 
-// lexicographic (class, value, index) minimum: the order both selection steps reduce under
-struct Pick {
-    int cls;
-    double val;
-    int idx;
-};
-__device__ __forceinline__ bool pick_before(const Pick& a, const Pick& b) {
-    if (a.cls != b.cls) return a.cls < b.cls;
-    if (a.val != b.val) return a.val < b.val;
-    return a.idx < b.idx;
-}
-__device__ __forceinline__ Pick block_pick(Pick mine, Pick* s_pick) {
-#pragma unroll
-    for (int o = 32; o > 0; o >>= 1) {
-        Pick other = {__shfl_xor(mine.cls, o, 64), __shfl_xor(mine.val, o, 64), __shfl_xor(mine.idx, o, 64)};
-        if (pick_before(other, mine)) mine = other;
-    }
-    __syncthreads();  // s_pick may still be read from the previous call
-    if (threadIdx.x % kWave == 0) s_pick[threadIdx.x / kWave] = mine;
-    __syncthreads();
-    Pick best = s_pick[0];
-    for (int w = 1; w < kMetricsThreads / kWave; ++w)
-        if (pick_before(s_pick[w], best)) best = s_pick[w];
-    return best;
-}
-
 // volumes (B,) f32, key (B,) f64 -> out[0]: m = first minimum of the volumes with NaN as the smallest value (argmin_kernel's rule,
 // lib/guide.py:650); a NaN minimum keeps m; else among the rows with (double)v_b < (double)v_m + trust the one with the smallest
 // finite key, first index on ties (infer_serial.py:119-129); m when no such row has a finite key.
@@ -264,33 +239,8 @@ __device__ __forceinline__ Pick block_pick(Pick mine, Pick* s_pick) {
 __global__ __launch_bounds__(kMetricsThreads) void select_row_kernel(const float* __restrict__ vol, const double* __restrict__ key, int B, double trust,
                                                                      int* __restrict__ out) {
     __shared__ Pick s_pick[kMetricsThreads / kWave];
-    const int tid = threadIdx.x;
-    vol += (size_t)blockIdx.x * B;
-    key += (size_t)blockIdx.x * B;
-    out += blockIdx.x;
-    const Pick none = {3, 0.0, 0x7fffffff};
-    Pick mine = none;
-    for (int b = tid; b < B; b += kMetricsThreads) {
-        const float x = vol[b];
-        const Pick c = (x != x) ? Pick{0, 0.0, b} : Pick{1, (double)x, b};
-        if (pick_before(c, mine)) mine = c;
-    }
-    const Pick m = block_pick(mine, s_pick);
-    if (m.cls == 0) {  // block-uniform: a NaN volume wins as it does in the reference
-        if (tid == 0) out[0] = m.idx;
-        return;
-    }
-    const double bound = m.val + trust;
-    mine = none;
-    for (int b = tid; b < B; b += kMetricsThreads) {
-        const double kb = key[b];
-        if ((double)vol[b] < bound && isfinite(kb)) {
-            const Pick c = {1, kb, b};
-            if (pick_before(c, mine)) mine = c;
-        }
-    }
-    const Pick w = block_pick(mine, s_pick);
-    if (tid == 0) out[0] = (w.cls == 1) ? w.idx : m.idx;
+    const int idx = segment_select<false>(vol + (size_t)blockIdx.x * B, key + (size_t)blockIdx.x * B, B, trust, s_pick);
+    if (threadIdx.x == 0) out[blockIdx.x] = idx;
 }
 
 }  // namespace edmp

@@ -33,6 +33,44 @@ def row_classes(clearance: np.ndarray, expansion: np.ndarray):
     return rc, np.ascontiguousarray(clearance[reps], dtype=np.float64), np.ascontiguousarray(expansion[reps], dtype=np.float64)
 
 
+def pick_goal(volumes, goals, start, volume_trust_region: float = 0.0008):
+    """The reference's IK-goal filter (infer_serial.py:119-129), the host rule stated once: sort the candidates by volume, keep those
+    with volume < min + volume_trust_region, take the one nearest to `start` (the first of the sorted list on equal distances: the
+    smaller volume, then - the sort is stable - the lower index).  volumes (M,), goals (M, 7), start (7,) -> (index into goals,
+    goals[index])."""
+    volumes, goals = np.asarray(volumes), np.asarray(goals)
+    indices = np.argsort(volumes, kind="stable")
+    indices = indices[volumes[indices] < np.min(volumes) + volume_trust_region]
+    index = int(indices[np.argmin(np.linalg.norm(start - goals[indices], axis=1))])
+    return index, goals[index]
+
+
+def goal_filter_inputs(n_scenes, starts, goals):
+    """SceneBatch.filter_goals' arguments, checked on the host before anything is launched: starts (S, 7) and a list of S arrays
+    (M_s, 7), M_s >= 1, all finite -> (starts (S,7) f64, goals (sum M_s, 7) f64 scene after scene, counts (S,) int32)."""
+    S = int(n_scenes)
+    st = np.ascontiguousarray(np.asarray(starts, dtype=np.float64))
+    if st.shape != (S, 7):
+        raise ValueError(f"starts must be ({S}, 7), got {st.shape}")
+    if isinstance(goals, np.ndarray) and goals.dtype != object:
+        goals = list(goals) if goals.ndim == 3 else None
+    if goals is None or len(goals) != S:
+        raise ValueError(f"goals must be a list of {S} arrays (M_s, 7), one per scene")
+    gl = []
+    for s, g in enumerate(goals):
+        a = np.asarray(g, dtype=np.float64)
+        if a.ndim != 2 or a.shape[1] != 7:
+            raise ValueError(f"goals[{s}] must be (M, 7), got {a.shape}")
+        if a.shape[0] < 1:
+            raise ValueError(f"goals[{s}] is empty: every scene brings at least one candidate")
+        if not np.isfinite(a).all():
+            raise ValueError(f"goals[{s}] holds non-finite values")
+        gl.append(a)
+    if not np.isfinite(st).all():
+        raise ValueError("starts holds non-finite values")
+    return st, np.ascontiguousarray(np.concatenate(gl)), np.asarray([a.shape[0] for a in gl], dtype=np.int32)
+
+
 class IntersectionVolumeGuide:
     """Same constructor / method signatures as the reference:
 
@@ -45,9 +83,13 @@ class IntersectionVolumeGuide:
     Link boxes: the reference measures the Franka collision meshes of pybullet_data every time a guide is built
     (lib/guide.py:245-282).  Here (franka.resolve_link_extents): ``link_mesh_extents`` (9,3) if given, else the meshes in
     ``mesh_dir``, else pybullet_data's directory when importable, else the placeholder table with one warning per process.
+
+    ``bind`` (default True): upload the scene tables and row arrays at once, as the reference's constructor builds its tensors.
+    bind=False builds the host tables only; the object binds at its first use.  A guide that only ever serves as one scene of a
+    SceneBatch never touches the device on its own.
     """
 
-    def __init__(self, obstacle_config, device, guide_cfgs, batch_size, *, link_mesh_extents=None, mesh_dir=None, obstacle_kinds=None):
+    def __init__(self, obstacle_config, device, guide_cfgs, batch_size, *, link_mesh_extents=None, mesh_dir=None, obstacle_kinds=None, bind=True):
         self.ctx = get_context(device)
         self.device = self.ctx.device
         self.guide_cfgs = guide_cfgs
@@ -73,7 +115,8 @@ class IntersectionVolumeGuide:
         # (r, r, h) boxes, quirk Q9).  The reference's loader orders obstacle_config cuboids first, then cylinders
         # (datasets/load_test_dataset.py:141-149), so kinds = [0] * num_cuboids + [1] * num_cylinders there.
         self._kinds = None if obstacle_kinds is None else self._check_kinds(obstacle_kinds)
-        self._bind()
+        if bind:
+            self._bind()
 
     # ---- binding -----------------------------------------------------------------------------------------------
     def _bind(self):
@@ -326,8 +369,11 @@ def scene_batch_tables(scenes):
 class SceneBatch:
     """S per-scene guides (IntersectionVolumeGuide, one context, equal batch_size and T, one robot) as ONE guide object of the
     library: scene s owns rows [s*B, (s+1)*B) of a (S*B, 7, N) run (Diffusion.denoise_guided_scenes).  The per-scene guides stay
-    what they were (the IK filter goes through them); the batch lives in its own resident slot, so switching between it and its
-    scenes re-uploads nothing while both stay resident.
+    what they were and may be unbound (IntersectionVolumeGuide(..., bind=False)): the batch reads their host tables only and lives in
+    its own resident slot, so switching between it and its scenes re-uploads nothing while both stay resident.
+
+    Before the run, filter_goals picks every scene's goal among its IK candidates in one call (the reference's IK-goal filter), so a
+    scene group touches the device through this one object from the first call to the last.
 
     The finished state is scored on the batch itself, one launch per step for all S scenes: row_swept_volumes, select_rows,
     choose_best_trajectories and success_rows take X as (S, B, 7, N) or (S*B, 7, N), ndarray or device tensor (the tensor of
@@ -389,6 +435,26 @@ class SceneBatch:
         if self._kinds is not None:
             _capi.check(ctx.lib.edmp_scene_batch_set_shapes(ctx.h, _capi.as_pi32(self._kinds), int(self._kinds.shape[0])), "edmp_scene_batch_set_shapes")
         ctx.bound_guide = self
+
+    # ---- before the run: the IK-goal filter of every scene ---------------------------------------------------------------
+    def filter_goals(self, starts, goals, volume_trust_region: float = 0.0008):
+        """The reference's IK-goal filter (infer_serial.py:117-129) for every scene of the batch in one call
+        (edmp_scenes_goal_filter_dev): starts (S, 7); goals a list of S arrays (M_s, 7), the scenes' own candidate counts.  Returns
+        (indices (S,) inside the scene, chosen (S, 7) f64, volumes: list of S (M_s,) f32 arrays) - per scene pick_goal's answer on that
+        scene's t = 0 candidate volumes.  Wrong shapes, an empty scene and non-finite goals or starts raise ValueError before anything
+        is launched."""
+        st, flat, counts = goal_filter_inputs(self.n_scenes, starts, goals)
+        self._bind()
+        ctx, S = self.ctx, self.n_scenes
+        gd = ctx.to_dev(flat, torch.float64)
+        vols = ctx.empty((flat.shape[0],), torch.float32)
+        idx = (C.c_int * S)()
+        _capi.check(ctx.lib.edmp_scenes_goal_filter_dev(ctx.h, ptr(gd), S, _capi.as_pi32(counts), _capi.as_pd(st), C.c_double(float(volume_trust_region)),
+                                                        ptr(vols), None, idx), "edmp_scenes_goal_filter_dev")
+        vh = ctx.to_host(vols)
+        off = np.concatenate([[0], np.cumsum(counts)])
+        indices = np.array(idx[:], dtype=np.int64)
+        return indices, flat[off[:-1] + indices].copy(), [vh[off[s]:off[s + 1]].copy() for s in range(S)]
 
     # ---- scoring the finished state of the batch ------------------------------------------------------------------------
     def _check_kinds(self, kinds):

@@ -294,6 +294,35 @@ int edmp_scenes_select_rows_dev(edmp_ctx* ctx, const float* volumes_dev, const d
 int edmp_scenes_success_rows_dev(edmp_ctx* ctx, const double* X_dev, int S, int B, int N, int substeps, const double* dh_f64,
                                  int32_t* ok_dev, int32_t* first_dev, int32_t* within_dev, int32_t* counts_host);
 
+/* The reference's IK-goal filter (infer_serial.py:117-129: guide.cost of every candidate at t = 0, summed; everything within
+ * volume_trust_region of the minimum; of those the goal nearest to the start) for ALL scenes of a bound scene batch in two launches,
+ * where the per-scene route is one guide object, one edmp_guide_cost_dev launch, a reduction and a copy back per scene.
+ * goals (sum n_goals, 7) f64 on the device, scene after scene; n_goals (S,) int32 on the host, each >= 1 (scenes bring unequal numbers
+ * of candidates); starts (S,7) f64 on the host.
+ *   volumes (sum n_goals,) f32: candidate r of scene s against scene s's uninflated (t = 0) obstacles: every (link, obstacle) element
+ *     is bit for bit the element edmp_guide_cost_dev(goal.reshape(1,7,1), t = 0) writes on scene s's own guide (the joints are cast to
+ *     f32, nothing is clipped); they are added as (float) sum_{l=0..8} ( sum_{ob=0..no-1} (double) v[l][ob] ), both sums sequential in
+ *     f64 in index order, rounded to f32 once.  The reference's torch f32 .sum(axis=(1,2)) differs from this by summation rounding only.
+ *   key (sum n_goals,) f64: sqrt(sum_j (start_s[j] - goal_r[j])^2), the squares added in joint order without contraction and the root
+ *     correctly rounded = np.linalg.norm(start - goals, axis=1) bit for bit (infer_serial.py:129).
+ *   index_host (S,) int, inside the scene: edmp_select_row_dev's rule on the scene's own rows - m = the first minimum volume (NaN counts
+ *     as smallest and keeps m); the candidates are the rows with (double) v < (double) v_m + trust_region; of those the smallest finite
+ *     key; on equal keys the smaller volume, then the lower index (the reference takes the arg-min over the volume-sorted list,
+ *     infer_serial.py:121-129); m if no candidate has a finite key.
+ * volumes_dev / key_dev may be NULL (kept in the guide object's scratch: pool blocks, grow-only; the context's epoch is bumped when a
+ * block moves).  The call synchronises (index_host).  No floating-point atomics: results are bit-identical between runs, and a scene's
+ * results depend neither on its neighbours nor on its position in the batch.
+ * Needs a bound scene batch of exactly S scenes (a batch of ONE scene included): refused with EDMP_ERR_STATE on a single-scene guide,
+ * with EDMP_ERR_ARG for another S, any n_goals[s] < 1, a NULL goals / n_goals / starts / index_host or a negative trust_region; a
+ * refused call launches nothing and changes nothing.
+ * The call reads the scene tables only: it does not touch the guide's start / goal pairs, the sampler or the model's buffers, so -
+ * unlike edmp_scenes_swept_volumes_dev - it does NOT end a segmented run: the next segment continues as if the call had not been made.
+ * (The scratch rule above is the one way it can still get in a run's way: a call whose scratch has to grow bumps the epoch, and a run in
+ * progress under the old epoch refuses its next segment.  A call of at least that many candidates before the run - the driver's order
+ * of events - leaves nothing to grow.) */
+int edmp_scenes_goal_filter_dev(edmp_ctx* ctx, const double* goals_dev, int S, const int32_t* n_goals, const double* starts,
+                                double trust_region, float* volumes_dev, double* key_dev, int* index_host);
+
 /* Device noise source — explicitly NOT the reference's NumPy RandomState stream (that contract is served by
  * edmp_denoise_guided_dev): Philox4x32-10 counter RNG + Box-Muller inside the sampler kernels, no noise tensor, no
  * host draw, no upload.  Same loop otherwise (replaces diffusion.py:300-356 with z ~ N(0, I) drawn on the GPU).
