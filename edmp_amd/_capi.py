@@ -86,6 +86,8 @@ SIGNATURES = {
     "edmp_scenes_select_rows_dev": (_i, [_vp, _vp, _vp, _i, _i, _d, C.POINTER(_i)]),
     "edmp_scenes_success_rows_dev": (_i, [_vp, _vp, _i, _i, _i, _i, _pd, _vp, _vp, _vp, _pi32]),
     "edmp_scenes_goal_filter_dev": (_i, [_vp, _vp, _i, _pi32, _pd, _d, _vp, _vp, C.POINTER(_i)]),
+    "edmp_ik_solve_dev": (_i, [_vp, _pd, _i, _pi32, _vp, _pd, _i, _d, _d, _d, _d, _vp, _vp, _vp]),
+    "edmp_ik_compact_dev": (_i, [_vp, _vp, _vp, _i, _pi32, _vp, _pi32]),
     "edmp_q_sample_dev": (_i, [_vp, _vp, _vp, _pi32, _i, _i, _i, _i, _i, _vp, _vp]),
     "edmp_unet_packed_size": (C.c_int64, [_vp, C.POINTER(C.c_int)]),
     "edmp_unet_read_packed": (_i, [_vp, _pf, C.c_int64]),

@@ -71,6 +71,31 @@ def goal_filter_inputs(n_scenes, starts, goals):
     return st, np.ascontiguousarray(np.concatenate(gl)), np.asarray([a.shape[0] for a in gl], dtype=np.int32)
 
 
+def goal_filter_device_inputs(n_scenes, starts, goals, counts):
+    """SceneBatch.filter_goals' device form, checked on the host before anything is launched: starts (S, 7) finite; goals a dense
+    (sum counts, 7) f64 device tensor, scene after scene; counts (S,), each >= 1 -> (starts (S,7) f64, counts (S,) int32).  The rows
+    themselves are not read back: they are what a kernel of this library wrote."""
+    S = int(n_scenes)
+    st = np.ascontiguousarray(np.asarray(starts, dtype=np.float64))
+    if st.shape != (S, 7):
+        raise ValueError(f"starts must be ({S}, 7), got {st.shape}")
+    if not np.isfinite(st).all():
+        raise ValueError("starts holds non-finite values")
+    if counts is None:
+        raise ValueError("the device form of goals is a dense (sum counts, 7) float64 device tensor together with counts=(S,)")
+    cn = np.asarray(counts)
+    if cn.shape != (S,) or not np.issubdtype(cn.dtype, np.integer):
+        raise ValueError(f"counts must be ({S},) integers, one per scene, got {cn.dtype} {cn.shape}")
+    for s in range(S):
+        if cn[s] < 1:
+            raise ValueError(f"scene {s} brings {int(cn[s])} goal candidates: every scene needs at least one (no IK solution for its target?)")
+    if not (isinstance(goals, torch.Tensor) and goals.is_cuda):
+        raise ValueError("the device form of goals is a dense (sum counts, 7) float64 device tensor together with counts=(S,)")
+    if goals.dtype != torch.float64 or goals.dim() != 2 or tuple(goals.shape) != (int(cn.sum()), 7):
+        raise ValueError(f"goals must be a float64 device tensor of shape ({int(cn.sum())}, 7) = (sum counts, 7), got {goals.dtype} {tuple(goals.shape)}")
+    return st, np.ascontiguousarray(cn.astype(np.int32))
+
+
 class IntersectionVolumeGuide:
     """Same constructor / method signatures as the reference:
 
@@ -437,24 +462,39 @@ class SceneBatch:
         ctx.bound_guide = self
 
     # ---- before the run: the IK-goal filter of every scene ---------------------------------------------------------------
-    def filter_goals(self, starts, goals, volume_trust_region: float = 0.0008):
+    def filter_goals(self, starts, goals, volume_trust_region: float = 0.0008, counts=None):
         """The reference's IK-goal filter (infer_serial.py:117-129) for every scene of the batch in one call
         (edmp_scenes_goal_filter_dev): starts (S, 7); goals a list of S arrays (M_s, 7), the scenes' own candidate counts.  Returns
         (indices (S,) inside the scene, chosen (S, 7) f64, volumes: list of S (M_s,) f32 arrays) - per scene pick_goal's answer on that
         scene's t = 0 candidate volumes.  Wrong shapes, an empty scene and non-finite goals or starts raise ValueError before anything
-        is launched."""
-        st, flat, counts = goal_filter_inputs(self.n_scenes, starts, goals)
+        is launched.
+
+        The device form: goals a dense (sum M_s, 7) f64 device tensor, scene after scene, with `counts` (S,) - what
+        ik.solve(..., return_device=True) returns as goals + counts - goes into the filter as it lies, without a host round trip; the
+        results are those of the host form on the same numbers.  A scene with a count of 0 raises ValueError naming the scene."""
+        flat = None
+        if counts is not None or (isinstance(goals, torch.Tensor) and goals.is_cuda):
+            st, counts = goal_filter_device_inputs(self.n_scenes, starts, goals, counts)
+        else:
+            st, flat, counts = goal_filter_inputs(self.n_scenes, starts, goals)
         self._bind()
         ctx, S = self.ctx, self.n_scenes
-        gd = ctx.to_dev(flat, torch.float64)
-        vols = ctx.empty((flat.shape[0],), torch.float32)
+        gd = ctx.to_dev(flat, torch.float64) if flat is not None else ctx.adopt(goals.contiguous())
+        vols = ctx.empty((gd.shape[0],), torch.float32)
         idx = (C.c_int * S)()
         _capi.check(ctx.lib.edmp_scenes_goal_filter_dev(ctx.h, ptr(gd), S, _capi.as_pi32(counts), _capi.as_pd(st), C.c_double(float(volume_trust_region)),
                                                         ptr(vols), None, idx), "edmp_scenes_goal_filter_dev")
         vh = ctx.to_host(vols)
         off = np.concatenate([[0], np.cumsum(counts)])
         indices = np.array(idx[:], dtype=np.int64)
-        return indices, flat[off[:-1] + indices].copy(), [vh[off[s]:off[s + 1]].copy() for s in range(S)]
+        if flat is None:
+            with torch.cuda.stream(ctx.stream):
+                picked = gd[torch.as_tensor(off[:-1] + indices, device=gd.device)]
+            chosen = ctx.to_host(picked)
+            gd.record_stream(ctx.stream)
+        else:
+            chosen = flat[off[:-1] + indices].copy()
+        return indices, chosen, [vh[off[s]:off[s + 1]].copy() for s in range(S)]
 
     # ---- scoring the finished state of the batch ------------------------------------------------------------------------
     def _check_kinds(self, kinds):

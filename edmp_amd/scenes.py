@@ -123,7 +123,9 @@ class ProblemSetDataset:
     is the length of the CUBBY list, like the reference's (:61).
 
     IK goals (robofin's ikfast on the problem's target pose, :170-187) are an explicit input: the problem's own ``goals`` list if
-    the file carries one, else ``ik(target_xyz, target_quaternion_wxyz) -> (n, 7)`` if a callable is given; neither -> ValueError."""
+    the file carries one, else ``ik(target_xyz, target_quaternion_wxyz) -> (n, 7)`` if a callable is given (``edmp_amd.ik.FrankaIK`` is
+    one: batched numerical IK on the GPU); neither -> ValueError.  A caller that solves a whole group's targets at once reads them with
+    ``target_pose`` and hands each problem's candidates to ``fetch_data(..., goals=)``."""
 
     def __init__(self, path, ik=None):
         import json
@@ -138,12 +140,26 @@ class ProblemSetDataset:
         if "merged_cubby" in self.data_nums and "cubby" in self.data_nums:
             self.data_nums["merged_cubby"] = len(self.problems["cubby"])  # datasets/load_test_dataset.py:61
 
-    def fetch_data(self, scene_num, scene_type="tabletop"):
+    def target_pose(self, scene_num, scene_type="tabletop"):
+        """(xyz (3,), quaternion_wxyz (4,)) f64 of the problem's target pose, or None when the problem carries its own ``goals`` (which
+        fetch_data then uses) - what an IK solver needs to produce them"""
+        if scene_type not in self.problems:
+            raise ModuleNotFoundError(f"no scene type {scene_type!r} in this problem set ({sorted(self.problems)})")
+        pr = self.problems[scene_type][scene_num]
+        if "goals" in pr and len(pr["goals"]):
+            return None
+        if "target" not in pr:
+            raise ValueError(f"{scene_type}[{scene_num}] carries neither IK goals nor a target pose")
+        return np.asarray(pr["target"]["xyz"], dtype=np.float64), np.asarray(pr["target"]["quaternion_wxyz"], dtype=np.float64)
+
+    def fetch_data(self, scene_num, scene_type="tabletop", goals=None):
         if scene_type not in self.problems:
             raise ModuleNotFoundError(f"no scene type {scene_type!r} in this problem set ({sorted(self.problems)})")
         pr = self.problems[scene_type][scene_num]
         if "goals" in pr and len(pr["goals"]):
             goals = np.atleast_2d(np.asarray(pr["goals"], dtype=np.float64))
+        elif goals is not None:  # computed by the caller from target_pose (a group's targets solved in one call)
+            goals = np.atleast_2d(np.asarray(goals, dtype=np.float64))
         elif self.ik is not None:
             goals = np.atleast_2d(np.asarray(self.ik(np.asarray(pr["target"]["xyz"], float), np.asarray(pr["target"]["quaternion_wxyz"], float)), dtype=np.float64))
         else:

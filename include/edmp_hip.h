@@ -323,6 +323,38 @@ int edmp_scenes_success_rows_dev(edmp_ctx* ctx, const double* X_dev, int S, int 
 int edmp_scenes_goal_filter_dev(edmp_ctx* ctx, const double* goals_dev, int S, const int32_t* n_goals, const double* starts,
                                 double trust_region, float* volumes_dev, double* key_dev, int* index_host);
 
+/* ---- IK goal candidates (csrc/ik.hip) ---------------------------------------------------------------------- */
+/* Stands for FrankaRobot.ik of the problem's target pose (datasets/load_test_dataset.py:170-187: robofin's ikfast, not part of this
+ * package): a batched NUMERICAL inverse kinematics of the 7-DoF arm, damped least squares from many seeds, for all targets of a scene
+ * group in ONE launch (one lane per seed, f64 throughout).  The candidates are points of the same solution continuum as the
+ * reference's, not its numbers.
+ *   targets (T,12) f64 on the host: row-major 3x4 [R | p] of the tool frame in the base frame;  n_seeds (T,) int32 on the host, each >= 1
+ *   (ragged);  seeds (sum n_seeds, 7) f64 on the device, target after target;  tool (12,) f64 on the host: the fixed 3x4 frame behind
+ *   the joint-7 frame of the modified-DH chain (lib/guide.py:29-35) whose pose is matched.
+ * Per seed, `iters` times: FK; e = [p_t - p ; 1/2 sum_k R[:,k] x R_t[:,k]]; the geometric 6x7 Jacobian J; dq = J^T (J J^T + lambda^2 I)^-1 e
+ * by a Cholesky factorisation; dq scaled so that max|dq| <= max_step; q clamped to the joint limits (diffusion/diffusion.py:282-296).
+ * After the last step, per seed (row r of the flat seed array):
+ *   q (sum,7) f64: the final configuration, inside the limits;
+ *   residuals (sum,2) f64: |p_t - p| [m] and the rotation angle of R^T R_t [rad], atan2(|vee|, (trace - 1) / 2) - the true angle: a pose
+ *     turned by pi has a vanishing cross-product error and must not pass;
+ *   valid (sum,) int32: 1 iff q and both residuals are finite, position <= tol_pos and angle <= tol_ang.
+ * A seed's outputs depend on (its target, the seed, the parameters) only - not on the other seeds or targets of the call - and are
+ * bit-identical between runs.  edmp_amd/ik.py's defaults: iters 64, lambda 0.01, max_step 0.5, tol_pos 1e-6, tol_ang 1e-6.
+ * EDMP_ERR_ARG, before anything is launched: a NULL pointer, T < 1, a count < 1, iters < 1, lambda <= 0, max_step <= 0, a negative
+ * tolerance, a non-finite parameter, target or tool entry, a target or tool rotation that is not orthonormal to 1e-9 (or a reflection).
+ * Context-level: needs no model, scene or rows, reads and replaces nothing of theirs, and does not end a segmented run.  Synchronises
+ * (the targets' device copy is a temporary of the call).
+ *
+ * edmp_ik_compact_dev: the valid rows of q, densely, in seed order, target after target -> goals (n_valid_total, 7) f64 on the device
+ * (room for sum n_seeds rows), counts_host (T,) int32 - exactly edmp_scenes_goal_filter_dev's goals_dev + n_goals, whose tie-breaks go
+ * by index, so the order is part of the result (stable; no atomics).  A target may come out with count 0; the filter refuses such a
+ * scene.  Same binding rules; synchronises (counts_host). */
+int edmp_ik_solve_dev(edmp_ctx* ctx, const double* targets, int T, const int32_t* n_seeds, const double* seeds_dev, const double* tool,
+                      int iters, double lambda, double max_step, double tol_pos, double tol_ang, double* q_dev, double* residuals_dev,
+                      int32_t* valid_dev);
+int edmp_ik_compact_dev(edmp_ctx* ctx, const double* q_dev, const int32_t* valid_dev, int T, const int32_t* n_seeds, double* goals_dev,
+                        int32_t* counts_host);
+
 /* Device noise source — explicitly NOT the reference's NumPy RandomState stream (that contract is served by
  * edmp_denoise_guided_dev): Philox4x32-10 counter RNG + Box-Muller inside the sampler kernels, no noise tensor, no
  * host draw, no upload.  Same loop otherwise (replaces diffusion.py:300-356 with z ~ N(0, I) drawn on the GPU).

@@ -130,7 +130,8 @@ def job_summary(results, world=1):
     return out
 
 
-def run(cfg_path, dataset=None, max_scenes=None, verbose=True, scenes_in_flight=1, shard_scenes=True, scenes_per_launch=1, ensemble_report=False, prefer=None):
+def run(cfg_path, dataset=None, max_scenes=None, verbose=True, scenes_in_flight=1, shard_scenes=True, scenes_per_launch=1, ensemble_report=False, prefer=None,
+        ik_seeds=0, ik_tool=None, ik_seed=0):
     """The reference's scene loop (infer_serial.py:95-170).  Under ``torch.distributed.run`` (one process per GPU, extension: the
     reference is one process) the scenes are dealt round-robin to the ranks - scene i of the cfg's order goes to rank i mod world -
     and nothing is exchanged until `job_summary` adds the tallies up: scenes are independent problems, this is the problem set's natural
@@ -158,7 +159,13 @@ def run(cfg_path, dataset=None, max_scenes=None, verbose=True, scenes_in_flight=
     the cfg with its rows' collision-free / ok counts, best row, minimum swept volume and the mean / median metrics of its collision-free
     rows (evaluation.ensemble_report).  ``prefer`` = "shortest" | "smoothest" (an extension) picks the plan with
     IntersectionVolumeGuide.select_row - among the rows within the trust region of the minimum swept volume, the shortest joint path /
-    the smoothest - instead of the first arg-min, and records `prefer` in the result.  Without either the results are the reference-shaped ones."""
+    the smoothest - instead of the first arg-min, and records `prefer` in the result.  Without either the results are the reference-shaped ones.
+
+    ``ik_seeds`` = n > 0 (an extension; 0 = off, nothing changes) plans a problem set whose problems carry a target pose and no IK goals:
+    the candidates come from edmp_amd.ik.FrankaIK (batched numerical IK on the GPU, n seeds per target from a private RandomState(ik_seed),
+    never the global stream the feeder is advancing); with scenes_per_launch the group's targets are solved in one solve_many call.
+    ``ik_tool`` is the frame the targets are given in, behind the joint-7 frame (ik.tool_frame: None = the reference's end-effector chain,
+    "flange", "hand" or a (4, 4) array - MPiNets' right_gripper offset is the caller's to pass).  Problems that carry goals keep them."""
     from concurrent.futures import ThreadPoolExecutor
 
     from edmp_amd.runtime import get_context, lane_context
@@ -218,6 +225,25 @@ def run(cfg_path, dataset=None, max_scenes=None, verbose=True, scenes_in_flight=
         ctx = lane_context(base, j)  # lane 0 = the device's context; further lanes are cached per (device, lane), not re-created per call
         lanes.append((Diffusion(T=T, device=ctx), TemporalUNet(model_name=model_name, input_dim=num_channels, time_dim=32, dims=(32, 64, 128, 256, 512, 512),
                                                                 device=ctx, max_batch=total_batch_size * kl)))
+
+    ik_seeds = int(ik_seeds)
+    if ik_seeds < 0:
+        raise ValueError(f"ik_seeds must be >= 0, got {ik_seeds}")
+    iks = []  # one solver per lane (a lane's context is only touched while its previous scene is done)
+    if ik_seeds > 0 and hasattr(dataset, "target_pose"):
+        from edmp_amd.ik import FrankaIK
+
+        iks = [FrankaIK(lane[0].ctx, n_seeds=ik_seeds, seed=ik_seed, tool=ik_tool) for lane in lanes]
+
+    def fetch(lane, scenes_of_group):
+        """dataset.fetch_data per scene; with ik_seeds, the targets of the scenes that bring no goals are solved first, in one call"""
+        if not iks:
+            return [dataset.fetch_data(scene_num=scene_num, scene_type=scene_type) for _, scene_type, scene_num in scenes_of_group]
+        poses = [dataset.target_pose(scene_num, scene_type) for _, scene_type, scene_num in scenes_of_group]
+        need = [j for j, p in enumerate(poses) if p is not None]
+        solved = dict(zip(need, iks[lane].solve_many([poses[j] for j in need])["goals"])) if need else {}
+        return [dataset.fetch_data(scene_num=scene_num, scene_type=scene_type, **({"goals": solved[j]} if j in solved else {}))
+                for j, (_, scene_type, scene_num) in enumerate(scenes_of_group)]
 
     def plan(lane, guide, start_joints, goal_joints, noise, meta, t0):
         diffuser, denoiser = lanes[lane]
@@ -290,7 +316,7 @@ def run(cfg_path, dataset=None, max_scenes=None, verbose=True, scenes_in_flight=
         """guides + IK filter of a scene group (infer_serial.py:108-129, once per scene there): the guides are host tables only
         (bind=False), the SceneBatch is the one object on the device, and ONE filter_goals call picks every scene's goal.
         -> (batch, [(guide, start, goal, meta, t0) per scene]); guide_ctor_s / ik_filter_s are the GROUP's times"""
-        data = [dataset.fetch_data(scene_num=scene_num, scene_type=scene_type) for _, scene_type, scene_num in scenes_of_group]
+        data = fetch(0, scenes_of_group)
         t0 = time.time()
         guides = []
         for obstacle_config, _, _, num_cuboids, num_cylinders, _, _ in data:
@@ -366,7 +392,7 @@ def run(cfg_path, dataset=None, max_scenes=None, verbose=True, scenes_in_flight=
                 lane = (i // world) % k
                 while len(pending) >= k:  # the lane's previous scene (and every earlier one) is done before its context is reused
                     collect(pending.pop(0))
-                obstacle_config, _, _, num_cuboids, num_cylinders, start_joints, all_ik_goals = dataset.fetch_data(scene_num=scene_num, scene_type=scene_type)
+                obstacle_config, _, _, num_cuboids, num_cylinders, start_joints, all_ik_goals = fetch(lane, [(i, scene_type, scene_num)])[0]
                 t0 = time.time()
                 # obstacle_config = cuboids first, then cylinders as (r, r, h) boxes (datasets/load_test_dataset.py:141-149); the
                 # success check spawns the latter as true cylinders (infer_serial.py:159-163 -> lib/environment.py:249-268)
@@ -415,12 +441,25 @@ def main(argv=None):
                                                                        "ensemble, its collision-free rows and their metrics (extension; adds `ensemble` to the results)")
     parser.add_argument("--prefer", choices=("shortest", "smoothest"), default=None, help="among the rows within the trust region of the minimum swept volume pick the "
                                                                                              "shortest joint path / the smoothest plan instead of the first arg-min (extension)")
+    parser.add_argument("--ik-seeds", type=int, default=0, help="solve the IK of problems that carry a target pose and no goals on the GPU, from this many "
+                                                                  "seeds per target (extension; 0 = off: such a problem set raises as before)")
+    parser.add_argument("--ik-tool", type=str, default=None, help="the frame the targets are given in: 'flange', 'hand', or a JSON / .npy file holding a (4, 4) "
+                                                                    "frame behind the joint-7 frame (default: the reference's end-effector chain)")
     args = parser.parse_args(argv)
+    ik_tool = args.ik_tool
+    if ik_tool is not None and ik_tool not in ("flange", "hand"):
+        if ik_tool.endswith(".npy"):
+            ik_tool = np.load(ik_tool)
+        else:
+            import json
+
+            with open(ik_tool) as f:
+                ik_tool = np.asarray(json.load(f), dtype=np.float64)
     rank = int(os.environ.get("RANK", "0"))
     if args.seed is not None:
         np.random.seed(args.seed + rank)
     results = run(args.cfg_path, scenes_in_flight=args.scenes_in_flight, max_scenes=args.max_scenes, scenes_per_launch=args.scenes_per_launch,
-                  ensemble_report=args.ensemble_report, prefer=args.prefer)
+                  ensemble_report=args.ensemble_report, prefer=args.prefer, ik_seeds=args.ik_seeds, ik_tool=ik_tool)
     if args.results_json:
         import json
 

@@ -16,9 +16,11 @@ attribute record, lets an exact list of NumPy's array / scalar / dtype reconstru
   * cuboids come before cylinders in obstacle_config (:141-149), a cylinder enters the guide as a box of extents (r, r, h)
     (:136-139, quirk Q9) - `problem_to_arrays` again, from the `radius` / `height` kept here;
   * obstacles that are neither Cuboid nor Cylinder are ignored, as the reference's isinstance chain ignores them (:105-116).
-IK goals (robofin's ikfast on `data.target`, :170-187) cannot be computed here: the end-effector target pose is written out
-(`target`), and goals are an explicit input - `--ik-goals file.json` = {"<scene_type>": [[[7 floats], ...] per problem]} - or
-are supplied at load time (`ProblemSetDataset(path, ik=callable)`).
+IK goals (robofin's ikfast on `data.target`, :170-187) are not computed by this converter: the end-effector target pose is written
+out (`target`, `"frame": "right_gripper"`), and goals are an explicit input - `--ik-goals file.json` = {"<scene_type>": [[[7 floats], ...]
+per problem]} - or are produced at load time (`ProblemSetDataset(path, ik=callable)`; `edmp_amd.ik.FrankaIK(device, tool=<frame>)` is such
+a callable: batched numerical IK on the GPU, `infer_serial.py --ik-seeds N --ik-tool <frame>`).  The offset of `right_gripper` from the
+joint-7 frame is defined by robofin's URDF, which this package cannot cite: the caller passes it as `tool=`.
 """
 from __future__ import annotations
 
