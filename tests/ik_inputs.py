@@ -94,8 +94,17 @@ def _errors(Re, pe, Rt, pt):
     return ep, er, tr
 
 
-def dls_numpy(target, seeds, tool=None, iters=ITERS, damping=DAMPING, max_step=MAX_STEP, tol_pos=TOL_POS, tol_ang=TOL_ANG):
-    """the iteration of csrc/ik.hip for one target (4, 4) and seeds (n, 7) -> (q (n, 7), residuals (n, 2), valid (n,) bool)"""
+VARIANTS = ("lever", "lambda", "l2_scale", "no_clamp_j6", "error_sign", "body_frame_error")
+
+
+def dls_numpy(target, seeds, tool=None, iters=ITERS, damping=DAMPING, max_step=MAX_STEP, tol_pos=TOL_POS, tol_ang=TOL_ANG, variant=None):
+    """the iteration of csrc/ik.hip for one target (4, 4) and seeds (n, 7) -> (q (n, 7), residuals (n, 2), valid (n,) bool).
+    `variant` names ONE deliberate mistake (VARIANTS) - the lever arm taken to the joint-7 origin instead of the tool point, lambda where
+    lambda^2 belongs, the L2 norm of the step where the max norm belongs, joint 6 left unclamped, the rotation error negated, the rotation
+    error in the tool's frame: they exist only so that tests/test_ik_reference_host.py can show that the gates of tests/ik_reference.py
+    separate each of them from the iteration; None is the iteration, with unchanged arithmetic"""
+    if variant is not None and variant not in VARIANTS:
+        raise ValueError(f"unknown variant {variant!r}")
     lo, hi = franka.joint_limits()
     tool4 = tool_matrix(tool)
     Rt, pt = np.asarray(target)[:3, :3], np.asarray(target)[:3, 3]
@@ -103,13 +112,22 @@ def dls_numpy(target, seeds, tool=None, iters=ITERS, damping=DAMPING, max_step=M
     for _ in range(int(iters)):
         z, p, Re, pe = _chain(q, tool4)
         ep, er, _ = _errors(Re, pe, Rt, pt)
+        if variant == "error_sign":
+            er = -er
+        elif variant == "body_frame_error":
+            er = np.einsum("nab,na->nb", Re, er)
         e = np.concatenate([ep, er], axis=1)
-        J = np.concatenate([np.cross(z, pe[:, None, :] - p), z], axis=2).transpose(0, 2, 1)  # (n, 6, 7)
-        A = J @ J.transpose(0, 2, 1) + damping * damping * np.eye(6)
+        tip = p[:, 6] if variant == "lever" else pe
+        J = np.concatenate([np.cross(z, tip[:, None, :] - p), z], axis=2).transpose(0, 2, 1)  # (n, 6, 7)
+        A = J @ J.transpose(0, 2, 1) + (damping if variant == "lambda" else damping * damping) * np.eye(6)
         dq = np.einsum("naj,na->nj", J, np.linalg.solve(A, e[:, :, None])[:, :, 0])
-        big = np.max(np.abs(dq), axis=1, keepdims=True)
+        big = np.linalg.norm(dq, axis=1, keepdims=True) if variant == "l2_scale" else np.max(np.abs(dq), axis=1, keepdims=True)
         dq = dq * np.where(big > max_step, max_step / np.where(big > 0, big, 1.0), 1.0)
+        if variant == "no_clamp_j6":
+            unclamped = (q + dq)[:, 5]
         q = np.clip(q + dq, lo, hi)
+        if variant == "no_clamp_j6":
+            q[:, 5] = unclamped
     _, _, Re, pe = _chain(q, tool4)
     ep, er, tr = _errors(Re, pe, Rt, pt)
     pos = np.linalg.norm(ep, axis=1)

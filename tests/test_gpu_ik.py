@@ -3,7 +3,8 @@
 
 The reference is not the code under test: tests/ik_inputs.py holds an f64 FK written from evaluation._dh / franka.DH_A_D_ALPHA /
 EE_STATIC_DH and a NumPy restatement of the iteration; tests/test_ik_host.py checks on the CPU that the restatement finds at least 32
-solutions per target from these seeds.  Every goal the GPU returns must reproduce its target under that FK."""
+solutions per target from these seeds.  Every goal the GPU returns must reproduce its target under that FK.  The iteration itself is
+compared step by step in tests/test_gpu_ik_steps.py."""
 import json
 import os
 
@@ -49,9 +50,12 @@ def test_every_goal_is_a_solution_in_seed_order(full):
 
 
 def test_yield_against_the_numpy_restatement(full):
-    """per target at least one solution and at least half as many as the restatement finds from the same seeds: per-seed outcomes may
-    differ (the early iterations are not contractive), the rate does not - the binomial spread at 256 seeds is 7-8 seeds, half the host
-    count is more than four spreads below it at the lowest yield, and far above what a wrong Jacobian, damping or clamp reaches"""
+    """per target at least one solution and at least half as many as the restatement finds from the same seeds.  Per seed, two correct
+    f64 formulations agree through 16 iterations (to 3e-13 rad after one step, 8e-11 after 16, over all 2048 seeds:
+    tests/ik_reference.floors) - that agreement is what tests/test_gpu_ik_steps.py holds the kernel to; by 64 iterations the steps far
+    from a solution have amplified the rounding so far that 91 of the 2048 rows end more than 1e-9 apart, some on another branch,
+    so at the default iteration count only the RATE is compared here: the binomial spread at 256 seeds is 7-8 seeds and half the host
+    count is more than four spreads below it at the lowest yield"""
     host = [int(v.sum()) for _, _, v in I.host_solutions()]
     gpu = [int(c) for c in full["counts"]]
     print("valid of 256 seeds per target: gpu", gpu, "host restatement", host)
