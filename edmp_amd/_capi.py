@@ -11,6 +11,7 @@ LIB_PATH = os.path.join(_HERE, "libedmp_hip.so")
 MAX_LEVELS = 8
 MAX_SCENES = 16  # EDMP_MAX_SCENES
 MAX_OBSTACLES = 64  # EDMP_MAX_OBSTACLES
+MAX_SPHERES = 128  # EDMP_MAX_SPHERES
 
 
 class UNetDesc(C.Structure):
@@ -98,6 +99,8 @@ SIGNATURES = {
     "edmp_unet_slot": (_i, [_vp, C.c_uint64]),
     "edmp_guide_slot": (_i, [_vp, C.c_uint64]),
     "edmp_argmin_dev": (_i, [_vp, _vp, _i, C.POINTER(C.c_int)]),
+    "edmp_sdf_set": (_i, [_vp, _pf, _i, _pi32, _pd, _pd, _i, _i]),
+    "edmp_sdf_rows_dev": (_i, [_vp, _vp, _i, _i, _i, _pd, _pd, _vp, _vp]),
     "edmp_sampler_set_allreduce": (_i, [_vp, _vp, _vp]),
     "edmp_rccl_load": (_i, [C.c_char_p]),
     "edmp_rccl_unique_id": (_i, [_vp]),

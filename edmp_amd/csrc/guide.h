@@ -51,7 +51,19 @@ struct Guide {
     float* cand_vol = nullptr;   // [cand_cap]
     double* cand_key = nullptr;  // [cand_cap]
     int cand_cap = 0;
+    // sphere signed-distance guide (sdf.hip, edmp_sdf_set): row-level like the arrays above; edmp_rows_set drops it
+    float* sdf_sph = nullptr;       // [sdf_ns][4] centre | radius in link-box frames, sorted by link
+    int sdf_ns = 0;                 // spheres (0: no table bound)
+    int sdf_link_off[EDMP_N_LINKS + 1] = {};
+    int32_t* sdf_rows = nullptr;    // [sdf_n] indices of the SDF rows
+    int sdf_n = 0;                  // SDF rows of the batch (0: the gradient paths launch what they always launched)
+    double* sdf_margin = nullptr;   // [B][T]
+    double* sdf_smooth = nullptr;   // [B]
 };
+
+// sdf.hip: overwrite graw / rowsq of the bound guide's SDF rows (no SDF rows: nothing is launched)
+int sdf_overlay(edmp_ctx* ctx, const double* joints, int ldw, int off, int L, int t, int do_clip);
+int guide_set_startgoal(edmp_ctx* ctx, const double* start, const double* goal);  // guide.hip
 
 // the per-scene entry points (cost, gradient, best trajectory, success, shapes) on a bound scene batch: refused, never answered
 // with scene 0's data

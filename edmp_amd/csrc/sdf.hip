@@ -1,0 +1,421 @@
+// sdf.hip — the sphere signed-distance guide for gfx950: a third guidance method beside the AABB-overlap volumes of guide.hip.
+//
+// No live counterpart in the reference: its sphere / SDF collision loss exists only in the vendored mpinets (mpinets/loss.py:47-94,
+// mpinets/geometry.py:238-288, 456-507) and its smoothness_cost (lib/guide.py:670-677) is never called.  The cost of a row at step t,
+// over the padded waypoints w = 0..L+1 (start, the L interior waypoints, goal), all arithmetic in f32:
+//   c(w, s)   = T_frame(link_s)(q_w) * static_frame[link_s] * centre_s       the chain, frames and link -> frame map of guide_kernel
+//   sdf_o(p)  = ||max(e, 0)|| + min(max_k e_k, 0)                            cuboid: e = |R_o^T (p - c_o)| - h_o
+//                                                                            cylinder: the same in 2-D on (rho - r, |z| - height / 2)
+//   d(w, s)   = min_o sdf_o(c(w, s)) - radius_s
+//   collision = sum_{w=1..L} sum_s max(0, m - d(w, s))                       m = sdf_margin[r][t - 1] for t >= 1, 0 at t = 0
+//   smooth    = smoothness[r] * sum_{w=0..L} ||q_{w+1} - q_w||^2             the FULL padded chain (lib/guide.py:670-677 drops both ends)
+//   cost      = collision + smooth;  the gradient is taken with respect to the L interior waypoints.
+// The obstacles are the TRUE primitives of the success check (Guide::obb / Guide::kind): oriented boxes, and cylinders of radius
+// dims[0] and half height dims[2] / 2 about their local z axis (success.hip, lib/environment.py:249-268).
+//
+// Sub-gradient conventions (the kernel holds to them; a checker has to keep its inputs away from these boundaries):
+//   * the first obstacle index wins a min_o tie (strict < in obstacle order);
+//   * the hinge is active iff m - d > 0;
+//   * inside a box the first axis of the maximal e_k carries the gradient;
+//   * ||.|| at exactly 0 (and rho = 0 on a cylinder axis, |p_k| at p_k = 0) contributes a zero gradient - torch gives NaN at the norm.
+//
+// Layout (that of guide_kernel<GM_GRAD, ., 4>): one 256-thread workgroup per row, lane = padded waypoint, the four waves take the
+// link groups {0,1,2}, {3,4}, {5,6}, {hand, finger}; per-joint partials meet in LDS and are added as ((w0 + w1) + w2) + w3.  The row's
+// obstacles are staged once per workgroup as f32 [16] = rotation (row-major, columns = axes) | centre | half extents | kind, the sphere
+// table (sorted by link on the host, table order kept inside a link) as f32 [4] = centre | radius.  No atomics: every sum has one order.
+#include "common.h"
+#include "guide.h"
+
+#include <algorithm>
+#include <cmath>
+
+namespace edmp {
+
+struct SdfArgs {
+    const double* joints;  // element (r, j, wi) at joints[(r*7 + j)*ldw + off + wi], wi in 0..L-1
+    int ldw, off;
+    int L, t;
+    int do_clip;          // clip to the joint limits in f64 before the f32 cast (diffusion.py:328), as guide_kernel
+    const int32_t* rows;  // gradient: the SDF rows of the batch, one workgroup each
+    const double* margin;  // [B][T]; read at t >= 1 only
+    int T;
+    const double* smooth;  // [B], or nullptr = 0 (edmp_sdf_rows_dev on rows that are not the bound ones)
+    const double* obb;     // [no][16] f64
+    const int32_t* kind;   // [no]
+    int no;
+    const float* spheres;  // [ns][4] sorted by link
+    int ns;
+    int link_off[EDMP_N_LINKS + 1];  // spheres of link l: [link_off[l], link_off[l+1])
+    const float* startgoal;          // [14] f32
+    float* graw;                     // gradient: [B][7][L]
+    double* rowsq;                   // gradient: per-row sum g^2
+    double* cost;                    // rows: [n]
+    double* clearance;               // rows: [n]
+};
+
+// signed distance of the world point (cx, cy, cz) to the staged obstacle ob[16]; e[3] and the local point come back for the gradient
+__device__ __forceinline__ float sdf_one(const float* ob, float cx, float cy, float cz, float p[3], float e[3]) {
+    const float dx = cx - ob[9], dy = cy - ob[10], dz = cz - ob[11];
+    p[0] = fmaf(ob[6], dz, fmaf(ob[3], dy, ob[0] * dx));
+    p[1] = fmaf(ob[7], dz, fmaf(ob[4], dy, ob[1] * dx));
+    p[2] = fmaf(ob[8], dz, fmaf(ob[5], dy, ob[2] * dx));
+    if (ob[15] != 0.f) {  // cylinder (obstacle-uniform, so wave-uniform)
+        const float rho = sqrtf(fmaf(p[1], p[1], p[0] * p[0]));
+        e[0] = rho - ob[12];
+        e[1] = fabsf(p[2]) - ob[14];
+        e[2] = -3.0e38f;  // no third axis: never positive, never the maximum
+    } else {
+        e[0] = fabsf(p[0]) - ob[12];
+        e[1] = fabsf(p[1]) - ob[13];
+        e[2] = fabsf(p[2]) - ob[14];
+    }
+    const float m0 = fmaxf(e[0], 0.f), m1 = fmaxf(e[1], 0.f), m2 = fmaxf(e[2], 0.f);
+    const float outside = sqrtf(fmaf(m2, m2, fmaf(m1, m1, m0 * m0)));
+    const float inside = fminf(fmaxf(e[0], fmaxf(e[1], e[2])), 0.f);
+    return outside + inside;
+}
+
+__device__ __forceinline__ float sgn(float v) { return v > 0.f ? 1.f : (v < 0.f ? -1.f : 0.f); }
+
+// world gradient of sdf_one at the same point (the conventions of the header)
+__device__ __forceinline__ void sdf_grad(const float* ob, float cx, float cy, float cz, float n[3]) {
+    float p[3], e[3];
+    (void)sdf_one(ob, cx, cy, cz, p, e);
+    const float m0 = fmaxf(e[0], 0.f), m1 = fmaxf(e[1], 0.f), m2 = fmaxf(e[2], 0.f);
+    const float outside = sqrtf(fmaf(m2, m2, fmaf(m1, m1, m0 * m0)));
+    float a0, a1, a2;  // d sdf / d e_k
+    if (outside > 0.f) {
+        a0 = m0 / outside;
+        a1 = m1 / outside;
+        a2 = m2 / outside;
+    } else {
+        const bool k0 = e[0] >= e[1] && e[0] >= e[2];
+        const bool k1 = !k0 && e[1] >= e[2];
+        a0 = k0 ? 1.f : 0.f;
+        a1 = k1 ? 1.f : 0.f;
+        a2 = (!k0 && !k1) ? 1.f : 0.f;
+    }
+    float gl[3];
+    if (ob[15] != 0.f) {
+        const float rho = sqrtf(fmaf(p[1], p[1], p[0] * p[0]));
+        const float ux = rho > 0.f ? p[0] / rho : 0.f, uy = rho > 0.f ? p[1] / rho : 0.f;
+        gl[0] = a0 * ux;
+        gl[1] = a0 * uy;
+        gl[2] = a1 * sgn(p[2]);
+    } else {
+        gl[0] = a0 * sgn(p[0]);
+        gl[1] = a1 * sgn(p[1]);
+        gl[2] = a2 * sgn(p[2]);
+    }
+#pragma unroll
+    for (int i = 0; i < 3; ++i) n[i] = fmaf(ob[i * 3 + 2], gl[2], fmaf(ob[i * 3 + 1], gl[1], ob[i * 3] * gl[0]));
+}
+
+// ROWS = false: the raw gradient of row a.rows[blockIdx.x] -> graw / rowsq (the contract of guide_kernel<GM_GRAD>).
+// ROWS = true: cost and minimum clearance of row blockIdx.x.  Cost: per lane and wave the hinge terms in f64 in (link, sphere) order,
+// the four waves' partials as ((w0 + w1) + w2) + w3, plus the lane's smoothness term, then wave_sum over the lanes.
+template <bool ROWS>
+__device__ __forceinline__ void sdf_row(const SdfArgs& a, const RobotConst& rc) {
+    __shared__ float s_ob[EDMP_MAX_OBSTACLES * 16];
+    __shared__ float s_sph[EDMP_MAX_SPHERES * 4];
+    __shared__ float s_g[3][7][64];  // partials of waves 1..3 (ROWS: [w][0] clearance)
+    __shared__ double s_c[3][64];    // ROWS: cost partials of waves 1..3
+    const int lane = threadIdx.x & 63;
+    const int wv = __builtin_amdgcn_readfirstlane(threadIdx.x >> 6);
+    const int r = ROWS ? (int)blockIdx.x : a.rows[blockIdx.x];
+    const int L = a.L, no = a.no;
+    for (int i = threadIdx.x; i < no * 16; i += 256) {
+        const int ob = i >> 4, k = i & 15;
+        const bool cyl = a.kind[ob] == 1;
+        const double v = a.obb[i];
+        // a cylinder's (r, r, h) row is stored halved like a box: slot 12 becomes the radius
+        s_ob[i] = (k == 15) ? (cyl ? 1.f : 0.f) : ((k == 12 && cyl) ? (float)(2.0 * v) : (float)v);
+    }
+    for (int i = threadIdx.x; i < a.ns * 4; i += 256) s_sph[i] = a.spheres[i];
+    __syncthreads();
+
+    const float m = (a.t >= 1) ? (float)a.margin[(size_t)r * a.T + (a.t - 1)] : 0.f;
+    const float lam = a.smooth ? (float)a.smooth[r] : 0.f;
+    const int my_jmax = wv == 0 ? 2 : wv == 1 ? 4 : 6;
+
+    // this lane's joint vector: padded waypoint w = lane (0 start, 1..L interior, >= L+1 goal), loaded as guide_kernel loads it
+    const int w = lane;
+    float q[7];
+    {
+        const int wi = min(max(w - 1, 0), L - 1);
+        double xr[7];
+#pragma unroll
+        for (int j = 0; j < 7; ++j) xr[j] = a.joints[((size_t)r * 7 + j) * a.ldw + a.off + wi];
+#pragma unroll
+        for (int j = 0; j < 7; ++j) {
+            double xd = xr[j];
+            if (a.do_clip) {
+                xd = xd < rc.qlo[j] ? rc.qlo[j] : xd;
+                xd = xd > rc.qhi[j] ? rc.qhi[j] : xd;
+            }
+            const float vs = a.startgoal[j], vg = a.startgoal[7 + j];
+            q[j] = (w == 0) ? vs : ((w > L) ? vg : (float)xd);
+        }
+    }
+    const bool interior = (w >= 1) && (w <= L);
+
+    float R[3][3] = {{1, 0, 0}, {0, 1, 0}, {0, 0, 1}};
+    float o[3] = {0, 0, 0};
+    float zax[7][3], org[7][3];
+    float g[7] = {0, 0, 0, 0, 0, 0, 0};
+    double cacc = 0.0;
+    float dmin = INFINITY;
+
+#pragma unroll
+    for (int j = 0; j < 7; ++j) {
+        if (j > my_jmax) break;  // (wave-uniform)
+        {
+            const float sq = sinf(q[j]), cq = cosf(q[j]);
+            const float aa = rc.dh[j][0], dd = rc.dh[j][1], ca = rc.dh[j][2], sa = rc.dh[j][3];
+            const float D[3][4] = {{cq, -sq, 0.f, aa}, {sq * ca, cq * ca, -sa, -sa * dd}, {sq * sa, cq * sa, ca, ca * dd}};
+            float Rn[3][3], on[3];
+#pragma unroll
+            for (int i = 0; i < 3; ++i) {
+#pragma unroll
+                for (int c = 0; c < 3; ++c) Rn[i][c] = fmaf(R[i][2], D[2][c], fmaf(R[i][1], D[1][c], R[i][0] * D[0][c]));
+                on[i] = fmaf(R[i][2], D[2][3], fmaf(R[i][1], D[1][3], R[i][0] * D[0][3])) + o[i];
+            }
+#pragma unroll
+            for (int i = 0; i < 3; ++i) {
+#pragma unroll
+                for (int c = 0; c < 3; ++c) R[i][c] = Rn[i][c];
+                o[i] = on[i];
+                zax[j][i] = Rn[i][2];
+                org[j][i] = on[i];
+            }
+        }
+#pragma unroll
+        for (int ll = 0; ll < 3; ++ll) {
+            if (ll > 0 && j != 6) continue;
+            const int l = (ll == 0) ? j : 6 + ll;
+            if ((l < 3 ? 0 : l < 5 ? 1 : l < 7 ? 2 : 3) != wv) continue;  // another wave's link (wave-uniform)
+            float LR[3][3], Lo[3];
+#pragma unroll
+            for (int i = 0; i < 3; ++i) {
+#pragma unroll
+                for (int c = 0; c < 3; ++c) LR[i][c] = fmaf(R[i][2], rc.sf[l][8 + c], fmaf(R[i][1], rc.sf[l][4 + c], R[i][0] * rc.sf[l][c]));
+                Lo[i] = fmaf(R[i][2], rc.sf[l][11], fmaf(R[i][1], rc.sf[l][7], R[i][0] * rc.sf[l][3])) + o[i];
+            }
+            const int s1 = a.link_off[l + 1];
+            for (int s = a.link_off[l]; s < s1; ++s) {
+                const float* sp = s_sph + s * 4;
+                const float cx = fmaf(LR[0][2], sp[2], fmaf(LR[0][1], sp[1], LR[0][0] * sp[0])) + Lo[0];
+                const float cy = fmaf(LR[1][2], sp[2], fmaf(LR[1][1], sp[1], LR[1][0] * sp[0])) + Lo[1];
+                const float cz = fmaf(LR[2][2], sp[2], fmaf(LR[2][1], sp[1], LR[2][0] * sp[0])) + Lo[2];
+                float best = INFINITY;
+                int bi = 0;
+                for (int ob = 0; ob < no; ++ob) {
+                    float p[3], e[3];
+                    const float d = sdf_one(s_ob + ob * 16, cx, cy, cz, p, e);
+                    if (d < best) {
+                        best = d;
+                        bi = ob;
+                    }
+                }
+                const float clr = best - sp[3];
+                const float h = m - clr;
+                if (ROWS) {
+                    dmin = fminf(dmin, clr);
+                    if (interior && h > 0.f) cacc += (double)h;
+                } else if (interior && h > 0.f) {
+                    float n[3];
+                    sdf_grad(s_ob + bi * 16, cx, cy, cz, n);
+                    // d c / d q_i = z_i x (c - o_i), i <= j; the hinge turns the sign
+#pragma unroll
+                    for (int i = 0; i <= j; ++i) {
+                        const float rx = cx - org[i][0], ry = cy - org[i][1], rz = cz - org[i][2];
+                        const float kx = zax[i][1] * rz - zax[i][2] * ry;
+                        const float ky = zax[i][2] * rx - zax[i][0] * rz;
+                        const float kz = zax[i][0] * ry - zax[i][1] * rx;
+                        g[i] -= fmaf(n[2], kz, fmaf(n[1], ky, n[0] * kx));
+                    }
+                }
+            }
+        }
+    }
+
+    if (wv > 0) {
+        if (ROWS) {
+            s_g[wv - 1][0][lane] = dmin;
+            s_c[wv - 1][lane] = cacc;
+        } else {
+#pragma unroll
+            for (int i = 0; i < 7; ++i) s_g[wv - 1][i][lane] = g[i];
+        }
+    }
+    __syncthreads();
+    if (wv > 0) return;
+    // wave 0 holds every joint of its lane's waypoint: the neighbours' joints come by two shuffles
+    float qp[7], qn[7];
+#pragma unroll
+    for (int j = 0; j < 7; ++j) {
+        qp[j] = __shfl_up(q[j], 1, 64);
+        qn[j] = __shfl_down(q[j], 1, 64);
+    }
+    if (ROWS) {
+        cacc = ((cacc + s_c[0][lane]) + s_c[1][lane]) + s_c[2][lane];
+        dmin = fminf(fminf(fminf(dmin, s_g[0][0][lane]), s_g[1][0][lane]), s_g[2][0][lane]);
+        float ss = 0.f;
+#pragma unroll
+        for (int j = 0; j < 7; ++j) {
+            const float df = qn[j] - q[j];
+            ss = fmaf(df, df, ss);
+        }
+        if (w <= L) cacc += (double)(lam * ss);  // segment (w, w+1)
+        if (w > L + 1) dmin = INFINITY;          // lanes behind the goal repeat it
+        const double tot = wave_sum(cacc);
+#pragma unroll
+        for (int s = 32; s > 0; s >>= 1) dmin = fminf(dmin, __shfl_xor(dmin, s, 64));
+        if (lane == 0) {
+            a.cost[r] = tot;
+            a.clearance[r] = (double)dmin;
+        }
+    } else {
+        const float l2 = 2.f * lam;
+        float sq = 0.f;
+#pragma unroll
+        for (int i = 0; i < 7; ++i) {
+            float gi = ((g[i] + s_g[0][i][lane]) + s_g[1][i][lane]) + s_g[2][i][lane];
+            gi = fmaf(l2, fmaf(2.f, q[i], -qp[i]) - qn[i], gi);  // 2 lambda (2 q_w - q_{w-1} - q_{w+1})
+            gi = interior ? gi : 0.f;
+            if (interior) a.graw[((size_t)r * 7 + i) * L + (w - 1)] = gi;
+            sq = fmaf(gi, gi, sq);
+        }
+        const double tot = wave_sum((double)sq);
+        if (lane == 0) a.rowsq[r] = tot;
+    }
+}
+
+__global__ __launch_bounds__(256, 3) void sdf_guide_kernel(SdfArgs a, RobotConst rc) { sdf_row<false>(a, rc); }
+__global__ __launch_bounds__(256, 4) void sdf_rows_kernel(SdfArgs a, RobotConst rc) { sdf_row<true>(a, rc); }
+
+static void fill_args(const Guide* g, SdfArgs& a, const double* joints, int ldw, int off, int L, int t, int do_clip) {
+    a.joints = joints;
+    a.ldw = ldw;
+    a.off = off;
+    a.L = L;
+    a.t = t;
+    a.do_clip = do_clip;
+    a.rows = g->sdf_rows;
+    a.margin = g->sdf_margin;
+    a.T = g->rows_T;
+    a.smooth = g->sdf_smooth;
+    a.obb = g->obb;
+    a.kind = g->kind;
+    a.no = g->no;
+    a.spheres = g->sdf_sph;
+    a.ns = g->sdf_ns;
+    for (int l = 0; l <= EDMP_N_LINKS; ++l) a.link_off[l] = g->sdf_link_off[l];
+    a.startgoal = g->startgoal;
+    a.graw = g->graw;
+    a.rowsq = g->rowsq;
+    a.cost = nullptr;
+    a.clearance = nullptr;
+}
+
+// guide.hip's gradient paths, after guide_kernel<GM_GRAD> and before the rowsq reduction: the SDF rows' graw / rowsq are overwritten
+int sdf_overlay(edmp_ctx* ctx, const double* joints, int ldw, int off, int L, int t, int do_clip) {
+    Guide* g = ctx->guide;
+    if (!g || g->sdf_n == 0) return EDMP_OK;
+    SdfArgs a;
+    fill_args(g, a, joints, ldw, off, L, t, do_clip);
+    hipLaunchKernelGGL(sdf_guide_kernel, dim3(g->sdf_n), dim3(256), 0, ctx->stream, a, g->rc);
+    EDMP_HIP_CHECK(hipGetLastError());
+    return EDMP_OK;
+}
+
+}  // namespace edmp
+
+using namespace edmp;
+
+extern "C" int edmp_sdf_set(edmp_ctx* ctx, const float* spheres, int n_spheres, const int32_t* sdf_row, const double* margin, const double* smoothness,
+                            int B, int T) {
+    EDMP_REQUIRE(ctx && ctx->guide && ctx->guide->obb && ctx->guide->row_class, "edmp_sdf_set: call edmp_scene_set and edmp_rows_set first");
+    Guide* g = ctx->guide;
+    if (g->is_batch || g->S > 1) {
+        set_error("edmp_sdf_set: the bound guide is a scene batch of %d scenes (edmp_scene_batch_set); SDF rows need one guide per scene", g->S);
+        return EDMP_ERR_STATE;
+    }
+    EDMP_REQUIRE(spheres && sdf_row && margin && smoothness, "edmp_sdf_set: null argument");
+    EDMP_REQUIRE(n_spheres >= 1 && n_spheres <= EDMP_MAX_SPHERES, "edmp_sdf_set: %d spheres outside 1..%d", n_spheres, EDMP_MAX_SPHERES);
+    EDMP_REQUIRE(B == g->B && T == g->rows_T, "edmp_sdf_set: %d rows x %d steps given, edmp_rows_set holds %d x %d", B, T, g->B, g->rows_T);
+    for (int s = 0; s < n_spheres; ++s) {
+        const float* sp = spheres + s * 5;
+        EDMP_REQUIRE(std::isfinite(sp[0]) && std::isfinite(sp[1]) && std::isfinite(sp[2]) && std::isfinite(sp[3]) && std::isfinite(sp[4]),
+                     "edmp_sdf_set: sphere %d holds a non-finite value", s);
+        EDMP_REQUIRE(sp[0] == std::floor(sp[0]) && sp[0] >= 0.f && sp[0] < (float)EDMP_N_LINKS, "edmp_sdf_set: sphere %d: link %g outside 0..%d", s,
+                     (double)sp[0], EDMP_N_LINKS - 1);
+        EDMP_REQUIRE(sp[4] > 0.f, "edmp_sdf_set: sphere %d: radius %g must be > 0", s, (double)sp[4]);
+    }
+    std::vector<int32_t> rows;
+    for (int b = 0; b < B; ++b) {
+        EDMP_REQUIRE(sdf_row[b] == 0 || sdf_row[b] == 1, "edmp_sdf_set: row %d: sdf_row must be 0 or 1", b);
+        EDMP_REQUIRE(std::isfinite(smoothness[b]) && smoothness[b] >= 0.0, "edmp_sdf_set: row %d: smoothness %g must be finite and >= 0", b, smoothness[b]);
+        if (sdf_row[b]) rows.push_back(b);
+    }
+    for (size_t i = 0; i < (size_t)B * T; ++i)
+        EDMP_REQUIRE(std::isfinite(margin[i]) && margin[i] >= 0.0, "edmp_sdf_set: row %d, step %d: margin %g must be finite and >= 0", (int)(i / T),
+                     (int)(i % T), margin[i]);
+    // the table sorted by link, table order kept inside a link: the kernel's wave of a link group walks one contiguous range
+    std::vector<float> sph((size_t)n_spheres * 4);
+    int k = 0;
+    for (int l = 0; l < EDMP_N_LINKS; ++l) {
+        g->sdf_link_off[l] = k;
+        for (int s = 0; s < n_spheres; ++s)
+            if ((int)spheres[s * 5] == l) {
+                for (int c = 0; c < 4; ++c) sph[(size_t)k * 4 + c] = spheres[s * 5 + 1 + c];
+                ++k;
+            }
+    }
+    g->sdf_link_off[EDMP_N_LINKS] = k;
+    ctx->epoch++;  // a captured whole-run graph holds the launch sequence of the old table
+    EDMP_HIP_CHECK(hipSetDevice(ctx->device));
+    EDMP_HIP_CHECK(hipStreamSynchronize(ctx->stream));  // nothing enqueued still reads the arrays that are replaced
+    g->sdf_n = g->sdf_ns = 0;
+    for (void** p : {(void**)&g->sdf_sph, (void**)&g->sdf_rows, (void**)&g->sdf_margin, (void**)&g->sdf_smooth}) {
+        ctx_release(ctx, *p);
+        *p = nullptr;
+    }
+    if (int rc = ctx_alloc(ctx, (void**)&g->sdf_sph, sph.size() * sizeof(float))) return rc;
+    if (int rc = ctx_alloc(ctx, (void**)&g->sdf_rows, std::max<size_t>(rows.size(), 1) * sizeof(int32_t))) return rc;
+    if (int rc = ctx_alloc(ctx, (void**)&g->sdf_margin, (size_t)B * T * sizeof(double))) return rc;
+    if (int rc = ctx_alloc(ctx, (void**)&g->sdf_smooth, (size_t)B * sizeof(double))) return rc;
+    hipError_t e = hipMemcpyAsync(g->sdf_sph, sph.data(), sph.size() * sizeof(float), hipMemcpyHostToDevice, ctx->stream);
+    if (e == hipSuccess && !rows.empty()) e = hipMemcpyAsync(g->sdf_rows, rows.data(), rows.size() * sizeof(int32_t), hipMemcpyHostToDevice, ctx->stream);
+    if (e == hipSuccess) e = hipMemcpyAsync(g->sdf_margin, margin, (size_t)B * T * sizeof(double), hipMemcpyHostToDevice, ctx->stream);
+    if (e == hipSuccess) e = hipMemcpyAsync(g->sdf_smooth, smoothness, (size_t)B * sizeof(double), hipMemcpyHostToDevice, ctx->stream);
+    const hipError_t e2 = hipStreamSynchronize(ctx->stream);  // the host vectors and the caller's arrays may go away after the call
+    EDMP_HIP_CHECK(e);
+    EDMP_HIP_CHECK(e2);
+    g->sdf_ns = n_spheres;
+    g->sdf_n = (int)rows.size();
+    return EDMP_OK;
+}
+
+extern "C" int edmp_sdf_rows_dev(edmp_ctx* ctx, const double* joints_dev, int n, int L, int t, const double* start, const double* goal,
+                                 double* cost_dev, double* clearance_dev) {
+    EDMP_REQUIRE(ctx && ctx->guide && ctx->guide->obb, "edmp_sdf_rows_dev: scene not set");
+    Guide* g = ctx->guide;
+    EDMP_REFUSE_SCENE_BATCH(g, "edmp_sdf_rows_dev");
+    EDMP_REQUIRE(g->sdf_ns > 0, "edmp_sdf_rows_dev: call edmp_sdf_set first (the sphere table)");
+    EDMP_REQUIRE(joints_dev && start && goal && cost_dev && clearance_dev, "edmp_sdf_rows_dev: null pointer");
+    EDMP_REQUIRE(n >= 1 && L >= 1 && L + 2 <= 64, "edmp_sdf_rows_dev: need n >= 1 and 1 <= L <= 62 waypoints per row (got %d, %d)", n, L);
+    EDMP_REQUIRE(t >= 0 && t <= g->rows_T, "edmp_sdf_rows_dev: t=%d outside 0..%d", t, g->rows_T);
+    EDMP_REQUIRE(t == 0 || n == g->B, "edmp_sdf_rows_dev: t >= 1 reads the rows' margin schedules: %d rows given, %d bound", n, g->B);
+    EDMP_HIP_CHECK(hipSetDevice(ctx->device));
+    sampler_end_run(ctx);  // (the guide's start / goal pair is replaced)
+    if (int rc = guide_set_startgoal(ctx, start, goal)) return rc;
+    SdfArgs a;
+    fill_args(g, a, joints_dev, L, 0, L, t, 0);
+    if (n != g->B) a.smooth = nullptr;  // rows that are not the bound ones carry no smoothness weight
+    a.cost = cost_dev;
+    a.clearance = clearance_dev;
+    hipLaunchKernelGGL(sdf_rows_kernel, dim3(n), dim3(256), 0, ctx->stream, a, g->rc);
+    EDMP_HIP_CHECK(hipGetLastError());
+    return EDMP_OK;
+}

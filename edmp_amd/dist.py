@@ -28,6 +28,9 @@ def shard_guide_cfgs(cfgs: dict, lo: int, hi: int) -> dict:
     out = dict(cfgs)
     for k in ("clearance", "expansion", "guidance_method", "grad_norm", "guidance_schedule", "volume_trust_region"):
         out[k] = np.ascontiguousarray(cfgs[k][lo:hi])
+    for k in ("sdf_rows", "sdf_margin", "smoothness"):  # present only when a guide uses the SDF method (guide_cfg.build_guide_cfgs)
+        if k in cfgs:
+            out[k] = np.ascontiguousarray(cfgs[k][lo:hi])
     out["total_batch_size"] = hi - lo
     return out
 

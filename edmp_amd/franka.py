@@ -175,3 +175,27 @@ def link_half_extents(link_mesh_extents=None) -> np.ndarray:
     ext = ext.copy()
     ext[-1, 1] *= 4
     return ext.astype(np.float32) / np.float32(2)
+
+
+def spheres_from_boxes(link_half_extents=None, max_per_link: int = 8) -> np.ndarray:
+    """Default sphere model of the SDF guide (csrc/sdf.hip): (n, 5) float32 rows [link 0..8, centre xyz in the link-box frame, radius]
+    covering the nine link boxes.  Along each box's longest axis (the first one on equal extents) sit
+    k = clamp(ceil(h_long / max(h_mid, 1e-3)), 1, max_per_link) spheres with centres (2i + 1 - k) / k * h_long, i = 0..k-1, and radius
+    sqrt(h_mid^2 + h_short^2 + (h_long / k)^2): each sphere circumscribes its slice of the box, so their union covers it.  robofin's
+    measured sphere list is not part of this package; pass such a table as ``spheres=`` instead."""
+    he = np.asarray(link_half_extents if link_half_extents is not None else globals()["link_half_extents"](), dtype=np.float64)
+    if he.shape != (N_LINKS, 3) or not np.all(np.isfinite(he)) or np.any(he <= 0):
+        raise ValueError(f"link_half_extents must be (9, 3), finite and > 0, got shape {he.shape}")
+    if not 1 <= int(max_per_link):
+        raise ValueError("max_per_link must be >= 1")
+    rows = []
+    for l in range(N_LINKS):
+        order = np.argsort(-he[l], kind="stable")  # long, mid, short
+        h_long, h_mid, h_short = he[l][order]
+        k = int(min(max(math.ceil(h_long / max(h_mid, 1e-3)), 1), int(max_per_link)))
+        rad = math.sqrt(h_mid ** 2 + h_short ** 2 + (h_long / k) ** 2)
+        for i in range(k):
+            c = [0.0, 0.0, 0.0]
+            c[int(order[0])] = (2 * i + 1 - k) / k * h_long
+            rows.append([float(l), *c, rad])
+    return np.asarray(rows, dtype=np.float32)

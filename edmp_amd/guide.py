@@ -96,6 +96,39 @@ def goal_filter_device_inputs(n_scenes, starts, goals, counts):
     return st, np.ascontiguousarray(cn.astype(np.int32))
 
 
+def sdf_tables(guide_cfgs, batch_size, T, link_half_extents, spheres=None):
+    """Host tables of the sphere signed-distance guide (edmp_sdf_set), checked before anything touches the device: the sphere table
+    (n, 5) f32 [link 0..8, centre xyz in the link-box frame, radius] - ``spheres`` or franka.spheres_from_boxes of the link boxes - and
+    the row arrays of ``guide_cfgs`` (``sdf_rows`` (B,), ``sdf_margin`` (B, T), ``smoothness`` (B,); a dict without them gives no SDF
+    rows, margin 0 and smoothness 0).  Returns dict(spheres, rows int32, margin f64, smooth f64)."""
+    B, T = int(batch_size), int(T)
+    sph = franka.spheres_from_boxes(link_half_extents) if spheres is None else np.asarray(spheres, dtype=np.float32)
+    if sph.ndim != 2 or sph.shape[1] != 5:
+        raise ValueError(f"spheres must be (n, 5) = [link, x, y, z, radius], got {sph.shape}")
+    if not 1 <= sph.shape[0] <= _capi.MAX_SPHERES:
+        raise ValueError(f"{sph.shape[0]} spheres outside 1..{_capi.MAX_SPHERES}")
+    if not np.isfinite(sph).all():
+        raise ValueError("spheres holds non-finite values")
+    if np.any(sph[:, 0] != np.floor(sph[:, 0])) or np.any(sph[:, 0] < 0) or np.any(sph[:, 0] >= franka.N_LINKS):
+        raise ValueError(f"spheres: link index outside 0..{franka.N_LINKS - 1}")
+    if np.any(sph[:, 4] <= 0):
+        raise ValueError("spheres: every radius must be > 0")
+    rows = np.asarray(guide_cfgs["sdf_rows"] if "sdf_rows" in guide_cfgs else np.zeros(B))
+    margin = np.asarray(guide_cfgs["sdf_margin"] if "sdf_margin" in guide_cfgs else np.zeros((B, T)), dtype=np.float64)
+    smooth = np.asarray(guide_cfgs["smoothness"] if "smoothness" in guide_cfgs else np.zeros(B), dtype=np.float64)
+    if rows.shape != (B,) or margin.shape != (B, T) or smooth.shape != (B,):
+        raise ValueError(f"sdf_rows / sdf_margin / smoothness must be ({B},), ({B}, {T}), ({B},), got {rows.shape}, {margin.shape}, {smooth.shape}")
+    if not np.all((rows == 0) | (rows == 1)):
+        raise ValueError("sdf_rows: one entry per row, 0 or 1")
+    if not (np.isfinite(margin).all() and np.all(margin >= 0) and np.isfinite(smooth).all() and np.all(smooth >= 0)):
+        raise ValueError("sdf_margin and smoothness must be finite and >= 0")
+    return dict(spheres=np.ascontiguousarray(sph), rows=np.ascontiguousarray(rows.astype(np.int32)), margin=np.ascontiguousarray(margin),
+                smooth=np.ascontiguousarray(smooth))
+
+
+spheres_from_boxes = franka.spheres_from_boxes
+
+
 class IntersectionVolumeGuide:
     """Same constructor / method signatures as the reference:
 
@@ -112,9 +145,17 @@ class IntersectionVolumeGuide:
     ``bind`` (default True): upload the scene tables and row arrays at once, as the reference's constructor builds its tensors.
     bind=False builds the host tables only; the object binds at its first use.  A guide that only ever serves as one scene of a
     SceneBatch never touches the device on its own.
+
+    The sphere signed-distance guide (csrc/sdf.hip; no counterpart in the reference's live path): rows that ``guide_cfgs["sdf_rows"]``
+    marks (guide_cfg.build_guide_cfgs, ``guidance_method: 'sdf'``) take their gradient from the clearance of a sphere model of the arm
+    to the TRUE obstacles - oriented boxes, and cylinders where ``obstacle_kinds`` says so (without kinds everything is a cuboid) - plus
+    an optional smoothness pull.  ``spheres`` (n, 5) [link 0..8, centre in the link-box frame, radius] replaces the default
+    franka.spheres_from_boxes of the link boxes.  get_gradient and the samplers need nothing else: the SDF rows' gradient is overlaid
+    below them.  sdf_rows(...) reports cost and minimum clearance of every row.
     """
 
-    def __init__(self, obstacle_config, device, guide_cfgs, batch_size, *, link_mesh_extents=None, mesh_dir=None, obstacle_kinds=None, bind=True):
+    def __init__(self, obstacle_config, device, guide_cfgs, batch_size, *, link_mesh_extents=None, mesh_dir=None, obstacle_kinds=None, bind=True,
+                 spheres=None):
         self.ctx = get_context(device)
         self.device = self.ctx.device
         self.guide_cfgs = guide_cfgs
@@ -140,6 +181,8 @@ class IntersectionVolumeGuide:
         # (r, r, h) boxes, quirk Q9).  The reference's loader orders obstacle_config cuboids first, then cylinders
         # (datasets/load_test_dataset.py:141-149), so kinds = [0] * num_cuboids + [1] * num_cylinders there.
         self._kinds = None if obstacle_kinds is None else self._check_kinds(obstacle_kinds)
+        self._spheres = spheres
+        self._sdf = sdf_tables(guide_cfgs, self.batch_size, self.T, self._half, spheres) if ("sdf_rows" in guide_cfgs or spheres is not None) else None
         if bind:
             self._bind()
 
@@ -193,6 +236,17 @@ class IntersectionVolumeGuide:
             "edmp_rows_set",
         )
         self._rows_token = token
+        if self._sdf is not None:  # the SDF table belongs to the rows: edmp_rows_set dropped it
+            self._set_sdf()
+
+    @property
+    def has_sdf_rows(self):
+        return self._sdf is not None and bool(self._sdf["rows"].any())
+
+    def _set_sdf(self):
+        d, ctx = self._sdf, self.ctx
+        _capi.check(ctx.lib.edmp_sdf_set(ctx.h, _capi.as_pf(d["spheres"]), int(d["spheres"].shape[0]), _capi.as_pi32(d["rows"]), _capi.as_pd(d["margin"]),
+                                         _capi.as_pd(d["smooth"]), self.batch_size, int(d["margin"].shape[1])), "edmp_sdf_set")
 
     # ---- reference API -----------------------------------------------------------------------------------------
     def define_obstacles(self, obstacle_config=None, t=0, batch_size=None):
@@ -259,6 +313,34 @@ class IntersectionVolumeGuide:
         out = ctx.empty((B, 7, L), torch.float64)
         _capi.check(ctx.lib.edmp_guide_gradient_dev(ctx.h, ptr(ji), B, L, _capi.as_pd(s), _capi.as_pd(g), int(t), ptr(out), None), "edmp_guide_gradient_dev")
         return ctx.to_host(out)
+
+    def sdf_rows(self, trajectories, start, goal, t=0):
+        """Cost and minimum clearance of EVERY row under the sphere signed-distance model (edmp_sdf_rows_dev): trajectories (n, 7, L)
+        interior waypoints, f64 (not clipped) -> {"cost": (n,) f64, "clearance": (n,) f64 = min over the padded chain start, waypoints,
+        goal and over the spheres of (distance to the nearest obstacle - radius)}.  t = 0: margin 0, any n (the rows' smoothness weights
+        only when n is the guide's batch); t >= 1: the rows' own margin at step t, n = the guide's batch.  A guide built without SDF
+        rows and without ``spheres`` uses the default sphere model."""
+        lazy = self._sdf is None
+        if lazy:
+            self._sdf = sdf_tables(self.guide_cfgs, self.batch_size, self.T, self._half, self._spheres)
+        self._bind()
+        if lazy:  # (a resident slot was bound without its rows being set again)
+            self._set_sdf()
+        ctx = self.ctx
+        if isinstance(trajectories, torch.Tensor) and trajectories.is_cuda:
+            X = ctx.adopt(trajectories.to(torch.float64).contiguous())
+        else:
+            X = ctx.to_dev(np.asarray(trajectories, dtype=np.float64), torch.float64)
+        if X.dim() != 3 or X.shape[1] != 7:
+            raise ValueError(f"trajectories must be (n, 7, L), got {tuple(X.shape)}")
+        n, L = X.shape[0], X.shape[2]
+        s = np.ascontiguousarray(np.asarray(start, dtype=np.float64).reshape(7))
+        g = np.ascontiguousarray(np.asarray(goal, dtype=np.float64).reshape(7))
+        out = ctx.empty((2, n), torch.float64)
+        _capi.check(ctx.lib.edmp_sdf_rows_dev(ctx.h, ptr(X), n, L, int(t), _capi.as_pd(s), _capi.as_pd(g), C.c_void_p(out[0].data_ptr()),
+                                              C.c_void_p(out[1].data_ptr())), "edmp_sdf_rows_dev")
+        h = ctx.to_host(out)
+        return {"cost": h[0].copy(), "clearance": h[1].copy()}
 
     def row_swept_volumes(self, start, goal, trajectories):
         """(B,) f32 t=0 swept volume per row and the argmin (first on ties)."""
@@ -414,6 +496,8 @@ class SceneBatch:
         for k, g in enumerate(guides):
             if not isinstance(g, IntersectionVolumeGuide):
                 raise ValueError(f"scene {k} is not an IntersectionVolumeGuide")
+            if g.has_sdf_rows:
+                raise ValueError(f"scene {k} has SDF rows (guidance_method 'sdf'): a scene batch does not carry them, plan that scene with its own guide")
             if g.ctx is not g0.ctx:
                 raise ValueError(f"scene {k} lives on another context than scene 0")
             if g.batch_size != g0.batch_size or g.T != g0.T:

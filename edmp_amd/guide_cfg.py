@@ -47,17 +47,24 @@ GUIDE_CATALOG = {
     21: _g((0.05, 0.05), *_E_18, "sv", True, "constant", 0.1),
 }
 
+# Guides beyond the reference's catalogue, under numbers it does not use.  101: the sphere signed-distance guide (csrc/sdf.hip) with a
+# margin that shrinks towards t = 0 and a light smoothness pull; `sdf` holds the optional keys of `hyperparameters.sdf`.
+EXTRA_GUIDES = {
+    101: dict(_g((0.05, 0.05), *_E_NONE, "sdf", False, "constant", 0.05), sdf=dict(margin=(0.02, 0.08), smoothness=0.01)),
+}
+METHODS = ("iv", "sv", "sdf")
+
 VOLUME_TRUST_REGION = 0.0008  # every shipped guide; the driver hard-codes the same value (infer_serial.py:125)
 
 
 def catalog_guide_dict(n: int) -> dict:
     """The dict a reference-schema guide<N>.yaml parses to."""
-    g = GUIDE_CATALOG[n]
+    g = GUIDE_CATALOG[n] if n in GUIDE_CATALOG else EXTRA_GUIDES[n]
     oe = {}
     for k, (isr, val) in zip("123", g["expansion"]):
         oe["isr" + k] = list(isr)
         oe["val" + k] = [float(val[0]), float(val[1])]
-    return {
+    d = {
         "index": n,
         "hyperparameters": {
             "obstacle_clearance": {"range": [float(g["clearance"][0]), float(g["clearance"][1])]},
@@ -68,6 +75,9 @@ def catalog_guide_dict(n: int) -> dict:
             "volume_trust_region": VOLUME_TRUST_REGION,
         },
     }
+    if "sdf" in g:
+        d["hyperparameters"]["sdf"] = {"margin": [float(v) for v in g["sdf"]["margin"]], "smoothness": float(g["sdf"]["smoothness"])}
+    return d
 
 
 def write_guide_yamls(guide_path: str, guides=None) -> None:
@@ -90,7 +100,7 @@ def load_guide_dict(n: int, guide_path: str | None = None) -> dict:
         p = os.path.join(guide_path, "cfgs", f"guide{n}.yaml")
         if os.path.exists(p):
             return load_yaml(p)
-    if n not in GUIDE_CATALOG:
+    if n not in GUIDE_CATALOG and n not in EXTRA_GUIDES:
         raise FileNotFoundError(f"guide{n}.yaml not found under {guide_path!r} and not in the built-in catalogue")
     return catalog_guide_dict(n)
 
@@ -100,6 +110,12 @@ def build_guide_cfgs(guide_dicts, batch_size_per_guide, T: int, rows_per_guide=N
 
     ``rows_per_guide`` (optional list) lets guide i own an arbitrary number of contiguous rows (needed for
     "B = 1024 with 6 guides"); default is the reference's ``batch_size_per_guide`` for every guide.
+
+    ``guidance_method`` is 'iv', 'sv' or 'sdf'; anything else raises ValueError.  'sdf' (the sphere signed-distance guide, csrc/sdf.hip;
+    not in the reference's schema) keeps ``guidance_method`` 0 on its rows and adds three arrays - only when some guide uses it, so the
+    dict of the reference's guides is key for key what it always was: ``sdf_rows`` (B,) 0/1, ``sdf_margin`` (B, T) = linspace of
+    ``hyperparameters.sdf.margin`` [m0, m1] (default: the guide's ``obstacle_clearance.range``) and ``smoothness`` (B,) =
+    ``hyperparameters.sdf.smoothness`` (default 0).
     """
     G = len(guide_dicts)
     counts = [int(batch_size_per_guide)] * G if rows_per_guide is None else [int(c) for c in rows_per_guide]
@@ -114,6 +130,11 @@ def build_guide_cfgs(guide_dicts, batch_size_per_guide, T: int, rows_per_guide=N
         "guidance_schedule": np.zeros((B, T)),
         "volume_trust_region": np.zeros((B,)),
     }
+    for g in guide_dicts:
+        if g["hyperparameters"]["guidance_method"] not in METHODS:
+            raise ValueError(f"guide {g.get('index', '?')}: guidance_method {g['hyperparameters']['guidance_method']!r} is none of {METHODS}")
+    if any(g["hyperparameters"]["guidance_method"] == "sdf" for g in guide_dicts):
+        cfgs.update(sdf_rows=np.zeros((B,)), sdf_margin=np.zeros((B, T)), smoothness=np.zeros((B,)))
     r0 = 0
     for g, cnt in zip(guide_dicts, counts):
         rows = slice(r0, r0 + cnt)
@@ -127,6 +148,15 @@ def build_guide_cfgs(guide_dicts, batch_size_per_guide, T: int, rows_per_guide=N
             v0, v1 = oe["val" + k]
             cfgs["expansion"][rows, lo:hi] = np.linspace(v0, v1, num=abs(hi - lo))
         cfgs["guidance_method"][rows] = 1 if h["guidance_method"] == "sv" else 0
+        if h["guidance_method"] == "sdf":
+            sd = h.get("sdf") or {}
+            m0, m1 = sd.get("margin", rng)
+            lam = float(sd.get("smoothness", 0.0))
+            if not (np.isfinite([m0, m1, lam]).all() and m0 >= 0 and m1 >= 0 and lam >= 0):
+                raise ValueError(f"guide {g.get('index', '?')}: sdf.margin and sdf.smoothness must be finite and >= 0")
+            cfgs["sdf_rows"][rows] = 1
+            cfgs["sdf_margin"][rows, :] = np.linspace(m0, m1, T)
+            cfgs["smoothness"][rows] = lam
         cfgs["grad_norm"][rows] = 1 if h["grad_norm"] else 0
         gs = h["guidance_schedule"]
         cfgs["guidance_schedule"][rows, :] = (1.4 + np.arange(T) / T) if gs["type"] == "varying" else gs["scale_val"]

@@ -33,6 +33,7 @@ extern "C" {
 #define EDMP_N_LINKS 9
 #define EDMP_MAX_OBSTACLES 64
 #define EDMP_MAX_SCENES 16
+#define EDMP_MAX_SPHERES 128
 
 typedef struct edmp_ctx edmp_ctx;
 
@@ -126,6 +127,31 @@ int edmp_row_swept_volumes_dev(edmp_ctx* ctx, const double* X_dev, int B, int N,
 /* torch.argmin over n f32 values on the device, as choose_best_trajectory uses it (lib/guide.py:650): first index of the
  * minimum; NaN counts as the smallest value (the first NaN wins).  The selection step of edmp_row_swept_volumes_dev. */
 int edmp_argmin_dev(edmp_ctx* ctx, const float* v_dev, int n, int* index_host);
+
+/* ---- sphere signed-distance guide (csrc/sdf.hip) --------------------------------------------------------------------- */
+/* A third guidance method beside iv / sv, with no live counterpart in the reference (its sphere / SDF loss sits only in the vendored
+ * mpinets/loss.py:47-94, mpinets/geometry.py:238-288, 456-507; its smoothness_cost, lib/guide.py:670-677, is never called).  An SDF row
+ * pushes a sphere model of the arm away from the TRUE obstacle primitives of the success check (oriented boxes; cylinders where
+ * edmp_scene_set_shapes says so) and, optionally, pulls consecutive waypoints together:
+ *   cost = sum_{w=1..L} sum_s max(0, m - d(w, s)) + smoothness * sum_{w=0..L} ||q_{w+1} - q_w||^2,
+ *   d(w, s) = min_o sdf_o(centre of sphere s at waypoint w) - radius_s,  m = margin[row][t - 1] for t >= 1 and 0 at t = 0,
+ * over the padded chain start, L interior waypoints, goal (the smoothness sum is the FULL chain; lib/guide.py:670-677 drops both end
+ * differences).  Arithmetic in f32; the formulas and the sub-gradient conventions are stated at the top of csrc/sdf.hip.
+ *
+ * edmp_sdf_set, after edmp_rows_set on a single-scene guide (a scene batch is refused with EDMP_ERR_STATE): spheres (n,5) f32 rows
+ * [link 0..8, centre xyz in the link-box frame, radius > 0], 1 <= n <= EDMP_MAX_SPHERES; sdf_row (B,) int32 0/1; margin (B,T) f64 and
+ * smoothness (B,) f64, finite and >= 0; B and T those of edmp_rows_set.  Rows with sdf_row = 1 keep method 0 in edmp_rows_set's table;
+ * in edmp_guide_gradient_dev, the teacher-forced steps and the device loops their raw gradient and sum g^2 are written by
+ * sdf_guide_kernel after the volume kernel, everything downstream (norm mixing, schedule, update) is unchanged.  With no such row
+ * nothing else is launched and every result is what it was.  The table belongs to the rows: a later edmp_rows_set drops it. */
+int edmp_sdf_set(edmp_ctx* ctx, const float* spheres, int n_spheres, const int32_t* sdf_row, const double* margin,
+                 const double* smoothness, int B, int T);
+/* cost (f64 sum of the f32 terms) and minimum clearance min_{w = 0..L+1, s} d(w, s) of EVERY row, SDF row or not: joints (n,7,L) f64 on
+ * the device (not clipped), start / goal (7,) f64 host, cost_dev / clearance_dev (n,) f64 on the device.  t = 0: any n, margin 0, and
+ * the smoothness weight of row r only when n is the bound row count (else 0); t >= 1: n must be the bound row count.  Ends a segmented
+ * run like edmp_guide_gradient_dev (the start / goal pair is replaced).  Does not synchronise. */
+int edmp_sdf_rows_dev(edmp_ctx* ctx, const double* joints_dev, int n, int L, int t, const double* start, const double* goal,
+                      double* cost_dev, double* clearance_dev);
 
 /* ---- plan success: the reference's simulator check, restated geometrically ------------------------------------ */
 /* The guide sees every obstacle as a box (cylinders enter as (r, r, h) boxes, datasets/load_test_dataset.py:136-139) but the

@@ -281,6 +281,7 @@ def run(cfg_path, dataset=None, max_scenes=None, verbose=True, scenes_in_flight=
                     rows_collision_free=chk["rows_collision_free"], rows_ok=chk["rows_ok"], rows=chk["rows"],
                     aabb_volume_zero=bool(ED.geometric_success(float(vols[idx]), trajectory)), first_collision_waypoint=int(chk["first"][idx]),
                     path_length=EV.path_lengths(trajectory), sparc=EV.smoothness(trajectory), planning_time_s=t_plan, scene_wall_s=time.time() - t0, trajectory=trajectory,
+                    **({"min_clearance": float(guide.sdf_rows(trajectory[None, :, 1:-1], start_joints, goal_joints)["clearance"][0])} if ensemble_report and guide.has_sdf_rows else {}),
                     **extras(vols, chk, met))
 
     t_success, t_strict, i, results, pending = 0, 0, 0, [], []
@@ -298,6 +299,8 @@ def run(cfg_path, dataset=None, max_scenes=None, verbose=True, scenes_in_flight=
                   f"also within the joint limits {r['success_strict']} ({r['rows_ok']}/{r['rows']})   running {t_success}/{len(results)} (strict {t_strict}/{len(results)})")
             for line in EV.format_ensemble_report(r.get("ensemble", ())):
                 print(line)
+            if "min_clearance" in r:  # (a run with an SDF guide: the sphere model's smallest clearance along the chosen plan)
+                print(f"    chosen plan: minimum sphere clearance {r['min_clearance']:.4f} m")
 
     # this rank's scenes, in the cfg's order (scene i of that order belongs to rank i mod world)
     mine = []
