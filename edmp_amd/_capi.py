@@ -101,6 +101,8 @@ SIGNATURES = {
     "edmp_argmin_dev": (_i, [_vp, _vp, _i, C.POINTER(C.c_int)]),
     "edmp_sdf_set": (_i, [_vp, _pf, _i, _pi32, _pd, _pd, _i, _i]),
     "edmp_sdf_rows_dev": (_i, [_vp, _vp, _i, _i, _i, _pd, _pd, _vp, _vp]),
+    "edmp_scene_batch_set_sdf": (_i, [_vp, _pf, _i, _pi32, _pd, _pd, _i, _i, _i]),
+    "edmp_scenes_sdf_rows_dev": (_i, [_vp, _vp, _i, _i, _i, _i, _pd, _pd, _vp, _vp]),
     "edmp_sampler_set_allreduce": (_i, [_vp, _vp, _vp]),
     "edmp_rccl_load": (_i, [C.c_char_p]),
     "edmp_rccl_unique_id": (_i, [_vp]),

@@ -64,6 +64,7 @@ struct Guide {
 // sdf.hip: overwrite graw / rowsq of the bound guide's SDF rows (no SDF rows: nothing is launched)
 int sdf_overlay(edmp_ctx* ctx, const double* joints, int ldw, int off, int L, int t, int do_clip);
 int guide_set_startgoal(edmp_ctx* ctx, const double* start, const double* goal);  // guide.hip
+int guide_set_startgoal_scenes(edmp_ctx* ctx, int S, const double* starts, const double* goals);  // guide.hip: [S][14] of a scene batch
 
 // the per-scene entry points (cost, gradient, best trajectory, success, shapes) on a bound scene batch: refused, never answered
 // with scene 0's data

@@ -23,6 +23,12 @@
 // link groups {0,1,2}, {3,4}, {5,6}, {hand, finger}; per-joint partials meet in LDS and are added as ((w0 + w1) + w2) + w3.  The row's
 // obstacles are staged once per workgroup as f32 [16] = rotation (row-major, columns = axes) | centre | half extents | kind, the sphere
 // table (sorted by link on the host, table order kept inside a link) as f32 [4] = centre | radius.  No atomics: every sum has one order.
+//
+// Scene batch (edmp_scene_batch_set_sdf): a row is one workgroup, hence one scene = row / rps.  The workgroup stages the obstacles and
+// kinds of ITS scene only (Guide::obb / Guide::kind hold every scene's primitives, scene after scene) and loops over that scene's own
+// count - no padding, so the first-index rule of a min_o tie is the scene's own - and reads its scene's start / goal pair; margin,
+// smoothness, graw and rowsq are indexed by the global row.  Everything behind the staging is the row's own arithmetic, so a row of
+// scene s computes what it computes on scene s's own guide.  One scene: rps = 0, slice 0 = the whole table.
 #include "common.h"
 #include "guide.h"
 
@@ -40,13 +46,14 @@ struct SdfArgs {
     const double* margin;  // [B][T]; read at t >= 1 only
     int T;
     const double* smooth;  // [B], or nullptr = 0 (edmp_sdf_rows_dev on rows that are not the bound ones)
-    const double* obb;     // [no][16] f64
-    const int32_t* kind;   // [no]
-    int no;
+    const double* obb;     // [sum of the scenes' obstacles][16] f64, scene after scene
+    const int32_t* kind;   // [the same]
+    int rps;               // scene batch: rows per scene (row r belongs to scene r / rps), else 0 = one scene
+    int sc_off[EDMP_MAX_SCENES], sc_cnt[EDMP_MAX_SCENES];  // scene s owns the obstacle rows [sc_off[s], sc_off[s] + sc_cnt[s]) (SceneSlices, success.hip)
     const float* spheres;  // [ns][4] sorted by link
     int ns;
     int link_off[EDMP_N_LINKS + 1];  // spheres of link l: [link_off[l], link_off[l+1])
-    const float* startgoal;          // [14] f32
+    const float* startgoal;          // [14] f32 (scene batch: [S][14])
     float* graw;                     // gradient: [B][7][L]
     double* rowsq;                   // gradient: per-row sum g^2
     double* cost;                    // rows: [n]
@@ -123,11 +130,15 @@ __device__ __forceinline__ void sdf_row(const SdfArgs& a, const RobotConst& rc) 
     const int lane = threadIdx.x & 63;
     const int wv = __builtin_amdgcn_readfirstlane(threadIdx.x >> 6);
     const int r = ROWS ? (int)blockIdx.x : a.rows[blockIdx.x];
-    const int L = a.L, no = a.no;
+    const int scene = __builtin_amdgcn_readfirstlane(a.rps ? r / a.rps : 0);  // (one row, one scene: workgroup-uniform)
+    const int L = a.L, no = min(a.sc_cnt[scene], EDMP_MAX_OBSTACLES);
+    const double* obb = a.obb + (size_t)a.sc_off[scene] * 16;
+    const int32_t* kind = a.kind + a.sc_off[scene];
+    const float* sg = a.startgoal + scene * 14;  // this row's scene's start | goal
     for (int i = threadIdx.x; i < no * 16; i += 256) {
         const int ob = i >> 4, k = i & 15;
-        const bool cyl = a.kind[ob] == 1;
-        const double v = a.obb[i];
+        const bool cyl = kind[ob] == 1;
+        const double v = obb[i];
         // a cylinder's (r, r, h) row is stored halved like a box: slot 12 becomes the radius
         s_ob[i] = (k == 15) ? (cyl ? 1.f : 0.f) : ((k == 12 && cyl) ? (float)(2.0 * v) : (float)v);
     }
@@ -153,7 +164,7 @@ __device__ __forceinline__ void sdf_row(const SdfArgs& a, const RobotConst& rc) 
                 xd = xd < rc.qlo[j] ? rc.qlo[j] : xd;
                 xd = xd > rc.qhi[j] ? rc.qhi[j] : xd;
             }
-            const float vs = a.startgoal[j], vg = a.startgoal[7 + j];
+            const float vs = sg[j], vg = sg[7 + j];
             q[j] = (w == 0) ? vs : ((w > L) ? vg : (float)xd);
         }
     }
@@ -307,7 +318,11 @@ static void fill_args(const Guide* g, SdfArgs& a, const double* joints, int ldw,
     a.smooth = g->sdf_smooth;
     a.obb = g->obb;
     a.kind = g->kind;
-    a.no = g->no;
+    a.rps = (g->S > 1) ? g->rps : 0;
+    for (int s = 0; s < EDMP_MAX_SCENES; ++s) {
+        a.sc_off[s] = s < g->S ? g->scene_off_h[s] : 0;
+        a.sc_cnt[s] = s < g->S ? g->scene_no_h[s] : 0;
+    }
     a.spheres = g->sdf_sph;
     a.ns = g->sdf_ns;
     for (int l = 0; l <= EDMP_N_LINKS; ++l) a.link_off[l] = g->sdf_link_off[l];
@@ -333,33 +348,35 @@ int sdf_overlay(edmp_ctx* ctx, const double* joints, int ldw, int off, int L, in
 
 using namespace edmp;
 
-extern "C" int edmp_sdf_set(edmp_ctx* ctx, const float* spheres, int n_spheres, const int32_t* sdf_row, const double* margin, const double* smoothness,
-                            int B, int T) {
-    EDMP_REQUIRE(ctx && ctx->guide && ctx->guide->obb && ctx->guide->row_class, "edmp_sdf_set: call edmp_scene_set and edmp_rows_set first");
+// edmp_sdf_set and edmp_scene_batch_set_sdf behind their own state checks: value checks, link sort, upload.  rps > 0 (a scene batch):
+// the n rows run scene after scene and a message names the scene and the row inside it.
+static int sdf_table_set(edmp_ctx* ctx, const char* what, const float* spheres, int n_spheres, const int32_t* sdf_row, const double* margin,
+                         const double* smoothness, int n, int T, int rps) {
     Guide* g = ctx->guide;
-    if (g->is_batch || g->S > 1) {
-        set_error("edmp_sdf_set: the bound guide is a scene batch of %d scenes (edmp_scene_batch_set); SDF rows need one guide per scene", g->S);
-        return EDMP_ERR_STATE;
-    }
-    EDMP_REQUIRE(spheres && sdf_row && margin && smoothness, "edmp_sdf_set: null argument");
-    EDMP_REQUIRE(n_spheres >= 1 && n_spheres <= EDMP_MAX_SPHERES, "edmp_sdf_set: %d spheres outside 1..%d", n_spheres, EDMP_MAX_SPHERES);
-    EDMP_REQUIRE(B == g->B && T == g->rows_T, "edmp_sdf_set: %d rows x %d steps given, edmp_rows_set holds %d x %d", B, T, g->B, g->rows_T);
+    EDMP_REQUIRE(spheres && sdf_row && margin && smoothness, "%s: null argument", what);
+    EDMP_REQUIRE(n_spheres >= 1 && n_spheres <= EDMP_MAX_SPHERES, "%s: %d spheres outside 1..%d", what, n_spheres, EDMP_MAX_SPHERES);
     for (int s = 0; s < n_spheres; ++s) {
         const float* sp = spheres + s * 5;
         EDMP_REQUIRE(std::isfinite(sp[0]) && std::isfinite(sp[1]) && std::isfinite(sp[2]) && std::isfinite(sp[3]) && std::isfinite(sp[4]),
-                     "edmp_sdf_set: sphere %d holds a non-finite value", s);
-        EDMP_REQUIRE(sp[0] == std::floor(sp[0]) && sp[0] >= 0.f && sp[0] < (float)EDMP_N_LINKS, "edmp_sdf_set: sphere %d: link %g outside 0..%d", s,
+                     "%s: sphere %d holds a non-finite value", what, s);
+        EDMP_REQUIRE(sp[0] == std::floor(sp[0]) && sp[0] >= 0.f && sp[0] < (float)EDMP_N_LINKS, "%s: sphere %d: link %g outside 0..%d", what, s,
                      (double)sp[0], EDMP_N_LINKS - 1);
-        EDMP_REQUIRE(sp[4] > 0.f, "edmp_sdf_set: sphere %d: radius %g must be > 0", s, (double)sp[4]);
+        EDMP_REQUIRE(sp[4] > 0.f, "%s: sphere %d: radius %g must be > 0", what, s, (double)sp[4]);
     }
+    char where[48];
+    auto row_name = [&](int b) {
+        if (rps) snprintf(where, sizeof(where), "scene %d, row %d", b / rps, b % rps);
+        else snprintf(where, sizeof(where), "row %d", b);
+        return where;
+    };
     std::vector<int32_t> rows;
-    for (int b = 0; b < B; ++b) {
-        EDMP_REQUIRE(sdf_row[b] == 0 || sdf_row[b] == 1, "edmp_sdf_set: row %d: sdf_row must be 0 or 1", b);
-        EDMP_REQUIRE(std::isfinite(smoothness[b]) && smoothness[b] >= 0.0, "edmp_sdf_set: row %d: smoothness %g must be finite and >= 0", b, smoothness[b]);
+    for (int b = 0; b < n; ++b) {
+        EDMP_REQUIRE(sdf_row[b] == 0 || sdf_row[b] == 1, "%s: %s: sdf_row must be 0 or 1", what, row_name(b));
+        EDMP_REQUIRE(std::isfinite(smoothness[b]) && smoothness[b] >= 0.0, "%s: %s: smoothness %g must be finite and >= 0", what, row_name(b), smoothness[b]);
         if (sdf_row[b]) rows.push_back(b);
     }
-    for (size_t i = 0; i < (size_t)B * T; ++i)
-        EDMP_REQUIRE(std::isfinite(margin[i]) && margin[i] >= 0.0, "edmp_sdf_set: row %d, step %d: margin %g must be finite and >= 0", (int)(i / T),
+    for (size_t i = 0; i < (size_t)n * T; ++i)
+        EDMP_REQUIRE(std::isfinite(margin[i]) && margin[i] >= 0.0, "%s: %s, step %d: margin %g must be finite and >= 0", what, row_name((int)(i / T)),
                      (int)(i % T), margin[i]);
     // the table sorted by link, table order kept inside a link: the kernel's wave of a link group walks one contiguous range
     std::vector<float> sph((size_t)n_spheres * 4);
@@ -383,18 +400,39 @@ extern "C" int edmp_sdf_set(edmp_ctx* ctx, const float* spheres, int n_spheres, 
     }
     if (int rc = ctx_alloc(ctx, (void**)&g->sdf_sph, sph.size() * sizeof(float))) return rc;
     if (int rc = ctx_alloc(ctx, (void**)&g->sdf_rows, std::max<size_t>(rows.size(), 1) * sizeof(int32_t))) return rc;
-    if (int rc = ctx_alloc(ctx, (void**)&g->sdf_margin, (size_t)B * T * sizeof(double))) return rc;
-    if (int rc = ctx_alloc(ctx, (void**)&g->sdf_smooth, (size_t)B * sizeof(double))) return rc;
+    if (int rc = ctx_alloc(ctx, (void**)&g->sdf_margin, (size_t)n * T * sizeof(double))) return rc;
+    if (int rc = ctx_alloc(ctx, (void**)&g->sdf_smooth, (size_t)n * sizeof(double))) return rc;
     hipError_t e = hipMemcpyAsync(g->sdf_sph, sph.data(), sph.size() * sizeof(float), hipMemcpyHostToDevice, ctx->stream);
     if (e == hipSuccess && !rows.empty()) e = hipMemcpyAsync(g->sdf_rows, rows.data(), rows.size() * sizeof(int32_t), hipMemcpyHostToDevice, ctx->stream);
-    if (e == hipSuccess) e = hipMemcpyAsync(g->sdf_margin, margin, (size_t)B * T * sizeof(double), hipMemcpyHostToDevice, ctx->stream);
-    if (e == hipSuccess) e = hipMemcpyAsync(g->sdf_smooth, smoothness, (size_t)B * sizeof(double), hipMemcpyHostToDevice, ctx->stream);
+    if (e == hipSuccess) e = hipMemcpyAsync(g->sdf_margin, margin, (size_t)n * T * sizeof(double), hipMemcpyHostToDevice, ctx->stream);
+    if (e == hipSuccess) e = hipMemcpyAsync(g->sdf_smooth, smoothness, (size_t)n * sizeof(double), hipMemcpyHostToDevice, ctx->stream);
     const hipError_t e2 = hipStreamSynchronize(ctx->stream);  // the host vectors and the caller's arrays may go away after the call
     EDMP_HIP_CHECK(e);
     EDMP_HIP_CHECK(e2);
     g->sdf_ns = n_spheres;
     g->sdf_n = (int)rows.size();
     return EDMP_OK;
+}
+
+extern "C" int edmp_sdf_set(edmp_ctx* ctx, const float* spheres, int n_spheres, const int32_t* sdf_row, const double* margin, const double* smoothness,
+                            int B, int T) {
+    EDMP_REQUIRE(ctx && ctx->guide && ctx->guide->obb && ctx->guide->row_class, "edmp_sdf_set: call edmp_scene_set and edmp_rows_set first");
+    Guide* g = ctx->guide;
+    if (g->is_batch || g->S > 1) {
+        set_error("edmp_sdf_set: the bound guide is a scene batch of %d scenes (edmp_scene_batch_set); a scene batch takes its table from edmp_scene_batch_set_sdf",
+                  g->S);
+        return EDMP_ERR_STATE;
+    }
+    EDMP_REQUIRE(B == g->B && T == g->rows_T, "edmp_sdf_set: %d rows x %d steps given, edmp_rows_set holds %d x %d", B, T, g->B, g->rows_T);
+    return sdf_table_set(ctx, "edmp_sdf_set", spheres, n_spheres, sdf_row, margin, smoothness, B, T, 0);
+}
+
+extern "C" int edmp_scene_batch_set_sdf(edmp_ctx* ctx, const float* spheres, int n_spheres, const int32_t* sdf_row, const double* margin,
+                                        const double* smoothness, int S, int B, int T) {
+    EDMP_REQUIRE_SCENE_BATCH(ctx, S, B, "edmp_scene_batch_set_sdf");
+    Guide* g = ctx->guide;
+    EDMP_REQUIRE(T == g->rows_T, "edmp_scene_batch_set_sdf: %d steps given, edmp_rows_set holds %d", T, g->rows_T);
+    return sdf_table_set(ctx, "edmp_scene_batch_set_sdf", spheres, n_spheres, sdf_row, margin, smoothness, S * B, T, B);
 }
 
 extern "C" int edmp_sdf_rows_dev(edmp_ctx* ctx, const double* joints_dev, int n, int L, int t, const double* start, const double* goal,
@@ -416,6 +454,31 @@ extern "C" int edmp_sdf_rows_dev(edmp_ctx* ctx, const double* joints_dev, int n,
     a.cost = cost_dev;
     a.clearance = clearance_dev;
     hipLaunchKernelGGL(sdf_rows_kernel, dim3(n), dim3(256), 0, ctx->stream, a, g->rc);
+    EDMP_HIP_CHECK(hipGetLastError());
+    return EDMP_OK;
+}
+
+// edmp_sdf_rows_dev for a bound scene batch: every row against its own scene's primitives, kinds and start / goal pair
+extern "C" int edmp_scenes_sdf_rows_dev(edmp_ctx* ctx, const double* X_dev, int S, int B, int N, int t, const double* starts, const double* goals,
+                                        double* cost_dev, double* clearance_dev) {
+    EDMP_REQUIRE_SCENE_BATCH(ctx, S, B, "edmp_scenes_sdf_rows_dev");
+    Guide* g = ctx->guide;
+    if (g->sdf_ns <= 0) {
+        set_error("edmp_scenes_sdf_rows_dev: call edmp_scene_batch_set_sdf first (the sphere table)");
+        return EDMP_ERR_STATE;
+    }
+    EDMP_REQUIRE(X_dev && starts && goals && cost_dev && clearance_dev, "edmp_scenes_sdf_rows_dev: null pointer");
+    EDMP_REQUIRE(N >= 3 && N <= 64, "edmp_scenes_sdf_rows_dev: need 3 <= N <= 64 waypoints per row (got %d)", N);
+    EDMP_REQUIRE(t >= 0 && t <= g->rows_T, "edmp_scenes_sdf_rows_dev: t=%d outside 0..%d", t, g->rows_T);
+    EDMP_HIP_CHECK(hipSetDevice(ctx->device));
+    sampler_end_run(ctx);  // (the guide's start / goal pairs are replaced)
+    if (int rc = guide_set_startgoal_scenes(ctx, S, starts, goals)) return rc;
+    SdfArgs a;
+    fill_args(g, a, X_dev, N, 1, N - 2, t, 0);
+    a.rps = B;  // (a batch of ONE scene too: rows / B = 0)
+    a.cost = cost_dev;
+    a.clearance = clearance_dev;
+    hipLaunchKernelGGL(sdf_rows_kernel, dim3(S * B), dim3(256), 0, ctx->stream, a, g->rc);
     EDMP_HIP_CHECK(hipGetLastError());
     return EDMP_OK;
 }

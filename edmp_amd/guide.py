@@ -441,7 +441,9 @@ def scene_batch_tables(scenes):
     obstacle_config (no, 10), row_class (B,) int32, class clearance / expansion (G, T), method (B,), grad_norm (B,) and
     guidance_schedule (B, T).  Returns the concatenation the C ABI takes: n_obstacles (S,) int32, obstacle_config (sum no, 10),
     n_classes (S,) int32, clearance / expansion (sum G, T), and the S*B row arrays with row_class renumbered across the scenes
-    (scene s's classes follow scene s-1's), so that every row of scene s indexes one of scene s's own class schedules."""
+    (scene s's classes follow scene s-1's), so that every row of scene s indexes one of scene s's own class schedules.  Scene dicts that
+    carry the row arrays of the sphere signed-distance guide - sdf_rows (B,), sdf_margin (B, T), smoothness (B,), all scenes or none - add
+    their concatenation (int32, f64, f64: what edmp_scene_batch_set_sdf takes); without them the result is the dict it always was."""
     if not 1 <= len(scenes) <= _capi.MAX_SCENES:
         raise ValueError(f"a scene batch holds 1..{_capi.MAX_SCENES} scenes, got {len(scenes)}")
     B = int(np.asarray(scenes[0]["row_class"]).shape[0])
@@ -467,10 +469,20 @@ def scene_batch_tables(scenes):
     def cat(key, dtype, shape_tail=()):
         return np.ascontiguousarray(np.concatenate([np.asarray(sc[key], dtype=dtype).reshape((-1,) + shape_tail) for sc in scenes]))
 
-    return dict(n_obstacles=np.asarray(n_obs, dtype=np.int32), obstacle_config=cat("obstacle_config", np.float64, (10,)),
-                n_classes=np.asarray(n_cls, dtype=np.int32), clearance=cat("clearance", np.float64, (T,)), expansion=cat("expansion", np.float64, (T,)),
-                row_class=np.ascontiguousarray(np.concatenate(row_class).astype(np.int32)), method=cat("method", np.float32),
-                grad_norm=cat("grad_norm", np.float64), guidance_schedule=cat("guidance_schedule", np.float64, (T,)))
+    out = dict(n_obstacles=np.asarray(n_obs, dtype=np.int32), obstacle_config=cat("obstacle_config", np.float64, (10,)),
+               n_classes=np.asarray(n_cls, dtype=np.int32), clearance=cat("clearance", np.float64, (T,)), expansion=cat("expansion", np.float64, (T,)),
+               row_class=np.ascontiguousarray(np.concatenate(row_class).astype(np.int32)), method=cat("method", np.float32),
+               grad_norm=cat("grad_norm", np.float64), guidance_schedule=cat("guidance_schedule", np.float64, (T,)))
+    with_sdf = ["sdf_rows" in sc for sc in scenes]
+    if any(with_sdf):
+        if not all(with_sdf):
+            raise ValueError(f"scene {with_sdf.index(False)} carries no sdf_rows: either every scene of a batch brings its SDF row arrays or none does")
+        for s, sc in enumerate(scenes):
+            shapes = tuple(np.shape(sc[k]) for k in ("sdf_rows", "sdf_margin", "smoothness"))
+            if shapes != ((B,), (B, T), (B,)):
+                raise ValueError(f"scene {s}: sdf_rows / sdf_margin / smoothness must be ({B},), ({B}, {T}), ({B},), got {shapes}")
+        out.update(sdf_rows=cat("sdf_rows", np.int32), sdf_margin=cat("sdf_margin", np.float64, (T,)), smoothness=cat("smoothness", np.float64))
+    return out
 
 
 class SceneBatch:
@@ -486,7 +498,14 @@ class SceneBatch:
     choose_best_trajectories and success_rows take X as (S, B, 7, N) or (S*B, 7, N), ndarray or device tensor (the tensor of
     denoise_guided_scenes(..., return_device=True) is adopted, not copied) and give, scene by scene, exactly what the scene's own
     guide gives for X[s].  The obstacle kinds of the success check are the guides' own at construction (a guide without kinds counts
-    as all cuboids); set_obstacle_kinds replaces them."""
+    as all cuboids); set_obstacle_kinds replaces them.
+
+    SDF rows (guidance_method 'sdf', csrc/sdf.hip): either every scene of the batch has them or none has - a mix is refused.  In the
+    driver a mix does not occur: ONE run config, hence one guide_cfgs, serves every scene of a group.  All members carry the same sphere
+    table (one robot per batch); the SDF masks, margins and smoothness weights are row arrays like method and grad_norm and may differ
+    from scene to scene.  The batch hands them over with edmp_scene_batch_set_sdf, and every scene's SDF rows - and the grad_norm rows
+    that share their norm - equal the scene's own serial run bit for bit.  sdf_rows(...) reports cost and minimum clearance of every row
+    of the finished state against its own scene."""
 
     def __init__(self, guides):
         guides = list(guides)
@@ -496,8 +515,11 @@ class SceneBatch:
         for k, g in enumerate(guides):
             if not isinstance(g, IntersectionVolumeGuide):
                 raise ValueError(f"scene {k} is not an IntersectionVolumeGuide")
-            if g.has_sdf_rows:
-                raise ValueError(f"scene {k} has SDF rows (guidance_method 'sdf'): a scene batch does not carry them, plan that scene with its own guide")
+            if g.has_sdf_rows != g0.has_sdf_rows:  # (the members' host tables only: nothing is concatenated or bound yet)
+                raise ValueError(f"scene {k} has {'' if g.has_sdf_rows else 'no '}SDF rows (guidance_method 'sdf') and scene 0 has {'' if g0.has_sdf_rows else 'no '}"
+                                 "SDF rows: either every scene of a batch has them or none has")
+            if g.has_sdf_rows and not np.array_equal(g._sdf["spheres"], g0._sdf["spheres"]):
+                raise ValueError(f"scene {k}: the sphere table differs from scene 0's (one robot, one sphere table per batch)")
             if g.ctx is not g0.ctx:
                 raise ValueError(f"scene {k} lives on another context than scene 0")
             if g.batch_size != g0.batch_size or g.T != g0.T:
@@ -507,10 +529,13 @@ class SceneBatch:
                     raise ValueError(f"scene {k}: link / DH / static-frame tables differ from scene 0's (one robot per batch)")
         self.guides, self.ctx, self.device = guides, g0.ctx, g0.device
         self.n_scenes, self.batch_size, self.T = len(guides), g0.batch_size, g0.T
+        sdf = g0.has_sdf_rows
         self.tables = scene_batch_tables([
             dict(obstacle_config=g.obstacle_config, row_class=g.row_class, clearance=g._cls_clr, expansion=g._cls_exp,
                  method=np.asarray(g.guide_cfgs["guidance_method"], dtype=np.float32).reshape(-1),
-                 grad_norm=np.asarray(g.guide_cfgs["grad_norm"], dtype=np.float64).reshape(-1), guidance_schedule=g._sched) for g in guides])
+                 grad_norm=np.asarray(g.guide_cfgs["grad_norm"], dtype=np.float64).reshape(-1), guidance_schedule=g._sched,
+                 **(dict(sdf_rows=g._sdf["rows"], sdf_margin=g._sdf["margin"], smoothness=g._sdf["smooth"]) if sdf else {})) for g in guides])
+        self._spheres = g0._sdf["spheres"] if sdf else None  # None: no SDF table is bound (sdf_rows builds one when a report is asked for)
         self._slot = new_slot_key()
         self._kinds = None
         if any(g._kinds is not None for g in guides):
@@ -541,9 +566,27 @@ class SceneBatch:
                                   _capi.as_pd(tb["guidance_schedule"]), self.n_scenes * self.batch_size, self.T),
             "edmp_rows_set",
         )
+        if self._spheres is not None:  # the SDF table belongs to the rows: after edmp_rows_set
+            self._set_sdf()
         if self._kinds is not None:
             _capi.check(ctx.lib.edmp_scene_batch_set_shapes(ctx.h, _capi.as_pi32(self._kinds), int(self._kinds.shape[0])), "edmp_scene_batch_set_shapes")
         ctx.bound_guide = self
+
+    @property
+    def has_sdf_rows(self):
+        return "sdf_rows" in self.tables and bool(self.tables["sdf_rows"].any())
+
+    def _set_sdf(self):
+        tb, ctx, B = self.tables, self.ctx, self.batch_size
+        if "sdf_rows" not in tb:  # a report on a batch without SDF rows: no row is overlaid; margins / weights where a member brings them
+            zero = dict(rows=np.zeros(B, dtype=np.int32), margin=np.zeros((B, self.T)), smooth=np.zeros(B))
+            parts = [g._sdf if g._sdf is not None else zero for g in self.guides]
+            tb = dict(sdf_rows=np.ascontiguousarray(np.concatenate([p["rows"] for p in parts]).astype(np.int32)),
+                      sdf_margin=np.ascontiguousarray(np.concatenate([p["margin"] for p in parts])),
+                      smoothness=np.ascontiguousarray(np.concatenate([p["smooth"] for p in parts])))
+        rows, margin, smooth = tb["sdf_rows"], tb["sdf_margin"], tb["smoothness"]
+        _capi.check(ctx.lib.edmp_scene_batch_set_sdf(ctx.h, _capi.as_pf(self._spheres), int(self._spheres.shape[0]), _capi.as_pi32(rows), _capi.as_pd(margin),
+                                                     _capi.as_pd(smooth), self.n_scenes, self.batch_size, self.T), "edmp_scene_batch_set_sdf")
 
     # ---- before the run: the IK-goal filter of every scene ---------------------------------------------------------------
     def filter_goals(self, starts, goals, volume_trust_region: float = 0.0008, counts=None):
@@ -690,3 +733,26 @@ class SceneBatch:
             f = ctx.to_host(flags).reshape(3, S, B)
             out.update(ok=f[0].astype(bool), first=f[1].copy(), within=f[2].astype(bool), collision_free=f[1] < 0)
         return out
+
+    def sdf_rows(self, trajectories, starts, goals, t=0):
+        """IntersectionVolumeGuide.sdf_rows for every scene (edmp_scenes_sdf_rows_dev): cost and minimum clearance of EVERY row of the
+        (S, B, 7, N) / (S*B, 7, N) state under the sphere signed-distance model, each row against its own scene's primitives, kinds and
+        start / goal pair -> {"cost": (S, B) f64, "clearance": (S, B) f64}; scene s's values are what guides[s].sdf_rows gives for
+        X[s][:, :, 1:-1].  t = 0: margin 0; t >= 1: the rows' own margins at step t.  A batch built without SDF rows uses scene 0's
+        sphere model (its ``spheres``, else the default of the link boxes) with margin 0 and smoothness 0 where the members bring none."""
+        s, g = self._pairs(starts, goals)
+        Xd, N = self._state(trajectories)
+        lazy = self._spheres is None
+        if lazy:
+            g0 = self.guides[0]
+            self._spheres = sdf_tables({}, g0.batch_size, g0.T, g0._half, g0._spheres)["spheres"]
+        self._bind()
+        if lazy:  # (a resident slot was bound without its table)
+            self._set_sdf()
+        ctx, S, B = self.ctx, self.n_scenes, self.batch_size
+        out = ctx.empty((2, S * B), torch.float64)
+        _capi.check(ctx.lib.edmp_scenes_sdf_rows_dev(ctx.h, ptr(Xd), S, B, N, int(t), _capi.as_pd(s), _capi.as_pd(g), C.c_void_p(out[0].data_ptr()),
+                                                     C.c_void_p(out[1].data_ptr())), "edmp_scenes_sdf_rows_dev")
+        Xd.record_stream(ctx.stream)
+        h = ctx.to_host(out)
+        return {"cost": h[0].reshape(S, B).copy(), "clearance": h[1].reshape(S, B).copy()}

@@ -138,7 +138,8 @@ int edmp_argmin_dev(edmp_ctx* ctx, const float* v_dev, int n, int* index_host);
  * over the padded chain start, L interior waypoints, goal (the smoothness sum is the FULL chain; lib/guide.py:670-677 drops both end
  * differences).  Arithmetic in f32; the formulas and the sub-gradient conventions are stated at the top of csrc/sdf.hip.
  *
- * edmp_sdf_set, after edmp_rows_set on a single-scene guide (a scene batch is refused with EDMP_ERR_STATE): spheres (n,5) f32 rows
+ * edmp_sdf_set, after edmp_rows_set on a single-scene guide (a scene batch is refused with EDMP_ERR_STATE; it takes its table from
+ * edmp_scene_batch_set_sdf below): spheres (n,5) f32 rows
  * [link 0..8, centre xyz in the link-box frame, radius > 0], 1 <= n <= EDMP_MAX_SPHERES; sdf_row (B,) int32 0/1; margin (B,T) f64 and
  * smoothness (B,) f64, finite and >= 0; B and T those of edmp_rows_set.  Rows with sdf_row = 1 keep method 0 in edmp_rows_set's table;
  * in edmp_guide_gradient_dev, the teacher-forced steps and the device loops their raw gradient and sum g^2 are written by
@@ -229,7 +230,8 @@ int edmp_denoise_guided_dev(edmp_ctx* ctx, const double* noise_dev, int B, const
  * those of the previous segment; anything else is refused with EDMP_ERR_STATE (the message names the expected and the given
  * step) and launches nothing.  A run ends when a segment reaches t_lo == 0, and is ended by every other loop entry point
  * (edmp_denoise_guided_dev / _rng_dev / edmp_denoise_scenes_dev), by the teacher-forced steps, edmp_guide_gradient_dev,
- * edmp_guide_swept_cost_dev, edmp_row_swept_volumes_dev and edmp_scenes_swept_volumes_dev (they replace a start / goal pair), by edmp_unet_forward_dev (the
+ * edmp_guide_swept_cost_dev, edmp_row_swept_volumes_dev, edmp_scenes_swept_volumes_dev, edmp_sdf_rows_dev and edmp_scenes_sdf_rows_dev (they replace a
+ * start / goal pair), by edmp_unet_forward_dev (the
  * model's input buffer carries the next segment's input), by a changed edmp_sampler_set_condition and by edmp_sampler_init: a
  * continuing segment after any of them is refused.  A run started with guided = 0 cannot be continued with guided = 1 (the guide
  * never received its pair).
@@ -319,6 +321,29 @@ int edmp_scenes_select_rows_dev(edmp_ctx* ctx, const float* volumes_dev, const d
  * NULL (synchronises when given): per scene [rows ok, rows within limits, rows collision-free, B]. */
 int edmp_scenes_success_rows_dev(edmp_ctx* ctx, const double* X_dev, int S, int B, int N, int substeps, const double* dh_f64,
                                  int32_t* ok_dev, int32_t* first_dev, int32_t* within_dev, int32_t* counts_host);
+
+/* ---- the sphere signed-distance guide inside a scene batch (csrc/sdf.hip) ------------------------------------------ */
+/* edmp_sdf_set for a bound scene batch, after edmp_scene_batch_set and edmp_rows_set: ONE sphere table (a batch has one robot),
+ * spheres (n,5) f32 as edmp_sdf_set; sdf_row (S*B,) int32 0/1, margin (S*B,T) f64 and smoothness (S*B,) f64, scene after scene, so the
+ * masks, margins and weights may differ from scene to scene.  The value checks are edmp_sdf_set's; a message names the scene and the row
+ * inside it.  Needs the bound guide to be a scene batch of exactly S scenes x B rows (a batch of ONE scene included): EDMP_ERR_STATE on a
+ * single-scene guide, EDMP_ERR_ARG for another S, B or T.  Bumps the context's epoch and synchronises, as edmp_sdf_set; a later
+ * edmp_rows_set drops the table.  In edmp_denoise_scenes_dev, its segments and edmp_sampler_seed_scenes_dev an SDF row of scene s is
+ * one workgroup of sdf_guide_kernel that stages the primitives and kinds of scene s only, loops over scene s's own obstacle count and
+ * reads scene s's start / goal pair; sum g^2 is formed per scene.  Scene s's rows - the SDF rows, and the grad_norm rows that share
+ * their norm - therefore equal, bit for bit, scene s's own serial run on a guide with edmp_sdf_set, whatever its neighbours and its
+ * position in the batch.  With no SDF row in the batch nothing else is launched and every result is what it was. */
+int edmp_scene_batch_set_sdf(edmp_ctx* ctx, const float* spheres, int n_spheres, const int32_t* sdf_row, const double* margin,
+                             const double* smoothness, int S, int B, int T);
+/* edmp_sdf_rows_dev per scene: X (S*B,7,N) f64 on the device (not clipped), 3 <= N <= 64, its interior columns 1..N-2 are the waypoints;
+ * starts / goals (S,7) f64 host; cost_dev / clearance_dev (S*B,) f64 on the device.  Every row is scored against its OWN scene's
+ * primitives, kinds and start / goal pair, with margin[row][t - 1] for t >= 1 (0 at t = 0) and the row's own smoothness weight: scene s's
+ * values equal, bit for bit, what edmp_sdf_rows_dev returns for X[s*B .. (s+1)*B)[:, :, 1:-1] on scene s's own guide.  Needs the table of
+ * edmp_scene_batch_set_sdf (EDMP_ERR_STATE without it).  Refused on a single-scene guide with EDMP_ERR_STATE, with another S or B, an N
+ * outside 3..64 or a t outside 0..T with EDMP_ERR_ARG; a refused call launches nothing.  Replaces the guide's start / goal pairs, so it
+ * ends a segmented run like edmp_scenes_swept_volumes_dev.  Does not synchronise. */
+int edmp_scenes_sdf_rows_dev(edmp_ctx* ctx, const double* X_dev, int S, int B, int N, int t, const double* starts, const double* goals,
+                             double* cost_dev, double* clearance_dev);
 
 /* The reference's IK-goal filter (infer_serial.py:117-129: guide.cost of every candidate at t = 0, summed; everything within
  * volume_trust_region of the minimum; of those the goal nearest to the start) for ALL scenes of a bound scene batch in two launches,

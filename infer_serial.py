@@ -149,7 +149,8 @@ def run(cfg_path, dataset=None, max_scenes=None, verbose=True, scenes_in_flight=
     object bound on the device and picks every scene's goal in one call (SceneBatch.filter_goals; the candidate volumes are summed in
     f64 there, so a goal can differ from the serial loop's only where a volume lies within f32 summation rounding of the trust-region
     threshold), the group is planned in one call, then the finished state stays on the device and every scene's best row and success are picked from its own rows by the
-    batch's own scoring calls (SceneBatch.select_rows / success_rows: one launch per step for the group).  Per-scene results equal the serial loop's bit
+    batch's own scoring calls (SceneBatch.select_rows / success_rows: one launch per step for the group; a config that lists an SDF guide
+    plans its SDF rows inside the batch, and with ensemble_report one SceneBatch.sdf_rows call gives every scene's `min_clearance`).  Per-scene results equal the serial loop's bit
     for bit; the last group may be smaller.  The model is built for k * rows, and the feeder keeps 2k whole-scene pinned buffers
     (k = 2 at 1024 rows: 4 x 734 MB page-locked).  Each result carries `scenes_in_launch`; its `denoise_s` is the GROUP's time.
     Not combined with scenes_in_flight > 1.
@@ -362,6 +363,8 @@ def run(cfg_path, dataset=None, max_scenes=None, verbose=True, scenes_in_flight=
         td = time.time()
         all_chk = batch.success_rows(Xd)
         te = time.time()
+        # (a run with an SDF guide: the sphere model's clearance of every row of the group in one call, the chosen rows' are reported)
+        all_clr = batch.sdf_rows(Xd, starts, goals)["clearance"] if ensemble_report and batch.has_sdf_rows else None
         X = diffuser.ctx.to_host(Xd)  # once, for the result dicts
         out = []
         for s, (guide, start_joints, goal_joints, meta, t0) in enumerate(group):
@@ -381,7 +384,8 @@ def run(cfg_path, dataset=None, max_scenes=None, verbose=True, scenes_in_flight=
                             success_proxy=int(chk["collision_free"][idx]), success_strict=int(chk["ok"][idx]), rows_collision_free=chk["rows_collision_free"],
                             rows_ok=chk["rows_ok"], rows=chk["rows"], aabb_volume_zero=bool(ED.geometric_success(float(vols[idx]), trajectory)),
                             first_collision_waypoint=int(chk["first"][idx]), path_length=EV.path_lengths(trajectory), sparc=EV.smoothness(trajectory),
-                            planning_time_s=t_plan, scene_wall_s=time.time() - t0, trajectory=trajectory, **extras(vols, chk, met)))
+                            planning_time_s=t_plan, scene_wall_s=time.time() - t0, trajectory=trajectory,
+                            **({"min_clearance": float(all_clr[s][idx])} if all_clr is not None else {}), **extras(vols, chk, met)))
         return out
 
     try:

@@ -2,7 +2,7 @@
 """sdf_guide_bench.py — what the sphere signed-distance guide (edmp_amd/csrc/sdf.hip) costs on one GPU, B = 1024, full TemporalUNet,
 noise resident on the device.  No gate: nothing here had been timed before.
 
-    python scripts/sdf_guide_bench.py [--reps 20] [--parent-root DIR] [--out profiles/sdf_guide_bench.json]
+    python scripts/sdf_guide_bench.py [--reps 20] [--parent-root DIR] [--only group] [--out profiles/sdf_guide_bench.json]
 
   flagship        a full plan (denoise_guided, 255 steps) with the six-guide ensemble [1,2,3,4,5,10] on a 16-obstacle scene - no SDF rows, so
                   the launches are those of the parent commit.  With --parent-root DIR (a built checkout of the parent commit) the same plan
@@ -13,6 +13,10 @@ noise resident on the device.  No gate: nothing here had been timed before.
   kernel          sdf_guide_kernel in the stream: edmp_guide_gradient_dev on device tensors, enqueued back to back between two events, with
                   k SDF rows minus the same call with none (k = 171 and 1024; 16 and 64 obstacles).  The volume kernel of the same call
                   (guide_kernel, 28 us per launch in DESIGN.md) runs in both.
+  group           four 16-obstacle scenes planned with the ensemble [1,2,3,4,5,101] (171 SDF rows per scene) one scene per launch chain
+                  (k = 1: four denoise_guided calls, one guide per scene) and as one scene group (k = 4: one denoise_guided_scenes call on a
+                  guide.SceneBatch, 4096 rows), the same resident noise in both; the time is that of the four scenes.  --only group runs this
+                  leg alone.
 
 Medians of --reps calls after 3 warm-up calls, with min / max.  Clock: host wall time around a synchronised call for the plans, HIP events on
 the context's stream for the kernel.  Prints ONE JSON line.  Informative: never bench.py's value."""
@@ -118,6 +122,48 @@ def kernel_times(ctx, reps, calls=50):
     return out
 
 
+def group_times(dif, ctx, reps, k=4, n_obstacles=16):
+    """k scenes with SDF rows: one launch chain per scene against one chain for the group (both leave the state on the device)"""
+    import numpy as np
+    import torch
+
+    from edmp_amd import guide_cfg as GC
+    from edmp_amd import scenes
+    from edmp_amd.guide import IntersectionVolumeGuide, SceneBatch
+    from edmp_amd.temporalunet import TemporalUNet
+
+    guides_of = FLAGSHIP[:-1] + (101,)
+    cfgs = GC.build_guide_cfgs([GC.load_guide_dict(g) for g in guides_of], 0, T, rows_per_guide=GC.split_rows(B, len(guides_of)))
+    net = TemporalUNet(None, C, 32, ctx, dims=(32, 64, 128, 256, 512, 512), seed=1, max_batch=k * B)
+    guides = [IntersectionVolumeGuide(scenes.random_scene(11 + s, n_obstacles), ctx, cfgs, B) for s in range(k)]
+    batch = SceneBatch(guides)
+    rs = np.random.RandomState(99)
+    noises = [ctx.to_dev(rs.standard_normal((T + 1, B, C, N)), torch.float64) for _ in range(k)]
+    starts, goals = np.tile(scenes.DEFAULT_START, (k, 1)), np.tile(scenes.DEFAULT_GOAL, (k, 1))
+
+    def serial():
+        for s, g in enumerate(guides):
+            dif.denoise_guided(net, g, N, C, cfgs["guidance_schedule"], batch_size=B, start=starts[s], goal=goals[s], noise=noises[s], return_device=True)
+
+    def group():
+        dif.denoise_guided_scenes(net, batch, N, C, starts, goals, noise=noises, return_device=True)
+
+    out = {"scenes": k, "rows_per_scene": B, "obstacles": n_obstacles, "guides": list(guides_of), "sdf_rows_per_scene": int(cfgs["sdf_rows"].sum())}
+    for name, fn in (("k1", serial), (f"k{k}", group)):
+        ms = []
+        for r in range(WARMUP + reps):
+            ctx.sync()
+            t0 = time.perf_counter()
+            fn()
+            ctx.sync()
+            if r >= WARMUP:
+                ms.append(1e3 * (time.perf_counter() - t0))
+        out[name] = spread(ms)
+    out[f"k1_over_k{k}"] = out["k1"]["median_ms"] / out[f"k{k}"]["median_ms"]
+    out["note"] = f"time of all {k} scenes: k1 = {k} denoise_guided calls in turn, k{k} = one denoise_guided_scenes call on the SceneBatch (the k noise streams are placed in the batch layout inside the call)"
+    return out
+
+
 def child(root, reps):
     """the flagship plan alone, with the package of `root`: prints one JSON line"""
     sys.path.insert(0, root)
@@ -129,6 +175,7 @@ def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--reps", type=int, default=20)
     ap.add_argument("--parent-root", type=str, default=None, help="a built checkout of the parent commit: time the flagship plan there too")
+    ap.add_argument("--only", choices=("group",), default=None, help="run one leg alone")
     ap.add_argument("--out", type=str, default=None)
     ap.add_argument("--child-root", type=str, default=None, help=argparse.SUPPRESS)
     a = ap.parse_args()
@@ -150,6 +197,17 @@ def main():
         out["flagship_agree_within_spread"] = bool(abs(sum(med["this"]) / 2 - sum(med["parent"]) / 2) <= noise_ms)
         out["flagship_spread_ms"] = noise_ms
     sys.path.insert(0, HERE)
+    if a.only == "group":
+        from edmp_amd.diffusion import Diffusion
+
+        dif = Diffusion(T, "cuda:0")
+        out["group"] = group_times(dif, dif.ctx, a.reps)
+        txt = json.dumps(out)
+        print(txt)
+        if a.out:
+            with open(a.out, "w") as f:
+                f.write(txt + "\n")
+        return
     net, dif, ctx, noise = setup()
     swapped = FLAGSHIP[:-1] + (101,)
     for n_obstacles in (16, 64):
@@ -158,6 +216,8 @@ def main():
         out[f"plan_obstacles_{n_obstacles}"] = {"six_guides": six, "guide_10_replaced_by_101": sdf,
                                                 "extra_us_per_guided_step": 1e3 * (sdf["median_ms"] - six["median_ms"]) / out["guided_steps"]}
     out["kernel"] = kernel_times(ctx, a.reps)
+    del net, noise
+    out["group"] = group_times(dif, ctx, a.reps)
     out["guide_kernel_us_per_launch_design_md"] = 28
     txt = json.dumps(out)
     print(txt)
