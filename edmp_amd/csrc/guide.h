@@ -66,8 +66,21 @@ int sdf_overlay(edmp_ctx* ctx, const double* joints, int ldw, int off, int L, in
 int guide_set_startgoal(edmp_ctx* ctx, const double* start, const double* goal);  // guide.hip
 int guide_set_startgoal_scenes(edmp_ctx* ctx, int S, const double* starts, const double* goals);  // guide.hip: [S][14] of a scene batch
 
-// the per-scene entry points (cost, gradient, best trajectory, success, shapes) on a bound scene batch: refused, never answered
-// with scene 0's data
+// ctx->d_int (EDMP_MAX_SCENES device ints for small read-backs), allocated at its first use and kept for the life of the context
+inline int ctx_small_ints(edmp_ctx* ctx) {
+    if (!ctx->d_int) EDMP_HIP_CHECK(hipMalloc((void**)&ctx->d_int, EDMP_MAX_SCENES * sizeof(int)));
+    return EDMP_OK;
+}
+
+// Which entry points take which kind of bound guide (the two macros below are the whole state check; include/edmp_hip.h states the rest):
+//   single only (EDMP_REFUSE_SCENE_BATCH: refused on a batch of S > 1 scenes, never answered with scene 0's data):
+//     edmp_guide_cost_dev, edmp_guide_swept_cost_dev, edmp_guide_gradient_dev, edmp_row_swept_volumes_dev, edmp_success_rows_dev,
+//     edmp_scene_set_shapes, edmp_sdf_rows_dev; with checks of their own edmp_sdf_set (a batch of ONE scene refused too) and the
+//     single-scene loops and teacher-forced steps of sampler.hip
+//   batch only (EDMP_REQUIRE_SCENE_BATCH: the bound guide came from edmp_scene_batch_set, a batch of ONE scene included, and holds
+//     exactly S scenes x B rows): edmp_scenes_swept_volumes_dev, edmp_scenes_select_rows_dev, edmp_scenes_success_rows_dev,
+//     edmp_scenes_sdf_rows_dev, edmp_scenes_goal_filter_dev, edmp_scene_batch_set_sdf; edmp_scene_batch_set_shapes (its own wording)
+//   either: edmp_rows_set, edmp_scene_read_aabbs, edmp_argmin_dev, edmp_select_row_dev, edmp_metrics_rows_dev (the last three read no guide)
 #define EDMP_REFUSE_SCENE_BATCH(g, what)                                                                                          \
     do {                                                                                                                          \
         if ((g) && (g)->S > 1) {                                                                                                  \
@@ -77,7 +90,6 @@ int guide_set_startgoal_scenes(edmp_ctx* ctx, int S, const double* starts, const
         }                                                                                                                         \
     } while (0)
 
-// the edmp_scenes_* scoring calls: the bound guide is a scene batch of exactly S scenes x B rows
 #define EDMP_REQUIRE_SCENE_BATCH(ctx, S_, B_, what)                                                                                       \
     do {                                                                                                                                  \
         if (!(ctx) || !(ctx)->guide || !(ctx)->guide->aabb || !(ctx)->guide->obb || !(ctx)->guide->row_class) {                         \

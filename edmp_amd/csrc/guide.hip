@@ -635,11 +635,11 @@ static int upload_startgoal(edmp_ctx* ctx, const float* start, const float* goal
     return EDMP_OK;
 }
 
-template <int MODE, class TIn>
-static int launch_guide(edmp_ctx* ctx, const TIn* joints, int ldw, int off, int n, int L, int t, int use_row_class, int do_clip, float* out,
-                        double* rowsq) {
-    Guide* g = ctx->guide;
-    GuideArgs<TIn> a;
+// the kernel arguments of every guide_kernel launch, from the bound guide (as fill_args in sdf.hip); a one-scene guide passes no class
+// table and rps = 0 - the single-scene hot path branches on them
+template <class TIn>
+static void fill_guide_args(const Guide* g, GuideArgs<TIn>& a, const TIn* joints, int ldw, int off, int n, int L, int t, int use_row_class, int do_clip,
+                            float* out, double* rowsq) {
     a.joints = joints;
     a.ldw = ldw;
     a.off = off;
@@ -659,6 +659,14 @@ static int launch_guide(edmp_ctx* ctx, const TIn* joints, int ldw, int off, int 
     a.startgoal = g->startgoal;
     a.out = out;
     a.rowsq = rowsq;
+}
+
+template <int MODE, class TIn>
+static int launch_guide(edmp_ctx* ctx, const TIn* joints, int ldw, int off, int n, int L, int t, int use_row_class, int do_clip, float* out,
+                        double* rowsq) {
+    Guide* g = ctx->guide;
+    GuideArgs<TIn> a;
+    fill_guide_args(g, a, joints, ldw, off, n, L, t, use_row_class, do_clip, out, rowsq);
     hipStream_t st = ctx->stream;
     if constexpr (MODE == GM_GRAD) {
         // the gradient: four waves per row, one per link group (round 5: 44 -> 28 us per launch against one wave per row)
@@ -938,7 +946,7 @@ extern "C" int edmp_rows_set(edmp_ctx* ctx, const int32_t* row_class, const floa
 extern "C" int edmp_argmin_dev(edmp_ctx* ctx, const float* v_dev, int n, int* index_host) {
     EDMP_REQUIRE(ctx && v_dev && index_host && n >= 1, "edmp_argmin_dev: bad arguments");
     EDMP_HIP_CHECK(hipSetDevice(ctx->device));
-    if (!ctx->d_int) EDMP_HIP_CHECK(hipMalloc((void**)&ctx->d_int, EDMP_MAX_SCENES * sizeof(int)));  // kept for the life of the context
+    if (int rc = ctx_small_ints(ctx)) return rc;
     int* d_idx = ctx->d_int;
     hipLaunchKernelGGL(argmin_kernel, dim3(1), dim3(64), 0, ctx->stream, v_dev, n, d_idx);
     hipError_t e = hipMemcpyAsync(index_host, d_idx, sizeof(int), hipMemcpyDeviceToHost, ctx->stream);
@@ -1013,55 +1021,26 @@ extern "C" int edmp_guide_gradient_dev(edmp_ctx* ctx, const double* joints_dev, 
     return EDMP_OK;
 }
 
-extern "C" int edmp_row_swept_volumes_dev(edmp_ctx* ctx, const double* X_dev, int B, int N, const double* start, const double* goal,
-                                          float* volumes_dev, int* best_index) {
-    int rc = check_cost_args(ctx, B, N - 2, 0, 0);
-    if (rc) return rc;
+// edmp_row_swept_volumes_dev and edmp_scenes_swept_volumes_dev behind their own state and argument checks: the t = 0 swept volume of
+// S scenes x B rows and the arg-min inside each scene.  batch = false: the one scene of a single-scene guide.
+static int swept_volumes(edmp_ctx* ctx, bool batch, const double* X_dev, int S, int B, int N, const double* starts, const double* goals, float* volumes_dev,
+                         int* best_index_host) {
     Guide* g = ctx->guide;
-    EDMP_REQUIRE(X_dev && start && goal, "null pointer");
-    EDMP_HIP_CHECK(hipSetDevice(ctx->device));
-    sampler_end_run(ctx);
-    rc = ensure_scratch(ctx, g, B, N - 2);
-    if (rc) return rc;
-    rc = guide_set_startgoal(ctx, start, goal);
-    if (rc) return rc;
-    float* dst = volumes_dev ? volumes_dev : g->vol_rows;
-    rc = launch_guide<GM_SV_ROWSUM, double>(ctx, X_dev, N, 1, B, N - 2, 0, 0, 0, dst, nullptr);
-    if (rc) return rc;
-    if (best_index) {
-        int* d_idx = reinterpret_cast<int*>(g->rowsq);  // scratch reuse (>= 8 bytes)
-        hipLaunchKernelGGL(argmin_kernel, dim3(1), dim3(64), 0, ctx->stream, dst, B, d_idx);
-        EDMP_HIP_CHECK(hipGetLastError());
-        EDMP_HIP_CHECK(hipMemcpyAsync(best_index, d_idx, sizeof(int), hipMemcpyDeviceToHost, ctx->stream));
-        EDMP_HIP_CHECK(hipStreamSynchronize(ctx->stream));
-    }
-    return EDMP_OK;
-}
-
-
-// the best-trajectory volumes of a whole scene batch: every row against its own scene's obstacles and start / goal pair, then one
-// arg-min wave per scene
-extern "C" int edmp_scenes_swept_volumes_dev(edmp_ctx* ctx, const double* X_dev, int S, int B, int N, const double* starts, const double* goals,
-                                             float* volumes_dev, int* best_index_host) {
-    EDMP_REQUIRE_SCENE_BATCH(ctx, S, B, "edmp_scenes_swept_volumes_dev");
-    Guide* g = ctx->guide;
-    EDMP_REQUIRE(N >= 3 && N <= 64, "edmp_scenes_swept_volumes_dev: need 3 <= N <= 64 waypoints per row (got %d)", N);
-    EDMP_REQUIRE(X_dev, "edmp_scenes_swept_volumes_dev: X_dev is NULL");
-    EDMP_REQUIRE(starts && goals, "edmp_scenes_swept_volumes_dev: starts and goals (S,7) are required (got %s NULL)",
-                 !starts && !goals ? "both" : (!starts ? "starts" : "goals"));
     EDMP_HIP_CHECK(hipSetDevice(ctx->device));
     sampler_end_run(ctx);  // (the guide's start / goal pairs are replaced)
     const int n = S * B;
     bool moved = false;
     int rc = ensure_scratch(ctx, g, n, N - 2, &moved);
-    if (moved) ctx->epoch++;
+    if (batch && moved) ctx->epoch++;  // (the single-scene call never bumped the epoch for its scratch)
     if (rc) return rc;
     rc = guide_set_startgoal_scenes(ctx, S, starts, goals);
     if (rc) return rc;
     float* dst = volumes_dev ? volumes_dev : g->vol_rows;
-    // t = 0: a class block is uninflated there, so ANY class of the row's scene serves - the row's own (class 0 would be scene 0's table)
-    rc = launch_guide<GM_SV_ROWSUM, double>(ctx, X_dev, N, 1, n, N - 2, 0, 1, 0, dst, nullptr);
+    // t = 0: a class block is uninflated there, so ANY class of the row's scene serves.  One scene: class 0 (use_row_class = 0); a batch:
+    // the row's own (class 0 would be scene 0's table)
+    rc = launch_guide<GM_SV_ROWSUM, double>(ctx, X_dev, N, 1, n, N - 2, 0, batch ? 1 : 0, 0, dst, nullptr);
     if (rc) return rc;
+    if (!batch && !best_index_host) return EDMP_OK;  // (a batch always leaves the arg-min in its scratch)
     int* d_idx = reinterpret_cast<int*>(g->rowsq);  // scratch reuse (S*B doubles hold S ints)
     hipLaunchKernelGGL(argmin_kernel, dim3(S), dim3(64), 0, ctx->stream, dst, B, d_idx);
     EDMP_HIP_CHECK(hipGetLastError());
@@ -1070,6 +1049,26 @@ extern "C" int edmp_scenes_swept_volumes_dev(edmp_ctx* ctx, const double* X_dev,
         EDMP_HIP_CHECK(hipStreamSynchronize(ctx->stream));
     }
     return EDMP_OK;
+}
+
+extern "C" int edmp_row_swept_volumes_dev(edmp_ctx* ctx, const double* X_dev, int B, int N, const double* start, const double* goal,
+                                          float* volumes_dev, int* best_index) {
+    int rc = check_cost_args(ctx, B, N - 2, 0, 0);
+    if (rc) return rc;
+    EDMP_REQUIRE(X_dev && start && goal, "null pointer");
+    return swept_volumes(ctx, false, X_dev, 1, B, N, start, goal, volumes_dev, best_index);
+}
+
+// the best-trajectory volumes of a whole scene batch: every row against its own scene's obstacles and start / goal pair, then one
+// arg-min wave per scene
+extern "C" int edmp_scenes_swept_volumes_dev(edmp_ctx* ctx, const double* X_dev, int S, int B, int N, const double* starts, const double* goals,
+                                             float* volumes_dev, int* best_index_host) {
+    EDMP_REQUIRE_SCENE_BATCH(ctx, S, B, "edmp_scenes_swept_volumes_dev");
+    EDMP_REQUIRE(N >= 3 && N <= 64, "edmp_scenes_swept_volumes_dev: need 3 <= N <= 64 waypoints per row (got %d)", N);
+    EDMP_REQUIRE(X_dev, "edmp_scenes_swept_volumes_dev: X_dev is NULL");
+    EDMP_REQUIRE(starts && goals, "edmp_scenes_swept_volumes_dev: starts and goals (S,7) are required (got %s NULL)",
+                 !starts && !goals ? "both" : (!starts ? "starts" : "goals"));
+    return swept_volumes(ctx, true, X_dev, S, B, N, starts, goals, volumes_dev, best_index_host);
 }
 
 // the candidate scratch of the guide object: grow-only pool blocks; *moved when a block was replaced
@@ -1119,32 +1118,17 @@ extern "C" int edmp_scenes_goal_filter_dev(edmp_ctx* ctx, const double* goals_de
     if (g->S > 1)
         for (int c = g->G - 1; c >= 0; --c) a.sl.cls[g->cls_scene_h[c]] = c;
     EDMP_HIP_CHECK(hipSetDevice(ctx->device));
-    if (!ctx->d_int) EDMP_HIP_CHECK(hipMalloc((void**)&ctx->d_int, EDMP_MAX_SCENES * sizeof(int)));  // kept for the life of the context
+    int rc = ctx_small_ints(ctx);
+    if (rc) return rc;
     bool moved = false;
-    int rc = ensure_cand_scratch(ctx, g, (int)total, &moved);
+    rc = ensure_cand_scratch(ctx, g, (int)total, &moved);
     if (moved) ctx->epoch++;
     if (rc) return rc;
     float* vol = volumes_dev ? volumes_dev : g->cand_vol;
     double* key = key_dev ? key_dev : g->cand_key;
-    a.joints = goals_dev;  // candidate r, joint j at goals[r * 7 + j]: one waypoint per row
-    a.ldw = 1;
-    a.off = 0;
-    a.n = (int)total;
-    a.L = 1;
-    a.t = 0;
-    a.use_row_class = 0;
-    a.do_clip = 0;  // (cost clips nothing)
-    a.row_class = g->row_class;
-    a.method = g->method;
-    a.aabb = g->aabb;
-    a.T = g->T;
-    a.no = g->no;
-    a.cls_no = (g->S > 1) ? g->cls_no : nullptr;
-    a.cls_off = (g->S > 1) ? g->cls_no + g->G : nullptr;
-    a.rps = 0;
-    a.startgoal = g->startgoal;  // (not read: no start / goal column in a candidate)
-    a.out = vol;
-    a.rowsq = nullptr;
+    // candidate r, joint j at goals[r * 7 + j]: one waypoint per row, t = 0, the class from a.sl and not from the rows, nothing clipped
+    fill_guide_args<double>(g, a, goals_dev, 1, 0, (int)total, 1, 0, 0, 0, vol, nullptr);
+    a.rps = 0;  // (no start / goal column in a candidate: the scene comes from a.sl)
     hipLaunchKernelGGL((guide_kernel<GM_CAND_VOL, double, 1, CandArgs>), dim3(blocks), dim3(256), 0, ctx->stream, a, g->rc);
     EDMP_HIP_CHECK(hipGetLastError());
     hipLaunchKernelGGL(goal_pick_kernel, dim3(S), dim3(kPickThreads), 0, ctx->stream, goals_dev, (const float*)vol, key, pk, trust_region, ctx->d_int);

@@ -284,28 +284,27 @@ extern "C" int edmp_metrics_rows_dev(edmp_ctx* ctx, const double* X_dev, int B, 
     return EDMP_OK;
 }
 
-extern "C" int edmp_select_row_dev(edmp_ctx* ctx, const float* volumes_dev, const double* key_dev, int B, double trust_region, int* index_host) {
-    EDMP_REQUIRE(ctx && volumes_dev && key_dev && index_host && B >= 1, "edmp_select_row_dev: need a context, volumes, key, index and B >= 1");
-    EDMP_REQUIRE(!std::isnan(trust_region) && trust_region >= 0.0, "edmp_select_row_dev: trust_region must be >= 0 (got %g)", trust_region);
+// edmp_select_row_dev and edmp_scenes_select_rows_dev behind their own state and pointer checks: the pick inside each of S segments of B rows
+static int select_rows(edmp_ctx* ctx, const char* what, const float* volumes_dev, const double* key_dev, int S, int B, double trust_region,
+                       int* index_host) {
+    EDMP_REQUIRE(!std::isnan(trust_region) && trust_region >= 0.0, "%s: trust_region must be >= 0 (got %g)", what, trust_region);
     EDMP_HIP_CHECK(hipSetDevice(ctx->device));
-    if (!ctx->d_int) EDMP_HIP_CHECK(hipMalloc((void**)&ctx->d_int, EDMP_MAX_SCENES * sizeof(int)));  // kept for the life of the context
-    hipLaunchKernelGGL(select_row_kernel, dim3(1), dim3(kMetricsThreads), 0, ctx->stream, volumes_dev, key_dev, B, trust_region, ctx->d_int);
+    if (int rc = ctx_small_ints(ctx)) return rc;
+    hipLaunchKernelGGL(select_row_kernel, dim3(S), dim3(kMetricsThreads), 0, ctx->stream, volumes_dev, key_dev, B, trust_region, ctx->d_int);
     EDMP_HIP_CHECK(hipGetLastError());
-    EDMP_HIP_CHECK(hipMemcpyAsync(index_host, ctx->d_int, sizeof(int), hipMemcpyDeviceToHost, ctx->stream));
+    EDMP_HIP_CHECK(hipMemcpyAsync(index_host, ctx->d_int, S * sizeof(int), hipMemcpyDeviceToHost, ctx->stream));
     EDMP_HIP_CHECK(hipStreamSynchronize(ctx->stream));
     return EDMP_OK;
+}
+
+extern "C" int edmp_select_row_dev(edmp_ctx* ctx, const float* volumes_dev, const double* key_dev, int B, double trust_region, int* index_host) {
+    EDMP_REQUIRE(ctx && volumes_dev && key_dev && index_host && B >= 1, "edmp_select_row_dev: need a context, volumes, key, index and B >= 1");
+    return select_rows(ctx, "edmp_select_row_dev", volumes_dev, key_dev, 1, B, trust_region, index_host);  // (needs no guide: any binding will do)
 }
 
 extern "C" int edmp_scenes_select_rows_dev(edmp_ctx* ctx, const float* volumes_dev, const double* key_dev, int S, int B, double trust_region,
                                            int* index_host) {
     EDMP_REQUIRE_SCENE_BATCH(ctx, S, B, "edmp_scenes_select_rows_dev");
     EDMP_REQUIRE(volumes_dev && key_dev && index_host, "edmp_scenes_select_rows_dev: need volumes, key and index");
-    EDMP_REQUIRE(!std::isnan(trust_region) && trust_region >= 0.0, "edmp_scenes_select_rows_dev: trust_region must be >= 0 (got %g)", trust_region);
-    EDMP_HIP_CHECK(hipSetDevice(ctx->device));
-    if (!ctx->d_int) EDMP_HIP_CHECK(hipMalloc((void**)&ctx->d_int, EDMP_MAX_SCENES * sizeof(int)));  // kept for the life of the context
-    hipLaunchKernelGGL(select_row_kernel, dim3(S), dim3(kMetricsThreads), 0, ctx->stream, volumes_dev, key_dev, B, trust_region, ctx->d_int);
-    EDMP_HIP_CHECK(hipGetLastError());
-    EDMP_HIP_CHECK(hipMemcpyAsync(index_host, ctx->d_int, S * sizeof(int), hipMemcpyDeviceToHost, ctx->stream));
-    EDMP_HIP_CHECK(hipStreamSynchronize(ctx->stream));
-    return EDMP_OK;
+    return select_rows(ctx, "edmp_scenes_select_rows_dev", volumes_dev, key_dev, S, B, trust_region, index_host);
 }

@@ -435,21 +435,19 @@ extern "C" int edmp_scene_batch_set_sdf(edmp_ctx* ctx, const float* spheres, int
     return sdf_table_set(ctx, "edmp_scene_batch_set_sdf", spheres, n_spheres, sdf_row, margin, smoothness, S * B, T, B);
 }
 
-extern "C" int edmp_sdf_rows_dev(edmp_ctx* ctx, const double* joints_dev, int n, int L, int t, const double* start, const double* goal,
-                                 double* cost_dev, double* clearance_dev) {
-    EDMP_REQUIRE(ctx && ctx->guide && ctx->guide->obb, "edmp_sdf_rows_dev: scene not set");
+// edmp_sdf_rows_dev and edmp_scenes_sdf_rows_dev behind their own state, table, pointer and shape checks: n rows of S scenes whose L
+// interior waypoints lie at columns off .. off + L - 1 of rows of ldw columns; starts / goals [S][7]; rps as SdfArgs::rps
+static int sdf_rows(edmp_ctx* ctx, const char* what, const double* joints_dev, int S, int n, int ldw, int off, int L, int t, int rps,
+                    const double* starts, const double* goals, double* cost_dev, double* clearance_dev) {
     Guide* g = ctx->guide;
-    EDMP_REFUSE_SCENE_BATCH(g, "edmp_sdf_rows_dev");
-    EDMP_REQUIRE(g->sdf_ns > 0, "edmp_sdf_rows_dev: call edmp_sdf_set first (the sphere table)");
-    EDMP_REQUIRE(joints_dev && start && goal && cost_dev && clearance_dev, "edmp_sdf_rows_dev: null pointer");
-    EDMP_REQUIRE(n >= 1 && L >= 1 && L + 2 <= 64, "edmp_sdf_rows_dev: need n >= 1 and 1 <= L <= 62 waypoints per row (got %d, %d)", n, L);
-    EDMP_REQUIRE(t >= 0 && t <= g->rows_T, "edmp_sdf_rows_dev: t=%d outside 0..%d", t, g->rows_T);
-    EDMP_REQUIRE(t == 0 || n == g->B, "edmp_sdf_rows_dev: t >= 1 reads the rows' margin schedules: %d rows given, %d bound", n, g->B);
+    EDMP_REQUIRE(t >= 0 && t <= g->rows_T, "%s: t=%d outside 0..%d", what, t, g->rows_T);
+    EDMP_REQUIRE(t == 0 || n == g->B, "%s: t >= 1 reads the rows' margin schedules: %d rows given, %d bound", what, n, g->B);  // (a batch: always its rows)
     EDMP_HIP_CHECK(hipSetDevice(ctx->device));
-    sampler_end_run(ctx);  // (the guide's start / goal pair is replaced)
-    if (int rc = guide_set_startgoal(ctx, start, goal)) return rc;
+    sampler_end_run(ctx);  // (the guide's start / goal pairs are replaced)
+    if (int rc = guide_set_startgoal_scenes(ctx, S, starts, goals)) return rc;
     SdfArgs a;
-    fill_args(g, a, joints_dev, L, 0, L, t, 0);
+    fill_args(g, a, joints_dev, ldw, off, L, t, 0);
+    a.rps = rps;
     if (n != g->B) a.smooth = nullptr;  // rows that are not the bound ones carry no smoothness weight
     a.cost = cost_dev;
     a.clearance = clearance_dev;
@@ -458,27 +456,27 @@ extern "C" int edmp_sdf_rows_dev(edmp_ctx* ctx, const double* joints_dev, int n,
     return EDMP_OK;
 }
 
+extern "C" int edmp_sdf_rows_dev(edmp_ctx* ctx, const double* joints_dev, int n, int L, int t, const double* start, const double* goal,
+                                 double* cost_dev, double* clearance_dev) {
+    EDMP_REQUIRE(ctx && ctx->guide && ctx->guide->obb, "edmp_sdf_rows_dev: scene not set");
+    EDMP_REFUSE_SCENE_BATCH(ctx->guide, "edmp_sdf_rows_dev");
+    EDMP_REQUIRE(ctx->guide->sdf_ns > 0, "edmp_sdf_rows_dev: call edmp_sdf_set first (the sphere table)");  // (EDMP_ERR_ARG; the batch: EDMP_ERR_STATE)
+    EDMP_REQUIRE(joints_dev && start && goal && cost_dev && clearance_dev, "edmp_sdf_rows_dev: null pointer");
+    EDMP_REQUIRE(n >= 1 && L >= 1 && L + 2 <= 64, "edmp_sdf_rows_dev: need n >= 1 and 1 <= L <= 62 waypoints per row (got %d, %d)", n, L);
+    // interior waypoints only, any n at t = 0; one scene: rps = 0
+    return sdf_rows(ctx, "edmp_sdf_rows_dev", joints_dev, 1, n, L, 0, L, t, 0, start, goal, cost_dev, clearance_dev);
+}
+
 // edmp_sdf_rows_dev for a bound scene batch: every row against its own scene's primitives, kinds and start / goal pair
 extern "C" int edmp_scenes_sdf_rows_dev(edmp_ctx* ctx, const double* X_dev, int S, int B, int N, int t, const double* starts, const double* goals,
                                         double* cost_dev, double* clearance_dev) {
     EDMP_REQUIRE_SCENE_BATCH(ctx, S, B, "edmp_scenes_sdf_rows_dev");
-    Guide* g = ctx->guide;
-    if (g->sdf_ns <= 0) {
+    if (ctx->guide->sdf_ns <= 0) {
         set_error("edmp_scenes_sdf_rows_dev: call edmp_scene_batch_set_sdf first (the sphere table)");
         return EDMP_ERR_STATE;
     }
     EDMP_REQUIRE(X_dev && starts && goals && cost_dev && clearance_dev, "edmp_scenes_sdf_rows_dev: null pointer");
     EDMP_REQUIRE(N >= 3 && N <= 64, "edmp_scenes_sdf_rows_dev: need 3 <= N <= 64 waypoints per row (got %d)", N);
-    EDMP_REQUIRE(t >= 0 && t <= g->rows_T, "edmp_scenes_sdf_rows_dev: t=%d outside 0..%d", t, g->rows_T);
-    EDMP_HIP_CHECK(hipSetDevice(ctx->device));
-    sampler_end_run(ctx);  // (the guide's start / goal pairs are replaced)
-    if (int rc = guide_set_startgoal_scenes(ctx, S, starts, goals)) return rc;
-    SdfArgs a;
-    fill_args(g, a, X_dev, N, 1, N - 2, t, 0);
-    a.rps = B;  // (a batch of ONE scene too: rows / B = 0)
-    a.cost = cost_dev;
-    a.clearance = clearance_dev;
-    hipLaunchKernelGGL(sdf_rows_kernel, dim3(S * B), dim3(256), 0, ctx->stream, a, g->rc);
-    EDMP_HIP_CHECK(hipGetLastError());
-    return EDMP_OK;
+    // the full state with its start / goal columns; rps = B forced, for a batch of ONE scene too (rows / B = 0)
+    return sdf_rows(ctx, "edmp_scenes_sdf_rows_dev", X_dev, S, S * B, N, 1, N - 2, t, B, starts, goals, cost_dev, clearance_dev);
 }

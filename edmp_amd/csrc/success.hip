@@ -336,43 +336,20 @@ static Robot64 robot64_of(const Guide* g, const double* dh_f64) {
     return rc;
 }
 
-extern "C" int edmp_scene_set_shapes(edmp_ctx* ctx, const int32_t* kind, int n_obstacles) {
-    EDMP_REQUIRE(ctx && ctx->guide && ctx->guide->obb && ctx->guide->kind, "edmp_scene_set_shapes: call edmp_scene_set first");
-    EDMP_REFUSE_SCENE_BATCH(ctx->guide, "edmp_scene_set_shapes");
-    Guide* g = ctx->guide;
-    EDMP_REQUIRE(kind && n_obstacles == g->no, "edmp_scene_set_shapes: need %d kinds (one per obstacle of the scene)", g->no);
-    for (int i = 0; i < n_obstacles; ++i) EDMP_REQUIRE(kind[i] == 0 || kind[i] == 1, "obstacle %d: kind must be 0 (cuboid) or 1 (cylinder)", i);
+// edmp_scene_set_shapes and edmp_scene_batch_set_shapes behind their own state and count checks: value check and upload of n kinds
+static int shapes_set(edmp_ctx* ctx, const int32_t* kind, int n) {
+    for (int i = 0; i < n; ++i) EDMP_REQUIRE(kind[i] == 0 || kind[i] == 1, "obstacle %d: kind must be 0 (cuboid) or 1 (cylinder)", i);
     EDMP_HIP_CHECK(hipSetDevice(ctx->device));
-    EDMP_HIP_CHECK(hipMemcpyAsync(g->kind, kind, n_obstacles * sizeof(int32_t), hipMemcpyHostToDevice, ctx->stream));
+    EDMP_HIP_CHECK(hipMemcpyAsync(ctx->guide->kind, kind, n * sizeof(int32_t), hipMemcpyHostToDevice, ctx->stream));
     EDMP_HIP_CHECK(hipStreamSynchronize(ctx->stream));
     return EDMP_OK;
 }
 
-extern "C" int edmp_success_rows_dev(edmp_ctx* ctx, const double* X_dev, int B, int N, int substeps, const double* dh_f64, int32_t* ok_dev,
-                                     int32_t* first_dev, int32_t* within_dev, int32_t* counts_host) {
-    EDMP_REQUIRE(ctx && ctx->guide && ctx->guide->obb, "edmp_success_rows_dev: scene not set");
-    EDMP_REFUSE_SCENE_BATCH(ctx->guide, "edmp_success_rows_dev");
-    Guide* g = ctx->guide;
-    EDMP_REQUIRE(X_dev && B >= 1 && N >= 2 && substeps >= 1 && substeps <= 64, "edmp_success_rows_dev: need B >= 1, N >= 2, 1 <= substeps <= 64");
-    EDMP_HIP_CHECK(hipSetDevice(ctx->device));
-    if (int rc = ensure_flags(ctx, g, B, 1)) return rc;
-    int32_t* ok = ok_dev ? ok_dev : g->flags;
-    int32_t* first = first_dev ? first_dev : g->flags + g->flags_B;
-    int32_t* within = within_dev ? within_dev : g->flags + 2 * (size_t)g->flags_B;
-    int32_t* counts = g->flags + 3 * (size_t)g->flags_B;
-    const Robot64 rc = robot64_of(g, dh_f64);
-    SceneSlices sl = {};
-    sl.rps = B;
-    sl.cnt[0] = g->no;
-    hipLaunchKernelGGL(success_rows_kernel, dim3(B), dim3(256), 0, ctx->stream, X_dev, B, N, substeps, g->obb, g->kind, sl, rc, ok, first, within);
-    EDMP_HIP_CHECK(hipGetLastError());
-    if (counts_host) {
-        hipLaunchKernelGGL(count_flags_kernel, dim3(1), dim3(256), 0, ctx->stream, ok, first, within, B, counts);
-        EDMP_HIP_CHECK(hipGetLastError());
-        EDMP_HIP_CHECK(hipMemcpyAsync(counts_host, counts, 4 * sizeof(int32_t), hipMemcpyDeviceToHost, ctx->stream));
-        EDMP_HIP_CHECK(hipStreamSynchronize(ctx->stream));
-    }
-    return EDMP_OK;
+extern "C" int edmp_scene_set_shapes(edmp_ctx* ctx, const int32_t* kind, int n_obstacles) {
+    EDMP_REQUIRE(ctx && ctx->guide && ctx->guide->obb && ctx->guide->kind, "edmp_scene_set_shapes: call edmp_scene_set first");
+    EDMP_REFUSE_SCENE_BATCH(ctx->guide, "edmp_scene_set_shapes");
+    EDMP_REQUIRE(kind && n_obstacles == ctx->guide->no, "edmp_scene_set_shapes: need %d kinds (one per obstacle of the scene)", ctx->guide->no);
+    return shapes_set(ctx, kind, n_obstacles);
 }
 
 extern "C" int edmp_scene_batch_set_shapes(edmp_ctx* ctx, const int32_t* kind, int n_total) {
@@ -389,42 +366,59 @@ extern "C" int edmp_scene_batch_set_shapes(edmp_ctx* ctx, const int32_t* kind, i
     const int total = g->scene_off_h.back() + g->scene_no_h.back();
     EDMP_REQUIRE(kind && n_total == total, "edmp_scene_batch_set_shapes: need %d kinds (one per obstacle of the batch's %d scenes, scene after scene), got %d",
                  total, g->S, n_total);
-    for (int i = 0; i < n_total; ++i) EDMP_REQUIRE(kind[i] == 0 || kind[i] == 1, "obstacle %d: kind must be 0 (cuboid) or 1 (cylinder)", i);
+    return shapes_set(ctx, kind, n_total);
+}
+
+// the caller's three flag arrays, each replaced by its block of the guide's flags scratch where it is NULL, and the count quadruples
+struct FlagPtrs {
+    int32_t *ok, *first, *within, *counts;
+};
+static FlagPtrs flags_or_scratch(const Guide* g, int32_t* ok_dev, int32_t* first_dev, int32_t* within_dev) {
+    const size_t fb = (size_t)g->flags_B;
+    return {ok_dev ? ok_dev : g->flags, first_dev ? first_dev : g->flags + fb, within_dev ? within_dev : g->flags + 2 * fb, g->flags + 3 * fb};
+}
+
+// edmp_success_rows_dev and edmp_scenes_success_rows_dev behind their own state and argument checks: S scenes x rps rows, one count
+// quadruple per scene.  batch = false: the one scene of a single-scene guide.
+static int success_rows(edmp_ctx* ctx, bool batch, const double* X_dev, int S, int rps, int N, int substeps, const double* dh_f64, int32_t* ok_dev,
+                        int32_t* first_dev, int32_t* within_dev, int32_t* counts_host) {
+    Guide* g = ctx->guide;
     EDMP_HIP_CHECK(hipSetDevice(ctx->device));
-    EDMP_HIP_CHECK(hipMemcpyAsync(g->kind, kind, n_total * sizeof(int32_t), hipMemcpyHostToDevice, ctx->stream));
-    EDMP_HIP_CHECK(hipStreamSynchronize(ctx->stream));
+    const int n = S * rps;
+    const int32_t* had = g->flags;
+    if (int rc = ensure_flags(ctx, g, n, S)) return rc;
+    if (batch && g->flags != had) ctx->epoch++;  // (the single-scene call never bumped the epoch for its flags)
+    const FlagPtrs f = flags_or_scratch(g, ok_dev, first_dev, within_dev);
+    const Robot64 rc = robot64_of(g, dh_f64);
+    SceneSlices sl = {};
+    sl.rps = rps;
+    for (int s = 0; s < S; ++s) {
+        sl.off[s] = batch ? g->scene_off_h[s] : 0;  // (the single-scene call: the whole table, g->no obstacles)
+        sl.cnt[s] = batch ? g->scene_no_h[s] : g->no;
+    }
+    hipLaunchKernelGGL(success_rows_kernel, dim3(n), dim3(256), 0, ctx->stream, X_dev, n, N, substeps, g->obb, g->kind, sl, rc, f.ok, f.first, f.within);
+    EDMP_HIP_CHECK(hipGetLastError());
+    if (counts_host) {
+        hipLaunchKernelGGL(count_flags_kernel, dim3(S), dim3(256), 0, ctx->stream, f.ok, f.first, f.within, rps, f.counts);
+        EDMP_HIP_CHECK(hipGetLastError());
+        EDMP_HIP_CHECK(hipMemcpyAsync(counts_host, f.counts, (size_t)S * 4 * sizeof(int32_t), hipMemcpyDeviceToHost, ctx->stream));
+        EDMP_HIP_CHECK(hipStreamSynchronize(ctx->stream));
+    }
     return EDMP_OK;
+}
+
+extern "C" int edmp_success_rows_dev(edmp_ctx* ctx, const double* X_dev, int B, int N, int substeps, const double* dh_f64, int32_t* ok_dev,
+                                     int32_t* first_dev, int32_t* within_dev, int32_t* counts_host) {
+    EDMP_REQUIRE(ctx && ctx->guide && ctx->guide->obb, "edmp_success_rows_dev: scene not set");
+    EDMP_REFUSE_SCENE_BATCH(ctx->guide, "edmp_success_rows_dev");
+    EDMP_REQUIRE(X_dev && B >= 1 && N >= 2 && substeps >= 1 && substeps <= 64, "edmp_success_rows_dev: need B >= 1, N >= 2, 1 <= substeps <= 64");
+    return success_rows(ctx, false, X_dev, 1, B, N, substeps, dh_f64, ok_dev, first_dev, within_dev, counts_host);
 }
 
 extern "C" int edmp_scenes_success_rows_dev(edmp_ctx* ctx, const double* X_dev, int S, int B, int N, int substeps, const double* dh_f64, int32_t* ok_dev,
                                             int32_t* first_dev, int32_t* within_dev, int32_t* counts_host) {
     EDMP_REQUIRE_SCENE_BATCH(ctx, S, B, "edmp_scenes_success_rows_dev");
-    Guide* g = ctx->guide;
     EDMP_REQUIRE(X_dev && N >= 2 && substeps >= 1 && substeps <= 64, "edmp_scenes_success_rows_dev: need X, N >= 2 (got %d), 1 <= substeps <= 64 (got %d)", N,
                  substeps);
-    EDMP_HIP_CHECK(hipSetDevice(ctx->device));
-    const int n = S * B;
-    const int32_t* had = g->flags;
-    if (int rc = ensure_flags(ctx, g, n, S)) return rc;
-    if (g->flags != had) ctx->epoch++;
-    int32_t* ok = ok_dev ? ok_dev : g->flags;
-    int32_t* first = first_dev ? first_dev : g->flags + g->flags_B;
-    int32_t* within = within_dev ? within_dev : g->flags + 2 * (size_t)g->flags_B;
-    int32_t* counts = g->flags + 3 * (size_t)g->flags_B;
-    const Robot64 rc = robot64_of(g, dh_f64);
-    SceneSlices sl = {};
-    sl.rps = B;
-    for (int s = 0; s < S; ++s) {
-        sl.off[s] = g->scene_off_h[s];
-        sl.cnt[s] = g->scene_no_h[s];
-    }
-    hipLaunchKernelGGL(success_rows_kernel, dim3(n), dim3(256), 0, ctx->stream, X_dev, n, N, substeps, g->obb, g->kind, sl, rc, ok, first, within);
-    EDMP_HIP_CHECK(hipGetLastError());
-    if (counts_host) {
-        hipLaunchKernelGGL(count_flags_kernel, dim3(S), dim3(256), 0, ctx->stream, ok, first, within, B, counts);
-        EDMP_HIP_CHECK(hipGetLastError());
-        EDMP_HIP_CHECK(hipMemcpyAsync(counts_host, counts, (size_t)S * 4 * sizeof(int32_t), hipMemcpyDeviceToHost, ctx->stream));
-        EDMP_HIP_CHECK(hipStreamSynchronize(ctx->stream));
-    }
-    return EDMP_OK;
+    return success_rows(ctx, true, X_dev, S, B, N, substeps, dh_f64, ok_dev, first_dev, within_dev, counts_host);
 }

@@ -532,7 +532,7 @@ class Diffusion:
         beside the loop.  ``zero_row0``: quirk Q3 on row 0 of every scene.  ``guided=False``: the unguided loop, per-scene conditioning.
         ``warm_start``: as in denoise_guided, x0 (S, C, N) - scene s's plan for all its rows - or (S, B, C, N); every scene's stream is then
         (lead + t_start - t_stop, B, C, N)."""
-        from .guide import SceneBatch
+        from .guide import SceneBatch, _pairs
 
         ctx = self.ctx
         if not isinstance(batch, SceneBatch):
@@ -552,13 +552,7 @@ class Diffusion:
             if needed:
                 raise ValueError("starts and goals are required when conditioning or guiding")
             starts = goals = np.zeros((S, 7))
-        sg = []
-        for name, v in (("starts", starts), ("goals", goals)):
-            a = np.ascontiguousarray(np.asarray(v, dtype=np.float64))
-            if a.shape != (S, 7):
-                raise ValueError(f"{name} must be ({S}, 7), got {a.shape}")
-            sg.append(a)
-        s_arr, g_arr = sg
+        s_arr, g_arr = _pairs(S, starts, goals)
         if isinstance(noise, str):
             raise _capi.EdmpError("the device noise mode (noise='device') has no scene batch: pass NumPy-stream noise")
         if noise is not None and (not isinstance(noise, (list, tuple)) or len(noise) != S):

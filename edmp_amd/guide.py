@@ -129,7 +129,117 @@ def sdf_tables(guide_cfgs, batch_size, T, link_half_extents, spheres=None):
 spheres_from_boxes = franka.spheres_from_boxes
 
 
-class IntersectionVolumeGuide:
+def _pair7(start, goal):
+    """one start / goal pair as two contiguous (7,) f64 arrays"""
+    return [np.ascontiguousarray(np.asarray(v, dtype=np.float64).reshape(7)) for v in (start, goal)]
+
+
+def _pairs(n_scenes, starts, goals):
+    """the start / goal pairs of a scene batch as two contiguous (S, 7) f64 arrays"""
+    out = []
+    for name, v in (("starts", starts), ("goals", goals)):
+        if v is None:
+            raise ValueError(f"{name} is required: ({n_scenes}, 7)")
+        a = np.ascontiguousarray(np.asarray(v, dtype=np.float64))
+        if a.shape != (n_scenes, 7):
+            raise ValueError(f"{name} must be ({n_scenes}, 7), got {a.shape}")
+        out.append(a)
+    return out
+
+
+class _SlotObject:
+    """What IntersectionVolumeGuide and SceneBatch share: the resident-slot protocol, and the scoring calls whose single-scene and
+    scene-batch entry points differ in their leading dimensions only.  Below, ``shape`` is (B,) for a guide and (S, B) for a batch: the
+    shape of every per-row result and, as leading arguments, what tells edmp_x from edmp_scenes_x.  A subclass brings ctx, _slot,
+    _upload() (its tables into the current slot), _sdf_host() (make the host sphere table if there is none: True if it did) and
+    _set_sdf()."""
+
+    def _bind(self):
+        ctx = self.ctx
+        if ctx.bound_guide is self:
+            return
+        # switch to this object's resident slot; the scene tables / row arrays are rebuilt only if the slot is empty
+        have = ctx.lib.edmp_guide_slot(ctx.h, self._slot)
+        if have < 0:
+            _capi.check(have, "edmp_guide_slot")
+        if have != 1:
+            ctx.bound_guide = None
+            self._upload()
+        ctx.bound_guide = self  # only a completely built object counts as bound
+
+    def _bind_sdf(self):
+        """_bind for a sphere report: an object built without a sphere table makes its host table first and hands it over once bound"""
+        lazy = self._sdf_host()
+        self._bind()
+        if lazy:  # (a resident slot was bound without its table)
+            self._set_sdf()
+
+    def _rows_f64(self, X):
+        """a device tensor adopted, anything else uploaded: the contiguous f64 device tensor"""
+        if isinstance(X, torch.Tensor) and X.is_cuda:
+            return self.ctx.adopt(X.to(torch.float64).contiguous())
+        return self.ctx.to_dev(X if isinstance(X, torch.Tensor) else np.asarray(X, dtype=np.float64), torch.float64)
+
+    def _call(self, single, batch, shape, *args):
+        """the entry point `single` for a guide, `batch` for a scene batch"""
+        name = batch if len(shape) == 2 else single
+        _capi.check(getattr(self.ctx.lib, name)(self.ctx.h, *args), name)
+
+    def _swept(self, Xd, shape, N, pair, want_index):
+        """the t = 0 swept volume of every row -> (volumes (rows,) f32 device tensor, arg-min inside each scene (S,) int64 or None)"""
+        vols = self.ctx.empty((int(np.prod(shape)),), torch.float32)
+        idx = (C.c_int * (shape[0] if len(shape) == 2 else 1))() if want_index else None
+        self._call("edmp_row_swept_volumes_dev", "edmp_scenes_swept_volumes_dev", shape, ptr(Xd), *shape, N, _capi.as_pd(pair[0]), _capi.as_pd(pair[1]),
+                   ptr(vols), idx)
+        return vols, (np.array(idx[:], dtype=np.int64) if want_index else None)
+
+    def _pick(self, Xd, vols, shape, prefer, volume_trust_region):
+        """the trust-region pick among the rows of each scene -> (indices (S,) int64, volumes f32, metrics dict of f64, both `shape`d);
+        volumes, metrics and the pick stay on the device, the indices come back"""
+        from .evaluation import metrics_rows_on
+
+        ctx = self.ctx
+        met = metrics_rows_on(ctx, Xd, return_device=True)
+        with torch.cuda.stream(ctx.stream):
+            key = met["joint_path_length"] if prefer == "shortest" else torch.neg(met["joint_sparc"])  # SPARC <= 0: closest to 0 = largest
+        idx = (C.c_int * (shape[0] if len(shape) == 2 else 1))()
+        self._call("edmp_select_row_dev", "edmp_scenes_select_rows_dev", shape, ptr(vols), ptr(key), *shape, C.c_double(float(volume_trust_region)), idx)
+        with torch.cuda.stream(ctx.stream):
+            m = torch.stack([met[k] for k in met])
+        mh = ctx.to_host(m)
+        return np.array(idx[:], dtype=np.int64), ctx.to_host(vols).reshape(shape), {k: mh[i].reshape(shape).copy() for i, k in enumerate(met)}
+
+    def _success(self, Xd, shape, N, substeps, return_device):
+        """the success dict: per-row arrays `shape`d, the four counts as ints for a guide and as (S,) arrays for a batch"""
+        ctx, batch = self.ctx, len(shape) == 2
+        flags = ctx.empty((3, int(np.prod(shape))), torch.int32)
+        counts = (C.c_int32 * (4 * (shape[0] if batch else 1)))()
+        dh = np.ascontiguousarray(franka.dh_table_f64())
+        self._call("edmp_success_rows_dev", "edmp_scenes_success_rows_dev", shape, ptr(Xd), *shape, N, int(substeps), _capi.as_pd(dh),
+                   C.c_void_p(flags[0].data_ptr()), C.c_void_p(flags[1].data_ptr()), C.c_void_p(flags[2].data_ptr()), counts)
+        cn = np.array(counts[:], dtype=np.int64).reshape(-1, 4)
+        out = {k: (cn[:, i].copy() if batch else int(cn[0, i])) for i, k in enumerate(("rows_ok", "rows_within", "rows_collision_free", "rows"))}
+        if return_device:
+            f = flags.view(3, *shape)
+            with torch.cuda.stream(ctx.stream):
+                cf = f[1] < 0
+            out.update(ok=f[0], first=f[1], within=f[2], collision_free=cf)
+        else:
+            f = ctx.to_host(flags).reshape(3, *shape)
+            out.update(ok=f[0].astype(bool), first=f[1].copy(), within=f[2].astype(bool), collision_free=f[1] < 0)
+        return out
+
+    def _sdf_report(self, Xd, shape, W, t, pair):
+        """cost and minimum clearance of every row under the sphere model; W = the waypoints per row that the entry point takes"""
+        ctx = self.ctx
+        out = ctx.empty((2, int(np.prod(shape))), torch.float64)
+        self._call("edmp_sdf_rows_dev", "edmp_scenes_sdf_rows_dev", shape, ptr(Xd), *shape, W, int(t), _capi.as_pd(pair[0]), _capi.as_pd(pair[1]),
+                   C.c_void_p(out[0].data_ptr()), C.c_void_p(out[1].data_ptr()))
+        h = ctx.to_host(out)
+        return {"cost": h[0].reshape(shape).copy(), "clearance": h[1].reshape(shape).copy()}
+
+
+class IntersectionVolumeGuide(_SlotObject):
     """Same constructor / method signatures as the reference:
 
         guide = IntersectionVolumeGuide(obstacle_config, device, guide_cfgs, batch_size)
@@ -187,18 +297,8 @@ class IntersectionVolumeGuide:
             self._bind()
 
     # ---- binding -----------------------------------------------------------------------------------------------
-    def _bind(self):
+    def _upload(self):
         ctx = self.ctx
-        if ctx.bound_guide is self:
-            return
-        # switch to this object's resident slot; the scene tables / row arrays are rebuilt only if the slot is empty
-        have = ctx.lib.edmp_guide_slot(ctx.h, self._slot)
-        if have < 0:
-            _capi.check(have, "edmp_guide_slot")
-        if have == 1:
-            ctx.bound_guide = self
-            return
-        ctx.bound_guide = None
         no = self.obstacle_config.shape[0]
         _capi.check(
             ctx.lib.edmp_scene_set(ctx.h, _capi.as_pd(self.obstacle_config), no, _capi.as_pd(self._cls_clr), _capi.as_pd(self._cls_exp),
@@ -209,7 +309,6 @@ class IntersectionVolumeGuide:
         self._set_rows(self._sched)
         if self._kinds is not None:
             _capi.check(ctx.lib.edmp_scene_set_shapes(ctx.h, _capi.as_pi32(self._kinds), no), "edmp_scene_set_shapes")
-        ctx.bound_guide = self  # only a completely built object counts as bound
 
     def _check_kinds(self, kinds):
         k = np.ascontiguousarray(np.asarray(kinds, dtype=np.int32).reshape(-1))
@@ -247,6 +346,12 @@ class IntersectionVolumeGuide:
         d, ctx = self._sdf, self.ctx
         _capi.check(ctx.lib.edmp_sdf_set(ctx.h, _capi.as_pf(d["spheres"]), int(d["spheres"].shape[0]), _capi.as_pi32(d["rows"]), _capi.as_pd(d["margin"]),
                                          _capi.as_pd(d["smooth"]), self.batch_size, int(d["margin"].shape[1])), "edmp_sdf_set")
+
+    def _sdf_host(self):
+        if self._sdf is not None:
+            return False
+        self._sdf = sdf_tables(self.guide_cfgs, self.batch_size, self.T, self._half, self._spheres)
+        return True
 
     # ---- reference API -----------------------------------------------------------------------------------------
     def define_obstacles(self, obstacle_config=None, t=0, batch_size=None):
@@ -308,8 +413,7 @@ class IntersectionVolumeGuide:
         ctx = self.ctx
         ji = ctx.to_dev(np.asarray(joint_input, dtype=np.float64), torch.float64)
         B, L = ji.shape[0], ji.shape[2]
-        s = np.ascontiguousarray(np.asarray(start, dtype=np.float64).reshape(7))
-        g = np.ascontiguousarray(np.asarray(goal, dtype=np.float64).reshape(7))
+        s, g = _pair7(start, goal)
         out = ctx.empty((B, 7, L), torch.float64)
         _capi.check(ctx.lib.edmp_guide_gradient_dev(ctx.h, ptr(ji), B, L, _capi.as_pd(s), _capi.as_pd(g), int(t), ptr(out), None), "edmp_guide_gradient_dev")
         return ctx.to_host(out)
@@ -320,43 +424,18 @@ class IntersectionVolumeGuide:
         goal and over the spheres of (distance to the nearest obstacle - radius)}.  t = 0: margin 0, any n (the rows' smoothness weights
         only when n is the guide's batch); t >= 1: the rows' own margin at step t, n = the guide's batch.  A guide built without SDF
         rows and without ``spheres`` uses the default sphere model."""
-        lazy = self._sdf is None
-        if lazy:
-            self._sdf = sdf_tables(self.guide_cfgs, self.batch_size, self.T, self._half, self._spheres)
-        self._bind()
-        if lazy:  # (a resident slot was bound without its rows being set again)
-            self._set_sdf()
-        ctx = self.ctx
-        if isinstance(trajectories, torch.Tensor) and trajectories.is_cuda:
-            X = ctx.adopt(trajectories.to(torch.float64).contiguous())
-        else:
-            X = ctx.to_dev(np.asarray(trajectories, dtype=np.float64), torch.float64)
+        self._bind_sdf()
+        X = self._rows_f64(trajectories)
         if X.dim() != 3 or X.shape[1] != 7:
             raise ValueError(f"trajectories must be (n, 7, L), got {tuple(X.shape)}")
-        n, L = X.shape[0], X.shape[2]
-        s = np.ascontiguousarray(np.asarray(start, dtype=np.float64).reshape(7))
-        g = np.ascontiguousarray(np.asarray(goal, dtype=np.float64).reshape(7))
-        out = ctx.empty((2, n), torch.float64)
-        _capi.check(ctx.lib.edmp_sdf_rows_dev(ctx.h, ptr(X), n, L, int(t), _capi.as_pd(s), _capi.as_pd(g), C.c_void_p(out[0].data_ptr()),
-                                              C.c_void_p(out[1].data_ptr())), "edmp_sdf_rows_dev")
-        h = ctx.to_host(out)
-        return {"cost": h[0].copy(), "clearance": h[1].copy()}
+        return self._sdf_report(X, (X.shape[0],), X.shape[2], t, _pair7(start, goal))
 
     def row_swept_volumes(self, start, goal, trajectories):
         """(B,) f32 t=0 swept volume per row and the argmin (first on ties)."""
         self._bind()
-        ctx = self.ctx
-        if isinstance(trajectories, torch.Tensor) and trajectories.is_cuda:
-            X = ctx.adopt(trajectories.to(torch.float64).contiguous())
-        else:
-            X = ctx.to_dev(np.asarray(trajectories, dtype=np.float64), torch.float64)
-        B, N = X.shape[0], X.shape[2]
-        s = np.ascontiguousarray(np.asarray(start, dtype=np.float64).reshape(7))
-        g = np.ascontiguousarray(np.asarray(goal, dtype=np.float64).reshape(7))
-        vols = ctx.empty((B,), torch.float32)
-        idx = C.c_int()
-        _capi.check(ctx.lib.edmp_row_swept_volumes_dev(ctx.h, ptr(X), B, N, _capi.as_pd(s), _capi.as_pd(g), ptr(vols), C.byref(idx)), "edmp_row_swept_volumes_dev")
-        return ctx.to_host(vols), idx.value
+        X = self._rows_f64(trajectories)
+        vols, idx = self._swept(X, (X.shape[0],), X.shape[2], _pair7(start, goal), True)
+        return self.ctx.to_host(vols), int(idx[0])
 
     def success_rows(self, trajectories, substeps: int = 4, return_device: bool = False):
         """Geometric success of EVERY row (edmp_success_rows_dev; stands for RobotEnvironment.benchmark_trajectory,
@@ -367,28 +446,10 @@ class IntersectionVolumeGuide:
         (lib/environment.py:659-661, 672); ``ok`` = collision_free AND within, the stricter flag.  With return_device the per-row
         arrays stay device tensors (ok / first / within int32, collision_free bool)."""
         self._bind()
-        ctx = self.ctx
-        if isinstance(trajectories, torch.Tensor) and trajectories.is_cuda:
-            X = ctx.adopt(trajectories.to(torch.float64).contiguous())
-        else:
-            X = ctx.to_dev(np.asarray(trajectories, dtype=np.float64), torch.float64)
+        X = self._rows_f64(trajectories)
         if X.dim() != 3 or X.shape[1] != 7:
             raise ValueError(f"trajectories must be (B, 7, N), got {tuple(X.shape)}")
-        B, N = X.shape[0], X.shape[2]
-        flags = ctx.empty((3, B), torch.int32)
-        counts = (C.c_int32 * 4)()
-        dh = np.ascontiguousarray(franka.dh_table_f64())
-        _capi.check(ctx.lib.edmp_success_rows_dev(ctx.h, ptr(X), B, N, int(substeps), _capi.as_pd(dh), C.c_void_p(flags[0].data_ptr()),
-                                                  C.c_void_p(flags[1].data_ptr()), C.c_void_p(flags[2].data_ptr()), counts), "edmp_success_rows_dev")
-        out = dict(rows_ok=int(counts[0]), rows_within=int(counts[1]), rows_collision_free=int(counts[2]), rows=int(counts[3]))
-        if return_device:
-            with torch.cuda.stream(ctx.stream):
-                cf = flags[1] < 0
-            out.update(ok=flags[0], first=flags[1], within=flags[2], collision_free=cf)
-        else:
-            f = ctx.to_host(flags)
-            out.update(ok=f[0].astype(bool), first=f[1].copy(), within=f[2].astype(bool), collision_free=f[1] < 0)
-        return out
+        return self._success(X, (X.shape[0],), X.shape[2], substeps, return_device)
 
     def metrics_rows(self, trajectories, dt: float = 0.1, return_device: bool = False):
         """evaluation.batch_metrics on this guide's context: path lengths and SPARC of EVERY row (edmp_metrics_rows_dev; stands for
@@ -410,25 +471,10 @@ class IntersectionVolumeGuide:
         if prefer not in ("shortest", "smoothest"):
             raise ValueError(f"prefer must be None, 'shortest' or 'smoothest', got {prefer!r}")
         self._bind()
-        ctx = self.ctx
-        if isinstance(trajectories, torch.Tensor) and trajectories.is_cuda:
-            X = ctx.adopt(trajectories.to(torch.float64).contiguous())
-        else:
-            X = ctx.to_dev(np.asarray(trajectories, dtype=np.float64), torch.float64)
-        B, N = X.shape[0], X.shape[2]
-        s = np.ascontiguousarray(np.asarray(start, dtype=np.float64).reshape(7))
-        g = np.ascontiguousarray(np.asarray(goal, dtype=np.float64).reshape(7))
-        vols = ctx.empty((B,), torch.float32)
-        _capi.check(ctx.lib.edmp_row_swept_volumes_dev(ctx.h, ptr(X), B, N, _capi.as_pd(s), _capi.as_pd(g), ptr(vols), None), "edmp_row_swept_volumes_dev")
-        met = self.metrics_rows(X, return_device=True)
-        with torch.cuda.stream(ctx.stream):
-            key = met["joint_path_length"] if prefer == "shortest" else torch.neg(met["joint_sparc"])  # SPARC <= 0: closest to 0 = largest
-        idx = C.c_int()
-        _capi.check(ctx.lib.edmp_select_row_dev(ctx.h, ptr(vols), ptr(key), B, C.c_double(float(volume_trust_region)), C.byref(idx)), "edmp_select_row_dev")
-        with torch.cuda.stream(ctx.stream):
-            m = torch.stack([met[k] for k in met])
-        mh = ctx.to_host(m)
-        return idx.value, ctx.to_host(vols), {k: mh[i].copy() for i, k in enumerate(met)}
+        X = self._rows_f64(trajectories)
+        vols, _ = self._swept(X, (X.shape[0],), X.shape[2], _pair7(start, goal), False)
+        idx, vh, met = self._pick(X, vols, (X.shape[0],), prefer, volume_trust_region)
+        return int(idx[0]), vh, met
 
     def choose_best_trajectory(self, start, goal, trajectories, *, prefer=None, volume_trust_region: float = 0.0008):
         """lib/guide.py:637-653; the keyword `prefer` (an extension, see select_row) breaks the tie among near-minimal rows."""
@@ -485,7 +531,7 @@ def scene_batch_tables(scenes):
     return out
 
 
-class SceneBatch:
+class SceneBatch(_SlotObject):
     """S per-scene guides (IntersectionVolumeGuide, one context, equal batch_size and T, one robot) as ONE guide object of the
     library: scene s owns rows [s*B, (s+1)*B) of a (S*B, 7, N) run (Diffusion.denoise_guided_scenes).  The per-scene guides stay
     what they were and may be unbound (IntersectionVolumeGuide(..., bind=False)): the batch reads their host tables only and lives in
@@ -543,17 +589,8 @@ class SceneBatch:
                 [g._kinds if g._kinds is not None else np.zeros(g.obstacle_config.shape[0], dtype=np.int32) for g in guides]).astype(np.int32))
         self._bind()
 
-    def _bind(self):
+    def _upload(self):
         ctx = self.ctx
-        if ctx.bound_guide is self:
-            return
-        have = ctx.lib.edmp_guide_slot(ctx.h, self._slot)
-        if have < 0:
-            _capi.check(have, "edmp_guide_slot")
-        if have == 1:
-            ctx.bound_guide = self
-            return
-        ctx.bound_guide = None
         tb, g0 = self.tables, self.guides[0]
         _capi.check(
             ctx.lib.edmp_scene_batch_set(ctx.h, self.n_scenes, _capi.as_pi32(tb["n_obstacles"]), _capi.as_pd(tb["obstacle_config"]),
@@ -570,7 +607,6 @@ class SceneBatch:
             self._set_sdf()
         if self._kinds is not None:
             _capi.check(ctx.lib.edmp_scene_batch_set_shapes(ctx.h, _capi.as_pi32(self._kinds), int(self._kinds.shape[0])), "edmp_scene_batch_set_shapes")
-        ctx.bound_guide = self
 
     @property
     def has_sdf_rows(self):
@@ -587,6 +623,13 @@ class SceneBatch:
         rows, margin, smooth = tb["sdf_rows"], tb["sdf_margin"], tb["smoothness"]
         _capi.check(ctx.lib.edmp_scene_batch_set_sdf(ctx.h, _capi.as_pf(self._spheres), int(self._spheres.shape[0]), _capi.as_pi32(rows), _capi.as_pd(margin),
                                                      _capi.as_pd(smooth), self.n_scenes, self.batch_size, self.T), "edmp_scene_batch_set_sdf")
+
+    def _sdf_host(self):
+        if self._spheres is not None:
+            return False
+        g0 = self.guides[0]
+        self._spheres = sdf_tables({}, g0.batch_size, g0.T, g0._half, g0._spheres)["spheres"]
+        return True
 
     # ---- before the run: the IK-goal filter of every scene ---------------------------------------------------------------
     def filter_goals(self, starts, goals, volume_trust_region: float = 0.0008, counts=None):
@@ -647,33 +690,15 @@ class SceneBatch:
         if not ((len(shape) == 4 and shape[:3] == (S, B, 7)) or (len(shape) == 3 and shape[:2] == (S * B, 7))):
             raise ValueError(f"trajectories must be ({S}, {B}, 7, N) or ({S * B}, 7, N), got {tuple(shape)}")
         N = int(shape[-1])
-        if isinstance(X, torch.Tensor) and X.is_cuda:
-            Xd = self.ctx.adopt(X.to(torch.float64).contiguous())
-        else:
-            Xd = self.ctx.to_dev(X if isinstance(X, torch.Tensor) else np.asarray(X, dtype=np.float64), torch.float64)
-        return Xd.reshape(S * B, 7, N), N
-
-    def _pairs(self, starts, goals):
-        out = []
-        for name, v in (("starts", starts), ("goals", goals)):
-            if v is None:
-                raise ValueError(f"{name} is required: ({self.n_scenes}, 7)")
-            a = np.ascontiguousarray(np.asarray(v, dtype=np.float64))
-            if a.shape != (self.n_scenes, 7):
-                raise ValueError(f"{name} must be ({self.n_scenes}, 7), got {a.shape}")
-            out.append(a)
-        return out
+        return self._rows_f64(X).reshape(S * B, 7, N), N
 
     def _volumes(self, starts, goals, X, want_index):
-        s, g = self._pairs(starts, goals)
+        pair = _pairs(self.n_scenes, starts, goals)
         Xd, N = self._state(X)
         self._bind()
-        ctx, S, B = self.ctx, self.n_scenes, self.batch_size
-        vols = ctx.empty((S * B,), torch.float32)
-        idx = (C.c_int * S)() if want_index else None
-        _capi.check(ctx.lib.edmp_scenes_swept_volumes_dev(ctx.h, ptr(Xd), S, B, N, _capi.as_pd(s), _capi.as_pd(g), ptr(vols), idx), "edmp_scenes_swept_volumes_dev")
-        Xd.record_stream(ctx.stream)
-        return Xd, vols, (np.array(idx[:], dtype=np.int64) if want_index else None)
+        vols, idx = self._swept(Xd, (self.n_scenes, self.batch_size), N, pair, want_index)
+        Xd.record_stream(self.ctx.stream)
+        return Xd, vols, idx
 
     def row_swept_volumes(self, starts, goals, trajectories):
         """per scene what IntersectionVolumeGuide.row_swept_volumes gives: ((S, B) f32 t = 0 swept volumes, (S,) arg-min inside the scene)"""
@@ -690,17 +715,7 @@ class SceneBatch:
         Xd, vols, idx = self._volumes(starts, goals, trajectories, prefer is None)
         if prefer is None:
             return idx, ctx.to_host(vols).reshape(S, B), None
-        from .evaluation import metrics_rows_on
-
-        met = metrics_rows_on(ctx, Xd, return_device=True)
-        with torch.cuda.stream(ctx.stream):
-            key = met["joint_path_length"] if prefer == "shortest" else torch.neg(met["joint_sparc"])  # SPARC <= 0: closest to 0 = largest
-        pick = (C.c_int * S)()
-        _capi.check(ctx.lib.edmp_scenes_select_rows_dev(ctx.h, ptr(vols), ptr(key), S, B, C.c_double(float(volume_trust_region)), pick), "edmp_scenes_select_rows_dev")
-        with torch.cuda.stream(ctx.stream):
-            m = torch.stack([met[k] for k in met])
-        mh = ctx.to_host(m)
-        return np.array(pick[:], dtype=np.int64), ctx.to_host(vols).reshape(S, B), {k: mh[i].reshape(S, B).copy() for i, k in enumerate(met)}
+        return self._pick(Xd, vols, (S, B), prefer, volume_trust_region)
 
     def choose_best_trajectories(self, starts, goals, trajectories, *, prefer=None, volume_trust_region: float = 0.0008):
         """choose_best_trajectory (lib/guide.py:637-653) for every scene: (S, 7, N), in the kind of array `trajectories` is"""
@@ -716,23 +731,7 @@ class SceneBatch:
         rows_ok, rows_within, rows_collision_free, rows as (S,) int arrays, one entry per scene."""
         Xd, N = self._state(trajectories)
         self._bind()
-        ctx, S, B = self.ctx, self.n_scenes, self.batch_size
-        flags = ctx.empty((3, S * B), torch.int32)
-        counts = (C.c_int32 * (4 * S))()
-        dh = np.ascontiguousarray(franka.dh_table_f64())
-        _capi.check(ctx.lib.edmp_scenes_success_rows_dev(ctx.h, ptr(Xd), S, B, N, int(substeps), _capi.as_pd(dh), C.c_void_p(flags[0].data_ptr()),
-                                                         C.c_void_p(flags[1].data_ptr()), C.c_void_p(flags[2].data_ptr()), counts), "edmp_scenes_success_rows_dev")
-        cn = np.array(counts[:], dtype=np.int64).reshape(S, 4)
-        out = dict(rows_ok=cn[:, 0].copy(), rows_within=cn[:, 1].copy(), rows_collision_free=cn[:, 2].copy(), rows=cn[:, 3].copy())
-        if return_device:
-            f = flags.view(3, S, B)
-            with torch.cuda.stream(ctx.stream):
-                cf = f[1] < 0
-            out.update(ok=f[0], first=f[1], within=f[2], collision_free=cf)
-        else:
-            f = ctx.to_host(flags).reshape(3, S, B)
-            out.update(ok=f[0].astype(bool), first=f[1].copy(), within=f[2].astype(bool), collision_free=f[1] < 0)
-        return out
+        return self._success(Xd, (self.n_scenes, self.batch_size), N, substeps, return_device)
 
     def sdf_rows(self, trajectories, starts, goals, t=0):
         """IntersectionVolumeGuide.sdf_rows for every scene (edmp_scenes_sdf_rows_dev): cost and minimum clearance of EVERY row of the
@@ -740,19 +739,9 @@ class SceneBatch:
         start / goal pair -> {"cost": (S, B) f64, "clearance": (S, B) f64}; scene s's values are what guides[s].sdf_rows gives for
         X[s][:, :, 1:-1].  t = 0: margin 0; t >= 1: the rows' own margins at step t.  A batch built without SDF rows uses scene 0's
         sphere model (its ``spheres``, else the default of the link boxes) with margin 0 and smoothness 0 where the members bring none."""
-        s, g = self._pairs(starts, goals)
+        pair = _pairs(self.n_scenes, starts, goals)
         Xd, N = self._state(trajectories)
-        lazy = self._spheres is None
-        if lazy:
-            g0 = self.guides[0]
-            self._spheres = sdf_tables({}, g0.batch_size, g0.T, g0._half, g0._spheres)["spheres"]
-        self._bind()
-        if lazy:  # (a resident slot was bound without its table)
-            self._set_sdf()
-        ctx, S, B = self.ctx, self.n_scenes, self.batch_size
-        out = ctx.empty((2, S * B), torch.float64)
-        _capi.check(ctx.lib.edmp_scenes_sdf_rows_dev(ctx.h, ptr(Xd), S, B, N, int(t), _capi.as_pd(s), _capi.as_pd(g), C.c_void_p(out[0].data_ptr()),
-                                                     C.c_void_p(out[1].data_ptr())), "edmp_scenes_sdf_rows_dev")
-        Xd.record_stream(ctx.stream)
-        h = ctx.to_host(out)
-        return {"cost": h[0].reshape(S, B).copy(), "clearance": h[1].reshape(S, B).copy()}
+        self._bind_sdf()
+        out = self._sdf_report(Xd, (self.n_scenes, self.batch_size), N, t, pair)
+        Xd.record_stream(self.ctx.stream)
+        return out
