@@ -1,5 +1,5 @@
-// guide.h — the per-scene guide object shared by guide.hip (tables, cost / gradient kernels) and success.hip (the
-// geometric success check over the finished batch).
+// guide.h — the per-scene guide object shared by guide.hip (tables, cost / gradient kernels), sdf.hip and success.hip (the
+// geometric success check over the finished batch).  The chain arithmetic behind RobotConst is chain.h.
 #pragma once
 #include "common.h"
 

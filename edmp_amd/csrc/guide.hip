@@ -14,6 +14,7 @@
 //     corner of every AABB face, with torch's sub-gradient conventions: first index on corner ties
 //     (torch.min/max(dim)), half/half on elementwise min/max ties, clamp(min=0) passes gradient at len >= 0.
 #include "common.h"
+#include "chain.h"
 #include "guide.h"
 #include "pick.h"
 
@@ -251,7 +252,7 @@ __global__ __launch_bounds__(256, (SPLIT == 4 ? 4 : 1)) void guide_kernel(Args a
     // instructions - an SGPR operand per instruction, the rest moved into VGPRs - and the loads' latency in the loop: not kept)
     const float* obs = s_obs[(SPLIT == 4 || CAND) ? 0 : wv];
     // SPLIT = 4: this wave's links and the last joint frame it needs
-    const int my_jmax = (SPLIT == 4) ? (wv == 0 ? 2 : wv == 1 ? 4 : 6) : 6;
+    const int my_jmax = (SPLIT == 4) ? wave_last_joint(wv) : 6;
 
     bool sv;
     if (MODE == GM_IV_VOL || CAND) sv = false;
@@ -300,7 +301,8 @@ __global__ __launch_bounds__(256, (SPLIT == 4 ? 4 : 1)) void guide_kernel(Args a
 #pragma unroll
     for (int j = 0; j < 7; ++j) {
         if (SPLIT == 4 && j > my_jmax) break;  // (wave-uniform)
-        // T <- T * DH_j(q_j)                                                              lib/guide.py:45-72, 92
+        // T <- T * DH_j(q_j): chain.h's f32 dh_step, and frame_apply below, as inline text - handing the helpers an address inside this
+        // kernel's by-value RobotConst changes how the whole kernel compiles (packed-f32 pairing, fma counts)    lib/guide.py:45-72, 92
         {
             float sq, cq;
             sq = sinf(q[j]);
@@ -328,7 +330,7 @@ __global__ __launch_bounds__(256, (SPLIT == 4 ? 4 : 1)) void guide_kernel(Args a
         for (int ll = 0; ll < 3; ++ll) {
             if (ll > 0 && j != 6) continue;
             const int l = (ll == 0) ? j : 6 + ll;
-            if (SPLIT == 4 && (l < 3 ? 0 : l < 5 ? 1 : l < 7 ? 2 : 3) != wv) continue;  // another wave's link (wave-uniform)
+            if (SPLIT == 4 && link_wave(l) != wv) continue;  // another wave's link (wave-uniform)
             // link transform = T * static_frame[l]                                          lib/guide.py:350
             float LR[3][3], Lo[3];
 #pragma unroll
@@ -808,13 +810,7 @@ static int scene_tables_set(edmp_ctx* ctx, int S, const int32_t* nos, const doub
     memcpy(g->rc.dh, dh, sizeof(g->rc.dh));
     memcpy(g->rc.sf, static_frames, sizeof(g->rc.sf));
     memcpy(g->rc.he, link_half_extents, sizeof(g->rc.he));
-    const double lo_deg[7] = {-166, -101, -166, -176, -166, -1, -166};
-    const double hi_deg[7] = {166, 101, 166, -4, 166, 215, 166};
-    const double pi = 3.141592653589793;  // == numpy.pi
-    for (int i = 0; i < 7; ++i) {
-        g->rc.qlo[i] = lo_deg[i] * (pi / 180);  // diffusion.py:282-296 evaluates deg*(np.pi/180)
-        g->rc.qhi[i] = hi_deg[i] * (pi / 180);
-    }
+    joint_limits_rad(g->rc.qlo, g->rc.qhi);  // diffusion.py:282-296 evaluates deg*(np.pi/180)
     std::vector<double> sizes(no_tot * 3), obb((size_t)no_tot * 16, 0.0);
     std::vector<float> tf(no_tot * 12);
     for (int o = 0; o < no_tot; ++o) {

@@ -6,7 +6,7 @@
 // redundant): every one reproduces the target pose to the stated tolerances, none is the reference's number.
 //
 // Design: one lane per seed, everything f64, the iteration count fixed inside the kernel.  Per iteration: the chain in modified DH
-// (the dh_apply form of success.hip / metrics.hip) followed by the fixed tool frame; the error e = [p_t - p ; 1/2 sum_k R[:,k] x R_t[:,k]];
+// (dh_step of chain.h) followed by the fixed tool frame; the error e = [p_t - p ; 1/2 sum_k R[:,k] x R_t[:,k]];
 // the geometric 6 x 7 Jacobian from the joint frames' z axes and origins; A = J J^T + lambda^2 I by an unrolled Cholesky factorisation
 // (SPD for lambda > 0), dq = J^T A^-1 e; the step scaled to max|dq| <= max_step and q clamped to the joint limits.  A workgroup is one
 // wave (64 lanes) of ONE target, so the target pose is wave-uniform and a group of a few hundred seeds spreads over many CUs; every
@@ -17,6 +17,7 @@
 #include <cmath>
 
 #include "common.h"
+#include "chain.h"
 
 namespace edmp {
 
@@ -33,13 +34,6 @@ struct IkParams {
     int iters;
     double lambda2, max_step, tol_pos, tol_ang;
 };
-
-// the seven joint rows [a, d, alpha] of the reference's modified-DH table (lib/guide.py:29-35) = franka.DH_A_D_ALPHA
-static const double kIkJointDh[7][3] = {{0, 0.333, 0},         {0, 0, -M_PI / 2},   {0, 0.316, M_PI / 2}, {0.0825, 0, M_PI / 2},
-                                        {-0.0825, 0.384, -M_PI / 2}, {0, 0, M_PI / 2}, {0.088, 0, M_PI / 2}};
-// franka.JOINT_LOWER_DEG / JOINT_UPPER_DEG (diffusion/diffusion.py:282-296), turned into rad as deg * (pi / 180) like franka.joint_limits()
-static const double kIkLowerDeg[7] = {-166.0, -101.0, -166.0, -176.0, -166.0, -1.0, -166.0};
-static const double kIkUpperDeg[7] = {166.0, 101.0, 166.0, -4.0, 166.0, 215.0, 166.0};
 
 // blocks: (n_blocks, 3) int32 {target, first seed (row of the flat arrays), seeds in this block (1..64)}
 __global__ __launch_bounds__(kIkThreads) void ik_solve_kernel(const double* __restrict__ targets, const int32_t* __restrict__ blocks,
@@ -70,32 +64,16 @@ __global__ __launch_bounds__(kIkThreads) void ik_solve_kernel(const double* __re
         for (int j = 0; j < 7; ++j) {
             double sq, cq;
             sincos(q[j], &sq, &cq);
-            const double aa = rb.dh[j][0], dd = rb.dh[j][1], ca = rb.dh[j][2], sa = rb.dh[j][3];
-            const double D[3][4] = {{cq, -sq, 0.0, aa}, {sq * ca, cq * ca, -sa, -sa * dd}, {sq * sa, cq * sa, ca, ca * dd}};
-            double Rn[3][3], on[3];
+            dh_step(R, o, sq, cq, rb.dh[j]);
 #pragma unroll
             for (int a = 0; a < 3; ++a) {
-#pragma unroll
-                for (int b = 0; b < 3; ++b) Rn[a][b] = R[a][0] * D[0][b] + R[a][1] * D[1][b] + R[a][2] * D[2][b];
-                on[a] = R[a][0] * D[0][3] + R[a][1] * D[1][3] + R[a][2] * D[2][3] + o[a];
-            }
-#pragma unroll
-            for (int a = 0; a < 3; ++a) {
-#pragma unroll
-                for (int b = 0; b < 3; ++b) R[a][b] = Rn[a][b];
-                o[a] = on[a];
-                z[j][a] = Rn[a][2];
-                p[j][a] = on[a];
+                z[j][a] = R[a][2];
+                p[j][a] = o[a];
             }
         }
         // the tool frame
         double Re[3][3], pe[3];
-#pragma unroll
-        for (int a = 0; a < 3; ++a) {
-#pragma unroll
-            for (int b = 0; b < 3; ++b) Re[a][b] = R[a][0] * rb.tool[b] + R[a][1] * rb.tool[4 + b] + R[a][2] * rb.tool[8 + b];
-            pe[a] = R[a][0] * rb.tool[3] + R[a][1] * rb.tool[7] + R[a][2] * rb.tool[11] + o[a];
-        }
+        frame_apply(R, o, rb.tool, Re, pe);
         // error: position, and 1/2 sum_k Re[:,k] x Rt[:,k] (= sin(angle) * axis, world frame)
         double e[6];
         e[0] = pt[0] - pe[0];
@@ -288,14 +266,8 @@ extern "C" int edmp_ik_solve_dev(edmp_ctx* ctx, const double* targets, int T, co
                      "edmp_ik_solve_dev: target %d: the rotation is not orthonormal to 1e-9 (|R^T R - I| = %g) or is a reflection", t, worst);
     }
     IkRobot rb;
-    for (int j = 0; j < 7; ++j) {
-        rb.dh[j][0] = kIkJointDh[j][0];
-        rb.dh[j][1] = kIkJointDh[j][1];
-        rb.dh[j][2] = std::cos(kIkJointDh[j][2]);
-        rb.dh[j][3] = std::sin(kIkJointDh[j][2]);
-        rb.qlo[j] = kIkLowerDeg[j] * (M_PI / 180);
-        rb.qhi[j] = kIkUpperDeg[j] * (M_PI / 180);
-    }
+    joint_dh64(nullptr, rb.dh);
+    joint_limits_rad(rb.qlo, rb.qhi);
     for (int i = 0; i < 12; ++i) rb.tool[i] = tool[i];
     const IkParams pr = {iters, lambda * lambda, max_step, tol_pos, tol_ang};
     // the block table: every block is one wave of one target

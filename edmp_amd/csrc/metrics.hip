@@ -20,6 +20,7 @@
 // Every sum runs in one fixed order that depends on the row's own data only: results are bit-identical between runs, for any B and
 // any position of the row in the batch.  No floating-point atomics.
 #include "common.h"
+#include "chain.h"
 #include "guide.h"
 #include "pick.h"
 
@@ -37,34 +38,10 @@ constexpr int kMetricsMaxNfft = 2048;           // 2^(ceil(log2 128) + 4)
 constexpr int kMetricsThreads = kPickThreads;  // (block_pick reduces over a workgroup of this size)
 constexpr int kDftBins = 4;  // bins a thread accumulates side by side (1024 bins at N = 50: one pass)
 
-// rows 8-10 of the reference's modified-DH table [a, d, alpha, theta] (lib/guide.py:36-38) = evaluation.EE_STATIC_DH
-static const double kEeStaticDh[3][4] = {{0.0, 0.107, 0.0, 0.0}, {0.0, 0.0, 0.0, -M_PI / 4}, {0.0, 0.1034, 0.0, 0.0}};
-// the seven joint rows [a, d, alpha] of the same table (lib/guide.py:29-35), used when the caller passes no dh_f64
-static const double kJointDh[7][3] = {{0, 0.333, 0},         {0, 0, -M_PI / 2},   {0, 0.316, M_PI / 2}, {0.0825, 0, M_PI / 2},
-                                      {-0.0825, 0.384, -M_PI / 2}, {0, 0, M_PI / 2}, {0.088, 0, M_PI / 2}};
-
 struct Chain64 {
     double dh[7][4];  // a, d, cos(alpha), sin(alpha)
-    double ee[3][6];  // a, d, cos(alpha), sin(alpha), cos(theta), sin(theta)
+    double ee[3][6];  // a, d, cos(alpha), sin(alpha), cos(theta), sin(theta): rows 8-10 of the table (chain.h: kEeStaticDh)
 };
-
-// (R | o) <- (R | o) * DH(a, d, alpha, q), modified DH as in success.hip
-__device__ __forceinline__ void dh_apply(double R[3][3], double o[3], double cq, double sq, double aa, double dd, double ca, double sa) {
-    const double D[3][4] = {{cq, -sq, 0.0, aa}, {sq * ca, cq * ca, -sa, -sa * dd}, {sq * sa, cq * sa, ca, ca * dd}};
-    double Rn[3][3], on[3];
-#pragma unroll
-    for (int a = 0; a < 3; ++a) {
-#pragma unroll
-        for (int b = 0; b < 3; ++b) Rn[a][b] = R[a][0] * D[0][b] + R[a][1] * D[1][b] + R[a][2] * D[2][b];
-        on[a] = R[a][0] * D[0][3] + R[a][1] * D[1][3] + R[a][2] * D[2][3] + o[a];
-    }
-#pragma unroll
-    for (int a = 0; a < 3; ++a) {
-#pragma unroll
-        for (int b = 0; b < 3; ++b) R[a][b] = Rn[a][b];
-        o[a] = on[a];
-    }
-}
 
 __device__ __forceinline__ double wave_max(double v) {
 #pragma unroll
@@ -105,10 +82,10 @@ __global__ __launch_bounds__(kMetricsThreads) void metrics_rows_kernel(const dou
         for (int j = 0; j < 7; ++j) {
             double sq, cq;
             sincos(xr[j * N + i], &sq, &cq);
-            dh_apply(R, o, cq, sq, ch.dh[j][0], ch.dh[j][1], ch.dh[j][2], ch.dh[j][3]);
+            dh_step(R, o, sq, cq, ch.dh[j]);  // (chain.h)
         }
 #pragma unroll 1
-        for (int j = 0; j < 3; ++j) dh_apply(R, o, ch.ee[j][4], ch.ee[j][5], ch.ee[j][0], ch.ee[j][1], ch.ee[j][2], ch.ee[j][3]);
+        for (int j = 0; j < 3; ++j) dh_step(R, o, ch.ee[j][5], ch.ee[j][4], ch.ee[j]);
         s_p[i][0] = o[0];
         s_p[i][1] = o[1];
         s_p[i][2] = o[2];
@@ -259,16 +236,7 @@ extern "C" int edmp_metrics_rows_dev(edmp_ctx* ctx, const double* X_dev, int B, 
     const double fs = 1.0 / dt, step = fs / (double)nfft;
     EDMP_REQUIRE(nfft <= kMetricsMaxNfft && std::isfinite(fs) && step > 0.0, "edmp_metrics_rows_dev: dt = %g gives no usable frequency axis", dt);
     Chain64 ch;
-    for (int j = 0; j < 7; ++j) {
-        if (dh_f64) {
-            for (int k = 0; k < 4; ++k) ch.dh[j][k] = dh_f64[j * 4 + k];
-        } else {
-            ch.dh[j][0] = kJointDh[j][0];
-            ch.dh[j][1] = kJointDh[j][1];
-            ch.dh[j][2] = std::cos(kJointDh[j][2]);
-            ch.dh[j][3] = std::sin(kJointDh[j][2]);
-        }
-    }
+    joint_dh64(dh_f64, ch.dh);
     for (int j = 0; j < 3; ++j) {
         ch.ee[j][0] = kEeStaticDh[j][0];
         ch.ee[j][1] = kEeStaticDh[j][1];

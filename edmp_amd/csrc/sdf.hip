@@ -30,6 +30,7 @@
 // smoothness, graw and rowsq are indexed by the global row.  Everything behind the staging is the row's own arithmetic, so a row of
 // scene s computes what it computes on scene s's own guide.  One scene: rps = 0, slice 0 = the whole table.
 #include "common.h"
+#include "chain.h"
 #include "guide.h"
 
 #include <algorithm>
@@ -147,7 +148,7 @@ __device__ __forceinline__ void sdf_row(const SdfArgs& a, const RobotConst& rc) 
 
     const float m = (a.t >= 1) ? (float)a.margin[(size_t)r * a.T + (a.t - 1)] : 0.f;
     const float lam = a.smooth ? (float)a.smooth[r] : 0.f;
-    const int my_jmax = wv == 0 ? 2 : wv == 1 ? 4 : 6;
+    const int my_jmax = wave_last_joint(wv);
 
     // this lane's joint vector: padded waypoint w = lane (0 start, 1..L interior, >= L+1 goal), loaded as guide_kernel loads it
     const int w = lane;
@@ -180,38 +181,19 @@ __device__ __forceinline__ void sdf_row(const SdfArgs& a, const RobotConst& rc) 
 #pragma unroll
     for (int j = 0; j < 7; ++j) {
         if (j > my_jmax) break;  // (wave-uniform)
-        {
-            const float sq = sinf(q[j]), cq = cosf(q[j]);
-            const float aa = rc.dh[j][0], dd = rc.dh[j][1], ca = rc.dh[j][2], sa = rc.dh[j][3];
-            const float D[3][4] = {{cq, -sq, 0.f, aa}, {sq * ca, cq * ca, -sa, -sa * dd}, {sq * sa, cq * sa, ca, ca * dd}};
-            float Rn[3][3], on[3];
+        dh_step(R, o, sinf(q[j]), cosf(q[j]), rc.dh[j]);
 #pragma unroll
-            for (int i = 0; i < 3; ++i) {
-#pragma unroll
-                for (int c = 0; c < 3; ++c) Rn[i][c] = fmaf(R[i][2], D[2][c], fmaf(R[i][1], D[1][c], R[i][0] * D[0][c]));
-                on[i] = fmaf(R[i][2], D[2][3], fmaf(R[i][1], D[1][3], R[i][0] * D[0][3])) + o[i];
-            }
-#pragma unroll
-            for (int i = 0; i < 3; ++i) {
-#pragma unroll
-                for (int c = 0; c < 3; ++c) R[i][c] = Rn[i][c];
-                o[i] = on[i];
-                zax[j][i] = Rn[i][2];
-                org[j][i] = on[i];
-            }
+        for (int i = 0; i < 3; ++i) {
+            zax[j][i] = R[i][2];
+            org[j][i] = o[i];
         }
 #pragma unroll
         for (int ll = 0; ll < 3; ++ll) {
             if (ll > 0 && j != 6) continue;
             const int l = (ll == 0) ? j : 6 + ll;
-            if ((l < 3 ? 0 : l < 5 ? 1 : l < 7 ? 2 : 3) != wv) continue;  // another wave's link (wave-uniform)
+            if (link_wave(l) != wv) continue;  // another wave's link (wave-uniform)
             float LR[3][3], Lo[3];
-#pragma unroll
-            for (int i = 0; i < 3; ++i) {
-#pragma unroll
-                for (int c = 0; c < 3; ++c) LR[i][c] = fmaf(R[i][2], rc.sf[l][8 + c], fmaf(R[i][1], rc.sf[l][4 + c], R[i][0] * rc.sf[l][c]));
-                Lo[i] = fmaf(R[i][2], rc.sf[l][11], fmaf(R[i][1], rc.sf[l][7], R[i][0] * rc.sf[l][3])) + o[i];
-            }
+            frame_apply(R, o, rc.sf[l], LR, Lo);
             const int s1 = a.link_off[l + 1];
             for (int s = a.link_off[l]; s < s1; ++s) {
                 const float* sp = s_sph + s * 4;

@@ -19,6 +19,7 @@
 // colliding configuration of the row is an LDS integer min — deterministic.  All f64: the decision margin of touching /
 // just-separated pairs (1e-9 m in the tests) is far below f32 resolution at arm's length.
 #include "common.h"
+#include "chain.h"
 #include "guide.h"
 
 namespace edmp {
@@ -230,32 +231,14 @@ __global__ __launch_bounds__(256) void success_rows_kernel(const double* __restr
         for (int j = 0; j < 7 && !hit; ++j) {
             double sq, cq;
             sincos(q[j], &sq, &cq);
-            const double aa = rc.dh[j][0], dd = rc.dh[j][1], ca = rc.dh[j][2], sa = rc.dh[j][3];
-            const double D[3][4] = {{cq, -sq, 0.0, aa}, {sq * ca, cq * ca, -sa, -sa * dd}, {sq * sa, cq * sa, ca, ca * dd}};
-            double Rn[3][3], on[3];
-#pragma unroll
-            for (int a = 0; a < 3; ++a) {
-#pragma unroll
-                for (int b = 0; b < 3; ++b) Rn[a][b] = R[a][0] * D[0][b] + R[a][1] * D[1][b] + R[a][2] * D[2][b];
-                on[a] = R[a][0] * D[0][3] + R[a][1] * D[1][3] + R[a][2] * D[2][3] + o[a];
-            }
-#pragma unroll
-            for (int a = 0; a < 3; ++a) {
-#pragma unroll
-                for (int b = 0; b < 3; ++b) R[a][b] = Rn[a][b];
-                o[a] = on[a];
-            }
+            dh_step(R, o, sq, cq, rc.dh[j]);
             const int nl = (j == 6) ? 3 : 1;  // link7, hand and finger ride the last frame               lib/guide.py:93-94
             for (int ll = 0; ll < nl && !hit; ++ll) {
                 const int l = (ll == 0) ? j : 6 + ll;
                 double LR[3][3], Lc[3], he[3];
+                frame_apply(R, o, rc.sf[l], LR, Lc);
 #pragma unroll
-                for (int a = 0; a < 3; ++a) {
-#pragma unroll
-                    for (int b = 0; b < 3; ++b) LR[a][b] = R[a][0] * rc.sf[l][b] + R[a][1] * rc.sf[l][4 + b] + R[a][2] * rc.sf[l][8 + b];
-                    Lc[a] = R[a][0] * rc.sf[l][3] + R[a][1] * rc.sf[l][7] + R[a][2] * rc.sf[l][11] + o[a];
-                    he[a] = rc.he[l][a];
-                }
+                for (int a = 0; a < 3; ++a) he[a] = rc.he[l][a];
                 for (int ob = 0; ob < no && !hit; ++ob) {
                     const double* od = s_ob + ob * 16;
                     hit = s_kind[ob] == 1 ? obb_cylinder_overlap(LR, Lc, he, od) : obb_overlap(LR, Lc, he, od);
@@ -321,6 +304,7 @@ static int ensure_flags(edmp_ctx* ctx, Guide* g, int rows, int quads) {
     return EDMP_OK;
 }
 
+// (no dh_f64: the scene's own f32 table widened, as include/edmp_hip.h promises - not the Franka table of chain.h's joint_dh64)
 static Robot64 robot64_of(const Guide* g, const double* dh_f64) {
     Robot64 rc;
     for (int j = 0; j < 7; ++j)
