@@ -63,6 +63,7 @@ SIGNATURES = {
     "edmp_row_swept_volumes_dev": (_i, [_vp, _vp, _i, _i, _pd, _pd, _vp, C.POINTER(_i)]),
     "edmp_scene_set_shapes": (_i, [_vp, _pi32, _i]),
     "edmp_success_rows_dev": (_i, [_vp, _vp, _i, _i, _i, _pd, _vp, _vp, _vp, _pi32]),
+    "edmp_self_collision_rows_dev": (_i, [_vp, _vp, _i, _i, _i, _pd, _pi32, _vp, _vp]),
     "edmp_metrics_rows_dev": (_i, [_vp, _vp, _i, _i, _d, _pd, _vp]),
     "edmp_select_row_dev": (_i, [_vp, _vp, _vp, _i, _d, C.POINTER(_i)]),
     "edmp_sampler_init": (_i, [_vp, _i, _d]),
@@ -100,6 +101,8 @@ SIGNATURES = {
     "edmp_guide_slot": (_i, [_vp, C.c_uint64]),
     "edmp_argmin_dev": (_i, [_vp, _vp, _i, C.POINTER(C.c_int)]),
     "edmp_sdf_set": (_i, [_vp, _pf, _i, _pi32, _pd, _pd, _i, _i]),
+    "edmp_sdf_set_self": (_i, [_vp, _pi32, _pd, _pd, _i, _i]),
+    "edmp_sdf_self_rows_dev": (_i, [_vp, _vp, _i, _i, _i, _i, _i, _vp, _vp]),
     "edmp_sdf_rows_dev": (_i, [_vp, _vp, _i, _i, _i, _pd, _pd, _vp, _vp]),
     "edmp_scene_batch_set_sdf": (_i, [_vp, _pf, _i, _pi32, _pd, _pd, _i, _i, _i]),
     "edmp_scenes_sdf_rows_dev": (_i, [_vp, _vp, _i, _i, _i, _i, _pd, _pd, _vp, _vp]),

@@ -1,5 +1,6 @@
-// guide.h — the per-scene guide object shared by guide.hip (tables, cost / gradient kernels), sdf.hip and success.hip (the
-// geometric success check over the finished batch).  The chain arithmetic behind RobotConst is chain.h.
+// guide.h — the per-scene guide object shared by guide.hip (tables, cost / gradient kernels), sdf.hip, success.hip (the
+// geometric success check over the finished batch) and selfcol.hip (the robot tables of the self-collision check).  The chain
+// arithmetic behind RobotConst is chain.h.
 #pragma once
 #include "common.h"
 
@@ -59,6 +60,15 @@ struct Guide {
     int sdf_n = 0;                  // SDF rows of the batch (0: the gradient paths launch what they always launched)
     double* sdf_margin = nullptr;   // [B][T]
     double* sdf_smooth = nullptr;   // [B]
+    std::vector<int32_t> sdf_row_h; // [B] host copy of edmp_sdf_set's 0/1 flags (edmp_sdf_set_self checks its weights against it)
+    // self-clearance term of the SDF guide (sdf.hip, edmp_sdf_set_self): belongs to the sphere table; edmp_sdf_set drops it
+    bool self_set = false;          // a pair list is bound (it may be empty)
+    int32_t* self_pairs = nullptr;  // [self_np][4] = sphere s, sphere u (link-sorted indices), link of s, link of u; s ascending, then u
+    int self_np = 0;
+    int32_t* self_rows = nullptr;   // [self_n] indices of the rows whose weight is > 0
+    int self_n = 0;                 // (0: the gradient paths launch what they launched without the term)
+    double* self_weight = nullptr;  // [B]
+    double* self_margin = nullptr;  // [B][T]
 };
 
 // sdf.hip: overwrite graw / rowsq of the bound guide's SDF rows (no SDF rows: nothing is launched)
@@ -80,7 +90,8 @@ inline int ctx_small_ints(edmp_ctx* ctx) {
 //   batch only (EDMP_REQUIRE_SCENE_BATCH: the bound guide came from edmp_scene_batch_set, a batch of ONE scene included, and holds
 //     exactly S scenes x B rows): edmp_scenes_swept_volumes_dev, edmp_scenes_select_rows_dev, edmp_scenes_success_rows_dev,
 //     edmp_scenes_sdf_rows_dev, edmp_scenes_goal_filter_dev, edmp_scene_batch_set_sdf; edmp_scene_batch_set_shapes (its own wording)
-//   either: edmp_rows_set, edmp_scene_read_aabbs, edmp_argmin_dev, edmp_select_row_dev, edmp_metrics_rows_dev (the last three read no guide)
+//   either: edmp_rows_set, edmp_scene_read_aabbs, edmp_argmin_dev, edmp_select_row_dev, edmp_metrics_rows_dev (the last three read no guide),
+//     edmp_self_collision_rows_dev (the robot tables only)
 #define EDMP_REFUSE_SCENE_BATCH(g, what)                                                                                          \
     do {                                                                                                                          \
         if ((g) && (g)->S > 1) {                                                                                                  \

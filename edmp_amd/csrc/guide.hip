@@ -72,7 +72,7 @@ void guide_destroy(edmp_ctx* ctx, Guide* g) {
     for (void* p : {(void*)g->aabb, (void*)g->row_class, (void*)g->method, (void*)g->grad_norm, (void*)g->sched, (void*)g->graw,
                     (void*)g->rowsq, (void*)g->sumsq, (void*)g->startgoal, (void*)g->vol_rows, (void*)g->obb, (void*)g->kind, (void*)g->flags,
                     (void*)g->cls_no, (void*)g->cand_vol, (void*)g->cand_key, (void*)g->sdf_sph, (void*)g->sdf_rows, (void*)g->sdf_margin,
-                    (void*)g->sdf_smooth})
+                    (void*)g->sdf_smooth, (void*)g->self_pairs, (void*)g->self_rows, (void*)g->self_weight, (void*)g->self_margin})
         ctx_release(ctx, p);
     delete g;
 }
@@ -936,6 +936,8 @@ extern "C" int edmp_rows_set(edmp_ctx* ctx, const int32_t* row_class, const floa
     g->rps = rps;
     g->rows_T = T;
     g->sdf_n = g->sdf_ns = 0;  // an SDF table (edmp_sdf_set) belongs to the rows it was set for
+    g->self_n = g->self_np = 0;  // (and its self term with it)
+    g->self_set = false;
     return EDMP_OK;
 }
 

@@ -29,6 +29,19 @@
 // count - no padding, so the first-index rule of a min_o tie is the scene's own - and reads its scene's start / goal pair; margin,
 // smoothness, graw and rowsq are indexed by the global row.  Everything behind the staging is the row's own arithmetic, so a row of
 // scene s computes what it computes on scene s's own guide.  One scene: rps = 0, slice 0 = the whole table.
+//
+// Self-clearance term (sdf_self_kernel, edmp_sdf_set_self): on the same sphere model, centres in f32 by the statements of sdf_row from
+// the same link-sorted table.  For an SDF row r at step t, over the sphere pairs (s, u) with mask[link_s][link_u], link_s < link_u:
+//   d(w; s, u) = ||c_s(q_w) - c_u(q_w)|| - r_s - r_u
+//   self(r)    = weight_r * sum_{w=1..L} sum_{(s,u)} max(0, m_r(t) - d(w; s, u))       m_r(t) = self_margin[r][t - 1] for t >= 1, 0 at t = 0
+// Interior waypoints only: no start / goal pair and nothing of the scene, so the term is the same inside a scene batch.  The hinge is
+// active iff m - d > 0 and a zero norm contributes a zero gradient, as above.  Gradient: with n = (c_s - c_u) / ||c_s - c_u||, a joint at
+// or below link_s's frame moves both centres rigidly and n . (z_i x (c_s - c_u)) is identically zero; only the joints i with
+// frame(link_s) < i <= frame(link_u) contribute, d d / d q_i = -n . (z_i x (c_u - o_i)), so d self / d q_i = weight * n . (z_i x (c_u - o_i))
+// on an active pair.  sdf_self_kernel runs after sdf_guide_kernel over the rows whose weight is > 0, adds this to the row's graw and
+// rewrites rowsq[r] from the final elements as sdf_row forms it.  Every wave walks the whole chain (it needs every z_i, o_i of its lane),
+// the link frames meet in LDS, pair p of the list (s ascending, then u) belongs to wave p % 4, a wave adds its pairs in list order and
+// the four partials are added as ((w0 + w1) + w2) + w3: one order, no atomics.
 #include "common.h"
 #include "chain.h"
 #include "guide.h"
@@ -287,6 +300,185 @@ __device__ __forceinline__ void sdf_row(const SdfArgs& a, const RobotConst& rc) 
 __global__ __launch_bounds__(256, 3) void sdf_guide_kernel(SdfArgs a, RobotConst rc) { sdf_row<false>(a, rc); }
 __global__ __launch_bounds__(256, 4) void sdf_rows_kernel(SdfArgs a, RobotConst rc) { sdf_row<true>(a, rc); }
 
+struct SelfArgs {
+    const double* joints;  // as SdfArgs
+    int ldw, off;
+    int L, t;
+    int do_clip;
+    const int32_t* rows;    // gradient: the rows whose weight is > 0, one workgroup each
+    const double* margin;   // [B][T]; read at t >= 1 only
+    int T;
+    const double* weight;   // [B], or nullptr = 1 (edmp_sdf_self_rows_dev on rows that are not the bound ones)
+    const float* spheres;   // [ns][4] sorted by link
+    const int32_t* pairs;   // [np][4] = s, u, link_s, link_u
+    int np;
+    float* graw;            // gradient: [B][7][L], the row's SDF gradient on entry
+    double* rowsq;
+    double* cost;           // rows: [n]
+    double* clearance;      // rows: [n]
+};
+
+__device__ __forceinline__ void sphere_centre(const float* fr, int lane, const float* sp, float c[3]) {
+    // frame_apply's LR | Lo of the sphere's link, staged as fr[k][lane], k = row * 4 + column; the statements of sdf_row
+#pragma unroll
+    for (int i = 0; i < 3; ++i)
+        c[i] = fmaf(fr[(i * 4 + 2) * 64 + lane], sp[2], fmaf(fr[(i * 4 + 1) * 64 + lane], sp[1], fr[(i * 4) * 64 + lane] * sp[0])) + fr[(i * 4 + 3) * 64 + lane];
+}
+
+// ROWS = false: add the self gradient of row a.rows[blockIdx.x] to graw and rewrite rowsq.  ROWS = true: weighted self cost and the
+// minimum d over interior waypoints and listed pairs of row blockIdx.x (+inf without a pair).
+template <bool ROWS>
+__device__ __forceinline__ void sdf_self_row(const SelfArgs& a, const RobotConst& rc) {
+    __shared__ float s_fr[EDMP_N_LINKS][12][64];  // link frames of every lane's waypoint
+    __shared__ float s_g[3][7][64];               // partials of waves 1..3 (ROWS: [w][0] minimum d)
+    __shared__ double s_c[3][64];                 // ROWS: cost partials of waves 1..3
+    const int lane = threadIdx.x & 63;
+    const int wv = __builtin_amdgcn_readfirstlane(threadIdx.x >> 6);
+    const int r = ROWS ? (int)blockIdx.x : a.rows[blockIdx.x];
+    const int L = a.L;
+    const float m = (a.t >= 1) ? (float)a.margin[(size_t)r * a.T + (a.t - 1)] : 0.f;
+
+    // lane = padded waypoint as in sdf_row; the end lanes repeat an interior waypoint and are not counted
+    const int w = lane;
+    const bool interior = (w >= 1) && (w <= L);
+    float q[7];
+    {
+        const int wi = min(max(w - 1, 0), L - 1);
+#pragma unroll
+        for (int j = 0; j < 7; ++j) {
+            double xd = a.joints[((size_t)r * 7 + j) * a.ldw + a.off + wi];
+            if (a.do_clip) {
+                xd = xd < rc.qlo[j] ? rc.qlo[j] : xd;
+                xd = xd > rc.qhi[j] ? rc.qhi[j] : xd;
+            }
+            q[j] = (float)xd;
+        }
+    }
+
+    float R[3][3] = {{1, 0, 0}, {0, 1, 0}, {0, 0, 1}};
+    float o[3] = {0, 0, 0};
+    float zax[7][3], org[7][3];
+#pragma unroll
+    for (int j = 0; j < 7; ++j) {
+        dh_step(R, o, sinf(q[j]), cosf(q[j]), rc.dh[j]);
+#pragma unroll
+        for (int i = 0; i < 3; ++i) {
+            zax[j][i] = R[i][2];
+            org[j][i] = o[i];
+        }
+#pragma unroll
+        for (int ll = 0; ll < 3; ++ll) {
+            if (ll > 0 && j != 6) continue;
+            const int l = (ll == 0) ? j : 6 + ll;
+            if (link_wave(l) != wv) continue;  // another wave stages this link (wave-uniform)
+            float LR[3][3], Lo[3];
+            frame_apply(R, o, rc.sf[l], LR, Lo);
+#pragma unroll
+            for (int i = 0; i < 3; ++i) {
+#pragma unroll
+                for (int k = 0; k < 3; ++k) s_fr[l][i * 4 + k][lane] = LR[i][k];
+                s_fr[l][i * 4 + 3][lane] = Lo[i];
+            }
+        }
+    }
+    __syncthreads();
+
+    float g[7] = {0, 0, 0, 0, 0, 0, 0};
+    double cacc = 0.0;
+    float dmin = INFINITY;
+    for (int p = wv; p < a.np; p += 4) {  // (wave-uniform: the list entries come by scalar loads)
+        const int s = a.pairs[p * 4], u = a.pairs[p * 4 + 1], ls = a.pairs[p * 4 + 2], lu = a.pairs[p * 4 + 3];
+        const float* sps = a.spheres + s * 4;
+        const float* spu = a.spheres + u * 4;
+        float cs[3], cu[3];
+        sphere_centre(&s_fr[ls][0][0], lane, sps, cs);
+        sphere_centre(&s_fr[lu][0][0], lane, spu, cu);
+        const float dx = cs[0] - cu[0], dy = cs[1] - cu[1], dz = cs[2] - cu[2];
+        const float nrm = sqrtf(fmaf(dz, dz, fmaf(dy, dy, dx * dx)));
+        const float d = nrm - sps[3] - spu[3];
+        const float h = m - d;
+        if (ROWS) {
+            dmin = fminf(dmin, d);
+            if (interior && h > 0.f) cacc += (double)h;
+        } else if (interior && h > 0.f && nrm > 0.f) {
+            const float nx = dx / nrm, ny = dy / nrm, nz = dz / nrm;
+            const int fs = min(ls, 6), fu = min(lu, 6);  // joint frame of a link (hand and finger ride on joint 6)
+#pragma unroll
+            for (int i = 0; i < 7; ++i) {
+                if (i <= fs || i > fu) continue;  // (wave-uniform)
+                const float rx = cu[0] - org[i][0], ry = cu[1] - org[i][1], rz = cu[2] - org[i][2];
+                const float kx = zax[i][1] * rz - zax[i][2] * ry;
+                const float ky = zax[i][2] * rx - zax[i][0] * rz;
+                const float kz = zax[i][0] * ry - zax[i][1] * rx;
+                g[i] += fmaf(nz, kz, fmaf(ny, ky, nx * kx));
+            }
+        }
+    }
+
+    if (wv > 0) {
+        if (ROWS) {
+            s_g[wv - 1][0][lane] = dmin;
+            s_c[wv - 1][lane] = cacc;
+        } else {
+#pragma unroll
+            for (int i = 0; i < 7; ++i) s_g[wv - 1][i][lane] = g[i];
+        }
+    }
+    __syncthreads();
+    if (wv > 0) return;
+    const double wt = a.weight ? a.weight[r] : 1.0;
+    if (ROWS) {
+        cacc = ((cacc + s_c[0][lane]) + s_c[1][lane]) + s_c[2][lane];
+        dmin = fminf(fminf(fminf(dmin, s_g[0][0][lane]), s_g[1][0][lane]), s_g[2][0][lane]);
+        if (!interior) dmin = INFINITY;
+        const double tot = wave_sum(cacc);
+#pragma unroll
+        for (int sft = 32; sft > 0; sft >>= 1) dmin = fminf(dmin, __shfl_xor(dmin, sft, 64));
+        if (lane == 0) {
+            a.cost[r] = wt * tot;
+            a.clearance[r] = (double)dmin;
+        }
+    } else {
+        const float wf = (float)wt;
+        float sq = 0.f;
+#pragma unroll
+        for (int i = 0; i < 7; ++i) {
+            float gi = 0.f;
+            if (interior) {
+                float* dst = a.graw + ((size_t)r * 7 + i) * L + (w - 1);
+                gi = fmaf(wf, ((g[i] + s_g[0][i][lane]) + s_g[1][i][lane]) + s_g[2][i][lane], *dst);
+                *dst = gi;
+            }
+            sq = fmaf(gi, gi, sq);
+        }
+        const double tot = wave_sum((double)sq);
+        if (lane == 0) a.rowsq[r] = tot;
+    }
+}
+
+__global__ __launch_bounds__(256) void sdf_self_kernel(SelfArgs a, RobotConst rc) { sdf_self_row<false>(a, rc); }
+__global__ __launch_bounds__(256) void sdf_self_rows_kernel(SelfArgs a, RobotConst rc) { sdf_self_row<true>(a, rc); }
+
+static void fill_self_args(const Guide* g, SelfArgs& a, const double* joints, int ldw, int off, int L, int t, int do_clip) {
+    a.joints = joints;
+    a.ldw = ldw;
+    a.off = off;
+    a.L = L;
+    a.t = t;
+    a.do_clip = do_clip;
+    a.rows = g->self_rows;
+    a.margin = g->self_margin;
+    a.T = g->rows_T;
+    a.weight = g->self_weight;
+    a.spheres = g->sdf_sph;
+    a.pairs = g->self_pairs;
+    a.np = g->self_np;
+    a.graw = g->graw;
+    a.rowsq = g->rowsq;
+    a.cost = nullptr;
+    a.clearance = nullptr;
+}
+
 static void fill_args(const Guide* g, SdfArgs& a, const double* joints, int ldw, int off, int L, int t, int do_clip) {
     a.joints = joints;
     a.ldw = ldw;
@@ -323,6 +515,12 @@ int sdf_overlay(edmp_ctx* ctx, const double* joints, int ldw, int off, int L, in
     fill_args(g, a, joints, ldw, off, L, t, do_clip);
     hipLaunchKernelGGL(sdf_guide_kernel, dim3(g->sdf_n), dim3(256), 0, ctx->stream, a, g->rc);
     EDMP_HIP_CHECK(hipGetLastError());
+    if (g->self_n > 0 && g->self_np > 0) {  // the self term of the weighted rows, on top of what sdf_guide_kernel left
+        SelfArgs sa;
+        fill_self_args(g, sa, joints, ldw, off, L, t, do_clip);
+        hipLaunchKernelGGL(sdf_self_kernel, dim3(g->self_n), dim3(256), 0, ctx->stream, sa, g->rc);
+        EDMP_HIP_CHECK(hipGetLastError());
+    }
     return EDMP_OK;
 }
 
@@ -376,6 +574,9 @@ static int sdf_table_set(edmp_ctx* ctx, const char* what, const float* spheres, 
     EDMP_HIP_CHECK(hipSetDevice(ctx->device));
     EDMP_HIP_CHECK(hipStreamSynchronize(ctx->stream));  // nothing enqueued still reads the arrays that are replaced
     g->sdf_n = g->sdf_ns = 0;
+    g->self_n = g->self_np = 0;  // the self term belongs to this table: a new table drops it
+    g->self_set = false;
+    g->sdf_row_h.assign(sdf_row, sdf_row + n);
     for (void** p : {(void**)&g->sdf_sph, (void**)&g->sdf_rows, (void**)&g->sdf_margin, (void**)&g->sdf_smooth}) {
         ctx_release(ctx, *p);
         *p = nullptr;
@@ -461,4 +662,96 @@ extern "C" int edmp_scenes_sdf_rows_dev(edmp_ctx* ctx, const double* X_dev, int 
     EDMP_REQUIRE(N >= 3 && N <= 64, "edmp_scenes_sdf_rows_dev: need 3 <= N <= 64 waypoints per row (got %d)", N);
     // the full state with its start / goal columns; rps = B forced, for a batch of ONE scene too (rows / B = 0)
     return sdf_rows(ctx, "edmp_scenes_sdf_rows_dev", X_dev, S, S * B, N, 1, N - 2, t, B, starts, goals, cost_dev, clearance_dev);
+}
+
+// ---- self-clearance term ------------------------------------------------------------------------------------------------------------
+extern "C" int edmp_sdf_set_self(edmp_ctx* ctx, const int32_t* pair_mask, const double* weight, const double* self_margin, int n, int T) {
+    EDMP_REQUIRE(ctx && ctx->guide && ctx->guide->obb && ctx->guide->row_class, "edmp_sdf_set_self: no guide bound (scene and rows first)");
+    Guide* g = ctx->guide;
+    if (g->sdf_ns <= 0) {
+        set_error("edmp_sdf_set_self: call edmp_sdf_set or edmp_scene_batch_set_sdf first (the term is defined on their sphere table)");
+        return EDMP_ERR_STATE;
+    }
+    EDMP_REQUIRE(pair_mask && weight && self_margin, "edmp_sdf_set_self: null argument");
+    EDMP_REQUIRE(n == g->B && T == g->rows_T, "edmp_sdf_set_self: %d rows x %d steps given, edmp_rows_set holds %d x %d", n, T, g->B, g->rows_T);
+    for (int a = 0; a < EDMP_N_LINKS; ++a)
+        for (int b = a + 1; b < EDMP_N_LINKS; ++b)
+            EDMP_REQUIRE(pair_mask[a * EDMP_N_LINKS + b] == 0 || pair_mask[a * EDMP_N_LINKS + b] == 1, "edmp_sdf_set_self: pair_mask[%d][%d] = %d must be 0 or 1", a,
+                         b, (int)pair_mask[a * EDMP_N_LINKS + b]);
+    const int rps = g->is_batch ? g->rps : 0;
+    char where[48];
+    auto row_name = [&](int b) {
+        if (rps) snprintf(where, sizeof(where), "scene %d, row %d", b / rps, b % rps);
+        else snprintf(where, sizeof(where), "row %d", b);
+        return where;
+    };
+    std::vector<int32_t> rows;
+    for (int b = 0; b < n; ++b) {
+        EDMP_REQUIRE(std::isfinite(weight[b]) && weight[b] >= 0.0, "edmp_sdf_set_self: %s: weight %g must be finite and >= 0", row_name(b), weight[b]);
+        if (weight[b] > 0.0) {
+            EDMP_REQUIRE(b < (int)g->sdf_row_h.size() && g->sdf_row_h[b] == 1, "edmp_sdf_set_self: %s: weight %g on a row that is not an SDF row", row_name(b),
+                         weight[b]);
+            rows.push_back(b);
+        }
+    }
+    for (size_t i = 0; i < (size_t)n * T; ++i)
+        EDMP_REQUIRE(std::isfinite(self_margin[i]) && self_margin[i] >= 0.0, "edmp_sdf_set_self: %s, step %d: self_margin %g must be finite and >= 0",
+                     row_name((int)(i / T)), (int)(i % T), self_margin[i]);
+    // the sphere pairs of the masked link pairs, in the order of the link-sorted table: s ascending, then u
+    std::vector<int32_t> pairs;
+    for (int la = 0; la < EDMP_N_LINKS; ++la)
+        for (int s = g->sdf_link_off[la]; s < g->sdf_link_off[la + 1]; ++s)
+            for (int lb = la + 1; lb < EDMP_N_LINKS; ++lb) {
+                if (!pair_mask[la * EDMP_N_LINKS + lb]) continue;
+                for (int u = g->sdf_link_off[lb]; u < g->sdf_link_off[lb + 1]; ++u) pairs.insert(pairs.end(), {s, u, la, lb});
+            }
+    ctx->epoch++;  // a captured whole-run graph holds the launch sequence without the term
+    EDMP_HIP_CHECK(hipSetDevice(ctx->device));
+    EDMP_HIP_CHECK(hipStreamSynchronize(ctx->stream));
+    g->self_n = g->self_np = 0;
+    g->self_set = false;
+    for (void** p : {(void**)&g->self_pairs, (void**)&g->self_rows, (void**)&g->self_weight, (void**)&g->self_margin}) {
+        ctx_release(ctx, *p);
+        *p = nullptr;
+    }
+    if (int rc = ctx_alloc(ctx, (void**)&g->self_pairs, std::max<size_t>(pairs.size(), 4) * sizeof(int32_t))) return rc;
+    if (int rc = ctx_alloc(ctx, (void**)&g->self_rows, std::max<size_t>(rows.size(), 1) * sizeof(int32_t))) return rc;
+    if (int rc = ctx_alloc(ctx, (void**)&g->self_weight, (size_t)n * sizeof(double))) return rc;
+    if (int rc = ctx_alloc(ctx, (void**)&g->self_margin, (size_t)n * T * sizeof(double))) return rc;
+    hipError_t e = hipSuccess;
+    if (!pairs.empty()) e = hipMemcpyAsync(g->self_pairs, pairs.data(), pairs.size() * sizeof(int32_t), hipMemcpyHostToDevice, ctx->stream);
+    if (e == hipSuccess && !rows.empty()) e = hipMemcpyAsync(g->self_rows, rows.data(), rows.size() * sizeof(int32_t), hipMemcpyHostToDevice, ctx->stream);
+    if (e == hipSuccess) e = hipMemcpyAsync(g->self_weight, weight, (size_t)n * sizeof(double), hipMemcpyHostToDevice, ctx->stream);
+    if (e == hipSuccess) e = hipMemcpyAsync(g->self_margin, self_margin, (size_t)n * T * sizeof(double), hipMemcpyHostToDevice, ctx->stream);
+    const hipError_t e2 = hipStreamSynchronize(ctx->stream);  // the host vectors and the caller's arrays may go away after the call
+    EDMP_HIP_CHECK(e);
+    EDMP_HIP_CHECK(e2);
+    g->self_np = (int)(pairs.size() / 4);
+    g->self_n = (int)rows.size();
+    g->self_set = true;
+    return EDMP_OK;
+}
+
+extern "C" int edmp_sdf_self_rows_dev(edmp_ctx* ctx, const double* joints_dev, int n, int ldw, int off, int L, int t, double* cost_dev,
+                                      double* clearance_dev) {
+    EDMP_REQUIRE(ctx && ctx->guide && ctx->guide->obb, "edmp_sdf_self_rows_dev: scene not set");
+    Guide* g = ctx->guide;
+    if (g->sdf_ns <= 0 || !g->self_set) {
+        set_error("edmp_sdf_self_rows_dev: call edmp_sdf_set_self first (the pair mask)");
+        return EDMP_ERR_STATE;
+    }
+    EDMP_REQUIRE(joints_dev && cost_dev && clearance_dev, "edmp_sdf_self_rows_dev: null pointer");
+    EDMP_REQUIRE(n >= 1 && L >= 1 && L + 2 <= 64, "edmp_sdf_self_rows_dev: need n >= 1 and 1 <= L <= 62 waypoints per row (got %d, %d)", n, L);
+    EDMP_REQUIRE(off >= 0 && ldw >= 1 && (int64_t)off + L <= ldw, "edmp_sdf_self_rows_dev: columns %d .. %d outside rows of %d", off, off + L - 1, ldw);
+    EDMP_REQUIRE(t >= 0 && t <= g->rows_T, "edmp_sdf_self_rows_dev: t=%d outside 0..%d", t, g->rows_T);
+    EDMP_REQUIRE(t == 0 || n == g->B, "edmp_sdf_self_rows_dev: t >= 1 reads the rows' margin schedules: %d rows given, %d bound", n, g->B);
+    EDMP_HIP_CHECK(hipSetDevice(ctx->device));
+    SelfArgs a;
+    fill_self_args(g, a, joints_dev, ldw, off, L, t, 0);
+    if (n != g->B) a.weight = nullptr;  // rows that are not the bound ones: weight 1, the bare hinge sum
+    a.cost = cost_dev;
+    a.clearance = clearance_dev;
+    hipLaunchKernelGGL(sdf_self_rows_kernel, dim3(n), dim3(256), 0, ctx->stream, a, g->rc);
+    EDMP_HIP_CHECK(hipGetLastError());
+    return EDMP_OK;
 }

@@ -49,6 +49,21 @@ def success_rate(trajectories, guide, substeps: int = 4) -> dict:
     return r
 
 
+def self_collision_rate(trajectories, guide, substeps: int = 4, pairs=None) -> dict:
+    """every row of a batch (n, 7, N) checked for self-collision on the GPU (guide.self_collision_rows, csrc/selfcol.hip; stands for the
+    `self_collision` metric of the reference's evaluation package, mpinets/metrics.py:278-292): that dict (first, pair, free) plus
+    rows_free, rows and rate = the share of self-collision-free rows.  `guide` may be a guide.SceneBatch with trajectories (S, B, 7, N) or
+    (S*B, 7, N): the per-row arrays are then (S, B), the counts and rates (S,).  ``pairs``: the (9, 9) mask of checked link pairs,
+    default franka.self_collision_pairs()."""
+    r = guide.self_collision_rows(trajectories, substeps=substeps, pairs=pairs)
+    free = np.asarray(r["free"])
+    per_scene = free.ndim == 2
+    r["rows_free"] = free.sum(axis=-1).astype(np.int64) if per_scene else int(free.sum())
+    r["rows"] = np.full(free.shape[0], free.shape[1], dtype=np.int64) if per_scene else int(free.shape[0])
+    r["rate"] = r["rows_free"] / np.maximum(r["rows"], 1)
+    return r
+
+
 # the fixed flange / hand chain behind joint 7: rows 8-10 of the reference's modified-DH table [a, d, alpha, theta]
 # (lib/guide.py:36-38), used only by get_end_effector_transform (lib/guide.py:100-116)
 EE_STATIC_DH = ((0.0, 0.107, 0.0, 0.0), (0.0, 0.0, 0.0, -np.pi / 4), (0.0, 0.1034, 0.0, 0.0))

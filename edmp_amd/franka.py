@@ -30,6 +30,31 @@ DH_A_D_ALPHA = np.array(
 )
 LINK_FRAME = np.array([0, 1, 2, 3, 4, 5, 6, 6, 6], dtype=np.int32)
 
+
+def self_collision_pairs(min_frame_gap: int = 3) -> np.ndarray:
+    """(9, 9) bool mask of the link-box pairs the self-collision check tests (csrc/selfcol.hip); only a < b is read.  The rule: the
+    joint-frame indices of the two links (LINK_FRAME) differ by at least `min_frame_gap`.  The link boxes are AABBs of the meshes, so
+    neighbours overlap by construction: at a frame gap of 0 or 1 in every configuration, at 2 in up to 98 % of them.  The default 3 gives
+    18 pairs: (0, 3..8), (1, 4..8), (2, 5..8), (3, 6..8).  A rule about this box model, not a statement about the real Franka: a caller
+    with better geometry passes a mask of their own."""
+    g = int(min_frame_gap)
+    if g < 0:
+        raise ValueError("min_frame_gap must be >= 0")
+    f = LINK_FRAME.astype(np.int64)
+    m = (f[None, :] - f[:, None]) >= g
+    return m & np.triu(np.ones((N_LINKS, N_LINKS), dtype=bool), 1)
+
+
+def check_pair_mask(pairs=None) -> np.ndarray:
+    """a caller's pair mask as the contiguous (81,) int32 the C ABI takes (None: self_collision_pairs()); entries must be 0 / 1 / bool"""
+    m = self_collision_pairs() if pairs is None else np.asarray(pairs)
+    if m.shape != (N_LINKS, N_LINKS):
+        raise ValueError(f"pairs must be a (9, 9) mask, got shape {m.shape}")
+    if m.dtype != bool and not np.all((m == 0) | (m == 1)):
+        raise ValueError("pairs: mask entries must be 0 or 1")
+    return np.ascontiguousarray(m.astype(np.int32).reshape(-1))
+
+
 _C, _S = 7.07106767e-01, 7.07106795e-01
 _TRANS = [
     (8.71e-05, -3.709035e-02, -6.851545e-02),

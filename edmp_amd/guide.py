@@ -96,11 +96,14 @@ def goal_filter_device_inputs(n_scenes, starts, goals, counts):
     return st, np.ascontiguousarray(cn.astype(np.int32))
 
 
-def sdf_tables(guide_cfgs, batch_size, T, link_half_extents, spheres=None):
+def sdf_tables(guide_cfgs, batch_size, T, link_half_extents, spheres=None, self_pairs=None):
     """Host tables of the sphere signed-distance guide (edmp_sdf_set), checked before anything touches the device: the sphere table
     (n, 5) f32 [link 0..8, centre xyz in the link-box frame, radius] - ``spheres`` or franka.spheres_from_boxes of the link boxes - and
     the row arrays of ``guide_cfgs`` (``sdf_rows`` (B,), ``sdf_margin`` (B, T), ``smoothness`` (B,); a dict without them gives no SDF
-    rows, margin 0 and smoothness 0).  Returns dict(spheres, rows int32, margin f64, smooth f64)."""
+    rows, margin 0 and smoothness 0).  The self-clearance term (edmp_sdf_set_self): ``sdf_self_weight`` (B,) and ``sdf_self_margin`` (B, T) of ``guide_cfgs``
+    (absent: 0), finite and >= 0, a weight > 0 only on an SDF row, and the (9, 9) link-pair mask ``self_pairs`` (None:
+    franka.self_collision_pairs()).  Returns dict(spheres, rows int32, margin f64, smooth f64, self_weight f64, self_margin f64,
+    self_mask (81,) int32)."""
     B, T = int(batch_size), int(T)
     sph = franka.spheres_from_boxes(link_half_extents) if spheres is None else np.asarray(spheres, dtype=np.float32)
     if sph.ndim != 2 or sph.shape[1] != 5:
@@ -122,8 +125,17 @@ def sdf_tables(guide_cfgs, batch_size, T, link_half_extents, spheres=None):
         raise ValueError("sdf_rows: one entry per row, 0 or 1")
     if not (np.isfinite(margin).all() and np.all(margin >= 0) and np.isfinite(smooth).all() and np.all(smooth >= 0)):
         raise ValueError("sdf_margin and smoothness must be finite and >= 0")
+    sw = np.asarray(guide_cfgs["sdf_self_weight"] if "sdf_self_weight" in guide_cfgs else np.zeros(B), dtype=np.float64)
+    sm = np.asarray(guide_cfgs["sdf_self_margin"] if "sdf_self_margin" in guide_cfgs else np.zeros((B, T)), dtype=np.float64)
+    if sw.shape != (B,) or sm.shape != (B, T):
+        raise ValueError(f"sdf_self_weight / sdf_self_margin must be ({B},), ({B}, {T}), got {sw.shape}, {sm.shape}")
+    if not (np.isfinite(sw).all() and np.all(sw >= 0) and np.isfinite(sm).all() and np.all(sm >= 0)):
+        raise ValueError("sdf_self_weight and sdf_self_margin must be finite and >= 0")
+    if np.any((sw > 0) & (rows != 1)):
+        raise ValueError(f"sdf_self_weight: row {int(np.nonzero((sw > 0) & (rows != 1))[0][0])} carries a weight > 0 and is not an SDF row")
     return dict(spheres=np.ascontiguousarray(sph), rows=np.ascontiguousarray(rows.astype(np.int32)), margin=np.ascontiguousarray(margin),
-                smooth=np.ascontiguousarray(smooth))
+                smooth=np.ascontiguousarray(smooth), self_weight=np.ascontiguousarray(sw), self_margin=np.ascontiguousarray(sm),
+                self_mask=franka.check_pair_mask(self_pairs))
 
 
 spheres_from_boxes = franka.spheres_from_boxes
@@ -229,12 +241,52 @@ class _SlotObject:
             out.update(ok=f[0].astype(bool), first=f[1].copy(), within=f[2].astype(bool), collision_free=f[1] < 0)
         return out
 
+    def _self_collision(self, Xd, shape, N, substeps, mask, return_device):
+        """the self-collision dict, per-row arrays `shape`d: first, pair (.., 2) with -1 rows, free.  One entry point for a guide and a
+        batch: the check reads the robot tables only.  mask: franka.check_pair_mask's (81,) int32."""
+        ctx = self.ctx
+        out = ctx.empty((2, int(np.prod(shape))), torch.int32)
+        dh = np.ascontiguousarray(franka.dh_table_f64())
+        _capi.check(ctx.lib.edmp_self_collision_rows_dev(ctx.h, ptr(Xd), int(np.prod(shape)), N, int(substeps), _capi.as_pd(dh), _capi.as_pi32(mask),
+                                                         C.c_void_p(out[0].data_ptr()), C.c_void_p(out[1].data_ptr())), "edmp_self_collision_rows_dev")
+        if return_device:
+            with torch.cuda.stream(ctx.stream):
+                first, code = out[0].view(*shape), out[1].view(*shape)
+                hit = code >= 0
+                pair = torch.where(hit.unsqueeze(-1), torch.stack([code // 9, code % 9], dim=-1), torch.full_like(code, -1).unsqueeze(-1))
+                res = {"first": first, "pair": pair.to(torch.int32), "free": ~hit}
+            ctx.hand_over(out)  # (the caller's torch ops on the results follow this context's stream)
+            return res
+        h = ctx.to_host(out)
+        first, code = h[0].reshape(shape).copy(), h[1].reshape(shape)
+        hit = code >= 0
+        pair = np.where(hit[..., None], np.stack([code // 9, code % 9], axis=-1), -1).astype(np.int32)
+        return {"first": first, "pair": pair, "free": ~hit}
+
     def _sdf_report(self, Xd, shape, W, t, pair):
         """cost and minimum clearance of every row under the sphere model; W = the waypoints per row that the entry point takes"""
         ctx = self.ctx
         out = ctx.empty((2, int(np.prod(shape))), torch.float64)
         self._call("edmp_sdf_rows_dev", "edmp_scenes_sdf_rows_dev", shape, ptr(Xd), *shape, W, int(t), _capi.as_pd(pair[0]), _capi.as_pd(pair[1]),
                    C.c_void_p(out[0].data_ptr()), C.c_void_p(out[1].data_ptr()))
+        h = ctx.to_host(out)
+        return {"cost": h[0].reshape(shape).copy(), "clearance": h[1].reshape(shape).copy()}
+
+
+    def _bind_self(self):
+        """_bind_sdf for the self-clearance report: an object without a weighted row hands its mask over once (all weights 0: the
+        gradient paths launch what they launched)"""
+        self._bind_sdf()
+        if not self._self_on:
+            self._self_on = True
+            self._set_self()
+
+    def _self_report(self, Xd, shape, ldw, off, L, t):
+        """weighted self cost and minimum self clearance of every row; the L interior waypoints at columns off .. of rows of ldw"""
+        ctx = self.ctx
+        out = ctx.empty((2, int(np.prod(shape))), torch.float64)
+        _capi.check(ctx.lib.edmp_sdf_self_rows_dev(ctx.h, ptr(Xd), int(np.prod(shape)), int(ldw), int(off), int(L), int(t), C.c_void_p(out[0].data_ptr()),
+                                                   C.c_void_p(out[1].data_ptr())), "edmp_sdf_self_rows_dev")
         h = ctx.to_host(out)
         return {"cost": h[0].reshape(shape).copy(), "clearance": h[1].reshape(shape).copy()}
 
@@ -262,10 +314,15 @@ class IntersectionVolumeGuide(_SlotObject):
     an optional smoothness pull.  ``spheres`` (n, 5) [link 0..8, centre in the link-box frame, radius] replaces the default
     franka.spheres_from_boxes of the link boxes.  get_gradient and the samplers need nothing else: the SDF rows' gradient is overlaid
     below them.  sdf_rows(...) reports cost and minimum clearance of every row.
+
+    Its self-clearance term: SDF rows with ``guide_cfgs["sdf_self_weight"]`` > 0 (guide_cfg: ``hyperparameters.sdf.self_weight``) are also
+    pushed away from themselves - the spheres of the link pairs that ``self_pairs`` masks ((9, 9), default
+    franka.self_collision_pairs()) are kept ``sdf_self_margin`` apart.  sdf_self_rows(...) reports the term's cost and the minimum self
+    clearance of every row.
     """
 
     def __init__(self, obstacle_config, device, guide_cfgs, batch_size, *, link_mesh_extents=None, mesh_dir=None, obstacle_kinds=None, bind=True,
-                 spheres=None):
+                 spheres=None, self_pairs=None):
         self.ctx = get_context(device)
         self.device = self.ctx.device
         self.guide_cfgs = guide_cfgs
@@ -292,7 +349,9 @@ class IntersectionVolumeGuide(_SlotObject):
         # (datasets/load_test_dataset.py:141-149), so kinds = [0] * num_cuboids + [1] * num_cylinders there.
         self._kinds = None if obstacle_kinds is None else self._check_kinds(obstacle_kinds)
         self._spheres = spheres
-        self._sdf = sdf_tables(guide_cfgs, self.batch_size, self.T, self._half, spheres) if ("sdf_rows" in guide_cfgs or spheres is not None) else None
+        self._self_pairs = franka.check_pair_mask(self_pairs)
+        self._sdf = sdf_tables(guide_cfgs, self.batch_size, self.T, self._half, spheres, self._self_pairs.reshape(9, 9)) if ("sdf_rows" in guide_cfgs or spheres is not None) else None
+        self._self_on = self.has_self_term  # the self table is handed over with the sphere table (sdf_self_rows turns it on too)
         if bind:
             self._bind()
 
@@ -342,15 +401,27 @@ class IntersectionVolumeGuide(_SlotObject):
     def has_sdf_rows(self):
         return self._sdf is not None and bool(self._sdf["rows"].any())
 
+    @property
+    def has_self_term(self):
+        """some SDF row carries a self-clearance weight > 0"""
+        return self._sdf is not None and bool((self._sdf["self_weight"] > 0).any())
+
     def _set_sdf(self):
         d, ctx = self._sdf, self.ctx
         _capi.check(ctx.lib.edmp_sdf_set(ctx.h, _capi.as_pf(d["spheres"]), int(d["spheres"].shape[0]), _capi.as_pi32(d["rows"]), _capi.as_pd(d["margin"]),
                                          _capi.as_pd(d["smooth"]), self.batch_size, int(d["margin"].shape[1])), "edmp_sdf_set")
+        if self._self_on:  # the self term belongs to the sphere table: edmp_sdf_set dropped it
+            self._set_self()
+
+    def _set_self(self):
+        d, ctx = self._sdf, self.ctx
+        _capi.check(ctx.lib.edmp_sdf_set_self(ctx.h, _capi.as_pi32(d["self_mask"]), _capi.as_pd(d["self_weight"]), _capi.as_pd(d["self_margin"]),
+                                              self.batch_size, int(d["self_margin"].shape[1])), "edmp_sdf_set_self")
 
     def _sdf_host(self):
         if self._sdf is not None:
             return False
-        self._sdf = sdf_tables(self.guide_cfgs, self.batch_size, self.T, self._half, self._spheres)
+        self._sdf = sdf_tables(self.guide_cfgs, self.batch_size, self.T, self._half, self._spheres, self._self_pairs.reshape(9, 9))
         return True
 
     # ---- reference API -----------------------------------------------------------------------------------------
@@ -430,6 +501,18 @@ class IntersectionVolumeGuide(_SlotObject):
             raise ValueError(f"trajectories must be (n, 7, L), got {tuple(X.shape)}")
         return self._sdf_report(X, (X.shape[0],), X.shape[2], t, _pair7(start, goal))
 
+    def sdf_self_rows(self, trajectories, t=0):
+        """Self-clearance term of EVERY row (edmp_sdf_self_rows_dev): trajectories (n, 7, L) interior waypoints, f64 (not clipped) ->
+        {"cost": (n,) f64 = weight * sum of the hinge terms, "clearance": (n,) f64 = min over the waypoints and the masked sphere pairs
+        of (centre distance - both radii), +inf when the mask selects no pair}.  t = 0: margin 0, any n (the rows' weights only when n
+        is the guide's batch, else weight 1); t >= 1: the rows' own self margin at step t, n = the guide's batch.  Needs no start /
+        goal pair and leaves a segmented run running."""
+        X = self._rows_f64(trajectories)
+        if X.dim() != 3 or X.shape[1] != 7:
+            raise ValueError(f"trajectories must be (n, 7, L), got {tuple(X.shape)}")
+        self._bind_self()
+        return self._self_report(X, (X.shape[0],), X.shape[2], 0, X.shape[2], t)
+
     def row_swept_volumes(self, start, goal, trajectories):
         """(B,) f32 t=0 swept volume per row and the argmin (first on ties)."""
         self._bind()
@@ -450,6 +533,20 @@ class IntersectionVolumeGuide(_SlotObject):
         if X.dim() != 3 or X.shape[1] != 7:
             raise ValueError(f"trajectories must be (B, 7, N), got {tuple(X.shape)}")
         return self._success(X, (X.shape[0],), X.shape[2], substeps, return_device)
+
+    def self_collision_rows(self, trajectories, substeps: int = 4, pairs=None, return_device: bool = False):
+        """Exact self-collision check of EVERY row (edmp_self_collision_rows_dev, csrc/selfcol.hip; stands for the `self_collision`
+        metric of the reference's evaluation package, mpinets/metrics.py:278-292): trajectories (n, 7, N) ndarray or device tensor, any
+        n >= 1 -> dict(first (n,) int32 waypoint index of the first configuration at which a masked pair of link boxes overlaps or -1,
+        pair (n, 2) int32 the first such pair (a, b), a < b, in row-major order at that configuration or (-1, -1), free (n,) bool).
+        The configurations are success_rows' (``substeps``); ``pairs`` is a (9, 9) 0/1 mask of which a < b is read, default
+        franka.self_collision_pairs().  With return_device the arrays stay device tensors."""
+        mask = franka.check_pair_mask(pairs)
+        self._bind()
+        X = self._rows_f64(trajectories)
+        if X.dim() != 3 or X.shape[1] != 7:
+            raise ValueError(f"trajectories must be (n, 7, N), got {tuple(X.shape)}")
+        return self._self_collision(X, (X.shape[0],), X.shape[2], substeps, mask, return_device)
 
     def metrics_rows(self, trajectories, dt: float = 0.1, return_device: bool = False):
         """evaluation.batch_metrics on this guide's context: path lengths and SPARC of EVERY row (edmp_metrics_rows_dev; stands for
@@ -528,6 +625,8 @@ def scene_batch_tables(scenes):
             if shapes != ((B,), (B, T), (B,)):
                 raise ValueError(f"scene {s}: sdf_rows / sdf_margin / smoothness must be ({B},), ({B}, {T}), ({B},), got {shapes}")
         out.update(sdf_rows=cat("sdf_rows", np.int32), sdf_margin=cat("sdf_margin", np.float64, (T,)), smoothness=cat("smoothness", np.float64))
+        if all("sdf_self_weight" in sc for sc in scenes):  # the self-clearance term's row arrays ride along (edmp_sdf_set_self)
+            out.update(sdf_self_weight=cat("sdf_self_weight", np.float64), sdf_self_margin=cat("sdf_self_margin", np.float64, (T,)))
     return out
 
 
@@ -580,7 +679,12 @@ class SceneBatch(_SlotObject):
             dict(obstacle_config=g.obstacle_config, row_class=g.row_class, clearance=g._cls_clr, expansion=g._cls_exp,
                  method=np.asarray(g.guide_cfgs["guidance_method"], dtype=np.float32).reshape(-1),
                  grad_norm=np.asarray(g.guide_cfgs["grad_norm"], dtype=np.float64).reshape(-1), guidance_schedule=g._sched,
-                 **(dict(sdf_rows=g._sdf["rows"], sdf_margin=g._sdf["margin"], smoothness=g._sdf["smooth"]) if sdf else {})) for g in guides])
+                 **(dict(sdf_rows=g._sdf["rows"], sdf_margin=g._sdf["margin"], smoothness=g._sdf["smooth"],
+                        sdf_self_weight=g._sdf["self_weight"], sdf_self_margin=g._sdf["self_margin"]) if sdf else {})) for g in guides])
+        for k, g in enumerate(guides):  # (host tables still: nothing is bound yet)
+            if not np.array_equal(g._self_pairs, g0._self_pairs):
+                raise ValueError(f"scene {k}: the self-clearance pair mask (self_pairs) differs from scene 0's: a batch takes one mask")
+        self._self_on = self.has_self_term
         self._spheres = g0._sdf["spheres"] if sdf else None  # None: no SDF table is bound (sdf_rows builds one when a report is asked for)
         self._slot = new_slot_key()
         self._kinds = None
@@ -612,6 +716,16 @@ class SceneBatch(_SlotObject):
     def has_sdf_rows(self):
         return "sdf_rows" in self.tables and bool(self.tables["sdf_rows"].any())
 
+    @property
+    def has_self_term(self):
+        return "sdf_self_weight" in self.tables and bool((self.tables["sdf_self_weight"] > 0).any())
+
+    def _set_self(self):
+        tb, ctx, n = self.tables, self.ctx, self.n_scenes * self.batch_size
+        w = tb["sdf_self_weight"] if "sdf_self_weight" in tb else np.zeros(n)
+        m = tb["sdf_self_margin"] if "sdf_self_margin" in tb else np.zeros((n, self.T))
+        _capi.check(ctx.lib.edmp_sdf_set_self(ctx.h, _capi.as_pi32(self.guides[0]._self_pairs), _capi.as_pd(w), _capi.as_pd(m), n, self.T), "edmp_sdf_set_self")
+
     def _set_sdf(self):
         tb, ctx, B = self.tables, self.ctx, self.batch_size
         if "sdf_rows" not in tb:  # a report on a batch without SDF rows: no row is overlaid; margins / weights where a member brings them
@@ -623,6 +737,8 @@ class SceneBatch(_SlotObject):
         rows, margin, smooth = tb["sdf_rows"], tb["sdf_margin"], tb["smoothness"]
         _capi.check(ctx.lib.edmp_scene_batch_set_sdf(ctx.h, _capi.as_pf(self._spheres), int(self._spheres.shape[0]), _capi.as_pi32(rows), _capi.as_pd(margin),
                                                      _capi.as_pd(smooth), self.n_scenes, self.batch_size, self.T), "edmp_scene_batch_set_sdf")
+        if self._self_on:
+            self._set_self()
 
     def _sdf_host(self):
         if self._spheres is not None:
@@ -733,6 +849,16 @@ class SceneBatch(_SlotObject):
         self._bind()
         return self._success(Xd, (self.n_scenes, self.batch_size), N, substeps, return_device)
 
+    def self_collision_rows(self, trajectories, substeps: int = 4, pairs=None, return_device: bool = False):
+        """IntersectionVolumeGuide.self_collision_rows for the (S, B, 7, N) / (S*B, 7, N) state in one call: first and free shaped
+        (S, B), pair (S, B, 2).  The check reads nothing of the scenes: a row's answer is what any guide of this robot gives for it."""
+        mask = franka.check_pair_mask(pairs)
+        Xd, N = self._state(trajectories)
+        self._bind()
+        out = self._self_collision(Xd, (self.n_scenes, self.batch_size), N, substeps, mask, return_device)
+        Xd.record_stream(self.ctx.stream)
+        return out
+
     def sdf_rows(self, trajectories, starts, goals, t=0):
         """IntersectionVolumeGuide.sdf_rows for every scene (edmp_scenes_sdf_rows_dev): cost and minimum clearance of EVERY row of the
         (S, B, 7, N) / (S*B, 7, N) state under the sphere signed-distance model, each row against its own scene's primitives, kinds and
@@ -743,5 +869,15 @@ class SceneBatch(_SlotObject):
         Xd, N = self._state(trajectories)
         self._bind_sdf()
         out = self._sdf_report(Xd, (self.n_scenes, self.batch_size), N, t, pair)
+        Xd.record_stream(self.ctx.stream)
+        return out
+
+    def sdf_self_rows(self, trajectories, t=0):
+        """IntersectionVolumeGuide.sdf_self_rows for the (S, B, 7, N) / (S*B, 7, N) state (its interior columns 1..N-2 are the
+        waypoints) in one call -> {"cost": (S, B) f64, "clearance": (S, B) f64}.  The term reads nothing of the scenes: scene s's values
+        are what guides[s].sdf_self_rows gives for X[s][:, :, 1:-1]."""
+        Xd, N = self._state(trajectories)
+        self._bind_self()
+        out = self._self_report(Xd, (self.n_scenes, self.batch_size), N, 1, N - 2, t)
         Xd.record_stream(self.ctx.stream)
         return out

@@ -48,9 +48,12 @@ GUIDE_CATALOG = {
 }
 
 # Guides beyond the reference's catalogue, under numbers it does not use.  101: the sphere signed-distance guide (csrc/sdf.hip) with a
-# margin that shrinks towards t = 0 and a light smoothness pull; `sdf` holds the optional keys of `hyperparameters.sdf`.
+# margin that shrinks towards t = 0 and a light smoothness pull; `sdf` holds the optional keys of `hyperparameters.sdf`.  102: 101 plus
+# the self-clearance term (sdf_self_kernel): the spheres of the masked link pairs are kept self_margin apart.
 EXTRA_GUIDES = {
     101: dict(_g((0.05, 0.05), *_E_NONE, "sdf", False, "constant", 0.05), sdf=dict(margin=(0.02, 0.08), smoothness=0.01)),
+    102: dict(_g((0.05, 0.05), *_E_NONE, "sdf", False, "constant", 0.05),
+              sdf=dict(margin=(0.02, 0.08), smoothness=0.01, self_margin=(0.01, 0.03), self_weight=1.0)),
 }
 METHODS = ("iv", "sv", "sdf")
 
@@ -77,6 +80,8 @@ def catalog_guide_dict(n: int) -> dict:
     }
     if "sdf" in g:
         d["hyperparameters"]["sdf"] = {"margin": [float(v) for v in g["sdf"]["margin"]], "smoothness": float(g["sdf"]["smoothness"])}
+        if "self_weight" in g["sdf"]:
+            d["hyperparameters"]["sdf"].update(self_margin=[float(v) for v in g["sdf"]["self_margin"]], self_weight=float(g["sdf"]["self_weight"]))
     return d
 
 
@@ -115,7 +120,9 @@ def build_guide_cfgs(guide_dicts, batch_size_per_guide, T: int, rows_per_guide=N
     not in the reference's schema) keeps ``guidance_method`` 0 on its rows and adds three arrays - only when some guide uses it, so the
     dict of the reference's guides is key for key what it always was: ``sdf_rows`` (B,) 0/1, ``sdf_margin`` (B, T) = linspace of
     ``hyperparameters.sdf.margin`` [m0, m1] (default: the guide's ``obstacle_clearance.range``) and ``smoothness`` (B,) =
-    ``hyperparameters.sdf.smoothness`` (default 0).
+    ``hyperparameters.sdf.smoothness`` (default 0).  The self-clearance term of an 'sdf' guide: ``hyperparameters.sdf.self_weight``
+    (default 0) and ``.self_margin`` [m0, m1] (default [0, 0]) add ``sdf_self_weight`` (B,) and ``sdf_self_margin`` (B, T) = linspace
+    over T - only when some guide sets a weight > 0, so every other dict stays key for key what it was.
     """
     G = len(guide_dicts)
     counts = [int(batch_size_per_guide)] * G if rows_per_guide is None else [int(c) for c in rows_per_guide]
@@ -135,6 +142,15 @@ def build_guide_cfgs(guide_dicts, batch_size_per_guide, T: int, rows_per_guide=N
             raise ValueError(f"guide {g.get('index', '?')}: guidance_method {g['hyperparameters']['guidance_method']!r} is none of {METHODS}")
     if any(g["hyperparameters"]["guidance_method"] == "sdf" for g in guide_dicts):
         cfgs.update(sdf_rows=np.zeros((B,)), sdf_margin=np.zeros((B, T)), smoothness=np.zeros((B,)))
+    for g in guide_dicts:
+        sd = g["hyperparameters"].get("sdf") or {}
+        sw, sm = sd.get("self_weight", 0.0), sd.get("self_margin", (0.0, 0.0))
+        if not (np.ndim(sw) == 0 and np.shape(sm) == (2,) and np.isfinite(sw) and np.isfinite(sm).all() and sw >= 0 and min(sm) >= 0):
+            raise ValueError(f"guide {g.get('index', '?')}: sdf.self_weight must be finite and >= 0 and sdf.self_margin two such values")
+        if sw > 0 and g["hyperparameters"]["guidance_method"] != "sdf":
+            raise ValueError(f"guide {g.get('index', '?')}: sdf.self_weight > 0 needs guidance_method 'sdf' (the term rides on the SDF rows)")
+        if sw > 0 and "sdf_self_weight" not in cfgs:
+            cfgs.update(sdf_self_weight=np.zeros((B,)), sdf_self_margin=np.zeros((B, T)))
     r0 = 0
     for g, cnt in zip(guide_dicts, counts):
         rows = slice(r0, r0 + cnt)
@@ -157,6 +173,9 @@ def build_guide_cfgs(guide_dicts, batch_size_per_guide, T: int, rows_per_guide=N
             cfgs["sdf_rows"][rows] = 1
             cfgs["sdf_margin"][rows, :] = np.linspace(m0, m1, T)
             cfgs["smoothness"][rows] = lam
+            if "sdf_self_weight" in cfgs:
+                cfgs["sdf_self_weight"][rows] = float(sd.get("self_weight", 0.0))
+                cfgs["sdf_self_margin"][rows, :] = np.linspace(*sd.get("self_margin", (0.0, 0.0)), T)
         cfgs["grad_norm"][rows] = 1 if h["grad_norm"] else 0
         gs = h["guidance_schedule"]
         cfgs["guidance_schedule"][rows, :] = (1.4 + np.arange(T) / T) if gs["type"] == "varying" else gs["scale_val"]

@@ -153,6 +153,28 @@ int edmp_sdf_set(edmp_ctx* ctx, const float* spheres, int n_spheres, const int32
  * run like edmp_guide_gradient_dev (the start / goal pair is replaced).  Does not synchronise. */
 int edmp_sdf_rows_dev(edmp_ctx* ctx, const double* joints_dev, int n, int L, int t, const double* start, const double* goal,
                       double* cost_dev, double* clearance_dev);
+/* Self-clearance term of the SDF rows, on the same sphere model (centres in f32 as above): for the sphere pairs (s, u) with
+ * pair_mask[link_s][link_u] == 1, link_s < link_u,
+ *   self(r) = weight[r] * sum_{w=1..L} sum_{(s,u)} max(0, m - d(w; s, u)),  d = ||c_s - c_u|| - radius_s - radius_u,
+ *   m = self_margin[r][t - 1] for t >= 1 and 0 at t = 0,
+ * interior waypoints only; the gradient and the sub-gradient conventions are stated at the top of csrc/sdf.hip.  edmp_sdf_set_self comes
+ * after edmp_sdf_set or edmp_scene_batch_set_sdf (EDMP_ERR_STATE without a sphere table): pair_mask (host, 81 int32 = (9,9) row-major,
+ * entries above the diagonal 0 or 1, the others not read; the links' spheres are paired in the order of the link-sorted table),
+ * weight (n,) and self_margin (n,T) f64, finite and >= 0, n = the bound rows (B, or S*B scene after scene) and T those of edmp_rows_set.
+ * A weight > 0 on a row that is not an SDF row is refused; the message names the row (and the scene, in a batch).  Every check comes
+ * before anything is changed.  In the gradient paths sdf_self_kernel runs after sdf_guide_kernel over the rows whose weight is > 0, adds
+ * the term's gradient to those rows' raw gradient and rewrites their sum g^2; with no such row nothing is launched, and a row outside
+ * the list keeps the bits it had.  Bumps the context's epoch and synchronises, as edmp_sdf_set.  The term belongs to the sphere table: a
+ * later edmp_sdf_set / edmp_scene_batch_set_sdf / edmp_rows_set drops it. */
+int edmp_sdf_set_self(edmp_ctx* ctx, const int32_t* pair_mask, const double* weight, const double* self_margin, int n, int T);
+/* the report of the term for EVERY row: element (r, j, w) of the L interior waypoints at joints_dev[(r*7 + j)*ldw + off + w], f64 on the
+ * device (not clipped), 1 <= L <= 62, off + L <= ldw; cost_dev (n,) f64 = self(r), clearance_dev (n,) f64 = the minimum d over interior
+ * waypoints and masked sphere pairs, +inf when the mask selects no pair.  t = 0: any n, margin 0, and the weight of row r only when n
+ * is the bound row count (else 1: the bare hinge sum); t >= 1: n must be the bound row count.  Needs edmp_sdf_set_self (EDMP_ERR_STATE
+ * without).  It replaces no start / goal pair and does NOT end a segmented run.  Argument errors come before any device call.  Does not
+ * synchronise. */
+int edmp_sdf_self_rows_dev(edmp_ctx* ctx, const double* joints_dev, int n, int ldw, int off, int L, int t, double* cost_dev,
+                           double* clearance_dev);
 
 /* ---- plan success: the reference's simulator check, restated geometrically ------------------------------------ */
 /* The guide sees every obstacle as a box (cylinders enter as (r, r, h) boxes, datasets/load_test_dataset.py:136-139) but the
@@ -171,6 +193,26 @@ int edmp_scene_set_shapes(edmp_ctx* ctx, const int32_t* kind, int n_obstacles);
  * 0/1.  counts_host (optional, synchronises): [rows ok, rows within limits, rows collision-free, B]. */
 int edmp_success_rows_dev(edmp_ctx* ctx, const double* X_dev, int B, int N, int substeps, const double* dh_f64, int32_t* ok_dev,
                           int32_t* first_dev, int32_t* within_dev, int32_t* counts_host);
+
+/* ---- self-collision of every row (csrc/selfcol.hip) ------------------------------------------------------------- */
+/* Stands for the `self_collision` metric of the reference's evaluation package (mpinets/metrics.py:278-292, 351-361; a plan with
+ * self-collision counts as a physical violation, :505), which asks robofin / pybullet - both absent: like the success check a geometric
+ * stand-in, exact on the 9 link boxes.  X (n,7,N) f64 on the device, N >= 2, 1 <= substeps <= 64.  Row r is self-colliding at
+ * configuration c - the success check's configurations: every waypoint plus substeps - 1 joint-space interpolants per segment, the same
+ * interpolation expression, nc = (N - 1) * substeps + 1 - if the boxes of any MASKED pair of links overlap there: f64 modified-DH poses,
+ * static frames and half extents of the bound guide's robot, the 15-axis separating-axis test of the success check, touching counts as
+ * overlap.  pair_mask (host, 81 int32 = (9,9) row-major): pair (a, b), a < b, is tested iff pair_mask[a*9 + b] == 1; those entries must
+ * be 0 or 1, entries on or below the diagonal are not read; an all-zero mask is legal and gives -1 everywhere.  (The link boxes are AABBs
+ * of meshes, neighbouring links overlap by construction: franka.self_collision_pairs() masks the pairs whose joint frames lie at least 3
+ * apart.)  dh_f64 as in edmp_success_rows_dev.
+ * Outputs (device, each optional): first (n,) int32 = waypoint index c / substeps of the first colliding configuration, or -1;
+ * pair (n,) int32 = a*9 + b of the first masked pair in row-major order that overlaps at THAT configuration, or -1.  Both come from one
+ * integer minimum over the key c*81 + a*9 + b: deterministic, and a row's answer depends on the row alone.
+ * Needs a bound guide for the robot tables - a single-scene guide or a scene batch alike (EDMP_ERR_STATE without one); it reads nothing
+ * of the scene, the rows or the sampler, so one entry point serves both for any n >= 1, allocates nothing, leaves the epoch alone and
+ * does NOT end a segmented run.  Argument errors (EDMP_ERR_ARG) come before any device call.  Does not synchronise. */
+int edmp_self_collision_rows_dev(edmp_ctx* ctx, const double* X_dev, int n, int N, int substeps, const double* dh_f64,
+                                 const int32_t* pair_mask, int32_t* first_dev, int32_t* pair_dev);
 
 /* ---- result metrics of a whole batch (csrc/metrics.hip) ----------------------------------------------------------- */
 /* stands for MetricsCalculator.path_length_metric and .smoothness_metric / .sparc (lib/metrics.py:32-45, 11-30, 47-125; end effector
@@ -234,7 +276,9 @@ int edmp_denoise_guided_dev(edmp_ctx* ctx, const double* noise_dev, int B, const
  * start / goal pair), by edmp_unet_forward_dev (the
  * model's input buffer carries the next segment's input), by a changed edmp_sampler_set_condition and by edmp_sampler_init: a
  * continuing segment after any of them is refused.  A run started with guided = 0 cannot be continued with guided = 1 (the guide
- * never received its pair).
+ * never received its pair).  Calls that read neither the guide's start / goal pairs, nor the sampler, nor the model's buffers leave a run
+ * as it stands, and the next segment continues as if they had not been made: edmp_scenes_goal_filter_dev, edmp_ik_solve_dev,
+ * edmp_self_collision_rows_dev and edmp_sdf_self_rows_dev.
  * start / goal are read by the init segment only (uploaded once, kept on the device); a continuing segment IGNORES its start /
  * goal arguments and goes on with the init segment's pair. */
 int edmp_denoise_guided_segment_dev(edmp_ctx* ctx, const double* noise_dev, int B, const double* start, const double* goal,

@@ -18,6 +18,7 @@ import torch
 
 from edmp_amd import dist as ED
 from edmp_amd import evaluation as EV
+from edmp_amd import franka
 from edmp_amd import guide_cfg as GC
 from edmp_amd.diffusion import DEFAULT_CHUNK_STEPS, Diffusion, PinnedNoiseStream, chunk_plan
 from edmp_amd.guide import IntersectionVolumeGuide, SceneBatch, pick_goal
@@ -112,12 +113,14 @@ class _NoiseFeeder:
         self.thread.join()
 
 
-def job_summary(results, world=1):
+def job_summary(results, world=1, self_collision=False):
     """This rank's tallies; under a launcher the sum over all ranks (all_gather_object of five small integers per rank - the
     trajectories stay where they were planned).  Keys: scenes, success_proxy (the reference's tally), success_strict, rows_collision_free, rows."""
     mine = dict(scenes=len(results), success_proxy=sum(r["success_proxy"] for r in results), success_strict=sum(r["success_strict"] for r in results),
                 rows_collision_free=sum(r["rows_collision_free"] for r in results), rows=sum(r["rows"] for r in results),
                 planning_time_s=float(sum(r["planning_time_s"] for r in results)))
+    if self_collision:  # (run(..., self_collision=True): every rank's results carry the keys)
+        mine.update(self_collision_free=sum(r["self_collision_free"] for r in results), rows_self_collision_free=sum(r["rows_self_collision_free"] for r in results))
     if world <= 1:
         return dict(mine, ranks=1)
     import torch.distributed as dist
@@ -131,7 +134,7 @@ def job_summary(results, world=1):
 
 
 def run(cfg_path, dataset=None, max_scenes=None, verbose=True, scenes_in_flight=1, shard_scenes=True, scenes_per_launch=1, ensemble_report=False, prefer=None,
-        ik_seeds=0, ik_tool=None, ik_seed=0):
+        ik_seeds=0, ik_tool=None, ik_seed=0, self_collision=False):
     """The reference's scene loop (infer_serial.py:95-170).  Under ``torch.distributed.run`` (one process per GPU, extension: the
     reference is one process) the scenes are dealt round-robin to the ranks - scene i of the cfg's order goes to rank i mod world -
     and nothing is exchanged until `job_summary` adds the tallies up: scenes are independent problems, this is the problem set's natural
@@ -166,7 +169,13 @@ def run(cfg_path, dataset=None, max_scenes=None, verbose=True, scenes_in_flight=
     the candidates come from edmp_amd.ik.FrankaIK (batched numerical IK on the GPU, n seeds per target from a private RandomState(ik_seed),
     never the global stream the feeder is advancing); with scenes_per_launch the group's targets are solved in one solve_many call.
     ``ik_tool`` is the frame the targets are given in, behind the joint-7 frame (ik.tool_frame: None = the reference's end-effector chain,
-    "flange", "hand" or a (4, 4) array - MPiNets' right_gripper offset is the caller's to pass).  Problems that carry goals keep them."""
+    "flange", "hand" or a (4, 4) array - MPiNets' right_gripper offset is the caller's to pass).  Problems that carry goals keep them.
+
+    ``self_collision`` (an extension; off: every result and every printed line is what it was) checks EVERY row of each batch for
+    self-collision on the GPU (IntersectionVolumeGuide / SceneBatch.self_collision_rows: the link boxes against each other under
+    franka.self_collision_pairs(); a scene group in one call) and adds to the scene's result `self_collision_free` (the chosen plan's
+    flag, tallied like success), `rows_self_collision_free`, `first_self_collision_waypoint` and `self_collision_pair` (the chosen plan's
+    first colliding pair as two franka.LINK_NAMES, None when free); with ensemble_report the chosen plan's flag and pair are printed."""
     from concurrent.futures import ThreadPoolExecutor
 
     from edmp_amd.runtime import get_context, lane_context
@@ -213,6 +222,12 @@ def run(cfg_path, dataset=None, max_scenes=None, verbose=True, scenes_in_flight=
         if ensemble_report:
             out["ensemble"] = EV.ensemble_report(guide_numbers, guide_rows, vols, chk, met)
         return out
+
+    def self_extras(sc, idx):
+        """the keys self_collision adds to a scene's result: sc = self_collision_rows' dict of the scene's rows"""
+        a, b = (int(v) for v in sc["pair"][idx])
+        return dict(self_collision_free=int(sc["free"][idx]), rows_self_collision_free=int(np.count_nonzero(sc["free"])),
+                    first_self_collision_waypoint=int(sc["first"][idx]), self_collision_pair=None if a < 0 else [franka.LINK_NAMES[a], franka.LINK_NAMES[b]])
 
     model_name = benchmark_cfg["model"]["model_dir"] + "TemporalUNetModel" + str(T) + "_N" + str(traj_len)
     if not os.path.exists(model_name):
@@ -283,12 +298,14 @@ def run(cfg_path, dataset=None, max_scenes=None, verbose=True, scenes_in_flight=
                     aabb_volume_zero=bool(ED.geometric_success(float(vols[idx]), trajectory)), first_collision_waypoint=int(chk["first"][idx]),
                     path_length=EV.path_lengths(trajectory), sparc=EV.smoothness(trajectory), planning_time_s=t_plan, scene_wall_s=time.time() - t0, trajectory=trajectory,
                     **({"min_clearance": float(guide.sdf_rows(trajectory[None, :, 1:-1], start_joints, goal_joints)["clearance"][0])} if ensemble_report and guide.has_sdf_rows else {}),
-                    **extras(vols, chk, met))
+                    **({"min_self_clearance": float(guide.sdf_self_rows(trajectory[None, :, 1:-1])["clearance"][0])} if ensemble_report and guide.has_self_term else {}),
+                    **(self_extras(guide.self_collision_rows(trajectories), idx) if self_collision else {}), **extras(vols, chk, met))
 
     t_success, t_strict, i, results, pending = 0, 0, 0, [], []
+    t_self = 0
 
     def collect(fut):
-        nonlocal t_success, t_strict
+        nonlocal t_success, t_strict, t_self
         r = fut.result() if hasattr(fut, "result") else fut
         r["done_at"] = time.time()
         results.append(r)
@@ -302,6 +319,15 @@ def run(cfg_path, dataset=None, max_scenes=None, verbose=True, scenes_in_flight=
                 print(line)
             if "min_clearance" in r:  # (a run with an SDF guide: the sphere model's smallest clearance along the chosen plan)
                 print(f"    chosen plan: minimum sphere clearance {r['min_clearance']:.4f} m")
+            if "min_self_clearance" in r:  # (the guide carries the self-clearance term: the sphere model's smallest distance to itself)
+                print(f"    chosen plan: minimum self clearance {r['min_self_clearance']:.4f} m")
+        if "self_collision_free" in r:
+            t_self += r["self_collision_free"]
+            if verbose:
+                print(f"    self-collision free {r['self_collision_free']} ({r['rows_self_collision_free']}/{r['rows']} rows of the batch)   running {t_self}/{len(results)}")
+                if "ensemble" in r:
+                    print("    chosen plan: " + ("no self-collision" if r["self_collision_pair"] is None else
+                                                 f"self-collision of {r['self_collision_pair'][0]} and {r['self_collision_pair'][1]} at waypoint {r['first_self_collision_waypoint']}"))
 
     # this rank's scenes, in the cfg's order (scene i of that order belongs to rank i mod world)
     mine = []
@@ -365,6 +391,8 @@ def run(cfg_path, dataset=None, max_scenes=None, verbose=True, scenes_in_flight=
         te = time.time()
         # (a run with an SDF guide: the sphere model's clearance of every row of the group in one call, the chosen rows' are reported)
         all_clr = batch.sdf_rows(Xd, starts, goals)["clearance"] if ensemble_report and batch.has_sdf_rows else None
+        all_sclr = batch.sdf_self_rows(Xd)["clearance"] if ensemble_report and batch.has_self_term else None
+        all_self = batch.self_collision_rows(Xd) if self_collision else None  # (the whole group in one call)
         X = diffuser.ctx.to_host(Xd)  # once, for the result dicts
         out = []
         for s, (guide, start_joints, goal_joints, meta, t0) in enumerate(group):
@@ -385,7 +413,9 @@ def run(cfg_path, dataset=None, max_scenes=None, verbose=True, scenes_in_flight=
                             rows_ok=chk["rows_ok"], rows=chk["rows"], aabb_volume_zero=bool(ED.geometric_success(float(vols[idx]), trajectory)),
                             first_collision_waypoint=int(chk["first"][idx]), path_length=EV.path_lengths(trajectory), sparc=EV.smoothness(trajectory),
                             planning_time_s=t_plan, scene_wall_s=time.time() - t0, trajectory=trajectory,
-                            **({"min_clearance": float(all_clr[s][idx])} if all_clr is not None else {}), **extras(vols, chk, met)))
+                            **({"min_clearance": float(all_clr[s][idx])} if all_clr is not None else {}),
+                            **({"min_self_clearance": float(all_sclr[s][idx])} if all_sclr is not None else {}),
+                            **(self_extras({k: v[s] for k, v in all_self.items()}, idx) if all_self is not None else {}), **extras(vols, chk, met)))
         return out
 
     try:
@@ -426,10 +456,12 @@ def run(cfg_path, dataset=None, max_scenes=None, verbose=True, scenes_in_flight=
         if feeder is not None:
             feeder.close()
     if world > 1 or verbose:
-        summary = job_summary(results, world)
+        summary = job_summary(results, world, self_collision)
         if verbose and rank == 0:
             print(f"[infer_serial] {summary['scenes']} scenes on {summary['ranks']} rank(s): success (proxy, collision-free) {summary['success_proxy']}/{summary['scenes']}, "
                   f"strict {summary['success_strict']}/{summary['scenes']}, rows collision-free {summary['rows_collision_free']}/{summary['rows']}")
+            if "self_collision_free" in summary:
+                print(f"[infer_serial] self-collision free {summary['self_collision_free']}/{summary['scenes']}, rows {summary['rows_self_collision_free']}/{summary['rows']}")
         run.last_summary = summary
     return results
 
@@ -452,6 +484,8 @@ def main(argv=None):
                                                                   "seeds per target (extension; 0 = off: such a problem set raises as before)")
     parser.add_argument("--ik-tool", type=str, default=None, help="the frame the targets are given in: 'flange', 'hand', or a JSON / .npy file holding a (4, 4) "
                                                                     "frame behind the joint-7 frame (default: the reference's end-effector chain)")
+    parser.add_argument("--self-collision", action="store_true", help="check every row of each batch for self-collision on the GPU (link boxes against each other) "
+                                                                      "and tally the chosen plans' flags (extension; adds `self_collision_free` to the results)")
     args = parser.parse_args(argv)
     ik_tool = args.ik_tool
     if ik_tool is not None and ik_tool not in ("flange", "hand"):
@@ -466,7 +500,7 @@ def main(argv=None):
     if args.seed is not None:
         np.random.seed(args.seed + rank)
     results = run(args.cfg_path, scenes_in_flight=args.scenes_in_flight, max_scenes=args.max_scenes, scenes_per_launch=args.scenes_per_launch,
-                  ensemble_report=args.ensemble_report, prefer=args.prefer, ik_seeds=args.ik_seeds, ik_tool=ik_tool)
+                  ensemble_report=args.ensemble_report, prefer=args.prefer, ik_seeds=args.ik_seeds, ik_tool=ik_tool, self_collision=args.self_collision)
     if args.results_json:
         import json
 

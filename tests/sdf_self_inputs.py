@@ -1,0 +1,171 @@
+"""Checker and inputs of the self-clearance term of the sphere signed-distance guide (sdf_self_kernel in edmp_amd/csrc/sdf.hip): a
+float64 torch-autograd evaluation written from the definition - not from the kernel - on the chain of tests/sdf_reference.py.
+
+    c_s(q)      = T_frame(link_s)(q) . static_frame[link_s] . centre_s
+    d(w; s, u)  = ||c_s(q_w) - c_u(q_w)|| - r_s - r_u       sphere pairs with mask[link_s][link_u], link_s < link_u
+    self(r)     = weight_r * sum_{w=1..L} sum_{(s,u)} max(0, m_r - d(w; s, u))         interior waypoints only
+
+autograd differentiates the whole expression, the rigid part below the lower link included.  The inputs of a case sit >= MIN_GAP away
+from every kink of the term (every |m - d|, every centre distance) and of the obstacle part (sdf_reference.assert_margins), at t = 0 and
+at T_CHECK; `find_seed(lambda s: check_case(name, s))` found the committed seeds.  Gate: sdf_reference.gate, i.e. max(4 x the deviation of
+the same formula in CPU float32 from float64, 4 f32 ulps), relative to the largest element.  For the minimum clearance the largest
+element is the largest sphere-centre COORDINATE, as in sdf_reference.clearance_gate: d is a difference of world coordinates of size
+~1 m, and float32 resolves it no finer than an ulp of those, however small d itself is."""
+import numpy as np
+import torch
+
+from edmp_amd import franka
+from tests import sdf_reference as R
+
+T, T_CHECK, MIN_GAP = R.T, R.T_CHECK, R.MIN_GAP
+SELF_MARGIN = (0.1, 0.4)  # wider than sample guide 102's, so that random configurations put terms on both sides of the hinge
+# one row per guide: method, grad_norm, smoothness, self weight
+ROW_GUIDES = (("sdf", False, 0.05, 0.7), ("sdf", True, 0.0, 1.5), ("sdf", False, 0.02, 0.0), ("iv", False, 0.0, 0.0), ("iv", True, 0.0, 0.0),
+              ("sv", False, 0.0, 0.0))
+SELF_ROWS, SDF_ROWS, B = (0, 1), (0, 1, 2), len(ROW_GUIDES)
+
+
+def guide_dict(method, grad_norm, smoothness, weight, index):
+    d = R.guide_dict(method, grad_norm, smoothness, index)
+    if weight > 0:
+        d["hyperparameters"]["sdf"].update(self_margin=list(SELF_MARGIN), self_weight=float(weight))
+    return d
+
+
+def mixed_cfgs(with_self=True, grad_norm=True):
+    """the 6-row ensemble; with_self=False: the same rows without the self keys; grad_norm=False: no row normalises"""
+    from edmp_amd import guide_cfg as GC
+
+    return GC.build_guide_cfgs([guide_dict(m, gn and grad_norm, lam, w if with_self else 0.0, 300 + i) for i, (m, gn, lam, w) in enumerate(ROW_GUIDES)], 1, T)
+
+
+def sphere_pairs(spheres, mask):
+    """index pairs (s, u) of the table as given with mask[link_s][link_u], link_s < link_u"""
+    link = np.asarray(spheres)[:, 0].astype(int)
+    mask = np.asarray(mask).reshape(9, 9)
+    return [(s, u) for s in range(len(link)) for u in range(len(link)) if link[s] < link[u] and mask[link[s], link[u]]]
+
+
+def centres(x, spheres, dtype):
+    """x (B, 7, L) tensor -> sphere centres (B, L, n, 3)"""
+    frames = R._chain(x.permute(0, 2, 1), dtype)
+    sf = torch.zeros(9, 4, 4, dtype=dtype)
+    sf[:, :3, :] = torch.tensor(franka.static_frames().astype(np.float64), dtype=dtype)
+    sf[:, 3, 3] = 1
+    cen = []
+    for row in np.asarray(spheres, dtype=np.float64):
+        l = int(row[0])
+        p = torch.tensor([row[1], row[2], row[3], 1.0], dtype=dtype)
+        cen.append((frames[int(franka.LINK_FRAME[l])] @ (sf[l] @ p))[..., :3])
+    return torch.stack(cen, dim=2)
+
+
+def evaluate_self(joints, spheres, mask, margin, weight, dtype=torch.float64, want_grad=True):
+    """joints (n, 7, L), margin (n,), weight (n,) -> dict of f64 ndarrays: cost (n,), clearance (n,) (+inf without a pair), grad (n, 7, L),
+    d and dist (n, L, pairs), coord_max"""
+    n = np.shape(joints)[0]
+    x = torch.tensor(np.asarray(joints, dtype=np.float64), dtype=dtype, requires_grad=want_grad)
+    c = centres(x, spheres, dtype)
+    pairs = sphere_pairs(spheres, mask)
+    rad = torch.tensor(np.asarray(spheres, dtype=np.float64)[:, 4], dtype=dtype)
+    out = dict(coord_max=float(c.detach().abs().max()))
+    if pairs:
+        si, ui = [p[0] for p in pairs], [p[1] for p in pairs]
+        dist = R._safe_norm(((c[:, :, si] - c[:, :, ui]) ** 2).sum(-1))
+        d = dist - rad[si] - rad[ui]
+        m = torch.tensor(np.asarray(margin, dtype=np.float64), dtype=dtype).view(n, 1, 1)
+        cost = torch.tensor(np.asarray(weight, dtype=np.float64), dtype=dtype) * torch.clamp(m - d, min=0).sum((1, 2))
+        clearance = d.reshape(n, -1).min(1).values
+    else:
+        dist = d = torch.zeros(n, x.shape[2], 0, dtype=dtype)
+        cost = (x * 0).sum((1, 2))
+        clearance = torch.full((n,), float("inf"), dtype=dtype)
+    if want_grad:
+        cost.sum().backward()
+        out["grad"] = x.grad.detach().to(torch.float64).numpy()
+    f64 = lambda t: t.detach().to(torch.float64).numpy()  # noqa: E731
+    out.update(cost=f64(cost), clearance=f64(clearance), d=f64(d), dist=f64(dist), margin=np.asarray(margin, dtype=np.float64))
+    return out
+
+
+def self_margins(ev):
+    """distance of an evaluate_self result from the term's kinks: hinge = min |m - d|, centre = smallest centre distance; active share"""
+    if ev["d"].size == 0:
+        return dict(hinge=float("inf"), centre=float("inf"), active=0.0)
+    h = ev["margin"].reshape(-1, 1, 1) - ev["d"]
+    return dict(hinge=float(np.abs(h).min()), centre=float(ev["dist"].min()), active=float(np.mean(h > 0)))
+
+
+def assert_self_margins(ev, what=""):
+    mg = self_margins(ev)
+    for k in ("hinge", "centre"):
+        assert mg[k] >= MIN_GAP, f"{what}: inputs sit {mg[k]:.3e} m from a kink of the self term ({k}); pick another seed"
+    return mg
+
+
+# name -> L, sphere table, seed of sdf_reference.make_case (3 obstacles, one of them a true cylinder)
+CASES = {
+    "L1_custom": dict(L=1, spheres="custom", seed=1),
+    "L2_default": dict(L=2, spheres="default", seed=0),
+    "L48_default": dict(L=48, spheres="default", seed=1),
+    "L48_custom": dict(L=48, spheres="custom", seed=0),
+    "L62_default": dict(L=62, spheres="default", seed=0),
+    "L62_custom": dict(L=62, spheres="custom", seed=0),
+}
+N_OBSTACLES, N_CYLINDERS = 3, 1
+_cache = {}
+
+
+def check_case(name, seed=None):
+    """inputs of a case with the checkers' float64 results - obstacle part (sdf_reference.evaluate) and self term - at t = 0 and at
+    T_CHECK, both asserted away from their kinks.  Computed once per case and shared; callers do not modify it."""
+    c = CASES[name]
+    seed = c["seed"] if seed is None else seed
+    if (name, seed) in _cache:
+        return _cache[(name, seed)]
+    cfgs = mixed_cfgs()
+    inp = R.make_case(seed, B, c["L"], N_OBSTACLES, N_CYLINDERS)
+    sph = R.case_spheres(c["spheres"])
+    mask = franka.self_collision_pairs()
+    args = (inp["joints"], inp["start"], inp["goal"], inp["obstacle_config"], inp["kinds"], sph)
+    mt, smt, w = cfgs["sdf_margin"][:, T_CHECK - 1], cfgs["sdf_self_margin"][:, T_CHECK - 1], cfgs["sdf_self_weight"]
+    sdf0 = R.evaluate(*args, np.zeros(B), cfgs["smoothness"], want_grad=False)
+    R.assert_margins(sdf0, f"{name} seed {seed} t=0")
+    sdft = R.evaluate(*args, mt, cfgs["smoothness"])
+    R.assert_margins(sdft, f"{name} seed {seed} t={T_CHECK}")
+    self0 = evaluate_self(inp["joints"], sph, mask, np.zeros(B), w)
+    selft = evaluate_self(inp["joints"], sph, mask, smt, w)
+    # the margins of EVERY row (the report evaluates them all): weight 1 everywhere
+    every = evaluate_self(inp["joints"], sph, mask, smt, np.ones(B), want_grad=False)
+    mg0, mgt = assert_self_margins(self0, f"{name} seed {seed} t=0"), assert_self_margins(every, f"{name} seed {seed} t={T_CHECK}")
+    assert all(np.abs(selft["grad"][r]).max() > 0 for r in SELF_ROWS), f"{name} seed {seed}: a weighted row has a zero self gradient"
+    assert not selft["grad"][[r for r in range(B) if r not in SELF_ROWS]].any()
+    out = dict(inp, name=name, spheres=sph, custom=c["spheres"] == "custom", mask=mask, cfgs=cfgs, L=c["L"], seed=seed, args=args, sdf0=sdf0, sdft=sdft,
+               self0=self0, selft=selft, margins0=mg0, marginst=mgt)
+    _cache[(name, seed)] = out
+    return out
+
+
+def yardstick(case, t):
+    """deviation of the same formulas in CPU float32 from float64: the whole gradient of the weighted rows (obstacle part + self term,
+    relative to its largest element), the self cost (relative to the largest) and the minimum self clearance (absolute)"""
+    cfgs = case["cfgs"]
+    m = np.zeros(B) if t == 0 else cfgs["sdf_self_margin"][:, t - 1]
+    ev = case["self0"] if t == 0 else case["selft"]
+    e32 = evaluate_self(case["joints"], case["spheres"], case["mask"], m, cfgs["sdf_self_weight"], dtype=torch.float32)
+    out = dict(cost=float(np.abs(e32["cost"] - ev["cost"]).max() / max(np.abs(ev["cost"]).max(), 1e-300)),
+               clearance_abs=float(np.abs(e32["clearance"] - ev["clearance"]).max()))
+    if t:
+        s32 = R.evaluate(*case["args"], cfgs["sdf_margin"][:, t - 1], cfgs["smoothness"], dtype=torch.float32)
+        rows = list(SELF_ROWS)
+        ref = total_gradient(case)[rows]
+        out["grad"] = float(np.abs(s32["grad"][rows] + e32["grad"][rows] - ref).max() / np.abs(ref).max())
+    return out
+
+
+def total_gradient(case):
+    """the float64 raw gradient of the SDF rows at T_CHECK: obstacle part + smoothness + self term (zero on the other rows)"""
+    g = np.zeros_like(case["sdft"]["grad"])
+    rows = list(SDF_ROWS)
+    g[rows] = case["sdft"]["grad"][rows] + case["selft"]["grad"][rows]
+    return g
