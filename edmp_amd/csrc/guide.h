@@ -13,6 +13,33 @@ struct RobotConst {
     double qlo[7], qhi[7];
 };
 
+// self-clearance term of the SDF guide (sdf.hip, edmp_sdf_set_self): belongs to the sphere table, whose drop() drops it
+struct SelfTerm {
+    bool set = false;          // a pair list is bound (it may be empty)
+    int32_t* pairs = nullptr;  // [np][4] = sphere s, sphere u (link-sorted indices), link of s, link of u; s ascending, then u
+    int np = 0;
+    int32_t* rows = nullptr;   // [n] indices of the rows whose weight is > 0
+    int n = 0;                 // (0: the gradient paths launch what they launched without the term)
+    double* weight = nullptr;  // [B]
+    double* margin = nullptr;  // [B][T]
+    void drop() { n = np = 0; set = false; }
+};
+
+// sphere signed-distance guide (sdf.hip, edmp_sdf_set): belongs to the rows it was set for
+struct SdfTable {
+    float* sph = nullptr;       // [ns][4] centre | radius in link-box frames, sorted by link
+    int ns = 0;                 // spheres (0: no table bound)
+    int link_off[EDMP_N_LINKS + 1] = {};
+    int32_t* rows = nullptr;    // [n] indices of the SDF rows
+    int n = 0;                  // SDF rows of the batch (0: the gradient paths launch what they always launched)
+    double* margin = nullptr;   // [B][T]
+    double* smooth = nullptr;   // [B]
+    std::vector<int32_t> row_h; // [B] host copy of edmp_sdf_set's 0/1 flags (edmp_sdf_set_self checks its weights against it)
+    SelfTerm self;
+    void drop() { n = ns = 0; self.drop(); }  // a new table, or new rows, drop the term too
+    std::array<void*, 8> blocks() const { return {sph, rows, margin, smooth, self.pairs, self.rows, self.weight, self.margin}; }  // (guide_destroy)
+};
+
 struct Guide {
     int no = 0, G = 0, T = 0;
     float* aabb = nullptr;  // [G][T+1][no][6]
@@ -52,23 +79,7 @@ struct Guide {
     float* cand_vol = nullptr;   // [cand_cap]
     double* cand_key = nullptr;  // [cand_cap]
     int cand_cap = 0;
-    // sphere signed-distance guide (sdf.hip, edmp_sdf_set): row-level like the arrays above; edmp_rows_set drops it
-    float* sdf_sph = nullptr;       // [sdf_ns][4] centre | radius in link-box frames, sorted by link
-    int sdf_ns = 0;                 // spheres (0: no table bound)
-    int sdf_link_off[EDMP_N_LINKS + 1] = {};
-    int32_t* sdf_rows = nullptr;    // [sdf_n] indices of the SDF rows
-    int sdf_n = 0;                  // SDF rows of the batch (0: the gradient paths launch what they always launched)
-    double* sdf_margin = nullptr;   // [B][T]
-    double* sdf_smooth = nullptr;   // [B]
-    std::vector<int32_t> sdf_row_h; // [B] host copy of edmp_sdf_set's 0/1 flags (edmp_sdf_set_self checks its weights against it)
-    // self-clearance term of the SDF guide (sdf.hip, edmp_sdf_set_self): belongs to the sphere table; edmp_sdf_set drops it
-    bool self_set = false;          // a pair list is bound (it may be empty)
-    int32_t* self_pairs = nullptr;  // [self_np][4] = sphere s, sphere u (link-sorted indices), link of s, link of u; s ascending, then u
-    int self_np = 0;
-    int32_t* self_rows = nullptr;   // [self_n] indices of the rows whose weight is > 0
-    int self_n = 0;                 // (0: the gradient paths launch what they launched without the term)
-    double* self_weight = nullptr;  // [B]
-    double* self_margin = nullptr;  // [B][T]
+    SdfTable sdf;  // row-level like the arrays above: edmp_rows_set drops it
 };
 
 // sdf.hip: overwrite graw / rowsq of the bound guide's SDF rows (no SDF rows: nothing is launched)

@@ -71,9 +71,9 @@ void guide_destroy(edmp_ctx* ctx, Guide* g) {
     if (!g) return;
     for (void* p : {(void*)g->aabb, (void*)g->row_class, (void*)g->method, (void*)g->grad_norm, (void*)g->sched, (void*)g->graw,
                     (void*)g->rowsq, (void*)g->sumsq, (void*)g->startgoal, (void*)g->vol_rows, (void*)g->obb, (void*)g->kind, (void*)g->flags,
-                    (void*)g->cls_no, (void*)g->cand_vol, (void*)g->cand_key, (void*)g->sdf_sph, (void*)g->sdf_rows, (void*)g->sdf_margin,
-                    (void*)g->sdf_smooth, (void*)g->self_pairs, (void*)g->self_rows, (void*)g->self_weight, (void*)g->self_margin})
+                    (void*)g->cls_no, (void*)g->cand_vol, (void*)g->cand_key})
         ctx_release(ctx, p);
+    for (void* p : g->sdf.blocks()) ctx_release(ctx, p);
     delete g;
 }
 
@@ -699,7 +699,7 @@ int guide_raw_gradient_from_X(edmp_ctx* ctx, const double* X_dev, int B, int N, 
     if (rc) return rc;
     rc = launch_guide<GM_GRAD, double>(ctx, X_dev, N, 1, B, N - 2, t, 1, 1, g->graw, g->rowsq);
     if (rc) return rc;
-    if (g->sdf_n) rc = sdf_overlay(ctx, X_dev, N, 1, N - 2, t, 1);  // the SDF rows' gradient replaces the volume gradient (sdf.hip)
+    if (g->sdf.n) rc = sdf_overlay(ctx, X_dev, N, 1, N - 2, t, 1);  // the SDF rows' gradient replaces the volume gradient (sdf.hip)
     if (rc) return rc;
     // a scene batch always reduces here: one sum per scene, each over its own rows (the update kernel's in-block re-sum is one sum)
     if (g->S > 1) hipLaunchKernelGGL(reduce_rowsq_kernel, dim3(g->S), dim3(256), 0, ctx->stream, g->rowsq, g->rps, g->sumsq);
@@ -935,9 +935,7 @@ extern "C" int edmp_rows_set(edmp_ctx* ctx, const int32_t* row_class, const floa
     g->B = B;
     g->rps = rps;
     g->rows_T = T;
-    g->sdf_n = g->sdf_ns = 0;  // an SDF table (edmp_sdf_set) belongs to the rows it was set for
-    g->self_n = g->self_np = 0;  // (and its self term with it)
-    g->self_set = false;
+    g->sdf.drop();  // an SDF table (edmp_sdf_set) belongs to the rows it was set for, and its self term with it
     return EDMP_OK;
 }
 
@@ -1009,7 +1007,7 @@ extern "C" int edmp_guide_gradient_dev(edmp_ctx* ctx, const double* joints_dev, 
     if (rc) return rc;
     rc = launch_guide<GM_GRAD, double>(ctx, joints_dev, L, 0, B, L, t, 1, 0, g->graw, g->rowsq);
     if (rc) return rc;
-    if (g->sdf_n) rc = sdf_overlay(ctx, joints_dev, L, 0, L, t, 0);
+    if (g->sdf.n) rc = sdf_overlay(ctx, joints_dev, L, 0, L, t, 0);
     if (rc) return rc;
     hipLaunchKernelGGL(reduce_rowsq_kernel, dim3(1), dim3(256), 0, ctx->stream, g->rowsq, B, g->sumsq);
     int total = B * 7 * L;

@@ -20,9 +20,9 @@
 //   * ||.|| at exactly 0 (and rho = 0 on a cylinder axis, |p_k| at p_k = 0) contributes a zero gradient - torch gives NaN at the norm.
 //
 // Layout (that of guide_kernel<GM_GRAD, ., 4>): one 256-thread workgroup per row, lane = padded waypoint, the four waves take the
-// link groups {0,1,2}, {3,4}, {5,6}, {hand, finger}; per-joint partials meet in LDS and are added as ((w0 + w1) + w2) + w3.  The row's
+// link groups {0,1,2}, {3,4}, {5,6}, {hand, finger} and meet in wave 0 (meet_in_wave0): no atomics, every sum has one order.  The row's
 // obstacles are staged once per workgroup as f32 [16] = rotation (row-major, columns = axes) | centre | half extents | kind, the sphere
-// table (sorted by link on the host, table order kept inside a link) as f32 [4] = centre | radius.  No atomics: every sum has one order.
+// table (sorted by link on the host, table order kept inside a link) as f32 [4] = centre | radius.
 //
 // Scene batch (edmp_scene_batch_set_sdf): a row is one workgroup, hence one scene = row / rps.  The workgroup stages the obstacles and
 // kinds of ITS scene only (Guide::obb / Guide::kind hold every scene's primitives, scene after scene) and loops over that scene's own
@@ -30,8 +30,9 @@
 // smoothness, graw and rowsq are indexed by the global row.  Everything behind the staging is the row's own arithmetic, so a row of
 // scene s computes what it computes on scene s's own guide.  One scene: rps = 0, slice 0 = the whole table.
 //
-// Self-clearance term (sdf_self_kernel, edmp_sdf_set_self): on the same sphere model, centres in f32 by the statements of sdf_row from
-// the same link-sorted table.  For an SDF row r at step t, over the sphere pairs (s, u) with mask[link_s][link_u], link_s < link_u:
+// Self-clearance term (sdf_self_kernel, edmp_sdf_set_self): on the same sphere model and link-sorted table; the lane's joints, sphere
+// centres, wave combine and rowsq are sdf_row's by the helpers below.  For an SDF row r at step t, over the sphere pairs (s, u) with
+// mask[link_s][link_u], link_s < link_u:
 //   d(w; s, u) = ||c_s(q_w) - c_u(q_w)|| - r_s - r_u
 //   self(r)    = weight_r * sum_{w=1..L} sum_{(s,u)} max(0, m_r(t) - d(w; s, u))       m_r(t) = self_margin[r][t - 1] for t >= 1, 0 at t = 0
 // Interior waypoints only: no start / goal pair and nothing of the scene, so the term is the same inside a scene batch.  The hinge is
@@ -39,9 +40,8 @@
 // or below link_s's frame moves both centres rigidly and n . (z_i x (c_s - c_u)) is identically zero; only the joints i with
 // frame(link_s) < i <= frame(link_u) contribute, d d / d q_i = -n . (z_i x (c_u - o_i)), so d self / d q_i = weight * n . (z_i x (c_u - o_i))
 // on an active pair.  sdf_self_kernel runs after sdf_guide_kernel over the rows whose weight is > 0, adds this to the row's graw and
-// rewrites rowsq[r] from the final elements as sdf_row forms it.  Every wave walks the whole chain (it needs every z_i, o_i of its lane),
-// the link frames meet in LDS, pair p of the list (s ascending, then u) belongs to wave p % 4, a wave adds its pairs in list order and
-// the four partials are added as ((w0 + w1) + w2) + w3: one order, no atomics.
+// rewrites rowsq[r].  Every wave walks the whole chain (it needs every z_i, o_i of its lane), the link frames meet in LDS, pair p of
+// the list (s ascending, then u) belongs to wave p % 4 and a wave adds its pairs in list order.
 #include "common.h"
 #include "chain.h"
 #include "guide.h"
@@ -51,14 +51,23 @@
 
 namespace edmp {
 
-struct SdfArgs {
+// what every kernel here takes of a row: its L interior waypoints, its margin schedule and where its results go
+struct RowView {
     const double* joints;  // element (r, j, wi) at joints[(r*7 + j)*ldw + off + wi], wi in 0..L-1
     int ldw, off;
     int L, t;
-    int do_clip;          // clip to the joint limits in f64 before the f32 cast (diffusion.py:328), as guide_kernel
-    const int32_t* rows;  // gradient: the SDF rows of the batch, one workgroup each
+    int do_clip;           // clip to the joint limits in f64 before the f32 cast (diffusion.py:328), as guide_kernel
+    const int32_t* rows;   // gradient: the rows of the batch that the kernel works on, one workgroup each
     const double* margin;  // [B][T]; read at t >= 1 only
     int T;
+    float* graw;           // gradient: [B][7][L]
+    double* rowsq;         // gradient: per-row sum g^2
+    double* cost;          // rows: [n]
+    double* clearance;     // rows: [n]
+};
+
+struct SdfArgs {
+    RowView v;             // rows: the SDF rows; margin: sdf_margin
     const double* smooth;  // [B], or nullptr = 0 (edmp_sdf_rows_dev on rows that are not the bound ones)
     const double* obb;     // [sum of the scenes' obstacles][16] f64, scene after scene
     const int32_t* kind;   // [the same]
@@ -68,10 +77,6 @@ struct SdfArgs {
     int ns;
     int link_off[EDMP_N_LINKS + 1];  // spheres of link l: [link_off[l], link_off[l+1])
     const float* startgoal;          // [14] f32 (scene batch: [S][14])
-    float* graw;                     // gradient: [B][7][L]
-    double* rowsq;                   // gradient: per-row sum g^2
-    double* cost;                    // rows: [n]
-    double* clearance;               // rows: [n]
 };
 
 // signed distance of the world point (cx, cy, cz) to the staged obstacle ob[16]; e[3] and the local point come back for the gradient
@@ -132,7 +137,94 @@ __device__ __forceinline__ void sdf_grad(const float* ob, float cx, float cy, fl
     for (int i = 0; i < 3; ++i) n[i] = fmaf(ob[i * 3 + 2], gl[2], fmaf(ob[i * 3 + 1], gl[1], ob[i * 3] * gl[0]));
 }
 
-// ROWS = false: the raw gradient of row a.rows[blockIdx.x] -> graw / rowsq (the contract of guide_kernel<GM_GRAD>).
+// ---- what the obstacle part (sdf_row) and the self term (sdf_self_row) share: the lane's waypoint, its chain, the wave combine ------
+// q = the joints of row r at padded waypoint w (0 and >= L+1 repeat the first / last interior waypoint), loaded as guide_kernel loads
+// them: f64, clipped under do_clip, then f32
+__device__ __forceinline__ void lane_joints(const RowView& v, const RobotConst& rc, int r, int w, float q[7]) {
+    const int wi = min(max(w - 1, 0), v.L - 1);
+#pragma unroll
+    for (int j = 0; j < 7; ++j) {
+        double xd = v.joints[((size_t)r * 7 + j) * v.ldw + v.off + wi];
+        if (v.do_clip) {
+            xd = xd < rc.qlo[j] ? rc.qlo[j] : xd;
+            xd = xd > rc.qhi[j] ? rc.qhi[j] : xd;
+        }
+        q[j] = (float)xd;
+    }
+}
+
+__device__ __forceinline__ float row_margin(const RowView& v, int r) { return (v.t >= 1) ? (float)v.margin[(size_t)r * v.T + (v.t - 1)] : 0.f; }
+
+// joint j of the lane's chain: (R | o) steps over it, zax[j] / org[j] take its axis and origin
+__device__ __forceinline__ void joint_step(const RobotConst& rc, const float q[7], int j, float R[3][3], float o[3], float zax[7][3], float org[7][3]) {
+    dh_step(R, o, sinf(q[j]), cosf(q[j]), rc.dh[j]);
+#pragma unroll
+    for (int i = 0; i < 3; ++i) {
+        zax[j][i] = R[i][2];
+        org[j][i] = o[i];
+    }
+}
+
+// world centre of the sphere sp = centre | radius of the link whose frame is LR | Lo
+__device__ __forceinline__ void sphere_world(const float LR[3][3], const float Lo[3], const float* sp, float c[3]) {
+#pragma unroll
+    for (int i = 0; i < 3; ++i) c[i] = fmaf(LR[i][2], sp[2], fmaf(LR[i][1], sp[1], LR[i][0] * sp[0])) + Lo[i];
+}
+
+// n . (z x (c - o)): what a unit turn of the joint with axis z through o moves the point c along n
+__device__ __forceinline__ float screw_dot(const float n[3], const float z[3], const float o[3], const float c[3]) {
+    const float rx = c[0] - o[0], ry = c[1] - o[1], rz = c[2] - o[2];
+    const float kx = z[1] * rz - z[2] * ry;
+    const float ky = z[2] * rx - z[0] * rz;
+    const float kz = z[0] * ry - z[1] * rx;
+    return fmaf(n[2], kz, fmaf(n[1], ky, n[0] * kx));
+}
+
+// The four waves' partials of a lane meet in wave 0 as ((w0 + w1) + w2) + w3: the seven gradient elements g, or (ROWS) the f32 minimum
+// dmin and the f64 sum cacc.  Waves 1..3 leave theirs in s_g / s_c (ROWS: s_g[.][0] holds dmin); false: the wave is done
+template <bool ROWS>
+__device__ __forceinline__ bool meet_in_wave0(float (*s_g)[7][64], double (*s_c)[64], int wv, int lane, float g[7], float& dmin, double& cacc) {
+    if (wv > 0) {
+        if (ROWS) {
+            s_g[wv - 1][0][lane] = dmin;
+            s_c[wv - 1][lane] = cacc;
+        } else {
+#pragma unroll
+            for (int i = 0; i < 7; ++i) s_g[wv - 1][i][lane] = g[i];
+        }
+    }
+    __syncthreads();
+    if (wv > 0) return false;
+    if (ROWS) {
+        cacc = ((cacc + s_c[0][lane]) + s_c[1][lane]) + s_c[2][lane];
+        dmin = fminf(fminf(fminf(dmin, s_g[0][0][lane]), s_g[1][0][lane]), s_g[2][0][lane]);
+    } else {
+#pragma unroll
+        for (int i = 0; i < 7; ++i) g[i] = ((g[i] + s_g[0][i][lane]) + s_g[1][i][lane]) + s_g[2][i][lane];
+    }
+    return true;
+}
+
+// rowsq = the sum over the wave's lanes of the lane's seven final gradient elements squared
+__device__ __forceinline__ void store_rowsq(const float g[7], int lane, double* rowsq) {
+    float sq = 0.f;
+#pragma unroll
+    for (int i = 0; i < 7; ++i) sq = fmaf(g[i], g[i], sq);
+    const double tot = wave_sum((double)sq);
+    if (lane == 0) *rowsq = tot;
+}
+
+// the report of a row: scale x the sum of the lanes' costs, and the smallest of their clearances
+__device__ __forceinline__ void store_report(double cacc, float dmin, double scale, int lane, double* cost, double* clearance) {
+    const double tot = wave_sum(cacc);
+    dmin = wave_min(dmin);
+    if (lane == 0) {
+        *cost = scale * tot;
+        *clearance = (double)dmin;
+    }
+}
+
+// ROWS = false: the raw gradient of row a.v.rows[blockIdx.x] -> graw / rowsq (the contract of guide_kernel<GM_GRAD>).
 // ROWS = true: cost and minimum clearance of row blockIdx.x.  Cost: per lane and wave the hinge terms in f64 in (link, sphere) order,
 // the four waves' partials as ((w0 + w1) + w2) + w3, plus the lane's smoothness term, then wave_sum over the lanes.
 template <bool ROWS>
@@ -143,9 +235,9 @@ __device__ __forceinline__ void sdf_row(const SdfArgs& a, const RobotConst& rc) 
     __shared__ double s_c[3][64];    // ROWS: cost partials of waves 1..3
     const int lane = threadIdx.x & 63;
     const int wv = __builtin_amdgcn_readfirstlane(threadIdx.x >> 6);
-    const int r = ROWS ? (int)blockIdx.x : a.rows[blockIdx.x];
+    const int r = ROWS ? (int)blockIdx.x : a.v.rows[blockIdx.x];
     const int scene = __builtin_amdgcn_readfirstlane(a.rps ? r / a.rps : 0);  // (one row, one scene: workgroup-uniform)
-    const int L = a.L, no = min(a.sc_cnt[scene], EDMP_MAX_OBSTACLES);
+    const int L = a.v.L, no = min(a.sc_cnt[scene], EDMP_MAX_OBSTACLES);
     const double* obb = a.obb + (size_t)a.sc_off[scene] * 16;
     const int32_t* kind = a.kind + a.sc_off[scene];
     const float* sg = a.startgoal + scene * 14;  // this row's scene's start | goal
@@ -159,65 +251,50 @@ __device__ __forceinline__ void sdf_row(const SdfArgs& a, const RobotConst& rc) 
     for (int i = threadIdx.x; i < a.ns * 4; i += 256) s_sph[i] = a.spheres[i];
     __syncthreads();
 
-    const float m = (a.t >= 1) ? (float)a.margin[(size_t)r * a.T + (a.t - 1)] : 0.f;
+    const float m = row_margin(a.v, r);
     const float lam = a.smooth ? (float)a.smooth[r] : 0.f;
-    const int my_jmax = wave_last_joint(wv);
 
-    // this lane's joint vector: padded waypoint w = lane (0 start, 1..L interior, >= L+1 goal), loaded as guide_kernel loads it
+    // this lane's joint vector: padded waypoint w = lane (0 start, 1..L interior, >= L+1 goal)
     const int w = lane;
     float q[7];
-    {
-        const int wi = min(max(w - 1, 0), L - 1);
-        double xr[7];
+    lane_joints(a.v, rc, r, w, q);
 #pragma unroll
-        for (int j = 0; j < 7; ++j) xr[j] = a.joints[((size_t)r * 7 + j) * a.ldw + a.off + wi];
-#pragma unroll
-        for (int j = 0; j < 7; ++j) {
-            double xd = xr[j];
-            if (a.do_clip) {
-                xd = xd < rc.qlo[j] ? rc.qlo[j] : xd;
-                xd = xd > rc.qhi[j] ? rc.qhi[j] : xd;
-            }
-            const float vs = sg[j], vg = sg[7 + j];
-            q[j] = (w == 0) ? vs : ((w > L) ? vg : (float)xd);
-        }
+    for (int j = 0; j < 7; ++j) {
+        const float vs = sg[j], vg = sg[7 + j];
+        q[j] = (w == 0) ? vs : ((w > L) ? vg : q[j]);
     }
     const bool interior = (w >= 1) && (w <= L);
 
-    float R[3][3] = {{1, 0, 0}, {0, 1, 0}, {0, 0, 1}};
-    float o[3] = {0, 0, 0};
-    float zax[7][3], org[7][3];
     float g[7] = {0, 0, 0, 0, 0, 0, 0};
     double cacc = 0.0;
     float dmin = INFINITY;
-
+    // the wave walks the chain up to its last link's joint (the loops stay here: as a walk that takes the sphere loop as its per-link
+    // action, sdf_guide_kernel compiled to 155 VGPRs instead of 132)
+    float R[3][3] = {{1, 0, 0}, {0, 1, 0}, {0, 0, 1}};
+    float o[3] = {0, 0, 0};
+    float zax[7][3], org[7][3];
+    const int my_jmax = wave_last_joint(wv);
 #pragma unroll
     for (int j = 0; j < 7; ++j) {
         if (j > my_jmax) break;  // (wave-uniform)
-        dh_step(R, o, sinf(q[j]), cosf(q[j]), rc.dh[j]);
-#pragma unroll
-        for (int i = 0; i < 3; ++i) {
-            zax[j][i] = R[i][2];
-            org[j][i] = o[i];
-        }
+        joint_step(rc, q, j, R, o, zax, org);
 #pragma unroll
         for (int ll = 0; ll < 3; ++ll) {
             if (ll > 0 && j != 6) continue;
-            const int l = (ll == 0) ? j : 6 + ll;
-            if (link_wave(l) != wv) continue;  // another wave's link (wave-uniform)
+            const int l = (ll == 0) ? j : 6 + ll;  // hand and finger ride on joint 6
+            if (link_wave(l) != wv) continue;      // another wave's link (wave-uniform)
             float LR[3][3], Lo[3];
             frame_apply(R, o, rc.sf[l], LR, Lo);
             const int s1 = a.link_off[l + 1];
             for (int s = a.link_off[l]; s < s1; ++s) {
                 const float* sp = s_sph + s * 4;
-                const float cx = fmaf(LR[0][2], sp[2], fmaf(LR[0][1], sp[1], LR[0][0] * sp[0])) + Lo[0];
-                const float cy = fmaf(LR[1][2], sp[2], fmaf(LR[1][1], sp[1], LR[1][0] * sp[0])) + Lo[1];
-                const float cz = fmaf(LR[2][2], sp[2], fmaf(LR[2][1], sp[1], LR[2][0] * sp[0])) + Lo[2];
+                float c[3];
+                sphere_world(LR, Lo, sp, c);
                 float best = INFINITY;
                 int bi = 0;
                 for (int ob = 0; ob < no; ++ob) {
                     float p[3], e[3];
-                    const float d = sdf_one(s_ob + ob * 16, cx, cy, cz, p, e);
+                    const float d = sdf_one(s_ob + ob * 16, c[0], c[1], c[2], p, e);
                     if (d < best) {
                         best = d;
                         bi = ob;
@@ -230,32 +307,16 @@ __device__ __forceinline__ void sdf_row(const SdfArgs& a, const RobotConst& rc) 
                     if (interior && h > 0.f) cacc += (double)h;
                 } else if (interior && h > 0.f) {
                     float n[3];
-                    sdf_grad(s_ob + bi * 16, cx, cy, cz, n);
+                    sdf_grad(s_ob + bi * 16, c[0], c[1], c[2], n);
                     // d c / d q_i = z_i x (c - o_i), i <= j; the hinge turns the sign
 #pragma unroll
-                    for (int i = 0; i <= j; ++i) {
-                        const float rx = cx - org[i][0], ry = cy - org[i][1], rz = cz - org[i][2];
-                        const float kx = zax[i][1] * rz - zax[i][2] * ry;
-                        const float ky = zax[i][2] * rx - zax[i][0] * rz;
-                        const float kz = zax[i][0] * ry - zax[i][1] * rx;
-                        g[i] -= fmaf(n[2], kz, fmaf(n[1], ky, n[0] * kx));
-                    }
+                    for (int i = 0; i <= j; ++i) g[i] -= screw_dot(n, zax[i], org[i], c);
                 }
             }
         }
     }
 
-    if (wv > 0) {
-        if (ROWS) {
-            s_g[wv - 1][0][lane] = dmin;
-            s_c[wv - 1][lane] = cacc;
-        } else {
-#pragma unroll
-            for (int i = 0; i < 7; ++i) s_g[wv - 1][i][lane] = g[i];
-        }
-    }
-    __syncthreads();
-    if (wv > 0) return;
+    if (!meet_in_wave0<ROWS>(s_g, s_c, wv, lane, g, dmin, cacc)) return;
     // wave 0 holds every joint of its lane's waypoint: the neighbours' joints come by two shuffles
     float qp[7], qn[7];
 #pragma unroll
@@ -264,8 +325,6 @@ __device__ __forceinline__ void sdf_row(const SdfArgs& a, const RobotConst& rc) 
         qn[j] = __shfl_down(q[j], 1, 64);
     }
     if (ROWS) {
-        cacc = ((cacc + s_c[0][lane]) + s_c[1][lane]) + s_c[2][lane];
-        dmin = fminf(fminf(fminf(dmin, s_g[0][0][lane]), s_g[1][0][lane]), s_g[2][0][lane]);
         float ss = 0.f;
 #pragma unroll
         for (int j = 0; j < 7; ++j) {
@@ -274,26 +333,16 @@ __device__ __forceinline__ void sdf_row(const SdfArgs& a, const RobotConst& rc) 
         }
         if (w <= L) cacc += (double)(lam * ss);  // segment (w, w+1)
         if (w > L + 1) dmin = INFINITY;          // lanes behind the goal repeat it
-        const double tot = wave_sum(cacc);
-#pragma unroll
-        for (int s = 32; s > 0; s >>= 1) dmin = fminf(dmin, __shfl_xor(dmin, s, 64));
-        if (lane == 0) {
-            a.cost[r] = tot;
-            a.clearance[r] = (double)dmin;
-        }
+        store_report(cacc, dmin, 1.0, lane, a.v.cost + r, a.v.clearance + r);
     } else {
         const float l2 = 2.f * lam;
-        float sq = 0.f;
 #pragma unroll
         for (int i = 0; i < 7; ++i) {
-            float gi = ((g[i] + s_g[0][i][lane]) + s_g[1][i][lane]) + s_g[2][i][lane];
-            gi = fmaf(l2, fmaf(2.f, q[i], -qp[i]) - qn[i], gi);  // 2 lambda (2 q_w - q_{w-1} - q_{w+1})
-            gi = interior ? gi : 0.f;
-            if (interior) a.graw[((size_t)r * 7 + i) * L + (w - 1)] = gi;
-            sq = fmaf(gi, gi, sq);
+            const float gi = fmaf(l2, fmaf(2.f, q[i], -qp[i]) - qn[i], g[i]);  // 2 lambda (2 q_w - q_{w-1} - q_{w+1})
+            g[i] = interior ? gi : 0.f;
+            if (interior) a.v.graw[((size_t)r * 7 + i) * L + (w - 1)] = gi;
         }
-        const double tot = wave_sum((double)sq);
-        if (lane == 0) a.rowsq[r] = tot;
+        store_rowsq(g, lane, a.v.rowsq + r);
     }
 }
 
@@ -301,87 +350,57 @@ __global__ __launch_bounds__(256, 3) void sdf_guide_kernel(SdfArgs a, RobotConst
 __global__ __launch_bounds__(256, 4) void sdf_rows_kernel(SdfArgs a, RobotConst rc) { sdf_row<true>(a, rc); }
 
 struct SelfArgs {
-    const double* joints;  // as SdfArgs
-    int ldw, off;
-    int L, t;
-    int do_clip;
-    const int32_t* rows;    // gradient: the rows whose weight is > 0, one workgroup each
-    const double* margin;   // [B][T]; read at t >= 1 only
-    int T;
+    RowView v;              // rows: the rows whose weight is > 0; margin: self_margin; graw: the row's SDF gradient on entry
     const double* weight;   // [B], or nullptr = 1 (edmp_sdf_self_rows_dev on rows that are not the bound ones)
     const float* spheres;   // [ns][4] sorted by link
     const int32_t* pairs;   // [np][4] = s, u, link_s, link_u
     int np;
-    float* graw;            // gradient: [B][7][L], the row's SDF gradient on entry
-    double* rowsq;
-    double* cost;           // rows: [n]
-    double* clearance;      // rows: [n]
 };
 
-__device__ __forceinline__ void sphere_centre(const float* fr, int lane, const float* sp, float c[3]) {
-    // frame_apply's LR | Lo of the sphere's link, staged as fr[k][lane], k = row * 4 + column; the statements of sdf_row
-#pragma unroll
-    for (int i = 0; i < 3; ++i)
-        c[i] = fmaf(fr[(i * 4 + 2) * 64 + lane], sp[2], fmaf(fr[(i * 4 + 1) * 64 + lane], sp[1], fr[(i * 4) * 64 + lane] * sp[0])) + fr[(i * 4 + 3) * 64 + lane];
-}
-
-// ROWS = false: add the self gradient of row a.rows[blockIdx.x] to graw and rewrite rowsq.  ROWS = true: weighted self cost and the
+// ROWS = false: add the self gradient of row a.v.rows[blockIdx.x] to graw and rewrite rowsq.  ROWS = true: weighted self cost and the
 // minimum d over interior waypoints and listed pairs of row blockIdx.x (+inf without a pair).
 template <bool ROWS>
 __device__ __forceinline__ void sdf_self_row(const SelfArgs& a, const RobotConst& rc) {
-    __shared__ float s_fr[EDMP_N_LINKS][12][64];  // link frames of every lane's waypoint
+    __shared__ float s_fr[EDMP_N_LINKS][12][64];  // link frames LR | Lo of every lane's waypoint, k = row * 4 + column
     __shared__ float s_g[3][7][64];               // partials of waves 1..3 (ROWS: [w][0] minimum d)
     __shared__ double s_c[3][64];                 // ROWS: cost partials of waves 1..3
     const int lane = threadIdx.x & 63;
     const int wv = __builtin_amdgcn_readfirstlane(threadIdx.x >> 6);
-    const int r = ROWS ? (int)blockIdx.x : a.rows[blockIdx.x];
-    const int L = a.L;
-    const float m = (a.t >= 1) ? (float)a.margin[(size_t)r * a.T + (a.t - 1)] : 0.f;
+    const int r = ROWS ? (int)blockIdx.x : a.v.rows[blockIdx.x];
+    const int L = a.v.L;
+    const float m = row_margin(a.v, r);
 
-    // lane = padded waypoint as in sdf_row; the end lanes repeat an interior waypoint and are not counted
+    // lane = padded waypoint; the end lanes repeat an interior waypoint and are not counted
     const int w = lane;
     const bool interior = (w >= 1) && (w <= L);
     float q[7];
-    {
-        const int wi = min(max(w - 1, 0), L - 1);
-#pragma unroll
-        for (int j = 0; j < 7; ++j) {
-            double xd = a.joints[((size_t)r * 7 + j) * a.ldw + a.off + wi];
-            if (a.do_clip) {
-                xd = xd < rc.qlo[j] ? rc.qlo[j] : xd;
-                xd = xd > rc.qhi[j] ? rc.qhi[j] : xd;
-            }
-            q[j] = (float)xd;
-        }
-    }
+    lane_joints(a.v, rc, r, w, q);
 
+    // every wave walks the whole chain (sdf_row's loops) and stages the frames of its own link group
     float R[3][3] = {{1, 0, 0}, {0, 1, 0}, {0, 0, 1}};
     float o[3] = {0, 0, 0};
     float zax[7][3], org[7][3];
 #pragma unroll
     for (int j = 0; j < 7; ++j) {
-        dh_step(R, o, sinf(q[j]), cosf(q[j]), rc.dh[j]);
-#pragma unroll
-        for (int i = 0; i < 3; ++i) {
-            zax[j][i] = R[i][2];
-            org[j][i] = o[i];
-        }
+        joint_step(rc, q, j, R, o, zax, org);
 #pragma unroll
         for (int ll = 0; ll < 3; ++ll) {
             if (ll > 0 && j != 6) continue;
-            const int l = (ll == 0) ? j : 6 + ll;
-            if (link_wave(l) != wv) continue;  // another wave stages this link (wave-uniform)
+            const int l = (ll == 0) ? j : 6 + ll;  // hand and finger ride on joint 6
+            if (link_wave(l) != wv) continue;      // another wave's link (wave-uniform)
             float LR[3][3], Lo[3];
             frame_apply(R, o, rc.sf[l], LR, Lo);
 #pragma unroll
-            for (int i = 0; i < 3; ++i) {
-#pragma unroll
-                for (int k = 0; k < 3; ++k) s_fr[l][i * 4 + k][lane] = LR[i][k];
-                s_fr[l][i * 4 + 3][lane] = Lo[i];
-            }
+            for (int k = 0; k < 12; ++k) s_fr[l][k][lane] = (k & 3) == 3 ? Lo[k >> 2] : LR[k >> 2][k & 3];
         }
     }
     __syncthreads();
+    auto centre = [&](int l, const float* sp, float c[3]) {  // sphere_world on link l's staged frame
+        float LR[3][3], Lo[3];
+#pragma unroll
+        for (int k = 0; k < 12; ++k) ((k & 3) == 3 ? Lo[k >> 2] : LR[k >> 2][k & 3]) = s_fr[l][k][lane];
+        sphere_world(LR, Lo, sp, c);
+    };
 
     float g[7] = {0, 0, 0, 0, 0, 0, 0};
     double cacc = 0.0;
@@ -391,8 +410,8 @@ __device__ __forceinline__ void sdf_self_row(const SelfArgs& a, const RobotConst
         const float* sps = a.spheres + s * 4;
         const float* spu = a.spheres + u * 4;
         float cs[3], cu[3];
-        sphere_centre(&s_fr[ls][0][0], lane, sps, cs);
-        sphere_centre(&s_fr[lu][0][0], lane, spu, cu);
+        centre(ls, sps, cs);
+        centre(lu, spu, cu);
         const float dx = cs[0] - cu[0], dy = cs[1] - cu[1], dz = cs[2] - cu[2];
         const float nrm = sqrtf(fmaf(dz, dz, fmaf(dy, dy, dx * dx)));
         const float d = nrm - sps[3] - spu[3];
@@ -401,95 +420,52 @@ __device__ __forceinline__ void sdf_self_row(const SelfArgs& a, const RobotConst
             dmin = fminf(dmin, d);
             if (interior && h > 0.f) cacc += (double)h;
         } else if (interior && h > 0.f && nrm > 0.f) {
-            const float nx = dx / nrm, ny = dy / nrm, nz = dz / nrm;
+            const float n[3] = {dx / nrm, dy / nrm, dz / nrm};
             const int fs = min(ls, 6), fu = min(lu, 6);  // joint frame of a link (hand and finger ride on joint 6)
 #pragma unroll
             for (int i = 0; i < 7; ++i) {
                 if (i <= fs || i > fu) continue;  // (wave-uniform)
-                const float rx = cu[0] - org[i][0], ry = cu[1] - org[i][1], rz = cu[2] - org[i][2];
-                const float kx = zax[i][1] * rz - zax[i][2] * ry;
-                const float ky = zax[i][2] * rx - zax[i][0] * rz;
-                const float kz = zax[i][0] * ry - zax[i][1] * rx;
-                g[i] += fmaf(nz, kz, fmaf(ny, ky, nx * kx));
+                g[i] += screw_dot(n, zax[i], org[i], cu);
             }
         }
     }
 
-    if (wv > 0) {
-        if (ROWS) {
-            s_g[wv - 1][0][lane] = dmin;
-            s_c[wv - 1][lane] = cacc;
-        } else {
-#pragma unroll
-            for (int i = 0; i < 7; ++i) s_g[wv - 1][i][lane] = g[i];
-        }
-    }
-    __syncthreads();
-    if (wv > 0) return;
+    if (!meet_in_wave0<ROWS>(s_g, s_c, wv, lane, g, dmin, cacc)) return;
     const double wt = a.weight ? a.weight[r] : 1.0;
     if (ROWS) {
-        cacc = ((cacc + s_c[0][lane]) + s_c[1][lane]) + s_c[2][lane];
-        dmin = fminf(fminf(fminf(dmin, s_g[0][0][lane]), s_g[1][0][lane]), s_g[2][0][lane]);
         if (!interior) dmin = INFINITY;
-        const double tot = wave_sum(cacc);
-#pragma unroll
-        for (int sft = 32; sft > 0; sft >>= 1) dmin = fminf(dmin, __shfl_xor(dmin, sft, 64));
-        if (lane == 0) {
-            a.cost[r] = wt * tot;
-            a.clearance[r] = (double)dmin;
-        }
+        store_report(cacc, dmin, wt, lane, a.v.cost + r, a.v.clearance + r);
     } else {
         const float wf = (float)wt;
-        float sq = 0.f;
 #pragma unroll
         for (int i = 0; i < 7; ++i) {
             float gi = 0.f;
             if (interior) {
-                float* dst = a.graw + ((size_t)r * 7 + i) * L + (w - 1);
-                gi = fmaf(wf, ((g[i] + s_g[0][i][lane]) + s_g[1][i][lane]) + s_g[2][i][lane], *dst);
+                float* dst = a.v.graw + ((size_t)r * 7 + i) * L + (w - 1);
+                gi = fmaf(wf, g[i], *dst);
                 *dst = gi;
             }
-            sq = fmaf(gi, gi, sq);
+            g[i] = gi;
         }
-        const double tot = wave_sum((double)sq);
-        if (lane == 0) a.rowsq[r] = tot;
+        store_rowsq(g, lane, a.v.rowsq + r);
     }
 }
 
 __global__ __launch_bounds__(256) void sdf_self_kernel(SelfArgs a, RobotConst rc) { sdf_self_row<false>(a, rc); }
 __global__ __launch_bounds__(256) void sdf_self_rows_kernel(SelfArgs a, RobotConst rc) { sdf_self_row<true>(a, rc); }
 
+static RowView row_view(const Guide* g, const double* joints, int ldw, int off, int L, int t, int do_clip, const int32_t* rows, const double* margin) {
+    return RowView{joints, ldw, off, L, t, do_clip, rows, margin, g->rows_T, g->graw, g->rowsq, nullptr, nullptr};
+}
+
 static void fill_self_args(const Guide* g, SelfArgs& a, const double* joints, int ldw, int off, int L, int t, int do_clip) {
-    a.joints = joints;
-    a.ldw = ldw;
-    a.off = off;
-    a.L = L;
-    a.t = t;
-    a.do_clip = do_clip;
-    a.rows = g->self_rows;
-    a.margin = g->self_margin;
-    a.T = g->rows_T;
-    a.weight = g->self_weight;
-    a.spheres = g->sdf_sph;
-    a.pairs = g->self_pairs;
-    a.np = g->self_np;
-    a.graw = g->graw;
-    a.rowsq = g->rowsq;
-    a.cost = nullptr;
-    a.clearance = nullptr;
+    const SelfTerm& s = g->sdf.self;
+    a = SelfArgs{row_view(g, joints, ldw, off, L, t, do_clip, s.rows, s.margin), s.weight, g->sdf.sph, s.pairs, s.np};
 }
 
 static void fill_args(const Guide* g, SdfArgs& a, const double* joints, int ldw, int off, int L, int t, int do_clip) {
-    a.joints = joints;
-    a.ldw = ldw;
-    a.off = off;
-    a.L = L;
-    a.t = t;
-    a.do_clip = do_clip;
-    a.rows = g->sdf_rows;
-    a.margin = g->sdf_margin;
-    a.T = g->rows_T;
-    a.smooth = g->sdf_smooth;
+    a.v = row_view(g, joints, ldw, off, L, t, do_clip, g->sdf.rows, g->sdf.margin);
+    a.smooth = g->sdf.smooth;
     a.obb = g->obb;
     a.kind = g->kind;
     a.rps = (g->S > 1) ? g->rps : 0;
@@ -497,30 +473,67 @@ static void fill_args(const Guide* g, SdfArgs& a, const double* joints, int ldw,
         a.sc_off[s] = s < g->S ? g->scene_off_h[s] : 0;
         a.sc_cnt[s] = s < g->S ? g->scene_no_h[s] : 0;
     }
-    a.spheres = g->sdf_sph;
-    a.ns = g->sdf_ns;
-    for (int l = 0; l <= EDMP_N_LINKS; ++l) a.link_off[l] = g->sdf_link_off[l];
+    a.spheres = g->sdf.sph;
+    a.ns = g->sdf.ns;
+    for (int l = 0; l <= EDMP_N_LINKS; ++l) a.link_off[l] = g->sdf.link_off[l];
     a.startgoal = g->startgoal;
-    a.graw = g->graw;
-    a.rowsq = g->rowsq;
-    a.cost = nullptr;
-    a.clearance = nullptr;
 }
 
 // guide.hip's gradient paths, after guide_kernel<GM_GRAD> and before the rowsq reduction: the SDF rows' graw / rowsq are overwritten
 int sdf_overlay(edmp_ctx* ctx, const double* joints, int ldw, int off, int L, int t, int do_clip) {
     Guide* g = ctx->guide;
-    if (!g || g->sdf_n == 0) return EDMP_OK;
+    if (!g || g->sdf.n == 0) return EDMP_OK;
     SdfArgs a;
     fill_args(g, a, joints, ldw, off, L, t, do_clip);
-    hipLaunchKernelGGL(sdf_guide_kernel, dim3(g->sdf_n), dim3(256), 0, ctx->stream, a, g->rc);
+    hipLaunchKernelGGL(sdf_guide_kernel, dim3(g->sdf.n), dim3(256), 0, ctx->stream, a, g->rc);
     EDMP_HIP_CHECK(hipGetLastError());
-    if (g->self_n > 0 && g->self_np > 0) {  // the self term of the weighted rows, on top of what sdf_guide_kernel left
+    if (g->sdf.self.n > 0 && g->sdf.self.np > 0) {  // the self term of the weighted rows, on top of what sdf_guide_kernel left
         SelfArgs sa;
         fill_self_args(g, sa, joints, ldw, off, L, t, do_clip);
-        hipLaunchKernelGGL(sdf_self_kernel, dim3(g->self_n), dim3(256), 0, ctx->stream, sa, g->rc);
+        hipLaunchKernelGGL(sdf_self_kernel, dim3(g->sdf.self.n), dim3(256), 0, ctx->stream, sa, g->rc);
         EDMP_HIP_CHECK(hipGetLastError());
     }
+    return EDMP_OK;
+}
+
+// row b as a message names it; rps > 0 (a scene batch): the rows run scene after scene, named by the scene and the row inside it
+static const char* row_name(char (&buf)[48], int b, int rps) {
+    if (rps) snprintf(buf, sizeof(buf), "scene %d, row %d", b / rps, b % rps);
+    else snprintf(buf, sizeof(buf), "row %d", b);
+    return buf;
+}
+
+// a [n][T] schedule of margins (name: what the message calls a value) is finite and >= 0
+static int check_schedule(const char* what, const char* name, const double* v, int n, int T, int rps) {
+    char where[48];
+    for (size_t i = 0; i < (size_t)n * T; ++i)
+        EDMP_REQUIRE(std::isfinite(v[i]) && v[i] >= 0.0, "%s: %s, step %d: %s %g must be finite and >= 0", what, row_name(where, (int)(i / T), rps),
+                     (int)(i % T), name, v[i]);
+    return EDMP_OK;
+}
+
+// Replace device arrays of the bound guide: *slot <- a block of max(bytes, min_bytes) holding the bytes at host.  drop() runs once
+// nothing enqueued reads the old arrays and before they go: it takes out of sight what the arrays back (the caller makes the new
+// ones visible after the call, when everything succeeded)
+struct Upload { void** slot; const void* host; size_t bytes, min_bytes; };
+template <class Drop>
+static int guide_upload(edmp_ctx* ctx, Drop drop, std::initializer_list<Upload> ups) {
+    ctx->epoch++;  // a captured whole-run graph holds the launch sequence of the old arrays
+    EDMP_HIP_CHECK(hipSetDevice(ctx->device));
+    EDMP_HIP_CHECK(hipStreamSynchronize(ctx->stream));  // nothing enqueued still reads the arrays that are replaced
+    drop();
+    for (const Upload& u : ups) {
+        ctx_release(ctx, *u.slot);
+        *u.slot = nullptr;
+    }
+    for (const Upload& u : ups)
+        if (int rc = ctx_alloc(ctx, u.slot, std::max(u.bytes, u.min_bytes))) return rc;
+    hipError_t e = hipSuccess;
+    for (const Upload& u : ups)
+        if (e == hipSuccess && u.bytes) e = hipMemcpyAsync(*u.slot, u.host, u.bytes, hipMemcpyHostToDevice, ctx->stream);
+    const hipError_t e2 = hipStreamSynchronize(ctx->stream);  // the host vectors and the caller's arrays may go away after the call
+    EDMP_HIP_CHECK(e);
+    EDMP_HIP_CHECK(e2);
     return EDMP_OK;
 }
 
@@ -532,7 +545,7 @@ using namespace edmp;
 // the n rows run scene after scene and a message names the scene and the row inside it.
 static int sdf_table_set(edmp_ctx* ctx, const char* what, const float* spheres, int n_spheres, const int32_t* sdf_row, const double* margin,
                          const double* smoothness, int n, int T, int rps) {
-    Guide* g = ctx->guide;
+    SdfTable& tb = ctx->guide->sdf;
     EDMP_REQUIRE(spheres && sdf_row && margin && smoothness, "%s: null argument", what);
     EDMP_REQUIRE(n_spheres >= 1 && n_spheres <= EDMP_MAX_SPHERES, "%s: %d spheres outside 1..%d", what, n_spheres, EDMP_MAX_SPHERES);
     for (int s = 0; s < n_spheres; ++s) {
@@ -544,56 +557,35 @@ static int sdf_table_set(edmp_ctx* ctx, const char* what, const float* spheres, 
         EDMP_REQUIRE(sp[4] > 0.f, "%s: sphere %d: radius %g must be > 0", what, s, (double)sp[4]);
     }
     char where[48];
-    auto row_name = [&](int b) {
-        if (rps) snprintf(where, sizeof(where), "scene %d, row %d", b / rps, b % rps);
-        else snprintf(where, sizeof(where), "row %d", b);
-        return where;
-    };
     std::vector<int32_t> rows;
     for (int b = 0; b < n; ++b) {
-        EDMP_REQUIRE(sdf_row[b] == 0 || sdf_row[b] == 1, "%s: %s: sdf_row must be 0 or 1", what, row_name(b));
-        EDMP_REQUIRE(std::isfinite(smoothness[b]) && smoothness[b] >= 0.0, "%s: %s: smoothness %g must be finite and >= 0", what, row_name(b), smoothness[b]);
+        EDMP_REQUIRE(sdf_row[b] == 0 || sdf_row[b] == 1, "%s: %s: sdf_row must be 0 or 1", what, row_name(where, b, rps));
+        EDMP_REQUIRE(std::isfinite(smoothness[b]) && smoothness[b] >= 0.0, "%s: %s: smoothness %g must be finite and >= 0", what, row_name(where, b, rps),
+                     smoothness[b]);
         if (sdf_row[b]) rows.push_back(b);
     }
-    for (size_t i = 0; i < (size_t)n * T; ++i)
-        EDMP_REQUIRE(std::isfinite(margin[i]) && margin[i] >= 0.0, "%s: %s, step %d: margin %g must be finite and >= 0", what, row_name((int)(i / T)),
-                     (int)(i % T), margin[i]);
+    if (int rc = check_schedule(what, "margin", margin, n, T, rps)) return rc;
     // the table sorted by link, table order kept inside a link: the kernel's wave of a link group walks one contiguous range
     std::vector<float> sph((size_t)n_spheres * 4);
     int k = 0;
     for (int l = 0; l < EDMP_N_LINKS; ++l) {
-        g->sdf_link_off[l] = k;
+        tb.link_off[l] = k;
         for (int s = 0; s < n_spheres; ++s)
             if ((int)spheres[s * 5] == l) {
                 for (int c = 0; c < 4; ++c) sph[(size_t)k * 4 + c] = spheres[s * 5 + 1 + c];
                 ++k;
             }
     }
-    g->sdf_link_off[EDMP_N_LINKS] = k;
-    ctx->epoch++;  // a captured whole-run graph holds the launch sequence of the old table
-    EDMP_HIP_CHECK(hipSetDevice(ctx->device));
-    EDMP_HIP_CHECK(hipStreamSynchronize(ctx->stream));  // nothing enqueued still reads the arrays that are replaced
-    g->sdf_n = g->sdf_ns = 0;
-    g->self_n = g->self_np = 0;  // the self term belongs to this table: a new table drops it
-    g->self_set = false;
-    g->sdf_row_h.assign(sdf_row, sdf_row + n);
-    for (void** p : {(void**)&g->sdf_sph, (void**)&g->sdf_rows, (void**)&g->sdf_margin, (void**)&g->sdf_smooth}) {
-        ctx_release(ctx, *p);
-        *p = nullptr;
-    }
-    if (int rc = ctx_alloc(ctx, (void**)&g->sdf_sph, sph.size() * sizeof(float))) return rc;
-    if (int rc = ctx_alloc(ctx, (void**)&g->sdf_rows, std::max<size_t>(rows.size(), 1) * sizeof(int32_t))) return rc;
-    if (int rc = ctx_alloc(ctx, (void**)&g->sdf_margin, (size_t)n * T * sizeof(double))) return rc;
-    if (int rc = ctx_alloc(ctx, (void**)&g->sdf_smooth, (size_t)n * sizeof(double))) return rc;
-    hipError_t e = hipMemcpyAsync(g->sdf_sph, sph.data(), sph.size() * sizeof(float), hipMemcpyHostToDevice, ctx->stream);
-    if (e == hipSuccess && !rows.empty()) e = hipMemcpyAsync(g->sdf_rows, rows.data(), rows.size() * sizeof(int32_t), hipMemcpyHostToDevice, ctx->stream);
-    if (e == hipSuccess) e = hipMemcpyAsync(g->sdf_margin, margin, (size_t)n * T * sizeof(double), hipMemcpyHostToDevice, ctx->stream);
-    if (e == hipSuccess) e = hipMemcpyAsync(g->sdf_smooth, smoothness, (size_t)n * sizeof(double), hipMemcpyHostToDevice, ctx->stream);
-    const hipError_t e2 = hipStreamSynchronize(ctx->stream);  // the host vectors and the caller's arrays may go away after the call
-    EDMP_HIP_CHECK(e);
-    EDMP_HIP_CHECK(e2);
-    g->sdf_ns = n_spheres;
-    g->sdf_n = (int)rows.size();
+    tb.link_off[EDMP_N_LINKS] = k;
+    if (int rc = guide_upload(ctx, [&] { tb.drop(); },  // (the self term belongs to this table: a new table drops it)
+                              {{(void**)&tb.sph, sph.data(), sph.size() * sizeof(float), 0},
+                               {(void**)&tb.rows, rows.data(), rows.size() * sizeof(int32_t), sizeof(int32_t)},
+                               {(void**)&tb.margin, margin, (size_t)n * T * sizeof(double), 0},
+                               {(void**)&tb.smooth, smoothness, (size_t)n * sizeof(double), 0}}))
+        return rc;
+    tb.row_h.assign(sdf_row, sdf_row + n);
+    tb.ns = n_spheres;
+    tb.n = (int)rows.size();
     return EDMP_OK;
 }
 
@@ -618,13 +610,19 @@ extern "C" int edmp_scene_batch_set_sdf(edmp_ctx* ctx, const float* spheres, int
     return sdf_table_set(ctx, "edmp_scene_batch_set_sdf", spheres, n_spheres, sdf_row, margin, smoothness, S * B, T, B);
 }
 
+// the step and row count of a report call: any n rows at t = 0, the bound rows (their margin schedules) at t >= 1
+static int check_report_rows(const char* what, const Guide* g, int n, int t) {
+    EDMP_REQUIRE(t >= 0 && t <= g->rows_T, "%s: t=%d outside 0..%d", what, t, g->rows_T);
+    EDMP_REQUIRE(t == 0 || n == g->B, "%s: t >= 1 reads the rows' margin schedules: %d rows given, %d bound", what, n, g->B);  // (a batch: always its rows)
+    return EDMP_OK;
+}
+
 // edmp_sdf_rows_dev and edmp_scenes_sdf_rows_dev behind their own state, table, pointer and shape checks: n rows of S scenes whose L
 // interior waypoints lie at columns off .. off + L - 1 of rows of ldw columns; starts / goals [S][7]; rps as SdfArgs::rps
 static int sdf_rows(edmp_ctx* ctx, const char* what, const double* joints_dev, int S, int n, int ldw, int off, int L, int t, int rps,
                     const double* starts, const double* goals, double* cost_dev, double* clearance_dev) {
     Guide* g = ctx->guide;
-    EDMP_REQUIRE(t >= 0 && t <= g->rows_T, "%s: t=%d outside 0..%d", what, t, g->rows_T);
-    EDMP_REQUIRE(t == 0 || n == g->B, "%s: t >= 1 reads the rows' margin schedules: %d rows given, %d bound", what, n, g->B);  // (a batch: always its rows)
+    if (int rc = check_report_rows(what, g, n, t)) return rc;
     EDMP_HIP_CHECK(hipSetDevice(ctx->device));
     sampler_end_run(ctx);  // (the guide's start / goal pairs are replaced)
     if (int rc = guide_set_startgoal_scenes(ctx, S, starts, goals)) return rc;
@@ -632,8 +630,8 @@ static int sdf_rows(edmp_ctx* ctx, const char* what, const double* joints_dev, i
     fill_args(g, a, joints_dev, ldw, off, L, t, 0);
     a.rps = rps;
     if (n != g->B) a.smooth = nullptr;  // rows that are not the bound ones carry no smoothness weight
-    a.cost = cost_dev;
-    a.clearance = clearance_dev;
+    a.v.cost = cost_dev;
+    a.v.clearance = clearance_dev;
     hipLaunchKernelGGL(sdf_rows_kernel, dim3(n), dim3(256), 0, ctx->stream, a, g->rc);
     EDMP_HIP_CHECK(hipGetLastError());
     return EDMP_OK;
@@ -643,7 +641,7 @@ extern "C" int edmp_sdf_rows_dev(edmp_ctx* ctx, const double* joints_dev, int n,
                                  double* cost_dev, double* clearance_dev) {
     EDMP_REQUIRE(ctx && ctx->guide && ctx->guide->obb, "edmp_sdf_rows_dev: scene not set");
     EDMP_REFUSE_SCENE_BATCH(ctx->guide, "edmp_sdf_rows_dev");
-    EDMP_REQUIRE(ctx->guide->sdf_ns > 0, "edmp_sdf_rows_dev: call edmp_sdf_set first (the sphere table)");  // (EDMP_ERR_ARG; the batch: EDMP_ERR_STATE)
+    EDMP_REQUIRE(ctx->guide->sdf.ns > 0, "edmp_sdf_rows_dev: call edmp_sdf_set first (the sphere table)");  // (EDMP_ERR_ARG; the batch: EDMP_ERR_STATE)
     EDMP_REQUIRE(joints_dev && start && goal && cost_dev && clearance_dev, "edmp_sdf_rows_dev: null pointer");
     EDMP_REQUIRE(n >= 1 && L >= 1 && L + 2 <= 64, "edmp_sdf_rows_dev: need n >= 1 and 1 <= L <= 62 waypoints per row (got %d, %d)", n, L);
     // interior waypoints only, any n at t = 0; one scene: rps = 0
@@ -654,7 +652,7 @@ extern "C" int edmp_sdf_rows_dev(edmp_ctx* ctx, const double* joints_dev, int n,
 extern "C" int edmp_scenes_sdf_rows_dev(edmp_ctx* ctx, const double* X_dev, int S, int B, int N, int t, const double* starts, const double* goals,
                                         double* cost_dev, double* clearance_dev) {
     EDMP_REQUIRE_SCENE_BATCH(ctx, S, B, "edmp_scenes_sdf_rows_dev");
-    if (ctx->guide->sdf_ns <= 0) {
+    if (ctx->guide->sdf.ns <= 0) {
         set_error("edmp_scenes_sdf_rows_dev: call edmp_scene_batch_set_sdf first (the sphere table)");
         return EDMP_ERR_STATE;
     }
@@ -668,7 +666,9 @@ extern "C" int edmp_scenes_sdf_rows_dev(edmp_ctx* ctx, const double* X_dev, int 
 extern "C" int edmp_sdf_set_self(edmp_ctx* ctx, const int32_t* pair_mask, const double* weight, const double* self_margin, int n, int T) {
     EDMP_REQUIRE(ctx && ctx->guide && ctx->guide->obb && ctx->guide->row_class, "edmp_sdf_set_self: no guide bound (scene and rows first)");
     Guide* g = ctx->guide;
-    if (g->sdf_ns <= 0) {
+    const SdfTable& tb = g->sdf;
+    SelfTerm& st = g->sdf.self;
+    if (tb.ns <= 0) {
         set_error("edmp_sdf_set_self: call edmp_sdf_set or edmp_scene_batch_set_sdf first (the term is defined on their sphere table)");
         return EDMP_ERR_STATE;
     }
@@ -680,55 +680,33 @@ extern "C" int edmp_sdf_set_self(edmp_ctx* ctx, const int32_t* pair_mask, const 
                          b, (int)pair_mask[a * EDMP_N_LINKS + b]);
     const int rps = g->is_batch ? g->rps : 0;
     char where[48];
-    auto row_name = [&](int b) {
-        if (rps) snprintf(where, sizeof(where), "scene %d, row %d", b / rps, b % rps);
-        else snprintf(where, sizeof(where), "row %d", b);
-        return where;
-    };
     std::vector<int32_t> rows;
     for (int b = 0; b < n; ++b) {
-        EDMP_REQUIRE(std::isfinite(weight[b]) && weight[b] >= 0.0, "edmp_sdf_set_self: %s: weight %g must be finite and >= 0", row_name(b), weight[b]);
+        EDMP_REQUIRE(std::isfinite(weight[b]) && weight[b] >= 0.0, "edmp_sdf_set_self: %s: weight %g must be finite and >= 0", row_name(where, b, rps), weight[b]);
         if (weight[b] > 0.0) {
-            EDMP_REQUIRE(b < (int)g->sdf_row_h.size() && g->sdf_row_h[b] == 1, "edmp_sdf_set_self: %s: weight %g on a row that is not an SDF row", row_name(b),
-                         weight[b]);
+            EDMP_REQUIRE(b < (int)tb.row_h.size() && tb.row_h[b] == 1, "edmp_sdf_set_self: %s: weight %g on a row that is not an SDF row",
+                         row_name(where, b, rps), weight[b]);
             rows.push_back(b);
         }
     }
-    for (size_t i = 0; i < (size_t)n * T; ++i)
-        EDMP_REQUIRE(std::isfinite(self_margin[i]) && self_margin[i] >= 0.0, "edmp_sdf_set_self: %s, step %d: self_margin %g must be finite and >= 0",
-                     row_name((int)(i / T)), (int)(i % T), self_margin[i]);
+    if (int rc = check_schedule("edmp_sdf_set_self", "self_margin", self_margin, n, T, rps)) return rc;
     // the sphere pairs of the masked link pairs, in the order of the link-sorted table: s ascending, then u
     std::vector<int32_t> pairs;
     for (int la = 0; la < EDMP_N_LINKS; ++la)
-        for (int s = g->sdf_link_off[la]; s < g->sdf_link_off[la + 1]; ++s)
+        for (int s = tb.link_off[la]; s < tb.link_off[la + 1]; ++s)
             for (int lb = la + 1; lb < EDMP_N_LINKS; ++lb) {
                 if (!pair_mask[la * EDMP_N_LINKS + lb]) continue;
-                for (int u = g->sdf_link_off[lb]; u < g->sdf_link_off[lb + 1]; ++u) pairs.insert(pairs.end(), {s, u, la, lb});
+                for (int u = tb.link_off[lb]; u < tb.link_off[lb + 1]; ++u) pairs.insert(pairs.end(), {s, u, la, lb});
             }
-    ctx->epoch++;  // a captured whole-run graph holds the launch sequence without the term
-    EDMP_HIP_CHECK(hipSetDevice(ctx->device));
-    EDMP_HIP_CHECK(hipStreamSynchronize(ctx->stream));
-    g->self_n = g->self_np = 0;
-    g->self_set = false;
-    for (void** p : {(void**)&g->self_pairs, (void**)&g->self_rows, (void**)&g->self_weight, (void**)&g->self_margin}) {
-        ctx_release(ctx, *p);
-        *p = nullptr;
-    }
-    if (int rc = ctx_alloc(ctx, (void**)&g->self_pairs, std::max<size_t>(pairs.size(), 4) * sizeof(int32_t))) return rc;
-    if (int rc = ctx_alloc(ctx, (void**)&g->self_rows, std::max<size_t>(rows.size(), 1) * sizeof(int32_t))) return rc;
-    if (int rc = ctx_alloc(ctx, (void**)&g->self_weight, (size_t)n * sizeof(double))) return rc;
-    if (int rc = ctx_alloc(ctx, (void**)&g->self_margin, (size_t)n * T * sizeof(double))) return rc;
-    hipError_t e = hipSuccess;
-    if (!pairs.empty()) e = hipMemcpyAsync(g->self_pairs, pairs.data(), pairs.size() * sizeof(int32_t), hipMemcpyHostToDevice, ctx->stream);
-    if (e == hipSuccess && !rows.empty()) e = hipMemcpyAsync(g->self_rows, rows.data(), rows.size() * sizeof(int32_t), hipMemcpyHostToDevice, ctx->stream);
-    if (e == hipSuccess) e = hipMemcpyAsync(g->self_weight, weight, (size_t)n * sizeof(double), hipMemcpyHostToDevice, ctx->stream);
-    if (e == hipSuccess) e = hipMemcpyAsync(g->self_margin, self_margin, (size_t)n * T * sizeof(double), hipMemcpyHostToDevice, ctx->stream);
-    const hipError_t e2 = hipStreamSynchronize(ctx->stream);  // the host vectors and the caller's arrays may go away after the call
-    EDMP_HIP_CHECK(e);
-    EDMP_HIP_CHECK(e2);
-    g->self_np = (int)(pairs.size() / 4);
-    g->self_n = (int)rows.size();
-    g->self_set = true;
+    if (int rc = guide_upload(ctx, [&] { st.drop(); },
+                              {{(void**)&st.pairs, pairs.data(), pairs.size() * sizeof(int32_t), 4 * sizeof(int32_t)},
+                               {(void**)&st.rows, rows.data(), rows.size() * sizeof(int32_t), sizeof(int32_t)},
+                               {(void**)&st.weight, weight, (size_t)n * sizeof(double), 0},
+                               {(void**)&st.margin, self_margin, (size_t)n * T * sizeof(double), 0}}))
+        return rc;
+    st.np = (int)(pairs.size() / 4);
+    st.n = (int)rows.size();
+    st.set = true;
     return EDMP_OK;
 }
 
@@ -736,21 +714,20 @@ extern "C" int edmp_sdf_self_rows_dev(edmp_ctx* ctx, const double* joints_dev, i
                                       double* clearance_dev) {
     EDMP_REQUIRE(ctx && ctx->guide && ctx->guide->obb, "edmp_sdf_self_rows_dev: scene not set");
     Guide* g = ctx->guide;
-    if (g->sdf_ns <= 0 || !g->self_set) {
+    if (g->sdf.ns <= 0 || !g->sdf.self.set) {
         set_error("edmp_sdf_self_rows_dev: call edmp_sdf_set_self first (the pair mask)");
         return EDMP_ERR_STATE;
     }
     EDMP_REQUIRE(joints_dev && cost_dev && clearance_dev, "edmp_sdf_self_rows_dev: null pointer");
     EDMP_REQUIRE(n >= 1 && L >= 1 && L + 2 <= 64, "edmp_sdf_self_rows_dev: need n >= 1 and 1 <= L <= 62 waypoints per row (got %d, %d)", n, L);
     EDMP_REQUIRE(off >= 0 && ldw >= 1 && (int64_t)off + L <= ldw, "edmp_sdf_self_rows_dev: columns %d .. %d outside rows of %d", off, off + L - 1, ldw);
-    EDMP_REQUIRE(t >= 0 && t <= g->rows_T, "edmp_sdf_self_rows_dev: t=%d outside 0..%d", t, g->rows_T);
-    EDMP_REQUIRE(t == 0 || n == g->B, "edmp_sdf_self_rows_dev: t >= 1 reads the rows' margin schedules: %d rows given, %d bound", n, g->B);
+    if (int rc = check_report_rows("edmp_sdf_self_rows_dev", g, n, t)) return rc;
     EDMP_HIP_CHECK(hipSetDevice(ctx->device));
     SelfArgs a;
     fill_self_args(g, a, joints_dev, ldw, off, L, t, 0);
     if (n != g->B) a.weight = nullptr;  // rows that are not the bound ones: weight 1, the bare hinge sum
-    a.cost = cost_dev;
-    a.clearance = clearance_dev;
+    a.v.cost = cost_dev;
+    a.v.clearance = clearance_dev;
     hipLaunchKernelGGL(sdf_self_rows_kernel, dim3(n), dim3(256), 0, ctx->stream, a, g->rc);
     EDMP_HIP_CHECK(hipGetLastError());
     return EDMP_OK;

@@ -263,15 +263,18 @@ class _SlotObject:
         pair = np.where(hit[..., None], np.stack([code // 9, code % 9], axis=-1), -1).astype(np.int32)
         return {"first": first, "pair": pair, "free": ~hit}
 
+    def _cost_clearance(self, out, shape):
+        """the (2, rows) f64 device output of a report kernel as host arrays of the caller's shape"""
+        h = self.ctx.to_host(out)
+        return {"cost": h[0].reshape(shape).copy(), "clearance": h[1].reshape(shape).copy()}
+
     def _sdf_report(self, Xd, shape, W, t, pair):
         """cost and minimum clearance of every row under the sphere model; W = the waypoints per row that the entry point takes"""
         ctx = self.ctx
         out = ctx.empty((2, int(np.prod(shape))), torch.float64)
         self._call("edmp_sdf_rows_dev", "edmp_scenes_sdf_rows_dev", shape, ptr(Xd), *shape, W, int(t), _capi.as_pd(pair[0]), _capi.as_pd(pair[1]),
                    C.c_void_p(out[0].data_ptr()), C.c_void_p(out[1].data_ptr()))
-        h = ctx.to_host(out)
-        return {"cost": h[0].reshape(shape).copy(), "clearance": h[1].reshape(shape).copy()}
-
+        return self._cost_clearance(out, shape)
 
     def _bind_self(self):
         """_bind_sdf for the self-clearance report: an object without a weighted row hands its mask over once (all weights 0: the
@@ -287,8 +290,7 @@ class _SlotObject:
         out = ctx.empty((2, int(np.prod(shape))), torch.float64)
         _capi.check(ctx.lib.edmp_sdf_self_rows_dev(ctx.h, ptr(Xd), int(np.prod(shape)), int(ldw), int(off), int(L), int(t), C.c_void_p(out[0].data_ptr()),
                                                    C.c_void_p(out[1].data_ptr())), "edmp_sdf_self_rows_dev")
-        h = ctx.to_host(out)
-        return {"cost": h[0].reshape(shape).copy(), "clearance": h[1].reshape(shape).copy()}
+        return self._cost_clearance(out, shape)
 
 
 class IntersectionVolumeGuide(_SlotObject):
