@@ -94,6 +94,7 @@ SIGNATURES = {
     "edmp_unet_packed_size": (C.c_int64, [_vp, C.POINTER(C.c_int)]),
     "edmp_unet_read_packed": (_i, [_vp, _pf, C.c_int64]),
     "edmp_unet_load_packed": (_i, [_vp, C.POINTER(UNetDesc), _pf, C.c_int64, _i, _i]),
+    "edmp_unet_plan_describe": (_i, [C.POINTER(UNetDesc), _i, C.POINTER(C.c_int), C.c_char_p, C.POINTER(C.c_int), C.POINTER(C.c_int64)]),
     "edmp_unet_flops_direct": (_i, [_vp, _pd]),
     "edmp_unet_flops_pipes": (_i, [_vp, _pd, _pd]),
     "edmp_prof_ops_bf16": (_i, [_vp, _i, C.POINTER(C.c_int), _pd]),
@@ -176,3 +177,18 @@ def as_pf(a):
 
 def as_pi32(a):
     return a.ctypes.data_as(_pi32)
+
+
+def plan_describe(input_dim, time_dim, dims, horizon, T):
+    """(kernel names per op, layout id, packed-image floats) of the layer program edmp_unet_load would build for this architecture
+    under the current builder switches (edmp_unet_plan_describe: host-only, needs no GPU)."""
+    lib = load()
+    d = UNetDesc()
+    d.input_dim, d.time_dim, d.n_levels, d.horizon, d.T = input_dim, time_dim, len(dims), horizon, T
+    for i, v in enumerate(dims):
+        d.dims[i] = v
+    n, layout, size = C.c_int(), C.c_int(), C.c_int64()
+    check(lib.edmp_unet_plan_describe(C.byref(d), 0, C.byref(n), None, None, None), "edmp_unet_plan_describe")
+    names = C.create_string_buffer(max(n.value, 1) * 64)
+    check(lib.edmp_unet_plan_describe(C.byref(d), n.value, C.byref(n), names, C.byref(layout), C.byref(size)), "edmp_unet_plan_describe")
+    return [names.raw[i * 64:(i + 1) * 64].split(b"\0", 1)[0].decode() for i in range(n.value)], layout.value, size.value

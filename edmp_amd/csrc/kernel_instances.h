@@ -1,5 +1,6 @@
 // kernel_instances.h — every instance of the position-tile kernels (wide.hip, bf3.hip) and of the whole-level kernel (level.hip)
-// the layer program can launch (unet.hip: launch_rcb / launch_wrs / launch_level), with the build shard that compiles it.
+// the layer program can launch, with the build shard that compiles it.  unet.hip expands these lists into its instance tables
+// (kConvInst / kLevelInst / kLevel2Inst): a layer has a kernel instance exactly when its row is listed here.
 // The sharded build (__graft_entry__.build) compiles kernel_shard.hip once per shard in parallel (one instance takes
 // 3-30 s of compile time, the lot in one translation unit a quarter of an hour); the core translation unit only sees
 // `extern template` declarations.  Shards are balanced by compile time.

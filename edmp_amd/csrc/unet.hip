@@ -119,21 +119,19 @@ static RawNet inventory(const edmp_unet_desc& d) {
 // OP_RCB: Conv1dBlock of a wide level on wide_conv_kernel; OP_WRS: down/up-sampling conv of a wide level on wide_conv_kernel;
 // OP_LVL: a whole 32/64-channel level (level.hip); OP_CONV / OP_GN: the generic fallback (any architecture)
 enum OpKind { OP_CONV = 0, OP_GN = 1, OP_RCB = 2, OP_WRS = 4, OP_LVL = 5 };
+struct ConvInst;    // rows of the instance tables (below, behind the kernels)
+struct LevelInst;
+struct Level2Inst;
 struct Op {
     OpKind kind;
     ConvP cv;
     GnP gn;
     RcbP rc;
     LevelP lv;    // OP_LVL: a whole level
-    int lv_variant;
-    int lv_sb;    // samples per workgroup (level_sb, frozen at build time)
+    const ConvInst* inst;       // OP_RCB / OP_WRS: the instance the plan chose (choose_conv)
+    const LevelInst* lv_inst;   // OP_LVL (choose_level)
+    const Level2Inst* lv_pair;  // OP_LVL: set = this level and the NEXT op (the following level) run as one launch (level.hip: level2_kernel)
     int lv_tb1, lv_tb2;  // offsets of the two blocks' time biases in the time-bias row
-    int lv_merge;        // OP_LVL: 1 = this level and the NEXT op (the following down level) run as one launch (level.hip: level2_kernel)
-    int rc_L;     // OP_RCB / OP_WRS: input positions
-    int rc_form;  // OP_RCB: 0 direct | 2 / 4 Karatsuba form at L = 2 / 4 (decided when the model was built)
-    int rc_ms;    // OP_RCB / OP_WRS: samples per workgroup (wide_ms, frozen at build time)
-    int rc_bf3;   // OP_RCB / OP_WRS: 1 = runs on the bf16 matrix pipe with exact products (bf3.hip; bf3_select, frozen at build time)
-    int wrs_kind; // OP_WRS: WK_DOWN / WK_UP
     int tb_off;   // GN: offset into the time-bias row, -1 if none
 
     double flops_nominal, flops_exec;  // per trajectory: every tap | MFMA work actually issued (padding taps skipped, Karatsuba forms)
@@ -388,9 +386,9 @@ __global__ __launch_bounds__(256) void conv_mfma_kernel(ConvP p) {
 #include "wide.hip"
 #include "bf3.hip"
 #include "level.hip"
-#ifdef EDMP_SHARDED  // the position-tile and whole-level kernels are compiled in parallel translation units (kernel_shard.hip)
 #include "kernel_instances.h"
 namespace edmp {
+#ifdef EDMP_SHARDED  // the position-tile and whole-level kernels are compiled in parallel translation units (kernel_shard.hip)
 #define EDMP_X(sh, K, MS, CG, GS, L, R) extern template int launch_wide_t<K, MS, CG, GS, L, R>(const RcbP&, hipStream_t);
 EDMP_WIDE_INSTANCES(EDMP_X)
 #undef EDMP_X
@@ -403,8 +401,60 @@ EDMP_LEVEL_INSTANCES(EDMP_X)
 #define EDMP_X(sh, MA, CA, LA, CINA, MB, CB, LB, CINB, SB) extern template int launch_level2_t<MA, CA, LA, CINA, MB, CB, LB, CINB, SB>(const LevelP&, const LevelP&, hipStream_t);
 EDMP_LEVEL2_INSTANCES(EDMP_X)
 #undef EDMP_X
-}  // namespace edmp
 #endif
+
+// ---- the instance tables: the lists of kernel_instances.h expanded once more, into rows of {template arguments, launcher}.
+// A layer has a kernel instance exactly when its row exists (find_*); the plan keeps the row (choose_conv / choose_level /
+// choose_pair below), and the packer's arguments, the launch and the printed kernel name all come from it.  These expansions are
+// the only place in this file that spells a template argument list (the unity build instantiates the kernels through them).
+struct ConvInst {  // wide.hip (fp32 MFMA) | bf3.hip (bf16x3: exact products on the bf16 matrix pipe)
+    bool bf3;
+    int kind, ms, cg, gs, L;  // WideKind, samples per workgroup, channels per workgroup, channels per GroupNorm group, input positions
+    bool res;                 // folds the block's residual 1x1 conv
+    int (*launch)(const RcbP&, hipStream_t, KernelAttrs*);  // KernelAttrs*: launch_bf3_t's query mode (ignored by a wide.hip row)
+};
+static const ConvInst kConvInst[] = {
+#define EDMP_X(sh, K, MS, CG, GS, L, R) {false, K, MS, CG, GS, L, R, [](const RcbP& p, hipStream_t s, KernelAttrs*) { return launch_wide_t<K, MS, CG, GS, L, R>(p, s); }},
+    EDMP_WIDE_INSTANCES(EDMP_X)
+#undef EDMP_X
+#define EDMP_X(sh, K, MS, CG, GS, L, R) {true, K, MS, CG, GS, L, R, &launch_bf3_t<K, MS, CG, GS, L, R>},
+    EDMP_BF3_INSTANCES(EDMP_X)
+#undef EDMP_X
+};
+struct LevelInst {  // level.hip: a whole 32/64-channel level
+    int mode, C, L, sb, cin;  // LevelMode, channels, positions, samples per workgroup, stored input channels
+    int (*launch)(const LevelP&, hipStream_t);
+};
+static const LevelInst kLevelInst[] = {
+#define EDMP_X(sh, M, C, L, SB, CIN) {M, C, L, SB, CIN, &launch_level_t<M, C, L, SB, CIN>},
+    EDMP_LEVEL_INSTANCES(EDMP_X)
+#undef EDMP_X
+};
+struct Level2Inst {  // level.hip: two consecutive levels in one launch (level2_kernel)
+    int ma, ca, la, cina, mb, cb, lb, cinb, sb;
+    int (*launch)(const LevelP&, const LevelP&, hipStream_t);
+};
+static const Level2Inst kLevel2Inst[] = {
+#define EDMP_X(sh, MA, CA, LA, CINA, MB, CB, LB, CINB, SB) {MA, CA, LA, CINA, MB, CB, LB, CINB, SB, &launch_level2_t<MA, CA, LA, CINA, MB, CB, LB, CINB, SB>},
+    EDMP_LEVEL2_INSTANCES(EDMP_X)
+#undef EDMP_X
+};
+static const ConvInst* find_conv(bool bf3, int kind, int ms, int cg, int gs, int L, bool res) {
+    for (const ConvInst& r : kConvInst)
+        if (r.bf3 == bf3 && r.kind == kind && r.ms == ms && r.cg == cg && r.gs == gs && r.L == L && r.res == res) return &r;
+    return nullptr;
+}
+static const LevelInst* find_level(int mode, int C, int L, int sb, int cin) {
+    for (const LevelInst& r : kLevelInst)
+        if (r.mode == mode && r.C == C && r.L == L && r.sb == sb && r.cin == cin) return &r;
+    return nullptr;
+}
+static const Level2Inst* find_level2(const LevelInst& a, const LevelInst& b) {  // (the pair's tile height is its own)
+    for (const Level2Inst& r : kLevel2Inst)
+        if (r.ma == a.mode && r.ca == a.C && r.la == a.L && r.cina == a.cin && r.mb == b.mode && r.cb == b.C && r.lb == b.L && r.cinb == b.cin) return &r;
+    return nullptr;
+}
+}  // namespace edmp
 namespace edmp {
 
 // GroupNorm(8 groups, eps 1e-5, biased variance) -> Mish -> (+ time bias[c] | + residual[b,l,c]) in place.
@@ -527,12 +577,12 @@ static void launch_conv_t(const ConvP& p, hipStream_t s) {
     dim3 grid((p.B + BM - 1) / BM, p.Lout * ((p.Cout + BN - 1) / BN));
     hipLaunchKernelGGL((conv_mfma_kernel<BM, BN, KC>), grid, dim3(256), 0, s, p);
 }
-static int pick_kc(const ConvP& p) {
-    auto ok = [&](int kc) { return p.C1 % kc == 0 && (p.C2 == 0 || p.C2 % kc == 0); };
+static int pick_kc(int c1, int c2) {
+    auto ok = [&](int kc) { return c1 % kc == 0 && (c2 == 0 || c2 % kc == 0); };
     return ok(64) ? 64 : ok(32) ? 32 : ok(16) ? 16 : 8;
 }
 static void launch_conv(const ConvP& p, hipStream_t s) {
-    const int kc = pick_kc(p);
+    const int kc = pick_kc(p.C1, p.C2);
     const bool wide = (p.Cout % 64 == 0);
     if (wide) {
         if (kc == 64) launch_conv_t<64, 64, 64>(p, s);
@@ -558,239 +608,110 @@ static int launch_gn(const GnP& p, hipStream_t s) {
     return EDMP_OK;
 }
 
-// Builder switches, read from the environment WHEN A MODEL IS BUILT (edmp_unet_load*) and frozen into its layer program:
-// two models built under different settings can live side by side in one process (A/B runs, the adversarial-weights test).
-// EDMP_NO_KARATSUBA=1: the L = 2 convolutions of the 512-channel levels in the direct form instead of the Karatsuba form
-// (3 instead of 4 matrix products; wide.hip WK_K5K2) and the L = 4 convolutions of the 256/512-channel levels (nested form, 9 instead
-// of 14 products; WK_K5K4).
-static bool karatsuba_l2() { return getenv("EDMP_NO_KARATSUBA") == nullptr; }
-static bool karatsuba_l4() { return karatsuba_l2(); }
-static bool rcb_supported(int cout, int L, int c1, int c2) {
-    const int cg = cout / 8;
-    const bool shape = (cg == 64 && (L == 2 || L == 4)) || (cg == 32 && (L == 4 || L == 7)) || (cg == 16 && (L == 7 || L == 13));
-    return shape && cout % 8 == 0 && c1 % 32 == 0 && c2 % 32 == 0 && (c2 == 0 || c2 == c1);  // wide.hip: equal halves of a concat
-}
-// bf16x3 split (bf3.hip): the direct-form instances whose weights meet >= 7 positions run on the bf16 matrix pipe with exact
-// products and fp32 accumulation - measured x1.2-1.55 per launch at HALF the fp32-MFMA kernel's error against float64
-// (profiles/r06_bf16x3.md).  EDMP_BF16X3=<mask> (read at model-build time, frozen into the layer program and the packed image's
-// layout id): bit 0 Conv1dBlock L = 7 / 256 ch, bit 1 Conv1dBlock L = 7 / 128 ch, bit 2 Conv1dBlock L = 13 / 128 ch,
-// bit 3 the k3s2 (L = 7) / ConvTranspose (L = 4) resamplers at 256 channels, bit 4 those at 512 channels (L = 4 / L = 2), bit 5 those at
-// 128 channels (L = 13 / L = 7), bit 6 Conv1dBlock L = 4 / 512 ch, bit 7 Conv1dBlock L = 4 / 256 ch (direct form on the bf16 pipe instead of the
-// nested Karatsuba form on the fp32 pipe).  0 = every conv on the fp32-MFMA kernels (bench.py's A/B leg).
+// Builder switches, read from the environment ONCE WHEN A MODEL IS BUILT (BuildSwitches::read, the only getenv of this file) and
+// frozen into its plan, layer program and packed-image layout id: two models built under different settings can live side by side
+// in one process (A/B runs, the adversarial-weights test).
+//   EDMP_NO_FUSED / EDMP_NO_RESFOLD / EDMP_NO_LEVEL: every conv on the generic kernels | the residual 1x1 conv as its own launch |
+//     no whole-level kernels.
+//   EDMP_NO_KARATSUBA=1: the L = 2 convolutions of the 512-channel levels in the direct form instead of the Karatsuba form (3 instead
+//     of 4 matrix products; wide.hip WK_K5K2) and the L = 4 convolutions of the 256/512-channel levels (nested form, 9 instead of 14
+//     products; WK_K5K4).
+//   EDMP_BF16X3=<mask>: bf16x3 split (bf3.hip): the direct-form instances whose weights meet >= 7 positions run on the bf16 matrix
+//     pipe with exact products and fp32 accumulation - measured x1.2-1.55 per launch at HALF the fp32-MFMA kernel's error against
+//     float64 (profiles/r06_bf16x3.md).  Bits: kConvFamilies below.  0 = every conv on the fp32-MFMA kernels (bench.py's A/B leg).
+//   EDMP_MS16=<mask>: 16-sample tiles for DIRECT-form fp32 instances of the 256 / 512-channel levels (choose_conv).  Bits: kConvFamilies.
+//   EDMP_LEVEL_SB=<d1><d2><d3><d4> (digits 2 / 4): samples per workgroup of the level kernels - down level at 32 channels, down level at
+//     64, up level, last up level.  4 = one workgroup per CU at B = 1024; 2 = two co-resident workgroups per CU (two waves per SIMD: one
+//     workgroup's GroupNorm / Mish epilogues, barriers and staging run under the other's MFMAs).
+//   EDMP_LEVEL_MERGE=<mask>: bit 0 = the two down levels of the 32/64-channel resolutions as ONE launch, level 1's k3s2 output handed to
+//     level 2 in LDS (level.hip: level2_kernel; two samples per workgroup); bit 1 = the two last up levels likewise, the ConvTranspose
+//     output of the 64-channel level going into the first half of the last level's input tile (the skip half still comes from HBM).
 static const int kBf3Default = 0xff;  // same-box bench A/Bs (profiles/r06_bf16x3.md): 0 -> 1 001 k, 0x7 -> 1 083 k, 0x3f -> 1 102 k traj-steps/s; another box: 0x3f 1 067 k, 0x7f 1 101 k, 0xbf 1 087 k, 0xff -> 1 120 k
-static int bf3_mask() {
-    const char* e = getenv("EDMP_BF16X3");
-    return e ? (int)strtol(e, nullptr, 0) : kBf3Default;
-}
-// kind: WK_K5 (a Conv1dBlock; L = its length), WK_DOWN / WK_UP (L = input length)
-static bool bf3_select(int cout, int L, int kind) {
-    const int cg = cout / 8, m = bf3_mask();
-    if (kind == WK_K5) {
-        if (cg == 32 && L == 7) return m & 1;
-        if (cg == 16 && L == 7) return m & 2;
-        if (cg == 16 && L == 13) return m & 4;
-        if (cg == 64 && L == 4) return m & 64;
-        if (cg == 32 && L == 4) return m & 128;
-    }
-    if (kind == WK_DOWN) {
-        if (cg == 32 && L == 7) return m & 8;
-        if (cg == 64 && L == 4) return m & 16;
-        if (cg == 16 && L == 13) return m & 32;
-    }
-    if (kind == WK_UP) {
-        if (cg == 32 && L == 4) return m & 8;
-        if (cg == 64 && L == 2) return m & 16;
-        if (cg == 16 && L == 7) return m & 32;
-    }
-    return false;
-}
-// form: 0 direct | 2 Karatsuba at L = 2 | 4 nested Karatsuba at L = 4 (rcb_form, frozen into the op at build time)
-static int rcb_form(int cout, int L) {
-    const int cg = cout / 8;
-    if (bf3_select(cout, L, WK_K5)) return 0;  // bf3.hip runs the direct form
-    if (cg == 64 && L == 2 && karatsuba_l2()) return 2;
-    if (cg >= 32 && L == 4 && karatsuba_l4()) return 4;
-    return 0;
-}
-// position-tile kernel (wide.hip) instances: the tile height MS = samples per workgroup.  16 for the 128-channel levels (32-sample
-// workgroups would leave half the CUs idle); 32 for the Karatsuba forms of the 256 / 512-channel levels (their weight stream per
-// FLOP doubles with 16-sample tiles: 16 TB/s out of the L2s at L = 4); and for the DIRECT-form instances of the 256 / 512-channel
-// levels - Conv1dBlock at L = 7, the k3s2 / ConvTranspose resamplers - 16 since round 5: 512 workgroups per launch, two co-resident per CU
-// (160 registers, 48 KB of LDS), one workgroup's prologue / epilogue / barriers run under the other's fp32 MFMAs (a wave's own VALU work
-// cannot: profiles/r05_coissue_control.md).  Same-stream A/B on isolated layer chains x1.06-1.08 (tools/dualbench.hip, profiles/r05_forkjoin.md).
-// EDMP_MS16=<mask> (read at model-build time, frozen into the layer program and the packed image's layout id) selects the families:
-// bit 0 Conv1dBlock L = 7 / 256 ch, bit 1 k3s2 L = 7 / 256 ch, bit 2 ConvTranspose L = 4 / 256 ch, bit 3 k3s2 L = 4 / 512 ch,
-// bit 4 ConvTranspose L = 2 / 512 ch.
 static const int kMs16Default = 0x05;  // same-box bench A/B, three alternated runs each: 986.5 k -> 989.8 k traj-steps/s (profiles/r05_forkjoin.md); bits 1, 3, 4 measured x0.98-1.01 per launch: off
-static int ms16_mask() {
-    const char* e = getenv("EDMP_MS16");
-    return e ? (int)strtol(e, nullptr, 0) : kMs16Default;
-}
-// kind: WK_K5 (a Conv1dBlock; L = its length), WK_DOWN / WK_UP (L = input length)
-static int wide_ms(int cout, int L, int kind) {
-    const int cg = cout / 8;
-    if (bf3_select(cout, L, kind)) return cg >= 32 ? 32 : 16;  // bf3.hip: 32-sample workgroups at 256 channels (256 workgroups), 16 at 128
-    if (cg < 32) return 16;
-    if (kind == WK_K5 && rcb_form(cout, L) != 0) return 32;
-    const int m = ms16_mask();
-    if (kind == WK_K5 && cg == 32 && L == 7) return (m & 1) ? 16 : 32;
-    if (kind == WK_DOWN && cg == 32 && L == 7) return (m & 2) ? 16 : 32;
-    if (kind == WK_UP && cg == 32 && L == 4) return (m & 4) ? 16 : 32;
-    if (kind == WK_DOWN && cg == 64 && L == 4) return (m & 8) ? 16 : 32;
-    if (kind == WK_UP && cg == 64 && L == 2) return (m & 16) ? 16 : 32;
-    return 32;
-}
-// q: see launch_bf3_t (bf16x3 ops only)
-static int launch_rcb(const RcbP& p, int L, int form, int ms, int bf3, hipStream_t s, KernelAttrs* q = nullptr) {
-    const int cg = p.Cout / 8;
-    const bool res = p.res_out != nullptr;
-    if (bf3) {
-#define EDMP_B3(MS, GS, LL) \
-    return res ? launch_bf3_t<WK_K5, MS, 32, GS, LL, true>(p, s, q) : launch_bf3_t<WK_K5, MS, 32, GS, LL, false>(p, s, q);
-        if (cg == 32 && L == 7) { EDMP_B3(32, 32, 7) }
-        if (cg == 16 && L == 7) { EDMP_B3(16, 16, 7) }
-        if (cg == 16 && L == 13) { EDMP_B3(16, 16, 13) }
-        if (cg == 32 && L == 4) { EDMP_B3(32, 32, 4) }
-#undef EDMP_B3
-        if (cg == 64 && L == 4) return res ? launch_bf3_t<WK_K5, 32, 64, 64, 4, true>(p, s, q) : launch_bf3_t<WK_K5, 32, 64, 64, 4, false>(p, s, q);
-        set_error("no bf16x3 conv+GroupNorm kernel for Cout=%d L=%d", p.Cout, L);
-        return EDMP_ERR_STATE;
-    }
-#define EDMP_K5(MS, CG, GS, LL) \
-    return res ? launch_wide_t<WK_K5, MS, CG, GS, LL, true>(p, s) : launch_wide_t<WK_K5, MS, CG, GS, LL, false>(p, s);
-    if (cg == 64 && L == 2) {
-        if (form == 2) return res ? launch_wide_t<WK_K5K2, 32, 64, 64, 2, true>(p, s) : launch_wide_t<WK_K5K2, 32, 64, 64, 2, false>(p, s);
-        EDMP_K5(32, 64, 64, 2)
-    }
-    if (cg == 64 && L == 4) {
-        if (form == 4) return res ? launch_wide_t<WK_K5K4, 32, 64, 64, 4, true>(p, s) : launch_wide_t<WK_K5K4, 32, 64, 64, 4, false>(p, s);
-        EDMP_K5(32, 64, 64, 4)
-    }
-    if (cg == 32 && L == 4) {
-        if (form == 4) return res ? launch_wide_t<WK_K5K4, 32, 32, 32, 4, true>(p, s) : launch_wide_t<WK_K5K4, 32, 32, 32, 4, false>(p, s);
-        EDMP_K5(32, 32, 32, 4)
-    }
-    if (cg == 32 && L == 7 && ms == 16) { EDMP_K5(16, 32, 32, 7) }
-    if (cg == 32 && L == 7) { EDMP_K5(32, 32, 32, 7) }
-    if (cg == 16 && L == 7) { EDMP_K5(16, 32, 16, 7) }
-    if (cg == 16 && L == 13) { EDMP_K5(16, 32, 16, 13) }
-#undef EDMP_K5
-    set_error("no fused conv+GroupNorm kernel for Cout=%d L=%d", p.Cout, L);
-    return EDMP_ERR_STATE;
-}
-
-// whole-level kernel variants (level.hip): (mode, channels, length, stored input channels) -> id, 0 = none
-static int level_variant(int mode, int C, int L, int c1, int c2) {
-    if (mode == LV_DOWN && C == 32 && L == 50 && c1 == 8 && c2 == 0) return 1;
-    if (mode == LV_DOWN && C == 64 && L == 25 && c1 == 32 && c2 == 0) return 2;
-    if (mode == LV_UP && C == 64 && L == 13 && c1 == 128 && c2 == 128) return 3;
-    if (mode == LV_UP_FINAL && C == 32 && L == 25 && c1 == 64 && c2 == 64) return 4;
-    return 0;
-}
-static int level_kx(int variant) { return variant == 1 ? 16 : variant == 2 ? 32 : variant == 3 ? 256 : 128; }
-// samples per workgroup of the level kernels, per variant: 4 = one workgroup per CU at B = 1024; 2 = two co-resident
-// workgroups per CU (two waves per SIMD: one workgroup's GroupNorm / Mish epilogues, barriers and staging run under the other's
-// MFMAs).  EDMP_LEVEL_SB=<d1><d2><d3><d4> (digits 2 / 4 for variants 1..4) overrides at model-build time (A/B runs).
-static int level_sb(int variant) {
-    static const char kDefault[] = "4222";  // same-box A/B (scripts/ab_models.py, round 3): -1.2 / -1.6 / -2.8 us per launch for variants 2 / 3 / 4, nothing for 1
-    const char* e = getenv("EDMP_LEVEL_SB");
-    const char* t = (e && strlen(e) == 4) ? e : kDefault;
-    return t[variant - 1] == '2' ? 2 : 4;
-}
-// EDMP_LEVEL_MERGE=<mask> (read at model-build time): bit 0 = the two down levels of the 32/64-channel resolutions (variants 1 + 2) as
-// ONE launch, level 1's k3s2 output handed to level 2 in LDS (level.hip: level2_kernel; two samples per workgroup); bit 1 = the two
-// last up levels (variants 3 + 4) likewise, the ConvTranspose output of the 64-channel level going into the first half of the last
-// level's input tile (the skip half still comes from HBM)
+static const char kLevelSbDefault[] = "4222";  // same-box A/B (scripts/ab_models.py, round 3): -1.2 / -1.6 / -2.8 us per launch for digits 2 / 3 / 4, nothing for 1
 static const int kLevelMergeDefault = 0x3;  // same-box bench A/B, three alternated runs each: bit 0 986.5 k -> 988.2 k; bits 0 + 1 993.8 k -> 997.7 k, bit 1 alone 992.5 k (profiles/r05_level_kernels.md)
-static int level_merge_mask() {
-    const char* e = getenv("EDMP_LEVEL_MERGE");
-    return e ? (int)strtol(e, nullptr, 0) : kLevelMergeDefault;
-}
-static int launch_level2(const LevelP& pa, const LevelP& pb, int va, int vb, hipStream_t s) {
-    if (va == 1 && vb == 2) return launch_level2_t<LV_DOWN, 32, 50, 8, LV_DOWN, 64, 25, 32, 2>(pa, pb, s);
-    if (va == 3 && vb == 4) return launch_level2_t<LV_UP, 64, 13, 256, LV_UP_FINAL, 32, 25, 128, 2>(pa, pb, s);
-    set_error("no merged whole-level kernel for variants %d + %d", va, vb);
-    return EDMP_ERR_STATE;
-}
-static int launch_level(const LevelP& p, int variant, int sb, hipStream_t s) {
-    switch (variant * 10 + sb) {
-        case 14: return launch_level_t<LV_DOWN, 32, 50, 4, 8>(p, s);
-        case 24: return launch_level_t<LV_DOWN, 64, 25, 4, 32>(p, s);
-        case 34: return launch_level_t<LV_UP, 64, 13, 4, 256>(p, s);
-        case 44: return launch_level_t<LV_UP_FINAL, 32, 25, 4, 128>(p, s);
-        case 12: return launch_level_t<LV_DOWN, 32, 50, 2, 8>(p, s);
-        case 22: return launch_level_t<LV_DOWN, 64, 25, 2, 32>(p, s);
-        case 32: return launch_level_t<LV_UP, 64, 13, 2, 256>(p, s);
-        case 42: return launch_level_t<LV_UP_FINAL, 32, 25, 2, 128>(p, s);
+struct BuildSwitches {
+    bool fused, resfold, level, karatsuba;
+    int bf3, ms16, level_merge;  // masks
+    int level_sb[4];
+    static BuildSwitches read() {
+        auto env = [](const char* name) { return getenv(name); };
+        auto mask = [&](const char* name, int dflt) { const char* e = env(name); return e ? (int)strtol(e, nullptr, 0) : dflt; };
+        BuildSwitches s;
+        s.fused = env("EDMP_NO_FUSED") == nullptr;
+        s.resfold = env("EDMP_NO_RESFOLD") == nullptr;
+        s.level = s.fused && env("EDMP_NO_LEVEL") == nullptr;
+        s.karatsuba = env("EDMP_NO_KARATSUBA") == nullptr;
+        s.bf3 = mask("EDMP_BF16X3", kBf3Default);
+        s.ms16 = mask("EDMP_MS16", kMs16Default);
+        s.level_merge = mask("EDMP_LEVEL_MERGE", kLevelMergeDefault);
+        const char* e = env("EDMP_LEVEL_SB");
+        for (int d = 0; d < 4; ++d) s.level_sb[d] = ((e && strlen(e) == 4) ? e : kLevelSbDefault)[d] == '2' ? 2 : 4;
+        return s;
     }
-    set_error("no whole-level kernel variant %d", variant);
-    return EDMP_ERR_STATE;
-}
+};
 
-// down/up-sampling convs of the wide levels (no GroupNorm behind them) on the position-tile kernel
-static bool wrs_supported(int cout, int cin, int Lin, bool transposed) {
+// packing forms of the weight image (Packer::tag); F_FRAG .. F_FRAG_BF3 are the weight-stream layouts of the position-tile kernels
+enum PackForm : uint64_t { F_CONV = 1, F_CONVT = 2, F_FRAG = 3, F_FRAG_K2 = 4, F_FRAG_K4 = 5, F_RESAMPLE = 6, F_VEC = 7, F_FRAG_BF3 = 8 };
+
+// The conv families a switch bit governs: kind (WK_K5: a Conv1dBlock; WK_DOWN / WK_UP: the k3s2 / ConvTranspose resamplers), Cout / 8,
+// L (input positions) -> bit of EDMP_BF16X3 (the family runs on bf3.hip) and bit of EDMP_MS16 (16-sample tiles on wide.hip); -1: none
+static const struct { int kind, cg, L, bf3_bit, ms16_bit; } kConvFamilies[] = {
+    {WK_K5, 32, 7, 0, 0},    {WK_K5, 16, 7, 1, -1},   {WK_K5, 16, 13, 2, -1},   // Conv1dBlock L = 7 / 256 ch, L = 7 / 128 ch, L = 13 / 128 ch
+    {WK_K5, 64, 4, 6, -1},   {WK_K5, 32, 4, 7, -1},   // Conv1dBlock L = 4 / 512 ch, / 256 ch: direct form on the bf16 pipe instead of the nested Karatsuba form on the fp32 pipe
+    {WK_DOWN, 32, 7, 3, 1},  {WK_UP, 32, 4, 3, 2},    // the resamplers at 256 channels
+    {WK_DOWN, 64, 4, 4, 3},  {WK_UP, 64, 2, 4, 4},    // at 512 channels
+    {WK_DOWN, 16, 13, 5, -1}, {WK_UP, 16, 7, 5, -1},  // at 128 channels
+};
+
+// What the plan decides for one conv op of a wide level (>= 128 channels), once: everything downstream - the packer (stream, row->ms),
+// the FLOP counts (form), the launch and the kernel name (row) - reads it from here.
+struct ConvChoice {
+    const ConvInst* row[2] = {nullptr, nullptr};  // [RES]: without | with the folded residual 1x1 conv (WK_K5); family, MS, GS are the row's.  row[0] == nullptr: no instance, the generic path runs the layer
+    int form = 0;                                 // 0 direct | 2 Karatsuba at L = 2 | 4 nested Karatsuba at L = 4
+    PackForm stream = F_FRAG;                     // layout of the weight stream
+};
+// kind: WK_K5 (a Conv1dBlock; L = its length), WK_DOWN / WK_UP (L = input length); c1, c2: stored input channels (c2: the skip half of a concat)
+static ConvChoice choose_conv(const BuildSwitches& sw, int kind, int cout, int L, int c1, int c2) {
+    ConvChoice c;
+    if (!sw.fused || cout % 8 != 0 || c1 % 32 != 0 || c2 % 32 != 0 || (c2 != 0 && c2 != c1)) return c;  // wide.hip: whole K groups, equal halves of a concat
     const int cg = cout / 8;
-    if (cout % 8 != 0 || cin % 32 != 0) return false;
-    if (transposed) return (cg == 64 && Lin == 2) || (cg == 32 && Lin == 4) || (cg == 16 && Lin == 7);
-    return (cg == 64 && Lin == 4) || (cg == 32 && Lin == 7) || (cg == 16 && Lin == 13);
-}
-static int launch_wrs(const RcbP& p, int kind, int Lin, int ms, int bf3, hipStream_t s, KernelAttrs* q = nullptr) {
-    const int cg = p.Cout / 8;
-    if (bf3) {  // bf3.hip: no GroupNorm behind a resampler, so 32-channel workgroups at every width
-        if (kind == WK_DOWN && cg == 32 && Lin == 7) return launch_bf3_t<WK_DOWN, 32, 32, 32, 7, false>(p, s, q);
-        if (kind == WK_UP && cg == 32 && Lin == 4) return launch_bf3_t<WK_UP, 32, 32, 32, 4, false>(p, s, q);
-        if (kind == WK_DOWN && cg == 64 && Lin == 4) return launch_bf3_t<WK_DOWN, 32, 32, 32, 4, false>(p, s, q);
-        if (kind == WK_UP && cg == 64 && Lin == 2) return launch_bf3_t<WK_UP, 32, 32, 32, 2, false>(p, s, q);
-        if (kind == WK_DOWN && cg == 16 && Lin == 13) return launch_bf3_t<WK_DOWN, 16, 32, 16, 13, false>(p, s, q);
-        if (kind == WK_UP && cg == 16 && Lin == 7) return launch_bf3_t<WK_UP, 16, 32, 16, 7, false>(p, s, q);
-        set_error("no bf16x3 resampling kernel for kind=%d Cout=%d Lin=%d", kind, p.Cout, Lin);
-        return EDMP_ERR_STATE;
-    }
-    if (ms == 16 && cg >= 32) {  // 16-sample tiles at 256 / 512 channels (wide_ms)
-        if (kind == WK_DOWN && cg == 32 && Lin == 7) return launch_wide_t<WK_DOWN, 16, 32, 32, 7, false>(p, s);
-        if (kind == WK_UP && cg == 32 && Lin == 4) return launch_wide_t<WK_UP, 16, 32, 32, 4, false>(p, s);
-        if (kind == WK_DOWN && cg == 64 && Lin == 4) return launch_wide_t<WK_DOWN, 16, 64, 64, 4, false>(p, s);
-        if (kind == WK_UP && cg == 64 && Lin == 2) return launch_wide_t<WK_UP, 16, 64, 64, 2, false>(p, s);
-    }
-    if (kind == WK_DOWN) {
-        if (cg == 64 && Lin == 4) return launch_wide_t<WK_DOWN, 32, 64, 64, 4, false>(p, s);
-        if (cg == 32 && Lin == 7) return launch_wide_t<WK_DOWN, 32, 32, 32, 7, false>(p, s);
-        if (cg == 16 && Lin == 13) return launch_wide_t<WK_DOWN, 16, 32, 16, 13, false>(p, s);
+    int bf3_bit = -1, ms16_bit = -1;
+    for (const auto& f : kConvFamilies)
+        if (f.kind == kind && f.cg == cg && f.L == L) bf3_bit = f.bf3_bit, ms16_bit = f.ms16_bit;
+    const bool bf3 = bf3_bit >= 0 && (sw.bf3 >> bf3_bit & 1);
+    int ms, cgw = std::max(cg, 32), gs = cg;  // a workgroup covers whole GroupNorm groups, at least 32 channels
+    if (bf3) {
+        ms = cg >= 32 ? 32 : 16;  // bf3.hip runs the direct form: 32-sample workgroups at 256 channels and above (256 workgroups), 16 at 128
+        if (kind != WK_K5) cgw = 32, gs = std::min(cg, 32);  // no GroupNorm behind a resampler, so 32-channel workgroups at every width
+        c.stream = F_FRAG_BF3;
     } else {
-        if (cg == 64 && Lin == 2) return launch_wide_t<WK_UP, 32, 64, 64, 2, false>(p, s);
-        if (cg == 32 && Lin == 4) return launch_wide_t<WK_UP, 32, 32, 32, 4, false>(p, s);
-        if (cg == 16 && Lin == 7) return launch_wide_t<WK_UP, 16, 32, 16, 7, false>(p, s);
+        if (kind == WK_K5 && sw.karatsuba) c.form = (cg == 64 && L == 2) ? 2 : (cg >= 32 && L == 4) ? 4 : 0;
+        // The tile height MS = samples per workgroup.  16 for the 128-channel levels (32-sample workgroups would leave half the CUs
+        // idle); 32 for the Karatsuba forms of the 256 / 512-channel levels (their weight stream per FLOP doubles with 16-sample tiles:
+        // 16 TB/s out of the L2s at L = 4); and for the DIRECT-form instances of the 256 / 512-channel levels 16 where EDMP_MS16 says so
+        // (round 5): 512 workgroups per launch, two co-resident per CU (160 registers, 48 KB of LDS), one workgroup's prologue /
+        // epilogue / barriers run under the other's fp32 MFMAs (a wave's own VALU work cannot: profiles/r05_coissue_control.md).
+        // Same-stream A/B on isolated layer chains x1.06-1.08 (tools/dualbench.hip, profiles/r05_forkjoin.md).
+        ms = (cg < 32 || (c.form == 0 && ms16_bit >= 0 && (sw.ms16 >> ms16_bit & 1))) ? 16 : 32;
+        c.stream = c.form == 2 ? F_FRAG_K2 : c.form == 4 ? F_FRAG_K4 : F_FRAG;
     }
-    set_error("no position-tile resampling kernel for kind=%d Cout=%d Lin=%d", kind, p.Cout, Lin);
-    return EDMP_ERR_STATE;
+    const int ikind = c.form == 2 ? WK_K5K2 : c.form == 4 ? WK_K5K4 : kind;
+    c.row[0] = find_conv(bf3, ikind, ms, cgw, gs, L, false);
+    c.row[1] = find_conv(bf3, ikind, ms, cgw, gs, L, true);
+    return c;
 }
-
-// kernel instance an op launches, spelled as rocprofv3's kernel trace prints it (minus the edmp:: prefix): lets
-// bench.py's per-kernel table be checked line by line against profiles/*_kernel_stats.csv
-static void op_kernel_name(const Op& op, char* out) {
-    if (op.kind == OP_RCB || op.kind == OP_WRS) {
-        const int cg = op.rc.Cout / 8, ms = op.rc_ms;
-        const int kind = op.kind == OP_RCB ? (op.rc_form == 2 ? 3 : op.rc_form == 4 ? 4 : 0) : op.wrs_kind;
-        if (op.rc_bf3 && op.kind == OP_WRS) snprintf(out, 64, "bf3_conv_kernel<%d, %d, 32, %d, %d, false>", kind, ms, cg < 32 ? 16 : 32, op.rc_L);
-        else
-        snprintf(out, 64, "%s_conv_kernel<%d, %d, %d, %d, %d, %s>", op.rc_bf3 ? "bf3" : "wide", kind, ms, cg < 32 ? 32 : cg, cg, op.rc_L,
-                 (op.kind == OP_RCB && op.rc.res_out) ? "true" : "false");
-    }
-    else if (op.kind == OP_LVL && op.lv_merge) snprintf(out, 64, op.lv_variant == 1 ? "level2_kernel<0, 32, 50, 8, 0, 64, 25, 32, 2>" : "level2_kernel<1, 64, 13, 256, 2, 32, 25, 128, 2>");
-    else if (op.kind == OP_LVL) {
-        static const char* lv_fmt[] = {"", "level_kernel<0, 32, 50, %d, 8>", "level_kernel<0, 64, 25, %d, 32>", "level_kernel<1, 64, 13, %d, 256>", "level_kernel<2, 32, 25, %d, 128>"};
-        snprintf(out, 64, lv_fmt[op.lv_variant], op.lv_sb);
-    }
-    else if (op.kind == OP_CONV) {
-        const int kc = pick_kc(op.cv);
-        if (op.cv.Cout % 64 == 0) snprintf(out, 64, "conv_mfma_kernel<64, 64, %d>", kc);
-        else snprintf(out, 64, "conv_mfma_kernel<128, 32, %d>", kc >= 32 ? 32 : kc);
-    } else {
-        const int n = (op.gn.C / 8) * op.gn.L;
-        snprintf(out, 64, "gn_mish_kernel<%d>", n <= 128 ? 2 : n <= 256 ? 4 : 8);
-    }
+// whole-level kernel (level.hip) for a level of `C` channels and `L` positions reading c1 (+ c2: the skip) stored channels; nullptr = none
+static const LevelInst* choose_level(const BuildSwitches& sw, int mode, int C, int L, int c1, int c2) {
+    if (!sw.level || (mode == LV_DOWN ? c2 != 0 : c2 != c1)) return nullptr;
+    const int digit = mode == LV_DOWN ? (C == 32 ? 0 : 1) : mode == LV_UP ? 2 : 3;
+    return find_level(mode, C, L, sw.level_sb[digit], c1 + c2);
 }
-
+// level `a` and the level behind it as one launch (nullptr: two launches)
+static const Level2Inst* choose_pair(const BuildSwitches& sw, const LevelInst* a, const LevelInst* b) {
+    if (!a || !b || !(sw.level_merge >> (a->mode == LV_DOWN ? 0 : 1) & 1)) return nullptr;
+    return find_level2(*a, *b);
+}
 
 // ---- the bf16x3 kernels' CU claim (bf3.hip: bf3_conv_kernel; profiles/r06_coresidency_fault.md) ------------------------------------
 // A bf16x3 workgroup must own its CU: one workgroup per CU, and its waves' registers fill the 512-entry file of every SIMD
@@ -806,10 +727,8 @@ static bool owns_cu(int regs, int block, int lds, int wg_per_cu) {
 
 static int check_bf3_cu_claim(UNet* u) {
     for (Op& op : u->prog) {
-        if (!((op.kind == OP_RCB || op.kind == OP_WRS) && op.rc_bf3)) continue;
-        int rc = op.kind == OP_RCB ? launch_rcb(op.rc, op.rc_L, op.rc_form, op.rc_ms, 1, nullptr, &op.attrs)
-                                   : launch_wrs(op.rc, op.wrs_kind, op.rc_L, op.rc_ms, 1, nullptr, &op.attrs);
-        if (rc) return rc;
+        if (!(op.inst && op.inst->bf3)) continue;
+        if (int rc = op.inst->launch(op.rc, nullptr, &op.attrs)) return rc;  // query mode: launches nothing
         const KernelAttrs& a = op.attrs;
         EDMP_REQUIRE(owns_cu(a.regs, a.block, a.lds, a.wg_per_cu),
                      "%s does not own its CU (%d VGPRs x %d threads, %d B of LDS, %d workgroups per CU): the bf16x3 containment of "
@@ -846,7 +765,6 @@ struct Packer {
             sig *= 1099511628211ull;
         }
     }
-    enum Form : uint64_t { F_CONV = 1, F_CONVT = 2, F_FRAG = 3, F_FRAG_K2 = 4, F_FRAG_K4 = 5, F_RESAMPLE = 6, F_VEC = 7, F_FRAG_BF3 = 8 };
     size_t add_untagged(size_t n) {
         size_t o = total;
         total += ((n + 3) / 4) * 4;  // keep every tensor 16-byte aligned
@@ -879,70 +797,44 @@ struct Packer {
         return o;
     }
     // Conv1d k5 weight (Cout, Cin, 5) [+ the block's residual 1x1 conv (Cout, Cin, 1)] -> the B-fragment stream of
-    // wide_conv_kernel: [Cout/32][CinP/8][slots][64][4], slots = the taps that can be valid at length L (+ the residual)
-    size_t conv_frag(const float* w, const float* wres, int cout, int cin, int cinp, int L) {
-        if (bf3_select(cout, L, WK_K5)) {  // bf3.hip: stream of bf16 triples [Cout/16][CinP/32][slots][3][64][8 bf16] (counted in floats here)
-            const int nslot = 5 + (wres ? 1 : 0);
-            tag(F_FRAG_BF3), tag(cout), tag(cinp), tag(L), tag(wres ? 1 : 0);
-            const size_t o = add(bf3_stream_elems(cout, cinp, nslot) / 2);
-            if (dry) return o;
-            std::vector<float> tmp((size_t)6 * cout * cinp, 0.0f);
-            for (int co = 0; co < cout; ++co)
-                for (int ci = 0; ci < cin; ++ci) {
-                    for (int t = 0; t < 5; ++t) tmp[((size_t)t * cout + co) * cinp + ci] = w[((size_t)co * cin + ci) * 5 + t];
-                    if (wres) tmp[((size_t)5 * cout + co) * cinp + ci] = wres[(size_t)co * cin + ci];
-                }
-            pack_fragments_bf3(tmp.data(), cout, cinp, 5, wres != nullptr, reinterpret_cast<unsigned short*>(&host[o]));
-            return o;
-        }
-        const int sw = wide_ms(cout, L, WK_K5);
-        const int kt0 = (L == 2) ? 1 : 0, ntap = (L == 2) ? 3 : 5, nslab = ntap + (wres ? 1 : 0);
-        tag((L == 4 && sw == 32 && karatsuba_l4()) ? F_FRAG_K4 : (L == 2 && sw == 32 && cout / 8 == 64 && karatsuba_l2()) ? F_FRAG_K2 : F_FRAG);
-        tag(cout), tag(cinp), tag(L), tag(wres ? 1 : 0), tag(sw);
-        if (dry) return add((size_t)(cout / sw) * (cinp / (sw == 32 ? 8 : 16)) * ((L == 4 && sw == 32 && karatsuba_l4()) ? 9 + (wres ? 1 : 0) : nslab) * 256);
+    // wide_conv_kernel: [Cout/32][CinP/8][slots][64][4], slots = the taps that can be valid at length L (+ the residual).
+    // form, sw: the stream layout and the tile height the plan chose for the op (ConvChoice; sw is unused by F_FRAG_BF3)
+    size_t conv_frag(const float* w, const float* wres, int cout, int cin, int cinp, int L, PackForm form, int sw) {
+        const bool bf3 = form == F_FRAG_BF3;  // bf3.hip: stream of bf16 triples [Cout/16][CinP/32][slots][3][64][8 bf16] (counted in floats here)
+        const int kt0 = (L == 2) ? 1 : 0, ntap = (L == 2) ? 3 : 5;
+        const int nslot = (bf3 ? 5 : form == F_FRAG_K4 ? 9 : ntap) + (wres ? 1 : 0);  // (the nested L = 4 form: nine slots instead of five)
+        tag(form), tag(cout), tag(cinp), tag(L), tag(wres ? 1 : 0);
+        if (!bf3) tag(sw);
+        const size_t o = add(bf3 ? bf3_stream_elems(cout, cinp, nslot) / 2 : (size_t)(cout / sw) * (cinp / (sw == 32 ? 8 : 16)) * nslot * 256);
+        if (dry) return o;
         std::vector<float> tmp((size_t)6 * cout * cinp, 0.0f);
         for (int co = 0; co < cout; ++co)
             for (int ci = 0; ci < cin; ++ci) {
                 for (int t = 0; t < 5; ++t) tmp[((size_t)t * cout + co) * cinp + ci] = w[((size_t)co * cin + ci) * 5 + t];
                 if (wres) tmp[((size_t)5 * cout + co) * cinp + ci] = wres[(size_t)co * cin + ci];
             }
-        const bool k4 = L == 4 && sw == 32 && karatsuba_l4();
-        size_t o = k4 ? add_untagged((size_t)(cout / sw) * (cinp / 8) * nslab * 256) : add((size_t)(cout / sw) * (cinp / (sw == 32 ? 8 : 16)) * nslab * 256);
-        if (k4) {
-            // nine slots (+ residual) instead of five: the stream is longer than `o` was sized for - re-reserve (signature
-            // unaffected: the dry path tags the nine-slot size only)
-            total = o;
-            if (!dry) host.resize(total);
-            o = add((size_t)(cout / 32) * (cinp / 8) * (9 + (wres ? 1 : 0)) * 256);
-            pack_fragments_k4(tmp.data(), cout, cinp, wres != nullptr, &host[o]);
-        } else if (L == 2 && sw == 32 && cout / 8 == 64 && karatsuba_l2()) pack_fragments_k2(tmp.data(), cout, cinp, wres != nullptr, &host[o]);
+        if (bf3) pack_fragments_bf3(tmp.data(), cout, cinp, 5, wres != nullptr, reinterpret_cast<unsigned short*>(&host[o]));
+        else if (form == F_FRAG_K4) pack_fragments_k4(tmp.data(), cout, cinp, wres != nullptr, &host[o]);
+        else if (form == F_FRAG_K2) pack_fragments_k2(tmp.data(), cout, cinp, wres != nullptr, &host[o]);
         else pack_fragments(tmp.data(), cout, cinp, kt0, ntap, wres != nullptr, &host[o], sw);
         return o;
     }
     // strided Conv1d k3 (Cout, Cin, 3) or ConvTranspose1d k4 (Cin, Cout, 4) of a wide level -> fragment stream, slot = tap
-    size_t resample_frag(const float* w, int cin, int cout, int k, bool transposed, int Lin) {
-        if (bf3_select(cout, Lin, transposed ? WK_UP : WK_DOWN)) {  // bf3.hip: bf16-triple stream, slot = tap
-            tag(F_FRAG_BF3), tag(F_RESAMPLE), tag(cout), tag(cin), tag(k), tag(transposed ? 1 : 0);
-            const size_t o = add(bf3_stream_elems(cout, cin, k) / 2);
-            if (dry) return o;
-            std::vector<float> tmp((size_t)6 * cout * cin, 0.0f);
-            for (int co = 0; co < cout; ++co)
-                for (int ci = 0; ci < cin; ++ci)
-                    for (int t = 0; t < k; ++t)
-                        tmp[((size_t)t * cout + co) * cin + ci] = transposed ? w[((size_t)ci * cout + co) * k + t] : w[((size_t)co * cin + ci) * k + t];
-            pack_fragments_bf3(tmp.data(), cout, cin, k, false, reinterpret_cast<unsigned short*>(&host[o]));
-            return o;
-        }
-        const int sw = wide_ms(cout, Lin, transposed ? WK_UP : WK_DOWN);
-        tag(F_RESAMPLE), tag(cout), tag(cin), tag(k), tag(transposed ? 1 : 0), tag(sw);
-        if (dry) return add((size_t)(cout / sw) * (cin / (sw == 32 ? 8 : 16)) * k * 256);
+    // (form: F_FRAG_BF3 = bf3.hip's bf16-triple stream | F_FRAG with the tile height sw)
+    size_t resample_frag(const float* w, int cin, int cout, int k, bool transposed, PackForm form, int sw) {
+        const bool bf3 = form == F_FRAG_BF3;
+        if (bf3) tag(F_FRAG_BF3);
+        tag(F_RESAMPLE), tag(cout), tag(cin), tag(k), tag(transposed ? 1 : 0);
+        if (!bf3) tag(sw);
+        const size_t o = add(bf3 ? bf3_stream_elems(cout, cin, k) / 2 : (size_t)(cout / sw) * (cin / (sw == 32 ? 8 : 16)) * k * 256);
+        if (dry) return o;
         std::vector<float> tmp((size_t)6 * cout * cin, 0.0f);
         for (int co = 0; co < cout; ++co)
             for (int ci = 0; ci < cin; ++ci)
                 for (int t = 0; t < k; ++t)
                     tmp[((size_t)t * cout + co) * cin + ci] = transposed ? w[((size_t)ci * cout + co) * k + t] : w[((size_t)co * cin + ci) * k + t];
-        size_t o = add((size_t)(cout / sw) * (cin / (sw == 32 ? 8 : 16)) * k * 256);
-        pack_fragments(tmp.data(), cout, cin, 0, k, false, &host[o], sw);
+        if (bf3) pack_fragments_bf3(tmp.data(), cout, cin, k, false, reinterpret_cast<unsigned short*>(&host[o]));
+        else pack_fragments(tmp.data(), cout, cin, 0, k, false, &host[o], sw);
         return o;
     }
     size_t vec(const float* v, int n) {
@@ -1009,26 +901,37 @@ struct POp {
     int tb_off;
     double fn, fe, fd;  // FLOPs per trajectory: nominal | issued | direct form without padding taps (0: same as fe)
     size_t br;  // bias of a residual 1x1 conv folded into an OP_RCB
-    int blk;
     int res_out;  // OP_RCB: buffer receiving the folded residual 1x1 conv (-1: none)
+    const ConvInst* inst;  // OP_RCB / OP_WRS: the instance that runs the op (choose_conv; the RES row once a residual is folded in)
     // OP_LVL: offsets of the level's tensors in the packed image, in LevelP order; lv_skip: buffer of the skip output (-1: none)
     size_t lvo[24];
-    int lv_variant, lv_tb1, lv_tb2, lv_skip, lv_merge;
+    const LevelInst* lv_inst;   // (choose_level)
+    const Level2Inst* lv_pair;  // set: this level and the next op as one launch (choose_pair)
+    int lv_tb1, lv_tb2, lv_skip;
     // fused conv+gn (OP_RCB): uses src1/src2/C1/C2/Lin/Cout/w/b/dst + gamma/beta/res/tb_off
 };
 
-// the builder's run-time switches, read ONCE per model build and frozen into its plan (two models built under different settings
-// coexist in one process: A/B runs, the adversarial-weights test)
-struct BuildSwitches {
-    bool fused, resfold, level;
-    static BuildSwitches read() {
-        BuildSwitches s;
-        s.fused = getenv("EDMP_NO_FUSED") == nullptr;
-        s.resfold = getenv("EDMP_NO_RESFOLD") == nullptr;
-        s.level = s.fused && getenv("EDMP_NO_LEVEL") == nullptr;
-        return s;
+// kernel instance an op launches, spelled as rocprofv3's kernel trace prints it (minus the edmp:: prefix): lets
+// bench.py's per-kernel table be checked line by line against profiles/*_kernel_stats.csv
+static void op_kernel_name(const POp& o, char* out) {
+    if (o.kind == OP_RCB || o.kind == OP_WRS) {
+        const ConvInst& r = *o.inst;
+        snprintf(out, 64, "%s_conv_kernel<%d, %d, %d, %d, %d, %s>", r.bf3 ? "bf3" : "wide", r.kind, r.ms, r.cg, r.gs, r.L, r.res ? "true" : "false");
+    } else if (o.kind == OP_LVL && o.lv_pair) {
+        const Level2Inst& r = *o.lv_pair;
+        snprintf(out, 64, "level2_kernel<%d, %d, %d, %d, %d, %d, %d, %d, %d>", r.ma, r.ca, r.la, r.cina, r.mb, r.cb, r.lb, r.cinb, r.sb);
+    } else if (o.kind == OP_LVL) {
+        const LevelInst& r = *o.lv_inst;
+        snprintf(out, 64, "level_kernel<%d, %d, %d, %d, %d>", r.mode, r.C, r.L, r.sb, r.cin);
+    } else if (o.kind == OP_CONV) {
+        const int kc = pick_kc(o.C1, o.C2);
+        if (o.Cout % 64 == 0) snprintf(out, 64, "conv_mfma_kernel<64, 64, %d>", kc);
+        else snprintf(out, 64, "conv_mfma_kernel<128, 32, %d>", kc >= 32 ? 32 : kc);
+    } else {
+        const int n = (o.C / 8) * o.L;
+        snprintf(out, 64, "gn_mish_kernel<%d>", n <= 128 ? 2 : n <= 256 ? 4 : 8);
     }
-};
+}
 
 // Walks the architecture (temporalunet.py:47-76) once: decides per layer which kernel family runs it, packs its weights into the
 // device image in that family's layout (or only sizes them: Packer::dry, loading a packed image), assigns activation buffers from a
@@ -1103,7 +1006,8 @@ struct LayerPlan {
             pops.push_back(o);
             return TH{o.dst, Cout, Lout};
         }
-        TH emit_wrs(TH a, size_t w, size_t b, int Cout, int kind, int k, int Lout) {
+        TH emit_wrs(TH a, size_t w, size_t b, int Cout, const ConvInst* inst, int k, int Lout) {
+            const int kind = inst->kind;
             POp o{};
             o.kind = OP_WRS;
             o.src1 = a.buf;
@@ -1119,7 +1023,7 @@ struct LayerPlan {
             o.b = b;
             o.dst = pool.get();
             o.res_out = -1;
-            o.blk = kind;
+            o.inst = inst;
             const bool tr = kind == WK_UP;
             o.fn = tr ? 2.0 * a.L * (double)a.C * Cout * k : 2.0 * Lout * Cout * (double)a.C * k;
             o.fe = 2.0 * (double)valid_pairs(a.L, Lout, k, 2, 1, tr) * Cout * (double)a.C;
@@ -1138,7 +1042,7 @@ struct LayerPlan {
             o.tb_off = tb_off;
             pops.push_back(o);
         }
-        TH emit_fused(TH a, const TH* a2, int cin_true, int cout, size_t w, size_t b, size_t gamma, size_t beta, int res_buf, int tbo) {
+        TH emit_fused(TH a, const TH* a2, int cin_true, int cout, const ConvChoice& ch, size_t w, size_t b, size_t gamma, size_t beta, int res_buf, int tbo) {
             POp o{};
             o.kind = OP_RCB;
             o.src1 = a.buf;
@@ -1156,12 +1060,11 @@ struct LayerPlan {
             o.res = res_buf;
             o.tb_off = tbo;
             o.res_out = -1;
+            o.inst = ch.row[0];
             o.dst = pool.get();
             o.fn = 2.0 * a.L * cout * (double)cin_true * 5;
-            // executed = issued MFMA work: the L = 2 Karatsuba form runs 3 matrix products where the direct form runs 4
-            const bool k2 = a.L == 2 && rcb_form(cout, a.L) == 2 && rcb_supported(cout, a.L, o.C1, o.C2);
-            const bool k4 = a.L == 4 && rcb_form(cout, a.L) == 4 && rcb_supported(cout, a.L, o.C1, o.C2);
-            o.fe = 2.0 * (k2 ? 3.0 : k4 ? 9.0 : (double)valid_pairs(a.L, a.L, 5, 1, 2, false)) * cout * (double)(o.C1 + o.C2);
+            // executed = issued MFMA work: the L = 2 Karatsuba form runs 3 matrix products where the direct form runs 4, the nested L = 4 form 9 for 14
+            o.fe = 2.0 * (ch.form == 2 ? 3.0 : ch.form == 4 ? 9.0 : (double)valid_pairs(a.L, a.L, 5, 1, 2, false)) * cout * (double)(o.C1 + o.C2);
             o.fd = 2.0 * (double)valid_pairs(a.L, a.L, 5, 1, 2, false) * cout * (double)(o.C1 + o.C2);
             pops.push_back(o);
             return TH{o.dst, cout, a.L};
@@ -1170,14 +1073,15 @@ struct LayerPlan {
             const RawRCB& r = inv.rcbs[rcb_idx++];
             const int cin_store = x.C + (x2 ? x2->C : 0);
             // conv1 (a residual 1x1 conv folded into the wide fused kernel is packed right behind it, as tap index 5)
-            const bool wide = sw.fused && rcb_supported(r.cout, x.L, x.C, x2 ? x2->C : 0);
+            const ConvChoice ch1 = choose_conv(sw, WK_K5, r.cout, x.L, x.C, x2 ? x2->C : 0), ch2 = choose_conv(sw, WK_K5, r.cout, x.L, r.cout, 0);
+            const bool wide = ch1.row[0] && ch2.row[0];  // (same shape: both or neither)
             const bool fold_res = wide && r.has_res && sw.resfold;
             // the position-tile kernel reads its weights as an MFMA fragment stream (wide.hip); the generic conv as [tap][Cout][Cin]
-            size_t w1 = wide ? pk.conv_frag(params + r.cb[0].w.off, fold_res ? params + r.rw.off : nullptr, r.cout, r.cin, cin_store, x.L)
+            size_t w1 = wide ? pk.conv_frag(params + r.cb[0].w.off, fold_res ? params + r.rw.off : nullptr, r.cout, r.cin, cin_store, x.L, ch1.stream, ch1.row[0]->ms)
                              : pk.conv(params + r.cb[0].w.off, r.cout, r.cin, 5, cin_store);
             size_t b1 = pk.vec(params + r.cb[0].b.off, r.cout);
             size_t g1 = pk.vec(params + r.cb[0].gw.off, r.cout), be1 = pk.vec(params + r.cb[0].gb.off, r.cout);
-            size_t w2 = wide ? pk.conv_frag(params + r.cb[1].w.off, nullptr, r.cout, r.cout, r.cout, x.L) : pk.conv(params + r.cb[1].w.off, r.cout, r.cout, 5, r.cout);
+            size_t w2 = wide ? pk.conv_frag(params + r.cb[1].w.off, nullptr, r.cout, r.cout, r.cout, x.L, ch2.stream, ch2.row[0]->ms) : pk.conv(params + r.cb[1].w.off, r.cout, r.cout, 5, r.cout);
             size_t b2 = pk.vec(params + r.cb[1].b.off, r.cout);
             size_t g2 = pk.vec(params + r.cb[1].gw.off, r.cout), be2 = pk.vec(params + r.cb[1].gb.off, r.cout);
             int tb_off = tb_cursor;
@@ -1185,12 +1089,13 @@ struct LayerPlan {
             append(tw_all, params + r.tw.off, (size_t)r.cout * td);
             append(tb_all, params + r.tb.off, r.cout);
             if (wide) {
-                TH h = emit_fused(x, x2, r.cin, r.cout, w1, b1, g1, be1, -1, tb_off);
+                TH h = emit_fused(x, x2, r.cin, r.cout, ch1, w1, b1, g1, be1, -1, tb_off);
                 int res_buf;
                 int rr_buf = -1;
                 if (fold_res) {
                     POp& c1 = pops.back();
                     c1.res_out = pool.get();
+                    c1.inst = ch1.row[1];
                     c1.br = pk.vec(params + r.rb.off, r.cout);
                     c1.fn += 2.0 * x.L * r.cout * (double)r.cin;
                     c1.fe += 2.0 * x.L * r.cout * (double)cin_store;
@@ -1207,7 +1112,7 @@ struct LayerPlan {
                 } else {
                     res_buf = x2 ? -2 : x.buf;
                 }
-                TH out = emit_fused(h, nullptr, r.cout, r.cout, w2, b2, g2, be2, res_buf, -1);
+                TH out = emit_fused(h, nullptr, r.cout, r.cout, ch2, w2, b2, g2, be2, res_buf, -1);
                 pool.put(h.buf);
                 if (rr_buf >= 0) pool.put(rr_buf);
                 return out;
@@ -1230,14 +1135,14 @@ struct LayerPlan {
 
         // a whole level in one launch (level.hip): RCB, RCB, resampling conv (+ the final Conv1dBlock); consumes two entries
         // of inv.rcbs like two emit_rcb calls would, in the same order (so the time-bias row keeps its layout)
-        TH emit_level(int mode, int variant, TH xin, const TH* x2, const RawT& rs_w, const RawT& rs_b, bool want_skip, TH* skip_th) {
+        TH emit_level(const LevelInst* lv, TH xin, const TH* x2, const RawT& rs_w, const RawT& rs_b, bool want_skip, TH* skip_th) {
             const RawRCB& r1 = inv.rcbs[rcb_idx++];
             const RawRCB& r2 = inv.rcbs[rcb_idx++];
-            const int Cc = r1.cout, Ll = xin.L, KX = level_kx(variant);
+            const int mode = lv->mode, Cc = r1.cout, Ll = xin.L, KX = std::max(lv->cin, 16);  // the first conv's K: stored input channels, padded to a whole K group
             const int cin_store = xin.C + (x2 ? x2->C : 0);
             POp o{};
             o.kind = OP_LVL;
-            o.lv_variant = variant;
+            o.lv_inst = lv;
             o.src1 = xin.buf;
             o.C1 = xin.C;
             o.src2 = x2 ? x2->buf : -1;
@@ -1245,13 +1150,13 @@ struct LayerPlan {
             o.Lin = Ll;
             o.Cout = Cc;
             size_t* q = o.lvo;
-            // LevelP order: w11 w12 w21 w22 wrs wfin | b11 g11 be11 rb1 | b12 g12 be12 | b21 g21 be21 | b22 g22 be22 | brs | bfin gfin befin
-            q[0] = pk.conv_frag(params + r1.cb[0].w.off, params + r1.rw.off, Cc, r1.cin, KX, Ll);
-            q[1] = pk.conv_frag(params + r1.cb[1].w.off, nullptr, Cc, Cc, Cc, Ll);
-            q[2] = pk.conv_frag(params + r2.cb[0].w.off, nullptr, Cc, Cc, Cc, Ll);
-            q[3] = pk.conv_frag(params + r2.cb[1].w.off, nullptr, Cc, Cc, Cc, Ll);
-            q[4] = pk.resample_frag(params + rs_w.off, Cc, Cc, mode == LV_DOWN ? 3 : 4, mode != LV_DOWN, Ll);
-            q[5] = (mode == LV_UP_FINAL) ? pk.conv_frag(params + inv.final_cb.w.off, nullptr, Cc, Cc, Cc, 50) : 0;
+            // the level kernels read plain fragment streams with 16-sample tiles.  LevelP order: w11 w12 w21 w22 wrs wfin | b11 g11 be11 rb1 | b12 g12 be12 | b21 g21 be21 | b22 g22 be22 | brs | bfin gfin befin
+            q[0] = pk.conv_frag(params + r1.cb[0].w.off, params + r1.rw.off, Cc, r1.cin, KX, Ll, F_FRAG, 16);
+            q[1] = pk.conv_frag(params + r1.cb[1].w.off, nullptr, Cc, Cc, Cc, Ll, F_FRAG, 16);
+            q[2] = pk.conv_frag(params + r2.cb[0].w.off, nullptr, Cc, Cc, Cc, Ll, F_FRAG, 16);
+            q[3] = pk.conv_frag(params + r2.cb[1].w.off, nullptr, Cc, Cc, Cc, Ll, F_FRAG, 16);
+            q[4] = pk.resample_frag(params + rs_w.off, Cc, Cc, mode == LV_DOWN ? 3 : 4, mode != LV_DOWN, F_FRAG, 16);
+            q[5] = (mode == LV_UP_FINAL) ? pk.conv_frag(params + inv.final_cb.w.off, nullptr, Cc, Cc, Cc, 50, F_FRAG, 16) : 0;
             q[6] = pk.vec(params + r1.cb[0].b.off, Cc), q[7] = pk.vec(params + r1.cb[0].gw.off, Cc), q[8] = pk.vec(params + r1.cb[0].gb.off, Cc);
             q[9] = pk.vec(params + r1.rb.off, Cc);
             q[10] = pk.vec(params + r1.cb[1].b.off, Cc), q[11] = pk.vec(params + r1.cb[1].gw.off, Cc), q[12] = pk.vec(params + r1.cb[1].gb.off, Cc);
@@ -1295,17 +1200,16 @@ struct LayerPlan {
         pool.pin(x_in_buf);  // written by the sampler kernels between forwards: never recycled as an activation
         std::vector<TH> skips;
         for (int i = 0; i < nd; ++i) {
-            if (const int lvv = (sw.level && i != nd - 1) ? level_variant(LV_DOWN, dm[i + 1], x.L, x.C, 0) : 0) {
+            if (const LevelInst* lv = (i != nd - 1) ? choose_level(sw, LV_DOWN, dm[i + 1], x.L, x.C, 0) : nullptr) {
                 // the skip of level 0 is never consumed (5 up-samplers for 6 skips, temporalunet.py:31-32,66-67): not even written
                 TH sk{-1, dm[i + 1], x.L};
-                TH xo = emit_level(LV_DOWN, lvv, x, nullptr, inv.down_w[i], inv.down_b[i], i > 0, &sk);
+                TH xo = emit_level(lv, x, nullptr, inv.down_w[i], inv.down_b[i], i > 0, &sk);
                 pool.put(x.buf);
                 skips.push_back(sk);
                 x = xo;
                 // merged with the next down level (level2_kernel): this level's output only ever exists in LDS - no tap
-                const bool merged = lvv == 1 && (level_merge_mask() & 1) && i + 1 < nd - 1 && level_variant(LV_DOWN, dm[i + 2], x.L, x.C, 0) == 2;
-                pops.back().lv_merge = merged ? 1 : 0;
-                if (!merged) {
+                pops.back().lv_pair = choose_pair(sw, lv, i + 1 < nd - 1 ? choose_level(sw, LV_DOWN, dm[i + 2], x.L, x.C, 0) : nullptr);
+                if (!pops.back().lv_pair) {
                     tapr.push_back({i, x.buf, x.C, x.L});
                     pool.pin(x.buf);
                 }
@@ -1318,10 +1222,10 @@ struct LayerPlan {
             skips.push_back(b);
             if (i != nd - 1) {
                 int Lout = (b.L - 1) / 2 + 1;
-                if (sw.fused && wrs_supported(dm[i + 1], b.C, b.L, false)) {
-                    size_t w = pk.resample_frag(params + inv.down_w[i].off, dm[i + 1], dm[i + 1], 3, false, b.L);
+                if (const ConvChoice ch = choose_conv(sw, WK_DOWN, dm[i + 1], b.L, b.C, 0); ch.row[0]) {
+                    size_t w = pk.resample_frag(params + inv.down_w[i].off, dm[i + 1], dm[i + 1], 3, false, ch.stream, ch.row[0]->ms);
                     size_t bb = pk.vec(params + inv.down_b[i].off, dm[i + 1]);
-                    x = emit_wrs(b, w, bb, dm[i + 1], WK_DOWN, 3, Lout);
+                    x = emit_wrs(b, w, bb, dm[i + 1], ch.row[0], 3, Lout);
                 } else {
                     size_t w = pk.conv(params + inv.down_w[i].off, dm[i + 1], dm[i + 1], 3, dm[i + 1]);
                     size_t bb = pk.vec(params + inv.down_b[i].off, dm[i + 1]);
@@ -1350,8 +1254,8 @@ struct LayerPlan {
             {
                 const bool last = (i == 2);
                 const int mode = (last && dm[1] == dm[i - 1] && 2 * x.L == N) ? LV_UP_FINAL : LV_UP;
-                if (const int lvv = sw.level ? level_variant(mode, dm[i - 1], x.L, x.C, sk.C) : 0) {
-                    TH xo = emit_level(mode, lvv, x, &sk, inv.up_w[j], inv.up_b[j], false, nullptr);
+                if (const LevelInst* lv = choose_level(sw, mode, dm[i - 1], x.L, x.C, sk.C)) {
+                    TH xo = emit_level(lv, x, &sk, inv.up_w[j], inv.up_b[j], false, nullptr);
                     pool.put(x.buf);
                     pool.put(sk.buf);
                     x = xo;
@@ -1359,10 +1263,9 @@ struct LayerPlan {
                         final_fused = true;  // the level kernel already applied final_conv.0
                     } else {
                         // merged with the last up level (level2_kernel): this level's output only ever exists in LDS - no tap
-                        const bool merged = lvv == 3 && (level_merge_mask() & 2) && i == 3 && !skips.empty() && dm[1] == dm[i - 2] && 2 * x.L == N &&
-                                            level_variant(LV_UP_FINAL, dm[i - 2], x.L, x.C, skips.back().C) == 4;
-                        pops.back().lv_merge = merged ? 1 : 0;
-                        if (!merged) {
+                        const bool next_is_final = i == 3 && !skips.empty() && dm[1] == dm[i - 2] && 2 * x.L == N;
+                        pops.back().lv_pair = choose_pair(sw, lv, next_is_final ? choose_level(sw, LV_UP_FINAL, dm[i - 2], x.L, x.C, skips.back().C) : nullptr);
+                        if (!pops.back().lv_pair) {
                             tapr.push_back({200 + j, x.buf, x.C, x.L});
                             pool.pin(x.buf);
                         }
@@ -1377,10 +1280,10 @@ struct LayerPlan {
             pool.put(a.buf);
             int Lout = 2 * b.L;
             if (Lout == 8 || Lout == 14 || Lout == 26) Lout -= 1;  // crop rule, temporalunet.py:70-71
-            if (sw.fused && wrs_supported(dm[i - 1], b.C, b.L, true)) {
-                size_t w = pk.resample_frag(params + inv.up_w[j].off, dm[i - 1], dm[i - 1], 4, true, b.L);
+            if (const ConvChoice ch = choose_conv(sw, WK_UP, dm[i - 1], b.L, b.C, 0); ch.row[0]) {
+                size_t w = pk.resample_frag(params + inv.up_w[j].off, dm[i - 1], dm[i - 1], 4, true, ch.stream, ch.row[0]->ms);
                 size_t bb = pk.vec(params + inv.up_b[j].off, dm[i - 1]);
-                x = emit_wrs(b, w, bb, dm[i - 1], WK_UP, 4, Lout);
+                x = emit_wrs(b, w, bb, dm[i - 1], ch.row[0], 4, Lout);
             } else {
                 size_t w = pk.convT(params + inv.up_w[j].off, dm[i - 1], dm[i - 1], 4);
                 size_t bb = pk.vec(params + inv.up_b[j].off, dm[i - 1]);
@@ -1411,6 +1314,8 @@ struct LayerPlan {
         o_tw = pk.vec(tw_all.data(), (int)tw_all.size()), o_tb = pk.vec(tb_all.data(), (int)tb_all.size());
         head_buf = x.buf;
         for (auto& o : pops) EDMP_REQUIRE(!((o.kind == OP_GN || o.kind == OP_RCB) && o.res == -2), "identity residual over a channel concat is not supported");
+        // a Conv1dBlock instance listed without the twin that folds the residual in
+        for (auto& o : pops) EDMP_REQUIRE(o.kind != OP_RCB || o.inst, "no fused conv+GroupNorm kernel for Cout=%d L=%d", o.Cout, o.Lin);
         // the generic GroupNorm keeps a group in registers (gn_mish_kernel, at most 8 x 64 elements): refuse the architecture
         // here, at load, rather than in the middle of its first forward (launch_gn keeps the same check)
         for (auto& o : pops)
@@ -1442,12 +1347,6 @@ static void resolve_program(UNet* u, const LayerPlan& pl) {
             c.bias = u->wpack + o.b;
             c.dst = u->bufs[o.dst];
             c.Cout = o.Cout;
-            op.flops_nominal = o.fn;
-            op.flops_exec = o.fe;
-            u->flops_nominal += o.fn;
-            u->flops_exec += o.fe;
-            op.flops_direct = o.fd > 0 ? o.fd : o.fe;
-            u->flops_direct += op.flops_direct;
         } else if (o.kind == OP_LVL) {
             LevelP& c = op.lv;
             const float* W0 = u->wpack;
@@ -1465,17 +1364,10 @@ static void resolve_program(UNet* u, const LayerPlan& pl) {
             c.tb1 = c.tb2 = nullptr;
             c.skip_out = o.lv_skip >= 0 ? u->bufs[o.lv_skip] : nullptr;
             c.out = u->bufs[o.dst];
-            op.lv_variant = o.lv_variant;
-            op.lv_merge = o.lv_merge;
-            op.lv_sb = level_sb(o.lv_variant);
+            op.lv_inst = o.lv_inst;
+            op.lv_pair = o.lv_pair;
             op.lv_tb1 = o.lv_tb1;
             op.lv_tb2 = o.lv_tb2;
-            op.flops_nominal = o.fn;
-            op.flops_exec = o.fe;
-            u->flops_nominal += o.fn;
-            u->flops_exec += o.fe;
-            op.flops_direct = o.fd > 0 ? o.fd : o.fe;
-            u->flops_direct += op.flops_direct;
         } else if (o.kind == OP_WRS) {
             RcbP& c = op.rc;
             c.src1 = u->bufs[o.src1];
@@ -1486,21 +1378,7 @@ static void resolve_program(UNet* u, const LayerPlan& pl) {
             c.bias = u->wpack + o.b;
             c.dst = u->bufs[o.dst];
             c.Cout = o.Cout;
-            op.rc_L = o.Lin;
-            op.wrs_kind = o.blk;
-            op.rc_ms = wide_ms(o.Cout, o.Lin, o.blk);
-            op.rc_bf3 = bf3_select(o.Cout, o.Lin, o.blk) ? 1 : 0;
-            op.flops_nominal = o.fn;
-            op.flops_exec = o.fe;
-            u->flops_nominal += o.fn;
-            u->flops_exec += o.fe;
-            op.flops_direct = o.fd > 0 ? o.fd : o.fe;
-            u->flops_direct += op.flops_direct;
-            if (op.rc_bf3) {
-                op.flops_bf16 = 6.0 * op.flops_direct;
-                u->flops_bf16 += op.flops_bf16;
-                u->flops_f32_moved += op.flops_exec;
-            }
+            op.inst = o.inst;
         } else if (o.kind == OP_RCB) {
             RcbP& c = op.rc;
             c.src1 = u->bufs[o.src1];
@@ -1517,22 +1395,8 @@ static void resolve_program(UNet* u, const LayerPlan& pl) {
             c.add_res = o.res >= 0 ? u->bufs[o.res] : nullptr;
             c.dst = u->bufs[o.dst];
             c.Cout = o.Cout;
-            op.rc_L = o.Lin;
-            op.rc_form = rcb_form(o.Cout, o.Lin);
-            op.rc_ms = wide_ms(o.Cout, o.Lin, WK_K5);
-            op.rc_bf3 = (op.rc_form == 0 && bf3_select(o.Cout, o.Lin, WK_K5)) ? 1 : 0;
+            op.inst = o.inst;
             op.tb_off = o.tb_off;
-            op.flops_nominal = o.fn;
-            op.flops_exec = o.fe;
-            u->flops_nominal += o.fn;
-            u->flops_exec += o.fe;
-            op.flops_direct = o.fd > 0 ? o.fd : o.fe;
-            u->flops_direct += op.flops_direct;
-            if (op.rc_bf3) {  // six exact partial products per fp32 product, issued on the bf16 pipe
-                op.flops_bf16 = 6.0 * op.flops_direct;
-                u->flops_bf16 += op.flops_bf16;
-                u->flops_f32_moved += op.flops_exec;
-            }
         } else {
             GnP& g = op.gn;
             g.y = u->bufs[o.y];
@@ -1544,16 +1408,35 @@ static void resolve_program(UNet* u, const LayerPlan& pl) {
             g.C = o.C;
             op.tb_off = o.tb_off;
         }
-        op_kernel_name(op, op.name);
+        op.flops_nominal = o.fn;  // (zero for an OP_GN)
+        op.flops_exec = o.fe;
+        op.flops_direct = o.fd > 0 ? o.fd : o.fe;
+        u->flops_nominal += op.flops_nominal;
+        u->flops_exec += op.flops_exec;
+        u->flops_direct += op.flops_direct;
+        if (op.inst && op.inst->bf3) {  // six exact partial products per fp32 product, issued on the bf16 pipe
+            op.flops_bf16 = 6.0 * op.flops_direct;
+            u->flops_bf16 += op.flops_bf16;
+            u->flops_f32_moved += op.flops_exec;
+        }
+        op_kernel_name(o, op.name);
         u->prog.push_back(op);
     }
     // a merged pair is ONE launch, attributed to its first op: that op carries the pair's FLOPs (the model totals are unaffected)
     for (size_t i = 0; i + 1 < u->prog.size(); ++i)
-        if (u->prog[i].kind == OP_LVL && u->prog[i].lv_merge) {
+        if (u->prog[i].kind == OP_LVL && u->prog[i].lv_pair) {
             Op &a = u->prog[i], &b = u->prog[i + 1];
             a.flops_nominal += b.flops_nominal, a.flops_exec += b.flops_exec, a.flops_direct += b.flops_direct;
             b.flops_nominal = b.flops_exec = b.flops_direct = 0.0;
         }
+}
+
+static int check_desc(const edmp_unet_desc* desc) {
+    EDMP_REQUIRE(desc->n_levels >= 2 && desc->n_levels <= EDMP_MAX_LEVELS, "n_levels out of range");
+    EDMP_REQUIRE(desc->input_dim >= 1 && desc->input_dim <= 8, "input_dim must be in 1..8");
+    EDMP_REQUIRE(desc->time_dim >= 4 && desc->time_dim % 2 == 0, "time_dim must be even");
+    for (int i = 0; i < desc->n_levels; ++i) EDMP_REQUIRE(desc->dims[i] % 8 == 0 && desc->dims[i] >= 8, "dims must be multiples of 8");
+    return EDMP_OK;
 }
 
 // builds the layer program + device weight image.  packed == nullptr: repack `params` (state-dict order) on the host;
@@ -1561,11 +1444,8 @@ static void resolve_program(UNet* u, const LayerPlan& pl) {
 static int unet_build(edmp_ctx* ctx, const edmp_unet_desc* desc, const float* params, int64_t n_params, int max_batch, const float* packed,
                       int64_t n_packed, int packed_layout) {
     ctx->epoch++;
-    EDMP_REQUIRE(desc->n_levels >= 2 && desc->n_levels <= EDMP_MAX_LEVELS, "n_levels out of range");
-    EDMP_REQUIRE(desc->input_dim >= 1 && desc->input_dim <= 8, "input_dim must be in 1..8");
-    EDMP_REQUIRE(desc->time_dim >= 4 && desc->time_dim % 2 == 0, "time_dim must be even");
+    if (int rc = check_desc(desc)) return rc;
     EDMP_REQUIRE(max_batch >= 1, "max_batch must be positive");
-    for (int i = 0; i < desc->n_levels; ++i) EDMP_REQUIRE(desc->dims[i] % 8 == 0 && desc->dims[i] >= 8, "dims must be multiples of 8");
     RawNet inv = inventory(*desc);
     static const float no_params = 0.0f;
     if (packed) {  // layout-only pass: the builder computes offsets from `params` but never reads through it (Packer::dry)
@@ -1648,6 +1528,21 @@ extern "C" int edmp_unet_load_packed(edmp_ctx* ctx, const edmp_unet_desc* desc, 
     return unet_build(ctx, desc, nullptr, 0, max_batch, packed, n_packed, layout);
 }
 
+// host-only: the layout-only plan (what loading a packed image computes) under the current builder switches, no device work
+extern "C" int edmp_unet_plan_describe(const edmp_unet_desc* desc, int cap, int* n_ops, char* names, int* layout, int64_t* n_packed) {
+    EDMP_REQUIRE(desc && n_ops, "edmp_unet_plan_describe: null argument");
+    if (int rc = check_desc(desc)) return rc;
+    static const float no_params = 0.0f;
+    LayerPlan pl(desc, &no_params, true);
+    if (int rc = pl.plan()) return rc;
+    const int n = (int)pl.pops.size();
+    *n_ops = n;
+    for (int i = 0; names && i < n && i < cap; ++i) op_kernel_name(pl.pops[i], names + (size_t)i * 64);
+    if (layout) *layout = pl.pk.layout_id(kPackVersion);
+    if (n_packed) *n_packed = (int64_t)pl.pk.total;
+    return EDMP_OK;
+}
+
 extern "C" int64_t edmp_unet_packed_size(edmp_ctx* ctx, int* layout) {
     if (layout) *layout = (ctx && ctx->unet) ? ctx->unet->layout : 0;
     return (ctx && ctx->unet) ? (int64_t)ctx->unet->wpack_floats : -1;
@@ -1690,7 +1585,7 @@ int unet_run_program(edmp_ctx* ctx, int B, int t, const TailP* tail, bool* tail_
     }
     // the tail of the reverse step runs inside the last level's launch when that level is the program's last op (LV_UP_FINAL, 32 channels)
     auto fuse_step_tail = [&](LevelP& p, const Op& o, int index, bool out_is_head_input) {
-        if (tail && tail_done && o.lv_variant == 4 && index + 1 == (int)u->prog.size() && u->head_cin == 32 && tail->N == u->desc.horizon && tail->C <= 8 && out_is_head_input) {
+        if (tail && tail_done && o.lv_inst->mode == LV_UP_FINAL && index + 1 == (int)u->prog.size() && u->head_cin == 32 && tail->N == u->desc.horizon && tail->C <= 8 && out_is_head_input) {
             p.tail = *tail;
             p.tail.on = 1;
             p.tail.w = u->head_w;
@@ -1722,8 +1617,8 @@ int unet_run_program(edmp_ctx* ctx, int B, int t, const TailP* tail, bool* tail_
             p.B = B;
             p.add_tb = op.tb_off >= 0 ? trow + op.tb_off : nullptr;
             EDMP_REQUIRE(!(p.add_tb && p.add_res), "fused conv block: a launch adds the time bias (conv1) or the residual (conv2), not both");
-            rc = launch_rcb(p, op.rc_L, op.rc_form, op.rc_ms, op.rc_bf3, s);
-        } else if (op.kind == OP_LVL && op.lv_merge) {
+            rc = op.inst->launch(p, s, nullptr);
+        } else if (op.kind == OP_LVL && op.lv_pair) {
             const Op& nx = u->prog[op_index + 1];
             LevelP pa = op.lv, pb = nx.lv;
             pa.B = pb.B = B;
@@ -1732,7 +1627,7 @@ int unet_run_program(edmp_ctx* ctx, int B, int t, const TailP* tail, bool* tail_
             pa.tb1 = trow + op.lv_tb1, pa.tb2 = trow + op.lv_tb2;
             pb.tb1 = trow + nx.lv_tb1, pb.tb2 = trow + nx.lv_tb2;
             fuse_step_tail(pb, nx, op_index + 1, out_is_head_input);
-            rc = launch_level2(pa, pb, op.lv_variant, nx.lv_variant, s);
+            rc = op.lv_pair->launch(pa, pb, s);
             skip_index = op_index + 1;
         } else if (op.kind == OP_LVL) {
             LevelP p = op.lv;
@@ -1741,11 +1636,11 @@ int unet_run_program(edmp_ctx* ctx, int B, int t, const TailP* tail, bool* tail_
             p.tb1 = trow + op.lv_tb1;
             p.tb2 = trow + op.lv_tb2;
             fuse_step_tail(p, op, op_index, out_is_head_input);
-            rc = launch_level(p, op.lv_variant, op.lv_sb, s);
+            rc = op.lv_inst->launch(p, s);
         } else if (op.kind == OP_WRS) {
             RcbP p = op.rc;
             p.B = B;
-            rc = launch_wrs(p, op.wrs_kind, op.rc_L, op.rc_ms, op.rc_bf3, s);
+            rc = op.inst->launch(p, s, nullptr);
         } else if (op.kind == OP_CONV) {
             ConvP p = op.cv;
             p.B = B;
@@ -1787,7 +1682,7 @@ int prof_fold(edmp_ctx* ctx) {
                 bool second_of_pair = false;  // (the second level of a merged pair is not a launch of its own)
                 for (const Op& op : ctx->unet->prog) {
                     p.conv_launches += (op.kind != OP_GN && !second_of_pair) ? 1 : 0;
-                    second_of_pair = op.kind == OP_LVL && op.lv_merge;
+                    second_of_pair = op.kind == OP_LVL && op.lv_pair;
                 }
             }
         } else {

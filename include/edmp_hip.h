@@ -73,6 +73,10 @@ int64_t edmp_unet_packed_size(edmp_ctx* ctx, int* layout);
 int edmp_unet_read_packed(edmp_ctx* ctx, float* out_host, int64_t capacity);
 int edmp_unet_load_packed(edmp_ctx* ctx, const edmp_unet_desc* desc, const float* packed, int64_t n_packed, int layout,
                           int max_batch);
+/* host-only (no context, no GPU): the layer program edmp_unet_load would build for `desc` under the current builder switches.
+ * For every op i < min(*n_ops, cap): the kernel instance name (64 bytes each) exactly as edmp_prof_ops reports it for the built model;
+ * *layout / *n_packed: the layout id and float count edmp_unet_packed_size reports for it.  No reference counterpart. */
+int edmp_unet_plan_describe(const edmp_unet_desc* desc, int cap, int* n_ops, char* names, int* layout, int64_t* n_packed);
 /* replaces TemporalUNet.forward (temporalunet.py:47-76): x (B,C,N) f32, integer t in [1,T] -> eps (B,C,N) f32 */
 int edmp_unet_forward_dev(edmp_ctx* ctx, const float* x_dev, int B, int t, float* eps_dev);
 /* debug/parity: copy an internal activation of the last forward, converted to the reference layout (B, C, L) f32, into

@@ -204,6 +204,23 @@ def test_architecture_vs_oracle(aid):
     assert not fails, "\n".join(fails)
 
 
+@pytest.mark.parametrize("aid", ARCH_IDS)
+def test_described_plan_is_the_bound_program(aid):
+    """edmp_unet_plan_describe (host-only; what tests/test_plan_record.py holds to the committed record) names, op for op, the kernels
+    the bound model launches, and reports the layout id and size of its packed image.  max_batch = 1, default switches."""
+    import ctypes as C
+
+    from edmp_amd import _capi
+    from tests.util import T
+
+    dims, cin, td, n, _ = _arch(aid)
+    names, layout, size = _capi.plan_describe(cin, td, dims, n, T)
+    net = _net(aid, max_batch=1)
+    assert _op_names(net) == names
+    lay = C.c_int()
+    assert (net.ctx.lib.edmp_unet_packed_size(net.ctx.h, C.byref(lay)), lay.value) == (size, layout)
+
+
 def test_kernel_families_of_the_sweep():
     """The layer programs really take the paths the sweep is for: bf16x3 instances in A1 / A2, both whole-level merges in A1, the
     generic kernels only in A5 / A6 / A9 / A10, and all three register widths of the generic GroupNorm across the sweep."""

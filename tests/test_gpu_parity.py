@@ -179,7 +179,7 @@ def test_fused_and_unfused_paths_agree(monkeypatch):
 def test_sixteen_sample_tiles_of_the_direct_form_instances(monkeypatch):
     """Round 5: the direct-form position-tile instances of the 256 / 512-channel levels (Conv1dBlock at L = 7, the k3s2 / ConvTranspose
     resamplers) exist with 16-sample tiles (v_mfma_f32_16x16x4_f32, two workgroups per CU) beside the 32-sample ones; EDMP_MS16=<mask>
-    picks per family at model-build time (unet.hip: wide_ms).  Same arithmetic, another summation order: every mask gives the network
+    picks per family at model-build time (unet.hip: choose_conv).  Same arithmetic, another summation order: every mask gives the network
     of the oracle within the gates of test_unet_golden, whole and ragged batches, and the families all differ from mask 0 only by rounding."""
     from edmp_amd import weights as W
     from edmp_amd.temporalunet import TemporalUNet

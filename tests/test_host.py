@@ -328,6 +328,9 @@ def test_c_abi_exports_every_declared_symbol():
     for i, v in enumerate((32, 64, 128, 256, 512, 512)):
         d.dims[i] = v
     assert lib.edmp_unet_param_count(ctypes.byref(d)) == 29_938_471  # host-only entry point
+    # so is the description of the layer plan: 40 launches per forward of the full-size network, a layout id, the image size
+    names, layout, size = _capi.plan_describe(7, 32, (32, 64, 128, 256, 512, 512), 50, 255)
+    assert len(names) == 42 and sum(nm.startswith("bf3_conv_kernel<") for nm in names) == 26 and layout > 0 and size > 0
 
 
 def test_product_fails_loudly_without_gpu():
