@@ -104,6 +104,8 @@ SIGNATURES = {
     "edmp_sdf_set": (_i, [_vp, _pf, _i, _pi32, _pd, _pd, _i, _i]),
     "edmp_sdf_set_self": (_i, [_vp, _pi32, _pd, _pd, _i, _i]),
     "edmp_sdf_self_rows_dev": (_i, [_vp, _vp, _i, _i, _i, _i, _i, _vp, _vp]),
+    "edmp_sdf_set_goal": (_i, [_vp, _pd, _pd, _pi32, _pd, _pd, _i]),
+    "edmp_sdf_goal_rows_dev": (_i, [_vp, _vp, _i, _i, _i, _i, _i, _vp, _vp, _vp, _vp]),
     "edmp_sdf_rows_dev": (_i, [_vp, _vp, _i, _i, _i, _pd, _pd, _vp, _vp]),
     "edmp_scene_batch_set_sdf": (_i, [_vp, _pf, _i, _pi32, _pd, _pd, _i, _i, _i]),
     "edmp_scenes_sdf_rows_dev": (_i, [_vp, _vp, _i, _i, _i, _i, _pd, _pd, _vp, _vp]),

@@ -25,6 +25,22 @@ struct SelfTerm {
     void drop() { n = np = 0; set = false; }
 };
 
+// tool-pose goal term of the SDF guide (sdf.hip, edmp_sdf_set_goal): belongs to the sphere table like the self term
+struct GoalTerm {
+    bool set = false;            // the row arrays, the tool frame and the target block are bound
+    bool derived = false;        // the targets are the poses of the scenes' goal configurations (guide_goal_targets), not the caller's
+    bool have_target = false;    // the target block holds every scene's pose (derived: since the last start / goal upload)
+    int32_t* rows = nullptr;     // [n] indices of the rows whose weight is > 0
+    int n = 0;                   // (0: the gradient paths launch what they launched without the term)
+    double* weight = nullptr;    // [B]
+    double* rotation = nullptr;  // [B]
+    int32_t* window = nullptr;   // [B]
+    float* target = nullptr;     // [EDMP_MAX_SCENES][12] f32 row-major [R* | p*] per scene
+    double tool[12] = {};        // the tool frame behind joint 7, row-major [R | p]
+    float target_h[EDMP_MAX_SCENES * 12] = {};  // host staging of a derived upload (it outlives the enqueued copy)
+    void drop() { n = 0; set = derived = have_target = false; }
+};
+
 // sphere signed-distance guide (sdf.hip, edmp_sdf_set): belongs to the rows it was set for
 struct SdfTable {
     float* sph = nullptr;       // [ns][4] centre | radius in link-box frames, sorted by link
@@ -36,8 +52,11 @@ struct SdfTable {
     double* smooth = nullptr;   // [B]
     std::vector<int32_t> row_h; // [B] host copy of edmp_sdf_set's 0/1 flags (edmp_sdf_set_self checks its weights against it)
     SelfTerm self;
-    void drop() { n = ns = 0; self.drop(); }  // a new table, or new rows, drop the term too
-    std::array<void*, 8> blocks() const { return {sph, rows, margin, smooth, self.pairs, self.rows, self.weight, self.margin}; }  // (guide_destroy)
+    GoalTerm goal;
+    void drop() { n = ns = 0; self.drop(); goal.drop(); }  // a new table, or new rows, drop the terms too
+    std::array<void*, 13> blocks() const {  // (guide_destroy)
+        return {sph, rows, margin, smooth, self.pairs, self.rows, self.weight, self.margin, goal.rows, goal.weight, goal.rotation, goal.window, goal.target};
+    }
 };
 
 struct Guide {
@@ -86,6 +105,9 @@ struct Guide {
 int sdf_overlay(edmp_ctx* ctx, const double* joints, int ldw, int off, int L, int t, int do_clip);
 int guide_set_startgoal(edmp_ctx* ctx, const double* start, const double* goal);  // guide.hip
 int guide_set_startgoal_scenes(edmp_ctx* ctx, int S, const double* starts, const double* goals);  // guide.hip: [S][14] of a scene batch
+// sdf.hip: a goal term with derived targets takes (R* | p*) = T_7(goal_s) . tool of the S goals [S][7] (f64 on the host) and enqueues its
+// upload on the context's stream; the caller's own synchronisation completes it.  No such term: nothing happens
+int guide_goal_targets(edmp_ctx* ctx, int S, const double* goals);
 
 // ctx->d_int (EDMP_MAX_SCENES device ints for small read-backs), allocated at its first use and kept for the life of the context
 inline int ctx_small_ints(edmp_ctx* ctx) {

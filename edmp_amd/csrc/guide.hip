@@ -623,12 +623,17 @@ static int ensure_scratch(edmp_ctx* ctx, Guide* g, int B, int L, bool* realloc =
     return EDMP_OK;
 }
 
-static int upload_startgoal(edmp_ctx* ctx, const float* start, const float* goal) {
+static int upload_startgoal(edmp_ctx* ctx, const float* start, const float* goal, const double* goal64 = nullptr) {
     Guide* g = ctx->guide;
     float sg[14];
     for (int i = 0; i < 7; ++i) {
         sg[i] = start ? start[i] : 0.f;
         sg[7 + i] = goal ? goal[i] : 0.f;
+    }
+    if (g->sdf.goal.set && g->sdf.goal.derived) {  // (guide_set_startgoal hands its f64 goal over; here the f32 one is all there is)
+        double g64[7];
+        for (int i = 0; i < 7; ++i) g64[i] = goal64 ? goal64[i] : (double)sg[7 + i];
+        if (int rc = guide_goal_targets(ctx, 1, g64)) return rc;
     }
     EDMP_HIP_CHECK(hipMemcpyAsync(g->startgoal, sg, sizeof(sg), hipMemcpyHostToDevice, ctx->stream));
     // the host array is on the stack: make the copy complete before returning (pageable-memory copies are staged
@@ -714,7 +719,7 @@ int guide_set_startgoal(edmp_ctx* ctx, const double* start, const double* goal) 
         s[i] = (float)start[i];
         gl[i] = (float)goal[i];
     }
-    return upload_startgoal(ctx, s, gl);
+    return upload_startgoal(ctx, s, gl, goal);
 }
 // scene batch: S rows of (start 7 | goal 7) f64 -> the guide's f32 [S][14]
 int guide_set_startgoal_scenes(edmp_ctx* ctx, int S, const double* starts, const double* goals) {
@@ -724,6 +729,7 @@ int guide_set_startgoal_scenes(edmp_ctx* ctx, int S, const double* starts, const
             sg[s * 14 + i] = (float)starts[s * 7 + i];
             sg[s * 14 + 7 + i] = (float)goals[s * 7 + i];
         }
+    if (int rc = guide_goal_targets(ctx, S, goals)) return rc;
     EDMP_HIP_CHECK(hipMemcpyAsync(ctx->guide->startgoal, sg, (size_t)S * 14 * sizeof(float), hipMemcpyHostToDevice, ctx->stream));
     EDMP_HIP_CHECK(hipStreamSynchronize(ctx->stream));  // the host array lives on this frame
     return EDMP_OK;

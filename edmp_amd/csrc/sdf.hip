@@ -42,6 +42,20 @@
 // on an active pair.  sdf_self_kernel runs after sdf_guide_kernel over the rows whose weight is > 0, adds this to the row's graw and
 // rewrites rowsq[r].  Every wave walks the whole chain (it needs every z_i, o_i of its lane), the link frames meet in LDS, pair p of
 // the list (s ascending, then u) belongs to wave p % 4 and a wave adds its pairs in list order.
+//
+// Tool-pose goal term (sdf_goal_kernel, edmp_sdf_set_goal): the only term that looks at where the tool is.  For an SDF row r with
+// goal_weight[r] > 0, over the interior waypoints w = 1..L, all arithmetic in f32:
+//   (R_w | p_w) = T_7(q_w) * tool                   joint-7 frame of the chain times a 3 x 4 tool frame
+//   e_pos(w)    = ||p_w - p*||^2
+//   e_ori(w)    = 3 - tr(R*^T R_w)                  = 4 sin^2(theta_w / 2): smooth everywhere, no kink at 0 or pi
+//   rho_r(w)    = max(0, w - L + K_r) / K_r         K_r = goal_window[r] >= 1: a linear ramp that is 1 at w = L
+//   goal(r)     = goal_weight[r] * sum_w rho_r(w) * (e_pos(w) + goal_rotation[r] * e_ori(w))
+// (R* | p*) is the target pose of the row's scene.  No dependence on t, none on the obstacles, no kink: nothing to keep inputs away from.
+// Gradient: with c_k, c*_k the columns of R_w, R* and a_w = sum_k c*_k x c_k (d c_k / d q_i = z_i x c_k, so d e_ori / d q_i = z_i . a_w),
+//   d goal / d q_{w,i} = weight * rho(w) * (2 (p_w - p*) . (z_i x (p_w - o_i)) + rotation * z_i . a_w)        all seven joints.
+// sdf_goal_kernel runs after sdf_guide_kernel and sdf_self_kernel over the rows whose weight is > 0, adds this to the row's graw and
+// rewrites rowsq[r].  One chain walk and seven dot products per waypoint: ONE wave per row, lane = padded waypoint as above, four rows to
+// a 256-thread workgroup (row = rows[blockIdx.x * 4 + wave]); a wave past the list leaves as a whole.  No LDS, no barrier, no atomics.
 #include "common.h"
 #include "chain.h"
 #include "guide.h"
@@ -454,6 +468,98 @@ __device__ __forceinline__ void sdf_self_row(const SelfArgs& a, const RobotConst
 __global__ __launch_bounds__(256) void sdf_self_kernel(SelfArgs a, RobotConst rc) { sdf_self_row<false>(a, rc); }
 __global__ __launch_bounds__(256) void sdf_self_rows_kernel(SelfArgs a, RobotConst rc) { sdf_self_row<true>(a, rc); }
 
+struct GoalArgs {
+    RowView v;               // rows: the rows whose weight is > 0; graw: what the kernels before left; cost: the report's first output
+    int n;                   // rows that the launch covers (waves past it leave)
+    const double* weight;    // [B], or nullptr = 1 (edmp_sdf_goal_rows_dev on rows that are not the bound ones)
+    const double* rotation;  // [B], or nullptr = 1
+    const int32_t* window;   // [B], or nullptr = L
+    const float* target;     // [S][12] row-major (R* | p*) per scene
+    int rps;                 // scene batch: rows per scene (row r reads scene r / rps's target), else 0 = one scene
+    float tool[12];          // row-major (R | p) behind joint 7
+    double* distance;        // rows: [n] ||p_L - p*||
+    double* angle;           // rows: [n] rotation angle between R_L and R*
+    double* min_distance;    // rows: [n] min_w ||p_w - p*||
+};
+
+// ROWS = false: add the goal gradient of row a.v.rows[idx] to graw and rewrite rowsq.  ROWS = true: weighted cost (lane terms summed in
+// f64), distance and angle at the last handed column, smallest distance over the handed columns, of row idx.  idx = blockIdx.x * 4 + wave.
+template <bool ROWS>
+__device__ __forceinline__ void sdf_goal_row(const GoalArgs& a, const RobotConst& rc) {
+    const int lane = threadIdx.x & 63;
+    const int idx = __builtin_amdgcn_readfirstlane((int)blockIdx.x * 4 + (int)(threadIdx.x >> 6));
+    if (idx >= a.n) return;  // (wave-uniform: the whole wave leaves; nothing below waits for another wave)
+    const int r = ROWS ? idx : a.v.rows[idx];
+    const int L = a.v.L;
+    const float* tg = a.target + (a.rps ? r / a.rps : 0) * 12;
+    const float wt = a.weight ? (float)a.weight[r] : 1.f;
+    const float rot = a.rotation ? (float)a.rotation[r] : 1.f;
+    const int K = a.window ? a.window[r] : L;
+
+    // lane = padded waypoint; the end lanes repeat an interior waypoint and are not counted
+    const int w = lane;
+    const bool interior = (w >= 1) && (w <= L);
+    float q[7];
+    lane_joints(a.v, rc, r, w, q);
+    float R[3][3] = {{1, 0, 0}, {0, 1, 0}, {0, 0, 1}};
+    float o[3] = {0, 0, 0};
+    float zax[7][3], org[7][3];
+#pragma unroll
+    for (int j = 0; j < 7; ++j) joint_step(rc, q, j, R, o, zax, org);
+    float TR[3][3], p[3];
+    frame_apply(R, o, a.tool, TR, p);
+
+    const float dp[3] = {p[0] - tg[3], p[1] - tg[7], p[2] - tg[11]};
+    const float epos = fmaf(dp[2], dp[2], fmaf(dp[1], dp[1], dp[0] * dp[0]));
+    // tr(R*^T R_w) = sum_k c*_k . c_k and a_w = sum_k c*_k x c_k, k in column order
+    float tr = 0.f, av[3] = {0.f, 0.f, 0.f};
+#pragma unroll
+    for (int k = 0; k < 3; ++k) {
+        const float sx = tg[k], sy = tg[4 + k], sz = tg[8 + k];
+        const float cx = TR[0][k], cy = TR[1][k], cz = TR[2][k];
+        tr += fmaf(sz, cz, fmaf(sy, cy, sx * cx));
+        av[0] += sy * cz - sz * cy;
+        av[1] += sz * cx - sx * cz;
+        av[2] += sx * cy - sy * cx;
+    }
+    const float rho = (float)max(0, w - L + K) / (float)K;
+
+    if (ROWS) {
+        const float dist = sqrtf(epos);
+        const double term = interior ? (double)(rho * fmaf(rot, 3.f - tr, epos)) : 0.0;
+        const double tot = wave_sum(term);
+        const float dmin = wave_min(interior ? dist : INFINITY);
+        const float an = sqrtf(fmaf(av[2], av[2], fmaf(av[1], av[1], av[0] * av[0])));
+        const float ang = atan2f(0.5f * an, 0.5f * (tr - 1.f));  // the form of ik.hip: exact near 0 and near pi
+        if (lane == L) {  // the last handed column
+            a.v.cost[r] = (double)wt * tot;
+            a.distance[r] = (double)dist;
+            a.angle[r] = (double)ang;
+            a.min_distance[r] = (double)dmin;
+        }
+    } else {
+        const float cf = wt * rho;
+        const float dp2[3] = {2.f * dp[0], 2.f * dp[1], 2.f * dp[2]};
+        float g[7];
+#pragma unroll
+        for (int i = 0; i < 7; ++i) {
+            const float za = fmaf(zax[i][2], av[2], fmaf(zax[i][1], av[1], zax[i][0] * av[0]));
+            const float term = fmaf(rot, za, screw_dot(dp2, zax[i], org[i], p));
+            float gi = 0.f;
+            if (interior) {
+                float* dst = a.v.graw + ((size_t)r * 7 + i) * L + (w - 1);
+                gi = fmaf(cf, term, *dst);
+                *dst = gi;
+            }
+            g[i] = gi;
+        }
+        store_rowsq(g, lane, a.v.rowsq + r);
+    }
+}
+
+__global__ __launch_bounds__(256) void sdf_goal_kernel(GoalArgs a, RobotConst rc) { sdf_goal_row<false>(a, rc); }
+__global__ __launch_bounds__(256) void sdf_goal_rows_kernel(GoalArgs a, RobotConst rc) { sdf_goal_row<true>(a, rc); }
+
 static RowView row_view(const Guide* g, const double* joints, int ldw, int off, int L, int t, int do_clip, const int32_t* rows, const double* margin) {
     return RowView{joints, ldw, off, L, t, do_clip, rows, margin, g->rows_T, g->graw, g->rowsq, nullptr, nullptr};
 }
@@ -461,6 +567,19 @@ static RowView row_view(const Guide* g, const double* joints, int ldw, int off, 
 static void fill_self_args(const Guide* g, SelfArgs& a, const double* joints, int ldw, int off, int L, int t, int do_clip) {
     const SelfTerm& s = g->sdf.self;
     a = SelfArgs{row_view(g, joints, ldw, off, L, t, do_clip, s.rows, s.margin), s.weight, g->sdf.sph, s.pairs, s.np};
+}
+
+static void fill_goal_args(const Guide* g, GoalArgs& a, const double* joints, int ldw, int off, int L, int t, int do_clip) {
+    const GoalTerm& gt = g->sdf.goal;
+    a.v = row_view(g, joints, ldw, off, L, t, do_clip, gt.rows, nullptr);  // (no margin schedule: the term does not depend on t)
+    a.n = gt.n;
+    a.weight = gt.weight;
+    a.rotation = gt.rotation;
+    a.window = gt.window;
+    a.target = gt.target;
+    a.rps = g->is_batch ? g->rps : 0;
+    for (int k = 0; k < 12; ++k) a.tool[k] = (float)gt.tool[k];
+    a.distance = a.angle = a.min_distance = nullptr;
 }
 
 static void fill_args(const Guide* g, SdfArgs& a, const double* joints, int ldw, int off, int L, int t, int do_clip) {
@@ -491,6 +610,16 @@ int sdf_overlay(edmp_ctx* ctx, const double* joints, int ldw, int off, int L, in
         SelfArgs sa;
         fill_self_args(g, sa, joints, ldw, off, L, t, do_clip);
         hipLaunchKernelGGL(sdf_self_kernel, dim3(g->sdf.self.n), dim3(256), 0, ctx->stream, sa, g->rc);
+        EDMP_HIP_CHECK(hipGetLastError());
+    }
+    if (g->sdf.goal.n > 0) {  // the goal term of the weighted rows, on top of both: one wave per row, four rows per workgroup
+        if (!g->sdf.goal.have_target) {  // (every gradient path hands its pair over first)
+            set_error("the goal term's targets are derived from the goal configurations and no start / goal pair has been handed over");
+            return EDMP_ERR_STATE;
+        }
+        GoalArgs ga;
+        fill_goal_args(g, ga, joints, ldw, off, L, t, do_clip);
+        hipLaunchKernelGGL(sdf_goal_kernel, dim3((ga.n + 3) / 4), dim3(256), 0, ctx->stream, ga, g->rc);
         EDMP_HIP_CHECK(hipGetLastError());
     }
     return EDMP_OK;
@@ -534,6 +663,26 @@ static int guide_upload(edmp_ctx* ctx, Drop drop, std::initializer_list<Upload> 
     const hipError_t e2 = hipStreamSynchronize(ctx->stream);  // the host vectors and the caller's arrays may go away after the call
     EDMP_HIP_CHECK(e);
     EDMP_HIP_CHECK(e2);
+    return EDMP_OK;
+}
+
+// the start / goal uploads of guide.hip call this (guide.h): derived targets (R* | p*) = T_7(goal_s) . tool, the host side of chain.h in f64
+int guide_goal_targets(edmp_ctx* ctx, int S, const double* goals) {
+    GoalTerm& gt = ctx->guide->sdf.goal;
+    if (!gt.set || !gt.derived) return EDMP_OK;
+    double dh[7][4];
+    joint_dh64(nullptr, dh);
+    for (int s = 0; s < S; ++s) {
+        double R[3][3] = {{1, 0, 0}, {0, 1, 0}, {0, 0, 1}}, o[3] = {0, 0, 0}, TR[3][3], p[3];
+        for (int j = 0; j < 7; ++j) dh_step(R, o, std::sin(goals[s * 7 + j]), std::cos(goals[s * 7 + j]), dh[j]);
+        frame_apply(R, o, gt.tool, TR, p);
+        for (int i = 0; i < 3; ++i) {
+            for (int c = 0; c < 3; ++c) gt.target_h[s * 12 + i * 4 + c] = (float)TR[i][c];
+            gt.target_h[s * 12 + i * 4 + 3] = (float)p[i];
+        }
+    }
+    EDMP_HIP_CHECK(hipMemcpyAsync(gt.target, gt.target_h, (size_t)S * 12 * sizeof(float), hipMemcpyHostToDevice, ctx->stream));
+    gt.have_target = true;
     return EDMP_OK;
 }
 
@@ -729,6 +878,101 @@ extern "C" int edmp_sdf_self_rows_dev(edmp_ctx* ctx, const double* joints_dev, i
     a.v.cost = cost_dev;
     a.v.clearance = clearance_dev;
     hipLaunchKernelGGL(sdf_self_rows_kernel, dim3(n), dim3(256), 0, ctx->stream, a, g->rc);
+    EDMP_HIP_CHECK(hipGetLastError());
+    return EDMP_OK;
+}
+
+// ---- tool-pose goal term -------------------------------------------------------------------------------------------------------------
+// the rotation part of a row-major [R | p] frame is orthonormal to 1e-6
+static bool frame_orthonormal(const double* f) {
+    for (int a = 0; a < 3; ++a)
+        for (int b = 0; b < 3; ++b) {
+            const double d = f[a] * f[b] + f[4 + a] * f[4 + b] + f[8 + a] * f[8 + b] - (a == b ? 1.0 : 0.0);
+            if (!(std::fabs(d) <= 1e-6)) return false;
+        }
+    return true;
+}
+
+extern "C" int edmp_sdf_set_goal(edmp_ctx* ctx, const double* weight, const double* rotation, const int32_t* window, const double* tool,
+                                 const double* target, int n) {
+    EDMP_REQUIRE(ctx && ctx->guide && ctx->guide->obb && ctx->guide->row_class, "edmp_sdf_set_goal: no guide bound (scene and rows first)");
+    Guide* g = ctx->guide;
+    const SdfTable& tb = g->sdf;
+    GoalTerm& gt = g->sdf.goal;
+    if (tb.ns <= 0) {
+        set_error("edmp_sdf_set_goal: call edmp_sdf_set or edmp_scene_batch_set_sdf first (the term is defined on their sphere table)");
+        return EDMP_ERR_STATE;
+    }
+    EDMP_REQUIRE(weight && rotation && window && tool, "edmp_sdf_set_goal: null argument");
+    EDMP_REQUIRE(n == g->B, "edmp_sdf_set_goal: %d rows given, edmp_rows_set holds %d", n, g->B);
+    const int S = g->S, rps = g->is_batch ? g->rps : 0;
+    for (int k = 0; k < 12; ++k) EDMP_REQUIRE(std::isfinite(tool[k]), "edmp_sdf_set_goal: the tool frame holds a non-finite value");
+    EDMP_REQUIRE(frame_orthonormal(tool), "edmp_sdf_set_goal: the rotation of the tool frame is not orthonormal to 1e-6");
+    for (int s = 0; target && s < S; ++s) {
+        for (int k = 0; k < 12; ++k) EDMP_REQUIRE(std::isfinite(target[s * 12 + k]), "edmp_sdf_set_goal: the target of scene %d holds a non-finite value", s);
+        EDMP_REQUIRE(frame_orthonormal(target + s * 12), "edmp_sdf_set_goal: the rotation of scene %d's target is not orthonormal to 1e-6", s);
+    }
+    char where[48];
+    std::vector<int32_t> rows;
+    for (int b = 0; b < n; ++b) {
+        EDMP_REQUIRE(std::isfinite(weight[b]) && weight[b] >= 0.0, "edmp_sdf_set_goal: %s: weight %g must be finite and >= 0", row_name(where, b, rps), weight[b]);
+        EDMP_REQUIRE(std::isfinite(rotation[b]) && rotation[b] >= 0.0, "edmp_sdf_set_goal: %s: rotation %g must be finite and >= 0", row_name(where, b, rps),
+                     rotation[b]);
+        EDMP_REQUIRE(window[b] >= 1, "edmp_sdf_set_goal: %s: window %d must be >= 1", row_name(where, b, rps), (int)window[b]);
+        if (weight[b] > 0.0) {
+            EDMP_REQUIRE(b < (int)tb.row_h.size() && tb.row_h[b] == 1, "edmp_sdf_set_goal: %s: weight %g on a row that is not an SDF row",
+                         row_name(where, b, rps), weight[b]);
+            rows.push_back(b);
+        }
+    }
+    std::vector<float> tg((size_t)S * 12);
+    for (size_t i = 0; target && i < tg.size(); ++i) tg[i] = (float)target[i];
+    if (int rc = guide_upload(ctx, [&] { gt.drop(); },
+                              {{(void**)&gt.rows, rows.data(), rows.size() * sizeof(int32_t), sizeof(int32_t)},
+                               {(void**)&gt.weight, weight, (size_t)n * sizeof(double), 0},
+                               {(void**)&gt.rotation, rotation, (size_t)n * sizeof(double), 0},
+                               {(void**)&gt.window, window, (size_t)n * sizeof(int32_t), 0},
+                               {(void**)&gt.target, tg.data(), target ? tg.size() * sizeof(float) : 0, EDMP_MAX_SCENES * 12 * sizeof(float)}}))
+        return rc;
+    for (int k = 0; k < 12; ++k) gt.tool[k] = tool[k];
+    gt.n = (int)rows.size();
+    gt.derived = target == nullptr;
+    gt.have_target = target != nullptr;  // derived: the next start / goal upload brings the poses (guide_goal_targets)
+    gt.set = true;
+    return EDMP_OK;
+}
+
+extern "C" int edmp_sdf_goal_rows_dev(edmp_ctx* ctx, const double* joints_dev, int n, int ldw, int off, int L, int t, double* cost_dev,
+                                      double* distance_dev, double* angle_dev, double* min_distance_dev) {
+    EDMP_REQUIRE(ctx && ctx->guide && ctx->guide->obb, "edmp_sdf_goal_rows_dev: scene not set");
+    Guide* g = ctx->guide;
+    if (g->sdf.ns <= 0 || !g->sdf.goal.set) {
+        set_error("edmp_sdf_goal_rows_dev: call edmp_sdf_set_goal first (the tool frame and the targets)");
+        return EDMP_ERR_STATE;
+    }
+    EDMP_REQUIRE(joints_dev && cost_dev && distance_dev && angle_dev && min_distance_dev, "edmp_sdf_goal_rows_dev: null pointer");
+    EDMP_REQUIRE(n >= 1 && L >= 1 && L + 2 <= 64, "edmp_sdf_goal_rows_dev: need n >= 1 and 1 <= L <= 62 waypoints per row (got %d, %d)", n, L);
+    EDMP_REQUIRE(off >= 0 && ldw >= 1 && (int64_t)off + L <= ldw, "edmp_sdf_goal_rows_dev: columns %d .. %d outside rows of %d", off, off + L - 1, ldw);
+    if (int rc = check_report_rows("edmp_sdf_goal_rows_dev", g, n, t)) return rc;
+    EDMP_REQUIRE(!g->is_batch || n == g->B, "edmp_sdf_goal_rows_dev: a scene batch reports its own rows (row r reads scene r / rows-per-scene's target): %d rows given, %d bound",
+                 n, g->B);
+    if (!g->sdf.goal.have_target) {
+        set_error("edmp_sdf_goal_rows_dev: the targets are derived from the goal configurations and no start / goal pair has been handed over since edmp_sdf_set_goal");
+        return EDMP_ERR_STATE;
+    }
+    EDMP_HIP_CHECK(hipSetDevice(ctx->device));
+    GoalArgs a;
+    fill_goal_args(g, a, joints_dev, ldw, off, L, t, 0);
+    a.n = n;
+    if (n != g->B) {  // rows that are not the bound ones: weight 1, rotation 1, the ramp over the whole row
+        a.weight = a.rotation = nullptr;
+        a.window = nullptr;
+    }
+    a.v.cost = cost_dev;
+    a.distance = distance_dev;
+    a.angle = angle_dev;
+    a.min_distance = min_distance_dev;
+    hipLaunchKernelGGL(sdf_goal_rows_kernel, dim3((n + 3) / 4), dim3(256), 0, ctx->stream, a, g->rc);
     EDMP_HIP_CHECK(hipGetLastError());
     return EDMP_OK;
 }

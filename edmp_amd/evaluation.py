@@ -95,6 +95,33 @@ def end_effector_positions(trajectory):
     return np.ascontiguousarray(T[:, :3, 3])
 
 
+def tool_pose_errors(q, target, tool=None) -> dict:
+    """ONE configuration q (7,) against a target pose, on the host in float64: the pose (joint-7 frame of the modified-DH chain) x
+    (tool frame, whatever ik.tool_frame takes) compared with `target` ((xyz, quaternion_wxyz) or a (4, 4) / (3, 4) pose) ->
+    dict(distance [m], angle [rad] = atan2(||a|| / 2, (tr - 1) / 2) with a = sum_k c*_k x c_k: exact near 0 and near pi,
+    position_error [cm] and orientation_error [deg], the units of the reference's evaluator (mpinets/metrics.py:364-385), and
+    e_pos = distance^2, e_ori = 3 - tr(R*^T R) = 4 sin^2(angle / 2), the two parts of the SDF guide's goal term, csrc/sdf.hip).
+    The checker of edmp_sdf_goal_rows_dev and the unit test of the driver's report."""
+    from . import ik
+
+    qv = np.asarray(q, dtype=np.float64)
+    if qv.shape != (7,):
+        raise ValueError(f"q must be 7 joint angles, got shape {qv.shape}")
+    tg = ik.pose_matrix(*target) if isinstance(target, (tuple, list)) and len(target) == 2 and np.ndim(target[0]) == 1 else target
+    tg = ik._check_frame(tg, "target")
+    T = np.eye(4)
+    for j in range(7):
+        a, d, al = franka.DH_A_D_ALPHA[j]
+        T = T @ _dh(a, d, al, qv[j])
+    P = T[:3] @ np.vstack([ik.tool_frame(tool), [0.0, 0.0, 0.0, 1.0]])
+    R, Rt = P[:, :3], tg[:, :3]
+    dp = P[:, 3] - tg[:, 3]
+    av = np.sum(np.cross(Rt.T, R.T), axis=0)  # sum over the columns k of c*_k x c_k
+    tr = float(np.sum(Rt * R))
+    dist, ang = float(np.linalg.norm(dp)), float(np.arctan2(np.linalg.norm(av) / 2, (tr - 1) / 2))
+    return dict(distance=dist, angle=ang, position_error=100.0 * dist, orientation_error=float(np.degrees(ang)), e_pos=float(dp @ dp), e_ori=3.0 - tr)
+
+
 def path_lengths(trajectory) -> dict:
     """MetricsCalculator.path_length_metric (lib/metrics.py:32-45): joint-space and end-effector path length."""
     tr = np.asarray(trajectory, dtype=np.float64)

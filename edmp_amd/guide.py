@@ -96,14 +96,27 @@ def goal_filter_device_inputs(n_scenes, starts, goals, counts):
     return st, np.ascontiguousarray(cn.astype(np.int32))
 
 
+def goal_pose(target):
+    """a goal target - (xyz, quaternion_wxyz) or a (4, 4) / (3, 4) pose - as the checked (3, 4) f64 [R* | p*]; None stays None"""
+    from . import ik
+
+    if target is None:
+        return None
+    if isinstance(target, (tuple, list)) and len(target) == 2 and np.ndim(target[0]) == 1:
+        target = ik.pose_matrix(target[0], target[1])
+    return ik._check_frame(target, "goal_target")
+
+
 def sdf_tables(guide_cfgs, batch_size, T, link_half_extents, spheres=None, self_pairs=None):
     """Host tables of the sphere signed-distance guide (edmp_sdf_set), checked before anything touches the device: the sphere table
     (n, 5) f32 [link 0..8, centre xyz in the link-box frame, radius] - ``spheres`` or franka.spheres_from_boxes of the link boxes - and
     the row arrays of ``guide_cfgs`` (``sdf_rows`` (B,), ``sdf_margin`` (B, T), ``smoothness`` (B,); a dict without them gives no SDF
     rows, margin 0 and smoothness 0).  The self-clearance term (edmp_sdf_set_self): ``sdf_self_weight`` (B,) and ``sdf_self_margin`` (B, T) of ``guide_cfgs``
     (absent: 0), finite and >= 0, a weight > 0 only on an SDF row, and the (9, 9) link-pair mask ``self_pairs`` (None:
-    franka.self_collision_pairs()).  Returns dict(spheres, rows int32, margin f64, smooth f64, self_weight f64, self_margin f64,
-    self_mask (81,) int32)."""
+    franka.self_collision_pairs()).  The tool-pose goal term (edmp_sdf_set_goal): ``sdf_goal_weight`` (B,), ``sdf_goal_rotation`` (B,)
+    finite and >= 0 and ``sdf_goal_window`` (B,) integers >= 1 (absent: 0, 0, 8), a weight > 0 only on an SDF row.  Returns dict(spheres,
+    rows int32, margin f64, smooth f64, self_weight f64, self_margin f64, self_mask (81,) int32, goal_weight f64, goal_rotation f64,
+    goal_window int32)."""
     B, T = int(batch_size), int(T)
     sph = franka.spheres_from_boxes(link_half_extents) if spheres is None else np.asarray(spheres, dtype=np.float32)
     if sph.ndim != 2 or sph.shape[1] != 5:
@@ -133,9 +146,24 @@ def sdf_tables(guide_cfgs, batch_size, T, link_half_extents, spheres=None, self_
         raise ValueError("sdf_self_weight and sdf_self_margin must be finite and >= 0")
     if np.any((sw > 0) & (rows != 1)):
         raise ValueError(f"sdf_self_weight: row {int(np.nonzero((sw > 0) & (rows != 1))[0][0])} carries a weight > 0 and is not an SDF row")
+    gw = np.asarray(guide_cfgs["sdf_goal_weight"] if "sdf_goal_weight" in guide_cfgs else np.zeros(B), dtype=np.float64)
+    gr = np.asarray(guide_cfgs["sdf_goal_rotation"] if "sdf_goal_rotation" in guide_cfgs else np.zeros(B), dtype=np.float64)
+    gk = np.asarray(guide_cfgs["sdf_goal_window"] if "sdf_goal_window" in guide_cfgs else np.full(B, 8))
+    if gw.shape != (B,) or gr.shape != (B,) or gk.shape != (B,):
+        raise ValueError(f"sdf_goal_weight / sdf_goal_rotation / sdf_goal_window must be ({B},), got {gw.shape}, {gr.shape}, {gk.shape}")
+    for name, v in (("sdf_goal_weight", gw), ("sdf_goal_rotation", gr)):
+        bad = ~(np.isfinite(v) & (v >= 0))
+        if bad.any():
+            raise ValueError(f"{name}: row {int(np.nonzero(bad)[0][0])} holds {v[bad][0]!r}: must be finite and >= 0")
+    bad = ~((gk == np.floor(gk)) & (gk >= 1)) if np.issubdtype(gk.dtype, np.number) else np.ones(B, dtype=bool)
+    if bad.any():
+        raise ValueError(f"sdf_goal_window: row {int(np.nonzero(bad)[0][0])} holds {gk[bad][0]!r}: must be an integer >= 1")
+    if np.any((gw > 0) & (rows != 1)):
+        raise ValueError(f"sdf_goal_weight: row {int(np.nonzero((gw > 0) & (rows != 1))[0][0])} carries a weight > 0 and is not an SDF row")
     return dict(spheres=np.ascontiguousarray(sph), rows=np.ascontiguousarray(rows.astype(np.int32)), margin=np.ascontiguousarray(margin),
                 smooth=np.ascontiguousarray(smooth), self_weight=np.ascontiguousarray(sw), self_margin=np.ascontiguousarray(sm),
-                self_mask=franka.check_pair_mask(self_pairs))
+                self_mask=franka.check_pair_mask(self_pairs), goal_weight=np.ascontiguousarray(gw), goal_rotation=np.ascontiguousarray(gr),
+                goal_window=np.ascontiguousarray(gk.astype(np.int32)))
 
 
 spheres_from_boxes = franka.spheres_from_boxes
@@ -293,6 +321,24 @@ class _SlotObject:
         return self._cost_clearance(out, shape)
 
 
+    def _bind_goal(self):
+        """_bind_sdf for the goal report: an object without a weighted row hands its tool frame and targets over once (all weights 0:
+        the gradient paths launch what they launched)"""
+        self._bind_sdf()
+        if not self._goal_on:
+            self._goal_on = True
+            self._set_goal()
+
+    def _goal_report(self, Xd, shape, ldw, off, L, t):
+        """weighted goal cost, tool distance and angle at the last column and the smallest distance, of every row"""
+        ctx = self.ctx
+        out = ctx.empty((4, int(np.prod(shape))), torch.float64)
+        _capi.check(ctx.lib.edmp_sdf_goal_rows_dev(ctx.h, ptr(Xd), int(np.prod(shape)), int(ldw), int(off), int(L), int(t), *(C.c_void_p(out[i].data_ptr()) for i in range(4))),
+                    "edmp_sdf_goal_rows_dev")
+        h = ctx.to_host(out)
+        return {k: h[i].reshape(shape).copy() for i, k in enumerate(("cost", "distance", "angle", "min_distance"))}
+
+
 class IntersectionVolumeGuide(_SlotObject):
     """Same constructor / method signatures as the reference:
 
@@ -321,10 +367,16 @@ class IntersectionVolumeGuide(_SlotObject):
     pushed away from themselves - the spheres of the link pairs that ``self_pairs`` masks ((9, 9), default
     franka.self_collision_pairs()) are kept ``sdf_self_margin`` apart.  sdf_self_rows(...) reports the term's cost and the minimum self
     clearance of every row.
+
+    Its tool-pose goal term: SDF rows with ``guide_cfgs["sdf_goal_weight"]`` > 0 (guide_cfg: ``hyperparameters.sdf.goal_weight``) are also
+    pulled, over their last ``sdf_goal_window`` waypoints, towards the pose ``goal_target`` - (xyz, quaternion_wxyz) or a (4, 4) / (3, 4)
+    pose of the tool frame ``goal_tool`` (whatever ik.tool_frame takes) in the base frame; None: the pose of the goal configuration of
+    each call.  ``sdf_goal_rotation`` weighs the orientation part.  sdf_goal_rows(...) reports the term's cost and every row's tool
+    distance and angle to the target.
     """
 
     def __init__(self, obstacle_config, device, guide_cfgs, batch_size, *, link_mesh_extents=None, mesh_dir=None, obstacle_kinds=None, bind=True,
-                 spheres=None, self_pairs=None):
+                 spheres=None, self_pairs=None, goal_target=None, goal_tool=None):
         self.ctx = get_context(device)
         self.device = self.ctx.device
         self.guide_cfgs = guide_cfgs
@@ -354,6 +406,11 @@ class IntersectionVolumeGuide(_SlotObject):
         self._self_pairs = franka.check_pair_mask(self_pairs)
         self._sdf = sdf_tables(guide_cfgs, self.batch_size, self.T, self._half, spheres, self._self_pairs.reshape(9, 9)) if ("sdf_rows" in guide_cfgs or spheres is not None) else None
         self._self_on = self.has_self_term  # the self table is handed over with the sphere table (sdf_self_rows turns it on too)
+        from . import ik
+
+        self._goal_tool = np.ascontiguousarray(ik.tool_frame(goal_tool))  # (3, 4)
+        self._goal_target = goal_pose(goal_target)  # (3, 4), or None = derived from the goal configuration
+        self._goal_on = self.has_goal_term  # likewise (sdf_goal_rows turns it on too)
         if bind:
             self._bind()
 
@@ -408,12 +465,26 @@ class IntersectionVolumeGuide(_SlotObject):
         """some SDF row carries a self-clearance weight > 0"""
         return self._sdf is not None and bool((self._sdf["self_weight"] > 0).any())
 
+    @property
+    def has_goal_term(self):
+        """some SDF row carries a goal weight > 0"""
+        return self._sdf is not None and bool((self._sdf["goal_weight"] > 0).any())
+
     def _set_sdf(self):
         d, ctx = self._sdf, self.ctx
         _capi.check(ctx.lib.edmp_sdf_set(ctx.h, _capi.as_pf(d["spheres"]), int(d["spheres"].shape[0]), _capi.as_pi32(d["rows"]), _capi.as_pd(d["margin"]),
                                          _capi.as_pd(d["smooth"]), self.batch_size, int(d["margin"].shape[1])), "edmp_sdf_set")
         if self._self_on:  # the self term belongs to the sphere table: edmp_sdf_set dropped it
             self._set_self()
+        if self._goal_on:  # and so does the goal term
+            self._set_goal()
+
+    def _set_goal(self):
+        d, ctx = self._sdf, self.ctx
+        tool = np.ascontiguousarray(self._goal_tool.reshape(12))
+        tg = None if self._goal_target is None else np.ascontiguousarray(self._goal_target.reshape(1, 12))
+        _capi.check(ctx.lib.edmp_sdf_set_goal(ctx.h, _capi.as_pd(d["goal_weight"]), _capi.as_pd(d["goal_rotation"]), _capi.as_pi32(d["goal_window"]),
+                                              _capi.as_pd(tool), None if tg is None else _capi.as_pd(tg), self.batch_size), "edmp_sdf_set_goal")
 
     def _set_self(self):
         d, ctx = self._sdf, self.ctx
@@ -514,6 +585,19 @@ class IntersectionVolumeGuide(_SlotObject):
             raise ValueError(f"trajectories must be (n, 7, L), got {tuple(X.shape)}")
         self._bind_self()
         return self._self_report(X, (X.shape[0],), X.shape[2], 0, X.shape[2], t)
+
+    def sdf_goal_rows(self, trajectories, t=0):
+        """Tool-pose goal term of EVERY row (edmp_sdf_goal_rows_dev): trajectories (n, 7, L) interior waypoints, f64 (not clipped) ->
+        {"cost": (n,) f64 = the weighted term, "distance": (n,) f64 tool distance to the target [m] and "angle": (n,) f64 rotation angle
+        to it [rad], both at the LAST handed column, "min_distance": (n,) f64 the smallest distance over the handed columns}.  Any n at
+        t = 0 (the rows' weights, rotations and windows only when n is the guide's batch, else 1, 1 and L); t changes nothing else.
+        With ``goal_target=None`` the target is the pose of the goal of the last call that took a start / goal pair (an error before
+        any).  Needs no start / goal pair itself and leaves a segmented run running."""
+        X = self._rows_f64(trajectories)
+        if X.dim() != 3 or X.shape[1] != 7:
+            raise ValueError(f"trajectories must be (n, 7, L), got {tuple(X.shape)}")
+        self._bind_goal()
+        return self._goal_report(X, (X.shape[0],), X.shape[2], 0, X.shape[2], t)
 
     def row_swept_volumes(self, start, goal, trajectories):
         """(B,) f32 t=0 swept volume per row and the argmin (first on ties)."""
@@ -629,6 +713,9 @@ def scene_batch_tables(scenes):
         out.update(sdf_rows=cat("sdf_rows", np.int32), sdf_margin=cat("sdf_margin", np.float64, (T,)), smoothness=cat("smoothness", np.float64))
         if all("sdf_self_weight" in sc for sc in scenes):  # the self-clearance term's row arrays ride along (edmp_sdf_set_self)
             out.update(sdf_self_weight=cat("sdf_self_weight", np.float64), sdf_self_margin=cat("sdf_self_margin", np.float64, (T,)))
+        if all("sdf_goal_weight" in sc for sc in scenes):  # and the goal term's (edmp_sdf_set_goal)
+            out.update(sdf_goal_weight=cat("sdf_goal_weight", np.float64), sdf_goal_rotation=cat("sdf_goal_rotation", np.float64),
+                       sdf_goal_window=cat("sdf_goal_window", np.int32))
     return out
 
 
@@ -652,7 +739,9 @@ class SceneBatch(_SlotObject):
     table (one robot per batch); the SDF masks, margins and smoothness weights are row arrays like method and grad_norm and may differ
     from scene to scene.  The batch hands them over with edmp_scene_batch_set_sdf, and every scene's SDF rows - and the grad_norm rows
     that share their norm - equal the scene's own serial run bit for bit.  sdf_rows(...) reports cost and minimum clearance of every row
-    of the finished state against its own scene."""
+    of the finished state against its own scene.  The self-clearance term takes one pair mask for the batch and the goal term one tool
+    frame (members that disagree are refused) and per-scene targets, all explicit or all derived from the scenes' goals; sdf_self_rows(...)
+    and sdf_goal_rows(...) report them."""
 
     def __init__(self, guides):
         guides = list(guides)
@@ -682,11 +771,20 @@ class SceneBatch(_SlotObject):
                  method=np.asarray(g.guide_cfgs["guidance_method"], dtype=np.float32).reshape(-1),
                  grad_norm=np.asarray(g.guide_cfgs["grad_norm"], dtype=np.float64).reshape(-1), guidance_schedule=g._sched,
                  **(dict(sdf_rows=g._sdf["rows"], sdf_margin=g._sdf["margin"], smoothness=g._sdf["smooth"],
-                        sdf_self_weight=g._sdf["self_weight"], sdf_self_margin=g._sdf["self_margin"]) if sdf else {})) for g in guides])
+                        sdf_self_weight=g._sdf["self_weight"], sdf_self_margin=g._sdf["self_margin"], sdf_goal_weight=g._sdf["goal_weight"],
+                        sdf_goal_rotation=g._sdf["goal_rotation"], sdf_goal_window=g._sdf["goal_window"]) if sdf else {})) for g in guides])
         for k, g in enumerate(guides):  # (host tables still: nothing is bound yet)
             if not np.array_equal(g._self_pairs, g0._self_pairs):
                 raise ValueError(f"scene {k}: the self-clearance pair mask (self_pairs) differs from scene 0's: a batch takes one mask")
+            if not np.array_equal(g._goal_tool, g0._goal_tool):
+                raise ValueError(f"scene {k}: the goal term's tool frame (goal_tool) differs from scene 0's: a batch takes one tool frame")
+            if (g._goal_target is None) != (g0._goal_target is None):
+                raise ValueError(f"scene {k} brings {'no' if g._goal_target is None else 'an explicit'} goal_target and scene 0 "
+                                 f"{'none' if g0._goal_target is None else 'an explicit one'}: the targets of a batch are either all explicit or all derived")
+        self._goal_tool = g0._goal_tool
+        self._goal_targets = None if g0._goal_target is None else np.ascontiguousarray(np.stack([g._goal_target.reshape(12) for g in guides]))
         self._self_on = self.has_self_term
+        self._goal_on = self.has_goal_term
         self._spheres = g0._sdf["spheres"] if sdf else None  # None: no SDF table is bound (sdf_rows builds one when a report is asked for)
         self._slot = new_slot_key()
         self._kinds = None
@@ -722,6 +820,20 @@ class SceneBatch(_SlotObject):
     def has_self_term(self):
         return "sdf_self_weight" in self.tables and bool((self.tables["sdf_self_weight"] > 0).any())
 
+    @property
+    def has_goal_term(self):
+        return "sdf_goal_weight" in self.tables and bool((self.tables["sdf_goal_weight"] > 0).any())
+
+    def _set_goal(self):
+        tb, ctx, n = self.tables, self.ctx, self.n_scenes * self.batch_size
+        w = tb["sdf_goal_weight"] if "sdf_goal_weight" in tb else np.zeros(n)
+        r = tb["sdf_goal_rotation"] if "sdf_goal_rotation" in tb else np.zeros(n)
+        k = tb["sdf_goal_window"] if "sdf_goal_window" in tb else np.full(n, 8, dtype=np.int32)
+        tool = np.ascontiguousarray(self._goal_tool.reshape(12))
+        tg = self._goal_targets
+        _capi.check(ctx.lib.edmp_sdf_set_goal(ctx.h, _capi.as_pd(w), _capi.as_pd(r), _capi.as_pi32(k), _capi.as_pd(tool), None if tg is None else _capi.as_pd(tg), n),
+                    "edmp_sdf_set_goal")
+
     def _set_self(self):
         tb, ctx, n = self.tables, self.ctx, self.n_scenes * self.batch_size
         w = tb["sdf_self_weight"] if "sdf_self_weight" in tb else np.zeros(n)
@@ -741,6 +853,8 @@ class SceneBatch(_SlotObject):
                                                      _capi.as_pd(smooth), self.n_scenes, self.batch_size, self.T), "edmp_scene_batch_set_sdf")
         if self._self_on:
             self._set_self()
+        if self._goal_on:
+            self._set_goal()
 
     def _sdf_host(self):
         if self._spheres is not None:
@@ -881,5 +995,16 @@ class SceneBatch(_SlotObject):
         Xd, N = self._state(trajectories)
         self._bind_self()
         out = self._self_report(Xd, (self.n_scenes, self.batch_size), N, 1, N - 2, t)
+        Xd.record_stream(self.ctx.stream)
+        return out
+
+    def sdf_goal_rows(self, trajectories, t=0, final=False):
+        """IntersectionVolumeGuide.sdf_goal_rows for the (S, B, 7, N) / (S*B, 7, N) state (its interior columns 1..N-2 are the
+        waypoints) in one call -> {"cost", "distance", "angle", "min_distance"}, each (S, B) f64, every row against its own scene's
+        target: scene s's values are what guides[s].sdf_goal_rows gives for X[s][:, :, 1:-1].  final=True hands the goal column over as
+        well (columns 1..N-1, as X[s][:, :, 1:]): distance and angle are then those of the plan's final tool pose."""
+        Xd, N = self._state(trajectories)
+        self._bind_goal()
+        out = self._goal_report(Xd, (self.n_scenes, self.batch_size), N, 1, N - 1 if final else N - 2, t)
         Xd.record_stream(self.ctx.stream)
         return out

@@ -49,11 +49,16 @@ GUIDE_CATALOG = {
 
 # Guides beyond the reference's catalogue, under numbers it does not use.  101: the sphere signed-distance guide (csrc/sdf.hip) with a
 # margin that shrinks towards t = 0 and a light smoothness pull; `sdf` holds the optional keys of `hyperparameters.sdf`.  102: 101 plus
-# the self-clearance term (sdf_self_kernel): the spheres of the masked link pairs are kept self_margin apart.
+# the self-clearance term (sdf_self_kernel): the spheres of the masked link pairs are kept self_margin apart.  103: 102 plus the tool-pose
+# goal term (sdf_goal_kernel) over the last eight waypoints.  The goal values are ILLUSTRATIVE: there are no trained weights to tune them
+# against, and no claim about success rates is made.
 EXTRA_GUIDES = {
     101: dict(_g((0.05, 0.05), *_E_NONE, "sdf", False, "constant", 0.05), sdf=dict(margin=(0.02, 0.08), smoothness=0.01)),
     102: dict(_g((0.05, 0.05), *_E_NONE, "sdf", False, "constant", 0.05),
               sdf=dict(margin=(0.02, 0.08), smoothness=0.01, self_margin=(0.01, 0.03), self_weight=1.0)),
+    103: dict(_g((0.05, 0.05), *_E_NONE, "sdf", False, "constant", 0.05),
+              sdf=dict(margin=(0.02, 0.08), smoothness=0.01, self_margin=(0.01, 0.03), self_weight=1.0, goal_weight=1.0, goal_rotation=0.05,
+                       goal_window=8)),
 }
 METHODS = ("iv", "sv", "sdf")
 
@@ -82,6 +87,9 @@ def catalog_guide_dict(n: int) -> dict:
         d["hyperparameters"]["sdf"] = {"margin": [float(v) for v in g["sdf"]["margin"]], "smoothness": float(g["sdf"]["smoothness"])}
         if "self_weight" in g["sdf"]:
             d["hyperparameters"]["sdf"].update(self_margin=[float(v) for v in g["sdf"]["self_margin"]], self_weight=float(g["sdf"]["self_weight"]))
+        if "goal_weight" in g["sdf"]:
+            d["hyperparameters"]["sdf"].update(goal_weight=float(g["sdf"]["goal_weight"]), goal_rotation=float(g["sdf"]["goal_rotation"]),
+                                               goal_window=int(g["sdf"]["goal_window"]))
     return d
 
 
@@ -122,7 +130,10 @@ def build_guide_cfgs(guide_dicts, batch_size_per_guide, T: int, rows_per_guide=N
     ``hyperparameters.sdf.margin`` [m0, m1] (default: the guide's ``obstacle_clearance.range``) and ``smoothness`` (B,) =
     ``hyperparameters.sdf.smoothness`` (default 0).  The self-clearance term of an 'sdf' guide: ``hyperparameters.sdf.self_weight``
     (default 0) and ``.self_margin`` [m0, m1] (default [0, 0]) add ``sdf_self_weight`` (B,) and ``sdf_self_margin`` (B, T) = linspace
-    over T - only when some guide sets a weight > 0, so every other dict stays key for key what it was.
+    over T - only when some guide sets a weight > 0, so every other dict stays key for key what it was.  The tool-pose goal term of an
+    'sdf' guide: ``hyperparameters.sdf.goal_weight`` (float, default 0), ``.goal_rotation`` (float, default 0) and ``.goal_window`` (int,
+    default 8) add ``sdf_goal_weight`` (B,), ``sdf_goal_rotation`` (B,) and ``sdf_goal_window`` (B,) int - again only when some guide sets
+    a weight > 0; a bad value raises ValueError naming the guide and its first row.
     """
     G = len(guide_dicts)
     counts = [int(batch_size_per_guide)] * G if rows_per_guide is None else [int(c) for c in rows_per_guide]
@@ -151,6 +162,18 @@ def build_guide_cfgs(guide_dicts, batch_size_per_guide, T: int, rows_per_guide=N
             raise ValueError(f"guide {g.get('index', '?')}: sdf.self_weight > 0 needs guidance_method 'sdf' (the term rides on the SDF rows)")
         if sw > 0 and "sdf_self_weight" not in cfgs:
             cfgs.update(sdf_self_weight=np.zeros((B,)), sdf_self_margin=np.zeros((B, T)))
+    for g, first in zip(guide_dicts, np.concatenate([[0], np.cumsum(counts)[:-1]])):
+        sd = g["hyperparameters"].get("sdf") or {}
+        gw, gr, gk = sd.get("goal_weight", 0.0), sd.get("goal_rotation", 0.0), sd.get("goal_window", 8)
+        where = f"guide {g.get('index', '?')} (row {int(first)})"
+        if not (np.ndim(gw) == 0 and np.ndim(gr) == 0 and np.isfinite(gw) and np.isfinite(gr) and gw >= 0 and gr >= 0):
+            raise ValueError(f"{where}: sdf.goal_weight and sdf.goal_rotation must be finite and >= 0, got {gw!r}, {gr!r}")
+        if isinstance(gk, bool) or not isinstance(gk, (int, np.integer)) or gk < 1:
+            raise ValueError(f"{where}: sdf.goal_window must be an integer >= 1, got {gk!r}")
+        if gw > 0 and g["hyperparameters"]["guidance_method"] != "sdf":
+            raise ValueError(f"{where}: sdf.goal_weight > 0 needs guidance_method 'sdf' (the term rides on the SDF rows)")
+        if gw > 0 and "sdf_goal_weight" not in cfgs:
+            cfgs.update(sdf_goal_weight=np.zeros((B,)), sdf_goal_rotation=np.zeros((B,)), sdf_goal_window=np.full((B,), 8, dtype=np.int64))
     r0 = 0
     for g, cnt in zip(guide_dicts, counts):
         rows = slice(r0, r0 + cnt)
@@ -176,6 +199,10 @@ def build_guide_cfgs(guide_dicts, batch_size_per_guide, T: int, rows_per_guide=N
             if "sdf_self_weight" in cfgs:
                 cfgs["sdf_self_weight"][rows] = float(sd.get("self_weight", 0.0))
                 cfgs["sdf_self_margin"][rows, :] = np.linspace(*sd.get("self_margin", (0.0, 0.0)), T)
+            if "sdf_goal_weight" in cfgs:
+                cfgs["sdf_goal_weight"][rows] = float(sd.get("goal_weight", 0.0))
+                cfgs["sdf_goal_rotation"][rows] = float(sd.get("goal_rotation", 0.0))
+                cfgs["sdf_goal_window"][rows] = int(sd.get("goal_window", 8))
         cfgs["grad_norm"][rows] = 1 if h["grad_norm"] else 0
         gs = h["guidance_schedule"]
         cfgs["guidance_schedule"][rows, :] = (1.4 + np.arange(T) / T) if gs["type"] == "varying" else gs["scale_val"]

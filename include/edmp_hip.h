@@ -179,6 +179,32 @@ int edmp_sdf_set_self(edmp_ctx* ctx, const int32_t* pair_mask, const double* wei
  * synchronise. */
 int edmp_sdf_self_rows_dev(edmp_ctx* ctx, const double* joints_dev, int n, int ldw, int off, int L, int t, double* cost_dev,
                            double* clearance_dev);
+/* Tool-pose goal term of the SDF rows (arithmetic in f32; the formulas are stated at the top of csrc/sdf.hip): with
+ * (R_w | p_w) = T_7(q_w) . tool, the joint-7 frame of the modified-DH chain times the tool frame, and (R* | p*) the target of the row's scene,
+ *   goal(r) = weight[r] * sum_{w=1..L} rho_r(w) * (||p_w - p*||^2 + rotation[r] * (3 - tr(R*^T R_w))),
+ *   rho_r(w) = max(0, w - L + window[r]) / window[r]   (a linear ramp over the last window[r] waypoints, 1 at w = L),
+ * interior waypoints only, no dependence on t or on the obstacles.  edmp_sdf_set_goal comes after edmp_sdf_set or
+ * edmp_scene_batch_set_sdf (EDMP_ERR_STATE without a sphere table), on a single-scene guide (S = 1) or a scene batch of S scenes:
+ * weight (n,) and rotation (n,) f64, finite and >= 0; window (n,) int32 >= 1; n = the bound rows (B, or S*B scene after scene); tool
+ * (12,) f64 = row-major 3 x 4 [R | p], one for the whole batch; target (S,12) f64 = each scene's [R* | p*], or NULL = the pose of the
+ * scene's goal configuration: then every start / goal upload (the gradient, the loops, the swept-volume and SDF reports) also computes
+ * T_7(goal_s) . tool on the host in f64 and uploads it in the same stream order.  Rotations must be orthonormal to 1e-6.  A weight > 0
+ * on a row that is not an SDF row is refused; the message names the row (and the scene, in a batch).  Every check comes before anything
+ * is changed.  In the gradient paths sdf_goal_kernel runs after sdf_guide_kernel and sdf_self_kernel over the rows whose weight is > 0
+ * (one wave per row), adds the term's gradient to their raw gradient and rewrites their sum g^2; with no such row nothing is launched
+ * and a row outside the list keeps the bits it had.  Bumps the context's epoch and synchronises, as edmp_sdf_set.  The term belongs to
+ * the sphere table: a later edmp_sdf_set / edmp_scene_batch_set_sdf / edmp_rows_set drops it. */
+int edmp_sdf_set_goal(edmp_ctx* ctx, const double* weight, const double* rotation, const int32_t* window, const double* tool,
+                      const double* target, int n);
+/* the report of the term for EVERY row, laid out as edmp_sdf_self_rows_dev takes them (not clipped), four (n,) f64 device outputs:
+ * cost_dev = goal(r); distance_dev = ||p_L - p*|| in metres and angle_dev = the rotation angle between R_L and R* in radians, both at
+ * the last handed column; min_distance_dev = the smallest ||p_w - p*|| over the handed columns.  t = 0: any n on a single-scene guide,
+ * with weight 1, rotation 1 and window L when n is not the bound row count; t >= 1: n must be the bound row count (t changes nothing
+ * else).  On a scene batch n is the bound row count and row r reads scene r / B's target.  Needs edmp_sdf_set_goal, and with derived
+ * targets a start / goal upload since (EDMP_ERR_STATE without).  It replaces no start / goal pair and does NOT end a segmented run.
+ * Argument errors come before any device call.  Does not synchronise. */
+int edmp_sdf_goal_rows_dev(edmp_ctx* ctx, const double* joints_dev, int n, int ldw, int off, int L, int t, double* cost_dev,
+                           double* distance_dev, double* angle_dev, double* min_distance_dev);
 
 /* ---- plan success: the reference's simulator check, restated geometrically ------------------------------------ */
 /* The guide sees every obstacle as a box (cylinders enter as (r, r, h) boxes, datasets/load_test_dataset.py:136-139) but the
@@ -282,7 +308,7 @@ int edmp_denoise_guided_dev(edmp_ctx* ctx, const double* noise_dev, int B, const
  * continuing segment after any of them is refused.  A run started with guided = 0 cannot be continued with guided = 1 (the guide
  * never received its pair).  Calls that read neither the guide's start / goal pairs, nor the sampler, nor the model's buffers leave a run
  * as it stands, and the next segment continues as if they had not been made: edmp_scenes_goal_filter_dev, edmp_ik_solve_dev,
- * edmp_self_collision_rows_dev and edmp_sdf_self_rows_dev.
+ * edmp_self_collision_rows_dev, edmp_sdf_self_rows_dev and edmp_sdf_goal_rows_dev.
  * start / goal are read by the init segment only (uploaded once, kept on the device); a continuing segment IGNORES its start /
  * goal arguments and goes on with the init segment's pair. */
 int edmp_denoise_guided_segment_dev(edmp_ctx* ctx, const double* noise_dev, int B, const double* start, const double* goal,

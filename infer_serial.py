@@ -175,7 +175,12 @@ def run(cfg_path, dataset=None, max_scenes=None, verbose=True, scenes_in_flight=
     self-collision on the GPU (IntersectionVolumeGuide / SceneBatch.self_collision_rows: the link boxes against each other under
     franka.self_collision_pairs(); a scene group in one call) and adds to the scene's result `self_collision_free` (the chosen plan's
     flag, tallied like success), `rows_self_collision_free`, `first_self_collision_waypoint` and `self_collision_pair` (the chosen plan's
-    first colliding pair as two franka.LINK_NAMES, None when free); with ensemble_report the chosen plan's flag and pair are printed."""
+    first colliding pair as two franka.LINK_NAMES, None when free); with ensemble_report the chosen plan's flag and pair are printed.
+
+    A run config with a goal-weighted SDF guide (``hyperparameters.sdf.goal_weight``, sample guide 103) hands every guide its target: the
+    problem's own target pose (``dataset.target_pose``, given in the frame ``ik_tool``) when it carries one, else the pose of the picked
+    goal configuration; with ensemble_report the chosen plan's ``position_error`` [cm] and ``orientation_error`` [deg] of the final tool
+    pose against it are added and printed, the units of the reference's evaluator (mpinets/metrics.py:364-385)."""
     from concurrent.futures import ThreadPoolExecutor
 
     from edmp_amd.runtime import get_context, lane_context
@@ -222,6 +227,22 @@ def run(cfg_path, dataset=None, max_scenes=None, verbose=True, scenes_in_flight=
         if ensemble_report:
             out["ensemble"] = EV.ensemble_report(guide_numbers, guide_rows, vols, chk, met)
         return out
+
+    def goal_kw(scenes_of_group):
+        """the goal term's constructor keywords, one dict per scene (empty without a goal-weighted guide: the guides are built as they
+        were): the problems' own target poses in the frame ik_tool when every scene of the group carries one, else the pose of the picked goal"""
+        if "sdf_goal_weight" not in guide_cfgs:
+            return [{} for _ in scenes_of_group]
+        probs = getattr(dataset, "problems", None)  # (ProblemSetDataset.target_pose answers None for a problem that brings its own IK goals)
+        targets = [probs[scene_type][scene_num].get("target") if probs is not None and scene_type in probs else None for _, scene_type, scene_num in scenes_of_group]
+        poses = [None if t is None else (t["xyz"], t["quaternion_wxyz"]) for t in targets]
+        if all(p is not None for p in poses):
+            return [dict(goal_target=(np.asarray(p[0], dtype=np.float64), np.asarray(p[1], dtype=np.float64)), goal_tool=ik_tool) for p in poses]
+        return [dict(goal_tool=ik_tool) for _ in poses]
+
+    def goal_extras(rep, idx):
+        """the chosen plan's final tool pose against the target, in the reference evaluator's units (mpinets/metrics.py:364-385)"""
+        return dict(position_error=100.0 * float(rep["distance"][idx]), orientation_error=float(np.degrees(rep["angle"][idx])))
 
     def self_extras(sc, idx):
         """the keys self_collision adds to a scene's result: sc = self_collision_rows' dict of the scene's rows"""
@@ -299,6 +320,7 @@ def run(cfg_path, dataset=None, max_scenes=None, verbose=True, scenes_in_flight=
                     path_length=EV.path_lengths(trajectory), sparc=EV.smoothness(trajectory), planning_time_s=t_plan, scene_wall_s=time.time() - t0, trajectory=trajectory,
                     **({"min_clearance": float(guide.sdf_rows(trajectory[None, :, 1:-1], start_joints, goal_joints)["clearance"][0])} if ensemble_report and guide.has_sdf_rows else {}),
                     **({"min_self_clearance": float(guide.sdf_self_rows(trajectory[None, :, 1:-1])["clearance"][0])} if ensemble_report and guide.has_self_term else {}),
+                    **(goal_extras(guide.sdf_goal_rows(trajectory[None, :, 1:]), 0) if ensemble_report and guide.has_goal_term else {}),  # (the goal column is the last handed one)
                     **(self_extras(guide.self_collision_rows(trajectories), idx) if self_collision else {}), **extras(vols, chk, met))
 
     t_success, t_strict, i, results, pending = 0, 0, 0, [], []
@@ -321,6 +343,8 @@ def run(cfg_path, dataset=None, max_scenes=None, verbose=True, scenes_in_flight=
                 print(f"    chosen plan: minimum sphere clearance {r['min_clearance']:.4f} m")
             if "min_self_clearance" in r:  # (the guide carries the self-clearance term: the sphere model's smallest distance to itself)
                 print(f"    chosen plan: minimum self clearance {r['min_self_clearance']:.4f} m")
+            if "position_error" in r:  # (the guide carries the goal term: the final tool pose against the target)
+                print(f"    chosen plan: position_error {r['position_error']:.3f} cm, orientation_error {r['orientation_error']:.3f} deg")
         if "self_collision_free" in r:
             t_self += r["self_collision_free"]
             if verbose:
@@ -349,10 +373,10 @@ def run(cfg_path, dataset=None, max_scenes=None, verbose=True, scenes_in_flight=
         data = fetch(0, scenes_of_group)
         t0 = time.time()
         guides = []
-        for obstacle_config, _, _, num_cuboids, num_cylinders, _, _ in data:
+        for (obstacle_config, _, _, num_cuboids, num_cylinders, _, _), gkw in zip(data, goal_kw(scenes_of_group)):
             kinds = np.concatenate([np.zeros(int(num_cuboids), dtype=np.int32), np.ones(int(num_cylinders), dtype=np.int32)])
             guides.append(IntersectionVolumeGuide(obstacle_config=obstacle_config, device=lanes[0][0].ctx, guide_cfgs=guide_cfgs, batch_size=total_batch_size,
-                                                  obstacle_kinds=kinds, mesh_dir=benchmark_cfg["model"].get("mesh_dir"), bind=False))
+                                                  obstacle_kinds=kinds, mesh_dir=benchmark_cfg["model"].get("mesh_dir"), bind=False, **gkw))
         batch = SceneBatch(guides)
         t1 = time.time()
         starts = np.stack([np.asarray(d[5], dtype=np.float64) for d in data])
@@ -392,6 +416,7 @@ def run(cfg_path, dataset=None, max_scenes=None, verbose=True, scenes_in_flight=
         # (a run with an SDF guide: the sphere model's clearance of every row of the group in one call, the chosen rows' are reported)
         all_clr = batch.sdf_rows(Xd, starts, goals)["clearance"] if ensemble_report and batch.has_sdf_rows else None
         all_sclr = batch.sdf_self_rows(Xd)["clearance"] if ensemble_report and batch.has_self_term else None
+        all_goal = batch.sdf_goal_rows(Xd, final=True) if ensemble_report and batch.has_goal_term else None
         all_self = batch.self_collision_rows(Xd) if self_collision else None  # (the whole group in one call)
         X = diffuser.ctx.to_host(Xd)  # once, for the result dicts
         out = []
@@ -415,6 +440,7 @@ def run(cfg_path, dataset=None, max_scenes=None, verbose=True, scenes_in_flight=
                             planning_time_s=t_plan, scene_wall_s=time.time() - t0, trajectory=trajectory,
                             **({"min_clearance": float(all_clr[s][idx])} if all_clr is not None else {}),
                             **({"min_self_clearance": float(all_sclr[s][idx])} if all_sclr is not None else {}),
+                            **(goal_extras({k: v[s] for k, v in all_goal.items()}, idx) if all_goal is not None else {}),
                             **(self_extras({k: v[s] for k, v in all_self.items()}, idx) if all_self is not None else {}), **extras(vols, chk, met)))
         return out
 
@@ -435,7 +461,7 @@ def run(cfg_path, dataset=None, max_scenes=None, verbose=True, scenes_in_flight=
                 # success check spawns the latter as true cylinders (infer_serial.py:159-163 -> lib/environment.py:249-268)
                 kinds = np.concatenate([np.zeros(int(num_cuboids), dtype=np.int32), np.ones(int(num_cylinders), dtype=np.int32)])
                 guide = IntersectionVolumeGuide(obstacle_config=obstacle_config, device=lanes[lane][0].ctx, guide_cfgs=guide_cfgs, batch_size=total_batch_size,
-                                                obstacle_kinds=kinds, mesh_dir=benchmark_cfg["model"].get("mesh_dir"))
+                                                obstacle_kinds=kinds, mesh_dir=benchmark_cfg["model"].get("mesh_dir"), **goal_kw([(i, scene_type, scene_num)])[0])
                 t1 = time.time()
                 # IK-goal filter                                                              infer_serial.py:117-129
                 volumes = guide.cost(torch.tensor(all_ik_goals.reshape((-1, 7, 1))), 0, batch_size=all_ik_goals.shape[0]).sum(axis=(1, 2)).cpu().numpy()

@@ -1,0 +1,218 @@
+"""Checker and inputs of the tool-pose goal term of the sphere signed-distance guide (sdf_goal_kernel in edmp_amd/csrc/sdf.hip): a
+float64 torch-autograd evaluation written from the definition - not from the kernel - on the chain of tests/sdf_reference.py.
+
+    (R_w | p_w) = T_7(q_w) . tool
+    e_pos(w)    = ||p_w - p*||^2            e_ori(w) = 3 - tr(R*^T R_w)
+    rho_r(w)    = max(0, w - L + K_r) / K_r
+    goal(r)     = weight_r * sum_{w=1..L} rho_r(w) * (e_pos(w) + rotation_r * e_ori(w))
+
+autograd differentiates the whole expression.  The term has no kink, so nothing is excluded and its own inputs need no margin; the
+mixed-ensemble cases also evaluate the obstacle part and the self term, whose inputs sit >= MIN_GAP from their kinks
+(sdf_reference.assert_margins, sdf_self_inputs.assert_self_margins; `find_seed(lambda s: check_case(name, s))` found the committed
+seeds).  The report's distance and angle come from evaluation.tool_pose_errors (host float64, one configuration at a time).  The same
+calls in torch.float32 are the yardstick.  Gates: sdf_reference.gate relative to the largest element for cost and gradient; distance and
+angle absolute, max(GATE_FACTOR x the float32 yardstick's absolute deviation, GATE_FLOOR x scale) with the largest tool / target
+coordinate as the distance's scale - a distance is a difference of world coordinates - and pi as the angle's."""
+import math
+
+import numpy as np
+import torch
+
+from edmp_amd import evaluation as EV
+from edmp_amd import franka, ik
+from tests import sdf_reference as R
+from tests import sdf_self_inputs as SELF
+
+T, T_CHECK = R.T, R.T_CHECK
+# one row per guide: method, grad_norm, smoothness, self weight, goal weight, goal rotation, window (an int, "L" or "L+5")
+ROW_GUIDES = (("sdf", False, 0.05, 0.0, 0.0, 0.0, 8),
+              ("sdf", False, 0.02, 0.7, 1.0, 0.05, 1),        # SDF + self + goal
+              ("iv", False, 0.0, 0.0, 0.0, 0.0, 8),
+              ("iv", True, 0.0, 0.0, 0.0, 0.0, 8),
+              ("sv", False, 0.0, 0.0, 0.0, 0.0, 8),
+              ("sdf", False, 0.0, 1.5, 0.0, 0.0, 8),          # SDF + self
+              ("sdf", True, 0.0, 0.0, 2.0, 0.5, 8),           # SDF + goal, normalised
+              ("sdf", False, 0.01, 0.0, 0.5, 1.0, "L"),       # SDF + goal
+              ("sv", True, 0.0, 0.0, 0.0, 0.0, 8),
+              ("iv", False, 0.0, 0.0, 0.0, 0.0, 8),
+              ("sdf", False, 0.0, 0.4, 1.5, 0.2, "L+5"),      # SDF + self + goal
+              ("sdf", False, 0.03, 0.0, 0.0, 0.0, 8))
+B = len(ROW_GUIDES)
+GOAL_ROWS = tuple(i for i, g in enumerate(ROW_GUIDES) if g[4] > 0)  # (1, 6, 7, 10): not contiguous, the last workgroup partial
+SDF_ROWS = tuple(i for i, g in enumerate(ROW_GUIDES) if g[0] == "sdf")
+assert GOAL_ROWS == (1, 6, 7, 10)
+CUSTOM_TOOL = np.array([[0.0, -1.0, 0.0, 0.03], [0.8, 0.0, -0.6, -0.02], [0.6, 0.0, 0.8, 0.15]])  # a rotation and an offset off every axis
+
+
+def window_of(spec, L):
+    return L if spec == "L" else L + 5 if spec == "L+5" else int(spec)
+
+
+def guide_dict(row, index, L, with_goal=True, grad_norm=True):
+    method, gn, lam, sw, gw, gr, gk = row
+    d = SELF.guide_dict(method, gn and grad_norm, lam, sw, index)
+    if gw > 0 and with_goal:
+        d["hyperparameters"]["sdf"].update(goal_weight=float(gw), goal_rotation=float(gr), goal_window=window_of(gk, L))
+    return d
+
+
+def mixed_cfgs(L, with_goal=True, grad_norm=True):
+    """the 12-row ensemble for rows of L waypoints (two windows depend on L); with_goal=False: the same rows without the goal keys;
+    grad_norm=False: no row normalises"""
+    from edmp_amd import guide_cfg as GC
+
+    return GC.build_guide_cfgs([guide_dict(g, 400 + i, L, with_goal, grad_norm) for i, g in enumerate(ROW_GUIDES)], 1, T)
+
+
+def pose_of(q, tool=None):
+    """(3, 4) float64 [R | p] of the tool frame at configuration q (7,): evaluation's modified-DH matrix, ik.tool_frame"""
+    M = np.eye(4)
+    for j in range(7):
+        a, d, al = franka.DH_A_D_ALPHA[j]
+        M = M @ EV._dh(a, d, al, float(q[j]))
+    return np.ascontiguousarray((M @ np.vstack([ik.tool_frame(tool), [0.0, 0.0, 0.0, 1.0]]))[:3])
+
+
+def tool_poses(x, tool, dtype):
+    """x (n, 7, L) tensor -> (R (n, L, 3, 3), p (n, L, 3)) of the tool frame"""
+    tl = torch.zeros(4, 4, dtype=dtype)
+    tl[:3] = torch.tensor(ik.tool_frame(tool), dtype=dtype)
+    tl[3, 3] = 1
+    P = R._chain(x.permute(0, 2, 1), dtype)[6] @ tl
+    return P[..., :3, :3], P[..., :3, 3]
+
+
+def evaluate_goal(joints, target, tool, weight, rotation, window, dtype=torch.float64, want_grad=True):
+    """joints (n, 7, L), target (3, 4) [R* | p*], weight / rotation / window (n,) -> dict of f64 ndarrays: cost (n,), grad (n, 7, L),
+    distance / angle (n,) at the last column, min_distance (n,), coord_max.  In float64 distance, angle and min_distance come from
+    evaluation.tool_pose_errors; in another dtype from the same formulas in that dtype (the yardstick)."""
+    jn = np.asarray(joints, dtype=np.float64)
+    n, _, L = jn.shape
+    x = torch.tensor(jn, dtype=dtype, requires_grad=want_grad)
+    tg = torch.tensor(np.asarray(target, dtype=np.float64), dtype=dtype)
+    Rw, pw = tool_poses(x, tool, dtype)
+    dp = pw - tg[:, 3]
+    e_pos = (dp ** 2).sum(-1)
+    tr = (Rw * tg[:, :3]).sum((-1, -2))
+    e_ori = 3 - tr
+    K = torch.tensor(np.asarray(window, dtype=np.float64), dtype=dtype).view(n, 1)
+    w = torch.arange(1, L + 1, dtype=dtype).view(1, L)
+    rho = torch.clamp(w - L + K, min=0) / K
+    wt = torch.tensor(np.asarray(weight, dtype=np.float64), dtype=dtype)
+    rot = torch.tensor(np.asarray(rotation, dtype=np.float64), dtype=dtype).view(n, 1)
+    cost = wt * (rho * (e_pos + rot * e_ori)).sum(1)
+    out = {}
+    if want_grad:
+        cost.sum().backward()
+        out["grad"] = x.grad.detach().to(torch.float64).numpy()
+    f64 = lambda t: t.detach().to(torch.float64).numpy()  # noqa: E731
+    if dtype == torch.float64:
+        errs = [[EV.tool_pose_errors(jn[r, :, c], target, tool) for c in range(L)] for r in range(n)]
+        dist = np.array([[e["distance"] for e in row] for row in errs])
+        out.update(distance=dist[:, -1].copy(), angle=np.array([row[-1]["angle"] for row in errs]), min_distance=dist.min(1))
+    else:
+        with torch.no_grad():
+            dist = torch.sqrt(e_pos)
+            av = torch.cross(tg[:, :3].T.expand(n, L, 3, 3), Rw.transpose(-1, -2), dim=-1).sum(-2)  # sum_k c*_k x c_k
+            ang = torch.atan2(av.norm(dim=-1) / 2, (tr - 1) / 2)
+        out.update(distance=f64(dist[:, -1]), angle=f64(ang[:, -1]), min_distance=f64(dist.min(1).values))
+    out.update(cost=f64(cost), coord_max=float(max(pw.detach().abs().max(), tg[:, 3].abs().max())))
+    return out
+
+
+# ---- targets ---------------------------------------------------------------------------------------------------------------------------
+TARGET_KINDS = ("exact", "random", "pi")
+
+
+def goal_configuration(kind, joints, seed=0):
+    """the configuration whose tool pose is the target: `exact` - row 0's last column (its distance and angle are ~0); `random` - a random
+    configuration; `pi` - row 0's last column with joint 7 turned by pi - 1e-3 (for a tool on the joint's axis the same place, turned)"""
+    q = np.array(joints[0, :, -1], dtype=np.float64)
+    if kind == "random":
+        lo, hi = franka.joint_limits()
+        q = np.random.RandomState(1000 + seed).uniform(lo, hi)
+    elif kind == "pi":
+        q[6] += math.pi - 1e-3
+    return q
+
+
+def random_pose(seed=0):
+    """a pose that is no configuration's: (xyz, quaternion_wxyz), through ik.pose_matrix"""
+    rs = np.random.RandomState(2000 + seed)
+    return rs.uniform([-0.5, -0.5, 0.1], [0.6, 0.5, 0.9]), rs.standard_normal(4)
+
+
+def report_yardstick(joints, target, tool, weight, rotation, window, ev):
+    """deviation of the same formulas in CPU float32 from `ev` (float64): cost relative to the largest, the three others absolute"""
+    e32 = evaluate_goal(joints, target, tool, weight, rotation, window, dtype=torch.float32, want_grad=False)
+    return dict(cost=float(np.abs(e32["cost"] - ev["cost"]).max() / max(np.abs(ev["cost"]).max(), 1e-300)),
+                distance_abs=float(np.abs(e32["distance"] - ev["distance"]).max()), angle_abs=float(np.abs(e32["angle"] - ev["angle"]).max()),
+                min_distance_abs=float(np.abs(e32["min_distance"] - ev["min_distance"]).max()))
+
+
+def abs_gate(yardstick_abs, scale):
+    return max(R.GATE_FACTOR * yardstick_abs, R.GATE_FLOOR * scale)
+
+
+# ---- the mixed ensemble -----------------------------------------------------------------------------------------------------------
+# name -> L, sphere table, tool frame, seed of sdf_reference.make_case (3 obstacles, one of them a true cylinder)
+CASES = {
+    "L1_custom": dict(L=1, spheres="custom", tool=CUSTOM_TOOL, seed=0),
+    "L2_flange": dict(L=2, spheres="default", tool="flange", seed=0),
+    "L48_custom": dict(L=48, spheres="custom", tool=CUSTOM_TOOL, seed=0),
+    "L62_flange": dict(L=62, spheres="default", tool="flange", seed=0),
+}
+N_OBSTACLES, N_CYLINDERS = 3, 1
+_cache = {}
+
+
+def goal_arrays(cfgs):
+    return cfgs["sdf_goal_weight"], cfgs["sdf_goal_rotation"], cfgs["sdf_goal_window"]
+
+
+def check_case(name, seed=None):
+    """inputs of a case with the checkers' float64 results at T_CHECK - obstacle part, self term (both asserted away from their kinks)
+    and goal term against the pose of a random configuration - and the goal term's gradient in float32.  Computed once per case and
+    shared; callers do not modify it."""
+    c = CASES[name]
+    seed = c["seed"] if seed is None else seed
+    if (name, seed) in _cache:
+        return _cache[(name, seed)]
+    L = c["L"]
+    cfgs = mixed_cfgs(L)
+    inp = R.make_case(seed, B, L, N_OBSTACLES, N_CYLINDERS)
+    sph = R.case_spheres(c["spheres"])
+    mask = franka.self_collision_pairs()
+    args = (inp["joints"], inp["start"], inp["goal"], inp["obstacle_config"], inp["kinds"], sph)
+    mt, smt, sw = cfgs["sdf_margin"][:, T_CHECK - 1], cfgs["sdf_self_margin"][:, T_CHECK - 1], cfgs["sdf_self_weight"]
+    sdft = R.evaluate(*args, mt, cfgs["smoothness"])
+    R.assert_margins(sdft, f"{name} seed {seed} t={T_CHECK}")
+    selft = SELF.evaluate_self(inp["joints"], sph, mask, smt, sw)
+    own = np.flatnonzero(sw > 0)  # (the rows the self kernel works on)
+    SELF.assert_self_margins(SELF.evaluate_self(inp["joints"][own], sph, mask, smt[own], np.ones(own.size), want_grad=False), f"{name} seed {seed}")
+    target = pose_of(goal_configuration("random", inp["joints"], seed), c["tool"])
+    goalt = evaluate_goal(inp["joints"], target, c["tool"], *goal_arrays(cfgs))
+    assert all(np.abs(goalt["grad"][r]).max() > 0 for r in GOAL_ROWS) and not goalt["grad"][[r for r in range(B) if r not in GOAL_ROWS]].any()
+    out = dict(inp, name=name, L=L, seed=seed, spheres=sph, custom=c["spheres"] == "custom", tool=c["tool"], mask=mask, cfgs=cfgs, args=args,
+               target=target, sdft=sdft, selft=selft, goalt=goalt)
+    _cache[(name, seed)] = out
+    return out
+
+
+def total_gradient(case):
+    """the float64 raw gradient of the SDF rows at T_CHECK: obstacle part + smoothness + self term + goal term (zero on the other rows)"""
+    g = np.zeros_like(case["sdft"]["grad"])
+    rows = list(SDF_ROWS)
+    g[rows] = case["sdft"]["grad"][rows] + case["selft"]["grad"][rows] + case["goalt"]["grad"][rows]
+    return g
+
+
+def gradient_yardstick(case):
+    """deviation of the whole gradient of the weighted rows, the same formulas in CPU float32, relative to its largest element"""
+    cfgs = case["cfgs"]
+    s32 = R.evaluate(*case["args"], cfgs["sdf_margin"][:, T_CHECK - 1], cfgs["smoothness"], dtype=torch.float32)
+    f32 = SELF.evaluate_self(case["joints"], case["spheres"], case["mask"], cfgs["sdf_self_margin"][:, T_CHECK - 1], cfgs["sdf_self_weight"], dtype=torch.float32)
+    g32 = evaluate_goal(case["joints"], case["target"], case["tool"], *goal_arrays(cfgs), dtype=torch.float32)
+    rows = list(GOAL_ROWS)
+    ref = total_gradient(case)[rows]
+    return float(np.abs(s32["grad"][rows] + f32["grad"][rows] + g32["grad"][rows] - ref).max() / np.abs(ref).max())
