@@ -38,6 +38,7 @@ ERR_LAYOUT = -4
 
 _vp, _i, _d = C.c_void_p, C.c_int, C.c_double
 _pd, _pf, _pi32 = C.POINTER(C.c_double), C.POINTER(C.c_float), C.POINTER(C.c_int32)
+_pu64 = C.POINTER(C.c_uint64)
 
 ALLREDUCE_FN = C.CFUNCTYPE(C.c_int, C.c_void_p, C.c_void_p, C.c_void_p)  # edmp_allreduce_fn(user, hip_stream, sumsq_dev)
 
@@ -77,6 +78,11 @@ SIGNATURES = {
     "edmp_denoise_guided_segment_dev": (_i, [_vp, _vp, _i, _pd, _pd, _i, _i, _i, _i, _i, _vp]),
     "edmp_denoise_guided_rng_dev": (_i, [_vp, C.c_uint64, _i, _pd, _pd, _i, _i, _i, _vp]),
     "edmp_rng_normal_dev": (_i, [_vp, C.c_uint64, _i, _i, _i, _i, _vp]),
+    "edmp_denoise_guided_rng_segment_dev": (_i, [_vp, C.c_uint64, _i, _pd, _pd, _i, _i, _i, _i, _i, _vp]),
+    "edmp_denoise_scenes_rng_dev": (_i, [_vp, _pu64, _i, _i, _pd, _pd, _i, _i, _i, _vp]),
+    "edmp_denoise_scenes_rng_segment_dev": (_i, [_vp, _pu64, _i, _i, _pd, _pd, _i, _i, _i, _i, _i, _vp]),
+    "edmp_sampler_seed_rng_dev": (_i, [_vp, _vp, _i, C.c_uint64, _i, _i, _pd, _pd, _i, _i, _vp]),
+    "edmp_sampler_seed_scenes_rng_dev": (_i, [_vp, _vp, _i, _pu64, _i, _i, _i, _pd, _pd, _i, _i, _vp]),
     "edmp_sampler_set_graph": (_i, [_vp, _i]),
     "edmp_scene_batch_set": (_i, [_vp, _i, _pi32, _pd, _pi32, _pd, _pd, _i, _pf, _pf, _pf]),
     "edmp_denoise_scenes_dev": (_i, [_vp, _vp, _i, _i, _pd, _pd, _i, _i, _i, _vp]),

@@ -102,7 +102,17 @@ __device__ __forceinline__ void level_body(const LevelP& p, float* lds, float* o
     const int wave = __builtin_amdgcn_readfirstlane(tid >> 6);
     const int s = wave % NSLABW;     // output slab
     const int hs = (wave / NSLABW) * SBW;  // first sample (within the workgroup) of this wave's rows
-    const int b0 = blockIdx.x * SB;
+    // This workgroup's samples: SB consecutive rows from b0, below row pB.  In a scene batch (p.tail.rps rows per scene) the workgroups
+    // are dealt scene by scene - the last one of a scene is short when SB does not divide rps -, so a row sits in the slot of the
+    // workgroup that it has in its scene's own run: the GroupNorm partial sums below are taken tile row by tile row, their order
+    // differs between the slots, and only so does a scene of a batch get the bits of its serial run at any number of rows per scene.
+    // Where SB divides rps (and for a single scene, rps = 0) this is blockIdx.x * SB and p.B.
+    int b0 = blockIdx.x * SB, pB = p.B;
+    if (p.tail.rps) {
+        const int per = (p.tail.rps + SB - 1) / SB, sc = blockIdx.x / per;
+        b0 = sc * p.tail.rps + (blockIdx.x - sc * per) * SB;
+        pB = min(p.B, (sc + 1) * p.tail.rps);
+    }
     const int col = s * 16 + (lane & 15);  // this lane's output channel
     const int kq4 = 4 * (lane >> 4);       // channel quad of the A / B fragments
     const int rq4 = 4 * (lane >> 4);       // first accumulator row of this lane within a tile
@@ -121,7 +131,7 @@ __device__ __forceinline__ void level_body(const LevelP& p, float* lds, float* o
         const int i = min(tid + it * 256, SB * L * QCH - 1);
         const int r = i / QCH, q = c * QCH + (i - r * QCH);
         const int sb = r / L, l = r - sb * L;
-        const int bb = min(b0 + sb, p.B - 1);
+        const int bb = min(b0 + sb, pB - 1);
         const int c14 = p.C1 >> 2;
         return (q < c14) ? *reinterpret_cast<const float4*>(p.src1 + ((size_t)bb * L + l) * p.C1 + 4 * q)
                          : *reinterpret_cast<const float4*>(p.src2 + ((size_t)bb * L + l) * p.C2 + 4 * (q - c14));
@@ -452,7 +462,7 @@ __device__ __forceinline__ void level_body(const LevelP& p, float* lds, float* o
         EDMP_IC(MT), EDMP_IC(L), p.b22, p.g22, p.be22, [&](int, int, int sm, int pos) __attribute__((always_inline)) { return TB[(sm * (L + 4) + pos + 2) * RSC + col]; },
         [&](int, int, int sm, int pos, float y) __attribute__((always_inline)) {
             TA[(sm * (L + 4) + pos + 2) * RSC + col] = y;
-            if (p.skip_out && b0 + sm < p.B) p.skip_out[((size_t)(b0 + sm) * L + pos) * C + col] = y;
+            if (p.skip_out && b0 + sm < pB) p.skip_out[((size_t)(b0 + sm) * L + pos) * C + col] = y;
         });
     __syncthreads();
     EDMP_STAMP(LVSLOT, 6)
@@ -477,7 +487,7 @@ __device__ __forceinline__ void level_body(const LevelP& p, float* lds, float* o
                 if constexpr (OUT_LDS) {
                     if (sm < SBW) out_tile[((hs + sm) * (LOUT + 4) + lo + 2) * out_rs + col] = acc[m][r] + brv;
                 } else {
-                    if (sm < SBW && b0 + hs + sm < p.B) p.out[((size_t)(b0 + hs + sm) * LOUT + lo) * C + col] = acc[m][r] + brv;
+                    if (sm < SBW && b0 + hs + sm < pB) p.out[((size_t)(b0 + hs + sm) * LOUT + lo) * C + col] = acc[m][r] + brv;
                 }
             }
     } else {
@@ -503,7 +513,7 @@ __device__ __forceinline__ void level_body(const LevelP& p, float* lds, float* o
                     const float y = acc[m][r] + brv;
                     if constexpr (MODE == LV_UP_FINAL) TF[((hs + sm) * (LOUT + 4) + lo + 2) * RSC + col] = y;
                     else if constexpr (OUT_LDS) out_tile[((hs + sm) * (LOUT + 4) + lo + 2) * out_rs + col] = y;
-                    else if (b0 + hs + sm < p.B) p.out[((size_t)(b0 + hs + sm) * LOUT + lo) * C + col] = y;
+                    else if (b0 + hs + sm < pB) p.out[((size_t)(b0 + hs + sm) * LOUT + lo) * C + col] = y;
                 }
             }
         if constexpr (MODE == LV_UP_FINAL) {
@@ -516,7 +526,7 @@ __device__ __forceinline__ void level_body(const LevelP& p, float* lds, float* o
             // fused tail (below): this thread's state / noise values are requested before the conv stage, they land under it
             double tail_x[8], tail_z[8];
             const int tail_sm = tid / LOUT, tail_pos = tid - tail_sm * LOUT;
-            const bool tail_mine = (C == 32) && p.tail.on && tid < SB * LOUT && b0 + tail_sm < p.B;
+            const bool tail_mine = (C == 32) && p.tail.on && tid < SB * LOUT && b0 + tail_sm < pB;
             if (tail_mine) tail_fetch(p.tail.X, p.tail.z, p.tail.rng != 0, b0 + tail_sm, tail_pos, LOUT, p.tail.C, tail_x, tail_z);
             // ... and the head's weights go into LDS behind the output tile (224 wave-uniform scalar loads in a row would
             // serialise on the scalar cache): TA / TB are dead since the barrier above
@@ -552,7 +562,7 @@ __device__ __forceinline__ void level_body(const LevelP& p, float* lds, float* o
                 } else {
 #pragma unroll
                     for (int e = 0; e < MTF * 4; ++e)
-                        if (yrow[e] >= 0 && b0 + yrow[e] / LOUT < p.B) p.out[((size_t)b0 * LOUT + yrow[e]) * C + col] = yv[e];
+                        if (yrow[e] >= 0 && b0 + yrow[e] / LOUT < pB) p.out[((size_t)b0 * LOUT + yrow[e]) * C + col] = yv[e];
                 }
                 if constexpr (C == 32) {
                     static_assert(SB * LOUT * RSC <= 2 * Cf::TC_FL && SB * LOUT <= 256, "the output tile fits the two dead activation tiles, one thread per row");
@@ -563,7 +573,7 @@ __device__ __forceinline__ void level_body(const LevelP& p, float* lds, float* o
                         for (int q = 0; q < C / 4; ++q) hv[q] = *reinterpret_cast<const float4*>(TY + tid * RSC + 4 * q);
                         const TailP& tl = p.tail;
                         const int b = b0 + tail_sm, pos = tail_pos, i = b * LOUT + pos;
-#define EDMP_TAIL(FIN, RN) head_psample_item<FIN, RN, C>(hv, tail_x, tail_z, i, b, pos, TW, TW + 8 * C, tl.X, nullptr, tl.xin, tl.sg, LOUT, tl.C, tl.c1, tl.sqrt_alpha, tl.beta, tl.zero_row0, tl.rps, tl.seed, tl.rng_step, tl.cond)
+#define EDMP_TAIL(FIN, RN) head_psample_item<FIN, RN, C>(hv, tail_x, tail_z, i, b, pos, TW, TW + 8 * C, tl.X, nullptr, tl.xin, tl.sg, LOUT, tl.C, tl.c1, tl.sqrt_alpha, tl.beta, tl.zero_row0, tl.rps, tl.seeds, tl.rng_step, tl.cond)
                         if (tl.finish) {
                             if (tl.rng) EDMP_TAIL(true, true);
                             else EDMP_TAIL(true, false);
@@ -583,10 +593,10 @@ __device__ __forceinline__ void level_body(const LevelP& p, float* lds, float* o
 }
 
 template <int MODE, int C, int L, int SB, int CIN>
-__global__ __launch_bounds__(256, (SB <= 2 ? 2 : 1)) void level_kernel(const float* a_src1, const float* a_src2, const float* a_w11, int a_C1, int a_C2, int a_B, LevelP pr) {
+__global__ __launch_bounds__(256, (SB <= 2 ? 2 : 1)) void level_kernel(const float* a_src1, const float* a_src2, const float* a_w11, int a_C1, int a_C2, int a_B, int a_rps, LevelP pr) {
     // (leading scalar arguments = what the input staging needs: preloaded into SGPRs at wave launch, see wide_conv_kernel)
     LevelP p = pr;
-    p.src1 = a_src1, p.src2 = a_src2, p.w11 = a_w11, p.C1 = a_C1, p.C2 = a_C2, p.B = a_B;
+    p.src1 = a_src1, p.src2 = a_src2, p.w11 = a_w11, p.C1 = a_C1, p.C2 = a_C2, p.B = a_B, p.tail.rps = a_rps;
     extern __shared__ __attribute__((aligned(16))) float lds[];
     level_body<MODE, C, L, SB, CIN>(p, lds, nullptr, 0, 0);
 }
@@ -597,19 +607,22 @@ __global__ __launch_bounds__(256, (SB <= 2 ? 2 : 1)) void level_kernel(const flo
 // Instances: the two down levels of the 32 / 64-channel resolutions; the two last up levels (level B's input = level A's output
 // followed by the skip tensor, which still comes from HBM).
 template <int MA, int CA, int LA, int CINA, int MB, int CB, int LB, int CINB, int SB>
-__global__ __launch_bounds__(256, (SB <= 2 ? 2 : 1)) void level2_kernel(const float* a_src1, const float* a_src2, const float* a_w11, int a_C1, int a_C2, int a_B, LevelP pa, LevelP pb) {
+__global__ __launch_bounds__(256, (SB <= 2 ? 2 : 1)) void level2_kernel(const float* a_src1, const float* a_src2, const float* a_w11, int a_C1, int a_C2, int a_B, int a_rps, LevelP pa, LevelP pb) {
     using CfA = LevelCfg<MA, CA, LA, SB, CINA>;
     using CfB = LevelCfg<MB, CB, LB, SB, CINB>;
     static_assert(CfA::LOUT == LB, "level B runs at level A's output length");
     static_assert(CfB::KX == CINB && CINB >= CA && CfB::TX_FL <= CfA::TX_ALLOC, "level B's input tile fits inside level A's (dead) input tile");
     LevelP p = pa;
-    p.src1 = a_src1, p.src2 = a_src2, p.w11 = a_w11, p.C1 = a_C1, p.C2 = a_C2, p.B = a_B;
-    pb.B = a_B;
+    p.src1 = a_src1, p.src2 = a_src2, p.w11 = a_w11, p.C1 = a_C1, p.C2 = a_C2, p.B = a_B, p.tail.rps = a_rps;
+    pb.B = a_B, pb.tail.rps = a_rps;
     extern __shared__ __attribute__((aligned(16))) float lds[];
     level_body<MA, CA, LA, SB, CINA, 0, true>(p, lds, lds, CfB::RSX, CfB::TX_FL);
     __syncthreads();  // every wave has written its part of level B's input and is done with level A's tiles
     level_body<MB, CB, LB, SB, CINB, CA, false>(pb, lds, nullptr, 0, 0);
 }
+
+// workgroups of a level launch: SB rows each, dealt scene by scene in a scene batch (level_body)
+static inline int level_grid(int B, int rps, int SB) { return rps ? (B / rps) * ((rps + SB - 1) / SB) : (B + SB - 1) / SB; }
 
 template <int MODE, int C, int L, int SB, int CIN>
 int launch_level_t(const LevelP& p, hipStream_t s) {
@@ -622,7 +635,7 @@ int launch_level_t(const LevelP& p, hipStream_t s) {
         EDMP_HIP_CHECK(hipFuncSetAttribute(reinterpret_cast<const void*>(&level_kernel<MODE, C, L, SB, CIN>), hipFuncAttributeMaxDynamicSharedMemorySize, (int)bytes));
         attr_set.store(1, std::memory_order_release);
     }
-    hipLaunchKernelGGL((level_kernel<MODE, C, L, SB, CIN>), dim3((p.B + SB - 1) / SB), dim3(256), bytes, s, p.src1, p.src2, p.w11, p.C1, p.C2, p.B, p);
+    hipLaunchKernelGGL((level_kernel<MODE, C, L, SB, CIN>), dim3(level_grid(p.B, p.tail.rps, SB)), dim3(256), bytes, s, p.src1, p.src2, p.w11, p.C1, p.C2, p.B, p.tail.rps, p);
     return EDMP_OK;
 }
 
@@ -638,7 +651,7 @@ int launch_level2_t(const LevelP& pa, const LevelP& pb, hipStream_t s) {
         EDMP_HIP_CHECK(hipFuncSetAttribute(reinterpret_cast<const void*>(&level2_kernel<MA, CA, LA, CINA, MB, CB, LB, CINB, SB>), hipFuncAttributeMaxDynamicSharedMemorySize, (int)bytes));
         attr_set.store(1, std::memory_order_release);
     }
-    hipLaunchKernelGGL((level2_kernel<MA, CA, LA, CINA, MB, CB, LB, CINB, SB>), dim3((pa.B + SB - 1) / SB), dim3(256), bytes, s, pa.src1, pa.src2, pa.w11, pa.C1, pa.C2, pa.B, pa, pb);
+    hipLaunchKernelGGL((level2_kernel<MA, CA, LA, CINA, MB, CB, LB, CINB, SB>), dim3(level_grid(pa.B, pa.tail.rps, SB)), dim3(256), bytes, s, pa.src1, pa.src2, pa.w11, pa.C1, pa.C2, pa.B, pa.tail.rps, pa, pb);
     return EDMP_OK;
 }
 

@@ -44,6 +44,9 @@ struct Sampler {
     int run_next = 0;       // the step the kept state stands at = the t_hi the next segment must bring (0 = no run in progress)
     uint64_t run_epoch = 0;  // ctx->epoch when the last segment returned: model, scene, rows and schedule tables of the run
     int run_guided = 0;     // the init segment was guided: only then does the guide hold the run's start / goal pair
+    int run_rng = 0;        // its noise source: 1 = the device source (its seeds sit in `seeds`), 0 = the caller's explicit stream
+    unsigned long long* seeds = nullptr;  // [EDMP_MAX_SCENES] the device source's seed of every scene of the run (one scene: entry 0),
+                                          // uploaded by the run's init beside sg: a continuing segment and a graph replay read it there
     int condition = 1;      // pin X[:, :, 0] / X[:, :, -1] to start / goal (diffusion.py:305-307, 347-349)
     int cap = 0;            // elements
     // whole-run hipGraph (edmp_sampler_set_graph): the enqueue of one denoise_loop call captured once and replayed while the
@@ -82,7 +85,7 @@ void sampler_end_run(edmp_ctx* ctx) {
 void sampler_destroy(Sampler* s) {
     if (!s) return;
     sampler_rccl_destroy(s);
-    for (void* p : {(void*)s->X, (void*)s->sg, (void*)s->qcoef})
+    for (void* p : {(void*)s->X, (void*)s->sg, (void*)s->seeds, (void*)s->qcoef})
         if (p) (void)hipFree(p);
     if (s->gexec) (void)hipGraphExecDestroy(s->gexec);
     delete s;
@@ -168,13 +171,17 @@ __global__ void rng_normal_kernel(uint64_t seed, int step, double* __restrict__ 
 }
 
 // X_T = N(0, I) with start/goal conditioning, plus the first UNet input              (diffusion.py:303-307)
-__global__ void init_state_rng_kernel(uint64_t seed, double* __restrict__ X, float* __restrict__ xin, const double* __restrict__ sg, int B, int C,
-                                      int N, int cond) {
+// rps != 0 (a scene batch): row b draws its scene's stream (tail.h: rng_scene) and conditions on its scene's start / goal pair
+__global__ void init_state_rng_kernel(const unsigned long long* __restrict__ seeds, double* __restrict__ X, float* __restrict__ xin,
+                                      const double* __restrict__ sg, int B, int C, int N, int cond, int rps) {
     int i = blockIdx.x * blockDim.x + threadIdx.x;
     if (i >= B * N) return;
     const int b = i / N, l = i - b * N;
     float z[8];
-    rng_normal8(seed, 0u, (uint32_t)i, z);
+    uint32_t elem;
+    const uint64_t seed = rng_scene(seeds, rps, b, i, N, &elem);
+    rng_normal8(seed, 0u, elem, z);
+    if (rps) sg += 14 * (b / rps);
     float xo[8] = {0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f};
     for (int c = 0; c < C && c < 8; ++c) {
         double x = (double)z[c];
@@ -210,7 +217,7 @@ template <bool FINISH, bool RNG, int CIN>
 __global__ __launch_bounds__(256) void head_psample_kernel(const float* __restrict__ h, const float* __restrict__ w, const float* __restrict__ bias,
                                                            double* __restrict__ X, const double* __restrict__ z, float* __restrict__ eps_out,
                                                            float* __restrict__ xin, const double* __restrict__ sg, int B, int N, int Cin, int C,
-                                                           double c1, double sqrt_alpha, double beta, int zero_row0, int rps, uint64_t seed, int rng_step, int cond) {
+                                                           double c1, double sqrt_alpha, double beta, int zero_row0, int rps, const unsigned long long* __restrict__ seeds, int rng_step, int cond) {
     int i = blockIdx.x * blockDim.x + threadIdx.x;
     if constexpr (CIN > 0) {  // compile-time width: all input loads are issued back to back; the shared tail does the rest
         // the head's weights through LDS (224 wave-uniform scalar loads in a row serialise on the scalar cache)
@@ -228,7 +235,7 @@ __global__ __launch_bounds__(256) void head_psample_kernel(const float* __restri
         tail_fetch(X, z, RNG, b, l, N, C, xv, zv);
         __syncthreads();
         if (mine)
-            head_psample_item<FINISH, RNG, (CIN > 0 ? CIN : 4)>(hv, xv, zv, i, b, l, sw, sw + 8 * CIN, X, eps_out, xin, sg, N, C, c1, sqrt_alpha, beta, zero_row0, rps, seed, rng_step, cond);
+            head_psample_item<FINISH, RNG, (CIN > 0 ? CIN : 4)>(hv, xv, zv, i, b, l, sw, sw + 8 * CIN, X, eps_out, xin, sg, N, C, c1, sqrt_alpha, beta, zero_row0, rps, seeds, rng_step, cond);
         return;
     }
     if (i >= B * N) return;
@@ -236,7 +243,11 @@ __global__ __launch_bounds__(256) void head_psample_kernel(const float* __restri
     const float* hp = h + (size_t)i * Cin;
     float xo[8] = {0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f};
     float zr[8] = {0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f};
-    if (RNG) rng_normal8(seed, (uint32_t)rng_step, (uint32_t)i, zr);
+    if (RNG) {
+        uint32_t elem;
+        const uint64_t seed = rng_scene(seeds, rps, b, i, N, &elem);
+        rng_normal8(seed, (uint32_t)rng_step, elem, zr);
+    }
     if (FINISH && rps) sg += 14 * (b / rps);
     // each thread's Cin inputs are read ONCE (float4) and reused by all C outputs; weights are wave-uniform (scalar loads)
     float acc[8];
@@ -308,8 +319,11 @@ __global__ void q_sample_kernel(const double* __restrict__ x, const double* __re
 //   X = sa * x0 + sb * eps (eps == nullptr: X = x0, a saved state), columns 0 / N-1 pinned to the run's start / goal pair when
 //   conditioning is on, and the first step's UNet input [B][N][8] f32 (channels >= C zero) as pack_state_kernel writes it.
 // x0 holds one plan per row (per_row) or one plan per group of rows: the whole batch (rps == 0), or the row's scene b / rps.
-__global__ void seed_state_kernel(const double* __restrict__ x0, int per_row, const double* __restrict__ eps, double sa, double sb,
-                                  double* __restrict__ X, float* __restrict__ xin, const double* __restrict__ sg, int B, int C, int N, int cond, int rps) {
+// RNG (edmp_sampler_seed_rng_dev, re-noising): eps = the step-0 draw of the row's device stream (tail.h: rng_scene) instead of eps[].
+template <bool RNG>
+__global__ void seed_state_kernel(const double* __restrict__ x0, int per_row, const double* __restrict__ eps, const unsigned long long* __restrict__ seeds,
+                                  double sa, double sb, double* __restrict__ X, float* __restrict__ xin, const double* __restrict__ sg, int B, int C, int N,
+                                  int cond, int rps) {
     int i = blockIdx.x * blockDim.x + threadIdx.x;
     if (i >= B * N) return;
     const int b = i / N, l = i - b * N;
@@ -317,12 +331,18 @@ __global__ void seed_state_kernel(const double* __restrict__ x0, int per_row, co
     const int src = per_row ? b : sc;
     sg += 14 * sc;
     float xo[8] = {0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f};
+    float zr[8] = {0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f};
+    if (RNG) {
+        uint32_t elem;
+        const uint64_t seed = rng_scene(seeds, rps, b, i, N, &elem);
+        rng_normal8(seed, 0u, elem, zr);
+    }
     for (int c = 0; c < C && c < 8; ++c) {
         const size_t idx = ((size_t)b * C + c) * N + l;
         double x = x0[((size_t)src * C + c) * N + l];
-        if (eps) {
+        if (RNG || eps) {
             double m;
-            x = q_noised(sa, x, sb, eps[idx], &m);
+            x = q_noised(sa, x, sb, RNG ? (double)zr[c] : eps[idx], &m);
         }
         if (cond && l == 0) x = sg[c];
         if (cond && l == N - 1) x = sg[7 + c];
@@ -377,13 +397,23 @@ static int set_startgoal_scenes(edmp_ctx* ctx, int S, const double* starts, cons
     return EDMP_OK;
 }
 
+// The device noise source's seeds of a run, one per scene (S = 1: the single scene's), into Sampler::seeds.  Called by a run's init
+// right before its start / goal upload, whose stream synchronisation covers this copy as well (`seeds` may live on the caller's stack).
+static int set_seeds(edmp_ctx* ctx, const uint64_t* seeds, int S) {
+    static_assert(sizeof(unsigned long long) == sizeof(uint64_t), "the seed table holds uint64 values");
+    EDMP_HIP_CHECK(hipMemcpyAsync(ctx->sampler->seeds, seeds, (size_t)S * sizeof(uint64_t), hipMemcpyHostToDevice, ctx->stream));
+    return EDMP_OK;
+}
+
+static const char* noise_source_name(int rng) { return rng ? "device noise source (Philox, the *_rng_* entry points)" : "explicit noise stream (noise_dev)"; }
+
 // One reverse step, first half.  `fused` (the device-resident loop): the UNet input of this step already sits in
 // unet->x_in (written by the previous step's tail kernel) and, on steps without guidance, the tail kernel also applies
 // the start/goal conditioning and writes the next input.  Otherwise (teacher-forced API): X comes from the caller, is
 // packed here, and conditioning is left to step_b so that the un-conditioned posterior can be returned.
 // rps: rows per scene of a scene batch (0 = one scene)
 static int step_a(edmp_ctx* ctx, double* X, const double* z, int B, int t, int zero_row0, int guided, float* eps_out, double* xpost_out,
-                  bool fused, bool use_rng = false, uint64_t seed = 0, int rps = 0) {
+                  bool fused, bool use_rng = false, int rps = 0) {
     Sampler* s = ctx->sampler;
     UNet* u = ctx->unet;
     const int C = u->desc.input_dim, N = u->desc.horizon;
@@ -413,7 +443,7 @@ static int step_a(edmp_ctx* ctx, double* X, const double* z, int B, int t, int z
         tail.beta = s->beta[t - 1];
         tail.zero_row0 = zr;
         tail.rps = rps;
-        tail.seed = seed;
+        tail.seeds = s->seeds;
         tail.rng_step = rstep;
         tail.cond = s->condition;
         tail.finish = g ? 0 : 1;
@@ -421,7 +451,7 @@ static int step_a(edmp_ctx* ctx, double* X, const double* z, int B, int t, int z
     }
     int rc = unet_run_program(ctx, B, t, want_tail ? &tail : nullptr, &tail_done);
     if (rc) return rc;
-#define EDMP_HP_ARGS(xin_ptr) hlast, u->head_w, u->head_b, X, z, eps_out, (xin_ptr), s->sg, B, N, u->head_cin, C, s->c1[t - 1], s->sqrt_alpha[t - 1], s->beta[t - 1], zr, rps, seed, rstep, s->condition
+#define EDMP_HP_ARGS(xin_ptr) hlast, u->head_w, u->head_b, X, z, eps_out, (xin_ptr), s->sg, B, N, u->head_cin, C, s->c1[t - 1], s->sqrt_alpha[t - 1], s->beta[t - 1], zr, rps, s->seeds, rstep, s->condition
 #define EDMP_HP_LAUNCH(FIN, RN, xin_ptr)                                                                                              \
     {                                                                                                                                  \
         if (u->head_cin == 32) hipLaunchKernelGGL((head_psample_kernel<FIN, RN, 32>), grid_bn, dim3(256), 0, st, EDMP_HP_ARGS(xin_ptr));      \
@@ -582,6 +612,8 @@ extern "C" int edmp_sampler_init(edmp_ctx* ctx, int T, double variance_thresh) {
     if (!ctx->sampler) {
         ctx->sampler = new Sampler();
         EDMP_HIP_CHECK(hipMalloc((void**)&ctx->sampler->sg, EDMP_MAX_SCENES * 14 * sizeof(double)));
+        EDMP_HIP_CHECK(hipMalloc((void**)&ctx->sampler->seeds, EDMP_MAX_SCENES * sizeof(unsigned long long)));
+        EDMP_HIP_CHECK(hipMemset(ctx->sampler->seeds, 0, EDMP_MAX_SCENES * sizeof(unsigned long long)));
     }
     Sampler* s = ctx->sampler;
     s->run_next = 0;  // new schedule tables: a segmented run in progress cannot be continued
@@ -690,7 +722,7 @@ extern "C" double* edmp_sumsq_ptr_dev(edmp_ctx* ctx) { return ctx ? guide_sumsq(
 // middle of a chunked run).  A continuation segment performs no host<->device synchronisation, so a caller can draw and
 // upload the next chunk of the NumPy noise stream while this one computes.
 // the stream work of one denoise_loop call: no host synchronisation, no allocation (capturable into a hipGraph)
-static int enqueue_loop(edmp_ctx* ctx, const double* noise_dev, bool use_rng, uint64_t seed, int B, int guided, int t_hi, int t_lo, bool init,
+static int enqueue_loop(edmp_ctx* ctx, const double* noise_dev, bool use_rng, int B, int guided, int t_hi, int t_lo, bool init,
                         int zero_row0, double* X_out_dev, int rps) {
     Sampler* s = ctx->sampler;
     const int C = ctx->unet->desc.input_dim, N = ctx->unet->desc.horizon;
@@ -700,8 +732,8 @@ static int enqueue_loop(edmp_ctx* ctx, const double* noise_dev, bool use_rng, ui
     if (init) {
         // X_T with start/goal conditioning                                              diffusion.py:303-307
         if (use_rng) {
-            hipLaunchKernelGGL(init_state_rng_kernel, dim3((B * N + 255) / 256), dim3(256), 0, st, seed, s->X, ctx->unet->x_in, s->sg, B, C, N,
-                               s->condition);
+            hipLaunchKernelGGL(init_state_rng_kernel, dim3((B * N + 255) / 256), dim3(256), 0, st, s->seeds, s->X, ctx->unet->x_in, s->sg, B, C, N,
+                               s->condition, rps);
         } else {
             EDMP_HIP_CHECK(hipMemcpyAsync(s->X, noise_dev, n * sizeof(double), hipMemcpyDeviceToDevice, st));
             if (s->condition) hipLaunchKernelGGL(condition_kernel, dim3((B * C + 255) / 256), dim3(256), 0, st, s->X, B, C, N, s->sg, rps);
@@ -711,7 +743,7 @@ static int enqueue_loop(edmp_ctx* ctx, const double* noise_dev, bool use_rng, ui
     }
     for (int t = t_hi; t > t_lo; --t) {
         const double* z = use_rng ? nullptr : noise_dev + (size_t)(t_hi - t) * n;
-        rc = step_a(ctx, s->X, z, B, t, zero_row0, guided, nullptr, nullptr, true, use_rng, seed, rps);
+        rc = step_a(ctx, s->X, z, B, t, zero_row0, guided, nullptr, nullptr, true, use_rng, rps);
         if (rc) return rc;
         if (s->ar_fn && guided && guided_step(t)) {
             // sharded logical batch: this rank's sum(g^2) -> the whole batch's, enqueued by the caller's collective on
@@ -753,13 +785,15 @@ static int check_run_state(edmp_ctx* ctx, int B, bool guided, int S) {
 // t_lo > 0 records the step the kept state stands at and the context's epoch, and a continuing segment (init == 0) must bring
 // exactly that t_hi under that epoch.  sampler_seed leaves the same record for a run that begins below T.  Every other loop call, a run that reached t_lo == 0, new start / goal pairs, a changed
 // conditioning switch and edmp_sampler_init end the run.  start / goal of a continuing segment are not read.
-static int denoise_loop(edmp_ctx* ctx, const double* noise_dev, bool use_rng, uint64_t seed, int B, const double* start, const double* goal,
+// use_rng: the device noise source under `seeds` (S values on the host, one per scene).  The run records its source with the rest
+// (Sampler::run_rng, the seeds in Sampler::seeds): a continuing segment must bring the same source and reads the recorded seeds, not `seeds`.
+static int denoise_loop(edmp_ctx* ctx, const double* noise_dev, bool use_rng, const uint64_t* seeds, int B, const double* start, const double* goal,
                         int guided, int t_hi, int t_lo, bool init, int zero_row0, double* X_out_dev, bool segment = false, int S = 1) {
     int rc = check_run_state(ctx, B, guided != 0, S);
     if (rc) return rc;
     const int rps = S > 1 ? B / S : 0;
-    EDMP_REQUIRE(S == 1 || !use_rng, "the device noise mode has no scene batch");
     EDMP_REQUIRE(noise_dev || use_rng, "null noise pointer");
+    EDMP_REQUIRE(!use_rng || !init || seeds, "null seeds");
     Sampler* s = ctx->sampler;
     const int T = s->T;
     EDMP_REQUIRE(t_hi >= 1 && t_hi <= T && t_lo >= 0 && t_lo < t_hi, "step range %d..%d outside 1..%d", t_hi, t_lo + 1, T);
@@ -773,15 +807,22 @@ static int denoise_loop(edmp_ctx* ctx, const double* noise_dev, bool use_rng, ui
         s->run_next = 0;
         rc = ensure_sampler_scratch(ctx, (int)n);
         if (rc) return rc;
+        if (use_rng && (rc = set_seeds(ctx, seeds, S))) return rc;
         rc = S > 1 ? set_startgoal_scenes(ctx, S, start, goal, guided != 0) : set_startgoal(ctx, start, goal, guided != 0);
         if (rc) return rc;
         s->run_B = B;
         s->run_rps = rps;
         s->run_guided = guided != 0;
+        s->run_rng = use_rng ? 1 : 0;
     } else {
         if (!(s->X && s->run_next > 0 && s->run_B == B && s->run_rps == rps)) {
             set_error("no run in progress for batch %d / %d scene(s): call with init first (a complete run, a run that reached step 0, new start / goal "
-                      "pairs and edmp_sampler_init end a segmented run)", B, S);
+                      "pairs and edmp_sampler_init end a segmented run); this segment brings the %s", B, S, noise_source_name(use_rng ? 1 : 0));
+            return EDMP_ERR_STATE;
+        }
+        if (s->run_rng != (use_rng ? 1 : 0)) {
+            set_error("the run in progress (step %d) draws from the %s, this segment brings the %s: a run keeps its noise source from its init to its end",
+                      s->run_next, noise_source_name(s->run_rng), noise_source_name(use_rng ? 1 : 0));
             return EDMP_ERR_STATE;
         }
         if (t_hi != s->run_next) {
@@ -809,7 +850,7 @@ static int denoise_loop(edmp_ctx* ctx, const double* noise_dev, bool use_rng, ui
             rc = guide_prepare(ctx, B, N - 2);
             if (rc) return rc;
         }
-        key.noise = noise_dev, key.hook = s->ar_fn ? s->ar_user : nullptr, key.seed = seed, key.use_rng = use_rng, key.B = B, key.guided = guided, key.t_hi = t_hi, key.t_lo = t_lo;
+        key.noise = noise_dev, key.hook = s->ar_fn ? s->ar_user : nullptr, key.seed = (use_rng && S == 1) ? seeds[0] : 0, key.use_rng = use_rng, key.B = B, key.guided = guided, key.t_hi = t_hi, key.t_lo = t_lo;
         key.init = init, key.zero_row0 = zero_row0, key.condition = s->condition, key.rps = rps, key.epoch = ctx->epoch;
         if (s->gexec && key == s->gkey) {
             s->graph_replays++;
@@ -823,8 +864,9 @@ static int denoise_loop(edmp_ctx* ctx, const double* noise_dev, bool use_rng, ui
         }
         EDMP_HIP_CHECK(hipStreamBeginCapture(st, hipStreamCaptureModeThreadLocal));
     }
-    // the copy-out stays outside the graph: callers hand a fresh output buffer to every call
-    rc = enqueue_loop(ctx, noise_dev, use_rng, seed, B, guided, t_hi, t_lo, init, zero_row0, graph ? nullptr : X_out_dev, rps);
+    // the copy-out stays outside the graph: callers hand a fresh output buffer to every call.  (The device source's seeds are no part of
+    // the capture either: the kernels read them from Sampler::seeds, which this call's init has uploaded ahead of the launch.)
+    rc = enqueue_loop(ctx, noise_dev, use_rng, B, guided, t_hi, t_lo, init, zero_row0, graph ? nullptr : X_out_dev, rps);
     if (graph) {
         hipGraph_t g = nullptr;
         hipError_t e = hipStreamEndCapture(st, &g);
@@ -853,19 +895,29 @@ extern "C" int edmp_denoise_guided_dev(edmp_ctx* ctx, const double* noise_dev, i
                                        int t_stop, int zero_row0, double* X_out_dev) {
     EDMP_REQUIRE(noise_dev && X_out_dev, "edmp_denoise_guided_dev: null pointer (use edmp_denoise_guided_rng_dev for the device noise source)");
     EDMP_REQUIRE(ctx && ctx->sampler, "sampler not initialised");
-    return denoise_loop(ctx, noise_dev, false, 0, B, start, goal, guided, ctx->sampler->T, t_stop, true, zero_row0, X_out_dev);
+    return denoise_loop(ctx, noise_dev, false, nullptr, B, start, goal, guided, ctx->sampler->T, t_stop, true, zero_row0, X_out_dev);
 }
 
 extern "C" int edmp_denoise_guided_rng_dev(edmp_ctx* ctx, uint64_t seed, int B, const double* start, const double* goal, int guided, int t_stop,
                                            int zero_row0, double* X_out_dev) {
     EDMP_REQUIRE(ctx && ctx->sampler && X_out_dev, "sampler not initialised / null output");
-    return denoise_loop(ctx, nullptr, true, seed, B, start, goal, guided, ctx->sampler->T, t_stop, true, zero_row0, X_out_dev);
+    return denoise_loop(ctx, nullptr, true, &seed, B, start, goal, guided, ctx->sampler->T, t_stop, true, zero_row0, X_out_dev);
+}
+
+// the all-reduce hook sums a sharded logical batch, whose rows' element indices the device source does not know (they are this rank's)
+#define EDMP_NO_HOOK_WITH_RNG(what) EDMP_REQUIRE(!ctx->sampler->ar_fn, what ": the device noise source does not run with an all-reduce hook installed")
+
+extern "C" int edmp_denoise_guided_rng_segment_dev(edmp_ctx* ctx, uint64_t seed, int B, const double* start, const double* goal, int guided,
+                                                   int t_hi, int t_lo, int init, int zero_row0, double* X_out_dev) {
+    EDMP_REQUIRE(ctx && ctx->sampler, "edmp_denoise_guided_rng_segment_dev: sampler not initialised");
+    EDMP_NO_HOOK_WITH_RNG("edmp_denoise_guided_rng_segment_dev");
+    return denoise_loop(ctx, nullptr, true, &seed, B, start, goal, guided, t_hi, t_lo, init != 0, zero_row0, X_out_dev, true);
 }
 
 extern "C" int edmp_denoise_guided_segment_dev(edmp_ctx* ctx, const double* noise_dev, int B, const double* start, const double* goal, int guided,
                                                int t_hi, int t_lo, int init, int zero_row0, double* X_out_dev) {
     EDMP_REQUIRE(ctx && ctx->sampler && noise_dev, "edmp_denoise_guided_segment_dev: bad arguments");
-    return denoise_loop(ctx, noise_dev, false, 0, B, start, goal, guided, t_hi, t_lo, init != 0, zero_row0, X_out_dev, true);
+    return denoise_loop(ctx, noise_dev, false, nullptr, B, start, goal, guided, t_hi, t_lo, init != 0, zero_row0, X_out_dev, true);
 }
 
 // a scene batch: S scenes x B rows as one (S*B, C, N) run; starts / goals may be NULL only when neither conditioning nor guided
@@ -887,7 +939,25 @@ extern "C" int edmp_denoise_scenes_dev(edmp_ctx* ctx, const double* noise_dev, i
     EDMP_REQUIRE(noise_dev && X_out_dev, "edmp_denoise_scenes_dev: null pointer");
     static const double zeros[EDMP_MAX_SCENES * 7] = {};
     if (int rc = scenes_args(ctx, S, B, starts, goals, guided, zeros)) return rc;
-    return denoise_loop(ctx, noise_dev, false, 0, S * B, starts, goals, guided, ctx->sampler->T, t_stop, true, zero_row0, X_out_dev, false, S);
+    return denoise_loop(ctx, noise_dev, false, nullptr, S * B, starts, goals, guided, ctx->sampler->T, t_stop, true, zero_row0, X_out_dev, false, S);
+}
+
+extern "C" int edmp_denoise_scenes_rng_dev(edmp_ctx* ctx, const uint64_t* seeds, int S, int B, const double* starts, const double* goals, int guided,
+                                           int t_stop, int zero_row0, double* X_out_dev) {
+    EDMP_REQUIRE(seeds && X_out_dev, "edmp_denoise_scenes_rng_dev: null pointer");
+    static const double zeros[EDMP_MAX_SCENES * 7] = {};
+    if (int rc = scenes_args(ctx, S, B, starts, goals, guided, zeros)) return rc;
+    EDMP_NO_HOOK_WITH_RNG("edmp_denoise_scenes_rng_dev");
+    return denoise_loop(ctx, nullptr, true, seeds, S * B, starts, goals, guided, ctx->sampler->T, t_stop, true, zero_row0, X_out_dev, false, S);
+}
+
+extern "C" int edmp_denoise_scenes_rng_segment_dev(edmp_ctx* ctx, const uint64_t* seeds, int S, int B, const double* starts, const double* goals, int guided,
+                                                   int t_hi, int t_lo, int init, int zero_row0, double* X_out_dev) {
+    EDMP_REQUIRE(seeds || !init, "edmp_denoise_scenes_rng_segment_dev: null seeds");
+    static const double zeros[EDMP_MAX_SCENES * 7] = {};
+    if (int rc = scenes_args(ctx, S, B, starts, goals, guided, zeros)) return rc;
+    EDMP_NO_HOOK_WITH_RNG("edmp_denoise_scenes_rng_segment_dev");
+    return denoise_loop(ctx, nullptr, true, seeds, S * B, starts, goals, guided, t_hi, t_lo, init != 0, zero_row0, X_out_dev, true, S);
 }
 
 extern "C" int edmp_denoise_scenes_segment_dev(edmp_ctx* ctx, const double* noise_dev, int S, int B, const double* starts, const double* goals, int guided,
@@ -895,13 +965,15 @@ extern "C" int edmp_denoise_scenes_segment_dev(edmp_ctx* ctx, const double* nois
     EDMP_REQUIRE(noise_dev, "edmp_denoise_scenes_segment_dev: null noise pointer");
     static const double zeros[EDMP_MAX_SCENES * 7] = {};
     if (int rc = scenes_args(ctx, S, B, starts, goals, guided, zeros)) return rc;
-    return denoise_loop(ctx, noise_dev, false, 0, S * B, starts, goals, guided, t_hi, t_lo, init != 0, zero_row0, X_out_dev, true, S);
+    return denoise_loop(ctx, noise_dev, false, nullptr, S * B, starts, goals, guided, t_hi, t_lo, init != 0, zero_row0, X_out_dev, true, S);
 }
 
 // The init of a segmented run that begins at t_start <= T from the caller's plan: the checks, the start / goal upload and the run
 // record of an init segment, with seed_state_kernel in the place of the X_T copy.  B = all rows (S * rows per scene).
+// seeds != nullptr: the run draws from the device source under these S seeds; with `renoise` its eps is the streams' step-0 draw (eps_dev is
+// null then), without it nothing is drawn here.  Either way the run record names that source, and the *_rng_* segments continue it.
 static int sampler_seed(edmp_ctx* ctx, const double* x0_dev, int x0_rows, const double* eps_dev, int B, const double* start, const double* goal,
-                        int guided, int t_start, double* X_out_dev, int S) {
+                        int guided, int t_start, double* X_out_dev, int S, const uint64_t* seeds = nullptr, bool renoise = false) {
     int rc = check_run_state(ctx, B, guided != 0, S);
     if (rc) return rc;
     Sampler* s = ctx->sampler;
@@ -916,16 +988,22 @@ static int sampler_seed(edmp_ctx* ctx, const double* x0_dev, int x0_rows, const 
     s->run_next = 0;
     rc = ensure_sampler_scratch(ctx, (int)n);
     if (rc) return rc;
+    if (seeds && (rc = set_seeds(ctx, seeds, S))) return rc;
     rc = S > 1 ? set_startgoal_scenes(ctx, S, start, goal, guided != 0) : set_startgoal(ctx, start, goal, guided != 0);
     if (rc) return rc;
     const double ab = s->alpha_bar[t_start - 1];
-    hipLaunchKernelGGL(seed_state_kernel, dim3((B * N + 255) / 256), dim3(256), 0, ctx->stream, x0_dev, x0_rows == B ? 1 : 0, eps_dev, sqrt(ab), sqrt(1.0 - ab),
-                       s->X, ctx->unet->x_in, s->sg, B, C, N, s->condition, rps);
+    if (seeds && renoise)
+        hipLaunchKernelGGL(seed_state_kernel<true>, dim3((B * N + 255) / 256), dim3(256), 0, ctx->stream, x0_dev, x0_rows == B ? 1 : 0, (const double*)nullptr, s->seeds,
+                           sqrt(ab), sqrt(1.0 - ab), s->X, ctx->unet->x_in, s->sg, B, C, N, s->condition, rps);
+    else
+        hipLaunchKernelGGL(seed_state_kernel<false>, dim3((B * N + 255) / 256), dim3(256), 0, ctx->stream, x0_dev, x0_rows == B ? 1 : 0, eps_dev, s->seeds,
+                           sqrt(ab), sqrt(1.0 - ab), s->X, ctx->unet->x_in, s->sg, B, C, N, s->condition, rps);
     EDMP_HIP_CHECK(hipGetLastError());
     if (X_out_dev) EDMP_HIP_CHECK(hipMemcpyAsync(X_out_dev, s->X, n * sizeof(double), hipMemcpyDeviceToDevice, ctx->stream));
     s->run_B = B;
     s->run_rps = rps;
     s->run_guided = guided != 0;
+    s->run_rng = seeds ? 1 : 0;
     s->run_next = t_start;
     s->run_epoch = ctx->epoch;
     return EDMP_OK;
@@ -942,6 +1020,22 @@ extern "C" int edmp_sampler_seed_scenes_dev(edmp_ctx* ctx, const double* x0_dev,
     static const double zeros[EDMP_MAX_SCENES * 7] = {};
     if (int rc = scenes_args(ctx, S, B, starts, goals, guided, zeros)) return rc;
     return sampler_seed(ctx, x0_dev, x0_rows, eps_dev, S * B, starts, goals, guided, t_start, X_out_dev, S);
+}
+
+extern "C" int edmp_sampler_seed_rng_dev(edmp_ctx* ctx, const double* x0_dev, int x0_rows, uint64_t seed, int renoise, int B, const double* start,
+                                         const double* goal, int guided, int t_start, double* X_out_dev) {
+    EDMP_REQUIRE(ctx && ctx->sampler, "edmp_sampler_seed_rng_dev: sampler not initialised");
+    EDMP_NO_HOOK_WITH_RNG("edmp_sampler_seed_rng_dev");
+    return sampler_seed(ctx, x0_dev, x0_rows, nullptr, B, start, goal, guided, t_start, X_out_dev, 1, &seed, renoise != 0);
+}
+
+extern "C" int edmp_sampler_seed_scenes_rng_dev(edmp_ctx* ctx, const double* x0_dev, int x0_rows, const uint64_t* seeds, int renoise, int S, int B,
+                                                const double* starts, const double* goals, int guided, int t_start, double* X_out_dev) {
+    EDMP_REQUIRE(seeds, "edmp_sampler_seed_scenes_rng_dev: null seeds");
+    static const double zeros[EDMP_MAX_SCENES * 7] = {};
+    if (int rc = scenes_args(ctx, S, B, starts, goals, guided, zeros)) return rc;
+    EDMP_NO_HOOK_WITH_RNG("edmp_sampler_seed_scenes_rng_dev");
+    return sampler_seed(ctx, x0_dev, x0_rows, nullptr, S * B, starts, goals, guided, t_start, X_out_dev, S, seeds, renoise != 0);
 }
 
 extern "C" int edmp_sampler_set_allreduce(edmp_ctx* ctx, edmp_allreduce_fn fn, void* user) {

@@ -12,6 +12,8 @@ namespace edmp {
 // Philox4x32-10 counter RNG (Salmon et al. 2011): counter = (element, step, block, 0), key = seed.  Eight standard
 // normals per (sample, waypoint) and step via Box-Muller, one per joint channel.  Removes the 0.9 s host draw and the
 // 734 MB upload per scene that the NumPy-stream contract costs.
+// element = the (row, waypoint) index inside the row's OWN scene and key = that scene's seed (rng_scene below), so a scene of a
+// scene batch draws what its serial run draws; step 0 = X_T of a full run or the eps of a re-noising warm start, 1 + T - t = step t.
 __device__ __forceinline__ void philox4x32_10(uint32_t c0, uint32_t c1, uint32_t c2, uint32_t c3, uint32_t k0, uint32_t k1, uint32_t (&out)[4]) {
 #pragma unroll
     for (int r = 0; r < 10; ++r) {
@@ -53,6 +55,15 @@ __device__ __forceinline__ void rng_normal8(uint64_t seed, uint32_t step, uint32
     }
 }
 
+// Row b's stream in a run of rps rows per scene (0 = one scene): its scene's seed out of the run's seed table (Sampler::seeds, one
+// entry per scene) and the scene-local element index of (b, l).  i = b * N + l.  A per-lane load: rps * N need not be a multiple
+// of 64, so a wave is not scene-uniform in general.
+__device__ __forceinline__ uint64_t rng_scene(const unsigned long long* __restrict__ seeds, int rps, int b, int i, int N, uint32_t* elem) {
+    const int sc = rps ? b / rps : 0;
+    *elem = (uint32_t)(i - sc * rps * N);
+    return seeds[sc];
+}
+
 // what the tail of reverse step t needs (sampler.hip: step_a fills it; level.hip consumes it)
 struct TailP {
     int on = 0;            // 0: the level kernel writes its activations to HBM and a separate launch does the tail
@@ -66,7 +77,7 @@ struct TailP {
     double c1 = 0.0, sqrt_alpha = 1.0, beta = 0.0;
     int zero_row0 = 0;
     int rps = 0;           // scene batch: rows per scene (row b is row b % rps of scene b / rps); 0 = one scene
-    unsigned long long seed = 0;
+    const unsigned long long* seeds = nullptr;  // device noise: one seed per scene (Sampler::seeds), read when rng != 0
     int rng_step = 0;
     int cond = 0;
     int finish = 0;  // steps without guidance: condition X and write the next UNet input
@@ -97,10 +108,14 @@ template <bool FINISH, bool RNG, int CIN>
 __device__ __forceinline__ void head_psample_item(const float4 (&hv)[CIN / 4], const double (&xv)[8], const double (&zv)[8], int i, int b, int l,
                                                   const float* __restrict__ w, const float* __restrict__ bias, double* __restrict__ X,
                                                   float* __restrict__ eps_out, float* __restrict__ xin, const double* __restrict__ sg, int N, int C, double c1,
-                                                  double sqrt_alpha, double beta, int zero_row0, int rps, uint64_t seed, int rng_step, int cond) {
+                                                  double sqrt_alpha, double beta, int zero_row0, int rps, const unsigned long long* __restrict__ seeds, int rng_step, int cond) {
     float xo[8] = {0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f};
     float zr[8] = {0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f};
-    if (RNG) rng_normal8(seed, (uint32_t)rng_step, (uint32_t)i, zr);
+    if (RNG) {
+        uint32_t elem;
+        const uint64_t seed = rng_scene(seeds, rps, b, i, N, &elem);
+        rng_normal8(seed, (uint32_t)rng_step, elem, zr);
+    }
     if (FINISH && rps) sg += 14 * (b / rps);
     float acc[8];
 #pragma unroll

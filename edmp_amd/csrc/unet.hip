@@ -1622,6 +1622,7 @@ int unet_run_program(edmp_ctx* ctx, int B, int t, const TailP* tail, bool* tail_
             const Op& nx = u->prog[op_index + 1];
             LevelP pa = op.lv, pb = nx.lv;
             pa.B = pb.B = B;
+            pa.tail.rps = pb.tail.rps = tail ? tail->rps : 0;  // a scene batch: the workgroups are dealt scene by scene (level.hip)
             const bool out_is_head_input = pb.out == u->h_last;
             pa.out = nullptr, pb.src1 = nullptr;  // (level B's first input half arrives in LDS)
             pa.tb1 = trow + op.lv_tb1, pa.tb2 = trow + op.lv_tb2;
@@ -1632,6 +1633,7 @@ int unet_run_program(edmp_ctx* ctx, int B, int t, const TailP* tail, bool* tail_
         } else if (op.kind == OP_LVL) {
             LevelP p = op.lv;
             p.B = B;
+            p.tail.rps = tail ? tail->rps : 0;
             const bool out_is_head_input = p.out == u->h_last;
             p.tb1 = trow + op.lv_tb1;
             p.tb2 = trow + op.lv_tb2;

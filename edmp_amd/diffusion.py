@@ -115,6 +115,49 @@ class WarmStart:
         return 1 if self.renoise else 0
 
 
+class DeviceNoise:
+    """The device noise source (Philox4x32-10 + Box-Muller inside the step tail, csrc/tail.h) as a ``noise=`` value, for every run form:
+    ``DeviceNoise(seed)`` - one scene (Diffusion.denoise_guided / denoise) - or ``DeviceNoise(seeds=[...])`` - one seed per scene of a
+    scene batch (Diffusion.denoise_guided_scenes).  Seeds are integers in [0, 2^64); equal seeds are allowed.  Row b, waypoint l of a
+    scene draws Philox counter (b N + l, step, block, 0) under the scene's seed as key - the index is the scene's own, so a scene's numbers
+    do not depend on its neighbours in a batch; step 0 = X_T of a full run or the eps of a re-noising warm start, 1 + T - t = reverse step
+    t.  A full single-scene run is exactly ``noise="device", seed=seed``.  Nothing is drawn, page-locked or uploaded on the host."""
+
+    def __init__(self, seed=None, *, seeds=None):
+        if (seed is None) == (seeds is None):
+            raise ValueError("DeviceNoise takes one seed, or seeds=[one per scene]")
+        self.single = seeds is None
+        vals = []
+        for v in ([seed] if self.single else list(seeds)):
+            if isinstance(v, bool):
+                raise TypeError("a seed must be an integer, got a bool")
+            try:
+                v = operator.index(v)
+            except TypeError:
+                raise TypeError(f"a seed must be an integer, got {type(v).__name__}") from None
+            if not 0 <= v < 2**64:
+                raise ValueError(f"a seed must lie in [0, 2^64), got {v}")
+            vals.append(v)
+        if not vals:
+            raise ValueError("DeviceNoise(seeds=...) needs at least one seed")
+        self.seeds = tuple(vals)
+
+    def _for_run(self, n_scenes, allreduce=None):
+        """the seeds for a run of `n_scenes` scenes (None = a single-scene call), before anything is bound or enqueued"""
+        if allreduce is not None:
+            raise ValueError("the device noise source does not combine with a sharded run (allreduce=...): its element index is the row's "
+                             "index on this rank")
+        if n_scenes is None:
+            if not self.single:
+                raise ValueError("a single-scene run takes DeviceNoise(seed), not DeviceNoise(seeds=[...])")
+            return self.seeds[0]
+        if self.single:
+            raise ValueError(f"a scene batch takes DeviceNoise(seeds=[...]) with one seed per scene ({n_scenes}), not a single seed")
+        if len(self.seeds) != n_scenes:
+            raise ValueError(f"DeviceNoise holds {len(self.seeds)} seeds, the scene batch has {n_scenes} scenes")
+        return (C.c_uint64 * n_scenes)(*self.seeds)
+
+
 def guided_step(t) -> bool:
     """the reverse steps that add the guide's gradient: every second one, down to t = 5 (diffusion.py:311, 326-327; the device loop's
     own copy of the rule is guided_step in csrc/sampler.hip)"""
@@ -452,7 +495,8 @@ class Diffusion:
                        chunk_steps=DEFAULT_CHUNK_STEPS, allreduce=None, warm_start=None):
         """diffusion.py:300-356.  ``noise``: optional pre-drawn (T+1,B,C,N) f64 ndarray / device tensor (default:
         drawn from the global NumPy RNG in the reference's order); ``noise="device"`` draws z on the GPU (Philox,
-        ``seed``) — a non-parity mode without the host draw / upload.  ``allreduce``: this call is one row shard
+        ``seed``) — a non-parity mode without the host draw / upload; a ``DeviceNoise(seed)`` is that source for every run form,
+        ``warm_start`` included (the string keeps its refusals).  ``allreduce``: this call is one row shard
         of a batch spread over several GPUs; an ``edmp_amd.dist.RcclAllReduce`` (native ncclAllReduce inside the device loop) or a
         callable that sums the f64 device scalar over ranks in place (edmp_amd.dist.allreduce_sum_; a Python callback per guided step).
         ``warm_start``: a WarmStart(x0, t_start, renoise) - the run covers steps t_start .. t_stop + 1 only, from x0 forward-noised to
@@ -461,6 +505,7 @@ class Diffusion:
         Returns (B,C,N) f64 ndarray (a fresh copy)."""
         ctx = self.ctx
         ws = warm_start
+        dev_seed = noise._for_run(None, allreduce) if isinstance(noise, DeviceNoise) else None
         if ws is not None:
             cn = (int(num_channels), int(traj_len))
             x0_rows = self._check_warm(ws, t_stop, noise, allreduce, {cn: 1, (int(batch_size),) + cn: int(batch_size)})
@@ -502,6 +547,16 @@ class Diffusion:
         if stream is not None:
             noise = stream.tensor
         with self._sharded(allreduce) if allreduce is not None else contextlib.nullcontext():
+            if dev_seed is not None:  # the device source in every run form: no chunk plan, no pinned ring, no draw thread
+                if ws is None:
+                    _capi.check(ctx.lib.edmp_denoise_guided_rng_dev(ctx.h, dev_seed, batch_size, sp, gp, guided, int(t_stop), zr, ptr(out)), "edmp_denoise_guided_rng_dev")
+                    return self._finish(out, return_device)
+                # a warm run: the seed call (eps = the stream's step-0 draw when re-noising) plus one segment
+                _capi.check(ctx.lib.edmp_sampler_seed_rng_dev(ctx.h, ptr(x0d), x0_rows, dev_seed, 1 if ws.renoise else 0, batch_size, sp, gp, guided, ws.t_start, None),
+                            "edmp_sampler_seed_rng_dev")
+                _capi.check(ctx.lib.edmp_denoise_guided_rng_segment_dev(ctx.h, dev_seed, batch_size, sp, gp, guided, ws.t_start, int(t_stop), 0, zr, ptr(out)),
+                            "edmp_denoise_guided_rng_segment_dev")
+                return self._finish(out, return_device, sync=True)
             if isinstance(noise, str):
                 if noise != "device":
                     raise ValueError("noise must be an array, a device tensor, None (NumPy stream) or 'device'")
@@ -539,6 +594,7 @@ class Diffusion:
             raise ValueError("batch must be a guide.SceneBatch")
         S, B = batch.n_scenes, batch.batch_size
         ws = warm_start
+        dev_seeds = noise._for_run(S) if isinstance(noise, DeviceNoise) else None
         if ws is not None:
             cn = (int(num_channels), int(traj_len))
             x0_rows = self._check_warm(ws, t_stop, noise, None, {(S,) + cn: S, (S, B) + cn: S * B})
@@ -555,6 +611,27 @@ class Diffusion:
         s_arr, g_arr = _pairs(S, starts, goals)
         if isinstance(noise, str):
             raise _capi.EdmpError("the device noise mode (noise='device') has no scene batch: pass NumPy-stream noise")
+        if dev_seeds is not None:  # the device source, one seed per scene: nothing is drawn, page-locked or uploaded on the host
+            Cc, N = int(num_channels), int(traj_len)
+            ctx.ensure_sampler(self.T, self.variance_thresh)
+            model._bind()
+            if guided:
+                batch._bind()
+            _capi.check(ctx.lib.edmp_sampler_set_condition(ctx.h, 1 if condition else 0))
+            out = ctx.empty((S * B, Cc, N), torch.float64)
+            sp, gp, gflag, zr = _capi.as_pd(s_arr), _capi.as_pd(g_arr), 1 if guided else 0, 1 if zero_row0 else 0
+            if ws is None:
+                _capi.check(ctx.lib.edmp_denoise_scenes_rng_dev(ctx.h, dev_seeds, S, B, sp, gp, gflag, int(t_stop), zr, ptr(out)), "edmp_denoise_scenes_rng_dev")
+            else:  # a warm run: the seed call plus one segment
+                x0d = ctx.to_dev(ws.x0, torch.float64)
+                try:
+                    _capi.check(ctx.lib.edmp_sampler_seed_scenes_rng_dev(ctx.h, ptr(x0d), x0_rows, dev_seeds, 1 if ws.renoise else 0, S, B, sp, gp, gflag, ws.t_start, None),
+                                "edmp_sampler_seed_scenes_rng_dev")
+                    _capi.check(ctx.lib.edmp_denoise_scenes_rng_segment_dev(ctx.h, dev_seeds, S, B, sp, gp, gflag, ws.t_start, int(t_stop), 0, zr, ptr(out)),
+                                "edmp_denoise_scenes_rng_segment_dev")
+                finally:
+                    ctx.sync()  # x0d dies with this frame
+            return self._finish(out, return_device, sync=True).reshape(S, B, Cc, N)
         if noise is not None and (not isinstance(noise, (list, tuple)) or len(noise) != S):
             raise ValueError(f"noise must be None or a list of {S} per-scene streams")
         Cc, N, T = int(num_channels), int(traj_len), self.T

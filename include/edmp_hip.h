@@ -489,6 +489,44 @@ int edmp_denoise_guided_rng_dev(edmp_ctx* ctx, uint64_t seed, int B, const doubl
                                 int t_stop, int zero_row0, double* X_out_dev);
 int edmp_rng_normal_dev(edmp_ctx* ctx, uint64_t seed, int step_index, int B, int C, int N, double* out_dev);
 
+/* The device noise source in the other run forms: segments, scene batches, warm starts.
+ *
+ * The stream contract.  Philox counter = (element, step, block, 0), key = seed (what edmp_denoise_guided_rng_dev and
+ * edmp_rng_normal_dev have always drawn), with
+ *   element = the (row, waypoint) index inside the row's OWN scene: (b - s * B) * N + l for row b of scene s = b / B of a scene batch,
+ *             b * N + l for a single scene;
+ *   key     = the seed of the row's scene: a scene batch takes S seeds on the host, one per scene, any uint64 values, equal ones allowed;
+ *   step    = 0 for the X_T draw of a full run - and for the eps draw of a re-noising warm start, which draws no X_T -,
+ *             1 + T - t for reverse step t.  The step is absolute, so a segment carries no stream state.
+ * Hence, bit for bit: scene s of a scene batch is the single-scene run of that scene under seeds[s], whatever its neighbours, their
+ * seeds and its position; every run equals the explicit-noise run fed the streams edmp_rng_normal_dev(seeds[s], step, B, ...)
+ * materialises; a segmented run equals the unsegmented one.
+ *
+ * edmp_denoise_guided_rng_segment_dev / edmp_denoise_scenes_rng_segment_dev are edmp_denoise_guided_segment_dev /
+ * edmp_denoise_scenes_segment_dev with the seed(s) in the place of noise_dev; edmp_denoise_scenes_rng_dev is edmp_denoise_scenes_dev
+ * likewise.  edmp_sampler_seed_rng_dev / edmp_sampler_seed_scenes_rng_dev are the seed calls with the seed(s) and `renoise` in the place
+ * of eps_dev: renoise != 0 forward-noises x0 with eps = the step-0 draw of every row's stream (products and sum rounded separately, as
+ * with eps_dev), renoise == 0 draws nothing and takes x0 as the state at t_start.
+ *
+ * A run records its noise source with the rest of its record: an init (init != 0, a whole run, a seed call) stores the source and,
+ * for the device source, the seeds in the context.  A continuing segment (init == 0) of a device-noise run reads the RECORDED seeds -
+ * its own seed argument is not read, like its start / goal pair (seeds may be NULL there) - and a continuing segment that brings
+ * the other source is refused with EDMP_ERR_STATE, the message naming both; a refused call changes nothing.  Segments are enqueued
+ * eagerly; edmp_denoise_scenes_rng_dev replays a hipGraph under edmp_sampler_set_graph like the other whole-run calls, and a replay
+ * draws under THIS call's seeds: the kernels read them from the context's seed table, uploaded before the launch.  With an
+ * all-reduce hook installed these five calls are refused with EDMP_ERR_ARG (a row shard's element indices are not the logical
+ * batch's). */
+int edmp_denoise_guided_rng_segment_dev(edmp_ctx* ctx, uint64_t seed, int B, const double* start, const double* goal, int guided,
+                                        int t_hi, int t_lo, int init, int zero_row0, double* X_out_dev);
+int edmp_denoise_scenes_rng_dev(edmp_ctx* ctx, const uint64_t* seeds, int S, int B, const double* starts, const double* goals, int guided,
+                                int t_stop, int zero_row0, double* X_out_dev);
+int edmp_denoise_scenes_rng_segment_dev(edmp_ctx* ctx, const uint64_t* seeds, int S, int B, const double* starts, const double* goals, int guided,
+                                        int t_hi, int t_lo, int init, int zero_row0, double* X_out_dev);
+int edmp_sampler_seed_rng_dev(edmp_ctx* ctx, const double* x0_dev, int x0_rows, uint64_t seed, int renoise, int B, const double* start,
+                              const double* goal, int guided, int t_start, double* X_out_dev);
+int edmp_sampler_seed_scenes_rng_dev(edmp_ctx* ctx, const double* x0_dev, int x0_rows, const uint64_t* seeds, int renoise, int S, int B,
+                                     const double* starts, const double* goals, int guided, int t_start, double* X_out_dev);
+
 /* Replay mode of the device-resident loop: on = 1 captures the stream work of one edmp_denoise_guided*_dev call
  * (255 reverse steps, ~16k kernel nodes) into a hipGraph the first time and replays it while the call's arguments,
  * scene, rows and weights stay the same (start/goal are read from a device buffer and may change freely).  Results are

@@ -20,7 +20,7 @@ from edmp_amd import dist as ED
 from edmp_amd import evaluation as EV
 from edmp_amd import franka
 from edmp_amd import guide_cfg as GC
-from edmp_amd.diffusion import DEFAULT_CHUNK_STEPS, Diffusion, PinnedNoiseStream, chunk_plan
+from edmp_amd.diffusion import DEFAULT_CHUNK_STEPS, DeviceNoise, Diffusion, PinnedNoiseStream, chunk_plan
 from edmp_amd.guide import IntersectionVolumeGuide, SceneBatch, pick_goal
 from edmp_amd.scenes import SyntheticDataset
 from edmp_amd.temporalunet import TemporalUNet
@@ -44,6 +44,12 @@ def _ranks(device):
     if not dist.is_initialized():
         dist.init_process_group(backend, **({"device_id": torch.device("cuda", index)} if backend == "nccl" else {}))
     return dist.get_rank(), dist.get_world_size(), f"cuda:{index}"
+
+
+def scene_seed(seed, i):
+    """the device noise seed of scene i of the cfg's order (i counts over all ranks) under ``--device-noise SEED``: a scene's stream is a
+    function of (SEED, i) alone - not of the grouping, the lanes, the ranks or the scenes planned before it"""
+    return (int(seed) + int(i) * 0x9E3779B97F4A7C15) % 2**64
 
 
 class _NoiseFeeder:
@@ -134,7 +140,7 @@ def job_summary(results, world=1, self_collision=False):
 
 
 def run(cfg_path, dataset=None, max_scenes=None, verbose=True, scenes_in_flight=1, shard_scenes=True, scenes_per_launch=1, ensemble_report=False, prefer=None,
-        ik_seeds=0, ik_tool=None, ik_seed=0, self_collision=False):
+        ik_seeds=0, ik_tool=None, ik_seed=0, self_collision=False, device_noise=None):
     """The reference's scene loop (infer_serial.py:95-170).  Under ``torch.distributed.run`` (one process per GPU, extension: the
     reference is one process) the scenes are dealt round-robin to the ranks - scene i of the cfg's order goes to rank i mod world -
     and nothing is exchanged until `job_summary` adds the tallies up: scenes are independent problems, this is the problem set's natural
@@ -177,6 +183,12 @@ def run(cfg_path, dataset=None, max_scenes=None, verbose=True, scenes_in_flight=
     flag, tallied like success), `rows_self_collision_free`, `first_self_collision_waypoint` and `self_collision_pair` (the chosen plan's
     first colliding pair as two franka.LINK_NAMES, None when free); with ensemble_report the chosen plan's flag and pair are printed.
 
+    ``device_noise`` = SEED (an extension; None: the NumPy stream, as above) draws every scene's noise on the GPU (diffusion.DeviceNoise:
+    Philox inside the step tail, explicitly no parity with the reference's stream): scene i of the cfg's order - i counts over all ranks -
+    runs under ``scene_seed(SEED, i)``, recorded as `noise_seed` in its result, so its plan is the same whatever scenes_per_launch,
+    scenes_in_flight, the number of ranks and the scenes planned before it.  No feeder thread is started, no page-locked scene buffer is
+    allocated and the global RandomState is neither read nor advanced.
+
     A run config with a goal-weighted SDF guide (``hyperparameters.sdf.goal_weight``, sample guide 103) hands every guide its target: the
     problem's own target pose (``dataset.target_pose``, given in the frame ``ik_tool``) when it carries one, else the pose of the picked
     goal configuration; with ensemble_report the chosen plan's ``position_error`` [cm] and ``orientation_error`` [deg] of the final tool
@@ -191,6 +203,8 @@ def run(cfg_path, dataset=None, max_scenes=None, verbose=True, scenes_in_flight=
         raise ValueError(f"scenes_per_launch must be >= 1, got {scenes_per_launch}")
     if kl > 1 and int(scenes_in_flight) > 1:
         raise ValueError("scenes_per_launch > 1 and scenes_in_flight > 1 do not combine: choose one")
+    if device_noise is not None:
+        DeviceNoise(device_noise)  # (an integer in [0, 2^64), or it raises)
     benchmark_cfg = GC.load_yaml(cfg_path)
     rank, world, device = _ranks(benchmark_cfg["model"]["device"]) if shard_scenes else (0, 1, benchmark_cfg["model"]["device"])
     traj_len = benchmark_cfg["model"]["traj_len"]
@@ -286,7 +300,7 @@ def run(cfg_path, dataset=None, max_scenes=None, verbose=True, scenes_in_flight=
         diffuser, denoiser = lanes[lane]
         tm = dict(meta.pop("timings"))
         pinned = None
-        if noise is not None:  # this scene's stream, drawn ahead by the feeder into page-locked memory: uploaded in chunks beside the loop
+        if noise is not None and not isinstance(noise, DeviceNoise):  # this scene's stream, drawn ahead by the feeder into page-locked memory: uploaded in chunks beside the loop
             t_w = time.time()
             pinned = noise.result() if hasattr(noise, "result") else noise
             tm["noise_wait_s"] = time.time() - t_w
@@ -364,7 +378,13 @@ def run(cfg_path, dataset=None, max_scenes=None, verbose=True, scenes_in_flight=
             i += 1
     # the noise of EVERY scene comes from the feeder thread, one whole scene ahead (round 6: the serial loop too - drawing chunk by chunk
     # beside the GPU had no margin left once a reverse step took 0.92 ms: a slower host capped the scene loop, BENCH_r05 0.947 x value)
-    feeder = _NoiseFeeder(base, len(mine), (T + 1, total_batch_size, num_channels, traj_len), 2 * kl if kl > 1 else k + 1) if mine else None
+    # (the device source needs none of it: no thread, no page-locked buffer, no draw from the global state)
+    feeder = _NoiseFeeder(base, len(mine), (T + 1, total_batch_size, num_channels, traj_len), 2 * kl if kl > 1 else k + 1) if mine and device_noise is None else None
+
+    def seed_meta(i):
+        """the key device_noise adds to scene i's result (none without it)"""
+        return {} if device_noise is None else {"noise_seed": scene_seed(device_noise, i)}
+
     run.last_setup_s = time.time() - t_enter  # config, dataset, model load / upload: per run, not per scene
     def prepare_group(scenes_of_group):
         """guides + IK filter of a scene group (infer_serial.py:108-129, once per scene there): the guides are host tables only
@@ -384,8 +404,8 @@ def run(cfg_path, dataset=None, max_scenes=None, verbose=True, scenes_in_flight=
         t2 = time.time()
         what = f"group of {len(data)} scenes"
         group = []
-        for (_, scene_type, scene_num), guide, d, goal_joints in zip(scenes_of_group, guides, data, chosen):
-            meta = dict(scene_type=scene_type, scene_num=scene_num,
+        for (i_scene, scene_type, scene_num), guide, d, goal_joints in zip(scenes_of_group, guides, data, chosen):
+            meta = dict(scene_type=scene_type, scene_num=scene_num, **seed_meta(i_scene),
                         timings=dict(guide_ctor_s=t1 - t0, guide_ctor_s_is=what, ik_filter_s=t2 - t1, ik_filter_s_is=what))
             group.append((guide, d[5], goal_joints, meta, t0))
         return batch, group
@@ -394,13 +414,13 @@ def run(cfg_path, dataset=None, max_scenes=None, verbose=True, scenes_in_flight=
         """k prepared scenes in one launch chain; per scene: best row, success, the serial loop's result keys"""
         diffuser, denoiser = lanes[0]
         t_w = time.time()
-        streams = [feeder.next() for _ in group]
+        streams = [feeder.next() for _ in group] if feeder is not None else DeviceNoise(seeds=[g[3]["noise_seed"] for g in group])
         noise_wait = time.time() - t_w
         starts, goals = np.stack([g[1] for g in group]), np.stack([g[2] for g in group])
         ta = time.time()
         Xd = diffuser.denoise_guided_scenes(denoiser, batch, traj_len, num_channels, starts, goals, noise=streams, condition=True, return_device=True)
         tb = time.time()
-        for st in streams:
+        for st in streams if feeder is not None else ():
             feeder.recycle(st)  # (the call synchronised before it returned the device state: every upload out of the buffers is done)
         # the finished (S, B, C, N) state stays on the device and is scored as ONE batch: per-scene volumes + pick, per-scene success
         # flags + counts, and the metrics of all S * B rows (they need no scene) - three calls for the group, not four per scene
@@ -471,11 +491,12 @@ def run(cfg_path, dataset=None, max_scenes=None, verbose=True, scenes_in_flight=
                 # numbers the reference's loop would give it (nothing else may draw from the global state while a run is in progress).
                 # (pool.submit hands the scenes to the lanes in order, the feeder hands the streams out in the same order)
                 # where a scene's "Planning Time" (infer_serial.py:108-157: guide construction + IK filter + sampling + best pick) goes
-                meta = dict(scene_type=scene_type, scene_num=scene_num, timings=dict(guide_ctor_s=t1 - t0, ik_filter_s=t2 - t1))
+                meta = dict(scene_type=scene_type, scene_num=scene_num, **seed_meta(i), timings=dict(guide_ctor_s=t1 - t0, ik_filter_s=t2 - t1))
+                noise = feeder.next() if feeder is not None else DeviceNoise(meta["noise_seed"])
                 if k == 1:
-                    collect(plan(lane, guide, start_joints, goal_joints, feeder.next(), meta, t0))  # serial: the reference's order of events
+                    collect(plan(lane, guide, start_joints, goal_joints, noise, meta, t0))  # serial: the reference's order of events
                 else:
-                    pending.append(pool.submit(plan, lane, guide, start_joints, goal_joints, feeder.next(), meta, t0))
+                    pending.append(pool.submit(plan, lane, guide, start_joints, goal_joints, noise, meta, t0))
             while pending:
                 collect(pending.pop(0))
     finally:
@@ -500,6 +521,8 @@ def main(argv=None):
                                                                              "the model is built for that many times the rows)")
     parser.add_argument("--max-scenes", type=int, default=None, help="stop after this many scenes of the cfg's order (all ranks together)")
     parser.add_argument("--seed", type=int, default=None, help="np.random.seed(seed + rank) before the loop (the reference never seeds; for repeatable runs)")
+    parser.add_argument("--device-noise", type=int, default=None, metavar="SEED", help="draw the noise on the GPU (Philox, no parity with the NumPy stream): scene i of the "
+                                                                                        "cfg's order runs under scene_seed(SEED, i), whatever the grouping, the lanes and the ranks (extension)")
     parser.add_argument("--results-json", type=str, default=None, help="write this rank's per-scene results (without the trajectories) and the job summary "
                                                                        "to PATH (rank 0) / PATH.rank<r> (other ranks)")
     parser.add_argument("--ensemble-report", action="store_true", help="score every row of each batch on the GPU (path lengths, SPARC) and report, per guide of the "
@@ -526,7 +549,8 @@ def main(argv=None):
     if args.seed is not None:
         np.random.seed(args.seed + rank)
     results = run(args.cfg_path, scenes_in_flight=args.scenes_in_flight, max_scenes=args.max_scenes, scenes_per_launch=args.scenes_per_launch,
-                  ensemble_report=args.ensemble_report, prefer=args.prefer, ik_seeds=args.ik_seeds, ik_tool=ik_tool, self_collision=args.self_collision)
+                  ensemble_report=args.ensemble_report, prefer=args.prefer, ik_seeds=args.ik_seeds, ik_tool=ik_tool, self_collision=args.self_collision,
+                  device_noise=args.device_noise)
     if args.results_json:
         import json
 
