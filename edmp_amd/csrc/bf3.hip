@@ -22,8 +22,8 @@
 //     with (nearly) equal numbers of (l, lp) pairs, found by exhaustive search at compile time (Bf3Cfg::part0_mask).
 //   * a chunk = 32 channels = ONE MFMA K.  It is worked in two PHASES with equal MFMA counts - A: the weight components lo and mid
 //     (products hi*lo, mid*mid, hi*mid), B: the weight component hi (lo*hi, mid*hi, hi*hi) - and a phase's weight registers are
-//     refilled with the next chunk's right after the phase: every weight fragment is requested half a chunk before its use with
-//     3 x NSLOT x 4 registers of weights in flight, no double buffer.
+//     refilled with the next chunk's when the phase is over (lo and mid right after phase A; hi at the head of the next chunk): every
+//     weight fragment is requested half a chunk before its use with 3 x NSLOT x 4 registers of weights in flight, no double buffer.
 //   * weights: fragment stream of bf16 triples [Cout/16][Cin/32][slot][component][64 lanes][8 bf16] (1 KiB blocks, 1.5x the
 //     bytes of the fp32 stream), split once at load (pack_fragments_bf3).
 #pragma once
@@ -141,6 +141,12 @@ struct Bf3Cfg {
         return -1;
     }
     static constexpr int first(int H) { return needed(H, 0) ? 0 : next(H, 0); }
+    // registers of the K loop's arrays (accumulators, weight fragments, the two activation fragment sets).  Where they leave room,
+    // the chunk loop is rotated across its barrier (a second stage address) and the hand-over's bias values are loaded in the prologue
+    // and held across the K loop (one or two registers).  <K5, 32, 64, 64, 4, true> (248 of 256) has none to spare - either change
+    // makes it spill: it keeps the barrier behind the chunk and loads its bias first behind the K loop, ahead of the epilogue's operands
+    static constexpr int KREGS = MAXT * NR * 8 + 3 * NSLOT * 4 + 2 * NR * 3 * 4;
+    static constexpr bool ROTATE = KREGS <= 240, BIAS_EARLY = ROTATE;
     // staging: float4 items [position][row][channel quad] of a chunk over the 256 staging threads
     static constexpr int A_F4 = LIN * MS * (KC / 4);
     static constexpr int NA = (A_F4 + 255) / 256;
@@ -164,8 +170,17 @@ struct Bf3Cfg {
 __device__ long long g_bf3_stamps[8][8];
 #define EDMP_BF3_STAMP(i) \
     if (blockIdx.x == 0 && lane == 0) g_bf3_stamps[wave][i] = clock64();
+// the chunk barrier, with the cycles a wave waits at it summed into stamp 5 (as wide.hip's bar_cyc).  The clock reads return through the
+// same counter as the LDS reads, so the MFMA side adds its difference up only after the entry's MFMAs are issued (EDMP_BF3_BAR_ADD)
+#define EDMP_BF3_CHUNK_BARRIER \
+    bar_t0 = clock64();        \
+    __syncthreads();           \
+    bar_t1 = clock64();
+#define EDMP_BF3_BAR_ADD bar_cyc += bar_t1 - bar_t0;
 #else
 #define EDMP_BF3_STAMP(i)
+#define EDMP_BF3_CHUNK_BARRIER __syncthreads();
+#define EDMP_BF3_BAR_ADD
 #endif
 
 template <int KIND, int MS, int CG, int GS, int LIN, bool RES>
@@ -199,6 +214,9 @@ __global__ __launch_bounds__(kBf3Threads) void bf3_conv_kernel(const float* a_sr
     const int co0 = grp * CG, b0 = tile * MS;
     const int ch1 = a_C1 / KC, ch2 = a_C2 / KC, nK = ch1 + ch2;
     EDMP_BF3_STAMP(0)
+#ifdef EDMP_BF3_STAMPS
+    long long bar_cyc = 0, bar_t0 = 0, bar_t1 = 0;
+#endif
     // The workgroup claims its waves' WHOLE register budget (2 waves per SIMD x 256 VGPRs = the SIMD's file): no wave of another kernel
     // can share a CU with it.  Measured need, not tidiness: with the 124-244 registers the kernels actually use, waves of the guide's
     // gradient kernel (guide.hip: guide_kernel<GM_GRAD>) that landed on a CU beside a bf16x3 workgroup - row chains, two scenes in
@@ -270,21 +288,28 @@ __global__ __launch_bounds__(kBf3Threads) void bf3_conv_kernel(const float* a_sr
     // one chunk of part H on stage `st` in two PHASES: A = the weight components lo and mid, B = the weight component hi (87 of the
     // 174 MFMAs each at L = 7); inside a phase one entry per needed input position: its activation components against every tile
     // the position feeds, smallest products first, consecutive MFMAs on different accumulators (9-15 MFMAs = 144-240 cycles per
-    // entry); the fragments of the NEXT entry are read one entry ahead (the first entry's right after the step's barrier; a ring of
-    // three stages that lets them be read before it was measured: no gain, 1.7 k cycles more prologue - profiles/r06_bf16x3.md).
-    // After phase A its weight components are refilled with the next chunk's, after phase B component hi: every weight fragment
-    // is requested half a chunk (~1.4 k cycles) before its first use.
-    auto chunk = [&](auto hc, const unsigned short* st, int kgn) __attribute__((always_inline)) {
-        constexpr int H = decltype(hc)::value;
-        u32x4_t av[2][NR][3];
-        {   // first entry (phase A: components hi, mid)
-            constexpr int lp0 = Cf::first(H) % LIN;
+    // entry); the fragments of the NEXT entry are read one entry ahead.  The chunk loop is ROTATED across its barrier: the last entry
+    // of a chunk has its fragments in registers, so the chunk's closing barrier is passed BEFORE that entry's MFMAs and the first
+    // entry of the next chunk is read from the other stage right behind it - the read's latency falls under the last entry's MFMAs
+    // instead of in front of the next chunk's first.  (The barrier keeps both duties: the staging waves' writes of the next stage
+    // are visible behind it, and every read of this stage has returned before it - the last entry's fragments were requested one
+    // entry earlier and the barrier's own wait covers them.  A ring of three stages that bought the same early read was measured:
+    // no gain, 1.7 k cycles more prologue - profiles/r06_bf16x3.md.)
+    // After phase A its weight components are refilled with the next chunk's; component hi, free after phase B, is requested at the
+    // head of the chunk that uses it (mfma_loop): every weight fragment is requested half a chunk (~1.4 k cycles) before its first use.
+    using AFrag = u32x4_t[2][NR][3];
+    auto read_first = [&](auto hc, AFrag& av, const unsigned short* st) __attribute__((always_inline)) {
+        constexpr int lp0 = Cf::first(decltype(hc)::value) % LIN;  // first entry (phase A: components hi, mid)
 #pragma unroll
-            for (int r = 0; r < NR; ++r) {
-                av[0][r][0] = *reinterpret_cast<const u32x4_t*>(st + (lp0 * 3 + 0) * PLANE + r * RBLK + afrag);
-                av[0][r][1] = *reinterpret_cast<const u32x4_t*>(st + (lp0 * 3 + 1) * PLANE + r * RBLK + afrag);
-            }
+        for (int r = 0; r < NR; ++r) {
+            av[0][r][0] = *reinterpret_cast<const u32x4_t*>(st + (lp0 * 3 + 0) * PLANE + r * RBLK + afrag);
+            av[0][r][1] = *reinterpret_cast<const u32x4_t*>(st + (lp0 * 3 + 1) * PLANE + r * RBLK + afrag);
         }
+    };
+    // av[0] holds the first entry's fragments on entry; on exit those of the next chunk's first entry, read from `stn` (more: there is one)
+    auto chunk = [&](auto hc, AFrag& av, const unsigned short* st, const unsigned short* stn, int kgn, bool more) __attribute__((always_inline)) {
+        constexpr int H = decltype(hc)::value;
+        if constexpr (!Cf::ROTATE) read_first(hc, av, st);
         static_for<0, 2>([&](auto pc) __attribute__((always_inline)) {
             constexpr int ph = decltype(pc)::value;
             static_for<0, LIN>([&](auto lpc) __attribute__((always_inline)) {
@@ -299,6 +324,13 @@ __global__ __launch_bounds__(kBf3Threads) void bf3_conv_kernel(const float* a_sr
                         for (int r = 0; r < NR; ++r)
 #pragma unroll
                             for (int m = 0; m < ncomp; ++m) av[buf ^ 1][r][m] = *reinterpret_cast<const u32x4_t*>(st + (lpn * 3 + m) * PLANE + r * RBLK + afrag);
+                        // the entry in front of the barrier: its reads first, so that the barrier's wait for them falls under this entry's MFMAs
+                        if constexpr (Cf::ROTATE && Cf::next(H, qn) < 0) __builtin_amdgcn_sched_barrier(0);
+                    }
+                    if constexpr (qn < 0 && Cf::ROTATE) {  // the chunk's last entry: the closing barrier, the next chunk's first fragments, then this entry's MFMAs
+                        static_assert(ph == 1 && buf == 1, "an even number of entries per chunk: the next chunk's first entry lands in register set 0");
+                        EDMP_BF3_CHUNK_BARRIER
+                        if (more) read_first(hc, av, stn);
                     }
                     // products (activation component ia, weight component wc), kept iff ia + wc <= 2; phase A: (hi, lo) (mid, mid) (hi, mid); phase B: (lo, hi) (mid, hi) (hi, hi)
                     static_for<0, 3>([&](auto kc) __attribute__((always_inline)) {
@@ -322,21 +354,29 @@ __global__ __launch_bounds__(kBf3Threads) void bf3_conv_kernel(const float* a_sr
                         });
                     });
                     __builtin_amdgcn_sched_barrier(0);
+                    if constexpr (qn < 0 && Cf::ROTATE) {
+                        EDMP_BF3_BAR_ADD
+                    }
                 }
             });
             // refill with the next chunk's components (the last chunk re-reads its own: harmless)
             if constexpr (ph == 0) {
                 load_w(kgn, std::integral_constant<int, 2>{});
                 load_w(kgn, std::integral_constant<int, 1>{});
-            } else {
+            } else if constexpr (!Cf::ROTATE) {  // (rotated: mfma_loop requests component hi at the head of its chunk)
                 load_w(kgn, std::integral_constant<int, 0>{});
             }
             __builtin_amdgcn_sched_barrier(0);
         });
+        if constexpr (!Cf::ROTATE) {
+            EDMP_BF3_CHUNK_BARRIER
+            EDMP_BF3_BAR_ADD
+        }
     };
 
     // ---- prologue: chunk 0 staged, chunks 1 and 2 and the weights of chunk 0 in flight
     f32x4 xa[NA], xb[NA];
+    float bias_v = 0.f, rbias_v = 0.f;
     if (!mfma_wave) {
         fetch(0, xa);
         fetch(min(1, nK - 1), xb);
@@ -345,16 +385,29 @@ __global__ __launch_bounds__(kBf3Threads) void bf3_conv_kernel(const float* a_sr
     } else {
         load_w(0, std::integral_constant<int, 2>{});
         load_w(0, std::integral_constant<int, 1>{});
-        load_w(0, std::integral_constant<int, 0>{});
+        if constexpr (!Cf::ROTATE) load_w(0, std::integral_constant<int, 0>{});  // (rotated: at the head of chunk 0)
+        // the hand-over's addends (spill), here so that it waits for no load of its own behind the epilogue's operand loads
+        if constexpr (Cf::BIAS_EARLY) {
+            bias_v = p.bias[co0 + s * 16 + (lane & 15)];
+            if constexpr (RES) rbias_v = p.res_bias[co0 + s * 16 + (lane & 15)];
+        }
     }
     __syncthreads();
     EDMP_BF3_STAMP(1)
 
     // one loop per role (the roles are wave-uniform; every wave passes the same nK barriers)
     auto mfma_loop = [&](auto hc) __attribute__((always_inline)) {
+        AFrag av;
+        if constexpr (Cf::ROTATE) read_first(hc, av, stg);
         for (int c = 0; c < nK; ++c) {
-            chunk(hc, stg + (c & 1) * STAGE, min(c + 1, nK - 1));
-            __syncthreads();
+            if constexpr (Cf::ROTATE) {
+                // component hi of THIS chunk, half a chunk before its use as ever - but requested here, at the head of the chunk, not
+                // behind the last one's MFMAs: the K loop then ends without a refill nobody reads, for which the hand-over behind it
+                // (it reuses the weight registers) would have to wait; and unconditional, as the waits for the fragments need it
+                load_w(c, std::integral_constant<int, 0>{});
+                __builtin_amdgcn_sched_barrier(0);
+            }
+            chunk(hc, av, stg + (c & 1) * STAGE, stg + ((c + 1) & 1) * STAGE, min(c + 1, nK - 1), c + 1 < nK);  // (the chunk barrier is inside)
         }
     };
     if (mfma_wave) {
@@ -365,14 +418,21 @@ __global__ __launch_bounds__(kBf3Threads) void bf3_conv_kernel(const float* a_sr
         for (int c = 0; c < nK; c += 2) {
             if (c + 1 < nK) commit(stg + STAGE, xb);
             if (c + 3 < nK) fetch(c + 3, xb);
-            __syncthreads();
+            {
+                EDMP_BF3_CHUNK_BARRIER
+                EDMP_BF3_BAR_ADD
+            }
             if (c + 1 < nK) {
                 if (c + 2 < nK) commit(stg, xa);
                 if (c + 4 < nK) fetch(c + 4, xa);
-                __syncthreads();
+                EDMP_BF3_CHUNK_BARRIER
+                EDMP_BF3_BAR_ADD
             }
         }
     }
+#ifdef EDMP_BF3_STAMPS
+    if (blockIdx.x == 0 && lane == 0) g_bf3_stamps[wave][5] = bar_cyc;
+#endif
     EDMP_BF3_STAMP(2)
 
     // ---- epilogue: big + sml (+ bias) -> LDS [row][position * CG + channel] (conv tiles; the residual tiles behind them); then all
@@ -383,6 +443,13 @@ __global__ __launch_bounds__(kBf3Threads) void bf3_conv_kernel(const float* a_sr
     constexpr int PPR = Cf::PPR, ROW_F4 = Cf::ROW_F4, NF4 = Cf::NF4;
     const int erow = tid / PPR, epart = tid % PPR;
     const int eb = min(b0 + erow, a_B - 1);
+    if constexpr (!Cf::BIAS_EARLY) {  // first in load order: the hand-over waits for these two alone
+        if (mfma_wave) {
+            bias_v = p.bias[co0 + s * 16 + (lane & 15)];
+            if constexpr (RES) rbias_v = p.res_bias[co0 + s * 16 + (lane & 15)];
+        }
+        __builtin_amdgcn_sched_barrier(0);
+    }
     float4 g4[GN ? NF4 : 1], be4[GN ? NF4 : 1], ad4[GN ? NF4 : 1];
     if constexpr (GN) {
 #pragma unroll
@@ -400,9 +467,6 @@ __global__ __launch_bounds__(kBf3Threads) void bf3_conv_kernel(const float* a_sr
     auto spill = [&](auto hc) __attribute__((always_inline)) {
         constexpr int H = decltype(hc)::value;
         const int col = s * 16 + (lane & 15);
-        const float bias_v = p.bias[co0 + col];
-        float rbias_v = 0.f;
-        if constexpr (RES) rbias_v = p.res_bias[co0 + col];
         const int row0 = (Cf::ROWSPLIT ? 16 * part : 0) + 4 * (lane >> 4);  // accumulator element r: row 4 * (lane / 16) + r, column lane % 16
         static_for<0, NTILE>([&](auto tc) __attribute__((always_inline)) {
             constexpr int tl = decltype(tc)::value;

@@ -7,6 +7,9 @@ declare -A F
 F[l7]="-DKINDV=0 -DLV=7 -DGSV=32 -DFMS=16 -DBMS=32"
 F[l7r]="-DKINDV=0 -DLV=7 -DGSV=32 -DFMS=16 -DBMS=32 -DRESV=1"
 F[l7s]="-DKINDV=0 -DLV=7 -DGSV=32 -DFMS=16 -DBMS=32 -DEDMP_BF3_STAMPS"
+F[l7g16s]="-DKINDV=0 -DLV=7 -DGSV=16 -DFMS=16 -DBMS=16 -DEDMP_BF3_STAMPS"
+F[k4as]="-DKINDV=0 -DFKIND=4 -DLV=4 -DGSV=64 -DFMS=32 -DBMS=32 -DFCG=64 -DBCG=64 -DEDMP_BF3_STAMPS"
+F[d128s]="-DKINDV=1 -DLV=13 -DGSV=16 -DFMS=16 -DBMS=16 -DEDMP_BF3_STAMPS"
 F[l7g16]="-DKINDV=0 -DLV=7 -DGSV=16 -DFMS=16 -DBMS=16"
 F[l7g16r]="-DKINDV=0 -DLV=7 -DGSV=16 -DFMS=16 -DBMS=16 -DRESV=1"
 F[l13]="-DKINDV=0 -DLV=13 -DGSV=16 -DFMS=16 -DBMS=16"

@@ -3,7 +3,7 @@
 // evaluation of the whole op (Conv1d k5 + bias -> GroupNorm(8) -> Mish -> + time bias, with RES also the folded residual 1x1 conv;
 // KIND 1 / 2: the strided / transposed resampling conv + bias) and microseconds per launch.
 //   hipcc --offload-arch=gfx950 -O3 -std=c++17 -mllvm -amdgpu-kernarg-preload-count=12 -DKINDV=0 -DLV=7 -DGSV=32 -DFMS=16 -DBMS=32 [-DRESV=1] [-DEDMP_BF3_STAMPS] tools/bf3bench6.hip -o tools/bf3bench6_x
-//   tools/bf3bench6_x [Cin = Cout] [weight family 0..3] [1: the input is two concatenated halves] [B = 1024]
+//   tools/bf3bench6_x [Cin = Cout] [weight family 0..3] [1: the input is two concatenated halves] [B = 1024] [1: timing and stamps only, no co-residency rounds]
 #include "../edmp_amd/csrc/common.h"
 #include "../edmp_amd/csrc/params.h"
 #include <cmath>
@@ -83,6 +83,7 @@ int main(int argc, char** argv) {
     const int B = argc > 4 ? atoi(argv[4]) : 1024, C = 8 * GS, Cin = argc > 1 ? atoi(argv[1]) : C;
     const int wkind = argc > 2 ? atoi(argv[2]) : 0;  // 0 uniform taps, 1 centre tap x30, 2 heavy-tailed (Student t, 2 d.o.f.), 3 per-channel scale spread 1e-3..1e3
     const int split = argc > 3 ? atoi(argv[3]) : 0;  // 1: the input is two tensors of Cin / 2 channels each (a concatenation)
+    const bool quick = argc > 5 && atoi(argv[5]) != 0;
     std::mt19937 g(1);
     std::uniform_real_distribution<float> d(-1.f, 1.f);
     std::normal_distribution<float> nd(0.f, 1.f);
@@ -126,7 +127,7 @@ int main(int argc, char** argv) {
     q.W = reinterpret_cast<const float*>(Wb);
     if (RES) q.res_out = r16;
     launch_wide_t<FKIND, FMS, FCG, GS, L, RES>(p, 0);
-    launch_bf3_t<KIND, BMS, BCG, GS, L, RES>(q, 0);
+    launch_bf3_t<KIND, BMS, BCG, GS, L, RES>(q, 0, nullptr);
     hipError_t e = hipDeviceSynchronize();
     if (e != hipSuccess) { printf("launch failed: %s\n", hipGetErrorString(e)); return 1; }
     std::vector<float> h32(nout), h16(nout), hr32(nres), hr16(nres);
@@ -207,14 +208,14 @@ int main(int argc, char** argv) {
         hipEventElapsedTime(&ms, e0, e1);
         best32 = std::min(best32, ms * 20.f);
         hipEventRecord(e0, 0);
-        for (int i = 0; i < 50; ++i) launch_bf3_t<KIND, BMS, BCG, GS, L, RES>(q, 0);
+        for (int i = 0; i < 50; ++i) launch_bf3_t<KIND, BMS, BCG, GS, L, RES>(q, 0, nullptr);
         hipEventRecord(e1, 0);
         hipEventSynchronize(e1);
         hipEventElapsedTime(&ms, e0, e1);
         best16 = std::min(best16, ms * 20.f);
     }
     printf("  us per launch (chains of 50): fp32-MFMA %.2f | bf16x3 %.2f | x%.3f\n", best32, best16, best32 / best16);
-    {   // co-residency check: the same launch on 4 streams at once (quarter batches, as the sampler's row chains do), many rounds, every output bit-compared with the serial one
+    if (!quick) {   // co-residency check: the same launch on 4 streams at once (quarter batches, as the sampler's row chains do), many rounds, every output bit-compared with the serial one
         hipStream_t st[4];
         float* yo[4];
         for (int k = 0; k < 4; ++k) { hipStreamCreate(&st[k]); hipMalloc((void**)&yo[k], nout * 4); }
@@ -229,7 +230,7 @@ int main(int argc, char** argv) {
                 if (C2) qq.src2 = q.src2 + (size_t)k * Bq * L * C2;
                 qq.dst = yo[k] + (size_t)k * Bq * LOUT * C;
                 if (RES) qq.res_out = r16 + (size_t)k * Bq * L * C;
-                for (int rep = 0; rep < 3; ++rep) launch_bf3_t<KIND, BMS, BCG, GS, L, RES>(qq, st[k]);
+                for (int rep = 0; rep < 3; ++rep) launch_bf3_t<KIND, BMS, BCG, GS, L, RES>(qq, st[k], nullptr);
             }
             hipDeviceSynchronize();
             for (int k = 0; k < 4; ++k) {
@@ -249,7 +250,7 @@ int main(int argc, char** argv) {
                 qq.dst = yo[k] + (size_t)k * Bq * LOUT * C;
                 if (RES) qq.res_out = ((k & 1) ? r16 : r32) + (size_t)k * Bq * L * C;
                 for (int rep = 0; rep < 3; ++rep) {
-                    if (k & 1) launch_bf3_t<KIND, BMS, BCG, GS, L, RES>(qq, st[k]);
+                    if (k & 1) launch_bf3_t<KIND, BMS, BCG, GS, L, RES>(qq, st[k], nullptr);
                     else launch_wide_t<FKIND, FMS, FCG, GS, L, RES>(qq, st[k]);
                 }
             }
@@ -276,7 +277,7 @@ int main(int argc, char** argv) {
                 hipMemsetAsync(cd, 0, NC * 4, st[0]);
                 hipLaunchKernelGGL(canary_kernel, dim3(NC / 256), dim3(256), 0, st[0], cd, IT, 0.3f);
                 for (int rep = 0; rep < 12; ++rep) {
-                    if (which == 0) launch_bf3_t<KIND, BMS, BCG, GS, L, RES>(q, st[1]);
+                    if (which == 0) launch_bf3_t<KIND, BMS, BCG, GS, L, RES>(q, st[1], nullptr);
                     else launch_wide_t<FKIND, FMS, FCG, GS, L, RES>(p, st[1]);
                 }
                 hipDeviceSynchronize();
@@ -293,7 +294,7 @@ int main(int argc, char** argv) {
     long long st[8][8];
     hipMemcpyFromSymbol(st, HIP_SYMBOL(edmp::g_bf3_stamps), sizeof(st));
     for (int w = 0; w < 8; ++w)
-        printf("  wave %d (%s): prologue %lld | K loop %lld | spill %lld | final pass %lld cycles\n", w, w < 4 ? "mfma" : "stage", st[w][1] - st[w][0], st[w][2] - st[w][1], st[w][3] - st[w][2], st[w][4] - st[w][3]);
+        printf("  wave %d (%s): prologue %lld | K loop %lld (of it waiting at the chunk barriers %lld) | spill %lld | final pass %lld cycles\n", w, w < 4 ? "mfma" : "stage", st[w][1] - st[w][0], st[w][2] - st[w][1], st[w][5], st[w][3] - st[w][2], st[w][4] - st[w][3]);
 #endif
     return nbad ? 2 : 0;
 }
