@@ -12,9 +12,10 @@
 // shorter - rounding chain, not reduced precision.  (Reference op: diffusion/models/blocks.py:22-28 Conv1dBlock, :147-164 the adds
 // and the residual 1x1 conv of ResidualConvolutionBlock, :213 / :251 the resampling convs.)
 //
-// Same contract as wide_conv_kernel<KIND, MS, CG, GS, LIN, RES> (wide.hip): a workgroup owns MS samples x CG = 32 output channels
-// (whole GroupNorm groups) x ALL output positions; an accumulator tile is (one output position, 16 samples) x (16 channels); the
-// pair (output l, input lp) contributes A[lp] x W[tap(l, lp)] iff that tap exists.  What differs:
+// Same contract as wide_conv_kernel<KIND, MS, CG, GS, LIN, RES> (wide.hip): a workgroup owns MS samples x CG output channels
+// (32, or 64 at 512 channels: whole GroupNorm groups; a 32-sample RESAMPLER, which has no GroupNorm, takes two adjacent 32-channel
+// groups per workgroup in a launch larger than the chip: Bf3Cfg::PAIRABLE, launch_bf3_t) x ALL output positions; an accumulator
+// tile is (one output position, 16 samples) x (16 channels); the pair (output l, input lp) contributes A[lp] x W[tap(l, lp)] iff that tap exists.  What differs:
 //   * eight waves: four issue MFMAs, four STAGE: global fp32 -> split into three bf16 planes (v_cvt_pk_bf16_f32: round to nearest)
 //     -> LDS (two stages), two chunks ahead in registers.  The split's VALU work (4.5 instructions per value) runs on the same SIMDs
 //     BESIDE the matrix pipe, in other waves' issue slots, not between a wave's own MFMAs.
@@ -61,9 +62,17 @@ inline void split3_bf16_rne(float x, unsigned short (&c)[3]) {
 
 template <int KIND, int MS, int CG, int GS, int LIN, bool RES>
 struct Bf3Cfg {
+    static constexpr int kKind = KIND, kMs = MS, kCg = CG, kGs = GS, kLin = LIN;  // (the kernel body takes the configuration as a type)
+    static constexpr bool kRes = RES;
     static constexpr int NTH = kBf3Threads, NMW = 4;  // threads; MFMA waves (waves 4..7 stage)
     static constexpr int LOUT = (KIND == WK_K5) ? LIN : (KIND == WK_DOWN) ? (LIN - 1) / 2 + 1 : ((2 * LIN == 8 || 2 * LIN == 14 || 2 * LIN == 26) ? 2 * LIN - 1 : 2 * LIN);
     static constexpr bool GN = (KIND == WK_K5);
+    // PAIRABLE: a 32-sample resampler with 32-channel workgroups.  No GroupNorm ties its workgroup to a channel group, so a launch
+    // larger than the chip (launch_bf3_t states the rule) runs it with workgroups of TWO adjacent channel groups: the CG = 64
+    // organisation below (four slabs, one per MFMA wave, both row blocks on every weight fragment) - half the workgroups, every
+    // weight fragment fetched once instead of twice, the same MFMAs in the same order on every accumulator: the same bits
+    static constexpr bool PAIRABLE = !GN && MS == 32 && CG == 32;
+    using Paired = std::conditional_t<PAIRABLE, Bf3Cfg<KIND, MS, 2 * CG, 2 * CG, LIN, RES>, Bf3Cfg>;
     static constexpr int SW = 16, S = CG / SW, PARTS = NMW / S;  // CG = 32: two slabs x two parts; CG = 64: four slabs, one wave each
     static constexpr bool ROWSPLIT = (PARTS == 2 && MS == 32);  // the two waves of a slab: sample halves (MS = 32) | output-position sets (MS = 16)
     static constexpr int NR = (PARTS == 1) ? MS / 16 : 1;       // 16-sample row blocks per wave (CG = 64: both halves of the 32 samples, sharing every weight fragment)
@@ -183,10 +192,13 @@ __device__ long long g_bf3_stamps[8][8];
 #define EDMP_BF3_BAR_ADD
 #endif
 
-template <int KIND, int MS, int CG, int GS, int LIN, bool RES>
-__global__ __launch_bounds__(kBf3Threads) void bf3_conv_kernel(const float* a_src1, const float* a_src2, const void* a_W, int a_C1, int a_C2, int a_Cout, int a_B,
-                                                       int a_gx_shift, int a_ng_shift, RcbP p) {
-    using Cf = Bf3Cfg<KIND, MS, CG, GS, LIN, RES>;
+// The kernel's text, for the configuration Cf it runs under (bf3_conv_kernel below: its own, or - a pairable instance in a launch
+// larger than the chip - the paired one): the workgroup's width, its slabs and parts, its channel offset and its place in the grid
+// all come from Cf.  `claim` is the kernel's CU claim (bf3_conv_kernel states it once; it runs here, behind the workgroup's place in the grid).
+template <class Cf, class Claim>
+__device__ __forceinline__ void bf3_conv_body(const float* a_src1, const float* a_src2, const void* a_W, int a_C1, int a_C2, int a_Cout, int a_B, int a_gx_shift, int a_ng_shift, const RcbP& p, Claim claim) {
+    constexpr int KIND = Cf::kKind, MS = Cf::kMs, CG = Cf::kCg, GS = Cf::kGs, LIN = Cf::kLin;
+    constexpr bool RES = Cf::kRes;
     constexpr int LOUT = Cf::LOUT, KC = Cf::KC, RS = Cf::RS, PLANE = Cf::PLANE, STAGE = Cf::STAGE, NSLOT = Cf::NSLOT, NTILE = Cf::NTILE, MAXT = Cf::MAXT;
     constexpr int YS = Cf::YS, RYS = Cf::RYS, NA = Cf::NA, A_F4 = Cf::A_F4, WBLK = Cf::WBLK;
     constexpr bool GN = Cf::GN;
@@ -217,14 +229,7 @@ __global__ __launch_bounds__(kBf3Threads) void bf3_conv_kernel(const float* a_sr
 #ifdef EDMP_BF3_STAMPS
     long long bar_cyc = 0, bar_t0 = 0, bar_t1 = 0;
 #endif
-    // The workgroup claims its waves' WHOLE register budget (2 waves per SIMD x 256 VGPRs = the SIMD's file): no wave of another kernel
-    // can share a CU with it.  Measured need, not tidiness: with the 124-244 registers the kernels actually use, waves of the guide's
-    // gradient kernel (guide.hip: guide_kernel<GM_GRAD>) that landed on a CU beside a bf16x3 workgroup - row chains, two scenes in
-    // flight: other streams - came back with lanes 48-63 of ONE register changed in ~0.1 % of the launches (one gradient element of one
-    // row; never with the fp32-MFMA program, never with this line: profiles/r06_coresidency_fault.md).  Cause not found (no LDS
-    // overrun: padding the allocation changes nothing; no register beyond the declared count in the ISA; a pure-VALU canary kernel
-    // beside the same launches stays bit-exact); the single-stream path never shares a CU anyway (one workgroup per CU).
-    asm volatile("v_mov_b32 v255, 0" ::: "v255");
+    claim();
 
     // ---- staging side (waves 4..7): item e = (position, sample row, channel quad) of a chunk
     const int ptid = tid & 255;
@@ -573,6 +578,33 @@ __global__ __launch_bounds__(kBf3Threads) void bf3_conv_kernel(const float* a_sr
     EDMP_BF3_STAMP(4)
 }
 
+// bit of the kernel argument a_ng_shift of a PAIRABLE instance: the launch runs the paired configuration (the rest of the argument is
+// the shift as ever).  A leading scalar argument, preloaded with the others: the choice costs no scalar-memory read ahead of the first loads
+constexpr int kBf3PairBit = 1 << 8;
+
+template <int KIND, int MS, int CG, int GS, int LIN, bool RES>
+__global__ __launch_bounds__(kBf3Threads) void bf3_conv_kernel(const float* a_src1, const float* a_src2, const void* a_W, int a_C1, int a_C2, int a_Cout, int a_B,
+                                                       int a_gx_shift, int a_ng_shift, RcbP p) {
+    using Cf = Bf3Cfg<KIND, MS, CG, GS, LIN, RES>;
+    // The workgroup claims its waves' WHOLE register budget (2 waves per SIMD x 256 VGPRs = the SIMD's file): no wave of another kernel
+    // can share a CU with it.  Measured need, not tidiness: with the 124-244 registers the kernels actually use, waves of the guide's
+    // gradient kernel (guide.hip: guide_kernel<GM_GRAD>) that landed on a CU beside a bf16x3 workgroup - row chains, two scenes in
+    // flight: other streams - came back with lanes 48-63 of ONE register changed in ~0.1 % of the launches (one gradient element of one
+    // row; never with the fp32-MFMA program, never with this line: profiles/r06_coresidency_fault.md).  Cause not found (no LDS
+    // overrun: padding the allocation changes nothing; no register beyond the declared count in the ISA; a pure-VALU canary kernel
+    // beside the same launches stays bit-exact); the single-stream path never shares a CU anyway (one workgroup per CU).
+    const auto claim = [] __device__() __attribute__((always_inline)) {
+        asm volatile("v_mov_b32 v255, 0" ::: "v255");
+    };
+    if constexpr (Cf::PAIRABLE) {
+        const int ng_shift = a_ng_shift & (kBf3PairBit - 1);
+        if (a_ng_shift & kBf3PairBit) bf3_conv_body<typename Cf::Paired>(a_src1, a_src2, a_W, a_C1, a_C2, a_Cout, a_B, a_gx_shift, ng_shift, p, claim);
+        else bf3_conv_body<Cf>(a_src1, a_src2, a_W, a_C1, a_C2, a_Cout, a_B, a_gx_shift, ng_shift, p, claim);
+    } else {
+        bf3_conv_body<Cf>(a_src1, a_src2, a_W, a_C1, a_C2, a_Cout, a_B, a_gx_shift, a_ng_shift, p, claim);
+    }
+}
+
 // host: [tap][Cout][Cin] (taps 0..ntap-1; tap index 5 = the folded residual 1x1 conv) -> bf16-triple fragment stream
 // [Cout/16][Cin/32][nslot][component 3][64 lanes][8 bf16]: lane (n = lane % 16, oct = lane / 16) holds
 // W_comp[slot][slab * 16 + n][32 kg + 8 oct + 0..7] - the B operand of v_mfma_f32_16x16x32_bf16.  `out` counts in bf16.
@@ -596,14 +628,33 @@ inline void pack_fragments_bf3(const float* w_tco_ci, int cout, int cin, int nta
             }
 }
 
+// compute units of the current device, asked once (the pairing rule of launch_bf3_t)
+inline int bf3_cu_count(int* out) {
+    static std::atomic<int> n_cu{0};
+    int n = n_cu.load(std::memory_order_acquire);
+    if (!n) {
+        int dev = 0;
+        EDMP_HIP_CHECK(hipGetDevice(&dev));
+        EDMP_HIP_CHECK(hipDeviceGetAttribute(&n, hipDeviceAttributeMultiprocessorCount, dev));
+        n_cu.store(n, std::memory_order_release);
+    }
+    *out = n;
+    return EDMP_OK;
+}
+
 // q != nullptr: launch nothing; fill q with what the runtime reports for this instance at its launch configuration (the CU-claim
-// check when a layer program is built, unet.hip: check_bf3_cu_claim)
+// check when a layer program is built, unet.hip: check_bf3_cu_claim); a pairable instance reports the larger of its two LDS sizes.
+// THE PAIRING RULE: a launch runs the paired configuration (Bf3Cfg::PAIRABLE: workgroups of 2 CG channels) iff the instance is
+// pairable, its channel groups are even in number and its workgroups outnumber the device's CUs - a bf16x3 workgroup owns its CU, so
+// such a launch takes more than one round, and no launch that fits the chip in one round gets fewer workgroups than it had
 template <int KIND, int MS, int CG, int GS, int LIN, bool RES>
 int launch_bf3_t(const RcbP& p, hipStream_t s, KernelAttrs* q) {
     using Cf = Bf3Cfg<KIND, MS, CG, GS, LIN, RES>;
+    using Pf = typename Cf::Paired;
     static std::atomic<int> attr_set{0};
-    constexpr size_t bytes = Cf::lds_bytes();
-    static_assert(bytes <= 160 * 1024, "bf16x3 position-tile kernel exceeds the 160 KiB LDS of a CU");
+    constexpr size_t max_bytes = Cf::lds_bytes() > Pf::lds_bytes() ? Cf::lds_bytes() : Pf::lds_bytes();
+    static_assert(max_bytes <= 160 * 1024, "bf16x3 position-tile kernel exceeds the 160 KiB LDS of a CU");
+    size_t bytes = max_bytes;
     const void* fn = reinterpret_cast<const void*>(&bf3_conv_kernel<KIND, MS, CG, GS, LIN, RES>);
     if (!attr_set.load(std::memory_order_acquire)) {
         EDMP_HIP_CHECK(hipFuncSetAttribute(fn, hipFuncAttributeMaxDynamicSharedMemorySize, (int)bytes));
@@ -622,13 +673,26 @@ int launch_bf3_t(const RcbP& p, hipStream_t s, KernelAttrs* q) {
     }
     EDMP_REQUIRE(p.C1 % Cf::KC == 0 && p.C2 % Cf::KC == 0 && p.Cout % CG == 0, "bf3_conv_kernel: channels must be multiples of 32 (C1=%d, C2=%d, Cout=%d)", p.C1, p.C2, p.Cout);
     EDMP_REQUIRE(p.C2 == 0 || p.C2 == p.C1, "bf3_conv_kernel: the two halves of a concatenated input must have the same width (C1=%d, C2=%d)", p.C1, p.C2);
-    const int ng = p.Cout / CG, nt = (p.B + MS - 1) / MS;
+    int ng = p.Cout / CG;
+    const int nt = (p.B + MS - 1) / MS;
+    bool pair = false;
+    if constexpr (Cf::PAIRABLE) {
+        int n_cu = 0;
+        if (const int rc = bf3_cu_count(&n_cu); rc != EDMP_OK) return rc;
+        pair = ng % 2 == 0 && ng * nt > n_cu;
+    }
+    if (pair) {
+        EDMP_REQUIRE(p.Cout % Pf::kCg == 0, "bf3_conv_kernel: paired workgroups need Cout to be a multiple of %d (Cout=%d)", Pf::kCg, p.Cout);
+        ng = p.Cout / Pf::kCg;
+    }
+    bytes = pair ? Pf::lds_bytes() : Cf::lds_bytes();
     const int gx = xcd_split(ng, nt, (double)p.Cout * (p.C1 + p.C2) * Cf::NSLOT * 1.5, (double)nt * MS * LIN * (p.C1 + p.C2));
     int gxs = -1, ngs = -1;
     if (gx > 0 && (ng & (ng - 1)) == 0) {
         gxs = __builtin_ctz(gx);
         ngs = __builtin_ctz(ng);
     }
+    if constexpr (Cf::PAIRABLE) ngs = (ngs < 0 ? 0 : ngs) | (pair ? kBf3PairBit : 0);  // (the shift is read only where gxs >= 0)
     hipLaunchKernelGGL((bf3_conv_kernel<KIND, MS, CG, GS, LIN, RES>), dim3(ng * nt), dim3(kBf3Threads), bytes, s, p.src1, p.src2, reinterpret_cast<const void*>(p.W), p.C1, p.C2, p.Cout, p.B, gxs, ngs, p);
     return EDMP_OK;
 }

@@ -683,7 +683,9 @@ static ConvChoice choose_conv(const BuildSwitches& sw, int kind, int cout, int L
     int ms, cgw = std::max(cg, 32), gs = cg;  // a workgroup covers whole GroupNorm groups, at least 32 channels
     if (bf3) {
         ms = cg >= 32 ? 32 : 16;  // bf3.hip runs the direct form: 32-sample workgroups at 256 channels and above (256 workgroups), 16 at 128
-        if (kind != WK_K5) cgw = 32, gs = std::min(cg, 32);  // no GroupNorm behind a resampler, so 32-channel workgroups at every width
+        // no GroupNorm behind a resampler, so its INSTANCE has 32-channel workgroups at every width; a launch of a 32-sample one that is
+        // larger than the chip runs them in pairs, 64 channels per workgroup (bf3.hip: Bf3Cfg::PAIRABLE, the rule in launch_bf3_t)
+        if (kind != WK_K5) cgw = 32, gs = std::min(cg, 32);
         c.stream = F_FRAG_BF3;
     } else {
         if (kind == WK_K5 && sw.karatsuba) c.form = (cg == 64 && L == 2) ? 2 : (cg >= 32 && L == 4) ? 4 : 0;
