@@ -14,8 +14,15 @@
 //     round-1 kernels of this file: conv_mfma_kernel (generic implicit GEMM), rcb_rows_kernel, rcb_block_kernel, gn_mish_kernel.
 //     Taps that fall into the zero padding are never issued.
 //   * the whole time-embedding MLP chain depends on t only and is precomputed for t = 1..T at load (time_table_kernel).
-//   * the layer program (which kernel, which buffers) is built once in edmp_unet_load / edmp_unet_load_packed.
+//   * the layer program (which kernel, which buffers) is built once in edmp_unet_load / edmp_unet_load_packed (unet_build):
+//       1. the architecture walk (Walk), layout-only and unbound: image size and layout id, buffer count and size, time-bias
+//          stride, every refusal.  No weights are read, nothing is written (edmp_unet_plan_describe is this pass alone).
+//       2. the device image, the activation buffers and the time-bias table are allocated.
+//       3. the same walk again, bound to them (Binder): it packs the image (unless a packed one is being loaded) and emits the
+//          program's ops - parameter struct, instance row, FLOP counts, name - the taps and the head / input pointers.
+//     An op is stated in one place, the emitter of its kind; unet_run_program launches what the walk emitted.
 #include <memory>
+#include <variant>
 
 #include "common.h"
 #define EDMP_STAMPS_DEFINE 1  // unity builds with -DEDMP_STAMPS: the stamp buffer lives here
@@ -122,24 +129,31 @@ enum OpKind { OP_CONV = 0, OP_GN = 1, OP_RCB = 2, OP_WRS = 4, OP_LVL = 5 };
 struct ConvInst;    // rows of the instance tables (below, behind the kernels)
 struct LevelInst;
 struct Level2Inst;
+// One op of the layer program, as the architecture walk (Walk, below) emits it and unet_run_program launches it.
 struct Op {
     OpKind kind;
-    ConvP cv;
-    GnP gn;
-    RcbP rc;
-    LevelP lv;    // OP_LVL: a whole level
-    const ConvInst* inst;       // OP_RCB / OP_WRS: the instance the plan chose (choose_conv)
-    const LevelInst* lv_inst;   // OP_LVL (choose_level)
-    const Level2Inst* lv_pair;  // OP_LVL: set = this level and the NEXT op (the following level) run as one launch (level.hip: level2_kernel)
-    int lv_tb1, lv_tb2;  // offsets of the two blocks' time biases in the time-bias row
-    int tb_off;   // GN: offset into the time-bias row, -1 if none
+    // the kernel parameters of the op's kind (OP_RCB and OP_WRS: RcbP), complete but for what a launch sets: B, the time-bias
+    // pointers of step t and the step tail
+    std::variant<ConvP, GnP, RcbP, LevelP> p;
+    const ConvP& cv() const { return std::get<ConvP>(p); }
+    const GnP& gn() const { return std::get<GnP>(p); }
+    const RcbP& rc() const { return std::get<RcbP>(p); }
+    const LevelP& lv() const { return std::get<LevelP>(p); }
+    const ConvInst* inst = nullptr;       // OP_RCB / OP_WRS: the instance the walk chose (choose_conv)
+    const LevelInst* lv_inst = nullptr;   // OP_LVL (choose_level)
+    const Level2Inst* lv_pair = nullptr;  // OP_LVL: set = this level and the NEXT op (the following level) run as one launch (level.hip: level2_kernel)
+    int tb1 = -1, tb2 = -1;  // offsets into the time-bias row, -1 = none.  OP_RCB / OP_GN: tb1 (a block's conv1); OP_LVL: the level's two blocks
 
-    double flops_nominal, flops_exec;  // per trajectory: every tap | MFMA work actually issued (padding taps skipped, Karatsuba forms)
-    double flops_direct;               // per trajectory: the direct form with padding taps skipped (round-1 'executed' accounting)
-    double flops_bf16;                 // per trajectory: MFMA work issued on the bf16 pipe (bf3.hip ops: 6 partial products x the direct form; else 0)
-    char name[64];                     // kernel instance as rocprofv3 prints it (without the edmp:: prefix)
-    KernelAttrs attrs;                 // bf16x3 ops: what the runtime reports for the instance (check_bf3_cu_claim); else zeros
+    double flops_nominal = 0, flops_exec = 0;  // per trajectory: every tap | MFMA work actually issued (padding taps skipped, Karatsuba forms)
+    double flops_direct = 0;                   // per trajectory: the direct form with padding taps skipped (round-1 'executed' accounting)
+    double flops_bf16 = 0;                     // per trajectory: MFMA work issued on the bf16 pipe (bf3.hip ops: 6 partial products x the direct form; else 0)
+    char name[64] = {};                        // kernel instance as rocprofv3 prints it (without the edmp:: prefix)
+    KernelAttrs attrs;                         // bf16x3 ops: what the runtime reports for the instance (check_bf3_cu_claim); else zeros
 };
+// The second level of a merged pair runs inside the launch of the op before it; an op is a launch of its own (timed, counted, carrying
+// FLOPs) unless it is that second level or a GroupNorm of the generic path (which rides untimed behind its conv).
+static bool second_of_pair(const std::vector<Op>& prog, size_t i) { return i > 0 && prog[i - 1].lv_pair; }
+static bool own_launch(const std::vector<Op>& prog, size_t i) { return prog[i].kind != OP_GN && !second_of_pair(prog, i); }
 
 struct UNet {
     edmp_unet_desc desc{};
@@ -404,7 +418,7 @@ EDMP_LEVEL2_INSTANCES(EDMP_X)
 #endif
 
 // ---- the instance tables: the lists of kernel_instances.h expanded once more, into rows of {template arguments, launcher}.
-// A layer has a kernel instance exactly when its row exists (find_*); the plan keeps the row (choose_conv / choose_level /
+// A layer has a kernel instance exactly when its row exists (find_*); the walk's op keeps the row (choose_conv / choose_level /
 // choose_pair below), and the packer's arguments, the launch and the printed kernel name all come from it.  These expansions are
 // the only place in this file that spells a template argument list (the unity build instantiates the kernels through them).
 struct ConvInst {  // wide.hip (fp32 MFMA) | bf3.hip (bf16x3: exact products on the bf16 matrix pipe)
@@ -609,7 +623,7 @@ static int launch_gn(const GnP& p, hipStream_t s) {
 }
 
 // Builder switches, read from the environment ONCE WHEN A MODEL IS BUILT (BuildSwitches::read, the only getenv of this file) and
-// frozen into its plan, layer program and packed-image layout id: two models built under different settings can live side by side
+// frozen into its layer program and packed-image layout id: two models built under different settings can live side by side
 // in one process (A/B runs, the adversarial-weights test).
 //   EDMP_NO_FUSED / EDMP_NO_RESFOLD / EDMP_NO_LEVEL: every conv on the generic kernels | the residual 1x1 conv as its own launch |
 //     no whole-level kernels.
@@ -664,7 +678,7 @@ static const struct { int kind, cg, L, bf3_bit, ms16_bit; } kConvFamilies[] = {
     {WK_DOWN, 16, 13, 5, -1}, {WK_UP, 16, 7, 5, -1},  // at 128 channels
 };
 
-// What the plan decides for one conv op of a wide level (>= 128 channels), once: everything downstream - the packer (stream, row->ms),
+// What the walk decides for one conv op of a wide level (>= 128 channels), once: everything downstream - the packer (stream, row->ms),
 // the FLOP counts (form), the launch and the kernel name (row) - reads it from here.
 struct ConvChoice {
     const ConvInst* row[2] = {nullptr, nullptr};  // [RES]: without | with the folded residual 1x1 conv (WK_K5); family, MS, GS are the row's.  row[0] == nullptr: no instance, the generic path runs the layer
@@ -730,7 +744,7 @@ static bool owns_cu(int regs, int block, int lds, int wg_per_cu) {
 static int check_bf3_cu_claim(UNet* u) {
     for (Op& op : u->prog) {
         if (!(op.inst && op.inst->bf3)) continue;
-        if (int rc = op.inst->launch(op.rc, nullptr, &op.attrs)) return rc;  // query mode: launches nothing
+        if (int rc = op.inst->launch(op.rc(), nullptr, &op.attrs)) return rc;  // query mode: launches nothing
         const KernelAttrs& a = op.attrs;
         EDMP_REQUIRE(owns_cu(a.regs, a.block, a.lds, a.wg_per_cu),
                      "%s does not own its CU (%d VGPRs x %d threads, %d B of LDS, %d workgroups per CU): the bf16x3 containment of "
@@ -800,7 +814,7 @@ struct Packer {
     }
     // Conv1d k5 weight (Cout, Cin, 5) [+ the block's residual 1x1 conv (Cout, Cin, 1)] -> the B-fragment stream of
     // wide_conv_kernel: [Cout/32][CinP/8][slots][64][4], slots = the taps that can be valid at length L (+ the residual).
-    // form, sw: the stream layout and the tile height the plan chose for the op (ConvChoice; sw is unused by F_FRAG_BF3)
+    // form, sw: the stream layout and the tile height the walk chose for the op (ConvChoice; sw is unused by F_FRAG_BF3)
     size_t conv_frag(const float* w, const float* wres, int cout, int cin, int cinp, int L, PackForm form, int sw) {
         const bool bf3 = form == F_FRAG_BF3;  // bf3.hip: stream of bf16 triples [Cout/16][CinP/32][slots][3][64][8 bf16] (counted in floats here)
         const int kt0 = (L == 2) ? 1 : 0, ntap = (L == 2) ? 3 : 5;
@@ -889,33 +903,10 @@ extern "C" int64_t edmp_unet_param_count(const edmp_unet_desc* desc) {
 // one written under other builder switches, fails to load instead of feeding a kernel the wrong fragment order.
 static const int kPackVersion = 301;
 
-// ---- step 1 of a model build: the LAYER PLAN -----------------------------------------------------------------------------
-// An op of the plan: which kernel family, which activation buffers (ids of the pool) and which tensors of the packed weight image
-// (float offsets); resolved to device pointers by resolve_program() once the image and the buffers exist.
-struct POp {
-    OpKind kind;
-    int src1, src2, C1, C2, Lin, Lout, ntaps, stride, pad, transposed, Cout;
-    size_t w, b;
-    int dst;
-    // gn
-    int y, L, C, res;
-    size_t gamma, beta;
-    int tb_off;
-    double fn, fe, fd;  // FLOPs per trajectory: nominal | issued | direct form without padding taps (0: same as fe)
-    size_t br;  // bias of a residual 1x1 conv folded into an OP_RCB
-    int res_out;  // OP_RCB: buffer receiving the folded residual 1x1 conv (-1: none)
-    const ConvInst* inst;  // OP_RCB / OP_WRS: the instance that runs the op (choose_conv; the RES row once a residual is folded in)
-    // OP_LVL: offsets of the level's tensors in the packed image, in LevelP order; lv_skip: buffer of the skip output (-1: none)
-    size_t lvo[24];
-    const LevelInst* lv_inst;   // (choose_level)
-    const Level2Inst* lv_pair;  // set: this level and the next op as one launch (choose_pair)
-    int lv_tb1, lv_tb2, lv_skip;
-    // fused conv+gn (OP_RCB): uses src1/src2/C1/C2/Lin/Cout/w/b/dst + gamma/beta/res/tb_off
-};
-
+// ---- the ARCHITECTURE WALK: the one place that states an op ---------------------------------------------------------------------
 // kernel instance an op launches, spelled as rocprofv3's kernel trace prints it (minus the edmp:: prefix): lets
 // bench.py's per-kernel table be checked line by line against profiles/*_kernel_stats.csv
-static void op_kernel_name(const POp& o, char* out) {
+static void op_kernel_name(const Op& o, char* out) {
     if (o.kind == OP_RCB || o.kind == OP_WRS) {
         const ConvInst& r = *o.inst;
         snprintf(out, 64, "%s_conv_kernel<%d, %d, %d, %d, %d, %s>", r.bf3 ? "bf3" : "wide", r.kind, r.ms, r.cg, r.gs, r.L, r.res ? "true" : "false");
@@ -926,281 +917,304 @@ static void op_kernel_name(const POp& o, char* out) {
         const LevelInst& r = *o.lv_inst;
         snprintf(out, 64, "level_kernel<%d, %d, %d, %d, %d>", r.mode, r.C, r.L, r.sb, r.cin);
     } else if (o.kind == OP_CONV) {
-        const int kc = pick_kc(o.C1, o.C2);
-        if (o.Cout % 64 == 0) snprintf(out, 64, "conv_mfma_kernel<64, 64, %d>", kc);
+        const int kc = pick_kc(o.cv().C1, o.cv().C2);
+        if (o.cv().Cout % 64 == 0) snprintf(out, 64, "conv_mfma_kernel<64, 64, %d>", kc);
         else snprintf(out, 64, "conv_mfma_kernel<128, 32, %d>", kc >= 32 ? 32 : kc);
     } else {
-        const int n = (o.C / 8) * o.L;
+        const int n = (o.gn().C / 8) * o.gn().L;
         snprintf(out, 64, "gn_mish_kernel<%d>", n <= 128 ? 2 : n <= 256 ? 4 : 8);
     }
 }
 
+// Where the walk's offsets and buffer ids become pointers: an offset into the packed weight image -> wpack + offset, an id of the
+// buffer pool -> that activation buffer.  Unbound (the layout-only pass: neither exists yet) both are nullptr.
+struct Binder {
+    const float* wpack = nullptr;
+    const std::vector<float*>* bufs = nullptr;
+    const float* w(size_t off) const { return wpack ? wpack + off : nullptr; }
+    float* buf(int id) const { return bufs ? (*bufs)[id] : nullptr; }
+};
+
+static int down_length(int L) { return (L - 1) / 2 + 1; }  // Conv1d k3 s2 p1
+static int up_length(int L) {                             // ConvTranspose1d k4 s2 p1, then the crop rule of temporalunet.py:70-71
+    const int Lout = 2 * L;
+    return (Lout == 8 || Lout == 14 || Lout == 26) ? Lout - 1 : Lout;
+}
+
 // Walks the architecture (temporalunet.py:47-76) once: decides per layer which kernel family runs it, packs its weights into the
-// device image in that family's layout (or only sizes them: Packer::dry, loading a packed image), assigns activation buffers from a
-// recycling pool and records the FLOP counts.  No device work.
-struct LayerPlan {
+// device image in that family's layout (or only sizes them: Packer::dry), assigns activation buffers from a recycling pool and
+// emits the layer program, FLOP counts and kernel names included.  No device work.  A model build runs it twice (unet_build).
+struct Walk {
     const edmp_unet_desc* desc;
     const float* params;   // state-dict blob (never read through when pk.dry)
     RawNet inv;
-    BuildSwitches sw;
+    const BuildSwitches sw;
+    const Binder bind;
     int N, td, nd, CP0 = 8;  // horizon, time_dim, levels, padded input channels
     std::vector<int> dm;     // input_dim, dims...
     // products
     Packer pk;
     BufPool pool;
-    std::vector<POp> pops;
+    std::vector<Op> ops;
+    std::vector<UNet::Tap> taps;
     std::vector<float> tw_all, tb_all;  // concatenated time-MLP weights of the residual blocks
     int tb_cursor = 0, rcb_idx = 0;
     int x_in_buf = -1, head_buf = -1;
-    bool final_fused = false;
-    struct TapRec { int which; int buf, C, L; };
-    std::vector<TapRec> tapr;
+    size_t max_lc;  // floats per sample of the largest activation
     size_t hw = 0, hb = 0, o_t1w = 0, o_t1b = 0, o_t3w = 0, o_t3b = 0, o_tw = 0, o_tb = 0;
     double head_flops = 0;
+    // what the walk refuses once it is through (the first of each kind)
+    bool identity_over_concat = false;
+    int no_twin_cout = 0, no_twin_L = 0, gn_group = 0;
 
-    LayerPlan(const edmp_unet_desc* d, const float* blob, bool layout_only) : desc(d), params(blob), inv(inventory(*d)), sw(BuildSwitches::read()) {
+    // layout_only: offsets and sizes, `blob` is not looked at (the first pass of a build; both passes of loading a packed image)
+    Walk(const edmp_unet_desc* d, const float* blob, bool layout_only, const BuildSwitches& s, const Binder& b) : desc(d), inv(inventory(*d)), sw(s), bind(b) {
+        static const float no_params = 0.0f;  // offsets are computed from `params` but never read through
+        params = layout_only ? &no_params : blob;
         N = d->horizon, td = d->time_dim, nd = d->n_levels;
         dm.push_back(d->input_dim);
         for (int i = 0; i < d->n_levels; ++i) dm.push_back(d->dims[i]);
         pk.dry = layout_only;
+        max_lc = (size_t)N * CP0;
     }
 
+    void append(std::vector<float>& v, const float* src, size_t n) {  // layout-only pass: sizes, no reads
+        if (pk.dry) v.resize(v.size() + n, 0.0f);
+        else v.insert(v.end(), src, src + n);
+    }
+    int time_bias(const RawRCB& r) {  // the block's columns of the time-bias table; returns their offset in a row
+        const int off = tb_cursor;
+        tb_cursor += r.cout;
+        append(tw_all, params + r.tw.off, (size_t)r.cout * td);
+        append(tb_all, params + r.tb.off, r.cout);
+        return off;
+    }
+    const float* vec(const RawT& t, int n) { return bind.w(pk.vec(params + t.off, n)); }
+    TH new_out(int C, int Lin, int Lout) {  // an op's output buffer
+        max_lc = std::max(max_lc, (size_t)std::max(Lin, Lout) * C);
+        return TH{pool.get(), C, Lout};
+    }
+    void tap(int which, TH x) {  // kept readable after a forward
+        taps.push_back({which, bind.buf(x.buf), x.C, x.L});
+        pool.pin(x.buf);
+    }
+    template <class P>
+    void set_src(P& p, TH a, const TH* a2) {
+        p.src1 = bind.buf(a.buf);
+        p.src2 = a2 ? bind.buf(a2->buf) : nullptr;
+        p.C1 = a.C;
+        p.C2 = a2 ? a2->C : 0;
+    }
+    Op& push(Op o) {
+        if (o.flops_direct == 0) o.flops_direct = o.flops_exec;
+        if (o.inst && o.inst->bf3) o.flops_bf16 = 6.0 * o.flops_direct;  // six exact partial products per fp32 product, issued on the bf16 pipe
+        if (!(o.kind == OP_RCB && !o.inst)) op_kernel_name(o, o.name);    // (a Conv1dBlock without its instance: refused below)
+        ops.push_back(o);
+        return ops.back();
+    }
 
-        void append(std::vector<float>& v, const float* src, size_t n) {  // layout-only pass: sizes, no reads
-            if (pk.dry) v.resize(v.size() + n, 0.0f);
-            else v.insert(v.end(), src, src + n);
-        }
-
-        static long valid_pairs(int Lin, int Lout, int k, int stride, int pad, bool tr) {
-            long cnt = 0;
-            for (int lo = 0; lo < Lout; ++lo)
-                for (int t = 0; t < k; ++t) {
-                    if (!tr) {
-                        int li = lo * stride + t - pad;
-                        if (li >= 0 && li < Lin) ++cnt;
-                    } else {
-                        int num = lo + pad - t;
-                        if (num >= 0 && num % stride == 0 && num / stride < Lin) ++cnt;
-                    }
-                }
-            return cnt;
-        }
-        TH emit_conv(TH a, const TH* a2, int cin_true, size_t w, size_t b, int Cout, int k, int stride, int pad, bool tr, int Lout) {
-            POp o{};
-            o.kind = OP_CONV;
-            o.src1 = a.buf;
-            o.C1 = a.C;
-            o.src2 = a2 ? a2->buf : -1;
-            o.C2 = a2 ? a2->C : 0;
-            o.Lin = a.L;
-            o.Lout = Lout;
-            o.ntaps = k;
-            o.stride = stride;
-            o.pad = pad;
-            o.transposed = tr;
-            o.Cout = Cout;
-            o.w = w;
-            o.b = b;
-            o.dst = pool.get();
-            // nominal FLOPs: what torch executes: conv 2*Lout*Cout*Cin*k ; convT 2*Lin*Cin*Cout*k (uncropped)
-            o.fn = tr ? 2.0 * a.L * cin_true * Cout * k : 2.0 * Lout * Cout * (double)cin_true * k;
-            o.fe = 2.0 * (double)valid_pairs(a.L, Lout, k, stride, pad, tr) * Cout * (double)(o.C1 + o.C2);
-            pops.push_back(o);
-            return TH{o.dst, Cout, Lout};
-        }
-        TH emit_wrs(TH a, size_t w, size_t b, int Cout, const ConvInst* inst, int k, int Lout) {
-            const int kind = inst->kind;
-            POp o{};
-            o.kind = OP_WRS;
-            o.src1 = a.buf;
-            o.C1 = a.C;
-            o.src2 = -1;
-            o.C2 = 0;
-            o.Lin = a.L;
-            o.Lout = Lout;
-            o.ntaps = k;
-            o.transposed = (kind == WK_UP);
-            o.Cout = Cout;
-            o.w = w;
-            o.b = b;
-            o.dst = pool.get();
-            o.res_out = -1;
-            o.inst = inst;
-            const bool tr = kind == WK_UP;
-            o.fn = tr ? 2.0 * a.L * (double)a.C * Cout * k : 2.0 * Lout * Cout * (double)a.C * k;
-            o.fe = 2.0 * (double)valid_pairs(a.L, Lout, k, 2, 1, tr) * Cout * (double)a.C;
-            pops.push_back(o);
-            return TH{o.dst, Cout, Lout};
-        }
-        void emit_gn(TH y, size_t gamma, size_t beta, int res_buf, int tb_off) {
-            POp o{};
-            o.kind = OP_GN;
-            o.y = y.buf;
-            o.L = y.L;
-            o.C = y.C;
-            o.gamma = gamma;
-            o.beta = beta;
-            o.res = res_buf;
-            o.tb_off = tb_off;
-            pops.push_back(o);
-        }
-        TH emit_fused(TH a, const TH* a2, int cin_true, int cout, const ConvChoice& ch, size_t w, size_t b, size_t gamma, size_t beta, int res_buf, int tbo) {
-            POp o{};
-            o.kind = OP_RCB;
-            o.src1 = a.buf;
-            o.C1 = a.C;
-            o.src2 = a2 ? a2->buf : -1;
-            o.C2 = a2 ? a2->C : 0;
-            o.Lin = a.L;
-            o.Lout = a.L;
-            o.ntaps = 5;
-            o.Cout = cout;
-            o.w = w;
-            o.b = b;
-            o.gamma = gamma;
-            o.beta = beta;
-            o.res = res_buf;
-            o.tb_off = tbo;
-            o.res_out = -1;
-            o.inst = ch.row[0];
-            o.dst = pool.get();
-            o.fn = 2.0 * a.L * cout * (double)cin_true * 5;
-            // executed = issued MFMA work: the L = 2 Karatsuba form runs 3 matrix products where the direct form runs 4, the nested L = 4 form 9 for 14
-            o.fe = 2.0 * (ch.form == 2 ? 3.0 : ch.form == 4 ? 9.0 : (double)valid_pairs(a.L, a.L, 5, 1, 2, false)) * cout * (double)(o.C1 + o.C2);
-            o.fd = 2.0 * (double)valid_pairs(a.L, a.L, 5, 1, 2, false) * cout * (double)(o.C1 + o.C2);
-            pops.push_back(o);
-            return TH{o.dst, cout, a.L};
-        }
-        TH emit_rcb(TH x, const TH* x2) {
-            const RawRCB& r = inv.rcbs[rcb_idx++];
-            const int cin_store = x.C + (x2 ? x2->C : 0);
-            // conv1 (a residual 1x1 conv folded into the wide fused kernel is packed right behind it, as tap index 5)
-            const ConvChoice ch1 = choose_conv(sw, WK_K5, r.cout, x.L, x.C, x2 ? x2->C : 0), ch2 = choose_conv(sw, WK_K5, r.cout, x.L, r.cout, 0);
-            const bool wide = ch1.row[0] && ch2.row[0];  // (same shape: both or neither)
-            const bool fold_res = wide && r.has_res && sw.resfold;
-            // the position-tile kernel reads its weights as an MFMA fragment stream (wide.hip); the generic conv as [tap][Cout][Cin]
-            size_t w1 = wide ? pk.conv_frag(params + r.cb[0].w.off, fold_res ? params + r.rw.off : nullptr, r.cout, r.cin, cin_store, x.L, ch1.stream, ch1.row[0]->ms)
-                             : pk.conv(params + r.cb[0].w.off, r.cout, r.cin, 5, cin_store);
-            size_t b1 = pk.vec(params + r.cb[0].b.off, r.cout);
-            size_t g1 = pk.vec(params + r.cb[0].gw.off, r.cout), be1 = pk.vec(params + r.cb[0].gb.off, r.cout);
-            size_t w2 = wide ? pk.conv_frag(params + r.cb[1].w.off, nullptr, r.cout, r.cout, r.cout, x.L, ch2.stream, ch2.row[0]->ms) : pk.conv(params + r.cb[1].w.off, r.cout, r.cout, 5, r.cout);
-            size_t b2 = pk.vec(params + r.cb[1].b.off, r.cout);
-            size_t g2 = pk.vec(params + r.cb[1].gw.off, r.cout), be2 = pk.vec(params + r.cb[1].gb.off, r.cout);
-            int tb_off = tb_cursor;
-            tb_cursor += r.cout;
-            append(tw_all, params + r.tw.off, (size_t)r.cout * td);
-            append(tb_all, params + r.tb.off, r.cout);
-            if (wide) {
-                TH h = emit_fused(x, x2, r.cin, r.cout, ch1, w1, b1, g1, be1, -1, tb_off);
-                int res_buf;
-                int rr_buf = -1;
-                if (fold_res) {
-                    POp& c1 = pops.back();
-                    c1.res_out = pool.get();
-                    c1.inst = ch1.row[1];
-                    c1.br = pk.vec(params + r.rb.off, r.cout);
-                    c1.fn += 2.0 * x.L * r.cout * (double)r.cin;
-                    c1.fe += 2.0 * x.L * r.cout * (double)cin_store;
-                    c1.fd += 2.0 * x.L * r.cout * (double)cin_store;
-                    rr_buf = c1.res_out;
-                    res_buf = c1.res_out;
-                } else if (r.has_res) {
-                    // (EDMP_NO_RESFOLD: the residual 1x1 conv as its own launch)
-                    size_t wr = pk.conv(params + r.rw.off, r.cout, r.cin, 1, cin_store);
-                    size_t br = pk.vec(params + r.rb.off, r.cout);
-                    TH rr = emit_conv(x, x2, r.cin, wr, br, r.cout, 1, 1, 0, false, x.L);
-                    rr_buf = rr.buf;
-                    res_buf = rr.buf;
+    static long valid_pairs(int Lin, int Lout, int k, int stride, int pad, bool tr) {
+        long cnt = 0;
+        for (int lo = 0; lo < Lout; ++lo)
+            for (int t = 0; t < k; ++t) {
+                if (!tr) {
+                    int li = lo * stride + t - pad;
+                    if (li >= 0 && li < Lin) ++cnt;
                 } else {
-                    res_buf = x2 ? -2 : x.buf;
+                    int num = lo + pad - t;
+                    if (num >= 0 && num % stride == 0 && num / stride < Lin) ++cnt;
                 }
-                TH out = emit_fused(h, nullptr, r.cout, r.cout, ch2, w2, b2, g2, be2, res_buf, -1);
-                pool.put(h.buf);
-                if (rr_buf >= 0) pool.put(rr_buf);
-                return out;
             }
-            TH y1 = emit_conv(x, x2, r.cin, w1, b1, r.cout, 5, 1, 2, false, x.L);
-            emit_gn(y1, g1, be1, -1, tb_off);
-            TH y2 = emit_conv(y1, nullptr, r.cout, w2, b2, r.cout, 5, 1, 2, false, x.L);
-            pool.put(y1.buf);
-            if (r.has_res) {
-                size_t wr = pk.conv(params + r.rw.off, r.cout, r.cin, 1, cin_store);
-                size_t br = pk.vec(params + r.rb.off, r.cout);
-                TH rr = emit_conv(x, x2, r.cin, wr, br, r.cout, 1, 1, 0, false, x.L);
-                emit_gn(y2, g2, be2, rr.buf, -1);
-                pool.put(rr.buf);
-            } else {
-                emit_gn(y2, g2, be2, x2 ? -2 : x.buf, -1);  // identity residual (blocks.py:151-152); -2 = unsupported concat
-            }
-            return y2;
+        return cnt;
+    }
+    // nominal FLOPs: what torch executes: conv 2*Lout*Cout*Cin*k ; convT 2*Lin*Cin*Cout*k (uncropped).  Issued: the taps that meet data, stored channels
+    static void conv_flops(Op& o, int Lin, int Lout, int cin_true, int cin_store, int Cout, int k, int stride, int pad, bool tr) {
+        o.flops_nominal = tr ? 2.0 * Lin * cin_true * Cout * k : 2.0 * Lout * Cout * (double)cin_true * k;
+        o.flops_exec = 2.0 * (double)valid_pairs(Lin, Lout, k, stride, pad, tr) * Cout * (double)cin_store;
+    }
+    TH emit_conv(TH a, const TH* a2, int cin_true, size_t w, size_t b, int Cout, int k, int stride, int pad, bool tr, int Lout) {
+        ConvP c{};
+        set_src(c, a, a2);
+        c.Lin = a.L, c.Lout = Lout, c.ntaps = k, c.stride = stride, c.pad = pad, c.transposed = tr;
+        c.W = bind.w(w), c.bias = bind.w(b), c.Cout = Cout;
+        const TH out = new_out(Cout, a.L, Lout);
+        c.dst = bind.buf(out.buf);
+        Op o{OP_CONV, c};
+        conv_flops(o, a.L, Lout, cin_true, c.C1 + c.C2, Cout, k, stride, pad, tr);
+        push(o);
+        return out;
+    }
+    TH emit_wrs(TH a, size_t w, size_t b, int Cout, const ConvInst* inst, int k, int Lout) {
+        RcbP c{};
+        set_src(c, a, nullptr);
+        c.W = bind.w(w), c.bias = bind.w(b), c.Cout = Cout;
+        const TH out = new_out(Cout, a.L, Lout);
+        c.dst = bind.buf(out.buf);
+        Op o{OP_WRS, c};
+        o.inst = inst;
+        conv_flops(o, a.L, Lout, a.C, a.C, Cout, k, 2, 1, inst->kind == WK_UP);
+        push(o);
+        return out;
+    }
+    void emit_gn(TH y, const float* gamma, const float* beta, const float* res, int tb_off) {
+        GnP g{};
+        g.y = bind.buf(y.buf), g.gamma = gamma, g.beta = beta, g.add_res = res, g.L = y.L, g.C = y.C;
+        // the generic GroupNorm keeps a group in registers (gn_mish_kernel, at most 8 x 64 elements)
+        if (!gn_group && (y.C / 8) * y.L > 512) gn_group = (y.C / 8) * y.L;
+        Op o{OP_GN, g};
+        o.tb1 = tb_off;
+        push(o);
+    }
+    // the resampler of a wide level: its fragment-stream instance if a row exists, else the generic conv
+    TH emit_resampler(int kind, TH a, const RawT& w, const RawT& b, int Lout) {
+        const bool up = kind == WK_UP;
+        const int C = a.C, k = up ? 4 : 3;
+        if (const ConvChoice ch = choose_conv(sw, kind, C, a.L, C, 0); ch.row[0]) {
+            const size_t wo = pk.resample_frag(params + w.off, C, C, k, up, ch.stream, ch.row[0]->ms), bo = pk.vec(params + b.off, C);
+            return emit_wrs(a, wo, bo, C, ch.row[0], k, Lout);
         }
+        const size_t wo = up ? pk.convT(params + w.off, C, C, k) : pk.conv(params + w.off, C, C, k, C), bo = pk.vec(params + b.off, C);
+        return emit_conv(a, nullptr, C, wo, bo, C, k, 2, 1, up, Lout);
+    }
+    // a block's residual 1x1 conv as its own launch (no instance folds it in, or EDMP_NO_RESFOLD)
+    TH emit_res_conv(const RawRCB& r, TH x, const TH* x2) {
+        const size_t wr = pk.conv(params + r.rw.off, r.cout, r.cin, 1, x.C + (x2 ? x2->C : 0)), br = pk.vec(params + r.rb.off, r.cout);
+        return emit_conv(x, x2, r.cin, wr, br, r.cout, 1, 1, 0, false, x.L);
+    }
+    struct BlockW { const float *w, *b, *gamma, *beta; };  // a packed Conv1dBlock
+    // Conv1dBlock on the position-tile kernel.  res: the residual conv2 adds | tbo: the time bias conv1 adds | fold: the block's
+    // residual 1x1 conv rides in this launch (its weights sit behind the taps in w); *fold receives its output
+    TH emit_fused(TH a, const TH* a2, int cin_true, int cout, const ConvChoice& ch, const BlockW& w, const float* res, int tbo, const RawT* fold_bias, TH* fold) {
+        RcbP c{};
+        set_src(c, a, a2);
+        c.W = w.w, c.bias = w.b, c.gamma = w.gamma, c.beta = w.beta, c.add_res = res, c.Cout = cout;
+        const TH out = new_out(cout, a.L, a.L);
+        c.dst = bind.buf(out.buf);
+        const int cin_store = c.C1 + c.C2;
+        Op o{OP_RCB};
+        o.tb1 = tbo;
+        o.inst = ch.row[fold ? 1 : 0];
+        if (!o.inst && !no_twin_cout) no_twin_cout = cout, no_twin_L = a.L;  // listed without the twin that folds the residual in
+        conv_flops(o, a.L, a.L, cin_true, cin_store, cout, 5, 1, 2, false);
+        o.flops_direct = o.flops_exec;
+        // issued MFMA work: the L = 2 Karatsuba form runs 3 matrix products where the direct form runs 4, the nested L = 4 form 9 for 14
+        if (ch.form) o.flops_exec = 2.0 * (ch.form == 2 ? 3.0 : 9.0) * cout * (double)cin_store;
+        if (fold) {
+            *fold = TH{pool.get(), cout, a.L};
+            c.res_out = bind.buf(fold->buf);
+            c.res_bias = vec(*fold_bias, cout);
+            o.flops_nominal += 2.0 * a.L * cout * (double)cin_true;
+            o.flops_exec += 2.0 * a.L * cout * (double)cin_store;
+            o.flops_direct += 2.0 * a.L * cout * (double)cin_store;
+        }
+        o.p = c;
+        push(o);
+        return out;
+    }
+    TH emit_rcb(TH x, const TH* x2) {
+        const RawRCB& r = inv.rcbs[rcb_idx++];
+        const int cin_store = x.C + (x2 ? x2->C : 0);
+        // conv1 (a residual 1x1 conv folded into the wide fused kernel is packed right behind it, as tap index 5)
+        const ConvChoice ch1 = choose_conv(sw, WK_K5, r.cout, x.L, x.C, x2 ? x2->C : 0), ch2 = choose_conv(sw, WK_K5, r.cout, x.L, r.cout, 0);
+        const bool wide = ch1.row[0] && ch2.row[0];  // (same shape: both or neither)
+        const bool fold_res = wide && r.has_res && sw.resfold;
+        // the position-tile kernel reads its weights as an MFMA fragment stream (wide.hip); the generic conv as [tap][Cout][Cin]
+        const size_t w1 = wide ? pk.conv_frag(params + r.cb[0].w.off, fold_res ? params + r.rw.off : nullptr, r.cout, r.cin, cin_store, x.L, ch1.stream, ch1.row[0]->ms)
+                               : pk.conv(params + r.cb[0].w.off, r.cout, r.cin, 5, cin_store);
+        const size_t b1 = pk.vec(params + r.cb[0].b.off, r.cout);
+        const BlockW k1{bind.w(w1), bind.w(b1), vec(r.cb[0].gw, r.cout), vec(r.cb[0].gb, r.cout)};
+        const size_t w2 = wide ? pk.conv_frag(params + r.cb[1].w.off, nullptr, r.cout, r.cout, r.cout, x.L, ch2.stream, ch2.row[0]->ms) : pk.conv(params + r.cb[1].w.off, r.cout, r.cout, 5, r.cout);
+        const size_t b2 = pk.vec(params + r.cb[1].b.off, r.cout);
+        const BlockW k2{bind.w(w2), bind.w(b2), vec(r.cb[1].gw, r.cout), vec(r.cb[1].gb, r.cout)};
+        const int tb_off = time_bias(r);
+        if (!r.has_res && x2) identity_over_concat = true;  // identity residual (blocks.py:151-152) over a channel concat
+        TH rr{-1, r.cout, x.L};                             // the residual 1x1 conv's output, where the block has one
+        if (wide) {
+            const TH h = emit_fused(x, x2, r.cin, r.cout, ch1, k1, nullptr, tb_off, &r.rb, fold_res ? &rr : nullptr);
+            if (r.has_res && !fold_res) rr = emit_res_conv(r, x, x2);
+            const TH out = emit_fused(h, nullptr, r.cout, r.cout, ch2, k2, bind.buf(r.has_res ? rr.buf : x.buf), -1, nullptr, nullptr);
+            pool.put(h.buf);
+            if (rr.buf >= 0) pool.put(rr.buf);
+            return out;
+        }
+        const TH y1 = emit_conv(x, x2, r.cin, w1, b1, r.cout, 5, 1, 2, false, x.L);
+        emit_gn(y1, k1.gamma, k1.beta, nullptr, tb_off);
+        const TH y2 = emit_conv(y1, nullptr, r.cout, w2, b2, r.cout, 5, 1, 2, false, x.L);
+        pool.put(y1.buf);
+        if (r.has_res) rr = emit_res_conv(r, x, x2);
+        emit_gn(y2, k2.gamma, k2.beta, bind.buf(r.has_res ? rr.buf : x.buf), -1);
+        if (rr.buf >= 0) pool.put(rr.buf);
+        return y2;
+    }
 
-        // a whole level in one launch (level.hip): RCB, RCB, resampling conv (+ the final Conv1dBlock); consumes two entries
-        // of inv.rcbs like two emit_rcb calls would, in the same order (so the time-bias row keeps its layout)
-        TH emit_level(const LevelInst* lv, TH xin, const TH* x2, const RawT& rs_w, const RawT& rs_b, bool want_skip, TH* skip_th) {
-            const RawRCB& r1 = inv.rcbs[rcb_idx++];
-            const RawRCB& r2 = inv.rcbs[rcb_idx++];
-            const int mode = lv->mode, Cc = r1.cout, Ll = xin.L, KX = std::max(lv->cin, 16);  // the first conv's K: stored input channels, padded to a whole K group
-            const int cin_store = xin.C + (x2 ? x2->C : 0);
-            POp o{};
-            o.kind = OP_LVL;
-            o.lv_inst = lv;
-            o.src1 = xin.buf;
-            o.C1 = xin.C;
-            o.src2 = x2 ? x2->buf : -1;
-            o.C2 = x2 ? x2->C : 0;
-            o.Lin = Ll;
-            o.Cout = Cc;
-            size_t* q = o.lvo;
-            // the level kernels read plain fragment streams with 16-sample tiles.  LevelP order: w11 w12 w21 w22 wrs wfin | b11 g11 be11 rb1 | b12 g12 be12 | b21 g21 be21 | b22 g22 be22 | brs | bfin gfin befin
-            q[0] = pk.conv_frag(params + r1.cb[0].w.off, params + r1.rw.off, Cc, r1.cin, KX, Ll, F_FRAG, 16);
-            q[1] = pk.conv_frag(params + r1.cb[1].w.off, nullptr, Cc, Cc, Cc, Ll, F_FRAG, 16);
-            q[2] = pk.conv_frag(params + r2.cb[0].w.off, nullptr, Cc, Cc, Cc, Ll, F_FRAG, 16);
-            q[3] = pk.conv_frag(params + r2.cb[1].w.off, nullptr, Cc, Cc, Cc, Ll, F_FRAG, 16);
-            q[4] = pk.resample_frag(params + rs_w.off, Cc, Cc, mode == LV_DOWN ? 3 : 4, mode != LV_DOWN, F_FRAG, 16);
-            q[5] = (mode == LV_UP_FINAL) ? pk.conv_frag(params + inv.final_cb.w.off, nullptr, Cc, Cc, Cc, 50, F_FRAG, 16) : 0;
-            q[6] = pk.vec(params + r1.cb[0].b.off, Cc), q[7] = pk.vec(params + r1.cb[0].gw.off, Cc), q[8] = pk.vec(params + r1.cb[0].gb.off, Cc);
-            q[9] = pk.vec(params + r1.rb.off, Cc);
-            q[10] = pk.vec(params + r1.cb[1].b.off, Cc), q[11] = pk.vec(params + r1.cb[1].gw.off, Cc), q[12] = pk.vec(params + r1.cb[1].gb.off, Cc);
-            q[13] = pk.vec(params + r2.cb[0].b.off, Cc), q[14] = pk.vec(params + r2.cb[0].gw.off, Cc), q[15] = pk.vec(params + r2.cb[0].gb.off, Cc);
-            q[16] = pk.vec(params + r2.cb[1].b.off, Cc), q[17] = pk.vec(params + r2.cb[1].gw.off, Cc), q[18] = pk.vec(params + r2.cb[1].gb.off, Cc);
-            q[19] = pk.vec(params + rs_b.off, Cc);
-            if (mode == LV_UP_FINAL) {
-                q[20] = pk.vec(params + inv.final_cb.b.off, Cc), q[21] = pk.vec(params + inv.final_cb.gw.off, Cc), q[22] = pk.vec(params + inv.final_cb.gb.off, Cc);
-            }
-            for (const RawRCB* r : {&r1, &r2}) {  // time-bias table columns, block order
-                (r == &r1 ? o.lv_tb1 : o.lv_tb2) = tb_cursor;
-                tb_cursor += Cc;
-                append(tw_all, params + r->tw.off, (size_t)Cc * td);
-                append(tb_all, params + r->tb.off, Cc);
-            }
-            o.lv_skip = -1;
-            if (want_skip) {
-                o.lv_skip = pool.get();
-                *skip_th = TH{o.lv_skip, Cc, Ll};
-            }
-            int Lout = (mode == LV_DOWN) ? (Ll - 1) / 2 + 1 : 2 * Ll;
-            if (mode != LV_DOWN && (Lout == 8 || Lout == 14 || Lout == 26)) Lout -= 1;
-            o.Lout = Lout;
-            o.dst = pool.get();
-            const double vp = (double)valid_pairs(Ll, Ll, 5, 1, 2, false);
-            const int k = mode == LV_DOWN ? 3 : 4;
-            o.fn = 2.0 * Ll * Cc * 5.0 * ((double)r1.cin + 3.0 * Cc) + 2.0 * Ll * Cc * (double)r1.cin +
-                   (mode == LV_DOWN ? 2.0 * Lout * Cc * (double)Cc * k : 2.0 * Ll * (double)Cc * Cc * k) + (mode == LV_UP_FINAL ? 2.0 * Lout * Cc * (double)Cc * 5 : 0.0);
-            o.fe = 2.0 * vp * Cc * ((double)cin_store + 3.0 * Cc) + 2.0 * Ll * Cc * (double)cin_store +
-                   2.0 * (double)valid_pairs(Ll, Lout, k, 2, 1, mode != LV_DOWN) * Cc * (double)Cc +
-                   (mode == LV_UP_FINAL ? 2.0 * (double)valid_pairs(Lout, Lout, 5, 1, 2, false) * Cc * (double)Cc : 0.0);
-            pops.push_back(o);
-            return TH{o.dst, Cc, Lout};
+    // a whole level in one launch (level.hip): RCB, RCB, resampling conv (+ the final Conv1dBlock); consumes two entries
+    // of inv.rcbs like two emit_rcb calls would, in the same order (so the time-bias row keeps its layout)
+    TH emit_level(const LevelInst* lv, TH xin, const TH* x2, const RawT& rs_w, const RawT& rs_b, bool want_skip, TH* skip_th) {
+        const RawRCB& r1 = inv.rcbs[rcb_idx++];
+        const RawRCB& r2 = inv.rcbs[rcb_idx++];
+        const int mode = lv->mode, Cc = r1.cout, Ll = xin.L, KX = std::max(lv->cin, 16);  // the first conv's K: stored input channels, padded to a whole K group
+        const bool fin = mode == LV_UP_FINAL;
+        const int cin_store = xin.C + (x2 ? x2->C : 0);
+        // the level kernels read plain fragment streams with 16-sample tiles
+        auto frag = [&](const RawT& w, const RawT* wres, int cin, int K, int L) {
+            return bind.w(pk.conv_frag(params + w.off, wres ? params + wres->off : nullptr, Cc, cin, K, L, F_FRAG, 16));
+        };
+        auto v = [&](const RawT& t) { return vec(t, Cc); };
+        LevelP c{};
+        set_src(c, xin, x2);
+        // the image holds the level's tensors in THIS order (statements run top to bottom; the packer appends)
+        c.w11 = frag(r1.cb[0].w, &r1.rw, r1.cin, KX, Ll);
+        c.w12 = frag(r1.cb[1].w, nullptr, Cc, Cc, Ll);
+        c.w21 = frag(r2.cb[0].w, nullptr, Cc, Cc, Ll);
+        c.w22 = frag(r2.cb[1].w, nullptr, Cc, Cc, Ll);
+        c.wrs = bind.w(pk.resample_frag(params + rs_w.off, Cc, Cc, mode == LV_DOWN ? 3 : 4, mode != LV_DOWN, F_FRAG, 16));
+        const float* none = bind.w(0);  // what the final block's arguments hold in the modes that have none: the image's base, never read
+        c.wfin = fin ? frag(inv.final_cb.w, nullptr, Cc, Cc, 50) : none;
+        c.b11 = v(r1.cb[0].b), c.g11 = v(r1.cb[0].gw), c.be11 = v(r1.cb[0].gb);
+        c.rb1 = v(r1.rb);
+        c.b12 = v(r1.cb[1].b), c.g12 = v(r1.cb[1].gw), c.be12 = v(r1.cb[1].gb);
+        c.b21 = v(r2.cb[0].b), c.g21 = v(r2.cb[0].gw), c.be21 = v(r2.cb[0].gb);
+        c.b22 = v(r2.cb[1].b), c.g22 = v(r2.cb[1].gw), c.be22 = v(r2.cb[1].gb);
+        c.brs = v(rs_b);
+        c.bfin = fin ? v(inv.final_cb.b) : none, c.gfin = fin ? v(inv.final_cb.gw) : none, c.befin = fin ? v(inv.final_cb.gb) : none;
+        Op o{OP_LVL};
+        o.lv_inst = lv;
+        o.tb1 = time_bias(r1), o.tb2 = time_bias(r2);  // time-bias table columns, block order
+        if (want_skip) {
+            *skip_th = TH{pool.get(), Cc, Ll};
+            c.skip_out = bind.buf(skip_th->buf);
         }
+        const int Lout = mode == LV_DOWN ? down_length(Ll) : up_length(Ll);
+        const TH out = new_out(Cc, Ll, Lout);
+        c.out = bind.buf(out.buf);
+        const double vp = (double)valid_pairs(Ll, Ll, 5, 1, 2, false);
+        const int k = mode == LV_DOWN ? 3 : 4;
+        o.flops_nominal = 2.0 * Ll * Cc * 5.0 * ((double)r1.cin + 3.0 * Cc) + 2.0 * Ll * Cc * (double)r1.cin +
+                          (mode == LV_DOWN ? 2.0 * Lout * Cc * (double)Cc * k : 2.0 * Ll * (double)Cc * Cc * k) + (fin ? 2.0 * Lout * Cc * (double)Cc * 5 : 0.0);
+        o.flops_exec = 2.0 * vp * Cc * ((double)cin_store + 3.0 * Cc) + 2.0 * Ll * Cc * (double)cin_store +
+                       2.0 * (double)valid_pairs(Ll, Lout, k, 2, 1, mode != LV_DOWN) * Cc * (double)Cc +
+                       (fin ? 2.0 * (double)valid_pairs(Lout, Lout, 5, 1, 2, false) * Cc * (double)Cc : 0.0);
+        o.p = c;
+        push(o);
+        return out;
+    }
+    // this level and the one behind it as one launch (level2_kernel): the first one's output only ever exists in LDS - no tap
+    void pair_or_tap(const LevelInst* lv, const LevelInst* next, int which, TH x) {
+        if (const Level2Inst* pair = choose_pair(sw, lv, next)) {
+            ops.back().lv_pair = pair;
+            op_kernel_name(ops.back(), ops.back().name);
+        } else {
+            tap(which, x);
+        }
+    }
 
     // the walk itself: down path, middle, up path, final block + head, time-embedding tensors
-    int plan() {
-
+    int walk() {
         TH x{pool.get(), CP0, N};
         x_in_buf = x.buf;
         pool.pin(x_in_buf);  // written by the sampler kernels between forwards: never recycled as an activation
         std::vector<TH> skips;
+        bool final_fused = false;
         for (int i = 0; i < nd; ++i) {
             if (const LevelInst* lv = (i != nd - 1) ? choose_level(sw, LV_DOWN, dm[i + 1], x.L, x.C, 0) : nullptr) {
                 // the skip of level 0 is never consumed (5 up-samplers for 6 skips, temporalunet.py:31-32,66-67): not even written
@@ -1209,12 +1223,7 @@ struct LayerPlan {
                 pool.put(x.buf);
                 skips.push_back(sk);
                 x = xo;
-                // merged with the next down level (level2_kernel): this level's output only ever exists in LDS - no tap
-                pops.back().lv_pair = choose_pair(sw, lv, i + 1 < nd - 1 ? choose_level(sw, LV_DOWN, dm[i + 2], x.L, x.C, 0) : nullptr);
-                if (!pops.back().lv_pair) {
-                    tapr.push_back({i, x.buf, x.C, x.L});
-                    pool.pin(x.buf);
-                }
+                pair_or_tap(lv, i + 1 < nd - 1 ? choose_level(sw, LV_DOWN, dm[i + 2], x.L, x.C, 0) : nullptr, i, x);
                 continue;
             }
             TH a = emit_rcb(x, nullptr);
@@ -1222,22 +1231,8 @@ struct LayerPlan {
             TH b = emit_rcb(a, nullptr);
             pool.put(a.buf);
             skips.push_back(b);
-            if (i != nd - 1) {
-                int Lout = (b.L - 1) / 2 + 1;
-                if (const ConvChoice ch = choose_conv(sw, WK_DOWN, dm[i + 1], b.L, b.C, 0); ch.row[0]) {
-                    size_t w = pk.resample_frag(params + inv.down_w[i].off, dm[i + 1], dm[i + 1], 3, false, ch.stream, ch.row[0]->ms);
-                    size_t bb = pk.vec(params + inv.down_b[i].off, dm[i + 1]);
-                    x = emit_wrs(b, w, bb, dm[i + 1], ch.row[0], 3, Lout);
-                } else {
-                    size_t w = pk.conv(params + inv.down_w[i].off, dm[i + 1], dm[i + 1], 3, dm[i + 1]);
-                    size_t bb = pk.vec(params + inv.down_b[i].off, dm[i + 1]);
-                    x = emit_conv(b, nullptr, dm[i + 1], w, bb, dm[i + 1], 3, 2, 1, false, Lout);
-                }
-            } else {
-                x = b;
-            }
-            tapr.push_back({i, x.buf, x.C, x.L});
-            pool.pin(x.buf);
+            x = (i != nd - 1) ? emit_resampler(WK_DOWN, b, inv.down_w[i], inv.down_b[i], down_length(b.L)) : b;
+            tap(i, x);
         }
         {
             // middle: input is skips.back() (same buffer, must stay alive for the up path)
@@ -1245,64 +1240,43 @@ struct LayerPlan {
             TH b = emit_rcb(a, nullptr);
             pool.put(a.buf);
             x = b;
-            tapr.push_back({100, x.buf, x.C, x.L});
-            pool.pin(x.buf);
+            tap(100, x);
         }
         for (int j = 0, i = nd; i > 1; --i, ++j) {
             TH sk = skips.back();
             skips.pop_back();
             EDMP_REQUIRE(sk.L == x.L && sk.C == x.C, "skip/upsample shape mismatch at up level %d (L %d vs %d)", j, sk.L, x.L);
             EDMP_REQUIRE(sk.buf >= 0, "up level %d consumes a skip tensor that the fused down level did not write", j);
-            {
-                const bool last = (i == 2);
-                const int mode = (last && dm[1] == dm[i - 1] && 2 * x.L == N) ? LV_UP_FINAL : LV_UP;
-                if (const LevelInst* lv = choose_level(sw, mode, dm[i - 1], x.L, x.C, sk.C)) {
-                    TH xo = emit_level(lv, x, &sk, inv.up_w[j], inv.up_b[j], false, nullptr);
-                    pool.put(x.buf);
-                    pool.put(sk.buf);
-                    x = xo;
-                    if (mode == LV_UP_FINAL) {
-                        final_fused = true;  // the level kernel already applied final_conv.0
-                    } else {
-                        // merged with the last up level (level2_kernel): this level's output only ever exists in LDS - no tap
-                        const bool next_is_final = i == 3 && !skips.empty() && dm[1] == dm[i - 2] && 2 * x.L == N;
-                        pops.back().lv_pair = choose_pair(sw, lv, next_is_final ? choose_level(sw, LV_UP_FINAL, dm[i - 2], x.L, x.C, skips.back().C) : nullptr);
-                        if (!pops.back().lv_pair) {
-                            tapr.push_back({200 + j, x.buf, x.C, x.L});
-                            pool.pin(x.buf);
-                        }
-                    }
-                    continue;
+            const int mode = (i == 2 && dm[1] == dm[i - 1] && 2 * x.L == N) ? LV_UP_FINAL : LV_UP;
+            if (const LevelInst* lv = choose_level(sw, mode, dm[i - 1], x.L, x.C, sk.C)) {
+                TH xo = emit_level(lv, x, &sk, inv.up_w[j], inv.up_b[j], false, nullptr);
+                pool.put(x.buf);
+                pool.put(sk.buf);
+                x = xo;
+                if (mode == LV_UP_FINAL) {
+                    final_fused = true;  // the level kernel already applied final_conv.0
+                } else {
+                    const bool next_is_final = i == 3 && !skips.empty() && dm[1] == dm[i - 2] && 2 * x.L == N;
+                    pair_or_tap(lv, next_is_final ? choose_level(sw, LV_UP_FINAL, dm[i - 2], x.L, x.C, skips.back().C) : nullptr, 200 + j, x);
                 }
+                continue;
             }
             TH a = emit_rcb(x, &sk);
             pool.put(x.buf);
             pool.put(sk.buf);
             TH b = emit_rcb(a, nullptr);
             pool.put(a.buf);
-            int Lout = 2 * b.L;
-            if (Lout == 8 || Lout == 14 || Lout == 26) Lout -= 1;  // crop rule, temporalunet.py:70-71
-            if (const ConvChoice ch = choose_conv(sw, WK_UP, dm[i - 1], b.L, b.C, 0); ch.row[0]) {
-                size_t w = pk.resample_frag(params + inv.up_w[j].off, dm[i - 1], dm[i - 1], 4, true, ch.stream, ch.row[0]->ms);
-                size_t bb = pk.vec(params + inv.up_b[j].off, dm[i - 1]);
-                x = emit_wrs(b, w, bb, dm[i - 1], ch.row[0], 4, Lout);
-            } else {
-                size_t w = pk.convT(params + inv.up_w[j].off, dm[i - 1], dm[i - 1], 4);
-                size_t bb = pk.vec(params + inv.up_b[j].off, dm[i - 1]);
-                x = emit_conv(b, nullptr, dm[i - 1], w, bb, dm[i - 1], 4, 2, 1, true, Lout);
-            }
+            x = emit_resampler(WK_UP, b, inv.up_w[j], inv.up_b[j], up_length(b.L));
             pool.put(b.buf);
-            tapr.push_back({200 + j, x.buf, x.C, x.L});
-            pool.pin(x.buf);
+            tap(200 + j, x);
         }
         EDMP_REQUIRE(x.L == N, "decoder output length %d != horizon %d", x.L, N);
         // final Conv1dBlock + 1x1 head
         if (!final_fused) {
-            size_t w = pk.conv(params + inv.final_cb.w.off, dm[1], dm[1], 5, dm[1]);
-            size_t b = pk.vec(params + inv.final_cb.b.off, dm[1]);
-            size_t g = pk.vec(params + inv.final_cb.gw.off, dm[1]), be = pk.vec(params + inv.final_cb.gb.off, dm[1]);
+            const size_t w = pk.conv(params + inv.final_cb.w.off, dm[1], dm[1], 5, dm[1]), b = pk.vec(params + inv.final_cb.b.off, dm[1]);
+            const float *g = vec(inv.final_cb.gw, dm[1]), *be = vec(inv.final_cb.gb, dm[1]);
             TH y = emit_conv(x, nullptr, dm[1], w, b, dm[1], 5, 1, 2, false, N);
-            emit_gn(y, g, be, -1, -1);
+            emit_gn(y, g, be, nullptr, -1);
             pool.put(x.buf);
             x = y;
         }
@@ -1315,123 +1289,20 @@ struct LayerPlan {
         o_t3w = pk.vec(params + inv.t3w.off, 4 * td * td), o_t3b = pk.vec(params + inv.t3b.off, td);
         o_tw = pk.vec(tw_all.data(), (int)tw_all.size()), o_tb = pk.vec(tb_all.data(), (int)tb_all.size());
         head_buf = x.buf;
-        for (auto& o : pops) EDMP_REQUIRE(!((o.kind == OP_GN || o.kind == OP_RCB) && o.res == -2), "identity residual over a channel concat is not supported");
-        // a Conv1dBlock instance listed without the twin that folds the residual in
-        for (auto& o : pops) EDMP_REQUIRE(o.kind != OP_RCB || o.inst, "no fused conv+GroupNorm kernel for Cout=%d L=%d", o.Cout, o.Lin);
-        // the generic GroupNorm keeps a group in registers (gn_mish_kernel, at most 8 x 64 elements): refuse the architecture
-        // here, at load, rather than in the middle of its first forward (launch_gn keeps the same check)
-        for (auto& o : pops)
-            EDMP_REQUIRE(!(o.kind == OP_GN && (o.C / 8) * o.L > 512), "GroupNorm group of %d elements exceeds the register-resident limit (512)", (o.C / 8) * o.L);
+        EDMP_REQUIRE(!identity_over_concat, "identity residual over a channel concat is not supported");
+        EDMP_REQUIRE(!no_twin_cout, "no fused conv+GroupNorm kernel for Cout=%d L=%d", no_twin_cout, no_twin_L);
+        // refuse the architecture here, at load, rather than in the middle of its first forward (launch_gn keeps the same check)
+        EDMP_REQUIRE(!gn_group, "GroupNorm group of %d elements exceeds the register-resident limit (512)", gn_group);
+        // a merged pair is ONE launch, attributed to its first op: that op carries the pair's FLOPs (the model totals are unaffected)
+        for (size_t i = 0; i < ops.size(); ++i)
+            if (second_of_pair(ops, i)) {
+                Op &a = ops[i - 1], &b = ops[i];
+                a.flops_nominal += b.flops_nominal, a.flops_exec += b.flops_exec, a.flops_direct += b.flops_direct;
+                b.flops_nominal = b.flops_exec = b.flops_direct = 0.0;
+            }
         return EDMP_OK;
     }
 };
-
-// ---- step 3: buffer ids / image offsets of the plan -> device pointers of the loaded model (the layer program unet_run_program walks)
-static void resolve_program(UNet* u, const LayerPlan& pl) {
-    const std::vector<POp>& pops = pl.pops;
-    for (auto& o : pops) {
-        Op op{};
-        op.kind = o.kind;
-        op.tb_off = -1;
-        if (o.kind == OP_CONV) {
-            ConvP& c = op.cv;
-            c.src1 = u->bufs[o.src1];
-            c.src2 = o.src2 >= 0 ? u->bufs[o.src2] : nullptr;
-            c.C1 = o.C1;
-            c.C2 = o.C2;
-            c.Lin = o.Lin;
-            c.Lout = o.Lout;
-            c.ntaps = o.ntaps;
-            c.stride = o.stride;
-            c.pad = o.pad;
-            c.transposed = o.transposed;
-            c.W = u->wpack + o.w;
-            c.bias = u->wpack + o.b;
-            c.dst = u->bufs[o.dst];
-            c.Cout = o.Cout;
-        } else if (o.kind == OP_LVL) {
-            LevelP& c = op.lv;
-            const float* W0 = u->wpack;
-            c.src1 = u->bufs[o.src1];
-            c.src2 = o.src2 >= 0 ? u->bufs[o.src2] : nullptr;
-            c.C1 = o.C1;
-            c.C2 = o.C2;
-            c.w11 = W0 + o.lvo[0], c.w12 = W0 + o.lvo[1], c.w21 = W0 + o.lvo[2], c.w22 = W0 + o.lvo[3], c.wrs = W0 + o.lvo[4], c.wfin = W0 + o.lvo[5];
-            c.b11 = W0 + o.lvo[6], c.g11 = W0 + o.lvo[7], c.be11 = W0 + o.lvo[8], c.rb1 = W0 + o.lvo[9];
-            c.b12 = W0 + o.lvo[10], c.g12 = W0 + o.lvo[11], c.be12 = W0 + o.lvo[12];
-            c.b21 = W0 + o.lvo[13], c.g21 = W0 + o.lvo[14], c.be21 = W0 + o.lvo[15];
-            c.b22 = W0 + o.lvo[16], c.g22 = W0 + o.lvo[17], c.be22 = W0 + o.lvo[18];
-            c.brs = W0 + o.lvo[19];
-            c.bfin = W0 + o.lvo[20], c.gfin = W0 + o.lvo[21], c.befin = W0 + o.lvo[22];
-            c.tb1 = c.tb2 = nullptr;
-            c.skip_out = o.lv_skip >= 0 ? u->bufs[o.lv_skip] : nullptr;
-            c.out = u->bufs[o.dst];
-            op.lv_inst = o.lv_inst;
-            op.lv_pair = o.lv_pair;
-            op.lv_tb1 = o.lv_tb1;
-            op.lv_tb2 = o.lv_tb2;
-        } else if (o.kind == OP_WRS) {
-            RcbP& c = op.rc;
-            c.src1 = u->bufs[o.src1];
-            c.src2 = nullptr;
-            c.C1 = o.C1;
-            c.C2 = 0;
-            c.W = u->wpack + o.w;
-            c.bias = u->wpack + o.b;
-            c.dst = u->bufs[o.dst];
-            c.Cout = o.Cout;
-            op.inst = o.inst;
-        } else if (o.kind == OP_RCB) {
-            RcbP& c = op.rc;
-            c.src1 = u->bufs[o.src1];
-            c.src2 = o.src2 >= 0 ? u->bufs[o.src2] : nullptr;
-            c.C1 = o.C1;
-            c.C2 = o.C2;
-            c.W = u->wpack + o.w;
-            c.bias = u->wpack + o.b;
-            c.res_out = o.res_out >= 0 ? u->bufs[o.res_out] : nullptr;
-            c.res_bias = o.res_out >= 0 ? u->wpack + o.br : nullptr;
-            c.gamma = u->wpack + o.gamma;
-            c.beta = u->wpack + o.beta;
-            c.add_tb = nullptr;
-            c.add_res = o.res >= 0 ? u->bufs[o.res] : nullptr;
-            c.dst = u->bufs[o.dst];
-            c.Cout = o.Cout;
-            op.inst = o.inst;
-            op.tb_off = o.tb_off;
-        } else {
-            GnP& g = op.gn;
-            g.y = u->bufs[o.y];
-            g.gamma = u->wpack + o.gamma;
-            g.beta = u->wpack + o.beta;
-            g.add_res = o.res >= 0 ? u->bufs[o.res] : nullptr;
-            g.add_tbias = nullptr;
-            g.L = o.L;
-            g.C = o.C;
-            op.tb_off = o.tb_off;
-        }
-        op.flops_nominal = o.fn;  // (zero for an OP_GN)
-        op.flops_exec = o.fe;
-        op.flops_direct = o.fd > 0 ? o.fd : o.fe;
-        u->flops_nominal += op.flops_nominal;
-        u->flops_exec += op.flops_exec;
-        u->flops_direct += op.flops_direct;
-        if (op.inst && op.inst->bf3) {  // six exact partial products per fp32 product, issued on the bf16 pipe
-            op.flops_bf16 = 6.0 * op.flops_direct;
-            u->flops_bf16 += op.flops_bf16;
-            u->flops_f32_moved += op.flops_exec;
-        }
-        op_kernel_name(o, op.name);
-        u->prog.push_back(op);
-    }
-    // a merged pair is ONE launch, attributed to its first op: that op carries the pair's FLOPs (the model totals are unaffected)
-    for (size_t i = 0; i + 1 < u->prog.size(); ++i)
-        if (u->prog[i].kind == OP_LVL && u->prog[i].lv_pair) {
-            Op &a = u->prog[i], &b = u->prog[i + 1];
-            a.flops_nominal += b.flops_nominal, a.flops_exec += b.flops_exec, a.flops_direct += b.flops_direct;
-            b.flops_nominal = b.flops_exec = b.flops_direct = 0.0;
-        }
-}
 
 static int check_desc(const edmp_unet_desc* desc) {
     EDMP_REQUIRE(desc->n_levels >= 2 && desc->n_levels <= EDMP_MAX_LEVELS, "n_levels out of range");
@@ -1442,19 +1313,18 @@ static int check_desc(const edmp_unet_desc* desc) {
 }
 
 // builds the layer program + device weight image.  packed == nullptr: repack `params` (state-dict order) on the host;
-// otherwise `packed` IS the device image (edmp_unet_read_packed of the same architecture): only the layout is computed
+// otherwise `packed` IS the device image (edmp_unet_read_packed of the same architecture): only the layout is computed.
+// The walk runs twice under one BuildSwitches value: pass 1 layout-only and unbound (what to allocate, every refusal), pass 2 bound to
+// the image and the buffers that then exist (the program, the taps; it packs unless `packed` is given).
 static int unet_build(edmp_ctx* ctx, const edmp_unet_desc* desc, const float* params, int64_t n_params, int max_batch, const float* packed,
                       int64_t n_packed, int packed_layout) {
     ctx->epoch++;
     if (int rc = check_desc(desc)) return rc;
     EDMP_REQUIRE(max_batch >= 1, "max_batch must be positive");
-    RawNet inv = inventory(*desc);
-    static const float no_params = 0.0f;
-    if (packed) {  // layout-only pass: the builder computes offsets from `params` but never reads through it (Packer::dry)
-        params = &no_params;
-        n_params = inv.total;
-    }
-    EDMP_REQUIRE(inv.total == n_params, "parameter blob has %lld floats, architecture needs %lld", (long long)n_params, (long long)inv.total);
+    const BuildSwitches sw = BuildSwitches::read();
+    // ---- pass 1: the layout
+    Walk lay(desc, nullptr, true, sw, Binder{});
+    EDMP_REQUIRE(packed || lay.inv.total == n_params, "parameter blob has %lld floats, architecture needs %lld", (long long)n_params, (long long)lay.inv.total);
     EDMP_HIP_CHECK(hipSetDevice(ctx->device));
     if (ctx->unet) {
         unet_destroy(ctx->unet);
@@ -1466,30 +1336,25 @@ static int unet_build(edmp_ctx* ctx, const edmp_unet_desc* desc, const float* pa
     UNet* u = guard.get();
     u->desc = *desc;
     u->max_batch = max_batch;
-    LayerPlan pl(desc, params, packed != nullptr);
-    if (int rc = pl.plan()) return rc;
-    u->tb_stride = pl.tb_cursor;
-    // ---- step 2: device image, activation buffers, time-bias table
-    size_t max_lc = (size_t)pl.N * pl.CP0;
-    for (auto& o : pl.pops)
-        if (o.kind == OP_CONV || o.kind == OP_RCB || o.kind == OP_WRS || o.kind == OP_LVL) max_lc = std::max(max_lc, (size_t)std::max(o.Lout, o.Lin) * o.Cout);
-    u->buf_cap = max_lc * (size_t)max_batch;
-    u->layout = pl.pk.layout_id(kPackVersion);
+    if (int rc = lay.walk()) return rc;
+    u->tb_stride = lay.tb_cursor;
+    u->buf_cap = lay.max_lc * (size_t)max_batch;
+    u->layout = lay.pk.layout_id(kPackVersion);
+    u->wpack_floats = lay.pk.total;
     if (packed && packed_layout != u->layout) {
         set_error("packed weight image has layout id %d, this library with the current builder switches packs %d: re-pack from the state dict", packed_layout, u->layout);
         return EDMP_ERR_LAYOUT;
     }
-    if (packed && (int64_t)pl.pk.total != n_packed) {
-        set_error("packed weight image has %lld floats, this architecture / library layout needs %zu", (long long)n_packed, pl.pk.total);
+    if (packed && (int64_t)u->wpack_floats != n_packed) {
+        set_error("packed weight image has %lld floats, this architecture / library layout needs %zu", (long long)n_packed, u->wpack_floats);
         return EDMP_ERR_LAYOUT;
     }
-    if (hipMalloc((void**)&u->wpack, pl.pk.total * sizeof(float)) != hipSuccess) {
-        set_error("hipMalloc of %zu weight bytes failed", pl.pk.total * sizeof(float));
+    // ---- device image, activation buffers, time-bias table
+    if (hipMalloc((void**)&u->wpack, u->wpack_floats * sizeof(float)) != hipSuccess) {
+        set_error("hipMalloc of %zu weight bytes failed", u->wpack_floats * sizeof(float));
         return EDMP_ERR_HIP;
     }
-    u->wpack_floats = pl.pk.total;
-    EDMP_HIP_CHECK(hipMemcpy(u->wpack, packed ? packed : pl.pk.host.data(), pl.pk.total * sizeof(float), hipMemcpyHostToDevice));
-    for (int i = 0; i < pl.pool.n; ++i) {
+    for (int i = 0; i < lay.pool.n; ++i) {
         float* p = nullptr;
         if (hipMalloc((void**)&p, u->buf_cap * sizeof(float)) != hipSuccess) {
             set_error("hipMalloc of activation buffer %d (%zu bytes) failed", i, u->buf_cap * sizeof(float));
@@ -1498,6 +1363,12 @@ static int unet_build(edmp_ctx* ctx, const edmp_unet_desc* desc, const float* pa
         u->bufs.push_back(p);
     }
     EDMP_HIP_CHECK(hipMalloc((void**)&u->tbias, (size_t)desc->T * u->tb_stride * sizeof(float)));
+    // ---- pass 2: the same walk, bound
+    Walk pl(desc, params, packed != nullptr, sw, Binder{u->wpack, &u->bufs});
+    if (int rc = pl.walk()) return rc;
+    EDMP_REQUIRE(pl.pk.layout_id(kPackVersion) == u->layout && pl.pk.total == u->wpack_floats && pl.pool.n == lay.pool.n,
+                 "the two passes of the model build disagree: layout id %d / %d, %zu / %zu floats", u->layout, pl.pk.layout_id(kPackVersion), u->wpack_floats, pl.pk.total);
+    EDMP_HIP_CHECK(hipMemcpy(u->wpack, packed ? packed : pl.pk.host.data(), u->wpack_floats * sizeof(float), hipMemcpyHostToDevice));
     {
         size_t sm = (size_t)(6 * pl.td) * sizeof(float);
         hipLaunchKernelGGL(time_table_kernel, dim3(desc->T), dim3(256), sm, ctx->stream, u->wpack + pl.o_t1w, u->wpack + pl.o_t1b,
@@ -1505,7 +1376,15 @@ static int unet_build(edmp_ctx* ctx, const edmp_unet_desc* desc, const float* pa
         EDMP_HIP_CHECK(hipGetLastError());
         EDMP_HIP_CHECK(hipStreamSynchronize(ctx->stream));
     }
-    resolve_program(u, pl);
+    u->prog = std::move(pl.ops);
+    u->taps = std::move(pl.taps);
+    for (const Op& op : u->prog) {
+        u->flops_nominal += op.flops_nominal;  // (zero for an OP_GN)
+        u->flops_exec += op.flops_exec;
+        u->flops_direct += op.flops_direct;
+        u->flops_bf16 += op.flops_bf16;
+        if (op.inst && op.inst->bf3) u->flops_f32_moved += op.flops_exec;
+    }
     if (int rc = check_bf3_cu_claim(u)) return rc;
     u->flops_nominal += pl.head_flops;
     u->flops_exec += pl.head_flops;
@@ -1515,7 +1394,6 @@ static int unet_build(edmp_ctx* ctx, const edmp_unet_desc* desc, const float* pa
     u->head_w = u->wpack + pl.hw;
     u->head_b = u->wpack + pl.hb;
     u->head_cin = pl.dm[1];
-    for (auto& t : pl.tapr) u->taps.push_back({t.which, u->bufs[t.buf], t.C, t.L});
     ctx->unet = guard.release();
     return EDMP_OK;
 }
@@ -1530,16 +1408,15 @@ extern "C" int edmp_unet_load_packed(edmp_ctx* ctx, const edmp_unet_desc* desc, 
     return unet_build(ctx, desc, nullptr, 0, max_batch, packed, n_packed, layout);
 }
 
-// host-only: the layout-only plan (what loading a packed image computes) under the current builder switches, no device work
+// host-only: pass 1 of a model build alone (the layout-only, unbound walk) under the current builder switches, no device work
 extern "C" int edmp_unet_plan_describe(const edmp_unet_desc* desc, int cap, int* n_ops, char* names, int* layout, int64_t* n_packed) {
     EDMP_REQUIRE(desc && n_ops, "edmp_unet_plan_describe: null argument");
     if (int rc = check_desc(desc)) return rc;
-    static const float no_params = 0.0f;
-    LayerPlan pl(desc, &no_params, true);
-    if (int rc = pl.plan()) return rc;
-    const int n = (int)pl.pops.size();
+    Walk pl(desc, nullptr, true, BuildSwitches::read(), Binder{});
+    if (int rc = pl.walk()) return rc;
+    const int n = (int)pl.ops.size();
     *n_ops = n;
-    for (int i = 0; names && i < n && i < cap; ++i) op_kernel_name(pl.pops[i], names + (size_t)i * 64);
+    for (int i = 0; names && i < n && i < cap; ++i) memcpy(names + (size_t)i * 64, pl.ops[i].name, 64);
     if (layout) *layout = pl.pk.layout_id(kPackVersion);
     if (n_packed) *n_packed = (int64_t)pl.pk.total;
     return EDMP_OK;
@@ -1560,6 +1437,18 @@ extern "C" int edmp_unet_read_packed(edmp_ctx* ctx, float* out_host, int64_t cap
 }
 
 namespace edmp {
+// an event pair for a bracket: a recycled one of Prof::pool, or a new one
+static int prof_events(Prof& pf, Prof::Pend& e) {
+    if (!pf.pool.empty()) {
+        e.a = pf.pool.back().first;
+        e.b = pf.pool.back().second;
+        pf.pool.pop_back();
+        return EDMP_OK;
+    }
+    EDMP_HIP_CHECK(hipEventCreate(&e.a));
+    EDMP_HIP_CHECK(hipEventCreate(&e.b));
+    return EDMP_OK;
+}
 // shared with sampler.hip: run the forward on the context's stream
 // run the layer program on u->x_in ([B][N][8], already filled); leaves the head input in u->h_last
 // `tail` (device-resident loop): if the program ends with the fused final level (LV_UP_FINAL, 32 channels into the head) the
@@ -1575,19 +1464,21 @@ int unet_run_program(edmp_ctx* ctx, int B, int t, const TailP* tail, bool* tail_
     Prof& pf = ctx->prof;
     Prof::Pend whole{nullptr, nullptr, -1};
     if (pf.on == 2) {  // one bracket around the whole program: the conv family's time with no per-launch event overhead
-        if (!pf.pool.empty()) {
-            whole.a = pf.pool.back().first;
-            whole.b = pf.pool.back().second;
-            pf.pool.pop_back();
-        } else {
-            EDMP_HIP_CHECK(hipEventCreate(&whole.a));
-            EDMP_HIP_CHECK(hipEventCreate(&whole.b));
-        }
+        if (int rc = prof_events(pf, whole)) return rc;
         EDMP_HIP_CHECK(hipEventRecord(whole.a, main_stream));
     }
+    const std::vector<Op>& prog = u->prog;
+    // a level's launch parameters at this batch and step
+    auto level_params = [&](const Op& o) {
+        LevelP p = o.lv();
+        p.B = B;
+        p.tail.rps = tail ? tail->rps : 0;  // a scene batch: the workgroups are dealt scene by scene (level.hip)
+        p.tb1 = trow + o.tb1, p.tb2 = trow + o.tb2;
+        return p;
+    };
     // the tail of the reverse step runs inside the last level's launch when that level is the program's last op (LV_UP_FINAL, 32 channels)
-    auto fuse_step_tail = [&](LevelP& p, const Op& o, int index, bool out_is_head_input) {
-        if (tail && tail_done && o.lv_inst->mode == LV_UP_FINAL && index + 1 == (int)u->prog.size() && u->head_cin == 32 && tail->N == u->desc.horizon && tail->C <= 8 && out_is_head_input) {
+    auto fuse_step_tail = [&](LevelP& p, const Op& o, size_t index) {
+        if (tail && tail_done && o.lv_inst->mode == LV_UP_FINAL && index + 1 == prog.size() && u->head_cin == 32 && tail->N == u->desc.horizon && tail->C <= 8 && p.out == u->h_last) {
             p.tail = *tail;
             p.tail.on = 1;
             p.tail.w = u->head_w;
@@ -1595,64 +1486,45 @@ int unet_run_program(edmp_ctx* ctx, int B, int t, const TailP* tail, bool* tail_
             *tail_done = true;
         }
     };
-    int op_index = -1, skip_index = -1;
-    for (const Op& op : u->prog) {
-        ++op_index;
-        if (op_index == skip_index) continue;  // the second level of a merged pair: ran inside the previous launch
+    for (size_t i = 0; i < prog.size(); ++i) {
+        const Op& op = prog[i];
+        if (second_of_pair(prog, i)) continue;  // ran inside the previous launch
         hipStream_t s = main_stream;
-        Prof::Pend ev{nullptr, nullptr, op_index};
-        const bool timed = pf.on == 1 && op.kind != OP_GN;
+        Prof::Pend ev{nullptr, nullptr, (int)i};
+        const bool timed = pf.on == 1 && own_launch(prog, i);
         if (timed) {
-            if (!pf.pool.empty()) {
-                ev.a = pf.pool.back().first;
-                ev.b = pf.pool.back().second;
-                pf.pool.pop_back();
-            } else {
-                EDMP_HIP_CHECK(hipEventCreate(&ev.a));
-                EDMP_HIP_CHECK(hipEventCreate(&ev.b));
-            }
+            if (int rc = prof_events(pf, ev)) return rc;
             EDMP_HIP_CHECK(hipEventRecord(ev.a, s));
         }
         int rc = EDMP_OK;
         if (op.kind == OP_RCB) {
-            RcbP p = op.rc;
+            RcbP p = op.rc();
             p.B = B;
-            p.add_tb = op.tb_off >= 0 ? trow + op.tb_off : nullptr;
+            p.add_tb = op.tb1 >= 0 ? trow + op.tb1 : nullptr;
             EDMP_REQUIRE(!(p.add_tb && p.add_res), "fused conv block: a launch adds the time bias (conv1) or the residual (conv2), not both");
             rc = op.inst->launch(p, s, nullptr);
         } else if (op.kind == OP_LVL && op.lv_pair) {
-            const Op& nx = u->prog[op_index + 1];
-            LevelP pa = op.lv, pb = nx.lv;
-            pa.B = pb.B = B;
-            pa.tail.rps = pb.tail.rps = tail ? tail->rps : 0;  // a scene batch: the workgroups are dealt scene by scene (level.hip)
-            const bool out_is_head_input = pb.out == u->h_last;
+            const Op& nx = prog[i + 1];
+            LevelP pa = level_params(op), pb = level_params(nx);
             pa.out = nullptr, pb.src1 = nullptr;  // (level B's first input half arrives in LDS)
-            pa.tb1 = trow + op.lv_tb1, pa.tb2 = trow + op.lv_tb2;
-            pb.tb1 = trow + nx.lv_tb1, pb.tb2 = trow + nx.lv_tb2;
-            fuse_step_tail(pb, nx, op_index + 1, out_is_head_input);
+            fuse_step_tail(pb, nx, i + 1);
             rc = op.lv_pair->launch(pa, pb, s);
-            skip_index = op_index + 1;
         } else if (op.kind == OP_LVL) {
-            LevelP p = op.lv;
-            p.B = B;
-            p.tail.rps = tail ? tail->rps : 0;
-            const bool out_is_head_input = p.out == u->h_last;
-            p.tb1 = trow + op.lv_tb1;
-            p.tb2 = trow + op.lv_tb2;
-            fuse_step_tail(p, op, op_index, out_is_head_input);
+            LevelP p = level_params(op);
+            fuse_step_tail(p, op, i);
             rc = op.lv_inst->launch(p, s);
         } else if (op.kind == OP_WRS) {
-            RcbP p = op.rc;
+            RcbP p = op.rc();
             p.B = B;
             rc = op.inst->launch(p, s, nullptr);
         } else if (op.kind == OP_CONV) {
-            ConvP p = op.cv;
+            ConvP p = op.cv();
             p.B = B;
             launch_conv(p, s);
         } else {
-            GnP g = op.gn;
+            GnP g = op.gn();
             g.B = B;
-            g.add_tbias = op.tb_off >= 0 ? trow + op.tb_off : nullptr;
+            g.add_tbias = op.tb1 >= 0 ? trow + op.tb1 : nullptr;
             rc = launch_gn(g, s);
         }
         if (rc) return rc;
@@ -1681,14 +1553,7 @@ int prof_fold(edmp_ctx* ctx) {
         EDMP_HIP_CHECK(hipEventElapsedTime(&ms, e.a, e.b));
         p.conv_ms += ms;
         if (e.op < 0) {  // whole-program bracket: counts every launch of the program
-            if (ctx->unet)
-            {
-                bool second_of_pair = false;  // (the second level of a merged pair is not a launch of its own)
-                for (const Op& op : ctx->unet->prog) {
-                    p.conv_launches += (op.kind != OP_GN && !second_of_pair) ? 1 : 0;
-                    second_of_pair = op.kind == OP_LVL && op.lv_pair;
-                }
-            }
+            for (size_t i = 0; i < nops; ++i) p.conv_launches += own_launch(ctx->unet->prog, i) ? 1 : 0;
         } else {
             p.conv_launches += 1;
         }
