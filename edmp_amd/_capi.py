@@ -12,6 +12,7 @@ MAX_LEVELS = 8
 MAX_SCENES = 16  # EDMP_MAX_SCENES
 MAX_OBSTACLES = 64  # EDMP_MAX_OBSTACLES
 MAX_SPHERES = 128  # EDMP_MAX_SPHERES
+MAX_SWEEP_SUBSTEPS = 64  # EDMP_MAX_SWEEP_SUBSTEPS
 
 
 class UNetDesc(C.Structure):
@@ -112,6 +113,9 @@ SIGNATURES = {
     "edmp_sdf_self_rows_dev": (_i, [_vp, _vp, _i, _i, _i, _i, _i, _vp, _vp]),
     "edmp_sdf_set_goal": (_i, [_vp, _pd, _pd, _pi32, _pd, _pd, _i]),
     "edmp_sdf_goal_rows_dev": (_i, [_vp, _vp, _i, _i, _i, _i, _i, _vp, _vp, _vp, _vp]),
+    "edmp_sdf_set_sweep": (_i, [_vp, _pd, _pi32, _i]),
+    "edmp_sdf_sweep_rows_dev": (_i, [_vp, _vp, _i, _i, _i, _pd, _pd, _i, _vp, _vp]),
+    "edmp_scenes_sdf_sweep_rows_dev": (_i, [_vp, _vp, _i, _i, _i, _i, _pd, _pd, _i, _vp, _vp]),
     "edmp_sdf_rows_dev": (_i, [_vp, _vp, _i, _i, _i, _pd, _pd, _vp, _vp]),
     "edmp_scene_batch_set_sdf": (_i, [_vp, _pf, _i, _pi32, _pd, _pd, _i, _i, _i]),
     "edmp_scenes_sdf_rows_dev": (_i, [_vp, _vp, _i, _i, _i, _i, _pd, _pd, _vp, _vp]),

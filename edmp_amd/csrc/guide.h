@@ -41,6 +41,17 @@ struct GoalTerm {
     void drop() { n = 0; set = derived = have_target = false; }
 };
 
+// swept-clearance term of the SDF guide (sdf.hip, edmp_sdf_set_sweep): belongs to the sphere table like the self and goal terms
+struct SweepTerm {
+    bool set = false;             // the row arrays are bound
+    int32_t* rows = nullptr;      // [n] indices of the rows whose weight is > 0
+    int n = 0;                    // (0: the gradient paths launch what they launched without the term)
+    double* weight = nullptr;     // [B]
+    int32_t* substeps = nullptr;  // [B]; 1 (no interpolant) on a row without a weight whose value lies outside 2..64
+    float* startgoal = nullptr;   // [EDMP_MAX_SCENES][14] f32: the pairs of the last report call (the guide's own stay what they are)
+    void drop() { n = 0; set = false; }
+};
+
 // sphere signed-distance guide (sdf.hip, edmp_sdf_set): belongs to the rows it was set for
 struct SdfTable {
     float* sph = nullptr;       // [ns][4] centre | radius in link-box frames, sorted by link
@@ -53,9 +64,11 @@ struct SdfTable {
     std::vector<int32_t> row_h; // [B] host copy of edmp_sdf_set's 0/1 flags (edmp_sdf_set_self checks its weights against it)
     SelfTerm self;
     GoalTerm goal;
-    void drop() { n = ns = 0; self.drop(); goal.drop(); }  // a new table, or new rows, drop the terms too
-    std::array<void*, 13> blocks() const {  // (guide_destroy)
-        return {sph, rows, margin, smooth, self.pairs, self.rows, self.weight, self.margin, goal.rows, goal.weight, goal.rotation, goal.window, goal.target};
+    SweepTerm sweep;
+    void drop() { n = ns = 0; self.drop(); goal.drop(); sweep.drop(); }  // a new table, or new rows, drop the terms too
+    std::array<void*, 17> blocks() const {  // (guide_destroy)
+        return {sph, rows, margin, smooth, self.pairs, self.rows, self.weight, self.margin, goal.rows, goal.weight, goal.rotation, goal.window, goal.target,
+                sweep.rows, sweep.weight, sweep.substeps, sweep.startgoal};
     }
 };
 

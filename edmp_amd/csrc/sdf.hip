@@ -56,6 +56,21 @@
 // sdf_goal_kernel runs after sdf_guide_kernel and sdf_self_kernel over the rows whose weight is > 0, adds this to the row's graw and
 // rewrites rowsq[r].  One chain walk and seven dot products per waypoint: ONE wave per row, lane = padded waypoint as above, four rows to
 // a 256-thread workgroup (row = rows[blockIdx.x * 4 + wave]); a wave past the list leaves as a whole.  No LDS, no barrier, no atomics.
+//
+// Swept-clearance term (sdf_sweep_kernel, edmp_sdf_set_sweep): the obstacle hinge at the configurations BETWEEN the waypoints that the
+// success check tests (success.hip: substeps - 1 joint-space interpolants per segment), so that guide and check look at the same set.
+// For an SDF row r with sweep_weight[r] > 0 and K = sweep_substeps[r], over the padded chain w = 0..L+1, all arithmetic in f32:
+//   q(w, k)  = (1 - f) q_w + f q_{w+1}      f = k / K, w = 0..L, k = 1..K-1; q_w the clipped, f32-cast joints above, q_0 / q_{L+1} the
+//                                           pinned start / goal
+//   sweep(r) = sweep_weight[r] * sum_{w=0..L} sum_{k=1..K-1} sum_s max(0, m_r(t) - d(q(w, k), s))
+// d, m_r(t) = the obstacle part's clearance and margin (sdf_margin), the same sphere table, staging and sub-gradient conventions.
+// Gradient with respect to the interior waypoints only: an active hinge at q(w, k) sends (1 - f) J^T n to waypoint w and f J^T n to
+// waypoint w + 1; what would land on start or goal is dropped.  sdf_sweep_kernel runs after the three kernels above over the rows whose
+// weight is > 0, adds weight x this to the row's graw and rewrites rowsq[r].  Layout: the obstacle part's (one workgroup per row, the
+// scene's own staging, four waves by link group) with lane = SEGMENT w holding q_w and q_{w+1} (one shuffle inside each wave).  Per k, in
+// a loop that is not unrolled (K is workgroup-uniform and nothing of the kernel's resources depends on it): one chain walk up to the
+// wave's last joint, the sphere loop of its links, and two sets of seven accumulators, (1 - f) x and f x.  Both sets meet in wave 0 as
+// ((w0 + w1) + w2) + w3; lane w then takes its own first set plus lane w-1's second set by one __shfl_up.  No atomics, one order of every sum.
 #include "common.h"
 #include "chain.h"
 #include "guide.h"
@@ -195,16 +210,17 @@ __device__ __forceinline__ float screw_dot(const float n[3], const float z[3], c
 }
 
 // The four waves' partials of a lane meet in wave 0 as ((w0 + w1) + w2) + w3: the seven gradient elements g, or (ROWS) the f32 minimum
-// dmin and the f64 sum cacc.  Waves 1..3 leave theirs in s_g / s_c (ROWS: s_g[.][0] holds dmin); false: the wave is done
-template <bool ROWS>
-__device__ __forceinline__ bool meet_in_wave0(float (*s_g)[7][64], double (*s_c)[64], int wv, int lane, float g[7], float& dmin, double& cacc) {
+// dmin and the f64 sum cacc.  Waves 1..3 leave theirs in s_g / s_c (ROWS: s_g[.][0] holds dmin); false: the wave is done.  NG = 14: the
+// sweep term's two sets of seven
+template <bool ROWS, int NG = 7>
+__device__ __forceinline__ bool meet_in_wave0(float (*s_g)[NG][64], double (*s_c)[64], int wv, int lane, float g[NG], float& dmin, double& cacc) {
     if (wv > 0) {
         if (ROWS) {
             s_g[wv - 1][0][lane] = dmin;
             s_c[wv - 1][lane] = cacc;
         } else {
 #pragma unroll
-            for (int i = 0; i < 7; ++i) s_g[wv - 1][i][lane] = g[i];
+            for (int i = 0; i < NG; ++i) s_g[wv - 1][i][lane] = g[i];
         }
     }
     __syncthreads();
@@ -214,7 +230,7 @@ __device__ __forceinline__ bool meet_in_wave0(float (*s_g)[7][64], double (*s_c)
         dmin = fminf(fminf(fminf(dmin, s_g[0][0][lane]), s_g[1][0][lane]), s_g[2][0][lane]);
     } else {
 #pragma unroll
-        for (int i = 0; i < 7; ++i) g[i] = ((g[i] + s_g[0][i][lane]) + s_g[1][i][lane]) + s_g[2][i][lane];
+        for (int i = 0; i < NG; ++i) g[i] = ((g[i] + s_g[0][i][lane]) + s_g[1][i][lane]) + s_g[2][i][lane];
     }
     return true;
 }
@@ -238,6 +254,19 @@ __device__ __forceinline__ void store_report(double cacc, float dmin, double sca
     }
 }
 
+// the workgroup's scene as the kernels read it: its no obstacles (f64 [16] rows, kinds) -> s_ob f32 [16], the sphere table -> s_sph.  All
+// 256 threads; the caller's barrier follows
+__device__ __forceinline__ void stage_scene(const double* obb, const int32_t* kind, int no, const float* spheres, int ns, float* s_ob, float* s_sph) {
+    for (int i = threadIdx.x; i < no * 16; i += 256) {
+        const int ob = i >> 4, k = i & 15;
+        const bool cyl = kind[ob] == 1;
+        const double v = obb[i];
+        // a cylinder's (r, r, h) row is stored halved like a box: slot 12 becomes the radius
+        s_ob[i] = (k == 15) ? (cyl ? 1.f : 0.f) : ((k == 12 && cyl) ? (float)(2.0 * v) : (float)v);
+    }
+    for (int i = threadIdx.x; i < ns * 4; i += 256) s_sph[i] = spheres[i];
+}
+
 // ROWS = false: the raw gradient of row a.v.rows[blockIdx.x] -> graw / rowsq (the contract of guide_kernel<GM_GRAD>).
 // ROWS = true: cost and minimum clearance of row blockIdx.x.  Cost: per lane and wave the hinge terms in f64 in (link, sphere) order,
 // the four waves' partials as ((w0 + w1) + w2) + w3, plus the lane's smoothness term, then wave_sum over the lanes.
@@ -255,14 +284,7 @@ __device__ __forceinline__ void sdf_row(const SdfArgs& a, const RobotConst& rc) 
     const double* obb = a.obb + (size_t)a.sc_off[scene] * 16;
     const int32_t* kind = a.kind + a.sc_off[scene];
     const float* sg = a.startgoal + scene * 14;  // this row's scene's start | goal
-    for (int i = threadIdx.x; i < no * 16; i += 256) {
-        const int ob = i >> 4, k = i & 15;
-        const bool cyl = kind[ob] == 1;
-        const double v = obb[i];
-        // a cylinder's (r, r, h) row is stored halved like a box: slot 12 becomes the radius
-        s_ob[i] = (k == 15) ? (cyl ? 1.f : 0.f) : ((k == 12 && cyl) ? (float)(2.0 * v) : (float)v);
-    }
-    for (int i = threadIdx.x; i < a.ns * 4; i += 256) s_sph[i] = a.spheres[i];
+    stage_scene(obb, kind, no, a.spheres, a.ns, s_ob, s_sph);
     __syncthreads();
 
     const float m = row_margin(a.v, r);
@@ -560,6 +582,137 @@ __device__ __forceinline__ void sdf_goal_row(const GoalArgs& a, const RobotConst
 __global__ __launch_bounds__(256) void sdf_goal_kernel(GoalArgs a, RobotConst rc) { sdf_goal_row<false>(a, rc); }
 __global__ __launch_bounds__(256) void sdf_goal_rows_kernel(GoalArgs a, RobotConst rc) { sdf_goal_row<true>(a, rc); }
 
+struct SweepArgs {
+    SdfArgs s;               // the obstacle part's arguments; v.rows: the rows whose weight is > 0; v.graw: what the kernels before left
+    const double* weight;    // [B], or nullptr = 1 (the report on rows that are not the bound ones)
+    const int32_t* substeps; // [B], or nullptr = K for every row
+    int K;
+};
+
+// ROWS = false: add the sweep gradient of row a.s.v.rows[blockIdx.x] to graw and rewrite rowsq.  ROWS = true: weighted sweep cost (the
+// hinge terms in f64 in (k, link, sphere) order per lane and wave, waves as ((w0 + w1) + w2) + w3, wave_sum over the lanes) and the
+// minimum clearance over the interpolants of all L + 1 segments (+inf without one) of row blockIdx.x.
+template <bool ROWS>
+__device__ __forceinline__ void sdf_sweep_row(const SweepArgs& sa, const RobotConst& rc) {
+    constexpr int NG = ROWS ? 1 : 14;
+    __shared__ float s_ob[EDMP_MAX_OBSTACLES * 16];
+    __shared__ float s_sph[EDMP_MAX_SPHERES * 4];
+    __shared__ float s_g[3][NG][64];  // partials of waves 1..3: [0..6] the (1 - f) set, [7..13] the f set (ROWS: [w][0] clearance)
+    __shared__ double s_c[3][64];     // ROWS: cost partials of waves 1..3
+    const SdfArgs& a = sa.s;
+    const int lane = threadIdx.x & 63;
+    const int wv = __builtin_amdgcn_readfirstlane(threadIdx.x >> 6);
+    const int r = __builtin_amdgcn_readfirstlane(ROWS ? (int)blockIdx.x : a.v.rows[blockIdx.x]);
+    const int scene = __builtin_amdgcn_readfirstlane(a.rps ? r / a.rps : 0);  // (one row, one scene: workgroup-uniform)
+    const int L = a.v.L, no = min(a.sc_cnt[scene], EDMP_MAX_OBSTACLES);
+    const float* sg = a.startgoal + scene * 14;  // this row's scene's start | goal
+    stage_scene(a.obb + (size_t)a.sc_off[scene] * 16, a.kind + a.sc_off[scene], no, a.spheres, a.ns, s_ob, s_sph);
+    __syncthreads();
+
+    const float m = row_margin(a.v, r);
+    const int K = __builtin_amdgcn_readfirstlane(sa.substeps ? sa.substeps[r] : sa.K);  // (a workgroup is one row: a scalar)
+
+    // lane = segment w = (padded waypoint w, padded waypoint w + 1); the neighbour's joints come by one shuffle
+    const int w = lane;
+    float q0[7], q1[7];
+    lane_joints(a.v, rc, r, w, q0);
+#pragma unroll
+    for (int j = 0; j < 7; ++j) {
+        const float vs = sg[j], vg = sg[7 + j];
+        q0[j] = (w == 0) ? vs : ((w > L) ? vg : q0[j]);
+        q1[j] = __shfl_down(q0[j], 1, 64);
+    }
+    const bool segment = w <= L;  // (L <= 62: lane w + 1 exists)
+
+    float g[NG];
+#pragma unroll
+    for (int i = 0; i < NG; ++i) g[i] = 0.f;
+    double cacc = 0.0;
+    float dmin = INFINITY;
+    const int my_jmax = wave_last_joint(wv);
+#pragma unroll 1
+    for (int k = 1; k < K; ++k) {
+        const float f = (float)k / (float)K, f1 = 1.f - f;
+        float q[7];
+#pragma unroll
+        for (int j = 0; j < 7; ++j) q[j] = fmaf(f, q1[j], f1 * q0[j]);
+        // sdf_row's walk at the interpolant
+        float R[3][3] = {{1, 0, 0}, {0, 1, 0}, {0, 0, 1}};
+        float o[3] = {0, 0, 0};
+        float zax[7][3], org[7][3];
+#pragma unroll
+        for (int j = 0; j < 7; ++j) {
+            if (j > my_jmax) break;  // (wave-uniform)
+            joint_step(rc, q, j, R, o, zax, org);
+#pragma unroll
+            for (int ll = 0; ll < 3; ++ll) {
+                if (ll > 0 && j != 6) continue;
+                const int l = (ll == 0) ? j : 6 + ll;  // hand and finger ride on joint 6
+                if (link_wave(l) != wv) continue;      // another wave's link (wave-uniform)
+                float LR[3][3], Lo[3];
+                frame_apply(R, o, rc.sf[l], LR, Lo);
+                const int s1 = a.link_off[l + 1];
+                for (int s = a.link_off[l]; s < s1; ++s) {
+                    const float* sp = s_sph + s * 4;
+                    float c[3];
+                    sphere_world(LR, Lo, sp, c);
+                    float best = INFINITY;
+                    int bi = 0;
+                    for (int ob = 0; ob < no; ++ob) {
+                        float p[3], e[3];
+                        const float d = sdf_one(s_ob + ob * 16, c[0], c[1], c[2], p, e);
+                        if (d < best) {
+                            best = d;
+                            bi = ob;
+                        }
+                    }
+                    const float clr = best - sp[3];
+                    const float h = m - clr;
+                    if constexpr (ROWS) {
+                        dmin = fminf(dmin, clr);
+                        if (segment && h > 0.f) cacc += (double)h;
+                    } else if (segment && h > 0.f) {
+                        float n[3];
+                        sdf_grad(s_ob + bi * 16, c[0], c[1], c[2], n);
+#pragma unroll
+                        for (int i = 0; i <= j; ++i) {
+                            const float jn = screw_dot(n, zax[i], org[i], c);  // the hinge turns the sign
+                            g[i] = fmaf(-f1, jn, g[i]);
+                            g[7 + i] = fmaf(-f, jn, g[7 + i]);
+                        }
+                    }
+                }
+            }
+        }
+    }
+
+    if (!meet_in_wave0<ROWS, NG>(s_g, s_c, wv, lane, g, dmin, cacc)) return;
+    const double wt = sa.weight ? sa.weight[r] : 1.0;
+    if constexpr (ROWS) {
+        if (!segment) dmin = INFINITY;  // lanes behind the last segment repeat the goal
+        store_report(cacc, dmin, wt, lane, a.v.cost + r, a.v.clearance + r);
+    } else {
+        const float wf = (float)wt;
+        const bool interior = (w >= 1) && (w <= L);
+        float gf[7];
+#pragma unroll
+        for (int i = 0; i < 7; ++i) {
+            const float prev = __shfl_up(g[7 + i], 1, 64);  // segment w - 1 ends at waypoint w
+            float gi = 0.f;
+            if (interior) {
+                float* dst = a.v.graw + ((size_t)r * 7 + i) * L + (w - 1);
+                gi = fmaf(wf, g[i] + prev, *dst);
+                *dst = gi;
+            }
+            gf[i] = gi;
+        }
+        store_rowsq(gf, lane, a.v.rowsq + r);
+    }
+}
+
+__global__ __launch_bounds__(256, 2) void sdf_sweep_kernel(SweepArgs a, RobotConst rc) { sdf_sweep_row<false>(a, rc); }
+__global__ __launch_bounds__(256, 5) void sdf_sweep_rows_kernel(SweepArgs a, RobotConst rc) { sdf_sweep_row<true>(a, rc); }
+
 static RowView row_view(const Guide* g, const double* joints, int ldw, int off, int L, int t, int do_clip, const int32_t* rows, const double* margin) {
     return RowView{joints, ldw, off, L, t, do_clip, rows, margin, g->rows_T, g->graw, g->rowsq, nullptr, nullptr};
 }
@@ -598,6 +751,16 @@ static void fill_args(const Guide* g, SdfArgs& a, const double* joints, int ldw,
     a.startgoal = g->startgoal;
 }
 
+static void fill_sweep_args(const Guide* g, SweepArgs& a, const double* joints, int ldw, int off, int L, int t, int do_clip) {
+    const SweepTerm& sw = g->sdf.sweep;
+    fill_args(g, a.s, joints, ldw, off, L, t, do_clip);  // (margin: the rows' own sdf_margin)
+    a.s.v.rows = sw.rows;
+    a.s.smooth = nullptr;
+    a.weight = sw.weight;
+    a.substeps = sw.substeps;
+    a.K = 0;
+}
+
 // guide.hip's gradient paths, after guide_kernel<GM_GRAD> and before the rowsq reduction: the SDF rows' graw / rowsq are overwritten
 int sdf_overlay(edmp_ctx* ctx, const double* joints, int ldw, int off, int L, int t, int do_clip) {
     Guide* g = ctx->guide;
@@ -620,6 +783,12 @@ int sdf_overlay(edmp_ctx* ctx, const double* joints, int ldw, int off, int L, in
         GoalArgs ga;
         fill_goal_args(g, ga, joints, ldw, off, L, t, do_clip);
         hipLaunchKernelGGL(sdf_goal_kernel, dim3((ga.n + 3) / 4), dim3(256), 0, ctx->stream, ga, g->rc);
+        EDMP_HIP_CHECK(hipGetLastError());
+    }
+    if (g->sdf.sweep.n > 0) {  // the swept-clearance term of the weighted rows, on top of all three: one workgroup per row
+        SweepArgs wa;
+        fill_sweep_args(g, wa, joints, ldw, off, L, t, do_clip);
+        hipLaunchKernelGGL(sdf_sweep_kernel, dim3(g->sdf.sweep.n), dim3(256), 0, ctx->stream, wa, g->rc);
         EDMP_HIP_CHECK(hipGetLastError());
     }
     return EDMP_OK;
@@ -975,4 +1144,111 @@ extern "C" int edmp_sdf_goal_rows_dev(edmp_ctx* ctx, const double* joints_dev, i
     hipLaunchKernelGGL(sdf_goal_rows_kernel, dim3((n + 3) / 4), dim3(256), 0, ctx->stream, a, g->rc);
     EDMP_HIP_CHECK(hipGetLastError());
     return EDMP_OK;
+}
+
+// ---- swept-clearance term -------------------------------------------------------------------------------------------------------------
+extern "C" int edmp_sdf_set_sweep(edmp_ctx* ctx, const double* weight, const int32_t* substeps, int n) {
+    EDMP_REQUIRE(ctx && ctx->guide && ctx->guide->obb && ctx->guide->row_class, "edmp_sdf_set_sweep: no guide bound (scene and rows first)");
+    Guide* g = ctx->guide;
+    const SdfTable& tb = g->sdf;
+    SweepTerm& sw = g->sdf.sweep;
+    if (tb.ns <= 0) {
+        set_error("edmp_sdf_set_sweep: call edmp_sdf_set or edmp_scene_batch_set_sdf first (the term is defined on their sphere table)");
+        return EDMP_ERR_STATE;
+    }
+    EDMP_REQUIRE(weight && substeps, "edmp_sdf_set_sweep: null argument");
+    EDMP_REQUIRE(n == g->B, "edmp_sdf_set_sweep: %d rows given, edmp_rows_set holds %d", n, g->B);
+    const int rps = g->is_batch ? g->rps : 0;
+    char where[48];
+    std::vector<int32_t> rows, ks(substeps, substeps + n);
+    for (int b = 0; b < n; ++b) {
+        EDMP_REQUIRE(std::isfinite(weight[b]) && weight[b] >= 0.0, "edmp_sdf_set_sweep: %s: weight %g must be finite and >= 0", row_name(where, b, rps), weight[b]);
+        const bool in_range = substeps[b] >= 2 && substeps[b] <= EDMP_MAX_SWEEP_SUBSTEPS;
+        if (weight[b] > 0.0) {
+            EDMP_REQUIRE(b < (int)tb.row_h.size() && tb.row_h[b] == 1, "edmp_sdf_set_sweep: %s: weight %g on a row that is not an SDF row",
+                         row_name(where, b, rps), weight[b]);
+            EDMP_REQUIRE(in_range, "edmp_sdf_set_sweep: %s: substeps %d outside 2..%d under a weight > 0", row_name(where, b, rps), (int)substeps[b],
+                         EDMP_MAX_SWEEP_SUBSTEPS);
+            rows.push_back(b);
+        } else if (!in_range) {
+            ks[b] = 1;  // a row without a weight: no interpolant (the report's loop stays bounded whatever the caller left there)
+        }
+    }
+    if (int rc = guide_upload(ctx, [&] { sw.drop(); },
+                              {{(void**)&sw.rows, rows.data(), rows.size() * sizeof(int32_t), sizeof(int32_t)},
+                               {(void**)&sw.weight, weight, (size_t)n * sizeof(double), 0},
+                               {(void**)&sw.substeps, ks.data(), (size_t)n * sizeof(int32_t), 0}}))
+        return rc;
+    sw.n = (int)rows.size();
+    sw.set = true;
+    return EDMP_OK;
+}
+
+// edmp_sdf_sweep_rows_dev and edmp_scenes_sdf_sweep_rows_dev behind their own state, table, pointer and shape checks (the arguments of
+// sdf_rows plus substeps).  The S start / goal pairs go into a block of the term's own: the guide's pairs, and so a segmented run, stay
+static int sdf_sweep_rows(edmp_ctx* ctx, const char* what, const double* joints_dev, int S, int n, int ldw, int off, int L, int t, int rps,
+                          const double* starts, const double* goals, int substeps, double* cost_dev, double* clearance_dev) {
+    Guide* g = ctx->guide;
+    SweepTerm& sw = g->sdf.sweep;
+    if (int rc = check_report_rows(what, g, n, t)) return rc;
+    EDMP_REQUIRE(substeps >= 0 && substeps <= EDMP_MAX_SWEEP_SUBSTEPS && substeps != 1, "%s: substeps %d must be 0 (the bound rows' own) or lie in 2..%d", what,
+                 substeps, EDMP_MAX_SWEEP_SUBSTEPS);
+    if (substeps == 0) {
+        if (!sw.set) {
+            set_error("%s: substeps = 0 reads the bound rows' weights and substeps: call edmp_sdf_set_sweep first", what);
+            return EDMP_ERR_STATE;
+        }
+        EDMP_REQUIRE(n == g->B, "%s: substeps = 0 reads the bound rows' weights and substeps: %d rows given, %d bound", what, n, g->B);
+    } else {
+        EDMP_REQUIRE(t == 0, "%s: substeps = %d > 0 reports the bare hinge sum at t = 0 only (t = %d given)", what, substeps, t);
+    }
+    for (int i = 0; i < S * 7; ++i) EDMP_REQUIRE(std::isfinite(starts[i]) && std::isfinite(goals[i]), "%s: scene %d: non-finite start / goal", what, i / 7);
+    EDMP_HIP_CHECK(hipSetDevice(ctx->device));
+    if (!sw.startgoal)
+        if (int rc = ctx_alloc(ctx, (void**)&sw.startgoal, EDMP_MAX_SCENES * 14 * sizeof(float))) return rc;
+    float sg[EDMP_MAX_SCENES * 14];
+    for (int s = 0; s < S; ++s)
+        for (int i = 0; i < 7; ++i) {
+            sg[s * 14 + i] = (float)starts[s * 7 + i];
+            sg[s * 14 + 7 + i] = (float)goals[s * 7 + i];
+        }
+    EDMP_HIP_CHECK(hipMemcpyAsync(sw.startgoal, sg, (size_t)S * 14 * sizeof(float), hipMemcpyHostToDevice, ctx->stream));
+    SweepArgs a;
+    fill_sweep_args(g, a, joints_dev, ldw, off, L, t, 0);
+    a.s.rps = rps;
+    a.s.startgoal = sw.startgoal;
+    if (substeps > 0) {  // weight 1 and K = substeps on any rows
+        a.weight = nullptr;
+        a.substeps = nullptr;
+        a.K = substeps;
+    }
+    a.s.v.cost = cost_dev;
+    a.s.v.clearance = clearance_dev;
+    hipLaunchKernelGGL(sdf_sweep_rows_kernel, dim3(n), dim3(256), 0, ctx->stream, a, g->rc);
+    const hipError_t e = hipGetLastError();
+    EDMP_HIP_CHECK(hipStreamSynchronize(ctx->stream));  // the host pairs live on this frame
+    EDMP_HIP_CHECK(e);
+    return EDMP_OK;
+}
+
+extern "C" int edmp_sdf_sweep_rows_dev(edmp_ctx* ctx, const double* joints_dev, int n, int L, int t, const double* start, const double* goal,
+                                       int substeps, double* cost_dev, double* clearance_dev) {
+    EDMP_REQUIRE(ctx && ctx->guide && ctx->guide->obb, "edmp_sdf_sweep_rows_dev: scene not set");
+    EDMP_REFUSE_SCENE_BATCH(ctx->guide, "edmp_sdf_sweep_rows_dev");
+    EDMP_REQUIRE(ctx->guide->sdf.ns > 0, "edmp_sdf_sweep_rows_dev: call edmp_sdf_set first (the sphere table)");
+    EDMP_REQUIRE(joints_dev && start && goal && cost_dev && clearance_dev, "edmp_sdf_sweep_rows_dev: null pointer");
+    EDMP_REQUIRE(n >= 1 && L >= 1 && L + 2 <= 64, "edmp_sdf_sweep_rows_dev: need n >= 1 and 1 <= L <= 62 waypoints per row (got %d, %d)", n, L);
+    return sdf_sweep_rows(ctx, "edmp_sdf_sweep_rows_dev", joints_dev, 1, n, L, 0, L, t, 0, start, goal, substeps, cost_dev, clearance_dev);
+}
+
+extern "C" int edmp_scenes_sdf_sweep_rows_dev(edmp_ctx* ctx, const double* X_dev, int S, int B, int N, int t, const double* starts, const double* goals,
+                                              int substeps, double* cost_dev, double* clearance_dev) {
+    EDMP_REQUIRE_SCENE_BATCH(ctx, S, B, "edmp_scenes_sdf_sweep_rows_dev");
+    if (ctx->guide->sdf.ns <= 0) {
+        set_error("edmp_scenes_sdf_sweep_rows_dev: call edmp_scene_batch_set_sdf first (the sphere table)");
+        return EDMP_ERR_STATE;
+    }
+    EDMP_REQUIRE(X_dev && starts && goals && cost_dev && clearance_dev, "edmp_scenes_sdf_sweep_rows_dev: null pointer");
+    EDMP_REQUIRE(N >= 3 && N <= 64, "edmp_scenes_sdf_sweep_rows_dev: need 3 <= N <= 64 waypoints per row (got %d)", N);
+    return sdf_sweep_rows(ctx, "edmp_scenes_sdf_sweep_rows_dev", X_dev, S, S * B, N, 1, N - 2, t, B, starts, goals, substeps, cost_dev, clearance_dev);
 }

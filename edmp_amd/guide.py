@@ -116,7 +116,9 @@ def sdf_tables(guide_cfgs, batch_size, T, link_half_extents, spheres=None, self_
     franka.self_collision_pairs()).  The tool-pose goal term (edmp_sdf_set_goal): ``sdf_goal_weight`` (B,), ``sdf_goal_rotation`` (B,)
     finite and >= 0 and ``sdf_goal_window`` (B,) integers >= 1 (absent: 0, 0, 8), a weight > 0 only on an SDF row.  Returns dict(spheres,
     rows int32, margin f64, smooth f64, self_weight f64, self_margin f64, self_mask (81,) int32, goal_weight f64, goal_rotation f64,
-    goal_window int32)."""
+    goal_window int32, sweep_weight f64, sweep_substeps int32).  The swept-clearance term (edmp_sdf_set_sweep): ``sdf_sweep_weight`` (B,)
+    finite and >= 0, a weight > 0 only on an SDF row, and ``sdf_sweep_substeps`` (B,) integers in 2..64 wherever the weight is > 0
+    (absent: 0, 4)."""
     B, T = int(batch_size), int(T)
     sph = franka.spheres_from_boxes(link_half_extents) if spheres is None else np.asarray(spheres, dtype=np.float32)
     if sph.ndim != 2 or sph.shape[1] != 5:
@@ -160,10 +162,24 @@ def sdf_tables(guide_cfgs, batch_size, T, link_half_extents, spheres=None, self_
         raise ValueError(f"sdf_goal_window: row {int(np.nonzero(bad)[0][0])} holds {gk[bad][0]!r}: must be an integer >= 1")
     if np.any((gw > 0) & (rows != 1)):
         raise ValueError(f"sdf_goal_weight: row {int(np.nonzero((gw > 0) & (rows != 1))[0][0])} carries a weight > 0 and is not an SDF row")
+    ww = np.asarray(guide_cfgs["sdf_sweep_weight"] if "sdf_sweep_weight" in guide_cfgs else np.zeros(B), dtype=np.float64)
+    wk = np.asarray(guide_cfgs["sdf_sweep_substeps"] if "sdf_sweep_substeps" in guide_cfgs else np.full(B, 4))
+    if ww.shape != (B,) or wk.shape != (B,):
+        raise ValueError(f"sdf_sweep_weight / sdf_sweep_substeps must be ({B},), got {ww.shape}, {wk.shape}")
+    bad = ~(np.isfinite(ww) & (ww >= 0))
+    if bad.any():
+        raise ValueError(f"sdf_sweep_weight: row {int(np.nonzero(bad)[0][0])} holds {ww[bad][0]!r}: must be finite and >= 0")
+    bad = ~((wk == np.floor(wk)) & (wk >= 2) & (wk <= _capi.MAX_SWEEP_SUBSTEPS)) if np.issubdtype(wk.dtype, np.number) else np.ones(B, dtype=bool)
+    bad &= ww > 0  # (a row without a weight has no interpolant to place)
+    if bad.any():
+        raise ValueError(f"sdf_sweep_substeps: row {int(np.nonzero(bad)[0][0])} holds {wk[bad][0]!r}: must be an integer in 2..{_capi.MAX_SWEEP_SUBSTEPS} under a weight > 0")
+    if np.any((ww > 0) & (rows != 1)):
+        raise ValueError(f"sdf_sweep_weight: row {int(np.nonzero((ww > 0) & (rows != 1))[0][0])} carries a weight > 0 and is not an SDF row")
     return dict(spheres=np.ascontiguousarray(sph), rows=np.ascontiguousarray(rows.astype(np.int32)), margin=np.ascontiguousarray(margin),
                 smooth=np.ascontiguousarray(smooth), self_weight=np.ascontiguousarray(sw), self_margin=np.ascontiguousarray(sm),
                 self_mask=franka.check_pair_mask(self_pairs), goal_weight=np.ascontiguousarray(gw), goal_rotation=np.ascontiguousarray(gr),
-                goal_window=np.ascontiguousarray(gk.astype(np.int32)))
+                goal_window=np.ascontiguousarray(gk.astype(np.int32)), sweep_weight=np.ascontiguousarray(ww),
+                sweep_substeps=np.ascontiguousarray(wk.astype(np.int32)))
 
 
 spheres_from_boxes = franka.spheres_from_boxes
@@ -338,6 +354,22 @@ class _SlotObject:
         h = ctx.to_host(out)
         return {k: h[i].reshape(shape).copy() for i, k in enumerate(("cost", "distance", "angle", "min_distance"))}
 
+    def _bind_sweep(self):
+        """_bind_sdf for the sweep report: an object without a weighted row hands its row arrays over once (all weights 0: the gradient
+        paths launch what they launched)"""
+        self._bind_sdf()
+        if not self._sweep_on:
+            self._sweep_on = True
+            self._set_sweep()
+
+    def _sweep_report(self, Xd, shape, W, t, pair, substeps):
+        """weighted sweep cost and the minimum clearance over the interpolants of every row; W as _sdf_report takes it"""
+        ctx = self.ctx
+        out = ctx.empty((2, int(np.prod(shape))), torch.float64)
+        self._call("edmp_sdf_sweep_rows_dev", "edmp_scenes_sdf_sweep_rows_dev", shape, ptr(Xd), *shape, W, int(t), _capi.as_pd(pair[0]), _capi.as_pd(pair[1]),
+                   0 if substeps is None else int(substeps), C.c_void_p(out[0].data_ptr()), C.c_void_p(out[1].data_ptr()))
+        return self._cost_clearance(out, shape)
+
 
 class IntersectionVolumeGuide(_SlotObject):
     """Same constructor / method signatures as the reference:
@@ -373,6 +405,11 @@ class IntersectionVolumeGuide(_SlotObject):
     pose of the tool frame ``goal_tool`` (whatever ik.tool_frame takes) in the base frame; None: the pose of the goal configuration of
     each call.  ``sdf_goal_rotation`` weighs the orientation part.  sdf_goal_rows(...) reports the term's cost and every row's tool
     distance and angle to the target.
+
+    Its swept-clearance term: SDF rows with ``guide_cfgs["sdf_sweep_weight"]`` > 0 (guide_cfg: ``hyperparameters.sdf.sweep_weight``) also
+    pay the obstacle hinge at the ``sdf_sweep_substeps`` - 1 joint-space interpolants of every segment of start, waypoints, goal: the
+    configurations the success check tests between the waypoints.  sdf_sweep_rows(...) reports the term's cost and every row's minimum
+    clearance over those interpolants.
     """
 
     def __init__(self, obstacle_config, device, guide_cfgs, batch_size, *, link_mesh_extents=None, mesh_dir=None, obstacle_kinds=None, bind=True,
@@ -411,6 +448,7 @@ class IntersectionVolumeGuide(_SlotObject):
         self._goal_tool = np.ascontiguousarray(ik.tool_frame(goal_tool))  # (3, 4)
         self._goal_target = goal_pose(goal_target)  # (3, 4), or None = derived from the goal configuration
         self._goal_on = self.has_goal_term  # likewise (sdf_goal_rows turns it on too)
+        self._sweep_on = self.has_sweep_term  # likewise (sdf_sweep_rows with the rows' own substeps turns it on too)
         if bind:
             self._bind()
 
@@ -470,6 +508,15 @@ class IntersectionVolumeGuide(_SlotObject):
         """some SDF row carries a goal weight > 0"""
         return self._sdf is not None and bool((self._sdf["goal_weight"] > 0).any())
 
+    @property
+    def has_sweep_term(self):
+        """some SDF row carries a swept-clearance weight > 0"""
+        return self._sdf is not None and bool((self._sdf["sweep_weight"] > 0).any())
+
+    def _set_sweep(self):
+        d, ctx = self._sdf, self.ctx
+        _capi.check(ctx.lib.edmp_sdf_set_sweep(ctx.h, _capi.as_pd(d["sweep_weight"]), _capi.as_pi32(d["sweep_substeps"]), self.batch_size), "edmp_sdf_set_sweep")
+
     def _set_sdf(self):
         d, ctx = self._sdf, self.ctx
         _capi.check(ctx.lib.edmp_sdf_set(ctx.h, _capi.as_pf(d["spheres"]), int(d["spheres"].shape[0]), _capi.as_pi32(d["rows"]), _capi.as_pd(d["margin"]),
@@ -478,6 +525,8 @@ class IntersectionVolumeGuide(_SlotObject):
             self._set_self()
         if self._goal_on:  # and so does the goal term
             self._set_goal()
+        if self._sweep_on:  # and the swept-clearance term
+            self._set_sweep()
 
     def _set_goal(self):
         d, ctx = self._sdf, self.ctx
@@ -599,6 +648,23 @@ class IntersectionVolumeGuide(_SlotObject):
         self._bind_goal()
         return self._goal_report(X, (X.shape[0],), X.shape[2], 0, X.shape[2], t)
 
+    def sdf_sweep_rows(self, trajectories, start, goal, t=0, substeps=None):
+        """Swept-clearance term of EVERY row (edmp_sdf_sweep_rows_dev): trajectories (n, 7, L) interior waypoints, f64 (not clipped) ->
+        {"cost": (n,) f64 = weight * sum of the hinge terms at the joint-space interpolants of the L + 1 segments of the padded chain
+        start, waypoints, goal, "clearance": (n,) f64 = the smallest sphere clearance over those interpolants (+inf for a row without
+        one)}.  substeps=None: the rows' own ``sdf_sweep_weight`` and ``sdf_sweep_substeps``, n = the guide's batch (t >= 1: their
+        margin at step t).  substeps=K in 2..64: weight 1 and K - 1 interpolants per segment on any n rows, at t = 0 - with the success
+        check's ``substeps`` the clearance covers the configurations that check tests between the waypoints.  The pair is kept apart
+        from the guide's own: a segmented run goes on running."""
+        X = self._rows_f64(trajectories)
+        if X.dim() != 3 or X.shape[1] != 7:
+            raise ValueError(f"trajectories must be (n, 7, L), got {tuple(X.shape)}")
+        if substeps is None:
+            self._bind_sweep()
+        else:
+            self._bind_sdf()
+        return self._sweep_report(X, (X.shape[0],), X.shape[2], t, _pair7(start, goal), substeps)
+
     def row_swept_volumes(self, start, goal, trajectories):
         """(B,) f32 t=0 swept volume per row and the argmin (first on ties)."""
         self._bind()
@@ -716,6 +782,8 @@ def scene_batch_tables(scenes):
         if all("sdf_goal_weight" in sc for sc in scenes):  # and the goal term's (edmp_sdf_set_goal)
             out.update(sdf_goal_weight=cat("sdf_goal_weight", np.float64), sdf_goal_rotation=cat("sdf_goal_rotation", np.float64),
                        sdf_goal_window=cat("sdf_goal_window", np.int32))
+        if all("sdf_sweep_weight" in sc for sc in scenes):  # and the swept-clearance term's (edmp_sdf_set_sweep)
+            out.update(sdf_sweep_weight=cat("sdf_sweep_weight", np.float64), sdf_sweep_substeps=cat("sdf_sweep_substeps", np.int32))
     return out
 
 
@@ -741,7 +809,8 @@ class SceneBatch(_SlotObject):
     that share their norm - equal the scene's own serial run bit for bit.  sdf_rows(...) reports cost and minimum clearance of every row
     of the finished state against its own scene.  The self-clearance term takes one pair mask for the batch and the goal term one tool
     frame (members that disagree are refused) and per-scene targets, all explicit or all derived from the scenes' goals; sdf_self_rows(...)
-    and sdf_goal_rows(...) report them."""
+    and sdf_goal_rows(...) report them.  The swept-clearance term's weights and substeps are row arrays like the margins;
+    sdf_sweep_rows(...) reports it for all scenes in one launch."""
 
     def __init__(self, guides):
         guides = list(guides)
@@ -772,7 +841,8 @@ class SceneBatch(_SlotObject):
                  grad_norm=np.asarray(g.guide_cfgs["grad_norm"], dtype=np.float64).reshape(-1), guidance_schedule=g._sched,
                  **(dict(sdf_rows=g._sdf["rows"], sdf_margin=g._sdf["margin"], smoothness=g._sdf["smooth"],
                         sdf_self_weight=g._sdf["self_weight"], sdf_self_margin=g._sdf["self_margin"], sdf_goal_weight=g._sdf["goal_weight"],
-                        sdf_goal_rotation=g._sdf["goal_rotation"], sdf_goal_window=g._sdf["goal_window"]) if sdf else {})) for g in guides])
+                        sdf_goal_rotation=g._sdf["goal_rotation"], sdf_goal_window=g._sdf["goal_window"], sdf_sweep_weight=g._sdf["sweep_weight"],
+                        sdf_sweep_substeps=g._sdf["sweep_substeps"]) if sdf else {})) for g in guides])
         for k, g in enumerate(guides):  # (host tables still: nothing is bound yet)
             if not np.array_equal(g._self_pairs, g0._self_pairs):
                 raise ValueError(f"scene {k}: the self-clearance pair mask (self_pairs) differs from scene 0's: a batch takes one mask")
@@ -785,6 +855,7 @@ class SceneBatch(_SlotObject):
         self._goal_targets = None if g0._goal_target is None else np.ascontiguousarray(np.stack([g._goal_target.reshape(12) for g in guides]))
         self._self_on = self.has_self_term
         self._goal_on = self.has_goal_term
+        self._sweep_on = self.has_sweep_term
         self._spheres = g0._sdf["spheres"] if sdf else None  # None: no SDF table is bound (sdf_rows builds one when a report is asked for)
         self._slot = new_slot_key()
         self._kinds = None
@@ -824,6 +895,16 @@ class SceneBatch(_SlotObject):
     def has_goal_term(self):
         return "sdf_goal_weight" in self.tables and bool((self.tables["sdf_goal_weight"] > 0).any())
 
+    @property
+    def has_sweep_term(self):
+        return "sdf_sweep_weight" in self.tables and bool((self.tables["sdf_sweep_weight"] > 0).any())
+
+    def _set_sweep(self):
+        tb, ctx, n = self.tables, self.ctx, self.n_scenes * self.batch_size
+        w = tb["sdf_sweep_weight"] if "sdf_sweep_weight" in tb else np.zeros(n)
+        k = tb["sdf_sweep_substeps"] if "sdf_sweep_substeps" in tb else np.full(n, 4, dtype=np.int32)
+        _capi.check(ctx.lib.edmp_sdf_set_sweep(ctx.h, _capi.as_pd(w), _capi.as_pi32(k), n), "edmp_sdf_set_sweep")
+
     def _set_goal(self):
         tb, ctx, n = self.tables, self.ctx, self.n_scenes * self.batch_size
         w = tb["sdf_goal_weight"] if "sdf_goal_weight" in tb else np.zeros(n)
@@ -855,6 +936,8 @@ class SceneBatch(_SlotObject):
             self._set_self()
         if self._goal_on:
             self._set_goal()
+        if self._sweep_on:
+            self._set_sweep()
 
     def _sdf_host(self):
         if self._spheres is not None:
@@ -985,6 +1068,22 @@ class SceneBatch(_SlotObject):
         Xd, N = self._state(trajectories)
         self._bind_sdf()
         out = self._sdf_report(Xd, (self.n_scenes, self.batch_size), N, t, pair)
+        Xd.record_stream(self.ctx.stream)
+        return out
+
+    def sdf_sweep_rows(self, trajectories, starts, goals, t=0, substeps=None):
+        """IntersectionVolumeGuide.sdf_sweep_rows for every scene in one launch (edmp_scenes_sdf_sweep_rows_dev): the swept-clearance
+        term's cost and the minimum clearance over the interpolants of EVERY row of the (S, B, 7, N) / (S*B, 7, N) state, each row
+        against its own scene's primitives, kinds and start / goal pair -> {"cost": (S, B) f64, "clearance": (S, B) f64}; scene s's
+        values are what guides[s].sdf_sweep_rows gives for X[s][:, :, 1:-1].  substeps=None: the rows' own weights and substeps;
+        substeps=K: weight 1 and K on every row, t = 0 only.  Leaves a segmented run running."""
+        pair = _pairs(self.n_scenes, starts, goals)
+        Xd, N = self._state(trajectories)
+        if substeps is None:
+            self._bind_sweep()
+        else:
+            self._bind_sdf()
+        out = self._sweep_report(Xd, (self.n_scenes, self.batch_size), N, t, pair, substeps)
         Xd.record_stream(self.ctx.stream)
         return out
 

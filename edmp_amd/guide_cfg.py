@@ -51,7 +51,8 @@ GUIDE_CATALOG = {
 # margin that shrinks towards t = 0 and a light smoothness pull; `sdf` holds the optional keys of `hyperparameters.sdf`.  102: 101 plus
 # the self-clearance term (sdf_self_kernel): the spheres of the masked link pairs are kept self_margin apart.  103: 102 plus the tool-pose
 # goal term (sdf_goal_kernel) over the last eight waypoints.  The goal values are ILLUSTRATIVE: there are no trained weights to tune them
-# against, and no claim about success rates is made.
+# against, and no claim about success rates is made.  104: 101 plus the swept-clearance term (sdf_sweep_kernel) at the success check's
+# default interpolants (substeps 4); ILLUSTRATIVE values again, no claim about success rates.
 EXTRA_GUIDES = {
     101: dict(_g((0.05, 0.05), *_E_NONE, "sdf", False, "constant", 0.05), sdf=dict(margin=(0.02, 0.08), smoothness=0.01)),
     102: dict(_g((0.05, 0.05), *_E_NONE, "sdf", False, "constant", 0.05),
@@ -59,6 +60,7 @@ EXTRA_GUIDES = {
     103: dict(_g((0.05, 0.05), *_E_NONE, "sdf", False, "constant", 0.05),
               sdf=dict(margin=(0.02, 0.08), smoothness=0.01, self_margin=(0.01, 0.03), self_weight=1.0, goal_weight=1.0, goal_rotation=0.05,
                        goal_window=8)),
+    104: dict(_g((0.05, 0.05), *_E_NONE, "sdf", False, "constant", 0.05), sdf=dict(margin=(0.02, 0.08), smoothness=0.01, sweep_weight=1.0, sweep_substeps=4)),
 }
 METHODS = ("iv", "sv", "sdf")
 
@@ -90,6 +92,8 @@ def catalog_guide_dict(n: int) -> dict:
         if "goal_weight" in g["sdf"]:
             d["hyperparameters"]["sdf"].update(goal_weight=float(g["sdf"]["goal_weight"]), goal_rotation=float(g["sdf"]["goal_rotation"]),
                                                goal_window=int(g["sdf"]["goal_window"]))
+        if "sweep_weight" in g["sdf"]:
+            d["hyperparameters"]["sdf"].update(sweep_weight=float(g["sdf"]["sweep_weight"]), sweep_substeps=int(g["sdf"]["sweep_substeps"]))
     return d
 
 
@@ -133,7 +137,9 @@ def build_guide_cfgs(guide_dicts, batch_size_per_guide, T: int, rows_per_guide=N
     over T - only when some guide sets a weight > 0, so every other dict stays key for key what it was.  The tool-pose goal term of an
     'sdf' guide: ``hyperparameters.sdf.goal_weight`` (float, default 0), ``.goal_rotation`` (float, default 0) and ``.goal_window`` (int,
     default 8) add ``sdf_goal_weight`` (B,), ``sdf_goal_rotation`` (B,) and ``sdf_goal_window`` (B,) int - again only when some guide sets
-    a weight > 0; a bad value raises ValueError naming the guide and its first row.
+    a weight > 0; a bad value raises ValueError naming the guide and its first row.  The swept-clearance term of an 'sdf' guide:
+    ``hyperparameters.sdf.sweep_weight`` (float, default 0) and ``.sweep_substeps`` (int in 2..64, default 4: the success check's) add
+    ``sdf_sweep_weight`` (B,) and ``sdf_sweep_substeps`` (B,) int32 - only when some guide sets a weight > 0, with the same errors.
     """
     G = len(guide_dicts)
     counts = [int(batch_size_per_guide)] * G if rows_per_guide is None else [int(c) for c in rows_per_guide]
@@ -174,6 +180,18 @@ def build_guide_cfgs(guide_dicts, batch_size_per_guide, T: int, rows_per_guide=N
             raise ValueError(f"{where}: sdf.goal_weight > 0 needs guidance_method 'sdf' (the term rides on the SDF rows)")
         if gw > 0 and "sdf_goal_weight" not in cfgs:
             cfgs.update(sdf_goal_weight=np.zeros((B,)), sdf_goal_rotation=np.zeros((B,)), sdf_goal_window=np.full((B,), 8, dtype=np.int64))
+    for g, first in zip(guide_dicts, np.concatenate([[0], np.cumsum(counts)[:-1]])):
+        sd = g["hyperparameters"].get("sdf") or {}
+        ww, wk = sd.get("sweep_weight", 0.0), sd.get("sweep_substeps", 4)
+        where = f"guide {g.get('index', '?')} (row {int(first)})"
+        if isinstance(ww, bool) or not (np.ndim(ww) == 0 and isinstance(ww, (int, float, np.integer, np.floating)) and np.isfinite(ww) and ww >= 0):
+            raise ValueError(f"{where}: sdf.sweep_weight must be finite and >= 0, got {ww!r}")
+        if isinstance(wk, bool) or not isinstance(wk, (int, np.integer)) or not 2 <= wk <= 64:
+            raise ValueError(f"{where}: sdf.sweep_substeps must be an integer in 2..64, got {wk!r}")
+        if ww > 0 and g["hyperparameters"]["guidance_method"] != "sdf":
+            raise ValueError(f"{where}: sdf.sweep_weight > 0 needs guidance_method 'sdf' (the term rides on the SDF rows)")
+        if ww > 0 and "sdf_sweep_weight" not in cfgs:
+            cfgs.update(sdf_sweep_weight=np.zeros((B,)), sdf_sweep_substeps=np.full((B,), 4, dtype=np.int32))
     r0 = 0
     for g, cnt in zip(guide_dicts, counts):
         rows = slice(r0, r0 + cnt)
@@ -203,6 +221,9 @@ def build_guide_cfgs(guide_dicts, batch_size_per_guide, T: int, rows_per_guide=N
                 cfgs["sdf_goal_weight"][rows] = float(sd.get("goal_weight", 0.0))
                 cfgs["sdf_goal_rotation"][rows] = float(sd.get("goal_rotation", 0.0))
                 cfgs["sdf_goal_window"][rows] = int(sd.get("goal_window", 8))
+            if "sdf_sweep_weight" in cfgs:
+                cfgs["sdf_sweep_weight"][rows] = float(sd.get("sweep_weight", 0.0))
+                cfgs["sdf_sweep_substeps"][rows] = int(sd.get("sweep_substeps", 4))
         cfgs["grad_norm"][rows] = 1 if h["grad_norm"] else 0
         gs = h["guidance_schedule"]
         cfgs["guidance_schedule"][rows, :] = (1.4 + np.arange(T) / T) if gs["type"] == "varying" else gs["scale_val"]

@@ -34,6 +34,7 @@ extern "C" {
 #define EDMP_MAX_OBSTACLES 64
 #define EDMP_MAX_SCENES 16
 #define EDMP_MAX_SPHERES 128
+#define EDMP_MAX_SWEEP_SUBSTEPS 64 /* edmp_sdf_set_sweep: interpolants per segment + 1 */
 
 typedef struct edmp_ctx edmp_ctx;
 
@@ -205,6 +206,32 @@ int edmp_sdf_set_goal(edmp_ctx* ctx, const double* weight, const double* rotatio
  * Argument errors come before any device call.  Does not synchronise. */
 int edmp_sdf_goal_rows_dev(edmp_ctx* ctx, const double* joints_dev, int n, int ldw, int off, int L, int t, double* cost_dev,
                            double* distance_dev, double* angle_dev, double* min_distance_dev);
+/* Swept-clearance term of the SDF rows (arithmetic in f32; the formulas are stated at the top of csrc/sdf.hip): the obstacle hinge of
+ * edmp_sdf_set at the configurations between the waypoints that the success check tests.  With K = substeps[r], over the padded chain
+ * w = 0..L+1 (start, the L interior waypoints, goal) and q(w, k) = (1 - k/K) q_w + (k/K) q_{w+1},
+ *   sweep(r) = weight[r] * sum_{w=0..L} sum_{k=1..K-1} sum_s max(0, m_r(t) - d(q(w, k), s)),
+ * d the obstacle part's clearance of sphere s and m_r(t) the row's own margin schedule (0 at t = 0).  The gradient is taken with respect
+ * to the interior waypoints: an active hinge at q(w, k) weighs on waypoint w with 1 - k/K and on waypoint w + 1 with k/K; the parts of
+ * the two end segments that belong to start and goal are dropped.  edmp_sdf_set_sweep comes after edmp_sdf_set or
+ * edmp_scene_batch_set_sdf (EDMP_ERR_STATE without a sphere table): weight (n,) f64 finite and >= 0, > 0 only on SDF rows; substeps (n,)
+ * int32 with 2 <= substeps <= EDMP_MAX_SWEEP_SUBSTEPS wherever the weight is > 0 (elsewhere a value outside that range stands for "no
+ * interpolant"); n = the bound rows (B, or S*B scene after scene).  A refusal names the row (and the scene, in a batch) and comes before
+ * anything is changed.  In the gradient paths sdf_sweep_kernel runs after sdf_guide_kernel, sdf_self_kernel and sdf_goal_kernel over the
+ * rows whose weight is > 0 (one workgroup per row), adds the term's gradient to their raw gradient and rewrites their sum g^2; with no
+ * such row nothing is launched and a row outside the list keeps the bits it had.  Bumps the context's epoch and synchronises, as
+ * edmp_sdf_set.  The term belongs to the sphere table: a later edmp_sdf_set / edmp_scene_batch_set_sdf / edmp_rows_set drops it. */
+int edmp_sdf_set_sweep(edmp_ctx* ctx, const double* weight, const int32_t* substeps, int n);
+/* the report of the term for EVERY row: the arguments of edmp_sdf_rows_dev / edmp_scenes_sdf_rows_dev (the same addressing of the L
+ * interior waypoints, not clipped) plus substeps.  cost_dev (n,) f64 = sweep(r), the hinge terms summed in f64; clearance_dev (n,) f64 =
+ * the smallest clearance over the interpolants of all L + 1 segments (+inf where a row has none).  substeps = 0: the bound rows' own
+ * weights and substeps (needs edmp_sdf_set_sweep, n = the bound rows; t >= 1 reads their margin schedules); substeps in
+ * 2..EDMP_MAX_SWEEP_SUBSTEPS: weight 1 and that K on any n rows, at t = 0 only.  The start / goal pairs go into a block of the term's
+ * own: the calls replace no pair of the guide and do NOT end a segmented run.  Argument errors come before any device call.  They
+ * synchronise the stream (the pairs are read from the caller's arrays). */
+int edmp_sdf_sweep_rows_dev(edmp_ctx* ctx, const double* joints_dev, int n, int L, int t, const double* start, const double* goal, int substeps,
+                            double* cost_dev, double* clearance_dev);
+int edmp_scenes_sdf_sweep_rows_dev(edmp_ctx* ctx, const double* X_dev, int S, int B, int N, int t, const double* starts, const double* goals,
+                                   int substeps, double* cost_dev, double* clearance_dev);
 
 /* ---- plan success: the reference's simulator check, restated geometrically ------------------------------------ */
 /* The guide sees every obstacle as a box (cylinders enter as (r, r, h) boxes, datasets/load_test_dataset.py:136-139) but the
@@ -308,7 +335,7 @@ int edmp_denoise_guided_dev(edmp_ctx* ctx, const double* noise_dev, int B, const
  * continuing segment after any of them is refused.  A run started with guided = 0 cannot be continued with guided = 1 (the guide
  * never received its pair).  Calls that read neither the guide's start / goal pairs, nor the sampler, nor the model's buffers leave a run
  * as it stands, and the next segment continues as if they had not been made: edmp_scenes_goal_filter_dev, edmp_ik_solve_dev,
- * edmp_self_collision_rows_dev, edmp_sdf_self_rows_dev and edmp_sdf_goal_rows_dev.
+ * edmp_self_collision_rows_dev, edmp_sdf_self_rows_dev, edmp_sdf_goal_rows_dev, edmp_sdf_sweep_rows_dev and edmp_scenes_sdf_sweep_rows_dev.
  * start / goal are read by the init segment only (uploaded once, kept on the device); a continuing segment IGNORES its start /
  * goal arguments and goes on with the init segment's pair. */
 int edmp_denoise_guided_segment_dev(edmp_ctx* ctx, const double* noise_dev, int B, const double* start, const double* goal,
