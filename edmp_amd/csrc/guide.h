@@ -13,43 +13,42 @@ struct RobotConst {
     double qlo[7], qhi[7];
 };
 
-// self-clearance term of the SDF guide (sdf.hip, edmp_sdf_set_self): belongs to the sphere table, whose drop() drops it
-struct SelfTerm {
-    bool set = false;          // a pair list is bound (it may be empty)
-    int32_t* pairs = nullptr;  // [np][4] = sphere s, sphere u (link-sorted indices), link of s, link of u; s ascending, then u
-    int np = 0;
+// What the optional terms of the SDF guide (sdf.hip) share.  A term belongs to the sphere table, whose drop() drops it
+struct RowTerm {
+    bool set = false;          // the term's arrays are bound (edmp_sdf_set_<term>)
     int32_t* rows = nullptr;   // [n] indices of the rows whose weight is > 0
     int n = 0;                 // (0: the gradient paths launch what they launched without the term)
     double* weight = nullptr;  // [B]
-    double* margin = nullptr;  // [B][T]
-    void drop() { n = np = 0; set = false; }
+    void drop() { n = 0; set = false; }
 };
 
-// tool-pose goal term of the SDF guide (sdf.hip, edmp_sdf_set_goal): belongs to the sphere table like the self term
-struct GoalTerm {
-    bool set = false;            // the row arrays, the tool frame and the target block are bound
+// self-clearance term (edmp_sdf_set_self); set: a pair list is bound (it may be empty)
+struct SelfTerm : RowTerm {
+    int32_t* pairs = nullptr;  // [np][4] = sphere s, sphere u (link-sorted indices), link of s, link of u; s ascending, then u
+    int np = 0;
+    double* margin = nullptr;  // [B][T]
+    void drop() { RowTerm::drop(); np = 0; }
+    std::vector<void*> blocks() const { return {pairs, rows, weight, margin}; }
+};
+
+// tool-pose goal term (edmp_sdf_set_goal); set: the row arrays, the tool frame and the target block are bound
+struct GoalTerm : RowTerm {
     bool derived = false;        // the targets are the poses of the scenes' goal configurations (guide_goal_targets), not the caller's
     bool have_target = false;    // the target block holds every scene's pose (derived: since the last start / goal upload)
-    int32_t* rows = nullptr;     // [n] indices of the rows whose weight is > 0
-    int n = 0;                   // (0: the gradient paths launch what they launched without the term)
-    double* weight = nullptr;    // [B]
     double* rotation = nullptr;  // [B]
     int32_t* window = nullptr;   // [B]
     float* target = nullptr;     // [EDMP_MAX_SCENES][12] f32 row-major [R* | p*] per scene
     double tool[12] = {};        // the tool frame behind joint 7, row-major [R | p]
     float target_h[EDMP_MAX_SCENES * 12] = {};  // host staging of a derived upload (it outlives the enqueued copy)
-    void drop() { n = 0; set = derived = have_target = false; }
+    void drop() { RowTerm::drop(); derived = have_target = false; }
+    std::vector<void*> blocks() const { return {rows, weight, rotation, window, target}; }
 };
 
-// swept-clearance term of the SDF guide (sdf.hip, edmp_sdf_set_sweep): belongs to the sphere table like the self and goal terms
-struct SweepTerm {
-    bool set = false;             // the row arrays are bound
-    int32_t* rows = nullptr;      // [n] indices of the rows whose weight is > 0
-    int n = 0;                    // (0: the gradient paths launch what they launched without the term)
-    double* weight = nullptr;     // [B]
+// swept-clearance term (edmp_sdf_set_sweep)
+struct SweepTerm : RowTerm {
     int32_t* substeps = nullptr;  // [B]; 1 (no interpolant) on a row without a weight whose value lies outside 2..64
     float* startgoal = nullptr;   // [EDMP_MAX_SCENES][14] f32: the pairs of the last report call (the guide's own stay what they are)
-    void drop() { n = 0; set = false; }
+    std::vector<void*> blocks() const { return {rows, weight, substeps, startgoal}; }
 };
 
 // sphere signed-distance guide (sdf.hip, edmp_sdf_set): belongs to the rows it was set for
@@ -61,14 +60,15 @@ struct SdfTable {
     int n = 0;                  // SDF rows of the batch (0: the gradient paths launch what they always launched)
     double* margin = nullptr;   // [B][T]
     double* smooth = nullptr;   // [B]
-    std::vector<int32_t> row_h; // [B] host copy of edmp_sdf_set's 0/1 flags (edmp_sdf_set_self checks its weights against it)
+    std::vector<int32_t> row_h; // [B] host copy of edmp_sdf_set's 0/1 flags (the terms' setters check their weights against it)
     SelfTerm self;
     GoalTerm goal;
     SweepTerm sweep;
     void drop() { n = ns = 0; self.drop(); goal.drop(); sweep.drop(); }  // a new table, or new rows, drop the terms too
-    std::array<void*, 17> blocks() const {  // (guide_destroy)
-        return {sph, rows, margin, smooth, self.pairs, self.rows, self.weight, self.margin, goal.rows, goal.weight, goal.rotation, goal.window, goal.target,
-                sweep.rows, sweep.weight, sweep.substeps, sweep.startgoal};
+    std::vector<void*> blocks() const {  // (guide_destroy): the table's own four and what each term reports
+        std::vector<void*> b{sph, rows, margin, smooth};
+        for (const std::vector<void*>& t : {self.blocks(), goal.blocks(), sweep.blocks()}) b.insert(b.end(), t.begin(), t.end());
+        return b;
     }
 };
 

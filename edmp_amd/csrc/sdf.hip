@@ -980,33 +980,56 @@ extern "C" int edmp_scenes_sdf_rows_dev(edmp_ctx* ctx, const double* X_dev, int 
     return sdf_rows(ctx, "edmp_scenes_sdf_rows_dev", X_dev, S, S * B, N, 1, N - 2, t, B, starts, goals, cost_dev, clearance_dev);
 }
 
+// ---- what the optional terms share on the host -------------------------------------------------------------------------------------------
+// A term's setter before its own checks: a guide with rows is bound, so is a sphere table (EDMP_ERR_STATE without one), no argument
+// is null, and the n rows - with the *T steps where the term has a schedule, T = nullptr where it has none - are those of edmp_rows_set
+static int term_precheck(edmp_ctx* ctx, const char* what, bool have_args, int n, const int* T = nullptr) {
+    EDMP_REQUIRE(ctx && ctx->guide && ctx->guide->obb && ctx->guide->row_class, "%s: no guide bound (scene and rows first)", what);
+    const Guide* g = ctx->guide;
+    if (g->sdf.ns <= 0) {
+        set_error("%s: call edmp_sdf_set or edmp_scene_batch_set_sdf first (the term is defined on their sphere table)", what);
+        return EDMP_ERR_STATE;
+    }
+    EDMP_REQUIRE(have_args, "%s: null argument", what);
+    if (!T) EDMP_REQUIRE(n == g->B, "%s: %d rows given, edmp_rows_set holds %d", what, n, g->B);
+    else EDMP_REQUIRE(n == g->B && *T == g->rows_T, "%s: %d rows x %d steps given, edmp_rows_set holds %d x %d", what, n, *T, g->B, g->rows_T);
+    return EDMP_OK;
+}
+
+// a term's weights: finite and >= 0, > 0 only on an SDF row of the table tb; rows <- the indices of the weighted rows
+static int weighted_rows(const char* what, const double* weight, int n, const SdfTable& tb, int rps, std::vector<int32_t>& rows) {
+    char where[48];
+    for (int b = 0; b < n; ++b) {
+        EDMP_REQUIRE(std::isfinite(weight[b]) && weight[b] >= 0.0, "%s: %s: weight %g must be finite and >= 0", what, row_name(where, b, rps), weight[b]);
+        if (weight[b] > 0.0) {
+            EDMP_REQUIRE(b < (int)tb.row_h.size() && tb.row_h[b] == 1, "%s: %s: weight %g on a row that is not an SDF row", what, row_name(where, b, rps), weight[b]);
+            rows.push_back(b);
+        }
+    }
+    return EDMP_OK;
+}
+
+// a report of the self or goal term before its own checks: n rows whose L interior waypoints lie at columns off .. off + L - 1 of rows
+// of ldw columns, at a step that the rows allow (check_report_rows)
+static int check_term_report(const char* what, const Guide* g, int n, int ldw, int off, int L, int t) {
+    EDMP_REQUIRE(n >= 1 && L >= 1 && L + 2 <= 64, "%s: need n >= 1 and 1 <= L <= 62 waypoints per row (got %d, %d)", what, n, L);
+    EDMP_REQUIRE(off >= 0 && ldw >= 1 && (int64_t)off + L <= ldw, "%s: columns %d .. %d outside rows of %d", what, off, off + L - 1, ldw);
+    return check_report_rows(what, g, n, t);
+}
+
 // ---- self-clearance term ------------------------------------------------------------------------------------------------------------
 extern "C" int edmp_sdf_set_self(edmp_ctx* ctx, const int32_t* pair_mask, const double* weight, const double* self_margin, int n, int T) {
-    EDMP_REQUIRE(ctx && ctx->guide && ctx->guide->obb && ctx->guide->row_class, "edmp_sdf_set_self: no guide bound (scene and rows first)");
+    if (int rc = term_precheck(ctx, "edmp_sdf_set_self", pair_mask && weight && self_margin, n, &T)) return rc;
     Guide* g = ctx->guide;
     const SdfTable& tb = g->sdf;
     SelfTerm& st = g->sdf.self;
-    if (tb.ns <= 0) {
-        set_error("edmp_sdf_set_self: call edmp_sdf_set or edmp_scene_batch_set_sdf first (the term is defined on their sphere table)");
-        return EDMP_ERR_STATE;
-    }
-    EDMP_REQUIRE(pair_mask && weight && self_margin, "edmp_sdf_set_self: null argument");
-    EDMP_REQUIRE(n == g->B && T == g->rows_T, "edmp_sdf_set_self: %d rows x %d steps given, edmp_rows_set holds %d x %d", n, T, g->B, g->rows_T);
     for (int a = 0; a < EDMP_N_LINKS; ++a)
         for (int b = a + 1; b < EDMP_N_LINKS; ++b)
             EDMP_REQUIRE(pair_mask[a * EDMP_N_LINKS + b] == 0 || pair_mask[a * EDMP_N_LINKS + b] == 1, "edmp_sdf_set_self: pair_mask[%d][%d] = %d must be 0 or 1", a,
                          b, (int)pair_mask[a * EDMP_N_LINKS + b]);
     const int rps = g->is_batch ? g->rps : 0;
-    char where[48];
     std::vector<int32_t> rows;
-    for (int b = 0; b < n; ++b) {
-        EDMP_REQUIRE(std::isfinite(weight[b]) && weight[b] >= 0.0, "edmp_sdf_set_self: %s: weight %g must be finite and >= 0", row_name(where, b, rps), weight[b]);
-        if (weight[b] > 0.0) {
-            EDMP_REQUIRE(b < (int)tb.row_h.size() && tb.row_h[b] == 1, "edmp_sdf_set_self: %s: weight %g on a row that is not an SDF row",
-                         row_name(where, b, rps), weight[b]);
-            rows.push_back(b);
-        }
-    }
+    if (int rc = weighted_rows("edmp_sdf_set_self", weight, n, tb, rps, rows)) return rc;
     if (int rc = check_schedule("edmp_sdf_set_self", "self_margin", self_margin, n, T, rps)) return rc;
     // the sphere pairs of the masked link pairs, in the order of the link-sorted table: s ascending, then u
     std::vector<int32_t> pairs;
@@ -1037,9 +1060,7 @@ extern "C" int edmp_sdf_self_rows_dev(edmp_ctx* ctx, const double* joints_dev, i
         return EDMP_ERR_STATE;
     }
     EDMP_REQUIRE(joints_dev && cost_dev && clearance_dev, "edmp_sdf_self_rows_dev: null pointer");
-    EDMP_REQUIRE(n >= 1 && L >= 1 && L + 2 <= 64, "edmp_sdf_self_rows_dev: need n >= 1 and 1 <= L <= 62 waypoints per row (got %d, %d)", n, L);
-    EDMP_REQUIRE(off >= 0 && ldw >= 1 && (int64_t)off + L <= ldw, "edmp_sdf_self_rows_dev: columns %d .. %d outside rows of %d", off, off + L - 1, ldw);
-    if (int rc = check_report_rows("edmp_sdf_self_rows_dev", g, n, t)) return rc;
+    if (int rc = check_term_report("edmp_sdf_self_rows_dev", g, n, ldw, off, L, t)) return rc;
     EDMP_HIP_CHECK(hipSetDevice(ctx->device));
     SelfArgs a;
     fill_self_args(g, a, joints_dev, ldw, off, L, t, 0);
@@ -1064,16 +1085,10 @@ static bool frame_orthonormal(const double* f) {
 
 extern "C" int edmp_sdf_set_goal(edmp_ctx* ctx, const double* weight, const double* rotation, const int32_t* window, const double* tool,
                                  const double* target, int n) {
-    EDMP_REQUIRE(ctx && ctx->guide && ctx->guide->obb && ctx->guide->row_class, "edmp_sdf_set_goal: no guide bound (scene and rows first)");
+    if (int rc = term_precheck(ctx, "edmp_sdf_set_goal", weight && rotation && window && tool, n)) return rc;
     Guide* g = ctx->guide;
     const SdfTable& tb = g->sdf;
     GoalTerm& gt = g->sdf.goal;
-    if (tb.ns <= 0) {
-        set_error("edmp_sdf_set_goal: call edmp_sdf_set or edmp_scene_batch_set_sdf first (the term is defined on their sphere table)");
-        return EDMP_ERR_STATE;
-    }
-    EDMP_REQUIRE(weight && rotation && window && tool, "edmp_sdf_set_goal: null argument");
-    EDMP_REQUIRE(n == g->B, "edmp_sdf_set_goal: %d rows given, edmp_rows_set holds %d", n, g->B);
     const int S = g->S, rps = g->is_batch ? g->rps : 0;
     for (int k = 0; k < 12; ++k) EDMP_REQUIRE(std::isfinite(tool[k]), "edmp_sdf_set_goal: the tool frame holds a non-finite value");
     EDMP_REQUIRE(frame_orthonormal(tool), "edmp_sdf_set_goal: the rotation of the tool frame is not orthonormal to 1e-6");
@@ -1083,16 +1098,11 @@ extern "C" int edmp_sdf_set_goal(edmp_ctx* ctx, const double* weight, const doub
     }
     char where[48];
     std::vector<int32_t> rows;
+    if (int rc = weighted_rows("edmp_sdf_set_goal", weight, n, tb, rps, rows)) return rc;
     for (int b = 0; b < n; ++b) {
-        EDMP_REQUIRE(std::isfinite(weight[b]) && weight[b] >= 0.0, "edmp_sdf_set_goal: %s: weight %g must be finite and >= 0", row_name(where, b, rps), weight[b]);
         EDMP_REQUIRE(std::isfinite(rotation[b]) && rotation[b] >= 0.0, "edmp_sdf_set_goal: %s: rotation %g must be finite and >= 0", row_name(where, b, rps),
                      rotation[b]);
         EDMP_REQUIRE(window[b] >= 1, "edmp_sdf_set_goal: %s: window %d must be >= 1", row_name(where, b, rps), (int)window[b]);
-        if (weight[b] > 0.0) {
-            EDMP_REQUIRE(b < (int)tb.row_h.size() && tb.row_h[b] == 1, "edmp_sdf_set_goal: %s: weight %g on a row that is not an SDF row",
-                         row_name(where, b, rps), weight[b]);
-            rows.push_back(b);
-        }
     }
     std::vector<float> tg((size_t)S * 12);
     for (size_t i = 0; target && i < tg.size(); ++i) tg[i] = (float)target[i];
@@ -1120,9 +1130,7 @@ extern "C" int edmp_sdf_goal_rows_dev(edmp_ctx* ctx, const double* joints_dev, i
         return EDMP_ERR_STATE;
     }
     EDMP_REQUIRE(joints_dev && cost_dev && distance_dev && angle_dev && min_distance_dev, "edmp_sdf_goal_rows_dev: null pointer");
-    EDMP_REQUIRE(n >= 1 && L >= 1 && L + 2 <= 64, "edmp_sdf_goal_rows_dev: need n >= 1 and 1 <= L <= 62 waypoints per row (got %d, %d)", n, L);
-    EDMP_REQUIRE(off >= 0 && ldw >= 1 && (int64_t)off + L <= ldw, "edmp_sdf_goal_rows_dev: columns %d .. %d outside rows of %d", off, off + L - 1, ldw);
-    if (int rc = check_report_rows("edmp_sdf_goal_rows_dev", g, n, t)) return rc;
+    if (int rc = check_term_report("edmp_sdf_goal_rows_dev", g, n, ldw, off, L, t)) return rc;
     EDMP_REQUIRE(!g->is_batch || n == g->B, "edmp_sdf_goal_rows_dev: a scene batch reports its own rows (row r reads scene r / rows-per-scene's target): %d rows given, %d bound",
                  n, g->B);
     if (!g->sdf.goal.have_target) {
@@ -1148,31 +1156,20 @@ extern "C" int edmp_sdf_goal_rows_dev(edmp_ctx* ctx, const double* joints_dev, i
 
 // ---- swept-clearance term -------------------------------------------------------------------------------------------------------------
 extern "C" int edmp_sdf_set_sweep(edmp_ctx* ctx, const double* weight, const int32_t* substeps, int n) {
-    EDMP_REQUIRE(ctx && ctx->guide && ctx->guide->obb && ctx->guide->row_class, "edmp_sdf_set_sweep: no guide bound (scene and rows first)");
+    if (int rc = term_precheck(ctx, "edmp_sdf_set_sweep", weight && substeps, n)) return rc;
     Guide* g = ctx->guide;
-    const SdfTable& tb = g->sdf;
     SweepTerm& sw = g->sdf.sweep;
-    if (tb.ns <= 0) {
-        set_error("edmp_sdf_set_sweep: call edmp_sdf_set or edmp_scene_batch_set_sdf first (the term is defined on their sphere table)");
-        return EDMP_ERR_STATE;
-    }
-    EDMP_REQUIRE(weight && substeps, "edmp_sdf_set_sweep: null argument");
-    EDMP_REQUIRE(n == g->B, "edmp_sdf_set_sweep: %d rows given, edmp_rows_set holds %d", n, g->B);
     const int rps = g->is_batch ? g->rps : 0;
     char where[48];
     std::vector<int32_t> rows, ks(substeps, substeps + n);
+    if (int rc = weighted_rows("edmp_sdf_set_sweep", weight, n, g->sdf, rps, rows)) return rc;
     for (int b = 0; b < n; ++b) {
-        EDMP_REQUIRE(std::isfinite(weight[b]) && weight[b] >= 0.0, "edmp_sdf_set_sweep: %s: weight %g must be finite and >= 0", row_name(where, b, rps), weight[b]);
         const bool in_range = substeps[b] >= 2 && substeps[b] <= EDMP_MAX_SWEEP_SUBSTEPS;
-        if (weight[b] > 0.0) {
-            EDMP_REQUIRE(b < (int)tb.row_h.size() && tb.row_h[b] == 1, "edmp_sdf_set_sweep: %s: weight %g on a row that is not an SDF row",
-                         row_name(where, b, rps), weight[b]);
+        if (weight[b] > 0.0)
             EDMP_REQUIRE(in_range, "edmp_sdf_set_sweep: %s: substeps %d outside 2..%d under a weight > 0", row_name(where, b, rps), (int)substeps[b],
                          EDMP_MAX_SWEEP_SUBSTEPS);
-            rows.push_back(b);
-        } else if (!in_range) {
+        else if (!in_range)
             ks[b] = 1;  // a row without a weight: no interpolant (the report's loop stays bounded whatever the caller left there)
-        }
     }
     if (int rc = guide_upload(ctx, [&] { sw.drop(); },
                               {{(void**)&sw.rows, rows.data(), rows.size() * sizeof(int32_t), sizeof(int32_t)},

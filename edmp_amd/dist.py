@@ -16,6 +16,8 @@ import numpy as np
 import torch
 import torch.distributed as dist
 
+from .sdf_terms import BASE_CFG_KEYS, CFG_KEYS
+
 
 def shard_rows(total_rows: int, rank: int, world: int):
     """rows [lo, hi) owned by `rank`: floor split, contiguous."""
@@ -28,9 +30,8 @@ def shard_guide_cfgs(cfgs: dict, lo: int, hi: int) -> dict:
     out = dict(cfgs)
     for k in ("clearance", "expansion", "guidance_method", "grad_norm", "guidance_schedule", "volume_trust_region"):
         out[k] = np.ascontiguousarray(cfgs[k][lo:hi])
-    # present only when a guide uses the SDF method, its self-clearance, goal and swept-clearance terms (guide_cfg.build_guide_cfgs)
-    for k in ("sdf_rows", "sdf_margin", "smoothness", "sdf_self_weight", "sdf_self_margin", "sdf_goal_weight", "sdf_goal_rotation", "sdf_goal_window",
-              "sdf_sweep_weight", "sdf_sweep_substeps"):
+    # present only when a guide uses the SDF method and its optional terms (guide_cfg.build_guide_cfgs)
+    for k in BASE_CFG_KEYS + CFG_KEYS:
         if k in cfgs:
             out[k] = np.ascontiguousarray(cfgs[k][lo:hi])
     out["total_batch_size"] = hi - lo

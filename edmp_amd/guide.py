@@ -9,6 +9,7 @@ import torch
 
 from . import _capi, franka
 from .runtime import get_context, ptr, new_slot_key
+from .sdf_terms import TERM, TERMS, default_rows, is_int, span
 
 
 def row_classes(clearance: np.ndarray, expansion: np.ndarray):
@@ -111,14 +112,16 @@ def sdf_tables(guide_cfgs, batch_size, T, link_half_extents, spheres=None, self_
     """Host tables of the sphere signed-distance guide (edmp_sdf_set), checked before anything touches the device: the sphere table
     (n, 5) f32 [link 0..8, centre xyz in the link-box frame, radius] - ``spheres`` or franka.spheres_from_boxes of the link boxes - and
     the row arrays of ``guide_cfgs`` (``sdf_rows`` (B,), ``sdf_margin`` (B, T), ``smoothness`` (B,); a dict without them gives no SDF
-    rows, margin 0 and smoothness 0).  The self-clearance term (edmp_sdf_set_self): ``sdf_self_weight`` (B,) and ``sdf_self_margin`` (B, T) of ``guide_cfgs``
-    (absent: 0), finite and >= 0, a weight > 0 only on an SDF row, and the (9, 9) link-pair mask ``self_pairs`` (None:
-    franka.self_collision_pairs()).  The tool-pose goal term (edmp_sdf_set_goal): ``sdf_goal_weight`` (B,), ``sdf_goal_rotation`` (B,)
-    finite and >= 0 and ``sdf_goal_window`` (B,) integers >= 1 (absent: 0, 0, 8), a weight > 0 only on an SDF row.  Returns dict(spheres,
-    rows int32, margin f64, smooth f64, self_weight f64, self_margin f64, self_mask (81,) int32, goal_weight f64, goal_rotation f64,
-    goal_window int32, sweep_weight f64, sweep_substeps int32).  The swept-clearance term (edmp_sdf_set_sweep): ``sdf_sweep_weight`` (B,)
-    finite and >= 0, a weight > 0 only on an SDF row, and ``sdf_sweep_substeps`` (B,) integers in 2..64 wherever the weight is > 0
-    (absent: 0, 4)."""
+    rows, margin 0 and smoothness 0).  The optional terms (sdf_terms.TERMS), each with its row arrays of ``guide_cfgs`` and the default of
+    an absent one, every array finite and >= 0 resp. an integer in its range, a weight > 0 only on an SDF row:
+      self-clearance (edmp_sdf_set_self): ``sdf_self_weight`` (B,) and ``sdf_self_margin`` (B, T) (absent: 0), and the (9, 9) link-pair
+        mask ``self_pairs`` (None: franka.self_collision_pairs());
+      tool-pose goal (edmp_sdf_set_goal): ``sdf_goal_weight`` (B,), ``sdf_goal_rotation`` (B,) and ``sdf_goal_window`` (B,) integers >= 1
+        (absent: 0, 0, 8);
+      swept clearance (edmp_sdf_set_sweep): ``sdf_sweep_weight`` (B,) and ``sdf_sweep_substeps`` (B,) integers in 2..64 wherever the
+        weight is > 0 (absent: 0, 4).
+    Returns dict(spheres, rows int32, margin f64, smooth f64, self_weight f64, self_margin f64, self_mask (81,) int32, goal_weight f64,
+    goal_rotation f64, goal_window int32, sweep_weight f64, sweep_substeps int32)."""
     B, T = int(batch_size), int(T)
     sph = franka.spheres_from_boxes(link_half_extents) if spheres is None else np.asarray(spheres, dtype=np.float32)
     if sph.ndim != 2 or sph.shape[1] != 5:
@@ -140,46 +143,34 @@ def sdf_tables(guide_cfgs, batch_size, T, link_half_extents, spheres=None, self_
         raise ValueError("sdf_rows: one entry per row, 0 or 1")
     if not (np.isfinite(margin).all() and np.all(margin >= 0) and np.isfinite(smooth).all() and np.all(smooth >= 0)):
         raise ValueError("sdf_margin and smoothness must be finite and >= 0")
-    sw = np.asarray(guide_cfgs["sdf_self_weight"] if "sdf_self_weight" in guide_cfgs else np.zeros(B), dtype=np.float64)
-    sm = np.asarray(guide_cfgs["sdf_self_margin"] if "sdf_self_margin" in guide_cfgs else np.zeros((B, T)), dtype=np.float64)
-    if sw.shape != (B,) or sm.shape != (B, T):
-        raise ValueError(f"sdf_self_weight / sdf_self_margin must be ({B},), ({B}, {T}), got {sw.shape}, {sm.shape}")
-    if not (np.isfinite(sw).all() and np.all(sw >= 0) and np.isfinite(sm).all() and np.all(sm >= 0)):
-        raise ValueError("sdf_self_weight and sdf_self_margin must be finite and >= 0")
-    if np.any((sw > 0) & (rows != 1)):
-        raise ValueError(f"sdf_self_weight: row {int(np.nonzero((sw > 0) & (rows != 1))[0][0])} carries a weight > 0 and is not an SDF row")
-    gw = np.asarray(guide_cfgs["sdf_goal_weight"] if "sdf_goal_weight" in guide_cfgs else np.zeros(B), dtype=np.float64)
-    gr = np.asarray(guide_cfgs["sdf_goal_rotation"] if "sdf_goal_rotation" in guide_cfgs else np.zeros(B), dtype=np.float64)
-    gk = np.asarray(guide_cfgs["sdf_goal_window"] if "sdf_goal_window" in guide_cfgs else np.full(B, 8))
-    if gw.shape != (B,) or gr.shape != (B,) or gk.shape != (B,):
-        raise ValueError(f"sdf_goal_weight / sdf_goal_rotation / sdf_goal_window must be ({B},), got {gw.shape}, {gr.shape}, {gk.shape}")
-    for name, v in (("sdf_goal_weight", gw), ("sdf_goal_rotation", gr)):
-        bad = ~(np.isfinite(v) & (v >= 0))
-        if bad.any():
-            raise ValueError(f"{name}: row {int(np.nonzero(bad)[0][0])} holds {v[bad][0]!r}: must be finite and >= 0")
-    bad = ~((gk == np.floor(gk)) & (gk >= 1)) if np.issubdtype(gk.dtype, np.number) else np.ones(B, dtype=bool)
-    if bad.any():
-        raise ValueError(f"sdf_goal_window: row {int(np.nonzero(bad)[0][0])} holds {gk[bad][0]!r}: must be an integer >= 1")
-    if np.any((gw > 0) & (rows != 1)):
-        raise ValueError(f"sdf_goal_weight: row {int(np.nonzero((gw > 0) & (rows != 1))[0][0])} carries a weight > 0 and is not an SDF row")
-    ww = np.asarray(guide_cfgs["sdf_sweep_weight"] if "sdf_sweep_weight" in guide_cfgs else np.zeros(B), dtype=np.float64)
-    wk = np.asarray(guide_cfgs["sdf_sweep_substeps"] if "sdf_sweep_substeps" in guide_cfgs else np.full(B, 4))
-    if ww.shape != (B,) or wk.shape != (B,):
-        raise ValueError(f"sdf_sweep_weight / sdf_sweep_substeps must be ({B},), got {ww.shape}, {wk.shape}")
-    bad = ~(np.isfinite(ww) & (ww >= 0))
-    if bad.any():
-        raise ValueError(f"sdf_sweep_weight: row {int(np.nonzero(bad)[0][0])} holds {ww[bad][0]!r}: must be finite and >= 0")
-    bad = ~((wk == np.floor(wk)) & (wk >= 2) & (wk <= _capi.MAX_SWEEP_SUBSTEPS)) if np.issubdtype(wk.dtype, np.number) else np.ones(B, dtype=bool)
-    bad &= ww > 0  # (a row without a weight has no interpolant to place)
-    if bad.any():
-        raise ValueError(f"sdf_sweep_substeps: row {int(np.nonzero(bad)[0][0])} holds {wk[bad][0]!r}: must be an integer in 2..{_capi.MAX_SWEEP_SUBSTEPS} under a weight > 0")
-    if np.any((ww > 0) & (rows != 1)):
-        raise ValueError(f"sdf_sweep_weight: row {int(np.nonzero((ww > 0) & (rows != 1))[0][0])} carries a weight > 0 and is not an SDF row")
-    return dict(spheres=np.ascontiguousarray(sph), rows=np.ascontiguousarray(rows.astype(np.int32)), margin=np.ascontiguousarray(margin),
-                smooth=np.ascontiguousarray(smooth), self_weight=np.ascontiguousarray(sw), self_margin=np.ascontiguousarray(sm),
-                self_mask=franka.check_pair_mask(self_pairs), goal_weight=np.ascontiguousarray(gw), goal_rotation=np.ascontiguousarray(gr),
-                goal_window=np.ascontiguousarray(gk.astype(np.int32)), sweep_weight=np.ascontiguousarray(ww),
-                sweep_substeps=np.ascontiguousarray(wk.astype(np.int32)))
+    tabs = {}
+    for term in TERMS:
+        shapes = [(B, T) if k.pair else (B,) for k in term.keys]
+        vals = [np.asarray(guide_cfgs[k.cfg] if k.cfg in guide_cfgs else default_rows(k, B, T), **({} if is_int(k) else dict(dtype=np.float64)))
+                for k in term.keys]
+        if [v.shape for v in vals] != shapes:
+            raise ValueError(f"{' / '.join(k.cfg for k in term.keys)} must be {', '.join(map(str, shapes))}, got {', '.join(str(v.shape) for v in vals)}")
+        weight = vals[0]
+        for k, v in zip(term.keys, vals):
+            if not is_int(k):
+                bad, must = ~(np.isfinite(v) & (v >= 0)), "finite and >= 0"
+            elif not np.issubdtype(v.dtype, np.number):
+                bad, must = np.ones(B, dtype=bool), span(k)
+            else:
+                bad, must = ~((v == np.floor(v)) & (v >= k.lo) & (True if k.hi is None else v <= k.hi)), span(k)
+            if k.check == "int_weighted":  # (a row without a weight has nothing that reads the value)
+                bad, must = bad & (weight > 0), must + " under a weight > 0"
+            if bad.any():
+                raise ValueError(f"{k.cfg}: row {int(np.nonzero(bad)[0][0])} holds {v[bad][0]!r}: must be {must}")
+        if np.any((weight > 0) & (rows != 1)):
+            raise ValueError(f"{term.keys[0].cfg}: row {int(np.nonzero((weight > 0) & (rows != 1))[0][0])} carries a weight > 0 and is not an SDF row")
+        tabs[term.name] = {k.hyper: np.ascontiguousarray(v.astype(k.dtype, copy=False)) for k, v in zip(term.keys, vals)}
+    extra = dict(self_mask=franka.check_pair_mask(self_pairs))  # what a term takes beside its row arrays (Term.extra), checked last
+    out = dict(spheres=np.ascontiguousarray(sph), rows=np.ascontiguousarray(rows.astype(np.int32)), margin=np.ascontiguousarray(margin),
+               smooth=np.ascontiguousarray(smooth))
+    for term in TERMS:
+        out.update(tabs[term.name], **{e: extra[e] for e in term.extra})
+    return out
 
 
 spheres_from_boxes = franka.spheres_from_boxes
@@ -203,12 +194,20 @@ def _pairs(n_scenes, starts, goals):
     return out
 
 
+def _term_flag(name):
+    """_SlotObject._term_on[name] under the attribute name the flag had before the terms shared one dict: callers that set it keep working"""
+    return property(lambda self: self._term_on[name], lambda self, on: self._term_on.__setitem__(name, on))
+
+
 class _SlotObject:
     """What IntersectionVolumeGuide and SceneBatch share: the resident-slot protocol, and the scoring calls whose single-scene and
     scene-batch entry points differ in their leading dimensions only.  Below, ``shape`` is (B,) for a guide and (S, B) for a batch: the
     shape of every per-row result and, as leading arguments, what tells edmp_x from edmp_scenes_x.  A subclass brings ctx, _slot,
     _upload() (its tables into the current slot), _sdf_host() (make the host sphere table if there is none: True if it did) and
-    _set_sdf()."""
+    _set_sdf().  The optional terms of the SDF guide (sdf_terms.TERMS) are handled here once; a subclass brings _term_arrays(name) (the
+    term's row arrays in the table's key order), _term_weight(name) (the weights it holds, None if it holds none) and what is its own:
+    _self_pairs (the pair mask), _goal_tool,
+    _goal_targets ((S, 12) or None = derived), _n_rows and T.  _term_on[name]: the term has been handed over with the sphere table."""
 
     def _bind(self):
         ctx = self.ctx
@@ -320,13 +319,43 @@ class _SlotObject:
                    C.c_void_p(out[0].data_ptr()), C.c_void_p(out[1].data_ptr()))
         return self._cost_clearance(out, shape)
 
-    def _bind_self(self):
-        """_bind_sdf for the self-clearance report: an object without a weighted row hands its mask over once (all weights 0: the
-        gradient paths launch what they launched)"""
+    def has_term(self, name):
+        """some SDF row carries a weight > 0 for the term `name` (sdf_terms.TERM)"""
+        w = self._term_weight(name)
+        return w is not None and bool((w > 0).any())
+
+    has_self_term = property(lambda self: self.has_term("self"), doc="some SDF row carries a self-clearance weight > 0")
+    has_goal_term = property(lambda self: self.has_term("goal"), doc="some SDF row carries a goal weight > 0")
+    has_sweep_term = property(lambda self: self.has_term("sweep"), doc="some SDF row carries a swept-clearance weight > 0")
+
+    _self_on, _goal_on, _sweep_on = (_term_flag(t.name) for t in TERMS)
+
+    def _bind_term(self, name):
+        """_bind_sdf for a term's report: an object without a weighted row hands the term over once (all weights 0: the gradient paths
+        launch what they launched)"""
         self._bind_sdf()
-        if not self._self_on:
-            self._self_on = True
-            self._set_self()
+        if not self._term_on[name]:
+            self._term_on[name] = True
+            self._set_term(name)
+
+    def _set_term(self, name):
+        """the term's row arrays (_term_arrays, in the table's key order) and what the object itself brings for it -> its setter"""
+        term, ctx, n = TERM[name], self.ctx, self._n_rows
+        rows = [(_capi.as_pi32 if is_int(k) else _capi.as_pd)(a) for k, a in zip(term.keys, self._term_arrays(name))]
+        if name == "self":
+            args = [_capi.as_pi32(self._self_pairs), *rows, n, self.T]
+        elif name == "goal":
+            tool, tg = np.ascontiguousarray(self._goal_tool.reshape(12)), self._goal_targets
+            args = [*rows, _capi.as_pd(tool), None if tg is None else _capi.as_pd(tg), n]
+        else:
+            args = [*rows, n]
+        _capi.check(getattr(ctx.lib, term.setter)(ctx.h, *args), term.setter)
+
+    def _set_terms(self):
+        """after a sphere table was set (it dropped the terms): every term that is on, in the table's order"""
+        for term in TERMS:
+            if self._term_on[term.name]:
+                self._set_term(term.name)
 
     def _self_report(self, Xd, shape, ldw, off, L, t):
         """weighted self cost and minimum self clearance of every row; the L interior waypoints at columns off .. of rows of ldw"""
@@ -336,15 +365,6 @@ class _SlotObject:
                                                    C.c_void_p(out[1].data_ptr())), "edmp_sdf_self_rows_dev")
         return self._cost_clearance(out, shape)
 
-
-    def _bind_goal(self):
-        """_bind_sdf for the goal report: an object without a weighted row hands its tool frame and targets over once (all weights 0:
-        the gradient paths launch what they launched)"""
-        self._bind_sdf()
-        if not self._goal_on:
-            self._goal_on = True
-            self._set_goal()
-
     def _goal_report(self, Xd, shape, ldw, off, L, t):
         """weighted goal cost, tool distance and angle at the last column and the smallest distance, of every row"""
         ctx = self.ctx
@@ -353,14 +373,6 @@ class _SlotObject:
                     "edmp_sdf_goal_rows_dev")
         h = ctx.to_host(out)
         return {k: h[i].reshape(shape).copy() for i, k in enumerate(("cost", "distance", "angle", "min_distance"))}
-
-    def _bind_sweep(self):
-        """_bind_sdf for the sweep report: an object without a weighted row hands its row arrays over once (all weights 0: the gradient
-        paths launch what they launched)"""
-        self._bind_sdf()
-        if not self._sweep_on:
-            self._sweep_on = True
-            self._set_sweep()
 
     def _sweep_report(self, Xd, shape, W, t, pair, substeps):
         """weighted sweep cost and the minimum clearance over the interpolants of every row; W as _sdf_report takes it"""
@@ -442,13 +454,12 @@ class IntersectionVolumeGuide(_SlotObject):
         self._spheres = spheres
         self._self_pairs = franka.check_pair_mask(self_pairs)
         self._sdf = sdf_tables(guide_cfgs, self.batch_size, self.T, self._half, spheres, self._self_pairs.reshape(9, 9)) if ("sdf_rows" in guide_cfgs or spheres is not None) else None
-        self._self_on = self.has_self_term  # the self table is handed over with the sphere table (sdf_self_rows turns it on too)
         from . import ik
 
         self._goal_tool = np.ascontiguousarray(ik.tool_frame(goal_tool))  # (3, 4)
         self._goal_target = goal_pose(goal_target)  # (3, 4), or None = derived from the goal configuration
-        self._goal_on = self.has_goal_term  # likewise (sdf_goal_rows turns it on too)
-        self._sweep_on = self.has_sweep_term  # likewise (sdf_sweep_rows with the rows' own substeps turns it on too)
+        # a term with a weighted row is handed over with the sphere table (its report, on the rows' own values, turns it on too)
+        self._term_on = {t.name: self.has_term(t.name) for t in TERMS}
         if bind:
             self._bind()
 
@@ -498,47 +509,20 @@ class IntersectionVolumeGuide(_SlotObject):
     def has_sdf_rows(self):
         return self._sdf is not None and bool(self._sdf["rows"].any())
 
-    @property
-    def has_self_term(self):
-        """some SDF row carries a self-clearance weight > 0"""
-        return self._sdf is not None and bool((self._sdf["self_weight"] > 0).any())
+    _n_rows = property(lambda self: self.batch_size)
+    _goal_targets = property(lambda self: None if self._goal_target is None else np.ascontiguousarray(self._goal_target.reshape(1, 12)))
 
-    @property
-    def has_goal_term(self):
-        """some SDF row carries a goal weight > 0"""
-        return self._sdf is not None and bool((self._sdf["goal_weight"] > 0).any())
+    def _term_arrays(self, name):
+        return [self._sdf[k.hyper] for k in TERM[name].keys]
 
-    @property
-    def has_sweep_term(self):
-        """some SDF row carries a swept-clearance weight > 0"""
-        return self._sdf is not None and bool((self._sdf["sweep_weight"] > 0).any())
-
-    def _set_sweep(self):
-        d, ctx = self._sdf, self.ctx
-        _capi.check(ctx.lib.edmp_sdf_set_sweep(ctx.h, _capi.as_pd(d["sweep_weight"]), _capi.as_pi32(d["sweep_substeps"]), self.batch_size), "edmp_sdf_set_sweep")
+    def _term_weight(self, name):
+        return None if self._sdf is None else self._sdf[TERM[name].keys[0].hyper]
 
     def _set_sdf(self):
         d, ctx = self._sdf, self.ctx
         _capi.check(ctx.lib.edmp_sdf_set(ctx.h, _capi.as_pf(d["spheres"]), int(d["spheres"].shape[0]), _capi.as_pi32(d["rows"]), _capi.as_pd(d["margin"]),
                                          _capi.as_pd(d["smooth"]), self.batch_size, int(d["margin"].shape[1])), "edmp_sdf_set")
-        if self._self_on:  # the self term belongs to the sphere table: edmp_sdf_set dropped it
-            self._set_self()
-        if self._goal_on:  # and so does the goal term
-            self._set_goal()
-        if self._sweep_on:  # and the swept-clearance term
-            self._set_sweep()
-
-    def _set_goal(self):
-        d, ctx = self._sdf, self.ctx
-        tool = np.ascontiguousarray(self._goal_tool.reshape(12))
-        tg = None if self._goal_target is None else np.ascontiguousarray(self._goal_target.reshape(1, 12))
-        _capi.check(ctx.lib.edmp_sdf_set_goal(ctx.h, _capi.as_pd(d["goal_weight"]), _capi.as_pd(d["goal_rotation"]), _capi.as_pi32(d["goal_window"]),
-                                              _capi.as_pd(tool), None if tg is None else _capi.as_pd(tg), self.batch_size), "edmp_sdf_set_goal")
-
-    def _set_self(self):
-        d, ctx = self._sdf, self.ctx
-        _capi.check(ctx.lib.edmp_sdf_set_self(ctx.h, _capi.as_pi32(d["self_mask"]), _capi.as_pd(d["self_weight"]), _capi.as_pd(d["self_margin"]),
-                                              self.batch_size, int(d["self_margin"].shape[1])), "edmp_sdf_set_self")
+        self._set_terms()  # the terms belong to the sphere table: edmp_sdf_set dropped them
 
     def _sdf_host(self):
         if self._sdf is not None:
@@ -632,7 +616,7 @@ class IntersectionVolumeGuide(_SlotObject):
         X = self._rows_f64(trajectories)
         if X.dim() != 3 or X.shape[1] != 7:
             raise ValueError(f"trajectories must be (n, 7, L), got {tuple(X.shape)}")
-        self._bind_self()
+        self._bind_term("self")
         return self._self_report(X, (X.shape[0],), X.shape[2], 0, X.shape[2], t)
 
     def sdf_goal_rows(self, trajectories, t=0):
@@ -645,7 +629,7 @@ class IntersectionVolumeGuide(_SlotObject):
         X = self._rows_f64(trajectories)
         if X.dim() != 3 or X.shape[1] != 7:
             raise ValueError(f"trajectories must be (n, 7, L), got {tuple(X.shape)}")
-        self._bind_goal()
+        self._bind_term("goal")
         return self._goal_report(X, (X.shape[0],), X.shape[2], 0, X.shape[2], t)
 
     def sdf_sweep_rows(self, trajectories, start, goal, t=0, substeps=None):
@@ -660,7 +644,7 @@ class IntersectionVolumeGuide(_SlotObject):
         if X.dim() != 3 or X.shape[1] != 7:
             raise ValueError(f"trajectories must be (n, 7, L), got {tuple(X.shape)}")
         if substeps is None:
-            self._bind_sweep()
+            self._bind_term("sweep")
         else:
             self._bind_sdf()
         return self._sweep_report(X, (X.shape[0],), X.shape[2], t, _pair7(start, goal), substeps)
@@ -777,13 +761,9 @@ def scene_batch_tables(scenes):
             if shapes != ((B,), (B, T), (B,)):
                 raise ValueError(f"scene {s}: sdf_rows / sdf_margin / smoothness must be ({B},), ({B}, {T}), ({B},), got {shapes}")
         out.update(sdf_rows=cat("sdf_rows", np.int32), sdf_margin=cat("sdf_margin", np.float64, (T,)), smoothness=cat("smoothness", np.float64))
-        if all("sdf_self_weight" in sc for sc in scenes):  # the self-clearance term's row arrays ride along (edmp_sdf_set_self)
-            out.update(sdf_self_weight=cat("sdf_self_weight", np.float64), sdf_self_margin=cat("sdf_self_margin", np.float64, (T,)))
-        if all("sdf_goal_weight" in sc for sc in scenes):  # and the goal term's (edmp_sdf_set_goal)
-            out.update(sdf_goal_weight=cat("sdf_goal_weight", np.float64), sdf_goal_rotation=cat("sdf_goal_rotation", np.float64),
-                       sdf_goal_window=cat("sdf_goal_window", np.int32))
-        if all("sdf_sweep_weight" in sc for sc in scenes):  # and the swept-clearance term's (edmp_sdf_set_sweep)
-            out.update(sdf_sweep_weight=cat("sdf_sweep_weight", np.float64), sdf_sweep_substeps=cat("sdf_sweep_substeps", np.int32))
+        for term in TERMS:  # a term's row arrays ride along when every scene brings them (its setter takes them)
+            if all(term.keys[0].cfg in sc for sc in scenes):
+                out.update({k.cfg: cat(k.cfg, k.dtype, (T,) if k.pair else ()) for k in term.keys})
     return out
 
 
@@ -840,9 +820,7 @@ class SceneBatch(_SlotObject):
                  method=np.asarray(g.guide_cfgs["guidance_method"], dtype=np.float32).reshape(-1),
                  grad_norm=np.asarray(g.guide_cfgs["grad_norm"], dtype=np.float64).reshape(-1), guidance_schedule=g._sched,
                  **(dict(sdf_rows=g._sdf["rows"], sdf_margin=g._sdf["margin"], smoothness=g._sdf["smooth"],
-                        sdf_self_weight=g._sdf["self_weight"], sdf_self_margin=g._sdf["self_margin"], sdf_goal_weight=g._sdf["goal_weight"],
-                        sdf_goal_rotation=g._sdf["goal_rotation"], sdf_goal_window=g._sdf["goal_window"], sdf_sweep_weight=g._sdf["sweep_weight"],
-                        sdf_sweep_substeps=g._sdf["sweep_substeps"]) if sdf else {})) for g in guides])
+                        **{k.cfg: g._sdf[k.hyper] for t in TERMS for k in t.keys}) if sdf else {})) for g in guides])
         for k, g in enumerate(guides):  # (host tables still: nothing is bound yet)
             if not np.array_equal(g._self_pairs, g0._self_pairs):
                 raise ValueError(f"scene {k}: the self-clearance pair mask (self_pairs) differs from scene 0's: a batch takes one mask")
@@ -853,9 +831,8 @@ class SceneBatch(_SlotObject):
                                  f"{'none' if g0._goal_target is None else 'an explicit one'}: the targets of a batch are either all explicit or all derived")
         self._goal_tool = g0._goal_tool
         self._goal_targets = None if g0._goal_target is None else np.ascontiguousarray(np.stack([g._goal_target.reshape(12) for g in guides]))
-        self._self_on = self.has_self_term
-        self._goal_on = self.has_goal_term
-        self._sweep_on = self.has_sweep_term
+        self._self_pairs = g0._self_pairs
+        self._term_on = {t.name: self.has_term(t.name) for t in TERMS}
         self._spheres = g0._sdf["spheres"] if sdf else None  # None: no SDF table is bound (sdf_rows builds one when a report is asked for)
         self._slot = new_slot_key()
         self._kinds = None
@@ -887,39 +864,13 @@ class SceneBatch(_SlotObject):
     def has_sdf_rows(self):
         return "sdf_rows" in self.tables and bool(self.tables["sdf_rows"].any())
 
-    @property
-    def has_self_term(self):
-        return "sdf_self_weight" in self.tables and bool((self.tables["sdf_self_weight"] > 0).any())
+    _n_rows = property(lambda self: self.n_scenes * self.batch_size)
 
-    @property
-    def has_goal_term(self):
-        return "sdf_goal_weight" in self.tables and bool((self.tables["sdf_goal_weight"] > 0).any())
+    def _term_arrays(self, name):
+        return [self.tables[k.cfg] if k.cfg in self.tables else default_rows(k, self._n_rows, self.T) for k in TERM[name].keys]
 
-    @property
-    def has_sweep_term(self):
-        return "sdf_sweep_weight" in self.tables and bool((self.tables["sdf_sweep_weight"] > 0).any())
-
-    def _set_sweep(self):
-        tb, ctx, n = self.tables, self.ctx, self.n_scenes * self.batch_size
-        w = tb["sdf_sweep_weight"] if "sdf_sweep_weight" in tb else np.zeros(n)
-        k = tb["sdf_sweep_substeps"] if "sdf_sweep_substeps" in tb else np.full(n, 4, dtype=np.int32)
-        _capi.check(ctx.lib.edmp_sdf_set_sweep(ctx.h, _capi.as_pd(w), _capi.as_pi32(k), n), "edmp_sdf_set_sweep")
-
-    def _set_goal(self):
-        tb, ctx, n = self.tables, self.ctx, self.n_scenes * self.batch_size
-        w = tb["sdf_goal_weight"] if "sdf_goal_weight" in tb else np.zeros(n)
-        r = tb["sdf_goal_rotation"] if "sdf_goal_rotation" in tb else np.zeros(n)
-        k = tb["sdf_goal_window"] if "sdf_goal_window" in tb else np.full(n, 8, dtype=np.int32)
-        tool = np.ascontiguousarray(self._goal_tool.reshape(12))
-        tg = self._goal_targets
-        _capi.check(ctx.lib.edmp_sdf_set_goal(ctx.h, _capi.as_pd(w), _capi.as_pd(r), _capi.as_pi32(k), _capi.as_pd(tool), None if tg is None else _capi.as_pd(tg), n),
-                    "edmp_sdf_set_goal")
-
-    def _set_self(self):
-        tb, ctx, n = self.tables, self.ctx, self.n_scenes * self.batch_size
-        w = tb["sdf_self_weight"] if "sdf_self_weight" in tb else np.zeros(n)
-        m = tb["sdf_self_margin"] if "sdf_self_margin" in tb else np.zeros((n, self.T))
-        _capi.check(ctx.lib.edmp_sdf_set_self(ctx.h, _capi.as_pi32(self.guides[0]._self_pairs), _capi.as_pd(w), _capi.as_pd(m), n, self.T), "edmp_sdf_set_self")
+    def _term_weight(self, name):
+        return self.tables.get(TERM[name].keys[0].cfg)
 
     def _set_sdf(self):
         tb, ctx, B = self.tables, self.ctx, self.batch_size
@@ -932,12 +883,7 @@ class SceneBatch(_SlotObject):
         rows, margin, smooth = tb["sdf_rows"], tb["sdf_margin"], tb["smoothness"]
         _capi.check(ctx.lib.edmp_scene_batch_set_sdf(ctx.h, _capi.as_pf(self._spheres), int(self._spheres.shape[0]), _capi.as_pi32(rows), _capi.as_pd(margin),
                                                      _capi.as_pd(smooth), self.n_scenes, self.batch_size, self.T), "edmp_scene_batch_set_sdf")
-        if self._self_on:
-            self._set_self()
-        if self._goal_on:
-            self._set_goal()
-        if self._sweep_on:
-            self._set_sweep()
+        self._set_terms()
 
     def _sdf_host(self):
         if self._spheres is not None:
@@ -1080,7 +1026,7 @@ class SceneBatch(_SlotObject):
         pair = _pairs(self.n_scenes, starts, goals)
         Xd, N = self._state(trajectories)
         if substeps is None:
-            self._bind_sweep()
+            self._bind_term("sweep")
         else:
             self._bind_sdf()
         out = self._sweep_report(Xd, (self.n_scenes, self.batch_size), N, t, pair, substeps)
@@ -1092,7 +1038,7 @@ class SceneBatch(_SlotObject):
         waypoints) in one call -> {"cost": (S, B) f64, "clearance": (S, B) f64}.  The term reads nothing of the scenes: scene s's values
         are what guides[s].sdf_self_rows gives for X[s][:, :, 1:-1]."""
         Xd, N = self._state(trajectories)
-        self._bind_self()
+        self._bind_term("self")
         out = self._self_report(Xd, (self.n_scenes, self.batch_size), N, 1, N - 2, t)
         Xd.record_stream(self.ctx.stream)
         return out
@@ -1103,7 +1049,7 @@ class SceneBatch(_SlotObject):
         target: scene s's values are what guides[s].sdf_goal_rows gives for X[s][:, :, 1:-1].  final=True hands the goal column over as
         well (columns 1..N-1, as X[s][:, :, 1:]): distance and angle are then those of the plan's final tool pose."""
         Xd, N = self._state(trajectories)
-        self._bind_goal()
+        self._bind_term("goal")
         out = self._goal_report(Xd, (self.n_scenes, self.batch_size), N, 1, N - 1 if final else N - 2, t)
         Xd.record_stream(self.ctx.stream)
         return out

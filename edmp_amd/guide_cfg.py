@@ -14,6 +14,8 @@ import os
 import numpy as np
 import yaml
 
+from .sdf_terms import TERMS, is_int, span
+
 # (clearance range, [(isr, val) x3 in file order isr1, isr2, isr3], method, grad_norm, schedule type, scale_val)
 _Z = (0.0, 0.0)
 
@@ -87,13 +89,11 @@ def catalog_guide_dict(n: int) -> dict:
     }
     if "sdf" in g:
         d["hyperparameters"]["sdf"] = {"margin": [float(v) for v in g["sdf"]["margin"]], "smoothness": float(g["sdf"]["smoothness"])}
-        if "self_weight" in g["sdf"]:
-            d["hyperparameters"]["sdf"].update(self_margin=[float(v) for v in g["sdf"]["self_margin"]], self_weight=float(g["sdf"]["self_weight"]))
-        if "goal_weight" in g["sdf"]:
-            d["hyperparameters"]["sdf"].update(goal_weight=float(g["sdf"]["goal_weight"]), goal_rotation=float(g["sdf"]["goal_rotation"]),
-                                               goal_window=int(g["sdf"]["goal_window"]))
-        if "sweep_weight" in g["sdf"]:
-            d["hyperparameters"]["sdf"].update(sweep_weight=float(g["sdf"]["sweep_weight"]), sweep_substeps=int(g["sdf"]["sweep_substeps"]))
+        for term in TERMS:  # a term's keys, when the guide carries its weight
+            if term.keys[0].hyper in g["sdf"]:
+                for k in term.keys:
+                    v = g["sdf"][k.hyper]
+                    d["hyperparameters"]["sdf"][k.hyper] = [float(x) for x in v] if k.pair else (int(v) if is_int(k) else float(v))
     return d
 
 
@@ -120,6 +120,22 @@ def load_guide_dict(n: int, guide_path: str | None = None) -> dict:
     if n not in GUIDE_CATALOG and n not in EXTRA_GUIDES:
         raise FileNotFoundError(f"guide{n}.yaml not found under {guide_path!r} and not in the built-in catalogue")
     return catalog_guide_dict(n)
+
+
+_REAL = (int, float, np.integer, np.floating)
+
+
+def _check_term(where, term, vals):
+    """the values one guide gives for a term's keys (sdf_terms: check), the float keys stage by stage, then the integer keys"""
+    fl = [(k, v) for k, v in zip(term.keys, vals) if not is_int(k)]
+    if not (all(not isinstance(v, bool) for k, v in fl if k.check == "real") and all(np.shape(v) == ((2,) if k.pair else ()) for k, v in fl)
+            and all(isinstance(v, _REAL) for k, v in fl if k.check == "real") and all(np.isfinite(v).all() for _, v in fl)
+            and all((min(v) if k.pair else v) >= 0 for k, v in fl)):
+        raise ValueError(f"{where}: {' and '.join('sdf.' + k.hyper for k, _ in fl)} must be finite and >= 0"
+                         f"{''.join(f' (sdf.{k.hyper}: two such values)' for k, _ in fl if k.pair)}, got {', '.join(repr(v) for _, v in fl)}")
+    for k, v in zip(term.keys, vals):
+        if is_int(k) and (isinstance(v, bool) or not isinstance(v, (int, np.integer)) or v < k.lo or (k.hi is not None and v > k.hi)):
+            raise ValueError(f"{where}: sdf.{k.hyper} must be {span(k)}, got {v!r}")
 
 
 def build_guide_cfgs(guide_dicts, batch_size_per_guide, T: int, rows_per_guide=None) -> dict:
@@ -159,39 +175,16 @@ def build_guide_cfgs(guide_dicts, batch_size_per_guide, T: int, rows_per_guide=N
             raise ValueError(f"guide {g.get('index', '?')}: guidance_method {g['hyperparameters']['guidance_method']!r} is none of {METHODS}")
     if any(g["hyperparameters"]["guidance_method"] == "sdf" for g in guide_dicts):
         cfgs.update(sdf_rows=np.zeros((B,)), sdf_margin=np.zeros((B, T)), smoothness=np.zeros((B,)))
-    for g in guide_dicts:
-        sd = g["hyperparameters"].get("sdf") or {}
-        sw, sm = sd.get("self_weight", 0.0), sd.get("self_margin", (0.0, 0.0))
-        if not (np.ndim(sw) == 0 and np.shape(sm) == (2,) and np.isfinite(sw) and np.isfinite(sm).all() and sw >= 0 and min(sm) >= 0):
-            raise ValueError(f"guide {g.get('index', '?')}: sdf.self_weight must be finite and >= 0 and sdf.self_margin two such values")
-        if sw > 0 and g["hyperparameters"]["guidance_method"] != "sdf":
-            raise ValueError(f"guide {g.get('index', '?')}: sdf.self_weight > 0 needs guidance_method 'sdf' (the term rides on the SDF rows)")
-        if sw > 0 and "sdf_self_weight" not in cfgs:
-            cfgs.update(sdf_self_weight=np.zeros((B,)), sdf_self_margin=np.zeros((B, T)))
-    for g, first in zip(guide_dicts, np.concatenate([[0], np.cumsum(counts)[:-1]])):
-        sd = g["hyperparameters"].get("sdf") or {}
-        gw, gr, gk = sd.get("goal_weight", 0.0), sd.get("goal_rotation", 0.0), sd.get("goal_window", 8)
-        where = f"guide {g.get('index', '?')} (row {int(first)})"
-        if not (np.ndim(gw) == 0 and np.ndim(gr) == 0 and np.isfinite(gw) and np.isfinite(gr) and gw >= 0 and gr >= 0):
-            raise ValueError(f"{where}: sdf.goal_weight and sdf.goal_rotation must be finite and >= 0, got {gw!r}, {gr!r}")
-        if isinstance(gk, bool) or not isinstance(gk, (int, np.integer)) or gk < 1:
-            raise ValueError(f"{where}: sdf.goal_window must be an integer >= 1, got {gk!r}")
-        if gw > 0 and g["hyperparameters"]["guidance_method"] != "sdf":
-            raise ValueError(f"{where}: sdf.goal_weight > 0 needs guidance_method 'sdf' (the term rides on the SDF rows)")
-        if gw > 0 and "sdf_goal_weight" not in cfgs:
-            cfgs.update(sdf_goal_weight=np.zeros((B,)), sdf_goal_rotation=np.zeros((B,)), sdf_goal_window=np.full((B,), 8, dtype=np.int64))
-    for g, first in zip(guide_dicts, np.concatenate([[0], np.cumsum(counts)[:-1]])):
-        sd = g["hyperparameters"].get("sdf") or {}
-        ww, wk = sd.get("sweep_weight", 0.0), sd.get("sweep_substeps", 4)
-        where = f"guide {g.get('index', '?')} (row {int(first)})"
-        if isinstance(ww, bool) or not (np.ndim(ww) == 0 and isinstance(ww, (int, float, np.integer, np.floating)) and np.isfinite(ww) and ww >= 0):
-            raise ValueError(f"{where}: sdf.sweep_weight must be finite and >= 0, got {ww!r}")
-        if isinstance(wk, bool) or not isinstance(wk, (int, np.integer)) or not 2 <= wk <= 64:
-            raise ValueError(f"{where}: sdf.sweep_substeps must be an integer in 2..64, got {wk!r}")
-        if ww > 0 and g["hyperparameters"]["guidance_method"] != "sdf":
-            raise ValueError(f"{where}: sdf.sweep_weight > 0 needs guidance_method 'sdf' (the term rides on the SDF rows)")
-        if ww > 0 and "sdf_sweep_weight" not in cfgs:
-            cfgs.update(sdf_sweep_weight=np.zeros((B,)), sdf_sweep_substeps=np.full((B,), 4, dtype=np.int32))
+    for term in TERMS:
+        for g, first in zip(guide_dicts, np.concatenate([[0], np.cumsum(counts)[:-1]])):
+            sd = g["hyperparameters"].get("sdf") or {}
+            vals = [sd.get(k.hyper, k.default) for k in term.keys]
+            where = f"guide {g.get('index', '?')} (row {int(first)})"
+            _check_term(where, term, vals)
+            if vals[0] > 0 and g["hyperparameters"]["guidance_method"] != "sdf":
+                raise ValueError(f"{where}: sdf.{term.keys[0].hyper} > 0 needs guidance_method 'sdf' (the term rides on the SDF rows)")
+            if vals[0] > 0 and term.keys[0].cfg not in cfgs:
+                cfgs.update({k.cfg: np.zeros((B, T)) if k.pair else np.full((B,), k.default, dtype=k.cfg_dtype) for k in term.keys})
     r0 = 0
     for g, cnt in zip(guide_dicts, counts):
         rows = slice(r0, r0 + cnt)
@@ -214,16 +207,11 @@ def build_guide_cfgs(guide_dicts, batch_size_per_guide, T: int, rows_per_guide=N
             cfgs["sdf_rows"][rows] = 1
             cfgs["sdf_margin"][rows, :] = np.linspace(m0, m1, T)
             cfgs["smoothness"][rows] = lam
-            if "sdf_self_weight" in cfgs:
-                cfgs["sdf_self_weight"][rows] = float(sd.get("self_weight", 0.0))
-                cfgs["sdf_self_margin"][rows, :] = np.linspace(*sd.get("self_margin", (0.0, 0.0)), T)
-            if "sdf_goal_weight" in cfgs:
-                cfgs["sdf_goal_weight"][rows] = float(sd.get("goal_weight", 0.0))
-                cfgs["sdf_goal_rotation"][rows] = float(sd.get("goal_rotation", 0.0))
-                cfgs["sdf_goal_window"][rows] = int(sd.get("goal_window", 8))
-            if "sdf_sweep_weight" in cfgs:
-                cfgs["sdf_sweep_weight"][rows] = float(sd.get("sweep_weight", 0.0))
-                cfgs["sdf_sweep_substeps"][rows] = int(sd.get("sweep_substeps", 4))
+            for term in TERMS:
+                if term.keys[0].cfg in cfgs:
+                    for k in term.keys:
+                        v = sd.get(k.hyper, k.default)
+                        cfgs[k.cfg][rows] = np.linspace(*v, T) if k.pair else (int(v) if is_int(k) else float(v))
         cfgs["grad_norm"][rows] = 1 if h["grad_norm"] else 0
         gs = h["guidance_schedule"]
         cfgs["guidance_schedule"][rows, :] = (1.4 + np.arange(T) / T) if gs["type"] == "varying" else gs["scale_val"]

@@ -7,45 +7,28 @@ floor of 4 f32 ulps of that largest element.  Every test prints the kernel's err
 EDMP_SDF_PARITY_OUT=<file> the records are also written there as JSON (profiles/sdf_guide_parity.json comes from such a run).  The
 inputs sit >= 1e-5 m away from every decision boundary of the cost (asserted by the checker's generator), so no element is excluded
 from any comparison."""
-import json
-import os
 
 import numpy as np
 import pytest
 import torch
 
 from tests import sdf_reference as R
+from tests import sdf_gpu
+from tests.sdf_gpu import DEV, recorder
 from tests.util import TINY_DIMS, noise_for
 
 pytestmark = pytest.mark.gpu
-DEV = "cuda:0"
 T = R.T
-RECORDS = []
 VOLUME_GATE = 5e-5  # the suite's gate of the iv / sv raw gradient against the f32 oracle (test_gpu_parity.test_gradient_vs_oracle_random)
 
 
-@pytest.fixture(scope="module", autouse=True)
-def _write_records():
-    yield
-    out = os.environ.get("EDMP_SDF_PARITY_OUT")
-    if out:
-        with open(out, "w") as f:
-            json.dump({"gate": "max(4 x CPU-float32 deviation from float64, 4 f32 ulps), relative to the largest element", "records": RECORDS}, f, indent=1)
-
-
-def record(**kw):
-    RECORDS.append(kw)
-    print("[sdf parity]", json.dumps(kw))
+record, _write_records = recorder("sdf parity", "EDMP_SDF_PARITY_OUT", "max(4 x CPU-float32 deviation from float64, 4 f32 ulps), relative to the largest element")
 
 
 def build_guide(case, cfgs=None, **kw):
-    from edmp_amd import franka
-    from edmp_amd.guide import IntersectionVolumeGuide
-
-    cfgs = case["cfgs"] if cfgs is None else cfgs
+    """sdf_gpu.build_guide; a case without a true cylinder hands no kinds over, and "custom" is the named case's sphere table"""
     custom = R.CASES[case["name"]]["spheres"] == "custom" if "name" in case else False
-    return IntersectionVolumeGuide(case["obstacle_config"], DEV, cfgs, cfgs["total_batch_size"], link_mesh_extents=franka.PLACEHOLDER_LINK_EXTENTS,
-                                   obstacle_kinds=case["kinds"] if case["kinds"].any() else None, spheres=case["spheres"] if custom else None, **kw)
+    return sdf_gpu.build_guide(dict(case, custom=custom), cfgs, obstacle_kinds=case["kinds"] if case["kinds"].any() else None, **kw)
 
 
 def get_case(name):

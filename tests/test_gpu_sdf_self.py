@@ -6,9 +6,7 @@ the largest element (for the minimum clearance: to the largest sphere-centre coo
 error, yardstick and gate; with EDMP_SDF_SELF_PARITY_OUT=<file> the records are written there as JSON (profiles/sdf_self_parity.json
 comes from such a run).  The inputs sit >= 1e-5 m from every kink, so no element is excluded from any comparison."""
 import ctypes as C
-import json
 import math
-import os
 
 import numpy as np
 import pytest
@@ -17,50 +15,13 @@ import torch
 from tests import scene_sdf_inputs as SI
 from tests import sdf_reference as R
 from tests import sdf_self_inputs as I
+from tests.sdf_gpu import DEV, build_guide, gradient_and_sumsq, recorder
 from tests.util import TINY_DIMS, noise_for
 
 pytestmark = pytest.mark.gpu
-DEV = "cuda:0"
 T, B = I.T, I.B
-RECORDS = []
-
-
-@pytest.fixture(scope="module", autouse=True)
-def _write_records():
-    yield
-    out = os.environ.get("EDMP_SDF_SELF_PARITY_OUT")
-    if out:
-        with open(out, "w") as f:
-            json.dump({"gate": "max(4 x CPU-float32 deviation from float64, 4 f32 ulps), relative to the largest element", "records": RECORDS}, f, indent=1)
-
-
-def record(**kw):
-    RECORDS.append(kw)
-    print("[sdf self parity]", json.dumps(kw))
-
-
-def build_guide(case, cfgs=None, **kw):
-    from edmp_amd import franka
-    from edmp_amd.guide import IntersectionVolumeGuide
-
-    cfgs = case["cfgs"] if cfgs is None else cfgs
-    return IntersectionVolumeGuide(case["obstacle_config"], DEV, cfgs, cfgs["total_batch_size"], link_mesh_extents=franka.PLACEHOLDER_LINK_EXTENTS,
-                                   obstacle_kinds=case["kinds"], spheres=case["spheres"] if case["custom"] else None, **kw)
-
-
-def gradient_and_sumsq(guide, joints, start, goal, t):
-    """get_gradient with the whole batch's sum g^2 (before mixing) read back as well"""
-    from edmp_amd import _capi
-    from edmp_amd.runtime import ptr
-
-    guide._bind()
-    ctx = guide.ctx
-    ji = ctx.to_dev(np.asarray(joints, dtype=np.float64), torch.float64)
-    n, L = ji.shape[0], ji.shape[2]
-    out, sq = ctx.empty((n, 7, L), torch.float64), ctx.empty((1,), torch.float64)
-    s, g = (np.ascontiguousarray(np.asarray(v, dtype=np.float64).reshape(7)) for v in (start, goal))
-    _capi.check(ctx.lib.edmp_guide_gradient_dev(ctx.h, ptr(ji), n, L, _capi.as_pd(s), _capi.as_pd(g), int(t), ptr(out), ptr(sq)), "edmp_guide_gradient_dev")
-    return ctx.to_host(out), float(ctx.to_host(sq)[0])
+record, _write_records = recorder("sdf self parity", "EDMP_SDF_SELF_PARITY_OUT",
+                                  "max(4 x CPU-float32 deviation from float64, 4 f32 ulps), relative to the largest element")
 
 
 @pytest.mark.parametrize("t", [0, I.T_CHECK])
@@ -331,7 +292,7 @@ def test_refusals():
     with pytest.raises(_capi.EdmpError, match="edmp_sdf_self_rows_dev"):
         guide.sdf_self_rows(np.zeros((2, 7, 63)), 0)
     # a later edmp_sdf_set drops the term: the gradient is that of the ensemble without it, and the report asks for the table again
-    guide._self_on = False
+    guide._term_on["self"] = False
     guide._set_sdf()
     G0 = build_guide(case, cfgs=I.mixed_cfgs(False)).get_gradient(case["joints"], case["start"], case["goal"], I.T_CHECK)
     guide._bind()

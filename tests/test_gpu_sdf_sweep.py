@@ -7,7 +7,6 @@ as sdf_reference.clearance_gate).  Every comparison prints its error, yardstick 
 records are written there as JSON (profiles/sdf_sweep_parity.json comes from such a run).  Waypoints and interpolants sit >= 1e-5 m
 from every kink, so no element is excluded from any comparison."""
 import ctypes as C
-import json
 import math
 import os
 
@@ -18,51 +17,14 @@ import torch
 from tests import scene_sdf_inputs as SI
 from tests import sdf_reference as R
 from tests import sdf_sweep_inputs as I
+from tests.sdf_gpu import DEV, build_guide, gradient_and_sumsq, recorder
 from tests.util import TINY_DIMS, noise_for
 
 pytestmark = pytest.mark.gpu
-DEV = "cuda:0"
 T, B = I.T, I.B
-RECORDS = []
-
-
-@pytest.fixture(scope="module", autouse=True)
-def _write_records():
-    yield
-    out = os.environ.get("EDMP_SDF_SWEEP_PARITY_OUT")
-    if out:
-        with open(out, "w") as f:
-            json.dump({"gate": "max(4 x CPU-float32 deviation from float64, 4 f32 ulps), relative to the largest element; clearance: absolute, "
-                               "floor 4 f32 ulps of the largest coordinate", "records": RECORDS}, f, indent=1)
-
-
-def record(**kw):
-    RECORDS.append(kw)
-    print("[sdf sweep parity]", json.dumps(kw))
-
-
-def build_guide(case, cfgs=None, **kw):
-    from edmp_amd import franka
-    from edmp_amd.guide import IntersectionVolumeGuide
-
-    cfgs = case["cfgs"] if cfgs is None else cfgs
-    return IntersectionVolumeGuide(case["obstacle_config"], DEV, cfgs, cfgs["total_batch_size"], link_mesh_extents=franka.PLACEHOLDER_LINK_EXTENTS,
-                                   obstacle_kinds=case["kinds"], spheres=case["spheres"] if case.get("custom") else None, **kw)
-
-
-def gradient_and_sumsq(guide, joints, start, goal, t):
-    """get_gradient with the whole batch's sum g^2 (before mixing) read back as well"""
-    from edmp_amd import _capi
-    from edmp_amd.runtime import ptr
-
-    guide._bind()
-    ctx = guide.ctx
-    ji = ctx.to_dev(np.asarray(joints, dtype=np.float64), torch.float64)
-    n, L = ji.shape[0], ji.shape[2]
-    out, sq = ctx.empty((n, 7, L), torch.float64), ctx.empty((1,), torch.float64)
-    s, g = (np.ascontiguousarray(np.asarray(v, dtype=np.float64).reshape(7)) for v in (start, goal))
-    _capi.check(ctx.lib.edmp_guide_gradient_dev(ctx.h, ptr(ji), n, L, _capi.as_pd(s), _capi.as_pd(g), int(t), ptr(out), ptr(sq)), "edmp_guide_gradient_dev")
-    return ctx.to_host(out), float(ctx.to_host(sq)[0])
+record, _write_records = recorder("sdf sweep parity", "EDMP_SDF_SWEEP_PARITY_OUT",
+                                  "max(4 x CPU-float32 deviation from float64, 4 f32 ulps), relative to the largest element; clearance: absolute, "
+                                  "floor 4 f32 ulps of the largest coordinate")
 
 
 def clearance_gate(y_abs, coord_max):
@@ -403,7 +365,7 @@ def test_refusals():
     assert np.array_equal(after["cost"], before["cost"]) and np.array_equal(after["clearance"], before["clearance"])
     assert np.array_equal(guide.get_gradient(*args, I.T_CHECK), G)
     # a later edmp_sdf_set drops the term: the gradient is that of the ensemble without it, and the report asks for the row arrays again
-    guide._sweep_on = False
+    guide._term_on["sweep"] = False
     guide._set_sdf()
     G0 = build_guide(case, cfgs=I.mixed_cfgs(case["K"], with_sweep=False)).get_gradient(*args, I.T_CHECK)
     guide._bind()
