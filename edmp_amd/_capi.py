@@ -13,6 +13,7 @@ MAX_SCENES = 16  # EDMP_MAX_SCENES
 MAX_OBSTACLES = 64  # EDMP_MAX_OBSTACLES
 MAX_SPHERES = 128  # EDMP_MAX_SPHERES
 MAX_SWEEP_SUBSTEPS = 64  # EDMP_MAX_SWEEP_SUBSTEPS
+MAX_REPAIR_ITERS = 1024  # EDMP_MAX_REPAIR_ITERS
 
 
 class UNetDesc(C.Structure):
@@ -116,6 +117,8 @@ SIGNATURES = {
     "edmp_sdf_set_sweep": (_i, [_vp, _pd, _pi32, _i]),
     "edmp_sdf_sweep_rows_dev": (_i, [_vp, _vp, _i, _i, _i, _pd, _pd, _i, _vp, _vp]),
     "edmp_scenes_sdf_sweep_rows_dev": (_i, [_vp, _vp, _i, _i, _i, _i, _pd, _pd, _i, _vp, _vp]),
+    "edmp_sdf_repair_rows_dev": (_i, [_vp, _vp, _i, _i, _pd, _pd, _pi32, _i, _i, _i, _d, _d, _d, _d, _vp, _vp, _vp]),
+    "edmp_scenes_sdf_repair_rows_dev": (_i, [_vp, _vp, _i, _i, _i, _pd, _pd, _pi32, _i, _i, _i, _d, _d, _d, _d, _vp, _vp, _vp]),
     "edmp_sdf_rows_dev": (_i, [_vp, _vp, _i, _i, _i, _pd, _pd, _vp, _vp]),
     "edmp_scene_batch_set_sdf": (_i, [_vp, _pf, _i, _pi32, _pd, _pd, _i, _i, _i]),
     "edmp_scenes_sdf_rows_dev": (_i, [_vp, _vp, _i, _i, _i, _i, _pd, _pd, _vp, _vp]),

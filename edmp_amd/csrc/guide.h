@@ -51,6 +51,14 @@ struct SweepTerm : RowTerm {
     std::vector<void*> blocks() const { return {rows, weight, substeps, startgoal}; }
 };
 
+// what a repair call (edmp_sdf_repair_rows_dev) keeps on the device: no term, nothing that a gradient path reads
+struct RepairBlocks {
+    float* startgoal = nullptr;  // [EDMP_MAX_SCENES][14] f32: the pairs of the last call (the guide's own stay what they are)
+    int32_t* rows = nullptr;     // [rows_cap] the listed rows of the last call that listed some, grow-only
+    int rows_cap = 0;
+    std::vector<void*> blocks() const { return {startgoal, rows}; }
+};
+
 // sphere signed-distance guide (sdf.hip, edmp_sdf_set): belongs to the rows it was set for
 struct SdfTable {
     float* sph = nullptr;       // [ns][4] centre | radius in link-box frames, sorted by link
@@ -64,10 +72,11 @@ struct SdfTable {
     SelfTerm self;
     GoalTerm goal;
     SweepTerm sweep;
+    RepairBlocks repair;
     void drop() { n = ns = 0; self.drop(); goal.drop(); sweep.drop(); }  // a new table, or new rows, drop the terms too
     std::vector<void*> blocks() const {  // (guide_destroy): the table's own four and what each term reports
         std::vector<void*> b{sph, rows, margin, smooth};
-        for (const std::vector<void*>& t : {self.blocks(), goal.blocks(), sweep.blocks()}) b.insert(b.end(), t.begin(), t.end());
+        for (const std::vector<void*>& t : {self.blocks(), goal.blocks(), sweep.blocks(), repair.blocks()}) b.insert(b.end(), t.begin(), t.end());
         return b;
     }
 };
@@ -131,11 +140,11 @@ inline int ctx_small_ints(edmp_ctx* ctx) {
 // Which entry points take which kind of bound guide (the two macros below are the whole state check; include/edmp_hip.h states the rest):
 //   single only (EDMP_REFUSE_SCENE_BATCH: refused on a batch of S > 1 scenes, never answered with scene 0's data):
 //     edmp_guide_cost_dev, edmp_guide_swept_cost_dev, edmp_guide_gradient_dev, edmp_row_swept_volumes_dev, edmp_success_rows_dev,
-//     edmp_scene_set_shapes, edmp_sdf_rows_dev; with checks of their own edmp_sdf_set (a batch of ONE scene refused too) and the
+//     edmp_scene_set_shapes, edmp_sdf_rows_dev, edmp_sdf_sweep_rows_dev, edmp_sdf_repair_rows_dev; with checks of their own edmp_sdf_set (a batch of ONE scene refused too) and the
 //     single-scene loops and teacher-forced steps of sampler.hip
 //   batch only (EDMP_REQUIRE_SCENE_BATCH: the bound guide came from edmp_scene_batch_set, a batch of ONE scene included, and holds
 //     exactly S scenes x B rows): edmp_scenes_swept_volumes_dev, edmp_scenes_select_rows_dev, edmp_scenes_success_rows_dev,
-//     edmp_scenes_sdf_rows_dev, edmp_scenes_goal_filter_dev, edmp_scene_batch_set_sdf; edmp_scene_batch_set_shapes (its own wording)
+//     edmp_scenes_sdf_rows_dev, edmp_scenes_sdf_sweep_rows_dev, edmp_scenes_sdf_repair_rows_dev, edmp_scenes_goal_filter_dev, edmp_scene_batch_set_sdf; edmp_scene_batch_set_shapes (its own wording)
 //   either: edmp_rows_set, edmp_scene_read_aabbs, edmp_argmin_dev, edmp_select_row_dev, edmp_metrics_rows_dev (the last three read no guide),
 //     edmp_self_collision_rows_dev (the robot tables only)
 #define EDMP_REFUSE_SCENE_BATCH(g, what)                                                                                          \

@@ -71,6 +71,30 @@
 // a loop that is not unrolled (K is workgroup-uniform and nothing of the kernel's resources depends on it): one chain walk up to the
 // wave's last joint, the sphere loop of its links, and two sets of seven accumulators, (1 - f) x and f x.  Both sets meet in wave 0 as
 // ((w0 + w1) + w2) + w3; lane w then takes its own first set plus lane w-1's second set by one __shfl_up.  No atomics, one order of every sum.
+//
+// Repair of finished rows (sdf_repair_kernel, edmp_sdf_repair_rows_dev / edmp_scenes_sdf_repair_rows_dev): projected descent on the swept
+// cost of a row of the finished state X (., 7, N) f64, between the end of the loop and the selection.  No guide rows, no step t: the call
+// brings the scalars margin m >= 0, smoothness lambda >= 0, substeps K in 1..EDMP_MAX_SWEEP_SUBSTEPS, iters n in 0..EDMP_MAX_REPAIR_ITERS,
+// step eta > 0 and max_step delta > 0.  The interior columns 1..N-2 are the L = N - 2 waypoints, the scene's start / goal pair the ends.
+// Evaluation E(x), all arithmetic in f32 in the statements above:
+//   q_w      = (float) clip(x_w), w = 1..L (lane_joints with do_clip = 1); q_0, q_{L+1} = the f32 casts of start and goal
+//   q(w, k)  = fmaf(f, q_{w+1}, (1 - f) q_w)      f = (float)k / (float)K, w = 0..L, k = 0..K-1, so q(w, 0) = q_w; the goal q_{L+1} joins the set
+//   H        = sum max(0, m - d(c, s))            over every configuration c of the set except start and goal, and every sphere s:
+//                                                 the obstacle part's hinge at margin m plus the sweep term at weight 1 and the same margin
+//   S        = lambda * sum_{w=0..L} ||q_{w+1} - q_w||^2
+//   g        = grad (H + S) with respect to the interior waypoints: an active hinge at q(w, k) sends (1 - f) J^T n to waypoint w and
+//              f J^T n to waypoint w + 1; what would land on start or goal is dropped
+//   cost     = H + S, the hinge terms summed in f64 per lane and wave in (k, link, sphere) order, waves as ((w0 + w1) + w2) + w3, plus the
+//              lane's smoothness term, then wave_sum over the lanes;  clearance = min d over ALL configurations of the set, start and goal included
+// Iteration: for i = 0, 1, ...: evaluate E(x_i); stop with iterations = i if no hinge term is active (H = 0) or i = n; otherwise every
+// interior element moves in f64: delta = min(max(-eta * (double)g, -delta_max), delta_max), x <- min(max(x + delta, qlo_j), qhi_j).  Columns
+// 0 and N-1 are never written; a row that is clear by m at every tested configuration keeps its bits (iterations = 0); iters = 0 is a pure
+// report; at most n + 1 evaluations.  Per row: cost and clearance of evaluation 0 and of the last evaluation, and iterations.  A row with
+// a non-finite element in its interior columns is not touched: iterations = -1, NaN reports.  Rows are independent: no whole-batch norm, no
+// atomics, one order of every sum.  The self-clearance and goal terms are NOT part of the repaired cost: start and goal are pinned, and
+// self_collision_rows stays the check for self-collision.  Layout: the sweep term's (one workgroup per listed row for the WHOLE run of the
+// row, the scene staged once, lane = segment w, k loop from 0, two sets of seven accumulators); wave 0 keeps the row's f64 state, seven
+// values per lane, applies the update and hands the new f32 joints and the stop decision to all four waves through LDS.
 #include "common.h"
 #include "chain.h"
 #include "guide.h"
@@ -713,6 +737,198 @@ __device__ __forceinline__ void sdf_sweep_row(const SweepArgs& sa, const RobotCo
 __global__ __launch_bounds__(256, 2) void sdf_sweep_kernel(SweepArgs a, RobotConst rc) { sdf_sweep_row<false>(a, rc); }
 __global__ __launch_bounds__(256, 5) void sdf_sweep_rows_kernel(SweepArgs a, RobotConst rc) { sdf_sweep_row<true>(a, rc); }
 
+struct RepairArgs {
+    SdfArgs s;            // v.joints = X with ldw = N, off = 1, L = N - 2, do_clip = 1; v.rows: the listed rows, or nullptr = every row;
+                          // startgoal: the call's own block; no margin schedule, no smoothness array
+    double* X;            // (n, 7, N) f64, updated in place
+    int K, iters;
+    float margin, smooth;
+    double step, max_step;
+    double* cost;         // (n, 2): evaluation 0 | the last evaluation
+    double* clearance;    // (n, 2)
+    int32_t* iterations;  // (n,)
+};
+
+// The whole run of one listed row (the definition: "Repair of finished rows" in the header).  sdf_sweep_row's walk with k from 0; both
+// accumulator sets, the f64 hinge sums and the clearances meet in wave 0, which owns the f64 state and the update.
+__global__ __launch_bounds__(256, 2) void sdf_repair_kernel(RepairArgs ra, RobotConst rc) {
+    __shared__ float s_ob[EDMP_MAX_OBSTACLES * 16];
+    __shared__ float s_sph[EDMP_MAX_SPHERES * 4];
+    __shared__ float s_g[3][14][64];  // partials of waves 1..3: [0..6] the (1 - f) set, [7..13] the f set
+    __shared__ double s_c[3][64];     // hinge sums of waves 1..3
+    __shared__ float s_d[3][64];      // clearances of waves 1..3
+    __shared__ float s_q[7][64];      // the padded chain's f32 joints, lane = padded waypoint: wave 0 writes, every wave reads
+    __shared__ int s_stop;            // wave 0's decision: -1 a non-finite row, 1 the run is over, 0 another trip
+    const SdfArgs& a = ra.s;
+    const int lane = threadIdx.x & 63;
+    const int wv = __builtin_amdgcn_readfirstlane(threadIdx.x >> 6);
+    const int r = __builtin_amdgcn_readfirstlane(a.v.rows ? a.v.rows[blockIdx.x] : (int)blockIdx.x);
+    const int scene = __builtin_amdgcn_readfirstlane(a.rps ? r / a.rps : 0);  // (one row, one scene: workgroup-uniform)
+    const int L = a.v.L, N = a.v.ldw, no = min(a.sc_cnt[scene], EDMP_MAX_OBSTACLES);
+    const int K = __builtin_amdgcn_readfirstlane(ra.K), iters = __builtin_amdgcn_readfirstlane(ra.iters);
+    const float* sg = a.startgoal + scene * 14;  // this row's scene's start | goal
+    stage_scene(a.obb + (size_t)a.sc_off[scene] * 16, a.kind + a.sc_off[scene], no, a.spheres, a.ns, s_ob, s_sph);
+
+    // lane = segment w = (padded waypoint w, padded waypoint w + 1); wave 0 holds the f64 element j of interior waypoint w in x[j]
+    const int w = lane;
+    const bool interior = (w >= 1) && (w <= L);
+    const bool segment = w <= L;  // (L <= 62: lane w + 1 exists)
+    double x[7] = {0, 0, 0, 0, 0, 0, 0};
+    if (wv == 0) {
+        float q[7];
+        lane_joints(a.v, rc, r, w, q);
+        bool bad = false;
+#pragma unroll
+        for (int j = 0; j < 7; ++j) {
+            x[j] = a.v.joints[((size_t)r * 7 + j) * N + a.v.off + min(max(w - 1, 0), L - 1)];  // the element lane_joints clipped and cast
+            bad = bad || (interior && !__builtin_isfinite(x[j]));
+            s_q[j][lane] = (w == 0) ? sg[j] : ((w > L) ? sg[7 + j] : q[j]);
+        }
+        const int any_bad = __any(bad ? 1 : 0);
+        if (lane == 0) s_stop = any_bad ? -1 : 0;
+    }
+    __syncthreads();
+    if (__builtin_amdgcn_readfirstlane(s_stop) < 0) {  // (one LDS value behind a barrier: the whole workgroup leaves)
+        if (threadIdx.x == 0) {
+            ra.cost[(size_t)r * 2] = ra.cost[(size_t)r * 2 + 1] = NAN;
+            ra.clearance[(size_t)r * 2] = ra.clearance[(size_t)r * 2 + 1] = NAN;
+            ra.iterations[r] = -1;
+        }
+        return;
+    }
+
+    const float m = ra.margin, lam = ra.smooth;
+    const int my_jmax = wave_last_joint(wv);
+    double cost_last = 0.0;
+    float clr_last = INFINITY;
+    int it = 0;
+    // Barrier uniformity: every trip holds two barriers (meet_in_wave0's and the one behind the update), so all four waves must take the
+    // same number of trips.  The only way out is s_stop, ONE LDS value that wave 0 writes between the two barriers and all 256 threads
+    // read behind the second; meet_in_wave0's `false` does not let waves 1..3 leave, and nothing per-wave or per-lane (an active hinge
+    // of the own link group, the lane's own gradient) may decide.  A workgroup that diverges here hangs.
+    for (;;) {
+        float q0[7], q1[7];
+#pragma unroll
+        for (int j = 0; j < 7; ++j) {
+            q0[j] = s_q[j][lane];
+            q1[j] = __shfl_down(q0[j], 1, 64);
+        }
+        float g[14];
+#pragma unroll
+        for (int i = 0; i < 14; ++i) g[i] = 0.f;
+        double cacc = 0.0;
+        float dmin = INFINITY;
+#pragma unroll 1
+        for (int k = 0; k < K; ++k) {
+            const float f = (float)k / (float)K, f1 = 1.f - f;
+            const bool hinge = (k == 0) ? interior : segment;           // every configuration except start and goal
+            const bool counted = segment || (k == 0 && w == L + 1);     // the clearance sees start and goal too
+            float q[7];
+#pragma unroll
+            for (int j = 0; j < 7; ++j) q[j] = fmaf(f, q1[j], f1 * q0[j]);
+            // sdf_row's walk at the configuration
+            float R[3][3] = {{1, 0, 0}, {0, 1, 0}, {0, 0, 1}};
+            float o[3] = {0, 0, 0};
+            float zax[7][3], org[7][3];
+#pragma unroll
+            for (int j = 0; j < 7; ++j) {
+                if (j > my_jmax) break;  // (wave-uniform)
+                joint_step(rc, q, j, R, o, zax, org);
+#pragma unroll
+                for (int ll = 0; ll < 3; ++ll) {
+                    if (ll > 0 && j != 6) continue;
+                    const int l = (ll == 0) ? j : 6 + ll;  // hand and finger ride on joint 6
+                    if (link_wave(l) != wv) continue;      // another wave's link (wave-uniform)
+                    float LR[3][3], Lo[3];
+                    frame_apply(R, o, rc.sf[l], LR, Lo);
+                    const int s1 = a.link_off[l + 1];
+                    for (int s = a.link_off[l]; s < s1; ++s) {
+                        const float* sp = s_sph + s * 4;
+                        float c[3];
+                        sphere_world(LR, Lo, sp, c);
+                        float best = INFINITY;
+                        int bi = 0;
+                        for (int ob = 0; ob < no; ++ob) {
+                            float p[3], e[3];
+                            const float d = sdf_one(s_ob + ob * 16, c[0], c[1], c[2], p, e);
+                            if (d < best) {
+                                best = d;
+                                bi = ob;
+                            }
+                        }
+                        const float clr = best - sp[3];
+                        const float h = m - clr;
+                        if (counted) dmin = fminf(dmin, clr);
+                        if (hinge && h > 0.f) {
+                            cacc += (double)h;
+                            float n[3];
+                            sdf_grad(s_ob + bi * 16, c[0], c[1], c[2], n);
+#pragma unroll
+                            for (int i = 0; i <= j; ++i) {
+                                const float jn = screw_dot(n, zax[i], org[i], c);  // the hinge turns the sign
+                                g[i] = fmaf(-f1, jn, g[i]);
+                                g[7 + i] = fmaf(-f, jn, g[7 + i]);
+                            }
+                        }
+                    }
+                }
+            }
+        }
+
+        if (wv > 0) {
+            s_c[wv - 1][lane] = cacc;
+            s_d[wv - 1][lane] = dmin;
+        }
+        if (meet_in_wave0<false, 14>(s_g, s_c, wv, lane, g, dmin, cacc)) {  // (waves 1..3 go on to the barrier below)
+            cacc = ((cacc + s_c[0][lane]) + s_c[1][lane]) + s_c[2][lane];
+            dmin = fminf(fminf(fminf(dmin, s_d[0][lane]), s_d[1][lane]), s_d[2][lane]);
+            const bool active = __any(cacc > 0.0 ? 1 : 0) != 0;  // H > 0: some hinge term of the row is active
+            const bool stop = !active || it == iters;            // (wave-uniform)
+            float qp[7], ss = 0.f;
+#pragma unroll
+            for (int j = 0; j < 7; ++j) {
+                qp[j] = __shfl_up(q0[j], 1, 64);
+                const float df = q1[j] - q0[j];
+                ss = fmaf(df, df, ss);
+            }
+            if (segment) cacc += (double)(lam * ss);  // segment (w, w+1), as sdf_row adds it
+            cost_last = wave_sum(cacc);
+            clr_last = wave_min(dmin);
+            if (it == 0 && lane == 0) {
+                ra.cost[(size_t)r * 2] = cost_last;
+                ra.clearance[(size_t)r * 2] = (double)clr_last;
+            }
+            const float l2 = 2.f * lam;
+#pragma unroll
+            for (int i = 0; i < 7; ++i) {
+                const float prev = __shfl_up(g[7 + i], 1, 64);  // segment w - 1 ends at waypoint w
+                const float gi = fmaf(l2, fmaf(2.f, q0[i], -qp[i]) - q1[i], g[i] + prev);  // + 2 lambda (2 q_w - q_{w-1} - q_{w+1})
+                if (!stop && interior) {
+                    const double dx = fmin(fmax(-ra.step * (double)gi, -ra.max_step), ra.max_step);
+                    x[i] = fmin(fmax(x[i] + dx, rc.qlo[i]), rc.qhi[i]);
+                    s_q[i][lane] = (float)x[i];  // (inside the limits: the clip of lane_joints changes nothing)
+                }
+            }
+            if (lane == 0) s_stop = stop ? 1 : 0;
+        }
+        __syncthreads();
+        if (__builtin_amdgcn_readfirstlane(s_stop)) break;  // the same value for all 256 threads
+        ++it;
+    }
+
+    if (wv == 0) {  // it = the updates that were applied
+        if (it > 0 && interior) {
+#pragma unroll
+            for (int j = 0; j < 7; ++j) ra.X[((size_t)r * 7 + j) * N + w] = x[j];
+        }
+        if (lane == 0) {
+            ra.cost[(size_t)r * 2 + 1] = cost_last;
+            ra.clearance[(size_t)r * 2 + 1] = (double)clr_last;
+            ra.iterations[r] = it;
+        }
+    }
+}
+
 static RowView row_view(const Guide* g, const double* joints, int ldw, int off, int L, int t, int do_clip, const int32_t* rows, const double* margin) {
     return RowView{joints, ldw, off, L, t, do_clip, rows, margin, g->rows_T, g->graw, g->rowsq, nullptr, nullptr};
 }
@@ -1248,4 +1464,100 @@ extern "C" int edmp_scenes_sdf_sweep_rows_dev(edmp_ctx* ctx, const double* X_dev
     EDMP_REQUIRE(X_dev && starts && goals && cost_dev && clearance_dev, "edmp_scenes_sdf_sweep_rows_dev: null pointer");
     EDMP_REQUIRE(N >= 3 && N <= 64, "edmp_scenes_sdf_sweep_rows_dev: need 3 <= N <= 64 waypoints per row (got %d)", N);
     return sdf_sweep_rows(ctx, "edmp_scenes_sdf_sweep_rows_dev", X_dev, S, S * B, N, 1, N - 2, t, B, starts, goals, substeps, cost_dev, clearance_dev);
+}
+
+// ---- repair of finished rows -----------------------------------------------------------------------------------------------------------
+// edmp_sdf_repair_rows_dev and edmp_scenes_sdf_repair_rows_dev behind their own state, table and pointer checks: n rows of S scenes of the
+// state X (n, 7, N), starts / goals [S][7], rps as SdfArgs::rps.  Every refusal comes before any device call.  The pairs and the row list
+// go into blocks of the call's own: the guide's pairs, and so a segmented run, stay
+static int sdf_repair_rows(edmp_ctx* ctx, const char* what, double* X_dev, int S, int n, int N, int rps, const double* starts, const double* goals,
+                           const int32_t* rows_host, int n_rows, int substeps, int iters, double margin, double smoothness, double step, double max_step,
+                           double* cost_dev, double* clearance_dev, int32_t* iterations_dev) {
+    Guide* g = ctx->guide;
+    RepairBlocks& rb = g->sdf.repair;
+    EDMP_REQUIRE(N >= 3 && N <= 64, "%s: need 3 <= N <= 64 waypoints per row (got %d)", what, N);
+    EDMP_REQUIRE(substeps >= 1 && substeps <= EDMP_MAX_SWEEP_SUBSTEPS, "%s: substeps %d outside 1..%d", what, substeps, EDMP_MAX_SWEEP_SUBSTEPS);
+    EDMP_REQUIRE(iters >= 0 && iters <= EDMP_MAX_REPAIR_ITERS, "%s: iters %d outside 0..%d", what, iters, EDMP_MAX_REPAIR_ITERS);
+    EDMP_REQUIRE(std::isfinite(margin) && margin >= 0.0, "%s: margin %g must be finite and >= 0", what, margin);
+    EDMP_REQUIRE(std::isfinite(smoothness) && smoothness >= 0.0, "%s: smoothness %g must be finite and >= 0", what, smoothness);
+    EDMP_REQUIRE(std::isfinite(step) && step > 0.0, "%s: step %g must be finite and > 0", what, step);
+    EDMP_REQUIRE(std::isfinite(max_step) && max_step > 0.0, "%s: max_step %g must be finite and > 0", what, max_step);
+    for (int i = 0; i < S * 7; ++i) EDMP_REQUIRE(std::isfinite(starts[i]) && std::isfinite(goals[i]), "%s: scene %d: non-finite start / goal", what, i / 7);
+    if (rows_host) {  // two workgroups on one row would race
+        EDMP_REQUIRE(n_rows >= 1 && n_rows <= n, "%s: %d listed rows outside 1..%d", what, n_rows, n);
+        std::vector<char> seen((size_t)n, 0);
+        for (int i = 0; i < n_rows; ++i) {
+            EDMP_REQUIRE(rows_host[i] >= 0 && rows_host[i] < n, "%s: rows[%d] = %d outside 0..%d", what, i, (int)rows_host[i], n - 1);
+            EDMP_REQUIRE(!seen[rows_host[i]], "%s: rows[%d] = %d is listed twice", what, i, (int)rows_host[i]);
+            seen[rows_host[i]] = 1;
+        }
+    }
+    const int launch = rows_host ? n_rows : n;
+    EDMP_HIP_CHECK(hipSetDevice(ctx->device));
+    if (!rb.startgoal)
+        if (int rc = ctx_alloc(ctx, (void**)&rb.startgoal, EDMP_MAX_SCENES * 14 * sizeof(float))) return rc;
+    if (rows_host && rb.rows_cap < n_rows) {
+        EDMP_HIP_CHECK(hipStreamSynchronize(ctx->stream));  // nothing enqueued still reads the list that goes
+        ctx_release(ctx, rb.rows);
+        rb.rows = nullptr;
+        rb.rows_cap = 0;
+        if (int rc = ctx_alloc(ctx, (void**)&rb.rows, (size_t)n_rows * sizeof(int32_t))) return rc;
+        rb.rows_cap = n_rows;
+    }
+    float sg[EDMP_MAX_SCENES * 14];
+    for (int s = 0; s < S; ++s)
+        for (int i = 0; i < 7; ++i) {
+            sg[s * 14 + i] = (float)starts[s * 7 + i];
+            sg[s * 14 + 7 + i] = (float)goals[s * 7 + i];
+        }
+    EDMP_HIP_CHECK(hipMemcpyAsync(rb.startgoal, sg, (size_t)S * 14 * sizeof(float), hipMemcpyHostToDevice, ctx->stream));
+    if (rows_host) EDMP_HIP_CHECK(hipMemcpyAsync(rb.rows, rows_host, (size_t)n_rows * sizeof(int32_t), hipMemcpyHostToDevice, ctx->stream));
+    RepairArgs a;
+    fill_args(g, a.s, X_dev, N, 1, N - 2, 0, 1);  // the full state with its start / goal columns, clipped as the guide clips; no step
+    a.s.v.rows = rows_host ? rb.rows : nullptr;
+    a.s.smooth = nullptr;
+    a.s.rps = rps;
+    a.s.startgoal = rb.startgoal;
+    a.X = X_dev;
+    a.K = substeps;
+    a.iters = iters;
+    a.margin = (float)margin;
+    a.smooth = (float)smoothness;
+    a.step = step;
+    a.max_step = max_step;
+    a.cost = cost_dev;
+    a.clearance = clearance_dev;
+    a.iterations = iterations_dev;
+    hipLaunchKernelGGL(sdf_repair_kernel, dim3(launch), dim3(256), 0, ctx->stream, a, g->rc);
+    const hipError_t e = hipGetLastError();
+    EDMP_HIP_CHECK(hipStreamSynchronize(ctx->stream));  // the host pairs live on this frame, the list in the caller's array
+    EDMP_HIP_CHECK(e);
+    return EDMP_OK;
+}
+
+extern "C" int edmp_sdf_repair_rows_dev(edmp_ctx* ctx, double* X_dev, int n, int N, const double* start, const double* goal, const int32_t* rows_host,
+                                        int n_rows, int substeps, int iters, double margin, double smoothness, double step, double max_step,
+                                        double* cost_dev, double* clearance_dev, int32_t* iterations_dev) {
+    EDMP_REQUIRE(ctx && ctx->guide && ctx->guide->obb, "edmp_sdf_repair_rows_dev: scene not set");
+    EDMP_REFUSE_SCENE_BATCH(ctx->guide, "edmp_sdf_repair_rows_dev");
+    EDMP_REQUIRE(ctx->guide->sdf.ns > 0, "edmp_sdf_repair_rows_dev: call edmp_sdf_set first (the sphere table)");
+    EDMP_REQUIRE(X_dev && start && goal && cost_dev && clearance_dev && iterations_dev, "edmp_sdf_repair_rows_dev: null pointer");
+    EDMP_REQUIRE(n >= 1, "edmp_sdf_repair_rows_dev: need n >= 1 rows (got %d)", n);
+    return sdf_repair_rows(ctx, "edmp_sdf_repair_rows_dev", X_dev, 1, n, N, 0, start, goal, rows_host, n_rows, substeps, iters, margin, smoothness, step,
+                           max_step, cost_dev, clearance_dev, iterations_dev);
+}
+
+// edmp_sdf_repair_rows_dev for a bound scene batch: every row against its own scene's primitives, kinds and start / goal pair
+extern "C" int edmp_scenes_sdf_repair_rows_dev(edmp_ctx* ctx, double* X_dev, int S, int B, int N, const double* starts, const double* goals,
+                                               const int32_t* rows_host, int n_rows, int substeps, int iters, double margin, double smoothness, double step,
+                                               double max_step, double* cost_dev, double* clearance_dev, int32_t* iterations_dev) {
+    EDMP_REQUIRE_SCENE_BATCH(ctx, S, B, "edmp_scenes_sdf_repair_rows_dev");
+    if (ctx->guide->sdf.ns <= 0) {
+        set_error("edmp_scenes_sdf_repair_rows_dev: call edmp_scene_batch_set_sdf first (the sphere table)");
+        return EDMP_ERR_STATE;
+    }
+    EDMP_REQUIRE(X_dev && starts && goals && cost_dev && clearance_dev && iterations_dev, "edmp_scenes_sdf_repair_rows_dev: null pointer");
+    // rps = B forced, for a batch of ONE scene too (rows / B = 0)
+    return sdf_repair_rows(ctx, "edmp_scenes_sdf_repair_rows_dev", X_dev, S, S * B, N, B, starts, goals, rows_host, n_rows, substeps, iters, margin, smoothness,
+                           step, max_step, cost_dev, clearance_dev, iterations_dev);
 }

@@ -382,6 +382,30 @@ class _SlotObject:
                    0 if substeps is None else int(substeps), C.c_void_p(out[0].data_ptr()), C.c_void_p(out[1].data_ptr()))
         return self._cost_clearance(out, shape)
 
+    def _repair(self, X, Xd, shape, N, pair, iters, substeps, margin, smoothness, step, max_step, rows, return_device):
+        """projected descent on the swept SDF cost of the (rows, 7, N) device state Xd (made from the caller's X) -> the repair dict, per-row
+        arrays `shape`d.  Always out of place: a device tensor of the caller's is cloned first, the kernel runs in place on the clone."""
+        ctx, n = self.ctx, int(np.prod(shape))
+        with torch.cuda.stream(ctx.stream):
+            if isinstance(X, torch.Tensor) and X.is_cuda:
+                Xd = Xd.clone()  # (_rows_f64 hands an f64 contiguous device tensor through as it is)
+            rep = torch.full((2, n, 2), float("nan"), dtype=torch.float64, device=ctx.device)  # rows outside `rows` are not written
+            its = torch.zeros((n,), dtype=torch.int32, device=ctx.device)
+        listed = None if rows is None else np.ascontiguousarray(np.asarray(rows, dtype=np.int32).reshape(-1))
+        self._call("edmp_sdf_repair_rows_dev", "edmp_scenes_sdf_repair_rows_dev", shape, ptr(Xd), *shape, N, _capi.as_pd(pair[0]), _capi.as_pd(pair[1]),
+                   None if listed is None else _capi.as_pi32(listed), 0 if listed is None else int(listed.shape[0]), int(substeps), int(iters), float(margin),
+                   float(smoothness), float(step), float(max_step), C.c_void_p(rep[0].data_ptr()), C.c_void_p(rep[1].data_ptr()), ptr(its))
+        keys = ("cost0", "cost", "clearance0", "clearance")
+        if return_device:
+            out = dict(trajectories=Xd.view(*shape, 7, N), iterations=its.view(*shape))
+            out.update({k: rep[i // 2, :, i % 2].view(*shape) for i, k in enumerate(keys)})
+            ctx.hand_over(Xd)  # (the caller's torch ops on the results follow this context's stream)
+            return out
+        h = ctx.to_host(rep)
+        out = dict(trajectories=ctx.to_host(Xd).reshape(*shape, 7, N), iterations=ctx.to_host(its).reshape(shape))
+        out.update({k: h[i // 2, :, i % 2].reshape(shape).copy() for i, k in enumerate(keys)})
+        return out
+
 
 class IntersectionVolumeGuide(_SlotObject):
     """Same constructor / method signatures as the reference:
@@ -422,6 +446,9 @@ class IntersectionVolumeGuide(_SlotObject):
     pay the obstacle hinge at the ``sdf_sweep_substeps`` - 1 joint-space interpolants of every segment of start, waypoints, goal: the
     configurations the success check tests between the waypoints.  sdf_sweep_rows(...) reports the term's cost and every row's minimum
     clearance over those interpolants.
+
+    After the loop: repair_rows(...) moves finished rows by projected descent on the same sphere model's hinge at the waypoints and those
+    interpolants (csrc/sdf.hip: sdf_repair_kernel), on any guide - it brings its own scalars and needs no SDF rows.
     """
 
     def __init__(self, obstacle_config, device, guide_cfgs, batch_size, *, link_mesh_extents=None, mesh_dir=None, obstacle_kinds=None, bind=True,
@@ -648,6 +675,29 @@ class IntersectionVolumeGuide(_SlotObject):
         else:
             self._bind_sdf()
         return self._sweep_report(X, (X.shape[0],), X.shape[2], t, _pair7(start, goal), substeps)
+
+    def repair_rows(self, trajectories, start, goal, iters=32, substeps=4, margin=0.02, smoothness=0.5, step=0.02, max_step=0.02, rows=None,
+                    return_device=False):
+        """Repair finished rows by projected descent on the swept SDF cost (edmp_sdf_repair_rows_dev, one launch for the whole run of every
+        row): trajectories (n, 7, N) f64, ndarray or device tensor, the FULL state - its interior columns 1..N-2 are the waypoints, start /
+        goal the pinned ends.  Per iteration a row's cost is the obstacle hinge at ``margin`` over the sphere model at every waypoint AND at
+        the ``substeps`` - 1 joint-space interpolants of every segment (with the success check's ``substeps`` both look at the same
+        configurations) plus ``smoothness`` times the squared segment lengths; every interior element moves by
+        -``step`` x gradient, clamped to +-``max_step`` [rad] and to the joint limits.  A row stops as soon as no hinge term is active, or
+        after ``iters`` updates; a row that is clear from the start keeps its bits.  Returns dict(trajectories (n, 7, N), cost0 / cost and
+        clearance0 / clearance (n,) f64 of the first / last evaluation - clearance = the smallest sphere clearance over all tested
+        configurations, start and goal included -, iterations (n,) int32: updates applied, -1 for a row with a non-finite interior element,
+        which is left as it is with NaN reports).  ``rows``: the row indices to work on (any order, no duplicates); the others keep their
+        bits and report NaN and 0 iterations.  Always out of place: the input is never modified.  The defaults are the values of one CPU
+        experiment on three constructed scenes (tests/repair_inputs.py) - illustrative, not tuned.  The self-clearance and goal terms are
+        not part of the repaired cost (self_collision_rows stays the check).  A guide built without SDF rows and without ``spheres`` uses
+        the default sphere model.  Leaves a segmented run running."""
+        X = self._rows_f64(trajectories)
+        if X.dim() != 3 or X.shape[1] != 7:
+            raise ValueError(f"trajectories must be (n, 7, N), got {tuple(X.shape)}")
+        self._bind_sdf()
+        return self._repair(trajectories, X, (X.shape[0],), X.shape[2], _pair7(start, goal), iters, substeps, margin, smoothness, step, max_step, rows,
+                            return_device)
 
     def row_swept_volumes(self, start, goal, trajectories):
         """(B,) f32 t=0 swept volume per row and the argmin (first on ties)."""
@@ -1030,6 +1080,19 @@ class SceneBatch(_SlotObject):
         else:
             self._bind_sdf()
         out = self._sweep_report(Xd, (self.n_scenes, self.batch_size), N, t, pair, substeps)
+        Xd.record_stream(self.ctx.stream)
+        return out
+
+    def repair_rows(self, trajectories, starts, goals, iters=32, substeps=4, margin=0.02, smoothness=0.5, step=0.02, max_step=0.02, rows=None,
+                    return_device=False):
+        """IntersectionVolumeGuide.repair_rows for every scene in one launch (edmp_scenes_sdf_repair_rows_dev): the (S, B, 7, N) /
+        (S*B, 7, N) state, each row against its own scene's primitives, kinds and start / goal pair -> the same dict with trajectories
+        (S, B, 7, N) and (S, B) per-row arrays; scene s's values are what guides[s].repair_rows gives for X[s].  ``rows`` indexes the S*B
+        rows scene after scene.  Out of place; leaves a segmented run running."""
+        pair = _pairs(self.n_scenes, starts, goals)
+        Xd, N = self._state(trajectories)
+        self._bind_sdf()
+        out = self._repair(trajectories, Xd, (self.n_scenes, self.batch_size), N, pair, iters, substeps, margin, smoothness, step, max_step, rows, return_device)
         Xd.record_stream(self.ctx.stream)
         return out
 

@@ -35,6 +35,7 @@ extern "C" {
 #define EDMP_MAX_SCENES 16
 #define EDMP_MAX_SPHERES 128
 #define EDMP_MAX_SWEEP_SUBSTEPS 64 /* edmp_sdf_set_sweep: interpolants per segment + 1 */
+#define EDMP_MAX_REPAIR_ITERS 1024 /* edmp_sdf_repair_rows_dev: a cap so that a launch stays bounded, not a tuned value */
 
 typedef struct edmp_ctx edmp_ctx;
 
@@ -232,6 +233,39 @@ int edmp_sdf_sweep_rows_dev(edmp_ctx* ctx, const double* joints_dev, int n, int 
                             double* cost_dev, double* clearance_dev);
 int edmp_scenes_sdf_sweep_rows_dev(edmp_ctx* ctx, const double* X_dev, int S, int B, int N, int t, const double* starts, const double* goals,
                                    int substeps, double* cost_dev, double* clearance_dev);
+/* Repair of finished rows: projected descent on the swept SDF cost, one 256-thread workgroup per listed row for the whole run of the row
+ * (sdf_repair_kernel; no launch per iteration).  X_dev (n, 7, N) f64 is updated IN PLACE: the interior columns 1..N-2 are the L = N - 2
+ * waypoints, start / goal form the padded ends (columns 0 and N-1 are never read as joints and never written).  Per call: margin m >= 0,
+ * smoothness lambda >= 0, substeps K in 1..EDMP_MAX_SWEEP_SUBSTEPS, iters n in 0..EDMP_MAX_REPAIR_ITERS, step eta > 0, max_step delta > 0.
+ * Evaluation E(x), all arithmetic in f32 in the statements of the SDF kernels (csrc/sdf.hip):
+ *   q_w = (float) clip(x_w) for w = 1..L, q_0 / q_{L+1} the f32 casts of start / goal;
+ *   q(w, k) = fmaf(f, q_{w+1}, (1 - f) q_w), f = (float)k / (float)K, w = 0..L, k = 0..K-1 (q(w, 0) = q_w), and the goal q_{L+1};
+ *   H = sum max(0, m - d(c, s)) over every such configuration c except start and goal and over every sphere s - the obstacle part's hinge
+ *       of edmp_sdf_set at margin m plus the sweep term at weight 1 and the same margin, with their sub-gradient conventions;
+ *   S = lambda * sum_{w=0..L} ||q_{w+1} - q_w||^2;   g = grad (H + S) with respect to the interior waypoints (an active hinge at q(w, k)
+ *       sends (1 - f) J^T n to waypoint w and f J^T n to waypoint w + 1; what would land on start or goal is dropped);
+ *   cost = H + S with the hinge terms summed in f64; clearance = min d over ALL of the configurations, start and goal included.
+ * Iteration, for i = 0, 1, ...: evaluate E(x_i); if no hinge term is active (H = 0) or i = n, stop with iterations = i; otherwise every
+ * interior element moves in f64 by delta = min(max(-eta * (double)g, -max_step), max_step), x <- min(max(x + delta, qlo_j), qhi_j) with
+ * the joint limits of the robot table.  So a row that is clear by m at every tested configuration keeps its bits (iterations = 0),
+ * iters = 0 is a pure report, and there are at most n + 1 evaluations.  Outputs, written for the listed rows only: cost_dev (n, 2) and
+ * clearance_dev (n, 2) f64 = evaluation 0 | the last evaluation; iterations_dev (n,) int32.  A row with a non-finite element in its
+ * interior columns is not touched: iterations = -1 and NaN in both pairs.  rows_host: n_rows row indices (host, any order, no
+ * duplicates), or NULL = every row (n_rows is ignored); a row outside the list keeps its bits in X and its report entries are not
+ * written.  Rows are independent (no whole-batch norm, no atomics, one order of every sum).  The self-clearance and goal terms are NOT
+ * part of the repaired cost.  edmp_sdf_repair_rows_dev needs a single-scene guide with a sphere table (edmp_sdf_set), any n >= 1;
+ * edmp_scenes_sdf_repair_rows_dev a bound scene batch with the table of edmp_scene_batch_set_sdf, X (S*B, 7, N), each row against its
+ * own scene's primitives, kinds and pair.  Refusals (3 <= N <= 64, K and iters in range, margin and smoothness finite and >= 0, step and
+ * max_step finite and > 0, start / goal finite, rows in range and without duplicates) come before any device call, name the offending
+ * value, and leave X and the context untouched.  The start / goal pairs go into a block of the call's own: the calls replace no pair of
+ * the guide, read nothing of the sampler and do NOT end a segmented run.  They synchronise the stream (pairs and list are read from the
+ * caller's arrays). */
+int edmp_sdf_repair_rows_dev(edmp_ctx* ctx, double* X_dev, int n, int N, const double* start, const double* goal, const int32_t* rows_host,
+                             int n_rows, int substeps, int iters, double margin, double smoothness, double step, double max_step,
+                             double* cost_dev, double* clearance_dev, int32_t* iterations_dev);
+int edmp_scenes_sdf_repair_rows_dev(edmp_ctx* ctx, double* X_dev, int S, int B, int N, const double* starts, const double* goals,
+                                    const int32_t* rows_host, int n_rows, int substeps, int iters, double margin, double smoothness, double step,
+                                    double max_step, double* cost_dev, double* clearance_dev, int32_t* iterations_dev);
 
 /* ---- plan success: the reference's simulator check, restated geometrically ------------------------------------ */
 /* The guide sees every obstacle as a box (cylinders enter as (r, r, h) boxes, datasets/load_test_dataset.py:136-139) but the
@@ -335,7 +369,8 @@ int edmp_denoise_guided_dev(edmp_ctx* ctx, const double* noise_dev, int B, const
  * continuing segment after any of them is refused.  A run started with guided = 0 cannot be continued with guided = 1 (the guide
  * never received its pair).  Calls that read neither the guide's start / goal pairs, nor the sampler, nor the model's buffers leave a run
  * as it stands, and the next segment continues as if they had not been made: edmp_scenes_goal_filter_dev, edmp_ik_solve_dev,
- * edmp_self_collision_rows_dev, edmp_sdf_self_rows_dev, edmp_sdf_goal_rows_dev, edmp_sdf_sweep_rows_dev and edmp_scenes_sdf_sweep_rows_dev.
+ * edmp_self_collision_rows_dev, edmp_sdf_self_rows_dev, edmp_sdf_goal_rows_dev, edmp_sdf_sweep_rows_dev, edmp_scenes_sdf_sweep_rows_dev,
+ * edmp_sdf_repair_rows_dev and edmp_scenes_sdf_repair_rows_dev.
  * start / goal are read by the init segment only (uploaded once, kept on the device); a continuing segment IGNORES its start /
  * goal arguments and goes on with the init segment's pair. */
 int edmp_denoise_guided_segment_dev(edmp_ctx* ctx, const double* noise_dev, int B, const double* start, const double* goal,

@@ -121,7 +121,17 @@ class _NoiseFeeder:
         self.thread.join()
 
 
-def job_summary(results, world=1, self_collision=False):
+def repair_tally(rep, iters, margin):
+    """what a repair_rows dict says about its rows, per row: moved (iterations > 0) and ended clear (the last evaluation had no active
+    hinge term).  A row that stopped before `iters` stopped BECAUSE no hinge was active; one that used all of them is counted clear when
+    its last clearance - over every tested configuration, start and goal included - is at least the margin as the kernel holds it (f32),
+    which leaves out only a row whose pinned start or goal itself sits inside the margin."""
+    it = np.asarray(rep["iterations"].cpu() if isinstance(rep["iterations"], torch.Tensor) else rep["iterations"])
+    clr = np.asarray(rep["clearance"].cpu() if isinstance(rep["clearance"], torch.Tensor) else rep["clearance"])
+    return it > 0, (it >= 0) & ((it < int(iters)) | (clr >= float(np.float32(margin))))
+
+
+def job_summary(results, world=1, self_collision=False, repair=False):
     """This rank's tallies; under a launcher the sum over all ranks (all_gather_object of five small integers per rank - the
     trajectories stay where they were planned).  Keys: scenes, success_proxy (the reference's tally), success_strict, rows_collision_free, rows."""
     mine = dict(scenes=len(results), success_proxy=sum(r["success_proxy"] for r in results), success_strict=sum(r["success_strict"] for r in results),
@@ -129,6 +139,8 @@ def job_summary(results, world=1, self_collision=False):
                 planning_time_s=float(sum(r["planning_time_s"] for r in results)))
     if self_collision:  # (run(..., self_collision=True): every rank's results carry the keys)
         mine.update(self_collision_free=sum(r["self_collision_free"] for r in results), rows_self_collision_free=sum(r["rows_self_collision_free"] for r in results))
+    if repair:  # (run(..., repair=ITERS): every rank's results carry the keys)
+        mine.update(rows_repaired=sum(r["rows_repaired"] for r in results), rows_repair_clear=sum(r["rows_repair_clear"] for r in results))
     if world <= 1:
         return dict(mine, ranks=1)
     import torch.distributed as dist
@@ -142,7 +154,7 @@ def job_summary(results, world=1, self_collision=False):
 
 
 def run(cfg_path, dataset=None, max_scenes=None, verbose=True, scenes_in_flight=1, shard_scenes=True, scenes_per_launch=1, ensemble_report=False, prefer=None,
-        ik_seeds=0, ik_tool=None, ik_seed=0, self_collision=False, device_noise=None):
+        ik_seeds=0, ik_tool=None, ik_seed=0, self_collision=False, device_noise=None, repair=0, repair_margin=0.02, repair_step=0.02):
     """The reference's scene loop (infer_serial.py:95-170).  Under ``torch.distributed.run`` (one process per GPU, extension: the
     reference is one process) the scenes are dealt round-robin to the ranks - scene i of the cfg's order goes to rank i mod world -
     and nothing is exchanged until `job_summary` adds the tallies up: scenes are independent problems, this is the problem set's natural
@@ -198,7 +210,14 @@ def run(cfg_path, dataset=None, max_scenes=None, verbose=True, scenes_in_flight=
 
     With ensemble_report a run with an SDF guide also adds ``min_swept_clearance`` next to ``min_clearance``: the chosen plan's smallest
     sphere clearance over the joint-space interpolants the success check tests between the waypoints (sdf_sweep_rows; the row's own
-    ``sweep_substeps`` where it carries the swept-clearance term, sample guide 104, else the check's CHECK_SUBSTEPS)."""
+    ``sweep_substeps`` where it carries the swept-clearance term, sample guide 104, else the check's CHECK_SUBSTEPS).
+
+    ``repair`` = ITERS > 0 (an extension; 0 = off: nothing is launched and every printed and returned value is what it was) sends the whole
+    finished batch through repair_rows after the loop and before the selection and the success check (IntersectionVolumeGuide.repair_rows;
+    a scene group through SceneBatch.repair_rows in one launch): at most ITERS projected descent steps of ``repair_step`` on the sphere
+    model's hinge at ``repair_margin`` over the waypoints and the CHECK_SUBSTEPS - 1 interpolants per segment that the success check tests.
+    Everything behind it sees the repaired rows.  Each result adds `rows_repaired` (rows that moved), `rows_repair_clear` (rows whose last
+    evaluation had no active hinge, repair_tally) and `repair_iters`; the per-scene line and the summary print the two counts."""
     from concurrent.futures import ThreadPoolExecutor
 
     from edmp_amd.runtime import get_context, lane_context
@@ -209,6 +228,9 @@ def run(cfg_path, dataset=None, max_scenes=None, verbose=True, scenes_in_flight=
         raise ValueError(f"scenes_per_launch must be >= 1, got {scenes_per_launch}")
     if kl > 1 and int(scenes_in_flight) > 1:
         raise ValueError("scenes_per_launch > 1 and scenes_in_flight > 1 do not combine: choose one")
+    repair = int(repair)
+    if repair < 0:
+        raise ValueError(f"repair must be >= 0 iterations (0 = off), got {repair}")
     if device_noise is not None:
         DeviceNoise(device_noise)  # (an integer in [0, 2^64), or it raises)
     benchmark_cfg = GC.load_yaml(cfg_path)
@@ -324,10 +346,19 @@ def run(cfg_path, dataset=None, max_scenes=None, verbose=True, scenes_in_flight=
         tb = time.time()
         if pinned is not None:
             feeder.recycle(pinned)  # (denoise_guided returned host trajectories: the upload out of the buffer is long done)
+        tm["denoise_s"] = tb - ta
+        repaired = {}
+        if repair:  # the whole batch, between the loop and the selection
+            rep = guide.repair_rows(trajectories, start_joints, goal_joints, iters=repair, substeps=CHECK_SUBSTEPS, margin=repair_margin, step=repair_step)
+            trajectories = rep["trajectories"]
+            moved, clear = repair_tally(rep, repair, repair_margin)
+            repaired = dict(rows_repaired=int(moved.sum()), rows_repair_clear=int(clear.sum()), repair_iters=int(repair))
+            tm["repair_s"] = time.time() - tb
+            tb = time.time()
         idx, vols, met = guide.select_row(start_joints, goal_joints, trajectories, prefer=prefer)
         trajectory = trajectories[idx]
         t_plan = time.time() - t0
-        tm["denoise_s"], tm["best_trajectory_s"] = tb - ta, time.time() - tb
+        tm["best_trajectory_s"] = time.time() - tb
         if ensemble_report and met is None:
             te = time.time()
             met = guide.metrics_rows(trajectories)
@@ -349,7 +380,7 @@ def run(cfg_path, dataset=None, max_scenes=None, verbose=True, scenes_in_flight=
                        if ensemble_report and guide.has_sdf_rows else {}),
                     **({"min_self_clearance": float(guide.sdf_self_rows(trajectory[None, :, 1:-1])["clearance"][0])} if ensemble_report and guide.has_self_term else {}),
                     **(goal_extras(guide.sdf_goal_rows(trajectory[None, :, 1:]), 0) if ensemble_report and guide.has_goal_term else {}),  # (the goal column is the last handed one)
-                    **(self_extras(guide.self_collision_rows(trajectories), idx) if self_collision else {}), **extras(vols, chk, met))
+                    **(self_extras(guide.self_collision_rows(trajectories), idx) if self_collision else {}), **repaired, **extras(vols, chk, met))
 
     t_success, t_strict, i, results, pending = 0, 0, 0, [], []
     t_self = 0
@@ -375,6 +406,8 @@ def run(cfg_path, dataset=None, max_scenes=None, verbose=True, scenes_in_flight=
                 print(f"    chosen plan: minimum self clearance {r['min_self_clearance']:.4f} m")
             if "position_error" in r:  # (the guide carries the goal term: the final tool pose against the target)
                 print(f"    chosen plan: position_error {r['position_error']:.3f} cm, orientation_error {r['orientation_error']:.3f} deg")
+        if verbose and "rows_repaired" in r:
+            print(f"    repair ({r['repair_iters']} iterations at most): {r['rows_repaired']}/{r['rows']} rows moved, {r['rows_repair_clear']}/{r['rows']} ended clear")
         if "self_collision_free" in r:
             t_self += r["self_collision_free"]
             if verbose:
@@ -438,6 +471,13 @@ def run(cfg_path, dataset=None, max_scenes=None, verbose=True, scenes_in_flight=
         tb = time.time()
         for st in streams if feeder is not None else ():
             feeder.recycle(st)  # (the call synchronised before it returned the device state: every upload out of the buffers is done)
+        t_rep, moved, clear = None, None, None
+        if repair:  # the whole group in one launch, between the loop and the selection; the repaired state stays on the device
+            rep = batch.repair_rows(Xd, starts, goals, iters=repair, substeps=CHECK_SUBSTEPS, margin=repair_margin, step=repair_step, return_device=True)
+            Xd = rep["trajectories"]
+            moved, clear = repair_tally(rep, repair, repair_margin)
+            t_rep = time.time() - tb
+            tb = time.time()
         # the finished (S, B, C, N) state stays on the device and is scored as ONE batch: per-scene volumes + pick, per-scene success
         # flags + counts, and the metrics of all S * B rows (they need no scene) - three calls for the group, not four per scene
         idxs, all_vols, all_met = batch.select_rows(starts, goals, Xd, prefer=prefer)
@@ -467,7 +507,9 @@ def run(cfg_path, dataset=None, max_scenes=None, verbose=True, scenes_in_flight=
             if t_met is not None:
                 tm["batch_metrics_s"] = t_met  # the whole group's call
             trajectory = trajectories[idx]
-            tm["denoise_s"] = tb - ta  # the whole group's loop
+            tm["denoise_s"] = tb - ta - (t_rep or 0.0)  # the whole group's loop
+            if t_rep is not None:
+                tm["repair_s"] = t_rep  # the whole group's call
             tm["denoise_s_is"] = f"group of {len(group)} scenes"
             tm["best_trajectory_s"], tm["success_check_s"] = tc - tb, te - td  # the whole group's calls
             t_plan = time.time() - t0
@@ -480,7 +522,9 @@ def run(cfg_path, dataset=None, max_scenes=None, verbose=True, scenes_in_flight=
                             **({"min_swept_clearance": float(all_swp[s][idx])} if all_swp is not None else {}),
                             **({"min_self_clearance": float(all_sclr[s][idx])} if all_sclr is not None else {}),
                             **(goal_extras({k: v[s] for k, v in all_goal.items()}, idx) if all_goal is not None else {}),
-                            **(self_extras({k: v[s] for k, v in all_self.items()}, idx) if all_self is not None else {}), **extras(vols, chk, met)))
+                            **(self_extras({k: v[s] for k, v in all_self.items()}, idx) if all_self is not None else {}),
+                            **(dict(rows_repaired=int(moved[s].sum()), rows_repair_clear=int(clear[s].sum()), repair_iters=int(repair)) if moved is not None else {}),
+                            **extras(vols, chk, met)))
         return out
 
     try:
@@ -522,12 +566,14 @@ def run(cfg_path, dataset=None, max_scenes=None, verbose=True, scenes_in_flight=
         if feeder is not None:
             feeder.close()
     if world > 1 or verbose:
-        summary = job_summary(results, world, self_collision)
+        summary = job_summary(results, world, self_collision, bool(repair))
         if verbose and rank == 0:
             print(f"[infer_serial] {summary['scenes']} scenes on {summary['ranks']} rank(s): success (proxy, collision-free) {summary['success_proxy']}/{summary['scenes']}, "
                   f"strict {summary['success_strict']}/{summary['scenes']}, rows collision-free {summary['rows_collision_free']}/{summary['rows']}")
             if "self_collision_free" in summary:
                 print(f"[infer_serial] self-collision free {summary['self_collision_free']}/{summary['scenes']}, rows {summary['rows_self_collision_free']}/{summary['rows']}")
+            if "rows_repaired" in summary:
+                print(f"[infer_serial] repair: {summary['rows_repaired']}/{summary['rows']} rows moved, {summary['rows_repair_clear']}/{summary['rows']} ended clear")
         run.last_summary = summary
     return results
 
@@ -554,6 +600,10 @@ def main(argv=None):
                                                                     "frame behind the joint-7 frame (default: the reference's end-effector chain)")
     parser.add_argument("--self-collision", action="store_true", help="check every row of each batch for self-collision on the GPU (link boxes against each other) "
                                                                       "and tally the chosen plans' flags (extension; adds `self_collision_free` to the results)")
+    parser.add_argument("--repair", type=int, default=0, metavar="ITERS", help="after the loop and before the selection, repair every row of each batch by at most "
+                                                                                "ITERS projected descent steps on the swept sphere-clearance cost (extension; 0 = off)")
+    parser.add_argument("--repair-margin", type=float, default=0.02, help="the clearance [m] that the repair asks of every tested configuration")
+    parser.add_argument("--repair-step", type=float, default=0.02, help="the repair's step size (a joint moves by at most 0.02 rad per iteration)")
     args = parser.parse_args(argv)
     ik_tool = args.ik_tool
     if ik_tool is not None and ik_tool not in ("flange", "hand"):
@@ -569,7 +619,7 @@ def main(argv=None):
         np.random.seed(args.seed + rank)
     results = run(args.cfg_path, scenes_in_flight=args.scenes_in_flight, max_scenes=args.max_scenes, scenes_per_launch=args.scenes_per_launch,
                   ensemble_report=args.ensemble_report, prefer=args.prefer, ik_seeds=args.ik_seeds, ik_tool=ik_tool, self_collision=args.self_collision,
-                  device_noise=args.device_noise)
+                  device_noise=args.device_noise, repair=args.repair, repair_margin=args.repair_margin, repair_step=args.repair_step)
     if args.results_json:
         import json
 

@@ -1,0 +1,229 @@
+"""Inputs and the float64 reference of the repair stage (sdf_repair_kernel, edmp_amd/csrc/sdf.hip), written from the definition with the
+two existing checkers - not from the kernel (test infrastructure, no GPU needed):
+
+    E(x):  q_w = clip(x_w);  H = sdf_reference.evaluate's hinge sum at the waypoints + sdf_sweep_inputs.evaluate_sweep's at the
+           interpolants, weight 1, the call's margin on every row (K = 1: no sweep part);  S = smoothness x the squared segment lengths;
+           g = their gradients added;  clearance = the smaller of the two minima (start and goal included)
+    step:  delta = min(max(-step x g, -max_step), max_step);  x <- min(max(x + delta, qlo), qhi) on the interior columns, NumPy f64
+    run:   evaluate; stop if H = 0 or i = iters; else step
+
+dtype=torch.float32 evaluates the same formulas in CPU float32: the yardstick of what float32 costs on the same inputs.  The cases go
+through sdf_reference.make_case; their seeds were searched with find_seed(lambda s: check_case(name, s)) so that waypoints AND
+interpolants sit >= MIN_GAP from every decision boundary at the case's margin, and every row has an active hinge there."""
+import numpy as np
+import torch
+
+from edmp_amd import franka
+from tests import sdf_reference as R
+from tests import sdf_sweep_inputs as SW
+
+MIN_GAP = R.MIN_GAP
+ROWS = 3
+# the defaults of repair_rows: the values of the graze experiment below
+DEFAULTS = dict(iters=32, substeps=4, margin=0.02, smoothness=0.5, step=0.02, max_step=0.02)
+
+
+def full_state(joints, start, goal):
+    """interior waypoints (n, 7, L) -> the state (n, 7, L + 2) with the pair in its end columns"""
+    j = np.asarray(joints, dtype=np.float64)
+    n = j.shape[0]
+    ends = [np.broadcast_to(np.asarray(v, dtype=np.float64).reshape(1, 7, 1), (n, 7, 1)) for v in (start, goal)]
+    return np.ascontiguousarray(np.concatenate([ends[0], j, ends[1]], axis=2))
+
+
+def reference_eval(X, start, goal, obstacle_config, kinds, spheres, margin, smoothness, K, dtype=torch.float64, want_grad=True):
+    """X (n, 7, N) -> f64 arrays cost, hinge, smooth, clearance (n,), grad (n, 7, L), active (n,) bool, and the two checker results"""
+    lo, hi = franka.joint_limits()
+    j = np.clip(np.asarray(X, dtype=np.float64)[:, :, 1:-1], lo[None, :, None], hi[None, :, None])
+    n = j.shape[0]
+    m = np.full(n, float(margin))
+    way = R.evaluate(j, start, goal, obstacle_config, kinds, spheres, m, np.full(n, float(smoothness)), dtype=dtype, want_grad=want_grad)
+    hinge, clr = way["collision"].copy(), way["clearance"].copy()
+    grad = way["grad"].copy() if want_grad else None
+    sweep = None
+    if K >= 2:
+        sweep = SW.evaluate_sweep(j, start, goal, obstacle_config, kinds, spheres, m, np.ones(n), int(K), dtype=dtype, want_grad=want_grad)
+        hinge += sweep["cost"]
+        clr = np.minimum(clr, sweep["clearance"])
+        if want_grad:
+            grad += sweep["grad"]
+    return dict(cost=hinge + way["smooth"], hinge=hinge, smooth=way["smooth"], clearance=clr, grad=grad, active=hinge > 0, way=way, sweep=sweep,
+                coord_max=max(way["coord_max"], sweep["coord_max"] if sweep else 0.0))
+
+
+def reference_delta(grad, step, max_step):
+    return np.minimum(np.maximum(-float(step) * grad, -float(max_step)), float(max_step))
+
+
+def reference_step(X, grad, step, max_step, rows=None):
+    """one update of the interior columns of the rows `rows` (default: all) -> a new state"""
+    lo, hi = franka.joint_limits()
+    out = np.array(X, dtype=np.float64)
+    rows = np.arange(out.shape[0]) if rows is None else np.asarray(rows)
+    moved = out[rows][:, :, 1:-1] + reference_delta(grad[rows], step, max_step)
+    sub = out[rows]
+    sub[:, :, 1:-1] = np.minimum(np.maximum(moved, lo[None, :, None]), hi[None, :, None])
+    out[rows] = sub
+    return out
+
+
+def reference_run(X, start, goal, obstacle_config, kinds, spheres, iters=32, substeps=4, margin=0.02, smoothness=0.5, step=0.02, max_step=0.02):
+    """the whole iteration -> dict(trajectories, cost0, cost, clearance0, clearance, hinge0, hinge, iterations)"""
+    X = np.array(X, dtype=np.float64)
+    n = X.shape[0]
+    its = np.zeros(n, dtype=np.int32)
+    live = np.ones(n, dtype=bool)
+    first, last = {}, {k: np.zeros(n) for k in ("cost", "clearance", "hinge")}
+    for i in range(int(iters) + 1):
+        idx = np.flatnonzero(live)
+        if idx.size == 0:
+            break
+        ev = reference_eval(X[idx], start, goal, obstacle_config, kinds, spheres, margin, smoothness, substeps)
+        for k in last:
+            last[k][idx] = ev[k]
+        if i == 0:
+            first = {k: v.copy() for k, v in last.items()}
+        go = ev["active"] & (i < iters)
+        its[idx] = i
+        live[idx[~go]] = False
+        if go.any():
+            X[idx[go]] = reference_step(X[idx[go]], ev["grad"][go], step, max_step)
+    return dict(trajectories=X, cost0=first["cost"], clearance0=first["clearance"], hinge0=first["hinge"], cost=last["cost"], clearance=last["clearance"],
+                hinge=last["hinge"], iterations=its)
+
+
+# name -> L, obstacles, true cylinders among them, sphere table, substeps, margin, seed of sdf_reference.make_case(seed, ROWS, ...)
+CASES = {
+    "L1_o1_K2": dict(L=1, no=1, ncyl=0, spheres="default", K=2, margin=0.3, seed=0),
+    "L2_o7c2_K1": dict(L=2, no=7, ncyl=2, spheres="default", K=1, margin=0.05, seed=1),
+    "L2_o7c2_K4": dict(L=2, no=7, ncyl=2, spheres="default", K=4, margin=0.05, seed=0),
+    "L5_o64_custom_K4": dict(L=5, no=64, ncyl=0, spheres="custom", K=4, margin=0.05, seed=0),
+    "L62_o7c2_K8": dict(L=62, no=7, ncyl=2, spheres="default", K=8, margin=0.05, seed=12),
+    "L48_o7_K4": dict(L=48, no=7, ncyl=0, spheres="default", K=4, margin=0.05, seed=1),
+}
+SMOOTHNESS = 0.5
+_cache = {}
+
+
+def check_case(name, seed=None):
+    """inputs of a case with the float64 reference evaluation at its margin; asserts the distance of the waypoints AND of all interpolants
+    from every decision boundary and an active hinge on every row.  Computed once per case and shared; callers do not modify it."""
+    c = CASES[name]
+    seed = c["seed"] if seed is None else seed
+    if (name, seed) in _cache:
+        return _cache[(name, seed)]
+    inp = R.make_case(seed, ROWS, c["L"], c["no"], c["ncyl"])
+    sph = R.case_spheres(c["spheres"])
+    X = full_state(inp["joints"], inp["start"], inp["goal"])
+    scene = (inp["start"], inp["goal"], inp["obstacle_config"], inp["kinds"], sph)
+    ev = reference_eval(X, *scene, c["margin"], SMOOTHNESS, c["K"])
+    what = f"{name} seed {seed}"
+    mg = R.assert_margins(ev["way"], what)
+    mgs = SW.assert_sweep_margins(ev["sweep"], what) if ev["sweep"] else None
+    assert ev["active"].all() and all(np.abs(ev["grad"][r]).max() > 0 for r in range(ROWS)), f"{what}: a row without an active hinge"
+    out = dict(inp, name=name, X=X, spheres=sph, custom=c["spheres"] == "custom", L=c["L"], K=c["K"], margin=c["margin"], smoothness=SMOOTHNESS, seed=seed,
+               scene=scene, ev=ev, margins=mg, sweep_margins=mgs, cfgs=plain_cfgs(ROWS))
+    _cache[(name, seed)] = out
+    return out
+
+
+def yardstick(case):
+    """deviation of the same formulas in CPU float32 from float64: cost relative to the largest, clearance absolute, and the gradient PER
+    ROW relative to the row's largest element"""
+    ev = case["ev"]
+    e32 = reference_eval(case["X"], *case["scene"], case["margin"], case["smoothness"], case["K"], dtype=torch.float32)
+    return dict(cost=float(np.abs(e32["cost"] - ev["cost"]).max() / np.abs(ev["cost"]).max()),
+                clearance_abs=float(np.abs(e32["clearance"] - ev["clearance"]).max()),
+                grad=np.array([np.abs(e32["grad"][r] - ev["grad"][r]).max() / np.abs(ev["grad"][r]).max() for r in range(ev["grad"].shape[0])]))
+
+
+def clearance_gate(y_abs, coord_max):
+    """sdf_reference.clearance_gate's rule on a yardstick that is already absolute"""
+    return max(R.GATE_FACTOR * y_abs, R.GATE_FLOOR * coord_max)
+
+
+def plain_cfgs(n):
+    """n rows of guide 1 (no SDF keys): the repair call brings its own scalars and the guide binds the default sphere model"""
+    from edmp_amd import guide_cfg as GC
+
+    return GC.build_guide_cfgs([GC.catalog_guide_dict(1)], n, R.T)
+
+
+# ---- the graze scenes: a straight-line plan whose hand grazes a small cube -----------------------------------------------------------------
+GRAZE_SHIFTS = (0.04, 0.0, -0.04)
+GRAZE_L = 12
+
+
+def graze_scene(shift):
+    """start / goal = the mid configuration with joint 0 at -0.5 / +0.5 rad, L = 12 on the straight line, one 0.06 m cube at the tool
+    position of joint 0 = 0 shifted radially (away from the base axis) by `shift` metres, default spheres"""
+    key = ("graze", shift)
+    if key in _cache:
+        return _cache[key]
+    from edmp_amd import evaluation as EV
+
+    lo, hi = franka.joint_limits()
+    mid = (lo + hi) / 2
+    start, goal, qm = mid.copy(), mid.copy(), mid.copy()
+    start[0], goal[0], qm[0] = -0.5, 0.5, 0.0
+    tool = np.asarray(EV.end_effector_positions(qm.reshape(7, 1))[0], dtype=np.float64)
+    radial = np.array([tool[0], tool[1], 0.0]) / np.hypot(tool[0], tool[1])
+    c = tool + shift * radial
+    oc = np.array([[c[0], c[1], c[2], 0.0, 0.0, 0.0, 1.0, 0.06, 0.06, 0.06]])
+    kinds = np.zeros(1, dtype=np.int32)
+    f = np.linspace(0.0, 1.0, GRAZE_L + 2)
+    X = np.ascontiguousarray((start[:, None] * (1 - f) + goal[:, None] * f)[None])  # (1, 7, 14)
+    X[0, :, 0], X[0, :, -1] = start, goal
+    sph = R.case_spheres("default")
+    out = dict(X=X, start=start, goal=goal, obstacle_config=oc, kinds=kinds, spheres=sph, custom=False, scene=(start, goal, oc, kinds, sph),
+               cfgs=plain_cfgs(1))
+    _cache[key] = out
+    return out
+
+
+# ---- the property test's rows --------------------------------------------------------------------------------------------------------------
+# seed: the first of sdf_reference.make_case whose start and goal keep >= 0.03 m of sphere clearance (a pinned end inside an obstacle can
+# never be repaired); amplitude: at 1.2 rad the float64 run leaves rows of every kind - clear from the start, repaired, out of iterations
+PROPERTY = dict(rows=32, L=12, no=7, ncyl=0, iters=16, seed=8, amplitude=1.2)
+
+
+def property_case():
+    """32 random plan-like rows (L = 12) among 7 obstacles with the default spheres: the straight line from start to goal of
+    make_case(seed) plus, per row and joint, a half-sine bump of a uniform random height in +-amplitude"""
+    if "property" in _cache:
+        return _cache["property"]
+    p = PROPERTY
+    inp = R.make_case(p["seed"], 1, p["L"], p["no"], p["ncyl"])
+    rs = np.random.RandomState(1000 + p["seed"])
+    f = np.linspace(0.0, 1.0, p["L"] + 2)
+    line = inp["start"][:, None] * (1 - f) + inp["goal"][:, None] * f
+    X = np.ascontiguousarray(line[None] + rs.uniform(-p["amplitude"], p["amplitude"], size=(p["rows"], 7, 1)) * np.sin(np.pi * f)[None, None, :])
+    X[:, :, 0], X[:, :, -1] = inp["start"], inp["goal"]
+    sph = R.case_spheres("default")
+    scene = (inp["start"], inp["goal"], inp["obstacle_config"], inp["kinds"], sph)
+    ends = R.evaluate(X[:1, :, 1:-1], *scene, np.zeros(1), np.zeros(1), want_grad=False)["d"][0]
+    assert min(ends[0].min(), ends[-1].min()) >= 0.03
+    out = dict(start=inp["start"], goal=inp["goal"], obstacle_config=inp["obstacle_config"], kinds=inp["kinds"], X=X, spheres=sph, custom=False, scene=scene,
+               cfgs=plain_cfgs(p["rows"]))
+    _cache["property"] = out
+    return out
+
+
+# ---- an element next to a joint limit ------------------------------------------------------------------------------------------------------
+def limit_case(step=0.02, max_step=1e-3, margin=0.3):
+    """the L = 2 case with ONE interior element of row 0 placed max_step / 2 inside a joint limit, at the first (joint, side) for which
+    the float64 gradient at that state (smoothness 0) pushes it outward by at least 2 max_step: a projected step lands on the limit"""
+    if "limit" in _cache:
+        return _cache["limit"]
+    base = check_case("L2_o7c2_K4")
+    lo, hi = franka.joint_limits()
+    for j in range(7):
+        for side, lim in ((1.0, hi[j]), (-1.0, lo[j])):
+            X = base["X"].copy()
+            X[0, j, 1] = lim - side * max_step / 2
+            g = reference_eval(X[:1], *base["scene"], margin, 0.0, base["K"])["grad"][0, j, 0]
+            if -side * step * g >= 2 * max_step:
+                out = dict(base, X=X, element=(0, j, 1), limit=float(lim), max_step=max_step, margin=margin)
+                _cache["limit"] = out
+                return out
+    raise AssertionError("no joint of the case is pushed outward at its limit")

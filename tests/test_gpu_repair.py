@@ -1,0 +1,418 @@
+"""The repair stage (sdf_repair_kernel, edmp_sdf_repair_rows_dev, edmp_scenes_sdf_repair_rows_dev) on the GPU against the float64
+reference of tests/repair_inputs.py, and against itself where the property is bit-equality.
+
+Gates: sdf_reference.gate - max(4 x the deviation of the reference's own formula in CPU float32 from float64, 4 f32 ulps), relative to the
+largest element (per row for the gradient); clearance: absolute, with the floor of a few f32 ulps of the largest coordinate that enters
+it (sdf_reference.clearance_gate's rule).  Every comparison prints its error, yardstick and gate; with EDMP_REPAIR_PARITY_OUT=<file> the
+records are written there as JSON (profiles/repair_parity.json comes from such a run).  Waypoints and interpolants of the cases sit
+>= 1e-5 m from every kink, so no element is excluded from any comparison."""
+import ctypes as C
+
+import numpy as np
+import pytest
+import torch
+
+from edmp_amd import franka
+from tests import repair_inputs as I
+from tests import sdf_reference as R
+from tests.sdf_gpu import DEV, recorder
+from tests.util import TINY_DIMS
+
+pytestmark = pytest.mark.gpu
+record, _write_records = recorder("repair parity", "EDMP_REPAIR_PARITY_OUT",
+                                  "max(4 x CPU-float32 deviation from float64, 4 f32 ulps), relative to the largest element (gradient: per row); "
+                                  "clearance: absolute, floor 4 f32 ulps of the largest coordinate")
+KEYS = ("trajectories", "cost0", "cost", "clearance0", "clearance", "iterations")
+
+
+def make_guide(case, device=DEV, **kw):
+    """the guide of a case: its obstacles and kinds, the placeholder link boxes, its sphere table where the case says "custom"; no SDF rows -
+    the repair call brings its own scalars"""
+    from edmp_amd.guide import IntersectionVolumeGuide
+
+    cfgs = case["cfgs"]
+    return IntersectionVolumeGuide(case["obstacle_config"], device, cfgs, cfgs["total_batch_size"], link_mesh_extents=franka.PLACEHOLDER_LINK_EXTENTS,
+                                   obstacle_kinds=case["kinds"], spheres=case["spheres"] if case["custom"] else None, **kw)
+
+
+def call(guide, case, X=None, **kw):
+    """repair_rows on the case's state and pair with the case's K, margin and smoothness unless kw says otherwise"""
+    for k, v in (("substeps", case.get("K", 4)), ("margin", case.get("margin", 0.02)), ("smoothness", case.get("smoothness", 0.5))):
+        kw.setdefault(k, v)
+    return guide.repair_rows(case["X"] if X is None else X, case["start"], case["goal"], **kw)
+
+
+def bits(a):
+    """raw bits, NaN patterns included"""
+    a = np.ascontiguousarray(a)
+    return a.view(np.int64 if a.dtype == np.float64 else np.int32)
+
+
+def same(a, b, keys=KEYS):
+    return all(np.array_equal(bits(a[k]), bits(b[k])) for k in keys)
+
+
+@pytest.mark.parametrize("name", list(I.CASES))
+def test_report_only(name):
+    """1. iters = 0: X comes back bit for bit, both report columns are equal, iterations = 0; clearance and cost against float64"""
+    case = I.check_case(name)
+    guide = make_guide(case)
+    out = call(guide, case, iters=0)
+    ev, y = case["ev"], I.yardstick(case)
+    assert np.array_equal(bits(out["trajectories"]), bits(case["X"])) and out["trajectories"].shape == case["X"].shape
+    assert np.array_equal(bits(out["cost"]), bits(out["cost0"])) and np.array_equal(bits(out["clearance"]), bits(out["clearance0"]))
+    assert out["iterations"].dtype == np.int32 and not out["iterations"].any()
+    scale = float(np.abs(ev["cost"]).max())
+    cost_err = float(np.abs(out["cost"] - ev["cost"]).max())
+    cgate = I.clearance_gate(y["clearance_abs"], ev["coord_max"])
+    clr_err = float(np.abs(out["clearance"] - ev["clearance"]).max())
+    inner = case["X"][:, :, 1:-1]
+    way = guide.sdf_rows(inner, case["start"], case["goal"], 0)["clearance"]
+    swept = guide.sdf_sweep_rows(inner, case["start"], case["goal"], 0, substeps=case["K"])["clearance"] if case["K"] >= 2 else np.full_like(way, np.inf)
+    record(test="report", case=name, cost_abs_err=cost_err, cost_scale=scale, cost_yardstick=y["cost"], cost_gate=R.gate(y["cost"]), clearance_abs_err=clr_err,
+           clearance_yardstick_abs=y["clearance_abs"], clearance_gate_abs=cgate, min_clearance=float(ev["clearance"].min()),
+           clearance_is_min_of_the_two_reports_bit_for_bit=bool(np.array_equal(bits(out["clearance"]), bits(np.minimum(way, swept)))))
+    assert clr_err <= cgate, (clr_err, cgate)
+    assert cost_err <= R.gate(y["cost"]) * scale, (cost_err, scale, y["cost"])
+
+
+@pytest.mark.parametrize("name", list(I.CASES))
+def test_one_step_against_float64(name):
+    """2. iters = 1 with max_step so large that nothing is clamped (and a step so small that nothing reaches a joint limit): per row
+    |(X1 - X0) - delta_ref| <= step x gate x max |g_ref|, no element excluded"""
+    case = I.check_case(name)
+    ev, y = case["ev"], I.yardstick(case)
+    eta, big = 1e-3, 1e3
+    dref = I.reference_delta(ev["grad"], eta, big)
+    assert np.array_equal(I.reference_step(case["X"], ev["grad"], eta, big)[:, :, 1:-1], case["X"][:, :, 1:-1] + dref)  # (no projection)
+    out = call(make_guide(case), case, iters=1, step=eta, max_step=big)
+    assert (out["iterations"] == 1).all() and np.array_equal(bits(out["trajectories"][:, :, [0, -1]]), bits(case["X"][:, :, [0, -1]]))
+    d = out["trajectories"][:, :, 1:-1] - case["X"][:, :, 1:-1]
+    for r in range(I.ROWS):
+        gmax = float(np.abs(ev["grad"][r]).max())
+        err, bound = float(np.abs(d[r] - dref[r]).max()), eta * R.gate(float(y["grad"][r])) * gmax
+        record(test="one_step", case=name, row=r, step_abs_err=err, grad_rel_err=err / (eta * gmax), yardstick=float(y["grad"][r]), gate=R.gate(float(y["grad"][r])),
+               bound=bound)
+        assert gmax > 0 and err <= bound, (r, err, bound)
+
+
+def test_clamp_projection_and_pinned_ends():
+    """3. a small max_step: every element with |step x g_ref| >= 2 max_step moves by exactly +-max_step; an element within max_step of a
+    joint limit whose gradient pushes outward lands exactly on the limit; columns 0 and N - 1 are neither read nor written"""
+    case = I.check_case("L5_o64_custom_K4")
+    g, eta, dm = case["ev"]["grad"], 0.02, 1e-4
+    X = case["X"].copy()
+    X[:, :, 0], X[:, :, -1] = 7.0, np.nan  # the pair comes from start / goal: the end columns are not read as joints
+    out = call(make_guide(case), case, X=X, iters=1, step=eta, max_step=dm)
+    assert (out["iterations"] == 1).all() and np.array_equal(bits(out["trajectories"][:, :, [0, -1]]), bits(X[:, :, [0, -1]]))
+    sure = np.abs(eta * g) >= 2 * dm
+    want = X[:, :, 1:-1] + np.where(g < 0, dm, -dm)
+    assert sure.sum() >= 20 and np.array_equal(out["trajectories"][:, :, 1:-1][sure], want[sure])
+    assert np.abs(out["trajectories"][:, :, 1:-1] - X[:, :, 1:-1]).max() <= dm * (1 + 1e-9)
+    pin = I.limit_case()
+    r, j, w = pin["element"]
+    out = make_guide(pin).repair_rows(pin["X"], pin["start"], pin["goal"], iters=1, substeps=pin["K"], margin=pin["margin"], smoothness=0.0, step=eta, max_step=pin["max_step"])
+    assert out["trajectories"][r, j, w] == pin["limit"] and pin["X"][r, j, w] != pin["limit"] and out["iterations"][r] == 1
+    lo, hi = franka.joint_limits()
+    assert (out["trajectories"][:, :, 1:-1] >= lo[None, :, None]).all() and (out["trajectories"][:, :, 1:-1] <= hi[None, :, None]).all()
+
+
+def chain_of_single_steps(guide, case, n, **kw):
+    X, its, out = case["X"], 0, None
+    for _ in range(n):
+        out = call(guide, case, X=X, iters=1, **kw)
+        X, its = out["trajectories"], its + out["iterations"]
+    return out, its
+
+
+@pytest.mark.parametrize("name", ["L2_o7c2_K4", "L62_o7c2_K8"])
+def test_n_iterations_in_one_launch_equal_n_launches(name):
+    """4. n = 5 at a margin at which the hinge stays active: X, the final report and the sum of the iterations, bit for bit - stale
+    registers, LDS or a misplaced barrier across iterations would show here"""
+    case = I.check_case(name)
+    guide = make_guide(case)
+    kw = dict(margin=0.3, step=0.005, max_step=0.01)
+    one = call(guide, case, iters=5, **kw)
+    last, its = chain_of_single_steps(guide, case, 5, **kw)
+    assert (one["iterations"] == 5).all() and np.array_equal(its, one["iterations"])
+    assert same(one, last, ("trajectories", "cost", "clearance"))
+    assert not np.array_equal(one["trajectories"], case["X"]) and np.isfinite(one["cost"]).all()
+
+
+@pytest.mark.parametrize("shift", I.GRAZE_SHIFTS)
+def test_graze_scenes(shift):
+    """4. + 9. the straight-line plan fails success_rows and is collision_free after the repair at the default parameters: last hinge 0
+    (a further call with iters = 1 finds nothing to do), final clearance >= 1e-4 m, iterations <= 32 - not compared with the reference's
+    count, float32 may flip a hinge; and the rows stop on the way at the same count in one launch as in single steps"""
+    g = I.graze_scene(shift)
+    guide = make_guide(g)
+    before = guide.success_rows(g["X"], substeps=4)
+    out = guide.repair_rows(g["X"], g["start"], g["goal"])
+    after = guide.success_rows(out["trajectories"], substeps=4)
+    again = guide.repair_rows(out["trajectories"], g["start"], g["goal"], iters=1)
+    record(test="graze", shift=shift, clearance0=float(out["clearance0"][0]), clearance=float(out["clearance"][0]), iterations=int(out["iterations"][0]),
+           first_before=int(before["first"][0]), largest_move=float(np.abs(out["trajectories"] - g["X"]).max()))
+    assert not before["collision_free"][0] and after["collision_free"][0]
+    assert 0 < out["iterations"][0] <= 32 and out["clearance"][0] >= 1e-4 and out["clearance0"][0] < 0
+    assert again["iterations"][0] == 0 and np.array_equal(bits(again["trajectories"]), bits(out["trajectories"]))
+    five = guide.repair_rows(g["X"], g["start"], g["goal"], iters=5)
+    last, its = chain_of_single_steps(guide, dict(g, K=4), 5)
+    assert np.array_equal(its, five["iterations"]) and same(five, last, ("trajectories", "cost", "clearance"))
+
+
+def test_clear_rows_keep_their_bits():
+    """5. every obstacle >= 5 m away: iterations = 0 and identical X"""
+    far = R.make_case(0, 3, 5, 7, 2, far=True)
+    case = dict(far, X=I.full_state(far["joints"], far["start"], far["goal"]), custom=False, spheres=None, cfgs=I.plain_cfgs(3))
+    out = call(make_guide(case), case)
+    assert not out["iterations"].any() and np.array_equal(bits(out["trajectories"]), bits(case["X"]))
+    assert same(out, dict(out, cost=out["cost0"], clearance=out["clearance0"])) and (out["clearance"] > 4.0).all()
+
+
+def test_rows_subset():
+    """6. rows= in non-monotonic order: the listed rows equal their values from the all-rows call, the others keep their bits and are not
+    reported; the same row content at another row index gives the same bits"""
+    case = I.check_case("L5_o64_custom_K4")
+    guide = make_guide(case)
+    full = call(guide, case, iters=3)
+    part = call(guide, case, iters=3, rows=[2, 0])
+    for k in KEYS:
+        assert np.array_equal(bits(part[k][[2, 0]]), bits(full[k][[2, 0]])), k
+    assert np.array_equal(bits(part["trajectories"][1]), bits(case["X"][1])) and part["iterations"][1] == 0
+    assert np.isnan(part["cost"][1]) and np.isnan(part["clearance0"][1])
+    perm = [1, 2, 0]
+    moved = call(guide, case, X=np.ascontiguousarray(case["X"][perm]), iters=3)
+    for k in KEYS:
+        assert np.array_equal(bits(moved[k]), bits(full[k][perm])), k
+    assert not np.array_equal(full["trajectories"], case["X"])
+
+
+def test_non_finite_row():
+    """7. a row with one NaN comes back untouched with iterations = -1 and NaN reports; its neighbours are what they are without it"""
+    case = I.check_case("L2_o7c2_K4")
+    guide = make_guide(case)
+    full = call(guide, case, iters=3)
+    for bad in (np.nan, np.inf):
+        X = case["X"].copy()
+        X[1, 3, 2] = bad
+        out = call(guide, case, X=X, iters=3)
+        assert out["iterations"].tolist() == [full["iterations"][0], -1, full["iterations"][2]]
+        assert np.array_equal(bits(out["trajectories"][1]), bits(X[1]))
+        assert all(np.isnan(out[k][1]) for k in ("cost0", "cost", "clearance0", "clearance"))
+        for k in KEYS:
+            assert np.array_equal(bits(out[k][[0, 2]]), bits(full[k][[0, 2]])), k
+
+
+def test_scene_batch_equals_serial_runs():
+    """8. three scenes with 1, 7 (2 cylinders) and 64 obstacles, 3 rows each: every output of scene s equals guides[s].repair_rows(X[s]),
+    bit for bit, also with the scenes in reversed order"""
+    from edmp_amd.guide import SceneBatch
+
+    parts = []
+    for seed, (no, ncyl) in enumerate(((1, 0), (7, 2), (64, 0))):
+        inp = R.make_case(40 + seed, 3, 5, no, ncyl)
+        parts.append(dict(inp, X=I.full_state(inp["joints"], inp["start"], inp["goal"]), custom=False, spheres=None, cfgs=I.plain_cfgs(3)))
+    kw = dict(iters=4, substeps=4, margin=0.1, smoothness=0.5, step=0.005, max_step=0.01)
+    for order in ((0, 1, 2), (2, 1, 0)):
+        ps = [parts[i] for i in order]
+        guides = [make_guide(p) for p in ps]
+        serial = [g.repair_rows(p["X"], p["start"], p["goal"], **kw) for g, p in zip(guides, ps)]
+        batch = SceneBatch(guides)
+        got = batch.repair_rows(np.stack([p["X"] for p in ps]), np.stack([p["start"] for p in ps]), np.stack([p["goal"] for p in ps]), **kw)
+        assert got["trajectories"].shape == (3, 3, 7, 7) and got["iterations"].shape == (3, 3)
+        for s in range(3):
+            for k in KEYS:
+                assert np.array_equal(bits(got[k][s]), bits(serial[s][k])), (order, s, k)
+        assert any(o["iterations"].any() for o in serial)
+        dev = batch.repair_rows(torch.as_tensor(np.stack([p["X"] for p in ps]), device=DEV), np.stack([p["start"] for p in ps]), np.stack([p["goal"] for p in ps]),
+                                return_device=True, **kw)
+        assert all(np.array_equal(bits(dev[k].cpu().numpy()), bits(got[k])) for k in KEYS)
+
+
+def test_property_clear_by_the_spheres_is_collision_free():
+    """10. 32 random rows at iters = 16: EVERY row whose reported final clearance exceeds 1e-4 m is collision_free under success_rows at
+    the same substeps, and at least half of the rows qualify (tests/test_repair_host.py shows the reference alone to reach that).  1e-4 m
+    is a condition, not a tolerance: three orders above the f32 resolution of a position at arm's length (1.2e-7 m at 1-2 m), while the
+    success kernel works in f64 - and the default spheres circumscribe the link boxes."""
+    p = I.property_case()
+    guide = make_guide(p)
+    Xd = torch.as_tensor(p["X"], device=DEV)
+    keep = Xd.clone()
+    out = guide.repair_rows(Xd, p["start"], p["goal"], iters=I.PROPERTY["iters"])
+    assert torch.equal(Xd, keep)  # always out of place
+    good = out["clearance"] > 1e-4
+    chk = guide.success_rows(out["trajectories"], substeps=4)
+    chk0 = guide.success_rows(p["X"], substeps=4)
+    record(test="property", rows=int(good.size), clear_before=int((out["clearance0"] > 1e-4).sum()), clear_after=int(good.sum()),
+           collision_free_before=int(chk0["rows_collision_free"]), collision_free_after=int(chk["rows_collision_free"]), moved=int((out["iterations"] > 0).sum()))
+    assert chk["collision_free"][good].all()
+    assert 2 * good.sum() >= good.size
+    assert (good & ~(out["clearance0"] > 1e-4)).any()
+
+
+def raw_call(guide, Xd, start, goal, rows=None, n=None, N=None, K=4, iters=1, margin=0.02, lam=0.5, step=0.02, dmax=0.02, name="edmp_sdf_repair_rows_dev", lead=None):
+    """the C entry point on a device state, with report buffers that a refused call must leave as they are -> (rc, message, cost, iterations)"""
+    from edmp_amd import _capi
+    from edmp_amd.runtime import ptr
+
+    ctx = guide.ctx
+    n = Xd.shape[0] if n is None else n
+    with torch.cuda.stream(ctx.stream):
+        rep = torch.full((2, Xd.shape[0], 2), -5.0, dtype=torch.float64, device=ctx.device)
+        its = torch.full((Xd.shape[0],), -7, dtype=torch.int32, device=ctx.device)
+    lst = None if rows is None else np.ascontiguousarray(np.asarray(rows, dtype=np.int32))
+    lead = (n,) if lead is None else lead
+    rc = getattr(ctx.lib, name)(ctx.h, ptr(Xd), *lead, Xd.shape[2] if N is None else N, _capi.as_pd(np.ascontiguousarray(start, dtype=np.float64)),
+                                _capi.as_pd(np.ascontiguousarray(goal, dtype=np.float64)), None if lst is None else _capi.as_pi32(lst), 0 if lst is None else len(lst),
+                                K, iters, margin, lam, step, dmax, C.c_void_p(rep[0].data_ptr()), C.c_void_p(rep[1].data_ptr()), ptr(its))
+    return rc, (ctx.lib.edmp_last_error() or b"").decode() if rc else "", ctx.to_host(rep), ctx.to_host(its)
+
+
+def test_refusals():
+    """11. each bad argument, duplicate rows included, is refused with a message that names the entry point and the value; X, the report
+    buffers and a following report are what they were"""
+    from edmp_amd.guide import SceneBatch
+
+    case = I.check_case("L2_o7c2_K4")
+    guide = make_guide(case)
+    before = call(guide, case, iters=2)
+    Xd = guide.ctx.to_dev(case["X"], torch.float64)
+    s, g = case["start"], case["goal"]
+    nan7 = s.copy()
+    nan7[4] = np.nan
+    bad = (("N = 2", dict(N=2), "N"), ("N = 65", dict(N=65), "N"), ("K = 0", dict(K=0), "substeps 0"), ("K = 65", dict(K=65), "substeps 65"),
+           ("iters = -1", dict(iters=-1), "iters -1"), ("iters = 1025", dict(iters=1025), "iters 1025"), ("NaN margin", dict(margin=float("nan")), "margin"),
+           ("negative margin", dict(margin=-0.01), "margin -0.01"), ("negative smoothness", dict(lam=-1.0), "smoothness -1"), ("inf smoothness", dict(lam=float("inf")), "smoothness"),
+           ("step = 0", dict(step=0.0), "step 0"), ("NaN step", dict(step=float("nan")), "step"), ("max_step = 0", dict(dmax=0.0), "max_step 0"),
+           ("inf max_step", dict(dmax=float("inf")), "max_step"), ("row 3 of 3", dict(rows=[0, 3]), "rows[1] = 3"), ("row -1", dict(rows=[-1]), "rows[0] = -1"),
+           ("a row twice", dict(rows=[1, 0, 1]), "rows[2] = 1 is listed twice"), ("more rows than there are", dict(rows=[0, 1, 2, 0]), "4 listed rows"),
+           ("n = 0", dict(n=0), "n >= 1"))
+    for what, kw, needle in bad:
+        rc, msg, rep, its = raw_call(guide, Xd, s, g, **kw)
+        assert rc == -1 and msg.startswith("edmp_sdf_repair_rows_dev") and needle in msg, (what, rc, msg)
+        assert (rep == -5.0).all() and (its == -7).all(), what
+    rc, msg, rep, its = raw_call(guide, Xd, nan7, g)
+    assert rc == -1 and "non-finite start / goal" in msg and (rep == -5.0).all()
+    rc, msg, _, _ = raw_call(guide, Xd, s, g, name="edmp_scenes_sdf_repair_rows_dev", lead=(1, 3))  # the batch's entry point on a single-scene guide
+    assert rc == -3 and msg.startswith("edmp_scenes_sdf_repair_rows_dev"), (rc, msg)
+    assert np.array_equal(bits(guide.ctx.to_host(Xd)), bits(case["X"]))
+    assert same(call(guide, case, iters=2), before)
+    # the accepted raw call works in place and writes the listed rows only
+    rc, msg, rep, its = raw_call(guide, Xd, s, g, rows=[2], iters=2, K=case["K"], margin=case["margin"])
+    assert rc == 0, msg
+    Xh = guide.ctx.to_host(Xd)
+    assert np.array_equal(bits(Xh[2]), bits(before["trajectories"][2])) and np.array_equal(bits(Xh[:2]), bits(case["X"][:2]))
+    assert its.tolist() == [-7, -7, before["iterations"][2]] and rep[0, 2, 1] == before["cost"][2] and (rep[:, :2] == -5.0).all()
+    with pytest.raises(ValueError):
+        guide.repair_rows(np.zeros((3, 6, 4)), s, g)
+    with pytest.raises(_capi_error(), match="iters -2"):
+        guide.repair_rows(case["X"], s, g, iters=-2)
+    # the single-scene entry point on a bound batch of two scenes
+    batch = SceneBatch([make_guide(case, bind=False), make_guide(case, bind=False)])
+    batch._bind_sdf()
+    X2 = batch.ctx.to_dev(np.concatenate([case["X"], case["X"]]), torch.float64)
+    rc, msg, _, _ = raw_call(batch, X2, s, g)
+    assert rc == -3 and msg.startswith("edmp_sdf_repair_rows_dev"), (rc, msg)
+    rc, msg, _, _ = raw_call(batch, X2, np.stack([s, s]), np.stack([g, g]), name="edmp_scenes_sdf_repair_rows_dev", lead=(3, 2))
+    assert rc == -1 and msg.startswith("edmp_scenes_sdf_repair_rows_dev"), (rc, msg)
+    with pytest.raises(_capi_error(), match="listed twice"):
+        batch.repair_rows(np.stack([case["X"], case["X"]]), np.stack([s, s]), np.stack([g, g]), rows=[4, 4])
+
+
+def _capi_error():
+    from edmp_amd import _capi
+
+    return _capi.EdmpError
+
+
+def test_a_segmented_run_goes_on():
+    """11. a repair_rows call - with another start / goal pair than the run's - between two segments of a segmented run: the run's result
+    is bit-identical to the uninterrupted one"""
+    from edmp_amd import _capi, scenes
+    from edmp_amd import guide_cfg as GC
+    from edmp_amd import weights as W
+    from edmp_amd.diffusion import Diffusion
+    from edmp_amd.guide import IntersectionVolumeGuide
+    from edmp_amd.runtime import ptr
+    from edmp_amd.temporalunet import TemporalUNet
+
+    T = R.T
+    net = TemporalUNet(None, 7, 32, DEV, dims=TINY_DIMS, state_dict=W.init_state_dict(5, 7, 32, TINY_DIMS), max_batch=64)
+    cfgs = GC.build_guide_cfgs([GC.load_guide_dict(n) for n in (1, 101, 13)], 4, T)
+    Bn = cfgs["total_batch_size"]
+    s, gl = np.asarray(scenes.DEFAULT_START, dtype=np.float64), np.asarray(scenes.DEFAULT_GOAL, dtype=np.float64)
+    dif = Diffusion(T, DEV)
+    rs = np.random.RandomState(11)
+    g = IntersectionVolumeGuide(scenes.random_scene(7, 8), DEV, cfgs, Bn)
+    ctx, lib = g.ctx, g.ctx.lib
+    z0 = ctx.to_dev(rs.standard_normal((1 + 4, Bn, 7, 50)), torch.float64)
+    z1 = ctx.to_dev(rs.standard_normal((4, Bn, 7, 50)), torch.float64)
+    X = rs.uniform(-1, 1, (5, 7, 50))
+    sp, gp = _capi.as_pd(np.ascontiguousarray(s)), _capi.as_pd(np.ascontiguousarray(gl))
+
+    def run(between):
+        dif._prepare(net, g, Bn, cfgs["guidance_schedule"])
+        _capi.check(lib.edmp_sampler_set_condition(ctx.h, 1))
+        out = ctx.empty((Bn, 7, 50), torch.float64)
+        _capi.check(lib.edmp_denoise_guided_segment_dev(ctx.h, ptr(z0), Bn, sp, gp, 1, T, T - 4, 1, 1, None), "first segment")
+        mid = between()
+        rc = lib.edmp_denoise_guided_segment_dev(ctx.h, ptr(z1), Bn, sp, gp, 1, T - 4, T - 8, 0, 1, ptr(out))
+        msg = lib.edmp_last_error().decode() if rc else ""
+        ctx.sync()
+        return rc, msg, ctx.to_host(out), mid
+
+    rc, msg, whole, _ = run(lambda: None)
+    assert rc == 0, msg
+    rc, msg, cut, mid = run(lambda: g.repair_rows(X, gl, s, iters=3, margin=0.1, rows=[4, 1]))
+    assert rc == 0, msg
+    assert np.isfinite(whole).all() and np.array_equal(whole, cut)
+    assert np.isfinite(mid["clearance"][[4, 1]]).all() and (mid["iterations"][[4, 1]] >= 0).all()
+
+
+def test_history():
+    """12. the L = 2 call gives the same bits after an L = 62, 64-obstacle call on the same context as on a fresh one"""
+    from edmp_amd.runtime import Context
+
+    small = I.check_case("L2_o7c2_K4")
+    inp = R.make_case(7, 3, 62, 64, 0)
+    big = dict(inp, X=I.full_state(inp["joints"], inp["start"], inp["goal"]), custom=False, spheres=None, cfgs=I.plain_cfgs(3))
+    outs = []
+    for history in (False, True):
+        ctx = Context(0)
+        try:
+            if history:
+                out = make_guide(big, device=ctx).repair_rows(big["X"], big["start"], big["goal"], iters=6, substeps=8, margin=0.3, rows=[2, 0, 1])
+                assert (out["iterations"] == 6).all()
+            outs.append(call(make_guide(small, device=ctx), small, iters=4, rows=[1, 2]))
+        finally:
+            ctx.close()
+    assert same(outs[0], outs[1]) and outs[0]["iterations"][1:].all()
+    assert same(outs[0], call(make_guide(small), small, iters=4, rows=[1, 2]))
+
+
+def test_driver_repairs_between_the_loop_and_the_selection():
+    """infer_serial --repair: off, no key is added; on, the serial loop (the guide) and the scene-group path (the SceneBatch, one launch)
+    report the same rows moved / ended clear and choose the same plan, whose pinned ends are the run's without the option"""
+    import os
+
+    import infer_serial
+    from edmp_amd import scenes
+
+    cfg = os.path.join(os.path.dirname(os.path.dirname(os.path.abspath(__file__))), "configs", "cfg_c1_plumbing.yaml")
+
+    def run(k, repair):
+        np.random.seed(31)
+        ds = scenes.SyntheticDataset(scene_types=("stress",), num_scenes_per_type=2, n_obstacles=6, n_cylinders=1)
+        return infer_serial.run(cfg, dataset=ds, verbose=False, scenes_per_launch=k, repair=repair, repair_margin=0.03)
+
+    off, serial, group = run(1, 0), run(1, 6), run(2, 6)
+    assert len(off) == len(serial) == len(group) == 2
+    for o, a, b in zip(off, serial, group):
+        assert "rows_repaired" not in o and "repair_s" not in o["timings"]
+        assert a["repair_iters"] == 6 and 0 <= a["rows_repair_clear"] <= a["rows"] and 0 <= a["rows_repaired"] <= a["rows"]
+        assert (a["rows_repaired"], a["rows_repair_clear"], a["best_row"]) == (b["rows_repaired"], b["rows_repair_clear"], b["best_row"])
+        assert np.array_equal(a["trajectory"], b["trajectory"]) and np.isfinite(a["trajectory"]).all()
+        assert np.array_equal(a["trajectory"][:, [0, -1]], o["trajectory"][:, [0, -1]])
+    assert sum(a["rows_repaired"] for a in serial) > 0
+    with pytest.raises(ValueError):
+        infer_serial.run(cfg, verbose=False, repair=-1)
