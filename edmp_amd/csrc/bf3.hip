@@ -23,8 +23,10 @@
 //     with (nearly) equal numbers of (l, lp) pairs, found by exhaustive search at compile time (Bf3Cfg::part0_mask).
 //   * a chunk = 32 channels = ONE MFMA K.  It is worked in two PHASES with equal MFMA counts - A: the weight components lo and mid
 //     (products hi*lo, mid*mid, hi*mid), B: the weight component hi (lo*hi, mid*hi, hi*hi) - and a phase's weight registers are
-//     refilled with the next chunk's when the phase is over (lo and mid right after phase A; hi at the head of the next chunk): every
-//     weight fragment is requested half a chunk before its use with 3 x NSLOT x 4 registers of weights in flight, no double buffer.
+//     refilled while the OTHER phase runs (lo and mid during phase B; hi during the next chunk's phase A): every weight fragment is
+//     requested half a chunk before its use with 3 x NSLOT x 4 registers of weights in flight, no double buffer.
+//   * an MFMA wave's memory instructions (fragment reads from LDS, weight loads) are dealt one per MFMA, not issued in bursts
+//     between the MFMAs (Bf3Cfg: the deal).
 //   * weights: fragment stream of bf16 triples [Cout/16][Cin/32][slot][component][64 lanes][8 bf16] (1 KiB blocks, 1.5x the
 //     bytes of the fp32 stream), split once at load (pack_fragments_bf3).
 #pragma once
@@ -150,12 +152,51 @@ struct Bf3Cfg {
         return -1;
     }
     static constexpr int first(int H) { return needed(H, 0) ? 0 : next(H, 0); }
+    // THE DEAL: an MFMA wave's memory instructions ride one per SLOT - the place behind an MFMA of an entry - not in bursts between the
+    // entries: alone in a slot a memory instruction issues in the MFMA's shadow, several in a row queue behind each other and hold the
+    // SIMD's issue port, which the staging wave beside shares (profiles/r04_side_cluster.txt found the same rule for wide.hip; measured
+    // here: profiles/bf3_issue_slots.json - a slot behind every SECOND MFMA gains less).  An entry's items: the fragment reads of the
+    // next entry (except in front of the rotated barrier: those go first, in one burst, so that the barrier's wait for them falls under
+    // the entry's MFMAs), then loads of weight registers that are dead in the phase - phase A: component hi of THIS chunk (5 at K5),
+    // phase B: lo and mid of the next (10) - as many as the phase's slots hold; what they do not hold goes behind the phase.
+    // Not DEALT: the 32-sample strided resamplers.  Their entries have 3 or 6 MFMAs for 2-3 reads, so nearly every slot would be taken
+    // (27 items in a phase's 30 slots at L = 7) and nothing rides in a shadow: measured 1-2 % slower dealt.  They keep the bursts: the
+    // reads in front of each entry, lo and mid behind phase A, hi at the head of its chunk (mfma_loop).
+    static constexpr bool DEALT = !(KIND == WK_DOWN && MS == 32);
+    static constexpr int DEAL = 1;  // MFMAs per slot
+    static constexpr int nfeed(int H, int lp, int upto = NTILE) {  // tiles below `upto` that part H's entry of input position lp feeds
+        int n = 0;
+        for (int t = 0; t < upto; ++t) n += (owned(t, H) && tslot(t, lp) >= 0) ? 1 : 0;
+        return n;
+    }
+    static constexpr int nslots(int H, int q) { return DEALT ? 3 * nfeed(H, q % LIN) * NR / DEAL : 0; }
+    static constexpr int nreads(int H, int q) {  // fragment reads entry q issues for its successor
+        const int qn = next(H, q);
+        return qn < 0 ? 0 : NR * (qn / LIN == 0 ? 2 : 3);
+    }
+    static constexpr int reads_dealt(int H, int q) {
+        const int qn = next(H, q);
+        if (qn < 0 || (ROTATE && next(H, qn) < 0)) return 0;
+        return nreads(H, q) < nslots(H, q) ? nreads(H, q) : nslots(H, q);
+    }
+    static constexpr int nweights(int ph) { return !DEALT ? 0 : ph == 0 ? NSLOT : 2 * NSLOT; }  // weight loads a phase deals
+    static constexpr int wbase(int H, int ph, int lp) {  // ... of them, those dealt by the phase's entries before position lp
+        int n = 0;
+        for (int i = 0; i < lp; ++i)
+            if (needed(H, i)) {
+                const int cap = nslots(H, ph * LIN + i) - reads_dealt(H, ph * LIN + i);
+                n += cap < nweights(ph) - n ? cap : nweights(ph) - n;
+            }
+        return n;
+    }
+    static constexpr int wdealt(int H, int q) { return wbase(H, q / LIN, q % LIN + 1) - wbase(H, q / LIN, q % LIN); }
     // registers of the K loop's arrays (accumulators, weight fragments, the two activation fragment sets).  Where they leave room,
     // the chunk loop is rotated across its barrier (a second stage address) and the hand-over's bias values are loaded in the prologue
     // and held across the K loop (one or two registers).  <K5, 32, 64, 64, 4, true> (248 of 256) has none to spare - either change
     // makes it spill: it keeps the barrier behind the chunk and loads its bias first behind the K loop, ahead of the epilogue's operands
     static constexpr int KREGS = MAXT * NR * 8 + 3 * NSLOT * 4 + 2 * NR * 3 * 4;
     static constexpr bool ROTATE = KREGS <= 240, BIAS_EARLY = ROTATE;
+    static_assert(DEALT || ROTATE, "the burst form of the K loop is kept for rotated instances only");
     // staging: float4 items [position][row][channel quad] of a chunk over the 256 staging threads
     static constexpr int A_F4 = LIN * MS * (KC / 4);
     static constexpr int NA = (A_F4 + 255) / 256;
@@ -278,6 +319,17 @@ __device__ __forceinline__ void bf3_conv_body(const float* a_src1, const float* 
 #pragma unroll
         for (int j = 0; j < NSLOT; ++j) bw[m][j] = *reinterpret_cast<const u32x4_t*>(w + j * 3 * 1024);
     };
+    // (the prologue's: lo and mid of chunk 0.)  In the K loop one fragment at a time, for the deal: load n of phase ph (A: component hi
+    // of chunk kgc; B: lo, then mid, of chunk kgn).  A buffer load through a descriptor of the slab's run (nK x WBLK bytes): the lane's
+    // 16 bytes are the vector offset, the fragment's place a scalar one - no vector address arithmetic among the MFMAs (a flat load's
+    // 64-bit address costs two VALU additions and a wait state per fragment past the 4 KiB the instruction's own offset reaches)
+    const auto wrs = __builtin_amdgcn_make_buffer_rsrc(const_cast<unsigned char*>(reinterpret_cast<const unsigned char*>(a_W) + ((size_t)(grp * Cf::S + s) * nK) * WBLK), 0, nK * WBLK, 0x00020000);
+    const int lane16 = 16 * lane;
+    auto load_dealt = [&](auto pc, auto nc, int kgc, int kgn) __attribute__((always_inline)) {
+        constexpr int ph = decltype(pc)::value, n = decltype(nc)::value;
+        constexpr int m = (ph == 0) ? 0 : (n < NSLOT ? 2 : 1), j = n % NSLOT;
+        bw[m][j] = __builtin_amdgcn_raw_buffer_load_b128(wrs, lane16, (ph == 0 ? kgc : kgn) * WBLK + m * 1024 + j * 3 * 1024, 0);
+    };
     f32x4_t big[MAXT][NR], sml[MAXT][NR];
 #pragma unroll
     for (int a = 0; a < MAXT; ++a)
@@ -300,8 +352,10 @@ __device__ __forceinline__ void bf3_conv_body(const float* a_src1, const float* 
     // are visible behind it, and every read of this stage has returned before it - the last entry's fragments were requested one
     // entry earlier and the barrier's own wait covers them.  A ring of three stages that bought the same early read was measured:
     // no gain, 1.7 k cycles more prologue - profiles/r06_bf16x3.md.)
-    // After phase A its weight components are refilled with the next chunk's; component hi, free after phase B, is requested at the
-    // head of the chunk that uses it (mfma_loop): every weight fragment is requested half a chunk (~1.4 k cycles) before its first use.
+    // Weight registers are refilled while they are dead (Bf3Cfg: the deal): component hi, free after phase B, in the first slots of
+    // phase A of the chunk that uses it - so the K loop ends without a hi refill nobody reads, for which the hand-over behind it (it
+    // reuses the weight registers) would have to wait - and lo and mid, free after phase A, with the next chunk's in the slots of
+    // phase B (the last chunk re-reads its own: harmless): every weight fragment is requested half a chunk (~1.4 k cycles) before its use.
     using AFrag = u32x4_t[2][NR][3];
     auto read_first = [&](auto hc, AFrag& av, const unsigned short* st) __attribute__((always_inline)) {
         constexpr int lp0 = Cf::first(decltype(hc)::value) % LIN;  // first entry (phase A: components hi, mid)
@@ -312,7 +366,7 @@ __device__ __forceinline__ void bf3_conv_body(const float* a_src1, const float* 
         }
     };
     // av[0] holds the first entry's fragments on entry; on exit those of the next chunk's first entry, read from `stn` (more: there is one)
-    auto chunk = [&](auto hc, AFrag& av, const unsigned short* st, const unsigned short* stn, int kgn, bool more) __attribute__((always_inline)) {
+    auto chunk = [&](auto hc, AFrag& av, const unsigned short* st, const unsigned short* stn, int kgc, int kgn, bool more) __attribute__((always_inline)) {
         constexpr int H = decltype(hc)::value;
         if constexpr (!Cf::ROTATE) read_first(hc, av, st);
         static_for<0, 2>([&](auto pc) __attribute__((always_inline)) {
@@ -323,14 +377,19 @@ __device__ __forceinline__ void bf3_conv_body(const float* a_src1, const float* 
                 if constexpr (Cf::needed(H, lp)) {
                     constexpr int buf = Cf::ord(H, q) & 1;
                     constexpr int qn = Cf::next(H, q);
-                    if constexpr (qn >= 0) {  // next entry's fragments: phase A reads the components hi and mid, phase B all three
-                        constexpr int lpn = qn % LIN, ncomp = (qn / LIN == 0) ? 2 : 3;
-#pragma unroll
-                        for (int r = 0; r < NR; ++r)
-#pragma unroll
-                            for (int m = 0; m < ncomp; ++m) av[buf ^ 1][r][m] = *reinterpret_cast<const u32x4_t*>(st + (lpn * 3 + m) * PLANE + r * RBLK + afrag);
+                    // next entry's fragments: phase A reads the components hi and mid, phase B all three.  The deal puts `rdd` of them
+                    // and `wd` weight loads into the slots behind this entry's MFMAs; the other reads go in front
+                    constexpr int rdd = Cf::reads_dealt(H, q), front = Cf::nreads(H, q) - rdd, wd = Cf::wdealt(H, q);
+                    auto read_next = [&](auto ic) __attribute__((always_inline)) {
+                        if constexpr (qn >= 0) {
+                            constexpr int lpn = qn % LIN, ncomp = (qn / LIN == 0) ? 2 : 3, r = decltype(ic)::value / ncomp, m = decltype(ic)::value % ncomp;
+                            av[buf ^ 1][r][m] = *reinterpret_cast<const u32x4_t*>(st + (lpn * 3 + m) * PLANE + r * RBLK + afrag);
+                        }
+                    };
+                    if constexpr (qn >= 0) {
+                        static_for<0, front>(read_next);
                         // the entry in front of the barrier: its reads first, so that the barrier's wait for them falls under this entry's MFMAs
-                        if constexpr (Cf::ROTATE && Cf::next(H, qn) < 0) __builtin_amdgcn_sched_barrier(0);
+                        if constexpr (Cf::DEALT ? front > 0 : Cf::next(H, qn) < 0) __builtin_amdgcn_sched_barrier(0);
                     }
                     if constexpr (qn < 0 && Cf::ROTATE) {  // the chunk's last entry: the closing barrier, the next chunk's first fragments, then this entry's MFMAs
                         static_assert(ph == 1 && buf == 1, "an even number of entries per chunk: the next chunk's first entry lands in register set 0");
@@ -348,13 +407,22 @@ __device__ __forceinline__ void bf3_conv_body(const float* a_src1, const float* 
                                 constexpr int sl = Cf::tslot(tl, lp) >= 0 ? Cf::tslot(tl, lp) : 0;
                                 constexpr int la = Cf::local(tl, H);
                                 constexpr bool one_acc = Cf::RES_ONE_ACC && tl >= LOUT;
-#pragma unroll
-                                for (int r = 0; r < NR; ++r) {  // (the row blocks share the weight fragment)
+                                static_for<0, NR>([&](auto rc) __attribute__((always_inline)) {  // (the row blocks share the weight fragment)
+                                    constexpr int r = decltype(rc)::value;
                                     if constexpr ((ia == 0 && wc == 0) || one_acc)
                                         big[la][r] = __builtin_amdgcn_mfma_f32_16x16x32_bf16(__builtin_bit_cast(bf16x8_t, av[buf][r][ia]), __builtin_bit_cast(bf16x8_t, bw[wc][sl]), big[la][r], 0, 0, 0);
                                     else
                                         sml[la][r] = __builtin_amdgcn_mfma_f32_16x16x32_bf16(__builtin_bit_cast(bf16x8_t, av[buf][r][ia]), __builtin_bit_cast(bf16x8_t, bw[wc][sl]), sml[la][r], 0, 0, 0);
-                                }
+                                    // the slot behind MFMA i of the entry: one memory instruction, alone
+                                    constexpr int i = (k * Cf::nfeed(H, lp) + Cf::nfeed(H, lp, tl)) * NR + r;
+                                    constexpr int slot = (i + 1) % Cf::DEAL == 0 ? (i + 1) / Cf::DEAL - 1 : -1;
+                                    if constexpr (slot >= 0 && slot < rdd + wd) {
+                                        __builtin_amdgcn_sched_barrier(0);
+                                        if constexpr (slot < rdd) read_next(std::integral_constant<int, front + (slot < rdd ? slot : 0)>{});
+                                        else load_dealt(pc, std::integral_constant<int, Cf::wbase(H, ph, lp) + slot - rdd>{}, kgc, kgn);
+                                        __builtin_amdgcn_sched_barrier(0);
+                                    }
+                                });
                             }
                         });
                     });
@@ -364,12 +432,11 @@ __device__ __forceinline__ void bf3_conv_body(const float* a_src1, const float* 
                     }
                 }
             });
-            // refill with the next chunk's components (the last chunk re-reads its own: harmless)
-            if constexpr (ph == 0) {
+            // the weight loads the phase's slots did not hold
+            static_for<Cf::wbase(H, ph, LIN), Cf::nweights(ph)>([&](auto nc) __attribute__((always_inline)) { load_dealt(pc, nc, kgc, kgn); });
+            if constexpr (!Cf::DEALT && ph == 0) {
                 load_w(kgn, std::integral_constant<int, 2>{});
                 load_w(kgn, std::integral_constant<int, 1>{});
-            } else if constexpr (!Cf::ROTATE) {  // (rotated: mfma_loop requests component hi at the head of its chunk)
-                load_w(kgn, std::integral_constant<int, 0>{});
             }
             __builtin_amdgcn_sched_barrier(0);
         });
@@ -390,7 +457,6 @@ __device__ __forceinline__ void bf3_conv_body(const float* a_src1, const float* 
     } else {
         load_w(0, std::integral_constant<int, 2>{});
         load_w(0, std::integral_constant<int, 1>{});
-        if constexpr (!Cf::ROTATE) load_w(0, std::integral_constant<int, 0>{});  // (rotated: at the head of chunk 0)
         // the hand-over's addends (spill), here so that it waits for no load of its own behind the epilogue's operand loads
         if constexpr (Cf::BIAS_EARLY) {
             bias_v = p.bias[co0 + s * 16 + (lane & 15)];
@@ -405,14 +471,11 @@ __device__ __forceinline__ void bf3_conv_body(const float* a_src1, const float* 
         AFrag av;
         if constexpr (Cf::ROTATE) read_first(hc, av, stg);
         for (int c = 0; c < nK; ++c) {
-            if constexpr (Cf::ROTATE) {
-                // component hi of THIS chunk, half a chunk before its use as ever - but requested here, at the head of the chunk, not
-                // behind the last one's MFMAs: the K loop then ends without a refill nobody reads, for which the hand-over behind it
-                // (it reuses the weight registers) would have to wait; and unconditional, as the waits for the fragments need it
+            if constexpr (!Cf::DEALT) {  // component hi of THIS chunk in one burst, half a chunk before its use
                 load_w(c, std::integral_constant<int, 0>{});
                 __builtin_amdgcn_sched_barrier(0);
             }
-            chunk(hc, av, stg + (c & 1) * STAGE, stg + ((c + 1) & 1) * STAGE, min(c + 1, nK - 1), c + 1 < nK);  // (the chunk barrier is inside)
+            chunk(hc, av, stg + (c & 1) * STAGE, stg + ((c + 1) & 1) * STAGE, c, min(c + 1, nK - 1), c + 1 < nK);  // (the chunk barrier is inside)
         }
     };
     if (mfma_wave) {
