@@ -10,8 +10,11 @@ stated in DESIGN.md: scenes/IK goals are synthetic unless a dataset object is su
 unless <model_dir>/TemporalUNetModel<T>_N<traj_len>/weights_latest.pt exists, success is the geometric proxy
 (pybullet absent)."""
 import argparse
+import json
 import os
 import time
+from concurrent.futures import ThreadPoolExecutor
+from types import SimpleNamespace
 
 import numpy as np
 import torch
@@ -22,6 +25,7 @@ from edmp_amd import franka
 from edmp_amd import guide_cfg as GC
 from edmp_amd.diffusion import DEFAULT_CHUNK_STEPS, DeviceNoise, Diffusion, PinnedNoiseStream, chunk_plan
 from edmp_amd.guide import IntersectionVolumeGuide, SceneBatch, pick_goal
+from edmp_amd.runtime import get_context, lane_context
 from edmp_amd.scenes import SyntheticDataset
 from edmp_amd.temporalunet import TemporalUNet
 
@@ -153,6 +157,334 @@ def job_summary(results, world=1, self_collision=False, repair=False):
     return out
 
 
+def _dataset(cfg):
+    """the run config's own dataset.  The reference's types (datasets/load_test_dataset.py:15-38: 'global' | 'hybrid' | 'both' ->
+    <path>/<type>_solvable_problems.pkl) are served from the JSON scripts/mpinets_pkl_to_json.py writes next to the pickle, when it is there"""
+    d = cfg["dataset"]
+    if d["dataset_type"] not in ("global", "hybrid", "both"):
+        return SyntheticDataset(d["dataset_type"], d_path=d["path"], scene_types=d["scene_types"], num_scenes_per_type=d.get("num_scenes_per_type", 1))
+    converted = os.path.join(d["path"], f"{d['dataset_type']}_solvable_problems.json")
+    if not os.path.exists(converted):
+        raise FileNotFoundError(f"{converted} not found: convert {d['dataset_type']}_solvable_problems.pkl with scripts/mpinets_pkl_to_json.py (IK goals via --ik-goals), "
+                                "or use dataset_type: 'synthetic'")
+    from edmp_amd.scenes import ProblemSetDataset
+
+    return ProblemSetDataset(converted)
+
+
+def _my_scenes(scene_types, dataset, max_scenes, rank, world):
+    """this rank's scenes as (i, scene_type, scene_num), in the cfg's order (scene i of that order belongs to rank i mod world)"""
+    mine, i = [], 0
+    for scene_type in scene_types:
+        for scene_num in range(dataset.data_nums[scene_type]):
+            if max_scenes is not None and i >= max_scenes:
+                break
+            if i % world == rank:
+                mine.append((i, scene_type, scene_num))
+            i += 1
+    return mine
+
+
+def _lanes(job, base, k, model_dir, max_batch):
+    """one (diffuser, denoiser) per scene in flight; the weights are replicated per context.  Lane 0 = the device's context `base`; further
+    lanes are cached per (device, lane), not re-created per call"""
+    model_name = model_dir + "TemporalUNetModel" + str(job.T) + "_N" + str(job.traj_len)
+    if not os.path.exists(model_name):
+        if job.verbose and job.rank == 0:
+            print(f"[infer_serial] {model_name} not found: using a seeded random-init denoiser (no trained weights offline)")
+        model_name = None
+    return [(Diffusion(T=job.T, device=ctx), TemporalUNet(model_name=model_name, input_dim=job.num_channels, time_dim=32, dims=(32, 64, 128, 256, 512, 512), device=ctx, max_batch=max_batch))
+            for ctx in (lane_context(base, j) for j in range(k))]
+
+
+def _fetch(job, lane, scenes):
+    """dataset.fetch_data per scene; with ik_seeds, the targets of the scenes that bring no goals are solved first, in one call"""
+    ds = job.dataset
+    if not job.iks:
+        return [ds.fetch_data(scene_num=scene_num, scene_type=scene_type) for _, scene_type, scene_num in scenes]
+    poses = [ds.target_pose(scene_num, scene_type) for _, scene_type, scene_num in scenes]
+    need = [j for j, p in enumerate(poses) if p is not None]
+    solved = dict(zip(need, job.iks[lane].solve_many([poses[j] for j in need])["goals"])) if need else {}
+    return [ds.fetch_data(scene_num=scene_num, scene_type=scene_type, **({"goals": solved[j]} if j in solved else {})) for j, (_, scene_type, scene_num) in enumerate(scenes)]
+
+
+def _goal_kw(job, scenes):
+    """the goal term's constructor keywords, one dict per scene (empty without a goal-weighted guide: the guides are built as they
+    were): the problems' own target poses in the frame ik_tool when every scene of the group carries one, else the pose of the picked goal"""
+    if "sdf_goal_weight" not in job.guide_cfgs:
+        return [{} for _ in scenes]
+    probs = getattr(job.dataset, "problems", None)  # (ProblemSetDataset.target_pose answers None for a problem that brings its own IK goals)
+    targets = [probs[scene_type][scene_num].get("target") if probs is not None and scene_type in probs else None for _, scene_type, scene_num in scenes]
+    poses = [None if t is None else (t["xyz"], t["quaternion_wxyz"]) for t in targets]
+    if all(p is not None for p in poses):
+        return [dict(goal_target=(np.asarray(p[0], dtype=np.float64), np.asarray(p[1], dtype=np.float64)), goal_tool=job.ik_tool) for p in poses]
+    return [dict(goal_tool=job.ik_tool) for _ in poses]
+
+
+def _guide(job, ctx, data, goal_kw, bind=True):
+    """the guide of one fetched scene on the context ctx.  obstacle_config = cuboids first, then cylinders as (r, r, h) boxes
+    (datasets/load_test_dataset.py:141-149); the success check spawns the latter as true cylinders (infer_serial.py:159-163 ->
+    lib/environment.py:249-268).  bind=False: host tables only, for a SceneBatch"""
+    obstacle_config, _, _, num_cuboids, num_cylinders, _, _ = data
+    kinds = np.concatenate([np.zeros(int(num_cuboids), dtype=np.int32), np.ones(int(num_cylinders), dtype=np.int32)])
+    return IntersectionVolumeGuide(obstacle_config=obstacle_config, device=ctx, guide_cfgs=job.guide_cfgs, batch_size=job.total_batch_size, obstacle_kinds=kinds,
+                                   mesh_dir=job.mesh_dir, bind=bind, **goal_kw)
+
+
+def _meta(job, scene):
+    """the head of a scene's result; `noise_seed` is the key device_noise adds to it (none without it)"""
+    i, scene_type, scene_num = scene
+    return dict(scene_type=scene_type, scene_num=scene_num, **({} if job.device_noise is None else {"noise_seed": scene_seed(job.device_noise, i)}))
+
+
+class _Path:
+    """What tells the serial loop from a scene group in the one scoring step (_score), the way guide._SlotObject's ``shape`` tells edmp_x
+    from edmp_scenes_x: obj = the IntersectionVolumeGuide, shape (B,), the rows a host (B, C, N) array | obj = the SceneBatch, shape
+    (S, B), the rows the (S, B, C, N) device state.  The serial loop asks the chosen-plan reports for the chosen row alone, a group for
+    all rows in one call.  `stamps` collects the times that become the result's `timings`, in `timings()`'s order; _score leaves `picked_at`
+    and `checked_at`, when the selection and the success check returned (where the serial loop's planning time and scene wall time end)."""
+
+    def __init__(self, obj, shape):
+        self.obj, self.shape, self.grouped, self.stamps = obj, shape, len(shape) == 2, {}
+        self.select = obj.select_rows if self.grouped else obj.select_row
+
+    def scenes(self, a):
+        """a per-row (or per-scene) result of `obj` with the scene axis in front"""
+        return a if self.grouped else np.asarray(a)[None]
+
+    def chosen(self, X, idx):
+        """-> (the rows the chosen-plan reports are asked for, per scene the chosen row's place in what they answer)"""
+        return (X, idx) if self.grouped else (X[idx][None], [0])
+
+    def interior(self, rows):
+        """what sdf_rows / sdf_sweep_rows / sdf_self_rows take: a guide the interior waypoints, a batch the full state"""
+        return rows if self.grouped else rows[:, :, 1:-1]
+
+    def goal_rows(self, rows):
+        """the goal report with the goal column handed over as well: the final tool pose's distance and angle"""
+        return self.obj.sdf_goal_rows(rows, final=True) if self.grouped else self.obj.sdf_goal_rows(rows[:, :, 1:])
+
+    def sweep_substeps(self, idx):
+        """the substeps of the swept clearance: the rows' own where they carry the swept-clearance term (sample guide 104), else the success
+        check's (success_rows' default) - for the chosen row of a guide; a batch takes its rows' own (None) as soon as one row carries the term"""
+        if self.grouped:
+            return None if self.obj.has_sweep_term else CHECK_SUBSTEPS
+        d = self.obj._sdf
+        return int(d["sweep_substeps"][idx]) if d["sweep_weight"][idx] > 0 else CHECK_SUBSTEPS
+
+    def host(self, X):
+        """the scored rows on the host, scene axis in front: a group's state comes back once, for the result dicts"""
+        return self.obj.ctx.to_host(X) if self.grouped else X[None]
+
+    def timings(self):
+        order = (("noise_wait_s", "batch_metrics_s", "denoise_s", "repair_s", "denoise_s_is", "best_trajectory_s", "success_check_s") if self.grouped else
+                 ("noise_wait_s", "denoise_s", "repair_s", "best_trajectory_s", "batch_metrics_s", "success_check_s"))
+        return {k: self.stamps[k] for k in order if k in self.stamps}
+
+
+def _score(job, on, X, starts, goals, tb):
+    """THE scoring step of both loops, from the end of the denoising loop (at time tb) to what _result writes down: repair -> select_row(s)
+    -> the metrics when the report wants them -> success_rows -> the chosen plans' sphere reports -> self_collision_rows, on the finished
+    rows X of the path `on` (_Path).  Every call scores ALL rows of X - a group's (S, B, C, N) state stays on the device and is scored as
+    one batch - but the chosen-plan reports, which the path says the rows of.  -> one record of scores per scene (the serial loop: one)."""
+    obj, st, report = on.obj, on.stamps, job.ensemble_report
+    moved = clear = None
+    if job.repair:  # the whole batch / group in one launch, between the loop and the selection; everything behind it sees the repaired rows
+        rep = obj.repair_rows(X, starts, goals, iters=job.repair, substeps=CHECK_SUBSTEPS, margin=job.repair_margin, step=job.repair_step, return_device=on.grouped)
+        X = rep["trajectories"]
+        moved, clear = (on.scenes(a) for a in repair_tally(rep, job.repair, job.repair_margin))
+        st["repair_s"] = time.time() - tb
+        tb = time.time()
+    idx, vols, met = on.select(starts, goals, X, prefer=job.prefer)
+    on.picked_at = tc = time.time()
+    st["best_trajectory_s"] = tc - tb
+    if report and met is None:  # (the metrics need no scene: one call over all rows)
+        met = {k: v.reshape(on.shape) for k, v in EV.batch_metrics(X.reshape((-1,) + tuple(X.shape[-2:])), device=obj.ctx).items()}
+        st["batch_metrics_s"] = time.time() - tc
+    # success: pybullet execution (lib/environment.py:632-680) is unavailable -> exact link-box vs cuboid / cylinder
+    # check along the interpolated trajectory, for EVERY row in one kernel (csrc/success.hip); the
+    # scene's success is the chosen row's flag (infer_serial.py:165-168) under the reference's rule - no contact;
+    # leaving the joint limits only prints there (lib/environment.py:659-661, 672) -, the stricter flag (also inside the
+    # limits) and the batch rates are reported next to it, as is the guide's own (conservative, AABB) criterion
+    td = time.time()
+    chk = obj.success_rows(X)
+    on.checked_at = te = time.time()
+    st["success_check_s"] = te - td
+    rows, place = on.chosen(X, idx)
+    chosen = {}
+    if report and obj.has_sdf_rows:  # (a run with an SDF guide: the sphere model's clearance, and the same at the success check's interpolants)
+        chosen["min_clearance"] = obj.sdf_rows(on.interior(rows), starts, goals)["clearance"]
+        chosen["min_swept_clearance"] = obj.sdf_sweep_rows(on.interior(rows), starts, goals, substeps=on.sweep_substeps(idx))["clearance"]
+    if report and obj.has_self_term:
+        chosen["min_self_clearance"] = obj.sdf_self_rows(on.interior(rows))["clearance"]
+    goal = on.goal_rows(rows) if report and obj.has_goal_term else None
+    selfcol = obj.self_collision_rows(X) if job.self_collision else None
+    lead = lambda d: None if d is None else {k: on.scenes(v) for k, v in d.items()}  # noqa: E731
+    of = lambda d, *at: None if d is None else {k: v[at] for k, v in d.items()}  # noqa: E731
+    idx, vols, X, chk, met, selfcol, goal, chosen = on.scenes(idx), on.scenes(vols), on.host(X), lead(chk), lead(met), lead(selfcol), lead(goal), lead(chosen)
+    return [SimpleNamespace(idx=int(i), vols=vols[s], trajectory=X[s][int(i)], met=of(met, s), selfcol=of(selfcol, s), chosen=of(chosen, s, place[s]), goal=of(goal, s, place[s]),
+                            chk={k: (v if np.ndim(v) else int(v)) for k, v in of(chk, s).items()},  # (the per-row flags, and the scene's counts as ints)
+                            repair=None if moved is None else (moved[s], clear[s])) for s, i in enumerate(idx)]
+
+
+def _result(job, meta, tm, sc, t0, plan_end, wall_end=None, scenes_in_launch=None):
+    """THE result dict of one scene: meta and the timings tm, `scenes_in_launch` behind them for a group, the base keys from the scene's scores
+    sc (_score), then what each extension adds, in this order.  plan_end: where the scene's "Planning Time" ends (infer_serial.py:108-157:
+    guide construction + IK filter + sampling + best pick); wall_end=None: now.  A new report is added here and in _score / _Path, nowhere else."""
+    idx, vols, chk, trajectory = sc.idx, sc.vols, sc.chk, sc.trajectory
+    r = dict(**meta, timings=tm, **({} if scenes_in_launch is None else {"scenes_in_launch": scenes_in_launch}),
+             best_row=idx, swept_volume=float(vols[idx]), success_proxy=int(chk["collision_free"][idx]), success_strict=int(chk["ok"][idx]),
+             rows_collision_free=chk["rows_collision_free"], rows_ok=chk["rows_ok"], rows=chk["rows"], aabb_volume_zero=bool(ED.geometric_success(float(vols[idx]), trajectory)),
+             first_collision_waypoint=int(chk["first"][idx]), path_length=EV.path_lengths(trajectory), sparc=EV.smoothness(trajectory), planning_time_s=plan_end - t0,
+             scene_wall_s=(time.time() if wall_end is None else wall_end) - t0, trajectory=trajectory)
+    r.update({k: float(v) for k, v in sc.chosen.items()})  # ensemble_report with an SDF guide: min_clearance, min_swept_clearance; with the self-clearance term: min_self_clearance
+    if sc.goal is not None:  # the guide carries the goal term: the chosen plan's final tool pose against the target, in the reference evaluator's units (mpinets/metrics.py:364-385)
+        r.update(position_error=100.0 * float(sc.goal["distance"]), orientation_error=float(np.degrees(sc.goal["angle"])))
+    if sc.selfcol is not None:  # self_collision: self_collision_rows' dict of the scene's rows
+        a, b = (int(v) for v in sc.selfcol["pair"][idx])
+        r.update(self_collision_free=int(sc.selfcol["free"][idx]), rows_self_collision_free=int(np.count_nonzero(sc.selfcol["free"])),
+                 first_self_collision_waypoint=int(sc.selfcol["first"][idx]), self_collision_pair=None if a < 0 else [franka.LINK_NAMES[a], franka.LINK_NAMES[b]])
+    if sc.repair is not None:  # repair: (moved, clear) of the scene's rows (repair_tally)
+        r.update(rows_repaired=int(sc.repair[0].sum()), rows_repair_clear=int(sc.repair[1].sum()), repair_iters=int(job.repair))
+    if job.prefer is not None:
+        r["prefer"] = job.prefer
+    if job.ensemble_report:
+        r["ensemble"] = EV.ensemble_report(job.guide_numbers, job.guide_rows, vols, chk, sc.met)
+    return r
+
+
+def _plan(job, lane, guide, start_joints, goal_joints, noise, meta, tm, t0):
+    """one prepared scene on its lane: the loop, the scoring step, the result"""
+    diffuser, denoiser = job.lanes[lane]
+    on = _Path(guide, (job.total_batch_size,))
+    pinned = None
+    if noise is not None and not isinstance(noise, DeviceNoise):  # this scene's stream, drawn ahead by the feeder into page-locked memory: uploaded in chunks beside the loop
+        t_w = time.time()
+        pinned = noise.result() if hasattr(noise, "result") else noise
+        on.stamps["noise_wait_s"] = time.time() - t_w
+        noise = pinned
+    ta = time.time()
+    trajectories = diffuser.denoise_guided(model=denoiser, guide=guide, batch_size=job.total_batch_size, traj_len=job.traj_len, num_channels=job.num_channels, condition=True,
+                                           benchmarking=True, start=start_joints, goal=goal_joints, guidance_schedule=job.guide_cfgs["guidance_schedule"], noise=noise)
+    tb = time.time()
+    if pinned is not None:
+        job.feeder.recycle(pinned)  # (denoise_guided returned host trajectories: the upload out of the buffer is long done)
+    on.stamps["denoise_s"] = tb - ta
+    sc, = _score(job, on, trajectories, start_joints, goal_joints, tb)
+    return _result(job, meta, {**tm, **on.timings()}, sc, t0, on.picked_at, on.checked_at)
+
+
+def _prepare_group(job, scenes):
+    """guides + IK filter of a scene group (infer_serial.py:108-129, once per scene there): the guides are host tables only
+    (bind=False), the SceneBatch is the one object on the device, and ONE filter_goals call picks every scene's goal.
+    -> (batch, [(start, goal, meta, timings, t0) per scene]); guide_ctor_s / ik_filter_s are the GROUP's times"""
+    data = _fetch(job, 0, scenes)
+    t0 = time.time()
+    batch = SceneBatch([_guide(job, job.lanes[0][0].ctx, d, gkw, bind=False) for d, gkw in zip(data, _goal_kw(job, scenes))])
+    t1 = time.time()
+    starts = np.stack([np.asarray(d[5], dtype=np.float64) for d in data])
+    _, chosen, _ = batch.filter_goals(starts, [d[6] for d in data])
+    t2 = time.time()
+    what = f"group of {len(data)} scenes"
+    return batch, [(d[5], goal_joints, _meta(job, scene), dict(guide_ctor_s=t1 - t0, guide_ctor_s_is=what, ik_filter_s=t2 - t1, ik_filter_s_is=what), t0)
+                   for scene, d, goal_joints in zip(scenes, data, chosen)]
+
+
+def _plan_group(job, batch, group):
+    """k prepared scenes in one launch chain and one scoring step; per scene the serial loop's result keys.  denoise_s, repair_s,
+    noise_wait_s, best_trajectory_s, batch_metrics_s and success_check_s are the whole group's calls"""
+    diffuser, denoiser = job.lanes[0]
+    on = _Path(batch, (len(group), job.total_batch_size))
+    t_w = time.time()
+    streams = [job.feeder.next() for _ in group] if job.feeder is not None else DeviceNoise(seeds=[g[2]["noise_seed"] for g in group])
+    on.stamps["noise_wait_s"] = time.time() - t_w
+    starts, goals = np.stack([g[0] for g in group]), np.stack([g[1] for g in group])
+    ta = time.time()
+    Xd = diffuser.denoise_guided_scenes(denoiser, batch, job.traj_len, job.num_channels, starts, goals, noise=streams, condition=True, return_device=True)
+    tb = time.time()
+    for st in streams if job.feeder is not None else ():
+        job.feeder.recycle(st)  # (the call synchronised before it returned the device state: every upload out of the buffers is done)
+    on.stamps.update(denoise_s=tb - ta, denoise_s_is=f"group of {len(group)} scenes")
+    scores = _score(job, on, Xd, starts, goals, tb)
+    return [_result(job, meta, {**tm, **on.timings()}, sc, t0, time.time(), scenes_in_launch=len(group)) for (_, _, meta, tm, t0), sc in zip(group, scores)]
+
+
+def _serial_loop(job, mine, k):
+    """the reference's loop, one scene after the other on k lanes: guide, IK-goal filter, then the lane plans the scene (k = 1: at once,
+    the reference's order of events).  The feeder thread draws every scene's whole stream in scene order from the global RandomState, so
+    every scene sees the numbers the reference's loop would give it (nothing else may draw from the global state while a run is in
+    progress); pool.submit hands the scenes to the lanes in order, the feeder hands the streams out in the same order"""
+    pending = []
+    with ThreadPoolExecutor(max_workers=k) as pool:
+        for scene in mine:
+            lane = (scene[0] // job.world) % k
+            while len(pending) >= k:  # the lane's previous scene (and every earlier one) is done before its context is reused
+                _collect(job, pending.pop(0))
+            data = _fetch(job, lane, [scene])[0]
+            start_joints, all_ik_goals = data[5], data[6]
+            t0 = time.time()
+            guide = _guide(job, job.lanes[lane][0].ctx, data, _goal_kw(job, [scene])[0])
+            t1 = time.time()
+            # IK-goal filter                                                              infer_serial.py:117-129
+            volumes = guide.cost(torch.tensor(all_ik_goals.reshape((-1, 7, 1))), 0, batch_size=all_ik_goals.shape[0]).sum(axis=(1, 2)).cpu().numpy()
+            _, goal_joints = pick_goal(volumes, all_ik_goals, start_joints)
+            t2 = time.time()
+            meta = _meta(job, scene)
+            noise = job.feeder.next() if job.feeder is not None else DeviceNoise(meta["noise_seed"])
+            args = (job, lane, guide, start_joints, goal_joints, noise, meta, dict(guide_ctor_s=t1 - t0, ik_filter_s=t2 - t1), t0)
+            if k == 1:
+                _collect(job, _plan(*args))
+            else:
+                pending.append(pool.submit(_plan, *args))
+        while pending:
+            _collect(job, pending.pop(0))
+
+
+def _print_scene(r, n, tally, prefix=""):
+    """the lines of scene n's result r under the running tallies"""
+    print(prefix + f"Scene {n} ({r['scene_type']}/{r['scene_num']}): planning {r['planning_time_s']:.2f} s, best row {r['best_row']}, swept volume "
+          f"{r['swept_volume']:.4g}, geometric success (proxy, collision-free) {r['success_proxy']} ({r['rows_collision_free']}/{r['rows']} rows of the batch); "
+          f"also within the joint limits {r['success_strict']} ({r['rows_ok']}/{r['rows']})   running {tally.success}/{n} (strict {tally.strict}/{n})")
+    for line in EV.format_ensemble_report(r.get("ensemble", ())):
+        print(line)
+    if "min_clearance" in r:  # (a run with an SDF guide: the sphere model's smallest clearance along the chosen plan)
+        print(f"    chosen plan: minimum sphere clearance {r['min_clearance']:.4f} m")
+    if "min_swept_clearance" in r:  # (the same at the configurations the success check interpolates between the waypoints)
+        print(f"    chosen plan: minimum swept sphere clearance {r['min_swept_clearance']:.4f} m")
+    if "min_self_clearance" in r:  # (the guide carries the self-clearance term: the sphere model's smallest distance to itself)
+        print(f"    chosen plan: minimum self clearance {r['min_self_clearance']:.4f} m")
+    if "position_error" in r:  # (the guide carries the goal term: the final tool pose against the target)
+        print(f"    chosen plan: position_error {r['position_error']:.3f} cm, orientation_error {r['orientation_error']:.3f} deg")
+    if "rows_repaired" in r:
+        print(f"    repair ({r['repair_iters']} iterations at most): {r['rows_repaired']}/{r['rows']} rows moved, {r['rows_repair_clear']}/{r['rows']} ended clear")
+    if "self_collision_free" in r:
+        print(f"    self-collision free {r['self_collision_free']} ({r['rows_self_collision_free']}/{r['rows']} rows of the batch)   running {tally.self_free}/{n}")
+        if "ensemble" in r:
+            print("    chosen plan: " + ("no self-collision" if r["self_collision_pair"] is None else
+                                         f"self-collision of {r['self_collision_pair'][0]} and {r['self_collision_pair'][1]} at waypoint {r['first_self_collision_waypoint']}"))
+
+
+def _collect(job, fut):
+    """a finished scene (or the future of one): stamped, kept, tallied, printed"""
+    r = fut.result() if hasattr(fut, "result") else fut
+    r["done_at"] = time.time()
+    job.results.append(r)
+    job.tally.success += r["success_proxy"]  # the reference's tally: collision-free (infer_serial.py:165-168 on lib/environment.py:672)
+    job.tally.strict += r["success_strict"]
+    job.tally.self_free += r.get("self_collision_free", 0)
+    if job.verbose:
+        _print_scene(r, len(job.results), job.tally, "" if job.world == 1 else f"[rank {job.rank}] ")
+
+
+def _print_summary(summary):
+    print(f"[infer_serial] {summary['scenes']} scenes on {summary['ranks']} rank(s): success (proxy, collision-free) {summary['success_proxy']}/{summary['scenes']}, "
+          f"strict {summary['success_strict']}/{summary['scenes']}, rows collision-free {summary['rows_collision_free']}/{summary['rows']}")
+    if "self_collision_free" in summary:
+        print(f"[infer_serial] self-collision free {summary['self_collision_free']}/{summary['scenes']}, rows {summary['rows_self_collision_free']}/{summary['rows']}")
+    if "rows_repaired" in summary:
+        print(f"[infer_serial] repair: {summary['rows_repaired']}/{summary['rows']} rows moved, {summary['rows_repair_clear']}/{summary['rows']} ended clear")
+
+
 def run(cfg_path, dataset=None, max_scenes=None, verbose=True, scenes_in_flight=1, shard_scenes=True, scenes_per_launch=1, ensemble_report=False, prefer=None,
         ik_seeds=0, ik_tool=None, ik_seed=0, self_collision=False, device_noise=None, repair=0, repair_margin=0.02, repair_step=0.02):
     """The reference's scene loop (infer_serial.py:95-170).  Under ``torch.distributed.run`` (one process per GPU, extension: the
@@ -218,10 +550,6 @@ def run(cfg_path, dataset=None, max_scenes=None, verbose=True, scenes_in_flight=
     model's hinge at ``repair_margin`` over the waypoints and the CHECK_SUBSTEPS - 1 interpolants per segment that the success check tests.
     Everything behind it sees the repaired rows.  Each result adds `rows_repaired` (rows that moved), `rows_repair_clear` (rows whose last
     evaluation had no active hinge, repair_tally) and `repair_iters`; the per-scene line and the summary print the two counts."""
-    from concurrent.futures import ThreadPoolExecutor
-
-    from edmp_amd.runtime import get_context, lane_context
-
     t_enter = time.time()
     kl = int(scenes_per_launch)
     if kl < 1:
@@ -233,349 +561,53 @@ def run(cfg_path, dataset=None, max_scenes=None, verbose=True, scenes_in_flight=
         raise ValueError(f"repair must be >= 0 iterations (0 = off), got {repair}")
     if device_noise is not None:
         DeviceNoise(device_noise)  # (an integer in [0, 2^64), or it raises)
-    benchmark_cfg = GC.load_yaml(cfg_path)
-    rank, world, device = _ranks(benchmark_cfg["model"]["device"]) if shard_scenes else (0, 1, benchmark_cfg["model"]["device"])
-    traj_len = benchmark_cfg["model"]["traj_len"]
-    T = benchmark_cfg["model"]["T"]
-    num_channels = benchmark_cfg["model"]["num_channels"]
+    cfg = GC.load_yaml(cfg_path)
+    model = cfg["model"]
+    rank, world, device = _ranks(model["device"]) if shard_scenes else (0, 1, model["device"])
     if dataset is None:
-        # the reference's own dataset types (datasets/load_test_dataset.py:15-38: 'global' | 'hybrid' | 'both' -> <path>/<type>_solvable_problems.pkl):
-        # served from the JSON scripts/mpinets_pkl_to_json.py writes next to the pickle, when it is there
-        dtype, dpath = benchmark_cfg["dataset"]["dataset_type"], benchmark_cfg["dataset"]["path"]
-        converted = os.path.join(dpath, f"{dtype}_solvable_problems.json")
-        if dtype in ("global", "hybrid", "both"):
-            if not os.path.exists(converted):
-                raise FileNotFoundError(f"{converted} not found: convert {dtype}_solvable_problems.pkl with scripts/mpinets_pkl_to_json.py (IK goals via --ik-goals), "
-                                        "or use dataset_type: 'synthetic'")
-            from edmp_amd.scenes import ProblemSetDataset
-
-            dataset = ProblemSetDataset(converted)
-    if dataset is None:
-        dataset = SyntheticDataset(benchmark_cfg["dataset"]["dataset_type"], d_path=benchmark_cfg["dataset"]["path"],
-                                   scene_types=benchmark_cfg["dataset"]["scene_types"],
-                                   num_scenes_per_type=benchmark_cfg["dataset"].get("num_scenes_per_type", 1))
-    guide_cfgs = GC.guide_cfgs_from_run_cfg(benchmark_cfg, base_dir=os.path.dirname(os.path.abspath(cfg_path)) + "/..")
-    total_batch_size = guide_cfgs["total_batch_size"]
+        dataset = _dataset(cfg)
+    guide_cfgs = GC.guide_cfgs_from_run_cfg(cfg, base_dir=os.path.dirname(os.path.abspath(cfg_path)) + "/..")
     if prefer not in (None, "shortest", "smoothest"):
         raise ValueError(f"prefer must be None, 'shortest' or 'smoothest', got {prefer!r}")
-    guide_numbers = [int(n) for n in benchmark_cfg["guide"]["guides"]]
-    guide_rows = GC.split_rows(int(benchmark_cfg["guide"]["total_rows"]), len(guide_numbers)) if benchmark_cfg["guide"].get("total_rows") else guide_cfgs["batch_size_per_guide"]
-
-    def extras(vols, chk, met):
-        """the keys the two extensions add to a scene's result (none without them)"""
-        out = {}
-        if prefer is not None:
-            out["prefer"] = prefer
-        if ensemble_report:
-            out["ensemble"] = EV.ensemble_report(guide_numbers, guide_rows, vols, chk, met)
-        return out
-
-    def goal_kw(scenes_of_group):
-        """the goal term's constructor keywords, one dict per scene (empty without a goal-weighted guide: the guides are built as they
-        were): the problems' own target poses in the frame ik_tool when every scene of the group carries one, else the pose of the picked goal"""
-        if "sdf_goal_weight" not in guide_cfgs:
-            return [{} for _ in scenes_of_group]
-        probs = getattr(dataset, "problems", None)  # (ProblemSetDataset.target_pose answers None for a problem that brings its own IK goals)
-        targets = [probs[scene_type][scene_num].get("target") if probs is not None and scene_type in probs else None for _, scene_type, scene_num in scenes_of_group]
-        poses = [None if t is None else (t["xyz"], t["quaternion_wxyz"]) for t in targets]
-        if all(p is not None for p in poses):
-            return [dict(goal_target=(np.asarray(p[0], dtype=np.float64), np.asarray(p[1], dtype=np.float64)), goal_tool=ik_tool) for p in poses]
-        return [dict(goal_tool=ik_tool) for _ in poses]
-
-    def goal_extras(rep, idx):
-        """the chosen plan's final tool pose against the target, in the reference evaluator's units (mpinets/metrics.py:364-385)"""
-        return dict(position_error=100.0 * float(rep["distance"][idx]), orientation_error=float(np.degrees(rep["angle"][idx])))
-
-    def sweep_substeps(guide, idx):
-        """the substeps of the chosen row's swept clearance: the row's own where it carries the swept-clearance term (sample guide 104),
-        else the success check's (IntersectionVolumeGuide.success_rows' default)"""
-        d = guide._sdf
-        return int(d["sweep_substeps"][idx]) if d["sweep_weight"][idx] > 0 else CHECK_SUBSTEPS
-
-    def self_extras(sc, idx):
-        """the keys self_collision adds to a scene's result: sc = self_collision_rows' dict of the scene's rows"""
-        a, b = (int(v) for v in sc["pair"][idx])
-        return dict(self_collision_free=int(sc["free"][idx]), rows_self_collision_free=int(np.count_nonzero(sc["free"])),
-                    first_self_collision_waypoint=int(sc["first"][idx]), self_collision_pair=None if a < 0 else [franka.LINK_NAMES[a], franka.LINK_NAMES[b]])
-
-    model_name = benchmark_cfg["model"]["model_dir"] + "TemporalUNetModel" + str(T) + "_N" + str(traj_len)
-    if not os.path.exists(model_name):
-        if verbose and rank == 0:
-            print(f"[infer_serial] {model_name} not found: using a seeded random-init denoiser (no trained weights offline)")
-        model_name = None
+    guide_numbers = [int(n) for n in cfg["guide"]["guides"]]
+    job = SimpleNamespace(  # what the functions above share: the config's constants, the options, the dataset, the lanes and the running tallies
+        T=model["T"], traj_len=model["traj_len"], num_channels=model["num_channels"], mesh_dir=model.get("mesh_dir"), guide_cfgs=guide_cfgs,
+        total_batch_size=guide_cfgs["total_batch_size"], guide_numbers=guide_numbers,
+        guide_rows=GC.split_rows(int(cfg["guide"]["total_rows"]), len(guide_numbers)) if cfg["guide"].get("total_rows") else guide_cfgs["batch_size_per_guide"],
+        dataset=dataset, rank=rank, world=world, verbose=verbose, prefer=prefer, ensemble_report=ensemble_report, self_collision=self_collision, device_noise=device_noise,
+        repair=repair, repair_margin=repair_margin, repair_step=repair_step, ik_tool=ik_tool, iks=[], feeder=None, results=[], tally=SimpleNamespace(success=0, strict=0, self_free=0))
     k = max(1, int(scenes_in_flight))
     base = get_context(device)
-    lanes = []  # one (context, diffuser, denoiser) per scene in flight; the weights are replicated per context
-    for j in range(k):
-        ctx = lane_context(base, j)  # lane 0 = the device's context; further lanes are cached per (device, lane), not re-created per call
-        lanes.append((Diffusion(T=T, device=ctx), TemporalUNet(model_name=model_name, input_dim=num_channels, time_dim=32, dims=(32, 64, 128, 256, 512, 512),
-                                                                device=ctx, max_batch=total_batch_size * kl)))
-
+    job.lanes = _lanes(job, base, k, model["model_dir"], max_batch=job.total_batch_size * kl)
     ik_seeds = int(ik_seeds)
     if ik_seeds < 0:
         raise ValueError(f"ik_seeds must be >= 0, got {ik_seeds}")
-    iks = []  # one solver per lane (a lane's context is only touched while its previous scene is done)
     if ik_seeds > 0 and hasattr(dataset, "target_pose"):
         from edmp_amd.ik import FrankaIK
 
-        iks = [FrankaIK(lane[0].ctx, n_seeds=ik_seeds, seed=ik_seed, tool=ik_tool) for lane in lanes]
-
-    def fetch(lane, scenes_of_group):
-        """dataset.fetch_data per scene; with ik_seeds, the targets of the scenes that bring no goals are solved first, in one call"""
-        if not iks:
-            return [dataset.fetch_data(scene_num=scene_num, scene_type=scene_type) for _, scene_type, scene_num in scenes_of_group]
-        poses = [dataset.target_pose(scene_num, scene_type) for _, scene_type, scene_num in scenes_of_group]
-        need = [j for j, p in enumerate(poses) if p is not None]
-        solved = dict(zip(need, iks[lane].solve_many([poses[j] for j in need])["goals"])) if need else {}
-        return [dataset.fetch_data(scene_num=scene_num, scene_type=scene_type, **({"goals": solved[j]} if j in solved else {}))
-                for j, (_, scene_type, scene_num) in enumerate(scenes_of_group)]
-
-    def plan(lane, guide, start_joints, goal_joints, noise, meta, t0):
-        diffuser, denoiser = lanes[lane]
-        tm = dict(meta.pop("timings"))
-        pinned = None
-        if noise is not None and not isinstance(noise, DeviceNoise):  # this scene's stream, drawn ahead by the feeder into page-locked memory: uploaded in chunks beside the loop
-            t_w = time.time()
-            pinned = noise.result() if hasattr(noise, "result") else noise
-            tm["noise_wait_s"] = time.time() - t_w
-            noise = pinned
-        ta = time.time()
-        trajectories = diffuser.denoise_guided(model=denoiser, guide=guide, batch_size=total_batch_size, traj_len=traj_len,
-                                               num_channels=num_channels, condition=True, benchmarking=True, start=start_joints,
-                                               goal=goal_joints, guidance_schedule=guide_cfgs["guidance_schedule"], noise=noise)
-        tb = time.time()
-        if pinned is not None:
-            feeder.recycle(pinned)  # (denoise_guided returned host trajectories: the upload out of the buffer is long done)
-        tm["denoise_s"] = tb - ta
-        repaired = {}
-        if repair:  # the whole batch, between the loop and the selection
-            rep = guide.repair_rows(trajectories, start_joints, goal_joints, iters=repair, substeps=CHECK_SUBSTEPS, margin=repair_margin, step=repair_step)
-            trajectories = rep["trajectories"]
-            moved, clear = repair_tally(rep, repair, repair_margin)
-            repaired = dict(rows_repaired=int(moved.sum()), rows_repair_clear=int(clear.sum()), repair_iters=int(repair))
-            tm["repair_s"] = time.time() - tb
-            tb = time.time()
-        idx, vols, met = guide.select_row(start_joints, goal_joints, trajectories, prefer=prefer)
-        trajectory = trajectories[idx]
-        t_plan = time.time() - t0
-        tm["best_trajectory_s"] = time.time() - tb
-        if ensemble_report and met is None:
-            te = time.time()
-            met = guide.metrics_rows(trajectories)
-            tm["batch_metrics_s"] = time.time() - te
-        # success: pybullet execution (lib/environment.py:632-680) is unavailable -> exact link-box vs cuboid / cylinder
-        # check along the interpolated trajectory, for EVERY row of the batch in one kernel (csrc/success.hip); the
-        # scene's success is the chosen row's flag (infer_serial.py:165-168) under the reference's rule - no contact;
-        # leaving the joint limits only prints there (lib/environment.py:659-661, 672) -, the stricter flag (also inside the
-        # limits) and the batch rates are reported next to it, as is the guide's own (conservative, AABB) criterion
-        tc = time.time()
-        chk = guide.success_rows(trajectories)
-        tm["success_check_s"] = time.time() - tc
-        return dict(**meta, timings=tm, best_row=int(idx), swept_volume=float(vols[idx]), success_proxy=int(chk["collision_free"][idx]), success_strict=int(chk["ok"][idx]),
-                    rows_collision_free=chk["rows_collision_free"], rows_ok=chk["rows_ok"], rows=chk["rows"],
-                    aabb_volume_zero=bool(ED.geometric_success(float(vols[idx]), trajectory)), first_collision_waypoint=int(chk["first"][idx]),
-                    path_length=EV.path_lengths(trajectory), sparc=EV.smoothness(trajectory), planning_time_s=t_plan, scene_wall_s=time.time() - t0, trajectory=trajectory,
-                    **({"min_clearance": float(guide.sdf_rows(trajectory[None, :, 1:-1], start_joints, goal_joints)["clearance"][0])} if ensemble_report and guide.has_sdf_rows else {}),
-                    **({"min_swept_clearance": float(guide.sdf_sweep_rows(trajectory[None, :, 1:-1], start_joints, goal_joints, substeps=sweep_substeps(guide, idx))["clearance"][0])}
-                       if ensemble_report and guide.has_sdf_rows else {}),
-                    **({"min_self_clearance": float(guide.sdf_self_rows(trajectory[None, :, 1:-1])["clearance"][0])} if ensemble_report and guide.has_self_term else {}),
-                    **(goal_extras(guide.sdf_goal_rows(trajectory[None, :, 1:]), 0) if ensemble_report and guide.has_goal_term else {}),  # (the goal column is the last handed one)
-                    **(self_extras(guide.self_collision_rows(trajectories), idx) if self_collision else {}), **repaired, **extras(vols, chk, met))
-
-    t_success, t_strict, i, results, pending = 0, 0, 0, [], []
-    t_self = 0
-
-    def collect(fut):
-        nonlocal t_success, t_strict, t_self
-        r = fut.result() if hasattr(fut, "result") else fut
-        r["done_at"] = time.time()
-        results.append(r)
-        t_success += r["success_proxy"]  # the reference's tally: collision-free (infer_serial.py:165-168 on lib/environment.py:672)
-        t_strict += r["success_strict"]
-        if verbose:
-            print(("" if world == 1 else f"[rank {rank}] ") + f"Scene {len(results)} ({r['scene_type']}/{r['scene_num']}): planning {r['planning_time_s']:.2f} s, best row {r['best_row']}, swept volume "
-                  f"{r['swept_volume']:.4g}, geometric success (proxy, collision-free) {r['success_proxy']} ({r['rows_collision_free']}/{r['rows']} rows of the batch); "
-                  f"also within the joint limits {r['success_strict']} ({r['rows_ok']}/{r['rows']})   running {t_success}/{len(results)} (strict {t_strict}/{len(results)})")
-            for line in EV.format_ensemble_report(r.get("ensemble", ())):
-                print(line)
-            if "min_clearance" in r:  # (a run with an SDF guide: the sphere model's smallest clearance along the chosen plan)
-                print(f"    chosen plan: minimum sphere clearance {r['min_clearance']:.4f} m")
-            if "min_swept_clearance" in r:  # (the same at the configurations the success check interpolates between the waypoints)
-                print(f"    chosen plan: minimum swept sphere clearance {r['min_swept_clearance']:.4f} m")
-            if "min_self_clearance" in r:  # (the guide carries the self-clearance term: the sphere model's smallest distance to itself)
-                print(f"    chosen plan: minimum self clearance {r['min_self_clearance']:.4f} m")
-            if "position_error" in r:  # (the guide carries the goal term: the final tool pose against the target)
-                print(f"    chosen plan: position_error {r['position_error']:.3f} cm, orientation_error {r['orientation_error']:.3f} deg")
-        if verbose and "rows_repaired" in r:
-            print(f"    repair ({r['repair_iters']} iterations at most): {r['rows_repaired']}/{r['rows']} rows moved, {r['rows_repair_clear']}/{r['rows']} ended clear")
-        if "self_collision_free" in r:
-            t_self += r["self_collision_free"]
-            if verbose:
-                print(f"    self-collision free {r['self_collision_free']} ({r['rows_self_collision_free']}/{r['rows']} rows of the batch)   running {t_self}/{len(results)}")
-                if "ensemble" in r:
-                    print("    chosen plan: " + ("no self-collision" if r["self_collision_pair"] is None else
-                                                 f"self-collision of {r['self_collision_pair'][0]} and {r['self_collision_pair'][1]} at waypoint {r['first_self_collision_waypoint']}"))
-
-    # this rank's scenes, in the cfg's order (scene i of that order belongs to rank i mod world)
-    mine = []
-    for scene_type in benchmark_cfg["dataset"]["scene_types"]:
-        for scene_num in range(dataset.data_nums[scene_type]):
-            if max_scenes is not None and i >= max_scenes:
-                break
-            if i % world == rank:
-                mine.append((i, scene_type, scene_num))
-            i += 1
+        job.iks = [FrankaIK(lane[0].ctx, n_seeds=ik_seeds, seed=ik_seed, tool=ik_tool) for lane in job.lanes]  # one solver per lane (a lane's context is only touched while its previous scene is done)
+    mine = _my_scenes(cfg["dataset"]["scene_types"], dataset, max_scenes, rank, world)
     # the noise of EVERY scene comes from the feeder thread, one whole scene ahead (round 6: the serial loop too - drawing chunk by chunk
     # beside the GPU had no margin left once a reverse step took 0.92 ms: a slower host capped the scene loop, BENCH_r05 0.947 x value)
     # (the device source needs none of it: no thread, no page-locked buffer, no draw from the global state)
-    feeder = _NoiseFeeder(base, len(mine), (T + 1, total_batch_size, num_channels, traj_len), 2 * kl if kl > 1 else k + 1) if mine and device_noise is None else None
-
-    def seed_meta(i):
-        """the key device_noise adds to scene i's result (none without it)"""
-        return {} if device_noise is None else {"noise_seed": scene_seed(device_noise, i)}
-
+    if mine and device_noise is None:
+        job.feeder = _NoiseFeeder(base, len(mine), (job.T + 1, job.total_batch_size, job.num_channels, job.traj_len), 2 * kl if kl > 1 else k + 1)
     run.last_setup_s = time.time() - t_enter  # config, dataset, model load / upload: per run, not per scene
-    def prepare_group(scenes_of_group):
-        """guides + IK filter of a scene group (infer_serial.py:108-129, once per scene there): the guides are host tables only
-        (bind=False), the SceneBatch is the one object on the device, and ONE filter_goals call picks every scene's goal.
-        -> (batch, [(guide, start, goal, meta, t0) per scene]); guide_ctor_s / ik_filter_s are the GROUP's times"""
-        data = fetch(0, scenes_of_group)
-        t0 = time.time()
-        guides = []
-        for (obstacle_config, _, _, num_cuboids, num_cylinders, _, _), gkw in zip(data, goal_kw(scenes_of_group)):
-            kinds = np.concatenate([np.zeros(int(num_cuboids), dtype=np.int32), np.ones(int(num_cylinders), dtype=np.int32)])
-            guides.append(IntersectionVolumeGuide(obstacle_config=obstacle_config, device=lanes[0][0].ctx, guide_cfgs=guide_cfgs, batch_size=total_batch_size,
-                                                  obstacle_kinds=kinds, mesh_dir=benchmark_cfg["model"].get("mesh_dir"), bind=False, **gkw))
-        batch = SceneBatch(guides)
-        t1 = time.time()
-        starts = np.stack([np.asarray(d[5], dtype=np.float64) for d in data])
-        _, chosen, _ = batch.filter_goals(starts, [d[6] for d in data])
-        t2 = time.time()
-        what = f"group of {len(data)} scenes"
-        group = []
-        for (i_scene, scene_type, scene_num), guide, d, goal_joints in zip(scenes_of_group, guides, data, chosen):
-            meta = dict(scene_type=scene_type, scene_num=scene_num, **seed_meta(i_scene),
-                        timings=dict(guide_ctor_s=t1 - t0, guide_ctor_s_is=what, ik_filter_s=t2 - t1, ik_filter_s_is=what))
-            group.append((guide, d[5], goal_joints, meta, t0))
-        return batch, group
-
-    def plan_group(batch, group):
-        """k prepared scenes in one launch chain; per scene: best row, success, the serial loop's result keys"""
-        diffuser, denoiser = lanes[0]
-        t_w = time.time()
-        streams = [feeder.next() for _ in group] if feeder is not None else DeviceNoise(seeds=[g[3]["noise_seed"] for g in group])
-        noise_wait = time.time() - t_w
-        starts, goals = np.stack([g[1] for g in group]), np.stack([g[2] for g in group])
-        ta = time.time()
-        Xd = diffuser.denoise_guided_scenes(denoiser, batch, traj_len, num_channels, starts, goals, noise=streams, condition=True, return_device=True)
-        tb = time.time()
-        for st in streams if feeder is not None else ():
-            feeder.recycle(st)  # (the call synchronised before it returned the device state: every upload out of the buffers is done)
-        t_rep, moved, clear = None, None, None
-        if repair:  # the whole group in one launch, between the loop and the selection; the repaired state stays on the device
-            rep = batch.repair_rows(Xd, starts, goals, iters=repair, substeps=CHECK_SUBSTEPS, margin=repair_margin, step=repair_step, return_device=True)
-            Xd = rep["trajectories"]
-            moved, clear = repair_tally(rep, repair, repair_margin)
-            t_rep = time.time() - tb
-            tb = time.time()
-        # the finished (S, B, C, N) state stays on the device and is scored as ONE batch: per-scene volumes + pick, per-scene success
-        # flags + counts, and the metrics of all S * B rows (they need no scene) - three calls for the group, not four per scene
-        idxs, all_vols, all_met = batch.select_rows(starts, goals, Xd, prefer=prefer)
-        tc = time.time()
-        t_met = None
-        if ensemble_report and all_met is None:
-            all_met = {k: v.reshape(len(group), total_batch_size) for k, v in EV.batch_metrics(Xd.reshape((-1,) + tuple(Xd.shape[-2:])), device=diffuser.ctx).items()}
-            t_met = time.time() - tc
-        td = time.time()
-        all_chk = batch.success_rows(Xd)
-        te = time.time()
-        # (a run with an SDF guide: the sphere model's clearance of every row of the group in one call, the chosen rows' are reported)
-        all_clr = batch.sdf_rows(Xd, starts, goals)["clearance"] if ensemble_report and batch.has_sdf_rows else None
-        # (and at the success check's interpolants: the rows' own substeps when the batch carries the swept-clearance term - 4, the check's, on its other rows)
-        all_swp = batch.sdf_sweep_rows(Xd, starts, goals, substeps=None if batch.has_sweep_term else CHECK_SUBSTEPS)["clearance"] if ensemble_report and batch.has_sdf_rows else None
-        all_sclr = batch.sdf_self_rows(Xd)["clearance"] if ensemble_report and batch.has_self_term else None
-        all_goal = batch.sdf_goal_rows(Xd, final=True) if ensemble_report and batch.has_goal_term else None
-        all_self = batch.self_collision_rows(Xd) if self_collision else None  # (the whole group in one call)
-        X = diffuser.ctx.to_host(Xd)  # once, for the result dicts
-        out = []
-        for s, (guide, start_joints, goal_joints, meta, t0) in enumerate(group):
-            tm = dict(meta.pop("timings"))
-            tm["noise_wait_s"] = noise_wait
-            trajectories, idx, vols = X[s], int(idxs[s]), all_vols[s]
-            met = None if all_met is None else {k: v[s] for k, v in all_met.items()}
-            chk = {k: (v[s] if k in ("ok", "first", "within", "collision_free") else int(v[s])) for k, v in all_chk.items()}
-            if t_met is not None:
-                tm["batch_metrics_s"] = t_met  # the whole group's call
-            trajectory = trajectories[idx]
-            tm["denoise_s"] = tb - ta - (t_rep or 0.0)  # the whole group's loop
-            if t_rep is not None:
-                tm["repair_s"] = t_rep  # the whole group's call
-            tm["denoise_s_is"] = f"group of {len(group)} scenes"
-            tm["best_trajectory_s"], tm["success_check_s"] = tc - tb, te - td  # the whole group's calls
-            t_plan = time.time() - t0
-            out.append(dict(**meta, timings=tm, scenes_in_launch=len(group), best_row=int(idx), swept_volume=float(vols[idx]),
-                            success_proxy=int(chk["collision_free"][idx]), success_strict=int(chk["ok"][idx]), rows_collision_free=chk["rows_collision_free"],
-                            rows_ok=chk["rows_ok"], rows=chk["rows"], aabb_volume_zero=bool(ED.geometric_success(float(vols[idx]), trajectory)),
-                            first_collision_waypoint=int(chk["first"][idx]), path_length=EV.path_lengths(trajectory), sparc=EV.smoothness(trajectory),
-                            planning_time_s=t_plan, scene_wall_s=time.time() - t0, trajectory=trajectory,
-                            **({"min_clearance": float(all_clr[s][idx])} if all_clr is not None else {}),
-                            **({"min_swept_clearance": float(all_swp[s][idx])} if all_swp is not None else {}),
-                            **({"min_self_clearance": float(all_sclr[s][idx])} if all_sclr is not None else {}),
-                            **(goal_extras({k: v[s] for k, v in all_goal.items()}, idx) if all_goal is not None else {}),
-                            **(self_extras({k: v[s] for k, v in all_self.items()}, idx) if all_self is not None else {}),
-                            **(dict(rows_repaired=int(moved[s].sum()), rows_repair_clear=int(clear[s].sum()), repair_iters=int(repair)) if moved is not None else {}),
-                            **extras(vols, chk, met)))
-        return out
-
     try:
         if kl > 1:
             for g0 in range(0, len(mine), kl):
-                for r in plan_group(*prepare_group(mine[g0:g0 + kl])):
-                    collect(r)
-            mine = []  # (planned above)
-        with ThreadPoolExecutor(max_workers=k) as pool:
-            for i, scene_type, scene_num in mine:
-                lane = (i // world) % k
-                while len(pending) >= k:  # the lane's previous scene (and every earlier one) is done before its context is reused
-                    collect(pending.pop(0))
-                obstacle_config, _, _, num_cuboids, num_cylinders, start_joints, all_ik_goals = fetch(lane, [(i, scene_type, scene_num)])[0]
-                t0 = time.time()
-                # obstacle_config = cuboids first, then cylinders as (r, r, h) boxes (datasets/load_test_dataset.py:141-149); the
-                # success check spawns the latter as true cylinders (infer_serial.py:159-163 -> lib/environment.py:249-268)
-                kinds = np.concatenate([np.zeros(int(num_cuboids), dtype=np.int32), np.ones(int(num_cylinders), dtype=np.int32)])
-                guide = IntersectionVolumeGuide(obstacle_config=obstacle_config, device=lanes[lane][0].ctx, guide_cfgs=guide_cfgs, batch_size=total_batch_size,
-                                                obstacle_kinds=kinds, mesh_dir=benchmark_cfg["model"].get("mesh_dir"), **goal_kw([(i, scene_type, scene_num)])[0])
-                t1 = time.time()
-                # IK-goal filter                                                              infer_serial.py:117-129
-                volumes = guide.cost(torch.tensor(all_ik_goals.reshape((-1, 7, 1))), 0, batch_size=all_ik_goals.shape[0]).sum(axis=(1, 2)).cpu().numpy()
-                _, goal_joints = pick_goal(volumes, all_ik_goals, start_joints)
-                t2 = time.time()
-                # the feeder thread draws every scene's whole stream in scene order from the global RandomState, so every scene sees the
-                # numbers the reference's loop would give it (nothing else may draw from the global state while a run is in progress).
-                # (pool.submit hands the scenes to the lanes in order, the feeder hands the streams out in the same order)
-                # where a scene's "Planning Time" (infer_serial.py:108-157: guide construction + IK filter + sampling + best pick) goes
-                meta = dict(scene_type=scene_type, scene_num=scene_num, **seed_meta(i), timings=dict(guide_ctor_s=t1 - t0, ik_filter_s=t2 - t1))
-                noise = feeder.next() if feeder is not None else DeviceNoise(meta["noise_seed"])
-                if k == 1:
-                    collect(plan(lane, guide, start_joints, goal_joints, noise, meta, t0))  # serial: the reference's order of events
-                else:
-                    pending.append(pool.submit(plan, lane, guide, start_joints, goal_joints, noise, meta, t0))
-            while pending:
-                collect(pending.pop(0))
+                for r in _plan_group(job, *_prepare_group(job, mine[g0:g0 + kl])):
+                    _collect(job, r)
+        else:
+            _serial_loop(job, mine, k)
     finally:
-        if feeder is not None:
-            feeder.close()
+        if job.feeder is not None:
+            job.feeder.close()
     if world > 1 or verbose:
-        summary = job_summary(results, world, self_collision, bool(repair))
+        run.last_summary = job_summary(job.results, world, self_collision, bool(repair))
         if verbose and rank == 0:
-            print(f"[infer_serial] {summary['scenes']} scenes on {summary['ranks']} rank(s): success (proxy, collision-free) {summary['success_proxy']}/{summary['scenes']}, "
-                  f"strict {summary['success_strict']}/{summary['scenes']}, rows collision-free {summary['rows_collision_free']}/{summary['rows']}")
-            if "self_collision_free" in summary:
-                print(f"[infer_serial] self-collision free {summary['self_collision_free']}/{summary['scenes']}, rows {summary['rows_self_collision_free']}/{summary['rows']}")
-            if "rows_repaired" in summary:
-                print(f"[infer_serial] repair: {summary['rows_repaired']}/{summary['rows']} rows moved, {summary['rows_repair_clear']}/{summary['rows']} ended clear")
-        run.last_summary = summary
-    return results
+            _print_summary(run.last_summary)
+    return job.results
 
 
 def main(argv=None):
@@ -610,8 +642,6 @@ def main(argv=None):
         if ik_tool.endswith(".npy"):
             ik_tool = np.load(ik_tool)
         else:
-            import json
-
             with open(ik_tool) as f:
                 ik_tool = np.asarray(json.load(f), dtype=np.float64)
     rank = int(os.environ.get("RANK", "0"))
@@ -621,8 +651,6 @@ def main(argv=None):
                   ensemble_report=args.ensemble_report, prefer=args.prefer, ik_seeds=args.ik_seeds, ik_tool=ik_tool, self_collision=args.self_collision,
                   device_noise=args.device_noise, repair=args.repair, repair_margin=args.repair_margin, repair_step=args.repair_step)
     if args.results_json:
-        import json
-
         rows = [{k: v for k, v in r.items() if k != "trajectory"} for r in results]
         with open(args.results_json + ("" if rank == 0 else f".rank{rank}"), "w") as f:
             json.dump({"rank": rank, "summary": getattr(run, "last_summary", None), "scenes": rows}, f, default=lambda o: o.tolist() if hasattr(o, "tolist") else str(o))
