@@ -780,6 +780,23 @@ static int check_run_state(edmp_ctx* ctx, int B, bool guided, int S) {
     return EDMP_OK;
 }
 
+// The start of a run of B rows over S scenes, whether it begins at T (denoise_loop's init) or below (sampler_seed): no run in progress,
+// scratch for n elements, the device source's seeds (null: an explicit stream), the start / goal pairs, and the run's own record.
+static int begin_run(edmp_ctx* ctx, size_t n, const uint64_t* seeds, int S, int B, const double* start, const double* goal, int guided) {
+    Sampler* s = ctx->sampler;
+    s->run_next = 0;
+    int rc = ensure_sampler_scratch(ctx, (int)n);
+    if (rc) return rc;
+    if (seeds && (rc = set_seeds(ctx, seeds, S))) return rc;
+    rc = S > 1 ? set_startgoal_scenes(ctx, S, start, goal, guided != 0) : set_startgoal(ctx, start, goal, guided != 0);
+    if (rc) return rc;
+    s->run_B = B;
+    s->run_rps = S > 1 ? B / S : 0;
+    s->run_guided = guided != 0;
+    s->run_rng = seeds ? 1 : 0;
+    return EDMP_OK;
+}
+
 // S > 1: a scene batch of S scenes x B / S rows; start / goal then hold S rows of 7 each
 // segment: one of the *_segment_dev entry points.  Only they leave a run in progress (Sampler::run_next): a segment that returns with
 // t_lo > 0 records the step the kept state stands at and the context's epoch, and a continuing segment (init == 0) must bring
@@ -804,16 +821,8 @@ static int denoise_loop(edmp_ctx* ctx, const double* noise_dev, bool use_rng, co
     hipStream_t st = ctx->stream;
     if (init) {
         EDMP_REQUIRE(start && goal, "null start/goal");
-        s->run_next = 0;
-        rc = ensure_sampler_scratch(ctx, (int)n);
+        rc = begin_run(ctx, n, use_rng ? seeds : nullptr, S, B, start, goal, guided);
         if (rc) return rc;
-        if (use_rng && (rc = set_seeds(ctx, seeds, S))) return rc;
-        rc = S > 1 ? set_startgoal_scenes(ctx, S, start, goal, guided != 0) : set_startgoal(ctx, start, goal, guided != 0);
-        if (rc) return rc;
-        s->run_B = B;
-        s->run_rps = rps;
-        s->run_guided = guided != 0;
-        s->run_rng = use_rng ? 1 : 0;
     } else {
         if (!(s->X && s->run_next > 0 && s->run_B == B && s->run_rps == rps)) {
             set_error("no run in progress for batch %d / %d scene(s): call with init first (a complete run, a run that reached step 0, new start / goal "
@@ -844,42 +853,40 @@ static int denoise_loop(edmp_ctx* ctx, const double* noise_dev, bool use_rng, co
     // a caller-supplied collective is not capturable; segments of a chunked run carry a fresh noise pointer each, so a
     // captured graph would never be replayed (capture + instantiate + destroy per chunk): they are enqueued directly
     const bool graph = !segment && s->graph_on == 1 && !ctx->prof.on && (!s->ar_fn || sampler_hook_is_native(s));
-    Sampler::GraphKey key;
-    if (graph) {
+    if (!graph) {
+        rc = enqueue_loop(ctx, noise_dev, use_rng, B, guided, t_hi, t_lo, init, zero_row0, X_out_dev, rps);
+    } else {
         if (guided) {
             rc = guide_prepare(ctx, B, N - 2);
             if (rc) return rc;
         }
+        Sampler::GraphKey key;
         key.noise = noise_dev, key.hook = s->ar_fn ? s->ar_user : nullptr, key.seed = (use_rng && S == 1) ? seeds[0] : 0, key.use_rng = use_rng, key.B = B, key.guided = guided, key.t_hi = t_hi, key.t_lo = t_lo;
         key.init = init, key.zero_row0 = zero_row0, key.condition = s->condition, key.rps = rps, key.epoch = ctx->epoch;
         if (s->gexec && key == s->gkey) {
             s->graph_replays++;
-            EDMP_HIP_CHECK(hipGraphLaunch(s->gexec, st));
-            if (X_out_dev) EDMP_HIP_CHECK(hipMemcpyAsync(X_out_dev, s->X, n * sizeof(double), hipMemcpyDeviceToDevice, st));
-            return EDMP_OK;
+        } else {  // capture this call's enqueue in the place of the graph held
+            if (s->gexec) {
+                (void)hipGraphExecDestroy(s->gexec);
+                s->gexec = nullptr;
+            }
+            EDMP_HIP_CHECK(hipStreamBeginCapture(st, hipStreamCaptureModeThreadLocal));
+            rc = enqueue_loop(ctx, noise_dev, use_rng, B, guided, t_hi, t_lo, init, zero_row0, nullptr, rps);
+            hipGraph_t g = nullptr;
+            hipError_t e = hipStreamEndCapture(st, &g);
+            if (rc) {
+                if (g) (void)hipGraphDestroy(g);
+                return rc;
+            }
+            EDMP_HIP_CHECK(e);
+            e = hipGraphInstantiate(&s->gexec, g, nullptr, nullptr, 0);
+            (void)hipGraphDestroy(g);
+            EDMP_HIP_CHECK(e);
+            s->gkey = key;
+            s->graph_captures++;
         }
-        if (s->gexec) {
-            (void)hipGraphExecDestroy(s->gexec);
-            s->gexec = nullptr;
-        }
-        EDMP_HIP_CHECK(hipStreamBeginCapture(st, hipStreamCaptureModeThreadLocal));
-    }
-    // the copy-out stays outside the graph: callers hand a fresh output buffer to every call.  (The device source's seeds are no part of
-    // the capture either: the kernels read them from Sampler::seeds, which this call's init has uploaded ahead of the launch.)
-    rc = enqueue_loop(ctx, noise_dev, use_rng, B, guided, t_hi, t_lo, init, zero_row0, graph ? nullptr : X_out_dev, rps);
-    if (graph) {
-        hipGraph_t g = nullptr;
-        hipError_t e = hipStreamEndCapture(st, &g);
-        if (rc) {
-            if (g) (void)hipGraphDestroy(g);
-            return rc;
-        }
-        EDMP_HIP_CHECK(e);
-        e = hipGraphInstantiate(&s->gexec, g, nullptr, nullptr, 0);
-        (void)hipGraphDestroy(g);
-        EDMP_HIP_CHECK(e);
-        s->gkey = key;
-        s->graph_captures++;
+        // the copy-out stays outside the graph: callers hand a fresh output buffer to every call.  (The device source's seeds are no part of
+        // the capture either: the kernels read them from Sampler::seeds, which this call's init has uploaded ahead of the launch.)
         EDMP_HIP_CHECK(hipGraphLaunch(s->gexec, st));
         if (X_out_dev) EDMP_HIP_CHECK(hipMemcpyAsync(X_out_dev, s->X, n * sizeof(double), hipMemcpyDeviceToDevice, st));
     }
@@ -920,8 +927,9 @@ extern "C" int edmp_denoise_guided_segment_dev(edmp_ctx* ctx, const double* nois
     return denoise_loop(ctx, noise_dev, false, nullptr, B, start, goal, guided, t_hi, t_lo, init != 0, zero_row0, X_out_dev, true);
 }
 
-// a scene batch: S scenes x B rows as one (S*B, C, N) run; starts / goals may be NULL only when neither conditioning nor guided
-static int scenes_args(edmp_ctx* ctx, int S, int B, const double*& starts, const double*& goals, int guided, const double* zeros) {
+// a scene batch: S scenes x B rows as one (S*B, C, N) run; starts / goals may be NULL only when neither conditioning nor guided (zeros stand in)
+static const double zeros[EDMP_MAX_SCENES * 7] = {};
+static int scenes_args(edmp_ctx* ctx, int S, int B, const double*& starts, const double*& goals, int guided) {
     EDMP_REQUIRE(ctx && ctx->sampler, "sampler not initialised");
     EDMP_REQUIRE(S >= 1 && S <= EDMP_MAX_SCENES, "scene batch: %d scenes outside 1..%d", S, EDMP_MAX_SCENES);
     EDMP_REQUIRE(B >= 1 && (!ctx->unet || (int64_t)S * B <= ctx->unet->max_batch), "scene batch: %d scenes x %d rows outside 1..%d rows (the model's max_batch)", S, B,
@@ -937,16 +945,14 @@ static int scenes_args(edmp_ctx* ctx, int S, int B, const double*& starts, const
 extern "C" int edmp_denoise_scenes_dev(edmp_ctx* ctx, const double* noise_dev, int S, int B, const double* starts, const double* goals, int guided,
                                        int t_stop, int zero_row0, double* X_out_dev) {
     EDMP_REQUIRE(noise_dev && X_out_dev, "edmp_denoise_scenes_dev: null pointer");
-    static const double zeros[EDMP_MAX_SCENES * 7] = {};
-    if (int rc = scenes_args(ctx, S, B, starts, goals, guided, zeros)) return rc;
+    if (int rc = scenes_args(ctx, S, B, starts, goals, guided)) return rc;
     return denoise_loop(ctx, noise_dev, false, nullptr, S * B, starts, goals, guided, ctx->sampler->T, t_stop, true, zero_row0, X_out_dev, false, S);
 }
 
 extern "C" int edmp_denoise_scenes_rng_dev(edmp_ctx* ctx, const uint64_t* seeds, int S, int B, const double* starts, const double* goals, int guided,
                                            int t_stop, int zero_row0, double* X_out_dev) {
     EDMP_REQUIRE(seeds && X_out_dev, "edmp_denoise_scenes_rng_dev: null pointer");
-    static const double zeros[EDMP_MAX_SCENES * 7] = {};
-    if (int rc = scenes_args(ctx, S, B, starts, goals, guided, zeros)) return rc;
+    if (int rc = scenes_args(ctx, S, B, starts, goals, guided)) return rc;
     EDMP_NO_HOOK_WITH_RNG("edmp_denoise_scenes_rng_dev");
     return denoise_loop(ctx, nullptr, true, seeds, S * B, starts, goals, guided, ctx->sampler->T, t_stop, true, zero_row0, X_out_dev, false, S);
 }
@@ -954,8 +960,7 @@ extern "C" int edmp_denoise_scenes_rng_dev(edmp_ctx* ctx, const uint64_t* seeds,
 extern "C" int edmp_denoise_scenes_rng_segment_dev(edmp_ctx* ctx, const uint64_t* seeds, int S, int B, const double* starts, const double* goals, int guided,
                                                    int t_hi, int t_lo, int init, int zero_row0, double* X_out_dev) {
     EDMP_REQUIRE(seeds || !init, "edmp_denoise_scenes_rng_segment_dev: null seeds");
-    static const double zeros[EDMP_MAX_SCENES * 7] = {};
-    if (int rc = scenes_args(ctx, S, B, starts, goals, guided, zeros)) return rc;
+    if (int rc = scenes_args(ctx, S, B, starts, goals, guided)) return rc;
     EDMP_NO_HOOK_WITH_RNG("edmp_denoise_scenes_rng_segment_dev");
     return denoise_loop(ctx, nullptr, true, seeds, S * B, starts, goals, guided, t_hi, t_lo, init != 0, zero_row0, X_out_dev, true, S);
 }
@@ -963,8 +968,7 @@ extern "C" int edmp_denoise_scenes_rng_segment_dev(edmp_ctx* ctx, const uint64_t
 extern "C" int edmp_denoise_scenes_segment_dev(edmp_ctx* ctx, const double* noise_dev, int S, int B, const double* starts, const double* goals, int guided,
                                                int t_hi, int t_lo, int init, int zero_row0, double* X_out_dev) {
     EDMP_REQUIRE(noise_dev, "edmp_denoise_scenes_segment_dev: null noise pointer");
-    static const double zeros[EDMP_MAX_SCENES * 7] = {};
-    if (int rc = scenes_args(ctx, S, B, starts, goals, guided, zeros)) return rc;
+    if (int rc = scenes_args(ctx, S, B, starts, goals, guided)) return rc;
     return denoise_loop(ctx, noise_dev, false, nullptr, S * B, starts, goals, guided, t_hi, t_lo, init != 0, zero_row0, X_out_dev, true, S);
 }
 
@@ -984,26 +988,14 @@ static int sampler_seed(edmp_ctx* ctx, const double* x0_dev, int x0_rows, const 
     EDMP_HIP_CHECK(hipSetDevice(ctx->device));
     const int C = ctx->unet->desc.input_dim, N = ctx->unet->desc.horizon;
     const size_t n = (size_t)B * C * N;
-    const int rps = S > 1 ? B / S : 0;
-    s->run_next = 0;
-    rc = ensure_sampler_scratch(ctx, (int)n);
-    if (rc) return rc;
-    if (seeds && (rc = set_seeds(ctx, seeds, S))) return rc;
-    rc = S > 1 ? set_startgoal_scenes(ctx, S, start, goal, guided != 0) : set_startgoal(ctx, start, goal, guided != 0);
+    rc = begin_run(ctx, n, seeds, S, B, start, goal, guided);
     if (rc) return rc;
     const double ab = s->alpha_bar[t_start - 1];
-    if (seeds && renoise)
-        hipLaunchKernelGGL(seed_state_kernel<true>, dim3((B * N + 255) / 256), dim3(256), 0, ctx->stream, x0_dev, x0_rows == B ? 1 : 0, (const double*)nullptr, s->seeds,
-                           sqrt(ab), sqrt(1.0 - ab), s->X, ctx->unet->x_in, s->sg, B, C, N, s->condition, rps);
-    else
-        hipLaunchKernelGGL(seed_state_kernel<false>, dim3((B * N + 255) / 256), dim3(256), 0, ctx->stream, x0_dev, x0_rows == B ? 1 : 0, eps_dev, s->seeds,
-                           sqrt(ab), sqrt(1.0 - ab), s->X, ctx->unet->x_in, s->sg, B, C, N, s->condition, rps);
+    const bool rng = seeds && renoise;  // the eps of the re-noising is the device source's step-0 draw: eps_dev is not read
+    hipLaunchKernelGGL(rng ? seed_state_kernel<true> : seed_state_kernel<false>, dim3((B * N + 255) / 256), dim3(256), 0, ctx->stream, x0_dev, x0_rows == B ? 1 : 0,
+                       rng ? (const double*)nullptr : eps_dev, s->seeds, sqrt(ab), sqrt(1.0 - ab), s->X, ctx->unet->x_in, s->sg, B, C, N, s->condition, s->run_rps);
     EDMP_HIP_CHECK(hipGetLastError());
     if (X_out_dev) EDMP_HIP_CHECK(hipMemcpyAsync(X_out_dev, s->X, n * sizeof(double), hipMemcpyDeviceToDevice, ctx->stream));
-    s->run_B = B;
-    s->run_rps = rps;
-    s->run_guided = guided != 0;
-    s->run_rng = seeds ? 1 : 0;
     s->run_next = t_start;
     s->run_epoch = ctx->epoch;
     return EDMP_OK;
@@ -1017,8 +1009,7 @@ extern "C" int edmp_sampler_seed_dev(edmp_ctx* ctx, const double* x0_dev, int x0
 
 extern "C" int edmp_sampler_seed_scenes_dev(edmp_ctx* ctx, const double* x0_dev, int x0_rows, const double* eps_dev, int S, int B, const double* starts,
                                             const double* goals, int guided, int t_start, double* X_out_dev) {
-    static const double zeros[EDMP_MAX_SCENES * 7] = {};
-    if (int rc = scenes_args(ctx, S, B, starts, goals, guided, zeros)) return rc;
+    if (int rc = scenes_args(ctx, S, B, starts, goals, guided)) return rc;
     return sampler_seed(ctx, x0_dev, x0_rows, eps_dev, S * B, starts, goals, guided, t_start, X_out_dev, S);
 }
 
@@ -1032,8 +1023,7 @@ extern "C" int edmp_sampler_seed_rng_dev(edmp_ctx* ctx, const double* x0_dev, in
 extern "C" int edmp_sampler_seed_scenes_rng_dev(edmp_ctx* ctx, const double* x0_dev, int x0_rows, const uint64_t* seeds, int renoise, int S, int B,
                                                 const double* starts, const double* goals, int guided, int t_start, double* X_out_dev) {
     EDMP_REQUIRE(seeds, "edmp_sampler_seed_scenes_rng_dev: null seeds");
-    static const double zeros[EDMP_MAX_SCENES * 7] = {};
-    if (int rc = scenes_args(ctx, S, B, starts, goals, guided, zeros)) return rc;
+    if (int rc = scenes_args(ctx, S, B, starts, goals, guided)) return rc;
     EDMP_NO_HOOK_WITH_RNG("edmp_sampler_seed_scenes_rng_dev");
     return sampler_seed(ctx, x0_dev, x0_rows, nullptr, S * B, starts, goals, guided, t_start, X_out_dev, S, seeds, renoise != 0);
 }

@@ -210,6 +210,18 @@ class PinnedNoiseStream:
                 raise self.error
 
 
+class _Form(NamedTuple):
+    """what a single-scene run and a scene batch differ in once their arguments are checked (Diffusion._run).  The entry points are
+    edmp_denoise_<kind>[_rng][_segment]_dev and edmp_sampler_seed[_scenes][_rng]_dev: _rng with `seeds`, _segment for a part of the loop."""
+
+    kind: str        # "guided" | "scenes"
+    lead: tuple      # the leading arguments of every call and the run's shape in front of (C, N): (B,) or (S, B)
+    seeds: object    # the device source's seed (one scene) or (S) seeds as those entry points take them; None: the run reads noise streams
+    place: object    # a scene batch: place(chunk (draws, S*B, C, N), S pieces (draws, B, C, N)) assembles a chunk of noise; None: one stream, its own chunk
+    settle: bool     # a scene batch synchronises with the host where one scene does not: before a device result of any direct run is handed over,
+                     # after a warm device-source run (its x0 upload may die), and before an error of a resident-stream run propagates
+
+
 class Diffusion:
     """Same constructor / method signatures as the reference ``Diffusion(T, device, variance_thresh=0.02)``."""
 
@@ -293,7 +305,9 @@ class Diffusion:
         return np.clip(joints, lo[np.newaxis, :, np.newaxis], hi[np.newaxis, :, np.newaxis])
 
     # ---- the loop ----------------------------------------------------------------------------------------------
-    def _prepare(self, model, guide, batch_size, guidance_schedule):
+    def _prepare(self, model, guide, batch_size, guidance_schedule, condition=None):
+        """bind the model and the guide object - a guide with its rows for `batch_size`, or a SceneBatch, whose rows are its own
+        (batch_size None) - and set the conditioning switch (`condition` None: left as it is)"""
         ctx = self.ctx
         if model.ctx is not ctx or (guide is not None and guide.ctx is not ctx):
             raise _capi.EdmpError("model, guide and diffuser must live on the same GPU")
@@ -301,9 +315,12 @@ class Diffusion:
         model._bind()
         if guide is not None:
             guide._bind()
-            if guide.batch_size != batch_size:
-                raise ValueError(f"guide was built for batch {guide.batch_size}, denoise_guided called with {batch_size}")
-            guide._set_rows(guidance_schedule if guidance_schedule is not None else guide._sched)
+            if batch_size is not None:
+                if guide.batch_size != batch_size:
+                    raise ValueError(f"guide was built for batch {guide.batch_size}, denoise_guided called with {batch_size}")
+                guide._set_rows(guidance_schedule if guidance_schedule is not None else guide._sched)
+        if condition is not None:
+            _capi.check(ctx.lib.edmp_sampler_set_condition(ctx.h, 1 if condition else 0))
 
     def _check_run(self, model, traj_len, num_channels, t_stop):
         if int(traj_len) != model.horizon or int(num_channels) != model.input_dim:
@@ -490,6 +507,87 @@ class Diffusion:
 
         return self._run_segments(plan, source, segment if trace is None else traced, out, return_device, drain)
 
+    def _run(self, form, noise, streams, draws, pairs, guided, cn, ws, x0_rows, t_stop, zero_row0, chunk_steps, return_device):
+        """The device-resident run behind denoise_guided and denoise_guided_scenes, on a bound model and guide (_prepare) and checked
+        arguments.  `form`: what the two differ in (_Form).  `noise`: None - the global NumPy stream, drawn chunk by chunk beside the loop -
+        or one stream of (draws, B, C, N) f64 per scene (a single-scene run: one), all pinned host tensors - `streams`: the
+        PinnedNoiseStream still filling each, or None - or all host arrays / device tensors; not read when the form brings seeds.
+        `pairs`: the start / goal arrays as the form's entry points take them.  Returns (rows, C, N) as _finish gives it."""
+        ctx, T, t_stop = self.ctx, self.T, int(t_stop)
+        rows, per = int(np.prod(form.lead)), (draws, form.lead[-1]) + cn
+        per_step = rows * cn[0] * cn[1]
+        rng = "" if form.seeds is None else "_rng"
+        out = ctx.empty((rows,) + cn, torch.float64)
+        sp, gp, zr = _capi.as_pd(pairs[0]), _capi.as_pd(pairs[1]), 1 if zero_row0 else 0
+        if ws is not None:
+            x0d = ctx.to_dev(ws.x0, torch.float64)
+
+        def seed(*source):  # (eps,) or (seeds, renoise)
+            name = f"edmp_sampler_seed{'_scenes' if form.kind == 'scenes' else ''}{rng}_dev"
+            _capi.check(getattr(ctx.lib, name)(ctx.h, ptr(x0d), x0_rows, *source, *form.lead, sp, gp, guided, ws.t_start, None), name)
+
+        def denoise(z, steps, X_out):  # steps: (t_stop,) - the whole run - or (t_hi, t_lo, init) - a segment
+            name = f"edmp_denoise_{form.kind}{rng}{'_segment' if len(steps) > 1 else ''}_dev"
+            _capi.check(getattr(ctx.lib, name)(ctx.h, z, *form.lead, sp, gp, guided, *steps, zr, ptr(X_out) if X_out is not None else None), name)
+
+        def segment(zd, seg, X_out):
+            init, z = 1 if seg.init else 0, ptr(zd)
+            if ws is not None:  # the seed call is the run's init; every segment continues it
+                eps, z = self._after_lead(zd, seg, ws, per_step)
+                if init:
+                    seed(eps)
+                init = 0
+            denoise(z, (seg.t_hi, seg.t_lo, init), X_out)
+
+        def plan():
+            return chunk_plan(T, t_stop, chunk_steps) if ws is None else warm_plan(ws.t_start, t_stop, ws.lead, chunk_steps)
+
+        def gather(n, pieces):
+            """the run's (n, rows, C, N) draws out of its streams' pieces: one scene's are its own, a scene batch's are placed scene by scene"""
+            if form.place is None:
+                return pieces[0]
+            with torch.cuda.stream(ctx.stream):
+                return form.place(ctx.empty((n, rows) + cn, torch.float64), [p.view((n,) + per[1:]) for p in pieces])
+
+        def fits(k, x):
+            if tuple(x.shape) != per or x.dtype != torch.float64:
+                raise _noise_error("noise" if len(noise) == 1 else f"noise[{k}]", per, x)
+
+        settled = form.settle or ws is not None  # a device result of a direct run is handed over after a host synchronisation
+        if form.seeds is not None:  # the device source in every run form: no chunk plan, no pinned ring, no draw thread
+            if ws is None:
+                denoise(form.seeds, (t_stop,), out)
+            else:  # a warm run: the seed call (eps = the stream's step-0 draw when re-noising) plus one segment
+                try:
+                    seed(form.seeds, 1 if ws.renoise else 0)
+                    denoise(form.seeds, (ws.t_start, t_stop, 0), out)
+                finally:
+                    if form.settle:
+                        ctx.sync()
+            return self._finish(out, return_device, sync=settled)
+        if noise is None:
+            return self._run_numpy_stream(plan(), per_step, chunk_steps, segment, out, return_device)
+        if _is_pinned_f64(noise[0]):  # uploaded in the same chunks as the on-the-fly stream, each scene's piece by DMA
+            for k, x in enumerate(noise):
+                fits(k, x)
+            parts = [self._pinned_chunks(x, st, per_step // len(noise)) for x, st in zip(noise, streams)]
+            return self._run_segments(plan(), lambda seg: gather(seg.draws, [part(seg) for part in parts]), segment, out, return_device)
+        try:
+            pieces = [ctx.adopt(x) if (isinstance(x, torch.Tensor) and x.is_cuda) else ctx.to_dev(x, torch.float64) for x in noise]
+            for k, x in enumerate(pieces):
+                fits(k, x)
+            nd = gather(draws, pieces)
+            if ws is None and draws == T + 1:
+                denoise(ptr(nd), (t_stop,), out)
+            else:  # resident streams that hold a part of the loop's draws - a warm run's, or X_T and the steps down to t_stop -: one segment
+                segment(nd, Segment(T if ws is None else ws.t_start, t_stop, True, draws, 0), out)
+        except BaseException:
+            if form.settle:
+                with contextlib.suppress(Exception):
+                    ctx.sync()
+            raise
+        return self._finish(out, return_device, sync=settled)
+
     def denoise_guided(self, model, guide, traj_len, num_channels, guidance_schedule, batch_size=1, start=None, goal=None,
                        condition=True, benchmarking=False, *, noise=None, seed=0, t_stop=0, zero_row0=True, return_device=False,
                        chunk_steps=DEFAULT_CHUNK_STEPS, allreduce=None, warm_start=None):
@@ -503,80 +601,30 @@ class Diffusion:
         t_start (or from x0 itself); ``noise`` is then (lead + t_start - t_stop, B, C, N), the eps draw first when re-noising (lead = 1),
         from the same sources.
         Returns (B,C,N) f64 ndarray (a fresh copy)."""
-        ctx = self.ctx
-        ws = warm_start
-        dev_seed = noise._for_run(None, allreduce) if isinstance(noise, DeviceNoise) else None
+        ws, cn = warm_start, (int(num_channels), int(traj_len))
+        seeds = noise._for_run(None, allreduce) if isinstance(noise, DeviceNoise) else None
+        draws, x0_rows = self.T + 1, None
         if ws is not None:
-            cn = (int(num_channels), int(traj_len))
             x0_rows = self._check_warm(ws, t_stop, noise, allreduce, {cn: 1, (int(batch_size),) + cn: int(batch_size)})
-            want = (ws.lead + ws.t_start - int(t_stop), int(batch_size)) + cn
-            if hasattr(noise, "shape") and tuple(noise.shape) != want:
-                raise _noise_error("noise", want, noise)
-        self._prepare(model, guide, batch_size, guidance_schedule)
-        _capi.check(ctx.lib.edmp_sampler_set_condition(ctx.h, 1 if condition else 0))
-        s, g = _startgoal(start, goal, needed=bool(condition) or guide is not None)
+            draws = ws.lead + ws.t_start - int(t_stop)
+            if hasattr(noise, "shape") and tuple(noise.shape) != (draws, int(batch_size)) + cn:
+                raise _noise_error("noise", (draws, int(batch_size)) + cn, noise)
+        self._prepare(model, guide, batch_size, guidance_schedule, condition)
+        pairs = _startgoal(start, goal, needed=bool(condition) or guide is not None)
         self._check_run(model, traj_len, num_channels, t_stop)
-        out = ctx.empty((batch_size, num_channels, traj_len), torch.float64)
         if allreduce is not None and (noise is None or isinstance(noise, str)):
             raise ValueError("sharded runs take an explicit noise array (this rank's rows of the global stream)")
-        shape = (self.T + 1, batch_size, num_channels, traj_len)
-        per_step = batch_size * num_channels * traj_len
-        sp, gp, guided, zr = _capi.as_pd(s), _capi.as_pd(g), 1 if guide is not None else 0, 1 if zero_row0 else 0
-        if ws is not None:
-            shape = (ws.lead + ws.t_start - int(t_stop),) + shape[1:]
-            x0d = ctx.to_dev(ws.x0, torch.float64)
-
-        def segment(zd, seg, X_out):
-            init, z = 1 if seg.init else 0, ptr(zd)
-            if ws is not None:  # the seed call is the run's init; every segment continues it
-                eps, z = self._after_lead(zd, seg, ws, per_step)
-                if init:
-                    _capi.check(ctx.lib.edmp_sampler_seed_dev(ctx.h, ptr(x0d), x0_rows, eps, batch_size, sp, gp, guided, ws.t_start, None), "edmp_sampler_seed_dev")
-                init = 0
-            _capi.check(
-                ctx.lib.edmp_denoise_guided_segment_dev(ctx.h, z, batch_size, sp, gp, guided, seg.t_hi, seg.t_lo, init, zr,
-                                                        ptr(X_out) if X_out is not None else None),
-                "edmp_denoise_guided_segment_dev",
-            )
-
-        t_top, plan_of = self.T, chunk_plan
-        if ws is not None:
-            t_top, plan_of = ws.t_start, lambda t_hi, t_lo, steps: warm_plan(t_hi, t_lo, ws.lead, steps)
-
         stream = noise if isinstance(noise, PinnedNoiseStream) else None
         if stream is not None:
             noise = stream.tensor
         with self._sharded(allreduce) if allreduce is not None else contextlib.nullcontext():
-            if dev_seed is not None:  # the device source in every run form: no chunk plan, no pinned ring, no draw thread
-                if ws is None:
-                    _capi.check(ctx.lib.edmp_denoise_guided_rng_dev(ctx.h, dev_seed, batch_size, sp, gp, guided, int(t_stop), zr, ptr(out)), "edmp_denoise_guided_rng_dev")
-                    return self._finish(out, return_device)
-                # a warm run: the seed call (eps = the stream's step-0 draw when re-noising) plus one segment
-                _capi.check(ctx.lib.edmp_sampler_seed_rng_dev(ctx.h, ptr(x0d), x0_rows, dev_seed, 1 if ws.renoise else 0, batch_size, sp, gp, guided, ws.t_start, None),
-                            "edmp_sampler_seed_rng_dev")
-                _capi.check(ctx.lib.edmp_denoise_guided_rng_segment_dev(ctx.h, dev_seed, batch_size, sp, gp, guided, ws.t_start, int(t_stop), 0, zr, ptr(out)),
-                            "edmp_denoise_guided_rng_segment_dev")
-                return self._finish(out, return_device, sync=True)
             if isinstance(noise, str):
                 if noise != "device":
                     raise ValueError("noise must be an array, a device tensor, None (NumPy stream) or 'device'")
-                _capi.check(ctx.lib.edmp_denoise_guided_rng_dev(ctx.h, int(seed) & 0xFFFFFFFFFFFFFFFF, batch_size, sp, gp, guided, int(t_stop), zr, ptr(out)),
-                            "edmp_denoise_guided_rng_dev")
-                return self._finish(out, return_device)
-            if noise is None:
-                return self._run_numpy_stream(plan_of(t_top, t_stop, chunk_steps), per_step, chunk_steps, segment, out, return_device)
-            if _is_pinned_f64(noise):  # uploaded in the same chunks as the on-the-fly stream
-                if tuple(noise.shape) != shape:
-                    raise _noise_error("noise", shape, noise)
-                return self._run_segments(plan_of(t_top, t_stop, chunk_steps), self._pinned_chunks(noise, stream, per_step), segment, out, return_device)
-            nd = ctx.adopt(noise) if (isinstance(noise, torch.Tensor) and noise.is_cuda) else ctx.to_dev(noise, torch.float64)
-            if tuple(nd.shape) != shape or nd.dtype != torch.float64:
-                raise _noise_error("noise", shape, nd)
-            if ws is not None:  # the resident stream of a warm run: seed + one segment
-                segment(nd, Segment(ws.t_start, int(t_stop), True, shape[0], 0), out)
-                return self._finish(out, return_device, sync=True)
-            _capi.check(ctx.lib.edmp_denoise_guided_dev(ctx.h, ptr(nd), batch_size, sp, gp, guided, int(t_stop), zr, ptr(out)), "edmp_denoise_guided_dev")
-            return self._finish(out, return_device)
+                seeds = int(seed) & 0xFFFFFFFFFFFFFFFF
+            form = _Form("guided", (batch_size,), seeds, None, settle=False)
+            return self._run(form, None if noise is None else [noise], [stream], draws, pairs, 1 if guide is not None else 0, cn, ws, x0_rows, t_stop, zero_row0,
+                             chunk_steps, return_device)
 
     def denoise_guided_scenes(self, model, batch, traj_len, num_channels, starts, goals, *, noise=None, t_stop=0, zero_row0=True, condition=True,
                               chunk_steps=DEFAULT_CHUNK_STEPS, return_device=False, guided=True, warm_start=None):
@@ -589,130 +637,50 @@ class Diffusion:
         (lead + t_start - t_stop, B, C, N)."""
         from .guide import SceneBatch, _pairs
 
-        ctx = self.ctx
         if not isinstance(batch, SceneBatch):
             raise ValueError("batch must be a guide.SceneBatch")
-        S, B = batch.n_scenes, batch.batch_size
-        ws = warm_start
-        dev_seeds = noise._for_run(S) if isinstance(noise, DeviceNoise) else None
+        S, B, T = batch.n_scenes, batch.batch_size, self.T
+        ws, cn = warm_start, (int(num_channels), int(traj_len))
+        seeds = noise._for_run(S) if isinstance(noise, DeviceNoise) else None
+        x0_rows = None
         if ws is not None:
-            cn = (int(num_channels), int(traj_len))
             x0_rows = self._check_warm(ws, t_stop, noise, None, {(S,) + cn: S, (S, B) + cn: S * B})
-        if model.ctx is not ctx or batch.ctx is not ctx:
+        if model.ctx is not self.ctx or batch.ctx is not self.ctx:
             raise _capi.EdmpError("model, scene batch and diffuser must live on the same GPU")
         self._check_run(model, traj_len, num_channels, t_stop)
         if S * B > model.max_batch:
             raise ValueError(f"{S} scenes x {B} rows exceed the model's max_batch ({model.max_batch})")
-        needed = bool(condition) or bool(guided)
         if starts is None or goals is None:
-            if needed:
+            if bool(condition) or bool(guided):
                 raise ValueError("starts and goals are required when conditioning or guiding")
             starts = goals = np.zeros((S, 7))
-        s_arr, g_arr = _pairs(S, starts, goals)
+        pairs = _pairs(S, starts, goals)
         if isinstance(noise, str):
             raise _capi.EdmpError("the device noise mode (noise='device') has no scene batch: pass NumPy-stream noise")
-        if dev_seeds is not None:  # the device source, one seed per scene: nothing is drawn, page-locked or uploaded on the host
-            Cc, N = int(num_channels), int(traj_len)
-            ctx.ensure_sampler(self.T, self.variance_thresh)
-            model._bind()
-            if guided:
-                batch._bind()
-            _capi.check(ctx.lib.edmp_sampler_set_condition(ctx.h, 1 if condition else 0))
-            out = ctx.empty((S * B, Cc, N), torch.float64)
-            sp, gp, gflag, zr = _capi.as_pd(s_arr), _capi.as_pd(g_arr), 1 if guided else 0, 1 if zero_row0 else 0
-            if ws is None:
-                _capi.check(ctx.lib.edmp_denoise_scenes_rng_dev(ctx.h, dev_seeds, S, B, sp, gp, gflag, int(t_stop), zr, ptr(out)), "edmp_denoise_scenes_rng_dev")
-            else:  # a warm run: the seed call plus one segment
-                x0d = ctx.to_dev(ws.x0, torch.float64)
-                try:
-                    _capi.check(ctx.lib.edmp_sampler_seed_scenes_rng_dev(ctx.h, ptr(x0d), x0_rows, dev_seeds, 1 if ws.renoise else 0, S, B, sp, gp, gflag, ws.t_start, None),
-                                "edmp_sampler_seed_scenes_rng_dev")
-                    _capi.check(ctx.lib.edmp_denoise_scenes_rng_segment_dev(ctx.h, dev_seeds, S, B, sp, gp, gflag, ws.t_start, int(t_stop), 0, zr, ptr(out)),
-                                "edmp_denoise_scenes_rng_segment_dev")
-                finally:
-                    ctx.sync()  # x0d dies with this frame
-            return self._finish(out, return_device, sync=True).reshape(S, B, Cc, N)
-        if noise is not None and (not isinstance(noise, (list, tuple)) or len(noise) != S):
-            raise ValueError(f"noise must be None or a list of {S} per-scene streams")
-        Cc, N, T = int(num_channels), int(traj_len), self.T
-        per = (T + 1, B, Cc, N)
-        if ws is not None:  # a warm run's streams hold exactly its draws, from every source
-            per = (ws.lead + ws.t_start - int(t_stop), B, Cc, N)
-        if noise is None:
-            # every scene's stream in scene order, as S serial calls draw them (each draws X_T and the steps down to t_stop + 1)
-            if ws is None:
-                per = (T + 1 - int(t_stop), B, Cc, N)
-            noise = [nprng.standard_normal(per) for _ in range(S)]
-        streams = [x if isinstance(x, PinnedNoiseStream) else None for x in noise]
-        tens = [x.tensor if isinstance(x, PinnedNoiseStream) else x for x in noise]
-        pinned = [_is_pinned_f64(x) for x in tens]
-        if any(pinned) and not all(pinned):
-            raise ValueError("noise: either every scene's stream is pinned host memory or none is")
-        for k, x in enumerate(tens):
-            if tuple(x.shape) not in ((per,) if ws is not None else (per, (T + 1, B, Cc, N))):
-                raise _noise_error(f"noise[{k}]", per if ws is not None else (T + 1, B, Cc, N), x)
-        ctx.ensure_sampler(self.T, self.variance_thresh)
-        model._bind()
-        if guided:
-            batch._bind()
-        _capi.check(ctx.lib.edmp_sampler_set_condition(ctx.h, 1 if condition else 0))
-        out = ctx.empty((S * B, Cc, N), torch.float64)
-        sp, gp, gflag, zr = _capi.as_pd(s_arr), _capi.as_pd(g_arr), 1 if guided else 0, 1 if zero_row0 else 0
-
-        if ws is not None:
-            x0d = ctx.to_dev(ws.x0, torch.float64)
-
-        def segment(zd, seg, X_out):
-            init, z = 1 if seg.init else 0, ptr(zd)
-            if ws is not None:  # the seed call is the run's init; every segment continues it
-                eps, z = self._after_lead(zd, seg, ws, S * B * Cc * N)
-                if init:
-                    _capi.check(ctx.lib.edmp_sampler_seed_scenes_dev(ctx.h, ptr(x0d), x0_rows, eps, S, B, sp, gp, gflag, ws.t_start, None),
-                                "edmp_sampler_seed_scenes_dev")
-                init = 0
-            _capi.check(
-                ctx.lib.edmp_denoise_scenes_segment_dev(ctx.h, z, S, B, sp, gp, gflag, seg.t_hi, seg.t_lo, init, zr,
-                                                        ptr(X_out) if X_out is not None else None),
-                "edmp_denoise_scenes_segment_dev",
-            )
-
-        plan = chunk_plan(T, t_stop, chunk_steps) if ws is None else warm_plan(ws.t_start, t_stop, ws.lead, chunk_steps)
-
-        if all(pinned):
-            # chunks of the S pinned streams (the single-scene plan), each scene's piece uploaded by DMA and placed at rows
-            # [s*B, (s+1)*B) of the chunk by a strided device copy
-            parts = [self._pinned_chunks(x, st, B * Cc * N) for x, st in zip(tens, streams)]
-
-            def source(seg):
-                chunk = ctx.empty((seg.draws, S * B, Cc, N), torch.float64)
-                pieces = [part(seg).view(seg.draws, B, Cc, N) for part in parts]
-                with torch.cuda.stream(ctx.stream):
-                    return place_scene_rows(chunk, pieces)
-
-            return self._run_segments(plan, source, segment, out, return_device).reshape(S, B, Cc, N)
-        steps = tens[0].shape[0]
-        if any(tuple(x.shape)[0] != steps for x in tens):
-            raise ValueError("noise: every scene's stream must have the same number of draws")
-        if any(isinstance(x, torch.Tensor) and x.dtype != torch.float64 for x in tens):
+        per = (T + 1 if ws is None else ws.lead + ws.t_start - int(t_stop), B) + cn  # a warm run's streams hold exactly its draws, from every source
+        streams = resident = None
+        if seeds is None:
+            if noise is not None and (not isinstance(noise, (list, tuple)) or len(noise) != S):
+                raise ValueError(f"noise must be None or a list of {S} per-scene streams")
+            if noise is None:
+                # every scene's stream in scene order, as S serial calls draw them (each draws X_T and the steps down to t_stop + 1)
+                if ws is None:
+                    per = (T + 1 - int(t_stop),) + per[1:]
+                noise = [nprng.standard_normal(per) for _ in range(S)]
+            streams = [x if isinstance(x, PinnedNoiseStream) else None for x in noise]
+            noise = [x.tensor if isinstance(x, PinnedNoiseStream) else x for x in noise]
+            pinned = [_is_pinned_f64(x) for x in noise]
+            if any(pinned) and not all(pinned):
+                raise ValueError("noise: either every scene's stream is pinned host memory or none is")
+            for k, x in enumerate(noise):
+                if tuple(x.shape) != per:
+                    raise _noise_error(f"noise[{k}]", per, x)
+            resident = not all(pinned)
+        self._prepare(model, batch if guided else None, None, None, condition)
+        if resident and any(isinstance(x, torch.Tensor) and x.dtype != torch.float64 for x in noise):
             raise ValueError("noise: every scene's stream must be f64")
-        nd = ctx.empty((steps, S * B, Cc, N), torch.float64)
-        try:
-            pieces = [ctx.adopt(x) if (isinstance(x, torch.Tensor) and x.is_cuda) else ctx.to_dev(np.asarray(x, dtype=np.float64), torch.float64) for x in tens]
-            with torch.cuda.stream(ctx.stream):
-                place_scene_rows(nd, pieces)
-            if ws is not None:  # the resident streams of a warm run: seed + one segment
-                segment(nd, Segment(ws.t_start, int(t_stop), True, steps, 0), out)
-            elif steps == T + 1:
-                _capi.check(ctx.lib.edmp_denoise_scenes_dev(ctx.h, ptr(nd), S, B, sp, gp, gflag, int(t_stop), zr, ptr(out)), "edmp_denoise_scenes_dev")
-            else:  # the NumPy stream of a run that stops at t_stop, X_T and T - t_stop steps: the whole run as one segment
-                segment(nd, Segment(T, int(t_stop), True, steps, 0), out)
-        except BaseException:
-            try:
-                ctx.sync()
-            except Exception:
-                pass
-            raise
-        return self._finish(out, return_device, sync=True).reshape(S, B, Cc, N)
+        form = _Form("scenes", (S, B), seeds, place_scene_rows, settle=True)
+        return self._run(form, noise, streams, per[0], pairs, 1 if guided else 0, cn, ws, x0_rows, t_stop, zero_row0, chunk_steps, return_device).reshape((S, B) + cn)
 
     def denoise(self, model, traj_len, num_channels, start=None, goal=None, condition=True, *, batch_size=1, noise=None, warm_start=None):
         """diffusion.py:253-278 (unguided), batched; returns X[0] like the reference when batch_size == 1."""
@@ -725,8 +693,7 @@ class Diffusion:
         ``allreduce(tensor)``: optional in-place sum over ranks of the device scalar sum(g^2) (multi-GPU)."""
         ctx = self.ctx
         B, Cc, N = X.shape
-        self._prepare(model, guide, B, guidance_schedule)
-        _capi.check(ctx.lib.edmp_sampler_set_condition(ctx.h, 1))
+        self._prepare(model, guide, B, guidance_schedule, condition=True)
         Xd = ctx.to_dev(np.array(X, dtype=np.float64), torch.float64)  # a fresh device tensor: updated in place below
         zd = ctx.to_dev(np.asarray(z, dtype=np.float64), torch.float64)
         s, g = _startgoal(start, goal, needed=True)
