@@ -105,13 +105,11 @@ SMOOTHNESS = 0.5
 _cache = {}
 
 
-def check_case(name, seed=None):
+@R.cached_case(CASES)
+def check_case(name, seed):
     """inputs of a case with the float64 reference evaluation at its margin; asserts the distance of the waypoints AND of all interpolants
     from every decision boundary and an active hinge on every row.  Computed once per case and shared; callers do not modify it."""
     c = CASES[name]
-    seed = c["seed"] if seed is None else seed
-    if (name, seed) in _cache:
-        return _cache[(name, seed)]
     inp = R.make_case(seed, ROWS, c["L"], c["no"], c["ncyl"])
     sph = R.case_spheres(c["spheres"])
     X = full_state(inp["joints"], inp["start"], inp["goal"])
@@ -121,10 +119,8 @@ def check_case(name, seed=None):
     mg = R.assert_margins(ev["way"], what)
     mgs = SW.assert_sweep_margins(ev["sweep"], what) if ev["sweep"] else None
     assert ev["active"].all() and all(np.abs(ev["grad"][r]).max() > 0 for r in range(ROWS)), f"{what}: a row without an active hinge"
-    out = dict(inp, name=name, X=X, spheres=sph, custom=c["spheres"] == "custom", L=c["L"], K=c["K"], margin=c["margin"], smoothness=SMOOTHNESS, seed=seed,
-               scene=scene, ev=ev, margins=mg, sweep_margins=mgs, cfgs=plain_cfgs(ROWS))
-    _cache[(name, seed)] = out
-    return out
+    return dict(inp, name=name, X=X, spheres=sph, custom=c["spheres"] == "custom", L=c["L"], K=c["K"], margin=c["margin"], smoothness=SMOOTHNESS, seed=seed,
+                scene=scene, ev=ev, margins=mg, sweep_margins=mgs, cfgs=plain_cfgs(ROWS))
 
 
 def yardstick(case):
@@ -135,11 +131,6 @@ def yardstick(case):
     return dict(cost=float(np.abs(e32["cost"] - ev["cost"]).max() / np.abs(ev["cost"]).max()),
                 clearance_abs=float(np.abs(e32["clearance"] - ev["clearance"]).max()),
                 grad=np.array([np.abs(e32["grad"][r] - ev["grad"][r]).max() / np.abs(ev["grad"][r]).max() for r in range(ev["grad"].shape[0])]))
-
-
-def clearance_gate(y_abs, coord_max):
-    """sdf_reference.clearance_gate's rule on a yardstick that is already absolute"""
-    return max(R.GATE_FACTOR * y_abs, R.GATE_FLOOR * coord_max)
 
 
 def plain_cfgs(n):

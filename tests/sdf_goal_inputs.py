@@ -48,20 +48,17 @@ def window_of(spec, L):
     return L if spec == "L" else L + 5 if spec == "L+5" else int(spec)
 
 
-def guide_dict(row, index, L, with_goal=True, grad_norm=True):
-    method, gn, lam, sw, gw, gr, gk = row
-    d = SELF.guide_dict(method, gn and grad_norm, lam, sw, index)
-    if gw > 0 and with_goal:
-        d["hyperparameters"]["sdf"].update(goal_weight=float(gw), goal_rotation=float(gr), goal_window=window_of(gk, L))
-    return d
-
-
-def mixed_cfgs(L, with_goal=True, grad_norm=True):
-    """the 12-row ensemble for rows of L waypoints (two windows depend on L); with_goal=False: the same rows without the goal keys;
-    grad_norm=False: no row normalises"""
-    from edmp_amd import guide_cfg as GC
-
-    return GC.build_guide_cfgs([guide_dict(g, 400 + i, L, with_goal, grad_norm) for i, g in enumerate(ROW_GUIDES)], 1, T)
+def mixed_cfgs(spec, with_term=True, grad_norm=None):
+    """the 12-row ensemble for rows of L waypoints (two windows depend on L), spec being L or a case that holds it; with_term=False: the
+    same rows without the goal keys; grad_norm=False: no row normalises"""
+    L = spec["L"] if isinstance(spec, dict) else spec
+    rows = []
+    for method, gn, lam, sw, gw, gr, gk in ROW_GUIDES:
+        keys = SELF.self_keys(sw)
+        if gw > 0 and with_term:
+            keys.update(goal_weight=float(gw), goal_rotation=float(gr), goal_window=window_of(gk, L))
+        rows.append((method, gn, lam, keys))
+    return R.mixed_ensemble(rows, 400, grad_norm)
 
 
 def pose_of(q, tool=None):
@@ -163,48 +160,31 @@ CASES = {
     "L62_flange": dict(L=62, spheres="default", tool="flange", seed=0),
 }
 N_OBSTACLES, N_CYLINDERS = 3, 1
-_cache = {}
 
 
 def goal_arrays(cfgs):
     return cfgs["sdf_goal_weight"], cfgs["sdf_goal_rotation"], cfgs["sdf_goal_window"]
 
 
-def check_case(name, seed=None):
+@R.cached_case(CASES)
+def check_case(name, seed):
     """inputs of a case with the checkers' float64 results at T_CHECK - obstacle part, self term (both asserted away from their kinks)
     and goal term against the pose of a random configuration - and the goal term's gradient in float32.  Computed once per case and
     shared; callers do not modify it."""
     c = CASES[name]
-    seed = c["seed"] if seed is None else seed
-    if (name, seed) in _cache:
-        return _cache[(name, seed)]
     L = c["L"]
     cfgs = mixed_cfgs(L)
-    inp = R.make_case(seed, B, L, N_OBSTACLES, N_CYLINDERS)
-    sph = R.case_spheres(c["spheres"])
+    inp, sph, args, _, _, sdft, _ = R.obstacle_part(f"{name} seed {seed}", seed, cfgs, L, N_OBSTACLES, N_CYLINDERS, c["spheres"], grad0=None)
     mask = franka.self_collision_pairs()
-    args = (inp["joints"], inp["start"], inp["goal"], inp["obstacle_config"], inp["kinds"], sph)
-    mt, smt, sw = cfgs["sdf_margin"][:, T_CHECK - 1], cfgs["sdf_self_margin"][:, T_CHECK - 1], cfgs["sdf_self_weight"]
-    sdft = R.evaluate(*args, mt, cfgs["smoothness"])
-    R.assert_margins(sdft, f"{name} seed {seed} t={T_CHECK}")
+    smt, sw = cfgs["sdf_self_margin"][:, T_CHECK - 1], cfgs["sdf_self_weight"]
     selft = SELF.evaluate_self(inp["joints"], sph, mask, smt, sw)
     own = np.flatnonzero(sw > 0)  # (the rows the self kernel works on)
     SELF.assert_self_margins(SELF.evaluate_self(inp["joints"][own], sph, mask, smt[own], np.ones(own.size), want_grad=False), f"{name} seed {seed}")
     target = pose_of(goal_configuration("random", inp["joints"], seed), c["tool"])
     goalt = evaluate_goal(inp["joints"], target, c["tool"], *goal_arrays(cfgs))
     assert all(np.abs(goalt["grad"][r]).max() > 0 for r in GOAL_ROWS) and not goalt["grad"][[r for r in range(B) if r not in GOAL_ROWS]].any()
-    out = dict(inp, name=name, L=L, seed=seed, spheres=sph, custom=c["spheres"] == "custom", tool=c["tool"], mask=mask, cfgs=cfgs, args=args,
-               target=target, sdft=sdft, selft=selft, goalt=goalt)
-    _cache[(name, seed)] = out
-    return out
-
-
-def total_gradient(case):
-    """the float64 raw gradient of the SDF rows at T_CHECK: obstacle part + smoothness + self term + goal term (zero on the other rows)"""
-    g = np.zeros_like(case["sdft"]["grad"])
-    rows = list(SDF_ROWS)
-    g[rows] = case["sdft"]["grad"][rows] + case["selft"]["grad"][rows] + case["goalt"]["grad"][rows]
-    return g
+    return dict(inp, name=name, L=L, seed=seed, spheres=sph, custom=c["spheres"] == "custom", tool=c["tool"], mask=mask, cfgs=cfgs, args=args,
+                target=target, sdft=sdft, selft=selft, goalt=goalt)
 
 
 def gradient_yardstick(case):
@@ -214,5 +194,5 @@ def gradient_yardstick(case):
     f32 = SELF.evaluate_self(case["joints"], case["spheres"], case["mask"], cfgs["sdf_self_margin"][:, T_CHECK - 1], cfgs["sdf_self_weight"], dtype=torch.float32)
     g32 = evaluate_goal(case["joints"], case["target"], case["tool"], *goal_arrays(cfgs), dtype=torch.float32)
     rows = list(GOAL_ROWS)
-    ref = total_gradient(case)[rows]
+    ref = R.total_gradient(case, "goal", SDF_ROWS)[rows]
     return float(np.abs(s32["grad"][rows] + f32["grad"][rows] + g32["grad"][rows] - ref).max() / np.abs(ref).max())

@@ -1,5 +1,6 @@
 """What the GPU tests of the sphere signed-distance guide and its terms share (test_gpu_sdf, test_gpu_sdf_self, test_gpu_sdf_goal,
-test_gpu_sdf_sweep, test_gpu_sdf_terms): building a guide from a case, the gradient with its sum of squares, and the parity records."""
+test_gpu_sdf_sweep, test_gpu_sdf_terms, test_gpu_scene_sdf, test_gpu_repair): building a guide from a case or one per scene, the tiny net
+and the ensembles of the runs, the gradient with its sum of squares, and the parity records."""
 import json
 import os
 
@@ -22,6 +23,42 @@ def build_guide(case, cfgs=None, **kw):
         kw.setdefault("goal_tool", case["tool"])
     return IntersectionVolumeGuide(case["obstacle_config"], DEV, cfgs, cfgs["total_batch_size"], link_mesh_extents=franka.PLACEHOLDER_LINK_EXTENTS,
                                    spheres=case["spheres"] if case.get("custom") else None, **kw)
+
+
+def scene_guides(parts, device=DEV, cfgs=None, each=lambda s: {}, **kw):
+    """one guide per scene of scene_sdf_inputs.scene_parts, with the scene's own cfgs unless cfgs lists others; each(s): scene s's own keywords"""
+    from edmp_amd.guide import IntersectionVolumeGuide
+
+    cfgs = [p["cfgs"] for p in parts] if cfgs is None else cfgs
+    return [IntersectionVolumeGuide(p["obstacle_config"], device, cfgs[s], cfgs[s]["total_batch_size"], obstacle_kinds=p["kinds"], **each(s), **kw)
+            for s, p in enumerate(parts)]
+
+
+def tiny_unet(device=DEV, max_batch=64):
+    from edmp_amd import weights as W
+    from edmp_amd.temporalunet import TemporalUNet
+    from tests.util import TINY_DIMS
+
+    return TemporalUNet(None, 7, 32, device, dims=TINY_DIMS, state_dict=W.init_state_dict(5, 7, 32, TINY_DIMS), max_batch=max_batch)
+
+
+@pytest.fixture(scope="module")
+def tiny_net():
+    """a test module imports this fixture and so builds its own net, once"""
+    return tiny_unet()
+
+
+def with_guide(guides, n):
+    """a guide list with sample guide n in the place of guide 101"""
+    return [n if g == 101 else g for g in guides]
+
+
+def run_cfgs(n):
+    """four rows each of guide 1, the SDF guide n and guide 13, whose rows normalise"""
+    from edmp_amd import guide_cfg as GC
+    from tests.sdf_reference import T
+
+    return GC.build_guide_cfgs([GC.load_guide_dict(g) for g in (1, n, 13)], 4, T)
 
 
 def gradient_and_sumsq(guide, joints, start, goal, t):

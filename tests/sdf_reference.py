@@ -218,11 +218,23 @@ def guide_dict(method, grad_norm, smoothness=0.0, index=0):
     return d
 
 
-def mixed_cfgs(with_sdf=True):
-    """the 6-row ensemble of ROW_GUIDES; with_sdf=False: the same rows with the two SDF guides turned into iv guides (no SDF keys)"""
+def mixed_ensemble(rows, index0, grad_norm=None):
+    """one way to build a mixed ensemble: guide_cfgs with one row per guide from rows of (method, grad_norm, smoothness, term keys), the
+    term keys - a dict, empty for a row without optional terms - going into hyperparameters.sdf; grad_norm=False: no row normalises"""
     from edmp_amd import guide_cfg as GC
 
-    return GC.build_guide_cfgs([guide_dict(m if (with_sdf or m != "sdf") else "iv", gn, lam, 200 + i) for i, (m, gn, lam) in enumerate(ROW_GUIDES)], 1, T)
+    ds = []
+    for i, (method, gn, lam, keys) in enumerate(rows):
+        d = guide_dict(method, gn if grad_norm is None else grad_norm, lam, index0 + i)
+        if keys:
+            d["hyperparameters"]["sdf"].update(keys)
+        ds.append(d)
+    return GC.build_guide_cfgs(ds, 1, T)
+
+
+def mixed_cfgs(with_sdf=True):
+    """the 6-row ensemble of ROW_GUIDES; with_sdf=False: the same rows with the two SDF guides turned into iv guides (no SDF keys)"""
+    return mixed_ensemble([(m if (with_sdf or m != "sdf") else "iv", gn, lam, None) for m, gn, lam in ROW_GUIDES], 200)
 
 
 # name -> L, obstacles, true cylinders among them, sphere table, seed of make_case (searched with find_seed(lambda s: check_case(name, s)))
@@ -233,34 +245,68 @@ CASES = {
     "L48_o7c2_custom": dict(L=48, no=7, ncyl=2, spheres="custom", seed=1),
     "L5_o64_custom": dict(L=5, no=64, ncyl=0, spheres="custom", seed=0),
 }
-_cache = {}
 
 
 def case_spheres(kind):
     return custom_spheres() if kind == "custom" else franka.spheres_from_boxes(franka.link_half_extents(franka.PLACEHOLDER_LINK_EXTENTS))
 
 
-def check_case(name, seed=None):
+def cached_case(cases):
+    """decorator of a module's check_case(name, seed): seed=None is the seed committed in `cases`, and every (name, seed) is computed once"""
+    def wrap(compute):
+        cache = {}
+
+        def check_case(name, seed=None):
+            key = (name, cases[name]["seed"] if seed is None else seed)
+            if key not in cache:
+                cache[key] = compute(*key)
+            return cache[key]
+
+        check_case.__doc__ = compute.__doc__
+        return check_case
+    return wrap
+
+
+def obstacle_part(what, seed, cfgs, L, no, ncyl, spheres, grad0=False):
+    """what every check_case starts from: make_case for the rows of cfgs, the sphere table, and the obstacle part at t = 0 (margin 0, every
+    row; grad0=None leaves it out) and at T_CHECK (the rows' own margins), each asserted away from the decision boundaries
+    -> inputs, sphere table, evaluate's leading arguments, result and margins at t = 0, result and margins at T_CHECK"""
+    B = cfgs["total_batch_size"]
+    inp = make_case(seed, B, L, no, ncyl)
+    sph = case_spheres(spheres)
+    args = (inp["joints"], inp["start"], inp["goal"], inp["obstacle_config"], inp["kinds"], sph)
+    ev0 = mg0 = None
+    if grad0 is not None:
+        ev0 = evaluate(*args, np.zeros(B), cfgs["smoothness"], want_grad=grad0)
+        mg0 = assert_margins(ev0, f"{what} t=0")
+    evt = evaluate(*args, cfgs["sdf_margin"][:, T_CHECK - 1], cfgs["smoothness"])
+    mgt = assert_margins(evt, f"{what} t={T_CHECK}")
+    return inp, sph, args, ev0, mg0, evt, mgt
+
+
+@cached_case(CASES)
+def check_case(name, seed):
     """inputs of a case with the checker's float64 results at t = 0 (margin 0, every row) and at T_CHECK (the rows' own margins); asserts
     the distance from the decision boundaries for both.  Computed once per case and shared; callers do not modify it."""
-    c = CASES[name]
-    seed = c["seed"] if seed is None else seed
-    key = (name, seed)
-    if key in _cache:
-        return _cache[key]
-    cfgs = mixed_cfgs()
-    B = cfgs["total_batch_size"]
-    inp = make_case(seed, B, c["L"], c["no"], c["ncyl"])
-    sph = case_spheres(c["spheres"])
-    args = (inp["joints"], inp["start"], inp["goal"], inp["obstacle_config"], inp["kinds"], sph)
-    ev0 = evaluate(*args, np.zeros(B), cfgs["smoothness"])
-    mg0 = assert_margins(ev0, f"{name} seed {seed} t=0")
-    evt = evaluate(*args, cfgs["sdf_margin"][:, T_CHECK - 1], cfgs["smoothness"])
-    mgt = assert_margins(evt, f"{name} seed {seed} t={T_CHECK}")
+    c, cfgs = CASES[name], mixed_cfgs()
+    inp, sph, args, ev0, mg0, evt, mgt = obstacle_part(f"{name} seed {seed}", seed, cfgs, c["L"], c["no"], c["ncyl"], c["spheres"], grad0=True)
     assert all(np.abs(evt["grad"][r]).max() > 0 for r in SDF_ROWS), f"{name} seed {seed}: an SDF row has a zero gradient"
-    out = dict(inp, spheres=sph, cfgs=cfgs, B=B, ev0=ev0, evt=evt, margins0=mg0, marginst=mgt, args=args, seed=seed, L=c["L"])
-    _cache[key] = out
-    return out
+    return dict(inp, spheres=sph, cfgs=cfgs, B=cfgs["total_batch_size"], ev0=ev0, evt=evt, margins0=mg0, marginst=mgt, args=args, seed=seed, L=c["L"])
+
+
+# the parts of a term's case that add up to the raw gradient of its SDF rows at T_CHECK: obstacle part + smoothness, then the terms
+GRADIENT_PARTS = {"self": ("sdft", "selft"), "goal": ("sdft", "selft", "goalt"), "sweep": ("sdft", "sweept")}
+
+
+def total_gradient(case, term_key, sdf_rows):
+    """the float64 raw gradient at T_CHECK of the mixed ensemble of a term's case: GRADIENT_PARTS added on the SDF rows, zero on the others"""
+    g = np.zeros_like(case["sdft"]["grad"])
+    rows = list(sdf_rows)
+    first, *others = GRADIENT_PARTS[term_key]
+    g[rows] = case[first]["grad"][rows]
+    for k in others:
+        g[rows] += case[k]["grad"][rows]
+    return g
 
 
 def f32_yardstick(case, t):
@@ -285,10 +331,15 @@ def gate(yardstick):
     return max(GATE_FACTOR * yardstick, GATE_FLOOR)
 
 
-def clearance_gate(case, t):
-    """absolute gate of the clearance: 4 x the CPU float32 deviation, with a floor of a few f32 ulps of the largest COORDINATE that enters
-    it - a clearance is a difference of world coordinates of the sphere centre and the obstacle (|c|, |c_o| up to ~1 m), so float32
-    cannot resolve it finer than an ulp of those, however small the clearance itself is"""
+def clearance_gate(y_abs, coord_max):
+    """absolute gate of a clearance from its absolute float32 yardstick: 4 x the CPU float32 deviation, with a floor of a few f32 ulps of the
+    largest COORDINATE that enters it - a clearance is a difference of world coordinates of the sphere centre and the obstacle (|c|, |c_o|
+    up to ~1 m), so float32 cannot resolve it finer than an ulp of those, however small the clearance itself is"""
+    return max(GATE_FACTOR * y_abs, GATE_FLOOR * coord_max)
+
+
+def case_clearance_gate(case, t):
+    """(clearance_gate, the absolute yardstick it is made from) of a check_case result of this module at step t"""
     ev = case["ev0"] if t == 0 else case["evt"]
     y = f32_yardstick(case, t)["clearance"] * float(np.abs(ev["clearance"]).max())
-    return max(GATE_FACTOR * y, GATE_FLOOR * ev["coord_max"]), y
+    return clearance_gate(y, ev["coord_max"]), y

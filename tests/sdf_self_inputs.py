@@ -25,18 +25,15 @@ ROW_GUIDES = (("sdf", False, 0.05, 0.7), ("sdf", True, 0.0, 1.5), ("sdf", False,
 SELF_ROWS, SDF_ROWS, B = (0, 1), (0, 1, 2), len(ROW_GUIDES)
 
 
-def guide_dict(method, grad_norm, smoothness, weight, index):
-    d = R.guide_dict(method, grad_norm, smoothness, index)
-    if weight > 0:
-        d["hyperparameters"]["sdf"].update(self_margin=list(SELF_MARGIN), self_weight=float(weight))
-    return d
+def self_keys(weight):
+    """the term's keys under hyperparameters.sdf of a row with this weight (none at weight 0)"""
+    return dict(self_margin=list(SELF_MARGIN), self_weight=float(weight)) if weight > 0 else {}
 
 
-def mixed_cfgs(with_self=True, grad_norm=True):
-    """the 6-row ensemble; with_self=False: the same rows without the self keys; grad_norm=False: no row normalises"""
-    from edmp_amd import guide_cfg as GC
-
-    return GC.build_guide_cfgs([guide_dict(m, gn and grad_norm, lam, w if with_self else 0.0, 300 + i) for i, (m, gn, lam, w) in enumerate(ROW_GUIDES)], 1, T)
+def mixed_cfgs(spec=None, with_term=True, grad_norm=None):
+    """the 6-row ensemble (the same for every case: spec is not read); with_term=False: the same rows without the self keys;
+    grad_norm=False: no row normalises"""
+    return R.mixed_ensemble([(m, gn, lam, self_keys(w if with_term else 0.0)) for m, gn, lam, w in ROW_GUIDES], 300, grad_norm)
 
 
 def sphere_pairs(spheres, mask):
@@ -113,26 +110,14 @@ CASES = {
     "L62_custom": dict(L=62, spheres="custom", seed=0),
 }
 N_OBSTACLES, N_CYLINDERS = 3, 1
-_cache = {}
-
-
-def check_case(name, seed=None):
+@R.cached_case(CASES)
+def check_case(name, seed):
     """inputs of a case with the checkers' float64 results - obstacle part (sdf_reference.evaluate) and self term - at t = 0 and at
     T_CHECK, both asserted away from their kinks.  Computed once per case and shared; callers do not modify it."""
-    c = CASES[name]
-    seed = c["seed"] if seed is None else seed
-    if (name, seed) in _cache:
-        return _cache[(name, seed)]
-    cfgs = mixed_cfgs()
-    inp = R.make_case(seed, B, c["L"], N_OBSTACLES, N_CYLINDERS)
-    sph = R.case_spheres(c["spheres"])
+    c, cfgs = CASES[name], mixed_cfgs()
+    inp, sph, args, sdf0, _, sdft, _ = R.obstacle_part(f"{name} seed {seed}", seed, cfgs, c["L"], N_OBSTACLES, N_CYLINDERS, c["spheres"])
     mask = franka.self_collision_pairs()
-    args = (inp["joints"], inp["start"], inp["goal"], inp["obstacle_config"], inp["kinds"], sph)
-    mt, smt, w = cfgs["sdf_margin"][:, T_CHECK - 1], cfgs["sdf_self_margin"][:, T_CHECK - 1], cfgs["sdf_self_weight"]
-    sdf0 = R.evaluate(*args, np.zeros(B), cfgs["smoothness"], want_grad=False)
-    R.assert_margins(sdf0, f"{name} seed {seed} t=0")
-    sdft = R.evaluate(*args, mt, cfgs["smoothness"])
-    R.assert_margins(sdft, f"{name} seed {seed} t={T_CHECK}")
+    smt, w = cfgs["sdf_self_margin"][:, T_CHECK - 1], cfgs["sdf_self_weight"]
     self0 = evaluate_self(inp["joints"], sph, mask, np.zeros(B), w)
     selft = evaluate_self(inp["joints"], sph, mask, smt, w)
     # the margins of EVERY row (the report evaluates them all): weight 1 everywhere
@@ -140,10 +125,8 @@ def check_case(name, seed=None):
     mg0, mgt = assert_self_margins(self0, f"{name} seed {seed} t=0"), assert_self_margins(every, f"{name} seed {seed} t={T_CHECK}")
     assert all(np.abs(selft["grad"][r]).max() > 0 for r in SELF_ROWS), f"{name} seed {seed}: a weighted row has a zero self gradient"
     assert not selft["grad"][[r for r in range(B) if r not in SELF_ROWS]].any()
-    out = dict(inp, name=name, spheres=sph, custom=c["spheres"] == "custom", mask=mask, cfgs=cfgs, L=c["L"], seed=seed, args=args, sdf0=sdf0, sdft=sdft,
-               self0=self0, selft=selft, margins0=mg0, marginst=mgt)
-    _cache[(name, seed)] = out
-    return out
+    return dict(inp, name=name, spheres=sph, custom=c["spheres"] == "custom", mask=mask, cfgs=cfgs, L=c["L"], seed=seed, args=args, sdf0=sdf0, sdft=sdft,
+                self0=self0, selft=selft, margins0=mg0, marginst=mgt)
 
 
 def yardstick(case, t):
@@ -158,14 +141,6 @@ def yardstick(case, t):
     if t:
         s32 = R.evaluate(*case["args"], cfgs["sdf_margin"][:, t - 1], cfgs["smoothness"], dtype=torch.float32)
         rows = list(SELF_ROWS)
-        ref = total_gradient(case)[rows]
+        ref = R.total_gradient(case, "self", SDF_ROWS)[rows]
         out["grad"] = float(np.abs(s32["grad"][rows] + e32["grad"][rows] - ref).max() / np.abs(ref).max())
     return out
-
-
-def total_gradient(case):
-    """the float64 raw gradient of the SDF rows at T_CHECK: obstacle part + smoothness + self term (zero on the other rows)"""
-    g = np.zeros_like(case["sdft"]["grad"])
-    rows = list(SDF_ROWS)
-    g[rows] = case["sdft"]["grad"][rows] + case["selft"]["grad"][rows]
-    return g

@@ -89,23 +89,12 @@ def assert_sweep_margins(sw, what=""):
     return mg
 
 
-def guide_dict(i, method, grad_norm, smoothness, sweep=None):
-    d = R.guide_dict(method, grad_norm, smoothness, 300 + i)
-    if sweep is not None:
-        d["hyperparameters"]["sdf"].update(sweep_weight=float(sweep[0]), sweep_substeps=int(sweep[1]))
-    return d
-
-
-def mixed_cfgs(K=(4, 2), with_sweep=True, grad_norm=None):
-    """the 7-row ensemble of ROW_GUIDES with the swept-clearance term on rows 0 and 1 (weights SWEEP_WEIGHT, substeps K[0], K[1]);
-    with_sweep=False: the same rows without it (no sweep keys); grad_norm=False: no row normalises"""
-    from edmp_amd import guide_cfg as GC
-
-    ds = []
-    for i, (m, gn, lam) in enumerate(ROW_GUIDES):
-        sweep = (SWEEP_WEIGHT[i], K[i]) if with_sweep and i in SWEEP_ROWS else None
-        ds.append(guide_dict(i, m, gn if grad_norm is None else grad_norm, lam, sweep))
-    return GC.build_guide_cfgs(ds, 1, T)
+def mixed_cfgs(spec, with_term=True, grad_norm=None):
+    """the 7-row ensemble of ROW_GUIDES with the swept-clearance term on rows 0 and 1 (weights SWEEP_WEIGHT, substeps K[0], K[1]), spec
+    being K or a case that holds it; with_term=False: the same rows without it (no sweep keys); grad_norm=False: no row normalises"""
+    K = spec["K"] if isinstance(spec, dict) else spec
+    return R.mixed_ensemble([(m, gn, lam, dict(sweep_weight=float(SWEEP_WEIGHT[i]), sweep_substeps=int(K[i])) if with_term and i in SWEEP_ROWS else None)
+                             for i, (m, gn, lam) in enumerate(ROW_GUIDES)], 300, grad_norm)
 
 
 # name -> L, obstacles, true cylinders among them, sphere table, substeps of rows 0 and 1, seed of sdf_reference.make_case(seed, B, ...)
@@ -121,26 +110,18 @@ CASES = {
 _cache = {}
 
 
-def check_case(name, seed=None):
+@R.cached_case(CASES)
+def check_case(name, seed):
     """inputs of a case with the checkers' float64 results - obstacle part at the waypoints (sdf_reference.evaluate) and the sweep term -
     at t = 0 and at T_CHECK; asserts the distance of the waypoints AND of all interpolants from every decision boundary for both, and
     that the term's gradient is non-zero on the weighted rows at T_CHECK.  `every0`: weight 1 and K[0] on the first UNBOUND_ROWS rows at
     t = 0 (the report with substeps= on rows that are not the bound ones).  Computed once per case and shared; callers do not modify it."""
     c = CASES[name]
-    seed = c["seed"] if seed is None else seed
-    if (name, seed) in _cache:
-        return _cache[(name, seed)]
     cfgs = mixed_cfgs(c["K"])
     assert cfgs["total_batch_size"] == B
-    inp = R.make_case(seed, B, c["L"], c["no"], c["ncyl"])
-    sph = R.case_spheres(c["spheres"])
-    args = (inp["joints"], inp["start"], inp["goal"], inp["obstacle_config"], inp["kinds"], sph)
-    mt, w, Ks = cfgs["sdf_margin"][:, T_CHECK - 1], cfgs["sdf_sweep_weight"], cfgs["sdf_sweep_substeps"]
     what = f"{name} seed {seed}"
-    sdf0 = R.evaluate(*args, np.zeros(B), cfgs["smoothness"], want_grad=False)
-    R.assert_margins(sdf0, f"{what} t=0")
-    sdft = R.evaluate(*args, mt, cfgs["smoothness"])
-    R.assert_margins(sdft, f"{what} t={T_CHECK}")
+    inp, sph, args, sdf0, _, sdft, _ = R.obstacle_part(what, seed, cfgs, c["L"], c["no"], c["ncyl"], c["spheres"])
+    mt, w, Ks = cfgs["sdf_margin"][:, T_CHECK - 1], cfgs["sdf_sweep_weight"], cfgs["sdf_sweep_substeps"]
     n = UNBOUND_ROWS
     every0 = evaluate_sweep(inp["joints"][:n], *args[1:], np.zeros(n), np.ones(n), c["K"][0], want_grad=False)
     mg_every = assert_sweep_margins(every0, f"{what} t=0, every row")
@@ -150,18 +131,8 @@ def check_case(name, seed=None):
     mgt = assert_sweep_margins(sweept, f"{what} t={T_CHECK}")
     assert all(np.abs(sweept["grad"][r]).max() > 0 for r in SWEEP_ROWS), f"{what}: a weighted row has a zero sweep gradient"
     assert not sweept["grad"][[r for r in range(B) if r not in SWEEP_ROWS]].any() and not sweept["cost"][[r for r in range(B) if r not in SWEEP_ROWS]].any()
-    out = dict(inp, name=name, spheres=sph, custom=c["spheres"] == "custom", cfgs=cfgs, L=c["L"], K=c["K"], seed=seed, args=args, sdf0=sdf0, sdft=sdft,
-               sweep0=sweep0, sweept=sweept, every0=every0, margins0=mg0, marginst=mgt, margins_every=mg_every)
-    _cache[(name, seed)] = out
-    return out
-
-
-def total_gradient(case):
-    """the float64 raw gradient at T_CHECK: obstacle part + smoothness on the SDF rows, + the sweep term on the weighted ones"""
-    g = np.zeros_like(case["sdft"]["grad"])
-    rows = list(SDF_ROWS)
-    g[rows] = case["sdft"]["grad"][rows] + case["sweept"]["grad"][rows]
-    return g
+    return dict(inp, name=name, spheres=sph, custom=c["spheres"] == "custom", cfgs=cfgs, L=c["L"], K=c["K"], seed=seed, args=args, sdf0=sdf0, sdft=sdft,
+                sweep0=sweep0, sweept=sweept, every0=every0, margins0=mg0, marginst=mgt, margins_every=mg_every)
 
 
 def yardstick(case, t):
@@ -177,7 +148,7 @@ def yardstick(case, t):
     if t:
         s32 = R.evaluate(*case["args"], m, cfgs["smoothness"], dtype=torch.float32)
         rows = list(SWEEP_ROWS)
-        ref = total_gradient(case)[rows]
+        ref = R.total_gradient(case, "sweep", SDF_ROWS)[rows]
         out["grad"] = float(np.abs(s32["grad"][rows] + e32["grad"][rows] - ref).max() / np.abs(ref).max())
     return out
 

@@ -15,8 +15,8 @@ import torch
 from edmp_amd import franka
 from tests import repair_inputs as I
 from tests import sdf_reference as R
-from tests.sdf_gpu import DEV, recorder
-from tests.util import TINY_DIMS
+from tests.sdf_gpu import DEV, recorder, run_cfgs, tiny_net  # noqa: F401  (tiny_net: this module's fixture)
+from tests.sdf_term_suite import segmented_run_goes_on
 
 pytestmark = pytest.mark.gpu
 record, _write_records = recorder("repair parity", "EDMP_REPAIR_PARITY_OUT",
@@ -64,7 +64,7 @@ def test_report_only(name):
     assert out["iterations"].dtype == np.int32 and not out["iterations"].any()
     scale = float(np.abs(ev["cost"]).max())
     cost_err = float(np.abs(out["cost"] - ev["cost"]).max())
-    cgate = I.clearance_gate(y["clearance_abs"], ev["coord_max"])
+    cgate = R.clearance_gate(y["clearance_abs"], ev["coord_max"])
     clr_err = float(np.abs(out["clearance"] - ev["clearance"]).max())
     inner = case["X"][:, :, 1:-1]
     way = guide.sdf_rows(inner, case["start"], case["goal"], 0)["clearance"]
@@ -325,47 +325,21 @@ def _capi_error():
     return _capi.EdmpError
 
 
-def test_a_segmented_run_goes_on():
+def test_a_segmented_run_goes_on(tiny_net):
     """11. a repair_rows call - with another start / goal pair than the run's - between two segments of a segmented run: the run's result
     is bit-identical to the uninterrupted one"""
-    from edmp_amd import _capi, scenes
-    from edmp_amd import guide_cfg as GC
-    from edmp_amd import weights as W
-    from edmp_amd.diffusion import Diffusion
+    from edmp_amd import scenes
     from edmp_amd.guide import IntersectionVolumeGuide
-    from edmp_amd.runtime import ptr
-    from edmp_amd.temporalunet import TemporalUNet
 
-    T = R.T
-    net = TemporalUNet(None, 7, 32, DEV, dims=TINY_DIMS, state_dict=W.init_state_dict(5, 7, 32, TINY_DIMS), max_batch=64)
-    cfgs = GC.build_guide_cfgs([GC.load_guide_dict(n) for n in (1, 101, 13)], 4, T)
-    Bn = cfgs["total_batch_size"]
+    cfgs = run_cfgs(101)
     s, gl = np.asarray(scenes.DEFAULT_START, dtype=np.float64), np.asarray(scenes.DEFAULT_GOAL, dtype=np.float64)
-    dif = Diffusion(T, DEV)
     rs = np.random.RandomState(11)
-    g = IntersectionVolumeGuide(scenes.random_scene(7, 8), DEV, cfgs, Bn)
-    ctx, lib = g.ctx, g.ctx.lib
-    z0 = ctx.to_dev(rs.standard_normal((1 + 4, Bn, 7, 50)), torch.float64)
-    z1 = ctx.to_dev(rs.standard_normal((4, Bn, 7, 50)), torch.float64)
-    X = rs.uniform(-1, 1, (5, 7, 50))
-    sp, gp = _capi.as_pd(np.ascontiguousarray(s)), _capi.as_pd(np.ascontiguousarray(gl))
+    g = IntersectionVolumeGuide(scenes.random_scene(7, 8), DEV, cfgs, cfgs["total_batch_size"])
 
-    def run(between):
-        dif._prepare(net, g, Bn, cfgs["guidance_schedule"])
-        _capi.check(lib.edmp_sampler_set_condition(ctx.h, 1))
-        out = ctx.empty((Bn, 7, 50), torch.float64)
-        _capi.check(lib.edmp_denoise_guided_segment_dev(ctx.h, ptr(z0), Bn, sp, gp, 1, T, T - 4, 1, 1, None), "first segment")
-        mid = between()
-        rc = lib.edmp_denoise_guided_segment_dev(ctx.h, ptr(z1), Bn, sp, gp, 1, T - 4, T - 8, 0, 1, ptr(out))
-        msg = lib.edmp_last_error().decode() if rc else ""
-        ctx.sync()
-        return rc, msg, ctx.to_host(out), mid
+    def between():  # (called once, after the noise of both segments has been drawn from rs)
+        return g.repair_rows(rs.uniform(-1, 1, (5, 7, 50)), gl, s, iters=3, margin=0.1, rows=[4, 1])
 
-    rc, msg, whole, _ = run(lambda: None)
-    assert rc == 0, msg
-    rc, msg, cut, mid = run(lambda: g.repair_rows(X, gl, s, iters=3, margin=0.1, rows=[4, 1]))
-    assert rc == 0, msg
-    assert np.isfinite(whole).all() and np.array_equal(whole, cut)
+    mid = segmented_run_goes_on(tiny_net, g, cfgs, s, gl, rs, between)
     assert np.isfinite(mid["clearance"][[4, 1]]).all() and (mid["iterations"][[4, 1]] >= 0).all()
 
 

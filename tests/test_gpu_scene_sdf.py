@@ -12,28 +12,14 @@ import torch
 
 from tests import scene_sdf_inputs as I
 from tests import sdf_reference as R
-from tests.util import T, TINY_DIMS
+from tests.sdf_gpu import DEV, scene_guides, tiny_unet
+from tests.util import T
 
 pytestmark = pytest.mark.gpu
 
-DEV = "cuda:0"
 S, B, N = I.S, I.B, I.N
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 ERR_ARG, ERR_STATE = -1, -3
-
-
-def _net(device):
-    from edmp_amd import weights as W
-    from edmp_amd.temporalunet import TemporalUNet
-
-    return TemporalUNet(None, 7, 32, device, dims=TINY_DIMS, state_dict=W.init_state_dict(5, 7, 32, TINY_DIMS), max_batch=S * B)
-
-
-def _guides(parts, device, cfgs=None, **kw):
-    from edmp_amd.guide import IntersectionVolumeGuide
-
-    return [IntersectionVolumeGuide(p["obstacle_config"], device, p["cfgs"] if cfgs is None else cfgs[s], B, obstacle_kinds=p["kinds"], **kw)
-            for s, p in enumerate(parts)]
 
 
 class Data:
@@ -44,15 +30,15 @@ class Data:
         from edmp_amd.diffusion import Diffusion
 
         self.parts = I.scene_parts()
-        self.net, self.dif = _net(DEV), Diffusion(T, DEV)
-        self.guides = _guides(self.parts, DEV)
+        self.net, self.dif = tiny_unet(DEV, max_batch=S * B), Diffusion(T, DEV)
+        self.guides = scene_guides(self.parts, DEV)
         self.starts = np.stack([p["start"] for p in self.parts])
         self.goals = np.stack([p["goal"] for p in self.parts])
         self.noises = I.noises()
         self.ref = self.serial(self.guides, self.noises)
         # conditions on the inputs (another seed if a scene misses one): the serial run is finite, and its SDF rows are not the rows of a
         # serial run whose sdf_rows are zeroed
-        plain = self.serial(_guides(self.parts, DEV, cfgs=[I.zero_mask(p["cfgs"]) for p in self.parts]), self.noises)
+        plain = self.serial(scene_guides(self.parts, DEV, cfgs=[I.zero_mask(p["cfgs"]) for p in self.parts]), self.noises)
         for s, p in enumerate(self.parts):
             rows = np.flatnonzero(np.asarray(p["cfgs"]["sdf_rows"]))
             assert np.isfinite(self.ref[s]).all(), s
@@ -154,8 +140,8 @@ def test_batch_without_sdf_rows_is_what_it_was(data):
     report asked of the plain batch builds its table lazily and changes nothing"""
     from edmp_amd.guide import SceneBatch
 
-    plain = SceneBatch(_guides(data.parts, DEV, cfgs=[I.without_sdf(p["cfgs"]) for p in data.parts], bind=False))
-    zero = SceneBatch(_guides(data.parts, DEV, cfgs=[I.zero_mask(p["cfgs"]) for p in data.parts], bind=False))
+    plain = SceneBatch(scene_guides(data.parts, DEV, cfgs=[I.without_sdf(p["cfgs"]) for p in data.parts], bind=False))
+    zero = SceneBatch(scene_guides(data.parts, DEV, cfgs=[I.zero_mask(p["cfgs"]) for p in data.parts], bind=False))
     assert not plain.has_sdf_rows and not zero.has_sdf_rows and set(plain.tables) == set(zero.tables) and "sdf_rows" not in plain.tables
     run = lambda b: data.dif.denoise_guided_scenes(data.net, b, N, 7, data.starts, data.goals, noise=data.noises, t_stop=100)  # noqa: E731
     Xp, Xz = run(plain), run(zero)
@@ -215,9 +201,9 @@ def test_the_table_belongs_to_the_rows(data):
 
     def objects(ctx):
         plain_cfgs = [I.without_sdf(p["cfgs"]) for p in data.parts]
-        return dict(sdf=_unbound_batch(_guides(data.parts, ctx, bind=False)),
-                    plain=_unbound_batch(_guides(data.parts[1:], ctx, cfgs=plain_cfgs[1:], bind=False)),
-                    single=_guides(data.parts[2:], ctx, cfgs=plain_cfgs[2:], bind=False)[0])
+        return dict(sdf=_unbound_batch(scene_guides(data.parts, ctx, bind=False)),
+                    plain=_unbound_batch(scene_guides(data.parts[1:], ctx, cfgs=plain_cfgs[1:], bind=False)),
+                    single=scene_guides(data.parts[2:], ctx, cfgs=plain_cfgs[2:], bind=False)[0])
 
     def run(dif, net, name, obj):
         kw = dict(t_stop=200)
@@ -234,12 +220,12 @@ def test_the_table_belongs_to_the_rows(data):
             obj._slot = 1
             assert ctx.lib.edmp_guide_slot(ctx.h, 1) == 0
             _into_current_slot(obj)
-            fresh[name] = run(Diffusion(T, ctx), _net(ctx), name, obj)
+            fresh[name] = run(Diffusion(T, ctx), tiny_unet(ctx, max_batch=S * B), name, obj)
         finally:
             ctx.close()
     ctx = Context(0)
     try:
-        dif, net, objs = Diffusion(T, ctx), _net(ctx), objects(ctx)
+        dif, net, objs = Diffusion(T, ctx), tiny_unet(ctx, max_batch=S * B), objects(ctx)
         assert ctx.lib.edmp_guide_slot(ctx.h, 1) == 0
         for name in ("sdf", "plain", "single", "sdf"):
             objs[name]._slot = 1
@@ -305,7 +291,7 @@ def test_refusals(data):
     rc = lib.edmp_sdf_rows_dev(h, ptr(Xd), S * B, N - 2, 0, pd(sa[0]), pd(ga[0]), C.c_void_p(out[0].data_ptr()), C.c_void_p(out[1].data_ptr()))
     assert rc == ERR_STATE and "scene batch" in _msg(lib), (rc, _msg(lib))
     # without a table: a plain batch at the C level
-    plain = SceneBatch(_guides(data.parts, DEV, cfgs=[I.without_sdf(p["cfgs"]) for p in data.parts], bind=False))
+    plain = SceneBatch(scene_guides(data.parts, DEV, cfgs=[I.without_sdf(p["cfgs"]) for p in data.parts], bind=False))
     plain._bind()
     rc, msg = report()
     assert rc != 0 and "edmp_scene_batch_set_sdf first" in msg, (rc, msg)
@@ -315,7 +301,7 @@ def test_refusals(data):
     # members with different sphere tables
     other = R.custom_spheres()
     with pytest.raises(ValueError, match="scene 1.*sphere table"):
-        SceneBatch([data.guides[0]] + _guides(data.parts[1:2], DEV, bind=False, spheres=other))
+        SceneBatch([data.guides[0]] + scene_guides(data.parts[1:2], DEV, bind=False, spheres=other))
     # and the batch still reports and plans what it did
     after = batch.sdf_rows(Xh, data.starts, data.goals, R.T_CHECK)
     assert after["cost"].tobytes() == before["cost"].tobytes() and after["clearance"].tobytes() == before["clearance"].tobytes()

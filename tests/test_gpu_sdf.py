@@ -14,8 +14,8 @@ import torch
 
 from tests import sdf_reference as R
 from tests import sdf_gpu
-from tests.sdf_gpu import DEV, recorder
-from tests.util import TINY_DIMS, noise_for
+from tests.sdf_gpu import DEV, recorder, tiny_net  # noqa: F401  (tiny_net: this module's fixture)
+from tests.util import noise_for
 
 pytestmark = pytest.mark.gpu
 T = R.T
@@ -76,7 +76,7 @@ def test_cost_and_clearance_of_every_row(name, t):
     y = R.f32_yardstick(case, t)
     cost_scale = float(np.abs(ev["cost"]).max())
     cost_err = float(np.abs(out["cost"] - ev["cost"]).max()) / cost_scale
-    cgate, cy = R.clearance_gate(case, t)
+    cgate, cy = R.case_clearance_gate(case, t)
     clr_err = float(np.abs(out["clearance"] - ev["clearance"]).max())
     record(test="cost_clearance", case=name, t=t, cost_rel_err=cost_err, cost_yardstick=y["cost"], cost_gate=R.gate(y["cost"]), clearance_abs_err=clr_err,
            clearance_yardstick_abs=cy, clearance_gate_abs=cgate)
@@ -140,15 +140,6 @@ def test_smoothness_alone(L):
     assert err <= R.gate(y), (err, y)
     assert np.abs(G[0] - ev["grad"][0]).max() / scale <= R.gate(y)  # the checker says the same
     assert not G[1].any()  # the SDF row without smoothness weight has nothing to follow (g / ||g_all|| of zeros)
-
-
-@pytest.fixture(scope="module")
-def tiny_net():
-    from edmp_amd import weights as W
-    from edmp_amd.temporalunet import TemporalUNet
-
-    sd = W.init_state_dict(5, 7, 32, TINY_DIMS)
-    return TemporalUNet(None, 7, 32, DEV, dims=TINY_DIMS, state_dict=sd, max_batch=64)
 
 
 def test_teacher_forced_step(tiny_net):

@@ -19,14 +19,16 @@ import torch
 from tests import scene_sdf_inputs as SI
 from tests import sdf_goal_inputs as I
 from tests import sdf_reference as R
-from tests.sdf_gpu import DEV, build_guide, gradient_and_sumsq, recorder
-from tests.util import TINY_DIMS
+from tests import sdf_term_suite as suite
+from tests.sdf_gpu import DEV, build_guide, recorder, tiny_net  # noqa: F401  (tiny_net: this module's fixture)
 
 pytestmark = pytest.mark.gpu
 T, B = I.T, I.B
 record, _write_records = recorder("sdf goal parity", "EDMP_SDF_GOAL_PARITY_OUT",
                                   "cost, gradient: max(4 x CPU-float32 deviation from float64, 4 f32 ulps), relative to the largest element; distance, angle: "
                                   "absolute, max(4 x CPU-float32 deviation, 4 f32 ulps of the largest coordinate / of pi)")
+TERM = suite.Term("goal", I, guide=103, rows=I.GOAL_ROWS, report=lambda g, X, start, goal, t: g.sdf_goal_rows(X, t), gradient_yardstick=I.gradient_yardstick,
+                  guide_kw=lambda case: dict(goal_target=case["target"]))
 
 
 def report_inputs(L, n, seed=0):
@@ -72,7 +74,7 @@ def test_report_of_every_row(L, tool, derived):
         inp = report_inputs(L, n)
         dicts = []  # n SDF rows, each with its own goal weight, rotation (0 among them) and window
         for i in range(n):
-            d = I.SELF.guide_dict("sdf", False, 0.0, 0.0, 500 + i)
+            d = R.guide_dict("sdf", False, 0.0, 500 + i)
             d["hyperparameters"]["sdf"].update(goal_weight=0.5 + 0.25 * i, goal_rotation=(0.0, 0.05, 1.0)[i % 3], goal_window=int(windows[i % 4]))
             dicts.append(d)
         cfgs = GC.build_guide_cfgs(dicts, 1, T)
@@ -105,48 +107,12 @@ def test_gradient_of_a_mixed_ensemble(name):
     """get_gradient on SDF + self + goal, SDF + goal, plain SDF, iv and sv rows, with and without grad_norm, the weighted rows {1, 6, 7,
     10}: against checker(obstacle + self + goal), the normalised one un-normalised by the device's own sum g^2; every other row that
     does not normalise BIT-identical to the same ensemble built without the goal keys"""
-    case = I.check_case(name)
-    t, cfgs, L = I.T_CHECK, case["cfgs"], case["L"]
-    y = I.gradient_yardstick(case)
-    ref = I.total_gradient(case)
-    args = (case["joints"], case["start"], case["goal"], t)
-    G, sq = gradient_and_sumsq(build_guide(case, goal_target=case["target"]), *args)
-    G_again, sq_again = gradient_and_sumsq(build_guide(case, goal_target=case["target"]), *args)
-    G0, sq0 = gradient_and_sumsq(build_guide(case, cfgs=I.mixed_cfgs(L, with_goal=False), goal_target=case["target"]), *args)
-    assert G.shape == ref.shape and np.isfinite(G).all()
-    assert np.array_equal(G, G_again) and sq == sq_again  # one order of every sum
-    rows = list(I.GOAL_ROWS)
-    scale = float(np.abs(ref[rows]).max())
-    err = {}
-    for r in rows:
-        raw = G[r] * float(np.float32(math.sqrt(sq))) if cfgs["grad_norm"][r] else G[r]
-        err[r] = float(np.abs(raw - ref[r]).max()) / scale
-    record(test="gradient", case=name, t=t, row_rel_err=err, yardstick=y, gate=R.gate(y),
-           goal_share_of_gradient=float(np.abs(case["goalt"]["grad"][rows]).max() / scale))
-    for r in rows:
-        assert err[r] <= R.gate(y), (r, err[r], y)
-        assert not np.array_equal(G[r], G0[r])  # the term does reach the row
-    assert sq != sq0
-    for r in range(B):
-        if r not in rows and not cfgs["grad_norm"][r]:
-            assert np.array_equal(G[r], G0[r]), r
+    suite.gradient_of_a_mixed_ensemble(TERM, record, name)
     # the sum g^2 is that of the final elements: on the ensemble in which no row normalises the returned gradient is the raw one
-    flat = I.mixed_cfgs(L, grad_norm=False)
-    Gf, sqf = gradient_and_sumsq(build_guide(case, cfgs=flat, goal_target=case["target"]), *args)
-    want = math.fsum((Gf.astype(np.float64) ** 2).ravel().tolist())
-    record(test="rowsq", case=name, rel_err=abs(sqf - want) / want, bound=8 * 2.0 ** -24)
-    assert abs(sqf - want) / want <= 8 * 2.0 ** -24, (sqf, want)  # seven f32 fmaf per lane, then f64 sums
+    suite.rowsq_is_the_sum_of_the_final_squares(TERM, record, name)
 
 
 # ---- runs ------------------------------------------------------------------------------------------------------------------------------
-@pytest.fixture(scope="module")
-def tiny_net():
-    from edmp_amd import weights as W
-    from edmp_amd.temporalunet import TemporalUNet
-
-    return TemporalUNet(None, 7, 32, DEV, dims=TINY_DIMS, state_dict=W.init_state_dict(5, 7, 32, TINY_DIMS), max_batch=64)
-
-
 def far_case(L=48, seed=0):
     """rows of 48 waypoints in a scene whose obstacles are >= 5 m away: no obstacle hinge is active at any margin"""
     inp = R.make_case(seed, B, L, I.N_OBSTACLES, I.N_CYLINDERS, far=True)
@@ -232,7 +198,7 @@ def test_device_loop(tiny_net, condition):
                                warm_start=WarmStart(X8, 8, renoise=False))
         return X, guide
 
-    cfgs, cfgs0 = I.mixed_cfgs(48, grad_norm=False), I.mixed_cfgs(48, with_goal=False, grad_norm=False)
+    cfgs, cfgs0 = I.mixed_cfgs(48, grad_norm=False), I.mixed_cfgs(48, with_term=False, grad_norm=False)
     assert not cfgs["grad_norm"].any()
     Xg, guide = run(cfgs, goal_target=target)
     X0, _ = run(cfgs0, goal_target=target)
@@ -252,10 +218,6 @@ def test_device_loop(tiny_net, condition):
         assert np.array_equal(X, Xg)
 
 
-def with_103(guides):
-    return [103 if n == 101 else n for n in guides]
-
-
 SCENE_GUIDES = (([1, 101, 10, 101], 1), ([101, 13], 2), ([5, 101], 2))  # B = 4 rows each; scene 1 mixes goal rows with rows that normalise
 
 
@@ -264,34 +226,13 @@ def test_scene_batch_equals_serial_runs(tiny_net, derived):
     """5. three scenes with different obstacle counts, goals and targets, guide 103 at different places: 8 steps (4 guided) of the batch
     equal each scene's serial run bit for bit - raw gradient, sum g^2 and the normalising neighbours all enter the state - and so does
     the report"""
-    from edmp_amd.diffusion import Diffusion
-    from edmp_amd.guide import IntersectionVolumeGuide, SceneBatch
-
-    parts = SI.scene_parts()
-    S, Bs, N = SI.S, 4, SI.N
-    cfgs = [SI.cfgs_for(with_103(gl), bpg) for gl, bpg in SCENE_GUIDES]
-    plain = [SI.cfgs_for(gl, bpg) for gl, bpg in SCENE_GUIDES]
-    assert all(c["total_batch_size"] == Bs and c["sdf_goal_weight"].any() and "sdf_goal_weight" not in q for c, q in zip(cfgs, plain))
-    tool = I.CUSTOM_TOOL
+    S, Bs = SI.S, 4
     targets = [None if derived else I.random_pose(40 + s) for s in range(S)]
-    mk = lambda cs: [IntersectionVolumeGuide(p["obstacle_config"], DEV, cs[s], Bs, obstacle_kinds=p["kinds"], goal_tool=tool, goal_target=targets[s])  # noqa: E731
-                     for s, p in enumerate(parts)]
-    guides, guides0 = mk(cfgs), mk(plain)
-    starts, goals = np.stack([p["start"] for p in parts]), np.stack([p["goal"] for p in parts])
     rs = np.random.RandomState(SI.NOISE_SEED)
-    noises = [rs.standard_normal((T + 1, Bs, 7, N)) for _ in range(S)]
-    dif, t_stop = Diffusion(T, DEV), T - 8
-    serial = lambda gs: [dif.denoise_guided(tiny_net, g, N, 7, g._sched, batch_size=Bs, start=starts[s], goal=goals[s], noise=noises[s], t_stop=t_stop)  # noqa: E731
-                         for s, g in enumerate(gs)]
-    ref, ref0 = serial(guides), serial(guides0)
-    batch = SceneBatch(guides)
-    assert batch.has_goal_term
-    got = dif.denoise_guided_scenes(tiny_net, batch, N, 7, starts, goals, noise=noises, t_stop=t_stop)
-    for s in range(S):
-        assert np.isfinite(ref[s]).all() and np.array_equal(got[s], ref[s]), s
-        assert not np.array_equal(ref[s], ref0[s]), s  # the term moves the weighted rows
-    gn = np.flatnonzero(cfgs[1]["grad_norm"])
-    assert gn.size and not np.array_equal(ref[1][gn], ref0[1][gn])  # and, through the norm, their normalising neighbours
+    noises = [rs.standard_normal((T + 1, Bs, 7, SI.N)) for _ in range(S)]
+    run = suite.scene_batch_run(TERM, tiny_net, SCENE_GUIDES, noises, 8, each=lambda s: dict(goal_tool=I.CUSTOM_TOOL, goal_target=targets[s]))
+    batch, guides, starts, goals, got = run.batch, run.guides, run.starts, run.goals, run.got
+    assert batch.batch_size == Bs
     rep = batch.sdf_goal_rows(got)
     fin = batch.sdf_goal_rows(got, final=True)
     for s in range(S):
@@ -317,13 +258,12 @@ def test_scene_batch_refusals():
         SceneBatch([mk(0), mk(1, goal_target=I.random_pose(1))])
     with pytest.raises(ValueError, match="scene 1.*goal_tool"):
         SceneBatch([mk(0, goal_tool="flange"), mk(1, goal_tool="hand")])
-    assert SceneBatch([mk(0, goal_tool="flange"), mk(1, goal_tool="flange")]).has_goal_term
+    assert SceneBatch([mk(0, goal_tool="flange"), mk(1, goal_tool="flange")]).has_term("goal")
 
 
 # ---- 6. state rules ----------------------------------------------------------------------------------------------------------------------
 def test_state_rules_and_refusals():
     from edmp_amd import _capi
-    from edmp_amd.guide import SceneBatch
 
     case = I.check_case("L2_flange")
     cfgs, L = case["cfgs"], case["L"]
@@ -331,22 +271,22 @@ def test_state_rules_and_refusals():
     k = np.ascontiguousarray(k.astype(np.int32))
     tool = np.ascontiguousarray(I.CUSTOM_TOOL.reshape(12))
     tgt = np.ascontiguousarray(case["target"].reshape(12))
-    no_sdf = {key: v for key, v in I.mixed_cfgs(L, with_goal=False).items() if not key.startswith("sdf_") and key != "smoothness"}
+    no_sdf = {key: v for key, v in I.mixed_cfgs(L, with_term=False).items() if not key.startswith("sdf_") and key != "smoothness"}
     plain = build_guide(case, cfgs=no_sdf)
     plain._bind()
     lib, h = plain.ctx.lib, plain.ctx.h
 
     def call(w_=w, r_=r, k_=k, tool_=tool, tgt_=tgt, n=B):
-        rc = lib.edmp_sdf_set_goal(h, _capi.as_pd(np.ascontiguousarray(w_)), _capi.as_pd(np.ascontiguousarray(r_)), _capi.as_pi32(np.ascontiguousarray(k_)),
-                                   _capi.as_pd(np.ascontiguousarray(tool_)), None if tgt_ is None else _capi.as_pd(np.ascontiguousarray(tgt_)), n)
-        return rc, (lib.edmp_last_error() or b"").decode()
+        return suite.setter_call(TERM, lib, h, _capi.as_pd(np.ascontiguousarray(w_)), _capi.as_pd(np.ascontiguousarray(r_)), _capi.as_pi32(np.ascontiguousarray(k_)),
+                                 _capi.as_pd(np.ascontiguousarray(tool_)), None if tgt_ is None else _capi.as_pd(np.ascontiguousarray(tgt_)), n)
 
     rc, msg = call()  # before the sphere table
     assert rc == -3 and msg.startswith("edmp_sdf_set_goal") and "edmp_sdf_set" in msg, (rc, msg)
     guide = build_guide(case, goal_target=case["target"])
     guide._bind()
     args = (case["joints"], case["start"], case["goal"], I.T_CHECK)
-    before, G = guide.sdf_goal_rows(case["joints"]), guide.get_gradient(*args)
+    state = lambda: suite.bound_state(guide, case, guide.sdf_goal_rows(case["joints"]))  # noqa: E731
+    before = state()
     w_bad = w.copy()
     w_bad[3] = 1.0  # an iv row
     k_bad = k.copy()
@@ -358,8 +298,7 @@ def test_state_rules_and_refusals():
                              ("target not orthonormal", dict(tgt_=2 * tgt), "target")):
         rc, msg = call(**kw)
         assert rc == -1 and msg.startswith("edmp_sdf_set_goal") and needle in msg, (what, rc, msg)
-    after = guide.sdf_goal_rows(case["joints"])
-    assert all(np.array_equal(after[key], before[key]) for key in before) and np.array_equal(guide.get_gradient(*args), G)
+    suite.assert_state_is(state(), before)
     with pytest.raises(_capi.EdmpError, match="edmp_sdf_goal_rows_dev"):
         guide.sdf_goal_rows(case["joints"][:3], I.T_CHECK)  # t >= 1: the bound rows
     with pytest.raises(_capi.EdmpError, match="edmp_sdf_goal_rows_dev"):
@@ -375,57 +314,26 @@ def test_state_rules_and_refusals():
     assert rows_dev() == 0, lib.edmp_last_error()
     plain.ctx.sync()
     # a new sphere table drops the term: the gradient is that of the ensemble without it, and the report asks for edmp_sdf_set_goal again
-    guide._term_on["goal"] = False
-    guide._set_sdf()
-    G0 = build_guide(case, cfgs=I.mixed_cfgs(L, with_goal=False)).get_gradient(*args)
-    guide._bind()
-    assert np.array_equal(guide.get_gradient(*args), G0) and not np.array_equal(G0, G)
+    suite.a_later_table_drops_the_term(TERM, guide, case, before[1])
     assert rows_dev() == -3 and b"edmp_sdf_set_goal" in lib.edmp_last_error()
     # in a batch the message names the scene and the row inside it
-    a, b = build_guide(case, bind=False), build_guide(case, bind=False)
-    batch = SceneBatch([a, b])
-    batch._bind()
-    rc = lib.edmp_sdf_set_goal(h, _capi.as_pd(np.concatenate([w, w_bad])), _capi.as_pd(np.concatenate([r, r])), _capi.as_pi32(np.concatenate([k, k])), _capi.as_pd(tool), None,
-                               2 * B)
-    msg = (lib.edmp_last_error() or b"").decode()
+    suite.bind_a_batch_of_two(case)
+    rc, msg = call(w_=np.concatenate([w, w_bad]), r_=np.concatenate([r, r]), k_=np.concatenate([k, k]), tgt_=None, n=2 * B)
     assert rc == -1 and "scene 1, row 3" in msg, (rc, msg)
 
 
 def test_a_segmented_run_goes_on(tiny_net):
     """edmp_sdf_goal_rows_dev between two segments of a segmented run: the run's result is bit-identical to the uninterrupted one, with an
     explicit target and with a derived one"""
-    from edmp_amd import _capi, scenes
-    from edmp_amd.diffusion import Diffusion
+    from edmp_amd import scenes
     from edmp_amd.guide import IntersectionVolumeGuide
-    from edmp_amd.runtime import ptr
 
     cfgs = I.mixed_cfgs(48)
     X8, _, s, gl = loop_inputs()
-    dif = Diffusion(T, DEV)
     rs = np.random.RandomState(11)
     for target in (I.pose_of(gl, "flange"), None):
         g = IntersectionVolumeGuide(scenes.random_scene(7, 8), DEV, cfgs, B, goal_tool="flange", goal_target=target)
-        ctx, lib = g.ctx, g.ctx.lib
-        z0 = ctx.to_dev(rs.standard_normal((1 + 4, B, 7, 50)), torch.float64)
-        z1 = ctx.to_dev(rs.standard_normal((4, B, 7, 50)), torch.float64)
-        sp, gp = _capi.as_pd(np.ascontiguousarray(s)), _capi.as_pd(np.ascontiguousarray(gl))
-
-        def run(between):
-            dif._prepare(tiny_net, g, B, cfgs["guidance_schedule"])
-            _capi.check(lib.edmp_sampler_set_condition(ctx.h, 1))
-            out = ctx.empty((B, 7, 50), torch.float64)
-            _capi.check(lib.edmp_denoise_guided_segment_dev(ctx.h, ptr(z0), B, sp, gp, 1, T, T - 4, 1, 1, None), "first segment")
-            mid = between()
-            rc = lib.edmp_denoise_guided_segment_dev(ctx.h, ptr(z1), B, sp, gp, 1, T - 4, T - 8, 0, 1, ptr(out))
-            msg = lib.edmp_last_error().decode() if rc else ""
-            ctx.sync()
-            return rc, msg, ctx.to_host(out), mid
-
-        rc, msg, whole, _ = run(lambda: None)
-        assert rc == 0, msg
-        rc, msg, cut, mid = run(lambda: g.sdf_goal_rows(X8[:, :, 1:-1]))
-        assert rc == 0, msg
-        assert np.isfinite(whole).all() and np.array_equal(whole, cut)
+        mid = suite.segmented_run_goes_on(tiny_net, g, cfgs, s, gl, rs, lambda: g.sdf_goal_rows(X8[:, :, 1:-1]))
         assert np.isfinite(mid["cost"]).all() and mid["cost"][list(I.GOAL_ROWS)].all()
 
 

@@ -7,7 +7,6 @@ as sdf_reference.clearance_gate).  Every comparison prints its error, yardstick 
 records are written there as JSON (profiles/sdf_sweep_parity.json comes from such a run).  Waypoints and interpolants sit >= 1e-5 m
 from every kink, so no element is excluded from any comparison."""
 import ctypes as C
-import math
 import os
 
 import numpy as np
@@ -17,18 +16,18 @@ import torch
 from tests import scene_sdf_inputs as SI
 from tests import sdf_reference as R
 from tests import sdf_sweep_inputs as I
-from tests.sdf_gpu import DEV, build_guide, gradient_and_sumsq, recorder
-from tests.util import TINY_DIMS, noise_for
+from tests import sdf_term_suite as suite
+from tests.sdf_gpu import DEV, build_guide, recorder, run_cfgs, tiny_net  # noqa: F401  (tiny_net: this module's fixture)
 
 pytestmark = pytest.mark.gpu
 T, B = I.T, I.B
 record, _write_records = recorder("sdf sweep parity", "EDMP_SDF_SWEEP_PARITY_OUT",
                                   "max(4 x CPU-float32 deviation from float64, 4 f32 ulps), relative to the largest element; clearance: absolute, "
                                   "floor 4 f32 ulps of the largest coordinate")
-
-
-def clearance_gate(y_abs, coord_max):
-    return max(R.GATE_FACTOR * y_abs, R.GATE_FLOOR * coord_max)
+TERM = suite.Term("sweep", I, guide=104, rows=I.SWEEP_ROWS, gradient_yardstick=lambda case: I.yardstick(case, I.T_CHECK)["grad"],
+                  report=lambda g, X, start, goal, t, substeps=None: g.sdf_sweep_rows(X, start, goal, t, substeps=substeps),
+                  gradient_record=lambda case: dict(substeps=list(case["K"]), active_share=case["marginst"]["active"]),
+                  report_steps=((0, dict(substeps=None)), (R.T_CHECK, dict(substeps=None)), (0, dict(substeps=3))))
 
 
 @pytest.mark.parametrize("t", [0, I.T_CHECK])
@@ -38,13 +37,13 @@ def test_cost_and_clearance_of_every_row(name, t):
     own weight and substeps; at t = 0 also substeps= on rows that are not the bound ones (weight 1)"""
     case = I.check_case(name)
     guide = build_guide(case)
-    assert guide.has_sweep_term
+    assert guide.has_term("sweep")
     ev = case["sweep0"] if t == 0 else case["sweept"]
     out = guide.sdf_sweep_rows(case["joints"], case["start"], case["goal"], t)
     y = I.yardstick(case, t)
     scale = float(np.abs(ev["cost"]).max())
     cost_err = float(np.abs(out["cost"] - ev["cost"]).max())
-    cgate = clearance_gate(y["clearance_abs"], ev["coord_max"])
+    cgate = R.clearance_gate(y["clearance_abs"], ev["coord_max"])
     clr_err = float(np.abs(out["clearance"] - ev["clearance"]).max())
     record(test="cost_clearance", case=name, t=t, cost_abs_err=cost_err, cost_scale=scale, cost_yardstick=y["cost"], cost_gate=R.gate(y["cost"]),
            clearance_abs_err=clr_err, clearance_yardstick_abs=y["clearance_abs"], clearance_gate_abs=cgate, min_clearance=float(ev["clearance"].min()))
@@ -62,9 +61,9 @@ def test_cost_and_clearance_of_every_row(name, t):
         yc = float(np.abs(b32["clearance"] - bare["clearance"]).max())
         berr, cerr = float(np.abs(sub["cost"] - bare["cost"]).max()), float(np.abs(sub["clearance"] - bare["clearance"]).max())
         record(test="cost_unbound_rows", case=name, substeps=K, cost_abs_err=berr, cost_scale=bscale, cost_yardstick=yb, cost_gate=R.gate(yb),
-               clearance_abs_err=cerr, clearance_gate_abs=clearance_gate(yc, bare["coord_max"]))
+               clearance_abs_err=cerr, clearance_gate_abs=R.clearance_gate(yc, bare["coord_max"]))
         assert berr <= R.gate(yb) * max(bscale, 1e-300), (berr, bscale, yb)
-        assert cerr <= clearance_gate(yc, bare["coord_max"]), cerr
+        assert cerr <= R.clearance_gate(yc, bare["coord_max"]), cerr
 
 
 def test_the_plate():
@@ -78,7 +77,7 @@ def test_the_plate():
     sw = swept.sdf_sweep_rows(*args, 0)["clearance"][0]
     also = plain.sdf_sweep_rows(p["joints"], p["start"], p["goal"], 0, substeps=I.PLATE_K)["clearance"][0]  # a guide without the term, the check's substeps handed in
     e32 = I.evaluate_sweep(*p["args"], np.zeros(1), np.ones(1), I.PLATE_K, dtype=torch.float32, want_grad=False)
-    cg = clearance_gate(abs(e32["clearance"][0] - p["sweep0"]["clearance"][0]), p["sweep0"]["coord_max"])
+    cg = R.clearance_gate(abs(e32["clearance"][0] - p["sweep0"]["clearance"][0]), p["sweep0"]["coord_max"])
     assert way > 0.07 and sw < -0.04 and also == sw
     assert abs(sw - p["sweep0"]["clearance"][0]) <= cg and abs(way - p["way0"]["clearance"][0]) <= R.GATE_FLOOR * p["way0"]["coord_max"] + cg
     G0 = plain.get_gradient(*args, I.T_CHECK)
@@ -99,50 +98,14 @@ def test_gradient_of_a_mixed_ensemble(name):
     """3. get_gradient on SDF + sweep (two rows, their own K), plain SDF, iv and sv rows, with and without grad_norm: the weighted rows
     against the checker (the normalising one un-normalised by the device's own sum g^2), bit-identical on a second call, every other row
     that does not normalise BIT-identical to the same ensemble built without the term"""
-    case = I.check_case(name)
-    t, cfgs = I.T_CHECK, case["cfgs"]
-    y = I.yardstick(case, t)
-    ref = I.total_gradient(case)
-    args = (case["joints"], case["start"], case["goal"], t)
-    G, sq = gradient_and_sumsq(build_guide(case), *args)
-    G_again, sq_again = gradient_and_sumsq(build_guide(case), *args)
-    G0, sq0 = gradient_and_sumsq(build_guide(case, cfgs=I.mixed_cfgs(case["K"], with_sweep=False)), *args)
-    assert G.shape == ref.shape and np.isfinite(G).all()
-    assert np.array_equal(G, G_again) and sq == sq_again  # one order of every sum
-    rows = list(I.SWEEP_ROWS)
-    scale = float(np.abs(ref[rows]).max())
-    err = {}
-    for r in rows:
-        raw = G[r] * float(np.float32(math.sqrt(sq))) if cfgs["grad_norm"][r] else G[r]
-        err[r] = float(np.abs(raw - ref[r]).max()) / scale
-    record(test="gradient", case=name, t=t, substeps=list(case["K"]), row_rel_err=err, yardstick=y["grad"], gate=R.gate(y["grad"]),
-           active_share=case["marginst"]["active"], sweep_share_of_gradient=float(np.abs(case["sweept"]["grad"][rows]).max() / scale))
-    for r in rows:
-        assert err[r] <= R.gate(y["grad"]), (r, err[r], y["grad"])
-        assert not np.array_equal(G[r], G0[r])  # the term does reach the row
-    assert sq != sq0
-    for r in range(B):
-        if r not in rows and not cfgs["grad_norm"][r]:
-            assert np.array_equal(G[r], G0[r]), r
+    suite.gradient_of_a_mixed_ensemble(TERM, record, name)
 
 
 @pytest.mark.parametrize("name", ["L1_o1_custom_K2", "L48_o64_default_K42", "L62_o7c2_default_K8"])
 def test_rowsq_is_the_sum_of_the_final_squares(name):
     """4. the sum g^2 the norm mixing reads, on an ensemble in which no row normalises (the returned gradient is the raw one): math.fsum
     of the returned squares to 8 x 2^-24 - seven f32 fmaf per lane, then f64 sums"""
-    case = I.check_case(name)
-    cfgs = I.mixed_cfgs(case["K"], grad_norm=False)
-    assert not cfgs["grad_norm"].any()
-    args = (case["joints"], case["start"], case["goal"], I.T_CHECK)
-    G, sq = gradient_and_sumsq(build_guide(case, cfgs=cfgs), *args)
-    G0, sq0 = gradient_and_sumsq(build_guide(case, cfgs=I.mixed_cfgs(case["K"], with_sweep=False, grad_norm=False)), *args)
-    want = math.fsum((G.astype(np.float64) ** 2).ravel().tolist())
-    rel = abs(sq - want) / want
-    record(test="rowsq", case=name, rel_err=rel, bound=8 * 2.0 ** -24)
-    assert rel <= 8 * 2.0 ** -24, (sq, want)
-    rows = list(I.SWEEP_ROWS)
-    others = [r for r in range(B) if r not in rows]
-    assert np.array_equal(G[others], G0[others]) and not np.array_equal(G[rows], G0[rows]) and sq != sq0
+    suite.rowsq_is_the_sum_of_the_final_squares(TERM, record, name)
 
 
 def test_ends():
@@ -176,175 +139,66 @@ def test_ends():
 
 
 # ---- runs --------------------------------------------------------------------------------------------------------------------------
-@pytest.fixture(scope="module")
-def tiny_net():
-    from edmp_amd import weights as W
-    from edmp_amd.temporalunet import TemporalUNet
-
-    return TemporalUNet(None, 7, 32, DEV, dims=TINY_DIMS, state_dict=W.init_state_dict(5, 7, 32, TINY_DIMS), max_batch=64)
-
-
-def with_104(guides):
-    return [104 if n == 101 else n for n in guides]
-
-
 def test_scene_batch_equals_serial_runs(tiny_net):
     """6. three scenes with guide 104 at different places (beside guide 13, whose rows normalise by the scene's ||g||): 24 guided steps of
     the batch equal each scene's serial run bit for bit, differ from the run without the term, and so does the report"""
-    from edmp_amd.diffusion import Diffusion
-    from edmp_amd.guide import IntersectionVolumeGuide, SceneBatch
-
-    parts = SI.scene_parts()
-    S, Bs, N = SI.S, SI.B, SI.N
-    cfgs = [SI.cfgs_for(with_104(p["guides"]), Bs // len(p["guides"])) for p in parts]
-    plain = [SI.cfgs_for(p["guides"], Bs // len(p["guides"])) for p in parts]
-    assert all(c["sdf_sweep_weight"].any() and "sdf_sweep_weight" not in q for c, q in zip(cfgs, plain))
-    mk = lambda cs: [IntersectionVolumeGuide(p["obstacle_config"], DEV, cs[s], Bs, obstacle_kinds=p["kinds"]) for s, p in enumerate(parts)]  # noqa: E731
-    guides, guides0 = mk(cfgs), mk(plain)
-    starts, goals = np.stack([p["start"] for p in parts]), np.stack([p["goal"] for p in parts])
-    noises = SI.noises()
-    dif, t_stop = Diffusion(T, DEV), T - 24
-    serial = lambda gs: [dif.denoise_guided(tiny_net, g, N, 7, g._sched, batch_size=Bs, start=starts[s], goal=goals[s], noise=noises[s], t_stop=t_stop)  # noqa: E731
-                         for s, g in enumerate(gs)]
-    ref, ref0 = serial(guides), serial(guides0)
-    batch = SceneBatch(guides)
-    assert batch.has_sweep_term
-    got = dif.denoise_guided_scenes(tiny_net, batch, N, 7, starts, goals, noise=noises, t_stop=t_stop)
-    for s in range(S):
-        assert np.isfinite(ref[s]).all() and np.array_equal(got[s], ref[s]), s
-        assert not np.array_equal(ref[s], ref0[s]), s  # the term moves the weighted rows
-    for t, K in ((0, None), (R.T_CHECK, None), (0, 3)):
-        rep = batch.sdf_sweep_rows(got, starts, goals, t, substeps=K)
-        assert rep["cost"].shape == (S, Bs)
-        for s in range(S):
-            one = guides[s].sdf_sweep_rows(got[s][:, :, 1:-1], starts[s], goals[s], t, substeps=K)
-            assert np.array_equal(rep["cost"][s], one["cost"]) and np.array_equal(rep["clearance"][s], one["clearance"]), (t, K, s)
-            assert np.isfinite(one["clearance"]).all()
-    # position independence: scene 1 alone in a batch of one
-    alone = dif.denoise_guided_scenes(tiny_net, SceneBatch([guides[1]]), N, 7, starts[1:2], goals[1:2], noise=[noises[1]], t_stop=t_stop)
-    assert np.array_equal(alone[0], ref[1])
-
-
-def run_cfgs(sdf_guide=104):
-    from edmp_amd import guide_cfg as GC
-
-    return GC.build_guide_cfgs([GC.load_guide_dict(n) for n in (1, sdf_guide, 13)], 4, T)
+    suite.scene_batch_equals_serial_runs(TERM, tiny_net)
 
 
 def test_device_loop_equals_the_stepwise_api(tiny_net):
     """7. six steps (three of them guided) of the device loop against edmp_step_a_dev / edmp_step_b_dev, guide 104 beside guides 1 and 13"""
-    from edmp_amd import scenes
-    from edmp_amd.diffusion import Diffusion, guided_step
-    from edmp_amd.guide import IntersectionVolumeGuide
-
-    cfgs = run_cfgs()
-    Bn = cfgs["total_batch_size"]
-    guide = IntersectionVolumeGuide(scenes.random_scene(7, 8), DEV, cfgs, Bn)
-    assert guide.has_sweep_term
-    dif = Diffusion(T, DEV)
-    noise = noise_for(4, Bn)
-    s, gl = scenes.DEFAULT_START, scenes.DEFAULT_GOAL
-    n = 6
-    assert sum(guided_step(t) for t in range(T, T - n, -1)) >= 1
-    X_loop = dif.denoise_guided(tiny_net, guide, 50, 7, cfgs["guidance_schedule"], batch_size=Bn, start=s, goal=gl, noise=noise, t_stop=T - n)
-    X = noise[0].copy()
-    X[:, :, 0], X[:, :, -1] = s, gl
-    for k, t in enumerate(range(T, T - n, -1)):
-        X = dif.denoise_step(tiny_net, guide, X, noise[1 + k], t, s, gl, cfgs["guidance_schedule"])["x_out"]
-    assert np.array_equal(X_loop, X)
+    suite.device_loop_equals_the_stepwise_api(TERM, tiny_net)
 
 
 def test_full_run_with_guide_104(tiny_net):
     """8. all 255 steps with guide 104 between guides 1 and 13: finite, bit-identical when repeated, not the run of guide 101 on guide
     104's rows and the same on guide 1's"""
-    from edmp_amd import scenes
-    from edmp_amd.diffusion import Diffusion
-    from edmp_amd.guide import IntersectionVolumeGuide
-
-    cfgs = run_cfgs()
-    Bn = cfgs["total_batch_size"]
-    scene, s, gl = scenes.random_scene(7, 8), scenes.DEFAULT_START, scenes.DEFAULT_GOAL
-    noise = noise_for(4, Bn)
-    dif = Diffusion(T, DEV)
-
-    def run(c):
-        guide = IntersectionVolumeGuide(scene, DEV, c, Bn)
-        return dif.denoise_guided(tiny_net, guide, 50, 7, c["guidance_schedule"], batch_size=Bn, start=s, goal=gl, noise=noise), guide
-
-    X1, guide = run(cfgs)
-    X2, _ = run(cfgs)
-    assert np.isfinite(X1).all() and np.array_equal(X1, X2)
-    X101, _ = run(run_cfgs(101))
-    assert not np.array_equal(X1[4:8], X101[4:8])
-    assert np.array_equal(X1[:4], X101[:4])  # guide 1 does not normalise: its rows do not see the term
-    rep = guide.sdf_sweep_rows(X1[:, :, 1:-1], s, gl, 0)
-    assert np.isfinite(rep["cost"]).all() and np.isfinite(rep["clearance"]).all() and not rep["cost"][:4].any()
+    suite.full_run(TERM, tiny_net)
 
 
 def test_a_segmented_run_goes_on(tiny_net):
     """8. a report call - with another start / goal pair than the run's - between two segments of a segmented run: the run's result is
     bit-identical to the uninterrupted one"""
-    from edmp_amd import _capi, scenes
-    from edmp_amd.diffusion import Diffusion
+    from edmp_amd import scenes
     from edmp_amd.guide import IntersectionVolumeGuide
-    from edmp_amd.runtime import ptr
 
-    cfgs = run_cfgs()
+    cfgs = run_cfgs(104)
     Bn = cfgs["total_batch_size"]
     s, gl = np.asarray(scenes.DEFAULT_START, dtype=np.float64), np.asarray(scenes.DEFAULT_GOAL, dtype=np.float64)
-    dif = Diffusion(T, DEV)
     rs = np.random.RandomState(11)
     g = IntersectionVolumeGuide(scenes.random_scene(7, 8), DEV, cfgs, Bn)
-    ctx, lib = g.ctx, g.ctx.lib
-    z0 = ctx.to_dev(rs.standard_normal((1 + 4, Bn, 7, 50)), torch.float64)
-    z1 = ctx.to_dev(rs.standard_normal((4, Bn, 7, 50)), torch.float64)
-    X = rs.uniform(-1, 1, (Bn, 7, 48))
-    sp, gp = _capi.as_pd(np.ascontiguousarray(s)), _capi.as_pd(np.ascontiguousarray(gl))
 
-    def run(between):
-        dif._prepare(tiny_net, g, Bn, cfgs["guidance_schedule"])
-        _capi.check(lib.edmp_sampler_set_condition(ctx.h, 1))
-        out = ctx.empty((Bn, 7, 50), torch.float64)
-        _capi.check(lib.edmp_denoise_guided_segment_dev(ctx.h, ptr(z0), Bn, sp, gp, 1, T, T - 4, 1, 1, None), "first segment")
-        mid = between()
-        rc = lib.edmp_denoise_guided_segment_dev(ctx.h, ptr(z1), Bn, sp, gp, 1, T - 4, T - 8, 0, 1, ptr(out))
-        msg = lib.edmp_last_error().decode() if rc else ""
-        ctx.sync()
-        return rc, msg, ctx.to_host(out), mid
+    def between():  # (called once, after the noise of both segments has been drawn from rs)
+        X = rs.uniform(-1, 1, (Bn, 7, 48))
+        return g.sdf_sweep_rows(X, gl, s, 0), g.sdf_sweep_rows(X[:3], gl, s, 0, substeps=5)
 
-    rc, msg, whole, _ = run(lambda: None)
-    assert rc == 0, msg
-    rc, msg, cut, mid = run(lambda: (g.sdf_sweep_rows(X, gl, s, 0), g.sdf_sweep_rows(X[:3], gl, s, 0, substeps=5)))
-    assert rc == 0, msg
-    assert np.isfinite(whole).all() and np.array_equal(whole, cut)
+    mid = suite.segmented_run_goes_on(tiny_net, g, cfgs, s, gl, rs, between)
     assert np.isfinite(mid[0]["clearance"]).all() and np.isfinite(mid[1]["clearance"]).all()
 
 
 def test_refusals():
     """9. every misuse is an error return whose message names the entry point, and the bound state is what it was"""
     from edmp_amd import _capi
-    from edmp_amd.guide import SceneBatch
     from edmp_amd.runtime import ptr
 
     case = I.check_case("L2_o7c2_default_K4")
     cfgs = case["cfgs"]
     args = (case["joints"], case["start"], case["goal"])
-    no_keys = {k: v for k, v in I.mixed_cfgs(case["K"], with_sweep=False).items() if k not in SI.SDF_KEYS}
+    no_keys = {k: v for k, v in I.mixed_cfgs(case, with_term=False).items() if k not in SI.SDF_KEYS}
     plain = build_guide(case, cfgs=no_keys)
     plain._bind()
     lib, h = plain.ctx.lib, plain.ctx.h
     w, k = np.ascontiguousarray(cfgs["sdf_sweep_weight"]), np.ascontiguousarray(cfgs["sdf_sweep_substeps"].astype(np.int32))
 
     def call(w_=w, k_=k, n=B):
-        rc = lib.edmp_sdf_set_sweep(h, _capi.as_pd(np.ascontiguousarray(w_)), _capi.as_pi32(np.ascontiguousarray(k_)), n)
-        return rc, (lib.edmp_last_error() or b"").decode()
+        return suite.setter_call(TERM, lib, h, _capi.as_pd(np.ascontiguousarray(w_)), _capi.as_pi32(np.ascontiguousarray(k_)), n)
 
     rc, msg = call()  # before edmp_sdf_set
     assert rc == -3 and msg.startswith("edmp_sdf_set_sweep") and "edmp_sdf_set" in msg, (rc, msg)
     guide = build_guide(case)
     guide._bind()
-    before = guide.sdf_sweep_rows(*args, I.T_CHECK)
-    G = guide.get_gradient(*args, I.T_CHECK)
+    state = lambda: suite.bound_state(guide, case, guide.sdf_sweep_rows(*args, I.T_CHECK))  # noqa: E731
+    before = state()
     w_bad = w.copy()
     w_bad[3] = 1.0  # an iv row
     k1, k65 = k.copy(), k.copy()
@@ -361,28 +215,19 @@ def test_refusals():
         guide.sdf_sweep_rows(*args, 0, substeps=65)
     with pytest.raises(_capi.EdmpError, match="edmp_sdf_sweep_rows_dev"):
         guide.sdf_sweep_rows(np.zeros((2, 7, 63)), case["start"], case["goal"], 0, substeps=4)
-    after = guide.sdf_sweep_rows(*args, I.T_CHECK)
-    assert np.array_equal(after["cost"], before["cost"]) and np.array_equal(after["clearance"], before["clearance"])
-    assert np.array_equal(guide.get_gradient(*args, I.T_CHECK), G)
+    suite.assert_state_is(state(), before)
     # a later edmp_sdf_set drops the term: the gradient is that of the ensemble without it, and the report asks for the row arrays again
-    guide._term_on["sweep"] = False
-    guide._set_sdf()
-    G0 = build_guide(case, cfgs=I.mixed_cfgs(case["K"], with_sweep=False)).get_gradient(*args, I.T_CHECK)
-    guide._bind()
-    assert np.array_equal(guide.get_gradient(*args, I.T_CHECK), G0)
+    suite.a_later_table_drops_the_term(TERM, guide, case, before[1])
     out = guide.ctx.empty((2, B), torch.float64)
     Xd = guide.ctx.to_dev(case["joints"], torch.float64)
     s7, g7 = _capi.as_pd(np.ascontiguousarray(case["start"])), _capi.as_pd(np.ascontiguousarray(case["goal"]))
     rc = lib.edmp_sdf_sweep_rows_dev(h, ptr(Xd), B, case["L"], 0, s7, g7, 0, C.c_void_p(out[0].data_ptr()), C.c_void_p(out[1].data_ptr()))
     assert rc == -3 and (lib.edmp_last_error() or b"").decode().startswith("edmp_sdf_sweep_rows_dev") and b"edmp_sdf_set_sweep" in lib.edmp_last_error()
     # in a batch the message names the scene and the row inside it
-    batch = SceneBatch([build_guide(case, bind=False), build_guide(case, bind=False)])
-    batch._bind()
-    rc = lib.edmp_sdf_set_sweep(h, _capi.as_pd(np.concatenate([w, w_bad])), _capi.as_pi32(np.concatenate([k, k])), 2 * B)
-    msg = (lib.edmp_last_error() or b"").decode()
+    suite.bind_a_batch_of_two(case)
+    rc, msg = call(w_=np.concatenate([w, w_bad]), k_=np.concatenate([k, k]), n=2 * B)
     assert rc == -1 and msg.startswith("edmp_sdf_set_sweep") and "scene 1, row 3" in msg, (rc, msg)
-    rc = lib.edmp_sdf_set_sweep(h, _capi.as_pd(np.concatenate([w, w])), _capi.as_pi32(np.concatenate([k, k65])), 2 * B)
-    msg = (lib.edmp_last_error() or b"").decode()
+    rc, msg = call(w_=np.concatenate([w, w]), k_=np.concatenate([k, k65]), n=2 * B)
     assert rc == -1 and "scene 1, row 1" in msg, (rc, msg)
 
 
