@@ -119,6 +119,8 @@ SIGNATURES = {
     "edmp_scenes_sdf_sweep_rows_dev": (_i, [_vp, _vp, _i, _i, _i, _i, _pd, _pd, _i, _vp, _vp]),
     "edmp_sdf_repair_rows_dev": (_i, [_vp, _vp, _i, _i, _pd, _pd, _pi32, _i, _i, _i, _d, _d, _d, _d, _vp, _vp, _vp]),
     "edmp_scenes_sdf_repair_rows_dev": (_i, [_vp, _vp, _i, _i, _i, _pd, _pd, _pi32, _i, _i, _i, _d, _d, _d, _d, _vp, _vp, _vp]),
+    "edmp_shortcut_rows_dev": (_i, [_vp, _vp, _i, _i, _pi32, _i, _i, _i, _d, _pd, _vp, _vp, _vp, _vp, _i]),
+    "edmp_scenes_shortcut_rows_dev": (_i, [_vp, _vp, _i, _i, _i, _pi32, _i, _i, _i, _d, _pd, _vp, _vp, _vp, _vp, _i]),
     "edmp_sdf_rows_dev": (_i, [_vp, _vp, _i, _i, _i, _pd, _pd, _vp, _vp]),
     "edmp_scene_batch_set_sdf": (_i, [_vp, _pf, _i, _pi32, _pd, _pd, _i, _i, _i]),
     "edmp_scenes_sdf_rows_dev": (_i, [_vp, _vp, _i, _i, _i, _i, _pd, _pd, _vp, _vp]),

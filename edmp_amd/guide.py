@@ -406,6 +406,29 @@ class _SlotObject:
         out.update({k: h[i // 2, :, i % 2].reshape(shape).copy() for i, k in enumerate(keys)})
         return out
 
+    def _shortcut(self, X, Xd, shape, N, passes, substeps, min_gain, rows, log_cap, return_device):
+        """shortcutting under the exact collision check of the (rows, 7, N) device state Xd (made from the caller's X) -> the shortcut dict,
+        per-row arrays `shape`d.  Always out of place: a device tensor of the caller's is cloned first, the kernel runs in place on the clone."""
+        ctx, n, cap = self.ctx, int(np.prod(shape)), int(log_cap)
+        with torch.cuda.stream(ctx.stream):
+            if isinstance(X, torch.Tensor) and X.is_cuda:
+                Xd = Xd.clone()  # (_rows_f64 hands an f64 contiguous device tensor through as it is)
+            counts = torch.zeros((2, n), dtype=torch.int32, device=ctx.device)  # rows outside `rows` are not written
+            length = torch.full((n, 2), float("nan"), dtype=torch.float64, device=ctx.device)
+            spans = torch.full((n, max(cap, 0), 2), -1, dtype=torch.int32, device=ctx.device)
+        listed = None if rows is None else np.ascontiguousarray(np.asarray(rows, dtype=np.int32).reshape(-1))
+        dh = np.ascontiguousarray(franka.dh_table_f64())
+        self._call("edmp_shortcut_rows_dev", "edmp_scenes_shortcut_rows_dev", shape, ptr(Xd), *shape, N, None if listed is None else _capi.as_pi32(listed),
+                   0 if listed is None else int(listed.shape[0]), int(substeps), int(passes), float(min_gain), _capi.as_pd(dh), C.c_void_p(counts[0].data_ptr()),
+                   C.c_void_p(counts[1].data_ptr()), ptr(length), ptr(spans) if cap > 0 else None, cap)
+        if return_device:
+            ctx.hand_over(Xd)  # (the caller's torch ops on the results follow this context's stream)
+            return dict(trajectories=Xd.view(*shape, 7, N), accepted=counts[0].view(*shape), tested=counts[1].view(*shape), length0=length[:, 0].view(*shape),
+                        length=length[:, 1].view(*shape), spans=spans.view(*shape, max(cap, 0), 2))
+        c, ln = ctx.to_host(counts), ctx.to_host(length)
+        return dict(trajectories=ctx.to_host(Xd).reshape(*shape, 7, N), accepted=c[0].reshape(shape).copy(), tested=c[1].reshape(shape).copy(),
+                    length0=ln[:, 0].reshape(shape).copy(), length=ln[:, 1].reshape(shape).copy(), spans=(ctx.to_host(spans) if cap > 0 else np.zeros((n, 0, 2), dtype=np.int32)).reshape(*shape, max(cap, 0), 2))
+
 
 class IntersectionVolumeGuide(_SlotObject):
     """Same constructor / method signatures as the reference:
@@ -698,6 +721,30 @@ class IntersectionVolumeGuide(_SlotObject):
         self._bind_sdf()
         return self._repair(trajectories, X, (X.shape[0],), X.shape[2], _pair7(start, goal), iters, substeps, margin, smoothness, step, max_step, rows,
                             return_device)
+
+    def shortcut_rows(self, trajectories, passes=2, substeps=4, min_gain=1e-6, rows=None, log_cap=128, return_device=False):
+        """Shortcut finished rows under the exact collision check (edmp_shortcut_rows_dev, csrc/shortcut.hip; one launch, one workgroup per
+        row for the whole run of the row): trajectories (n, 7, N) f64, ndarray or device tensor, 3 <= N <= 64, columns 0 and N-1 the pinned
+        start and goal.  Per pass the spans s = N-1, then (s+1)//2 down to 2, are walked from i = 0: where replacing the waypoints between
+        i and j = i + s by points of the joint-space chord x_i -> x_j shortens the joint path by more than ``min_gain`` [rad], the new piece
+        is tested with success_rows' own test at exactly the configurations success_rows will test on it - the new waypoints and the
+        ``substeps`` - 1 interpolants of each of its segments - and taken if nothing is hit (then i = j, else i + 1).  A pass that accepts
+        nothing ends the row; ``passes`` = 0 is a pure report, and more than 1024 passes (EDMP_MAX_SHORTCUT_PASSES, a cap so that a launch
+        stays bounded) are refused.  Consequences: the joint path length never grows; columns 0 and N-1 are
+        never written; waypoints are convex combinations of waypoints, so ``within`` cannot get worse; every configuration success_rows
+        (at the same ``substeps``) tests on the output is either unchanged or was tested, so ``first`` < 0 before implies ``first`` < 0
+        after; a colliding row may become free, when its colliding part lies inside an accepted span.  Self-collision is NOT part of the
+        test - a joint-space chord can fold the arm: self_collision_rows stays the check.  Returns dict(trajectories (n, 7, N), accepted and
+        tested (n,) int32 true counts of accepted spans and tested candidates, length0 / length (n,) f64 joint path length before / after
+        as an index-order sum, spans (n, log_cap, 2) int32 the first ``log_cap`` accepted (i, j) in order, the rest -1).  A row with a
+        non-finite element is left as it is: accepted = -1, NaN lengths.  ``rows``: the row indices to work on (any order, no duplicates);
+        the others keep their bits and report 0 and NaN.  Always out of place: the input is never modified.  Leaves a segmented run
+        running."""
+        X = self._rows_f64(trajectories)
+        if X.dim() != 3 or X.shape[1] != 7:
+            raise ValueError(f"trajectories must be (n, 7, N), got {tuple(X.shape)}")
+        self._bind()
+        return self._shortcut(trajectories, X, (X.shape[0],), X.shape[2], passes, substeps, min_gain, rows, log_cap, return_device)
 
     def row_swept_volumes(self, start, goal, trajectories):
         """(B,) f32 t=0 swept volume per row and the argmin (first on ties)."""
@@ -1093,6 +1140,17 @@ class SceneBatch(_SlotObject):
         Xd, N = self._state(trajectories)
         self._bind_sdf()
         out = self._repair(trajectories, Xd, (self.n_scenes, self.batch_size), N, pair, iters, substeps, margin, smoothness, step, max_step, rows, return_device)
+        Xd.record_stream(self.ctx.stream)
+        return out
+
+    def shortcut_rows(self, trajectories, passes=2, substeps=4, min_gain=1e-6, rows=None, log_cap=128, return_device=False):
+        """IntersectionVolumeGuide.shortcut_rows for every scene in one launch (edmp_scenes_shortcut_rows_dev): the (S, B, 7, N) /
+        (S*B, 7, N) state, each row against its own scene's obstacles and kinds -> the same dict with trajectories (S, B, 7, N), (S, B)
+        per-row arrays and spans (S, B, log_cap, 2); scene s's values are what guides[s].shortcut_rows gives for X[s].  ``rows`` indexes the
+        S*B rows scene after scene.  0 <= ``passes`` <= 1024 (EDMP_MAX_SHORTCUT_PASSES).  Out of place; leaves a segmented run running."""
+        Xd, N = self._state(trajectories)
+        self._bind()
+        out = self._shortcut(trajectories, Xd, (self.n_scenes, self.batch_size), N, passes, substeps, min_gain, rows, log_cap, return_device)
         Xd.record_stream(self.ctx.stream)
         return out
 

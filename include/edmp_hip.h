@@ -36,6 +36,7 @@ extern "C" {
 #define EDMP_MAX_SPHERES 128
 #define EDMP_MAX_SWEEP_SUBSTEPS 64 /* edmp_sdf_set_sweep: interpolants per segment + 1 */
 #define EDMP_MAX_REPAIR_ITERS 1024 /* edmp_sdf_repair_rows_dev: a cap so that a launch stays bounded, not a tuned value */
+#define EDMP_MAX_SHORTCUT_PASSES 1024 /* edmp_shortcut_rows_dev: a cap so that a launch stays bounded, not a tuned value */
 
 typedef struct edmp_ctx edmp_ctx;
 
@@ -284,6 +285,43 @@ int edmp_scene_set_shapes(edmp_ctx* ctx, const int32_t* kind, int n_obstacles);
  * 0/1.  counts_host (optional, synchronises): [rows ok, rows within limits, rows collision-free, B]. */
 int edmp_success_rows_dev(edmp_ctx* ctx, const double* X_dev, int B, int N, int substeps, const double* dh_f64, int32_t* ok_dev,
                           int32_t* first_dev, int32_t* within_dev, int32_t* counts_host);
+
+/* ---- shortcutting of finished rows under the exact collision check (csrc/shortcut.hip) ------------------------------------------ */
+/* The stage between repair and selection: one 256-thread workgroup per listed row for the whole run of the row (shortcut_rows_kernel; no
+ * launch per candidate).  X_dev (n, 7, N) f64 is updated IN PLACE; columns 0 and N-1 are the pinned start and goal and are never written.
+ * Per call: passes in 0..EDMP_MAX_SHORTCUT_PASSES, substeps K in 1..64, min_gain >= 0 [rad].  All arithmetic in f64, every operation of
+ * the gain and of the piece rounded on its own (no fused multiply-add).  The rule, per row x:
+ *   spans: s_0 = N - 1, s_{k+1} = (s_k + 1) / 2 (integer division), ending after the entry s = 2 (N = 50: 49, 25, 13, 7, 4, 2);
+ *   for each pass p = 0..passes-1, for each span s in that order: i = 0, and while i + s <= N - 1, with j = i + s:
+ *     gain = (sum_{m=i}^{j-1} |x_{m+1} - x_m|) - |x_j - x_i|, the norms over the seven joints (squares summed in joint order), the segment
+ *       lengths summed in index order; if not gain > min_gain: i += 1 and nothing is tested;
+ *     piece: y_m = x_i + ((double)(m - i) / (double)(j - i)) * (x_j - x_i) for m = i+1..j-1, y_i = x_i, y_j = x_j;
+ *     test: every configuration of the piece strictly between waypoint i and waypoint j as edmp_success_rows_dev forms them - y_m itself
+ *       and (1.0 - f) * y_m + f * y_{m+1}, f = (double)k / (double)K, k = 1..K-1, on every segment m = i..j-1 - against the scene's
+ *       obstacles by that check's own test (nine link boxes, 15-axis test for boxes, clipped-polytope test for cylinders, touching counts);
+ *     no hit: x_m <- y_m for m = i+1..j-1, the span (i, j) is logged, i = j; otherwise i += 1;
+ *   a pass that accepts nothing ends the row (a further pass would repeat it); passes = 0 is a pure report.
+ * So the joint path length never grows, waypoints only move to convex combinations of waypoints (the joint-limit flag cannot get worse),
+ * and every configuration the success check tests on the output is either unchanged or was tested here: a row with first < 0 before has
+ * first < 0 after.  A colliding row may become free, when its colliding part lies inside an accepted span.  Self-collision is NOT part
+ * of the test (a joint-space chord can fold the arm): edmp_self_collision_rows_dev stays the check.
+ * Outputs, written for the listed rows only: accepted_dev (n,) int32 accepted spans, tested_dev (n,) int32 tested candidates (true counts,
+ * not capped), length_dev (n, 2) f64 = the joint path length (the segment lengths summed in index order) before | after, spans_dev
+ * (n, log_cap, 2) int32 = the first log_cap accepted (i, j) in order, the rest -1 (log_cap = 0: not read, may be NULL).  A row with a
+ * non-finite element is not touched: accepted = -1, tested = 0, NaN lengths, a log of -1.  rows_host: n_rows row indices (host, any
+ * order, no duplicates), or NULL = every row (n_rows is ignored); a row outside the list keeps its bits in X and its report entries are
+ * not written.  dh_f64 as in edmp_success_rows_dev.  Rows are independent (no atomics, one order of every sum): a row's result depends
+ * on the row and its scene alone.  edmp_shortcut_rows_dev needs a single-scene guide, any n >= 1; edmp_scenes_shortcut_rows_dev a bound
+ * scene batch, X (S*B, 7, N), each row against its own scene's obstacles and kinds.  Refusals (3 <= N <= 64, K and passes in range,
+ * min_gain finite and >= 0, log_cap >= 0, rows in range and without duplicates, null pointers) come before any device call, name the
+ * offending value, and leave X, the outputs and the context untouched.  The calls read nothing of the sampler, replace no start / goal
+ * pair and do NOT end a segmented run.  They synchronise the stream (the list is read from the caller's array). */
+int edmp_shortcut_rows_dev(edmp_ctx* ctx, double* X_dev, int n, int N, const int32_t* rows_host, int n_rows, int substeps, int passes,
+                           double min_gain, const double* dh_f64, int32_t* accepted_dev, int32_t* tested_dev, double* length_dev,
+                           int32_t* spans_dev, int log_cap);
+int edmp_scenes_shortcut_rows_dev(edmp_ctx* ctx, double* X_dev, int S, int B, int N, const int32_t* rows_host, int n_rows, int substeps,
+                                  int passes, double min_gain, const double* dh_f64, int32_t* accepted_dev, int32_t* tested_dev,
+                                  double* length_dev, int32_t* spans_dev, int log_cap);
 
 /* ---- self-collision of every row (csrc/selfcol.hip) ------------------------------------------------------------- */
 /* Stands for the `self_collision` metric of the reference's evaluation package (mpinets/metrics.py:278-292, 351-361; a plan with

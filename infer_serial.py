@@ -135,7 +135,7 @@ def repair_tally(rep, iters, margin):
     return it > 0, (it >= 0) & ((it < int(iters)) | (clr >= float(np.float32(margin))))
 
 
-def job_summary(results, world=1, self_collision=False, repair=False):
+def job_summary(results, world=1, self_collision=False, repair=False, shortcut=False):
     """This rank's tallies; under a launcher the sum over all ranks (all_gather_object of five small integers per rank - the
     trajectories stay where they were planned).  Keys: scenes, success_proxy (the reference's tally), success_strict, rows_collision_free, rows."""
     mine = dict(scenes=len(results), success_proxy=sum(r["success_proxy"] for r in results), success_strict=sum(r["success_strict"] for r in results),
@@ -145,6 +145,8 @@ def job_summary(results, world=1, self_collision=False, repair=False):
         mine.update(self_collision_free=sum(r["self_collision_free"] for r in results), rows_self_collision_free=sum(r["rows_self_collision_free"] for r in results))
     if repair:  # (run(..., repair=ITERS): every rank's results carry the keys)
         mine.update(rows_repaired=sum(r["rows_repaired"] for r in results), rows_repair_clear=sum(r["rows_repair_clear"] for r in results))
+    if shortcut:  # (run(..., shortcut=PASSES): every rank's results carry the key)
+        mine.update(rows_shortcut=sum(r["rows_shortcut"] for r in results))
     if world <= 1:
         return dict(mine, ranks=1)
     import torch.distributed as dist
@@ -277,13 +279,13 @@ class _Path:
         return self.obj.ctx.to_host(X) if self.grouped else X[None]
 
     def timings(self):
-        order = (("noise_wait_s", "batch_metrics_s", "denoise_s", "repair_s", "denoise_s_is", "best_trajectory_s", "success_check_s") if self.grouped else
-                 ("noise_wait_s", "denoise_s", "repair_s", "best_trajectory_s", "batch_metrics_s", "success_check_s"))
+        order = (("noise_wait_s", "batch_metrics_s", "denoise_s", "repair_s", "shortcut_s", "denoise_s_is", "best_trajectory_s", "success_check_s") if self.grouped else
+                 ("noise_wait_s", "denoise_s", "repair_s", "shortcut_s", "best_trajectory_s", "batch_metrics_s", "success_check_s"))
         return {k: self.stamps[k] for k in order if k in self.stamps}
 
 
 def _score(job, on, X, starts, goals, tb):
-    """THE scoring step of both loops, from the end of the denoising loop (at time tb) to what _result writes down: repair -> select_row(s)
+    """THE scoring step of both loops, from the end of the denoising loop (at time tb) to what _result writes down: repair -> shortcut -> select_row(s)
     -> the metrics when the report wants them -> success_rows -> the chosen plans' sphere reports -> self_collision_rows, on the finished
     rows X of the path `on` (_Path).  Every call scores ALL rows of X - a group's (S, B, C, N) state stays on the device and is scored as
     one batch - but the chosen-plan reports, which the path says the rows of.  -> one record of scores per scene (the serial loop: one)."""
@@ -294,6 +296,13 @@ def _score(job, on, X, starts, goals, tb):
         X = rep["trajectories"]
         moved, clear = (on.scenes(a) for a in repair_tally(rep, job.repair, job.repair_margin))
         st["repair_s"] = time.time() - tb
+        tb = time.time()
+    cut = None
+    if job.shortcut:  # likewise one launch, after the repair and before the selection; everything behind it sees the shortened rows
+        sh = obj.shortcut_rows(X, passes=job.shortcut, substeps=CHECK_SUBSTEPS, log_cap=0, return_device=on.grouped)
+        X = sh["trajectories"]
+        cut = on.scenes(np.asarray(sh["accepted"].cpu() if isinstance(sh["accepted"], torch.Tensor) else sh["accepted"]) > 0)
+        st["shortcut_s"] = time.time() - tb
         tb = time.time()
     idx, vols, met = on.select(starts, goals, X, prefer=job.prefer)
     on.picked_at = tc = time.time()
@@ -324,7 +333,7 @@ def _score(job, on, X, starts, goals, tb):
     idx, vols, X, chk, met, selfcol, goal, chosen = on.scenes(idx), on.scenes(vols), on.host(X), lead(chk), lead(met), lead(selfcol), lead(goal), lead(chosen)
     return [SimpleNamespace(idx=int(i), vols=vols[s], trajectory=X[s][int(i)], met=of(met, s), selfcol=of(selfcol, s), chosen=of(chosen, s, place[s]), goal=of(goal, s, place[s]),
                             chk={k: (v if np.ndim(v) else int(v)) for k, v in of(chk, s).items()},  # (the per-row flags, and the scene's counts as ints)
-                            repair=None if moved is None else (moved[s], clear[s])) for s, i in enumerate(idx)]
+                            repair=None if moved is None else (moved[s], clear[s]), shortcut=None if cut is None else cut[s]) for s, i in enumerate(idx)]
 
 
 def _result(job, meta, tm, sc, t0, plan_end, wall_end=None, scenes_in_launch=None):
@@ -346,6 +355,8 @@ def _result(job, meta, tm, sc, t0, plan_end, wall_end=None, scenes_in_launch=Non
                  first_self_collision_waypoint=int(sc.selfcol["first"][idx]), self_collision_pair=None if a < 0 else [franka.LINK_NAMES[a], franka.LINK_NAMES[b]])
     if sc.repair is not None:  # repair: (moved, clear) of the scene's rows (repair_tally)
         r.update(rows_repaired=int(sc.repair[0].sum()), rows_repair_clear=int(sc.repair[1].sum()), repair_iters=int(job.repair))
+    if sc.shortcut is not None:  # shortcut: the scene's rows with at least one accepted span
+        r.update(rows_shortcut=int(sc.shortcut.sum()), shortcut_passes=int(job.shortcut))
     if job.prefer is not None:
         r["prefer"] = job.prefer
     if job.ensemble_report:
@@ -457,6 +468,8 @@ def _print_scene(r, n, tally, prefix=""):
         print(f"    chosen plan: position_error {r['position_error']:.3f} cm, orientation_error {r['orientation_error']:.3f} deg")
     if "rows_repaired" in r:
         print(f"    repair ({r['repair_iters']} iterations at most): {r['rows_repaired']}/{r['rows']} rows moved, {r['rows_repair_clear']}/{r['rows']} ended clear")
+    if "rows_shortcut" in r:
+        print(f"    shortcut ({r['shortcut_passes']} passes at most): {r['rows_shortcut']}/{r['rows']} rows shortened")
     if "self_collision_free" in r:
         print(f"    self-collision free {r['self_collision_free']} ({r['rows_self_collision_free']}/{r['rows']} rows of the batch)   running {tally.self_free}/{n}")
         if "ensemble" in r:
@@ -483,10 +496,12 @@ def _print_summary(summary):
         print(f"[infer_serial] self-collision free {summary['self_collision_free']}/{summary['scenes']}, rows {summary['rows_self_collision_free']}/{summary['rows']}")
     if "rows_repaired" in summary:
         print(f"[infer_serial] repair: {summary['rows_repaired']}/{summary['rows']} rows moved, {summary['rows_repair_clear']}/{summary['rows']} ended clear")
+    if "rows_shortcut" in summary:
+        print(f"[infer_serial] shortcut: {summary['rows_shortcut']}/{summary['rows']} rows shortened")
 
 
 def run(cfg_path, dataset=None, max_scenes=None, verbose=True, scenes_in_flight=1, shard_scenes=True, scenes_per_launch=1, ensemble_report=False, prefer=None,
-        ik_seeds=0, ik_tool=None, ik_seed=0, self_collision=False, device_noise=None, repair=0, repair_margin=0.02, repair_step=0.02):
+        ik_seeds=0, ik_tool=None, ik_seed=0, self_collision=False, device_noise=None, repair=0, repair_margin=0.02, repair_step=0.02, shortcut=0):
     """The reference's scene loop (infer_serial.py:95-170).  Under ``torch.distributed.run`` (one process per GPU, extension: the
     reference is one process) the scenes are dealt round-robin to the ranks - scene i of the cfg's order goes to rank i mod world -
     and nothing is exchanged until `job_summary` adds the tallies up: scenes are independent problems, this is the problem set's natural
@@ -549,7 +564,15 @@ def run(cfg_path, dataset=None, max_scenes=None, verbose=True, scenes_in_flight=
     a scene group through SceneBatch.repair_rows in one launch): at most ITERS projected descent steps of ``repair_step`` on the sphere
     model's hinge at ``repair_margin`` over the waypoints and the CHECK_SUBSTEPS - 1 interpolants per segment that the success check tests.
     Everything behind it sees the repaired rows.  Each result adds `rows_repaired` (rows that moved), `rows_repair_clear` (rows whose last
-    evaluation had no active hinge, repair_tally) and `repair_iters`; the per-scene line and the summary print the two counts."""
+    evaluation had no active hinge, repair_tally) and `repair_iters`; the per-scene line and the summary print the two counts.
+
+    ``shortcut`` = PASSES > 0 (an extension; 0 = off: nothing is launched and every printed and returned value is what it was) sends the
+    whole batch through shortcut_rows after the repair and before the selection (IntersectionVolumeGuide.shortcut_rows; a scene group
+    through SceneBatch.shortcut_rows in one launch): at most PASSES passes of joint-space shortcuts, each accepted only if the success
+    check's own test passes at the configurations the check will test on it (CHECK_SUBSTEPS), so a row that is collision-free stays so.
+    Self-collision is not part of that test: ``self_collision`` tallies after the stage.  Everything behind it sees the shortened rows.
+    Each result adds `rows_shortcut` (rows with an accepted span) and `shortcut_passes`, and `shortcut_s` to the timings; the per-scene
+    line and the summary print the count."""
     t_enter = time.time()
     kl = int(scenes_per_launch)
     if kl < 1:
@@ -559,6 +582,9 @@ def run(cfg_path, dataset=None, max_scenes=None, verbose=True, scenes_in_flight=
     repair = int(repair)
     if repair < 0:
         raise ValueError(f"repair must be >= 0 iterations (0 = off), got {repair}")
+    shortcut = int(shortcut)
+    if shortcut < 0:
+        raise ValueError(f"shortcut must be >= 0 passes (0 = off), got {shortcut}")
     if device_noise is not None:
         DeviceNoise(device_noise)  # (an integer in [0, 2^64), or it raises)
     cfg = GC.load_yaml(cfg_path)
@@ -575,7 +601,7 @@ def run(cfg_path, dataset=None, max_scenes=None, verbose=True, scenes_in_flight=
         total_batch_size=guide_cfgs["total_batch_size"], guide_numbers=guide_numbers,
         guide_rows=GC.split_rows(int(cfg["guide"]["total_rows"]), len(guide_numbers)) if cfg["guide"].get("total_rows") else guide_cfgs["batch_size_per_guide"],
         dataset=dataset, rank=rank, world=world, verbose=verbose, prefer=prefer, ensemble_report=ensemble_report, self_collision=self_collision, device_noise=device_noise,
-        repair=repair, repair_margin=repair_margin, repair_step=repair_step, ik_tool=ik_tool, iks=[], feeder=None, results=[], tally=SimpleNamespace(success=0, strict=0, self_free=0))
+        repair=repair, repair_margin=repair_margin, repair_step=repair_step, shortcut=shortcut, ik_tool=ik_tool, iks=[], feeder=None, results=[], tally=SimpleNamespace(success=0, strict=0, self_free=0))
     k = max(1, int(scenes_in_flight))
     base = get_context(device)
     job.lanes = _lanes(job, base, k, model["model_dir"], max_batch=job.total_batch_size * kl)
@@ -604,7 +630,7 @@ def run(cfg_path, dataset=None, max_scenes=None, verbose=True, scenes_in_flight=
         if job.feeder is not None:
             job.feeder.close()
     if world > 1 or verbose:
-        run.last_summary = job_summary(job.results, world, self_collision, bool(repair))
+        run.last_summary = job_summary(job.results, world, self_collision, bool(repair), bool(shortcut))
         if verbose and rank == 0:
             _print_summary(run.last_summary)
     return job.results
@@ -636,6 +662,9 @@ def main(argv=None):
                                                                                 "ITERS projected descent steps on the swept sphere-clearance cost (extension; 0 = off)")
     parser.add_argument("--repair-margin", type=float, default=0.02, help="the clearance [m] that the repair asks of every tested configuration")
     parser.add_argument("--repair-step", type=float, default=0.02, help="the repair's step size (a joint moves by at most 0.02 rad per iteration)")
+    parser.add_argument("--shortcut", type=int, default=0, metavar="PASSES", help="after the repair and before the selection, shorten every row of each batch by at most "
+                                                                                    "PASSES passes of joint-space shortcuts, each accepted only under the exact collision check "
+                                                                                    "(extension; 0 = off)")
     args = parser.parse_args(argv)
     ik_tool = args.ik_tool
     if ik_tool is not None and ik_tool not in ("flange", "hand"):
@@ -649,7 +678,7 @@ def main(argv=None):
         np.random.seed(args.seed + rank)
     results = run(args.cfg_path, scenes_in_flight=args.scenes_in_flight, max_scenes=args.max_scenes, scenes_per_launch=args.scenes_per_launch,
                   ensemble_report=args.ensemble_report, prefer=args.prefer, ik_seeds=args.ik_seeds, ik_tool=ik_tool, self_collision=args.self_collision,
-                  device_noise=args.device_noise, repair=args.repair, repair_margin=args.repair_margin, repair_step=args.repair_step)
+                  device_noise=args.device_noise, repair=args.repair, repair_margin=args.repair_margin, repair_step=args.repair_step, shortcut=args.shortcut)
     if args.results_json:
         rows = [{k: v for k, v in r.items() if k != "trajectory"} for r in results]
         with open(args.results_json + ("" if rank == 0 else f".rank{rank}"), "w") as f:
