@@ -5,31 +5,12 @@ import pytest
 
 from edmp_amd import franka, scenes
 from oracle import success_oracle as SO
+from tests.overlap_inputs import axis_distance_numeric as _axis_distance_numeric  # (it is the yardstick of test_overlap_host.py too)
 
 
 def _rand_rot(rs):
     q = rs.standard_normal(4)
     return SO.quat_xyzw_to_matrix(q / np.linalg.norm(q))
-
-
-def _axis_distance_numeric(Rb, cb, hb, Rc, cc, H):
-    """min over (box ∩ slab) of the distance to the cylinder axis, by SLSQP in box coordinates; None if the set is empty."""
-    from scipy.optimize import minimize
-
-    R = Rc.T @ Rb
-    t = Rc.T @ (cb - cc)
-    if abs(t[2]) > H + hb @ np.abs(R[2]):
-        return None
-    f = lambda u: float(np.sum((t + R @ u)[:2] ** 2))  # noqa: E731
-    g = lambda u: 2 * R[:2].T @ (t + R @ u)[:2]  # noqa: E731
-    cons = [{"type": "ineq", "fun": lambda u: H - (t + R @ u)[2], "jac": lambda u: -R[2]},
-            {"type": "ineq", "fun": lambda u: H + (t + R @ u)[2], "jac": lambda u: R[2]}]
-    best = None
-    for u0 in (np.zeros(3), hb * 0.9, -hb * 0.9):
-        r = minimize(f, u0, jac=g, bounds=[(-h, h) for h in hb], constraints=cons, method="SLSQP", options={"ftol": 1e-15, "maxiter": 300})
-        if r.success and (best is None or r.fun < best):
-            best = r.fun
-    return None if best is None else float(np.sqrt(max(best, 0.0)))
 
 
 def test_box_cylinder_against_numerical_minimisation():
