@@ -432,19 +432,56 @@ def sinusoidal_pos_emb(t: torch.Tensor, dim: int):
     return torch.cat((e.sin(), e.cos()), dim=-1)
 
 
-def _conv_block(sd, p, x):
+class ForwardObserver:
+    """Optional hooks into unet_forward for the tests that census or perturb a GroupNorm -> Mish epilogue (tests/hostile_weights.py).
+    ``gn_eps`` replaces GroupNorm's eps, ``mish_fn(x)`` replaces Mish, ``gn_fn(x, gamma, beta)`` the whole GroupNorm of a Conv1dBlock,
+    ``conv_fn(x, w, b)`` its k = 5 convolution; ``on_gn_input(name, x)`` / ``on_mish_input(name, x)`` see every
+    GroupNorm input (name = the Conv1dBlock's prefix) and every Mish input (a Conv1dBlock's prefix, "time_embedding" for the
+    Mish between the two embedding layers, "time_mlp" for the one every block's time MLP starts with).  Without an observer
+    unet_forward gives bit-identical results to the forward before there was one (tests/test_oracle_golden.py); the time MLP's Mish of
+    the embedding, the same in every block, is now evaluated once per forward."""
+
+    gn_eps = 1e-5
+    mish_fn = None
+    gn_fn = None
+    conv_fn = None
+
+    def on_gn_input(self, name, x):
+        pass
+
+    def on_mish_input(self, name, x):
+        pass
+
+
+def _mish(x, name, obs):
+    if obs is None:
+        return F.mish(x)
+    obs.on_mish_input(name, x)
+    return F.mish(x) if obs.mish_fn is None else obs.mish_fn(x)
+
+
+def _conv_block(sd, p, x, obs=None):
     """Conv1d(k, pad k//2) -> GroupNorm(8) -> Mish.  blocks.py:22-28"""
     w = sd[p + ".block.0.weight"]
-    x = F.conv1d(x, w, sd[p + ".block.0.bias"], padding=w.shape[-1] // 2)
-    x = F.group_norm(x, 8, sd[p + ".block.2.weight"], sd[p + ".block.2.bias"], eps=1e-5)
-    return F.mish(x)
+    if obs is None or obs.conv_fn is None:
+        x = F.conv1d(x, w, sd[p + ".block.0.bias"], padding=w.shape[-1] // 2)
+    else:
+        x = obs.conv_fn(x, w, sd[p + ".block.0.bias"])
+    if obs is not None:
+        obs.on_gn_input(p, x)
+    if obs is None or obs.gn_fn is None:
+        x = F.group_norm(x, 8, sd[p + ".block.2.weight"], sd[p + ".block.2.bias"], eps=1e-5 if obs is None else obs.gn_eps)
+    else:
+        x = obs.gn_fn(x, sd[p + ".block.2.weight"], sd[p + ".block.2.bias"])
+    return _mish(x, p, obs)
 
 
-def _rcb(sd, p, x, temb):
-    """ResidualConvolutionBlock.forward, blocks.py:154-166"""
-    tb = F.linear(F.mish(temb), sd[p + ".time_mlp.time_mlp.1.weight"], sd[p + ".time_mlp.time_mlp.1.bias"])
-    out = _conv_block(sd, p + ".blocks.0", x) + tb[:, :, None]
-    out = _conv_block(sd, p + ".blocks.1", out)
+def _rcb(sd, p, x, temb, obs=None):
+    """ResidualConvolutionBlock.forward, blocks.py:154-166 (``temb`` arrives with the time MLP's Mish applied: every block applies
+    the same one to the same embedding)"""
+    tb = F.linear(temb, sd[p + ".time_mlp.time_mlp.1.weight"], sd[p + ".time_mlp.time_mlp.1.bias"])
+    out = _conv_block(sd, p + ".blocks.0", x, obs) + tb[:, :, None]
+    out = _conv_block(sd, p + ".blocks.1", out, obs)
     if (p + ".residual_conv.weight") in sd:
         res = F.conv1d(x, sd[p + ".residual_conv.weight"], sd[p + ".residual_conv.bias"])
     else:
@@ -452,38 +489,40 @@ def _rcb(sd, p, x, temb):
     return out + res
 
 
-def unet_forward(sd, x: torch.Tensor, t: torch.Tensor, time_dim: int = 32, trace: dict | None = None):
+def unet_forward(sd, x: torch.Tensor, t: torch.Tensor, time_dim: int = 32, trace: dict | None = None, observer: ForwardObserver | None = None):
     """sd: state dict (names as in SURVEY.md §8a 'U'); x (B, C, N) f32; t (1,) f32 -> (B, C, N) f32."""
+    obs = observer
     n_down = 1 + max(int(k.split(".")[1]) for k in sd if k.startswith("down_samplers."))
     n_up = 1 + max(int(k.split(".")[1]) for k in sd if k.startswith("up_samplers."))
     temb = sinusoidal_pos_emb(t, time_dim)
     temb = F.linear(temb, sd["time_embedding.time_mlp.1.weight"], sd["time_embedding.time_mlp.1.bias"])
-    temb = F.linear(F.mish(temb), sd["time_embedding.time_mlp.3.weight"], sd["time_embedding.time_mlp.3.bias"])
+    temb = F.linear(_mish(temb, "time_embedding", obs), sd["time_embedding.time_mlp.3.weight"], sd["time_embedding.time_mlp.3.bias"])
+    temb = _mish(temb, "time_mlp", obs)
     hs = []
     for i in range(n_down):
         p = f"down_samplers.{i}.down"
-        x = _rcb(sd, p + ".0", x, temb)
-        x = _rcb(sd, p + ".1", x, temb)
+        x = _rcb(sd, p + ".0", x, temb, obs)
+        x = _rcb(sd, p + ".1", x, temb, obs)
         hs.append(x)
         if (p + ".3.weight") in sd:
             x = F.conv1d(x, sd[p + ".3.weight"], sd[p + ".3.bias"], stride=2, padding=1)
         if trace is not None:
             trace[f"down{i}"] = x.clone()
-    x = _rcb(sd, "middle_block.middle.0", x, temb)
-    x = _rcb(sd, "middle_block.middle.2", x, temb)
+    x = _rcb(sd, "middle_block.middle.0", x, temb, obs)
+    x = _rcb(sd, "middle_block.middle.2", x, temb, obs)
     if trace is not None:
         trace["mid"] = x.clone()
     for i in range(n_up):
         p = f"up_samplers.{i}.up"
         x = torch.cat([x, hs.pop()], dim=1)
-        x = _rcb(sd, p + ".0", x, temb)
-        x = _rcb(sd, p + ".1", x, temb)
+        x = _rcb(sd, p + ".0", x, temb, obs)
+        x = _rcb(sd, p + ".1", x, temb, obs)
         x = F.conv_transpose1d(x, sd[p + ".3.weight"], sd[p + ".3.bias"], stride=2, padding=1)
         if x.shape[2] in (8, 14, 26):  # temporalunet.py:70-71
             x = x[:, :, : x.shape[2] - 1]
         if trace is not None:
             trace[f"up{i}"] = x.clone()
-    x = _conv_block(sd, "final_conv.0", x)
+    x = _conv_block(sd, "final_conv.0", x, obs)
     return F.conv1d(x, sd["final_conv.1.weight"], sd["final_conv.1.bias"])
 
 

@@ -14,6 +14,8 @@ import numpy as np
 import pytest
 import torch
 
+from tests.taps import missing_tap_explained as _missing_tap_explained
+from tests.taps import tap_key as _tap_key
 from tests.util import T, cfgs_for, maxabs, rmse
 from tests.util import f64_error_ratio as _ratio
 
@@ -97,22 +99,6 @@ def _refs(aid):
         out[t] = (y32, {k: v.numpy() for k, v in tr32.items()}, y64, {k: v.numpy() for k, v in tr64.items()})
     _REFS[aid] = (x, out)
     return _REFS[aid]
-
-
-def _tap_key(which):
-    return "mid" if which == 100 else f"down{which}" if which < 100 else f"up{which - 200}"
-
-
-def _missing_tap_explained(which, n_levels, names):
-    """a tap the program has no HBM copy of: level 0's output handed to level 1 in LDS (level2_kernel bit 0), the up level merged
-    into the last one (bit 1), and the last up level itself (its output feeds final_conv.0 inside the same launch)"""
-    if which == 0:
-        return any(s.startswith("level2_kernel<0") for s in names)
-    if which == 200 + n_levels - 3:
-        return any(s.startswith("level2_kernel<1") for s in names)
-    if which == 200 + n_levels - 2:
-        return any(s.startswith("level_kernel<2") or s.startswith("level2_kernel<1") for s in names)
-    return False
 
 
 def _sweep(aid, net, tag):
