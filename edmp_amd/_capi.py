@@ -14,6 +14,7 @@ MAX_OBSTACLES = 64  # EDMP_MAX_OBSTACLES
 MAX_SPHERES = 128  # EDMP_MAX_SPHERES
 MAX_SWEEP_SUBSTEPS = 64  # EDMP_MAX_SWEEP_SUBSTEPS
 MAX_REPAIR_ITERS = 1024  # EDMP_MAX_REPAIR_ITERS
+MAX_TIMED_SAMPLES = 1048576  # EDMP_MAX_TIMED_SAMPLES
 
 
 class UNetDesc(C.Structure):
@@ -121,6 +122,8 @@ SIGNATURES = {
     "edmp_scenes_sdf_repair_rows_dev": (_i, [_vp, _vp, _i, _i, _i, _pd, _pd, _pi32, _i, _i, _i, _d, _d, _d, _d, _vp, _vp, _vp]),
     "edmp_shortcut_rows_dev": (_i, [_vp, _vp, _i, _i, _pi32, _i, _i, _i, _d, _pd, _vp, _vp, _vp, _vp, _i]),
     "edmp_scenes_shortcut_rows_dev": (_i, [_vp, _vp, _i, _i, _i, _pi32, _i, _i, _i, _d, _pd, _vp, _vp, _vp, _vp, _i]),
+    "edmp_time_rows_dev": (_i, [_vp, _vp, _i, _i, _pd, _pd, _pd, _vp, _vp, _vp, _vp, _vp, _vp]),
+    "edmp_sample_rows_dev": (_i, [_vp, _vp, _i, _i, _vp, _vp, _vp, _vp, _vp, _pi32, _i, _d, _i, _vp, _vp, _vp]),
     "edmp_sdf_rows_dev": (_i, [_vp, _vp, _i, _i, _i, _pd, _pd, _vp, _vp]),
     "edmp_scene_batch_set_sdf": (_i, [_vp, _pf, _i, _pi32, _pd, _pd, _i, _i, _i]),
     "edmp_scenes_sdf_rows_dev": (_i, [_vp, _vp, _i, _i, _i, _i, _pd, _pd, _vp, _vp]),

@@ -204,6 +204,140 @@ def batch_metrics(trajectories, device="cuda:0", dt: float = 0.1, return_device:
     return metrics_rows_on(get_context(device), trajectories, dt, return_device)
 
 
+PROFILE_KEYS = ("y", "phase", "times", "duration", "limit", "seg")  # edmp_time_rows_dev's outputs, what edmp_sample_rows_dev reads
+LIMIT_NAMES = ("rest", "velocity_before", "velocity_after", "corner_jump", "acceleration", "deceleration")  # the codes of `limit`
+
+
+def _rows_state(ctx, trajectories):
+    """(n, 7, N) ndarray or device tensor -> the contiguous f64 device tensor on ctx's stream"""
+    import torch
+
+    if isinstance(trajectories, torch.Tensor) and trajectories.is_cuda:
+        X = ctx.adopt(trajectories.to(torch.float64).contiguous())
+    else:
+        X = ctx.to_dev(np.asarray(trajectories, dtype=np.float64), torch.float64)
+    if X.dim() != 3 or X.shape[1] != 7:
+        raise ValueError(f"trajectories must be (n, 7, N), got {tuple(X.shape)}")
+    return X
+
+
+def time_rows_on(ctx, trajectories, vmax=None, amax=None, jump=None, scale=(1, 1), return_device: bool = False) -> dict:
+    """edmp_time_rows_dev on the context `ctx` (runtime.Context): see time_rows."""
+    import torch
+
+    from . import _capi
+    from .runtime import ptr
+
+    vm, am, jm = franka.timing_limits(vmax, amax, jump, scale)
+    X = _rows_state(ctx, trajectories)
+    n, N = X.shape[0], X.shape[2]
+    out = dict(y=ctx.empty((n, N), torch.float64), phase=ctx.empty((n, max(N - 1, 0), 3), torch.float64), times=ctx.empty((n, N), torch.float64),
+               duration=ctx.empty((n,), torch.float64), limit=ctx.empty((n, N), torch.int32), seg=ctx.empty((n, max(N - 1, 0), 2), torch.float64))
+    _capi.check(ctx.lib.edmp_time_rows_dev(ctx.h, ptr(X), n, N, _capi.as_pd(vm), _capi.as_pd(am), _capi.as_pd(jm), *(ptr(out[k]) for k in PROFILE_KEYS)),
+                "edmp_time_rows_dev")
+    if return_device:
+        X.record_stream(ctx.stream)  # (the kernel may still be reading it when the caller drops the tensor)
+        for k in PROFILE_KEYS:
+            ctx.hand_over(out[k])
+    else:
+        out = {k: ctx.to_host(out[k]) for k in PROFILE_KEYS}
+    out.update(vmax=vm, amax=am, jump=jm)
+    return out
+
+
+def time_rows(trajectories, vmax=None, amax=None, jump=None, scale=(1, 1), device="cuda:0", return_device: bool = False) -> dict:
+    """Time EVERY finished row under joint velocity, acceleration and corner velocity-jump limits (edmp_time_rows_dev, csrc/timing.hip; the
+    reference replays its plans at constant velocity and ships no timing): trajectories (n, 7, N) ndarray or device tensor, 2 <= N <= 64 ->
+    the profile of the fastest rest-to-rest motion ALONG each row's polyline: dict(y (n, N) = squared path speed at the waypoints, phase
+    (n, N-1, 3) = accelerate | cruise | decelerate times of each segment [s], times (n, N) waypoint times, duration (n,) [s], limit (n, N)
+    int32 = the constraint that binds each waypoint (index into LIMIT_NAMES), seg (n, N-1, 2) = path acceleration | peak squared speed of
+    each segment; device tensors with return_device) plus the limits used, vmax / amax / jump (7,).  Limits: franka.timing_limits - Franka's
+    published joint velocity and acceleration limits times scale = (sv, sa), and an illustrative corner jump of amax * 1 ms.  The rule is
+    stated in include/edmp_hip.h.  |qdot| <= vmax everywhere, |qddot| <= amax inside segments, the velocity jump at a corner <= jump, and
+    the path is the input polyline: what success_rows, self_collision_rows and shortcut_rows said of the row holds for the timed motion.  A
+    row with a non-finite element is not timed (NaN, limit -1).  Needs no scene and no guide.  Runs on the GPU only."""
+    from .runtime import get_context
+
+    return time_rows_on(get_context(device), trajectories, vmax, amax, jump, scale, return_device)
+
+
+def sample_count(duration, period) -> int:
+    """1 + the smallest k with float(k) * period >= duration: the samples of a row up to and including the first one at rest at the goal
+    (edmp_sample_rows_dev states its count the same way); 0 for a row that was not timed"""
+    duration, period = float(duration), float(period)
+    if not np.isfinite(duration):
+        return 0
+    k = int(np.ceil(duration / period))
+    while k > 0 and float(k - 1) * period >= duration:
+        k -= 1
+    while float(k) * period < duration:
+        k += 1
+    return 1 + k
+
+
+def sample_rows_on(ctx, trajectories, profile, period, rows=None, max_samples=None, return_device: bool = False) -> dict:
+    """edmp_sample_rows_dev on the context `ctx` (runtime.Context): see sample_rows."""
+    import torch
+
+    from . import _capi
+    from .runtime import ptr
+
+    period = float(period)
+    if not (np.isfinite(period) and period > 0):
+        raise ValueError(f"period must be finite and > 0, got {period!r}")
+    X = _rows_state(ctx, trajectories)
+    n, N = X.shape[0], X.shape[2]
+    prof = {}
+    for k in ("y", "phase", "times", "duration", "seg"):  # (limit is a report, the sampler does not read it)
+        v = profile[k]
+        t = ctx.adopt(v.to(torch.float64).contiguous()) if isinstance(v, torch.Tensor) and v.is_cuda else ctx.to_dev(np.asarray(v, dtype=np.float64), torch.float64)
+        want = dict(y=(n, N), phase=(n, N - 1, 3), times=(n, N), duration=(n,), seg=(n, N - 1, 2))[k]
+        if tuple(t.shape) != want:
+            raise ValueError(f"profile[{k!r}] must be {want} for trajectories {tuple(X.shape)}, got {tuple(t.shape)}")
+        prof[k] = t
+    listed = None if rows is None else np.ascontiguousarray(np.asarray(rows, dtype=np.int32).reshape(-1))
+    if listed is not None and listed.size and (listed.min() < 0 or listed.max() >= n):
+        raise ValueError(f"rows must lie in 0..{n - 1}, got {listed.tolist()}")
+    dur = profile["duration"]
+    dur = (ctx.to_host(dur) if isinstance(dur, torch.Tensor) else np.asarray(dur, dtype=np.float64)).reshape(-1)
+    order = np.arange(n) if listed is None else listed
+    counts = [sample_count(dur[r], period) for r in order]
+    if max_samples is None:
+        M = max(1, max(counts, default=1))
+    else:
+        M = int(max_samples)
+        short = [(int(r), c) for r, c in zip(order, counts) if c > M]
+        if short:
+            raise ValueError(f"max_samples = {M} is smaller than the {short[0][1]} samples of row {short[0][0]}")
+    R = int(order.shape[0])
+    with torch.cuda.stream(ctx.stream):
+        q = torch.empty((R, 7, max(M, 0)), dtype=torch.float64, device=ctx.device)
+        qd = torch.empty_like(q)
+        count = torch.empty((R,), dtype=torch.int32, device=ctx.device)
+    _capi.check(ctx.lib.edmp_sample_rows_dev(ctx.h, ptr(X), n, N, ptr(prof["y"]), ptr(prof["phase"]), ptr(prof["times"]), ptr(prof["duration"]), ptr(prof["seg"]),
+                                             None if listed is None else _capi.as_pi32(listed), 0 if listed is None else R, period, M, ptr(q), ptr(qd), ptr(count)),
+                "edmp_sample_rows_dev")
+    t = np.arange(M, dtype=np.float64) * period
+    if return_device:
+        for v in (q, qd, count):
+            ctx.hand_over(v)
+        return dict(q=q, qd=qd, count=count, t=t)
+    return dict(q=ctx.to_host(q), qd=ctx.to_host(qd), count=ctx.to_host(count), t=t)
+
+
+def sample_rows(trajectories, profile, period, rows=None, max_samples=None, device="cuda:0", return_device: bool = False) -> dict:
+    """The timed motion of the listed rows at a controller period (edmp_sample_rows_dev, csrc/timing.hip): trajectories (n, 7, N) and the
+    `profile` time_rows gave for them, period [s] -> dict(q (R, 7, M) joint positions and qd (R, 7, M) joint velocities at t = k * period,
+    count (R,) int32 = the samples of each row up to and including the first at rest at the goal (sample_count), t (M,)).  ``rows``: row
+    indices in any order without duplicates, default every row; slot k of the outputs belongs to rows[k].  ``max_samples`` = M defaults to
+    the largest count of the listed rows; a smaller value is refused, naming the row; more than 1048576 (EDMP_MAX_TIMED_SAMPLES) are refused
+    by the library.  Every sample lies on its segment of the polyline; samples at or past count - 1 are the goal column bit for bit, at
+    rest.  A row that was not timed gives NaN samples and count 0.  Runs on the GPU only."""
+    from .runtime import get_context
+
+    return sample_rows_on(get_context(device), trajectories, profile, period, rows, max_samples, return_device)
+
+
 def ensemble_report(guides, batch_size_per_guide, volumes, success, metrics) -> list:
     """Which guide of the ensemble produced collision-free, short, smooth plans: one entry per guide slice of the batch.  Guide i of
     `guides` (the run cfg's guide numbers) owns rows [i * bpg, (i + 1) * bpg) (infer_serial.py:70-91); `batch_size_per_guide` may also

@@ -113,6 +113,28 @@ def joint_limits():
     return lo, hi
 
 
+# Franka's published interface limits (Franka Control Interface documentation, "Robot and interface specifications", joint space limits
+# of the Panda): the defaults of the time parameterisation (evaluation.time_rows, csrc/timing.hip).  The reference has no such table.
+JOINT_VELOCITY_LIMITS = (2.175, 2.175, 2.175, 2.175, 2.61, 2.61, 2.61)  # rad/s
+JOINT_ACCELERATION_LIMITS = (15.0, 7.5, 10.0, 12.5, 15.0, 20.0, 20.0)  # rad/s^2
+CONTROL_PERIOD = 1e-3  # s: the 1 kHz control loop
+
+
+def timing_limits(vmax=None, amax=None, jump=None, scale=(1.0, 1.0)):
+    """(vmax, amax, jump), each (7,) float64, as edmp_time_rows_dev takes them.  vmax / amax default to the tables above and are multiplied
+    by scale = (sv, sa).  jump, the velocity change allowed at a corner of the polyline, defaults to JOINT_ACCELERATION_LIMITS * 1e-3 - what
+    one 1 kHz control period may carry at full acceleration; an ILLUSTRATIVE value, not a published one, and not scaled."""
+    sv, sa = (float(s) for s in scale)
+    out = []
+    for name, v, default, s in (("vmax", vmax, JOINT_VELOCITY_LIMITS, sv), ("amax", amax, JOINT_ACCELERATION_LIMITS, sa),
+                                ("jump", jump, [a * CONTROL_PERIOD for a in JOINT_ACCELERATION_LIMITS], 1.0)):
+        arr = np.ascontiguousarray(np.asarray(default if v is None else v, dtype=np.float64) * s)
+        if arr.shape != (7,) or not np.all(np.isfinite(arr)) or not np.all(arr > 0):
+            raise ValueError(f"{name} must be 7 finite values > 0, got {arr!r}")
+        out.append(arr)
+    return tuple(out)
+
+
 # PLACEHOLDER (see module docstring): (l, b, h) mesh AABB extents for link1..link7, hand, finger, finger y BEFORE x4
 PLACEHOLDER_LINK_EXTENTS = np.array(
     [

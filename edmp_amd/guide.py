@@ -251,12 +251,15 @@ class _SlotObject:
     def _pick(self, Xd, vols, shape, prefer, volume_trust_region):
         """the trust-region pick among the rows of each scene -> (indices (S,) int64, volumes f32, metrics dict of f64, both `shape`d);
         volumes, metrics and the pick stay on the device, the indices come back"""
-        from .evaluation import metrics_rows_on
+        from .evaluation import metrics_rows_on, time_rows_on
 
         ctx = self.ctx
         met = metrics_rows_on(ctx, Xd, return_device=True)
-        with torch.cuda.stream(ctx.stream):
-            key = met["joint_path_length"] if prefer == "shortest" else torch.neg(met["joint_sparc"])  # SPARC <= 0: closest to 0 = largest
+        if prefer == "fastest":  # the duration of the timed motion at the default limits (csrc/timing.hip); NaN for a row that was not timed
+            key = time_rows_on(ctx, Xd, return_device=True)["duration"]
+        else:
+            with torch.cuda.stream(ctx.stream):
+                key = met["joint_path_length"] if prefer == "shortest" else torch.neg(met["joint_sparc"])  # SPARC <= 0: closest to 0 = largest
         idx = (C.c_int * (shape[0] if len(shape) == 2 else 1))()
         self._call("edmp_select_row_dev", "edmp_scenes_select_rows_dev", shape, ptr(vols), ptr(key), *shape, C.c_double(float(volume_trust_region)), idx)
         with torch.cuda.stream(ctx.stream):
@@ -788,18 +791,34 @@ class IntersectionVolumeGuide(_SlotObject):
 
         return metrics_rows_on(self.ctx, trajectories, dt, return_device)
 
+    def time_rows(self, trajectories, vmax=None, amax=None, jump=None, scale=(1, 1), return_device: bool = False):
+        """evaluation.time_rows on this guide's context: the fastest rest-to-rest motion along every row's polyline under joint velocity,
+        acceleration and corner velocity-jump limits (edmp_time_rows_dev, csrc/timing.hip) -> the profile dict.  Reads nothing of the
+        scene; leaves a segmented run running."""
+        from .evaluation import time_rows_on
+
+        return time_rows_on(self.ctx, trajectories, vmax, amax, jump, scale, return_device)
+
+    def sample_rows(self, trajectories, profile, period, rows=None, max_samples=None, return_device: bool = False):
+        """evaluation.sample_rows on this guide's context: the timed motion of the listed rows at a controller period
+        (edmp_sample_rows_dev) -> dict(q, qd (R, 7, M), count (R,), t (M,)).  Leaves a segmented run running."""
+        from .evaluation import sample_rows_on
+
+        return sample_rows_on(self.ctx, trajectories, profile, period, rows, max_samples, return_device)
+
     def select_row(self, start, goal, trajectories, prefer=None, volume_trust_region: float = 0.0008):
         """The row choose_best_trajectory returns, as (index, volumes (B,) f32, metrics dict or None).  prefer=None: the reference's
         rule, the first arg-min of the t = 0 swept volume (lib/guide.py:637-653) - row_swept_volumes' index, nothing else is launched.
         prefer="shortest" / "smoothest": the rule of the reference's IK-goal filter (infer_serial.py:119-129) applied to the plans -
         among the rows whose volume lies within `volume_trust_region` of the minimum, the one with the smallest joint path length /
         the joint SPARC closest to 0 (edmp_select_row_dev on edmp_metrics_rows_dev's output; volumes, metrics and the pick stay on the
-        device, one index comes back)."""
+        device, one index comes back).  prefer="fastest": the same pick with the key = the duration of the row's timed motion at the default
+        limits (evaluation.time_rows); a row that was not timed has a non-finite key and is passed over."""
         if prefer is None:
             vols, idx = self.row_swept_volumes(start, goal, trajectories)
             return idx, vols, None
-        if prefer not in ("shortest", "smoothest"):
-            raise ValueError(f"prefer must be None, 'shortest' or 'smoothest', got {prefer!r}")
+        if prefer not in ("shortest", "smoothest", "fastest"):
+            raise ValueError(f"prefer must be None, 'shortest', 'smoothest' or 'fastest', got {prefer!r}")
         self._bind()
         X = self._rows_f64(trajectories)
         vols, _ = self._swept(X, (X.shape[0],), X.shape[2], _pair7(start, goal), False)
@@ -1065,10 +1084,10 @@ class SceneBatch(_SlotObject):
 
     def select_rows(self, starts, goals, trajectories, prefer=None, volume_trust_region: float = 0.0008):
         """IntersectionVolumeGuide.select_row for every scene of the batch: (indices (S,) inside the scene, volumes (S, B) f32, metrics
-        dict of (S, B) f64 arrays or None).  prefer=None: the first arg-min per scene; "shortest" / "smoothest": the trust-region pick
-        (edmp_scenes_select_rows_dev on ONE edmp_metrics_rows_dev call over the S*B rows)."""
-        if prefer not in (None, "shortest", "smoothest"):
-            raise ValueError(f"prefer must be None, 'shortest' or 'smoothest', got {prefer!r}")
+        dict of (S, B) f64 arrays or None).  prefer=None: the first arg-min per scene; "shortest" / "smoothest" / "fastest": the trust-region
+        pick (edmp_scenes_select_rows_dev on ONE edmp_metrics_rows_dev - for "fastest" also ONE edmp_time_rows_dev - call over the S*B rows)."""
+        if prefer not in (None, "shortest", "smoothest", "fastest"):
+            raise ValueError(f"prefer must be None, 'shortest', 'smoothest' or 'fastest', got {prefer!r}")
         ctx, S, B = self.ctx, self.n_scenes, self.batch_size
         Xd, vols, idx = self._volumes(starts, goals, trajectories, prefer is None)
         if prefer is None:
@@ -1153,6 +1172,28 @@ class SceneBatch(_SlotObject):
         out = self._shortcut(trajectories, Xd, (self.n_scenes, self.batch_size), N, passes, substeps, min_gain, rows, log_cap, return_device)
         Xd.record_stream(self.ctx.stream)
         return out
+
+    def time_rows(self, trajectories, vmax=None, amax=None, jump=None, scale=(1, 1), return_device: bool = False):
+        """IntersectionVolumeGuide.time_rows for the (S, B, 7, N) / (S*B, 7, N) state in ONE launch (a reshape: the rule reads nothing of a
+        scene) -> the profile dict with every array shaped (S, B, ...); scene s's values are bit for bit what guides[s].time_rows gives for
+        X[s].  Leaves a segmented run running."""
+        from .evaluation import PROFILE_KEYS, time_rows_on
+
+        Xd, N = self._state(trajectories)
+        out = time_rows_on(self.ctx, Xd, vmax, amax, jump, scale, return_device)
+        for k in PROFILE_KEYS:
+            out[k] = out[k].reshape(self.n_scenes, self.batch_size, *out[k].shape[1:])
+        return out
+
+    def sample_rows(self, trajectories, profile, period, rows=None, max_samples=None, return_device: bool = False):
+        """IntersectionVolumeGuide.sample_rows for the (S, B, 7, N) / (S*B, 7, N) state and the profile SceneBatch.time_rows gave, in ONE
+        launch: ``rows`` indexes the S*B rows scene after scene (default all); q, qd (R, 7, M) and count (R,) in list order.  Leaves a
+        segmented run running."""
+        from .evaluation import PROFILE_KEYS, sample_rows_on
+
+        Xd, N = self._state(trajectories)
+        flat = {k: profile[k].reshape(self.n_scenes * self.batch_size, *profile[k].shape[2:]) for k in PROFILE_KEYS if k in profile}
+        return sample_rows_on(self.ctx, Xd, flat, period, rows, max_samples, return_device)
 
     def sdf_self_rows(self, trajectories, t=0):
         """IntersectionVolumeGuide.sdf_self_rows for the (S, B, 7, N) / (S*B, 7, N) state (its interior columns 1..N-2 are the

@@ -37,6 +37,7 @@ extern "C" {
 #define EDMP_MAX_SWEEP_SUBSTEPS 64 /* edmp_sdf_set_sweep: interpolants per segment + 1 */
 #define EDMP_MAX_REPAIR_ITERS 1024 /* edmp_sdf_repair_rows_dev: a cap so that a launch stays bounded, not a tuned value */
 #define EDMP_MAX_SHORTCUT_PASSES 1024 /* edmp_shortcut_rows_dev: a cap so that a launch stays bounded, not a tuned value */
+#define EDMP_MAX_TIMED_SAMPLES 1048576 /* edmp_sample_rows_dev: samples per row; a cap so that a launch stays bounded, not a tuned value */
 
 typedef struct edmp_ctx edmp_ctx;
 
@@ -322,6 +323,57 @@ int edmp_shortcut_rows_dev(edmp_ctx* ctx, double* X_dev, int n, int N, const int
 int edmp_scenes_shortcut_rows_dev(edmp_ctx* ctx, double* X_dev, int S, int B, int N, const int32_t* rows_host, int n_rows, int substeps,
                                   int passes, double min_gain, const double* dh_f64, int32_t* accepted_dev, int32_t* tested_dev,
                                   double* length_dev, int32_t* spans_dev, int log_cap);
+
+/* ---- time parameterisation of finished rows (csrc/timing.hip) ---------------------------------------------------- */
+/* The stage after shortcutting, which the reference does not ship (it replays plans at constant velocity): the fastest rest-to-rest
+ * motion ALONG the polyline of every row under joint velocity, joint acceleration and corner velocity-jump limits, and its samples at a
+ * controller period.  X_dev (n, 7, N) f64, 2 <= N <= 64; vmax [rad/s], amax [rad/s^2], jump [rad/s] are host arrays of 7, finite and > 0.
+ * All arithmetic in f64, every operation rounded on its own (no fused multiply-add), min(a, b) = b < a ? b : a.  The rule, per row x, with
+ * the path parameter s in [0, N-1] and y = (ds/dt)^2:
+ *   segment i = 0..N-2: d_i = x_{i+1} - x_i;  V_i = min_j vmax_j / |d_ij|, A_i = min_j amax_j / |d_ij| over the joints with d_ij != 0, in
+ *     joint order.  d_i = 0 is a ZERO SEGMENT: it takes no time, has no V_i / A_i and hands y across unchanged.
+ *   waypoint caps: c_0 = c_{N-1} = 0 (rest to rest); interior c_i = min(V_{i-1}^2, V_i^2, J_i^2), J_i = min_j jump_j / |d_ij - d_{i-1,j}|;
+ *     terms with a zero denominator and the V of a zero segment are left out; nothing left = +inf (y stays finite: y_0 = 0 and every
+ *     transfer adds a finite amount).
+ *   forward pass:  y_0 = 0, y_{i+1} = min(c_{i+1}, y_i + 2 A_i), a zero segment min(c_{i+1}, y_i);
+ *   backward pass: y_i = min(y_i, y_{i+1} + 2 A_i), a zero segment min(y_i, y_{i+1}).
+ *   inside a non-zero segment, the optimum given its end values: accelerate at A_i, cruise at V_i, decelerate at A_i, with the peak
+ *     p_i = min(V_i^2, (y_i + y_{i+1}) / 2 + A_i) and the phase times t_acc = max(0, (sqrt p_i - sqrt y_i) / A_i),
+ *     t_dec = max(0, (sqrt p_i - sqrt y_{i+1}) / A_i), t_cru = max(0, 1 - (p_i - y_i) / (2 A_i) - (p_i - y_{i+1}) / (2 A_i)) / sqrt p_i;
+ *     a zero segment has three zeros.  Waypoint times: T_0 = 0 and one running sum t += t_acc, t += t_cru, t += t_dec in index order,
+ *     T_{i+1} = t; duration = T_{N-1}.
+ *   limit_i: the constraint that binds waypoint i = the first index of the minimum among 0 = rest end, 1 = V_{i-1}^2, 2 = V_i^2,
+ *     3 = J_i^2, 4 = y_{i-1} + 2 A_{i-1} with the forward pass's y_{i-1} (a zero segment: y_{i-1}), 5 = y_{i+1} + 2 A_i with the backward
+ *     pass's y_{i+1}.  Both ends are 0.
+ *   motion at time t < duration: segment i = the largest i <= N-2 with T_i <= t, tau = t - T_i;
+ *     tau < t_acc:               sdot = sqrt y_i + A_i tau,            s = sqrt y_i * tau + (A_i / 2) tau^2
+ *     else t2 = tau - t_acc < t_cru:  sdot = sqrt p_i,                  s = (p_i - y_i) / (2 A_i) + sqrt p_i * t2
+ *     else t3 = t2 - t_cru:      sdot = sqrt p_i - A_i t3,             s = (1 - (p_i - y_{i+1}) / (2 A_i)) + (sqrt p_i * t3 - (A_i / 2) t3^2)
+ *     sdot clamped to [0, sqrt p_i], s to [0, 1];  q = x_i + s (x_{i+1} - x_i),  qdot = (x_{i+1} - x_i) sdot.
+ *     t >= duration: q = the goal column bit for bit, qdot = 0.
+ *   samples: t_k = (double)k * period, k = 0..M-1.  count = 1 + the smallest k with (double)k * period >= duration (duration = 0: 1),
+ *     saturated at INT32_MAX; samples at or past count - 1 hold the goal at rest.
+ *   a row with a non-finite element is not timed: y, phase, times, duration and its samples are NaN, limit = -1, count = 0.
+ * Consequences: |qdot_j| <= vmax_j everywhere and |qddot_j| <= amax_j inside segments; the velocity jump at waypoint i is
+ * |d_ij - d_{i-1,j}| sqrt y_i <= jump_j; the path is the input polyline, so what the success, self-collision and shortcut stages said of
+ * it holds for what is executed; collinear runs (what edmp_shortcut_rows_dev writes) carry no corner cap; a repeated waypoint is
+ * conservative (the speed is handed across instead of optimised over), never unsafe.  y is the component-wise largest point of
+ * {0 <= y_i <= c_i, |y_{i+1} - y_i| <= 2 A_i}: the time optimum on this path, zero-segment hand-over excepted.
+ *
+ * edmp_time_rows_dev (time_rows_kernel: one wave per row, four rows per workgroup, lane = waypoint) writes y (n, N), phase (n, N-1, 3) =
+ * t_acc | t_cru | t_dec, times (n, N), duration (n,), limit (n, N) int32 and seg (n, N-1, 2) = A_i | p_i (0 | y_i on a zero segment): the
+ * per-segment values the sampler needs, so that the sampler reads the limits nowhere else.  Does not synchronise.
+ * edmp_sample_rows_dev (sample_rows_kernel: workgroup = listed row x 256 samples) takes X and that profile, rows_host = n_rows row
+ * indices (host, any order, no duplicates) or NULL = every row (n_rows is ignored), period > 0 [s] and M in 1..EDMP_MAX_TIMED_SAMPLES,
+ * and writes q, qdot (R, 7, M) f64 and count (R,) int32, R = n_rows (or n): slot k belongs to row rows[k]; nothing else is written.
+ * count is the row's true count and may exceed M.  Synchronises (the list is read from the caller's array).
+ * Both need a context only - no model, scene, guide or sampler - leave the epoch alone and do NOT end a segmented run.  Refusals (N, n,
+ * limits, period, M, rows out of range or listed twice, null pointers) come before any device call and name the offending value. */
+int edmp_time_rows_dev(edmp_ctx* ctx, const double* X_dev, int n, int N, const double* vmax, const double* amax, const double* jump,
+                       double* y_dev, double* phase_dev, double* times_dev, double* duration_dev, int32_t* limit_dev, double* seg_dev);
+int edmp_sample_rows_dev(edmp_ctx* ctx, const double* X_dev, int n, int N, const double* y_dev, const double* phase_dev,
+                         const double* times_dev, const double* duration_dev, const double* seg_dev, const int32_t* rows_host, int n_rows,
+                         double period, int M, double* q_dev, double* qd_dev, int32_t* count_dev);
 
 /* ---- self-collision of every row (csrc/selfcol.hip) ------------------------------------------------------------- */
 /* Stands for the `self_collision` metric of the reference's evaluation package (mpinets/metrics.py:278-292, 351-361; a plan with

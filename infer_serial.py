@@ -331,9 +331,25 @@ def _score(job, on, X, starts, goals, tb):
     lead = lambda d: None if d is None else {k: on.scenes(v) for k, v in d.items()}  # noqa: E731
     of = lambda d, *at: None if d is None else {k: v[at] for k, v in d.items()}  # noqa: E731
     idx, vols, X, chk, met, selfcol, goal, chosen = on.scenes(idx), on.scenes(vols), on.host(X), lead(chk), lead(met), lead(selfcol), lead(goal), lead(chosen)
+    timed = _time_plans(job, obj.ctx, np.stack([X[s][int(i)] for s, i in enumerate(idx)])) if job.time_plan is not None else None
     return [SimpleNamespace(idx=int(i), vols=vols[s], trajectory=X[s][int(i)], met=of(met, s), selfcol=of(selfcol, s), chosen=of(chosen, s, place[s]), goal=of(goal, s, place[s]),
                             chk={k: (v if np.ndim(v) else int(v)) for k, v in of(chk, s).items()},  # (the per-row flags, and the scene's counts as ints)
-                            repair=None if moved is None else (moved[s], clear[s]), shortcut=None if cut is None else cut[s]) for s, i in enumerate(idx)]
+                            repair=None if moved is None else (moved[s], clear[s]), shortcut=None if cut is None else cut[s], timed=None if timed is None else timed[s])
+            for s, i in enumerate(idx)]
+
+
+def _time_plans(job, ctx, plans):
+    """the chosen plans (S, 7, N) timed under the default joint velocity, acceleration and corner-jump limits (EV.time_rows_on, one launch for
+    the group) -> per scene dict(duration_s, binding_constraints = how many waypoints each constraint binds), and with a period (job.time_plan
+    a number) the sample count of the timed motion at that period, from the sampler itself (EV.sample_rows_on, one launch)"""
+    prof = EV.time_rows_on(ctx, plans)
+    out = [dict(duration_s=float(d), binding_constraints={name: int(np.count_nonzero(lim == k)) for k, name in enumerate(EV.LIMIT_NAMES)})
+           for d, lim in zip(prof["duration"], prof["limit"])]
+    if job.time_plan is not True:
+        count = EV.sample_rows_on(ctx, plans, prof, job.time_plan)["count"]
+        for o, c in zip(out, count):
+            o.update(time_period_s=float(job.time_plan), timed_samples=int(c))
+    return out
 
 
 def _result(job, meta, tm, sc, t0, plan_end, wall_end=None, scenes_in_launch=None):
@@ -357,6 +373,8 @@ def _result(job, meta, tm, sc, t0, plan_end, wall_end=None, scenes_in_launch=Non
         r.update(rows_repaired=int(sc.repair[0].sum()), rows_repair_clear=int(sc.repair[1].sum()), repair_iters=int(job.repair))
     if sc.shortcut is not None:  # shortcut: the scene's rows with at least one accepted span
         r.update(rows_shortcut=int(sc.shortcut.sum()), shortcut_passes=int(job.shortcut))
+    if sc.timed is not None:  # time_plan: the chosen plan's timed motion
+        r.update(sc.timed)
     if job.prefer is not None:
         r["prefer"] = job.prefer
     if job.ensemble_report:
@@ -470,6 +488,10 @@ def _print_scene(r, n, tally, prefix=""):
         print(f"    repair ({r['repair_iters']} iterations at most): {r['rows_repaired']}/{r['rows']} rows moved, {r['rows_repair_clear']}/{r['rows']} ended clear")
     if "rows_shortcut" in r:
         print(f"    shortcut ({r['shortcut_passes']} passes at most): {r['rows_shortcut']}/{r['rows']} rows shortened")
+    if "duration_s" in r:
+        census = ", ".join(f"{k} {v}" for k, v in r["binding_constraints"].items() if v)
+        print(f"    chosen plan: duration_s {r['duration_s']:.3f} under the joint velocity / acceleration / corner limits; waypoints bound by: {census}"
+              + (f"; {r['timed_samples']} samples at {r['time_period_s']:g} s" if "timed_samples" in r else ""))
     if "self_collision_free" in r:
         print(f"    self-collision free {r['self_collision_free']} ({r['rows_self_collision_free']}/{r['rows']} rows of the batch)   running {tally.self_free}/{n}")
         if "ensemble" in r:
@@ -501,7 +523,8 @@ def _print_summary(summary):
 
 
 def run(cfg_path, dataset=None, max_scenes=None, verbose=True, scenes_in_flight=1, shard_scenes=True, scenes_per_launch=1, ensemble_report=False, prefer=None,
-        ik_seeds=0, ik_tool=None, ik_seed=0, self_collision=False, device_noise=None, repair=0, repair_margin=0.02, repair_step=0.02, shortcut=0):
+        ik_seeds=0, ik_tool=None, ik_seed=0, self_collision=False, device_noise=None, repair=0, repair_margin=0.02, repair_step=0.02, shortcut=0,
+        time_plan=None):
     """The reference's scene loop (infer_serial.py:95-170).  Under ``torch.distributed.run`` (one process per GPU, extension: the
     reference is one process) the scenes are dealt round-robin to the ranks - scene i of the cfg's order goes to rank i mod world -
     and nothing is exchanged until `job_summary` adds the tallies up: scenes are independent problems, this is the problem set's natural
@@ -566,6 +589,12 @@ def run(cfg_path, dataset=None, max_scenes=None, verbose=True, scenes_in_flight=
     Everything behind it sees the repaired rows.  Each result adds `rows_repaired` (rows that moved), `rows_repair_clear` (rows whose last
     evaluation had no active hinge, repair_tally) and `repair_iters`; the per-scene line and the summary print the two counts.
 
+    ``time_plan`` (an extension; None = off: nothing is launched and every printed and returned value is what it was): True times each scene's
+    chosen plan under Franka's joint velocity and acceleration limits and an illustrative corner velocity-jump limit (evaluation.time_rows:
+    the fastest rest-to-rest motion along the plan's own polyline) and adds `duration_s` and `binding_constraints` (waypoints bound by each
+    constraint) to the result; a number is also the period [s] at which that motion is sampled (evaluation.sample_rows), adding
+    `time_period_s` and `timed_samples`.  ``prefer`` = "fastest" picks, inside the trust region, the row with the shortest such duration.
+
     ``shortcut`` = PASSES > 0 (an extension; 0 = off: nothing is launched and every printed and returned value is what it was) sends the
     whole batch through shortcut_rows after the repair and before the selection (IntersectionVolumeGuide.shortcut_rows; a scene group
     through SceneBatch.shortcut_rows in one launch): at most PASSES passes of joint-space shortcuts, each accepted only if the success
@@ -582,6 +611,10 @@ def run(cfg_path, dataset=None, max_scenes=None, verbose=True, scenes_in_flight=
     repair = int(repair)
     if repair < 0:
         raise ValueError(f"repair must be >= 0 iterations (0 = off), got {repair}")
+    if time_plan is not None and time_plan is not True:
+        time_plan = float(time_plan)
+        if not (np.isfinite(time_plan) and time_plan > 0):
+            raise ValueError(f"time_plan must be None (off), True, or a sample period > 0 [s], got {time_plan}")
     shortcut = int(shortcut)
     if shortcut < 0:
         raise ValueError(f"shortcut must be >= 0 passes (0 = off), got {shortcut}")
@@ -593,15 +626,15 @@ def run(cfg_path, dataset=None, max_scenes=None, verbose=True, scenes_in_flight=
     if dataset is None:
         dataset = _dataset(cfg)
     guide_cfgs = GC.guide_cfgs_from_run_cfg(cfg, base_dir=os.path.dirname(os.path.abspath(cfg_path)) + "/..")
-    if prefer not in (None, "shortest", "smoothest"):
-        raise ValueError(f"prefer must be None, 'shortest' or 'smoothest', got {prefer!r}")
+    if prefer not in (None, "shortest", "smoothest", "fastest"):
+        raise ValueError(f"prefer must be None, 'shortest', 'smoothest' or 'fastest', got {prefer!r}")
     guide_numbers = [int(n) for n in cfg["guide"]["guides"]]
     job = SimpleNamespace(  # what the functions above share: the config's constants, the options, the dataset, the lanes and the running tallies
         T=model["T"], traj_len=model["traj_len"], num_channels=model["num_channels"], mesh_dir=model.get("mesh_dir"), guide_cfgs=guide_cfgs,
         total_batch_size=guide_cfgs["total_batch_size"], guide_numbers=guide_numbers,
         guide_rows=GC.split_rows(int(cfg["guide"]["total_rows"]), len(guide_numbers)) if cfg["guide"].get("total_rows") else guide_cfgs["batch_size_per_guide"],
         dataset=dataset, rank=rank, world=world, verbose=verbose, prefer=prefer, ensemble_report=ensemble_report, self_collision=self_collision, device_noise=device_noise,
-        repair=repair, repair_margin=repair_margin, repair_step=repair_step, shortcut=shortcut, ik_tool=ik_tool, iks=[], feeder=None, results=[], tally=SimpleNamespace(success=0, strict=0, self_free=0))
+        repair=repair, repair_margin=repair_margin, repair_step=repair_step, shortcut=shortcut, time_plan=time_plan, ik_tool=ik_tool, iks=[], feeder=None, results=[], tally=SimpleNamespace(success=0, strict=0, self_free=0))
     k = max(1, int(scenes_in_flight))
     base = get_context(device)
     job.lanes = _lanes(job, base, k, model["model_dir"], max_batch=job.total_batch_size * kl)
@@ -650,8 +683,9 @@ def main(argv=None):
                                                                        "to PATH (rank 0) / PATH.rank<r> (other ranks)")
     parser.add_argument("--ensemble-report", action="store_true", help="score every row of each batch on the GPU (path lengths, SPARC) and report, per guide of the "
                                                                        "ensemble, its collision-free rows and their metrics (extension; adds `ensemble` to the results)")
-    parser.add_argument("--prefer", choices=("shortest", "smoothest"), default=None, help="among the rows within the trust region of the minimum swept volume pick the "
-                                                                                             "shortest joint path / the smoothest plan instead of the first arg-min (extension)")
+    parser.add_argument("--prefer", choices=("shortest", "smoothest", "fastest"), default=None, help="among the rows within the trust region of the minimum swept volume pick the "
+                                                                                             "shortest joint path / the smoothest plan / the plan with the shortest timed motion "
+                                                                                             "instead of the first arg-min (extension)")
     parser.add_argument("--ik-seeds", type=int, default=0, help="solve the IK of problems that carry a target pose and no goals on the GPU, from this many "
                                                                   "seeds per target (extension; 0 = off: such a problem set raises as before)")
     parser.add_argument("--ik-tool", type=str, default=None, help="the frame the targets are given in: 'flange', 'hand', or a JSON / .npy file holding a (4, 4) "
@@ -662,6 +696,9 @@ def main(argv=None):
                                                                                 "ITERS projected descent steps on the swept sphere-clearance cost (extension; 0 = off)")
     parser.add_argument("--repair-margin", type=float, default=0.02, help="the clearance [m] that the repair asks of every tested configuration")
     parser.add_argument("--repair-step", type=float, default=0.02, help="the repair's step size (a joint moves by at most 0.02 rad per iteration)")
+    parser.add_argument("--time-plan", type=float, nargs="?", const=True, default=None, metavar="PERIOD", help="time the chosen plan under the joint velocity, acceleration "
+                        "and corner velocity-jump limits (the fastest rest-to-rest motion along its polyline) and report its duration_s and which constraint binds "
+                        "how many waypoints; with PERIOD [s] also the sample count of that motion at the period (extension; off: nothing changes)")
     parser.add_argument("--shortcut", type=int, default=0, metavar="PASSES", help="after the repair and before the selection, shorten every row of each batch by at most "
                                                                                     "PASSES passes of joint-space shortcuts, each accepted only under the exact collision check "
                                                                                     "(extension; 0 = off)")
@@ -678,7 +715,7 @@ def main(argv=None):
         np.random.seed(args.seed + rank)
     results = run(args.cfg_path, scenes_in_flight=args.scenes_in_flight, max_scenes=args.max_scenes, scenes_per_launch=args.scenes_per_launch,
                   ensemble_report=args.ensemble_report, prefer=args.prefer, ik_seeds=args.ik_seeds, ik_tool=ik_tool, self_collision=args.self_collision,
-                  device_noise=args.device_noise, repair=args.repair, repair_margin=args.repair_margin, repair_step=args.repair_step, shortcut=args.shortcut)
+                  device_noise=args.device_noise, repair=args.repair, repair_margin=args.repair_margin, repair_step=args.repair_step, shortcut=args.shortcut, time_plan=args.time_plan)
     if args.results_json:
         rows = [{k: v for k, v in r.items() if k != "trajectory"} for r in results]
         with open(args.results_json + ("" if rank == 0 else f".rank{rank}"), "w") as f:
