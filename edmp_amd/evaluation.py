@@ -221,6 +221,16 @@ def _rows_state(ctx, trajectories):
     return X
 
 
+def _device_f64(ctx, v, want, name, X):
+    """an array or device tensor that goes with the state X -> the contiguous f64 device tensor on ctx's stream, its shape checked"""
+    import torch
+
+    t = ctx.adopt(v.to(torch.float64).contiguous()) if isinstance(v, torch.Tensor) and v.is_cuda else ctx.to_dev(np.asarray(v, dtype=np.float64), torch.float64)
+    if tuple(t.shape) != want:
+        raise ValueError(f"{name} must be {want} for trajectories {tuple(X.shape)}, got {tuple(t.shape)}")
+    return t
+
+
 def time_rows_on(ctx, trajectories, vmax=None, amax=None, jump=None, scale=(1, 1), return_device: bool = False) -> dict:
     """edmp_time_rows_dev on the context `ctx` (runtime.Context): see time_rows."""
     import torch
@@ -275,26 +285,14 @@ def sample_count(duration, period) -> int:
     return 1 + k
 
 
-def sample_rows_on(ctx, trajectories, profile, period, rows=None, max_samples=None, return_device: bool = False) -> dict:
-    """edmp_sample_rows_dev on the context `ctx` (runtime.Context): see sample_rows."""
+def _sample_setup(ctx, n, profile, period, rows, max_samples):
+    """what both samplers settle before their call: the period, the checked row list, M and the output tensors ->
+    (period, listed, R, M, q, qd, count)"""
     import torch
-
-    from . import _capi
-    from .runtime import ptr
 
     period = float(period)
     if not (np.isfinite(period) and period > 0):
         raise ValueError(f"period must be finite and > 0, got {period!r}")
-    X = _rows_state(ctx, trajectories)
-    n, N = X.shape[0], X.shape[2]
-    prof = {}
-    for k in ("y", "phase", "times", "duration", "seg"):  # (limit is a report, the sampler does not read it)
-        v = profile[k]
-        t = ctx.adopt(v.to(torch.float64).contiguous()) if isinstance(v, torch.Tensor) and v.is_cuda else ctx.to_dev(np.asarray(v, dtype=np.float64), torch.float64)
-        want = dict(y=(n, N), phase=(n, N - 1, 3), times=(n, N), duration=(n,), seg=(n, N - 1, 2))[k]
-        if tuple(t.shape) != want:
-            raise ValueError(f"profile[{k!r}] must be {want} for trajectories {tuple(X.shape)}, got {tuple(t.shape)}")
-        prof[k] = t
     listed = None if rows is None else np.ascontiguousarray(np.asarray(rows, dtype=np.int32).reshape(-1))
     if listed is not None and listed.size and (listed.min() < 0 or listed.max() >= n):
         raise ValueError(f"rows must lie in 0..{n - 1}, got {listed.tolist()}")
@@ -314,15 +312,32 @@ def sample_rows_on(ctx, trajectories, profile, period, rows=None, max_samples=No
         q = torch.empty((R, 7, max(M, 0)), dtype=torch.float64, device=ctx.device)
         qd = torch.empty_like(q)
         count = torch.empty((R,), dtype=torch.int32, device=ctx.device)
-    _capi.check(ctx.lib.edmp_sample_rows_dev(ctx.h, ptr(X), n, N, ptr(prof["y"]), ptr(prof["phase"]), ptr(prof["times"]), ptr(prof["duration"]), ptr(prof["seg"]),
-                                             None if listed is None else _capi.as_pi32(listed), 0 if listed is None else R, period, M, ptr(q), ptr(qd), ptr(count)),
-                "edmp_sample_rows_dev")
+    return period, listed, R, M, q, qd, count
+
+
+def _sample_result(ctx, q, qd, count, M, period, return_device):
     t = np.arange(M, dtype=np.float64) * period
     if return_device:
         for v in (q, qd, count):
             ctx.hand_over(v)
         return dict(q=q, qd=qd, count=count, t=t)
     return dict(q=ctx.to_host(q), qd=ctx.to_host(qd), count=ctx.to_host(count), t=t)
+
+
+def sample_rows_on(ctx, trajectories, profile, period, rows=None, max_samples=None, return_device: bool = False) -> dict:
+    """edmp_sample_rows_dev on the context `ctx` (runtime.Context): see sample_rows."""
+    from . import _capi
+    from .runtime import ptr
+
+    X = _rows_state(ctx, trajectories)
+    n, N = X.shape[0], X.shape[2]
+    want = dict(y=(n, N), phase=(n, N - 1, 3), times=(n, N), duration=(n,), seg=(n, N - 1, 2))  # (limit is a report, the sampler does not read it)
+    period, listed, R, M, q, qd, count = _sample_setup(ctx, n, profile, period, rows, max_samples)
+    prof = {k: _device_f64(ctx, profile[k], want[k], f"profile[{k!r}]", X) for k in want}
+    _capi.check(ctx.lib.edmp_sample_rows_dev(ctx.h, ptr(X), n, N, ptr(prof["y"]), ptr(prof["phase"]), ptr(prof["times"]), ptr(prof["duration"]), ptr(prof["seg"]),
+                                             None if listed is None else _capi.as_pi32(listed), 0 if listed is None else R, period, M, ptr(q), ptr(qd), ptr(count)),
+                "edmp_sample_rows_dev")
+    return _sample_result(ctx, q, qd, count, M, period, return_device)
 
 
 def sample_rows(trajectories, profile, period, rows=None, max_samples=None, device="cuda:0", return_device: bool = False) -> dict:
@@ -336,6 +351,88 @@ def sample_rows(trajectories, profile, period, rows=None, max_samples=None, devi
     from .runtime import get_context
 
     return sample_rows_on(get_context(device), trajectories, profile, period, rows, max_samples, return_device)
+
+
+BLENDED_PROFILE_KEYS = PROFILE_KEYS + ("blend",)  # edmp_time_blended_rows_dev's outputs; the profile dict also carries `beta`
+BLEND_CODE_NAMES = ("none", "not_needed", "no_gain", "blended", "blocked")  # the codes of blend_rows' `code`; -1 = a row left alone
+
+
+def blend_arguments(deviation, reach, substeps, halvings):
+    """(deviation (7,) float64, reach, substeps, halvings) as edmp_blend_rows_dev takes them: a scalar deviation [rad] stands for all seven
+    joints.  The library checks the ranges."""
+    dev = np.ascontiguousarray(np.broadcast_to(np.asarray(deviation, dtype=np.float64), (7,)))
+    return dev, float(reach), int(substeps), int(halvings)
+
+
+def time_blended_rows_on(ctx, trajectories, beta, vmax=None, amax=None, jump=None, scale=(1, 1), return_device: bool = False) -> dict:
+    """edmp_time_blended_rows_dev on the context `ctx` (runtime.Context): see time_blended_rows."""
+    import torch
+
+    from . import _capi
+    from .runtime import ptr
+
+    vm, am, jm = franka.timing_limits(vmax, amax, jump, scale)
+    X = _rows_state(ctx, trajectories)
+    n, N = X.shape[0], X.shape[2]
+    b = _device_f64(ctx, beta, (n, N), "beta", X)
+    out = dict(y=ctx.empty((n, N), torch.float64), phase=ctx.empty((n, max(N - 1, 0), 3), torch.float64), times=ctx.empty((n, N, 2), torch.float64),
+               duration=ctx.empty((n,), torch.float64), limit=ctx.empty((n, N), torch.int32), seg=ctx.empty((n, max(N - 1, 0), 2), torch.float64),
+               blend=ctx.empty((n, N), torch.float64))
+    _capi.check(ctx.lib.edmp_time_blended_rows_dev(ctx.h, ptr(X), n, N, ptr(b), _capi.as_pd(vm), _capi.as_pd(am), _capi.as_pd(jm),
+                                                   *(ptr(out[k]) for k in BLENDED_PROFILE_KEYS)), "edmp_time_blended_rows_dev")
+    if return_device:
+        X.record_stream(ctx.stream)  # (the kernel may still be reading them when the caller drops the tensors)
+        b.record_stream(ctx.stream)
+        for k in BLENDED_PROFILE_KEYS:
+            ctx.hand_over(out[k])
+        out["beta"] = b
+    else:
+        out = {k: ctx.to_host(out[k]) for k in BLENDED_PROFILE_KEYS}
+        out["beta"] = ctx.to_host(b)
+    out.update(vmax=vm, amax=am, jump=jm)
+    return out
+
+
+def time_blended_rows(trajectories, beta, vmax=None, amax=None, jump=None, scale=(1, 1), device="cuda:0", return_device: bool = False) -> dict:
+    """Time every finished row along its BLENDED path (edmp_time_blended_rows_dev, csrc/blend.hip): trajectories (n, 7, N), 2 <= N <= 64,
+    and beta (n, N) as blend_rows gave it (guide.blend_rows: corner i is replaced by the parabolic blend from x_i - beta_i d_{i-1} to
+    x_i + beta_i d_i) -> time_rows' profile dict with two changes - times is (n, N, 2) = the time entering | leaving waypoint i's blend, and
+    limit code 3 means "corner: jump cap or blend acceleration cap" - plus blend (n, N) = the time spent on each blend and beta itself,
+    which sample_blended_rows reads.  The rule is time_rows' forward / backward pass with the blend's acceleration cap (2 beta_i) K_i as
+    the corner cap and the straight part l_i = 1 - beta_i - beta_{i+1} as the segment; include/edmp_hip.h states it in full.  The
+    velocity is continuous at a blended corner, |qdot| <= vmax and |qddot| <= amax hold on straight parts and on blends.  With beta = 0
+    everywhere every common output has time_rows' bits.  A row with a non-finite element (of X or beta) is not timed.  Needs no scene
+    and no guide.  Runs on the GPU only."""
+    from .runtime import get_context
+
+    return time_blended_rows_on(get_context(device), trajectories, beta, vmax, amax, jump, scale, return_device)
+
+
+def sample_blended_rows_on(ctx, trajectories, profile, period, rows=None, max_samples=None, return_device: bool = False) -> dict:
+    """edmp_sample_blended_rows_dev on the context `ctx` (runtime.Context): see sample_blended_rows."""
+    from . import _capi
+    from .runtime import ptr
+
+    X = _rows_state(ctx, trajectories)
+    n, N = X.shape[0], X.shape[2]
+    want = dict(beta=(n, N), y=(n, N), phase=(n, N - 1, 3), times=(n, N, 2), duration=(n,), seg=(n, N - 1, 2))  # (limit and blend are reports, not read)
+    period, listed, R, M, q, qd, count = _sample_setup(ctx, n, profile, period, rows, max_samples)
+    prof = {k: _device_f64(ctx, profile[k], want[k], f"profile[{k!r}]", X) for k in want}
+    _capi.check(ctx.lib.edmp_sample_blended_rows_dev(ctx.h, ptr(X), n, N, ptr(prof["beta"]), ptr(prof["y"]), ptr(prof["phase"]), ptr(prof["times"]),
+                                                     ptr(prof["duration"]), ptr(prof["seg"]), None if listed is None else _capi.as_pi32(listed),
+                                                     0 if listed is None else R, period, M, ptr(q), ptr(qd), ptr(count)), "edmp_sample_blended_rows_dev")
+    return _sample_result(ctx, q, qd, count, M, period, return_device)
+
+
+def sample_blended_rows(trajectories, profile, period, rows=None, max_samples=None, device="cuda:0", return_device: bool = False) -> dict:
+    """The blended, timed motion of the listed rows at a controller period (edmp_sample_blended_rows_dev, csrc/blend.hip): trajectories
+    (n, 7, N) and the `profile` time_blended_rows gave for them (it carries beta) -> sample_rows' dict(q, qd (R, 7, M), count (R,), t (M,)).
+    On a straight part q = x_i + (beta_i + s) d_i; on blend i q = x_i + beta_i (u^2 d_i - (1 - u)^2 d_{i-1}) and qdot = sqrt y_i ((1 - u)
+    d_{i-1} + u d_i), u the fraction of the blend's time.  ``rows``, ``max_samples``, count, the goal's bits at rest past the duration and
+    the NaN row are sample_rows'.  With beta = 0 everywhere: sample_rows' bits.  Runs on the GPU only."""
+    from .runtime import get_context
+
+    return sample_blended_rows_on(get_context(device), trajectories, profile, period, rows, max_samples, return_device)
 
 
 def ensemble_report(guides, batch_size_per_guide, volumes, success, metrics) -> list:

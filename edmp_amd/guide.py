@@ -433,6 +433,33 @@ class _SlotObject:
                     length0=ln[:, 0].reshape(shape).copy(), length=ln[:, 1].reshape(shape).copy(), spans=(ctx.to_host(spans) if cap > 0 else np.zeros((n, 0, 2), dtype=np.int32)).reshape(*shape, max(cap, 0), 2))
 
 
+    def _blend(self, Xd, shape, N, deviation, reach, substeps, halvings, vmax, amax, jump, scale, rows, return_device):
+        """the corner blends of the (rows, 7, N) device state Xd under the exact collision check -> the blend dict, per-row arrays `shape`d.
+        Rows outside `rows` are not written by the library: they keep beta 0, code 0, halved 0, tested 0 (an unblended row)."""
+        from .evaluation import blend_arguments
+
+        ctx, n = self.ctx, int(np.prod(shape))
+        vm, am, jm = franka.timing_limits(vmax, amax, jump, scale)
+        dev, reach, substeps, halvings = blend_arguments(deviation, reach, substeps, halvings)
+        with torch.cuda.stream(ctx.stream):
+            beta = torch.zeros((n, N), dtype=torch.float64, device=ctx.device)
+            codes = torch.zeros((2, n, N), dtype=torch.int32, device=ctx.device)
+            tested = torch.zeros((n,), dtype=torch.int32, device=ctx.device)
+        listed = None if rows is None else np.ascontiguousarray(np.asarray(rows, dtype=np.int32).reshape(-1))
+        dh = np.ascontiguousarray(franka.dh_table_f64())
+        self._call("edmp_blend_rows_dev", "edmp_scenes_blend_rows_dev", shape, ptr(Xd), *shape, N, None if listed is None else _capi.as_pi32(listed),
+                   0 if listed is None else int(listed.shape[0]), _capi.as_pd(vm), _capi.as_pd(am), _capi.as_pd(jm), _capi.as_pd(dev), reach, substeps, halvings,
+                   _capi.as_pd(dh), ptr(beta), C.c_void_p(codes[0].data_ptr()), C.c_void_p(codes[1].data_ptr()), ptr(tested))
+        lim = dict(vmax=vm, amax=am, jump=jm, deviation=dev, reach=reach, substeps=substeps, halvings=halvings)
+        if return_device:
+            for v in (beta, codes, tested):
+                ctx.hand_over(v)  # (the caller's torch ops on the results follow this context's stream)
+            return dict(beta=beta.view(*shape, N), code=codes[0].view(*shape, N), halved=codes[1].view(*shape, N), tested=tested.view(*shape), **lim)
+        c = ctx.to_host(codes)
+        return dict(beta=ctx.to_host(beta).reshape(*shape, N), code=c[0].reshape(*shape, N).copy(), halved=c[1].reshape(*shape, N).copy(),
+                    tested=ctx.to_host(tested).reshape(shape), **lim)
+
+
 class IntersectionVolumeGuide(_SlotObject):
     """Same constructor / method signatures as the reference:
 
@@ -805,6 +832,43 @@ class IntersectionVolumeGuide(_SlotObject):
         from .evaluation import sample_rows_on
 
         return sample_rows_on(self.ctx, trajectories, profile, period, rows, max_samples, return_device)
+
+    def blend_rows(self, trajectories, deviation=0.01, reach=0.4, substeps=4, halvings=2, vmax=None, amax=None, jump=None, scale=(1, 1), rows=None,
+                   return_device: bool = False):
+        """Choose a parabolic blend for every corner of finished rows under the exact collision check (edmp_blend_rows_dev, csrc/blend.hip;
+        one launch, one workgroup per row): trajectories (n, 7, N) f64, ndarray or device tensor, 2 <= N <= 64, are only read.  Corner i is
+        replaced by the quadratic Bezier curve from x_i - beta d_{i-1} over x_i to x_i + beta d_i, which a timed motion crosses at constant
+        acceleration and with continuous velocity.  Only a corner whose velocity-jump cap binds (J_i^2 < min(V_{i-1}^2, V_i^2)) is blended;
+        beta starts at min(``reach``, 4 ``deviation``_j / |Delta_ij|) and is halved up to ``halvings`` times until the blend's ``substeps`` + 1
+        configurations u = k / substeps - both ends included - clear the scene's obstacles under success_rows' own test; a beta whose
+        acceleration cap is no better than the jump cap ends the corner.  -> dict(beta (n, N) f64, code (n, N) int32 - index into
+        evaluation.BLEND_CODE_NAMES: 0 none (an end, a repeated waypoint, no corner), 1 not needed, 2 no gain, 3 blended, 4 blocked -
+        halved (n, N) int32, tested (n,) int32 configurations tested) plus the arguments used.  The blend departs from the polyline by at
+        most beta |Delta_ij| / 4 <= ``deviation`` [rad, a scalar or one per joint] in joint j.  Self-collision is NOT tested.  A row with a
+        non-finite element is left alone: code -1, beta NaN.  ``rows``: the rows to work on (any order, no duplicates); the others report
+        beta 0, code 0: unblended.  The defaults are illustrative, not tuned: 10 mrad, reach 0.4 (at most 0.45), limits of
+        franka.timing_limits.  Hand beta to time_blended_rows.  Leaves a segmented run running."""
+        X = self._rows_f64(trajectories)
+        if X.dim() != 3 or X.shape[1] != 7:
+            raise ValueError(f"trajectories must be (n, 7, N), got {tuple(X.shape)}")
+        self._bind()
+        out = self._blend(X, (X.shape[0],), X.shape[2], deviation, reach, substeps, halvings, vmax, amax, jump, scale, rows, return_device)
+        X.record_stream(self.ctx.stream)
+        return out
+
+    def time_blended_rows(self, trajectories, beta, vmax=None, amax=None, jump=None, scale=(1, 1), return_device: bool = False):
+        """evaluation.time_blended_rows on this guide's context: the fastest rest-to-rest motion along every row's blended path
+        (edmp_time_blended_rows_dev, csrc/blend.hip) -> the blended profile dict.  Reads nothing of the scene; leaves a segmented run running."""
+        from .evaluation import time_blended_rows_on
+
+        return time_blended_rows_on(self.ctx, trajectories, beta, vmax, amax, jump, scale, return_device)
+
+    def sample_blended_rows(self, trajectories, profile, period, rows=None, max_samples=None, return_device: bool = False):
+        """evaluation.sample_blended_rows on this guide's context (edmp_sample_blended_rows_dev) -> dict(q, qd (R, 7, M), count (R,), t (M,)).
+        Leaves a segmented run running."""
+        from .evaluation import sample_blended_rows_on
+
+        return sample_blended_rows_on(self.ctx, trajectories, profile, period, rows, max_samples, return_device)
 
     def select_row(self, start, goal, trajectories, prefer=None, volume_trust_region: float = 0.0008):
         """The row choose_best_trajectory returns, as (index, volumes (B,) f32, metrics dict or None).  prefer=None: the reference's
@@ -1194,6 +1258,40 @@ class SceneBatch(_SlotObject):
         Xd, N = self._state(trajectories)
         flat = {k: profile[k].reshape(self.n_scenes * self.batch_size, *profile[k].shape[2:]) for k in PROFILE_KEYS if k in profile}
         return sample_rows_on(self.ctx, Xd, flat, period, rows, max_samples, return_device)
+
+    def blend_rows(self, trajectories, deviation=0.01, reach=0.4, substeps=4, halvings=2, vmax=None, amax=None, jump=None, scale=(1, 1), rows=None,
+                   return_device: bool = False):
+        """IntersectionVolumeGuide.blend_rows for every scene in one launch (edmp_scenes_blend_rows_dev): the (S, B, 7, N) / (S*B, 7, N)
+        state, each row against its own scene's obstacles and kinds -> the same dict with beta, code, halved (S, B, N) and tested (S, B);
+        scene s's values are bit for bit what guides[s].blend_rows gives for X[s].  ``rows`` indexes the S*B rows scene after scene.  Leaves a
+        segmented run running."""
+        Xd, N = self._state(trajectories)
+        self._bind()
+        out = self._blend(Xd, (self.n_scenes, self.batch_size), N, deviation, reach, substeps, halvings, vmax, amax, jump, scale, rows, return_device)
+        Xd.record_stream(self.ctx.stream)
+        return out
+
+    def time_blended_rows(self, trajectories, beta, vmax=None, amax=None, jump=None, scale=(1, 1), return_device: bool = False):
+        """IntersectionVolumeGuide.time_blended_rows for the (S, B, 7, N) / (S*B, 7, N) state and beta (S, B, N) / (S*B, N) in ONE launch ->
+        the blended profile dict with every array shaped (S, B, ...); scene s's values are bit for bit what guides[s].time_blended_rows gives
+        for X[s] and beta[s].  Leaves a segmented run running."""
+        from .evaluation import BLENDED_PROFILE_KEYS, time_blended_rows_on
+
+        Xd, N = self._state(trajectories)
+        out = time_blended_rows_on(self.ctx, Xd, beta.reshape(self.n_scenes * self.batch_size, N), vmax, amax, jump, scale, return_device)
+        for k in BLENDED_PROFILE_KEYS + ("beta",):
+            out[k] = out[k].reshape(self.n_scenes, self.batch_size, *out[k].shape[1:])
+        return out
+
+    def sample_blended_rows(self, trajectories, profile, period, rows=None, max_samples=None, return_device: bool = False):
+        """IntersectionVolumeGuide.sample_blended_rows for the (S, B, 7, N) / (S*B, 7, N) state and the profile SceneBatch.time_blended_rows
+        gave, in ONE launch: ``rows`` indexes the S*B rows scene after scene (default all); q, qd (R, 7, M) and count (R,) in list order.
+        Leaves a segmented run running."""
+        from .evaluation import BLENDED_PROFILE_KEYS, sample_blended_rows_on
+
+        Xd, N = self._state(trajectories)
+        flat = {k: profile[k].reshape(self.n_scenes * self.batch_size, *profile[k].shape[2:]) for k in BLENDED_PROFILE_KEYS + ("beta",) if k in profile}
+        return sample_blended_rows_on(self.ctx, Xd, flat, period, rows, max_samples, return_device)
 
     def sdf_self_rows(self, trajectories, t=0):
         """IntersectionVolumeGuide.sdf_self_rows for the (S, B, 7, N) / (S*B, 7, N) state (its interior columns 1..N-2 are the

@@ -375,6 +375,83 @@ int edmp_sample_rows_dev(edmp_ctx* ctx, const double* X_dev, int n, int N, const
                          const double* times_dev, const double* duration_dev, const double* seg_dev, const int32_t* rows_host, int n_rows,
                          double period, int M, double* q_dev, double* qd_dev, int32_t* count_dev);
 
+/* ---- corner blends of finished rows: chosen under the exact collision check, timed and sampled (csrc/blend.hip) -- */
+/* The stage after the one above, for a motion that may LEAVE the polyline by a bounded amount.  On the polyline every real corner carries
+ * the velocity-jump cap and the arm all but stops there.  Here corner i is replaced by a parabolic blend: the quadratic Bezier curve with
+ * the control points x_i - beta_i d_{i-1}, x_i, x_i + beta_i d_i, traversed at constant acceleration.  Notation as above: d_i = x_{i+1} -
+ * x_i, Delta_i = d_i - d_{i-1}, V_i, A_i, J_i as in edmp_time_rows_dev, and K_i = min_j amax_j / |Delta_ij| over the joints with
+ * Delta_ij != 0.  All arithmetic in f64, every operation rounded on its own (no fused multiply-add), min(a, b) = b < a ? b : a.
+ *
+ * 1. edmp_blend_rows_dev / edmp_scenes_blend_rows_dev choose beta (blend_rows_kernel: one 256-thread workgroup per listed row, thread =
+ * (corner, configuration)).  X_dev (n, 7, N) f64, 2 <= N <= 64, is only read; vmax, amax, jump as above; deviation[7] [rad], finite and
+ * > 0, the largest departure from the polyline per joint; reach in (0, 0.45], the largest beta; substeps K_b in 1..8; halvings H in 0..8.
+ * Per interior waypoint i = 1..N-2, in this order:
+ *   code 0, beta = 0: d_{i-1} = 0 or d_i = 0 (a zero segment beside it, a repeated waypoint included) or Delta_i = 0 in every joint.
+ *   code 1 (not needed), beta = 0: not J_i^2 < min(V_{i-1}^2, V_i^2) - the corner cap does not bind there, and a blend would only
+ *     shorten the straight parts beside it.
+ *   otherwise beta0 = min(reach, min_j (4.0 * deviation_j) / |Delta_ij|) in joint order, and for h = 0..H with beta = beta0 * 2^-h:
+ *     not (2.0 * beta) * K_i > J_i^2: code 2 (no gain: the blend's cap is no better than the jump cap), beta = 0, stop;
+ *     the K_b + 1 configurations at u = (double)k / (double)K_b, k = 0..K_b:
+ *       q_j(u) = x_ij + beta * ((u * u) * d_ij - ((1.0 - u) * (1.0 - u)) * d_{i-1,j}),  d_ij = x_{i+1,j} - x_ij, d_{i-1,j} = x_ij - x_{i-1,j},
+ *     each tested against the row's own scene's obstacles and kinds by edmp_success_rows_dev's own test (nine link boxes, 15-axis test for
+ *     boxes, clipped-polytope test for cylinders, touching counts);  no hit: code 3 (blended), this beta is kept, halved = h, stop.
+ *   all H + 1 tries hit: code 4 (blocked), beta = 0.
+ * Both ends are code 0, beta 0.  Outputs: beta_dev (n, N) f64, code_dev (n, N) int32, halved_dev (n, N) int32 (0 unless code 3),
+ * tested_dev (n,) int32 = the configurations of the row's tries, K_b + 1 for every (corner, h) that reached the test.  A row with a
+ * non-finite element is left alone: code -1, beta NaN, halved 0, tested 0.  rows_host: n_rows row indices (host, any order, no
+ * duplicates), or NULL = every row (n_rows is ignored); the entries of a row outside the list are NOT written.
+ * Guarantees: the blend of corner i runs from x_i - beta d_{i-1} to x_i + beta d_i and is tangent to both segments there; it departs from
+ * the polyline by at most beta |Delta_ij| / 4 <= deviation_j in joint j (at u = 1/2; every point of the curve is a convex combination of
+ * points of the two segments); beta <= reach <= 0.45 keeps neighbouring blends apart; every accepted blend was tested at its K_b + 1
+ * configurations, both ends included, by the success check's own test - what lies between them is as untested as what lies between the
+ * success check's own substeps.  Self-collision is NOT tested: edmp_self_collision_rows_dev stays the check.  dh_f64 as in
+ * edmp_success_rows_dev.  edmp_blend_rows_dev needs a single-scene guide, any n >= 1; edmp_scenes_blend_rows_dev a bound scene batch,
+ * X (S*B, 7, N).  They read nothing of the sampler, do NOT end a segmented run, and synchronise the stream.
+ *
+ * 2. edmp_time_blended_rows_dev times the blended path (time_blended_rows_kernel: one wave per row, lane = waypoint).  beta_dev (n, N)
+ * as stage 1 wrote it: 0 <= beta_i <= 0.45, 0 at both ends and beside a zero segment.  The rule is edmp_time_rows_dev's with two changes:
+ *   l_i = (1.0 - beta_i) - beta_{i+1}: the straight part of segment i, from s = beta_i to s = 1 - beta_{i+1} of it;
+ *   c_i = min(V_{i-1}^2, V_i^2, beta_i > 0 ? (2.0 * beta_i) * K_i : J_i^2): on blend i the joint acceleration is y_i Delta_i / (2 beta_i);
+ *   forward y_{i+1} = min(c_{i+1}, y_i + (2.0 * A_i) * l_i), backward y_i = min(y_i, y_{i+1} + (2.0 * A_i) * l_i), zero segments as above;
+ *   p_i = min(V_i^2, (y_i + y_{i+1}) / 2 + A_i * l_i);  t_acc, t_dec as above,  t_cru = max(0, l_i - (p_i - y_i) / (2 A_i) - (p_i -
+ *     y_{i+1}) / (2 A_i)) / sqrt p_i;
+ *   blend i is crossed at the constant path speed sqrt y_i in the time b_i = (2.0 * beta_i) / sqrt y_i (beta_i = 0: 0); a blended corner
+ *     has non-zero neighbours and l >= 0.1, so y_i > 0 there;
+ *   one running sum in the order line 0 (t_acc, t_cru, t_dec), blend 1, line 1, ...: times[i] = (the sum entering blend i, the sum leaving
+ *     it); times[0] = (0, 0); duration = the sum after line N-2;
+ *   limit_i as above, candidate 3 being the corner's cap: jump cap or blend acceleration cap, candidates 4 and 5 with (2 A) l.
+ * Outputs: y (n, N), phase (n, N-1, 3), times (n, N, 2), duration (n,), limit (n, N) int32, seg (n, N-1, 2) = A_i | p_i, blend (n, N) =
+ * b_i.  A row with a non-finite element of X or beta is not timed (NaN, limit -1).  With beta = 0 everywhere l_i = 1.0, (2 A_i) 1.0 and
+ * A_i 1.0 are exact: y, phase, duration, limit and seg have edmp_time_rows_dev's bits, and times[i] = (T_i, T_i).  Consequences: the
+ * velocity is continuous at a blended corner; |qdot_j| <= vmax_j everywhere, |qddot_j| <= amax_j on straight parts and on blends; y is
+ * the component-wise largest point of {0 <= y_i <= c_i, |y_{i+1} - y_i| <= 2 A_i l_i}.  Does not synchronise.
+ *
+ * 3. edmp_sample_blended_rows_dev samples that motion (sample_blended_rows_kernel: workgroup = listed row x 256 samples); rows_host,
+ * period, M, count, the goal's bits at rest at and past the duration and the NaN row as in edmp_sample_rows_dev.  At t < duration: the
+ * flat times array F (2 N values) gives the starts of the 2 N - 3 pieces: piece p starts at F[p + 1]; p even is the straight part of
+ * segment i = p / 2, p odd is blend i = (p + 1) / 2; the piece is the largest p with F[p + 1] <= t, tau = t - F[p + 1].
+ *   straight part: s and sdot from the closed-form quadratic of the phase as above, with l_i in the place of 1 in the third phase, s
+ *     clamped to [0, l_i];  q = x_i + (beta_i + s) * d_i,  qdot = d_i * sdot;
+ *   blend: u = (tau * sqrt y_i) / (2.0 * beta_i) clamped to [0, 1];  q as in stage 1;  qdot_j = sqrt y_i * ((1.0 - u) * d_{i-1,j} + u * d_ij).
+ * With beta = 0 everywhere q, qdot and count have edmp_sample_rows_dev's bits.  Synchronises.
+ * Stages 2 and 3 need a context only, leave the epoch alone and do NOT end a segmented run.  Refusals of all four (N, n, limits,
+ * deviation, reach, substeps, halvings, period, M, rows out of range or listed twice, null pointers, the wrong kind of bound guide) come
+ * before any device call and name the offending value. */
+int edmp_blend_rows_dev(edmp_ctx* ctx, const double* X_dev, int n, int N, const int32_t* rows_host, int n_rows, const double* vmax,
+                        const double* amax, const double* jump, const double* deviation, double reach, int substeps, int halvings,
+                        const double* dh_f64, double* beta_dev, int32_t* code_dev, int32_t* halved_dev, int32_t* tested_dev);
+int edmp_scenes_blend_rows_dev(edmp_ctx* ctx, const double* X_dev, int S, int B, int N, const int32_t* rows_host, int n_rows,
+                               const double* vmax, const double* amax, const double* jump, const double* deviation, double reach,
+                               int substeps, int halvings, const double* dh_f64, double* beta_dev, int32_t* code_dev,
+                               int32_t* halved_dev, int32_t* tested_dev);
+int edmp_time_blended_rows_dev(edmp_ctx* ctx, const double* X_dev, int n, int N, const double* beta_dev, const double* vmax,
+                               const double* amax, const double* jump, double* y_dev, double* phase_dev, double* times_dev,
+                               double* duration_dev, int32_t* limit_dev, double* seg_dev, double* blend_dev);
+int edmp_sample_blended_rows_dev(edmp_ctx* ctx, const double* X_dev, int n, int N, const double* beta_dev, const double* y_dev,
+                                 const double* phase_dev, const double* times_dev, const double* duration_dev, const double* seg_dev,
+                                 const int32_t* rows_host, int n_rows, double period, int M, double* q_dev, double* qd_dev,
+                                 int32_t* count_dev);
+
 /* ---- self-collision of every row (csrc/selfcol.hip) ------------------------------------------------------------- */
 /* Stands for the `self_collision` metric of the reference's evaluation package (mpinets/metrics.py:278-292, 351-361; a plan with
  * self-collision counts as a physical violation, :505), which asks robofin / pybullet - both absent: like the success check a geometric

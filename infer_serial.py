@@ -331,24 +331,47 @@ def _score(job, on, X, starts, goals, tb):
     lead = lambda d: None if d is None else {k: on.scenes(v) for k, v in d.items()}  # noqa: E731
     of = lambda d, *at: None if d is None else {k: v[at] for k, v in d.items()}  # noqa: E731
     idx, vols, X, chk, met, selfcol, goal, chosen = on.scenes(idx), on.scenes(vols), on.host(X), lead(chk), lead(met), lead(selfcol), lead(goal), lead(chosen)
-    timed = _time_plans(job, obj.ctx, np.stack([X[s][int(i)] for s, i in enumerate(idx)])) if job.time_plan is not None else None
+    timed = _time_plans(job, on, X, idx) if job.time_plan is not None else None
     return [SimpleNamespace(idx=int(i), vols=vols[s], trajectory=X[s][int(i)], met=of(met, s), selfcol=of(selfcol, s), chosen=of(chosen, s, place[s]), goal=of(goal, s, place[s]),
                             chk={k: (v if np.ndim(v) else int(v)) for k, v in of(chk, s).items()},  # (the per-row flags, and the scene's counts as ints)
                             repair=None if moved is None else (moved[s], clear[s]), shortcut=None if cut is None else cut[s], timed=None if timed is None else timed[s])
             for s, i in enumerate(idx)]
 
 
-def _time_plans(job, ctx, plans):
-    """the chosen plans (S, 7, N) timed under the default joint velocity, acceleration and corner-jump limits (EV.time_rows_on, one launch for
-    the group) -> per scene dict(duration_s, binding_constraints = how many waypoints each constraint binds), and with a period (job.time_plan
-    a number) the sample count of the timed motion at that period, from the sampler itself (EV.sample_rows_on, one launch)"""
+def _time_plans(job, on, X, idx):
+    """the chosen plans - row idx[s] of the host state X (S, B, 7, N) - timed under the default joint velocity, acceleration and corner-jump
+    limits (EV.time_rows_on, one launch for the group) -> per scene dict(duration_s, binding_constraints = how many waypoints each
+    constraint binds), and with a period (job.time_plan a number) the sample count of the timed motion at that period, from the sampler
+    itself (EV.sample_rows_on, one launch).  With job.blend (a deviation [rad]) the chosen plans' corners are blended under the exact
+    collision check against their own scenes (blend_rows on the chosen rows alone, one launch) and the blended path is timed
+    (EV.time_blended_rows_on): `blended_duration_s`, `corner_codes` (the census of the interior waypoints' blend codes), `blend_deviation_rad`
+    and `blend_reach` are added, and a period samples the faster of the two motions (`sampled_motion`)."""
+    obj, ctx = on.obj, on.obj.ctx
+    plans = np.stack([X[s][int(i)] for s, i in enumerate(idx)])
     prof = EV.time_rows_on(ctx, plans)
     out = [dict(duration_s=float(d), binding_constraints={name: int(np.count_nonzero(lim == k)) for k, name in enumerate(EV.LIMIT_NAMES)})
            for d, lim in zip(prof["duration"], prof["limit"])]
+    if job.blend is None:
+        if job.time_plan is not True:
+            count = EV.sample_rows_on(ctx, plans, prof, job.time_plan)["count"]
+            for o, c in zip(out, count):
+                o.update(time_period_s=float(job.time_plan), timed_samples=int(c))
+        return out
+    S, B, _, N = X.shape
+    rows = [s * B + int(i) for s, i in enumerate(idx)]
+    bl = obj.blend_rows(X if on.grouped else X[0], deviation=job.blend, reach=job.blend_reach, substeps=CHECK_SUBSTEPS, rows=rows)
+    beta, code = bl["beta"].reshape(S * B, N)[rows], bl["code"].reshape(S * B, N)[rows]
+    bprof = EV.time_blended_rows_on(ctx, plans, beta)
+    for o, d, c in zip(out, bprof["duration"], code):
+        o.update(blended_duration_s=float(d), corner_codes={name: int(np.count_nonzero(c[1:-1] == k)) for k, name in enumerate(EV.BLEND_CODE_NAMES)},
+                 blend_deviation_rad=float(job.blend), blend_reach=float(job.blend_reach))
     if job.time_plan is not True:
-        count = EV.sample_rows_on(ctx, plans, prof, job.time_plan)["count"]
-        for o, c in zip(out, count):
-            o.update(time_period_s=float(job.time_plan), timed_samples=int(c))
+        faster = [s for s in range(S) if bprof["duration"][s] < prof["duration"][s]]  # (a NaN duration compares false: the polyline's count, 0)
+        plain = [s for s in range(S) if s not in faster]
+        for motion, listed, sample, p in (("blended", faster, EV.sample_blended_rows_on, bprof), ("polyline", plain, EV.sample_rows_on, prof)):
+            if listed:
+                for s, c in zip(listed, sample(ctx, plans, p, job.time_plan, rows=listed)["count"]):
+                    out[s].update(time_period_s=float(job.time_plan), timed_samples=int(c), sampled_motion=motion)
     return out
 
 
@@ -492,6 +515,11 @@ def _print_scene(r, n, tally, prefix=""):
         census = ", ".join(f"{k} {v}" for k, v in r["binding_constraints"].items() if v)
         print(f"    chosen plan: duration_s {r['duration_s']:.3f} under the joint velocity / acceleration / corner limits; waypoints bound by: {census}"
               + (f"; {r['timed_samples']} samples at {r['time_period_s']:g} s" if "timed_samples" in r else ""))
+        if "blended_duration_s" in r:
+            census = ", ".join(f"{k} {v}" for k, v in r["corner_codes"].items() if v)
+            print(f"    chosen plan: blended_duration_s {r['blended_duration_s']:.3f} with corner blends within {r['blend_deviation_rad']:g} rad of the polyline "
+                  f"(reach {r['blend_reach']:g}) under the exact collision check; corners: {census}"
+                  + (f"; the samples are the {r['sampled_motion']} motion's" if "sampled_motion" in r else ""))
     if "self_collision_free" in r:
         print(f"    self-collision free {r['self_collision_free']} ({r['rows_self_collision_free']}/{r['rows']} rows of the batch)   running {tally.self_free}/{n}")
         if "ensemble" in r:
@@ -524,7 +552,7 @@ def _print_summary(summary):
 
 def run(cfg_path, dataset=None, max_scenes=None, verbose=True, scenes_in_flight=1, shard_scenes=True, scenes_per_launch=1, ensemble_report=False, prefer=None,
         ik_seeds=0, ik_tool=None, ik_seed=0, self_collision=False, device_noise=None, repair=0, repair_margin=0.02, repair_step=0.02, shortcut=0,
-        time_plan=None):
+        time_plan=None, blend=None, blend_reach=0.4):
     """The reference's scene loop (infer_serial.py:95-170).  Under ``torch.distributed.run`` (one process per GPU, extension: the
     reference is one process) the scenes are dealt round-robin to the ranks - scene i of the cfg's order goes to rank i mod world -
     and nothing is exchanged until `job_summary` adds the tallies up: scenes are independent problems, this is the problem set's natural
@@ -595,6 +623,14 @@ def run(cfg_path, dataset=None, max_scenes=None, verbose=True, scenes_in_flight=
     constraint) to the result; a number is also the period [s] at which that motion is sampled (evaluation.sample_rows), adding
     `time_period_s` and `timed_samples`.  ``prefer`` = "fastest" picks, inside the trust region, the row with the shortest such duration.
 
+    ``blend`` = DEVIATION [rad] (an extension; None = off: nothing is launched and every printed and returned value is what it was; needs
+    ``time_plan``) also blends the chosen plan's corners (IntersectionVolumeGuide / SceneBatch.blend_rows on the chosen rows: parabolic
+    blends within DEVIATION of the polyline per joint and at most ``blend_reach`` <= 0.45 of a segment long, each accepted only if the
+    success check's own test clears its CHECK_SUBSTEPS + 1 configurations) and times the blended path (evaluation.time_blended_rows),
+    adding `blended_duration_s`, `corner_codes` (how many interior waypoints got each blend code), `blend_deviation_rad` and `blend_reach`
+    next to `duration_s`; with a period the faster of the two motions is the one sampled and `sampled_motion` names it.  The selection
+    does not see blended durations.
+
     ``shortcut`` = PASSES > 0 (an extension; 0 = off: nothing is launched and every printed and returned value is what it was) sends the
     whole batch through shortcut_rows after the repair and before the selection (IntersectionVolumeGuide.shortcut_rows; a scene group
     through SceneBatch.shortcut_rows in one launch): at most PASSES passes of joint-space shortcuts, each accepted only if the success
@@ -615,6 +651,14 @@ def run(cfg_path, dataset=None, max_scenes=None, verbose=True, scenes_in_flight=
         time_plan = float(time_plan)
         if not (np.isfinite(time_plan) and time_plan > 0):
             raise ValueError(f"time_plan must be None (off), True, or a sample period > 0 [s], got {time_plan}")
+    if blend is not None:
+        blend, blend_reach = float(blend), float(blend_reach)
+        if time_plan is None:
+            raise ValueError("blend needs time_plan: the blended motion is reported next to the timed one")
+        if not (np.isfinite(blend) and blend > 0):
+            raise ValueError(f"blend must be None (off) or a deviation > 0 [rad], got {blend}")
+        if not 0 < blend_reach <= 0.45:
+            raise ValueError(f"blend_reach must lie in (0, 0.45], got {blend_reach}")
     shortcut = int(shortcut)
     if shortcut < 0:
         raise ValueError(f"shortcut must be >= 0 passes (0 = off), got {shortcut}")
@@ -634,7 +678,7 @@ def run(cfg_path, dataset=None, max_scenes=None, verbose=True, scenes_in_flight=
         total_batch_size=guide_cfgs["total_batch_size"], guide_numbers=guide_numbers,
         guide_rows=GC.split_rows(int(cfg["guide"]["total_rows"]), len(guide_numbers)) if cfg["guide"].get("total_rows") else guide_cfgs["batch_size_per_guide"],
         dataset=dataset, rank=rank, world=world, verbose=verbose, prefer=prefer, ensemble_report=ensemble_report, self_collision=self_collision, device_noise=device_noise,
-        repair=repair, repair_margin=repair_margin, repair_step=repair_step, shortcut=shortcut, time_plan=time_plan, ik_tool=ik_tool, iks=[], feeder=None, results=[], tally=SimpleNamespace(success=0, strict=0, self_free=0))
+        repair=repair, repair_margin=repair_margin, repair_step=repair_step, shortcut=shortcut, time_plan=time_plan, blend=blend, blend_reach=blend_reach, ik_tool=ik_tool, iks=[], feeder=None, results=[], tally=SimpleNamespace(success=0, strict=0, self_free=0))
     k = max(1, int(scenes_in_flight))
     base = get_context(device)
     job.lanes = _lanes(job, base, k, model["model_dir"], max_batch=job.total_batch_size * kl)
@@ -702,7 +746,13 @@ def main(argv=None):
     parser.add_argument("--shortcut", type=int, default=0, metavar="PASSES", help="after the repair and before the selection, shorten every row of each batch by at most "
                                                                                     "PASSES passes of joint-space shortcuts, each accepted only under the exact collision check "
                                                                                     "(extension; 0 = off)")
+    parser.add_argument("--blend", type=float, default=None, metavar="DEVIATION", help="with --time-plan: blend the chosen plan's corners by parabolic blends that stay "
+                        "within DEVIATION [rad] of the polyline per joint and pass the exact collision check, and report blended_duration_s and the census of "
+                        "the corner codes next to duration_s; with a PERIOD the faster of the two motions is sampled (extension; off: nothing changes)")
+    parser.add_argument("--blend-reach", type=float, default=0.4, metavar="R", help="the largest part of a neighbouring segment that a blend may take, in (0, 0.45]")
     args = parser.parse_args(argv)
+    if args.blend is not None and args.time_plan is None:
+        parser.error("--blend requires --time-plan")
     ik_tool = args.ik_tool
     if ik_tool is not None and ik_tool not in ("flange", "hand"):
         if ik_tool.endswith(".npy"):
@@ -715,7 +765,8 @@ def main(argv=None):
         np.random.seed(args.seed + rank)
     results = run(args.cfg_path, scenes_in_flight=args.scenes_in_flight, max_scenes=args.max_scenes, scenes_per_launch=args.scenes_per_launch,
                   ensemble_report=args.ensemble_report, prefer=args.prefer, ik_seeds=args.ik_seeds, ik_tool=ik_tool, self_collision=args.self_collision,
-                  device_noise=args.device_noise, repair=args.repair, repair_margin=args.repair_margin, repair_step=args.repair_step, shortcut=args.shortcut, time_plan=args.time_plan)
+                  device_noise=args.device_noise, repair=args.repair, repair_margin=args.repair_margin, repair_step=args.repair_step, shortcut=args.shortcut, time_plan=args.time_plan,
+                  blend=args.blend, blend_reach=args.blend_reach)
     if args.results_json:
         rows = [{k: v for k, v in r.items() if k != "trajectory"} for r in results]
         with open(args.results_json + ("" if rank == 0 else f".rank{rank}"), "w") as f:
