@@ -297,7 +297,9 @@ def _sample_setup(ctx, n, profile, period, rows, max_samples):
     if listed is not None and listed.size and (listed.min() < 0 or listed.max() >= n):
         raise ValueError(f"rows must lie in 0..{n - 1}, got {listed.tolist()}")
     dur = profile["duration"]
-    dur = (ctx.to_host(dur) if isinstance(dur, torch.Tensor) else np.asarray(dur, dtype=np.float64)).reshape(-1)
+    if isinstance(dur, torch.Tensor):  # read on this context's stream, so adopted HERE: the trajectories may be a host array, and then nothing was adopted yet
+        dur = ctx.to_host(ctx.adopt(dur) if dur.is_cuda else dur)
+    dur = np.asarray(dur, dtype=np.float64).reshape(-1)
     order = np.arange(n) if listed is None else listed
     counts = [sample_count(dur[r], period) for r in order]
     if max_samples is None:

@@ -281,6 +281,7 @@ class _SlotObject:
             f = flags.view(3, *shape)
             with torch.cuda.stream(ctx.stream):
                 cf = f[1] < 0
+            ctx.hand_over(cf)  # (a stream-wide wait: it covers cf, enqueued after the synchronisation that brought the counts back, and the flags alike)
             out.update(ok=f[0], first=f[1], within=f[2], collision_free=cf)
         else:
             f = ctx.to_host(flags).reshape(3, *shape)
