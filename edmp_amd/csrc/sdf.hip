@@ -98,6 +98,7 @@
 #include "common.h"
 #include "chain.h"
 #include "guide.h"
+#include "rowlist.h"  // check_rows: the row list of the repair calls
 
 #include <algorithm>
 #include <cmath>
@@ -1483,15 +1484,7 @@ static int sdf_repair_rows(edmp_ctx* ctx, const char* what, double* X_dev, int S
     EDMP_REQUIRE(std::isfinite(step) && step > 0.0, "%s: step %g must be finite and > 0", what, step);
     EDMP_REQUIRE(std::isfinite(max_step) && max_step > 0.0, "%s: max_step %g must be finite and > 0", what, max_step);
     for (int i = 0; i < S * 7; ++i) EDMP_REQUIRE(std::isfinite(starts[i]) && std::isfinite(goals[i]), "%s: scene %d: non-finite start / goal", what, i / 7);
-    if (rows_host) {  // two workgroups on one row would race
-        EDMP_REQUIRE(n_rows >= 1 && n_rows <= n, "%s: %d listed rows outside 1..%d", what, n_rows, n);
-        std::vector<char> seen((size_t)n, 0);
-        for (int i = 0; i < n_rows; ++i) {
-            EDMP_REQUIRE(rows_host[i] >= 0 && rows_host[i] < n, "%s: rows[%d] = %d outside 0..%d", what, i, (int)rows_host[i], n - 1);
-            EDMP_REQUIRE(!seen[rows_host[i]], "%s: rows[%d] = %d is listed twice", what, i, (int)rows_host[i]);
-            seen[rows_host[i]] = 1;
-        }
-    }
+    if (int rc = check_rows(what, rows_host, n_rows, n)) return rc;  // (rowlist.h)
     const int launch = rows_host ? n_rows : n;
     EDMP_HIP_CHECK(hipSetDevice(ctx->device));
     if (!rb.startgoal)

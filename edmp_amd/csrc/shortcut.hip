@@ -20,6 +20,7 @@
 #include "chain.h"
 #include "guide.h"
 #include "linkbox.h"  // Robot64, SceneSlices, configuration_hits, interp_joint: shared with success.hip
+#include "rowlist.h"  // check_rows, rows_upload, rows_call_end: shared with timing.hip and blend.hip
 
 // the gain and the piece are stated as separately rounded f64 operations (the host rule's): no fused multiply-add in this file's own code
 #pragma clang fp contract(off)
@@ -207,8 +208,7 @@ __global__ __launch_bounds__(256) void shortcut_rows_kernel(ShortcutArgs a, Scen
 using namespace edmp;
 
 // edmp_shortcut_rows_dev and edmp_scenes_shortcut_rows_dev behind their own state checks: n = S x rps rows of the state X (n, 7, N).
-// Every refusal comes before any device call.  The row list goes into a block of the call's own, taken from the context's pool and
-// given back after the call's synchronise: nothing of the guide, the sampler or a segmented run is replaced.
+// Every refusal comes before any device call.  The row list goes into a block of the call's own (rowlist.h).
 static int shortcut_rows(edmp_ctx* ctx, const char* what, bool batch, double* X_dev, int S, int rps, int N, const int32_t* rows_host, int n_rows,
                          int substeps, int passes, double min_gain, const double* dh_f64, int32_t* accepted_dev, int32_t* tested_dev, double* length_dev,
                          int32_t* spans_dev, int log_cap) {
@@ -220,26 +220,11 @@ static int shortcut_rows(edmp_ctx* ctx, const char* what, bool batch, double* X_
     EDMP_REQUIRE(passes >= 0 && passes <= EDMP_MAX_SHORTCUT_PASSES, "%s: passes %d outside 0..%d", what, passes, EDMP_MAX_SHORTCUT_PASSES);
     EDMP_REQUIRE(std::isfinite(min_gain) && min_gain >= 0.0, "%s: min_gain %g must be finite and >= 0", what, min_gain);
     EDMP_REQUIRE(log_cap >= 0 && (log_cap == 0 || spans_dev), "%s: log_cap %d needs log_cap >= 0 and a span log of that many entries per row", what, log_cap);
-    if (rows_host) {  // two workgroups on one row would race
-        EDMP_REQUIRE(n_rows >= 1 && n_rows <= n, "%s: %d listed rows outside 1..%d", what, n_rows, n);
-        std::vector<char> seen((size_t)n, 0);
-        for (int i = 0; i < n_rows; ++i) {
-            EDMP_REQUIRE(rows_host[i] >= 0 && rows_host[i] < n, "%s: rows[%d] = %d outside 0..%d", what, i, (int)rows_host[i], n - 1);
-            EDMP_REQUIRE(!seen[rows_host[i]], "%s: rows[%d] = %d is listed twice", what, i, (int)rows_host[i]);
-            seen[rows_host[i]] = 1;
-        }
-    }
+    if (int rc = check_rows(what, rows_host, n_rows, n)) return rc;
     const int launch = rows_host ? n_rows : n;
     EDMP_HIP_CHECK(hipSetDevice(ctx->device));
     int32_t* rows_dev = nullptr;
-    if (rows_host) {
-        if (int rc = ctx_alloc(ctx, (void**)&rows_dev, (size_t)n_rows * sizeof(int32_t))) return rc;
-        const hipError_t e = hipMemcpyAsync(rows_dev, rows_host, (size_t)n_rows * sizeof(int32_t), hipMemcpyHostToDevice, ctx->stream);
-        if (e != hipSuccess) {
-            ctx_release(ctx, rows_dev);
-            EDMP_HIP_CHECK(e);
-        }
-    }
+    if (int rc = rows_upload(ctx, rows_host, n_rows, &rows_dev)) return rc;
     ShortcutArgs a;
     a.X = X_dev;
     a.rows = rows_dev;
@@ -255,12 +240,7 @@ static int shortcut_rows(edmp_ctx* ctx, const char* what, bool batch, double* X_
     a.length = length_dev;
     a.spans = spans_dev;
     hipLaunchKernelGGL(shortcut_rows_kernel, dim3(launch), dim3(256), 0, ctx->stream, a, scene_slices_of(g, batch, S, rps), robot64_of(g, dh_f64));
-    const hipError_t e = hipGetLastError();
-    const hipError_t w = hipStreamSynchronize(ctx->stream);  // the list lives in the caller's array, its device block goes back to the pool
-    if (rows_dev) ctx_release(ctx, rows_dev);
-    EDMP_HIP_CHECK(w);
-    EDMP_HIP_CHECK(e);
-    return EDMP_OK;
+    return rows_call_end(ctx, rows_dev);
 }
 
 extern "C" int edmp_shortcut_rows_dev(edmp_ctx* ctx, double* X_dev, int n, int N, const int32_t* rows_host, int n_rows, int substeps, int passes,

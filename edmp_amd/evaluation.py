@@ -205,6 +205,7 @@ def batch_metrics(trajectories, device="cuda:0", dt: float = 0.1, return_device:
 
 
 PROFILE_KEYS = ("y", "phase", "times", "duration", "limit", "seg")  # edmp_time_rows_dev's outputs, what edmp_sample_rows_dev reads
+BLENDED_PROFILE_KEYS = PROFILE_KEYS + ("blend",)  # edmp_time_blended_rows_dev's outputs; the profile dict also carries `beta`
 LIMIT_NAMES = ("rest", "velocity_before", "velocity_after", "corner_jump", "acceleration", "deceleration")  # the codes of `limit`
 
 
@@ -231,28 +232,39 @@ def _device_f64(ctx, v, want, name, X):
     return t
 
 
-def time_rows_on(ctx, trajectories, vmax=None, amax=None, jump=None, scale=(1, 1), return_device: bool = False) -> dict:
-    """edmp_time_rows_dev on the context `ctx` (runtime.Context): see time_rows."""
+def _time_rows(ctx, X, beta, limits, return_device):
+    """The one timing call behind time_rows_on (beta None: edmp_time_rows_dev, PROFILE_KEYS) and time_blended_rows_on (beta (n, N):
+    edmp_time_blended_rows_dev, BLENDED_PROFILE_KEYS, two times per waypoint, beta in the result).  X and beta: device tensors that the
+    caller has brought onto ctx's stream; limits = (vmax, amax, jump)."""
     import torch
 
     from . import _capi
     from .runtime import ptr
 
-    vm, am, jm = franka.timing_limits(vmax, amax, jump, scale)
-    X = _rows_state(ctx, trajectories)
+    blended = beta is not None
+    entry, keys, given = ("edmp_time_blended_rows_dev", BLENDED_PROFILE_KEYS, (X, beta)) if blended else ("edmp_time_rows_dev", PROFILE_KEYS, (X,))
     n, N = X.shape[0], X.shape[2]
-    out = dict(y=ctx.empty((n, N), torch.float64), phase=ctx.empty((n, max(N - 1, 0), 3), torch.float64), times=ctx.empty((n, N), torch.float64),
-               duration=ctx.empty((n,), torch.float64), limit=ctx.empty((n, N), torch.int32), seg=ctx.empty((n, max(N - 1, 0), 2), torch.float64))
-    _capi.check(ctx.lib.edmp_time_rows_dev(ctx.h, ptr(X), n, N, _capi.as_pd(vm), _capi.as_pd(am), _capi.as_pd(jm), *(ptr(out[k]) for k in PROFILE_KEYS)),
-                "edmp_time_rows_dev")
+    shape = dict(y=(n, N), phase=(n, max(N - 1, 0), 3), times=(n, N, 2) if blended else (n, N), duration=(n,), limit=(n, N), seg=(n, max(N - 1, 0), 2),
+                 blend=(n, N))
+    out = {k: ctx.empty(shape[k], torch.int32 if k == "limit" else torch.float64) for k in keys}
+    _capi.check(getattr(ctx.lib, entry)(ctx.h, ptr(X), n, N, *(ptr(t) for t in given[1:]), *(_capi.as_pd(v) for v in limits), *(ptr(out[k]) for k in keys)), entry)
     if return_device:
-        X.record_stream(ctx.stream)  # (the kernel may still be reading it when the caller drops the tensor)
-        for k in PROFILE_KEYS:
+        for t in given:
+            t.record_stream(ctx.stream)  # (the kernel may still be reading it when the caller drops the tensor)
+        for k in keys:
             ctx.hand_over(out[k])
     else:
-        out = {k: ctx.to_host(out[k]) for k in PROFILE_KEYS}
-    out.update(vmax=vm, amax=am, jump=jm)
+        out = {k: ctx.to_host(out[k]) for k in keys}
+    if blended:
+        out["beta"] = beta if return_device else ctx.to_host(beta)
+    out.update(zip(("vmax", "amax", "jump"), limits))
     return out
+
+
+def time_rows_on(ctx, trajectories, vmax=None, amax=None, jump=None, scale=(1, 1), return_device: bool = False) -> dict:
+    """edmp_time_rows_dev on the context `ctx` (runtime.Context): see time_rows."""
+    limits = franka.timing_limits(vmax, amax, jump, scale)
+    return _time_rows(ctx, _rows_state(ctx, trajectories), None, limits, return_device)
 
 
 def time_rows(trajectories, vmax=None, amax=None, jump=None, scale=(1, 1), device="cuda:0", return_device: bool = False) -> dict:
@@ -285,11 +297,12 @@ def sample_count(duration, period) -> int:
     return 1 + k
 
 
-def _sample_setup(ctx, n, profile, period, rows, max_samples):
-    """what both samplers settle before their call: the period, the checked row list, M and the output tensors ->
-    (period, listed, R, M, q, qd, count)"""
+def _sample_setup(ctx, X, want, profile, period, rows, max_samples):
+    """what both samplers settle before their call: the period, the checked row list, M, the output tensors and the arrays of `want`
+    (name -> shape) that the entry reads of the profile, on ctx's stream -> (period, listed, R, M, q, qd, count, prof)"""
     import torch
 
+    n = X.shape[0]
     period = float(period)
     if not (np.isfinite(period) and period > 0):
         raise ValueError(f"period must be finite and > 0, got {period!r}")
@@ -314,7 +327,8 @@ def _sample_setup(ctx, n, profile, period, rows, max_samples):
         q = torch.empty((R, 7, max(M, 0)), dtype=torch.float64, device=ctx.device)
         qd = torch.empty_like(q)
         count = torch.empty((R,), dtype=torch.int32, device=ctx.device)
-    return period, listed, R, M, q, qd, count
+    prof = {k: _device_f64(ctx, profile[k], want[k], f"profile[{k!r}]", X) for k in want}
+    return period, listed, R, M, q, qd, count, prof
 
 
 def _sample_result(ctx, q, qd, count, M, period, return_device):
@@ -326,20 +340,27 @@ def _sample_result(ctx, q, qd, count, M, period, return_device):
     return dict(q=ctx.to_host(q), qd=ctx.to_host(qd), count=ctx.to_host(count), t=t)
 
 
-def sample_rows_on(ctx, trajectories, profile, period, rows=None, max_samples=None, return_device: bool = False) -> dict:
-    """edmp_sample_rows_dev on the context `ctx` (runtime.Context): see sample_rows."""
+def _sample_rows(ctx, X, profile, period, rows, max_samples, return_device, blended):
+    """The one sampler call behind sample_rows_on (edmp_sample_rows_dev) and sample_blended_rows_on (edmp_sample_blended_rows_dev: beta
+    too, two times per waypoint).  X: the state on ctx's stream."""
     from . import _capi
     from .runtime import ptr
 
-    X = _rows_state(ctx, trajectories)
     n, N = X.shape[0], X.shape[2]
-    want = dict(y=(n, N), phase=(n, N - 1, 3), times=(n, N), duration=(n,), seg=(n, N - 1, 2))  # (limit is a report, the sampler does not read it)
-    period, listed, R, M, q, qd, count = _sample_setup(ctx, n, profile, period, rows, max_samples)
-    prof = {k: _device_f64(ctx, profile[k], want[k], f"profile[{k!r}]", X) for k in want}
-    _capi.check(ctx.lib.edmp_sample_rows_dev(ctx.h, ptr(X), n, N, ptr(prof["y"]), ptr(prof["phase"]), ptr(prof["times"]), ptr(prof["duration"]), ptr(prof["seg"]),
-                                             None if listed is None else _capi.as_pi32(listed), 0 if listed is None else R, period, M, ptr(q), ptr(qd), ptr(count)),
-                "edmp_sample_rows_dev")
+    # what the entry reads of the profile, in its argument order (limit and blend are reports, the samplers do not read them)
+    want = dict(y=(n, N), phase=(n, N - 1, 3), times=(n, N, 2) if blended else (n, N), duration=(n,), seg=(n, N - 1, 2))
+    if blended:
+        want = dict(beta=(n, N), **want)
+    entry = "edmp_sample_blended_rows_dev" if blended else "edmp_sample_rows_dev"
+    period, listed, R, M, q, qd, count, prof = _sample_setup(ctx, X, want, profile, period, rows, max_samples)
+    _capi.check(getattr(ctx.lib, entry)(ctx.h, ptr(X), n, N, *(ptr(prof[k]) for k in want), None if listed is None else _capi.as_pi32(listed),
+                                        0 if listed is None else R, period, M, ptr(q), ptr(qd), ptr(count)), entry)
     return _sample_result(ctx, q, qd, count, M, period, return_device)
+
+
+def sample_rows_on(ctx, trajectories, profile, period, rows=None, max_samples=None, return_device: bool = False) -> dict:
+    """edmp_sample_rows_dev on the context `ctx` (runtime.Context): see sample_rows."""
+    return _sample_rows(ctx, _rows_state(ctx, trajectories), profile, period, rows, max_samples, return_device, False)
 
 
 def sample_rows(trajectories, profile, period, rows=None, max_samples=None, device="cuda:0", return_device: bool = False) -> dict:
@@ -355,7 +376,6 @@ def sample_rows(trajectories, profile, period, rows=None, max_samples=None, devi
     return sample_rows_on(get_context(device), trajectories, profile, period, rows, max_samples, return_device)
 
 
-BLENDED_PROFILE_KEYS = PROFILE_KEYS + ("blend",)  # edmp_time_blended_rows_dev's outputs; the profile dict also carries `beta`
 BLEND_CODE_NAMES = ("none", "not_needed", "no_gain", "blended", "blocked")  # the codes of blend_rows' `code`; -1 = a row left alone
 
 
@@ -368,35 +388,13 @@ def blend_arguments(deviation, reach, substeps, halvings):
 
 def time_blended_rows_on(ctx, trajectories, beta, vmax=None, amax=None, jump=None, scale=(1, 1), return_device: bool = False) -> dict:
     """edmp_time_blended_rows_dev on the context `ctx` (runtime.Context): see time_blended_rows."""
-    import torch
-
-    from . import _capi
-    from .runtime import ptr
-
-    vm, am, jm = franka.timing_limits(vmax, amax, jump, scale)
+    limits = franka.timing_limits(vmax, amax, jump, scale)
     X = _rows_state(ctx, trajectories)
-    n, N = X.shape[0], X.shape[2]
-    b = _device_f64(ctx, beta, (n, N), "beta", X)
-    out = dict(y=ctx.empty((n, N), torch.float64), phase=ctx.empty((n, max(N - 1, 0), 3), torch.float64), times=ctx.empty((n, N, 2), torch.float64),
-               duration=ctx.empty((n,), torch.float64), limit=ctx.empty((n, N), torch.int32), seg=ctx.empty((n, max(N - 1, 0), 2), torch.float64),
-               blend=ctx.empty((n, N), torch.float64))
-    _capi.check(ctx.lib.edmp_time_blended_rows_dev(ctx.h, ptr(X), n, N, ptr(b), _capi.as_pd(vm), _capi.as_pd(am), _capi.as_pd(jm),
-                                                   *(ptr(out[k]) for k in BLENDED_PROFILE_KEYS)), "edmp_time_blended_rows_dev")
-    if return_device:
-        X.record_stream(ctx.stream)  # (the kernel may still be reading them when the caller drops the tensors)
-        b.record_stream(ctx.stream)
-        for k in BLENDED_PROFILE_KEYS:
-            ctx.hand_over(out[k])
-        out["beta"] = b
-    else:
-        out = {k: ctx.to_host(out[k]) for k in BLENDED_PROFILE_KEYS}
-        out["beta"] = ctx.to_host(b)
-    out.update(vmax=vm, amax=am, jump=jm)
-    return out
+    return _time_rows(ctx, X, _device_f64(ctx, beta, (X.shape[0], X.shape[2]), "beta", X), limits, return_device)
 
 
 def time_blended_rows(trajectories, beta, vmax=None, amax=None, jump=None, scale=(1, 1), device="cuda:0", return_device: bool = False) -> dict:
-    """Time every finished row along its BLENDED path (edmp_time_blended_rows_dev, csrc/blend.hip): trajectories (n, 7, N), 2 <= N <= 64,
+    """Time every finished row along its BLENDED path (edmp_time_blended_rows_dev, csrc/timing.hip): trajectories (n, 7, N), 2 <= N <= 64,
     and beta (n, N) as blend_rows gave it (guide.blend_rows: corner i is replaced by the parabolic blend from x_i - beta_i d_{i-1} to
     x_i + beta_i d_i) -> time_rows' profile dict with two changes - times is (n, N, 2) = the time entering | leaving waypoint i's blend, and
     limit code 3 means "corner: jump cap or blend acceleration cap" - plus blend (n, N) = the time spent on each blend and beta itself,
@@ -412,22 +410,11 @@ def time_blended_rows(trajectories, beta, vmax=None, amax=None, jump=None, scale
 
 def sample_blended_rows_on(ctx, trajectories, profile, period, rows=None, max_samples=None, return_device: bool = False) -> dict:
     """edmp_sample_blended_rows_dev on the context `ctx` (runtime.Context): see sample_blended_rows."""
-    from . import _capi
-    from .runtime import ptr
-
-    X = _rows_state(ctx, trajectories)
-    n, N = X.shape[0], X.shape[2]
-    want = dict(beta=(n, N), y=(n, N), phase=(n, N - 1, 3), times=(n, N, 2), duration=(n,), seg=(n, N - 1, 2))  # (limit and blend are reports, not read)
-    period, listed, R, M, q, qd, count = _sample_setup(ctx, n, profile, period, rows, max_samples)
-    prof = {k: _device_f64(ctx, profile[k], want[k], f"profile[{k!r}]", X) for k in want}
-    _capi.check(ctx.lib.edmp_sample_blended_rows_dev(ctx.h, ptr(X), n, N, ptr(prof["beta"]), ptr(prof["y"]), ptr(prof["phase"]), ptr(prof["times"]),
-                                                     ptr(prof["duration"]), ptr(prof["seg"]), None if listed is None else _capi.as_pi32(listed),
-                                                     0 if listed is None else R, period, M, ptr(q), ptr(qd), ptr(count)), "edmp_sample_blended_rows_dev")
-    return _sample_result(ctx, q, qd, count, M, period, return_device)
+    return _sample_rows(ctx, _rows_state(ctx, trajectories), profile, period, rows, max_samples, return_device, True)
 
 
 def sample_blended_rows(trajectories, profile, period, rows=None, max_samples=None, device="cuda:0", return_device: bool = False) -> dict:
-    """The blended, timed motion of the listed rows at a controller period (edmp_sample_blended_rows_dev, csrc/blend.hip): trajectories
+    """The blended, timed motion of the listed rows at a controller period (edmp_sample_blended_rows_dev, csrc/timing.hip): trajectories
     (n, 7, N) and the `profile` time_blended_rows gave for them (it carries beta) -> sample_rows' dict(q, qd (R, 7, M), count (R,), t (M,)).
     On a straight part q = x_i + (beta_i + s) d_i; on blend i q = x_i + beta_i (u^2 d_i - (1 - u)^2 d_{i-1}) and qdot = sqrt y_i ((1 - u)
     d_{i-1} + u d_i), u the fraction of the blend's time.  ``rows``, ``max_samples``, count, the goal's bits at rest past the duration and

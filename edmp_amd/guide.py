@@ -859,7 +859,7 @@ class IntersectionVolumeGuide(_SlotObject):
 
     def time_blended_rows(self, trajectories, beta, vmax=None, amax=None, jump=None, scale=(1, 1), return_device: bool = False):
         """evaluation.time_blended_rows on this guide's context: the fastest rest-to-rest motion along every row's blended path
-        (edmp_time_blended_rows_dev, csrc/blend.hip) -> the blended profile dict.  Reads nothing of the scene; leaves a segmented run running."""
+        (edmp_time_blended_rows_dev, csrc/timing.hip) -> the blended profile dict.  Reads nothing of the scene; leaves a segmented run running."""
         from .evaluation import time_blended_rows_on
 
         return time_blended_rows_on(self.ctx, trajectories, beta, vmax, amax, jump, scale, return_device)
@@ -1238,6 +1238,16 @@ class SceneBatch(_SlotObject):
         Xd.record_stream(self.ctx.stream)
         return out
 
+    def _flat_profile(self, profile, keys):
+        """a profile dict shaped (S, B, ...) -> the arrays of `keys` it holds, shaped (S*B, ...)"""
+        return {k: profile[k].reshape(self.n_scenes * self.batch_size, *profile[k].shape[2:]) for k in keys if k in profile}
+
+    def _scene_profile(self, out, keys):
+        """a profile dict shaped (S*B, ...) -> the same dict with the arrays of `keys` shaped (S, B, ...)"""
+        for k in keys:
+            out[k] = out[k].reshape(self.n_scenes, self.batch_size, *out[k].shape[1:])
+        return out
+
     def time_rows(self, trajectories, vmax=None, amax=None, jump=None, scale=(1, 1), return_device: bool = False):
         """IntersectionVolumeGuide.time_rows for the (S, B, 7, N) / (S*B, 7, N) state in ONE launch (a reshape: the rule reads nothing of a
         scene) -> the profile dict with every array shaped (S, B, ...); scene s's values are bit for bit what guides[s].time_rows gives for
@@ -1245,10 +1255,7 @@ class SceneBatch(_SlotObject):
         from .evaluation import PROFILE_KEYS, time_rows_on
 
         Xd, N = self._state(trajectories)
-        out = time_rows_on(self.ctx, Xd, vmax, amax, jump, scale, return_device)
-        for k in PROFILE_KEYS:
-            out[k] = out[k].reshape(self.n_scenes, self.batch_size, *out[k].shape[1:])
-        return out
+        return self._scene_profile(time_rows_on(self.ctx, Xd, vmax, amax, jump, scale, return_device), PROFILE_KEYS)
 
     def sample_rows(self, trajectories, profile, period, rows=None, max_samples=None, return_device: bool = False):
         """IntersectionVolumeGuide.sample_rows for the (S, B, 7, N) / (S*B, 7, N) state and the profile SceneBatch.time_rows gave, in ONE
@@ -1257,8 +1264,7 @@ class SceneBatch(_SlotObject):
         from .evaluation import PROFILE_KEYS, sample_rows_on
 
         Xd, N = self._state(trajectories)
-        flat = {k: profile[k].reshape(self.n_scenes * self.batch_size, *profile[k].shape[2:]) for k in PROFILE_KEYS if k in profile}
-        return sample_rows_on(self.ctx, Xd, flat, period, rows, max_samples, return_device)
+        return sample_rows_on(self.ctx, Xd, self._flat_profile(profile, PROFILE_KEYS), period, rows, max_samples, return_device)
 
     def blend_rows(self, trajectories, deviation=0.01, reach=0.4, substeps=4, halvings=2, vmax=None, amax=None, jump=None, scale=(1, 1), rows=None,
                    return_device: bool = False):
@@ -1280,9 +1286,7 @@ class SceneBatch(_SlotObject):
 
         Xd, N = self._state(trajectories)
         out = time_blended_rows_on(self.ctx, Xd, beta.reshape(self.n_scenes * self.batch_size, N), vmax, amax, jump, scale, return_device)
-        for k in BLENDED_PROFILE_KEYS + ("beta",):
-            out[k] = out[k].reshape(self.n_scenes, self.batch_size, *out[k].shape[1:])
-        return out
+        return self._scene_profile(out, BLENDED_PROFILE_KEYS + ("beta",))
 
     def sample_blended_rows(self, trajectories, profile, period, rows=None, max_samples=None, return_device: bool = False):
         """IntersectionVolumeGuide.sample_blended_rows for the (S, B, 7, N) / (S*B, 7, N) state and the profile SceneBatch.time_blended_rows
@@ -1291,8 +1295,7 @@ class SceneBatch(_SlotObject):
         from .evaluation import BLENDED_PROFILE_KEYS, sample_blended_rows_on
 
         Xd, N = self._state(trajectories)
-        flat = {k: profile[k].reshape(self.n_scenes * self.batch_size, *profile[k].shape[2:]) for k in BLENDED_PROFILE_KEYS + ("beta",) if k in profile}
-        return sample_blended_rows_on(self.ctx, Xd, flat, period, rows, max_samples, return_device)
+        return sample_blended_rows_on(self.ctx, Xd, self._flat_profile(profile, BLENDED_PROFILE_KEYS + ("beta",)), period, rows, max_samples, return_device)
 
     def sdf_self_rows(self, trajectories, t=0):
         """IntersectionVolumeGuide.sdf_self_rows for the (S, B, 7, N) / (S*B, 7, N) state (its interior columns 1..N-2 are the

@@ -375,7 +375,7 @@ int edmp_sample_rows_dev(edmp_ctx* ctx, const double* X_dev, int n, int N, const
                          const double* times_dev, const double* duration_dev, const double* seg_dev, const int32_t* rows_host, int n_rows,
                          double period, int M, double* q_dev, double* qd_dev, int32_t* count_dev);
 
-/* ---- corner blends of finished rows: chosen under the exact collision check, timed and sampled (csrc/blend.hip) -- */
+/* ---- corner blends of finished rows: chosen under the exact collision check (csrc/blend.hip), timed and sampled (csrc/timing.hip) -- */
 /* The stage after the one above, for a motion that may LEAVE the polyline by a bounded amount.  On the polyline every real corner carries
  * the velocity-jump cap and the arm all but stops there.  Here corner i is replaced by a parabolic blend: the quadratic Bezier curve with
  * the control points x_i - beta_i d_{i-1}, x_i, x_i + beta_i d_i, traversed at constant acceleration.  Notation as above: d_i = x_{i+1} -
@@ -408,7 +408,7 @@ int edmp_sample_rows_dev(edmp_ctx* ctx, const double* X_dev, int n, int N, const
  * edmp_success_rows_dev.  edmp_blend_rows_dev needs a single-scene guide, any n >= 1; edmp_scenes_blend_rows_dev a bound scene batch,
  * X (S*B, 7, N).  They read nothing of the sampler, do NOT end a segmented run, and synchronise the stream.
  *
- * 2. edmp_time_blended_rows_dev times the blended path (time_blended_rows_kernel: one wave per row, lane = waypoint).  beta_dev (n, N)
+ * 2. edmp_time_blended_rows_dev times the blended path (time_rows_kernel's blended instantiation: one wave per row, lane = waypoint).  beta_dev (n, N)
  * as stage 1 wrote it: 0 <= beta_i <= 0.45, 0 at both ends and beside a zero segment.  The rule is edmp_time_rows_dev's with two changes:
  *   l_i = (1.0 - beta_i) - beta_{i+1}: the straight part of segment i, from s = beta_i to s = 1 - beta_{i+1} of it;
  *   c_i = min(V_{i-1}^2, V_i^2, beta_i > 0 ? (2.0 * beta_i) * K_i : J_i^2): on blend i the joint acceleration is y_i Delta_i / (2 beta_i);
@@ -426,7 +426,7 @@ int edmp_sample_rows_dev(edmp_ctx* ctx, const double* X_dev, int n, int N, const
  * velocity is continuous at a blended corner; |qdot_j| <= vmax_j everywhere, |qddot_j| <= amax_j on straight parts and on blends; y is
  * the component-wise largest point of {0 <= y_i <= c_i, |y_{i+1} - y_i| <= 2 A_i l_i}.  Does not synchronise.
  *
- * 3. edmp_sample_blended_rows_dev samples that motion (sample_blended_rows_kernel: workgroup = listed row x 256 samples); rows_host,
+ * 3. edmp_sample_blended_rows_dev samples that motion (sample_rows_kernel's blended instantiation: workgroup = listed row x 256 samples); rows_host,
  * period, M, count, the goal's bits at rest at and past the duration and the NaN row as in edmp_sample_rows_dev.  At t < duration: the
  * flat times array F (2 N values) gives the starts of the 2 N - 3 pieces: piece p starts at F[p + 1]; p even is the straight part of
  * segment i = p / 2, p odd is blend i = (p + 1) / 2; the piece is the largest p with F[p + 1] <= t, tau = t - F[p + 1].

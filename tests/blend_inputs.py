@@ -1,8 +1,8 @@
 """The corner-blend stage's rule as plain Python loops in float64, its admission check and the inputs of its tests (test infrastructure, no
 GPU needed).
 
-The rule is the specification of blend_rows_kernel, time_blended_rows_kernel and sample_blended_rows_kernel (edmp_amd/csrc/blend.hip;
-include/edmp_hip.h states it), written from the definition with the success check's host twin as the judge - not from the kernels.  Python
+The rule is the specification of blend_rows_kernel (edmp_amd/csrc/blend.hip) and of the blended instantiations of time_rows_kernel and
+sample_rows_kernel (edmp_amd/csrc/timing.hip; include/edmp_hip.h states it), written from the definition with the success check's host twin as the judge - not from the kernels.  Python
 floats are IEEE doubles and every operation below is rounded on its own.
 
     d_i = x_{i+1} - x_i,  Delta_i = d_i - d_{i-1};  V_i, A_i, J_i as in tests/timing_inputs.py;  K_i = min_j amax_j / |Delta_ij|

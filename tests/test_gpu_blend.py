@@ -1,4 +1,4 @@
-"""The corner-blend stage (blend_rows_kernel, time_blended_rows_kernel, sample_blended_rows_kernel; edmp_blend_rows_dev,
+"""The corner-blend stage (blend_rows_kernel in blend.hip, the blended time_rows_kernel and sample_rows_kernel in timing.hip; edmp_blend_rows_dev,
 edmp_scenes_blend_rows_dev, edmp_time_blended_rows_dev, edmp_sample_blended_rows_dev) on the GPU against the rule of tests/blend_inputs.py
 on admitted cases, and against itself or the unblended entry points where the property is bit-equality.
 
