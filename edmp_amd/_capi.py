@@ -122,10 +122,14 @@ SIGNATURES = {
     "edmp_scenes_sdf_repair_rows_dev": (_i, [_vp, _vp, _i, _i, _i, _pd, _pd, _pi32, _i, _i, _i, _d, _d, _d, _d, _vp, _vp, _vp]),
     "edmp_shortcut_rows_dev": (_i, [_vp, _vp, _i, _i, _pi32, _i, _i, _i, _d, _pd, _vp, _vp, _vp, _vp, _i]),
     "edmp_scenes_shortcut_rows_dev": (_i, [_vp, _vp, _i, _i, _i, _pi32, _i, _i, _i, _d, _pd, _vp, _vp, _vp, _vp, _i]),
+    "edmp_shortcut_rows_self_dev": (_i, [_vp, _vp, _i, _i, _pi32, _i, _i, _i, _d, _pd, _vp, _vp, _vp, _vp, _i, _pi32, _vp]),
+    "edmp_scenes_shortcut_rows_self_dev": (_i, [_vp, _vp, _i, _i, _i, _pi32, _i, _i, _i, _d, _pd, _vp, _vp, _vp, _vp, _i, _pi32, _vp]),
     "edmp_time_rows_dev": (_i, [_vp, _vp, _i, _i, _pd, _pd, _pd, _vp, _vp, _vp, _vp, _vp, _vp]),
     "edmp_sample_rows_dev": (_i, [_vp, _vp, _i, _i, _vp, _vp, _vp, _vp, _vp, _pi32, _i, _d, _i, _vp, _vp, _vp]),
     "edmp_blend_rows_dev": (_i, [_vp, _vp, _i, _i, _pi32, _i, _pd, _pd, _pd, _pd, _d, _i, _i, _pd, _vp, _vp, _vp, _vp]),
     "edmp_scenes_blend_rows_dev": (_i, [_vp, _vp, _i, _i, _i, _pi32, _i, _pd, _pd, _pd, _pd, _d, _i, _i, _pd, _vp, _vp, _vp, _vp]),
+    "edmp_blend_rows_self_dev": (_i, [_vp, _vp, _i, _i, _pi32, _i, _pd, _pd, _pd, _pd, _d, _i, _i, _pd, _vp, _vp, _vp, _vp, _pi32, _vp]),
+    "edmp_scenes_blend_rows_self_dev": (_i, [_vp, _vp, _i, _i, _i, _pi32, _i, _pd, _pd, _pd, _pd, _d, _i, _i, _pd, _vp, _vp, _vp, _vp, _pi32, _vp]),
     "edmp_time_blended_rows_dev": (_i, [_vp, _vp, _i, _i, _vp, _pd, _pd, _pd, _vp, _vp, _vp, _vp, _vp, _vp, _vp]),
     "edmp_sample_blended_rows_dev": (_i, [_vp, _vp, _i, _i, _vp, _vp, _vp, _vp, _vp, _vp, _pi32, _i, _d, _i, _vp, _vp, _vp]),
     "edmp_sdf_rows_dev": (_i, [_vp, _vp, _i, _i, _i, _pd, _pd, _vp, _vp]),

@@ -140,11 +140,11 @@ inline int ctx_small_ints(edmp_ctx* ctx) {
 // Which entry points take which kind of bound guide (the two macros below are the whole state check; include/edmp_hip.h states the rest):
 //   single only (EDMP_REFUSE_SCENE_BATCH: refused on a batch of S > 1 scenes, never answered with scene 0's data):
 //     edmp_guide_cost_dev, edmp_guide_swept_cost_dev, edmp_guide_gradient_dev, edmp_row_swept_volumes_dev, edmp_success_rows_dev,
-//     edmp_scene_set_shapes, edmp_sdf_rows_dev, edmp_sdf_sweep_rows_dev, edmp_sdf_repair_rows_dev, edmp_shortcut_rows_dev, edmp_blend_rows_dev; with checks of their own edmp_sdf_set (a batch of ONE scene refused too) and the
+//     edmp_scene_set_shapes, edmp_sdf_rows_dev, edmp_sdf_sweep_rows_dev, edmp_sdf_repair_rows_dev, edmp_shortcut_rows_dev, edmp_shortcut_rows_self_dev, edmp_blend_rows_dev, edmp_blend_rows_self_dev; with checks of their own edmp_sdf_set (a batch of ONE scene refused too) and the
 //     single-scene loops and teacher-forced steps of sampler.hip
 //   batch only (EDMP_REQUIRE_SCENE_BATCH: the bound guide came from edmp_scene_batch_set, a batch of ONE scene included, and holds
 //     exactly S scenes x B rows): edmp_scenes_swept_volumes_dev, edmp_scenes_select_rows_dev, edmp_scenes_success_rows_dev,
-//     edmp_scenes_sdf_rows_dev, edmp_scenes_sdf_sweep_rows_dev, edmp_scenes_sdf_repair_rows_dev, edmp_scenes_shortcut_rows_dev, edmp_scenes_blend_rows_dev, edmp_scenes_goal_filter_dev, edmp_scene_batch_set_sdf; edmp_scene_batch_set_shapes (its own wording)
+//     edmp_scenes_sdf_rows_dev, edmp_scenes_sdf_sweep_rows_dev, edmp_scenes_sdf_repair_rows_dev, edmp_scenes_shortcut_rows_dev, edmp_scenes_shortcut_rows_self_dev, edmp_scenes_blend_rows_dev, edmp_scenes_blend_rows_self_dev, edmp_scenes_goal_filter_dev, edmp_scene_batch_set_sdf; edmp_scene_batch_set_shapes (its own wording)
 //   either: edmp_rows_set, edmp_scene_read_aabbs, edmp_argmin_dev, edmp_select_row_dev, edmp_metrics_rows_dev (the last three read no guide),
 //     edmp_self_collision_rows_dev (the robot tables only)
 #define EDMP_REFUSE_SCENE_BATCH(g, what)                                                                                          \

@@ -1,6 +1,7 @@
 // linkbox.h — what the exact f64 link-box checks share: the robot tables in f64, the box / box separating-axis test, the box / cylinder
-// test and the test of ONE configuration against a scene's obstacles.  success.hip (link boxes against the scene's obstacles), shortcut.hip
-// (the same test on the configurations of a candidate shortcut) and selfcol.hip (link boxes against each other) include it.
+// test, the test of ONE configuration against a scene's obstacles and the test of ONE configuration's link boxes against each other (the
+// pair plan of a (9, 9) mask, one lower link with its masked partners).  success.hip (link boxes against the scene's obstacles),
+// shortcut.hip and blend.hip (both tests on the configurations of a candidate) and selfcol.hip (link boxes against each other) include it.
 #pragma once
 #include "common.h"
 #include "chain.h"
@@ -179,6 +180,12 @@ __device__ __noinline__ inline bool obb_cylinder_overlap(const double Rb[3][3], 
 // The shortcut stage's guarantee - every configuration the success check tests on an accepted piece was tested - needs the same BITS in
 // two translation units, so the one fused multiply-add is written out and does not hang on each unit's contraction setting: the rounded
 // product f b, then fma(1 - f, a, .).  (What the compiler made of the plain expression in success_rows_kernel before: its results stay.)
+// self_collision_rows_kernel writes the plain expression (1.0 - f) * a + f * b; its code object holds ONE v_mul_f64 (f b) and ONE
+// v_fmac_f64 (that product plus (1 - f) a, one rounding) for it - this form, read off the disassembly -, so the self items of shortcut.hip take their configurations
+// through interp_joint too and see the bits self_collision_rows will form on the output.  NOTHING pins that contraction: another compiler,
+// other flags or a contraction pragma in selfcol.hip can give the plain expression there another rounding, and the bit-level form of the
+// guarantee (a row self_collision_rows calls free before a shortcut is free after it) then holds only up to one rounding of a joint value -
+// whoever changes how selfcol.hip is built reads its disassembly again, or writes interp_joint there (which would change its results).
 __device__ __forceinline__ double interp_joint(double a, double b, double f) { return fma(1.0 - f, a, f * b); }
 
 // ONE configuration against the `no` obstacles ob / kind (16 doubles and one int each): the chain walk in f64, every link box
@@ -212,6 +219,102 @@ __device__ __forceinline__ bool configuration_hits(Joint joint, const Robot64& r
         }
     }
     return hit;
+}
+
+// ---- link boxes against each other -------------------------------------------------------------------------------------------------------
+// the lower links with a non-empty mask row, ascending: link a, the mask bits of its partners b > a, the last joint frame one of them rides
+struct PairPlan {
+    int na;
+    int a[EDMP_N_LINKS - 1], bits[EDMP_N_LINKS - 1], jlast[EDMP_N_LINKS - 1];
+};
+
+// ONE configuration, ONE lower link a, its masked partners `bits` (b > a): walk the chain to a's frame and keep that one box pose (12
+// doubles), walk on and test each masked b by obb_overlap as its frame arrives (the frame of link l is monotone in l, so b's never
+// precedes a's), stop at the first hit - b ascends, so it is the smallest - or after frame jlast.  -> that b, or -1.  joint(j) gives the
+// value of joint j; it is asked once per joint, in order, up to jlast at most.  The rules of selfcol.hip hold here: nine f64 frames are
+// not held per thread (re-walking the chain per a costs a few sincos, the frames would cost the registers), the joint loop is not
+// unrolled and no per-thread array is indexed by the joint number - every table index (joint, link) is uniform over the lanes still in
+// the loop -, so nothing goes to scratch.
+template <class Joint>
+__device__ __forceinline__ int configuration_self_hit(Joint joint, const Robot64& rc, int a, int bits, int jlast) {
+    double R[3][3] = {{1, 0, 0}, {0, 1, 0}, {0, 0, 1}};
+    double o[3] = {0, 0, 0};
+    double Ra[3][3] = {{1, 0, 0}, {0, 1, 0}, {0, 0, 1}}, ca[3] = {0, 0, 0}, ha[3] = {0, 0, 0};
+    int hit = -1;
+#pragma unroll 1
+    for (int j = 0; j <= jlast && hit < 0; ++j) {
+        const double q = joint(j);
+        double sq, cq;
+        sincos(q, &sq, &cq);
+        dh_step(R, o, sq, cq, rc.dh[j]);
+        const int nl = (j == 6) ? 3 : 1;  // link7, hand and finger ride the last frame               lib/guide.py:93-94
+#pragma unroll 1
+        for (int ll = 0; ll < nl && hit < 0; ++ll) {
+            const int l = (ll == 0) ? j : 6 + ll;
+            if (l < a || (l > a && !((bits >> l) & 1))) continue;
+            double ob[15];
+            {
+                double LR[3][3], Lc[3];
+                frame_apply(R, o, rc.sf[l], LR, Lc);
+#pragma unroll
+                for (int m = 0; m < 3; ++m) {
+#pragma unroll
+                    for (int k = 0; k < 3; ++k) ob[m * 3 + k] = LR[m][k];
+                    ob[9 + m] = Lc[m];
+                    ob[12 + m] = rc.he[l][m];
+                }
+            }
+            if (l == a) {  // the one pose this item keeps
+#pragma unroll
+                for (int m = 0; m < 3; ++m) {
+#pragma unroll
+                    for (int k = 0; k < 3; ++k) Ra[m][k] = ob[m * 3 + k];
+                    ca[m] = ob[9 + m];
+                    ha[m] = ob[12 + m];
+                }
+            } else if (obb_overlap(Ra, ca, ha, ob)) {
+                hit = l;
+            }
+        }
+    }
+    return hit;
+}
+
+// what a kernel templated on SELF reads its further arguments through: the ONE element of the SELF instantiation's argument pack, nothing
+// for the plain instantiation (whose kernel arguments are then exactly what they were before the template)
+struct NoSelfArguments {};
+__device__ __forceinline__ NoSelfArguments self_arguments() { return {}; }
+template <class T>
+__device__ __forceinline__ const T& self_arguments(const T& t) {
+    return t;
+}
+
+// the plan of an 81-entry 0/1 mask of which the entries above the diagonal are read.  -> false with (*bad_a, *bad_b) the first entry that
+// is neither 0 nor 1 (the plan is then not to be used)
+inline bool pair_plan_of(const int32_t* pair_mask, PairPlan* plan, int* bad_a, int* bad_b) {
+    *plan = PairPlan{};
+    for (int a = 0; a < EDMP_N_LINKS; ++a) {
+        int bits = 0, jlast = 0;
+        for (int b = a + 1; b < EDMP_N_LINKS; ++b) {  // (entries on or below the diagonal are not read)
+            const int32_t m = pair_mask[a * EDMP_N_LINKS + b];
+            if (m != 0 && m != 1) {
+                *bad_a = a;
+                *bad_b = b;
+                return false;
+            }
+            if (m) {
+                bits |= 1 << b;
+                jlast = b < 7 ? b : 6;  // the joint frame link b rides (franka.LINK_FRAME)
+            }
+        }
+        if (bits) {
+            plan->a[plan->na] = a;
+            plan->bits[plan->na] = bits;
+            plan->jlast[plan->na] = jlast;
+            plan->na++;
+        }
+    }
+    return true;
 }
 
 // the obstacle rows of every scene of the guide object inside obb / kind: scene s owns rows [off[s], off[s] + cnt[s]); row r of the

@@ -12,7 +12,7 @@
 // minimum, so the answer is deterministic and depends on the row alone.  first = c / substeps (the waypoint index of the first colliding
 // configuration, -1 none), pair = a * 9 + b (the first masked pair in row-major order that overlaps THERE, -1 none).
 //
-// Design: one 256-thread workgroup per row, all f64 (the decision margin of the tests, 1e-9 m, is far below f32 resolution at arm's
+// Design (linkbox.h: PairPlan, configuration_self_hit hold the plan and the work item's body): one 256-thread workgroup per row, all f64 (the decision margin of the tests, 1e-9 m, is far below f32 resolution at arm's
 // length).  A work item is (configuration c, lower link a with a non-empty mask row): it walks the chain to a's frame, keeps that ONE box
 // pose (12 doubles), walks on and tests each masked b > a as its frame arrives (LINK_FRAME is monotone, so b's frame never precedes
 // a's), stopping at its first hit - b ascends, so that hit is the item's smallest key - or after the last frame a masked b rides.
@@ -28,12 +28,6 @@
 #include "linkbox.h"
 
 namespace edmp {
-
-// the lower links with a non-empty mask row, ascending: link a, the mask bits of its partners b > a, the last joint frame one of them rides
-struct PairPlan {
-    int na;
-    int a[EDMP_N_LINKS - 1], bits[EDMP_N_LINKS - 1], jlast[EDMP_N_LINKS - 1];
-};
 
 constexpr int kNoKey = 0x7fffffff;
 
@@ -61,47 +55,9 @@ __global__ __launch_bounds__(256) void self_collision_rows_kernel(const double* 
         if (c * 81 + a * 9 >= __hip_atomic_load(&s_key, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_WORKGROUP)) break;
         const int i = c / substeps, s = c - i * substeps;
         const double f = (double)s / (double)substeps;
-        double R[3][3] = {{1, 0, 0}, {0, 1, 0}, {0, 0, 1}};
-        double o[3] = {0, 0, 0};
-        double Ra[3][3] = {{1, 0, 0}, {0, 1, 0}, {0, 0, 1}}, ca[3] = {0, 0, 0}, ha[3] = {0, 0, 0};
-        int hit = -1;
-#pragma unroll 1
-        for (int j = 0; j <= jlast && hit < 0; ++j) {
-            // the success check's interpolation expression                                     success.hip: success_rows_kernel
-            const double q = (s == 0) ? xr[j * N + i] : (1.0 - f) * xr[j * N + i] + f * xr[j * N + i + 1];
-            double sq, cq;
-            sincos(q, &sq, &cq);
-            dh_step(R, o, sq, cq, rc.dh[j]);
-            const int nl = (j == 6) ? 3 : 1;  // link7, hand and finger ride the last frame               lib/guide.py:93-94
-#pragma unroll 1
-            for (int ll = 0; ll < nl && hit < 0; ++ll) {
-                const int l = (ll == 0) ? j : 6 + ll;
-                if (l < a || (l > a && !((bits >> l) & 1))) continue;
-                double ob[15];
-                {
-                    double LR[3][3], Lc[3];
-                    frame_apply(R, o, rc.sf[l], LR, Lc);
-#pragma unroll
-                    for (int m = 0; m < 3; ++m) {
-#pragma unroll
-                        for (int k = 0; k < 3; ++k) ob[m * 3 + k] = LR[m][k];
-                        ob[9 + m] = Lc[m];
-                        ob[12 + m] = rc.he[l][m];
-                    }
-                }
-                if (l == a) {  // the one pose this item keeps
-#pragma unroll
-                    for (int m = 0; m < 3; ++m) {
-#pragma unroll
-                        for (int k = 0; k < 3; ++k) Ra[m][k] = ob[m * 3 + k];
-                        ca[m] = ob[9 + m];
-                        ha[m] = ob[12 + m];
-                    }
-                } else if (obb_overlap(Ra, ca, ha, ob)) {
-                    hit = l;
-                }
-            }
-        }
+        // the success check's interpolation expression                                         success.hip: success_rows_kernel
+        const int hit = configuration_self_hit(
+            [&](int j) { return (s == 0) ? xr[j * N + i] : (1.0 - f) * xr[j * N + i] + f * xr[j * N + i + 1]; }, rc, a, bits, jlast);
         if (hit >= 0) atomicMin(&s_key, c * 81 + a * 9 + hit);
     }
     __syncthreads();
@@ -116,9 +72,6 @@ __global__ __launch_bounds__(256) void self_collision_rows_kernel(const double* 
 
 using namespace edmp;
 
-// the joint frame link l rides (franka.LINK_FRAME)
-static int link_frame(int l) { return l < 7 ? l : 6; }
-
 extern "C" int edmp_self_collision_rows_dev(edmp_ctx* ctx, const double* X_dev, int n, int N, int substeps, const double* dh_f64,
                                             const int32_t* pair_mask, int32_t* first_dev, int32_t* pair_dev) {
     EDMP_REQUIRE(ctx, "edmp_self_collision_rows_dev: null context");
@@ -132,24 +85,10 @@ extern "C" int edmp_self_collision_rows_dev(edmp_ctx* ctx, const double* X_dev, 
     // the key c * 81 + a * 9 + b and the item index c * na + item are 32-bit
     EDMP_REQUIRE(((int64_t)(N - 1) * substeps + 1) * 81 < (int64_t)kNoKey, "edmp_self_collision_rows_dev: (N - 1) * substeps + 1 = %lld configurations per row, the key holds %d",
                  (long long)((int64_t)(N - 1) * substeps + 1), kNoKey / 81);
-    PairPlan plan = {};
-    for (int a = 0; a < EDMP_N_LINKS; ++a) {
-        int bits = 0, jlast = 0;
-        for (int b = a + 1; b < EDMP_N_LINKS; ++b) {  // (entries on or below the diagonal are not read)
-            const int32_t m = pair_mask[a * EDMP_N_LINKS + b];
-            EDMP_REQUIRE(m == 0 || m == 1, "edmp_self_collision_rows_dev: pair_mask[%d][%d] = %d, mask entries are 0 or 1", a, b, (int)m);
-            if (m) {
-                bits |= 1 << b;
-                jlast = link_frame(b);
-            }
-        }
-        if (bits) {
-            plan.a[plan.na] = a;
-            plan.bits[plan.na] = bits;
-            plan.jlast[plan.na] = jlast;
-            plan.na++;
-        }
-    }
+    PairPlan plan;
+    int bad_a = 0, bad_b = 0;
+    if (!pair_plan_of(pair_mask, &plan, &bad_a, &bad_b))
+        EDMP_REQUIRE(false, "edmp_self_collision_rows_dev: pair_mask[%d][%d] = %d, mask entries are 0 or 1", bad_a, bad_b, (int)pair_mask[bad_a * EDMP_N_LINKS + bad_b]);
     EDMP_HIP_CHECK(hipSetDevice(ctx->device));
     if (plan.na == 0 || (!first_dev && !pair_dev)) {  // an all-zero mask: -1 everywhere, no chain to walk
         if (first_dev) EDMP_HIP_CHECK(hipMemsetAsync(first_dev, 0xff, (size_t)n * sizeof(int32_t), ctx->stream));

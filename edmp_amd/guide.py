@@ -410,55 +410,86 @@ class _SlotObject:
         out.update({k: h[i // 2, :, i % 2].reshape(shape).copy() for i, k in enumerate(keys)})
         return out
 
-    def _shortcut(self, X, Xd, shape, N, passes, substeps, min_gain, rows, log_cap, return_device):
+    def _self_mask(self, self_pairs):
+        """the ``self_pairs`` argument of shortcut_rows / blend_rows -> None (no self test: the plain entry points) or the (81,) int32 mask:
+        True the guide's own (what its SDF self term uses), anything else through franka.check_pair_mask"""
+        if self_pairs is None:
+            return None
+        if self_pairs is True:
+            return np.ascontiguousarray(self._self_pairs, dtype=np.int32).reshape(81)
+        if self_pairs is False:
+            raise ValueError("self_pairs: None (no self test), True (the guide's own pair mask) or a (9, 9) mask")
+        return franka.check_pair_mask(self_pairs)
+
+    def _shortcut(self, X, Xd, shape, N, passes, substeps, min_gain, rows, log_cap, return_device, self_pairs=None):
         """shortcutting under the exact collision check of the (rows, 7, N) device state Xd (made from the caller's X) -> the shortcut dict,
-        per-row arrays `shape`d.  Always out of place: a device tensor of the caller's is cloned first, the kernel runs in place on the clone."""
+        per-row arrays `shape`d.  Always out of place: a device tensor of the caller's is cloned first, the kernel runs in place on the clone.
+        self_pairs not None: the *_self_dev entry points, the dict gains self_rejected and self_pairs."""
         ctx, n, cap = self.ctx, int(np.prod(shape)), int(log_cap)
+        mask = self._self_mask(self_pairs)
         with torch.cuda.stream(ctx.stream):
             if isinstance(X, torch.Tensor) and X.is_cuda:
                 Xd = Xd.clone()  # (_rows_f64 hands an f64 contiguous device tensor through as it is)
-            counts = torch.zeros((2, n), dtype=torch.int32, device=ctx.device)  # rows outside `rows` are not written
+            counts = torch.zeros((2 if mask is None else 3, n), dtype=torch.int32, device=ctx.device)  # rows outside `rows` are not written
             length = torch.full((n, 2), float("nan"), dtype=torch.float64, device=ctx.device)
             spans = torch.full((n, max(cap, 0), 2), -1, dtype=torch.int32, device=ctx.device)
         listed = None if rows is None else np.ascontiguousarray(np.asarray(rows, dtype=np.int32).reshape(-1))
         dh = np.ascontiguousarray(franka.dh_table_f64())
-        self._call("edmp_shortcut_rows_dev", "edmp_scenes_shortcut_rows_dev", shape, ptr(Xd), *shape, N, None if listed is None else _capi.as_pi32(listed),
+        names = ("edmp_shortcut_rows_dev", "edmp_scenes_shortcut_rows_dev") if mask is None else ("edmp_shortcut_rows_self_dev", "edmp_scenes_shortcut_rows_self_dev")
+        extra = () if mask is None else (_capi.as_pi32(mask), C.c_void_p(counts[2].data_ptr()))
+        self._call(*names, shape, ptr(Xd), *shape, N, None if listed is None else _capi.as_pi32(listed),
                    0 if listed is None else int(listed.shape[0]), int(substeps), int(passes), float(min_gain), _capi.as_pd(dh), C.c_void_p(counts[0].data_ptr()),
-                   C.c_void_p(counts[1].data_ptr()), ptr(length), ptr(spans) if cap > 0 else None, cap)
+                   C.c_void_p(counts[1].data_ptr()), ptr(length), ptr(spans) if cap > 0 else None, cap, *extra)
         if return_device:
             ctx.hand_over(Xd)  # (the caller's torch ops on the results follow this context's stream)
-            return dict(trajectories=Xd.view(*shape, 7, N), accepted=counts[0].view(*shape), tested=counts[1].view(*shape), length0=length[:, 0].view(*shape),
-                        length=length[:, 1].view(*shape), spans=spans.view(*shape, max(cap, 0), 2))
+            out = dict(trajectories=Xd.view(*shape, 7, N), accepted=counts[0].view(*shape), tested=counts[1].view(*shape), length0=length[:, 0].view(*shape),
+                       length=length[:, 1].view(*shape), spans=spans.view(*shape, max(cap, 0), 2))
+            if mask is not None:
+                out.update(self_rejected=counts[2].view(*shape), self_pairs=mask.reshape(9, 9).copy())
+            return out
         c, ln = ctx.to_host(counts), ctx.to_host(length)
-        return dict(trajectories=ctx.to_host(Xd).reshape(*shape, 7, N), accepted=c[0].reshape(shape).copy(), tested=c[1].reshape(shape).copy(),
-                    length0=ln[:, 0].reshape(shape).copy(), length=ln[:, 1].reshape(shape).copy(), spans=(ctx.to_host(spans) if cap > 0 else np.zeros((n, 0, 2), dtype=np.int32)).reshape(*shape, max(cap, 0), 2))
+        out = dict(trajectories=ctx.to_host(Xd).reshape(*shape, 7, N), accepted=c[0].reshape(shape).copy(), tested=c[1].reshape(shape).copy(),
+                   length0=ln[:, 0].reshape(shape).copy(), length=ln[:, 1].reshape(shape).copy(), spans=(ctx.to_host(spans) if cap > 0 else np.zeros((n, 0, 2), dtype=np.int32)).reshape(*shape, max(cap, 0), 2))
+        if mask is not None:
+            out.update(self_rejected=c[2].reshape(shape).copy(), self_pairs=mask.reshape(9, 9).copy())
+        return out
 
 
-    def _blend(self, Xd, shape, N, deviation, reach, substeps, halvings, vmax, amax, jump, scale, rows, return_device):
+    def _blend(self, Xd, shape, N, deviation, reach, substeps, halvings, vmax, amax, jump, scale, rows, return_device, self_pairs=None):
         """the corner blends of the (rows, 7, N) device state Xd under the exact collision check -> the blend dict, per-row arrays `shape`d.
-        Rows outside `rows` are not written by the library: they keep beta 0, code 0, halved 0, tested 0 (an unblended row)."""
+        Rows outside `rows` are not written by the library: they keep beta 0, code 0, halved 0, tested 0 (an unblended row).  self_pairs
+        not None: the *_self_dev entry points, the dict gains self_hits and self_pairs."""
         from .evaluation import blend_arguments
 
         ctx, n = self.ctx, int(np.prod(shape))
+        mask = self._self_mask(self_pairs)
         vm, am, jm = franka.timing_limits(vmax, amax, jump, scale)
         dev, reach, substeps, halvings = blend_arguments(deviation, reach, substeps, halvings)
         with torch.cuda.stream(ctx.stream):
             beta = torch.zeros((n, N), dtype=torch.float64, device=ctx.device)
-            codes = torch.zeros((2, n, N), dtype=torch.int32, device=ctx.device)
+            codes = torch.zeros((2 if mask is None else 3, n, N), dtype=torch.int32, device=ctx.device)
             tested = torch.zeros((n,), dtype=torch.int32, device=ctx.device)
         listed = None if rows is None else np.ascontiguousarray(np.asarray(rows, dtype=np.int32).reshape(-1))
         dh = np.ascontiguousarray(franka.dh_table_f64())
-        self._call("edmp_blend_rows_dev", "edmp_scenes_blend_rows_dev", shape, ptr(Xd), *shape, N, None if listed is None else _capi.as_pi32(listed),
+        names = ("edmp_blend_rows_dev", "edmp_scenes_blend_rows_dev") if mask is None else ("edmp_blend_rows_self_dev", "edmp_scenes_blend_rows_self_dev")
+        extra = () if mask is None else (_capi.as_pi32(mask), C.c_void_p(codes[2].data_ptr()))
+        self._call(*names, shape, ptr(Xd), *shape, N, None if listed is None else _capi.as_pi32(listed),
                    0 if listed is None else int(listed.shape[0]), _capi.as_pd(vm), _capi.as_pd(am), _capi.as_pd(jm), _capi.as_pd(dev), reach, substeps, halvings,
-                   _capi.as_pd(dh), ptr(beta), C.c_void_p(codes[0].data_ptr()), C.c_void_p(codes[1].data_ptr()), ptr(tested))
+                   _capi.as_pd(dh), ptr(beta), C.c_void_p(codes[0].data_ptr()), C.c_void_p(codes[1].data_ptr()), ptr(tested), *extra)
         lim = dict(vmax=vm, amax=am, jump=jm, deviation=dev, reach=reach, substeps=substeps, halvings=halvings)
         if return_device:
             for v in (beta, codes, tested):
                 ctx.hand_over(v)  # (the caller's torch ops on the results follow this context's stream)
-            return dict(beta=beta.view(*shape, N), code=codes[0].view(*shape, N), halved=codes[1].view(*shape, N), tested=tested.view(*shape), **lim)
+            out = dict(beta=beta.view(*shape, N), code=codes[0].view(*shape, N), halved=codes[1].view(*shape, N), tested=tested.view(*shape), **lim)
+            if mask is not None:
+                out.update(self_hits=codes[2].view(*shape, N), self_pairs=mask.reshape(9, 9).copy())
+            return out
         c = ctx.to_host(codes)
-        return dict(beta=ctx.to_host(beta).reshape(*shape, N), code=c[0].reshape(*shape, N).copy(), halved=c[1].reshape(*shape, N).copy(),
-                    tested=ctx.to_host(tested).reshape(shape), **lim)
+        out = dict(beta=ctx.to_host(beta).reshape(*shape, N), code=c[0].reshape(*shape, N).copy(), halved=c[1].reshape(*shape, N).copy(),
+                   tested=ctx.to_host(tested).reshape(shape), **lim)
+        if mask is not None:
+            out.update(self_hits=c[2].reshape(*shape, N).copy(), self_pairs=mask.reshape(9, 9).copy())
+        return out
 
 
 class IntersectionVolumeGuide(_SlotObject):
@@ -753,7 +784,7 @@ class IntersectionVolumeGuide(_SlotObject):
         return self._repair(trajectories, X, (X.shape[0],), X.shape[2], _pair7(start, goal), iters, substeps, margin, smoothness, step, max_step, rows,
                             return_device)
 
-    def shortcut_rows(self, trajectories, passes=2, substeps=4, min_gain=1e-6, rows=None, log_cap=128, return_device=False):
+    def shortcut_rows(self, trajectories, passes=2, substeps=4, min_gain=1e-6, rows=None, log_cap=128, return_device=False, self_pairs=None):
         """Shortcut finished rows under the exact collision check (edmp_shortcut_rows_dev, csrc/shortcut.hip; one launch, one workgroup per
         row for the whole run of the row): trajectories (n, 7, N) f64, ndarray or device tensor, 3 <= N <= 64, columns 0 and N-1 the pinned
         start and goal.  Per pass the spans s = N-1, then (s+1)//2 down to 2, are walked from i = 0: where replacing the waypoints between
@@ -764,8 +795,13 @@ class IntersectionVolumeGuide(_SlotObject):
         stays bounded) are refused.  Consequences: the joint path length never grows; columns 0 and N-1 are
         never written; waypoints are convex combinations of waypoints, so ``within`` cannot get worse; every configuration success_rows
         (at the same ``substeps``) tests on the output is either unchanged or was tested, so ``first`` < 0 before implies ``first`` < 0
-        after; a colliding row may become free, when its colliding part lies inside an accepted span.  Self-collision is NOT part of the
-        test - a joint-space chord can fold the arm: self_collision_rows stays the check.  Returns dict(trajectories (n, 7, N), accepted and
+        after; a colliding row may become free, when its colliding part lies inside an accepted span.  Self-collision: with
+        ``self_pairs`` = None (the default) it is NOT part of the test - a joint-space chord can fold the arm, self_collision_rows stays the
+        check.  With ``self_pairs`` = True (the guide's own pair mask, what its SDF self term uses) or a (9, 9) 0/1 mask
+        (franka.check_pair_mask) a candidate must also keep every masked pair of link boxes apart at the same configurations, by
+        self_collision_rows' own test on the bits it forms (edmp_shortcut_rows_self_dev): a row that self_collision_rows(substeps, pairs=mask)
+        calls free before is free after, and the dict gains self_rejected (n,) int32 - the tested candidates that the obstacle test passed
+        and the self test rejected - and self_pairs, the (9, 9) mask used.  Returns dict(trajectories (n, 7, N), accepted and
         tested (n,) int32 true counts of accepted spans and tested candidates, length0 / length (n,) f64 joint path length before / after
         as an index-order sum, spans (n, log_cap, 2) int32 the first ``log_cap`` accepted (i, j) in order, the rest -1).  A row with a
         non-finite element is left as it is: accepted = -1, NaN lengths.  ``rows``: the row indices to work on (any order, no duplicates);
@@ -775,7 +811,7 @@ class IntersectionVolumeGuide(_SlotObject):
         if X.dim() != 3 or X.shape[1] != 7:
             raise ValueError(f"trajectories must be (n, 7, N), got {tuple(X.shape)}")
         self._bind()
-        return self._shortcut(trajectories, X, (X.shape[0],), X.shape[2], passes, substeps, min_gain, rows, log_cap, return_device)
+        return self._shortcut(trajectories, X, (X.shape[0],), X.shape[2], passes, substeps, min_gain, rows, log_cap, return_device, self_pairs)
 
     def row_swept_volumes(self, start, goal, trajectories):
         """(B,) f32 t=0 swept volume per row and the argmin (first on ties)."""
@@ -835,7 +871,7 @@ class IntersectionVolumeGuide(_SlotObject):
         return sample_rows_on(self.ctx, trajectories, profile, period, rows, max_samples, return_device)
 
     def blend_rows(self, trajectories, deviation=0.01, reach=0.4, substeps=4, halvings=2, vmax=None, amax=None, jump=None, scale=(1, 1), rows=None,
-                   return_device: bool = False):
+                   return_device: bool = False, self_pairs=None):
         """Choose a parabolic blend for every corner of finished rows under the exact collision check (edmp_blend_rows_dev, csrc/blend.hip;
         one launch, one workgroup per row): trajectories (n, 7, N) f64, ndarray or device tensor, 2 <= N <= 64, are only read.  Corner i is
         replaced by the quadratic Bezier curve from x_i - beta d_{i-1} over x_i to x_i + beta d_i, which a timed motion crosses at constant
@@ -845,7 +881,11 @@ class IntersectionVolumeGuide(_SlotObject):
         acceleration cap is no better than the jump cap ends the corner.  -> dict(beta (n, N) f64, code (n, N) int32 - index into
         evaluation.BLEND_CODE_NAMES: 0 none (an end, a repeated waypoint, no corner), 1 not needed, 2 no gain, 3 blended, 4 blocked -
         halved (n, N) int32, tested (n,) int32 configurations tested) plus the arguments used.  The blend departs from the polyline by at
-        most beta |Delta_ij| / 4 <= ``deviation`` [rad, a scalar or one per joint] in joint j.  Self-collision is NOT tested.  A row with a
+        most beta |Delta_ij| / 4 <= ``deviation`` [rad, a scalar or one per joint] in joint j.  Self-collision is NOT tested with
+        ``self_pairs`` = None (the default).  With ``self_pairs`` = True (the guide's own pair mask) or a (9, 9) 0/1 mask a try must also keep
+        every masked pair of link boxes apart at its ``substeps`` + 1 configurations (edmp_blend_rows_self_dev; self_collision_rows' own
+        test): the dict gains self_hits (n, N) int32 - the tries of corner i that the obstacle test passed and the self test rejected - and
+        self_pairs, the (9, 9) mask used; a corner whose every try is hit, by whichever test, is code 4.  A row with a
         non-finite element is left alone: code -1, beta NaN.  ``rows``: the rows to work on (any order, no duplicates); the others report
         beta 0, code 0: unblended.  The defaults are illustrative, not tuned: 10 mrad, reach 0.4 (at most 0.45), limits of
         franka.timing_limits.  Hand beta to time_blended_rows.  Leaves a segmented run running."""
@@ -853,7 +893,7 @@ class IntersectionVolumeGuide(_SlotObject):
         if X.dim() != 3 or X.shape[1] != 7:
             raise ValueError(f"trajectories must be (n, 7, N), got {tuple(X.shape)}")
         self._bind()
-        out = self._blend(X, (X.shape[0],), X.shape[2], deviation, reach, substeps, halvings, vmax, amax, jump, scale, rows, return_device)
+        out = self._blend(X, (X.shape[0],), X.shape[2], deviation, reach, substeps, halvings, vmax, amax, jump, scale, rows, return_device, self_pairs)
         X.record_stream(self.ctx.stream)
         return out
 
@@ -1227,14 +1267,15 @@ class SceneBatch(_SlotObject):
         Xd.record_stream(self.ctx.stream)
         return out
 
-    def shortcut_rows(self, trajectories, passes=2, substeps=4, min_gain=1e-6, rows=None, log_cap=128, return_device=False):
+    def shortcut_rows(self, trajectories, passes=2, substeps=4, min_gain=1e-6, rows=None, log_cap=128, return_device=False, self_pairs=None):
         """IntersectionVolumeGuide.shortcut_rows for every scene in one launch (edmp_scenes_shortcut_rows_dev): the (S, B, 7, N) /
         (S*B, 7, N) state, each row against its own scene's obstacles and kinds -> the same dict with trajectories (S, B, 7, N), (S, B)
         per-row arrays and spans (S, B, log_cap, 2); scene s's values are what guides[s].shortcut_rows gives for X[s].  ``rows`` indexes the
-        S*B rows scene after scene.  0 <= ``passes`` <= 1024 (EDMP_MAX_SHORTCUT_PASSES).  Out of place; leaves a segmented run running."""
+        S*B rows scene after scene.  0 <= ``passes`` <= 1024 (EDMP_MAX_SHORTCUT_PASSES).  ``self_pairs`` as there, ONE mask for all scenes
+        (edmp_scenes_shortcut_rows_self_dev): self_rejected (S, B).  Out of place; leaves a segmented run running."""
         Xd, N = self._state(trajectories)
         self._bind()
-        out = self._shortcut(trajectories, Xd, (self.n_scenes, self.batch_size), N, passes, substeps, min_gain, rows, log_cap, return_device)
+        out = self._shortcut(trajectories, Xd, (self.n_scenes, self.batch_size), N, passes, substeps, min_gain, rows, log_cap, return_device, self_pairs)
         Xd.record_stream(self.ctx.stream)
         return out
 
@@ -1267,14 +1308,15 @@ class SceneBatch(_SlotObject):
         return sample_rows_on(self.ctx, Xd, self._flat_profile(profile, PROFILE_KEYS), period, rows, max_samples, return_device)
 
     def blend_rows(self, trajectories, deviation=0.01, reach=0.4, substeps=4, halvings=2, vmax=None, amax=None, jump=None, scale=(1, 1), rows=None,
-                   return_device: bool = False):
+                   return_device: bool = False, self_pairs=None):
         """IntersectionVolumeGuide.blend_rows for every scene in one launch (edmp_scenes_blend_rows_dev): the (S, B, 7, N) / (S*B, 7, N)
         state, each row against its own scene's obstacles and kinds -> the same dict with beta, code, halved (S, B, N) and tested (S, B);
-        scene s's values are bit for bit what guides[s].blend_rows gives for X[s].  ``rows`` indexes the S*B rows scene after scene.  Leaves a
-        segmented run running."""
+        scene s's values are bit for bit what guides[s].blend_rows gives for X[s].  ``rows`` indexes the S*B rows scene after scene.
+        ``self_pairs`` as there, ONE mask for all scenes (edmp_scenes_blend_rows_self_dev): self_hits (S, B, N).  Leaves a segmented run
+        running."""
         Xd, N = self._state(trajectories)
         self._bind()
-        out = self._blend(Xd, (self.n_scenes, self.batch_size), N, deviation, reach, substeps, halvings, vmax, amax, jump, scale, rows, return_device)
+        out = self._blend(Xd, (self.n_scenes, self.batch_size), N, deviation, reach, substeps, halvings, vmax, amax, jump, scale, rows, return_device, self_pairs)
         Xd.record_stream(self.ctx.stream)
         return out
 

@@ -305,7 +305,8 @@ int edmp_success_rows_dev(edmp_ctx* ctx, const double* X_dev, int B, int N, int 
  * So the joint path length never grows, waypoints only move to convex combinations of waypoints (the joint-limit flag cannot get worse),
  * and every configuration the success check tests on the output is either unchanged or was tested here: a row with first < 0 before has
  * first < 0 after.  A colliding row may become free, when its colliding part lies inside an accepted span.  Self-collision is NOT part
- * of the test (a joint-space chord can fold the arm): edmp_self_collision_rows_dev stays the check.
+ * of THIS test (a joint-space chord can fold the arm; edmp_self_collision_rows_dev stays the check): it is part of the test of
+ * edmp_shortcut_rows_self_dev and edmp_scenes_shortcut_rows_self_dev below.
  * Outputs, written for the listed rows only: accepted_dev (n,) int32 accepted spans, tested_dev (n,) int32 tested candidates (true counts,
  * not capped), length_dev (n, 2) f64 = the joint path length (the segment lengths summed in index order) before | after, spans_dev
  * (n, log_cap, 2) int32 = the first log_cap accepted (i, j) in order, the rest -1 (log_cap = 0: not read, may be NULL).  A row with a
@@ -323,6 +324,30 @@ int edmp_shortcut_rows_dev(edmp_ctx* ctx, double* X_dev, int n, int N, const int
 int edmp_scenes_shortcut_rows_dev(edmp_ctx* ctx, double* X_dev, int S, int B, int N, const int32_t* rows_host, int n_rows, int substeps,
                                   int passes, double min_gain, const double* dh_f64, int32_t* accepted_dev, int32_t* tested_dev,
                                   double* length_dev, int32_t* spans_dev, int log_cap);
+/* The same stage with the arm's own link boxes in the test: the rule above, with the step
+ *     test: ... against the scene's obstacles by that check's own test, AND against the arm itself: at each of those configurations the
+ *       boxes of every MASKED pair of links (a, b), a < b, by edmp_self_collision_rows_dev's test (f64 modified-DH poses, the 15-axis
+ *       test, touching counts), the interpolants in the bits that check forms ((1.0 - f) * y_m + f * y_{m+1} as ONE fused multiply-add
+ *       onto the rounded product f * y_{m+1}: what both checks compute);
+ *     no obstacle hit and no masked pair overlapping: x_m <- y_m, the span is logged, i = j; otherwise i += 1.
+ * pair_mask (host, 81 int32 = (9, 9) row-major) as in edmp_self_collision_rows_dev: pair (a, b), a < b, is tested iff pair_mask[a*9 + b]
+ * == 1; those entries must be 0 or 1 (refused otherwise, naming the entry), entries on or below the diagonal are not read; ONE mask for
+ * every row, in a scene batch too.  So, beside the guarantees above: a row that edmp_self_collision_rows_dev (same substeps, same mask,
+ * same dh_f64) calls free before is free after - every configuration it tests on the output is unchanged or was tested here, in its
+ * bits.  self_rejected_dev (n,) int32, written for the listed rows: the tested candidates that the obstacle test passed and the self test
+ * rejected (a candidate hit by both counts in tested only); 0 for a row with a non-finite element.  tested counts candidates as before.
+ * An all-zero mask is legal: the rule and the kernel of edmp_shortcut_rows_dev, self_rejected zero-filled for all n rows.  Otherwise
+ * shortcut_rows_kernel<true>: the test's work items are (configuration, test) - the obstacle test, then one item per lower link with a
+ * masked partner - under two flags per candidate (obstacle hit, self hit; an obstacle item is skipped only when the obstacle flag is up,
+ * a self item when either is): deterministic, no atomics.  Everything else - outputs, the NaN row, rows_host, refusals before any device
+ * call (pair_mask and self_rejected_dev must not be NULL), what the calls leave alone, the synchronisation - as above. */
+int edmp_shortcut_rows_self_dev(edmp_ctx* ctx, double* X_dev, int n, int N, const int32_t* rows_host, int n_rows, int substeps, int passes,
+                                double min_gain, const double* dh_f64, int32_t* accepted_dev, int32_t* tested_dev, double* length_dev,
+                                int32_t* spans_dev, int log_cap, const int32_t* pair_mask, int32_t* self_rejected_dev);
+int edmp_scenes_shortcut_rows_self_dev(edmp_ctx* ctx, double* X_dev, int S, int B, int N, const int32_t* rows_host, int n_rows, int substeps,
+                                       int passes, double min_gain, const double* dh_f64, int32_t* accepted_dev, int32_t* tested_dev,
+                                       double* length_dev, int32_t* spans_dev, int log_cap, const int32_t* pair_mask,
+                                       int32_t* self_rejected_dev);
 
 /* ---- time parameterisation of finished rows (csrc/timing.hip) ---------------------------------------------------- */
 /* The stage after shortcutting, which the reference does not ship (it replays plans at constant velocity): the fastest rest-to-rest
@@ -404,7 +429,16 @@ int edmp_sample_rows_dev(edmp_ctx* ctx, const double* X_dev, int n, int N, const
  * the polyline by at most beta |Delta_ij| / 4 <= deviation_j in joint j (at u = 1/2; every point of the curve is a convex combination of
  * points of the two segments); beta <= reach <= 0.45 keeps neighbouring blends apart; every accepted blend was tested at its K_b + 1
  * configurations, both ends included, by the success check's own test - what lies between them is as untested as what lies between the
- * success check's own substeps.  Self-collision is NOT tested: edmp_self_collision_rows_dev stays the check.  dh_f64 as in
+ * success check's own substeps.  Self-collision is NOT tested by these two (edmp_self_collision_rows_dev stays the check); it is by
+ * edmp_blend_rows_self_dev and edmp_scenes_blend_rows_self_dev: stage 1 with one more condition on a try - at each of its K_b + 1
+ * configurations no MASKED pair of link boxes (a, b), a < b, may overlap, by edmp_self_collision_rows_dev's test (touching counts).  A try
+ * is kept iff neither test hits; all H + 1 tries hit, by whichever test: code 4.  pair_mask (host, 81 int32, entries above the diagonal
+ * read, each 0 or 1, refused otherwise; ONE mask for every row and scene) as in edmp_self_collision_rows_dev.  self_hits_dev (n, N) int32,
+ * written for the listed rows: the tries of corner i that the obstacle test passed and the self test rejected (a try hit by both is not
+ * counted); 0 for a row with a non-finite element.  Codes, beta, halved and tested (K_b + 1 per try) as above.  An all-zero mask: the
+ * kernel of edmp_blend_rows_dev, self_hits zero-filled for all n rows; otherwise blend_rows_kernel<true>, the items (configuration, test)
+ * under two flags per tried corner as in edmp_shortcut_rows_self_dev.  Self-collision BETWEEN the tested configurations is as untested
+ * as obstacle collision there.  dh_f64 as in
  * edmp_success_rows_dev.  edmp_blend_rows_dev needs a single-scene guide, any n >= 1; edmp_scenes_blend_rows_dev a bound scene batch,
  * X (S*B, 7, N).  They read nothing of the sampler, do NOT end a segmented run, and synchronise the stream.
  *
@@ -444,6 +478,14 @@ int edmp_scenes_blend_rows_dev(edmp_ctx* ctx, const double* X_dev, int S, int B,
                                const double* vmax, const double* amax, const double* jump, const double* deviation, double reach,
                                int substeps, int halvings, const double* dh_f64, double* beta_dev, int32_t* code_dev,
                                int32_t* halved_dev, int32_t* tested_dev);
+int edmp_blend_rows_self_dev(edmp_ctx* ctx, const double* X_dev, int n, int N, const int32_t* rows_host, int n_rows, const double* vmax,
+                             const double* amax, const double* jump, const double* deviation, double reach, int substeps, int halvings,
+                             const double* dh_f64, double* beta_dev, int32_t* code_dev, int32_t* halved_dev, int32_t* tested_dev,
+                             const int32_t* pair_mask, int32_t* self_hits_dev);
+int edmp_scenes_blend_rows_self_dev(edmp_ctx* ctx, const double* X_dev, int S, int B, int N, const int32_t* rows_host, int n_rows,
+                                    const double* vmax, const double* amax, const double* jump, const double* deviation, double reach,
+                                    int substeps, int halvings, const double* dh_f64, double* beta_dev, int32_t* code_dev,
+                                    int32_t* halved_dev, int32_t* tested_dev, const int32_t* pair_mask, int32_t* self_hits_dev);
 int edmp_time_blended_rows_dev(edmp_ctx* ctx, const double* X_dev, int n, int N, const double* beta_dev, const double* vmax,
                                const double* amax, const double* jump, double* y_dev, double* phase_dev, double* times_dev,
                                double* duration_dev, int32_t* limit_dev, double* seg_dev, double* blend_dev);

@@ -135,7 +135,7 @@ def repair_tally(rep, iters, margin):
     return it > 0, (it >= 0) & ((it < int(iters)) | (clr >= float(np.float32(margin))))
 
 
-def job_summary(results, world=1, self_collision=False, repair=False, shortcut=False):
+def job_summary(results, world=1, self_collision=False, repair=False, shortcut=False, self_safe=False):
     """This rank's tallies; under a launcher the sum over all ranks (all_gather_object of five small integers per rank - the
     trajectories stay where they were planned).  Keys: scenes, success_proxy (the reference's tally), success_strict, rows_collision_free, rows."""
     mine = dict(scenes=len(results), success_proxy=sum(r["success_proxy"] for r in results), success_strict=sum(r["success_strict"] for r in results),
@@ -147,6 +147,8 @@ def job_summary(results, world=1, self_collision=False, repair=False, shortcut=F
         mine.update(rows_repaired=sum(r["rows_repaired"] for r in results), rows_repair_clear=sum(r["rows_repair_clear"] for r in results))
     if shortcut:  # (run(..., shortcut=PASSES): every rank's results carry the key)
         mine.update(rows_shortcut=sum(r["rows_shortcut"] for r in results))
+        if self_safe:  # (run(..., shortcut=PASSES, self_safe=True))
+            mine.update(shortcut_self_rejected=sum(r["shortcut_self_rejected"] for r in results))
     if world <= 1:
         return dict(mine, ranks=1)
     import torch.distributed as dist
@@ -297,11 +299,15 @@ def _score(job, on, X, starts, goals, tb):
         moved, clear = (on.scenes(a) for a in repair_tally(rep, job.repair, job.repair_margin))
         st["repair_s"] = time.time() - tb
         tb = time.time()
-    cut = None
+    cut = cut_self = None
     if job.shortcut:  # likewise one launch, after the repair and before the selection; everything behind it sees the shortened rows
-        sh = obj.shortcut_rows(X, passes=job.shortcut, substeps=CHECK_SUBSTEPS, log_cap=0, return_device=on.grouped)
+        safe = dict(self_pairs=True) if job.self_safe else {}  # (self_safe: a candidate must also keep the arm free of itself, under the guide's own pair mask)
+        sh = obj.shortcut_rows(X, passes=job.shortcut, substeps=CHECK_SUBSTEPS, log_cap=0, return_device=on.grouped, **safe)
         X = sh["trajectories"]
-        cut = on.scenes(np.asarray(sh["accepted"].cpu() if isinstance(sh["accepted"], torch.Tensor) else sh["accepted"]) > 0)
+        host = lambda v: np.asarray(v.cpu() if isinstance(v, torch.Tensor) else v)  # noqa: E731
+        cut = on.scenes(host(sh["accepted"]) > 0)
+        if job.self_safe:
+            cut_self = on.scenes(host(sh["self_rejected"]))
         st["shortcut_s"] = time.time() - tb
         tb = time.time()
     idx, vols, met = on.select(starts, goals, X, prefer=job.prefer)
@@ -334,7 +340,7 @@ def _score(job, on, X, starts, goals, tb):
     timed = _time_plans(job, on, X, idx) if job.time_plan is not None else None
     return [SimpleNamespace(idx=int(i), vols=vols[s], trajectory=X[s][int(i)], met=of(met, s), selfcol=of(selfcol, s), chosen=of(chosen, s, place[s]), goal=of(goal, s, place[s]),
                             chk={k: (v if np.ndim(v) else int(v)) for k, v in of(chk, s).items()},  # (the per-row flags, and the scene's counts as ints)
-                            repair=None if moved is None else (moved[s], clear[s]), shortcut=None if cut is None else cut[s], timed=None if timed is None else timed[s])
+                            repair=None if moved is None else (moved[s], clear[s]), shortcut=None if cut is None else cut[s], shortcut_self=None if cut_self is None else cut_self[s], timed=None if timed is None else timed[s])
             for s, i in enumerate(idx)]
 
 
@@ -359,12 +365,16 @@ def _time_plans(job, on, X, idx):
         return out
     S, B, _, N = X.shape
     rows = [s * B + int(i) for s, i in enumerate(idx)]
-    bl = obj.blend_rows(X if on.grouped else X[0], deviation=job.blend, reach=job.blend_reach, substeps=CHECK_SUBSTEPS, rows=rows)
+    safe = dict(self_pairs=True) if job.self_safe else {}  # (self_safe: a try must also keep the arm free of itself, under the guide's own pair mask)
+    bl = obj.blend_rows(X if on.grouped else X[0], deviation=job.blend, reach=job.blend_reach, substeps=CHECK_SUBSTEPS, rows=rows, **safe)
     beta, code = bl["beta"].reshape(S * B, N)[rows], bl["code"].reshape(S * B, N)[rows]
     bprof = EV.time_blended_rows_on(ctx, plans, beta)
     for o, d, c in zip(out, bprof["duration"], code):
         o.update(blended_duration_s=float(d), corner_codes={name: int(np.count_nonzero(c[1:-1] == k)) for k, name in enumerate(EV.BLEND_CODE_NAMES)},
                  blend_deviation_rad=float(job.blend), blend_reach=float(job.blend_reach))
+    if job.self_safe:
+        for o, h in zip(out, bl["self_hits"].reshape(S * B, N)[rows]):
+            o.update(blend_self_rejected_tries=int(h.sum()))
     if job.time_plan is not True:
         faster = [s for s in range(S) if bprof["duration"][s] < prof["duration"][s]]  # (a NaN duration compares false: the polyline's count, 0)
         plain = [s for s in range(S) if s not in faster]
@@ -396,6 +406,8 @@ def _result(job, meta, tm, sc, t0, plan_end, wall_end=None, scenes_in_launch=Non
         r.update(rows_repaired=int(sc.repair[0].sum()), rows_repair_clear=int(sc.repair[1].sum()), repair_iters=int(job.repair))
     if sc.shortcut is not None:  # shortcut: the scene's rows with at least one accepted span
         r.update(rows_shortcut=int(sc.shortcut.sum()), shortcut_passes=int(job.shortcut))
+        if sc.shortcut_self is not None:  # self_safe: the candidates of the scene's rows that the self test alone rejected
+            r.update(shortcut_self_rejected=int(sc.shortcut_self.sum()))
     if sc.timed is not None:  # time_plan: the chosen plan's timed motion
         r.update(sc.timed)
     if job.prefer is not None:
@@ -510,7 +522,8 @@ def _print_scene(r, n, tally, prefix=""):
     if "rows_repaired" in r:
         print(f"    repair ({r['repair_iters']} iterations at most): {r['rows_repaired']}/{r['rows']} rows moved, {r['rows_repair_clear']}/{r['rows']} ended clear")
     if "rows_shortcut" in r:
-        print(f"    shortcut ({r['shortcut_passes']} passes at most): {r['rows_shortcut']}/{r['rows']} rows shortened")
+        print(f"    shortcut ({r['shortcut_passes']} passes at most): {r['rows_shortcut']}/{r['rows']} rows shortened"
+              + (f"; {r['shortcut_self_rejected']} candidates rejected by the self-collision test alone" if "shortcut_self_rejected" in r else ""))
     if "duration_s" in r:
         census = ", ".join(f"{k} {v}" for k, v in r["binding_constraints"].items() if v)
         print(f"    chosen plan: duration_s {r['duration_s']:.3f} under the joint velocity / acceleration / corner limits; waypoints bound by: {census}"
@@ -519,7 +532,8 @@ def _print_scene(r, n, tally, prefix=""):
             census = ", ".join(f"{k} {v}" for k, v in r["corner_codes"].items() if v)
             print(f"    chosen plan: blended_duration_s {r['blended_duration_s']:.3f} with corner blends within {r['blend_deviation_rad']:g} rad of the polyline "
                   f"(reach {r['blend_reach']:g}) under the exact collision check; corners: {census}"
-                  + (f"; the samples are the {r['sampled_motion']} motion's" if "sampled_motion" in r else ""))
+                  + (f"; the samples are the {r['sampled_motion']} motion's" if "sampled_motion" in r else "")
+                  + (f"; {r['blend_self_rejected_tries']} corner tries rejected by the self-collision test alone" if "blend_self_rejected_tries" in r else ""))
     if "self_collision_free" in r:
         print(f"    self-collision free {r['self_collision_free']} ({r['rows_self_collision_free']}/{r['rows']} rows of the batch)   running {tally.self_free}/{n}")
         if "ensemble" in r:
@@ -547,12 +561,13 @@ def _print_summary(summary):
     if "rows_repaired" in summary:
         print(f"[infer_serial] repair: {summary['rows_repaired']}/{summary['rows']} rows moved, {summary['rows_repair_clear']}/{summary['rows']} ended clear")
     if "rows_shortcut" in summary:
-        print(f"[infer_serial] shortcut: {summary['rows_shortcut']}/{summary['rows']} rows shortened")
+        print(f"[infer_serial] shortcut: {summary['rows_shortcut']}/{summary['rows']} rows shortened"
+              + (f", {summary['shortcut_self_rejected']} candidates rejected by the self-collision test alone" if "shortcut_self_rejected" in summary else ""))
 
 
 def run(cfg_path, dataset=None, max_scenes=None, verbose=True, scenes_in_flight=1, shard_scenes=True, scenes_per_launch=1, ensemble_report=False, prefer=None,
         ik_seeds=0, ik_tool=None, ik_seed=0, self_collision=False, device_noise=None, repair=0, repair_margin=0.02, repair_step=0.02, shortcut=0,
-        time_plan=None, blend=None, blend_reach=0.4):
+        time_plan=None, blend=None, blend_reach=0.4, self_safe=False):
     """The reference's scene loop (infer_serial.py:95-170).  Under ``torch.distributed.run`` (one process per GPU, extension: the
     reference is one process) the scenes are dealt round-robin to the ranks - scene i of the cfg's order goes to rank i mod world -
     and nothing is exchanged until `job_summary` adds the tallies up: scenes are independent problems, this is the problem set's natural
@@ -635,9 +650,17 @@ def run(cfg_path, dataset=None, max_scenes=None, verbose=True, scenes_in_flight=
     whole batch through shortcut_rows after the repair and before the selection (IntersectionVolumeGuide.shortcut_rows; a scene group
     through SceneBatch.shortcut_rows in one launch): at most PASSES passes of joint-space shortcuts, each accepted only if the success
     check's own test passes at the configurations the check will test on it (CHECK_SUBSTEPS), so a row that is collision-free stays so.
-    Self-collision is not part of that test: ``self_collision`` tallies after the stage.  Everything behind it sees the shortened rows.
+    Self-collision is not part of that test unless ``self_safe`` is set: ``self_collision`` tallies after the stage.  Everything behind it
+    sees the shortened rows.
     Each result adds `rows_shortcut` (rows with an accepted span) and `shortcut_passes`, and `shortcut_s` to the timings; the per-scene
-    line and the summary print the count."""
+    line and the summary print the count.
+
+    ``self_safe`` (an extension; False = off: nothing new is launched, printed or returned; needs ``shortcut`` or ``blend``) passes
+    self_pairs=True to those two stages: a shortcut candidate or a corner blend must also keep every masked pair of the arm's link boxes
+    apart at the configurations it is tested at (the guide's own pair mask, the one ``self_collision`` checks under), so a row that is
+    self-collision free before the stages is self-collision free after them.  Adds `shortcut_self_rejected` (the candidates of the
+    scene's rows that the obstacle test passed and the self test rejected) with ``shortcut`` and `blend_self_rejected_tries` (the same
+    for the chosen plan's corner tries) with ``blend``."""
     t_enter = time.time()
     kl = int(scenes_per_launch)
     if kl < 1:
@@ -662,6 +685,9 @@ def run(cfg_path, dataset=None, max_scenes=None, verbose=True, scenes_in_flight=
     shortcut = int(shortcut)
     if shortcut < 0:
         raise ValueError(f"shortcut must be >= 0 passes (0 = off), got {shortcut}")
+    self_safe = bool(self_safe)
+    if self_safe and not shortcut and blend is None:
+        raise ValueError("self_safe needs shortcut or blend: it is the self-collision test of those two stages")
     if device_noise is not None:
         DeviceNoise(device_noise)  # (an integer in [0, 2^64), or it raises)
     cfg = GC.load_yaml(cfg_path)
@@ -678,7 +704,7 @@ def run(cfg_path, dataset=None, max_scenes=None, verbose=True, scenes_in_flight=
         total_batch_size=guide_cfgs["total_batch_size"], guide_numbers=guide_numbers,
         guide_rows=GC.split_rows(int(cfg["guide"]["total_rows"]), len(guide_numbers)) if cfg["guide"].get("total_rows") else guide_cfgs["batch_size_per_guide"],
         dataset=dataset, rank=rank, world=world, verbose=verbose, prefer=prefer, ensemble_report=ensemble_report, self_collision=self_collision, device_noise=device_noise,
-        repair=repair, repair_margin=repair_margin, repair_step=repair_step, shortcut=shortcut, time_plan=time_plan, blend=blend, blend_reach=blend_reach, ik_tool=ik_tool, iks=[], feeder=None, results=[], tally=SimpleNamespace(success=0, strict=0, self_free=0))
+        repair=repair, repair_margin=repair_margin, repair_step=repair_step, shortcut=shortcut, time_plan=time_plan, blend=blend, blend_reach=blend_reach, self_safe=self_safe, ik_tool=ik_tool, iks=[], feeder=None, results=[], tally=SimpleNamespace(success=0, strict=0, self_free=0))
     k = max(1, int(scenes_in_flight))
     base = get_context(device)
     job.lanes = _lanes(job, base, k, model["model_dir"], max_batch=job.total_batch_size * kl)
@@ -707,7 +733,7 @@ def run(cfg_path, dataset=None, max_scenes=None, verbose=True, scenes_in_flight=
         if job.feeder is not None:
             job.feeder.close()
     if world > 1 or verbose:
-        run.last_summary = job_summary(job.results, world, self_collision, bool(repair), bool(shortcut))
+        run.last_summary = job_summary(job.results, world, self_collision, bool(repair), bool(shortcut), self_safe)
         if verbose and rank == 0:
             _print_summary(run.last_summary)
     return job.results
@@ -749,10 +775,15 @@ def main(argv=None):
     parser.add_argument("--blend", type=float, default=None, metavar="DEVIATION", help="with --time-plan: blend the chosen plan's corners by parabolic blends that stay "
                         "within DEVIATION [rad] of the polyline per joint and pass the exact collision check, and report blended_duration_s and the census of "
                         "the corner codes next to duration_s; with a PERIOD the faster of the two motions is sampled (extension; off: nothing changes)")
+    parser.add_argument("--self-safe", action="store_true", help="with --shortcut and / or --blend: a shortcut candidate or a corner blend must also keep the arm's "
+                        "link boxes apart (the pair mask of --self-collision), so a row that is self-collision free before those stages is after them; "
+                        "reports the candidates and corner tries that this test alone rejected")
     parser.add_argument("--blend-reach", type=float, default=0.4, metavar="R", help="the largest part of a neighbouring segment that a blend may take, in (0, 0.45]")
     args = parser.parse_args(argv)
     if args.blend is not None and args.time_plan is None:
         parser.error("--blend requires --time-plan")
+    if args.self_safe and not args.shortcut and args.blend is None:
+        parser.error("--self-safe requires --shortcut or --blend")
     ik_tool = args.ik_tool
     if ik_tool is not None and ik_tool not in ("flange", "hand"):
         if ik_tool.endswith(".npy"):
@@ -766,7 +797,7 @@ def main(argv=None):
     results = run(args.cfg_path, scenes_in_flight=args.scenes_in_flight, max_scenes=args.max_scenes, scenes_per_launch=args.scenes_per_launch,
                   ensemble_report=args.ensemble_report, prefer=args.prefer, ik_seeds=args.ik_seeds, ik_tool=ik_tool, self_collision=args.self_collision,
                   device_noise=args.device_noise, repair=args.repair, repair_margin=args.repair_margin, repair_step=args.repair_step, shortcut=args.shortcut, time_plan=args.time_plan,
-                  blend=args.blend, blend_reach=args.blend_reach)
+                  blend=args.blend, blend_reach=args.blend_reach, self_safe=args.self_safe)
     if args.results_json:
         rows = [{k: v for k, v in r.items() if k != "trajectory"} for r in results]
         with open(args.results_json + ("" if rank == 0 else f".rank{rank}"), "w") as f:

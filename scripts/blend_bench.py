@@ -10,7 +10,12 @@ codes; the durations of the unblended (edmp_time_rows_dev) and of the blended mo
 
 A sample is ONE call followed by the context's synchronise (the blend and sample calls end in one themselves) inside a host perf_counter
 window; each figure is the median of `calls` samples after `warmup`.  Prints ONE JSON line and writes it to --out.  Informative: no time
-is gated, and this is never bench.py's value."""
+is gated, and this is never bench.py's value.
+
+With --self-safe-out FILE the script runs ONE other leg instead: guide.blend_rows on the same two states with self_pairs=None and
+self_pairs=True (the self-collision test of the tries, blend_rows_kernel<true>), the two taken alternately, medians of `calls` calls each
+with the context's synchronise, with the rejected counts; the record goes under "blend" into FILE (profiles/self_safe_bench.json, which
+scripts/shortcut_bench.py shares)."""
 from __future__ import annotations
 
 import argparse
@@ -114,6 +119,31 @@ def measure(rows=1024, calls=20, warmup=3, device="cuda:0", commit=None):
     }
 
 
+def measure_self_safe(rows=1024, calls=20, warmup=3):
+    """the self-safe leg: the same two states and scene (scripts/shortcut_bench.py: bench_state), guide.blend_rows with self_pairs=None and True"""
+    import torch
+
+    from shortcut_bench import alternate, bench_state  # (scripts/ is this script's directory)
+
+    guide, X0 = bench_state(rows)
+    states = {"sampler_like": X0,
+              "after_shortcut": guide.shortcut_rows(X0, passes=PASSES, substeps=K, log_cap=0, return_device=True)["trajectories"].contiguous()}
+    out = {}
+    for name, Xd in states.items():
+        med, spread, last = alternate(guide.ctx, lambda pairs: guide.blend_rows(Xd, deviation=DEVIATION, reach=REACH, substeps=SUBSTEPS, halvings=HALVINGS, return_device=True,
+                                                                                self_pairs=pairs), calls, warmup)
+        out[name] = {"call_s": med, "spread_s": spread, "on_over_off": med["on"] / med["off"],
+                     "configurations_tested": {k: int(v["tested"].sum()) for k, v in last.items()}, "blended": {k: int((v["code"] == 3).sum()) for k, v in last.items()},
+                     "self_hits": int(last["on"]["self_hits"].sum()), "codes_equal": bool(torch.equal(last["on"]["code"], last["off"]["code"]))}
+    return {
+        "rows": rows, "N": N, "obstacles": 16, "blend": f"deviation {DEVIATION} rad, reach {REACH}, substeps {SUBSTEPS}, halvings {HALVINGS} (illustrative defaults)",
+        "calls": calls, "warmup": warmup, "pair_mask": "franka.self_collision_pairs(): 18 pairs, 6 lower links",
+        "clock": "median of `calls` guide.blend_rows(return_device=True) calls per leg, taken alternately, each with the context's synchronise inside a host perf_counter window",
+        "states": out,
+        "box": {"gpu": torch.cuda.get_device_name(0), "cpu": platform.processor() or platform.machine(), "torch": torch.__version__, "hip": torch.version.hip},
+    }
+
+
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--rows", type=int, default=1024)
@@ -121,7 +151,15 @@ def main():
     ap.add_argument("--warmup", type=int, default=3)
     ap.add_argument("--out", type=str, default=os.path.join(ROOT, "profiles", "blend_bench.json"))
     ap.add_argument("--commit", type=str, default=None, help="commit the working tree is based on (default: git rev-parse, where the tree is a checkout)")
+    ap.add_argument("--self-safe-out", type=str, default=None, help="run the self-safe leg alone and put its record under \"blend\" into this JSON file")
     a = ap.parse_args()
+    if a.self_safe_out:
+        from shortcut_bench import merge_into  # (scripts/ is this script's directory)
+
+        out = measure_self_safe(a.rows, calls=a.calls, warmup=a.warmup)
+        print(json.dumps(out))
+        merge_into(a.self_safe_out, "blend", out)
+        return
     out = measure(a.rows, calls=a.calls, warmup=a.warmup, commit=a.commit)
     print(json.dumps(out))
     if a.out:
