@@ -124,6 +124,8 @@ SIGNATURES = {
     "edmp_scenes_shortcut_rows_dev": (_i, [_vp, _vp, _i, _i, _i, _pi32, _i, _i, _i, _d, _pd, _vp, _vp, _vp, _vp, _i]),
     "edmp_shortcut_rows_self_dev": (_i, [_vp, _vp, _i, _i, _pi32, _i, _i, _i, _d, _pd, _vp, _vp, _vp, _vp, _i, _pi32, _vp]),
     "edmp_scenes_shortcut_rows_self_dev": (_i, [_vp, _vp, _i, _i, _i, _pi32, _i, _i, _i, _d, _pd, _vp, _vp, _vp, _vp, _i, _pi32, _vp]),
+    "edmp_certify_rows_dev": (_i, [_vp, _vp, _i, _i, _pi32, _i, _i, _d, _pd, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _pd]),
+    "edmp_scenes_certify_rows_dev": (_i, [_vp, _vp, _i, _i, _i, _pi32, _i, _i, _d, _pd, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _pd]),
     "edmp_time_rows_dev": (_i, [_vp, _vp, _i, _i, _pd, _pd, _pd, _vp, _vp, _vp, _vp, _vp, _vp]),
     "edmp_sample_rows_dev": (_i, [_vp, _vp, _i, _i, _vp, _vp, _vp, _vp, _vp, _pi32, _i, _d, _i, _vp, _vp, _vp]),
     "edmp_blend_rows_dev": (_i, [_vp, _vp, _i, _i, _pi32, _i, _pd, _pd, _pd, _pd, _d, _i, _i, _pd, _vp, _vp, _vp, _vp]),

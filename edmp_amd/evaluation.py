@@ -376,6 +376,7 @@ def sample_rows(trajectories, profile, period, rows=None, max_samples=None, devi
     return sample_rows_on(get_context(device), trajectories, profile, period, rows, max_samples, return_device)
 
 
+CERTIFY_VERDICT_NAMES = ("free", "hit", "undecided", "invalid")  # the codes of certify_rows' `verdict`; -1 = a row outside `rows`
 BLEND_CODE_NAMES = ("none", "not_needed", "no_gain", "blended", "blocked")  # the codes of blend_rows' `code`; -1 = a row left alone
 
 

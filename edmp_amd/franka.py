@@ -224,6 +224,33 @@ def link_half_extents(link_mesh_extents=None) -> np.ndarray:
     return ext.astype(np.float32) / np.float32(2)
 
 
+def motion_radii(link_mesh_extents=None, dh=None) -> np.ndarray:
+    """(9, 7) float64 motion radii of the continuous certificate (csrc/clearance.h: motion_radii; guide.certify_rows returns the table the
+    library used as ``radii``): turning joint j alone by dq moves every point of link box l by at most |dq| rho[l][j].  For link l riding
+    joint frame k = LINK_FRAME[l] and j <= k, rho[l][j] = sum_{i=j+1..k} sqrt(a_i^2 + d_i^2) + max over the 8 corners c = +-he_l of
+    |p_l + S_l c|, (S_l | p_l) the link's static frame; 0 for j > k.  The tables are the ones a guide hands the library: the float32
+    static frames and half extents widened, ``dh`` (7, 4) [a, d, cos(alpha), sin(alpha)], default dh_table_f64()."""
+    he = link_half_extents(link_mesh_extents).astype(np.float64)
+    sf = static_frames().astype(np.float64)
+    tab = dh_table_f64() if dh is None else np.asarray(dh, dtype=np.float64)
+    if tab.shape != (N_JOINTS, 4):
+        raise ValueError(f"dh must be (7, 4), got {tab.shape}")
+    rho = np.zeros((N_LINKS, N_JOINTS), dtype=np.float64)
+    for l in range(N_LINKS):
+        k = int(LINK_FRAME[l])
+        far = 0.0
+        for c in range(8):
+            corner = [he[l, a] if (c >> a) & 1 else -he[l, a] for a in range(3)]
+            v = [sf[l, a, 3] + (sf[l, a, 0] * corner[0] + sf[l, a, 1] * corner[1] + sf[l, a, 2] * corner[2]) for a in range(3)]
+            far = max(far, math.sqrt(v[0] * v[0] + v[1] * v[1] + v[2] * v[2]))
+        for j in range(k + 1):
+            s = 0.0
+            for i in range(j + 1, k + 1):
+                s = s + math.sqrt(tab[i, 0] * tab[i, 0] + tab[i, 1] * tab[i, 1])
+            rho[l, j] = s + far
+    return rho
+
+
 def spheres_from_boxes(link_half_extents=None, max_per_link: int = 8) -> np.ndarray:
     """Default sphere model of the SDF guide (csrc/sdf.hip): (n, 5) float32 rows [link 0..8, centre xyz in the link-box frame, radius]
     covering the nine link boxes.  Along each box's longest axis (the first one on equal extents) sit

@@ -454,6 +454,37 @@ class _SlotObject:
             out.update(self_rejected=c[2].reshape(shape).copy(), self_pairs=mask.reshape(9, 9).copy())
         return out
 
+    @staticmethod
+    def _host_state(trajectories):
+        """the state of certify_rows, a HOST-ONLY call: an ndarray, nested lists or a CPU tensor -> the contiguous f64 host array.  A device
+        tensor is refused (numpy will not read one): the call has no part in the stream order between a caller's stream and the context's."""
+        try:
+            return np.ascontiguousarray(trajectories, dtype=np.float64)
+        except TypeError as e:
+            raise TypeError("certify_rows takes host arrays (an ndarray or a CPU tensor) and returns host arrays; for a device-resident state "
+                            "call edmp_certify_rows_dev / edmp_scenes_certify_rows_dev, or copy it to the host first") from e
+
+    def _certify(self, Xd, shape, N, depth, margin, rows):
+        """the continuous certificate of the (rows, 7, N) device state Xd -> the certify dict of host arrays, per-row arrays `shape`d.  Rows
+        outside `rows` are not written by the library: they keep verdict -1, segment -1, fraction -1, link -1, evaluations 0, undecided 0,
+        bound NaN."""
+        ctx, n = self.ctx, int(np.prod(shape))
+        with torch.cuda.stream(ctx.stream):
+            ints = torch.zeros((5, n), dtype=torch.int32, device=ctx.device)  # verdict, segment, link, evaluations, undecided
+            ints[:3] = -1
+            reals = torch.full((2, n), float("nan"), dtype=torch.float64, device=ctx.device)  # fraction, bound
+            reals[0] = -1.0
+        listed = None if rows is None else np.ascontiguousarray(np.asarray(rows, dtype=np.int32).reshape(-1))
+        dh = np.ascontiguousarray(franka.dh_table_f64())
+        radii = np.zeros(63, dtype=np.float64)
+        self._call("edmp_certify_rows_dev", "edmp_scenes_certify_rows_dev", shape, ptr(Xd), *shape, N, None if listed is None else _capi.as_pi32(listed),
+                   0 if listed is None else int(listed.shape[0]), int(depth), float(margin), _capi.as_pd(dh), C.c_void_p(ints[0].data_ptr()),
+                   C.c_void_p(ints[1].data_ptr()), C.c_void_p(reals[0].data_ptr()), C.c_void_p(ints[2].data_ptr()), C.c_void_p(ints[3].data_ptr()),
+                   C.c_void_p(ints[4].data_ptr()), C.c_void_p(reals[1].data_ptr()), _capi.as_pd(radii))
+        keys_i, keys_r = ("verdict", "segment", "link", "evaluations", "undecided"), ("fraction", "bound")
+        extra = dict(radii=radii.reshape(9, 7), depth=int(depth), margin=float(margin))
+        hi, hr = ctx.to_host(ints), ctx.to_host(reals)
+        return dict({k: hi[i].reshape(shape).copy() for i, k in enumerate(keys_i)}, **{k: hr[i].reshape(shape).copy() for i, k in enumerate(keys_r)}, **extra)
 
     def _blend(self, Xd, shape, N, deviation, reach, substeps, halvings, vmax, amax, jump, scale, rows, return_device, self_pairs=None):
         """the corner blends of the (rows, 7, N) device state Xd under the exact collision check -> the blend dict, per-row arrays `shape`d.
@@ -812,6 +843,28 @@ class IntersectionVolumeGuide(_SlotObject):
             raise ValueError(f"trajectories must be (n, 7, N), got {tuple(X.shape)}")
         self._bind()
         return self._shortcut(trajectories, X, (X.shape[0],), X.shape[2], passes, substeps, min_gain, rows, log_cap, return_device, self_pairs)
+
+    def certify_rows(self, trajectories, depth=6, margin=0.0, rows=None):
+        """Continuous collision certificate of finished rows (edmp_certify_rows_dev, csrc/certify.hip; one launch, one workgroup per row):
+        trajectories (n, 7, N) f64, 2 <= N <= 64.  A HOST-ONLY call: trajectories is an ndarray or a CPU tensor (a device tensor is refused
+        with a TypeError) and every result is a host array - the C entry point is the interface for a device-resident state.  success_rows tests a list of configurations; this check
+        answers for EVERY configuration of the joint-space polyline.  Per (segment, link) an interval of the segment is certified where a
+        lower bound g on the distance between the link box and the obstacles at its centre (csrc/clearance.h) exceeds what the box can move
+        inside the interval (the motion radii, franka.motion_radii) by more than ``margin`` [m]; otherwise the exact test decides whether
+        the centre is a hit, else the interval is halved, down to ``depth`` (0..10) halvings.  Returns dict(verdict (n,) int32: 0 free - a
+        proof that no link box touches an obstacle anywhere on the polyline -, 1 hit - an exact collision at the reported configuration -,
+        2 undecided at the depth limit, 3 invalid (a non-finite element; nothing evaluated), names in evaluation.CERTIFY_VERDICT_NAMES;
+        segment, fraction (dyadic, exact), link: the lexicographically smallest (segment, fraction, link) among the hits (verdict 1) or
+        the first undecided intervals (verdict 2), else -1, -1.0, -1; evaluations, undecided (n,) int32 sums over the row's (N - 1) x 9
+        items; bound (n,) f64 the minimum of g - reach over the certified intervals, +inf without one: on a verdict-0 row every link box
+        keeps more than bound > margin from every obstacle; radii (9, 7) the table used; depth, margin).  Joint limits are not part of it
+        (``within`` stays success_rows'), nor is self-collision.  ``rows``: the row indices to work on (any order, no duplicates); the
+        others report verdict -1 and NaN bound.  Read only; leaves a segmented run running."""
+        host = self._host_state(trajectories)
+        if host.ndim != 3 or host.shape[1] != 7:
+            raise ValueError(f"trajectories must be (n, 7, N), got {tuple(host.shape)}")
+        self._bind()
+        return self._certify(self.ctx.to_dev(host, torch.float64), (host.shape[0],), host.shape[2], depth, margin, rows)
 
     def row_swept_volumes(self, start, goal, trajectories):
         """(B,) f32 t=0 swept volume per row and the argmin (first on ties)."""
@@ -1276,6 +1329,17 @@ class SceneBatch(_SlotObject):
         Xd, N = self._state(trajectories)
         self._bind()
         out = self._shortcut(trajectories, Xd, (self.n_scenes, self.batch_size), N, passes, substeps, min_gain, rows, log_cap, return_device, self_pairs)
+        Xd.record_stream(self.ctx.stream)
+        return out
+
+    def certify_rows(self, trajectories, depth=6, margin=0.0, rows=None):
+        """IntersectionVolumeGuide.certify_rows for every scene in one launch (edmp_scenes_certify_rows_dev): the (S, B, 7, N) /
+        (S*B, 7, N) state as a HOST array (a device tensor is refused, as there), each row against its own scene's obstacles and kinds
+        -> the same dict of host arrays with (S, B) per-row arrays; scene s's values are what guides[s].certify_rows gives for X[s].
+        ``rows`` indexes the S*B rows scene after scene.  Read only; leaves a segmented run running."""
+        Xd, N = self._state(self._host_state(trajectories))
+        self._bind()
+        out = self._certify(Xd, (self.n_scenes, self.batch_size), N, depth, margin, rows)
         Xd.record_stream(self.ctx.stream)
         return out
 

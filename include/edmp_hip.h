@@ -349,6 +349,49 @@ int edmp_scenes_shortcut_rows_self_dev(edmp_ctx* ctx, double* X_dev, int S, int 
                                        double* length_dev, int32_t* spans_dev, int log_cap, const int32_t* pair_mask,
                                        int32_t* self_rejected_dev);
 
+/* ---- continuous collision certificate of finished rows (csrc/certify.hip, csrc/clearance.h) ------------------------------------ */
+/* A check whose answer holds for EVERY configuration of the joint-space polyline of a row, not for a list of them: the success check and
+ * the stages built on it test the waypoints and substeps - 1 interpolants per segment, and an obstacle thinner than their spacing can be
+ * passed through unseen.  One 256-thread workgroup per listed row (certify_rows_kernel), X_dev (n, 7, N) f64, 2 <= N <= 64, read only.
+ * All arithmetic in f64.  Off by default everywhere: no other entry point calls it.
+ *   motion radii rho[l][j] (9 x 7, computed on the host from the tables the kernel is handed; radii_out, host, 63 doubles, receives them if
+ *     not NULL): for link l riding joint frame k (link l for l < 7, else 6) and j <= k,
+ *       rho[l][j] = sum_{i=j+1..k} sqrt(a_i^2 + d_i^2) + max over the 8 corners c = +-he_l of |p_l + S_l c|,   0 for j > k,
+ *     (S_l | p_l) the link's static frame: turning joint j by dq moves every point of box l by at most |dq| rho[l][j].
+ *   gap(box, obstacle): a lower bound on the Euclidean distance, positive only if the shapes are disjoint - the maximum over unit axes of
+ *     the separation of the projections.  Box / box, in the 15-axis test's own R, A = |R| + 1e-12, t: the six face axes and the nine edge
+ *     axes, each divided by its norm sqrt(1 - R[i][j]^2) and skipped where 1 - R[i][j]^2 < 1e-6.  Box / cylinder: the cylinder axis, the
+ *     three box normals n against the cylinder's extent H |n.z| + r sqrt(1 - (n.z)^2), and the radial direction from the cylinder's axis
+ *     line to the box centre (skipped where that distance is < 1e-9).
+ *   item (segment w, link l), a = x_w, b = x_{w+1}: L = sum_j |b_j - a_j| rho[l][j].  An in-order walk of the binary tree over the segment
+ *     with integer position pos in [0, 2^D) and a level: the interval [pos, pos + size), size = 2^(D - level), has the centre
+ *     u = (2 pos + size) / 2^(D+1); the configuration there is the success check's interpolant fma(1 - u, a_j, u b_j); g = the minimum
+ *     of gap over the row's scene's obstacles for the box of link l at it; reach = L size / 2^(D+1).  Then
+ *       1. g - reach > margin + 1e-9: the interval is certified; min(g - reach) is kept; pos += size, level = D - ctz(pos);
+ *       2. else, if the exact test (15-axis / clipped-polytope, touching counts) finds the box overlapping an obstacle here: the item ends
+ *          with a hit at this u;
+ *       3. else, if level == D or reach == 0: one undecided interval is counted (the first is remembered); advance as in 1;
+ *       4. else level += 1.
+ *     The walk takes at most 2^(D+1) - 1 evaluations.
+ * Outputs, (n,) each, written for the listed rows only: verdict_dev int32 = 1 (hit) if any item hit, else 2 (undecided) if any item counted
+ * an undecided interval, else 0 (free: no link box touches an obstacle anywhere on the polyline, and keeps more than bound > margin from
+ * every obstacle); 3 (invalid) for a row with a non-finite element, for which nothing is evaluated.  segment_dev int32, fraction_dev f64
+ * (= u, dyadic, exact), link_dev int32: the lexicographically smallest (segment, u, link) among the items' hits (verdict 1) or among the
+ * items' first undecided intervals (verdict 2); -1, -1.0, -1 otherwise.  evaluations_dev, undecided_dev int32: sums over the items.
+ * bound_dev f64: the minimum of g - reach over all accepted intervals, +inf if there is none.  Joint limits are not part of the
+ * certificate.  No output depends on the order in which the items finish (integer minima and sums, an f64 minimum).
+ * depth D in 0..10, margin finite and >= 0 [m].  rows_host: n_rows row indices (host, any order, no duplicates), or NULL = every row
+ * (n_rows is ignored).  dh_f64 as in edmp_success_rows_dev.  edmp_certify_rows_dev needs a single-scene guide, any n >= 1;
+ * edmp_scenes_certify_rows_dev a bound scene batch, X (S*B, 7, N), each row against its own scene's obstacles and kinds.  Refusals (N,
+ * depth, margin, rows, null pointers) come before any device call and name the argument.  The calls replace nothing of the guide or the
+ * sampler and do NOT end a segmented run.  They run on the context's stream and synchronise it. */
+int edmp_certify_rows_dev(edmp_ctx* ctx, const double* X_dev, int n, int N, const int32_t* rows_host, int n_rows, int depth, double margin,
+                          const double* dh_f64, int32_t* verdict_dev, int32_t* segment_dev, double* fraction_dev, int32_t* link_dev,
+                          int32_t* evaluations_dev, int32_t* undecided_dev, double* bound_dev, double* radii_out);
+int edmp_scenes_certify_rows_dev(edmp_ctx* ctx, const double* X_dev, int S, int B, int N, const int32_t* rows_host, int n_rows, int depth,
+                                 double margin, const double* dh_f64, int32_t* verdict_dev, int32_t* segment_dev, double* fraction_dev,
+                                 int32_t* link_dev, int32_t* evaluations_dev, int32_t* undecided_dev, double* bound_dev, double* radii_out);
+
 /* ---- time parameterisation of finished rows (csrc/timing.hip) ---------------------------------------------------- */
 /* The stage after shortcutting, which the reference does not ship (it replays plans at constant velocity): the fastest rest-to-rest
  * motion ALONG the polyline of every row under joint velocity, joint acceleration and corner velocity-jump limits, and its samples at a

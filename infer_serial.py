@@ -135,6 +135,22 @@ def repair_tally(rep, iters, margin):
     return it > 0, (it >= 0) & ((it < int(iters)) | (clr >= float(np.float32(margin))))
 
 
+CERTIFY_KEYS = ("verdict", "segment", "fraction", "link", "bound")  # what the driver reads of certify_rows' dict
+
+
+def certify_tally(cert, collision_free, idx, depth, margin):
+    """what one scene's result says of the continuous certificate: the census of the rows' verdicts, the rows that the sampled success check
+    passes and the certificate reports as hit, and the chosen plan's verdict with its bound (free) or its hit / first undecided interval"""
+    v = np.asarray(cert["verdict"])
+    out = dict(certify_depth=int(depth), certify_margin=float(margin), certify_rows={name: int(np.count_nonzero(v == k)) for k, name in enumerate(EV.CERTIFY_VERDICT_NAMES)},
+               rows_passed_but_certified_hit=int(np.count_nonzero((v == 1) & np.asarray(collision_free, dtype=bool))), certify_verdict=EV.CERTIFY_VERDICT_NAMES[int(v[idx])])
+    if v[idx] == 0:
+        out.update(certify_bound=float(cert["bound"][idx]))
+    elif v[idx] in (1, 2):
+        out.update(certify_at=dict(segment=int(cert["segment"][idx]), fraction=float(cert["fraction"][idx]), link=franka.LINK_NAMES[int(cert["link"][idx])]))
+    return out
+
+
 def job_summary(results, world=1, self_collision=False, repair=False, shortcut=False, self_safe=False):
     """This rank's tallies; under a launcher the sum over all ranks (all_gather_object of five small integers per rank - the
     trajectories stay where they were planned).  Keys: scenes, success_proxy (the reference's tally), success_strict, rows_collision_free, rows."""
@@ -281,8 +297,8 @@ class _Path:
         return self.obj.ctx.to_host(X) if self.grouped else X[None]
 
     def timings(self):
-        order = (("noise_wait_s", "batch_metrics_s", "denoise_s", "repair_s", "shortcut_s", "denoise_s_is", "best_trajectory_s", "success_check_s") if self.grouped else
-                 ("noise_wait_s", "denoise_s", "repair_s", "shortcut_s", "best_trajectory_s", "batch_metrics_s", "success_check_s"))
+        order = (("noise_wait_s", "batch_metrics_s", "denoise_s", "repair_s", "shortcut_s", "certify_s", "denoise_s_is", "best_trajectory_s", "success_check_s") if self.grouped else
+                 ("noise_wait_s", "denoise_s", "repair_s", "shortcut_s", "certify_s", "best_trajectory_s", "batch_metrics_s", "success_check_s"))
         return {k: self.stamps[k] for k in order if k in self.stamps}
 
 
@@ -310,6 +326,13 @@ def _score(job, on, X, starts, goals, tb):
             cut_self = on.scenes(host(sh["self_rejected"]))
         st["shortcut_s"] = time.time() - tb
         tb = time.time()
+    cert = Xh = None
+    if job.certify is not None:  # likewise one launch, on the rows the selection sees: the continuous certificate of every row (a report; nothing behind it reads it)
+        Xh = on.host(X)  # (certify_rows is a host-only call: a group's state comes back here, once, and serves the result dicts below)
+        out = obj.certify_rows(Xh if on.grouped else X, depth=job.certify, margin=job.certify_margin)
+        cert = {k: on.scenes(out[k]) for k in CERTIFY_KEYS}
+        st["certify_s"] = time.time() - tb
+        tb = time.time()
     idx, vols, met = on.select(starts, goals, X, prefer=job.prefer)
     on.picked_at = tc = time.time()
     st["best_trajectory_s"] = tc - tb
@@ -336,11 +359,12 @@ def _score(job, on, X, starts, goals, tb):
     selfcol = obj.self_collision_rows(X) if job.self_collision else None
     lead = lambda d: None if d is None else {k: on.scenes(v) for k, v in d.items()}  # noqa: E731
     of = lambda d, *at: None if d is None else {k: v[at] for k, v in d.items()}  # noqa: E731
-    idx, vols, X, chk, met, selfcol, goal, chosen = on.scenes(idx), on.scenes(vols), on.host(X), lead(chk), lead(met), lead(selfcol), lead(goal), lead(chosen)
+    idx, vols, X, chk, met, selfcol, goal, chosen = on.scenes(idx), on.scenes(vols), (on.host(X) if Xh is None else Xh), lead(chk), lead(met), lead(selfcol), lead(goal), lead(chosen)
     timed = _time_plans(job, on, X, idx) if job.time_plan is not None else None
     return [SimpleNamespace(idx=int(i), vols=vols[s], trajectory=X[s][int(i)], met=of(met, s), selfcol=of(selfcol, s), chosen=of(chosen, s, place[s]), goal=of(goal, s, place[s]),
                             chk={k: (v if np.ndim(v) else int(v)) for k, v in of(chk, s).items()},  # (the per-row flags, and the scene's counts as ints)
-                            repair=None if moved is None else (moved[s], clear[s]), shortcut=None if cut is None else cut[s], shortcut_self=None if cut_self is None else cut_self[s], timed=None if timed is None else timed[s])
+                            repair=None if moved is None else (moved[s], clear[s]), shortcut=None if cut is None else cut[s], shortcut_self=None if cut_self is None else cut_self[s], timed=None if timed is None else timed[s],
+                            certify=of(cert, s))
             for s, i in enumerate(idx)]
 
 
@@ -410,6 +434,8 @@ def _result(job, meta, tm, sc, t0, plan_end, wall_end=None, scenes_in_launch=Non
             r.update(shortcut_self_rejected=int(sc.shortcut_self.sum()))
     if sc.timed is not None:  # time_plan: the chosen plan's timed motion
         r.update(sc.timed)
+    if sc.certify is not None:  # certify: certify_rows' per-row arrays of the scene's rows
+        r.update(certify_tally(sc.certify, chk["collision_free"], idx, job.certify, job.certify_margin))
     if job.prefer is not None:
         r["prefer"] = job.prefer
     if job.ensemble_report:
@@ -524,6 +550,13 @@ def _print_scene(r, n, tally, prefix=""):
     if "rows_shortcut" in r:
         print(f"    shortcut ({r['shortcut_passes']} passes at most): {r['rows_shortcut']}/{r['rows']} rows shortened"
               + (f"; {r['shortcut_self_rejected']} candidates rejected by the self-collision test alone" if "shortcut_self_rejected" in r else ""))
+    if "certify_rows" in r:
+        c = r["certify_rows"]
+        at = r.get("certify_at")
+        print(f"    certificate (depth {r['certify_depth']}, margin {r['certify_margin']:g} m): rows free {c['free']}, hit {c['hit']}, undecided {c['undecided']}, invalid "
+              f"{c['invalid']}; {r['rows_passed_but_certified_hit']} rows pass the sampled check and are certified hit; chosen plan: {r['certify_verdict']}"
+              + (f", every link box farther than {r['certify_bound']:.4g} m from every obstacle" if "certify_bound" in r else "")
+              + (f" at segment {at['segment']}, fraction {at['fraction']:g}, {at['link']}" if at else ""))
     if "duration_s" in r:
         census = ", ".join(f"{k} {v}" for k, v in r["binding_constraints"].items() if v)
         print(f"    chosen plan: duration_s {r['duration_s']:.3f} under the joint velocity / acceleration / corner limits; waypoints bound by: {census}"
@@ -567,7 +600,7 @@ def _print_summary(summary):
 
 def run(cfg_path, dataset=None, max_scenes=None, verbose=True, scenes_in_flight=1, shard_scenes=True, scenes_per_launch=1, ensemble_report=False, prefer=None,
         ik_seeds=0, ik_tool=None, ik_seed=0, self_collision=False, device_noise=None, repair=0, repair_margin=0.02, repair_step=0.02, shortcut=0,
-        time_plan=None, blend=None, blend_reach=0.4, self_safe=False):
+        time_plan=None, blend=None, blend_reach=0.4, self_safe=False, certify=None, certify_margin=0.0):
     """The reference's scene loop (infer_serial.py:95-170).  Under ``torch.distributed.run`` (one process per GPU, extension: the
     reference is one process) the scenes are dealt round-robin to the ranks - scene i of the cfg's order goes to rank i mod world -
     and nothing is exchanged until `job_summary` adds the tallies up: scenes are independent problems, this is the problem set's natural
@@ -660,7 +693,15 @@ def run(cfg_path, dataset=None, max_scenes=None, verbose=True, scenes_in_flight=
     apart at the configurations it is tested at (the guide's own pair mask, the one ``self_collision`` checks under), so a row that is
     self-collision free before the stages is self-collision free after them.  Adds `shortcut_self_rejected` (the candidates of the
     scene's rows that the obstacle test passed and the self test rejected) with ``shortcut`` and `blend_self_rejected_tries` (the same
-    for the chosen plan's corner tries) with ``blend``."""
+    for the chosen plan's corner tries) with ``blend``.
+
+    ``certify`` = DEPTH in 0..10 (an extension; None = off: nothing is launched, printed or returned) sends the whole batch through
+    certify_rows after the repair and the shortcuts and before the selection (a scene group through SceneBatch.certify_rows in one launch):
+    the continuous collision certificate of every row over its whole joint-space polyline, with ``certify_margin`` [m] of clearance asked.
+    It is a report - the selection and the success check do not read it.  Each result adds `certify_rows` (the census of free / hit /
+    undecided / invalid rows), `rows_passed_but_certified_hit` (rows that success_rows passes and the certificate reports as hit),
+    `certify_verdict` of the chosen plan with its `certify_bound` (free) or `certify_at` (segment, fraction, link of the hit or of the first
+    undecided interval), `certify_depth`, `certify_margin`, and `certify_s` to the timings."""
     t_enter = time.time()
     kl = int(scenes_per_launch)
     if kl < 1:
@@ -682,6 +723,12 @@ def run(cfg_path, dataset=None, max_scenes=None, verbose=True, scenes_in_flight=
             raise ValueError(f"blend must be None (off) or a deviation > 0 [rad], got {blend}")
         if not 0 < blend_reach <= 0.45:
             raise ValueError(f"blend_reach must lie in (0, 0.45], got {blend_reach}")
+    if certify is not None:
+        certify, certify_margin = int(certify), float(certify_margin)
+        if not 0 <= certify <= 10:
+            raise ValueError(f"certify must be None (off) or a depth in 0..10, got {certify}")
+        if not (np.isfinite(certify_margin) and certify_margin >= 0):
+            raise ValueError(f"certify_margin must be finite and >= 0 [m], got {certify_margin}")
     shortcut = int(shortcut)
     if shortcut < 0:
         raise ValueError(f"shortcut must be >= 0 passes (0 = off), got {shortcut}")
@@ -704,7 +751,7 @@ def run(cfg_path, dataset=None, max_scenes=None, verbose=True, scenes_in_flight=
         total_batch_size=guide_cfgs["total_batch_size"], guide_numbers=guide_numbers,
         guide_rows=GC.split_rows(int(cfg["guide"]["total_rows"]), len(guide_numbers)) if cfg["guide"].get("total_rows") else guide_cfgs["batch_size_per_guide"],
         dataset=dataset, rank=rank, world=world, verbose=verbose, prefer=prefer, ensemble_report=ensemble_report, self_collision=self_collision, device_noise=device_noise,
-        repair=repair, repair_margin=repair_margin, repair_step=repair_step, shortcut=shortcut, time_plan=time_plan, blend=blend, blend_reach=blend_reach, self_safe=self_safe, ik_tool=ik_tool, iks=[], feeder=None, results=[], tally=SimpleNamespace(success=0, strict=0, self_free=0))
+        repair=repair, repair_margin=repair_margin, repair_step=repair_step, shortcut=shortcut, certify=certify, certify_margin=certify_margin, time_plan=time_plan, blend=blend, blend_reach=blend_reach, self_safe=self_safe, ik_tool=ik_tool, iks=[], feeder=None, results=[], tally=SimpleNamespace(success=0, strict=0, self_free=0))
     k = max(1, int(scenes_in_flight))
     base = get_context(device)
     job.lanes = _lanes(job, base, k, model["model_dir"], max_batch=job.total_batch_size * kl)
@@ -778,6 +825,11 @@ def main(argv=None):
     parser.add_argument("--self-safe", action="store_true", help="with --shortcut and / or --blend: a shortcut candidate or a corner blend must also keep the arm's "
                         "link boxes apart (the pair mask of --self-collision), so a row that is self-collision free before those stages is after them; "
                         "reports the candidates and corner tries that this test alone rejected")
+    parser.add_argument("--certify", type=int, nargs="?", const=6, default=None, metavar="DEPTH", help="after the repair and the shortcuts and before the selection, certify every "
+                        "row of each batch collision-free over its WHOLE joint-space polyline (conservative advancement, at most DEPTH halvings per segment, "
+                        "default 6): per scene the census of free / hit / undecided / invalid rows, the rows that the sampled success check passes and the "
+                        "certificate reports as hit, and the chosen plan's verdict (extension; off: nothing is launched or printed)")
+    parser.add_argument("--certify-margin", type=float, default=0.0, metavar="M", help="the clearance [m] that a certified row keeps from every obstacle")
     parser.add_argument("--blend-reach", type=float, default=0.4, metavar="R", help="the largest part of a neighbouring segment that a blend may take, in (0, 0.45]")
     args = parser.parse_args(argv)
     if args.blend is not None and args.time_plan is None:
@@ -797,7 +849,7 @@ def main(argv=None):
     results = run(args.cfg_path, scenes_in_flight=args.scenes_in_flight, max_scenes=args.max_scenes, scenes_per_launch=args.scenes_per_launch,
                   ensemble_report=args.ensemble_report, prefer=args.prefer, ik_seeds=args.ik_seeds, ik_tool=ik_tool, self_collision=args.self_collision,
                   device_noise=args.device_noise, repair=args.repair, repair_margin=args.repair_margin, repair_step=args.repair_step, shortcut=args.shortcut, time_plan=args.time_plan,
-                  blend=args.blend, blend_reach=args.blend_reach, self_safe=args.self_safe)
+                  certify=args.certify, certify_margin=args.certify_margin, blend=args.blend, blend_reach=args.blend_reach, self_safe=args.self_safe)
     if args.results_json:
         rows = [{k: v for k, v in r.items() if k != "trajectory"} for r in results]
         with open(args.results_json + ("" if rank == 0 else f".rank{rank}"), "w") as f:
